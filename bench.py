@@ -844,6 +844,52 @@ def spawn_check():
     return 0
 
 
+DUMP_SEED = 0x5EED            # --dump-outputs: the fixed choice of frames whose records are written in full
+DUMP_FRAMES = 16
+DUMP_RECORDS_PER_FRAME = 4096  # 16 frames x 4096 records x 624 B = 41 MB at most, under the 64 MB the dump may take
+DUMP_POINT_FIELDS = ("xpos", "ypos", "scale", "sharpness", "edgeness", "orientation", "score", "ambiguity", "match",
+                     "match_xpos", "match_ypos", "match_error", "subsampling")
+
+
+def dump_outputs(out_dir, counts, offsets, records):
+    """Write what the timed path (misift_extract_batch_packed_async) returned for one batch: the per-frame keypoint counts
+    and the packed SiftPoint records (`records`: capi.POINT_DTYPE; frame f's are records[offsets[f]:offsets[f + 1]]).
+      counts.npy       float64 [B]        keypoints of every frame of the batch
+      points.npy       float64 [n, 13]    the SiftPoint fields of DUMP_POINT_FIELDS, one row per record
+      descriptors.npy  float32 [n, 128]   the descriptors of the same records
+      point_frame.npy  float64 [n]        the frame (index in the batch) of every row
+    Records are written for a fixed, seeded sample of DUMP_FRAMES frames (all of them when the batch is smaller), at most
+    DUMP_RECORDS_PER_FRAME per frame.  The library appends a frame's records in atomic order (options.deterministic = 0),
+    so every frame's records are sorted by their fields first (position before anything else): the rows of two runs on
+    the same inputs then line up.  Returns the paths written."""
+    import numpy as np
+    counts = np.asarray(counts)
+    nframes = len(counts)
+    frames = np.sort(np.random.default_rng(DUMP_SEED).choice(nframes, size=min(nframes, DUMP_FRAMES), replace=False))
+    first = [DUMP_POINT_FIELDS.index(k) for k in ("subsampling", "ypos", "xpos", "scale", "orientation")]
+    points, descriptors, point_frame = [], [], []
+    for f in frames:
+        r = records[int(offsets[f]):int(offsets[f + 1])]
+        head = np.stack([r[k].astype(np.float64) for k in DUMP_POINT_FIELDS], axis=1)
+        desc = r["data"].astype(np.float32)
+        keys = np.concatenate([head[:, first], head, desc], axis=1)       # leftmost column = primary key
+        order = np.lexsort(keys.T[::-1])[:DUMP_RECORDS_PER_FRAME]
+        points.append(head[order])
+        descriptors.append(desc[order])
+        point_frame.append(np.full(len(order), float(f)))
+    arrays = {"counts": counts.astype(np.float64),
+              "points": np.concatenate(points) if points else np.zeros((0, len(DUMP_POINT_FIELDS))),
+              "descriptors": np.concatenate(descriptors) if descriptors else np.zeros((0, 128), np.float32),
+              "point_frame": np.concatenate(point_frame) if point_frame else np.zeros(0)}
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    os.makedirs(out_dir, exist_ok=True)
+    paths = []
+    for name, a in arrays.items():
+        paths.append(os.path.join(out_dir, name + ".npy"))
+        np.save(paths[-1], a)
+    return paths
+
+
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -881,6 +927,9 @@ def parse_args():
                     help="N > 1: root of the SiftData gather — 'rotate': step %% N (every rank's xGMI ingress takes its turn: "
                          "one fixed root needs 7 x 77 MB per 1.17 ms step = 460 GB/s into ONE GPU, DESIGN.md section 6); "
                          "'fixed': rank 0 (BASELINE config 4 as written).  The line reports the other mode in `gather`")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned for its last step as DIR/<name>.npy "
+                         "(dump_outputs): two builds run with the same arguments can then be compared output for output")
     ap.add_argument("--preroll-steps", type=int, default=60,
                     help="untimed steps before the warm-up: the shader clock needs ~40 ms of this load to settle (DESIGN.md "
                          "section 5), so that a 20-step timed window measures the same steady state as a 100-step one; the line "
@@ -1876,13 +1925,6 @@ def main():
         sys.exit(spawn_check())
     if args.batches_in_flight <= 0:
         args.batches_in_flight = 2
-    # HIP multiplexes a process's streams onto 4 hardware queues unless told otherwise, and a stream that shares a
-    # queue with the extraction stream runs BEHIND the batches queued there: the gather's communication stream then
-    # completes batch k-2 only after batch k, the host cannot run ahead and the pipeline loses its depth (1 rank through
-    # the communicator: 41 k instead of 51 k frames/s; the host-fed pipe wanders between 16 k and 24 k).  Must be set
-    # before the HIP runtime initialises, i.e. before torch is imported; a caller's own setting wins.
-    if not os.environ.get("BENCH_NO_QUEUE_DEFAULT"):     # developer switch: leave HIP's default of 4 hardware queues
-        os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
     if args.pmc_child:
         return pmc_child()
     if args.emulate_ranks > 0:
@@ -1891,6 +1933,8 @@ def main():
     b.leg_matcher()               # BASELINE config 5 (its own timed region)
     b.setup_inputs()
     b.leg_timed_loop()            # `value` (+ `no_preroll`)
+    if args.dump_outputs and b.rank == 0:
+        dump_outputs(args.dump_outputs, b.last_counts, b.last_offs, b.last_recs)
     b.leg_other_root()            # N > 1: the other gather root
     b.leg_kernel_events()
     b.leg_single_frame()          # BASELINE configs 2 and 3

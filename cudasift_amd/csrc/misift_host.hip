@@ -186,25 +186,6 @@ static int resolve_profile(misift_ctx *ctx)
   return MISIFT_OK;
 }
 
-// Streams of one process share HIP's hardware queues (4 by default): the communication stream then queues behind
-// the extraction stream's kernels and a pipelined gather loses ~20 %.  Say so once.
-static void warn_hw_queues_once(const char *who)
-{
-  const char *e = getenv("GPU_MAX_HW_QUEUES");
-  if (e && atoi(e) >= 8) return;
-  // a warning, not an error: stderr only — misift_last_error() of a successful call stays empty
-  if (!getenv("MISIFT_QUIET"))
-    fprintf(stderr, "misift: warning: %s: GPU_MAX_HW_QUEUES is %s; with fewer than 8 hardware queues the communication / "
-                    "copy streams share a queue with the extraction stream (set GPU_MAX_HW_QUEUES=8 before the first HIP "
-                    "call, or create the first misift context before any other HIP call: it sets it)\n", who,
-            e ? e : "unset (HIP default: 4)");
-}
-void misift_warn_hw_queues(const char *who)
-{
-  static std::once_flag once;            // communicators are created from several host threads at the same time
-  std::call_once(once, warn_hw_queues_once, who);
-}
-
 // ----------------------------------------------------------------- context
 struct CtxFull {
   misift_ctx c;
@@ -215,18 +196,8 @@ static CtxExtra *extra(misift_ctx *ctx) { return &reinterpret_cast<CtxFull *>(ct
 // MISIFT_DEVICES="2,3" (SURVEY section 5): device i of this library = HIP device list[i], the others do not exist for
 // it — like HIP_VISIBLE_DEVICES but for libmisift.so only (a process that shares the GPUs with another runtime keeps
 // its own numbering).  Unset or empty: every HIP device, identity.  Read once.
-// HIP reads GPU_MAX_HW_QUEUES when it initialises; a C++ caller that never heard of it gets 4 hardware queues and loses
-// ~20 % through a communicator or a host-fed pipe.  If the variable is unset when the library makes its
-// first HIP call (device enumeration), set it — it takes effect when this is also the process's first HIP call (the normal case for
-// a program that uses the library through cudaSift.h), and is harmless otherwise.  Never overrides the caller's value.
-static void default_hw_queues_once(void)
-{
-  if (!getenv("GPU_MAX_HW_QUEUES") && !getenv("MISIFT_KEEP_HW_QUEUES")) setenv("GPU_MAX_HW_QUEUES", "8", 0);
-}
-
 static std::vector<int> build_device_map(void)
 {
-  default_hw_queues_once();            // before the library's first HIP call
   std::vector<int> m;
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess) n = 0;

@@ -432,7 +432,6 @@ static int comm_finish_create(misift_ctx *ctx, ncclComm_t nc, bool owns, misift_
     NCCL_TRY(g_rccl.CommCount(nc, &c->nranks));
     NCCL_TRY(g_rccl.CommUserRank(nc, &c->rank));
   }
-  misift_warn_hw_queues("misift_comm_create");
   int lo = 0, hi = 0;
   HIP_TRY(hipDeviceGetStreamPriorityRange(&lo, &hi));
   HIP_TRY(hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, hi));

@@ -214,3 +214,50 @@ def test_under_the_drivers_launcher_a_silent_rank_ends_the_job():
     assert r.returncode != 0
     assert "watchdog: rank" in r.stderr and "pretend_collective" in r.stderr, r.stderr[-2000:]
     assert time.time() - t0 < 120
+
+
+def test_dump_outputs_are_bounded_and_independent_of_record_order(tmp_path, monkeypatch):
+    """--dump-outputs: float32 / float64 .npy files within 64 MB; the same fixed sample of frames every time, at most
+    DUMP_RECORDS_PER_FRAME records each; a batch whose records sit in another order inside their frames (the library's
+    atomic appends) dumps byte for byte the same."""
+    import sys
+    from cudasift_amd import capi
+    b = _bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--dump-outputs", str(tmp_path / "a")])
+    assert b.parse_args().dump_outputs == str(tmp_path / "a")
+    rng = np.random.default_rng(5)
+    counts = rng.integers(0, 6000, 40)
+    counts[:3] = (0, 1, 5000)
+    offs = np.concatenate([[0], np.cumsum(counts)])
+    recs = np.zeros(int(offs[-1]), capi.POINT_DTYPE)
+    for k in ("xpos", "ypos", "scale", "sharpness", "edgeness", "orientation"):
+        recs[k] = rng.integers(0, 50, len(recs)) * 0.5        # coarse values: ties on the leading sort keys
+    recs["subsampling"] = 2.0 ** rng.integers(-1, 4, len(recs))
+    recs["match"] = -1
+    recs["data"] = rng.random((len(recs), 128))
+    shuffled = recs.copy()
+    for f in range(len(counts)):
+        seg = shuffled[offs[f]:offs[f + 1]]
+        shuffled[offs[f]:offs[f + 1]] = seg[rng.permutation(len(seg))]
+    paths_a = b.dump_outputs(str(tmp_path / "a"), counts, offs, recs)
+    paths_b = b.dump_outputs(str(tmp_path / "b"), counts, offs, shuffled)
+    assert [os.path.basename(p) for p in paths_a] == ["counts.npy", "points.npy", "descriptors.npy", "point_frame.npy"]
+    total = 0
+    for pa, pb in zip(paths_a, paths_b):
+        a, c = np.load(pa), np.load(pb)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, c), pa
+        total += os.path.getsize(pa)
+    assert total <= 64 << 20
+    d = {os.path.basename(p)[:-4]: np.load(p) for p in paths_a}
+    assert np.array_equal(d["counts"], counts)
+    frames = np.sort(np.random.default_rng(b.DUMP_SEED).choice(len(counts), b.DUMP_FRAMES, replace=False))
+    for f in frames:
+        rows = d["point_frame"] == f
+        assert rows.sum() == min(counts[f], b.DUMP_RECORDS_PER_FRAME)
+        pts, desc = d["points"][rows], d["descriptors"][rows]
+        sub, y = pts[:, b.DUMP_POINT_FIELDS.index("subsampling")], pts[:, b.DUMP_POINT_FIELDS.index("ypos")]
+        assert np.all((np.diff(sub) > 0) | ((np.diff(sub) == 0) & (np.diff(y) >= 0)))
+        seg = recs[offs[f]:offs[f + 1]]                        # every row is one of the frame's records
+        mine = {r.tobytes() for r in seg["data"]}
+        assert all(r.tobytes() in mine for r in desc)
+    assert set(np.unique(d["point_frame"])) <= set(frames)

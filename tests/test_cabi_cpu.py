@@ -10,6 +10,12 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INC = os.path.join(ROOT, "include")
+DROPIN = os.path.join(ROOT, "oracle", "_ref", "cudasift_dropin")
+
+
+def needed_libs(exe):
+    out = subprocess.check_output(["readelf", "-d", exe], text=True)
+    return set(re.findall(r"\(NEEDED\)\s+Shared library: \[([^\]]+)\]", out))
 
 
 def declared_functions():
@@ -126,27 +132,16 @@ def test_managedmem_flavour_builds_and_exports(tmp_path):
     exe = tmp_path / "layout"
     subprocess.check_call(["g++", "-std=c++17", "-DMANAGEDMEM", "-I", INC, str(src), "-o", str(exe)])
     assert subprocess.check_output([str(exe)], text=True).split() == ["576", "16", "8"]
-    ref = os.environ.get("REF", "/root/reference")
-    if os.path.exists(os.path.join(ref, "mainSift.cpp")):
-        exe2 = tmp_path / "dropin_managed"
-        subprocess.check_call(["g++", "-O1", "-std=c++17", "-DMANAGEDMEM", "-I", INC, "-I",
-                               os.path.join(ROOT, "cudasift_amd", "compat"), os.path.join(ref, "mainSift.cpp"),
-                               os.path.join(ref, "geomFuncs.cpp"), "-o", str(exe2), "-L",
-                               os.path.join(ROOT, "cudasift_amd"), "-lcudasift_managed", "-lmisift",
-                               "-Wl,-rpath," + os.path.join(ROOT, "cudasift_amd")])
-        assert os.path.exists(exe2)
+    if os.path.exists(DROPIN + "_managed"):
+        assert "libcudasift_managed.so" in needed_libs(DROPIN + "_managed")
 
 
-def test_reference_main_compiles_unchanged(tmp_path):
-    ref = os.environ.get("REF", "/root/reference")
-    if not os.path.exists(os.path.join(ref, "mainSift.cpp")):
-        pytest.skip("reference tree absent")
-    exe = tmp_path / "dropin"
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-I", INC, "-I", os.path.join(ROOT, "cudasift_amd", "compat"),
-                           os.path.join(ref, "mainSift.cpp"), os.path.join(ref, "geomFuncs.cpp"), "-o", str(exe),
-                           "-L", os.path.join(ROOT, "cudasift_amd"), "-lcudasift", "-lmisift",
-                           "-Wl,-rpath," + os.path.join(ROOT, "cudasift_amd")])
-    assert os.path.exists(exe)
+def test_reference_main_compiles_unchanged():
+    """build() compiles the reference's own mainSift.cpp + geomFuncs.cpp unchanged against include/ and links them to the
+    shim (`make dropin`: oracle/_ref/cudasift_dropin, wherever the reference tree is present at build time)."""
+    if not os.path.exists(DROPIN):
+        pytest.skip("oracle/_ref/cudasift_dropin not built (reference tree absent at build time)")
+    assert "libcudasift.so" in needed_libs(DROPIN)
 
 
 def test_header_is_plain_c99(tmp_path):
