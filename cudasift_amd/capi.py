@@ -94,6 +94,8 @@ SIGNATURES = {
     "misift_test_elementary": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i]),
     "misift_test_match_split": (_i, [_vp, _vp, _i, _vp, _i, _i, _i]),
     "misift_test_match_plan": (_i, [_i, _i, _i, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "misift_test_match_batch_plan": (_i, [_i, _i, _i, _vp, _vp, _vp, _ip, _ip, _ip]),
+    "misift_match_batch": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i]),
     "misift_test_frame_shares": (_i, [_i, _i, C.c_void_p, C.c_void_p]),
     "misift_test_set_knob": (_i, [_vp, C.c_char_p, C.c_double]),
     "misift_test_knob_names": (C.c_char_p, []),
@@ -496,6 +498,21 @@ class Context:
         else:
             check(lib().misift_match_rows(self.h, d1.ptr, row_begin, row_count, d2.ptr, n2), "misift_match_rows")
         return self.download(d1, (len(pts1),), POINT_DTYPE)
+
+    def match_batch(self, pairs, recs1, nframes1, counts1, offsets1=None, stride1=0, recs2=None, nframes2=None,
+                    counts2=None, offsets2=None, stride2=None):
+        """misift_match_batch: for each row (f1, f2) of `pairs`, MatchSiftData of frame f1 of set 1 against frame f2 of
+        set 2, on device buffers (DevBuf or raw device pointers).  Frame f of a set holds max(counts[f], 0) records from
+        record offsets[f] (offsets None: f * stride).  Set 2 defaults to set 1 (frame f against frame f + 1 of one
+        batch).  Enqueued on the context stream: the results are there once sync() (or later stream work) has run."""
+        def ptr(b):
+            return b.ptr if isinstance(b, DevBuf) else b
+        if recs2 is None:
+            recs2, nframes2, counts2, offsets2, stride2 = recs1, nframes1, counts1, offsets1, stride1
+        pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        check(lib().misift_match_batch(self.h, len(pairs), pairs.ctypes.data, ptr(recs1), nframes1, ptr(counts1),
+                                       ptr(offsets1), stride1, ptr(recs2), nframes2, ptr(counts2), ptr(offsets2),
+                                       stride1 if stride2 is None else stride2), "misift_match_batch")
 
     def match_split(self, pts1, n1, pts2, n2, own_tile_begin, own_tile_end):
         """Test hook: misift_match with the column sweep cut into two launches (the sharded matcher's cut)."""

@@ -510,7 +510,13 @@ int launch_match(misift_ctx *ctx, SiftPointD *pts1, int row_begin, int row_count
 int launch_match_split(misift_ctx *ctx, SiftPointD *pts1, int row_begin, int row_count, const SiftPointD *pts2, int n2,
                        const SiftPointD *pts2_own, int own_t0, int own_t1, hipEvent_t rest_ready, int phase,
                        int packed2 = 0);     // packed2: set 2 is an array of MISIFT_MATCH_COLUMN_BYTES match columns, not records
-enum { MATCH_PHASE_ALL = 0, MATCH_PHASE_OWN = 1, MATCH_PHASE_REST = 2 };   // both launches + merge / the own-shard launch / the rest + merge
+enum { MATCH_PHASE_ALL = 0, MATCH_PHASE_OWN = 1, MATCH_PHASE_REST = 2 };
+// misift_match_batch: plan + sweep + merge on the context stream.  h_pairs: pinned host copy of the pairs (read by the first
+// launch); d_plan: match_batch_plan_bytes(npairs) bytes of device memory
+size_t match_batch_plan_bytes(int npairs);
+int launch_match_batch(misift_ctx *ctx, int npairs, const int *h_pairs, void *d_plan, SiftPointD *recs1,
+                       const int *counts1, const int *offsets1, int stride1, const SiftPointD *recs2,
+                       const int *counts2, const int *offsets2, int stride2);   // both launches + merge / the own-shard launch / the rest + merge
 int launch_test_exp2(misift_ctx *ctx, const float *x, float *out, int n);
 int launch_test_points_fn(misift_ctx *ctx, int fn, const float *x, const float *y, float *out, float *out2, int n);
 int launch_selftest(misift_ctx *ctx);

@@ -15,8 +15,10 @@
 // (matching.cu:375-390) can be reproduced exactly — or replaced by the exact second best.
 // Columns are split into chunks across workgroups to fill 256 CUs; a small merge kernel
 // combines the per-chunk class triples and writes score/match/ambiguity/match_xpos/ypos.
+// match_batch_*: the same sweep over many independent frame pairs whose sizes only the device knows (misift_match_batch).
 #include <stdlib.h>
 #include <string.h>
+#include <vector>
 #include "common.hpp"
 
 typedef float floatx16 __attribute__((ext_vector_type(16)));
@@ -134,326 +136,8 @@ __global__ __launch_bounds__(64 * MT_WG_WAVES, 8 / MT_WG_WAVES) void match_kerne
   MT_STAMP_MIN(0);                 // first workgroup starts
   MT_STAMP_MAX(1);                 // last workgroup starts
 
-  // ---- A fragment: row (lane&31) of this wave, k = 2t + half, t = 0..63
-  const int row_local = rb * MT_ROWS_PER_BLOCK + wave * 32 + col;          // within [0,row_count)
-  const int row_ld = G.row_begin + min(row_local, G.row_count - 1);
-  float a[64];
-  {
-    const float4 *src = reinterpret_cast<const float4 *>(pts1[row_ld].data);
-#if MT_A_SWAP
-    // The two lanes of a row fetch adjacent float4s (k = 8i..8i+3 | 8i+4..8i+7) and trade the halves they do not need
-    // with v_permlane32_swap (lanes 32-63 of the first operand <-> lanes 0-31 of the second): 16 loads per lane
-    // instead of 32 of which half of every float4 was thrown away — the row fetch is the head of a small launch's
-    // critical path and bound by the texture addresser (32 cache lines per instruction: rows are 576 bytes apart).
-#pragma unroll
-    for (int i = 0; i < 16; i++) {
-      const float4 v = src[2 * i + half];
-      const auto xy = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, v.x), __builtin_bit_cast(unsigned, v.y), false, false);
-      const auto zw = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, v.z), __builtin_bit_cast(unsigned, v.w), false, false);
-      a[4 * i + 0] = __builtin_bit_cast(float, (unsigned)xy[0]);       // k = 8i     | 8i + 1
-      a[4 * i + 1] = __builtin_bit_cast(float, (unsigned)zw[0]);       // k = 8i + 2 | 8i + 3
-      a[4 * i + 2] = __builtin_bit_cast(float, (unsigned)xy[1]);       // k = 8i + 4 | 8i + 5
-      a[4 * i + 3] = __builtin_bit_cast(float, (unsigned)zw[1]);       // k = 8i + 6 | 8i + 7
-    }
-#else
-#pragma unroll
-    for (int j = 0; j < 32; j++) {
-      const float4 v = src[j];
-      a[2 * j] = half ? v.y : v.x;
-      a[2 * j + 1] = half ? v.w : v.z;
-    }
-#endif
-  }
-  // ---- per-lane running top-2 for 16 rows (accumulator register r <-> row (r&3)+8*(r>>2)+4*half)
-  float mx[16], sec[16];
-  int ix[16];
-#pragma unroll
-  for (int r = 0; r < 16; r++) { mx[r] = 0.0f; sec[r] = 0.0f; ix[r] = -1; }
-
-  // ---- B staging: thread -> (column scol + 8j, float4 index f4), j = 0..7
-  const int scol = tid >> 5, f4 = tid & 31;
-  float4 stage[MT_STAGE];
-#ifndef MT_LEAN_STAGING
-#define MT_LEAN_STAGING 1
-#endif
-#ifndef MT_TOP2_FILTER
-#define MT_TOP2_FILTER 0
-#endif
-#if MT_LEAN_STAGING
-  // r06: the staging costs the SIMD VALU time the matrix pipe does not get back (SQ counters: MFMA busy + VALU issuing ~ 1 of
-  // the launch's SIMD-cycles).  (a) one 32-bit byte offset per thread and load (clamp + v_mad_u32_u24) against a wave-uniform
-  // (SGPR) tile base instead of clamp + 64-bit multiply-add + 64-bit shift-add per load; (b) the even-k / odd-k halves of a staged float4 go to LDS as ds_write2_b32
-  // x,z | y,w — two separate registers each — instead of ds_write2_b64 of register PAIRS the compiler has to assemble with
-  // three v_mov per float4.  24 + 8 of the ~196 non-MFMA VALU instructions per super-tile and wavefront.
-  const unsigned vconst = (unsigned)G.data_off2 * 4u + (unsigned)f4 * 16u;
-  auto gload = [&](int st) {
-    const int c0 = tile_col0(G, st);                                         // wave-uniform
-    const char *sb = reinterpret_cast<const char *>(set2) + (size_t)c0 * (size_t)G.stride2 * 4u;
-    const int last = G.n2 - 1 - c0;                                          // (scalar) the clamp matters in a partial last super-tile only
-#pragma unroll
-    for (int j = 0; j < MT_STAGE; j++) {
-      const unsigned rel = (unsigned)min(scol + 2 * MT_WG_WAVES * j, last);
-      stage[j] = *reinterpret_cast<const float4 *>(sb + (__umul24(rel, (unsigned)G.stride2 * 4u) + vconst));
-    }
-  };
-  auto lstore = [&](int buf) {
-#pragma unroll
-    for (int j = 0; j < MT_STAGE; j++) {
-      float *d = &Bs[buf][(scol + 2 * MT_WG_WAVES * j) * MT_BSTRIDE + 2 * f4];       // k = 4*f4 .. 4*f4+3
-      const unsigned a = (unsigned)(size_t)(__attribute__((address_space(3))) float *)d;
-      asm volatile("ds_write2_b32 %0, %1, %2 offset1:1" :: "v"(a), "v"(stage[j].x), "v"(stage[j].z) : "memory");            // even k -> half 0
-      asm volatile("ds_write2_b32 %0, %1, %2 offset0:64 offset1:65" :: "v"(a), "v"(stage[j].y), "v"(stage[j].w) : "memory"); // odd k -> half 1
-    }
-  };
-  // the compiler's wait-count bookkeeping does not see the DS stores issued from inline asm: before a barrier that publishes
-  // them, wait for them by hand
-#define MT_LDS_STORES_DONE() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
-#else
-  auto gload = [&](int st) {
-#pragma unroll
-    for (int j = 0; j < MT_STAGE; j++) {
-      const int p2 = min(tile_col0(G, st) + scol + 2 * MT_WG_WAVES * j, G.n2 - 1);
-      stage[j] = reinterpret_cast<const float4 *>(set2 + (size_t)p2 * G.stride2 + G.data_off2)[f4];
-    }
-  };
-  auto lstore = [&](int buf) {
-#pragma unroll
-    for (int j = 0; j < MT_STAGE; j++) {
-      float *d = &Bs[buf][(scol + 2 * MT_WG_WAVES * j) * MT_BSTRIDE + 2 * f4];       // k = 4*f4 .. 4*f4+3
-      *reinterpret_cast<float2 *>(d) = make_float2(stage[j].x, stage[j].z);        // even k -> half 0
-      *reinterpret_cast<float2 *>(d + 64) = make_float2(stage[j].y, stage[j].w);   // odd k  -> half 1
-    }
-  };
-#define MT_LDS_STORES_DONE() do { } while (0)
-#endif
-
-#ifndef MT_PIPE_EPILOGUE
-#define MT_PIPE_EPILOGUE 1
-#endif
-#ifndef MT_EARLY_STORE
-#define MT_EARLY_STORE 1
-#endif
-#ifndef MT_EARLY_STORE_AT
-#define MT_EARLY_STORE_AT 10
-#endif
-// timing-only experiments (wrong results): what the barrier / the LDS store / the global loads cost (tools/variants.sh)
-#ifndef MT_EXP_NOBARRIER
-#define MT_EXP_NOBARRIER 0
-#endif
-#ifndef MT_EXP_NOSTORE
-#define MT_EXP_NOSTORE 0
-#endif
-#ifndef MT_EXP_NOGLOAD
-#define MT_EXP_NOGLOAD 0
-#endif
-#if (MT_EXP_NOBARRIER || MT_EXP_NOSTORE || MT_EXP_NOGLOAD) && !defined(MISIFT_TIMING_ONLY_BUILD)
-#error "MT_EXP_* are timing-only experiments that compute WRONG results: build them with -DMISIFT_TIMING_ONLY_BUILD (tools/variants.sh), never into libmisift.so"
-#endif
-  if (st0 < st1) {
-    gload(st0);
-#if MT_STAMPS
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    MT_STAMP_MAX(2);               // rows of set 1 and the first super-tile have arrived
-#endif
-    lstore(0);
-  }
-  MT_LDS_STORES_DONE();
-  __syncthreads();
-  MT_STAMP_MAX(3);                 // first super-tile staged
-#if MT_PIPE_EPILOGUE
-  // Software pipeline over the super-tiles (r03): the top-2 update of tile t-1 (128 VALU instructions on its 32 finished
-  // accumulator registers) is issued BETWEEN the MFMAs of tile t instead of after them, so a wavefront's matrix pipe
-  // never waits for its own epilogue.  Two accumulator sets alternate (the loop body is instantiated for both, no
-  // register copies): 32 more VGPRs, still 2 wavefronts per SIMD.
-  auto tile = [&](const int st, floatx16 &acc0, floatx16 &acc1, const floatx16 &prev0, const floatx16 &prev1,
-                  const bool have_prev) __attribute__((always_inline)) {
-    const int buf = (st - st0) & 1;
-#if !MT_EXP_NOGLOAD
-    gload(min(st + 1, st1 - 1));
-#endif
-    const float4 *b0 = reinterpret_cast<const float4 *>(&Bs[buf][col * MT_BSTRIDE + half * 64]);
-    const float4 *b1 = reinterpret_cast<const float4 *>(&Bs[buf][(col + 32) * MT_BSTRIDE + half * 64]);
-    acc0 = floatx16{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    acc1 = floatx16{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    const int pc0 = tile_col0(G, st - 1) + col, pc1 = pc0 + 32;          // columns of the previous tile
-    const bool do0 = have_prev && pc0 < G.ncols, do1 = have_prev && pc1 < G.ncols;
-    float4 p0 = b0[0], p1 = b1[0], q0, q1;
-#pragma unroll
-    for (int i = 0; i < 16; i += 2) {
-      q0 = b0[i + 1]; q1 = b1[i + 1];
-      __builtin_amdgcn_sched_barrier(0);
-      acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4 * i + 0], p0.x, acc0, 0, 0, 0);
-      acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4 * i + 0], p1.x, acc1, 0, 0, 0);
-      acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4 * i + 1], p0.y, acc0, 0, 0, 0);
-      acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4 * i + 1], p1.y, acc1, 0, 0, 0);
-      __builtin_amdgcn_sched_barrier(0);
-      // previous tile, ascending column order within the residue class: its columns 0-31 (chain 0) during the first
-      // four slots of this tile's k-loop, columns 32-63 (chain 1) during the last four; four rows per slot
-      {
-        const int t4 = 4 * ((i >> 1) & 3);
-#if MT_TOP2_FILTER
-        // r06: a score changes a lane's top two only if it beats the running SECOND best — after a few hundred columns that
-        // is rare (2/n per lane), so the three instructions behind the compare run only when some lane of the wavefront needs
-        // them (wave-uniform branch): on 100 000 columns ~17 % of the row updates.  Exact: a score that is not above `sec`
-        // (or is NaN) leaves (mx, sec, ix) untouched in top2_update as well.
-        if (i < 8) {
-#pragma unroll
-          for (int r = 0; r < 4; r++) {
-            const float sc = prev0[t4 + r];
-            if (__builtin_amdgcn_ballot_w64(do0 && sc > sec[t4 + r]) != 0ull) {
-              if (do0) top2_update(sc, pc0, mx[t4 + r], sec[t4 + r], ix[t4 + r]);
-            }
-          }
-        } else {
-#pragma unroll
-          for (int r = 0; r < 4; r++) {
-            const float sc = prev1[t4 + r];
-            if (__builtin_amdgcn_ballot_w64(do1 && sc > sec[t4 + r]) != 0ull) {
-              if (do1) top2_update(sc, pc1, mx[t4 + r], sec[t4 + r], ix[t4 + r]);
-            }
-          }
-        }
-#else
-        if (i < 8) {
-          if (do0) {
-#pragma unroll
-            for (int r = 0; r < 4; r++) top2_update(prev0[t4 + r], pc0, mx[t4 + r], sec[t4 + r], ix[t4 + r]);
-          }
-        } else {
-          if (do1) {
-#pragma unroll
-            for (int r = 0; r < 4; r++) top2_update(prev1[t4 + r], pc1, mx[t4 + r], sec[t4 + r], ix[t4 + r]);
-          }
-        }
-#endif
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4 * i + 2], p0.z, acc0, 0, 0, 0);
-      acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4 * i + 2], p1.z, acc1, 0, 0, 0);
-      acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4 * i + 3], p0.w, acc0, 0, 0, 0);
-      acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4 * i + 3], p1.w, acc1, 0, 0, 0);
-      __builtin_amdgcn_sched_barrier(0);
-      if (i + 2 < 16) { p0 = b0[i + 2]; p1 = b1[i + 2]; }
-      __builtin_amdgcn_sched_barrier(0);
-      acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4 * i + 4], q0.x, acc0, 0, 0, 0);
-      acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4 * i + 4], q1.x, acc1, 0, 0, 0);
-      acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4 * i + 5], q0.y, acc0, 0, 0, 0);
-      acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4 * i + 5], q1.y, acc1, 0, 0, 0);
-      __builtin_amdgcn_sched_barrier(0);
-#if MT_EARLY_STORE
-      // the next tile's operands go to the other LDS buffer in the MIDDLE of this tile's MFMA stream (the loads were
-      // issued at its start; that buffer's readers all passed the previous barrier): nothing but the barrier itself is
-      // left between the last MFMA of this tile and the first operand read of the next
-#if !MT_EXP_NOSTORE
-      if (i == MT_EARLY_STORE_AT) lstore(buf ^ 1);
-#endif
-      __builtin_amdgcn_sched_barrier(0);
-#endif
-      acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4 * i + 6], q0.z, acc0, 0, 0, 0);
-      acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4 * i + 6], q1.z, acc1, 0, 0, 0);
-      acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4 * i + 7], q0.w, acc0, 0, 0, 0);
-      acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4 * i + 7], q1.w, acc1, 0, 0, 0);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-#if !MT_EARLY_STORE
-    lstore(buf ^ 1);
-#endif
-#if !MT_EXP_NOBARRIER
-    MT_LDS_STORES_DONE();
-    __syncthreads();
-#endif
-  };
-  {
-    floatx16 A0, A1, B0, B1;
-    int st = st0;
-    bool have = false;
-    for (; st + 1 < st1; st += 2) {
-      tile(st, A0, A1, B0, B1, have);
-      tile(st + 1, B0, B1, A0, A1, true);
-      have = true;
-    }
-    if (st < st1) {                       // an odd tile left: it finishes B, then its own results are in A
-      tile(st, A0, A1, B0, B1, have);
-      const int c0 = tile_col0(G, st) + col, c1 = c0 + 32;
-      if (c0 < G.ncols) {
-#pragma unroll
-        for (int r = 0; r < 16; r++) top2_update(A0[r], c0, mx[r], sec[r], ix[r]);
-      }
-      if (c1 < G.ncols) {
-#pragma unroll
-        for (int r = 0; r < 16; r++) top2_update(A1[r], c1, mx[r], sec[r], ix[r]);
-      }
-    } else if (have) {                    // the last tile of an even count sits in B
-      const int c0 = tile_col0(G, st1 - 1) + col, c1 = c0 + 32;
-      if (c0 < G.ncols) {
-#pragma unroll
-        for (int r = 0; r < 16; r++) top2_update(B0[r], c0, mx[r], sec[r], ix[r]);
-      }
-      if (c1 < G.ncols) {
-#pragma unroll
-        for (int r = 0; r < 16; r++) top2_update(B1[r], c1, mx[r], sec[r], ix[r]);
-      }
-    }
-  }
-#else
-  for (int st = st0; st < st1; st++) {
-    const int buf = (st - st0) & 1;
-    gload(min(st + 1, st1 - 1));     // unconditional (the last iteration re-fetches its own tile): no phi copies of the 32 staging registers
-    const float4 *b0 = reinterpret_cast<const float4 *>(&Bs[buf][col * MT_BSTRIDE + half * 64]);
-    const float4 *b1 = reinterpret_cast<const float4 *>(&Bs[buf][(col + 32) * MT_BSTRIDE + half * 64]);
-    floatx16 acc0 = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    floatx16 acc1 = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    // software pipeline: the ds_read_b128 pair of the next 4 k-pairs is in flight while 8 MFMAs run
-    float4 p0 = b0[0], p1 = b1[0], q0, q1;
-#pragma unroll
-    for (int i = 0; i < 16; i += 2) {
-      q0 = b0[i + 1]; q1 = b1[i + 1];
-      __builtin_amdgcn_sched_barrier(0);        // keep the prefetch ahead of the MFMAs that hide it
-      acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4 * i + 0], p0.x, acc0, 0, 0, 0);
-      acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4 * i + 0], p1.x, acc1, 0, 0, 0);
-      acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4 * i + 1], p0.y, acc0, 0, 0, 0);
-      acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4 * i + 1], p1.y, acc1, 0, 0, 0);
-      acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4 * i + 2], p0.z, acc0, 0, 0, 0);
-      acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4 * i + 2], p1.z, acc1, 0, 0, 0);
-      acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4 * i + 3], p0.w, acc0, 0, 0, 0);
-      acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4 * i + 3], p1.w, acc1, 0, 0, 0);
-      __builtin_amdgcn_sched_barrier(0);
-      if (i + 2 < 16) { p0 = b0[i + 2]; p1 = b1[i + 2]; }
-      __builtin_amdgcn_sched_barrier(0);
-      acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4 * i + 4], q0.x, acc0, 0, 0, 0);
-      acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4 * i + 4], q1.x, acc1, 0, 0, 0);
-      acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4 * i + 5], q0.y, acc0, 0, 0, 0);
-      acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4 * i + 5], q1.y, acc1, 0, 0, 0);
-      acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4 * i + 6], q0.z, acc0, 0, 0, 0);
-      acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4 * i + 6], q1.z, acc1, 0, 0, 0);
-      acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4 * i + 7], q0.w, acc0, 0, 0, 0);
-      acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4 * i + 7], q1.w, acc1, 0, 0, 0);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    // ascending column order within the residue class: columns 0-31 of the super-tile first
-    const int c0 = tile_col0(G, st) + col, c1 = c0 + 32;
-    if (c0 < G.ncols) {
-#pragma unroll
-      for (int r = 0; r < 16; r++) top2_update(acc0[r], c0, mx[r], sec[r], ix[r]);
-    }
-    if (c1 < G.ncols) {
-#pragma unroll
-      for (int r = 0; r < 16; r++) top2_update(acc1[r], c1, mx[r], sec[r], ix[r]);
-    }
-    lstore(buf ^ 1);
-    MT_LDS_STORES_DONE();
-    __syncthreads();
-  }
-
-#endif
-  MT_STAMP_MAX(4);                 // sweep done
-  // ---- reduce the 4 residues of a class (lanes 4c..4c+3 of the same half): exact merge
-#pragma unroll
-  for (int r = 0; r < 16; r++)
-    top2_merge(mx[r], sec[r], ix[r], quad_xchg<0xB1>(mx[r]), quad_xchg<0xB1>(sec[r]), quad_xchg<0xB1>(ix[r]));
-#pragma unroll
-  for (int r = 0; r < 16; r++)
-    top2_merge(mx[r], sec[r], ix[r], quad_xchg<0x4E>(mx[r]), quad_xchg<0x4E>(sec[r]), quad_xchg<0x4E>(ix[r]));
+  // the sweep (match_sweep.inc, shared with match_batch_kernel): leaves mx / sec / ix
+#include "match_sweep.inc"
   if ((lane & 3) == 0) {
     const int cls = col >> 2;
 #pragma unroll
@@ -671,4 +355,352 @@ int launch_match_split(misift_ctx *ctx, SiftPointD *pts1, int row_begin, int row
 int launch_match(misift_ctx *ctx, SiftPointD *pts1, int row_begin, int row_count, const SiftPointD *pts2, int n2)
 {
   return launch_match_split(ctx, pts1, row_begin, row_count, pts2, n2, nullptr, 0, 0, nullptr, MATCH_PHASE_ALL, 0);
+}
+
+// ============================================================================ batched pair matching (misift_match_batch)
+// MatchSiftData of many independent (frame of set 1, frame of set 2) pairs in three launches, with the frames' sizes known
+// on the device only:
+//   match_batch_plan_kernel   one workgroup: reads counts / offsets, writes one MbPair per pair (shape, chunking, and
+//                             exclusive prefix sums of work items and row blocks).  The work list is implicit: item i
+//                             belongs to the last pair with item0 <= i, and is (row block, column chunk) of that pair.
+//   match_batch_kernel        persistent grid of two workgroups per CU; each takes items in a fixed stride and runs the
+//                             same sweep as match_kernel (match_sweep.inc) on them.  With one chunk per row block the
+//                             workgroup merges the eight classes and writes its rows itself; otherwise it stores the
+//                             per-class triples of the item and
+//   match_batch_merge_kernel  merges them over the chunks (it returns at once when nothing was chunked).
+// Columns are cut into chunks only when the row blocks of the whole call do not fill one round (two workgroups per CU);
+// the cut then leaves at most 2 * target items, so the partials buffer has a bound the host knows (mb_partial_items).
+struct MbPair {
+  int n1, n2, off1, off2;        // frame sizes (records, counts < 0 -> 0) and first records
+  int ncols, ntiles;             // columns that take part (32*floor(n2/32) or n2), 64-column super-tiles
+  int nrb, nchunks, tpc;         // 128-row blocks, column chunks, super-tiles per chunk
+  int item0, rb0;                // first work item / first row block of the pair (entry npairs: the totals)
+  int pad;
+};
+#define MB_HDR_INTS 4            // plan header: items, chunk count C, row blocks, 0 — then MbPair[npairs + 1]
+#define MB_PART_FLOATS (MT_ROWS_PER_BLOCK * 8 * 3)     // per-class (max, second, index) of an item's 128 rows
+
+__host__ __device__ __forceinline__ void mb_pair_shape(int n1, int n2, int full, int &ncols, int &ntiles, int &nrb)
+{
+  if (n1 <= 0 || n2 <= 0) { ncols = 0; ntiles = 0; nrb = 0; return; }     // matching.cu:1095-1096: pair left untouched
+  ncols = full ? n2 : MT_TILE * (n2 / MT_TILE);
+  ntiles = (ncols + MT_SUPER - 1) / MT_SUPER;
+  nrb = (n1 + MT_ROWS_PER_BLOCK - 1) / MT_ROWS_PER_BLOCK;
+}
+// one round = two workgroups per CU (match_kernel's occupancy)
+__host__ __device__ __forceinline__ int mb_target(int ncu) { return 2 * (ncu > 0 ? ncu : 256); }
+// chunks per row block for a call of R row blocks: 1 when they fill a round, else ceil(target / R), so that
+// R * C < target + R < 2 * target
+__host__ __device__ __forceinline__ int mb_batch_chunks(long long R, int ncu)
+{
+  const long long t = mb_target(ncu);
+  if (R <= 0 || R >= t) return 1;
+  return (int)((t + R - 1) / R);
+}
+__host__ __device__ __forceinline__ void mb_pair_chunks(int ntiles, int C, int &nchunks, int &tpc)
+{
+  if (ntiles <= 0 || C <= 1) { nchunks = 1; tpc = ntiles > 0 ? ntiles : 1; return; }
+  nchunks = C < ntiles ? C : ntiles;
+  tpc = (ntiles + nchunks - 1) / nchunks;
+  nchunks = (ntiles + tpc - 1) / tpc;                   // no empty chunk
+}
+int mb_partial_items(int ncu) { return 2 * mb_target(ncu); }
+
+// exclusive scan of two ints over a 1024-thread workgroup; *tot = the workgroup's totals
+__device__ __forceinline__ void mb_block_scan2(int &a, int &b, int &tot_a, int &tot_b, int (*s)[2])
+{
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int ia = a, ib = b;
+  for (int d = 1; d < 64; d <<= 1) {
+    const int oa = __shfl_up(ia, d, 64), ob = __shfl_up(ib, d, 64);
+    if (lane >= d) { ia += oa; ib += ob; }
+  }
+  if (lane == 63) { s[wave][0] = ia; s[wave][1] = ib; }
+  __syncthreads();
+  int ba = 0, bb = 0;
+  tot_a = 0; tot_b = 0;
+  for (int w = 0; w < 16; w++) {
+    if (w < wave) { ba += s[w][0]; bb += s[w][1]; }
+    tot_a += s[w][0]; tot_b += s[w][1];
+  }
+  __syncthreads();
+  a = ba + ia - a;
+  b = bb + ib - b;
+}
+
+__global__ __launch_bounds__(1024) void match_batch_plan_kernel(const int *__restrict__ pairs, int npairs,
+                                                                const int *__restrict__ counts1,
+                                                                const int *__restrict__ offsets1, int stride1,
+                                                                const int *__restrict__ counts2,
+                                                                const int *__restrict__ offsets2, int stride2,
+                                                                int match_full, int ncu, int *__restrict__ hdr,
+                                                                MbPair *__restrict__ plan)
+{
+  __shared__ int s_scan[16][2];
+  __shared__ long long s_sum[16];
+  const int tid = threadIdx.x;
+  long long rsum = 0;
+  for (int p = tid; p < npairs; p += 1024) {
+    const int f1 = pairs[2 * p], f2 = pairs[2 * p + 1];
+    MbPair P;
+    P.n1 = max(counts1[f1], 0);
+    P.n2 = max(counts2[f2], 0);
+    P.off1 = offsets1 ? offsets1[f1] : f1 * stride1;
+    P.off2 = offsets2 ? offsets2[f2] : f2 * stride2;
+    mb_pair_shape(P.n1, P.n2, match_full, P.ncols, P.ntiles, P.nrb);
+    P.nchunks = 1; P.tpc = 1; P.item0 = 0; P.rb0 = 0; P.pad = 0;
+    plan[p] = P;
+    rsum += P.nrb;
+  }
+  for (int d = 32; d >= 1; d >>= 1) rsum += __shfl_down(rsum, d, 64);
+  if ((tid & 63) == 0) s_sum[tid >> 6] = rsum;
+  __syncthreads();
+  long long R = 0;
+  for (int w = 0; w < 16; w++) R += s_sum[w];
+  const int C = mb_batch_chunks(R, ncu);
+  int carry_items = 0, carry_rb = 0;
+  for (int base = 0; base < npairs; base += 1024) {
+    const int p = base + tid;                                  // the thread that wrote plan[p] above
+    int items = 0, rbs = 0, nch = 1, tpc = 1;
+    if (p < npairs) {
+      mb_pair_chunks(plan[p].ntiles, C, nch, tpc);
+      rbs = plan[p].nrb;
+      items = rbs * nch;
+    }
+    int ti, tr;
+    mb_block_scan2(items, rbs, ti, tr, s_scan);
+    if (p < npairs) {
+      plan[p].nchunks = nch; plan[p].tpc = tpc;
+      plan[p].item0 = carry_items + items; plan[p].rb0 = carry_rb + rbs;
+    }
+    carry_items += ti; carry_rb += tr;
+  }
+  if (tid == 0) {
+    MbPair E = {0, 0, 0, 0, 0, 0, 0, 1, 1, carry_items, carry_rb, 0};
+    plan[npairs] = E;
+    hdr[0] = carry_items; hdr[1] = C; hdr[2] = carry_rb; hdr[3] = 0;
+  }
+}
+
+// The reference's final combination of the eight class summaries of one row (matching.cu:375-390; exact second best
+// under match_exact_top2) and the row's five match fields — what match_merge_kernel does for a row of misift_match.
+// set2: the pair's set-2 records.
+__device__ __forceinline__ void mb_write_row(SiftPointD *o, const float *set2, int exact_top2, const float (&cmax)[8],
+                                             const float (&csec)[8], const int (&cidx)[8])
+{
+  float max_score, sec_score;
+  int index;
+  if (exact_top2) {
+    max_score = cmax[0]; sec_score = csec[0]; index = cidx[0];
+#pragma unroll
+    for (int c = 1; c < 8; c++) top2_merge(max_score, sec_score, index, cmax[c], csec[c], cidx[c]);
+  } else {
+    max_score = cmax[0]; sec_score = csec[0]; index = cidx[0];
+#pragma unroll
+    for (int y = 0; y < 8; y++)
+      if (index != cidx[y]) {
+        if (cmax[y] > max_score) {
+          sec_score = fmaxf(max_score, sec_score);
+          max_score = cmax[y];
+          index = cidx[y];
+        } else if (cmax[y] > sec_score)
+          sec_score = cmax[y];
+      }
+  }
+  o->score = max_score;
+  o->match = index;
+  const float *m2 = set2 + (size_t)(index >= 0 ? index : 0) * (MISIFT_POINT_BYTES / 4);
+  o->match_xpos = index >= 0 ? m2[0] : 0.0f;              // never reads sift2[-1]
+  o->match_ypos = index >= 0 ? m2[1] : 0.0f;
+  o->ambiguity = sec_score / (max_score + 1e-6f);
+}
+
+// the last pair whose prefix value (item0 or rb0) is <= v (pairs without work share their successor's value)
+template <bool ROWBLOCKS> __device__ __forceinline__ int mb_find_pair(const MbPair *__restrict__ plan, int npairs, int v)
+{
+  int lo = 0, hi = npairs - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if ((ROWBLOCKS ? plan[mid].rb0 : plan[mid].item0) <= v) lo = mid;
+    else hi = mid - 1;
+  }
+  return lo;
+}
+
+// recs1 / recs2 may be the same array (frame f against frame f + 1 of one packed batch): the sweep reads descriptors and
+// xpos / ypos only, and the rows written here are the five match fields — never the same bytes.
+__global__ __launch_bounds__(64 * MT_WG_WAVES, 8 / MT_WG_WAVES) void match_batch_kernel(SiftPointD *recs1,
+                                                                                        const float *recs2,
+                                                                                        const int *__restrict__ hdr,
+                                                                                        const MbPair *__restrict__ plan,
+                                                                                        int npairs, int exact_top2,
+                                                                                        float *__restrict__ partial)
+{
+  __shared__ float Bs[2][MT_SUPER * MT_BSTRIDE];
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int half = lane >> 5, col = lane & 31;
+  const int nitems = hdr[0], C = hdr[1];
+  // consecutive items (the row blocks of one pair) go to the workgroups of one XCD: that pair's set 2 stays in its L2
+  for (int it = (int)xcd_remap(blockIdx.x, gridDim.x); it < nitems; it += gridDim.x) {
+    const MbPair P = plan[mb_find_pair<false>(plan, npairs, it)];
+    const int local = it - P.item0, rb = local / P.nchunks, chunk = local - rb * P.nchunks;
+    const int st0 = chunk * P.tpc, st1 = min(st0 + P.tpc, P.ntiles);
+    MatchGeom G;
+    G.row_begin = 0; G.row_count = P.n1; G.n1_total = P.n1;
+    G.n2 = P.n2; G.ncols = P.ncols;
+    G.ntiles = P.ntiles; G.nchunks = P.nchunks; G.tiles_per_chunk = P.tpc;
+    G.tile_base = 0; G.hole_begin = 0x7fffffff; G.hole_len = 0;
+    G.chunk_base = 0; G.nchunks_total = P.nchunks;
+    G.stride2 = MISIFT_POINT_BYTES / 4; G.data_off2 = 16; G.xy_off2 = 0;
+    const SiftPointD *pts1 = recs1 + P.off1;
+    const float *set2 = recs2 + (size_t)P.off2 * (MISIFT_POINT_BYTES / 4);
+    // the sweep of match_kernel (match_sweep.inc): leaves mx / sec / ix
+#include "match_sweep.inc"
+    if (C == 1) {
+      // the item covers all columns: merge the eight classes here, through the first LDS buffer (free after the sweep)
+      float *T = &Bs[0][0];
+      if ((lane & 3) == 0) {
+        const int cls = col >> 2;
+#pragma unroll
+        for (int r = 0; r < 16; r++) {
+          float *q = T + ((wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * half) * 8 + cls) * 3;
+          q[0] = mx[r];
+          q[1] = sec[r];
+          q[2] = __int_as_float(ix[r]);
+        }
+      }
+      __syncthreads();
+      const int row = rb * MT_ROWS_PER_BLOCK + tid;
+      if (tid < MT_ROWS_PER_BLOCK && row < P.n1) {
+        float cmax[8], csec[8];
+        int cidx[8];
+#pragma unroll
+        for (int c = 0; c < 8; c++) {
+          const float *q = T + (tid * 8 + c) * 3;
+          float m = 0.0f, sd = 0.0f;                 // as match_merge_kernel: the one chunk merged into (0, 0, -1)
+          int ixm = -1;
+          top2_merge(m, sd, ixm, q[0], q[1], __float_as_int(q[2]));
+          cmax[c] = m; csec[c] = sd; cidx[c] = ixm;
+        }
+        mb_write_row(recs1 + P.off1 + row, set2, exact_top2, cmax, csec, cidx);
+      }
+    } else if ((lane & 3) == 0) {
+      float *pb = partial + (size_t)it * MB_PART_FLOATS;
+      const int cls = col >> 2;
+#pragma unroll
+      for (int r = 0; r < 16; r++) {
+        const int rl = wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+        if (rb * MT_ROWS_PER_BLOCK + rl < P.n1) {
+          float *q = pb + (rl * 8 + cls) * 3;
+          q[0] = mx[r];
+          q[1] = sec[r];
+          reinterpret_cast<int *>(q)[2] = ix[r];
+        }
+      }
+    }
+    __syncthreads();                 // T / Bs are read no more before the next item's first staging store
+  }
+}
+
+// Chunked calls only: a unit is 32 rows of one row block, eight threads per row (one per class) merging that class over
+// the pair's chunks in ascending order, as match_merge_kernel does.
+__global__ __launch_bounds__(256) void match_batch_merge_kernel(SiftPointD *recs1, const float *recs2,
+                                                                const int *__restrict__ hdr,
+                                                                const MbPair *__restrict__ plan, int npairs,
+                                                                int exact_top2, const float *__restrict__ partial)
+{
+  if (hdr[1] <= 1) return;
+  const int nunits = hdr[2] * (MT_ROWS_PER_BLOCK / 32);
+  for (int u = blockIdx.x; u < nunits; u += gridDim.x) {
+    const int grb = u / (MT_ROWS_PER_BLOCK / 32);
+    const MbPair P = plan[mb_find_pair<true>(plan, npairs, grb)];
+    const int rb = grb - P.rb0;
+    const int rl = (u % (MT_ROWS_PER_BLOCK / 32)) * 32 + (threadIdx.x >> 3), cls = threadIdx.x & 7;
+    const int row = rb * MT_ROWS_PER_BLOCK + rl;
+    const bool live = row < P.n1;
+    float m = 0.0f, sd = 0.0f;
+    int ixm = -1;
+    if (live) {
+      const float *q = partial + (size_t)(P.item0 + rb * P.nchunks) * MB_PART_FLOATS + (rl * 8 + cls) * 3;
+      for (int ch = 0; ch < P.nchunks; ch++, q += MB_PART_FLOATS) top2_merge(m, sd, ixm, q[0], q[1], __float_as_int(q[2]));
+    }
+    float cmax[8], csec[8];
+    int cidx[8];
+#pragma unroll
+    for (int c = 0; c < 8; c++) {
+      cmax[c] = __shfl(m, c, 8);
+      csec[c] = __shfl(sd, c, 8);
+      cidx[c] = __shfl(ixm, c, 8);
+    }
+    if (live && cls == 0)
+      mb_write_row(recs1 + P.off1 + row, recs2 + (size_t)P.off2 * (MISIFT_POINT_BYTES / 4), exact_top2, cmax, csec, cidx);
+  }
+}
+
+// host-only test hook (no device needed): the plan match_batch_plan_kernel makes for pairs of n1[i] x n2[i] records on a
+// chip of num_cus CUs.  plan5[5 i ..]: first item, row blocks, super-tiles, chunks, super-tiles per chunk of pair i.
+extern "C" int misift_test_match_batch_plan(int num_cus, int match_full, int npairs, const int *n1, const int *n2,
+                                            int *plan5, int *nitems, int *chunks, int *partial_items_bound)
+{
+  if (npairs < 0 || (npairs > 0 && (!n1 || !n2 || !plan5)) || !nitems || !chunks || !partial_items_bound)
+    return MISIFT_EINVAL;
+  std::vector<int> ntiles(npairs), nrb(npairs);
+  long long R = 0;
+  for (int p = 0; p < npairs; p++) {
+    int ncols;
+    mb_pair_shape(n1[p] > 0 ? n1[p] : 0, n2[p] > 0 ? n2[p] : 0, match_full, ncols, ntiles[p], nrb[p]);
+    R += nrb[p];
+  }
+  const int C = mb_batch_chunks(R, num_cus);
+  long long items = 0;
+  for (int p = 0; p < npairs; p++) {
+    int nch, tpc;
+    mb_pair_chunks(ntiles[p], C, nch, tpc);
+    int *o = plan5 + 5 * (size_t)p;
+    o[0] = (int)items; o[1] = nrb[p]; o[2] = ntiles[p]; o[3] = nch; o[4] = tpc;
+    items += (long long)nrb[p] * nch;
+  }
+  *nitems = (int)items;
+  *chunks = C;
+  *partial_items_bound = mb_partial_items(num_cus);
+  return MISIFT_OK;
+}
+
+// Enqueue the three launches of misift_match_batch on the context stream.  h_pairs: pinned host memory the plan kernel
+// reads (the caller keeps it unchanged until that kernel has run); d_plan: MB_HDR_INTS + (npairs + 1) MbPair words.
+size_t match_batch_plan_bytes(int npairs) { return sizeof(int) * MB_HDR_INTS + sizeof(MbPair) * ((size_t)npairs + 1); }
+int launch_match_batch(misift_ctx *ctx, int npairs, const int *h_pairs, void *d_plan, SiftPointD *recs1,
+                       const int *counts1, const int *offsets1, int stride1, const SiftPointD *recs2,
+                       const int *counts2, const int *offsets2, int stride2)
+{
+  if (npairs <= 0) return MISIFT_OK;
+  {
+    int rc = misift_ensure_tmp(ctx, (size_t)mb_partial_items(ctx->num_cus) * MB_PART_FLOATS * sizeof(float));
+    if (rc) return rc;
+  }
+  int *hdr = reinterpret_cast<int *>(d_plan);
+  MbPair *plan = reinterpret_cast<MbPair *>(hdr + MB_HDR_INTS);
+  float *partial = reinterpret_cast<float *>(ctx->d_match_tmp);
+  const float *f2 = reinterpret_cast<const float *>(recs2);
+  const int grid = mb_target(ctx->num_cus);
+  {
+    LaunchScope ls(ctx, "match_batch_plan");
+    hipLaunchKernelGGL(match_batch_plan_kernel, dim3(1), dim3(1024), 0, ctx->stream, h_pairs, npairs, counts1, offsets1,
+                       stride1, counts2, offsets2, stride2, ctx->opt.match_full, ctx->num_cus, hdr, plan);
+    int rc = ls.finish();
+    if (rc) return rc;
+  }
+  {
+    LaunchScope ls(ctx, "match_batch_mfma");
+    hipLaunchKernelGGL(match_batch_kernel, dim3(grid), dim3(64 * MT_WG_WAVES), 0, ctx->stream, recs1, f2, hdr, plan,
+                       npairs, ctx->opt.match_exact_top2, partial);
+    int rc = ls.finish();
+    if (rc) return rc;
+  }
+  {
+    LaunchScope ls(ctx, "match_batch_merge");
+    hipLaunchKernelGGL(match_batch_merge_kernel, dim3(grid), dim3(256), 0, ctx->stream, recs1, f2, hdr, plan, npairs,
+                       ctx->opt.match_exact_top2, partial);
+    return ls.finish();
+  }
 }

@@ -122,6 +122,15 @@ struct CtxExtra {
   float taps_table[8 * 12 * 16];
   float k9_blur = -1.0f, k9[9], k5[5];
   bool k5_done = false;
+  // misift_match_batch: pinned copies of the callers' pair lists, a ring of MB_RING slots (a slot is refilled once the call
+  // that last used it has run: mb_done), and the device plan (header + one MbPair per pair)
+  static const int MB_RING = 4;
+  int *mb_pairs[MB_RING] = {};
+  size_t mb_pairs_cap[MB_RING] = {};
+  hipEvent_t mb_done[MB_RING] = {};
+  unsigned mb_next = 0;
+  void *d_mb_plan = nullptr;
+  size_t mb_plan_bytes = 0;
 };
 static CtxExtra *extra(misift_ctx *ctx);
 
@@ -623,6 +632,11 @@ extern "C" void misift_ctx_destroy(misift_ctx *ctx)
   if (x->gev_out) hipEventDestroy(x->gev_out);
   for (auto &p : x->pending) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
   for (auto e : x->pool) hipEventDestroy(e);
+  for (int i = 0; i < CtxExtra::MB_RING; i++) {
+    if (x->mb_done[i]) hipEventDestroy(x->mb_done[i]);
+    if (x->mb_pairs[i]) hipHostFree(x->mb_pairs[i]);
+  }
+  if (x->d_mb_plan) misift_dev_free(x->d_mb_plan);
   if (ctx->d_counters) misift_dev_free(ctx->d_counters);
   if (ctx->h_counters) hipHostFree(ctx->h_counters);
   if (ctx->d_flags) misift_dev_free(ctx->d_flags);
@@ -2029,6 +2043,54 @@ extern "C" int misift_test_match_split(misift_ctx *ctx, void *d_pts1, int n1, co
 extern "C" int misift_match(misift_ctx *ctx, void *d_pts1, int n1, const void *d_pts2, int n2)
 {
   return misift_match_rows(ctx, d_pts1, 0, n1, d_pts2, n2);
+}
+
+// Many (frame of set 1, frame of set 2) pairs of device-resident batches in one stream-ordered call: no host wait and no
+// host read of the counts.  The arguments are checked here, before anything is enqueued.
+extern "C" int misift_match_batch(misift_ctx *ctx, int npairs, const int *pairs, void *d_recs1, int nframes1,
+                                  const int *d_counts1, const int *d_offsets1, int stride1, const void *d_recs2,
+                                  int nframes2, const int *d_counts2, const int *d_offsets2, int stride2)
+{
+  ARG_CHECK(ctx && npairs >= 0);
+  if (npairs == 0) return MISIFT_OK;
+  ARG_CHECK(pairs && d_recs1 && d_recs2 && d_counts1 && d_counts2 && nframes1 > 0 && nframes2 > 0);
+  ARG_CHECK(d_offsets1 || stride1 >= 0);
+  ARG_CHECK(d_offsets2 || stride2 >= 0);
+  std::vector<char> taken((size_t)nframes1, 0);
+  for (int p = 0; p < npairs; p++) {
+    const int f1 = pairs[2 * p], f2 = pairs[2 * p + 1];
+    ARG_CHECK(f1 >= 0 && f1 < nframes1 && f2 >= 0 && f2 < nframes2);
+    ARG_CHECK(!taken[f1]);                                 // a set-1 frame in at most one pair
+    taken[f1] = 1;
+  }
+  RoctxRange range("misift_match_batch");
+  HIP_TRY(hipSetDevice(ctx->device));
+  CtxExtra *x = extra(ctx);
+  const int slot = (int)(x->mb_next++ % CtxExtra::MB_RING);
+  if (x->mb_done[slot]) HIP_TRY(hipEventSynchronize(x->mb_done[slot]));
+  else HIP_TRY(hipEventCreateWithFlags(&x->mb_done[slot], hipEventDisableTiming));
+  const size_t pair_bytes = sizeof(int) * 2 * (size_t)npairs;
+  if (pair_bytes > x->mb_pairs_cap[slot]) {
+    if (x->mb_pairs[slot]) HIP_TRY(hipHostFree(x->mb_pairs[slot]));
+    x->mb_pairs[slot] = nullptr; x->mb_pairs_cap[slot] = 0;
+    HIP_TRY(hipHostMalloc((void **)&x->mb_pairs[slot], pair_bytes, hipHostMallocDefault));
+    x->mb_pairs_cap[slot] = pair_bytes;
+  }
+  memcpy(x->mb_pairs[slot], pairs, pair_bytes);
+  const size_t plan_bytes = match_batch_plan_bytes(npairs);
+  if (plan_bytes > x->mb_plan_bytes) {
+    if (x->d_mb_plan) {
+      HIP_TRY(hipStreamSynchronize(ctx->stream));
+      HIP_TRY(misift_dev_free(x->d_mb_plan));
+    }
+    x->d_mb_plan = nullptr; x->mb_plan_bytes = 0;
+    HIP_TRY(misift_dev_alloc(&x->d_mb_plan, plan_bytes, "match_batch_plan"));
+    x->mb_plan_bytes = plan_bytes;
+  }
+  const int rc = launch_match_batch(ctx, npairs, x->mb_pairs[slot], x->d_mb_plan, (SiftPointD *)d_recs1, d_counts1,
+                                    d_offsets1, stride1, (const SiftPointD *)d_recs2, d_counts2, d_offsets2, stride2);
+  HIP_TRY(hipEventRecord(x->mb_done[slot], ctx->stream));
+  return rc;
 }
 
 // ------------------------------------------------------------------- timing

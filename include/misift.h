@@ -339,6 +339,27 @@ int misift_match(misift_ctx *ctx, void *d_pts1, int n1, const void *d_pts2, int 
  * of set 1 against all of set 2 (each GPU takes one row block). */
 int misift_match_rows(misift_ctx *ctx, void *d_pts1, int row_begin, int row_count,
                       const void *d_pts2, int n2);
+/* Batched pair matching (no reference counterpart; the C++ drop-in headers, cudaSift.h, do not change): for each pair
+ * i, MatchSiftData(frame pairs[2i] of set 1, frame pairs[2i+1] of set 2), stream-ordered on the context stream, with
+ * no host synchronisation and no host read of the counts.
+ * Frame f of a set: its records start at d_recs + d_offsets[f] (d_offsets NULL: at f * stride records), and it holds
+ * max(d_counts[f], 0) of them (-1 = an overflowed frame = no records) — the layout misift_extract_batch_packed_async
+ * leaves, or a padded one (d_offsets NULL, stride = max_pts).  Fills score, ambiguity, match, match_xpos, match_ypos of
+ * set 1's records exactly as misift_match on that pair would, in every misift_options match mode; match indices are
+ * frame-local.  A pair with n1 == 0 or n2 == 0 leaves its set-1 records untouched (matching.cu:1095-1096).
+ *   - The call returns before the GPU work is done.  `pairs` (npairs x 2 ints) is host memory the library copies: the
+ *     caller may reuse it at once.
+ *   - d_recs1 == d_recs2 is allowed (frame f against frame f + 1 of one packed batch): the call reads only descriptors
+ *     and xpos / ypos, and writes only the five match fields.
+ *   - A set-1 frame may appear in at most one pair.  npairs < 0, a frame index outside [0, nframes) of its set or a
+ *     repeated set-1 frame: MISIFT_EINVAL, before anything is enqueued.  npairs == 0: nothing happens.
+ *   - Three launches whatever npairs (plan, sweep, merge of chunked columns); nothing is sized by max_pts.
+ *   - Directly behind misift_extract_batch_packed_async on the same context (K = 1) no synchronisation is needed.  With
+ *     K > 1 batches in flight the extraction does not run on the context stream: order the call behind it with
+ *     misift_ctx_wait_batch / misift_ctx_record_batch (see below). */
+int misift_match_batch(misift_ctx *ctx, int npairs, const int *pairs,
+                       void *d_recs1, int nframes1, const int *d_counts1, const int *d_offsets1, int stride1,
+                       const void *d_recs2, int nframes2, const int *d_counts2, const int *d_offsets2, int stride2);
 
 /* Batches in flight (no reference counterpart: ExtractSift is synchronous, cudaSiftH.cu:72-144).  A context is one
  * in-order pipeline; with K > 1 it owns K child pipelines (own stream, counters, candidate lists, detection staging) and
@@ -350,6 +371,8 @@ int misift_match_rows(misift_ctx *ctx, void *d_pts1, int row_begin, int row_coun
  *     caller's behind the most recent batch), misift_ctx_wait_batch (a stream of the caller's waits for it),
  *     misift_gather_post (marks the most recent batch) or misift_ctx_sync;
  *   - the scratch arena and the output buffers of a call must stay untouched until that batch is done: rotate >= K sets.
+ *   - misift_match_batch (which runs on the context stream) on a batch's packed records: make the context stream wait for
+ *     that batch first (misift_ctx_wait_batch(ctx, <the context's stream>), or an event from misift_ctx_record_batch).
  * K = 1 (default) is the plain in-order context.  Also MISIFT_BATCHES_IN_FLIGHT at context creation.  Changing K drains
  * the context. */
 int misift_ctx_set_batches_in_flight(misift_ctx *ctx, int k);
@@ -481,6 +504,13 @@ int misift_test_match_split(misift_ctx *ctx, void *d_pts1, int n1, const void *d
 
 /* Test-only, host-only (no device needed): the matcher's column-chunk plan for n1 x n2 on a chip of num_cus CUs. */
 int misift_test_match_plan(int num_cus, int n1, int n2, int *nchunks, int *tiles_per_chunk, int *ntiles);
+/* Test-only, host-only: the work list misift_match_batch's plan kernel builds for pairs of n1[i] x n2[i] records on a chip
+ * of num_cus CUs, in the context's match_full mode.  plan5[5i..5i+4] = first work item, 128-row blocks, 64-column
+ * super-tiles, column chunks, super-tiles per chunk of pair i (items of a pair: row block major, chunk minor);
+ * *nitems = items in all; *chunks = the call's chunk count (1: no column split, no partials); *partial_items_bound =
+ * the items the partials buffer holds, which a call with *chunks > 1 never exceeds. */
+int misift_test_match_batch_plan(int num_cus, int match_full, int npairs, const int *n1, const int *n2, int *plan5,
+                                 int *nitems, int *chunks, int *partial_items_bound);
 
 /* Test-only, host-only: how the balanced per-keypoint launches (MISIFT_BALANCE=1) split `nblocks` workgroups among
  * `nframes` frames holding points[f] keypoints: shares[f] = 1 + floor((nblocks - nframes) * points[f] / sum), the formula
