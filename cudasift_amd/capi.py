@@ -96,6 +96,10 @@ SIGNATURES = {
     "misift_test_match_plan": (_i, [_i, _i, _i, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "misift_test_match_batch_plan": (_i, [_i, _i, _i, _vp, _vp, _vp, _ip, _ip, _ip]),
     "misift_match_batch": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i]),
+    "misift_find_homography_batch": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _f, _f, _f, _vp, _vp]),
+    "misift_improve_homography_batch": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _f, _f, _f, _vp, _vp]),
+    "misift_test_libc_rand": (_i, [C.c_uint, _i, _vp]),
+    "misift_test_homography_samples": (_i, [C.c_uint, _i, _i, _vp]),
     "misift_test_frame_shares": (_i, [_i, _i, C.c_void_p, C.c_void_p]),
     "misift_test_set_knob": (_i, [_vp, C.c_char_p, C.c_double]),
     "misift_test_knob_names": (C.c_char_p, []),
@@ -513,6 +517,44 @@ class Context:
         check(lib().misift_match_batch(self.h, len(pairs), pairs.ctypes.data, ptr(recs1), nframes1, ptr(counts1),
                                        ptr(offsets1), stride1, ptr(recs2), nframes2, ptr(counts2), ptr(offsets2),
                                        stride1 if stride2 is None else stride2), "misift_match_batch")
+
+    def find_homography_batch(self, frames, seeds, recs, nframes, counts, offsets=None, stride=0, max_pts=8192,
+                              num_loops=1000, min_score=0.85, max_ambiguity=0.95, thresh=5.0, homography=None,
+                              num_matches=None):
+        """misift_find_homography_batch: FindHomography of frame frames[i] of a device-resident record batch, as after
+        srand(seeds[i]), into slot i of the device buffers `homography` (nsel x 9 floats) and `num_matches` (nsel ints),
+        allocated here when None and returned.  Frames as in match_batch.  Enqueued on the context stream: the results
+        are there once sync() (or later stream work) has run."""
+        def ptr(b):
+            return b.ptr if isinstance(b, DevBuf) else b
+        frames = np.ascontiguousarray(frames, np.int32).reshape(-1)
+        seeds = np.ascontiguousarray(seeds, np.uint32).reshape(-1)
+        assert len(seeds) == len(frames)
+        if homography is None:
+            homography = self.zeros(4 * 9 * max(len(frames), 1))
+        if num_matches is None:
+            num_matches = self.zeros(4 * max(len(frames), 1))
+        check(lib().misift_find_homography_batch(self.h, len(frames), frames.ctypes.data, seeds.ctypes.data, ptr(recs),
+                                                 nframes, ptr(counts), ptr(offsets), stride, max_pts, num_loops,
+                                                 min_score, max_ambiguity, thresh, ptr(homography), ptr(num_matches)),
+              "misift_find_homography_batch")
+        return homography, num_matches
+
+    def improve_homography_batch(self, frames, recs, nframes, counts, homography, offsets=None, stride=0, num_fit=None,
+                                 num_loops=5, min_score=0.0, max_ambiguity=0.80, thresh=3.0):
+        """misift_improve_homography_batch: ImproveHomography of frame frames[i] from the start homography[9i..9i+8]
+        (device, refined in place), writing match_error of the frame's records and num_fit[i] (device, nsel ints,
+        allocated here when None and returned).  Enqueued on the context stream."""
+        def ptr(b):
+            return b.ptr if isinstance(b, DevBuf) else b
+        frames = np.ascontiguousarray(frames, np.int32).reshape(-1)
+        if num_fit is None:
+            num_fit = self.zeros(4 * max(len(frames), 1))
+        check(lib().misift_improve_homography_batch(self.h, len(frames), frames.ctypes.data, ptr(recs), nframes,
+                                                    ptr(counts), ptr(offsets), stride, num_loops, min_score,
+                                                    max_ambiguity, thresh, ptr(homography), ptr(num_fit)),
+              "misift_improve_homography_batch")
+        return num_fit
 
     def match_split(self, pts1, n1, pts2, n2, own_tile_begin, own_tile_end):
         """Test hook: misift_match with the column sweep cut into two launches (the sharded matcher's cut)."""

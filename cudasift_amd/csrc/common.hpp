@@ -517,6 +517,15 @@ size_t match_batch_plan_bytes(int npairs);
 int launch_match_batch(misift_ctx *ctx, int npairs, const int *h_pairs, void *d_plan, SiftPointD *recs1,
                        const int *counts1, const int *offsets1, int stride1, const SiftPointD *recs2,
                        const int *counts2, const int *offsets2, int stride2);   // both launches + merge / the own-shard launch / the rest + merge
+// misift_find_homography_batch / misift_improve_homography_batch on the context stream (homography.hip).  h_frames,
+// h_seeds: pinned host copies of the caller's lists (read by the launches); find takes its temp from misift_ensure_tmp
+size_t find_homography_batch_tmp_bytes(int nsel, int max_pts, int num_loops);
+int launch_find_homography_batch(misift_ctx *ctx, int nsel, const int *h_frames, const unsigned *h_seeds,
+                                 const SiftPointD *recs, const int *counts, const int *offsets, int stride, int max_pts,
+                                 int num_loops, float min_score, float max_ambiguity, float thresh, float *H, int *num);
+int launch_improve_homography_batch(misift_ctx *ctx, int nsel, const int *h_frames, SiftPointD *recs,
+                                    const int *counts, const int *offsets, int stride, int num_loops, float min_score,
+                                    float max_ambiguity, float thresh, float *H, int *num_fit);
 int launch_test_exp2(misift_ctx *ctx, const float *x, float *out, int n);
 int launch_test_points_fn(misift_ctx *ctx, int fn, const float *x, const float *y, float *out, float *out2, int n);
 int launch_selftest(misift_ctx *ctx);

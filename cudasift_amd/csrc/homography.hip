@@ -26,6 +26,7 @@
 #include <string.h>
 #include <vector>
 #include "common.hpp"
+#include "libc_rand.hpp"
 
 namespace {
 
@@ -48,36 +49,9 @@ __global__ __launch_bounds__(1024) void homo_gather_kernel(const float *__restri
                                                              float *__restrict__ coord, int *__restrict__ valid,
                                                              int *__restrict__ num_valid)
 {
-  __shared__ int wave_cnt[16];
-  __shared__ int base_s;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (tid == 0) base_s = 0;
-  __syncthreads();
-  for (int i0 = 0; i0 < npts; i0 += 1024) {
-    const int i = i0 + tid;
-    bool ok = false;
-    if (i < npts) {
-      const float *p = pts + (size_t)i * PT_WORDS;
-      coord[0 * stride + i] = p[OFF_XPOS];
-      coord[1 * stride + i] = p[OFF_YPOS];
-      coord[2 * stride + i] = p[OFF_MXPOS];
-      coord[3 * stride + i] = p[OFF_MYPOS];
-      ok = p[OFF_SCORE] > min_score && p[OFF_AMBIG] < max_ambiguity;      // matching.cu:1035
-    }
-    const unsigned long long m = __ballot(ok);
-    if (lane == 0) wave_cnt[wave] = __popcll(m);
-    __syncthreads();
-    int off = base_s;
-    for (int w = 0; w < wave; w++) off += wave_cnt[w];
-    if (ok) valid[off + __popcll(m & ((1ull << lane) - 1ull))] = i;
-    __syncthreads();
-    if (tid == 0) {
-      int s = 0;
-      for (int w = 0; w < 16; w++) s += wave_cnt[w];
-      base_s += s;
-    }
-    __syncthreads();
-  }
+#define HOMO_CORE_GATHER
+#include "homography_core.inc"
+#undef HOMO_CORE_GATHER
   if (tid == 0) *num_valid = base_s;
 }
 
@@ -149,30 +123,9 @@ __global__ __launch_bounds__(64) void homo_solve_kernel(const float *__restrict_
 {
   const int idx = blockIdx.x * 64 + threadIdx.x;
   if (idx >= num_loops) return;
-  float m[8][8], inv[8][8], rhs[8], x[8];
-  int perm[8];
-  for (int i = 0; i < 4; i++) {
-    const int pt = valid[sample[i * num_loops + idx]];
-    const float x1 = coord[0 * stride + pt], y1 = coord[1 * stride + pt];
-    const float x2 = coord[2 * stride + pt], y2 = coord[3 * stride + pt];
-    float *r1 = m[2 * i], *r2 = m[2 * i + 1];
-    r1[0] = x1; r1[1] = y1; r1[2] = 1.0f; r1[3] = 0.0f; r1[4] = 0.0f; r1[5] = 0.0f;
-    r1[6] = -x2 * x1; r1[7] = -x2 * y1;
-    r2[0] = 0.0f; r2[1] = 0.0f; r2[2] = 0.0f; r2[3] = x1; r2[4] = y1; r2[5] = 1.0f;
-    r2[6] = -y2 * x1; r2[7] = -y2 * y1;
-    rhs[2 * i] = x2;
-    rhs[2 * i + 1] = y2;
-  }
-  lu8(m, perm);
-  for (int c = 0; c < 8; c++) {
-    lu8_unit_solve(m, perm, c, x);
-    for (int r = 0; r < 8; r++) inv[r][c] = x[r];
-  }
-  for (int r = 0; r < 8; r++) {
-    float s = 0.0f;
-    for (int k = 0; k < 8; k++) s = fmaf(inv[r][k], rhs[k], s);
-    homo[r * num_loops + idx] = s;
-  }
+#define HOMO_CORE_SOLVE
+#include "homography_core.inc"
+#undef HOMO_CORE_SOLVE
 }
 
 // ---- count: one wavefront per hypothesis ---------------------------------------------------------
@@ -189,13 +142,9 @@ __global__ __launch_bounds__(256) void homo_count_kernel(const float *__restrict
   for (int i = lane; i < npts; i += 64) {
     const float x1 = coord[0 * stride + i], y1 = coord[1 * stride + i];
     const float x2 = coord[2 * stride + i], y2 = coord[3 * stride + i];
-    const float nomx = mul_rz(a[0], x1) + mul_rz(a[1], y1) + a[2];
-    const float nomy = mul_rz(a[3], x1) + mul_rz(a[4], y1) + a[5];
-    const float deno = mul_rz(a[6], x1) + mul_rz(a[7], y1) + 1.0f;
-    const float errx = mul_rz(x2, deno) - nomx;
-    const float erry = mul_rz(y2, deno) - nomy;
-    const float err2 = mul_rz(errx, errx) + mul_rz(erry, erry);
-    cnt += err2 < mul_rz(thresh2, mul_rz(deno, deno)) ? 1 : 0;
+#define HOMO_CORE_INLIER
+#include "homography_core.inc"
+#undef HOMO_CORE_INLIER
   }
   for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
   if (lane == 0) counts[hyp] = cnt;
@@ -205,22 +154,10 @@ __global__ __launch_bounds__(256) void homo_count_kernel(const float *__restrict
 __global__ __launch_bounds__(1024) void homo_pick_kernel(const int *__restrict__ counts, const float *__restrict__ homo,
                                                            int num_loops, float *__restrict__ result)
 {
-  __shared__ unsigned long long best_s[16];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  // key = count in the high word, (INT_MAX - index) in the low word: max key = largest count, smallest index
-  unsigned long long best = 0;
-  for (int i = tid; i < num_loops; i += 1024) {
-    const unsigned long long key = ((unsigned long long)(unsigned)counts[i] << 32) | (unsigned)(0x7fffffff - i);
-    best = key > best ? key : best;
-  }
-  for (int off = 32; off > 0; off >>= 1) {
-    const unsigned long long o = __shfl_xor(best, off, 64);
-    best = o > best ? o : best;
-  }
-  if (lane == 0) best_s[wave] = best;
-  __syncthreads();
+#define HOMO_CORE_PICK
+#include "homography_core.inc"
+#undef HOMO_CORE_PICK
   if (tid == 0) {
-    for (int w = 1; w < 16; w++) best = best_s[w] > best ? best_s[w] : best;
     const int idx = 0x7fffffff - (int)(unsigned)(best & 0xffffffffull);
     for (int k = 0; k < 8; k++) result[k] = homo[k * num_loops + idx];
     reinterpret_cast<int *>(result)[8] = (int)(best >> 32);
@@ -340,98 +277,9 @@ __device__ __forceinline__ double pick8(int k, double v0, double v1, double v2, 
 __global__ __launch_bounds__(64) void improve_homography_kernel(ImproveArgs P, SiftPointD *__restrict__ pts_rw,
                                                                 float *__restrict__ result)
 {
-  __shared__ double s_M[64], s_X[8], s_A[8];
-  const int lane = threadIdx.x;
-  // lane -> accumulator: lanes 0..35 = M[r][c] for r <= c (row-major upper triangle), lanes 36..43 = X[r]
-  int r = 0, c = 0;
-  bool is_m = lane < 36, is_x = lane >= 36 && lane < 44;
-  if (is_m) {
-    int k = lane;
-    for (r = 0; r < 8; r++) {
-      const int len = 8 - r;
-      if (k < len) { c = r + k; break; }
-      k -= len;
-    }
-  } else if (is_x) {
-    r = lane - 36;
-  }
-  if (lane < 8) s_A[lane] = P.a0[lane];
-  __syncthreads();
-  for (int loop = 0; loop < P.num_loops; loop++) {
-    const double A0 = s_A[0], A1 = s_A[1], A2 = s_A[2], A3 = s_A[3], A4 = s_A[4], A5 = s_A[5], A6 = s_A[6], A7 = s_A[7];
-    double acc = 0.0;
-    for (int i = 0; i < P.npts; i++) {
-      const SiftPointD &pt = P.pts[i];
-      const float x = pt.xpos, y = pt.ypos, mx = pt.match_xpos, my = pt.match_ypos;
-      if (pt.score < P.min_score || pt.ambiguity > P.max_ambiguity) continue;
-      const float den = A6 * x + A7 * y + 1.0f;
-      const float dx = (A0 * x + A1 * y + A2) / den - mx;
-      const float dy = (A3 * x + A4 * y + A5) / den - my;
-      const float err = dx * dx + dy * dy;
-      const float wei = (err < P.limit ? 1.0f : 0.0f);
-      const double xd = x, yd = y;
-      const double p6 = -x * mx, p7 = -y * mx, q6 = -x * my, q7 = -y * my;      // float products, then widened
-      // Y1 = (x, y, 1, 0, 0, 0, p6, p7), Y2 = (0, 0, 0, x, y, 1, q6, q7)
-      const double y1r = pick8(r, xd, yd, 1.0, 0.0, 0.0, 0.0, p6, p7), y2r = pick8(r, 0.0, 0.0, 0.0, xd, yd, 1.0, q6, q7);
-      if (is_m) {
-        const double y1c = pick8(c, xd, yd, 1.0, 0.0, 0.0, 0.0, p6, p7), y2c = pick8(c, 0.0, 0.0, 0.0, xd, yd, 1.0, q6, q7);
-        acc += (y1c * y1r * wei);
-        acc += (y2c * y2r * wei);
-      } else if (is_x) {
-        acc += y1r * mx * wei;
-        acc += y2r * my * wei;
-      }
-    }
-    if (is_m) { s_M[r * 8 + c] = acc; s_M[c * 8 + r] = acc; }
-    if (is_x) s_X[r] = acc;
-    __syncthreads();
-    if (lane == 0) {                                    // cv::solve(M, X, A, DECOMP_CHOLESKY), geomFuncs.cpp:55
-      double L[64], B[8];
-      for (int k = 0; k < 64; k++) L[k] = s_M[k];
-      for (int k = 0; k < 8; k++) B[k] = s_X[k];
-      bool ok = true;
-      for (int i = 0; i < 8 && ok; i++)
-        for (int j = 0; j <= i; j++) {
-          double s = L[i * 8 + j];
-          for (int k = 0; k < j; k++) s -= L[i * 8 + k] * L[j * 8 + k];
-          if (i == j) {
-            if (!(s > 0)) { ok = false; break; }
-            L[i * 8 + i] = sqrt(s);
-          } else {
-            L[i * 8 + j] = s / L[j * 8 + j];
-          }
-        }
-      if (ok) {
-        for (int i = 0; i < 8; i++) {
-          double s = B[i];
-          for (int k = 0; k < i; k++) s -= L[i * 8 + k] * B[k];
-          B[i] = s / L[i * 8 + i];
-        }
-        for (int i = 7; i >= 0; i--) {
-          double s = B[i];
-          for (int k = i + 1; k < 8; k++) s -= L[k * 8 + i] * B[k];
-          B[i] = s / L[i * 8 + i];
-        }
-        for (int k = 0; k < 8; k++) s_A[k] = B[k];
-      } else {
-        for (int k = 0; k < 8; k++) s_A[k] = 0.0;       // cv::solve zeroes the solution when the factorisation fails
-      }
-    }
-    __syncthreads();
-  }
-  const double A0 = s_A[0], A1 = s_A[1], A2 = s_A[2], A3 = s_A[3], A4 = s_A[4], A5 = s_A[5], A6 = s_A[6], A7 = s_A[7];
-  int numfit = 0;
-  for (int i = lane; i < P.npts; i += 64) {
-    SiftPointD &pt = pts_rw[i];
-    const float x = pt.xpos, y = pt.ypos;
-    const float den = A6 * x + A7 * y + 1.0;
-    const float dx = (A0 * x + A1 * y + A2) / den - pt.match_xpos;
-    const float dy = (A3 * x + A4 * y + A5) / den - pt.match_ypos;
-    const float err = dx * dx + dy * dy;
-    if (err < P.limit) numfit++;
-    pt.match_error = sqrtf(err);
-  }
-  for (int m = 32; m > 0; m >>= 1) numfit += __shfl_xor(numfit, m, 64);
+#define HOMO_CORE_IMPROVE
+#include "homography_core.inc"
+#undef HOMO_CORE_IMPROVE
   if (lane < 8) result[lane] = (float)s_A[lane];
   if (lane == 0) {
     result[8] = 1.0f;
@@ -470,5 +318,305 @@ extern "C" int misift_improve_homography(misift_ctx *ctx, void *d_pts, int npts,
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   memcpy(homography, h, 9 * sizeof(float));
   memcpy(num_fit, &h[9], sizeof(int));
+  return MISIFT_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// Batches: misift_find_homography_batch / misift_improve_homography_batch.  Entry e works on frame frames[e] of a
+// device-resident record batch (counts and offsets read on the device) and writes result slot e; no host round trip.
+// Find, four launches whatever the number of entries (L = num_loops rounded up to 16):
+//   gather  one 1024-thread workgroup per entry: the gather of homo_gather_kernel into the entry's temp, then wave 0 draws
+//           the entry's L x 4 sample positions from libc rand() restated on the device (libc_rand.hpp), seeded with
+//           seeds[e]: the same draws as srand(seeds[e]) followed by the single call.  Entries with fewer than 8 records,
+//           fewer than 8 valid points, or more than max_pts records are marked done here.
+//   solve   one lane per (entry, hypothesis): the single call's solve; also zeroes the entry's counts.
+//   count   the hot path: one 64-lane workgroup per (entry, 64 hypotheses, 512-point chunk).  The chunk's coordinates
+//           are staged once in LDS and read by broadcast; each lane holds one hypothesis in registers and tests every
+//           point of the chunk with the single call's inlier test, then adds its count atomically (an integer sum, so
+//           the order of the chunks does not matter).
+//   pick    one 1024-thread workgroup per entry: the single call's pick -> H (H[8] = 1) and the count; identity H and
+//           0 (or -1 over max_pts) for the entries the gather marked done.
+// Improve, one launch: one 64-lane workgroup per entry runs the single call's rounds on the frame's records in place.
+namespace {
+
+constexpr int HB_CHUNK = 512;                  // points per count workgroup (8 KiB of LDS)
+
+// the ring of the device rand(): word `slot` is the register of lane `slot` of a wavefront; all 64 lanes run the draw
+// (every index is wave-uniform)
+struct LibcRandWaveRing {
+  uint32_t w;
+  __device__ uint32_t get(uint32_t slot) const { return (uint32_t)__builtin_amdgcn_readlane((int)w, (int)slot); }
+  __device__ void set(uint32_t slot, uint32_t v) { w = (threadIdx.x & 63) == slot ? v : w; }
+};
+
+struct HbArgs {
+  const SiftPointD *recs;
+  const int *counts, *offsets;                 // device; offsets NULL: frame f at f * stride records
+  long long stride;
+  const int *frames;                           // pinned host copies of the caller's lists
+  const unsigned *seeds;
+  int max_pts, mp16, num_loops;                // mp16 = max_pts rounded up to 16; num_loops rounded up to 16
+  float min_score, max_ambiguity, thresh2;
+  // temp, per entry e: coord[4 x mp16] | valid[mp16] | sample[4 x L] | homo[8 x L] | hcount[L] | meta[2]
+  float *coord;
+  int *valid, *sample;
+  float *homo;
+  int *hcount, *meta;                          // meta[2e] = points to count (0: entry done), meta[2e+1] = its result
+  float *H;                                    // out: nsel x 9
+  int *num;                                    // out: nsel
+};
+
+__device__ __forceinline__ size_t hb_frame_base(const HbArgs &G, int f)
+{
+  return G.offsets ? (size_t)G.offsets[f] : (size_t)f * (size_t)G.stride;
+}
+
+__global__ __launch_bounds__(1024) void homo_batch_gather_kernel(HbArgs G)
+{
+  const int e = blockIdx.x;
+  const int f = G.frames[e];
+  const int n = G.counts[f];
+  if (n < 8 || n > G.max_pts) {                // matching.cu:1016-1017 (count -1 included); over max_pts: -1, nothing read
+    if (threadIdx.x == 0) { G.meta[2 * e] = 0; G.meta[2 * e + 1] = n > G.max_pts ? -1 : 0; }
+    return;
+  }
+  const float *pts = reinterpret_cast<const float *>(G.recs + hb_frame_base(G, f));
+  const int npts = n, stride = G.mp16;
+  const float min_score = G.min_score, max_ambiguity = G.max_ambiguity;
+  float *coord = G.coord + (size_t)e * 4 * G.mp16;
+  int *valid = G.valid + (size_t)e * G.mp16;
+#define HOMO_CORE_GATHER
+#include "homography_core.inc"
+#undef HOMO_CORE_GATHER
+  const int num_valid = base_s;
+  if (num_valid < 8) {
+    if (tid == 0) { G.meta[2 * e] = 0; G.meta[2 * e + 1] = 0; }
+    return;
+  }
+  if (tid < 64) {                              // wave 0: the entry's rand() stream, in the reference's draw order
+    const int L = G.num_loops;
+    int *sample = G.sample + (size_t)e * 4 * L;
+    LibcRand<LibcRandWaveRing> g;
+    g.seed(G.seeds[e]);
+    const FastMod31 fm((uint32_t)num_valid);
+    for (int loop = 0; loop < L; loop++) {
+      int p[4];
+      homography_draw4(g, fm, p);
+      if (tid == 0)
+        for (int k = 0; k < 4; k++) sample[k * L + loop] = p[k];
+    }
+    if (tid == 0) { G.meta[2 * e] = npts; G.meta[2 * e + 1] = 0; }
+  }
+}
+
+__global__ __launch_bounds__(64) void homo_batch_solve_kernel(HbArgs G, int hblocks)
+{
+  const int e = blockIdx.x / hblocks;
+  const int idx = (blockIdx.x % hblocks) * 64 + threadIdx.x;
+  const int num_loops = G.num_loops;
+  if (G.meta[2 * e] == 0 || idx >= num_loops) return;
+  const float *coord = G.coord + (size_t)e * 4 * G.mp16;
+  const int stride = G.mp16;
+  const int *valid = G.valid + (size_t)e * G.mp16;
+  const int *sample = G.sample + (size_t)e * 4 * num_loops;
+  float *homo = G.homo + (size_t)e * 8 * num_loops;
+  G.hcount[(size_t)e * num_loops + idx] = 0;
+#define HOMO_CORE_SOLVE
+#include "homography_core.inc"
+#undef HOMO_CORE_SOLVE
+}
+
+__global__ __launch_bounds__(64) void homo_batch_count_kernel(HbArgs G, int hblocks, int chunks)
+{
+  __shared__ float4 s_pt[HB_CHUNK];
+  const int c = blockIdx.x % chunks, eh = blockIdx.x / chunks;
+  const int e = eh / hblocks, hb = eh % hblocks;
+  const int npts = G.meta[2 * e];
+  const int i0 = c * HB_CHUNK;
+  if (i0 >= npts) return;                      // beyond the frame, or an entry already done (npts 0)
+  const int n = min(HB_CHUNK, npts - i0);
+  const int L = G.num_loops, mp = G.mp16;
+  const float *coord = G.coord + (size_t)e * 4 * mp + i0;
+  for (int i = threadIdx.x; i < n; i += 64)
+    s_pt[i] = make_float4(coord[i], coord[mp + i], coord[2 * mp + i], coord[3 * mp + i]);
+  __syncthreads();
+  const int hyp = hb * 64 + threadIdx.x;
+  if (hyp >= L) return;
+  const float *homo = G.homo + (size_t)e * 8 * L;
+  float a[8];
+  for (int k = 0; k < 8; k++) a[k] = homo[k * L + hyp];
+  const float thresh2 = G.thresh2;
+  int cnt = 0;
+  for (int i = 0; i < n; i++) {
+    const float4 q = s_pt[i];
+    const float x1 = q.x, y1 = q.y, x2 = q.z, y2 = q.w;
+#define HOMO_CORE_INLIER
+#include "homography_core.inc"
+#undef HOMO_CORE_INLIER
+  }
+  atomicAdd(&G.hcount[(size_t)e * L + hyp], cnt);
+}
+
+__global__ __launch_bounds__(1024) void homo_batch_pick_kernel(HbArgs G)
+{
+  const int e = blockIdx.x;
+  float *H = G.H + (size_t)9 * e;
+  if (G.meta[2 * e] == 0) {                    // identity and 0, or -1 for a frame over max_pts
+    if (threadIdx.x < 9) H[threadIdx.x] = threadIdx.x % 4 == 0 ? 1.0f : 0.0f;
+    if (threadIdx.x == 0) G.num[e] = G.meta[2 * e + 1];
+    return;
+  }
+  const int num_loops = G.num_loops;
+  const int *counts = G.hcount + (size_t)e * num_loops;
+#define HOMO_CORE_PICK
+#include "homography_core.inc"
+#undef HOMO_CORE_PICK
+  if (tid == 0) {
+    const int idx = 0x7fffffff - (int)(unsigned)(best & 0xffffffffull);
+    const float *homo = G.homo + (size_t)e * 8 * num_loops;
+    for (int k = 0; k < 8; k++) H[k] = homo[k * num_loops + idx];
+    H[8] = 1.0f;
+    G.num[e] = (int)(best >> 32);
+  }
+}
+
+struct HbImproveArgs {
+  SiftPointD *recs;
+  const int *counts, *offsets;
+  long long stride;
+  const int *frames;                           // pinned host copy
+  int num_loops;
+  float min_score, max_ambiguity, limit;
+  float *H;                                    // in / out: nsel x 9
+  int *num_fit;
+};
+
+__global__ __launch_bounds__(64) void improve_homography_batch_kernel(HbImproveArgs B)
+{
+  const int e = blockIdx.x, f = B.frames[e];
+  const size_t base = B.offsets ? (size_t)B.offsets[f] : (size_t)f * (size_t)B.stride;
+  float *h = B.H + (size_t)9 * e;
+  ImproveArgs P;
+  P.pts = B.recs + base;
+  P.npts = max(B.counts[f], 0);
+  P.num_loops = B.num_loops;
+  P.min_score = B.min_score; P.max_ambiguity = B.max_ambiguity; P.limit = B.limit;
+  for (int i = 0; i < 8; i++) P.a0[i] = h[i] / h[8];           // float division, as the single call does on the host
+  SiftPointD *pts_rw = B.recs + base;
+#define HOMO_CORE_IMPROVE
+#include "homography_core.inc"
+#undef HOMO_CORE_IMPROVE
+  // every lane read h[] before the fragment's first barrier
+  if (lane < 8) h[lane] = (float)s_A[lane];
+  if (lane == 0) {
+    h[8] = 1.0f;
+    B.num_fit[e] = numfit;
+  }
+}
+
+size_t round16(size_t v) { return (v + 15) / 16 * 16; }
+
+}  // namespace
+
+size_t find_homography_batch_tmp_bytes(int nsel, int max_pts, int num_loops)
+{
+  const size_t mp = round16((size_t)max_pts), L = round16((size_t)num_loops);
+  return (size_t)nsel * (sizeof(float) * 4 * mp + sizeof(int) * mp + sizeof(int) * 4 * L + sizeof(float) * 8 * L +
+                         sizeof(int) * L + sizeof(int) * 2);
+}
+
+int launch_find_homography_batch(misift_ctx *ctx, int nsel, const int *h_frames, const unsigned *h_seeds,
+                                 const SiftPointD *recs, const int *counts, const int *offsets, int stride, int max_pts,
+                                 int num_loops, float min_score, float max_ambiguity, float thresh, float *H, int *num)
+{
+  HbArgs G;
+  G.recs = recs; G.counts = counts; G.offsets = offsets; G.stride = stride;
+  G.frames = h_frames; G.seeds = h_seeds;
+  G.max_pts = max_pts;
+  G.mp16 = (int)round16((size_t)max_pts);
+  G.num_loops = (int)round16((size_t)num_loops);
+  G.min_score = min_score; G.max_ambiguity = max_ambiguity; G.thresh2 = thresh * thresh;
+  const size_t mp = (size_t)G.mp16, L = (size_t)G.num_loops, ns = (size_t)nsel;
+  const int hblocks = (G.num_loops + 63) / 64, chunks = (int)((mp + HB_CHUNK - 1) / HB_CHUNK);
+  if ((long long)nsel * hblocks * chunks > 0x7fffffffLL) {
+    misift_set_error("misift_find_homography_batch: %d entries x %d loops x %d points is beyond one launch", nsel,
+                     num_loops, max_pts);
+    return MISIFT_EINVAL;
+  }
+  int rc = misift_ensure_tmp(ctx, find_homography_batch_tmp_bytes(nsel, max_pts, num_loops));
+  if (rc) return rc;
+  G.coord = reinterpret_cast<float *>(ctx->d_match_tmp);
+  G.valid = reinterpret_cast<int *>(G.coord + ns * 4 * mp);
+  G.sample = G.valid + ns * mp;
+  G.homo = reinterpret_cast<float *>(G.sample + ns * 4 * L);
+  G.hcount = reinterpret_cast<int *>(G.homo + ns * 8 * L);
+  G.meta = G.hcount + ns * L;
+  G.H = H; G.num = num;
+  {
+    LaunchScope ls(ctx, "homo_batch_gather");
+    hipLaunchKernelGGL(homo_batch_gather_kernel, dim3(nsel), dim3(1024), 0, ctx->stream, G);
+    rc = ls.finish();
+    if (rc) return rc;
+  }
+  {
+    LaunchScope ls(ctx, "homo_batch_solve");
+    hipLaunchKernelGGL(homo_batch_solve_kernel, dim3(nsel * hblocks), dim3(64), 0, ctx->stream, G, hblocks);
+    rc = ls.finish();
+    if (rc) return rc;
+  }
+  {
+    LaunchScope ls(ctx, "homo_batch_count");
+    hipLaunchKernelGGL(homo_batch_count_kernel, dim3(nsel * hblocks * chunks), dim3(64), 0, ctx->stream, G, hblocks,
+                       chunks);
+    rc = ls.finish();
+    if (rc) return rc;
+  }
+  LaunchScope ls(ctx, "homo_batch_pick");
+  hipLaunchKernelGGL(homo_batch_pick_kernel, dim3(nsel), dim3(1024), 0, ctx->stream, G);
+  return ls.finish();
+}
+
+int launch_improve_homography_batch(misift_ctx *ctx, int nsel, const int *h_frames, SiftPointD *recs,
+                                    const int *counts, const int *offsets, int stride, int num_loops, float min_score,
+                                    float max_ambiguity, float thresh, float *H, int *num_fit)
+{
+  HbImproveArgs B;
+  B.recs = recs; B.counts = counts; B.offsets = offsets; B.stride = stride;
+  B.frames = h_frames;
+  B.num_loops = num_loops;
+  B.min_score = min_score; B.max_ambiguity = max_ambiguity; B.limit = thresh * thresh;
+  B.H = H; B.num_fit = num_fit;
+  LaunchScope ls(ctx, "improve_homography_batch");
+  hipLaunchKernelGGL(improve_homography_batch_kernel, dim3(nsel), dim3(64), 0, ctx->stream, B);
+  return ls.finish();
+}
+
+// Test-only, host-only: the restated libc rand() and the sample draw the batch kernels run (libc_rand.hpp).
+extern "C" int misift_test_libc_rand(unsigned seed, int n, int *out)
+{
+  if (n < 0 || (n > 0 && !out)) {
+    misift_set_error("misift_test_libc_rand: invalid argument");
+    return MISIFT_EINVAL;
+  }
+  LibcRand<LibcRandArrayRing> g;
+  g.seed(seed);
+  for (int i = 0; i < n; i++) out[i] = g.next();
+  return MISIFT_OK;
+}
+
+extern "C" int misift_test_homography_samples(unsigned seed, int num_valid, int num_loops, int *out)
+{
+  if (num_valid < 8 || num_loops < 0 || (num_loops > 0 && !out)) {
+    misift_set_error("misift_test_homography_samples: invalid argument");
+    return MISIFT_EINVAL;
+  }
+  LibcRand<LibcRandArrayRing> g;
+  g.seed(seed);
+  const FastMod31 fm((uint32_t)num_valid);
+  for (int loop = 0; loop < num_loops; loop++) {
+    int p[4];
+    homography_draw4(g, fm, p);
+    for (int k = 0; k < 4; k++) out[4 * loop + k] = p[k];
+  }
   return MISIFT_OK;
 }

@@ -122,8 +122,9 @@ struct CtxExtra {
   float taps_table[8 * 12 * 16];
   float k9_blur = -1.0f, k9[9], k5[5];
   bool k5_done = false;
-  // misift_match_batch: pinned copies of the callers' pair lists, a ring of MB_RING slots (a slot is refilled once the call
-  // that last used it has run: mb_done), and the device plan (header + one MbPair per pair)
+  // misift_match_batch and misift_*_homography_batch: pinned copies of the callers' pair / frame / seed lists, a ring of
+  // MB_RING slots (a slot is refilled once the call that last used it has run: mb_done), and misift_match_batch's device
+  // plan (header + one MbPair per pair)
   static const int MB_RING = 4;
   int *mb_pairs[MB_RING] = {};
   size_t mb_pairs_cap[MB_RING] = {};
@@ -2045,6 +2046,24 @@ extern "C" int misift_match(misift_ctx *ctx, void *d_pts1, int n1, const void *d
   return misift_match_rows(ctx, d_pts1, 0, n1, d_pts2, n2);
 }
 
+// The next slot of the pinned ring for a batch call's host lists, holding at least `bytes`: it waits for the call that
+// last used the slot (mb_done), so the caller may copy its lists in and must record mb_done[*slot] behind its launches.
+static int mb_ring_slot(misift_ctx *ctx, size_t bytes, int *slot_out)
+{
+  CtxExtra *x = extra(ctx);
+  const int slot = (int)(x->mb_next++ % CtxExtra::MB_RING);
+  if (x->mb_done[slot]) HIP_TRY(hipEventSynchronize(x->mb_done[slot]));
+  else HIP_TRY(hipEventCreateWithFlags(&x->mb_done[slot], hipEventDisableTiming));
+  if (bytes > x->mb_pairs_cap[slot]) {
+    if (x->mb_pairs[slot]) HIP_TRY(hipHostFree(x->mb_pairs[slot]));
+    x->mb_pairs[slot] = nullptr; x->mb_pairs_cap[slot] = 0;
+    HIP_TRY(hipHostMalloc((void **)&x->mb_pairs[slot], bytes, hipHostMallocDefault));
+    x->mb_pairs_cap[slot] = bytes;
+  }
+  *slot_out = slot;
+  return MISIFT_OK;
+}
+
 // Many (frame of set 1, frame of set 2) pairs of device-resident batches in one stream-ordered call: no host wait and no
 // host read of the counts.  The arguments are checked here, before anything is enqueued.
 extern "C" int misift_match_batch(misift_ctx *ctx, int npairs, const int *pairs, void *d_recs1, int nframes1,
@@ -2066,16 +2085,10 @@ extern "C" int misift_match_batch(misift_ctx *ctx, int npairs, const int *pairs,
   RoctxRange range("misift_match_batch");
   HIP_TRY(hipSetDevice(ctx->device));
   CtxExtra *x = extra(ctx);
-  const int slot = (int)(x->mb_next++ % CtxExtra::MB_RING);
-  if (x->mb_done[slot]) HIP_TRY(hipEventSynchronize(x->mb_done[slot]));
-  else HIP_TRY(hipEventCreateWithFlags(&x->mb_done[slot], hipEventDisableTiming));
+  int slot;
   const size_t pair_bytes = sizeof(int) * 2 * (size_t)npairs;
-  if (pair_bytes > x->mb_pairs_cap[slot]) {
-    if (x->mb_pairs[slot]) HIP_TRY(hipHostFree(x->mb_pairs[slot]));
-    x->mb_pairs[slot] = nullptr; x->mb_pairs_cap[slot] = 0;
-    HIP_TRY(hipHostMalloc((void **)&x->mb_pairs[slot], pair_bytes, hipHostMallocDefault));
-    x->mb_pairs_cap[slot] = pair_bytes;
-  }
+  int rc = mb_ring_slot(ctx, pair_bytes, &slot);
+  if (rc) return rc;
   memcpy(x->mb_pairs[slot], pairs, pair_bytes);
   const size_t plan_bytes = match_batch_plan_bytes(npairs);
   if (plan_bytes > x->mb_plan_bytes) {
@@ -2087,8 +2100,77 @@ extern "C" int misift_match_batch(misift_ctx *ctx, int npairs, const int *pairs,
     HIP_TRY(misift_dev_alloc(&x->d_mb_plan, plan_bytes, "match_batch_plan"));
     x->mb_plan_bytes = plan_bytes;
   }
-  const int rc = launch_match_batch(ctx, npairs, x->mb_pairs[slot], x->d_mb_plan, (SiftPointD *)d_recs1, d_counts1,
-                                    d_offsets1, stride1, (const SiftPointD *)d_recs2, d_counts2, d_offsets2, stride2);
+  rc = launch_match_batch(ctx, npairs, x->mb_pairs[slot], x->d_mb_plan, (SiftPointD *)d_recs1, d_counts1,
+                          d_offsets1, stride1, (const SiftPointD *)d_recs2, d_counts2, d_offsets2, stride2);
+  HIP_TRY(hipEventRecord(x->mb_done[slot], ctx->stream));
+  return rc;
+}
+
+// Many frames of a device-resident batch through FindHomography / ImproveHomography in one stream-ordered call each: no
+// host wait and no host read of the counts.  The arguments are checked here, before anything is enqueued; the host lists
+// go to a pinned slot of the same ring as misift_match_batch's pairs.
+static int check_homography_frames(int nsel, const int *frames, int nframes)
+{
+  std::vector<char> taken((size_t)nframes, 0);
+  for (int i = 0; i < nsel; i++) {
+    const int f = frames[i];
+    ARG_CHECK(f >= 0 && f < nframes);
+    ARG_CHECK(!taken[f]);                                   // a frame in at most one entry
+    taken[f] = 1;
+  }
+  return MISIFT_OK;
+}
+
+extern "C" int misift_find_homography_batch(misift_ctx *ctx, int nsel, const int *frames, const unsigned *seeds,
+                                            const void *d_recs, int nframes, const int *d_counts, const int *d_offsets,
+                                            int stride, int max_pts, int num_loops, float min_score,
+                                            float max_ambiguity, float thresh, float *d_homography, int *d_num_matches)
+{
+  ARG_CHECK(ctx && nsel >= 0);
+  if (nsel == 0) return MISIFT_OK;
+  ARG_CHECK(frames && seeds && d_recs && d_counts && nframes > 0 && d_homography && d_num_matches);
+  ARG_CHECK(d_offsets || stride >= 0);
+  ARG_CHECK(num_loops >= 1 && max_pts >= 1);
+  int rc = check_homography_frames(nsel, frames, nframes);
+  if (rc) return rc;
+  RoctxRange range("misift_find_homography_batch");
+  HIP_TRY(hipSetDevice(ctx->device));
+  CtxExtra *x = extra(ctx);
+  int slot;
+  rc = mb_ring_slot(ctx, sizeof(int) * 2 * (size_t)nsel, &slot);
+  if (rc) return rc;
+  int *h_frames = x->mb_pairs[slot];
+  unsigned *h_seeds = reinterpret_cast<unsigned *>(h_frames + nsel);
+  memcpy(h_frames, frames, sizeof(int) * (size_t)nsel);
+  memcpy(h_seeds, seeds, sizeof(unsigned) * (size_t)nsel);
+  rc = launch_find_homography_batch(ctx, nsel, h_frames, h_seeds, (const SiftPointD *)d_recs, d_counts, d_offsets,
+                                    stride, max_pts, num_loops, min_score, max_ambiguity, thresh, d_homography,
+                                    d_num_matches);
+  HIP_TRY(hipEventRecord(x->mb_done[slot], ctx->stream));
+  return rc;
+}
+
+extern "C" int misift_improve_homography_batch(misift_ctx *ctx, int nsel, const int *frames, void *d_recs, int nframes,
+                                               const int *d_counts, const int *d_offsets, int stride, int num_loops,
+                                               float min_score, float max_ambiguity, float thresh, float *d_homography,
+                                               int *d_num_fit)
+{
+  ARG_CHECK(ctx && nsel >= 0);
+  if (nsel == 0) return MISIFT_OK;
+  ARG_CHECK(frames && d_recs && d_counts && nframes > 0 && d_homography && d_num_fit);
+  ARG_CHECK(d_offsets || stride >= 0);
+  ARG_CHECK(num_loops >= 0);
+  int rc = check_homography_frames(nsel, frames, nframes);
+  if (rc) return rc;
+  RoctxRange range("misift_improve_homography_batch");
+  HIP_TRY(hipSetDevice(ctx->device));
+  CtxExtra *x = extra(ctx);
+  int slot;
+  rc = mb_ring_slot(ctx, sizeof(int) * (size_t)nsel, &slot);
+  if (rc) return rc;
+  memcpy(x->mb_pairs[slot], frames, sizeof(int) * (size_t)nsel);
+  rc = launch_improve_homography_batch(ctx, nsel, x->mb_pairs[slot], (SiftPointD *)d_recs, d_counts, d_offsets, stride,
+                                       num_loops, min_score, max_ambiguity, thresh, d_homography, d_num_fit);
   HIP_TRY(hipEventRecord(x->mb_done[slot], ctx->stream));
   return rc;
 }

@@ -371,8 +371,9 @@ int misift_match_batch(misift_ctx *ctx, int npairs, const int *pairs,
  *     caller's behind the most recent batch), misift_ctx_wait_batch (a stream of the caller's waits for it),
  *     misift_gather_post (marks the most recent batch) or misift_ctx_sync;
  *   - the scratch arena and the output buffers of a call must stay untouched until that batch is done: rotate >= K sets.
- *   - misift_match_batch (which runs on the context stream) on a batch's packed records: make the context stream wait for
- *     that batch first (misift_ctx_wait_batch(ctx, <the context's stream>), or an event from misift_ctx_record_batch).
+ *   - misift_match_batch, misift_find_homography_batch and misift_improve_homography_batch (which run on the context
+ *     stream) on a batch's packed records: make the context stream wait for that batch first (misift_ctx_wait_batch(ctx,
+ *     <the context's stream>), or an event from misift_ctx_record_batch).
  * K = 1 (default) is the plain in-order context.  Also MISIFT_BATCHES_IN_FLIGHT at context creation.  Changing K drains
  * the context. */
 int misift_ctx_set_batches_in_flight(misift_ctx *ctx, int k);
@@ -486,6 +487,40 @@ int misift_find_homography(misift_ctx *ctx, const void *d_pts, int npts, float *
  * bit-identical to the reference's result. */
 int misift_improve_homography(misift_ctx *ctx, void *d_pts, int npts, float *homography9, int num_loops,
                               float min_score, float max_ambiguity, float thresh, int *num_fit);
+/* Batched homography estimation (no reference counterpart; the C++ drop-in headers, cudaSift.h, do not change): entry i
+ * works on frame frames[i] of a device-resident record batch and writes result slot i, stream-ordered on the context
+ * stream, with no host synchronisation and no host read of the counts.  Together with misift_extract_batch_packed_async
+ * and misift_match_batch a whole batch runs extract -> match -> find -> improve with no host read in between.
+ * Frame f: its records start at d_recs + d_offsets[f] (d_offsets NULL: at f * stride records) and it holds
+ * max(d_counts[f], 0) of them — the layout of misift_match_batch (set 1 of a match batch, match fields filled in).
+ *   - find: d_homography[9i..9i+8] and d_num_matches[i] are bit-identical to srand(seeds[i]) followed by
+ *     misift_find_homography on that frame alone (and to orc_find_homography after the same srand).  Each entry draws
+ *     its samples on the device from its own seed (glibc's rand() restated); the process's rand() state is neither read
+ *     nor changed.  Fewer than 8 records (count -1 included) or fewer than 8 valid points: identity H and 0.  Nothing is
+ *     written into d_recs.
+ *   - max_pts bounds the records of a frame, as in the extraction calls; temp memory is sized from nsel, max_pts and
+ *     num_loops (rounded up to 16) only.  A frame whose device count exceeds max_pts is neither truncated nor read: it
+ *     gets d_num_matches[i] = -1 and the identity H.
+ *   - improve: d_homography (in: the start, e.g. find's result; out: the refined H, [8] = 1), d_num_fit[i] and the
+ *     match_error of every record of the frame are bit-identical to misift_improve_homography(frame start,
+ *     max(count, 0), H_i, ...); H_i is divided by H_i[8] on the device, and a frame with no records gets the zeroed
+ *     solution when num_loops >= 1 (the Cholesky factorisation fails).  Only match_error is written.
+ *   - The calls return before the GPU work is done.  `frames` and `seeds` (nsel entries each) are host memory the library
+ *     copies: the caller may reuse them at once.
+ *   - nsel < 0, a frame index outside [0, nframes), a repeated frame, a NULL output, num_loops < 1 (find) or < 0
+ *     (improve), max_pts < 1: MISIFT_EINVAL, before anything is enqueued.  nsel == 0: nothing happens.
+ *   - Find: four launches whatever nsel (gather + device draw, solve, count, pick); improve: one.
+ *   - Directly behind misift_extract_batch_packed_async / misift_match_batch on the same context (K = 1) no
+ *     synchronisation is needed.  With K > 1 batches in flight the extraction does not run on the context stream: order
+ *     the call behind it with misift_ctx_wait_batch / misift_ctx_record_batch (see below). */
+int misift_find_homography_batch(misift_ctx *ctx, int nsel, const int *frames, const unsigned *seeds,
+                                 const void *d_recs, int nframes, const int *d_counts, const int *d_offsets,
+                                 int stride, int max_pts, int num_loops, float min_score, float max_ambiguity,
+                                 float thresh, float *d_homography /* nsel x 9 */, int *d_num_matches /* nsel */);
+int misift_improve_homography_batch(misift_ctx *ctx, int nsel, const int *frames,
+                                    void *d_recs, int nframes, const int *d_counts, const int *d_offsets, int stride,
+                                    int num_loops, float min_score, float max_ambiguity, float thresh,
+                                    float *d_homography /* in/out, nsel x 9 */, int *d_num_fit /* nsel */);
 
 /* cudaMallocManaged as used by the reference's MANAGEDMEM build flavour (cudaSiftH.cu:239-240): one pointer valid on
  * host and device (SiftData.m_data). */
@@ -511,6 +546,11 @@ int misift_test_match_plan(int num_cus, int n1, int n2, int *nchunks, int *tiles
  * the items the partials buffer holds, which a call with *chunks > 1 never exceeds. */
 int misift_test_match_batch_plan(int num_cus, int match_full, int npairs, const int *n1, const int *n2, int *plan5,
                                  int *nitems, int *chunks, int *partial_items_bound);
+/* Test-only, host-only: the libc rand() misift_find_homography_batch restates on the device: out[k] = the k-th rand()
+ * after srand(seed), k < n.  And the sample positions it draws: out[4 * loop + j] = position j (in the ordered list of
+ * num_valid >= 8 valid points) of hypothesis loop, in the reference's rejection-loop order (matching.cu:1041-1053). */
+int misift_test_libc_rand(unsigned seed, int n, int *out);
+int misift_test_homography_samples(unsigned seed, int num_valid, int num_loops, int *out);
 
 /* Test-only, host-only: how the balanced per-keypoint launches (MISIFT_BALANCE=1) split `nblocks` workgroups among
  * `nframes` frames holding points[f] keypoints: shares[f] = 1 + floor((nblocks - nframes) * points[f] / sum), the formula
