@@ -98,6 +98,7 @@ SIGNATURES = {
     "misift_match_batch": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i]),
     "misift_find_homography_batch": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _f, _f, _f, _vp, _vp]),
     "misift_improve_homography_batch": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _f, _f, _f, _vp, _vp]),
+    "misift_match_guided_batch": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _f, _i, _vp]),
     "misift_test_libc_rand": (_i, [C.c_uint, _i, _vp]),
     "misift_test_homography_samples": (_i, [C.c_uint, _i, _i, _vp]),
     "misift_test_frame_shares": (_i, [_i, _i, C.c_void_p, C.c_void_p]),
@@ -555,6 +556,27 @@ class Context:
                                                     max_ambiguity, thresh, ptr(homography), ptr(num_fit)),
               "misift_improve_homography_batch")
         return num_fit
+
+    def match_guided_batch(self, pairs, recs1, nframes1, counts1, homography, radius, offsets1=None, stride1=0,
+                           recs2=None, nframes2=None, counts2=None, offsets2=None, stride2=None, max_pts=8192,
+                           num_found=None):
+        """misift_match_guided_batch: for each row (f1, f2) of `pairs`, every record of frame f1 of set 1 matched against
+        the records of frame f2 of set 2 within `radius` of its projection through homography[9i..9i+8] (device, npairs
+        x 9 floats, e.g. find_homography_batch's result).  Frames and the set-2 default as in match_batch.  Writes
+        num_found (device, npairs ints, allocated here when None and returned): rows matched, 0 for an empty side, -1
+        over max_pts.  Enqueued on the context stream."""
+        def ptr(b):
+            return b.ptr if isinstance(b, DevBuf) else b
+        if recs2 is None:
+            recs2, nframes2, counts2, offsets2, stride2 = recs1, nframes1, counts1, offsets1, stride1
+        pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        if num_found is None:
+            num_found = self.zeros(4 * max(len(pairs), 1))
+        check(lib().misift_match_guided_batch(self.h, len(pairs), pairs.ctypes.data, ptr(recs1), nframes1, ptr(counts1),
+                                              ptr(offsets1), stride1, ptr(recs2), nframes2, ptr(counts2),
+                                              ptr(offsets2), stride1 if stride2 is None else stride2, ptr(homography),
+                                              radius, max_pts, ptr(num_found)), "misift_match_guided_batch")
+        return num_found
 
     def match_split(self, pts1, n1, pts2, n2, own_tile_begin, own_tile_end):
         """Test hook: misift_match with the column sweep cut into two launches (the sharded matcher's cut)."""

@@ -526,6 +526,15 @@ int launch_find_homography_batch(misift_ctx *ctx, int nsel, const int *h_frames,
 int launch_improve_homography_batch(misift_ctx *ctx, int nsel, const int *h_frames, SiftPointD *recs,
                                     const int *counts, const int *offsets, int stride, int num_loops, float min_score,
                                     float max_ambiguity, float thresh, float *H, int *num_fit);
+// misift_match_guided_batch on the context stream (kernels_guided.hip): bin + match.  h_pairs, h_pair_d (the index of
+// each pair's set-2 frame among the nd distinct ones), h_distinct: pinned host copies (read by the first launch); temp
+// from misift_ensure_tmp, sized from npairs, nd and max_pts only
+size_t match_guided_batch_tmp_bytes(int npairs, int nd, int max_pts);
+int launch_match_guided_batch(misift_ctx *ctx, int npairs, const int *h_pairs, const int *h_pair_d,
+                              const int *h_distinct, int nd, SiftPointD *recs1, const int *counts1,
+                              const int *offsets1, int stride1, const SiftPointD *recs2, const int *counts2,
+                              const int *offsets2, int stride2, const float *H, float radius, int max_pts,
+                              int *num_found);
 int launch_test_exp2(misift_ctx *ctx, const float *x, float *out, int n);
 int launch_test_points_fn(misift_ctx *ctx, int fn, const float *x, const float *y, float *out, float *out2, int n);
 int launch_selftest(misift_ctx *ctx);

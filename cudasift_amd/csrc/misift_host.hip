@@ -2175,6 +2175,52 @@ extern "C" int misift_improve_homography_batch(misift_ctx *ctx, int nsel, const 
   return rc;
 }
 
+// Homography-guided matching of many frame pairs in one stream-ordered call: no host wait and no host read of the counts.
+// The arguments are checked here, before anything is enqueued; the pairs, each pair's index among the distinct set-2
+// frames and those frames go to a pinned slot of the same ring as misift_match_batch's pairs.
+extern "C" int misift_match_guided_batch(misift_ctx *ctx, int npairs, const int *pairs, void *d_recs1, int nframes1,
+                                         const int *d_counts1, const int *d_offsets1, int stride1, const void *d_recs2,
+                                         int nframes2, const int *d_counts2, const int *d_offsets2, int stride2,
+                                         const float *d_homography, float radius, int max_pts, int *d_num_found)
+{
+  ARG_CHECK(ctx && npairs >= 0);
+  if (npairs == 0) return MISIFT_OK;
+  ARG_CHECK(pairs && d_recs1 && d_recs2 && d_counts1 && d_counts2 && d_homography && nframes1 > 0 && nframes2 > 0);
+  ARG_CHECK(d_offsets1 || stride1 >= 0);
+  ARG_CHECK(d_offsets2 || stride2 >= 0);
+  ARG_CHECK(radius > 0.0f);                                // NaN fails too
+  ARG_CHECK(max_pts >= 1);
+  std::vector<char> taken((size_t)nframes1, 0);
+  std::vector<int> dindex((size_t)nframes2, -1), pair_d((size_t)npairs), distinct;
+  for (int p = 0; p < npairs; p++) {
+    const int f1 = pairs[2 * p], f2 = pairs[2 * p + 1];
+    ARG_CHECK(f1 >= 0 && f1 < nframes1 && f2 >= 0 && f2 < nframes2);
+    ARG_CHECK(!taken[f1]);                                 // a set-1 frame in at most one pair
+    taken[f1] = 1;
+    if (dindex[f2] < 0) {
+      dindex[f2] = (int)distinct.size();
+      distinct.push_back(f2);
+    }
+    pair_d[p] = dindex[f2];
+  }
+  const int nd = (int)distinct.size();
+  RoctxRange range("misift_match_guided_batch");
+  HIP_TRY(hipSetDevice(ctx->device));
+  CtxExtra *x = extra(ctx);
+  int slot;
+  int rc = mb_ring_slot(ctx, sizeof(int) * (3 * (size_t)npairs + nd), &slot);
+  if (rc) return rc;
+  int *h_pairs = x->mb_pairs[slot], *h_pair_d = h_pairs + 2 * (size_t)npairs, *h_distinct = h_pair_d + npairs;
+  memcpy(h_pairs, pairs, sizeof(int) * 2 * (size_t)npairs);
+  memcpy(h_pair_d, pair_d.data(), sizeof(int) * (size_t)npairs);
+  memcpy(h_distinct, distinct.data(), sizeof(int) * (size_t)nd);
+  rc = launch_match_guided_batch(ctx, npairs, h_pairs, h_pair_d, h_distinct, nd, (SiftPointD *)d_recs1, d_counts1,
+                                 d_offsets1, stride1, (const SiftPointD *)d_recs2, d_counts2, d_offsets2, stride2,
+                                 d_homography, radius, max_pts, d_num_found);
+  HIP_TRY(hipEventRecord(x->mb_done[slot], ctx->stream));
+  return rc;
+}
+
 // ------------------------------------------------------------------- timing
 extern "C" int misift_timer_start(misift_ctx *ctx)
 {

@@ -371,9 +371,9 @@ int misift_match_batch(misift_ctx *ctx, int npairs, const int *pairs,
  *     caller's behind the most recent batch), misift_ctx_wait_batch (a stream of the caller's waits for it),
  *     misift_gather_post (marks the most recent batch) or misift_ctx_sync;
  *   - the scratch arena and the output buffers of a call must stay untouched until that batch is done: rotate >= K sets.
- *   - misift_match_batch, misift_find_homography_batch and misift_improve_homography_batch (which run on the context
- *     stream) on a batch's packed records: make the context stream wait for that batch first (misift_ctx_wait_batch(ctx,
- *     <the context's stream>), or an event from misift_ctx_record_batch).
+ *   - misift_match_batch, misift_find_homography_batch, misift_improve_homography_batch and misift_match_guided_batch
+ *     (which run on the context stream) on a batch's packed records: make the context stream wait for that batch first
+ *     (misift_ctx_wait_batch(ctx, <the context's stream>), or an event from misift_ctx_record_batch).
  * K = 1 (default) is the plain in-order context.  Also MISIFT_BATCHES_IN_FLIGHT at context creation.  Changing K drains
  * the context. */
 int misift_ctx_set_batches_in_flight(misift_ctx *ctx, int k);
@@ -521,6 +521,40 @@ int misift_improve_homography_batch(misift_ctx *ctx, int nsel, const int *frames
                                     void *d_recs, int nframes, const int *d_counts, const int *d_offsets, int stride,
                                     int num_loops, float min_score, float max_ambiguity, float thresh,
                                     float *d_homography /* in/out, nsel x 9 */, int *d_num_fit /* nsel */);
+/* Homography-guided matching (no reference counterpart as an API: MatchAll, mainSift.cpp:95-147, does it as a host
+ * diagnostic; the C++ drop-in headers, cudaSift.h, do not change): for each pair i = (f1, f2) = (pairs[2i], pairs[2i+1]),
+ * every record of frame f1 of set 1 is matched only against the records of frame f2 of set 2 that lie within `radius`
+ * of its projection through d_homography[9i..9i+8] (set-1 positions to set-2 positions; the layout of
+ * misift_find_homography_batch's output when frames[i] is pair i's set-1 frame; all nine entries used as given),
+ * stream-ordered on the context stream, with no host synchronisation and no host read of the counts.
+ * Frames, pairs and layouts as in misift_match_batch: d_offsets or stride, count -1 = no records, a set-1 frame in at
+ * most one pair, a set-2 frame in any number (keyframe mode), d_recs1 == d_recs2 allowed.  With n1 = max(count1[f1], 0)
+ * and n2 = max(count2[f2], 0):
+ *   - n1 > max_pts or n2 > max_pts: set 1 untouched, d_num_found[i] = -1.  n1 == 0 or n2 == 0: untouched, 0.
+ *   - Otherwise every row (x, y) of set 1, in fp32 with every operation rounded (no contraction):
+ *     den = H6*x + H7*y + H8, px = (H0*x + H1*y + H2) / den, py = (H3*x + H4*y + H5) / den; record j of set 2 is a
+ *     candidate iff (px - x2)*(px - x2) + (py - y2)*(py - y2) < radius*radius (rounded to fp32 once).  A non-finite
+ *     projection or position is never a candidate.  Scores are the matcher's k-ordered fmaf chain; the row gets the
+ *     exact top-2 over its candidates as misift_match with match_full = 1, match_exact_top2 = 1 would give it (only
+ *     scores > 0 count, match = the smallest frame-local index that attains the best score, -1 and score 0 when none
+ *     does), whatever the options of the context.  d_num_found[i] = rows with match >= 0 (d_num_found may be NULL).
+ *     radius = +inf with the identity H equals misift_match in that mode, byte for byte.
+ *   - Only score, ambiguity, match, match_xpos and match_ypos of set-1 rows of some pair are written.
+ *   - The call returns before the GPU work is done.  `pairs` (npairs x 2 ints) is host memory the library copies: the
+ *     caller may reuse it at once.
+ *   - npairs < 0, a frame index outside [0, nframes) of its set, a repeated set-1 frame, NULL records, counts or
+ *     d_homography, radius NaN or <= 0, max_pts < 1: MISIFT_EINVAL, before anything is enqueued.  npairs == 0: nothing
+ *     happens.
+ *   - Two launches whatever npairs (bin set 2 into a cell grid, match); temp memory is sized from npairs, the distinct
+ *     set-2 frames and max_pts only, and no descriptor dot product is computed for a non-candidate.
+ *   - Directly behind misift_extract_batch_packed_async / misift_match_batch / misift_find_homography_batch on the same
+ *     context (K = 1) no synchronisation is needed.  With K > 1 batches in flight the extraction does not run on the
+ *     context stream: order the call behind it with misift_ctx_wait_batch / misift_ctx_record_batch (see below). */
+int misift_match_guided_batch(misift_ctx *ctx, int npairs, const int *pairs,
+                              void *d_recs1, int nframes1, const int *d_counts1, const int *d_offsets1, int stride1,
+                              const void *d_recs2, int nframes2, const int *d_counts2, const int *d_offsets2, int stride2,
+                              const float *d_homography /* npairs x 9, device */, float radius, int max_pts,
+                              int *d_num_found /* npairs, device, may be NULL */);
 
 /* cudaMallocManaged as used by the reference's MANAGEDMEM build flavour (cudaSiftH.cu:239-240): one pointer valid on
  * host and device (SiftData.m_data). */
