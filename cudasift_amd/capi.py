@@ -99,6 +99,10 @@ SIGNATURES = {
     "misift_find_homography_batch": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _f, _f, _f, _vp, _vp]),
     "misift_improve_homography_batch": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _f, _f, _f, _vp, _vp]),
     "misift_match_guided_batch": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _f, _i, _vp]),
+    "misift_quantize_batch": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp]),
+    "misift_match_batch_i8": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i]),
+    "misift_test_quantize": (_i, [_vp, C.c_long, _vp]),
+    "misift_test_match_i8_plan": (_i, [_i, _i, _vp, _vp, _vp, _ip, _ip, _ip]),
     "misift_test_libc_rand": (_i, [C.c_uint, _i, _vp]),
     "misift_test_homography_samples": (_i, [C.c_uint, _i, _i, _vp]),
     "misift_test_frame_shares": (_i, [_i, _i, C.c_void_p, C.c_void_p]),
@@ -577,6 +581,34 @@ class Context:
                                               ptr(offsets2), stride1 if stride2 is None else stride2, ptr(homography),
                                               radius, max_pts, ptr(num_found)), "misift_match_guided_batch")
         return num_found
+
+    def quantize_batch(self, recs, nframes, counts, offsets=None, stride=0, q=None):
+        """misift_quantize_batch: the 8-bit descriptors of every record of every frame (frames as in match_batch) into
+        `q` (device, 128 bytes per record index, 16-byte aligned; allocated here for the records of the largest index a
+        frame can reach when None: pass q for packed layouts whose total only the device knows).  Returns q.  Enqueued
+        on the context stream."""
+        def ptr(b):
+            return b.ptr if isinstance(b, DevBuf) else b
+        if q is None:
+            assert isinstance(recs, DevBuf), "pass q when recs is a raw pointer"
+            q = self.zeros(max(128 * (recs.nbytes // 576), 16))
+        check(lib().misift_quantize_batch(self.h, ptr(recs), nframes, ptr(counts), ptr(offsets), stride, ptr(q)),
+              "misift_quantize_batch")
+        return q
+
+    def match_batch_i8(self, pairs, recs1, q1, nframes1, counts1, offsets1=None, stride1=0, recs2=None, q2=None,
+                       nframes2=None, counts2=None, offsets2=None, stride2=None):
+        """misift_match_batch_i8: match_batch on the 8-bit descriptors q1 / q2 (quantize_batch's output for recs1 /
+        recs2) on the int8 matrix cores.  Set 2 defaults to set 1.  Enqueued on the context stream."""
+        def ptr(b):
+            return b.ptr if isinstance(b, DevBuf) else b
+        if recs2 is None:
+            recs2, q2, nframes2, counts2, offsets2, stride2 = recs1, q1, nframes1, counts1, offsets1, stride1
+        pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        check(lib().misift_match_batch_i8(self.h, len(pairs), pairs.ctypes.data, ptr(recs1), ptr(q1), nframes1,
+                                          ptr(counts1), ptr(offsets1), stride1, ptr(recs2), ptr(q2), nframes2,
+                                          ptr(counts2), ptr(offsets2), stride1 if stride2 is None else stride2),
+              "misift_match_batch_i8")
 
     def match_split(self, pts1, n1, pts2, n2, own_tile_begin, own_tile_end):
         """Test hook: misift_match with the column sweep cut into two launches (the sharded matcher's cut)."""

@@ -535,6 +535,16 @@ int launch_match_guided_batch(misift_ctx *ctx, int npairs, const int *h_pairs, c
                               const int *offsets1, int stride1, const SiftPointD *recs2, const int *counts2,
                               const int *offsets2, int stride2, const float *H, float radius, int max_pts,
                               int *num_found);
+// misift_quantize_batch / misift_match_batch_i8 on the context stream (kernels_match_i8.hip).  h_pairs: pinned host copy
+// of the pairs (read by the first launch); d_plan: match_i8_plan_bytes(npairs) bytes of device memory; partials from
+// misift_ensure_tmp, sized from the CU count only
+int launch_quantize_batch(misift_ctx *ctx, const SiftPointD *recs, int nframes, const int *counts, const int *offsets,
+                          int stride, int8_t *q);
+size_t match_i8_plan_bytes(int npairs);
+int launch_match_batch_i8(misift_ctx *ctx, int npairs, const int *h_pairs, void *d_plan, SiftPointD *recs1,
+                          const int8_t *q1, const int *counts1, const int *offsets1, int stride1,
+                          const SiftPointD *recs2, const int8_t *q2, const int *counts2, const int *offsets2,
+                          int stride2);
 int launch_test_exp2(misift_ctx *ctx, const float *x, float *out, int n);
 int launch_test_points_fn(misift_ctx *ctx, int fn, const float *x, const float *y, float *out, float *out2, int n);
 int launch_selftest(misift_ctx *ctx);

@@ -2064,6 +2064,35 @@ static int mb_ring_slot(misift_ctx *ctx, size_t bytes, int *slot_out)
   return MISIFT_OK;
 }
 
+// The device plan of misift_match_batch / misift_match_batch_i8 (grow-only, stream-ordered like the calls that use it).
+static int ensure_mb_plan(misift_ctx *ctx, size_t bytes)
+{
+  CtxExtra *x = extra(ctx);
+  if (bytes > x->mb_plan_bytes) {
+    if (x->d_mb_plan) {
+      HIP_TRY(hipStreamSynchronize(ctx->stream));
+      HIP_TRY(misift_dev_free(x->d_mb_plan));
+    }
+    x->d_mb_plan = nullptr; x->mb_plan_bytes = 0;
+    HIP_TRY(misift_dev_alloc(&x->d_mb_plan, bytes, "match_batch_plan"));
+    x->mb_plan_bytes = bytes;
+  }
+  return MISIFT_OK;
+}
+
+// The pair checks of the batch matchers: indices in range, a set-1 frame in at most one pair.
+static int check_match_pairs(int npairs, const int *pairs, int nframes1, int nframes2)
+{
+  std::vector<char> taken((size_t)nframes1, 0);
+  for (int p = 0; p < npairs; p++) {
+    const int f1 = pairs[2 * p], f2 = pairs[2 * p + 1];
+    ARG_CHECK(f1 >= 0 && f1 < nframes1 && f2 >= 0 && f2 < nframes2);
+    ARG_CHECK(!taken[f1]);                                 // a set-1 frame in at most one pair
+    taken[f1] = 1;
+  }
+  return MISIFT_OK;
+}
+
 // Many (frame of set 1, frame of set 2) pairs of device-resident batches in one stream-ordered call: no host wait and no
 // host read of the counts.  The arguments are checked here, before anything is enqueued.
 extern "C" int misift_match_batch(misift_ctx *ctx, int npairs, const int *pairs, void *d_recs1, int nframes1,
@@ -2075,31 +2104,18 @@ extern "C" int misift_match_batch(misift_ctx *ctx, int npairs, const int *pairs,
   ARG_CHECK(pairs && d_recs1 && d_recs2 && d_counts1 && d_counts2 && nframes1 > 0 && nframes2 > 0);
   ARG_CHECK(d_offsets1 || stride1 >= 0);
   ARG_CHECK(d_offsets2 || stride2 >= 0);
-  std::vector<char> taken((size_t)nframes1, 0);
-  for (int p = 0; p < npairs; p++) {
-    const int f1 = pairs[2 * p], f2 = pairs[2 * p + 1];
-    ARG_CHECK(f1 >= 0 && f1 < nframes1 && f2 >= 0 && f2 < nframes2);
-    ARG_CHECK(!taken[f1]);                                 // a set-1 frame in at most one pair
-    taken[f1] = 1;
-  }
+  int rc = check_match_pairs(npairs, pairs, nframes1, nframes2);
+  if (rc) return rc;
   RoctxRange range("misift_match_batch");
   HIP_TRY(hipSetDevice(ctx->device));
   CtxExtra *x = extra(ctx);
   int slot;
   const size_t pair_bytes = sizeof(int) * 2 * (size_t)npairs;
-  int rc = mb_ring_slot(ctx, pair_bytes, &slot);
+  rc = mb_ring_slot(ctx, pair_bytes, &slot);
   if (rc) return rc;
   memcpy(x->mb_pairs[slot], pairs, pair_bytes);
-  const size_t plan_bytes = match_batch_plan_bytes(npairs);
-  if (plan_bytes > x->mb_plan_bytes) {
-    if (x->d_mb_plan) {
-      HIP_TRY(hipStreamSynchronize(ctx->stream));
-      HIP_TRY(misift_dev_free(x->d_mb_plan));
-    }
-    x->d_mb_plan = nullptr; x->mb_plan_bytes = 0;
-    HIP_TRY(misift_dev_alloc(&x->d_mb_plan, plan_bytes, "match_batch_plan"));
-    x->mb_plan_bytes = plan_bytes;
-  }
+  rc = ensure_mb_plan(ctx, match_batch_plan_bytes(npairs));
+  if (rc) return rc;
   rc = launch_match_batch(ctx, npairs, x->mb_pairs[slot], x->d_mb_plan, (SiftPointD *)d_recs1, d_counts1,
                           d_offsets1, stride1, (const SiftPointD *)d_recs2, d_counts2, d_offsets2, stride2);
   HIP_TRY(hipEventRecord(x->mb_done[slot], ctx->stream));
@@ -2217,6 +2233,49 @@ extern "C" int misift_match_guided_batch(misift_ctx *ctx, int npairs, const int 
   rc = launch_match_guided_batch(ctx, npairs, h_pairs, h_pair_d, h_distinct, nd, (SiftPointD *)d_recs1, d_counts1,
                                  d_offsets1, stride1, (const SiftPointD *)d_recs2, d_counts2, d_offsets2, stride2,
                                  d_homography, radius, max_pts, d_num_found);
+  HIP_TRY(hipEventRecord(x->mb_done[slot], ctx->stream));
+  return rc;
+}
+
+// 8-bit descriptors of every record of a device-resident batch, one stream-ordered launch with the counts on the device.
+extern "C" int misift_quantize_batch(misift_ctx *ctx, const void *d_recs, int nframes, const int *d_counts,
+                                     const int *d_offsets, int stride, int8_t *d_q)
+{
+  ARG_CHECK(ctx && d_recs && d_counts && d_q && nframes >= 0);
+  ARG_CHECK(((uintptr_t)d_q & 15) == 0);
+  ARG_CHECK(d_offsets || stride >= 0);
+  if (nframes == 0) return MISIFT_OK;
+  RoctxRange range("misift_quantize_batch");
+  HIP_TRY(hipSetDevice(ctx->device));
+  return launch_quantize_batch(ctx, (const SiftPointD *)d_recs, nframes, d_counts, d_offsets, stride, d_q);
+}
+
+// misift_match_batch on 8-bit descriptors (int8 matrix cores): the same pairs, layouts, checks and stream semantics.
+extern "C" int misift_match_batch_i8(misift_ctx *ctx, int npairs, const int *pairs, void *d_recs1, const int8_t *d_q1,
+                                     int nframes1, const int *d_counts1, const int *d_offsets1, int stride1,
+                                     const void *d_recs2, const int8_t *d_q2, int nframes2, const int *d_counts2,
+                                     const int *d_offsets2, int stride2)
+{
+  ARG_CHECK(ctx && npairs >= 0);
+  if (npairs == 0) return MISIFT_OK;
+  ARG_CHECK(pairs && d_recs1 && d_recs2 && d_q1 && d_q2 && d_counts1 && d_counts2 && nframes1 > 0 && nframes2 > 0);
+  ARG_CHECK(((uintptr_t)d_q1 & 15) == 0 && ((uintptr_t)d_q2 & 15) == 0);
+  ARG_CHECK(d_offsets1 || stride1 >= 0);
+  ARG_CHECK(d_offsets2 || stride2 >= 0);
+  int rc = check_match_pairs(npairs, pairs, nframes1, nframes2);
+  if (rc) return rc;
+  RoctxRange range("misift_match_batch_i8");
+  HIP_TRY(hipSetDevice(ctx->device));
+  CtxExtra *x = extra(ctx);
+  int slot;
+  const size_t pair_bytes = sizeof(int) * 2 * (size_t)npairs;
+  rc = mb_ring_slot(ctx, pair_bytes, &slot);
+  if (rc) return rc;
+  memcpy(x->mb_pairs[slot], pairs, pair_bytes);
+  rc = ensure_mb_plan(ctx, match_i8_plan_bytes(npairs));
+  if (rc) return rc;
+  rc = launch_match_batch_i8(ctx, npairs, x->mb_pairs[slot], x->d_mb_plan, (SiftPointD *)d_recs1, d_q1, d_counts1,
+                             d_offsets1, stride1, (const SiftPointD *)d_recs2, d_q2, d_counts2, d_offsets2, stride2);
   HIP_TRY(hipEventRecord(x->mb_done[slot], ctx->stream));
   return rc;
 }

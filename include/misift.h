@@ -556,6 +556,44 @@ int misift_match_guided_batch(misift_ctx *ctx, int npairs, const int *pairs,
                               const float *d_homography /* npairs x 9, device */, float radius, int max_pts,
                               int *d_num_found /* npairs, device, may be NULL */);
 
+/* 8-bit descriptors (no reference counterpart; the C++ drop-in headers do not change): for every record r of every frame
+ * of a device-resident batch (frames as in misift_match_batch: d_offsets or stride, max(d_counts[f], 0) records),
+ * d_q[128 r + k] = (int8) clamp(rint(256 * data[k]), 0, 127), r being the record's global index — so d_q mirrors the
+ * record index space and misift_match_batch_i8 takes the same counts, offsets and stride.  rint rounds half to even in
+ * fp32 (256 * d is exact); NaN -> 0, +inf -> 127, negative values -> 0.  No other byte of d_q is written.
+ *   - One launch, stream-ordered on the context stream, with no host read of the counts; the call returns before the
+ *     GPU work is done.
+ *   - NULL d_recs, d_counts or d_q, d_q not 16-byte aligned, nframes < 0, or d_offsets NULL with stride < 0:
+ *     MISIFT_EINVAL, before anything is enqueued.  nframes == 0: nothing happens.
+ *   - Directly behind misift_extract_batch_packed_async on the same context (K = 1) no synchronisation is needed; with
+ *     K > 1 batches in flight order it with misift_ctx_wait_batch / misift_ctx_record_batch (see below). */
+int misift_quantize_batch(misift_ctx *ctx, const void *d_recs, int nframes, const int *d_counts, const int *d_offsets,
+                          int stride, int8_t *d_q /* 128 bytes per record, device, 16-byte aligned */);
+/* Batched pair matching on 8-bit descriptors and the int8 matrix cores (no reference counterpart; opt-in: every other
+ * call keeps its bits).  Pairs, frames, layouts, argument checks and stream semantics are those of misift_match_batch;
+ * d_q1 / d_q2 are the 128-byte descriptors of the records of d_recs1 / d_recs2 at the same record indices (what
+ * misift_quantize_batch writes).  The call reads only q and set 2's xpos / ypos.  For each row i of a pair with n1 > 0
+ * and n2 > 0, against every column j of its set-2 frame (whatever match_full / match_exact_top2 say):
+ *   - S_ij = sum_k q1[i][k] * q2[j][k], exact in int32; only S_ij > 0 counts.  best = the largest, m = the SMALLEST
+ *     frame-local j that attains it, second = the largest over j != m (0 when there is none).
+ *   - score = (float)best * 2^-16 (exact; 0 when no S_ij > 0), ambiguity = ((float)second * 2^-16) / (score + 1e-6f) in
+ *     fp32, match = m or -1, match_xpos / match_ypos = xpos / ypos of set-2 record m, or 0.  For quantised unit
+ *     descriptors score is a cosine on the scale of misift_match's, so the rows feed misift_find_homography_batch as
+ *     they are.
+ *   - Only those five fields of set-1 rows of some pair are written; a pair with an empty side stays untouched.
+ *   - d_recs1 == d_recs2 and d_q1 == d_q2 are allowed.  A set-1 frame may appear in at most one pair, a set-2 frame in
+ *     any number.  `pairs` is host memory the library copies.  The call returns before the GPU work is done.
+ *   - npairs < 0, a frame index outside [0, nframes) of its set, a repeated set-1 frame, a NULL pointer, d_q1 or d_q2
+ *     not 16-byte aligned: MISIFT_EINVAL, before anything is enqueued.  npairs == 0: nothing happens.
+ *   - Three launches whatever npairs (plan, sweep, merge of chunked columns); temp memory is sized from npairs and the
+ *     CU count only, never by max_pts.
+ *   - Ordering behind misift_extract_batch_packed_async / misift_quantize_batch as for misift_match_batch. */
+int misift_match_batch_i8(misift_ctx *ctx, int npairs, const int *pairs,
+                          void *d_recs1, const int8_t *d_q1, int nframes1, const int *d_counts1, const int *d_offsets1,
+                          int stride1,
+                          const void *d_recs2, const int8_t *d_q2, int nframes2, const int *d_counts2,
+                          const int *d_offsets2, int stride2);
+
 /* cudaMallocManaged as used by the reference's MANAGEDMEM build flavour (cudaSiftH.cu:239-240): one pointer valid on
  * host and device (SiftData.m_data). */
 int misift_malloc_managed(size_t bytes, void **out);
@@ -585,6 +623,13 @@ int misift_test_match_batch_plan(int num_cus, int match_full, int npairs, const 
  * num_valid >= 8 valid points) of hypothesis loop, in the reference's rejection-loop order (matching.cu:1041-1053). */
 int misift_test_libc_rand(unsigned seed, int n, int *out);
 int misift_test_homography_samples(unsigned seed, int num_valid, int num_loops, int *out);
+/* Test-only, host-only: misift_quantize_batch's rule on n floats, dst[i] = rule(src[i]).  And the work list
+ * misift_match_batch_i8's plan kernel builds for pairs of n1[i] x n2[i] records on a chip of num_cus CUs: plan5[5i..5i+4] =
+ * first work item, 128-row blocks, 32-column tiles, column chunks, tiles per chunk of pair i; *nitems, *chunks and
+ * *partial_items_bound as for misift_test_match_batch_plan. */
+int misift_test_quantize(const float *src, long n, int8_t *dst);
+int misift_test_match_i8_plan(int num_cus, int npairs, const int *n1, const int *n2, int *plan5, int *nitems,
+                              int *chunks, int *partial_items_bound);
 
 /* Test-only, host-only: how the balanced per-keypoint launches (MISIFT_BALANCE=1) split `nblocks` workgroups among
  * `nframes` frames holding points[f] keypoints: shares[f] = 1 + floor((nblocks - nframes) * points[f] / sum), the formula
