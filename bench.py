@@ -12,6 +12,11 @@ whole BASELINE config 4 job at N = 1) and rotates through them; with N > 1 the v
 batch are gathered on ONE rank over RCCL/xGMI (misift_gather_*; the root rotates with the step by default, --gather-root), pipelined under the following batches.  Per-GPU
 work is fixed as N grows ("weak").  Rank 0 prints ONE JSON line; `value` is whole-job frames/s.
 
+A plain run does only what `value` needs: set-up, the frame generator, the steps in front of the timed window, the K timed
+steps, --dump-outputs, the line.  `--full` adds everything else the line has carried: the matcher leg, the window without
+pre-roll, the other gather root, per-kernel durations and the roofline (rocprofv3 child passes), the single-frame,
+skewed-batch, 1280x960 and PCIe-inclusive side measurements, the self-validation against the oracle and the CPU baseline.
+
 torch is plumbing only (device memory, the frame generator, rendezvous/barrier): all compute AND the data-path
 collectives go through the C-ABI of libmisift.so (cudasift_amd.capi).  The oracle is the checker of the
 self-validation and the thing timed in the `cpu_baseline` leg — never part of the measured path.
@@ -930,6 +935,10 @@ def parse_args():
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the timed path returned for its last step as DIR/<name>.npy "
                          "(dump_outputs): two builds run with the same arguments can then be compared output for output")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side leg (matcher, per-kernel durations and roofline, latency, skewed batch, 1280x960, "
+                         "PCIe, self-validation, CPU baseline, ...); the --no-* switches above act on these.  Without it the run "
+                         "does only what `value` needs")
     ap.add_argument("--preroll-steps", type=int, default=60,
                     help="untimed steps before the warm-up: the shader clock needs ~40 ms of this load to settle (DESIGN.md "
                          "section 5), so that a 20-step timed window measures the same steady state as a 100-step one; the line "
@@ -1001,7 +1010,7 @@ class Bench:
                       file=sys.stderr)
                 sys.exit(5)
         self.orc = None
-        if not args.no_cpu and rank == 0:
+        if args.full and not args.no_cpu and rank == 0:
             from oracle import pyoracle as orc
             self.orc = orc
         self.cfg2 = self.match = self.latency = self.pcie = self.skewed = self.gather_info = self.step_ms = None
@@ -1111,17 +1120,24 @@ class Bench:
         matcher): per-launch durations (a 30-step run under rocprofv3 --kernel-trace, r03) show the VALU-bound kernels
         speeding up over the first ~30 steps (dog_scan 0.69 -> 0.57 ms) while the HBM-bound lowpass_down is flat — the shader
         clock ramps up over ~40 ms of this load.  So: (1) the driver's window as it stands, W + K steps from cold —
-        reported as `no_preroll`; (2) an untimed pre-roll of the same steps, then W + K again — `value`."""
+        reported as `no_preroll` (--full; a plain run runs the same steps untimed, so that the timed window follows the
+        same history and ends on the same batch); (2) an untimed pre-roll of the same steps, then W + K again — `value`."""
         args, np, torch = self.args, self.np, self.torch
         B, world = self.B, self.world
         PRE = self.PRE = max(0, args.preroll_steps)
         k = 0
         if PRE > 0:
-            self.wd.stage("timed window without pre-roll")
-            dt0, _, _, k = self.timed_window(0, args.warmup, args.steps)
-            self.no_preroll = {"value": round(world * B * args.steps / dt0, 1), "ms_per_step": round(1e3 * dt0 / args.steps, 4),
-                               "note": "the same W warm-up + K timed steps measured FIRST, straight after the frame generator, "
-                                       "without the untimed pre-roll (the shader clock is still ramping: DESIGN.md section 5)"}
+            if args.full:
+                self.wd.stage("timed window without pre-roll")
+                dt0, _, _, k = self.timed_window(0, args.warmup, args.steps)
+                self.no_preroll = {"value": round(world * B * args.steps / dt0, 1), "ms_per_step": round(1e3 * dt0 / args.steps, 4),
+                                   "note": "the same W warm-up + K timed steps measured FIRST, straight after the frame generator, "
+                                           "without the untimed pre-roll (the shader clock is still ramping: DESIGN.md section 5)"}
+            else:
+                self.wd.stage("window without pre-roll, untimed")
+                k = args.warmup + args.steps
+                self.pl.run(0, k)
+                self.barrier()
             self.wd.stage("pre-roll")
             self.pl.run(k, PRE)
             k += PRE
@@ -1166,12 +1182,14 @@ class Bench:
                             "p90": round(float(np.percentile(d, 90)), 4), "samples": int(len(d)),
                             "note": "HIP-event interval between the ends of steps k and k+contexts (same stream) / contexts, "
                                     "over the timed, pipelined loop"}
-        # the timed loop's LAST step, kept for the self-validation
+        # the timed loop's LAST step, kept for the self-validation and --dump-outputs
         capi = self.capi
         last_slot, self.last_b0 = self.last_k % pl.NSLOT, (self.last_k % self.NB) * B
         last_cnt = pl.cnts[last_slot].cpu().numpy().copy()
         self.last_counts, self.last_offs = last_cnt[:B], last_cnt[B:]
-        self.last_recs = pl.packed[last_slot][: int(self.last_offs[B]) * 576].cpu().numpy().view(capi.POINT_DTYPE).copy()
+        self.last_recs = None
+        if args.full or args.dump_outputs:
+            self.last_recs = pl.packed[last_slot][: int(self.last_offs[B]) * 576].cpu().numpy().view(capi.POINT_DTYPE).copy()
 
     def leg_other_root(self):
         """N > 1: the same loop with the OTHER gather root (reported beside the headline, never `value`)."""
@@ -1810,9 +1828,12 @@ class Bench:
                           "path": "unfused" if args.unfused else "fused dog+detect",
                           "keypoints_per_frame": round(self.kp_per_frame, 1),
                           "timing_definition": "T2 of BASELINE.md section 2: device-resident end to end, LowPass ... descriptors + "
-                                               "count read-back (T1 and T3 of the same run: `timing_definitions`)",
+                                               "count read-back (T1 and T3 of the same run: `timing_definitions`, --full)",
                           "preroll_steps": self.PRE,
                           "value_without_preroll": self.no_preroll["value"] if self.no_preroll else None},
+               "full": bool(args.full)}
+        if args.full:
+            out.update({
                "timing_definitions": self.timing_definitions(),
                "config2_1280x960": self.cfg2,
                "no_preroll": self.no_preroll,
@@ -1821,19 +1842,23 @@ class Bench:
                               "compare_points: identical keypoint set; position, scale, orientation, sharpness, edgeness "
                               "bit-identical; every descriptor element within 1e-6; no outlier budget)" % (validated - 1))
                if validated else "skipped (--no-cpu)",
-               "roofline": self.roofline, "kernels": self.kernels, "step_ms": self.step_ms, "match": self.match,
-               "cpu_baseline": self.cpu, "pcie_inclusive": self.pcie, "single_frame": self.latency, "skewed_batch": self.skewed,
+               "roofline": self.roofline, "kernels": self.kernels, "match": self.match,
+               "cpu_baseline": self.cpu, "pcie_inclusive": self.pcie, "single_frame": self.latency, "skewed_batch": self.skewed})
+        out.update({
+               "step_ms": self.step_ms,
                "gather": self.gather_info, "rccl_ranks": int(comm.size) if comm else 0,
                "preroll_steps": self.PRE,
                "preroll_note": "untimed steps of the same loop before the W warm-up steps (clock settling, DESIGN.md section 5); "
-                               "the timed region is exactly `steps` steps; `no_preroll` is the same window measured first, without them",
-               "stages_s": {n: t for n, t in self.wd.history if t >= 0.5},
-               "kernels_note": "ms_per_step = dispatch durations from the rocprofv3 kernel trace of a child run (hip_event_ms_per_step: "
-                               "the library's event pairs over 10 more steps of the pipelined loop); dog_scan runs as two launches "
-                               "per step (fine levels on the context stream, the coarse ScaleDowns + coarse levels beside it on a "
-                               "second stream) whose durations overlap — union_ms_per_step is the wall time either was running.  "
-                               "With --contexts > 1 kernels of several batches share the GPU, every duration is stretched by its "
-                               "neighbours and alone_ms_per_step gives the same kernels with one batch at a time on one context"}
+                               "the timed region is exactly `steps` steps; `no_preroll` (--full) is the same window measured first, "
+                               "without them",
+               "stages_s": {n: t for n, t in self.wd.history if t >= 0.5}})
+        if args.full:
+            out["kernels_note"] = ("ms_per_step = dispatch durations from the rocprofv3 kernel trace of a child run (hip_event_ms_per_step: "
+                                   "the library's event pairs over 10 more steps of the pipelined loop); dog_scan runs as two launches "
+                                   "per step (fine levels on the context stream, the coarse ScaleDowns + coarse levels beside it on a "
+                                   "second stream) whose durations overlap — union_ms_per_step is the wall time either was running.  "
+                                   "With --contexts > 1 kernels of several batches share the GPU, every duration is stretched by its "
+                                   "neighbours and alone_ms_per_step gives the same kernels with one batch at a time on one context")
         C.CDLL(None).fflush(None)          # RCCL's version banner sits in the C stdio buffer: get it out first,
         print(json.dumps(out), flush=True)  # the JSON line is the LAST line of stdout
 
@@ -1930,20 +1955,22 @@ def main():
     if args.emulate_ranks > 0:
         return emulate_ranks(args)
     b = Bench(args)
-    b.leg_matcher()               # BASELINE config 5 (its own timed region)
+    if args.full:
+        b.leg_matcher()           # BASELINE config 5 (its own timed region)
     b.setup_inputs()
-    b.leg_timed_loop()            # `value` (+ `no_preroll`)
+    b.leg_timed_loop()            # `value` (+ `no_preroll` with --full)
     if args.dump_outputs and b.rank == 0:
         dump_outputs(args.dump_outputs, b.last_counts, b.last_offs, b.last_recs)
-    b.leg_other_root()            # N > 1: the other gather root
-    b.leg_kernel_events()
-    b.leg_single_frame()          # BASELINE configs 2 and 3
-    b.leg_skewed_batch()
-    b.leg_config2()
-    b.leg_pcie()
-    b.leg_counters_and_trace()    # rocprofv3 child passes (rank 0, N = 1)
-    b.leg_roofline()
-    b.leg_validate_and_cpu()
+    if args.full:
+        b.leg_other_root()        # N > 1: the other gather root
+        b.leg_kernel_events()
+        b.leg_single_frame()      # BASELINE configs 2 and 3
+        b.leg_skewed_batch()
+        b.leg_config2()
+        b.leg_pcie()
+        b.leg_counters_and_trace()    # rocprofv3 child passes (rank 0, N = 1)
+        b.leg_roofline()
+        b.leg_validate_and_cpu()
     b.emit()
     b.close()
 

@@ -216,6 +216,41 @@ def test_under_the_drivers_launcher_a_silent_rank_ends_the_job():
     assert time.time() - t0 < 120
 
 
+def _legs_run(monkeypatch, argv):
+    """main() with a Bench that only records which of its methods were called, in order."""
+    import sys
+    b = _bench()
+    calls = []
+
+    class FakeBench:
+        rank = 0
+        last_counts = last_offs = last_recs = None
+
+        def __init__(self, args):
+            calls.append("__init__")
+
+        def __getattr__(self, name):
+            return lambda: calls.append(name)
+
+    monkeypatch.setattr(b, "Bench", FakeBench)
+    monkeypatch.setattr(b, "dump_outputs", lambda *a: calls.append("dump_outputs"))
+    monkeypatch.delenv("WORLD_SIZE", raising=False)
+    monkeypatch.setattr(sys, "argv", ["bench.py"] + argv)
+    b.main()
+    return calls
+
+
+def test_plain_run_does_only_what_the_headline_needs(monkeypatch):
+    """`--gpus 1 --steps K --warmup W`: inputs, the timed loop, the dump, the line — no side leg; `--full` runs every
+    side leg as before, in the same order around the same timed loop."""
+    plain = _legs_run(monkeypatch, ["--gpus", "1", "--steps", "20", "--warmup", "5", "--dump-outputs", "x"])
+    assert plain == ["__init__", "setup_inputs", "leg_timed_loop", "dump_outputs", "emit", "close"]
+    full = _legs_run(monkeypatch, ["--gpus", "1", "--steps", "20", "--warmup", "5", "--full"])
+    assert full == ["__init__", "leg_matcher", "setup_inputs", "leg_timed_loop", "leg_other_root", "leg_kernel_events",
+                    "leg_single_frame", "leg_skewed_batch", "leg_config2", "leg_pcie", "leg_counters_and_trace",
+                    "leg_roofline", "leg_validate_and_cpu", "emit", "close"]
+
+
 def test_dump_outputs_are_bounded_and_independent_of_record_order(tmp_path, monkeypatch):
     """--dump-outputs: float32 / float64 .npy files within 64 MB; the same fixed sample of frames every time, at most
     DUMP_RECORDS_PER_FRAME records each; a batch whose records sit in another order inside their frames (the library's

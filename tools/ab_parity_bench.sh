@@ -13,7 +13,7 @@ for lib in "$@"; do
 done
 for rep in 1 2; do
   for lib in "$@"; do
-    MISIFT_LIB=$lib timeout 600 python bench.py --no-cpu --no-match --no-pcie --no-latency --no-pmc --steps 100 --warmup 20 > /tmp/ab.json 2>/tmp/ab.err
+    MISIFT_LIB=$lib timeout 600 python bench.py --full --no-cpu --no-match --no-pcie --no-latency --no-pmc --steps 100 --warmup 20 > /tmp/ab.json 2>/tmp/ab.err
     python - "$lib" >> $out <<'PY'
 import json, sys
 try:
