@@ -224,6 +224,19 @@ class DevBuf:
             pass
 
 
+def _dptr(b):
+    """A device pointer argument: a DevBuf's pointer, or a raw pointer (int or None) as given."""
+    return b.ptr if isinstance(b, DevBuf) else b
+
+
+def _set2(set1, set2):
+    """The set-2 arguments of a batch call, both tuples from recs to stride: set 1's when recs2 is None, else set 2's
+    with stride2 defaulting to stride1."""
+    if set2[0] is None:
+        return set1
+    return set2 if set2[-1] is not None else set2[:-1] + set1[-1:]
+
+
 class Context:
     """One per device (+ optional hipStream_t given as an int)."""
 
@@ -514,14 +527,12 @@ class Context:
         set 2, on device buffers (DevBuf or raw device pointers).  Frame f of a set holds max(counts[f], 0) records from
         record offsets[f] (offsets None: f * stride).  Set 2 defaults to set 1 (frame f against frame f + 1 of one
         batch).  Enqueued on the context stream: the results are there once sync() (or later stream work) has run."""
-        def ptr(b):
-            return b.ptr if isinstance(b, DevBuf) else b
-        if recs2 is None:
-            recs2, nframes2, counts2, offsets2, stride2 = recs1, nframes1, counts1, offsets1, stride1
+        recs2, nframes2, counts2, offsets2, stride2 = _set2((recs1, nframes1, counts1, offsets1, stride1),
+                                                            (recs2, nframes2, counts2, offsets2, stride2))
         pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
-        check(lib().misift_match_batch(self.h, len(pairs), pairs.ctypes.data, ptr(recs1), nframes1, ptr(counts1),
-                                       ptr(offsets1), stride1, ptr(recs2), nframes2, ptr(counts2), ptr(offsets2),
-                                       stride1 if stride2 is None else stride2), "misift_match_batch")
+        check(lib().misift_match_batch(self.h, len(pairs), pairs.ctypes.data, _dptr(recs1), nframes1,
+                                       _dptr(counts1), _dptr(offsets1), stride1, _dptr(recs2), nframes2,
+                                       _dptr(counts2), _dptr(offsets2), stride2), "misift_match_batch")
 
     def find_homography_batch(self, frames, seeds, recs, nframes, counts, offsets=None, stride=0, max_pts=8192,
                               num_loops=1000, min_score=0.85, max_ambiguity=0.95, thresh=5.0, homography=None,
@@ -530,8 +541,6 @@ class Context:
         srand(seeds[i]), into slot i of the device buffers `homography` (nsel x 9 floats) and `num_matches` (nsel ints),
         allocated here when None and returned.  Frames as in match_batch.  Enqueued on the context stream: the results
         are there once sync() (or later stream work) has run."""
-        def ptr(b):
-            return b.ptr if isinstance(b, DevBuf) else b
         frames = np.ascontiguousarray(frames, np.int32).reshape(-1)
         seeds = np.ascontiguousarray(seeds, np.uint32).reshape(-1)
         assert len(seeds) == len(frames)
@@ -539,9 +548,10 @@ class Context:
             homography = self.zeros(4 * 9 * max(len(frames), 1))
         if num_matches is None:
             num_matches = self.zeros(4 * max(len(frames), 1))
-        check(lib().misift_find_homography_batch(self.h, len(frames), frames.ctypes.data, seeds.ctypes.data, ptr(recs),
-                                                 nframes, ptr(counts), ptr(offsets), stride, max_pts, num_loops,
-                                                 min_score, max_ambiguity, thresh, ptr(homography), ptr(num_matches)),
+        check(lib().misift_find_homography_batch(self.h, len(frames), frames.ctypes.data, seeds.ctypes.data,
+                                                 _dptr(recs), nframes, _dptr(counts), _dptr(offsets), stride, max_pts,
+                                                 num_loops, min_score, max_ambiguity, thresh, _dptr(homography),
+                                                 _dptr(num_matches)),
               "misift_find_homography_batch")
         return homography, num_matches
 
@@ -550,14 +560,12 @@ class Context:
         """misift_improve_homography_batch: ImproveHomography of frame frames[i] from the start homography[9i..9i+8]
         (device, refined in place), writing match_error of the frame's records and num_fit[i] (device, nsel ints,
         allocated here when None and returned).  Enqueued on the context stream."""
-        def ptr(b):
-            return b.ptr if isinstance(b, DevBuf) else b
         frames = np.ascontiguousarray(frames, np.int32).reshape(-1)
         if num_fit is None:
             num_fit = self.zeros(4 * max(len(frames), 1))
-        check(lib().misift_improve_homography_batch(self.h, len(frames), frames.ctypes.data, ptr(recs), nframes,
-                                                    ptr(counts), ptr(offsets), stride, num_loops, min_score,
-                                                    max_ambiguity, thresh, ptr(homography), ptr(num_fit)),
+        check(lib().misift_improve_homography_batch(self.h, len(frames), frames.ctypes.data, _dptr(recs), nframes,
+                                                    _dptr(counts), _dptr(offsets), stride, num_loops, min_score,
+                                                    max_ambiguity, thresh, _dptr(homography), _dptr(num_fit)),
               "misift_improve_homography_batch")
         return num_fit
 
@@ -569,17 +577,15 @@ class Context:
         x 9 floats, e.g. find_homography_batch's result).  Frames and the set-2 default as in match_batch.  Writes
         num_found (device, npairs ints, allocated here when None and returned): rows matched, 0 for an empty side, -1
         over max_pts.  Enqueued on the context stream."""
-        def ptr(b):
-            return b.ptr if isinstance(b, DevBuf) else b
-        if recs2 is None:
-            recs2, nframes2, counts2, offsets2, stride2 = recs1, nframes1, counts1, offsets1, stride1
+        recs2, nframes2, counts2, offsets2, stride2 = _set2((recs1, nframes1, counts1, offsets1, stride1),
+                                                            (recs2, nframes2, counts2, offsets2, stride2))
         pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
         if num_found is None:
             num_found = self.zeros(4 * max(len(pairs), 1))
-        check(lib().misift_match_guided_batch(self.h, len(pairs), pairs.ctypes.data, ptr(recs1), nframes1, ptr(counts1),
-                                              ptr(offsets1), stride1, ptr(recs2), nframes2, ptr(counts2),
-                                              ptr(offsets2), stride1 if stride2 is None else stride2, ptr(homography),
-                                              radius, max_pts, ptr(num_found)), "misift_match_guided_batch")
+        check(lib().misift_match_guided_batch(self.h, len(pairs), pairs.ctypes.data, _dptr(recs1), nframes1,
+                                              _dptr(counts1), _dptr(offsets1), stride1, _dptr(recs2), nframes2,
+                                              _dptr(counts2), _dptr(offsets2), stride2, _dptr(homography), radius,
+                                              max_pts, _dptr(num_found)), "misift_match_guided_batch")
         return num_found
 
     def quantize_batch(self, recs, nframes, counts, offsets=None, stride=0, q=None):
@@ -587,12 +593,11 @@ class Context:
         `q` (device, 128 bytes per record index, 16-byte aligned; allocated here for the records of the largest index a
         frame can reach when None: pass q for packed layouts whose total only the device knows).  Returns q.  Enqueued
         on the context stream."""
-        def ptr(b):
-            return b.ptr if isinstance(b, DevBuf) else b
         if q is None:
             assert isinstance(recs, DevBuf), "pass q when recs is a raw pointer"
             q = self.zeros(max(128 * (recs.nbytes // 576), 16))
-        check(lib().misift_quantize_batch(self.h, ptr(recs), nframes, ptr(counts), ptr(offsets), stride, ptr(q)),
+        check(lib().misift_quantize_batch(self.h, _dptr(recs), nframes, _dptr(counts), _dptr(offsets), stride,
+                                          _dptr(q)),
               "misift_quantize_batch")
         return q
 
@@ -600,14 +605,12 @@ class Context:
                        nframes2=None, counts2=None, offsets2=None, stride2=None):
         """misift_match_batch_i8: match_batch on the 8-bit descriptors q1 / q2 (quantize_batch's output for recs1 /
         recs2) on the int8 matrix cores.  Set 2 defaults to set 1.  Enqueued on the context stream."""
-        def ptr(b):
-            return b.ptr if isinstance(b, DevBuf) else b
-        if recs2 is None:
-            recs2, q2, nframes2, counts2, offsets2, stride2 = recs1, q1, nframes1, counts1, offsets1, stride1
+        recs2, q2, nframes2, counts2, offsets2, stride2 = _set2((recs1, q1, nframes1, counts1, offsets1, stride1),
+                                                                (recs2, q2, nframes2, counts2, offsets2, stride2))
         pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
-        check(lib().misift_match_batch_i8(self.h, len(pairs), pairs.ctypes.data, ptr(recs1), ptr(q1), nframes1,
-                                          ptr(counts1), ptr(offsets1), stride1, ptr(recs2), ptr(q2), nframes2,
-                                          ptr(counts2), ptr(offsets2), stride1 if stride2 is None else stride2),
+        check(lib().misift_match_batch_i8(self.h, len(pairs), pairs.ctypes.data, _dptr(recs1), _dptr(q1), nframes1,
+                                          _dptr(counts1), _dptr(offsets1), stride1, _dptr(recs2), _dptr(q2), nframes2,
+                                          _dptr(counts2), _dptr(offsets2), stride2),
               "misift_match_batch_i8")
 
     def match_split(self, pts1, n1, pts2, n2, own_tile_begin, own_tile_end):

@@ -40,6 +40,16 @@ struct alignas(16) SiftPointD {   // device view of the 576-byte record
 };
 static_assert(sizeof(SiftPointD) == MISIFT_POINT_BYTES, "record size");
 
+// One set of records of a batch call (misift_match_batch and its kin): frame f holds counts[f] records from record
+// base(f) of recs — offsets[f] when offsets is given, else f * stride.  counts and offsets are device memory.  recs is
+// written only by the calls that write match fields of that set.
+struct BatchLayout {
+  SiftPointD *recs;
+  const int *counts, *offsets;
+  int stride;
+  __host__ __device__ long long base(int f) const { return offsets ? (long long)offsets[f] : (long long)f * stride; }
+};
+
 struct Taps5 { float k[5]; };                    // k[0] = centre tap
 struct LaplaceTaps { float k[NUM_BLURS][5]; };   // per blur scale, k[.][0] = centre
 
@@ -108,6 +118,37 @@ __device__ __forceinline__ unsigned xcd_remap(unsigned b, unsigned nb)
   const unsigned q = nb >> 3, r = nb & 7u, xcd = b & 7u, i = b >> 3;
   const unsigned base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
   return base + i;
+}
+
+// Exclusive scan of N ints per thread over a 1024-thread workgroup: v[k] becomes the sum of v[k] over the threads before
+// this one, tot[k] the workgroup's total.  s: 16 x N ints of LDS.  Every thread of the workgroup calls it.
+template <int N> __device__ __forceinline__ void block_scan(int (&v)[N], int (&tot)[N], int (*s)[N])
+{
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int inc[N], base[N];
+#pragma unroll
+  for (int k = 0; k < N; k++) { inc[k] = v[k]; base[k] = 0; tot[k] = 0; }
+  for (int d = 1; d < 64; d <<= 1) {
+    int o[N];
+#pragma unroll
+    for (int k = 0; k < N; k++) o[k] = __shfl_up(inc[k], d, 64);
+    if (lane >= d)
+#pragma unroll
+      for (int k = 0; k < N; k++) inc[k] += o[k];
+  }
+  if (lane == 63)
+#pragma unroll
+    for (int k = 0; k < N; k++) s[wave][k] = inc[k];
+  __syncthreads();
+  for (int w = 0; w < 16; w++)
+#pragma unroll
+    for (int k = 0; k < N; k++) {
+      if (w < wave) base[k] += s[w][k];
+      tot[k] += s[w][k];
+    }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < N; k++) v[k] = base[k] + inc[k] - v[k];
 }
 
 // The same dot product where the reference writes it as ONE expression k4*c + k3*p1 + ... (LowPassBlock,
@@ -511,40 +552,29 @@ int launch_match_split(misift_ctx *ctx, SiftPointD *pts1, int row_begin, int row
                        const SiftPointD *pts2_own, int own_t0, int own_t1, hipEvent_t rest_ready, int phase,
                        int packed2 = 0);     // packed2: set 2 is an array of MISIFT_MATCH_COLUMN_BYTES match columns, not records
 enum { MATCH_PHASE_ALL = 0, MATCH_PHASE_OWN = 1, MATCH_PHASE_REST = 2 };
-// misift_match_batch: plan + sweep + merge on the context stream.  h_pairs: pinned host copy of the pairs (read by the first
-// launch); d_plan: match_batch_plan_bytes(npairs) bytes of device memory
-size_t match_batch_plan_bytes(int npairs);
-int launch_match_batch(misift_ctx *ctx, int npairs, const int *h_pairs, void *d_plan, SiftPointD *recs1,
-                       const int *counts1, const int *offsets1, int stride1, const SiftPointD *recs2,
-                       const int *counts2, const int *offsets2, int stride2);   // both launches + merge / the own-shard launch / the rest + merge
-// misift_find_homography_batch / misift_improve_homography_batch on the context stream (homography.hip).  h_frames,
-// h_seeds: pinned host copies of the caller's lists (read by the launches); find takes its temp from misift_ensure_tmp
+// The batch calls on the context stream.  h_*: pinned host copies of the caller's lists (read by the launches).
+// misift_match_batch / misift_match_batch_i8 (kernels_match.hip, kernels_match_i8.hip): plan + sweep + merge; d_plan:
+// pair_plan_bytes(npairs) bytes of device memory (pair_plan.hpp); partials from misift_ensure_tmp, sized from the CUs
+int launch_match_batch(misift_ctx *ctx, int npairs, const int *h_pairs, void *d_plan, const BatchLayout &set1,
+                       const BatchLayout &set2);
+int launch_match_batch_i8(misift_ctx *ctx, int npairs, const int *h_pairs, void *d_plan, const BatchLayout &set1,
+                          const int8_t *q1, const BatchLayout &set2, const int8_t *q2);
+int launch_quantize_batch(misift_ctx *ctx, const BatchLayout &set, int nframes, int8_t *q);
+// misift_find_homography_batch / misift_improve_homography_batch (homography.hip); find takes its temp from
+// misift_ensure_tmp
 size_t find_homography_batch_tmp_bytes(int nsel, int max_pts, int num_loops);
 int launch_find_homography_batch(misift_ctx *ctx, int nsel, const int *h_frames, const unsigned *h_seeds,
-                                 const SiftPointD *recs, const int *counts, const int *offsets, int stride, int max_pts,
-                                 int num_loops, float min_score, float max_ambiguity, float thresh, float *H, int *num);
-int launch_improve_homography_batch(misift_ctx *ctx, int nsel, const int *h_frames, SiftPointD *recs,
-                                    const int *counts, const int *offsets, int stride, int num_loops, float min_score,
-                                    float max_ambiguity, float thresh, float *H, int *num_fit);
-// misift_match_guided_batch on the context stream (kernels_guided.hip): bin + match.  h_pairs, h_pair_d (the index of
-// each pair's set-2 frame among the nd distinct ones), h_distinct: pinned host copies (read by the first launch); temp
-// from misift_ensure_tmp, sized from npairs, nd and max_pts only
+                                 const BatchLayout &set, int max_pts, int num_loops, float min_score,
+                                 float max_ambiguity, float thresh, float *H, int *num);
+int launch_improve_homography_batch(misift_ctx *ctx, int nsel, const int *h_frames, const BatchLayout &set,
+                                    int num_loops, float min_score, float max_ambiguity, float thresh, float *H,
+                                    int *num_fit);
+// misift_match_guided_batch (kernels_guided.hip): bin + match.  h_pair_d: the index of each pair's set-2 frame among
+// the nd distinct ones, h_distinct; temp from misift_ensure_tmp, sized from npairs, nd and max_pts only
 size_t match_guided_batch_tmp_bytes(int npairs, int nd, int max_pts);
 int launch_match_guided_batch(misift_ctx *ctx, int npairs, const int *h_pairs, const int *h_pair_d,
-                              const int *h_distinct, int nd, SiftPointD *recs1, const int *counts1,
-                              const int *offsets1, int stride1, const SiftPointD *recs2, const int *counts2,
-                              const int *offsets2, int stride2, const float *H, float radius, int max_pts,
-                              int *num_found);
-// misift_quantize_batch / misift_match_batch_i8 on the context stream (kernels_match_i8.hip).  h_pairs: pinned host copy
-// of the pairs (read by the first launch); d_plan: match_i8_plan_bytes(npairs) bytes of device memory; partials from
-// misift_ensure_tmp, sized from the CU count only
-int launch_quantize_batch(misift_ctx *ctx, const SiftPointD *recs, int nframes, const int *counts, const int *offsets,
-                          int stride, int8_t *q);
-size_t match_i8_plan_bytes(int npairs);
-int launch_match_batch_i8(misift_ctx *ctx, int npairs, const int *h_pairs, void *d_plan, SiftPointD *recs1,
-                          const int8_t *q1, const int *counts1, const int *offsets1, int stride1,
-                          const SiftPointD *recs2, const int8_t *q2, const int *counts2, const int *offsets2,
-                          int stride2);
+                              const int *h_distinct, int nd, const BatchLayout &set1, const BatchLayout &set2,
+                              const float *H, float radius, int max_pts, int *num_found);
 int launch_test_exp2(misift_ctx *ctx, const float *x, float *out, int n);
 int launch_test_points_fn(misift_ctx *ctx, int fn, const float *x, const float *y, float *out, float *out2, int n);
 int launch_selftest(misift_ctx *ctx);

@@ -350,9 +350,7 @@ struct LibcRandWaveRing {
 };
 
 struct HbArgs {
-  const SiftPointD *recs;
-  const int *counts, *offsets;                 // device; offsets NULL: frame f at f * stride records
-  long long stride;
+  BatchLayout set;
   const int *frames;                           // pinned host copies of the caller's lists
   const unsigned *seeds;
   int max_pts, mp16, num_loops;                // mp16 = max_pts rounded up to 16; num_loops rounded up to 16
@@ -366,21 +364,16 @@ struct HbArgs {
   int *num;                                    // out: nsel
 };
 
-__device__ __forceinline__ size_t hb_frame_base(const HbArgs &G, int f)
-{
-  return G.offsets ? (size_t)G.offsets[f] : (size_t)f * (size_t)G.stride;
-}
-
 __global__ __launch_bounds__(1024) void homo_batch_gather_kernel(HbArgs G)
 {
   const int e = blockIdx.x;
   const int f = G.frames[e];
-  const int n = G.counts[f];
+  const int n = G.set.counts[f];
   if (n < 8 || n > G.max_pts) {                // matching.cu:1016-1017 (count -1 included); over max_pts: -1, nothing read
     if (threadIdx.x == 0) { G.meta[2 * e] = 0; G.meta[2 * e + 1] = n > G.max_pts ? -1 : 0; }
     return;
   }
-  const float *pts = reinterpret_cast<const float *>(G.recs + hb_frame_base(G, f));
+  const float *pts = reinterpret_cast<const float *>(G.set.recs + G.set.base(f));
   const int npts = n, stride = G.mp16;
   const float min_score = G.min_score, max_ambiguity = G.max_ambiguity;
   float *coord = G.coord + (size_t)e * 4 * G.mp16;
@@ -481,9 +474,7 @@ __global__ __launch_bounds__(1024) void homo_batch_pick_kernel(HbArgs G)
 }
 
 struct HbImproveArgs {
-  SiftPointD *recs;
-  const int *counts, *offsets;
-  long long stride;
+  BatchLayout set;
   const int *frames;                           // pinned host copy
   int num_loops;
   float min_score, max_ambiguity, limit;
@@ -494,15 +485,15 @@ struct HbImproveArgs {
 __global__ __launch_bounds__(64) void improve_homography_batch_kernel(HbImproveArgs B)
 {
   const int e = blockIdx.x, f = B.frames[e];
-  const size_t base = B.offsets ? (size_t)B.offsets[f] : (size_t)f * (size_t)B.stride;
+  const long long base = B.set.base(f);
   float *h = B.H + (size_t)9 * e;
   ImproveArgs P;
-  P.pts = B.recs + base;
-  P.npts = max(B.counts[f], 0);
+  P.pts = B.set.recs + base;
+  P.npts = max(B.set.counts[f], 0);
   P.num_loops = B.num_loops;
   P.min_score = B.min_score; P.max_ambiguity = B.max_ambiguity; P.limit = B.limit;
   for (int i = 0; i < 8; i++) P.a0[i] = h[i] / h[8];           // float division, as the single call does on the host
-  SiftPointD *pts_rw = B.recs + base;
+  SiftPointD *pts_rw = B.set.recs + base;
 #define HOMO_CORE_IMPROVE
 #include "homography_core.inc"
 #undef HOMO_CORE_IMPROVE
@@ -526,11 +517,11 @@ size_t find_homography_batch_tmp_bytes(int nsel, int max_pts, int num_loops)
 }
 
 int launch_find_homography_batch(misift_ctx *ctx, int nsel, const int *h_frames, const unsigned *h_seeds,
-                                 const SiftPointD *recs, const int *counts, const int *offsets, int stride, int max_pts,
-                                 int num_loops, float min_score, float max_ambiguity, float thresh, float *H, int *num)
+                                 const BatchLayout &set, int max_pts, int num_loops, float min_score,
+                                 float max_ambiguity, float thresh, float *H, int *num)
 {
   HbArgs G;
-  G.recs = recs; G.counts = counts; G.offsets = offsets; G.stride = stride;
+  G.set = set;
   G.frames = h_frames; G.seeds = h_seeds;
   G.max_pts = max_pts;
   G.mp16 = (int)round16((size_t)max_pts);
@@ -576,12 +567,12 @@ int launch_find_homography_batch(misift_ctx *ctx, int nsel, const int *h_frames,
   return ls.finish();
 }
 
-int launch_improve_homography_batch(misift_ctx *ctx, int nsel, const int *h_frames, SiftPointD *recs,
-                                    const int *counts, const int *offsets, int stride, int num_loops, float min_score,
-                                    float max_ambiguity, float thresh, float *H, int *num_fit)
+int launch_improve_homography_batch(misift_ctx *ctx, int nsel, const int *h_frames, const BatchLayout &set,
+                                    int num_loops, float min_score, float max_ambiguity, float thresh, float *H,
+                                    int *num_fit)
 {
   HbImproveArgs B;
-  B.recs = recs; B.counts = counts; B.offsets = offsets; B.stride = stride;
+  B.set = set;
   B.frames = h_frames;
   B.num_loops = num_loops;
   B.min_score = min_score; B.max_ambiguity = max_ambiguity; B.limit = thresh * thresh;

@@ -12,7 +12,7 @@
 //          compact cell-ordered array of (x2, y2, j) and the cells' starts.  Records with a non-finite position are
 //          left out: their gate error is never finite, so they are never candidates.  One extra workgroup reads the
 //          pairs' counts on the device and writes the work list: (pair, 64-row group) items, numbered by an
-//          exclusive prefix sum, as misift_match_batch's plan does, and zeroes (or sets to -1) num_found.
+//          exclusive prefix sum (block_scan), as misift_match_batch's plan does, and zeroes (or sets to -1) num_found.
 //   match  a persistent grid of one-wave workgroups over the items.  Each lane projects one row and walks the entries
 //          of the cells its disc can reach, one entry per step, testing the exact gate.  The passing (row, candidate)
 //          pairs are compacted through a wave prefix sum into an LDS queue; every 64 of them, each lane computes one
@@ -45,10 +45,7 @@ struct GmPair {                  // one per pair, written by the plan workgroup
 };
 
 struct GmArgs {
-  SiftPointD *recs1;
-  const SiftPointD *recs2;
-  const int *counts1, *offsets1, *counts2, *offsets2;   // device; offsets NULL: frame f at f * stride records
-  long long stride1, stride2;
+  BatchLayout set1, set2;
   const int *pairs;              // pinned host: npairs x 2, then pair_d[npairs], then distinct[nd]
   const int *pair_d, *distinct;
   int npairs, nd, max_pts;
@@ -71,53 +68,32 @@ __device__ __forceinline__ int gm_cell(double v, int g)
 
 __device__ __forceinline__ bool gm_finite(float v) { return __builtin_isfinite(v); }
 
-// exclusive scan over a 1024-thread workgroup; *tot = the workgroup's total
-__device__ __forceinline__ int gm_block_scan(int v, int &tot, int *s)
-{
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int inc = v;
-  for (int d = 1; d < 64; d <<= 1) {
-    const int o = __shfl_up(inc, d, 64);
-    if (lane >= d) inc += o;
-  }
-  if (lane == 63) s[wave] = inc;
-  __syncthreads();
-  int base = 0;
-  tot = 0;
-  for (int w = 0; w < 16; w++) {
-    if (w < wave) base += s[w];
-    tot += s[w];
-  }
-  __syncthreads();
-  return base + inc - v;
-}
-
 // The work list: item0[p] = first (pair, 64-row group) item of pair p.  A pair over max_pts on either side gets
 // num_found -1 and no items, a pair with an empty side 0 and no items.
 __device__ void gm_plan(const GmArgs &A)
 {
-  __shared__ int s_scan[16];
+  __shared__ int s_scan[16][1];
   const int tid = threadIdx.x;
   int carry = 0;
   for (int base = 0; base < A.npairs; base += 1024) {
     const int p = base + tid;
-    int items = 0;
+    int items[1] = {0};
     if (p < A.npairs) {
       const int f1 = A.pairs[2 * p], f2 = A.pairs[2 * p + 1];
-      const int n1 = max(A.counts1[f1], 0), n2 = max(A.counts2[f2], 0);
+      const int n1 = max(A.set1.counts[f1], 0), n2 = max(A.set2.counts[f2], 0);
       const bool over = n1 > A.max_pts || n2 > A.max_pts;
-      if (!over && n1 > 0 && n2 > 0) items = (n1 + 63) / 64;
+      if (!over && n1 > 0 && n2 > 0) items[0] = (n1 + 63) / 64;
       GmPair P;
-      P.base1 = A.offsets1 ? (long long)A.offsets1[f1] : (long long)f1 * A.stride1;
+      P.base1 = A.set1.base(f1);
       P.n1 = n1;
       P.d = A.pair_d[p];
       A.pinfo[p] = P;
       if (A.num_found) A.num_found[p] = over ? -1 : 0;
     }
-    int tot;
-    const int ex = gm_block_scan(items, tot, s_scan);
-    if (p < A.npairs) A.item0[p] = carry + ex;
-    carry += tot;
+    int tot[1];
+    block_scan(items, tot, s_scan);
+    if (p < A.npairs) A.item0[p] = carry + items[0];
+    carry += tot[0];
   }
   if (tid == 0) A.item0[A.npairs] = carry;
 }
@@ -130,15 +106,15 @@ __global__ __launch_bounds__(1024) void guided_bin_kernel(GmArgs A)
   }
   __shared__ int s_cnt[GM_GRID * GM_GRID];
   __shared__ float s_red[4][16];
-  __shared__ int s_scan[16];
+  __shared__ int s_scan[16][1];
   __shared__ double s_g[4];
   __shared__ int s_gi[2];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int d = blockIdx.x, f = A.distinct[d];
-  const int n2 = max(A.counts2[f], 0);
+  const int n2 = max(A.set2.counts[f], 0);
   if (n2 == 0 || n2 > A.max_pts) return;            // no pair of this frame has items
-  const long long base2 = A.offsets2 ? (long long)A.offsets2[f] : (long long)f * A.stride2;
-  const SiftPointD *rec = A.recs2 + base2;
+  const long long base2 = A.set2.base(f);
+  const SiftPointD *rec = A.set2.recs + base2;
   // 1. bounding box of the finite positions
   float xmin = __builtin_inff(), ymin = __builtin_inff(), xmax = -__builtin_inff(), ymax = -__builtin_inff();
   for (int j = tid; j < n2; j += 1024) {
@@ -188,20 +164,20 @@ __global__ __launch_bounds__(1024) void guided_bin_kernel(GmArgs A)
   }
   __syncthreads();
   int *starts = A.starts + (size_t)d * GM_STARTS;
-  int v[4], sum = 0;
+  int v[4], run[1] = {0};
   for (int k = 0; k < 4; k++) {
     const int c = 4 * tid + k;
     v[k] = c < ncell ? s_cnt[c] : 0;
-    sum += v[k];
+    run[0] += v[k];
   }
-  int tot;
-  int run = gm_block_scan(sum, tot, s_scan);
+  int tot[1];
+  block_scan(run, tot, s_scan);
   for (int k = 0; k < 4; k++) {
     const int c = 4 * tid + k;
-    if (c < ncell) { starts[c] = run; s_cnt[c] = run; }
-    run += v[k];
+    if (c < ncell) { starts[c] = run[0]; s_cnt[c] = run[0]; }
+    run[0] += v[k];
   }
-  if (tid == 0) starts[ncell] = tot;
+  if (tid == 0) starts[ncell] = tot[0];
   __syncthreads();
   float4 *ent = A.entries + (size_t)d * A.max_pts;
   for (int j = tid; j < n2; j += 1024) {
@@ -240,8 +216,8 @@ __global__ __launch_bounds__(64) void guided_match_kernel(GmArgs A)
     const GmGrid G = A.grid[P.d];
     const int r = (it - A.item0[p]) * 64 + lane;
     const bool active = r < P.n1;
-    SiftPointD *rows = A.recs1 + P.base1 + (it - A.item0[p]) * 64;
-    const SiftPointD *rec2 = A.recs2 + G.base2;
+    SiftPointD *rows = A.set1.recs + P.base1 + (it - A.item0[p]) * 64;
+    const SiftPointD *rec2 = A.set2.recs + G.base2;
     const int *starts = A.starts + (size_t)P.d * GM_STARTS;
     const float4 *ent = A.entries + (size_t)P.d * A.max_pts;
     // projection, in MatchAll's order (mainSift.cpp:109-111), no contraction
@@ -358,17 +334,13 @@ size_t match_guided_batch_tmp_bytes(int npairs, int nd, int max_pts)
 }
 
 int launch_match_guided_batch(misift_ctx *ctx, int npairs, const int *h_pairs, const int *h_pair_d,
-                              const int *h_distinct, int nd, SiftPointD *recs1, const int *counts1,
-                              const int *offsets1, int stride1, const SiftPointD *recs2, const int *counts2,
-                              const int *offsets2, int stride2, const float *H, float radius, int max_pts,
-                              int *num_found)
+                              const int *h_distinct, int nd, const BatchLayout &set1, const BatchLayout &set2,
+                              const float *H, float radius, int max_pts, int *num_found)
 {
   int rc = misift_ensure_tmp(ctx, match_guided_batch_tmp_bytes(npairs, nd, max_pts));
   if (rc) return rc;
   GmArgs A;
-  A.recs1 = recs1; A.recs2 = recs2;
-  A.counts1 = counts1; A.offsets1 = offsets1; A.counts2 = counts2; A.offsets2 = offsets2;
-  A.stride1 = stride1; A.stride2 = stride2;
+  A.set1 = set1; A.set2 = set2;
   A.pairs = h_pairs; A.pair_d = h_pair_d; A.distinct = h_distinct;
   A.npairs = npairs; A.nd = nd; A.max_pts = max_pts;
   A.rp = (double)radius * (1.0 + 1.0 / 1024) + 1e-20;

@@ -20,6 +20,7 @@
 #include <string.h>
 #include <vector>
 #include "common.hpp"
+#include "pair_plan.hpp"
 
 typedef float floatx16 __attribute__((ext_vector_type(16)));
 
@@ -360,81 +361,25 @@ int launch_match(misift_ctx *ctx, SiftPointD *pts1, int row_begin, int row_count
 // ============================================================================ batched pair matching (misift_match_batch)
 // MatchSiftData of many independent (frame of set 1, frame of set 2) pairs in three launches, with the frames' sizes known
 // on the device only:
-//   match_batch_plan_kernel   one workgroup: reads counts / offsets, writes one MbPair per pair (shape, chunking, and
-//                             exclusive prefix sums of work items and row blocks).  The work list is implicit: item i
-//                             belongs to the last pair with item0 <= i, and is (row block, column chunk) of that pair.
+//   pair_plan_kernel          one workgroup: the work list of the pairs (pair_plan.hpp), here with 128-row blocks and
+//                             64-column super-tiles; it serves misift_match_batch_i8 too.
 //   match_batch_kernel        persistent grid of two workgroups per CU; each takes items in a fixed stride and runs the
 //                             same sweep as match_kernel (match_sweep.inc) on them.  With one chunk per row block the
 //                             workgroup merges the eight classes and writes its rows itself; otherwise it stores the
 //                             per-class triples of the item and
 //   match_batch_merge_kernel  merges them over the chunks (it returns at once when nothing was chunked).
-// Columns are cut into chunks only when the row blocks of the whole call do not fill one round (two workgroups per CU);
-// the cut then leaves at most 2 * target items, so the partials buffer has a bound the host knows (mb_partial_items).
-struct MbPair {
-  int n1, n2, off1, off2;        // frame sizes (records, counts < 0 -> 0) and first records
-  int ncols, ntiles;             // columns that take part (32*floor(n2/32) or n2), 64-column super-tiles
-  int nrb, nchunks, tpc;         // 128-row blocks, column chunks, super-tiles per chunk
-  int item0, rb0;                // first work item / first row block of the pair (entry npairs: the totals)
-  int pad;
-};
-#define MB_HDR_INTS 4            // plan header: items, chunk count C, row blocks, 0 — then MbPair[npairs + 1]
+// Columns are cut into chunks only when the row blocks of the whole call do not fill one round (two workgroups per CU).
 #define MB_PART_FLOATS (MT_ROWS_PER_BLOCK * 8 * 3)     // per-class (max, second, index) of an item's 128 rows
 
-__host__ __device__ __forceinline__ void mb_pair_shape(int n1, int n2, int full, int &ncols, int &ntiles, int &nrb)
+// one round = two workgroups per CU (match_kernel's occupancy); columns 32 * floor(n2 / 32) unless match_full
+static PairShape mb_shape(int ncu, int full)
 {
-  if (n1 <= 0 || n2 <= 0) { ncols = 0; ntiles = 0; nrb = 0; return; }     // matching.cu:1095-1096: pair left untouched
-  ncols = full ? n2 : MT_TILE * (n2 / MT_TILE);
-  ntiles = (ncols + MT_SUPER - 1) / MT_SUPER;
-  nrb = (n1 + MT_ROWS_PER_BLOCK - 1) / MT_ROWS_PER_BLOCK;
-}
-// one round = two workgroups per CU (match_kernel's occupancy)
-__host__ __device__ __forceinline__ int mb_target(int ncu) { return 2 * (ncu > 0 ? ncu : 256); }
-// chunks per row block for a call of R row blocks: 1 when they fill a round, else ceil(target / R), so that
-// R * C < target + R < 2 * target
-__host__ __device__ __forceinline__ int mb_batch_chunks(long long R, int ncu)
-{
-  const long long t = mb_target(ncu);
-  if (R <= 0 || R >= t) return 1;
-  return (int)((t + R - 1) / R);
-}
-__host__ __device__ __forceinline__ void mb_pair_chunks(int ntiles, int C, int &nchunks, int &tpc)
-{
-  if (ntiles <= 0 || C <= 1) { nchunks = 1; tpc = ntiles > 0 ? ntiles : 1; return; }
-  nchunks = C < ntiles ? C : ntiles;
-  tpc = (ntiles + nchunks - 1) / nchunks;
-  nchunks = (ntiles + tpc - 1) / tpc;                   // no empty chunk
-}
-int mb_partial_items(int ncu) { return 2 * mb_target(ncu); }
-
-// exclusive scan of two ints over a 1024-thread workgroup; *tot = the workgroup's totals
-__device__ __forceinline__ void mb_block_scan2(int &a, int &b, int &tot_a, int &tot_b, int (*s)[2])
-{
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int ia = a, ib = b;
-  for (int d = 1; d < 64; d <<= 1) {
-    const int oa = __shfl_up(ia, d, 64), ob = __shfl_up(ib, d, 64);
-    if (lane >= d) { ia += oa; ib += ob; }
-  }
-  if (lane == 63) { s[wave][0] = ia; s[wave][1] = ib; }
-  __syncthreads();
-  int ba = 0, bb = 0;
-  tot_a = 0; tot_b = 0;
-  for (int w = 0; w < 16; w++) {
-    if (w < wave) { ba += s[w][0]; bb += s[w][1]; }
-    tot_a += s[w][0]; tot_b += s[w][1];
-  }
-  __syncthreads();
-  a = ba + ia - a;
-  b = bb + ib - b;
+  return PairShape{MT_ROWS_PER_BLOCK, MT_SUPER, full ? 1 : MT_TILE, 2 * (ncu > 0 ? ncu : 256)};
 }
 
-__global__ __launch_bounds__(1024) void match_batch_plan_kernel(const int *__restrict__ pairs, int npairs,
-                                                                const int *__restrict__ counts1,
-                                                                const int *__restrict__ offsets1, int stride1,
-                                                                const int *__restrict__ counts2,
-                                                                const int *__restrict__ offsets2, int stride2,
-                                                                int match_full, int ncu, int *__restrict__ hdr,
-                                                                MbPair *__restrict__ plan)
+__global__ __launch_bounds__(1024) void pair_plan_kernel(const int *__restrict__ pairs, int npairs, BatchLayout set1,
+                                                         BatchLayout set2, PairShape S, int *__restrict__ hdr,
+                                                         PairPlan *__restrict__ plan)
 {
   __shared__ int s_scan[16][2];
   __shared__ long long s_sum[16];
@@ -442,12 +387,12 @@ __global__ __launch_bounds__(1024) void match_batch_plan_kernel(const int *__res
   long long rsum = 0;
   for (int p = tid; p < npairs; p += 1024) {
     const int f1 = pairs[2 * p], f2 = pairs[2 * p + 1];
-    MbPair P;
-    P.n1 = max(counts1[f1], 0);
-    P.n2 = max(counts2[f2], 0);
-    P.off1 = offsets1 ? offsets1[f1] : f1 * stride1;
-    P.off2 = offsets2 ? offsets2[f2] : f2 * stride2;
-    mb_pair_shape(P.n1, P.n2, match_full, P.ncols, P.ntiles, P.nrb);
+    PairPlan P;
+    P.n1 = max(set1.counts[f1], 0);
+    P.n2 = max(set2.counts[f2], 0);
+    P.off1 = (int)set1.base(f1);               // plan offsets are ints, as the API's offsets are
+    P.off2 = (int)set2.base(f2);
+    pair_shape(S, P.n1, P.n2, P.ncols, P.ntiles, P.nrb);
     P.nchunks = 1; P.tpc = 1; P.item0 = 0; P.rb0 = 0; P.pad = 0;
     plan[p] = P;
     rsum += P.nrb;
@@ -457,29 +402,68 @@ __global__ __launch_bounds__(1024) void match_batch_plan_kernel(const int *__res
   __syncthreads();
   long long R = 0;
   for (int w = 0; w < 16; w++) R += s_sum[w];
-  const int C = mb_batch_chunks(R, ncu);
+  const int C = pair_batch_chunks(S, R);
   int carry_items = 0, carry_rb = 0;
   for (int base = 0; base < npairs; base += 1024) {
     const int p = base + tid;                                  // the thread that wrote plan[p] above
-    int items = 0, rbs = 0, nch = 1, tpc = 1;
+    int v[2] = {0, 0}, nch = 1, tpc = 1;                       // v: items, row blocks
     if (p < npairs) {
-      mb_pair_chunks(plan[p].ntiles, C, nch, tpc);
-      rbs = plan[p].nrb;
-      items = rbs * nch;
+      pair_chunks(plan[p].ntiles, C, nch, tpc);
+      v[1] = plan[p].nrb;
+      v[0] = v[1] * nch;
     }
-    int ti, tr;
-    mb_block_scan2(items, rbs, ti, tr, s_scan);
+    int tot[2];
+    block_scan(v, tot, s_scan);
     if (p < npairs) {
       plan[p].nchunks = nch; plan[p].tpc = tpc;
-      plan[p].item0 = carry_items + items; plan[p].rb0 = carry_rb + rbs;
+      plan[p].item0 = carry_items + v[0]; plan[p].rb0 = carry_rb + v[1];
     }
-    carry_items += ti; carry_rb += tr;
+    carry_items += tot[0]; carry_rb += tot[1];
   }
   if (tid == 0) {
-    MbPair E = {0, 0, 0, 0, 0, 0, 0, 1, 1, carry_items, carry_rb, 0};
+    PairPlan E = {0, 0, 0, 0, 0, 0, 0, 1, 1, carry_items, carry_rb, 0};
     plan[npairs] = E;
     hdr[0] = carry_items; hdr[1] = C; hdr[2] = carry_rb; hdr[3] = 0;
   }
+}
+
+size_t pair_plan_bytes(int npairs) { return sizeof(int) * PAIR_HDR_INTS + sizeof(PairPlan) * ((size_t)npairs + 1); }
+
+int launch_pair_plan(misift_ctx *ctx, const char *name, const PairShape &S, int npairs, const int *h_pairs,
+                     const BatchLayout &set1, const BatchLayout &set2, void *d_plan)
+{
+  int *hdr = reinterpret_cast<int *>(d_plan);
+  LaunchScope ls(ctx, name);
+  hipLaunchKernelGGL(pair_plan_kernel, dim3(1), dim3(1024), 0, ctx->stream, h_pairs, npairs, set1, set2, S, hdr,
+                     reinterpret_cast<PairPlan *>(hdr + PAIR_HDR_INTS));
+  return ls.finish();
+}
+
+int pair_plan_host(const PairShape &S, int npairs, const int *n1, const int *n2, int *plan5, int *nitems, int *chunks,
+                   int *partial_items_bound)
+{
+  if (npairs < 0 || (npairs > 0 && (!n1 || !n2 || !plan5)) || !nitems || !chunks || !partial_items_bound)
+    return MISIFT_EINVAL;
+  std::vector<int> ntiles(npairs), nrb(npairs);
+  long long R = 0;
+  for (int p = 0; p < npairs; p++) {
+    int ncols;
+    pair_shape(S, n1[p] > 0 ? n1[p] : 0, n2[p] > 0 ? n2[p] : 0, ncols, ntiles[p], nrb[p]);
+    R += nrb[p];
+  }
+  const int C = pair_batch_chunks(S, R);
+  long long items = 0;
+  for (int p = 0; p < npairs; p++) {
+    int nch, tpc;
+    pair_chunks(ntiles[p], C, nch, tpc);
+    int *o = plan5 + 5 * (size_t)p;
+    o[0] = (int)items; o[1] = nrb[p]; o[2] = ntiles[p]; o[3] = nch; o[4] = tpc;
+    items += (long long)nrb[p] * nch;
+  }
+  *nitems = (int)items;
+  *chunks = C;
+  *partial_items_bound = pair_partial_items(S);
+  return MISIFT_OK;
 }
 
 // The reference's final combination of the eight class summaries of one row (matching.cu:375-390; exact second best
@@ -515,24 +499,12 @@ __device__ __forceinline__ void mb_write_row(SiftPointD *o, const float *set2, i
   o->ambiguity = sec_score / (max_score + 1e-6f);
 }
 
-// the last pair whose prefix value (item0 or rb0) is <= v (pairs without work share their successor's value)
-template <bool ROWBLOCKS> __device__ __forceinline__ int mb_find_pair(const MbPair *__restrict__ plan, int npairs, int v)
-{
-  int lo = 0, hi = npairs - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if ((ROWBLOCKS ? plan[mid].rb0 : plan[mid].item0) <= v) lo = mid;
-    else hi = mid - 1;
-  }
-  return lo;
-}
-
 // recs1 / recs2 may be the same array (frame f against frame f + 1 of one packed batch): the sweep reads descriptors and
 // xpos / ypos only, and the rows written here are the five match fields — never the same bytes.
 __global__ __launch_bounds__(64 * MT_WG_WAVES, 8 / MT_WG_WAVES) void match_batch_kernel(SiftPointD *recs1,
                                                                                         const float *recs2,
                                                                                         const int *__restrict__ hdr,
-                                                                                        const MbPair *__restrict__ plan,
+                                                                                        const PairPlan *__restrict__ plan,
                                                                                         int npairs, int exact_top2,
                                                                                         float *__restrict__ partial)
 {
@@ -542,7 +514,7 @@ __global__ __launch_bounds__(64 * MT_WG_WAVES, 8 / MT_WG_WAVES) void match_batch
   const int nitems = hdr[0], C = hdr[1];
   // consecutive items (the row blocks of one pair) go to the workgroups of one XCD: that pair's set 2 stays in its L2
   for (int it = (int)xcd_remap(blockIdx.x, gridDim.x); it < nitems; it += gridDim.x) {
-    const MbPair P = plan[mb_find_pair<false>(plan, npairs, it)];
+    const PairPlan P = plan[pair_find<false>(plan, npairs, it)];
     const int local = it - P.item0, rb = local / P.nchunks, chunk = local - rb * P.nchunks;
     const int st0 = chunk * P.tpc, st1 = min(st0 + P.tpc, P.ntiles);
     MatchGeom G;
@@ -606,14 +578,14 @@ __global__ __launch_bounds__(64 * MT_WG_WAVES, 8 / MT_WG_WAVES) void match_batch
 // the pair's chunks in ascending order, as match_merge_kernel does.
 __global__ __launch_bounds__(256) void match_batch_merge_kernel(SiftPointD *recs1, const float *recs2,
                                                                 const int *__restrict__ hdr,
-                                                                const MbPair *__restrict__ plan, int npairs,
+                                                                const PairPlan *__restrict__ plan, int npairs,
                                                                 int exact_top2, const float *__restrict__ partial)
 {
   if (hdr[1] <= 1) return;
   const int nunits = hdr[2] * (MT_ROWS_PER_BLOCK / 32);
   for (int u = blockIdx.x; u < nunits; u += gridDim.x) {
     const int grb = u / (MT_ROWS_PER_BLOCK / 32);
-    const MbPair P = plan[mb_find_pair<true>(plan, npairs, grb)];
+    const PairPlan P = plan[pair_find<true>(plan, npairs, grb)];
     const int rb = grb - P.rb0;
     const int rl = (u % (MT_ROWS_PER_BLOCK / 32)) * 32 + (threadIdx.x >> 3), cls = threadIdx.x & 7;
     const int row = rb * MT_ROWS_PER_BLOCK + rl;
@@ -637,70 +609,38 @@ __global__ __launch_bounds__(256) void match_batch_merge_kernel(SiftPointD *recs
   }
 }
 
-// host-only test hook (no device needed): the plan match_batch_plan_kernel makes for pairs of n1[i] x n2[i] records on a
-// chip of num_cus CUs.  plan5[5 i ..]: first item, row blocks, super-tiles, chunks, super-tiles per chunk of pair i.
+// host-only test hook (no device needed): the plan misift_match_batch makes for pairs of n1[i] x n2[i] records on a chip
+// of num_cus CUs (pair_plan_host; tiles are 64-column super-tiles)
 extern "C" int misift_test_match_batch_plan(int num_cus, int match_full, int npairs, const int *n1, const int *n2,
                                             int *plan5, int *nitems, int *chunks, int *partial_items_bound)
 {
-  if (npairs < 0 || (npairs > 0 && (!n1 || !n2 || !plan5)) || !nitems || !chunks || !partial_items_bound)
-    return MISIFT_EINVAL;
-  std::vector<int> ntiles(npairs), nrb(npairs);
-  long long R = 0;
-  for (int p = 0; p < npairs; p++) {
-    int ncols;
-    mb_pair_shape(n1[p] > 0 ? n1[p] : 0, n2[p] > 0 ? n2[p] : 0, match_full, ncols, ntiles[p], nrb[p]);
-    R += nrb[p];
-  }
-  const int C = mb_batch_chunks(R, num_cus);
-  long long items = 0;
-  for (int p = 0; p < npairs; p++) {
-    int nch, tpc;
-    mb_pair_chunks(ntiles[p], C, nch, tpc);
-    int *o = plan5 + 5 * (size_t)p;
-    o[0] = (int)items; o[1] = nrb[p]; o[2] = ntiles[p]; o[3] = nch; o[4] = tpc;
-    items += (long long)nrb[p] * nch;
-  }
-  *nitems = (int)items;
-  *chunks = C;
-  *partial_items_bound = mb_partial_items(num_cus);
-  return MISIFT_OK;
+  return pair_plan_host(mb_shape(num_cus, match_full), npairs, n1, n2, plan5, nitems, chunks, partial_items_bound);
 }
 
-// Enqueue the three launches of misift_match_batch on the context stream.  h_pairs: pinned host memory the plan kernel
-// reads (the caller keeps it unchanged until that kernel has run); d_plan: MB_HDR_INTS + (npairs + 1) MbPair words.
-size_t match_batch_plan_bytes(int npairs) { return sizeof(int) * MB_HDR_INTS + sizeof(MbPair) * ((size_t)npairs + 1); }
-int launch_match_batch(misift_ctx *ctx, int npairs, const int *h_pairs, void *d_plan, SiftPointD *recs1,
-                       const int *counts1, const int *offsets1, int stride1, const SiftPointD *recs2,
-                       const int *counts2, const int *offsets2, int stride2)
+// Enqueue the three launches of misift_match_batch on the context stream (common.hpp).
+int launch_match_batch(misift_ctx *ctx, int npairs, const int *h_pairs, void *d_plan, const BatchLayout &set1,
+                       const BatchLayout &set2)
 {
   if (npairs <= 0) return MISIFT_OK;
-  {
-    int rc = misift_ensure_tmp(ctx, (size_t)mb_partial_items(ctx->num_cus) * MB_PART_FLOATS * sizeof(float));
-    if (rc) return rc;
-  }
-  int *hdr = reinterpret_cast<int *>(d_plan);
-  MbPair *plan = reinterpret_cast<MbPair *>(hdr + MB_HDR_INTS);
+  const PairShape S = mb_shape(ctx->num_cus, ctx->opt.match_full);
+  int rc = misift_ensure_tmp(ctx, (size_t)pair_partial_items(S) * MB_PART_FLOATS * sizeof(float));
+  if (rc) return rc;
+  rc = launch_pair_plan(ctx, "match_batch_plan", S, npairs, h_pairs, set1, set2, d_plan);
+  if (rc) return rc;
+  const int *hdr = reinterpret_cast<const int *>(d_plan);
+  const PairPlan *plan = reinterpret_cast<const PairPlan *>(hdr + PAIR_HDR_INTS);
   float *partial = reinterpret_cast<float *>(ctx->d_match_tmp);
-  const float *f2 = reinterpret_cast<const float *>(recs2);
-  const int grid = mb_target(ctx->num_cus);
-  {
-    LaunchScope ls(ctx, "match_batch_plan");
-    hipLaunchKernelGGL(match_batch_plan_kernel, dim3(1), dim3(1024), 0, ctx->stream, h_pairs, npairs, counts1, offsets1,
-                       stride1, counts2, offsets2, stride2, ctx->opt.match_full, ctx->num_cus, hdr, plan);
-    int rc = ls.finish();
-    if (rc) return rc;
-  }
+  const float *f2 = reinterpret_cast<const float *>(set2.recs);
+  const int grid = S.target;
   {
     LaunchScope ls(ctx, "match_batch_mfma");
-    hipLaunchKernelGGL(match_batch_kernel, dim3(grid), dim3(64 * MT_WG_WAVES), 0, ctx->stream, recs1, f2, hdr, plan,
+    hipLaunchKernelGGL(match_batch_kernel, dim3(grid), dim3(64 * MT_WG_WAVES), 0, ctx->stream, set1.recs, f2, hdr, plan,
                        npairs, ctx->opt.match_exact_top2, partial);
-    int rc = ls.finish();
+    rc = ls.finish();
     if (rc) return rc;
   }
-  {
-    LaunchScope ls(ctx, "match_batch_merge");
-    hipLaunchKernelGGL(match_batch_merge_kernel, dim3(grid), dim3(256), 0, ctx->stream, recs1, f2, hdr, plan, npairs,
-                       ctx->opt.match_exact_top2, partial);
-    return ls.finish();
-  }
+  LaunchScope ls(ctx, "match_batch_merge");
+  hipLaunchKernelGGL(match_batch_merge_kernel, dim3(grid), dim3(256), 0, ctx->stream, set1.recs, f2, hdr, plan, npairs,
+                     ctx->opt.match_exact_top2, partial);
+  return ls.finish();
 }

@@ -3,9 +3,8 @@
 //
 // quantize_i8_kernel   one launch: q[r] = quantize_i8(data of record r) (quantize_i8.hpp), 128 bytes at d_q + 128 r, for
 //                      every record of every frame; eight lanes per record, 16 bytes each.
-// match_i8_plan_kernel one workgroup: reads counts / offsets, writes one I8Pair per pair and the prefix sums of work items
-//                      and row blocks (the implicit work list of misift_match_batch: item i = (row block, column chunk)
-//                      of the last pair with item0 <= i).
+// pair_plan_kernel     the work list of misift_match_batch (pair_plan.hpp), here with 128-row blocks and 32-column tiles
+//                      and every column taking part.
 // match_i8_kernel      persistent grid, two waves per workgroup, 64 rows per wave (128-row blocks).  A wave keeps its
 //                      rows' q in VGPRs (two 32-row A tiles x 128 bytes) and sweeps 32-column tiles of set 2, loaded
 //                      straight from global memory one tile ahead: per tile 2 x 4 v_mfma_i32_32x32x32_i8 give the exact
@@ -19,15 +18,14 @@
 //                      With one column chunk per row block the wave writes its rows; otherwise it stores (best, index,
 //                      second) per row and chunk, and
 // match_i8_merge_kernel merges them over the chunks (it returns at once when nothing was chunked).
-// Columns are cut into chunks only when the row blocks of the call do not fill I8_TARGET_ROUNDS rounds of the grid, so
-// the partials buffer has a bound the host knows (i8_partial_items).
+// Columns are cut into chunks only when the row blocks of the call do not fill I8_TARGET_ROUNDS rounds of the grid.
 //
 // The A and B fragments of the i8 MFMA are loaded by the same code (lane l: row / column l & 31, bytes 64 (l >> 5) + 16 s
 // of k-step s), so the sum over k is right whatever order the hardware pairs the bytes of one k-step in; integer sums do
 // not depend on order.
 #include <stdint.h>
-#include <vector>
 #include "common.hpp"
+#include "pair_plan.hpp"
 #include "quantize_i8.hpp"
 
 namespace {
@@ -43,48 +41,23 @@ constexpr unsigned I8_OFF = 1u << 30;            // key of S = 0, t = 511
 constexpr unsigned I8_VALID = I8_OFF + 512u;     // smallest key with S >= 1
 constexpr int I8_WG_PER_CU = 4;                  // workgroups per CU of the persistent grid (8 waves)
 constexpr int I8_TARGET_ROUNDS = 4;              // items a call is cut into when its row blocks are few, in grid rounds
-constexpr int I8_HDR_INTS = 4;                   // plan header: items, chunk count C, row blocks, 0 — then I8Pair[npairs + 1]
-
-struct I8Pair {
-  int n1, n2, off1, off2;        // frame sizes (counts < 0 -> 0) and first records
-  int ntiles, nrb, nchunks, tpc; // 32-column tiles, 128-row blocks, column chunks, tiles per chunk
-  int item0, rb0, pad0, pad1;    // first work item / first row block of the pair (entry npairs: the totals)
-};
 
 struct I8Args {
   SiftPointD *recs1;
   const SiftPointD *recs2;
   const int8_t *q1, *q2;
   const int *hdr;
-  const I8Pair *plan;
+  const PairPlan *plan;
   int npairs;
   int4 *partial;                 // items x I8_ROWS x (best, index, second, 0), chunked calls only
 };
 
 __host__ __device__ __forceinline__ int i8_grid(int ncu) { return I8_WG_PER_CU * (ncu > 0 ? ncu : 256); }
-__host__ __device__ __forceinline__ int i8_target(int ncu) { return I8_TARGET_ROUNDS * i8_grid(ncu); }
-__host__ __device__ __forceinline__ void i8_pair_shape(int n1, int n2, int &ntiles, int &nrb)
+// the plan's shape: 128-row blocks, 32-column tiles, every column
+PairShape i8_shape(int ncu)
 {
-  if (n1 <= 0 || n2 <= 0) { ntiles = 0; nrb = 0; return; }            // a pair with an empty side stays untouched
-  ntiles = (n2 + I8_TILE - 1) / I8_TILE;
-  nrb = (n1 + I8_ROWS - 1) / I8_ROWS;
+  return PairShape{I8_ROWS, I8_TILE, 1, I8_TARGET_ROUNDS * i8_grid(ncu)};
 }
-// chunks per row block for a call of R row blocks: 1 when they fill the target, else ceil(target / R), so that
-// R * C < target + R < 2 * target
-__host__ __device__ __forceinline__ int i8_batch_chunks(long long R, int ncu)
-{
-  const long long t = i8_target(ncu);
-  if (R <= 0 || R >= t) return 1;
-  return (int)((t + R - 1) / R);
-}
-__host__ __device__ __forceinline__ void i8_pair_chunks(int ntiles, int C, int &nchunks, int &tpc)
-{
-  if (ntiles <= 0 || C <= 1) { nchunks = 1; tpc = ntiles > 0 ? ntiles : 1; return; }
-  nchunks = C < ntiles ? C : ntiles;
-  tpc = (ntiles + nchunks - 1) / nchunks;
-  nchunks = (ntiles + tpc - 1) / tpc;                    // no empty chunk
-}
-int i8_partial_items(int ncu) { return 2 * i8_target(ncu); }
 
 // (m, i, s) <- the top two of (m, i, s) and (mo, io, so): score descending, index ascending; a tie of the best scores
 // makes the loser's score the runner-up.  "None" is (0, -1, 0); real entries have m > 0.
@@ -106,40 +79,6 @@ __device__ __forceinline__ void i8_write_row(SiftPointD *o, const SiftPointD *se
   o->ambiguity = ((float)s * 0x1p-16f) / (score + 1e-6f);
 }
 
-// the last pair whose prefix value (item0 or rb0) is <= v (pairs without work share their successor's value)
-template <bool ROWBLOCKS> __device__ __forceinline__ int i8_find_pair(const I8Pair *__restrict__ plan, int npairs, int v)
-{
-  int lo = 0, hi = npairs - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if ((ROWBLOCKS ? plan[mid].rb0 : plan[mid].item0) <= v) lo = mid;
-    else hi = mid - 1;
-  }
-  return lo;
-}
-
-// exclusive scan of two ints over a 1024-thread workgroup; tot_* = the workgroup's totals
-__device__ __forceinline__ void i8_block_scan2(int &a, int &b, int &tot_a, int &tot_b, int (*s)[2])
-{
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int ia = a, ib = b;
-  for (int d = 1; d < 64; d <<= 1) {
-    const int oa = __shfl_up(ia, d, 64), ob = __shfl_up(ib, d, 64);
-    if (lane >= d) { ia += oa; ib += ob; }
-  }
-  if (lane == 63) { s[wave][0] = ia; s[wave][1] = ib; }
-  __syncthreads();
-  int ba = 0, bb = 0;
-  tot_a = 0; tot_b = 0;
-  for (int w = 0; w < 16; w++) {
-    if (w < wave) { ba += s[w][0]; bb += s[w][1]; }
-    tot_a += s[w][0]; tot_b += s[w][1];
-  }
-  __syncthreads();
-  a = ba + ia - a;
-  b = bb + ib - b;
-}
-
 __device__ __forceinline__ unsigned i8_pack4(float4 v)
 {
   return (unsigned)(uint8_t)quantize_i8(v.x) | (unsigned)(uint8_t)quantize_i8(v.y) << 8 |
@@ -148,15 +87,13 @@ __device__ __forceinline__ unsigned i8_pack4(float4 v)
 
 }  // namespace
 
-__global__ __launch_bounds__(256) void quantize_i8_kernel(const SiftPointD *__restrict__ recs, int nframes,
-                                                          const int *__restrict__ counts,
-                                                          const int *__restrict__ offsets, int stride,
-                                                          int8_t *__restrict__ q)
+__global__ __launch_bounds__(256) void quantize_i8_kernel(BatchLayout set, int nframes, int8_t *__restrict__ q)
 {
+  const SiftPointD *__restrict__ recs = set.recs;
   const int sub = threadIdx.x & 7;
   for (int f = blockIdx.y; f < nframes; f += gridDim.y) {
-    const int n = max(counts[f], 0);
-    const long long base = offsets ? (long long)offsets[f] : (long long)f * stride;
+    const int n = max(set.counts[f], 0);
+    const long long base = set.base(f);
     for (int r = blockIdx.x * 32 + (threadIdx.x >> 3); r < n; r += gridDim.x * 32) {
       const float4 *src = reinterpret_cast<const float4 *>(recs[base + r].data) + 4 * sub;
       int4 w;
@@ -166,59 +103,6 @@ __global__ __launch_bounds__(256) void quantize_i8_kernel(const SiftPointD *__re
       w.w = (int)i8_pack4(src[3]);
       reinterpret_cast<int4 *>(q + (base + r) * 128)[sub] = w;
     }
-  }
-}
-
-__global__ __launch_bounds__(1024) void match_i8_plan_kernel(const int *__restrict__ pairs, int npairs,
-                                                             const int *__restrict__ counts1,
-                                                             const int *__restrict__ offsets1, int stride1,
-                                                             const int *__restrict__ counts2,
-                                                             const int *__restrict__ offsets2, int stride2, int ncu,
-                                                             int *__restrict__ hdr, I8Pair *__restrict__ plan)
-{
-  __shared__ int s_scan[16][2];
-  __shared__ long long s_sum[16];
-  const int tid = threadIdx.x;
-  long long rsum = 0;
-  for (int p = tid; p < npairs; p += 1024) {
-    const int f1 = pairs[2 * p], f2 = pairs[2 * p + 1];
-    I8Pair P;
-    P.n1 = max(counts1[f1], 0);
-    P.n2 = max(counts2[f2], 0);
-    P.off1 = offsets1 ? offsets1[f1] : f1 * stride1;
-    P.off2 = offsets2 ? offsets2[f2] : f2 * stride2;
-    i8_pair_shape(P.n1, P.n2, P.ntiles, P.nrb);
-    P.nchunks = 1; P.tpc = 1; P.item0 = 0; P.rb0 = 0; P.pad0 = 0; P.pad1 = 0;
-    plan[p] = P;
-    rsum += P.nrb;
-  }
-  for (int d = 32; d >= 1; d >>= 1) rsum += __shfl_down(rsum, d, 64);
-  if ((tid & 63) == 0) s_sum[tid >> 6] = rsum;
-  __syncthreads();
-  long long R = 0;
-  for (int w = 0; w < 16; w++) R += s_sum[w];
-  const int C = i8_batch_chunks(R, ncu);
-  int carry_items = 0, carry_rb = 0;
-  for (int base = 0; base < npairs; base += 1024) {
-    const int p = base + tid;                                  // the thread that wrote plan[p] above
-    int items = 0, rbs = 0, nch = 1, tpc = 1;
-    if (p < npairs) {
-      i8_pair_chunks(plan[p].ntiles, C, nch, tpc);
-      rbs = plan[p].nrb;
-      items = rbs * nch;
-    }
-    int ti, tr;
-    i8_block_scan2(items, rbs, ti, tr, s_scan);
-    if (p < npairs) {
-      plan[p].nchunks = nch; plan[p].tpc = tpc;
-      plan[p].item0 = carry_items + items; plan[p].rb0 = carry_rb + rbs;
-    }
-    carry_items += ti; carry_rb += tr;
-  }
-  if (tid == 0) {
-    I8Pair E = {0, 0, 0, 0, 0, 0, 1, 1, carry_items, carry_rb, 0, 0};
-    plan[npairs] = E;
-    hdr[0] = carry_items; hdr[1] = C; hdr[2] = carry_rb; hdr[3] = 0;
   }
 }
 
@@ -233,7 +117,7 @@ __global__ __launch_bounds__(64 * I8_WAVES) void match_i8_kernel(I8Args A)
   // the row this lane owns in the fold and the output: row register c & 15 of A tile c >> 4, lane half h
   const int own = 32 * (c >> 4) + (c & 3) + 8 * ((c & 15) >> 2) + 4 * h;
   for (int it = (int)xcd_remap(blockIdx.x, gridDim.x); it < nitems; it += gridDim.x) {
-    I8Pair P = A.plan[i8_find_pair<false>(A.plan, A.npairs, it)];
+    PairPlan P = A.plan[pair_find<false>(A.plan, A.npairs, it)];
     // wave-uniform: keep the loop bounds and the key constant in SGPRs
     P.n1 = __builtin_amdgcn_readfirstlane(P.n1); P.n2 = __builtin_amdgcn_readfirstlane(P.n2);
     P.off1 = __builtin_amdgcn_readfirstlane(P.off1); P.off2 = __builtin_amdgcn_readfirstlane(P.off2);
@@ -337,7 +221,7 @@ __global__ __launch_bounds__(I8_ROWS) void match_i8_merge_kernel(I8Args A)
   if (A.hdr[1] <= 1) return;
   const int nrbs = A.hdr[2];
   for (int g = blockIdx.x; g < nrbs; g += gridDim.x) {
-    const I8Pair P = A.plan[i8_find_pair<true>(A.plan, A.npairs, g)];
+    const PairPlan P = A.plan[pair_find<true>(A.plan, A.npairs, g)];
     const int rb = g - P.rb0, row = rb * I8_ROWS + threadIdx.x;
     if (row >= P.n1) continue;
     int M = 0, I = -1, S2 = 0;
@@ -358,36 +242,15 @@ extern "C" int misift_test_quantize(const float *src, long n, int8_t *dst)
   return MISIFT_OK;
 }
 
-// host-only test hook (no device needed): the plan match_i8_plan_kernel makes for pairs of n1[i] x n2[i] records on a chip
-// of num_cus CUs.  plan5[5 i ..]: first item, row blocks, tiles, chunks, tiles per chunk of pair i.
+// host-only test hook (no device needed): the plan misift_match_batch_i8 makes for pairs of n1[i] x n2[i] records on a
+// chip of num_cus CUs (pair_plan_host; tiles are 32 columns)
 extern "C" int misift_test_match_i8_plan(int num_cus, int npairs, const int *n1, const int *n2, int *plan5, int *nitems,
                                          int *chunks, int *partial_items_bound)
 {
-  if (npairs < 0 || (npairs > 0 && (!n1 || !n2 || !plan5)) || !nitems || !chunks || !partial_items_bound)
-    return MISIFT_EINVAL;
-  std::vector<int> ntiles(npairs), nrb(npairs);
-  long long R = 0;
-  for (int p = 0; p < npairs; p++) {
-    i8_pair_shape(n1[p] > 0 ? n1[p] : 0, n2[p] > 0 ? n2[p] : 0, ntiles[p], nrb[p]);
-    R += nrb[p];
-  }
-  const int C = i8_batch_chunks(R, num_cus);
-  long long items = 0;
-  for (int p = 0; p < npairs; p++) {
-    int nch, tpc;
-    i8_pair_chunks(ntiles[p], C, nch, tpc);
-    int *o = plan5 + 5 * (size_t)p;
-    o[0] = (int)items; o[1] = nrb[p]; o[2] = ntiles[p]; o[3] = nch; o[4] = tpc;
-    items += (long long)nrb[p] * nch;
-  }
-  *nitems = (int)items;
-  *chunks = C;
-  *partial_items_bound = i8_partial_items(num_cus);
-  return MISIFT_OK;
+  return pair_plan_host(i8_shape(num_cus), npairs, n1, n2, plan5, nitems, chunks, partial_items_bound);
 }
 
-int launch_quantize_batch(misift_ctx *ctx, const SiftPointD *recs, int nframes, const int *counts, const int *offsets,
-                          int stride, int8_t *q)
+int launch_quantize_batch(misift_ctx *ctx, const BatchLayout &set, int nframes, int8_t *q)
 {
   if (nframes <= 0) return MISIFT_OK;
   // counts live on the device: enough workgroups per frame to cover the largest frame of a big call in a few strides
@@ -396,42 +259,30 @@ int launch_quantize_batch(misift_ctx *ctx, const SiftPointD *recs, int nframes, 
   int gx = 8 * ncu / gy;
   gx = gx < 1 ? 1 : (gx > 1024 ? 1024 : gx);
   LaunchScope ls(ctx, "quantize_i8");
-  hipLaunchKernelGGL(quantize_i8_kernel, dim3(gx, gy), dim3(256), 0, ctx->stream, recs, nframes, counts, offsets, stride,
-                     q);
+  hipLaunchKernelGGL(quantize_i8_kernel, dim3(gx, gy), dim3(256), 0, ctx->stream, set, nframes, q);
   return ls.finish();
 }
 
-size_t match_i8_plan_bytes(int npairs) { return sizeof(int) * I8_HDR_INTS + sizeof(I8Pair) * ((size_t)npairs + 1); }
-
-int launch_match_batch_i8(misift_ctx *ctx, int npairs, const int *h_pairs, void *d_plan, SiftPointD *recs1,
-                          const int8_t *q1, const int *counts1, const int *offsets1, int stride1,
-                          const SiftPointD *recs2, const int8_t *q2, const int *counts2, const int *offsets2,
-                          int stride2)
+int launch_match_batch_i8(misift_ctx *ctx, int npairs, const int *h_pairs, void *d_plan, const BatchLayout &set1,
+                          const int8_t *q1, const BatchLayout &set2, const int8_t *q2)
 {
   if (npairs <= 0) return MISIFT_OK;
-  {
-    int rc = misift_ensure_tmp(ctx, (size_t)i8_partial_items(ctx->num_cus) * I8_ROWS * sizeof(int4));
-    if (rc) return rc;
-  }
+  const PairShape S = i8_shape(ctx->num_cus);
+  int rc = misift_ensure_tmp(ctx, (size_t)pair_partial_items(S) * I8_ROWS * sizeof(int4));
+  if (rc) return rc;
+  rc = launch_pair_plan(ctx, "match_i8_plan", S, npairs, h_pairs, set1, set2, d_plan);
+  if (rc) return rc;
   I8Args A;
-  A.recs1 = recs1; A.recs2 = recs2; A.q1 = q1; A.q2 = q2;
-  int *hdr = reinterpret_cast<int *>(d_plan);
-  A.hdr = hdr;
-  A.plan = reinterpret_cast<const I8Pair *>(hdr + I8_HDR_INTS);
+  A.recs1 = set1.recs; A.recs2 = set2.recs; A.q1 = q1; A.q2 = q2;
+  A.hdr = reinterpret_cast<const int *>(d_plan);
+  A.plan = reinterpret_cast<const PairPlan *>(A.hdr + PAIR_HDR_INTS);
   A.npairs = npairs;
   A.partial = reinterpret_cast<int4 *>(ctx->d_match_tmp);
   const int grid = i8_grid(ctx->num_cus);
   {
-    LaunchScope ls(ctx, "match_i8_plan");
-    hipLaunchKernelGGL(match_i8_plan_kernel, dim3(1), dim3(1024), 0, ctx->stream, h_pairs, npairs, counts1, offsets1,
-                       stride1, counts2, offsets2, stride2, ctx->num_cus, hdr, reinterpret_cast<I8Pair *>(hdr + I8_HDR_INTS));
-    int rc = ls.finish();
-    if (rc) return rc;
-  }
-  {
     LaunchScope ls(ctx, "match_i8_mfma");
     hipLaunchKernelGGL(match_i8_kernel, dim3(grid), dim3(64 * I8_WAVES), 0, ctx->stream, A);
-    int rc = ls.finish();
+    rc = ls.finish();
     if (rc) return rc;
   }
   LaunchScope ls(ctx, "match_i8_merge");

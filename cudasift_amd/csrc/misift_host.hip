@@ -12,6 +12,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <math.h>
+#include <initializer_list>
 #include <map>
 #include <mutex>
 #include <string>
@@ -19,6 +20,7 @@
 #include <vector>
 #include "common.hpp"
 #include "chain.hpp"
+#include "pair_plan.hpp"
 
 // ------------------------------------------------------------------ errors
 static thread_local char g_err[512] = "";
@@ -33,13 +35,14 @@ void misift_set_error(const char *fmt, ...)
 
 extern "C" const char *misift_last_error(void) { return g_err; }
 
-#define ARG_CHECK(cond)                                                       \
+#define ARG_CHECK_IN(who, cond)                                               \
   do {                                                                        \
     if (!(cond)) {                                                            \
-      misift_set_error("%s: invalid argument: %s", __func__, #cond);          \
+      misift_set_error("%s: invalid argument: %s", who, #cond);               \
       return MISIFT_EINVAL;                                                   \
     }                                                                         \
   } while (0)
+#define ARG_CHECK(cond) ARG_CHECK_IN(__func__, cond)
 
 // ------------------------------------------------------------------ roctx
 // Named ranges for rocprofv3 --marker-trace / rocprof-sys: one range per entry-point call and one
@@ -124,7 +127,7 @@ struct CtxExtra {
   bool k5_done = false;
   // misift_match_batch and misift_*_homography_batch: pinned copies of the callers' pair / frame / seed lists, a ring of
   // MB_RING slots (a slot is refilled once the call that last used it has run: mb_done), and misift_match_batch's device
-  // plan (header + one MbPair per pair)
+  // plan (header + one PairPlan per pair)
   static const int MB_RING = 4;
   int *mb_pairs[MB_RING] = {};
   size_t mb_pairs_cap[MB_RING] = {};
@@ -2080,21 +2083,63 @@ static int ensure_mb_plan(misift_ctx *ctx, size_t bytes)
   return MISIFT_OK;
 }
 
-// The pair checks of the batch matchers: indices in range, a set-1 frame in at most one pair.
-static int check_match_pairs(int npairs, const int *pairs, int nframes1, int nframes2)
+// The checks of the batch calls, made before anything is enqueued; an error names the entry point `who`.
+// One set of records: without offsets, frame f starts at record f * stride.
+static int batch_layout(const char *who, const void *recs, const int *counts, const int *offsets, int stride,
+                        BatchLayout *set)
+{
+  ARG_CHECK_IN(who, offsets || stride >= 0);
+  *set = BatchLayout{(SiftPointD *)recs, counts, offsets, stride};
+  return MISIFT_OK;
+}
+
+// A list of n entries of `step` ints: a frame of the first batch (nframes1 frames), and for pairs (step 2) a frame of
+// the second (nframes2 frames).  Every index in range; a frame of the first batch in at most one entry.
+static int check_frames(const char *who, int n, const int *list, int step, int nframes1, int nframes2)
 {
   std::vector<char> taken((size_t)nframes1, 0);
-  for (int p = 0; p < npairs; p++) {
-    const int f1 = pairs[2 * p], f2 = pairs[2 * p + 1];
-    ARG_CHECK(f1 >= 0 && f1 < nframes1 && f2 >= 0 && f2 < nframes2);
-    ARG_CHECK(!taken[f1]);                                 // a set-1 frame in at most one pair
+  for (int i = 0; i < n; i++) {
+    const int f1 = list[step * i], f2 = step == 2 ? list[step * i + 1] : 0;
+    ARG_CHECK_IN(who, f1 >= 0 && f1 < nframes1 && (step == 1 || (f2 >= 0 && f2 < nframes2)));
+    ARG_CHECK_IN(who, !taken[f1]);
     taken[f1] = 1;
   }
   return MISIFT_OK;
 }
 
+// The host side of a batch call, behind its checks: the caller's host lists go, in order, to the next slot of the pinned
+// ring; plan_bytes > 0 provides the device plan of the pair matchers; launch(slot, plan) enqueues the launches, and
+// mb_done of the slot is recorded behind them, also when a launch failed.
+struct HostList {
+  const void *src;
+  size_t bytes;
+};
+template <class Launch>
+static int run_batch(misift_ctx *ctx, std::initializer_list<HostList> lists, size_t plan_bytes, Launch launch)
+{
+  HIP_TRY(hipSetDevice(ctx->device));
+  CtxExtra *x = extra(ctx);
+  size_t bytes = 0;
+  for (const HostList &l : lists) bytes += l.bytes;
+  int slot;
+  int rc = mb_ring_slot(ctx, bytes, &slot);
+  if (rc) return rc;
+  char *h = reinterpret_cast<char *>(x->mb_pairs[slot]);
+  for (const HostList &l : lists) {
+    memcpy(h, l.src, l.bytes);
+    h += l.bytes;
+  }
+  if (plan_bytes) {
+    rc = ensure_mb_plan(ctx, plan_bytes);
+    if (rc) return rc;
+  }
+  rc = launch(x->mb_pairs[slot], x->d_mb_plan);
+  HIP_TRY(hipEventRecord(x->mb_done[slot], ctx->stream));
+  return rc;
+}
+
 // Many (frame of set 1, frame of set 2) pairs of device-resident batches in one stream-ordered call: no host wait and no
-// host read of the counts.  The arguments are checked here, before anything is enqueued.
+// host read of the counts.
 extern "C" int misift_match_batch(misift_ctx *ctx, int npairs, const int *pairs, void *d_recs1, int nframes1,
                                   const int *d_counts1, const int *d_offsets1, int stride1, const void *d_recs2,
                                   int nframes2, const int *d_counts2, const int *d_offsets2, int stride2)
@@ -2102,41 +2147,20 @@ extern "C" int misift_match_batch(misift_ctx *ctx, int npairs, const int *pairs,
   ARG_CHECK(ctx && npairs >= 0);
   if (npairs == 0) return MISIFT_OK;
   ARG_CHECK(pairs && d_recs1 && d_recs2 && d_counts1 && d_counts2 && nframes1 > 0 && nframes2 > 0);
-  ARG_CHECK(d_offsets1 || stride1 >= 0);
-  ARG_CHECK(d_offsets2 || stride2 >= 0);
-  int rc = check_match_pairs(npairs, pairs, nframes1, nframes2);
+  BatchLayout set1, set2;
+  int rc = batch_layout(__func__, d_recs1, d_counts1, d_offsets1, stride1, &set1);
+  if (!rc) rc = batch_layout(__func__, d_recs2, d_counts2, d_offsets2, stride2, &set2);
+  if (!rc) rc = check_frames(__func__, npairs, pairs, 2, nframes1, nframes2);
   if (rc) return rc;
-  RoctxRange range("misift_match_batch");
-  HIP_TRY(hipSetDevice(ctx->device));
-  CtxExtra *x = extra(ctx);
-  int slot;
-  const size_t pair_bytes = sizeof(int) * 2 * (size_t)npairs;
-  rc = mb_ring_slot(ctx, pair_bytes, &slot);
-  if (rc) return rc;
-  memcpy(x->mb_pairs[slot], pairs, pair_bytes);
-  rc = ensure_mb_plan(ctx, match_batch_plan_bytes(npairs));
-  if (rc) return rc;
-  rc = launch_match_batch(ctx, npairs, x->mb_pairs[slot], x->d_mb_plan, (SiftPointD *)d_recs1, d_counts1,
-                          d_offsets1, stride1, (const SiftPointD *)d_recs2, d_counts2, d_offsets2, stride2);
-  HIP_TRY(hipEventRecord(x->mb_done[slot], ctx->stream));
-  return rc;
+  RoctxRange range(__func__);
+  return run_batch(ctx, {{pairs, sizeof(int) * 2 * (size_t)npairs}}, pair_plan_bytes(npairs),
+                   [&](int *h_pairs, void *d_plan) {
+                     return launch_match_batch(ctx, npairs, h_pairs, d_plan, set1, set2);
+                   });
 }
 
 // Many frames of a device-resident batch through FindHomography / ImproveHomography in one stream-ordered call each: no
-// host wait and no host read of the counts.  The arguments are checked here, before anything is enqueued; the host lists
-// go to a pinned slot of the same ring as misift_match_batch's pairs.
-static int check_homography_frames(int nsel, const int *frames, int nframes)
-{
-  std::vector<char> taken((size_t)nframes, 0);
-  for (int i = 0; i < nsel; i++) {
-    const int f = frames[i];
-    ARG_CHECK(f >= 0 && f < nframes);
-    ARG_CHECK(!taken[f]);                                   // a frame in at most one entry
-    taken[f] = 1;
-  }
-  return MISIFT_OK;
-}
-
+// host wait and no host read of the counts.
 extern "C" int misift_find_homography_batch(misift_ctx *ctx, int nsel, const int *frames, const unsigned *seeds,
                                             const void *d_recs, int nframes, const int *d_counts, const int *d_offsets,
                                             int stride, int max_pts, int num_loops, float min_score,
@@ -2145,25 +2169,19 @@ extern "C" int misift_find_homography_batch(misift_ctx *ctx, int nsel, const int
   ARG_CHECK(ctx && nsel >= 0);
   if (nsel == 0) return MISIFT_OK;
   ARG_CHECK(frames && seeds && d_recs && d_counts && nframes > 0 && d_homography && d_num_matches);
-  ARG_CHECK(d_offsets || stride >= 0);
+  BatchLayout set;
+  int rc = batch_layout(__func__, d_recs, d_counts, d_offsets, stride, &set);
+  if (rc) return rc;
   ARG_CHECK(num_loops >= 1 && max_pts >= 1);
-  int rc = check_homography_frames(nsel, frames, nframes);
+  rc = check_frames(__func__, nsel, frames, 1, nframes, 0);
   if (rc) return rc;
-  RoctxRange range("misift_find_homography_batch");
-  HIP_TRY(hipSetDevice(ctx->device));
-  CtxExtra *x = extra(ctx);
-  int slot;
-  rc = mb_ring_slot(ctx, sizeof(int) * 2 * (size_t)nsel, &slot);
-  if (rc) return rc;
-  int *h_frames = x->mb_pairs[slot];
-  unsigned *h_seeds = reinterpret_cast<unsigned *>(h_frames + nsel);
-  memcpy(h_frames, frames, sizeof(int) * (size_t)nsel);
-  memcpy(h_seeds, seeds, sizeof(unsigned) * (size_t)nsel);
-  rc = launch_find_homography_batch(ctx, nsel, h_frames, h_seeds, (const SiftPointD *)d_recs, d_counts, d_offsets,
-                                    stride, max_pts, num_loops, min_score, max_ambiguity, thresh, d_homography,
-                                    d_num_matches);
-  HIP_TRY(hipEventRecord(x->mb_done[slot], ctx->stream));
-  return rc;
+  RoctxRange range(__func__);
+  return run_batch(ctx, {{frames, sizeof(int) * (size_t)nsel}, {seeds, sizeof(unsigned) * (size_t)nsel}}, 0,
+                   [&](int *h_frames, void *) {
+                     return launch_find_homography_batch(ctx, nsel, h_frames, (const unsigned *)(h_frames + nsel), set,
+                                                         max_pts, num_loops, min_score, max_ambiguity, thresh,
+                                                         d_homography, d_num_matches);
+                   });
 }
 
 extern "C" int misift_improve_homography_batch(misift_ctx *ctx, int nsel, const int *frames, void *d_recs, int nframes,
@@ -2174,26 +2192,21 @@ extern "C" int misift_improve_homography_batch(misift_ctx *ctx, int nsel, const 
   ARG_CHECK(ctx && nsel >= 0);
   if (nsel == 0) return MISIFT_OK;
   ARG_CHECK(frames && d_recs && d_counts && nframes > 0 && d_homography && d_num_fit);
-  ARG_CHECK(d_offsets || stride >= 0);
+  BatchLayout set;
+  int rc = batch_layout(__func__, d_recs, d_counts, d_offsets, stride, &set);
+  if (rc) return rc;
   ARG_CHECK(num_loops >= 0);
-  int rc = check_homography_frames(nsel, frames, nframes);
+  rc = check_frames(__func__, nsel, frames, 1, nframes, 0);
   if (rc) return rc;
-  RoctxRange range("misift_improve_homography_batch");
-  HIP_TRY(hipSetDevice(ctx->device));
-  CtxExtra *x = extra(ctx);
-  int slot;
-  rc = mb_ring_slot(ctx, sizeof(int) * (size_t)nsel, &slot);
-  if (rc) return rc;
-  memcpy(x->mb_pairs[slot], frames, sizeof(int) * (size_t)nsel);
-  rc = launch_improve_homography_batch(ctx, nsel, x->mb_pairs[slot], (SiftPointD *)d_recs, d_counts, d_offsets, stride,
-                                       num_loops, min_score, max_ambiguity, thresh, d_homography, d_num_fit);
-  HIP_TRY(hipEventRecord(x->mb_done[slot], ctx->stream));
-  return rc;
+  RoctxRange range(__func__);
+  return run_batch(ctx, {{frames, sizeof(int) * (size_t)nsel}}, 0, [&](int *h_frames, void *) {
+    return launch_improve_homography_batch(ctx, nsel, h_frames, set, num_loops, min_score, max_ambiguity, thresh,
+                                           d_homography, d_num_fit);
+  });
 }
 
 // Homography-guided matching of many frame pairs in one stream-ordered call: no host wait and no host read of the counts.
-// The arguments are checked here, before anything is enqueued; the pairs, each pair's index among the distinct set-2
-// frames and those frames go to a pinned slot of the same ring as misift_match_batch's pairs.
+// The host lists: the pairs, each pair's index among the distinct set-2 frames, and those frames.
 extern "C" int misift_match_guided_batch(misift_ctx *ctx, int npairs, const int *pairs, void *d_recs1, int nframes1,
                                          const int *d_counts1, const int *d_offsets1, int stride1, const void *d_recs2,
                                          int nframes2, const int *d_counts2, const int *d_offsets2, int stride2,
@@ -2202,17 +2215,17 @@ extern "C" int misift_match_guided_batch(misift_ctx *ctx, int npairs, const int 
   ARG_CHECK(ctx && npairs >= 0);
   if (npairs == 0) return MISIFT_OK;
   ARG_CHECK(pairs && d_recs1 && d_recs2 && d_counts1 && d_counts2 && d_homography && nframes1 > 0 && nframes2 > 0);
-  ARG_CHECK(d_offsets1 || stride1 >= 0);
-  ARG_CHECK(d_offsets2 || stride2 >= 0);
+  BatchLayout set1, set2;
+  int rc = batch_layout(__func__, d_recs1, d_counts1, d_offsets1, stride1, &set1);
+  if (!rc) rc = batch_layout(__func__, d_recs2, d_counts2, d_offsets2, stride2, &set2);
+  if (rc) return rc;
   ARG_CHECK(radius > 0.0f);                                // NaN fails too
   ARG_CHECK(max_pts >= 1);
-  std::vector<char> taken((size_t)nframes1, 0);
+  rc = check_frames(__func__, npairs, pairs, 2, nframes1, nframes2);
+  if (rc) return rc;
   std::vector<int> dindex((size_t)nframes2, -1), pair_d((size_t)npairs), distinct;
   for (int p = 0; p < npairs; p++) {
-    const int f1 = pairs[2 * p], f2 = pairs[2 * p + 1];
-    ARG_CHECK(f1 >= 0 && f1 < nframes1 && f2 >= 0 && f2 < nframes2);
-    ARG_CHECK(!taken[f1]);                                 // a set-1 frame in at most one pair
-    taken[f1] = 1;
+    const int f2 = pairs[2 * p + 1];
     if (dindex[f2] < 0) {
       dindex[f2] = (int)distinct.size();
       distinct.push_back(f2);
@@ -2220,21 +2233,16 @@ extern "C" int misift_match_guided_batch(misift_ctx *ctx, int npairs, const int 
     pair_d[p] = dindex[f2];
   }
   const int nd = (int)distinct.size();
-  RoctxRange range("misift_match_guided_batch");
-  HIP_TRY(hipSetDevice(ctx->device));
-  CtxExtra *x = extra(ctx);
-  int slot;
-  int rc = mb_ring_slot(ctx, sizeof(int) * (3 * (size_t)npairs + nd), &slot);
-  if (rc) return rc;
-  int *h_pairs = x->mb_pairs[slot], *h_pair_d = h_pairs + 2 * (size_t)npairs, *h_distinct = h_pair_d + npairs;
-  memcpy(h_pairs, pairs, sizeof(int) * 2 * (size_t)npairs);
-  memcpy(h_pair_d, pair_d.data(), sizeof(int) * (size_t)npairs);
-  memcpy(h_distinct, distinct.data(), sizeof(int) * (size_t)nd);
-  rc = launch_match_guided_batch(ctx, npairs, h_pairs, h_pair_d, h_distinct, nd, (SiftPointD *)d_recs1, d_counts1,
-                                 d_offsets1, stride1, (const SiftPointD *)d_recs2, d_counts2, d_offsets2, stride2,
-                                 d_homography, radius, max_pts, d_num_found);
-  HIP_TRY(hipEventRecord(x->mb_done[slot], ctx->stream));
-  return rc;
+  RoctxRange range(__func__);
+  return run_batch(ctx,
+                   {{pairs, sizeof(int) * 2 * (size_t)npairs},
+                    {pair_d.data(), sizeof(int) * (size_t)npairs},
+                    {distinct.data(), sizeof(int) * (size_t)nd}},
+                   0, [&](int *h_pairs, void *) {
+                     const int *h_pair_d = h_pairs + 2 * (size_t)npairs;
+                     return launch_match_guided_batch(ctx, npairs, h_pairs, h_pair_d, h_pair_d + npairs, nd, set1,
+                                                      set2, d_homography, radius, max_pts, d_num_found);
+                   });
 }
 
 // 8-bit descriptors of every record of a device-resident batch, one stream-ordered launch with the counts on the device.
@@ -2243,11 +2251,13 @@ extern "C" int misift_quantize_batch(misift_ctx *ctx, const void *d_recs, int nf
 {
   ARG_CHECK(ctx && d_recs && d_counts && d_q && nframes >= 0);
   ARG_CHECK(((uintptr_t)d_q & 15) == 0);
-  ARG_CHECK(d_offsets || stride >= 0);
+  BatchLayout set;
+  int rc = batch_layout(__func__, d_recs, d_counts, d_offsets, stride, &set);
+  if (rc) return rc;
   if (nframes == 0) return MISIFT_OK;
-  RoctxRange range("misift_quantize_batch");
+  RoctxRange range(__func__);
   HIP_TRY(hipSetDevice(ctx->device));
-  return launch_quantize_batch(ctx, (const SiftPointD *)d_recs, nframes, d_counts, d_offsets, stride, d_q);
+  return launch_quantize_batch(ctx, set, nframes, d_q);
 }
 
 // misift_match_batch on 8-bit descriptors (int8 matrix cores): the same pairs, layouts, checks and stream semantics.
@@ -2260,24 +2270,16 @@ extern "C" int misift_match_batch_i8(misift_ctx *ctx, int npairs, const int *pai
   if (npairs == 0) return MISIFT_OK;
   ARG_CHECK(pairs && d_recs1 && d_recs2 && d_q1 && d_q2 && d_counts1 && d_counts2 && nframes1 > 0 && nframes2 > 0);
   ARG_CHECK(((uintptr_t)d_q1 & 15) == 0 && ((uintptr_t)d_q2 & 15) == 0);
-  ARG_CHECK(d_offsets1 || stride1 >= 0);
-  ARG_CHECK(d_offsets2 || stride2 >= 0);
-  int rc = check_match_pairs(npairs, pairs, nframes1, nframes2);
+  BatchLayout set1, set2;
+  int rc = batch_layout(__func__, d_recs1, d_counts1, d_offsets1, stride1, &set1);
+  if (!rc) rc = batch_layout(__func__, d_recs2, d_counts2, d_offsets2, stride2, &set2);
+  if (!rc) rc = check_frames(__func__, npairs, pairs, 2, nframes1, nframes2);
   if (rc) return rc;
-  RoctxRange range("misift_match_batch_i8");
-  HIP_TRY(hipSetDevice(ctx->device));
-  CtxExtra *x = extra(ctx);
-  int slot;
-  const size_t pair_bytes = sizeof(int) * 2 * (size_t)npairs;
-  rc = mb_ring_slot(ctx, pair_bytes, &slot);
-  if (rc) return rc;
-  memcpy(x->mb_pairs[slot], pairs, pair_bytes);
-  rc = ensure_mb_plan(ctx, match_i8_plan_bytes(npairs));
-  if (rc) return rc;
-  rc = launch_match_batch_i8(ctx, npairs, x->mb_pairs[slot], x->d_mb_plan, (SiftPointD *)d_recs1, d_q1, d_counts1,
-                             d_offsets1, stride1, (const SiftPointD *)d_recs2, d_q2, d_counts2, d_offsets2, stride2);
-  HIP_TRY(hipEventRecord(x->mb_done[slot], ctx->stream));
-  return rc;
+  RoctxRange range(__func__);
+  return run_batch(ctx, {{pairs, sizeof(int) * 2 * (size_t)npairs}}, pair_plan_bytes(npairs),
+                   [&](int *h_pairs, void *d_plan) {
+                     return launch_match_batch_i8(ctx, npairs, h_pairs, d_plan, set1, d_q1, set2, d_q2);
+                   });
 }
 
 // ------------------------------------------------------------------- timing
