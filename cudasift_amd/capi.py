@@ -96,6 +96,8 @@ SIGNATURES = {
     "misift_test_match_plan": (_i, [_i, _i, _i, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "misift_test_match_batch_plan": (_i, [_i, _i, _i, _vp, _vp, _vp, _ip, _ip, _ip]),
     "misift_match_batch": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i]),
+    "misift_match_pairs_batch": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp,
+                                      _vp]),
     "misift_find_homography_batch": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _f, _f, _f, _vp, _vp]),
     "misift_improve_homography_batch": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _f, _f, _f, _vp, _vp]),
     "misift_match_guided_batch": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _f, _i, _vp]),
@@ -533,6 +535,32 @@ class Context:
         check(lib().misift_match_batch(self.h, len(pairs), pairs.ctypes.data, _dptr(recs1), nframes1,
                                        _dptr(counts1), _dptr(offsets1), stride1, _dptr(recs2), nframes2,
                                        _dptr(counts2), _dptr(offsets2), stride2), "misift_match_batch")
+
+    def match_pairs_batch(self, pairs, recs1, nframes1, counts1, offsets1=None, stride1=0, recs2=None, nframes2=None,
+                          counts2=None, offsets2=None, stride2=None, max_pts=8192, mutual=False, out=None,
+                          out_counts=None, num_matched=None):
+        """misift_match_pairs_batch: match_batch into pair-indexed output rows — row r of pair i is the record
+        out[i * max_pts + r] (device, npairs * max_pts records, allocated here when None) — so frames may repeat across
+        pairs; with `mutual` only rows that are also their match's best row keep the match.  Frames and the set-2
+        default as in match_batch.  out_counts (npairs ints: n1, or -1 over max_pts) and num_matched (npairs ints: rows
+        with match >= 0, -1 over max_pts) are device buffers, allocated here when None; returns (out, out_counts,
+        num_matched).  Enqueued on the context stream."""
+        recs2, nframes2, counts2, offsets2, stride2 = _set2((recs1, nframes1, counts1, offsets1, stride1),
+                                                            (recs2, nframes2, counts2, offsets2, stride2))
+        pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        n = max(len(pairs), 1)
+        if out is None:
+            out = self.zeros(POINT_DTYPE.itemsize * n * max(max_pts, 1))
+        if out_counts is None:
+            out_counts = self.zeros(4 * n)
+        if num_matched is None:
+            num_matched = self.zeros(4 * n)
+        check(lib().misift_match_pairs_batch(self.h, len(pairs), pairs.ctypes.data, _dptr(recs1), nframes1,
+                                             _dptr(counts1), _dptr(offsets1), stride1, _dptr(recs2), nframes2,
+                                             _dptr(counts2), _dptr(offsets2), stride2, max_pts, int(mutual),
+                                             _dptr(out), _dptr(out_counts), _dptr(num_matched)),
+              "misift_match_pairs_batch")
+        return out, out_counts, num_matched
 
     def find_homography_batch(self, frames, seeds, recs, nframes, counts, offsets=None, stride=0, max_pts=8192,
                               num_loops=1000, min_score=0.85, max_ambiguity=0.95, thresh=5.0, homography=None,

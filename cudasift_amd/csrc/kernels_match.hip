@@ -93,6 +93,43 @@ template <int CTRL> __device__ __forceinline__ float quad_xchg(float v)
   return __builtin_bit_cast(float, quad_xchg<CTRL>(__builtin_bit_cast(int, v)));
 }
 
+// Column keys of misift_match_pairs_batch's mutual check (match_sweep.inc under MT_COL_KEYS): key = (fp32 bits of S) << 32
+// | (0xFFFFFFFF - row), so that for S > 0 the unsigned order of keys is (larger S, then smaller row) and an atomic max
+// over any cut of the rows and columns leaves the reversed match of the column: what misift_match with the sets swapped
+// finds in match_full + match_exact_top2 mode.  0 = no row with S > 0.
+// colkey_step over a lane's accumulator registers in ascending order (rows ascend with the register, match_sweep.inc):
+// strict '>' keeps the smallest row of a tie; NaN and S <= 0 never enter.
+__device__ __forceinline__ void colkey_step(float s, int r, float &kb, int &kr)
+{
+  const bool gt = s > kb;
+  kb = gt ? s : kb;
+  kr = gt ? r : kr;
+}
+// The lane's key for its column, combined with lane ^ 32 (the other 16 rows of the wavefront's 32), and one atomic max
+// per column from the lanes of half 0: 32 consecutive columns, 256 contiguous bytes.  A padded row (>= n1) is a copy of
+// row n1 - 1 (match_sweep.inc clamps the fetch), so its score is bit-identical to that row's: clamping its index to
+// last = n1 - 1 makes its key that row's key.
+__device__ __forceinline__ void colkey_flush(unsigned long long *key, float kb, int kr, int row0, int last, int half)
+{
+  const int row = min(row0 + (kr & 3) + 8 * (kr >> 2), last);
+  const unsigned hi = kb > 0.0f ? __float_as_uint(kb) : 0u, lo = kb > 0.0f ? 0xFFFFFFFFu - (unsigned)row : 0u;
+  const auto h2 = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);     // [1] in lanes 0-31: lane + 32's value
+  const auto l2 = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
+  const unsigned long long mine = ((unsigned long long)hi << 32) | lo;
+  const unsigned long long other = ((unsigned long long)(unsigned)h2[1] << 32) | (unsigned)l2[1];
+  const unsigned long long k = mine > other ? mine : other;
+  if (half == 0 && k != 0ull) __hip_atomic_fetch_max(key, k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+template <class V>
+__device__ __forceinline__ void colkey_tile(unsigned long long *key, const V &acc, int row0, int last, int half)
+{
+  float kb = 0.0f;
+  int kr = 0;
+#pragma unroll
+  for (int r = 0; r < 16; r++) colkey_step(acc[r], r, kb, kr);
+  colkey_flush(key, kb, kr, row0, last, half);
+}
+
 // One workgroup = 4 wavefronts = 128 rows of set 1; it sweeps a chunk of 64-column super-tiles of set 2.
 // Per super-tile every wavefront runs TWO independent accumulator chains (columns 0-31 and 32-63) of
 // 64 dependent v_mfma_f32_32x32x2_f32 each, interleaved, so the 64-cycle dependent-issue latency of one
@@ -381,50 +418,19 @@ __global__ __launch_bounds__(1024) void pair_plan_kernel(const int *__restrict__
                                                          BatchLayout set2, PairShape S, int *__restrict__ hdr,
                                                          PairPlan *__restrict__ plan)
 {
-  __shared__ int s_scan[16][2];
-  __shared__ long long s_sum[16];
-  const int tid = threadIdx.x;
-  long long rsum = 0;
-  for (int p = tid; p < npairs; p += 1024) {
-    const int f1 = pairs[2 * p], f2 = pairs[2 * p + 1];
-    PairPlan P;
-    P.n1 = max(set1.counts[f1], 0);
-    P.n2 = max(set2.counts[f2], 0);
-    P.off1 = (int)set1.base(f1);               // plan offsets are ints, as the API's offsets are
-    P.off2 = (int)set2.base(f2);
-    pair_shape(S, P.n1, P.n2, P.ncols, P.ntiles, P.nrb);
-    P.nchunks = 1; P.tpc = 1; P.item0 = 0; P.rb0 = 0; P.pad = 0;
-    plan[p] = P;
-    rsum += P.nrb;
-  }
-  for (int d = 32; d >= 1; d >>= 1) rsum += __shfl_down(rsum, d, 64);
-  if ((tid & 63) == 0) s_sum[tid >> 6] = rsum;
-  __syncthreads();
-  long long R = 0;
-  for (int w = 0; w < 16; w++) R += s_sum[w];
-  const int C = pair_batch_chunks(S, R);
-  int carry_items = 0, carry_rb = 0;
-  for (int base = 0; base < npairs; base += 1024) {
-    const int p = base + tid;                                  // the thread that wrote plan[p] above
-    int v[2] = {0, 0}, nch = 1, tpc = 1;                       // v: items, row blocks
-    if (p < npairs) {
-      pair_chunks(plan[p].ntiles, C, nch, tpc);
-      v[1] = plan[p].nrb;
-      v[0] = v[1] * nch;
-    }
-    int tot[2];
-    block_scan(v, tot, s_scan);
-    if (p < npairs) {
-      plan[p].nchunks = nch; plan[p].tpc = tpc;
-      plan[p].item0 = carry_items + v[0]; plan[p].rb0 = carry_rb + v[1];
-    }
-    carry_items += tot[0]; carry_rb += tot[1];
-  }
-  if (tid == 0) {
-    PairPlan E = {0, 0, 0, 0, 0, 0, 0, 1, 1, carry_items, carry_rb, 0};
-    plan[npairs] = E;
-    hdr[0] = carry_items; hdr[1] = C; hdr[2] = carry_rb; hdr[3] = 0;
-  }
+#define PAIR_PLAN_CAPPED 0
+#include "pair_plan_body.inc"
+#undef PAIR_PLAN_CAPPED
+}
+// misift_match_pairs_batch: oversized pairs get no work
+__global__ __launch_bounds__(1024) void pair_plan_capped_kernel(const int *__restrict__ pairs, int npairs,
+                                                                BatchLayout set1, BatchLayout set2, PairShape S,
+                                                                int max_pts, int *__restrict__ num_matched,
+                                                                int *__restrict__ hdr, PairPlan *__restrict__ plan)
+{
+#define PAIR_PLAN_CAPPED 1
+#include "pair_plan_body.inc"
+#undef PAIR_PLAN_CAPPED
 }
 
 size_t pair_plan_bytes(int npairs) { return sizeof(int) * PAIR_HDR_INTS + sizeof(PairPlan) * ((size_t)npairs + 1); }
@@ -468,7 +474,29 @@ int pair_plan_host(const PairShape &S, int npairs, const int *n1, const int *n2,
 
 // The reference's final combination of the eight class summaries of one row (matching.cu:375-390; exact second best
 // under match_exact_top2) and the row's five match fields — what match_merge_kernel does for a row of misift_match.
-// set2: the pair's set-2 records.
+// set2: the pair's set-2 records.  mb_combine: the same combination without the stores (match_pairs_final_kernel; kept
+// apart from mb_write_row, whose callers compile as they did).
+__device__ __forceinline__ void mb_combine(int exact_top2, const float (&cmax)[8], const float (&csec)[8],
+                                           const int (&cidx)[8], float &max_score, float &sec_score, int &index)
+{
+  if (exact_top2) {
+    max_score = cmax[0]; sec_score = csec[0]; index = cidx[0];
+#pragma unroll
+    for (int c = 1; c < 8; c++) top2_merge(max_score, sec_score, index, cmax[c], csec[c], cidx[c]);
+  } else {
+    max_score = cmax[0]; sec_score = csec[0]; index = cidx[0];
+#pragma unroll
+    for (int y = 0; y < 8; y++)
+      if (index != cidx[y]) {
+        if (cmax[y] > max_score) {
+          sec_score = fmaxf(max_score, sec_score);
+          max_score = cmax[y];
+          index = cidx[y];
+        } else if (cmax[y] > sec_score)
+          sec_score = cmax[y];
+      }
+  }
+}
 __device__ __forceinline__ void mb_write_row(SiftPointD *o, const float *set2, int exact_top2, const float (&cmax)[8],
                                              const float (&csec)[8], const int (&cidx)[8])
 {
@@ -642,5 +670,233 @@ int launch_match_batch(misift_ctx *ctx, int npairs, const int *h_pairs, void *d_
   LaunchScope ls(ctx, "match_batch_merge");
   hipLaunchKernelGGL(match_batch_merge_kernel, dim3(grid), dim3(256), 0, ctx->stream, set1.recs, f2, hdr, plan, npairs,
                      ctx->opt.match_exact_top2, partial);
+  return ls.finish();
+}
+
+// ============================================================================ pair-indexed matching (misift_match_pairs_batch)
+// The pairs of misift_match_batch, but every pair writes its own output rows out[i * max_pts + row], so that frames may
+// repeat across pairs, and with `mutual` only the rows that are also their column's reversed match keep their match.
+//   pair_plan_capped_kernel   the plan of match_batch (same PairShape), oversized pairs without work;
+//   (mutual) memset           the column keys of every (pair, column) to 0;
+//   match_pairs_kernel        the sweep of match_batch_kernel (match_sweep.inc); unchunked calls write the seven output
+//                             fields of their rows (and count them without mutual), chunked ones their partials; with
+//                             MUTUAL it maintains the column keys;
+//   match_pairs_final_kernel  per (pair, row): the chunk merge or the row the sweep wrote, the mutual test against the
+//                             key of its match, the final row, d_num_matched and d_out_counts.
+// recs1 / recs2 are read only; they may be the same array.
+__device__ __forceinline__ void mp_no_match(SiftPointD *o)
+{
+  o->score = 0.0f;
+  o->ambiguity = 0.0f;
+  o->match = -1;
+  o->match_xpos = 0.0f;
+  o->match_ypos = 0.0f;
+}
+
+template <bool MUTUAL>
+__global__ __launch_bounds__(64 * MT_WG_WAVES, 8 / MT_WG_WAVES) void match_pairs_kernel(const SiftPointD *recs1,
+                                                                                        const float *recs2,
+                                                                                        const int *__restrict__ hdr,
+                                                                                        const PairPlan *__restrict__ plan,
+                                                                                        int npairs, int exact_top2,
+                                                                                        int max_pts, SiftPointD *out,
+                                                                                        unsigned long long *keys,
+                                                                                        int *num_matched,
+                                                                                        float *__restrict__ partial)
+{
+  __shared__ float Bs[2][MT_SUPER * MT_BSTRIDE];
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int half = lane >> 5, col = lane & 31;
+  const int nitems = hdr[0], C = hdr[1];
+  for (int it = (int)xcd_remap(blockIdx.x, gridDim.x); it < nitems; it += gridDim.x) {
+    const int pi = pair_find<false>(plan, npairs, it);
+    const PairPlan P = plan[pi];
+    const int local = it - P.item0, rb = local / P.nchunks, chunk = local - rb * P.nchunks;
+    const int st0 = chunk * P.tpc, st1 = min(st0 + P.tpc, P.ntiles);
+    MatchGeom G;
+    G.row_begin = 0; G.row_count = P.n1; G.n1_total = P.n1;
+    G.n2 = P.n2; G.ncols = P.ncols;
+    G.ntiles = P.ntiles; G.nchunks = P.nchunks; G.tiles_per_chunk = P.tpc;
+    G.tile_base = 0; G.hole_begin = 0x7fffffff; G.hole_len = 0;
+    G.chunk_base = 0; G.nchunks_total = P.nchunks;
+    G.stride2 = MISIFT_POINT_BYTES / 4; G.data_off2 = 16; G.xy_off2 = 0;
+    const SiftPointD *pts1 = recs1 + P.off1;
+    const float *set2 = recs2 + (size_t)P.off2 * (MISIFT_POINT_BYTES / 4);
+    unsigned long long *const ck_keys = keys + (size_t)pi * max_pts;
+    const int ck_row0 = rb * MT_ROWS_PER_BLOCK + wave * 32 + 4 * half, ck_last = P.n1 - 1;
+#define MT_COL_KEYS MUTUAL
+#include "match_sweep.inc"
+#undef MT_COL_KEYS
+    bool matched = false;            // unchunked, no filter: the row's final match is known here, and counted here
+    if (C == 1) {
+      float *T = &Bs[0][0];
+      if ((lane & 3) == 0) {
+        const int cls = col >> 2;
+#pragma unroll
+        for (int r = 0; r < 16; r++) {
+          float *q = T + ((wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * half) * 8 + cls) * 3;
+          q[0] = mx[r];
+          q[1] = sec[r];
+          q[2] = __int_as_float(ix[r]);
+        }
+      }
+      __syncthreads();
+      const int row = rb * MT_ROWS_PER_BLOCK + tid;
+      if (tid < MT_ROWS_PER_BLOCK && row < P.n1) {
+        float cmax[8], csec[8];
+        int cidx[8];
+#pragma unroll
+        for (int c = 0; c < 8; c++) {
+          const float *q = T + (tid * 8 + c) * 3;
+          float m = 0.0f, sd = 0.0f;
+          int ixm = -1;
+          top2_merge(m, sd, ixm, q[0], q[1], __float_as_int(q[2]));
+          cmax[c] = m; csec[c] = sd; cidx[c] = ixm;
+        }
+        SiftPointD *o = out + (size_t)pi * max_pts + row;
+        o->xpos = pts1[row].xpos;
+        o->ypos = pts1[row].ypos;
+        mb_write_row(o, set2, exact_top2, cmax, csec, cidx);
+        if (!MUTUAL) matched = o->match >= 0;
+      }
+    } else if ((lane & 3) == 0) {
+      float *pb = partial + (size_t)it * MB_PART_FLOATS;
+      const int cls = col >> 2;
+#pragma unroll
+      for (int r = 0; r < 16; r++) {
+        const int rl = wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+        if (rb * MT_ROWS_PER_BLOCK + rl < P.n1) {
+          float *q = pb + (rl * 8 + cls) * 3;
+          q[0] = mx[r];
+          q[1] = sec[r];
+          reinterpret_cast<int *>(q)[2] = ix[r];
+        }
+      }
+    }
+    const int n = __syncthreads_count(matched);
+    if (!MUTUAL && tid == 0 && n > 0 && num_matched) atomicAdd(num_matched + pi, n);
+  }
+}
+
+// A unit is 32 rows of one pair, eight threads per row (one per class, as match_batch_merge_kernel); units of rows at or
+// above n1 and of oversized pairs only write the pair's count.
+__global__ __launch_bounds__(256) void match_pairs_final_kernel(const SiftPointD *recs1, const float *recs2,
+                                                                const int *__restrict__ hdr,
+                                                                const PairPlan *__restrict__ plan, int npairs,
+                                                                int exact_top2, int max_pts, int mutual,
+                                                                SiftPointD *out, int *__restrict__ out_counts,
+                                                                int *__restrict__ num_matched,
+                                                                const unsigned long long *__restrict__ keys,
+                                                                const float *__restrict__ partial)
+{
+  const int C = hdr[1];
+  const int groups = (max_pts + 31) / 32;
+  const long long nunits = (long long)npairs * groups;
+  const int rl = threadIdx.x >> 3, cls = threadIdx.x & 7;
+  for (long long u = blockIdx.x; u < nunits; u += gridDim.x) {
+    const int pi = (int)(u / groups), g = (int)(u - (long long)pi * groups);
+    const PairPlan P = plan[pi];
+    if (g == 0 && threadIdx.x == 0) out_counts[pi] = P.pad ? -1 : P.n1;
+    if (P.pad || g * 32 >= P.n1) continue;                       // uniform over the workgroup
+    if (!mutual && C == 1 && P.n2 > 0) continue;                 // the sweep wrote and counted these rows
+    const int row = g * 32 + rl;
+    const bool live = row < P.n1;
+    SiftPointD *o = out + (size_t)pi * max_pts + row;
+    const float *set2 = recs2 + (size_t)P.off2 * (MISIFT_POINT_BYTES / 4);
+    int index = -1;
+    float max_score = 0.0f, sec_score = 0.0f;
+    const bool lead = live && cls == 0;                           // the thread that writes the row
+    if (P.n2 == 0) {
+      if (lead) {                                                 // no column: a no-match row
+        o->xpos = recs1[P.off1 + row].xpos;
+        o->ypos = recs1[P.off1 + row].ypos;
+        mp_no_match(o);
+      }
+    } else if (C > 1) {
+      const int rb = row / MT_ROWS_PER_BLOCK, rr = row % MT_ROWS_PER_BLOCK;
+      float m = 0.0f, sd = 0.0f;
+      int ixm = -1;
+      if (live) {
+        const float *q = partial + (size_t)(P.item0 + rb * P.nchunks) * MB_PART_FLOATS + (rr * 8 + cls) * 3;
+        for (int ch = 0; ch < P.nchunks; ch++, q += MB_PART_FLOATS) top2_merge(m, sd, ixm, q[0], q[1], __float_as_int(q[2]));
+      }
+      float cmax[8], csec[8];
+      int cidx[8];
+#pragma unroll
+      for (int c = 0; c < 8; c++) {
+        cmax[c] = __shfl(m, c, 8);
+        csec[c] = __shfl(sd, c, 8);
+        cidx[c] = __shfl(ixm, c, 8);
+      }
+      if (lead) mb_combine(exact_top2, cmax, csec, cidx, max_score, sec_score, index);
+    } else if (lead) {
+      index = o->match;                                           // the row match_pairs_kernel wrote
+    }
+    // the mutual test: the column's key names its best row (0 cannot occur here: S of this row and its match is > 0)
+    const bool reject = mutual && index >= 0 && 0xFFFFFFFFu - (unsigned)keys[(size_t)pi * max_pts + index] != (unsigned)row;
+    if (reject) index = -1;
+    if (lead && P.n2 > 0 && C > 1) {
+      o->xpos = recs1[P.off1 + row].xpos;
+      o->ypos = recs1[P.off1 + row].ypos;
+      if (reject) {
+        mp_no_match(o);
+      } else {
+        o->score = max_score;
+        o->match = index;
+        const float *m2 = set2 + (size_t)(index >= 0 ? index : 0) * (MISIFT_POINT_BYTES / 4);
+        o->match_xpos = index >= 0 ? m2[0] : 0.0f;
+        o->match_ypos = index >= 0 ? m2[1] : 0.0f;
+        o->ambiguity = sec_score / (max_score + 1e-6f);
+      }
+    } else if (reject) {
+      mp_no_match(o);                                             // unchunked: xpos / ypos are the sweep's
+    }
+    const int n = __syncthreads_count(lead && index >= 0);
+    if (num_matched && threadIdx.x == 0 && n > 0) atomicAdd(num_matched + pi, n);
+  }
+}
+
+static size_t mp_keys_bytes(int npairs, int max_pts) { return sizeof(unsigned long long) * (size_t)npairs * max_pts; }
+
+// Enqueue misift_match_pairs_batch on the context stream (common.hpp): plan, (mutual) key memset, sweep, finalize.
+int launch_match_pairs_batch(misift_ctx *ctx, int npairs, const int *h_pairs, void *d_plan, const BatchLayout &set1,
+                             const BatchLayout &set2, int max_pts, int mutual, void *d_out, int *d_out_counts,
+                             int *d_num_matched)
+{
+  if (npairs <= 0) return MISIFT_OK;
+  const PairShape S = mb_shape(ctx->num_cus, ctx->opt.match_full);
+  const size_t part_bytes = (size_t)pair_partial_items(S) * MB_PART_FLOATS * sizeof(float);
+  const size_t key_bytes = mutual ? mp_keys_bytes(npairs, max_pts) : 0;
+  int rc = misift_ensure_tmp(ctx, part_bytes + key_bytes);
+  if (rc) return rc;
+  float *partial = reinterpret_cast<float *>(ctx->d_match_tmp);
+  unsigned long long *keys = mutual ? reinterpret_cast<unsigned long long *>((char *)ctx->d_match_tmp + part_bytes) : nullptr;
+  int *hdr = reinterpret_cast<int *>(d_plan);
+  PairPlan *plan = reinterpret_cast<PairPlan *>(hdr + PAIR_HDR_INTS);
+  {
+    LaunchScope ls(ctx, "match_pairs_plan");
+    hipLaunchKernelGGL(pair_plan_capped_kernel, dim3(1), dim3(1024), 0, ctx->stream, h_pairs, npairs, set1, set2, S,
+                       max_pts, d_num_matched, hdr, plan);
+    rc = ls.finish();
+    if (rc) return rc;
+  }
+  if (mutual) HIP_TRY(hipMemsetAsync(keys, 0, key_bytes, ctx->stream));
+  const float *f2 = reinterpret_cast<const float *>(set2.recs);
+  SiftPointD *out = reinterpret_cast<SiftPointD *>(d_out);
+  const int grid = S.target;
+  {
+    LaunchScope ls(ctx, "match_pairs_mfma");
+    if (mutual)
+      hipLaunchKernelGGL(match_pairs_kernel<true>, dim3(grid), dim3(64 * MT_WG_WAVES), 0, ctx->stream, set1.recs, f2,
+                         hdr, plan, npairs, ctx->opt.match_exact_top2, max_pts, out, keys, d_num_matched, partial);
+    else
+      hipLaunchKernelGGL(match_pairs_kernel<false>, dim3(grid), dim3(64 * MT_WG_WAVES), 0, ctx->stream, set1.recs, f2,
+                         hdr, plan, npairs, ctx->opt.match_exact_top2, max_pts, out, keys, d_num_matched, partial);
+    rc = ls.finish();
+    if (rc) return rc;
+  }
+  LaunchScope ls(ctx, "match_pairs_final");
+  hipLaunchKernelGGL(match_pairs_final_kernel, dim3(grid), dim3(256), 0, ctx->stream, set1.recs, f2, hdr, plan, npairs,
+                     ctx->opt.match_exact_top2, max_pts, mutual, out, d_out_counts, d_num_matched, keys, partial);
   return ls.finish();
 }

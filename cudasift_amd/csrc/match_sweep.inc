@@ -8,6 +8,12 @@
 // G.row_begin, 0 <= rb * 128 < G.row_count), st0 / st1 (virtual super-tiles to sweep), tid, wave, lane, half, col,
 // Bs[2][MT_SUPER * MT_BSTRIDE] (LDS).  Leaves in scope mx[16], sec[16], ix[16]: per lane (4c + j, half) and accumulator
 // row r, the exact top-2 of class c over the swept columns.  Bs is not read any more after the last barrier of the sweep.
+//
+// Column keys (match_pairs_kernel only: MT_COL_KEYS defined, as a constant expression that enables them): for every swept
+// column c < G.ncols, one vector global_atomic_max_u64 per wavefront of colkey(best score of the wavefront's 32 rows,
+// its smallest row) into ck_keys[c] (kernels_match.hip: colkey_step / colkey_flush).  Expects ck_keys, ck_row0 (the
+// row of accumulator register 0 of this lane: rb * 128 + wave * 32 + 4 * half) and ck_last (n1 - 1) in scope.  Where
+// MT_COL_KEYS is not defined the sweep is the one match_kernel and match_batch_kernel compile.
   // ---- A fragment: row (lane&31) of this wave, k = 2t + half, t = 0..63
   const int row_local = rb * MT_ROWS_PER_BLOCK + wave * 32 + col;          // within [0,row_count)
   const int row_ld = G.row_begin + min(row_local, G.row_count - 1);
@@ -120,6 +126,9 @@
 #ifndef MT_EXP_NOGLOAD
 #define MT_EXP_NOGLOAD 0
 #endif
+#if defined(MT_COL_KEYS) && (MT_TOP2_FILTER || !MT_PIPE_EPILOGUE)
+#error "the column keys live in the pipelined epilogue without MT_TOP2_FILTER"
+#endif
 #if (MT_EXP_NOBARRIER || MT_EXP_NOSTORE || MT_EXP_NOGLOAD) && !defined(MISIFT_TIMING_ONLY_BUILD)
 #error "MT_EXP_* are timing-only experiments that compute WRONG results: build them with -DMISIFT_TIMING_ONLY_BUILD (tools/variants.sh), never into libmisift.so"
 #endif
@@ -151,6 +160,10 @@
     acc1 = floatx16{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     const int pc0 = tile_col0(G, st - 1) + col, pc1 = pc0 + 32;          // columns of the previous tile
     const bool do0 = have_prev && pc0 < G.ncols, do1 = have_prev && pc1 < G.ncols;
+#ifdef MT_COL_KEYS
+    float kb = 0.0f;               // column key of the previous tile's column pc0 (slots 0-6), then pc1 (slots 8-14)
+    int kr = 0;
+#endif
     float4 p0 = b0[0], p1 = b1[0], q0, q1;
 #pragma unroll
     for (int i = 0; i < 16; i += 2) {
@@ -192,11 +205,26 @@
           if (do0) {
 #pragma unroll
             for (int r = 0; r < 4; r++) top2_update(prev0[t4 + r], pc0, mx[t4 + r], sec[t4 + r], ix[t4 + r]);
+#ifdef MT_COL_KEYS
+            if constexpr (MT_COL_KEYS) {
+#pragma unroll
+              for (int r = 0; r < 4; r++) colkey_step(prev0[t4 + r], t4 + r, kb, kr);
+              if (i == 6) colkey_flush(ck_keys + pc0, kb, kr, ck_row0, ck_last, half);
+            }
+#endif
           }
         } else {
           if (do1) {
 #pragma unroll
             for (int r = 0; r < 4; r++) top2_update(prev1[t4 + r], pc1, mx[t4 + r], sec[t4 + r], ix[t4 + r]);
+#ifdef MT_COL_KEYS
+            if constexpr (MT_COL_KEYS) {
+              if (i == 8) { kb = 0.0f; kr = 0; }
+#pragma unroll
+              for (int r = 0; r < 4; r++) colkey_step(prev1[t4 + r], t4 + r, kb, kr);
+              if (i == 14) colkey_flush(ck_keys + pc1, kb, kr, ck_row0, ck_last, half);
+            }
+#endif
           }
         }
 #endif
@@ -252,20 +280,32 @@
       if (c0 < G.ncols) {
 #pragma unroll
         for (int r = 0; r < 16; r++) top2_update(A0[r], c0, mx[r], sec[r], ix[r]);
+#ifdef MT_COL_KEYS
+        if constexpr (MT_COL_KEYS) colkey_tile(ck_keys + c0, A0, ck_row0, ck_last, half);
+#endif
       }
       if (c1 < G.ncols) {
 #pragma unroll
         for (int r = 0; r < 16; r++) top2_update(A1[r], c1, mx[r], sec[r], ix[r]);
+#ifdef MT_COL_KEYS
+        if constexpr (MT_COL_KEYS) colkey_tile(ck_keys + c1, A1, ck_row0, ck_last, half);
+#endif
       }
     } else if (have) {                    // the last tile of an even count sits in B
       const int c0 = tile_col0(G, st1 - 1) + col, c1 = c0 + 32;
       if (c0 < G.ncols) {
 #pragma unroll
         for (int r = 0; r < 16; r++) top2_update(B0[r], c0, mx[r], sec[r], ix[r]);
+#ifdef MT_COL_KEYS
+        if constexpr (MT_COL_KEYS) colkey_tile(ck_keys + c0, B0, ck_row0, ck_last, half);
+#endif
       }
       if (c1 < G.ncols) {
 #pragma unroll
         for (int r = 0; r < 16; r++) top2_update(B1[r], c1, mx[r], sec[r], ix[r]);
+#ifdef MT_COL_KEYS
+        if constexpr (MT_COL_KEYS) colkey_tile(ck_keys + c1, B1, ck_row0, ck_last, half);
+#endif
       }
     }
   }

@@ -2094,13 +2094,15 @@ static int batch_layout(const char *who, const void *recs, const int *counts, co
 }
 
 // A list of n entries of `step` ints: a frame of the first batch (nframes1 frames), and for pairs (step 2) a frame of
-// the second (nframes2 frames).  Every index in range; a frame of the first batch in at most one entry.
-static int check_frames(const char *who, int n, const int *list, int step, int nframes1, int nframes2)
+// the second (nframes2 frames).  Every index in range; a frame of the first batch in at most one entry unless `repeats`.
+static int check_frames(const char *who, int n, const int *list, int step, int nframes1, int nframes2,
+                        bool repeats = false)
 {
   std::vector<char> taken((size_t)nframes1, 0);
   for (int i = 0; i < n; i++) {
     const int f1 = list[step * i], f2 = step == 2 ? list[step * i + 1] : 0;
     ARG_CHECK_IN(who, f1 >= 0 && f1 < nframes1 && (step == 1 || (f2 >= 0 && f2 < nframes2)));
+    if (repeats) continue;
     ARG_CHECK_IN(who, !taken[f1]);
     taken[f1] = 1;
   }
@@ -2156,6 +2158,32 @@ extern "C" int misift_match_batch(misift_ctx *ctx, int npairs, const int *pairs,
   return run_batch(ctx, {{pairs, sizeof(int) * 2 * (size_t)npairs}}, pair_plan_bytes(npairs),
                    [&](int *h_pairs, void *d_plan) {
                      return launch_match_batch(ctx, npairs, h_pairs, d_plan, set1, set2);
+                   });
+}
+
+// misift_match_batch into pair-indexed output rows, with an optional mutual-nearest-neighbour check: frames may repeat.
+extern "C" int misift_match_pairs_batch(misift_ctx *ctx, int npairs, const int *pairs, const void *d_recs1,
+                                        int nframes1, const int *d_counts1, const int *d_offsets1, int stride1,
+                                        const void *d_recs2, int nframes2, const int *d_counts2, const int *d_offsets2,
+                                        int stride2, int max_pts, int mutual, void *d_out, int *d_out_counts,
+                                        int *d_num_matched)
+{
+  ARG_CHECK(ctx && npairs >= 0);
+  if (npairs == 0) return MISIFT_OK;
+  ARG_CHECK(pairs && d_recs1 && d_recs2 && d_counts1 && d_counts2 && d_out && d_out_counts && nframes1 > 0 &&
+            nframes2 > 0);
+  ARG_CHECK(max_pts >= 1 && (mutual == 0 || mutual == 1));
+  ARG_CHECK(d_out != d_recs1 && d_out != d_recs2);
+  BatchLayout set1, set2;
+  int rc = batch_layout(__func__, d_recs1, d_counts1, d_offsets1, stride1, &set1);
+  if (!rc) rc = batch_layout(__func__, d_recs2, d_counts2, d_offsets2, stride2, &set2);
+  if (!rc) rc = check_frames(__func__, npairs, pairs, 2, nframes1, nframes2, true);
+  if (rc) return rc;
+  RoctxRange range(__func__);
+  return run_batch(ctx, {{pairs, sizeof(int) * 2 * (size_t)npairs}}, pair_plan_bytes(npairs),
+                   [&](int *h_pairs, void *d_plan) {
+                     return launch_match_pairs_batch(ctx, npairs, h_pairs, d_plan, set1, set2, max_pts, mutual, d_out,
+                                                     d_out_counts, d_num_matched);
                    });
 }
 

@@ -360,6 +360,38 @@ int misift_match_rows(misift_ctx *ctx, void *d_pts1, int row_begin, int row_coun
 int misift_match_batch(misift_ctx *ctx, int npairs, const int *pairs,
                        void *d_recs1, int nframes1, const int *d_counts1, const int *d_offsets1, int stride1,
                        const void *d_recs2, int nframes2, const int *d_counts2, const int *d_offsets2, int stride2);
+/* Pair-indexed batch matching (no reference counterpart): the pairs, frames, layouts (d_offsets or stride), count -1 and
+ * stream semantics of misift_match_batch, but pair i writes its own output rows instead of the set-1 records, so that
+ * frames may repeat: windowed (f against f + 1 ... f + W), keyframe and exhaustive matching in one call.  For pair
+ * i = (f1, f2), n1 = max(count1[f1], 0) and n2 = max(count2[f2], 0).
+ *   - A set-1 frame and a set-2 frame may appear in any number of pairs; (f, f) and d_recs1 == d_recs2 are allowed.
+ *     Nothing in d_recs1 or d_recs2 is written.
+ *   - n1 > max_pts or n2 > max_pts: d_out_counts[i] = -1 and d_num_matched[i] = -1; none of the pair's output bytes is
+ *     written.  Otherwise d_out_counts[i] = n1, and output row r < n1 of pair i is the record d_out + (i * max_pts + r),
+ *     of which exactly seven fields are written: xpos and ypos (set-1 record r's), and score, ambiguity, match,
+ *     match_xpos, match_ypos, bit-identical to what misift_match on that pair writes into set-1 record r under the
+ *     context's match_full / match_exact_top2 options (what misift_match_batch writes).  n2 == 0: every row is a
+ *     no-match row (score 0, ambiguity 0, match -1, match_xpos 0, match_ypos 0).  Every other byte of d_out is untouched.
+ *   - mutual = 1 (cross-check): a row r with forward match m >= 0 keeps it only if r is the best row of column m over
+ *     all n1 rows — the largest score S_rm > 0, the smallest row on a tie: the match misift_match with the sets swapped
+ *     writes for set-2 record m in match_full + match_exact_top2 mode; otherwise it becomes a no-match row.  mutual = 0:
+ *     no filter.
+ *   - d_num_matched (may be NULL): per pair, the output rows with match >= 0 after the filter.
+ *   - The output is a batch the homography calls take as it is: frame i = pair i, d_offsets NULL, stride = max_pts,
+ *     counts = d_out_counts (misift_find_homography_batch, misift_improve_homography_batch).
+ *   - npairs < 0, a frame index outside [0, nframes) of its set, a NULL records, counts or output pointer, max_pts < 1,
+ *     mutual other than 0 or 1, d_out equal to d_recs1 or d_recs2: MISIFT_EINVAL, before anything is enqueued.
+ *     npairs == 0: nothing happens.
+ *   - The call returns before the GPU work is done.  `pairs` is host memory the library copies.  Three launches and,
+ *     with mutual, one memset, whatever npairs (plan, sweep, finalize); temp memory is sized from npairs, max_pts and
+ *     the CU count only.  Ordering behind batches in flight (K > 1): as misift_match_batch. */
+int misift_match_pairs_batch(misift_ctx *ctx, int npairs, const int *pairs,
+                             const void *d_recs1, int nframes1, const int *d_counts1, const int *d_offsets1, int stride1,
+                             const void *d_recs2, int nframes2, const int *d_counts2, const int *d_offsets2, int stride2,
+                             int max_pts, int mutual,
+                             void *d_out,          /* npairs * max_pts records (576 B each), device */
+                             int *d_out_counts,    /* npairs, device */
+                             int *d_num_matched);  /* npairs, device, may be NULL */
 
 /* Batches in flight (no reference counterpart: ExtractSift is synchronous, cudaSiftH.cu:72-144).  A context is one
  * in-order pipeline; with K > 1 it owns K child pipelines (own stream, counters, candidate lists, detection staging) and
