@@ -96,6 +96,7 @@ def lib():
         L.orc_match.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int]
         L.orc_match_rows.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, C.c_int]
         L.orc_match_argmax.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp]
+        L.orc_match_core.argtypes = [vp, C.c_long, C.c_int, vp, C.c_long, C.c_int, C.c_int] + [vp] * 8
         L.orc_find_homography.argtypes = [vp, C.c_int, fp, C.POINTER(C.c_int), C.c_int, C.c_float, C.c_float, C.c_float]
         L.orc_find_homography.restype = C.c_int
         L.orc_improve_homography.argtypes = [vp, C.c_int, fp, C.c_int, C.c_float, C.c_float, C.c_float]
@@ -317,6 +318,39 @@ def match(pts1, n1, pts2, n2, full=False, exact=False):
 def match_rows(pts1, row0, nrows, pts2, n2, full=False, exact=False):
     flags = (1 if full else 0) | (2 if exact else 0)
     lib().orc_match_rows(_p(pts1), row0, nrows, _p(pts2), n2, flags)
+
+
+def match_core(a, b, columns=True):
+    """orc_match_core over packed [n1,128] / [n2,128] float32 descriptors, both modes in one pass.  Returns a dict of
+    per-row arrays — cls_best / cls_idx / cls_sec: the reference mode's 8-class merge over the first 32*floor(n2/32)
+    columns; ex_best / ex_idx / ex_sec: the exact top-2 over all n2 columns — and, with `columns`, per column
+    col_best / col_row: the largest S > 0 and its row (the smallest on a tie, -1 for none), which is the match of the
+    reversed full + exact MatchSiftData."""
+    a = _f32(a).reshape(-1, 128)
+    b = _f32(b).reshape(-1, 128)
+    n1, n2 = a.shape[0], b.shape[0]
+    r = {k: np.zeros(n1, np.int32 if k.endswith("idx") else np.float32)
+         for k in ("cls_best", "cls_idx", "cls_sec", "ex_best", "ex_idx", "ex_sec")}
+    if columns:
+        r["col_best"], r["col_row"] = np.zeros(n2, np.float32), np.zeros(n2, np.int32)
+    lib().orc_match_core(_p(a), 128, n1, _p(b), 128, n2, 32 * (n2 // 32),
+                         *[_p(r[k]) for k in ("cls_best", "cls_idx", "cls_sec", "ex_best", "ex_idx", "ex_sec")],
+                         _p(r["col_best"]) if columns else None, _p(r["col_row"]) if columns else None)
+    return r
+
+
+def match_records(pts1, pts2, core, exact):
+    """The records MatchSiftData leaves in set 1 (a copy of pts1) from a match_core result: the reference mode's fields
+    (exact False: reference columns, 8-class merge) or full + exact's; match_xpos / match_ypos from pts2."""
+    pre = "ex_" if exact else "cls_"
+    best, idx, sec = core[pre + "best"], core[pre + "idx"], core[pre + "sec"]
+    out = pts1.copy()
+    out["score"], out["match"] = best, idx
+    mm = np.maximum(idx, 0)
+    out["match_xpos"] = np.where(idx >= 0, pts2["xpos"][mm], np.float32(0))
+    out["match_ypos"] = np.where(idx >= 0, pts2["ypos"][mm], np.float32(0))
+    out["ambiguity"] = sec / (best + np.float32(1e-6))
+    return out
 
 
 def match_argmax(a, b):

@@ -62,6 +62,7 @@
  * #9/#10 selectable, #11 never writes past n1, #13 ScaleDown guarded, descriptor
  * votes landing at index >= 128 (angi==8 in the last cell) are dropped.
  */
+#include <immintrin.h>
 #include <math.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -1469,6 +1470,163 @@ static inline float dot128(const float *a, const float *b)
 }
 float orc_dot128(const float *a, const float *b) { return dot128(a, b); }
 
+/* The matcher's one core: every row of a[n1] (row i at a + i*lda) against every column of b[n2] (column j at
+ * b + j*ldb), each score the dot128 chain.  Rows are cut into contiguous ranges, one per thread, and walked in blocks of
+ * MC_ROWS rows; set 2 is transposed into 32-column slabs of 16 KiB that stay in L1 while a block's rows pass over
+ * them, two rows at a time (eight independent 8-lane FMA chains).  Per row the columns arrive in ascending order.
+ * Outputs (any group may be NULL):
+ *   cls_*  the 8-class (best, index, runner-up) merge of matching.cu:375-390 over columns [0, ncls);
+ *   ex_*   the exact top-2 (best, index, second) over all n2 columns;
+ *   col_*  per column the best row: the largest S > 0, the smallest row on a tie (col_row -1: none).  Each thread
+ *          keeps its own column state over its ascending rows; the states are merged by (score, row). */
+#define MC_ROWS 256
+
+typedef struct {
+  float cmax[8], csec[8], emax, esec;
+  int cidx[8], eidx;
+} mc_row_t;
+
+static inline void mc_take(mc_row_t *R, const float *acc, int c0, int nb, int ncls)
+{
+  for (int j = 0; j < nb; j++) {                    /* ascending column within every class */
+    const int col = c0 + j;
+    const float sc = acc[j];
+    if (col < ncls) {
+      const int c = j >> 2;
+      if (sc > R->cmax[c]) { R->csec[c] = R->cmax[c]; R->cmax[c] = sc; R->cidx[c] = col; }
+      else if (sc > R->csec[c]) R->csec[c] = sc;
+    }
+    if (sc > R->emax) { R->esec = R->emax; R->emax = sc; R->eidx = col; }
+    else if (sc > R->esec) R->esec = sc;
+  }
+}
+
+/* lowest score that could still change the row's state over this slab (all updates need sc > a runner-up) */
+static inline float mc_floor(const mc_row_t *R, int cls_live)
+{
+  float t = R->esec;
+  if (cls_live)
+    for (int c = 0; c < 8; c++) t = R->csec[c] < t ? R->csec[c] : t;
+  return t;
+}
+
+void orc_match_core(const float *a, long lda, int n1, const float *b, long ldb, int n2, int ncls,
+                    float *cls_best, int *cls_idx, float *cls_sec, float *ex_best, int *ex_idx, float *ex_sec,
+                    float *col_best, int *col_row)
+{
+  if (n1 <= 0) return;
+  if (ncls > n2) ncls = n2;
+  const int nslab = (n2 + 31) / 32;
+  for (int j = 0; col_best && j < n2; j++) { col_best[j] = 0.0f; col_row[j] = -1; }
+  float *bt = (float *)aligned_alloc(64, sizeof(float) * 4096 * (size_t)(nslab > 0 ? nslab : 1));
+#pragma omp parallel for schedule(static)
+  for (int s = 0; s < nslab; s++)                   /* slab s: bt[s][k][32], zero past n2 */
+    for (int k = 0; k < 128; k++)
+      for (int j = 0; j < 32; j++) {
+        const int col = 32 * s + j;
+        bt[(size_t)s * 4096 + k * 32 + j] = col < n2 ? b[(size_t)col * ldb + k] : 0.0f;
+      }
+  int nthr = 1;
+#ifdef _OPENMP
+  nthr = omp_get_max_threads();
+#endif
+  if (nthr > (n1 + 1) / 2) nthr = (n1 + 1) / 2;
+  float *tcb = NULL;
+  int *tcr = NULL;
+  if (col_best) {
+    tcb = (float *)malloc(sizeof(float) * (size_t)n2 * nthr);
+    tcr = (int *)malloc(sizeof(int) * (size_t)n2 * nthr);
+  }
+#pragma omp parallel num_threads(nthr)
+  {
+    int t = 0;
+#ifdef _OPENMP
+    t = omp_get_thread_num();
+#endif
+    const int r0 = (int)((long long)n1 * t / nthr), r1 = (int)((long long)n1 * (t + 1) / nthr);
+    float *cb = tcb ? tcb + (size_t)n2 * t : NULL;
+    int *cr = tcr ? tcr + (size_t)n2 * t : NULL;
+    for (int j = 0; cb && j < n2; j++) { cb[j] = 0.0f; cr[j] = -1; }
+    mc_row_t *st = (mc_row_t *)malloc(sizeof(mc_row_t) * MC_ROWS);
+    for (int rb = r0; rb < r1; rb += MC_ROWS) {
+      const int nr = r1 - rb < MC_ROWS ? r1 - rb : MC_ROWS;
+      for (int i = 0; i < nr; i++) {
+        for (int c = 0; c < 8; c++) { st[i].cmax[c] = 0.0f; st[i].csec[c] = 0.0f; st[i].cidx[c] = -1; }
+        st[i].emax = 0.0f; st[i].esec = 0.0f; st[i].eidx = -1;
+      }
+      for (int s = 0; s < nslab; s++) {
+        const float *sl = bt + (size_t)s * 4096;
+        const int c0 = 32 * s, nb = n2 - c0 < 32 ? n2 - c0 : 32, cls_live = c0 < ncls;
+        for (int i = 0; i < nr; i += 2) {
+          const int two = i + 1 < nr;
+          const float *a0 = a + (size_t)(rb + i) * lda, *a1 = two ? a0 + lda : a0;
+          __m256 x[8];
+          for (int v = 0; v < 8; v++) x[v] = _mm256_setzero_ps();
+          for (int k = 0; k < 128; k++) {            /* per lane: s = fmaf(a[k], b[k], s), k ascending (dot128) */
+            const __m256 p = _mm256_broadcast_ss(a0 + k), q = _mm256_broadcast_ss(a1 + k);
+            for (int v = 0; v < 4; v++) {
+              const __m256 bk = _mm256_load_ps(sl + k * 32 + 8 * v);
+              x[v] = _mm256_fmadd_ps(p, bk, x[v]);
+              x[4 + v] = _mm256_fmadd_ps(q, bk, x[4 + v]);
+            }
+          }
+          float acc[2][32] __attribute__((aligned(32)));
+          for (int v = 0; v < 4; v++) { _mm256_store_ps(acc[0] + 8 * v, x[v]); _mm256_store_ps(acc[1] + 8 * v, x[4 + v]); }
+          for (int h = 0; h <= two; h++) {
+            mc_row_t *R = &st[i + h];
+            const __m256 fl = _mm256_set1_ps(mc_floor(R, cls_live));
+            int hit = 0;
+            for (int v = 0; v < 4; v++) hit |= _mm256_movemask_ps(_mm256_cmp_ps(x[4 * h + v], fl, _CMP_GT_OQ));
+            if (hit) mc_take(R, acc[h], c0, nb, ncls);
+            if (cb) {
+              const int row = rb + i + h;
+              float *pb = cb + c0;
+              int *pr = cr + c0;
+              for (int j = 0; j < nb; j++)           /* rows ascend within a thread: strict > keeps the smallest */
+                if (acc[h][j] > pb[j]) { pb[j] = acc[h][j]; pr[j] = row; }
+            }
+          }
+        }
+      }
+      for (int i = 0; i < nr; i++) {
+        const mc_row_t *R = &st[i];
+        const int r = rb + i;
+        if (cls_best) {                                /* matching.cu:375-390 */
+          float max_score = R->cmax[0], sec_score = R->csec[0];
+          int index = R->cidx[0];
+          for (int y = 0; y < 8; y++)
+            if (index != R->cidx[y]) {
+              if (R->cmax[y] > max_score) {
+                sec_score = fmaxf(max_score, sec_score);
+                max_score = R->cmax[y];
+                index = R->cidx[y];
+              } else if (R->cmax[y] > sec_score)
+                sec_score = R->cmax[y];
+            }
+          cls_best[r] = max_score; cls_idx[r] = index; cls_sec[r] = sec_score;
+        }
+        if (ex_best) { ex_best[r] = R->emax; ex_idx[r] = R->eidx; ex_sec[r] = R->esec; }
+      }
+    }
+    free(st);
+  }
+  if (col_best) {
+#pragma omp parallel for schedule(static)
+    for (int j = 0; j < n2; j++) {
+      float best = 0.0f;
+      int row = -1;
+      for (int t = 0; t < nthr; t++) {               /* by (score, row): the order of the threads does not matter */
+        const float s = tcb[(size_t)n2 * t + j];
+        const int r = tcr[(size_t)n2 * t + j];
+        if (r >= 0 && (s > best || (s == best && (row < 0 || r < row)))) { best = s; row = r; }
+      }
+      col_best[j] = best; col_row[j] = row;
+    }
+    free(tcb); free(tcr);
+  }
+  free(bt);
+}
+
 /* MatchSiftData: CleanMatches (matching.cu:289) + FindMaxCorr10 (:301-397).
  * flags bit0: use all n2 columns instead of 32*floor(n2/32) (Appendix B #9);
  * flags bit1: exact second best instead of the 8-class merge (Appendix B #10).
@@ -1477,59 +1635,25 @@ void orc_match_rows(SiftPoint *s1, int row0, int nrows, const SiftPoint *s2, int
 {
   const int full = flags & 1, exact = flags & 2;
   const int ncols = full ? n2 : 32 * (n2 / 32);
-  /* transposed copy of set 2 so the k-ordered chains of 32 columns vectorise */
-  float *bt = (float *)malloc(sizeof(float) * 128 * (size_t)(ncols > 0 ? ncols : 1));
-  for (int j = 0; j < ncols; j++)
-    for (int k = 0; k < 128; k++) bt[(size_t)k * ncols + j] = s2[j].data[k];
-#pragma omp parallel for schedule(dynamic, 8)
-  for (int r = row0; r < row0 + nrows; r++) {
-    const float *a = s1[r].data;
-    float cmax[8], csec[8];
-    int cidx[8];
-    for (int c = 0; c < 8; c++) { cmax[c] = 0.0f; csec[c] = 0.0f; cidx[c] = -1; }
-    float emax = 0.0f, esec = 0.0f;   /* exact top-2 */
-    int eidx = -1;
-    for (int bp2 = 0; bp2 < ncols; bp2 += 32) {
-      int nb = ncols - bp2 < 32 ? ncols - bp2 : 32;
-      float acc[32];
-      for (int j = 0; j < 32; j++) acc[j] = 0.0f;
-      for (int k = 0; k < 128; k++) {
-        const float ak = a[k];
-        const float *brow = bt + (size_t)k * ncols + bp2;
-        for (int j = 0; j < nb; j++) acc[j] = fmaf(ak, brow[j], acc[j]);
-      }
-      for (int j = 0; j < nb; j++) {                 /* ascending p2 within every class */
-        int c = j >> 2;
-        float sc = acc[j];
-        if (sc > cmax[c]) { csec[c] = cmax[c]; cmax[c] = sc; cidx[c] = bp2 + j; }
-        else if (sc > csec[c]) csec[c] = sc;
-        if (sc > emax) { esec = emax; emax = sc; eidx = bp2 + j; }
-        else if (sc > esec) esec = sc;
-      }
-    }
-    float max_score, sec_score;
-    int index;
-    if (exact) {
-      max_score = emax; sec_score = esec; index = eidx;
-    } else {                                         /* matching.cu:375-390 */
-      max_score = cmax[0]; sec_score = csec[0]; index = cidx[0];
-      for (int y = 0; y < 8; y++)
-        if (index != cidx[y]) {
-          if (cmax[y] > max_score) {
-            sec_score = fmaxf(max_score, sec_score);
-            max_score = cmax[y];
-            index = cidx[y];
-          } else if (cmax[y] > sec_score)
-            sec_score = cmax[y];
-        }
-    }
-    s1[r].score = max_score;
-    s1[r].match = index;
-    s1[r].match_xpos = index >= 0 ? s2[index].xpos : 0.0f;   /* never reads sift2[-1] */
-    s1[r].match_ypos = index >= 0 ? s2[index].ypos : 0.0f;
-    s1[r].ambiguity = sec_score / (max_score + 1e-6f);
+  if (nrows <= 0) return;
+  float *best = (float *)malloc(sizeof(float) * 2 * (size_t)nrows);
+  int *idx = (int *)malloc(sizeof(int) * (size_t)nrows);
+  float *sec = best + nrows;
+  const long ld = sizeof(SiftPoint) / sizeof(float);
+  if (exact)
+    orc_match_core(s1[row0].data, ld, nrows, s2[0].data, ld, ncols, 0, NULL, NULL, NULL, best, idx, sec, NULL, NULL);
+  else
+    orc_match_core(s1[row0].data, ld, nrows, s2[0].data, ld, ncols, ncols, best, idx, sec, NULL, NULL, NULL, NULL, NULL);
+  for (int i = 0; i < nrows; i++) {
+    SiftPoint *p = &s1[row0 + i];
+    const int index = idx[i];
+    p->score = best[i];
+    p->match = index;
+    p->match_xpos = index >= 0 ? s2[index].xpos : 0.0f;   /* never reads sift2[-1] */
+    p->match_ypos = index >= 0 ? s2[index].ypos : 0.0f;
+    p->ambiguity = sec[i] / (best[i] + 1e-6f);
   }
-  free(bt);
+  free(best); free(idx);
 }
 
 void orc_match(SiftPoint *s1, int n1, const SiftPoint *s2, int n2, int flags)
