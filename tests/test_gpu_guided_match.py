@@ -7,6 +7,7 @@ of both sets are compared: only the five match fields of set-1 rows of some pair
 import numpy as np
 import pytest
 
+from batch_util import MATCH_FIELDS, frames, guarded_context, layout, orc, same_bytes, span
 from synth import descriptors_to_points, synth_descriptors, synth_frame
 
 pytestmark = pytest.mark.gpu
@@ -17,13 +18,7 @@ SIZES2 = [4100, 2000, 129, 128, 127, 64, 33, 32, 31, 20, 1, 0, 300]
 PAIRS = [(i, (5 * i + 2) % 13) for i in range(13)]
 # one set-2 frame in several pairs; frame 1 is also set 1 of a pair; frame 6 has count -1
 KEYFRAME_PAIRS = [(0, 1), (2, 1), (5, 1), (7, 3), (10, 3), (11, 4), (13, 1), (1, 12), (6, 3)]
-MATCH_FIELDS = ("score", "ambiguity", "match", "match_xpos", "match_ypos")
 IMPROVE = dict(min_score=0.0, max_ambiguity=0.80, thresh=3.0)
-
-
-def _orc():
-    from oracle import pyoracle
-    return pyoracle
 
 
 def _homography(i, persp=True):
@@ -34,20 +29,6 @@ def _homography(i, persp=True):
                   [s * np.sin(a), s * np.cos(a), -7.0 + 0.5 * i],
                   [2e-5 * (i % 3) if persp else 0.0, -1e-5 if persp else 0.0, 1.0 + (0.03 if persp else 0.0)]])
     return H.astype(np.float32)
-
-
-def _frames(sizes, seed):
-    """Records with random descriptors, positions and (poisoned) other fields, so untouched bytes show."""
-    from cudasift_amd import capi
-    rng = np.random.default_rng(seed)
-    out = []
-    for f, n in enumerate(sizes):
-        p = descriptors_to_points(synth_descriptors(n, seed * 100 + f), capi.POINT_DTYPE)
-        for k in ("xpos", "ypos", "scale", "orientation", "score", "ambiguity", "match_xpos", "match_ypos", "match_error"):
-            p[k] = rng.random(n, dtype=np.float32) * 500
-        p["match"] = rng.integers(-5, 5000, n)
-        out.append(p)
-    return out
 
 
 def _plant(fr1, fr2, pairs, Hs, seed):
@@ -71,29 +52,9 @@ def _plant(fr1, fr2, pairs, Hs, seed):
             b[k2][dup + 1] = b[k2][dup]
 
 
-def _layout(frames, counts, padded):
-    """(records, offsets or None, stride): packed like misift_extract_batch_packed_async leaves it (a frame of count
-    -1 holds no records), or padded to a common stride with offsets = None."""
-    from cudasift_amd import capi
-    if padded:
-        stride = max(len(p) for p in frames)
-        recs = np.zeros(stride * len(frames), capi.POINT_DTYPE)
-        for f, p in enumerate(frames):
-            recs[f * stride:f * stride + len(p)] = p
-        return recs, None, stride
-    kept = [p if c >= 0 else p[:0] for p, c in zip(frames, counts)]
-    offs = np.concatenate([[0], np.cumsum([len(p) for p in kept])]).astype(np.int32)
-    return np.concatenate(kept), offs, 0
-
-
-def _span(offs, stride, f, n):
-    b = int(offs[f]) if offs is not None else f * stride
-    return slice(b, b + n)
-
-
 def _expected(pairs, Hs, radius, max_pts, recs1, counts1, offs1, stride1, recs2, counts2, offs2, stride2):
     """Set 1 and num_found after misift_match_guided_batch, restated from the contract with the oracle's matcher."""
-    o = _orc()
+    o = orc()
     exp = recs1.copy()
     nf = np.zeros(len(pairs), np.int32)
     r2 = np.float32(radius) * np.float32(radius)
@@ -104,9 +65,9 @@ def _expected(pairs, Hs, radius, max_pts, recs1, counts1, offs1, stride1, recs2,
             continue
         if n1 == 0 or n2 == 0:
             continue
-        s1 = _span(offs1, stride1, f1, n1)
+        s1 = span(offs1, stride1, f1, n1)
         p1 = exp[s1].copy()
-        p2 = recs2[_span(offs2, stride2, f2, n2)]
+        p2 = recs2[span(offs2, stride2, f2, n2)]
         h = np.asarray(Hs[i], np.float32).reshape(9)
         x, y = p1["xpos"], p1["ypos"]
         with np.errstate(all="ignore"):
@@ -151,15 +112,9 @@ def _run(c, pairs, Hs, radius, recs1, counts1, offs1, stride1, recs2=None, count
             c.download(nf, (len(pairs),), np.int32))
 
 
-def _same_bytes(a, b, what):
-    if a.tobytes() != b.tobytes():
-        bad = np.nonzero(a.view(np.uint8).reshape(len(a), -1) != b.view(np.uint8).reshape(len(b), -1))[0]
-        raise AssertionError("%s: %d records differ, first %s" % (what, len(np.unique(bad)), bad[:8]))
-
-
 def _parity_case(seed):
-    f1 = _frames(SIZES1, seed)
-    f2 = _frames(SIZES2, seed + 1)
+    f1 = frames(SIZES1, seed, False)
+    f2 = frames(SIZES2, seed + 1, False)
     Hs = [_homography(i) for i in range(len(PAIRS))]
     _plant(f1, f2, PAIRS, Hs, seed + 2)
     return f1, f2, Hs
@@ -169,16 +124,16 @@ def _parity_case(seed):
 @pytest.mark.parametrize("radius", [0.5, 10.0, 64.0])
 def test_parity_with_oracle(ctx, radius, padded):
     f1, f2, Hs = _parity_case(3)
-    r1, o1, s1 = _layout(f1, COUNTS1, padded)
-    r2, o2, s2 = _layout(f2, SIZES2, padded)
+    r1, o1, s1 = layout(f1, COUNTS1, padded, min_stride=0, pad_error=0.0)
+    r2, o2, s2 = layout(f2, SIZES2, padded, min_stride=0, pad_error=0.0)
     exp, enf = _expected(PAIRS, Hs, radius, 8192, r1, COUNTS1, o1, s1, r2, SIZES2, o2, s2)
     got1, got2, nf = _run(ctx, PAIRS, Hs, radius, r1, COUNTS1, o1, s1, r2, SIZES2, o2, s2)
-    _same_bytes(got1, exp, "set 1")
-    _same_bytes(got2, r2, "set 2 (read only)")
+    same_bytes(got1, exp, "set 1")
+    same_bytes(got2, r2, "set 2 (read only)")
     assert np.array_equal(nf, enf), (nf, enf)
     assert enf.sum() > 100, enf
     # ties for the best score were planted: the smallest index wins, and the runner-up is the same score
-    sl = _span(o1, s1, 10, 2000)
+    sl = span(o1, s1, 10, 2000)
     tie = got1["ambiguity"][sl] == got1["score"][sl] / (got1["score"][sl] + np.float32(1e-6))
     assert (tie & (got1["match"][sl] >= 0)).sum() > 10
 
@@ -187,23 +142,23 @@ def test_keyframe_pairs_and_shared_buffer(ctx):
     """A set-2 frame in several pairs, and d_recs1 == d_recs2 (frames of one packed batch against each other)."""
     sizes = [300, 2000, 129, 1, 33, 64, 0, 128, 127, 31, 500, 77, 4100, 20]
     counts = sizes[:6] + [-1] + sizes[7:]
-    fr = _frames(sizes, 11)
+    fr = frames(sizes, 11, False)
     Hs = [_homography(i) for i in range(len(KEYFRAME_PAIRS))]
     _plant(fr, fr, KEYFRAME_PAIRS, Hs, 12)
-    recs, offs, _ = _layout(fr, counts, False)
+    recs, offs, _ = layout(fr, counts, False, min_stride=0, pad_error=0.0)
     exp, enf = _expected(KEYFRAME_PAIRS, Hs, 12.0, 8192, recs, counts, offs, 0, recs, counts, offs, 0)
     got, _, nf = _run(ctx, KEYFRAME_PAIRS, Hs, 12.0, recs, counts, offs, 0)
     # set 2 is the input batch itself: the oracle read the positions and descriptors of `recs`, which the call never
     # writes, so every byte of the shared buffer must equal the restated set 1
-    _same_bytes(got, exp, "shared batch")
+    same_bytes(got, exp, "shared batch")
     assert np.array_equal(nf, enf), (nf, enf)
 
 
 @pytest.mark.parametrize("n1,n2", [(2000, 4100), (33, 129)])
 def test_unbounded_radius_identity_equals_exact_full_match(ctx, n1, n2):
     """radius = +inf and the identity H: every record is a candidate, so the call equals misift_match in exact, full mode."""
-    f1 = _frames([n1], 21)
-    f2 = _frames([n2], 22)
+    f1 = frames([n1], 21, False)
+    f2 = frames([n2], 22, False)
     got, _, nf = _run(ctx, [(0, 0)], [np.eye(3, dtype=np.float32)], float("inf"), f1[0], [n1], None, n1,
                       f2[0], [n2], None, n2)
     ctx.set_options(match_full=1, match_exact_top2=1)
@@ -211,7 +166,7 @@ def test_unbounded_radius_identity_equals_exact_full_match(ctx, n1, n2):
         exp = ctx.match(f1[0].copy(), n1, f2[0].copy(), n2)
     finally:
         ctx.set_options(match_full=0, match_exact_top2=0)
-    _same_bytes(got, exp, "set 1")
+    same_bytes(got, exp, "set 1")
     assert nf[0] == (exp["match"] >= 0).sum() == n1
 
 
@@ -249,7 +204,7 @@ def test_guided_match_rejects_decoys(ctx):
     assert np.array_equal(guided["match"], np.arange(n))
     assert ctx.download(nf, (1,), np.int32)[0] == n
     exp, enf = _expected([(0, 0)], [H], radius, 8192, s1, [n], None, n, s2, [2 * n], None, 2 * n)
-    _same_bytes(guided, exp, "guided rows")
+    same_bytes(guided, exp, "guided rows")
     assert enf[0] == n
 
 
@@ -292,7 +247,7 @@ def test_chain_behind_real_extraction(ctx):
     # the extraction and improve's match_error; the restatement only reads positions and descriptors)
     exp, enf = _expected(pairs, list(H), 4.0, mp, got, counts, offs, 0, got, counts, offs, 0)
     for i, (f1, _) in enumerate(pairs):
-        s1 = _span(offs, 0, f1, int(counts[f1]))
+        s1 = span(offs, 0, f1, int(counts[f1]))
         for k in MATCH_FIELDS:
             assert np.array_equal(exp[s1][k], got[s1][k]), (f1, k)
     assert np.array_equal(nf, enf), (nf, enf)
@@ -301,7 +256,7 @@ def test_chain_behind_real_extraction(ctx):
     # improve ran on the guided matches: H, num_fit and match_error as the single call from find's H
     for i, (f1, _) in enumerate(pairs):
         n1 = int(counts[f1])
-        s1 = _span(offs, 0, f1, n1)
+        s1 = span(offs, 0, f1, n1)
         dm = ctx.upload(got[s1].copy())
         He, nfe = ctx.improve_homography(dm.ptr, n1, H[i], 5, **IMPROVE)
         after = ctx.download(dm, (n1,), capi.POINT_DTYPE)
@@ -313,10 +268,10 @@ def test_edge_cases(ctx):
     """NaN H and a zero denominator: no candidate, no fault.  A radius whose square underflows: no candidate.  max_pts
     overflow on either side: -1, set 1 untouched.  Two runs: the same bytes."""
     sizes1, sizes2 = [150, 60, 90, 80, 70], [50, 150, 90, 80, 70]
-    f1 = _frames(sizes1, 51)
-    f2 = _frames(sizes2, 52)
-    r1, o1, _ = _layout(f1, sizes1, False)
-    r2, o2, _ = _layout(f2, sizes2, False)
+    f1 = frames(sizes1, 51, False)
+    f2 = frames(sizes2, 52, False)
+    r1, o1, _ = layout(f1, sizes1, False, min_stride=0, pad_error=0.0)
+    r2, o2, _ = layout(f2, sizes2, False, min_stride=0, pad_error=0.0)
     nan_h = np.full((3, 3), np.nan, np.float32)
     zero_den = _homography(1)
     zero_den[2] = 0.0
@@ -324,24 +279,24 @@ def test_edge_cases(ctx):
     Hs = [np.eye(3, dtype=np.float32), np.eye(3, dtype=np.float32), nan_h, zero_den, np.eye(3, dtype=np.float32)]
     f2[4]["xpos"] = f1[4]["xpos"][:70]                 # exact coincidences: err = 0, still not < fl(1e-30^2) = 0
     f2[4]["ypos"] = f1[4]["ypos"][:70]
-    r2, o2, _ = _layout(f2, sizes2, False)
+    r2, o2, _ = layout(f2, sizes2, False, min_stride=0, pad_error=0.0)
     for radius in (1e-30, 50.0):
         got1, got2, nf = _run(ctx, pairs, Hs, radius, r1, sizes1, o1, 0, r2, sizes2, o2, 0, max_pts=100)
         again1, _, nf2 = _run(ctx, pairs, Hs, radius, r1, sizes1, o1, 0, r2, sizes2, o2, 0, max_pts=100)
-        _same_bytes(got1, again1, "two runs")
+        same_bytes(got1, again1, "two runs")
         assert np.array_equal(nf, nf2)
         exp, enf = _expected(pairs, Hs, radius, 100, r1, sizes1, o1, 0, r2, sizes2, o2, 0)
-        _same_bytes(got1, exp, "set 1, radius %g" % radius)
-        _same_bytes(got2, r2, "set 2")
+        same_bytes(got1, exp, "set 1, radius %g" % radius)
+        same_bytes(got2, r2, "set 2")
         assert nf[0] == -1 and nf[1] == -1 and nf[2] == 0 and nf[3] == 0, nf
         for f in (0, 1):                               # over max_pts: untouched
-            sl = _span(o1, 0, f, sizes1[f])
-            _same_bytes(got1[sl], r1[sl], "frame %d over max_pts" % f)
+            sl = span(o1, 0, f, sizes1[f])
+            same_bytes(got1[sl], r1[sl], "frame %d over max_pts" % f)
         for f in (2, 3):                               # NaN H, zero denominator: nothing matched
-            sl = _span(o1, 0, f, sizes1[f])
+            sl = span(o1, 0, f, sizes1[f])
             assert (got1["match"][sl] == -1).all() and (got1["score"][sl] == 0).all()
             assert (got1["ambiguity"][sl] == 0).all() and (got1["match_xpos"][sl] == 0).all()
-        sl = _span(o1, 0, 4, 70)
+        sl = span(o1, 0, 4, 70)
         if radius < 1:
             assert nf[4] == 0 and (got1["match"][sl] == -1).all()
         else:
@@ -352,7 +307,7 @@ def test_argument_errors(ctx):
     """Every MISIFT_EINVAL case returns before anything is enqueued: the poisoned outputs stay as they were."""
     from cudasift_amd import capi
     L = capi.lib()
-    fr = _frames([32, 32], 61)
+    fr = frames([32, 32], 61, False)
     recs_h = np.concatenate(fr)
     recs = ctx.upload(recs_h)
     counts = ctx.upload(np.array([32, 32], np.int32))
@@ -392,23 +347,14 @@ def test_guard_mode(ctx):
     bytes as the unguarded context."""
     from cudasift_amd import capi
     f1, f2, Hs = _parity_case(71)
-    r1, o1, s1 = _layout(f1, COUNTS1, False)
-    r2, o2, s2 = _layout(f2, SIZES2, False)
-    old = capi.set_guard(True)
-    try:
-        g = capi.Context(0)
-        try:
-            got = _run(g, PAIRS, Hs, 10.0, r1, COUNTS1, o1, s1, r2, SIZES2, o2, s2)
-            inf = _run(g, [(10, 1)], [np.eye(3, dtype=np.float32)], float("inf"), r1, COUNTS1, o1, s1, r2, SIZES2, o2, s2)
-            n = capi.check_guards()
-            assert n >= 3, n
-        finally:
-            g.close()
-    finally:
-        capi.set_guard(old)
+    r1, o1, s1 = layout(f1, COUNTS1, False, min_stride=0, pad_error=0.0)
+    r2, o2, s2 = layout(f2, SIZES2, False, min_stride=0, pad_error=0.0)
+    with guarded_context(3) as g:
+        got = _run(g, PAIRS, Hs, 10.0, r1, COUNTS1, o1, s1, r2, SIZES2, o2, s2)
+        inf = _run(g, [(10, 1)], [np.eye(3, dtype=np.float32)], float("inf"), r1, COUNTS1, o1, s1, r2, SIZES2, o2, s2)
     assert capi.check_guards() >= 0
     again = _run(ctx, PAIRS, Hs, 10.0, r1, COUNTS1, o1, s1, r2, SIZES2, o2, s2)
-    _same_bytes(got[0], again[0], "guarded vs unguarded")
+    same_bytes(got[0], again[0], "guarded vs unguarded")
     assert np.array_equal(got[2], again[2])
     again = _run(ctx, [(10, 1)], [np.eye(3, dtype=np.float32)], float("inf"), r1, COUNTS1, o1, s1, r2, SIZES2, o2, s2)
-    _same_bytes(inf[0], again[0], "guarded vs unguarded, radius inf")
+    same_bytes(inf[0], again[0], "guarded vs unguarded, radius inf")

@@ -9,6 +9,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from batch_util import guarded_context, layout, orc, span
 from synth import synth_frame, synth_matches
 
 pytestmark = pytest.mark.gpu
@@ -19,11 +20,6 @@ IMPROVE = dict(min_score=0.0, max_ambiguity=0.80, thresh=3.0)
 IDENTITY = np.eye(3, dtype=np.float32)
 
 
-def _orc():
-    from oracle import pyoracle
-    return pyoracle
-
-
 def _frames(sizes, seed):
     from cudasift_amd import capi
     out = []
@@ -32,34 +28,13 @@ def _frames(sizes, seed):
     return out
 
 
-def _layout(frames, counts, padded):
-    """(records, offsets or None, stride): packed as misift_extract_batch_packed_async leaves it (a frame of count -1 holds
-    no records), or padded to a common stride with offsets = None."""
-    from cudasift_amd import capi
-    if padded:
-        stride = max(max(len(p) for p in frames), 1)
-        recs = np.zeros(stride * len(frames), capi.POINT_DTYPE)
-        recs["match_error"] = -7.0
-        for f, p in enumerate(frames):
-            recs[f * stride:f * stride + len(p)] = p
-        return recs, None, stride
-    kept = [p if c >= 0 else p[:0] for p, c in zip(frames, counts)]
-    offs = np.concatenate([[0], np.cumsum([len(p) for p in kept])]).astype(np.int32)
-    return np.concatenate(kept), offs, 0
-
-
-def _span(offs, stride, f, n):
-    b = int(offs[f]) if offs is not None else f * stride
-    return slice(b, b + n)
-
-
 def _bits(a):
     return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 def _single_find(ctx, recs, n, seed, loops, oracle=True):
     """srand(seed) + misift_find_homography on one frame (and the oracle after the same srand)."""
-    o = _orc()
+    o = orc()
     if n < 8:
         return IDENTITY, 0
     d = ctx.upload(recs)
@@ -88,7 +63,7 @@ def _check_find(ctx, frames_sel, seeds, recs, counts, offs, stride, loops, oracl
     H, nm = _run_find(ctx, frames_sel, seeds, recs, counts, offs, stride, loops)
     for i, (f, s) in enumerate(zip(frames_sel, seeds)):
         n = max(int(counts[f]), 0)
-        He, ne = _single_find(ctx, recs[_span(offs, stride, f, n)].copy(), n, s, loops, oracle)
+        He, ne = _single_find(ctx, recs[span(offs, stride, f, n)].copy(), n, s, loops, oracle)
         assert nm[i] == ne and np.array_equal(_bits(H[i]), _bits(He)), (i, f, n, loops, nm[i], ne)
     return H, nm
 
@@ -97,7 +72,7 @@ def _check_find(ctx, frames_sel, seeds, recs, counts, offs, stride, loops, oracl
 @pytest.mark.parametrize("loops", [50, 1000])
 def test_find_bit_identical(ctx, padded, loops):
     fr = _frames(SIZES, 3)
-    recs, offs, stride = _layout(fr, SIZES, padded)
+    recs, offs, stride = layout(fr, SIZES, padded, min_stride=1, pad_error=-7.0)
     sel = [6, 0, 4, 1, 5, 3, 2]                       # not in frame order
     seeds = [11, 12, 13, 0, 2**32 - 1, 12345, 7]
     H, nm = _check_find(ctx, sel, seeds, recs, SIZES, offs, stride, loops, oracle=loops <= 1000)
@@ -112,7 +87,7 @@ def test_find_ragged_and_degenerate(ctx):
     fr[2]["score"] = 0.0                              # only 5 valid points left in frame 2
     fr[2]["score"][[3, 50, 100, 200, 299]] = 0.99
     fr[2]["ambiguity"] = 0.5
-    recs, offs, stride = _layout(fr, counts, False)
+    recs, offs, stride = layout(fr, counts, False, min_stride=1, pad_error=-7.0)
     sel = [0, 1, 2, 3, 4]
     H, nm = _check_find(ctx, sel, [1, 2, 3, 4, 5], recs, counts, offs, stride, 1000)
     for i in (1, 2, 4):
@@ -122,14 +97,14 @@ def test_find_ragged_and_degenerate(ctx):
 def test_find_10000_loops(ctx):
     sizes = [40, 1500]
     fr = _frames(sizes, 9)
-    recs, offs, stride = _layout(fr, sizes, False)
+    recs, offs, stride = layout(fr, sizes, False, min_stride=1, pad_error=-7.0)
     _check_find(ctx, [0, 1], [99, 100], recs, sizes, offs, stride, 10000)
 
 
 def test_process_rand_state_untouched(ctx):
-    o = _orc()
+    o = orc()
     fr = _frames([777, 1500], 4)
-    recs, offs, stride = _layout(fr, [777, 1500], False)
+    recs, offs, stride = layout(fr, [777, 1500], False, min_stride=1, pad_error=-7.0)
     LIBC = C.CDLL(None)
     o.srand(5)
     expect = [LIBC.rand() for _ in range(64)]
@@ -156,7 +131,7 @@ def test_improve_bit_identical(ctx, padded, loops):
     sizes = [1500, 0, 777, 40, 5000, 300]
     counts = [1500, 0, 777, -1, 5000, 300]             # frame 5: in no entry
     fr = _frames(sizes, 6)
-    recs, offs, stride = _layout(fr, counts, padded)
+    recs, offs, stride = layout(fr, counts, padded, min_stride=1, pad_error=-7.0)
     recs["match_error"] = np.arange(len(recs), dtype=np.float32) * 0.5 - 3.0
     sel = [4, 0, 3, 1, 2]
     H0 = []
@@ -168,7 +143,7 @@ def test_improve_bit_identical(ctx, padded, loops):
     exp = recs.copy()
     for i, f in enumerate(sel):
         n = max(counts[f], 0)
-        sl = _span(offs, stride, f, n)
+        sl = span(offs, stride, f, n)
         d = ctx.upload(recs[sl].copy()) if n else ctx.zeros(576)      # a frame with no records: start pointer, 0 records
         He, ne = ctx.improve_homography(d.ptr, n, H0[i], loops, **IMPROVE)
         if n:
@@ -182,29 +157,19 @@ def test_improve_bit_identical(ctx, padded, loops):
 def test_count_above_max_pts_guarded(ctx):
     """A frame whose device count exceeds max_pts gets -1 and the identity H, and nothing past its records is read: the
     buffer ends where the frame's real records end.  On a guarded context (temp starts as 0xFF, bands checked)."""
-    from cudasift_amd import capi
     sizes = [1500, 300, 777]
     fr = _frames(sizes, 8)
-    recs, offs, _ = _layout(fr, sizes, False)
+    recs, offs, _ = layout(fr, sizes, False, min_stride=1, pad_error=-7.0)
     counts = np.array([1500, 5000, 777], np.int32)     # frame 1 claims 5000 records; 300 exist, the buffer ends after it
     order = [0, 2, 1]
     fr2 = [fr[i] for i in order]
     recs = np.concatenate(fr2)
     offs = np.array([0, 1500 + 777, 1500, len(recs)], np.int32)
-    old = capi.set_guard(True)
-    try:
-        g = capi.Context(0)
-        try:
-            H, nm = _run_find(g, [0, 1, 2], [1, 2, 3], recs, counts, offs, 0, 1000, max_pts=2000)
-            n = capi.check_guards()
-            assert n >= 3, n
-        finally:
-            g.close()
-    finally:
-        capi.set_guard(old)
+    with guarded_context(3) as g:
+        H, nm = _run_find(g, [0, 1, 2], [1, 2, 3], recs, counts, offs, 0, 1000, max_pts=2000)
     assert nm[1] == -1 and np.array_equal(_bits(H[1]), _bits(IDENTITY)), nm
     for i, f in ((0, 0), (2, 2)):
-        He, ne = _single_find(ctx, recs[_span(offs, 0, f, int(counts[f]))].copy(), int(counts[f]), i + 1, 1000,
+        He, ne = _single_find(ctx, recs[span(offs, 0, f, int(counts[f]))].copy(), int(counts[f]), i + 1, 1000,
                               oracle=False)
         assert nm[i] == ne and np.array_equal(_bits(H[i]), _bits(He)), (i, nm[i], ne)
 
@@ -250,7 +215,7 @@ def test_chain_behind_real_extraction(ctx):
     """misift_extract_batch_packed_async -> misift_match_batch (f, f + 1) -> find batch -> improve batch, with no host read
     in between, against the synchronous per-pair chain on the same records."""
     from cudasift_amd import capi
-    o = _orc()
+    o = orc()
     B, h, w, mp = 6, 480, 640, 4096
     frames = np.stack([synth_frame(f, w, h) for f in range(B)]).astype(np.float32)
     frames[1:] = np.stack([np.roll(frames[0], (2 * f, 3 * f), axis=(0, 1)) for f in range(1, B)])
@@ -278,7 +243,7 @@ def test_chain_behind_real_extraction(ctx):
     assert (counts > 100).all(), counts
     for i, (f1, f2) in enumerate(pairs):
         n1, n2 = int(counts[f1]), int(counts[f2])
-        s1, s2 = _span(offs, 0, f1, n1), _span(offs, 0, f2, n2)
+        s1, s2 = span(offs, 0, f1, n1), span(offs, 0, f2, n2)
         m = ctx.match(got[s1].copy(), n1, got[s2].copy(), n2)
         for k in ("score", "ambiguity", "match", "match_xpos", "match_ypos"):
             assert np.array_equal(m[k], got[s1][k]), (f1, k)

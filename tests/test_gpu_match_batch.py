@@ -5,7 +5,8 @@ everything else — other fields, frames in no pair, pairs with an empty side, p
 import numpy as np
 import pytest
 
-from synth import descriptors_to_points, synth_descriptors, synth_frame
+from batch_util import MATCH_FIELDS, frames, guarded_context, layout, num_cus, orc, same_bytes, sequence_case, span
+from synth import synth_frame
 
 pytestmark = pytest.mark.gpu
 
@@ -13,46 +14,6 @@ SIZES1 = [0, 1, 20, 31, 32, 33, 64, 127, 128, 129, 2000, 4100, 50, 77]   # frame
 COUNTS1 = SIZES1[:12] + [-1, 77]
 SIZES2 = [4100, 2000, 129, 128, 127, 64, 33, 32, 31, 20, 1, 0, 300]
 PAIRS = [(i, (5 * i + 2) % 13) for i in range(13)]
-MATCH_FIELDS = ("score", "ambiguity", "match", "match_xpos", "match_ypos")
-
-
-def _orc():
-    from oracle import pyoracle
-    return pyoracle
-
-
-def _frames(sizes, seed, l2=False):
-    """Records with random descriptors, positions and (poisoned) other fields, so untouched bytes show."""
-    from cudasift_amd import capi
-    rng = np.random.default_rng(seed)
-    out = []
-    for f, n in enumerate(sizes):
-        p = descriptors_to_points(synth_descriptors(n, seed * 100 + f, l2), capi.POINT_DTYPE)
-        for k in ("xpos", "ypos", "scale", "orientation", "score", "ambiguity", "match_xpos", "match_ypos", "match_error"):
-            p[k] = rng.random(n, dtype=np.float32) * 500
-        p["match"] = rng.integers(-5, 5000, n)
-        out.append(p)
-    return out
-
-
-def _layout(frames, counts, padded):
-    """(records, offsets or None, stride): packed like misift_extract_batch_packed_async leaves it (a frame of count
-    -1 holds no records), or padded to a common stride with offsets = None."""
-    from cudasift_amd import capi
-    if padded:
-        stride = max(len(p) for p in frames)
-        recs = np.zeros(stride * len(frames), capi.POINT_DTYPE)
-        for f, p in enumerate(frames):
-            recs[f * stride:f * stride + len(p)] = p
-        return recs, None, stride
-    kept = [p if c >= 0 else p[:0] for p, c in zip(frames, counts)]
-    offs = np.concatenate([[0], np.cumsum([len(p) for p in kept])]).astype(np.int32)
-    return np.concatenate(kept), offs, 0
-
-
-def _span(offs, stride, f, n):
-    b = int(offs[f]) if offs is not None else f * stride
-    return slice(b, b + n)
 
 
 def _run_batch(c, pairs, recs1, counts1, offs1, stride1, recs2=None, counts2=None, offs2=None, stride2=0):
@@ -73,7 +34,7 @@ def _run_batch(c, pairs, recs1, counts1, offs1, stride1, recs2=None, counts2=Non
 
 def _expected(ctx, pairs, recs1, counts1, offs1, stride1, recs2, counts2, offs2, stride2, full, exact, oracle=True):
     """Set 1 after one misift_match per pair (and the same rows from the oracle)."""
-    o = _orc()
+    o = orc()
     exp = recs1.copy()
     ctx.set_options(match_full=int(full), match_exact_top2=int(exact))
     try:
@@ -81,7 +42,7 @@ def _expected(ctx, pairs, recs1, counts1, offs1, stride1, recs2, counts2, offs2,
             n1, n2 = max(int(counts1[f1]), 0), max(int(counts2[f2]), 0)
             if n1 == 0 or n2 == 0:
                 continue
-            s1, s2 = _span(offs1, stride1, f1, n1), _span(offs2, stride2, f2, n2)
+            s1, s2 = span(offs1, stride1, f1, n1), span(offs2, stride2, f2, n2)
             p1, p2 = recs1[s1].copy(), recs2[s2].copy()
             got = ctx.match(p1, n1, p2, n2)
             if oracle:
@@ -95,31 +56,25 @@ def _expected(ctx, pairs, recs1, counts1, offs1, stride1, recs2, counts2, offs2,
     return exp
 
 
-def _same_bytes(a, b, what):
-    if a.tobytes() != b.tobytes():
-        bad = np.nonzero(a.view(np.uint8).reshape(len(a), -1) != b.view(np.uint8).reshape(len(b), -1))[0]
-        raise AssertionError("%s: %d records differ, first %s" % (what, len(np.unique(bad)), bad[:8]))
-
-
 @pytest.mark.parametrize("padded", [False, True])
 @pytest.mark.parametrize("full,exact", [(False, False), (True, False), (False, True)])
 def test_parity_with_single_pair_matching(ctx, full, exact, padded):
-    f1 = _frames(SIZES1, 3, l2=exact)
-    f2 = _frames(SIZES2, 4, l2=exact)
-    r1, o1, s1 = _layout(f1, COUNTS1, padded)
-    r2, o2, s2 = _layout(f2, SIZES2, padded)
+    f1 = frames(SIZES1, 3, exact)
+    f2 = frames(SIZES2, 4, exact)
+    r1, o1, s1 = layout(f1, COUNTS1, padded, min_stride=0, pad_error=0.0)
+    r2, o2, s2 = layout(f2, SIZES2, padded, min_stride=0, pad_error=0.0)
     exp = _expected(ctx, PAIRS, r1, COUNTS1, o1, s1, r2, SIZES2, o2, s2, full, exact)
     ctx.set_options(match_full=int(full), match_exact_top2=int(exact))
     try:
         got1, got2 = _run_batch(ctx, PAIRS, r1, COUNTS1, o1, s1, r2, SIZES2, o2, s2)
     finally:
         ctx.set_options(match_full=0, match_exact_top2=0)
-    _same_bytes(got1, exp, "set 1")
-    _same_bytes(got2, r2, "set 2 (read only)")
+    same_bytes(got1, exp, "set 1")
+    same_bytes(got2, r2, "set 2 (read only)")
     # the n2 < 32 pair of reference mode: no column takes part -> match -1, score 0
     f = SIZES1.index(129)
     n2 = SIZES2[dict(PAIRS)[f]]
-    sl = _span(o1, s1, f, 129)
+    sl = span(o1, s1, f, 129)
     if n2 < 32 and not full:
         assert (got1["match"][sl] == -1).all() and (got1["score"][sl] == 0).all()
 
@@ -147,7 +102,7 @@ def test_behind_real_extraction(ctx):
     # misift_match on host copies of each pair recomputes the five fields from the same descriptors: frame f is set 1 of
     # pair f and set 2 of pair f - 1, and the batch wrote nothing but the match fields of set-1 rows
     exp = _expected(ctx, pairs, got, counts, offs, 0, got, counts, offs, 0, False, False, oracle=False)
-    _same_bytes(got, exp, "packed batch")
+    same_bytes(got, exp, "packed batch")
 
 
 def test_argument_errors(ctx):
@@ -170,12 +125,7 @@ def test_argument_errors(ctx):
 
 
 def _batch_case(c, n_pairs, seed, sizes_lo, sizes_hi):
-    rng = np.random.default_rng(seed)
-    nf = n_pairs + 1
-    sizes = rng.integers(sizes_lo, sizes_hi, nf)
-    fr = _frames(sizes, seed)
-    recs, offs, _ = _layout(fr, sizes, False)
-    pairs = [(f, f + 1) for f in range(n_pairs)]
+    pairs, recs, sizes, offs = sequence_case(n_pairs, seed, sizes_lo, sizes_hi, False)
     got, _ = _run_batch(c, pairs, recs, sizes, offs, 0)
     return pairs, recs, sizes, offs, got
 
@@ -190,36 +140,21 @@ def test_large_and_small_batches(ctx, n_pairs, lo, hi):
     n2 = np.array([sizes[b] for _, b in pairs], np.int32)
     plan = np.zeros((n_pairs, 5), np.int32)
     ni, ch, bound = C.c_int(), C.c_int(), C.c_int()
-    cus = capi.lib().misift_device_info
-    info = [C.c_int() for _ in range(5)]
-    name = C.create_string_buffer(64)
-    sz = C.c_size_t()
-    capi.check(cus(0, name, 64, C.byref(info[0]), C.byref(info[1]), C.byref(sz), C.byref(info[2]), C.byref(info[3])),
-               "misift_device_info")
-    capi.lib().misift_test_match_batch_plan(info[2].value, 0, n_pairs, n1.ctypes.data, n2.ctypes.data, plan.ctypes.data,
+    capi.lib().misift_test_match_batch_plan(num_cus(), 0, n_pairs, n1.ctypes.data, n2.ctypes.data, plan.ctypes.data,
                                             C.byref(ni), C.byref(ch), C.byref(bound))
     assert (ch.value == 1) == (n_pairs >= 64), (n_pairs, ch.value)
     exp = _expected(ctx, pairs, recs, sizes, offs, 0, recs, sizes, offs, 0, False, False, oracle=n_pairs < 8)
-    _same_bytes(got, exp, "%d pairs" % n_pairs)
+    same_bytes(got, exp, "%d pairs" % n_pairs)
 
 
 def test_guard_mode(ctx):
     """One chunked and one unchunked batch on a fresh guarded context (plan and partials buffers start as 0xFF): no band
     damaged, same bytes as the unguarded context."""
     from cudasift_amd import capi
-    old = capi.set_guard(True)
-    try:
-        g = capi.Context(0)
-        try:
-            small = _batch_case(g, 3, 5, 1000, 3000)
-            large = _batch_case(g, 80, 6, 1500, 2500)
-            n = capi.check_guards()
-            assert n >= 3, n
-        finally:
-            g.close()
-    finally:
-        capi.set_guard(old)
+    with guarded_context(3) as g:
+        small = _batch_case(g, 3, 5, 1000, 3000)
+        large = _batch_case(g, 80, 6, 1500, 2500)
     assert capi.check_guards() >= 0
     for (pairs, recs, sizes, offs, got), seed, lo, hi in ((small, 5, 1000, 3000), (large, 6, 1500, 2500)):
         again = _batch_case(ctx, len(pairs), seed, lo, hi)[4]
-        _same_bytes(got, again, "guarded vs unguarded")
+        same_bytes(got, again, "guarded vs unguarded")

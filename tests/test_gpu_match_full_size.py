@@ -14,14 +14,13 @@ import threading
 import numpy as np
 import pytest
 
+from batch_util import MATCH_FIELDS, i8_records, num_cus, quantize_np, same_rows
 from synth import descriptors_to_points, synth_descriptors
-from test_gpu_match_i8 import quantize_np
 
 pytestmark = pytest.mark.gpu
 
 N = 100000
 NUM_CUS = 256
-MATCH_FIELDS = ("score", "ambiguity", "match", "match_xpos", "match_ypos")
 OUT_FIELDS = ("xpos", "ypos") + MATCH_FIELDS
 ROW0, NROWS = 50001, 12512              # misift_match_rows: starts inside a 128-row block
 WORLD, SHARD = 8, N // 8
@@ -53,20 +52,6 @@ def _plant(d2):
     return edges
 
 
-def _i8_records(p1, p2, core):
-    """misift_match_batch_i8's five fields from the oracle's exact integer top-2 (test_gpu_match_i8.match_np's
-    contract: scores scaled by 2^-16)."""
-    out = p1.copy()
-    sc = np.float32(2.0 ** -16)
-    best, idx = core["ex_best"] * sc, core["ex_idx"]
-    out["score"], out["match"] = best, idx
-    out["ambiguity"] = (core["ex_sec"] * sc) / (best + np.float32(1e-6))
-    mm = np.maximum(idx, 0)
-    out["match_xpos"] = np.where(idx >= 0, p2["xpos"][mm], np.float32(0))
-    out["match_ypos"] = np.where(idx >= 0, p2["ypos"][mm], np.float32(0))
-    return out
-
-
 @pytest.fixture(scope="module")
 def full():
     from cudasift_amd import capi
@@ -79,18 +64,7 @@ def full():
     core8 = orc.match_core(q1.astype(np.float32), q2.astype(np.float32), columns=False)
     return dict(p1=p1, p2=p2, edges=edges, core=core, core8=core8, q1=q1, q2=q2,
                 exp={ex: orc.match_records(p1, p2, core, ex) for ex in (False, True)},
-                exp8=_i8_records(p1, p2, core8))
-
-
-def _same(got, exp, what, fields=None):
-    """Byte equality of whole records (fields None) or of the named fields, with the first differing rows on failure."""
-    if fields is None:
-        a, b = got.view(np.uint8).reshape(len(got), -1), exp.view(np.uint8).reshape(len(exp), -1)
-    else:
-        a = np.stack([np.ascontiguousarray(got[k]).view(np.uint32) for k in fields], 1)
-        b = np.stack([np.ascontiguousarray(exp[k]).view(np.uint32) for k in fields], 1)
-    bad = np.nonzero((a != b).any(1))[0]
-    assert len(bad) == 0, "%s: %d rows differ, first %s" % (what, len(bad), bad[:8])
+                exp8=i8_records(p1, p2, core8))
 
 
 class _mode:
@@ -109,18 +83,10 @@ class _mode:
         return False
 
 
-def _num_cus():
-    from cudasift_amd import capi
-    cus, i = C.c_int(), [C.c_int() for _ in range(3)]
-    capi.check(capi.lib().misift_device_info(0, C.create_string_buffer(64), 64, C.byref(i[0]), C.byref(i[1]),
-                                             C.byref(C.c_size_t()), C.byref(cus), C.byref(i[2])), "misift_device_info")
-    return cus.value
-
-
 def _match_plan(n1, n2):
     from cudasift_amd import capi
     a, b, c = C.c_int(), C.c_int(), C.c_int()
-    capi.check(capi.lib().misift_test_match_plan(_num_cus(), n1, n2, C.byref(a), C.byref(b), C.byref(c)),
+    capi.check(capi.lib().misift_test_match_plan(num_cus(), n1, n2, C.byref(a), C.byref(b), C.byref(c)),
                "misift_test_match_plan")
     return a.value, b.value, c.value
 
@@ -129,7 +95,7 @@ def _pair_plan(hook, *lead):
     from cudasift_amd import capi
     n = np.array([N], np.int32)
     plan, ni, ch, pb = np.zeros(5, np.int32), C.c_int(), C.c_int(), C.c_int()
-    capi.check(getattr(capi.lib(), hook)(_num_cus(), *lead, 1, n.ctypes.data, n.ctypes.data, plan.ctypes.data,
+    capi.check(getattr(capi.lib(), hook)(num_cus(), *lead, 1, n.ctypes.data, n.ctypes.data, plan.ctypes.data,
                                          C.byref(ni), C.byref(ch), C.byref(pb)), hook)
     return plan.tolist()
 
@@ -138,7 +104,7 @@ def test_plans_and_planted_ties(full):
     """The plans the calls below take, and the ties they meet: for every planted edge some rows' best (reference mode,
     full + exact, int8) is the duplicate left of the edge, with a runner-up of the same score; the mutual check both
     keeps and rejects rows."""
-    assert _num_cus() == NUM_CUS
+    assert num_cus() == NUM_CUS
     for n1, plan in MATCH_PLANS.items():
         assert _match_plan(n1, N) == plan, n1
         ch, tpc, _ = plan
@@ -169,7 +135,7 @@ def test_match(ctx, full, exact):
     assert _match_plan(N, N) == MATCH_PLANS[N]
     with _mode(ctx, exact):
         got = ctx.match(full["p1"], N, full["p2"], N)
-    _same(got, full["exp"][exact], "misift_match")
+    same_rows(got, full["exp"][exact], "misift_match")
 
 
 @pytest.mark.parametrize("exact", [False, True], ids=["reference", "full_exact"])
@@ -180,7 +146,7 @@ def test_match_rows(ctx, full, exact):
         got = ctx.match(full["p1"], N, full["p2"], N, row_begin=ROW0, row_count=NROWS)
     exp = full["p1"].copy()
     exp[ROW0:ROW0 + NROWS] = full["exp"][exact][ROW0:ROW0 + NROWS]
-    _same(got, exp, "misift_match_rows")
+    same_rows(got, exp, "misift_match_rows")
 
 
 def _pair_set(ctx, full):
@@ -198,8 +164,8 @@ def test_match_batch(ctx, full, exact):
         ctx.match_batch([(0, 1)], d, 2, dc, do, 0)
         ctx.sync()
     got = ctx.download(d, (2 * N,), capi.POINT_DTYPE)
-    _same(got[:N], full["exp"][exact], "misift_match_batch")
-    _same(got[N:], full["p2"], "set 2")
+    same_rows(got[:N], full["exp"][exact], "misift_match_batch")
+    same_rows(got[N:], full["p2"], "set 2")
 
 
 @pytest.mark.parametrize("exact", [False, True], ids=["reference", "full_exact"])
@@ -225,7 +191,7 @@ def test_match_pairs_batch(ctx, full, exact, mutual):
         for k in MATCH_FIELDS:
             exp[k][rej] = 0
         exp["match"][rej] = -1
-    _same(got, exp, "misift_match_pairs_batch", OUT_FIELDS)
+    same_rows(got, exp, "misift_match_pairs_batch", OUT_FIELDS)
     raw = got.view(np.uint8).reshape(N, 576).copy()
     for k in OUT_FIELDS:
         off = capi.POINT_DTYPE.fields[k][1]
@@ -249,8 +215,8 @@ def test_match_batch_i8(ctx, full):
     ctx.match_batch_i8([(0, 1)], d, dq, 2, dc, do, 0)
     ctx.sync()
     got = ctx.download(d, (2 * N,), capi.POINT_DTYPE)
-    _same(got[:N], full["exp8"], "misift_match_batch_i8")
-    _same(got[N:], full["p2"], "set 2")
+    same_rows(got[:N], full["exp8"], "misift_match_batch_i8")
+    same_rows(got[N:], full["p2"], "set 2")
 
 
 def _rank(capi, rank, lw, full, out, errs):
@@ -293,8 +259,8 @@ def test_match_sharded_loopback(ctx, full, overlap):
     exp = full["exp"][False]
     for r in range(WORLD):
         rows, res = out[r]
-        _same(rows, exp[r * SHARD:(r + 1) * SHARD], "rank %d rows" % r)
-        _same(res, exp, "rank %d results" % r, ("score", "ambiguity", "match"))
+        same_rows(rows, exp[r * SHARD:(r + 1) * SHARD], "rank %d rows" % r)
+        same_rows(res, exp, "rank %d results" % r, ("score", "ambiguity", "match"))
 
 
 @pytest.mark.parametrize("exact", [False, True], ids=["reference", "full_exact"])
@@ -310,4 +276,4 @@ def test_match_l2_sample(ctx, exact):
     for r0 in (0, 31000, 64001, N - 512):
         exp = p1.copy()
         orc.match_rows(exp, r0, 512, p2, N, full=exact, exact=exact)
-        _same(got[r0:r0 + 512], exp[r0:r0 + 512], "L2 rows %d.." % r0)
+        same_rows(got[r0:r0 + 512], exp[r0:r0 + 512], "L2 rows %d.." % r0)

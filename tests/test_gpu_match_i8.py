@@ -1,15 +1,16 @@
 """misift_quantize_batch + misift_match_batch_i8: 8-bit descriptors and batched pair matching on the int8 matrix cores.
 
-Integer scores are exact, so every byte is checked against a numpy restatement of the contract: quantisation against
-np.clip(np.rint(256 d), 0, 127), matching against a float64 matmul of the integer q (exact below 2^53).  Bytes the calls
-must not write — other fields, frames in no pair, pairs with an empty side, q outside the frames, set 2 — stay
-byte-identical."""
+Integer scores are exact, so every byte is checked against a numpy restatement of the contract (batch_util):
+quantisation against np.clip(np.rint(256 d), 0, 127), matching against a float64 matmul of the integer q (exact below
+2^53).  Bytes the calls must not write — other fields, frames in no pair, pairs with an empty side, q outside the frames,
+set 2 — stay byte-identical."""
 import ctypes as C
 import os
 
 import numpy as np
 import pytest
 
+from batch_util import frames, guarded_context, layout, match_np, num_cus, quantize_np, same_bytes, sequence_case, span
 from synth import descriptors_to_points, synth_descriptors, synth_frame
 
 pytestmark = pytest.mark.gpu
@@ -18,65 +19,7 @@ SIZES1 = [0, 1, 20, 31, 32, 33, 64, 127, 128, 129, 2000, 4100, 50, 77]   # frame
 COUNTS1 = SIZES1[:12] + [-1, 77]
 SIZES2 = [4100, 2000, 129, 128, 127, 64, 33, 32, 31, 20, 1, 0, 300]
 PAIRS = [(i, (5 * i + 2) % 13) for i in range(13)]
-MATCH_FIELDS = ("score", "ambiguity", "match", "match_xpos", "match_ypos")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def quantize_np(d):
-    with np.errstate(invalid="ignore", over="ignore"):
-        v = np.clip(np.rint(np.float32(256) * np.asarray(d, np.float32)), 0, 127)
-    return np.where(np.isnan(v), 0, v).astype(np.int8)
-
-
-def match_np(p1, q1, p2, q2):
-    """The five match fields of set-1 rows p1 (q1: their int8 descriptors) against set 2 (p2, q2)."""
-    out = p1.copy()
-    S = q1.astype(np.float64) @ q2.astype(np.float64).T
-    S = np.where(S > 0, S, 0.0)
-    best = S.max(1)
-    m = np.where(best > 0, S.argmax(1), -1)                  # argmax: the first (smallest) index of the maximum
-    S[np.arange(len(S)), np.maximum(m, 0)] = 0
-    sec = np.where(m >= 0, S.max(1) if S.shape[1] else 0, 0)
-    score = best.astype(np.float32) * np.float32(2.0 ** -16)
-    out["score"] = score
-    out["ambiguity"] = (sec.astype(np.float32) * np.float32(2.0 ** -16)) / (score + np.float32(1e-6))
-    out["match"] = m
-    mm = np.maximum(m, 0)
-    out["match_xpos"] = np.where(m >= 0, p2["xpos"][mm], np.float32(0))
-    out["match_ypos"] = np.where(m >= 0, p2["ypos"][mm], np.float32(0))
-    return out
-
-
-def _frames(sizes, seed, l2=True):
-    """Records with random descriptors, positions and (poisoned) other fields, so untouched bytes show."""
-    from cudasift_amd import capi
-    rng = np.random.default_rng(seed)
-    out = []
-    for f, n in enumerate(sizes):
-        p = descriptors_to_points(synth_descriptors(n, seed * 100 + f, l2), capi.POINT_DTYPE)
-        for k in ("xpos", "ypos", "scale", "orientation", "score", "ambiguity", "match_xpos", "match_ypos", "match_error"):
-            p[k] = rng.random(n, dtype=np.float32) * 500
-        p["match"] = rng.integers(-5, 5000, n)
-        out.append(p)
-    return out
-
-
-def _layout(frames, counts, padded):
-    from cudasift_amd import capi
-    if padded:
-        stride = max(len(p) for p in frames)
-        recs = np.zeros(stride * len(frames), capi.POINT_DTYPE)
-        for f, p in enumerate(frames):
-            recs[f * stride:f * stride + len(p)] = p
-        return recs, None, stride
-    kept = [p if c >= 0 else p[:0] for p, c in zip(frames, counts)]
-    offs = np.concatenate([[0], np.cumsum([len(p) for p in kept])]).astype(np.int32)
-    return np.concatenate(kept), offs, 0
-
-
-def _span(offs, stride, f, n):
-    b = int(offs[f]) if offs is not None else f * stride
-    return slice(b, b + n)
 
 
 def _q_expected(recs, counts, offs, stride, pattern):
@@ -84,7 +27,7 @@ def _q_expected(recs, counts, offs, stride, pattern):
     q = pattern.copy()
     for f, c in enumerate(counts):
         n = max(int(c), 0)
-        sl = _span(offs, stride, f, n)
+        sl = span(offs, stride, f, n)
         q[sl] = quantize_np(recs["data"][sl])
     return q
 
@@ -95,17 +38,9 @@ def _expected(pairs, recs1, q1, counts1, offs1, stride1, recs2, q2, counts2, off
         n1, n2 = max(int(counts1[f1]), 0), max(int(counts2[f2]), 0)
         if n1 == 0 or n2 == 0:
             continue
-        s1, s2 = _span(offs1, stride1, f1, n1), _span(offs2, stride2, f2, n2)
+        s1, s2 = span(offs1, stride1, f1, n1), span(offs2, stride2, f2, n2)
         exp[s1] = match_np(recs1[s1], q1[s1], recs2[s2], q2[s2])
     return exp
-
-
-def _same_bytes(a, b, what):
-    if a.tobytes() != b.tobytes():
-        av = a.view(np.uint8).reshape(len(a), -1)
-        bv = b.view(np.uint8).reshape(len(b), -1)
-        bad = np.nonzero((av != bv).any(1))[0]
-        raise AssertionError("%s: %d records differ, first %s" % (what, len(bad), bad[:8]))
 
 
 def _pattern(n, seed=9):
@@ -125,7 +60,7 @@ def _quantize(c, recs, counts, offs, stride, pattern):
 
 @pytest.mark.parametrize("padded", [False, True])
 def test_quantize_bytes(ctx, padded):
-    recs, offs, stride = _layout(_frames(SIZES1, 3), COUNTS1, padded)
+    recs, offs, stride = layout(frames(SIZES1, 3, True), COUNTS1, padded, min_stride=0, pad_error=0.0)
     rng = np.random.default_rng(1)
     recs["data"][::7, ::5] = rng.normal(0, 0.4, recs["data"][::7, ::5].shape)     # negatives and saturation too
     recs["data"][3, :4] = [np.nan, np.inf, -np.inf, 127.5 / 256]
@@ -134,14 +69,14 @@ def test_quantize_bytes(ctx, padded):
     assert np.array_equal(got, _q_expected(recs, COUNTS1, offs, stride, pat))
     if padded:                                                # count -1 frame and padding keep the pattern
         f = 12
-        assert np.array_equal(got[_span(None, stride, f, stride)], pat[_span(None, stride, f, stride)])
+        assert np.array_equal(got[span(None, stride, f, stride)], pat[span(None, stride, f, stride)])
 
 
 @pytest.mark.parametrize("padded", [False, True])
 def test_match_bytes(ctx, padded):
     from cudasift_amd import capi
-    r1, o1, s1 = _layout(_frames(SIZES1, 3), COUNTS1, padded)
-    r2, o2, s2 = _layout(_frames(SIZES2, 4), SIZES2, padded)
+    r1, o1, s1 = layout(frames(SIZES1, 3, True), COUNTS1, padded, min_stride=0, pad_error=0.0)
+    r2, o2, s2 = layout(frames(SIZES2, 4, True), SIZES2, padded, min_stride=0, pad_error=0.0)
     d1, c1, do1, dq1, q1 = _quantize(ctx, r1, COUNTS1, o1, s1, _pattern(len(r1), 1))
     d2, c2, do2, dq2, q2 = _quantize(ctx, r2, SIZES2, o2, s2, _pattern(len(r2), 2))
     ctx.set_options(match_full=1, match_exact_top2=1)        # ignored by the int8 matcher: every column, exact top 2
@@ -153,8 +88,8 @@ def test_match_bytes(ctx, padded):
     got1 = ctx.download(d1, (len(r1),), capi.POINT_DTYPE)
     got2 = ctx.download(d2, (len(r2),), capi.POINT_DTYPE)
     assert np.array_equal(ctx.download(dq1, q1.shape, np.int8), q1)
-    _same_bytes(got1, _expected(PAIRS, r1, q1, COUNTS1, o1, s1, r2, q2, SIZES2, o2, s2), "set 1")
-    _same_bytes(got2, r2, "set 2 (read only)")
+    same_bytes(got1, _expected(PAIRS, r1, q1, COUNTS1, o1, s1, r2, q2, SIZES2, o2, s2), "set 1")
+    same_bytes(got2, r2, "set 2 (read only)")
 
 
 def test_keyframe_and_same_buffer(ctx):
@@ -162,20 +97,20 @@ def test_keyframe_and_same_buffer(ctx):
     and d_q1 == d_q2."""
     from cudasift_amd import capi
     sizes = [300, 2000, 129, 31, 1, 0, 700]
-    recs, offs, _ = _layout(_frames(sizes, 8), sizes, False)
+    recs, offs, _ = layout(frames(sizes, 8, True), sizes, False, min_stride=0, pad_error=0.0)
     d, dc, do, dq, q = _quantize(ctx, recs, sizes, offs, 0, _pattern(len(recs)))
     ref = ctx.upload(recs)
     key = [(f, 0) for f in range(1, len(sizes))]
     ctx.match_batch_i8(key, d, dq, len(sizes), dc, do, 0, ref, dq, len(sizes), dc, do, 0)
     ctx.sync()
-    _same_bytes(ctx.download(d, (len(recs),), capi.POINT_DTYPE),
+    same_bytes(ctx.download(d, (len(recs),), capi.POINT_DTYPE),
                 _expected(key, recs, q, sizes, offs, 0, recs, q, sizes, offs, 0), "keyframe")
     d = ctx.upload(recs)
     seq = [(f, f + 1) for f in range(len(sizes) - 1)]
     ctx.match_batch_i8(seq, d, dq, len(sizes), dc, do, 0)
     ctx.sync()
     got = ctx.download(d, (len(recs),), capi.POINT_DTYPE)
-    _same_bytes(got, _expected(seq, recs, q, sizes, offs, 0, recs, q, sizes, offs, 0), "d_recs1 == d_recs2")
+    same_bytes(got, _expected(seq, recs, q, sizes, offs, 0, recs, q, sizes, offs, 0), "d_recs1 == d_recs2")
 
 
 def test_ties_zero_rows_and_single_candidates(ctx):
@@ -202,7 +137,7 @@ def test_ties_zero_rows_and_single_candidates(ctx):
     ctx.match_batch_i8([(0, 1)], d, dq, 2, dc, do, 0)
     ctx.sync()
     got = ctx.download(d, (len(recs),), capi.POINT_DTYPE)
-    _same_bytes(got, _expected([(0, 1)], recs, q, counts, offs, 0, recs, q, counts, offs, 0), "ties")
+    same_bytes(got, _expected([(0, 1)], recs, q, counts, offs, 0, recs, q, counts, offs, 0), "ties")
     r = got[:6]
     assert r["match"][0] == 5 and r["match_xpos"][0] == np.float32(5.25)
     assert r["ambiguity"][0] == r["score"][0] / (r["score"][0] + np.float32(1e-6))
@@ -215,25 +150,21 @@ def test_column_chunks(ctx):
     """64 rows x 60 000 columns: one row block, columns cut into chunks and merged; every byte exact."""
     from cudasift_amd import capi
     sizes = [64, 60000]
-    fr = _frames(sizes, 12)
+    fr = frames(sizes, 12, True)
     fr[1]["data"][59990] = fr[0]["data"][3]                   # a match in the last chunk
     fr[1]["data"][31] = fr[0]["data"][4]
     fr[1]["data"][40000] = fr[0]["data"][4]
-    recs, offs, _ = _layout(fr, sizes, False)
-    cus = C.c_int()
+    recs, offs, _ = layout(fr, sizes, False, min_stride=0, pad_error=0.0)
     n1, n2 = np.array([64], np.int32), np.array([60000], np.int32)
     plan, ni, ch, bound = np.zeros(5, np.int32), C.c_int(), C.c_int(), C.c_int()
-    info = [C.c_int() for _ in range(4)]
-    capi.check(capi.lib().misift_device_info(0, C.create_string_buffer(64), 64, C.byref(info[0]), C.byref(info[1]),
-                                             C.byref(C.c_size_t()), C.byref(cus), C.byref(info[3])), "misift_device_info")
-    capi.lib().misift_test_match_i8_plan(cus.value, 1, n1.ctypes.data, n2.ctypes.data, plan.ctypes.data, C.byref(ni),
+    capi.lib().misift_test_match_i8_plan(num_cus(), 1, n1.ctypes.data, n2.ctypes.data, plan.ctypes.data, C.byref(ni),
                                          C.byref(ch), C.byref(bound))
     assert ch.value > 1 and plan[3] > 1, (ch.value, plan)
     d, dc, do, dq, q = _quantize(ctx, recs, sizes, offs, 0, _pattern(len(recs)))
     ctx.match_batch_i8([(0, 1)], d, dq, 2, dc, do, 0)
     ctx.sync()
     got = ctx.download(d, (len(recs),), capi.POINT_DTYPE)
-    _same_bytes(got, _expected([(0, 1)], recs, q, sizes, offs, 0, recs, q, sizes, offs, 0), "64 x 60000")
+    same_bytes(got, _expected([(0, 1)], recs, q, sizes, offs, 0, recs, q, sizes, offs, 0), "64 x 60000")
     assert got["match"][3] == 59990 and got["match"][4] == 31
 
 
@@ -303,7 +234,7 @@ def test_chain_behind_extraction(ctx):
     for f1, f2 in pairs:
         s1, s2 = slice(offs[f1], offs[f1] + counts[f1]), slice(offs[f2], offs[f2] + counts[f2])
         exp[s1] = match_np(got[s1], q[s1], got[s2], q[s2])
-    _same_bytes(got, exp, "chain")
+    same_bytes(got, exp, "chain")
     # the same find on the same (now final) records gives the same H and counts: find ran behind the match
     H2, nm2 = ctx.find_homography_batch(np.arange(B - 1), seeds, packed, B, cnt.ptr, cnt.ptr + 4 * B, 0, max_pts=mp)
     ctx.sync()
@@ -312,13 +243,10 @@ def test_chain_behind_extraction(ctx):
     assert (ctx.download(nm, (B - 1,), np.int32) > 8).all()
 
 
-def _batch_case(c, n_pairs, seed, lo, hi):
+def _i8_case(c, n_pairs, seed, lo, hi):
     from cudasift_amd import capi
-    rng = np.random.default_rng(seed)
-    sizes = rng.integers(lo, hi, n_pairs + 1)
-    recs, offs, _ = _layout(_frames(sizes, seed), sizes, False)
+    pairs, recs, sizes, offs = sequence_case(n_pairs, seed, lo, hi, True)
     d, dc, do, dq, q = _quantize(c, recs, sizes, offs, 0, _pattern(len(recs)))
-    pairs = [(f, f + 1) for f in range(n_pairs)]
     c.match_batch_i8(pairs, d, dq, len(sizes), dc, do, 0)
     c.sync()
     return pairs, recs, q, sizes, offs, c.download(d, (len(recs),), capi.POINT_DTYPE)
@@ -328,28 +256,10 @@ def test_guard_mode(ctx):
     """Two chunked batches (3 pairs: many chunks per row block; 40 pairs: a few) on a fresh guarded context (plan and
     partials start as 0xFF): no band damaged, every byte as the restatement says.  The unchunked path runs guarded in
     test_unchunked_batch_two_windows."""
-    from cudasift_amd import capi
-    old = capi.set_guard(True)
-    try:
-        g = capi.Context(0)
-        try:
-            cases = [_batch_case(g, 3, 5, 1000, 3000), _batch_case(g, 40, 6, 1500, 2500)]
-            assert capi.check_guards() >= 3
-        finally:
-            g.close()
-    finally:
-        capi.set_guard(old)
+    with guarded_context(3) as g:
+        cases = [_i8_case(g, 3, 5, 1000, 3000), _i8_case(g, 40, 6, 1500, 2500)]
     for pairs, recs, q, sizes, offs, got in cases:
-        _same_bytes(got, _expected(pairs, recs, q, sizes, offs, 0, recs, q, sizes, offs, 0), "%d pairs" % len(pairs))
-
-
-def _num_cus():
-    from cudasift_amd import capi
-    cus = C.c_int()
-    info = [C.c_int() for _ in range(3)]
-    capi.check(capi.lib().misift_device_info(0, C.create_string_buffer(64), 64, C.byref(info[0]), C.byref(info[1]),
-                                             C.byref(C.c_size_t()), C.byref(cus), C.byref(info[2])), "misift_device_info")
-    return cus.value
+        same_bytes(got, _expected(pairs, recs, q, sizes, offs, 0, recs, q, sizes, offs, 0), "%d pairs" % len(pairs))
 
 
 def test_unchunked_batch_two_windows(ctx):
@@ -358,21 +268,21 @@ def test_unchunked_batch_two_windows(ctx):
     two key windows of 512.  Copies of a record 32 k columns apart lie in one lane's column stream, inside a window and
     across the window boundary; the lane's own top-2 must keep the earliest.  Run plain and on a guarded context."""
     from cudasift_amd import capi
-    cus = _num_cus()
+    cus = num_cus()
     nf, n2 = 16 * cus + 6, 20000
     rng = np.random.default_rng(31)
     sizes = rng.integers(1, 9, nf)
     counts = sizes.copy()
     counts[11] = -1                                           # no records: one row block fewer, still a full target
-    p2 = _frames([n2], 32)[0]
+    p2 = frames([n2], 32, True)[0]
     dup = {100: (196, 19204, 101), 16400: (16560, 19600), 16359: (16391,), 5000: (5032, 16392)}
     for j, copies in dup.items():                             # column j % 32 is the lane; tile 512 opens window 1
         for k in copies:
             p2["data"][k] = p2["data"][j]
-    fr = _frames(sizes, 33)
+    fr = frames(sizes, 33, True)
     for f, j in zip((0, 1, 2, 3), dup):
         fr[f]["data"][0] = p2["data"][j]
-    recs, offs, _ = _layout(fr, counts, False)
+    recs, offs, _ = layout(fr, counts, False, min_stride=0, pad_error=0.0)
     n1, n2s = np.maximum(counts, 0).astype(np.int32), np.full(nf, n2, np.int32)
     plan = np.zeros((nf, 5), np.int32)
     ni, ch, bound = C.c_int(), C.c_int(), C.c_int()
@@ -397,18 +307,10 @@ def test_unchunked_batch_two_windows(ctx):
         assert np.array_equal(q, q1)
         return c.download(d, (len(recs),), capi.POINT_DTYPE)
 
-    _same_bytes(run(ctx), exp, "unchunked, two windows")
-    old = capi.set_guard(True)
-    try:
-        g = capi.Context(0)
-        try:
-            got = run(g)
-            assert capi.check_guards() >= 3
-        finally:
-            g.close()
-    finally:
-        capi.set_guard(old)
-    _same_bytes(got, exp, "unchunked, guarded")
+    same_bytes(run(ctx), exp, "unchunked, two windows")
+    with guarded_context(3) as g:
+        got = run(g)
+    same_bytes(got, exp, "unchunked, guarded")
     sc = got["score"][first]
     assert (got["ambiguity"][first] == sc / (sc + np.float32(1e-6))).all()
 
@@ -439,7 +341,7 @@ def test_quality_on_golden_pair(ctx):
         ctx.sync()
         res[name] = [int(ctx.download(nm, (1,), np.int32)[0]) for nm in nms]
     got = ctx.download(d, (len(recs),), capi.POINT_DTYPE)[:len(left)]
-    _same_bytes(got, _expected([(0, 1)], recs, q, counts, offs, 0, recs, q, counts, offs, 0)[:len(left)], "golden")
+    same_bytes(got, _expected([(0, 1)], recs, q, counts, offs, 0, recs, q, counts, offs, 0)[:len(left)], "golden")
     gate = (ex["score"] > 0.85) & (ex["ambiguity"] < 0.95)
     assert gate.sum() > 300
     assert (got["match"][gate] == ex["match"][gate]).mean() >= 0.99

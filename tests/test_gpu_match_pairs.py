@@ -9,6 +9,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from batch_util import MATCH_FIELDS, expected_pair, frames, guarded_context, layout, no_match_rows, num_cus, orc, span
 from synth import descriptors_to_points, synth_descriptors, synth_frame
 
 pytestmark = pytest.mark.gpu
@@ -17,78 +18,9 @@ SIZES1 = [0, 1, 20, 31, 32, 33, 64, 127, 128, 129, 2000, 4100, 50, 77]   # frame
 COUNTS1 = SIZES1[:12] + [-1, 77]
 SIZES2 = [4100, 2000, 129, 128, 127, 64, 33, 32, 31, 20, 1, 0, 300]
 PAIRS = [(i, (5 * i + 2) % 13) for i in range(13)]
-MATCH_FIELDS = ("score", "ambiguity", "match", "match_xpos", "match_ypos")
 OUT_FIELDS = ("xpos", "ypos") + MATCH_FIELDS
 POISON = 0xA5
 MISIFT_OK, MISIFT_EINVAL = 0, -1
-
-
-def _orc():
-    from oracle import pyoracle
-    return pyoracle
-
-
-def _frames(sizes, seed, l2=False):
-    """Records with random descriptors, positions and (poisoned) other fields."""
-    from cudasift_amd import capi
-    rng = np.random.default_rng(seed)
-    out = []
-    for f, n in enumerate(sizes):
-        p = descriptors_to_points(synth_descriptors(n, seed * 100 + f, l2), capi.POINT_DTYPE)
-        for k in ("xpos", "ypos", "scale", "orientation", "score", "ambiguity", "match_xpos", "match_ypos", "match_error"):
-            p[k] = rng.random(n, dtype=np.float32) * 500
-        p["match"] = rng.integers(-5, 5000, n)
-        out.append(p)
-    return out
-
-
-def _layout(frames, counts, padded):
-    """(records, offsets or None, stride): packed (a frame of count -1 holds no records) or padded to a common stride."""
-    from cudasift_amd import capi
-    if padded:
-        stride = max(max(len(p) for p in frames), 1)
-        recs = np.zeros(stride * len(frames), capi.POINT_DTYPE)
-        for f, p in enumerate(frames):
-            recs[f * stride:f * stride + len(p)] = p
-        return recs, None, stride
-    kept = [p if c >= 0 else p[:0] for p, c in zip(frames, counts)]
-    offs = np.concatenate([[0], np.cumsum([len(p) for p in kept])]).astype(np.int32)
-    return np.concatenate(kept), offs, 0
-
-
-def _span(offs, stride, f, n):
-    b = int(offs[f]) if offs is not None else f * stride
-    return slice(b, b + n)
-
-
-def no_match_rows(p1):
-    """The rows a pair with no column (or a rejected row) gets: xpos / ypos of set 1, no match."""
-    e = np.zeros(len(p1), p1.dtype)
-    e["xpos"], e["ypos"] = p1["xpos"], p1["ypos"]
-    e["match"] = -1
-    return e
-
-
-def expected_pair(p1, p2, full, exact, mutual):
-    """The seven output fields of one pair from the oracle: forward MatchSiftData under (full, exact); with mutual, a row
-    r with match m >= 0 keeps it only if the reversed match (set 2 against set 1, full + exact) of m is r.  Returns the
-    rows (structured, only OUT_FIELDS meaningful) and the number with match >= 0."""
-    o = _orc()
-    n1, n2 = len(p1), len(p2)
-    e = no_match_rows(p1)
-    if n1 == 0 or n2 == 0:
-        return e, 0
-    fw = p1.copy()
-    o.match(fw, n1, p2.copy(), n2, full=full, exact=exact)
-    for k in MATCH_FIELDS:
-        e[k] = fw[k]
-    if mutual:
-        rv = p2.copy()
-        o.match(rv, n2, p1.copy(), n1, full=True, exact=True)
-        m = e["match"]
-        bad = (m >= 0) & (rv["match"][np.clip(m, 0, n2 - 1)] != np.arange(n1))
-        e[bad] = no_match_rows(p1[bad])
-    return e, int((e["match"] >= 0).sum())
 
 
 def _fields_equal(got, exp, what):
@@ -159,7 +91,7 @@ def _check(ctx, pairs, r1, c1, o1, s1, r2, c2, o2, s2, full, exact, mutual, max_
             continue
         assert oc[i] == n1, (i, oc[i], n1)
         exp_counts.append(n1)
-        p1, p2 = r1[_span(o1, s1, f1, n1)], r2[_span(o2, s2, f2, n2)]
+        p1, p2 = r1[span(o1, s1, f1, n1)], r2[span(o2, s2, f2, n2)]
         e, k = expected_pair(p1, p2, full, exact, mutual)
         _fields_equal(got[i * max_pts:i * max_pts + n1], e, "pair %d (%d x %d)" % (i, n1, n2))
         assert nm[i] == k, (i, nm[i], k)
@@ -172,10 +104,10 @@ def _check(ctx, pairs, r1, c1, o1, s1, r2, c2, o2, s2, full, exact, mutual, max_
 def test_same_answer_as_match_batch(ctx, full, exact, padded):
     """Each set-1 frame in one pair: the seven fields equal misift_match_batch's set-1 rows byte for byte, and the oracle."""
     from cudasift_amd import capi
-    f1 = _frames(SIZES1, 3, l2=exact)
-    f2 = _frames(SIZES2, 4, l2=exact)
-    r1, o1, s1 = _layout(f1, COUNTS1, padded)
-    r2, o2, s2 = _layout(f2, SIZES2, padded)
+    f1 = frames(SIZES1, 3, exact)
+    f2 = frames(SIZES2, 4, exact)
+    r1, o1, s1 = layout(f1, COUNTS1, padded, min_stride=1, pad_error=0.0)
+    r2, o2, s2 = layout(f2, SIZES2, padded, min_stride=1, pad_error=0.0)
     got, oc, _ = _check(ctx, PAIRS, r1, COUNTS1, o1, s1, r2, SIZES2, o2, s2, full, exact, 0)
     ctx.set_options(match_full=int(full), match_exact_top2=int(exact))
     try:
@@ -194,25 +126,20 @@ def test_same_answer_as_match_batch(ctx, full, exact, padded):
             continue
         rows = got[i * 4100:i * 4100 + n1]
         if n2 == 0:
-            _fields_equal(rows, no_match_rows(r1[_span(o1, s1, a, n1)]), "empty set 2")
+            _fields_equal(rows, no_match_rows(r1[span(o1, s1, a, n1)]), "empty set 2")
             continue
-        _fields_equal(rows, mb[_span(o1, s1, a, n1)], "pair %d against misift_match_batch" % i)
+        _fields_equal(rows, mb[span(o1, s1, a, n1)], "pair %d against misift_match_batch" % i)
 
 
 def _chunked(n1, n2):
     """Whether misift_match_batch's planner (the one misift_match_pairs_batch runs) cuts the columns into chunks."""
     from cudasift_amd import capi
     L = capi.lib()
-    info = [C.c_int() for _ in range(5)]
-    name = C.create_string_buffer(64)
-    sz = C.c_size_t()
-    capi.check(L.misift_device_info(0, name, 64, C.byref(info[0]), C.byref(info[1]), C.byref(sz), C.byref(info[2]),
-                                    C.byref(info[3])), "misift_device_info")
     n1 = np.asarray(n1, np.int32)
     n2 = np.asarray(n2, np.int32)
     plan5 = np.zeros(5 * len(n1), np.int32)
     ni, ch, pb = C.c_int(), C.c_int(), C.c_int()
-    capi.check(L.misift_test_match_batch_plan(info[2].value, 0, len(n1), n1.ctypes.data, n2.ctypes.data,
+    capi.check(L.misift_test_match_batch_plan(num_cus(), 0, len(n1), n1.ctypes.data, n2.ctypes.data,
                                               plan5.ctypes.data, C.byref(ni), C.byref(ch), C.byref(pb)),
                "misift_test_match_batch_plan")
     return ch.value > 1
@@ -222,8 +149,8 @@ def _chunked(n1, n2):
 def test_many_to_many(ctx, mutual):
     """Windowed, keyframe (both directions), self pairs and d_recs1 == d_recs2, in a chunked and an unchunked plan."""
     small = [1300 + 13 * f for f in range(16)]                 # 11-12 row blocks each: the call fills a round
-    frames = _frames(small, 7)
-    r, o, s = _layout(frames, small, False)
+    fr = frames(small, 7, False)
+    r, o, s = layout(fr, small, False, min_stride=1, pad_error=0.0)
     window = [(f, g) for f in range(16) for g in range(f + 1, min(f + 4, 16))]
     keyframe = [(15, k) for k in (0, 5, 10)] + [(k, 15) for k in (0, 5, 10)]
     selfp = [(3, 3), (9, 9)]
@@ -232,8 +159,8 @@ def test_many_to_many(ctx, mutual):
     _check(ctx, pairs, r, small, o, s, None, None, None, 0, False, False, mutual, max_pts=1500, same=True)
     _check(ctx, pairs, r, small, o, s, r.copy(), small, o, s, True, True, mutual, max_pts=1500)
     big = [3000, 2500, 2800]
-    frames = _frames(big, 8)
-    r, o, s = _layout(frames, big, True)
+    fr = frames(big, 8, False)
+    r, o, s = layout(fr, big, True, min_stride=1, pad_error=0.0)
     pairs = [(0, 1), (0, 2), (1, 0), (2, 2)]
     assert _chunked([big[a] for a, _ in pairs], [big[b] for _, b in pairs])
     _check(ctx, pairs, r, big, o, s, None, None, None, 0, False, True, mutual, max_pts=3000, same=True)
@@ -282,8 +209,8 @@ def test_mutual_rule_with_ties(ctx, full, exact):
 def test_oversized_pairs_and_argument_errors(ctx):
     from cudasift_amd import capi
     sizes = [100, 700, 40]
-    frames = _frames(sizes, 9)
-    r, o, s = _layout(frames, sizes, False)
+    fr = frames(sizes, 9, False)
+    r, o, s = layout(fr, sizes, False, min_stride=1, pad_error=0.0)
     pairs = [(0, 1), (1, 0), (0, 2), (2, 0), (1, 1)]
     got, oc, nm = _check(ctx, pairs, r, sizes, o, s, None, None, None, 0, False, False, 1, max_pts=512, same=True)
     assert list(oc) == [-1, -1, 100, 40, -1] and nm[0] == -1 and nm[1] == -1 and nm[4] == -1
@@ -319,7 +246,7 @@ def test_mutual_output_feeds_find_homography(ctx):
     """Extracted frames -> mutual pairs -> misift_find_homography_batch on the output as it is: H and inlier counts equal
     srand(seed) + misift_find_homography on the downloaded rows."""
     from cudasift_amd import capi
-    o = _orc()
+    o = orc()
     B, h, w, mp = 4, 480, 640, 4096
     base = synth_frame(0, w, h).astype(np.float32)
     frames = np.stack([np.roll(base, (2 * f, 3 * f), axis=(0, 1)) for f in range(B)]).astype(np.float32)
@@ -357,18 +284,10 @@ def test_mutual_output_feeds_find_homography(ctx):
 def test_guard_mode(ctx):
     """One mutual call with every allocation guarded: no band damaged."""
     from cudasift_amd import capi
-    prev = capi.set_guard(True)
-    try:
-        g = capi.Context(0)
-        try:
-            sizes = [500, 130, 2000]
-            frames = _frames(sizes, 11)
-            r, o, s = _layout(frames, sizes, False)
-            pairs = [(0, 1), (1, 2), (2, 0), (2, 2)]
-            _check(g, pairs, r, sizes, o, s, None, None, None, 0, False, False, 1, max_pts=2000, same=True)
-            capi.check_guards()
-        finally:
-            g.close()
-    finally:
-        capi.set_guard(prev)
+    with guarded_context(None) as g:
+        sizes = [500, 130, 2000]
+        fr = frames(sizes, 11, False)
+        r, o, s = layout(fr, sizes, False, min_stride=1, pad_error=0.0)
+        pairs = [(0, 1), (1, 2), (2, 0), (2, 2)]
+        _check(g, pairs, r, sizes, o, s, None, None, None, 0, False, False, 1, max_pts=2000, same=True)
     capi.check_guards()

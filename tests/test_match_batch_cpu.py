@@ -5,6 +5,8 @@ import ctypes as C
 
 import numpy as np
 
+from batch_util import check_pair_plan
+
 
 def _plan(L, cus, full, n1, n2):
     n1 = np.ascontiguousarray(n1, np.int32)
@@ -16,31 +18,9 @@ def _plan(L, cus, full, n1, n2):
     return out[:len(n1)], ni.value, ch.value, bound.value
 
 
-def _check(L, cus, full, n1, n2):
+def _check_batch_plan(L, cus, full, n1, n2):
     plan, nitems, chunks, bound = _plan(L, cus, full, n1, n2)
-    covered = np.zeros(nitems, np.int32)
-    rows_total = 0
-    for p, (item0, nrb, ntiles, nch, tpc) in enumerate(plan):
-        a, b = max(int(n1[p]), 0), max(int(n2[p]), 0)
-        ncols = (b if full else 32 * (b // 32)) if a and b else 0
-        assert nrb == ((a + 127) // 128 if a and b else 0), (p, a, b, nrb)
-        assert ntiles == (ncols + 63) // 64
-        assert nch >= 1 and tpc >= 1
-        if ntiles:
-            assert nch * tpc >= ntiles and (nch - 1) * tpc < ntiles          # no empty chunk
-            if chunks == 1:
-                assert nch == 1 and tpc == ntiles
-        # the items of the pair: row block major, chunk minor; together they cover every (row block, super-tile) once
-        tiles = np.zeros((nrb, max(ntiles, 1)), np.int32)
-        for i in range(nrb * nch):
-            rb, c = divmod(i, nch)
-            covered[item0 + i] += 1
-            t0, t1 = c * tpc, min(c * tpc + tpc, ntiles)
-            tiles[rb, t0:t1] += 1
-        if nrb and ntiles:
-            assert (tiles[:, :ntiles] == 1).all(), p
-        rows_total += nrb
-    assert (covered == 1).all()                               # items are a partition of [0, nitems)
+    rows_total = check_pair_plan(plan, nitems, chunks, n1, n2, lambda b: ((b if full else 32 * (b // 32)) + 63) // 64)
     assert chunks >= 1
     if rows_total >= 2 * cus:
         assert chunks == 1                                    # a full round of row blocks: no partials at all
@@ -60,17 +40,17 @@ def test_match_batch_plan_covers_every_block_once():
     for n1, n2 in cases:
         for cus in (256, 64, 304):
             for full in (0, 1):
-                _check(L, cus, full, n1, n2)
+                _check_batch_plan(L, cus, full, n1, n2)
 
 
 def test_match_batch_plan_splits_small_batches_only():
     from cudasift_amd import capi
     L = capi.lib()
-    _, chunks = _check(L, 256, 0, [2000] * 64, [2000] * 64)      # 64 x 16 row blocks: two full rounds
+    _, chunks = _check_batch_plan(L, 256, 0, [2000] * 64, [2000] * 64)     # 64 x 16 row blocks: two full rounds
     assert chunks == 1
-    nitems, chunks = _check(L, 256, 0, [2000] * 4, [2000] * 4)   # 64 row blocks: columns cut to fill 512 slots
+    nitems, chunks = _check_batch_plan(L, 256, 0, [2000] * 4, [2000] * 4)  # 64 row blocks: columns cut to fill 512 slots
     assert chunks == 8 and nitems == 4 * 16 * 8
-    assert _check(L, 256, 0, [], [])[0] == 0
+    assert _check_batch_plan(L, 256, 0, [], [])[0] == 0
 
 
 def test_match_batch_plan_rejects_bad_arguments():

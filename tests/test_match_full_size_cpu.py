@@ -2,24 +2,19 @@
 against: bit-identical to a plain loop over orc_dot128 with a restated top-2 and class merge (ragged and tiny shapes,
 zero and negative rows, ties inside a 32-column slab and across slabs), its per-column best equal to the reversed
 MatchSiftData, its integer top-2 equal to the int8 contract, and within a rigorous fp32 bound of float64 at full size.
-The GPU module's comparison must reject a single wrong index, a score one ulp off and a tie resolved the wrong way."""
+The GPU module's comparison (batch_util.same_rows) must reject a single wrong index, a score one ulp off and a tie
+resolved the wrong way."""
 import numpy as np
 import pytest
 
+from batch_util import i8_records, match_np, orc, quantize_np, same_rows
 from synth import descriptors_to_points, synth_descriptors
-from test_gpu_match_full_size import _same
-from test_gpu_match_i8 import match_np, quantize_np
-
-
-def _orc():
-    from oracle import pyoracle
-    return pyoracle
 
 
 def _plain(a, b):
     """The score matrix pair by pair through orc_dot128, then the two modes restated row by row."""
     import ctypes as C
-    o = _orc()
+    o = orc()
     a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
     n1, n2 = len(a), len(b)
     S = np.zeros((n1, n2), np.float32)
@@ -90,7 +85,7 @@ def _cmp(got, exp):
 def test_core_equals_plain_loop(n1, n2):
     a, b = _tie_sets(n1, n2, 7 + n1 + n2)
     exp, _, col_best, col_row = _plain(a, b)
-    got = _orc().match_core(a, b)
+    got = orc().match_core(a, b)
     _cmp({k: got[k] for k in exp}, exp)
     assert np.array_equal(got["col_best"].view(np.uint32), col_best.view(np.uint32))
     assert np.array_equal(got["col_row"], col_row)
@@ -106,13 +101,13 @@ def test_core_does_not_depend_on_threads(threads):
     import ctypes as C
     a, b = _tie_sets(600, 250, 3)
     a[300:] = a[:300]                               # every column's best row has a twin in another thread's range
-    ref = _orc().match_core(a, b)
+    ref = orc().match_core(a, b)
     set_threads = C.CDLL("libgomp.so.1").omp_set_num_threads      # the runtime liboracle.so is linked against
     set_threads(threads)
     try:
-        got = _orc().match_core(a, b)
+        got = orc().match_core(a, b)
     finally:
-        set_threads(_orc().cpu_budget())
+        set_threads(orc().cpu_budget())
     _cmp(got, ref)
     assert (ref["col_row"][ref["col_row"] >= 0] < 300).all()
 
@@ -122,7 +117,7 @@ def test_core_rows_match_reference_matcher(n1, n2):
     """orc_match_rows runs on the core: the records equal match_records of one core pass in both modes, and the
     per-column best is the reversed full + exact match."""
     from cudasift_amd.capi import POINT_DTYPE
-    o = _orc()
+    o = orc()
     a, b = _tie_sets(n1, n2, 11)
     p1, p2 = descriptors_to_points(a, POINT_DTYPE), descriptors_to_points(b, POINT_DTYPE)
     core = o.match_core(a, b)
@@ -139,7 +134,7 @@ def test_core_rows_match_reference_matcher(n1, n2):
 def test_core_integer_top2_equals_int8_contract():
     """q as float32: every partial sum is an exact integer, so the exact top-2 is the int8 matcher's (match_np)."""
     from cudasift_amd.capi import POINT_DTYPE
-    o = _orc()
+    o = orc()
     rng = np.random.default_rng(5)
     d1, d2 = synth_descriptors(300, 21, l2=True), synth_descriptors(700, 22, l2=True)
     d1[0] = 0                                       # all-zero row
@@ -152,8 +147,7 @@ def test_core_integer_top2_equals_int8_contract():
     p2["xpos"] = rng.random(700, dtype=np.float32) * 500
     exp = match_np(p1, q1, p2, q2)
     core = o.match_core(q1.astype(np.float32), q2.astype(np.float32), columns=False)
-    from test_gpu_match_full_size import _i8_records
-    got = _i8_records(p1, p2, core)
+    got = i8_records(p1, p2, core)
     assert got.tobytes() == exp.tobytes()
     assert core["ex_idx"][0] == -1 and (core["ex_idx"][1:] == 3).all() and (core["ex_best"] == core["ex_sec"]).all()
     assert core["ex_best"][2] == 128 * 127 * 127
@@ -163,7 +157,7 @@ def test_core_within_fp32_bound_of_float64_at_scale():
     """2048 rows of bench.py's sets against all 100 000 columns: every score lies within the fp32 chain's bound
     gamma_128 * sum |a_k b_k| of its pair's float64 dot, and every chosen column within twice the bound of the row's
     float64 maximum."""
-    o = _orc()
+    o = orc()
     a, b = synth_descriptors(100000, 12345)[:2048], synth_descriptors(100000, 12346)
     core = o.match_core(a, b, columns=False)
     u = 2.0 ** -24
@@ -185,25 +179,25 @@ def test_comparison_rejects_single_faults():
     """What the GPU module compares with: one wrong index, one score one ulp off, one tie resolved to the larger
     column — each alone fails the comparison."""
     from cudasift_amd.capi import POINT_DTYPE
-    o = _orc()
+    o = orc()
     a, b = _tie_sets(70, 130, 4)
     p1, p2 = descriptors_to_points(a, POINT_DTYPE), descriptors_to_points(b, POINT_DTYPE)
     core = o.match_core(a, b)
     exp = o.match_records(p1, p2, core, True)
-    _same(exp.copy(), exp, "unchanged")
+    same_rows(exp.copy(), exp, "unchanged")
     bad = exp.copy()
     bad["match"][10] += 1
     with pytest.raises(AssertionError):
-        _same(bad, exp, "index")
+        same_rows(bad, exp, "index")
     bad = exp.copy()
     bad["score"][11] = np.nextafter(bad["score"][11], np.float32(np.inf))
     with pytest.raises(AssertionError):
-        _same(bad, exp, "score")
+        same_rows(bad, exp, "score")
     r = 6                                           # its best is the tie of columns 31 and 32: the smaller must win
     assert exp["match"][r] == 31 and core["ex_sec"][r] == core["ex_best"][r]
     bad = exp.copy()
     bad["match"][r], bad["match_xpos"][r], bad["match_ypos"][r] = 32, p2["xpos"][32], p2["ypos"][32]
     with pytest.raises(AssertionError):
-        _same(bad, exp, "tie")
+        same_rows(bad, exp, "tie")
     with pytest.raises(AssertionError):
-        _same(bad, exp, "tie", ("match",))
+        same_rows(bad, exp, "tie", ("match",))

@@ -5,6 +5,8 @@ import ctypes as C
 
 import numpy as np
 
+from batch_util import check_pair_plan, quantize_np
+
 
 def _quantize(d):
     from cudasift_amd import capi
@@ -14,19 +16,12 @@ def _quantize(d):
     return out
 
 
-def _numpy_rule(d):
-    d = np.asarray(d, np.float32)
-    with np.errstate(invalid="ignore", over="ignore"):
-        v = np.clip(np.rint(np.float32(256) * d), 0, 127)
-    return np.where(np.isnan(v), 0, v).astype(np.int8)
-
-
 def test_quantize_random_matches_numpy():
     rng = np.random.default_rng(5)
     d = np.concatenate([rng.random(200000, dtype=np.float32) * 0.6,             # SIFT range and past saturation
                         rng.normal(0, 1, 50000).astype(np.float32),
                         (rng.integers(0, 256, 20000) / np.float32(512)).astype(np.float32)])   # exact halves
-    assert np.array_equal(_quantize(d), _numpy_rule(d))
+    assert np.array_equal(_quantize(d), quantize_np(d))
 
 
 def test_quantize_edges():
@@ -38,7 +33,7 @@ def test_quantize_edges():
     want = np.array(list(cases.values()), np.int8)
     got = _quantize(d)
     assert np.array_equal(got, want), [(float(a), int(b), int(c)) for a, b, c in zip(d, got, want) if b != c]
-    assert np.array_equal(got, _numpy_rule(d))
+    assert np.array_equal(got, quantize_np(d))
     # every NaN payload and sign
     nans = np.array([0x7FC00000, 0xFFC00000, 0x7F800001, 0xFFFFFFFF, 0x7FBFFFFF], np.uint32).view(f32)
     assert (_quantize(nans) == 0).all()
@@ -62,29 +57,9 @@ def _plan(L, cus, n1, n2):
     return out[:len(n1)], ni.value, ch.value, bound.value
 
 
-def _check(L, cus, n1, n2):
+def _check_i8_plan(L, cus, n1, n2):
     plan, nitems, chunks, bound = _plan(L, cus, n1, n2)
-    covered = np.zeros(nitems, np.int32)
-    rows_total = 0
-    for p, (item0, nrb, ntiles, nch, tpc) in enumerate(plan):
-        a, b = max(int(n1[p]), 0), max(int(n2[p]), 0)
-        assert nrb == ((a + 127) // 128 if a and b else 0), (p, a, b, nrb)
-        assert ntiles == ((b + 31) // 32 if a and b else 0)                  # every column takes part
-        assert nch >= 1 and tpc >= 1
-        if ntiles:
-            assert nch * tpc >= ntiles and (nch - 1) * tpc < ntiles          # no empty chunk
-            if chunks == 1:
-                assert nch == 1 and tpc == ntiles
-        tiles = np.zeros((nrb, max(ntiles, 1)), np.int32)
-        for i in range(nrb * nch):
-            rb, c = divmod(i, nch)
-            covered[item0 + i] += 1
-            t0, t1 = c * tpc, min(c * tpc + tpc, ntiles)
-            tiles[rb, t0:t1] += 1
-        if nrb and ntiles:
-            assert (tiles[:, :ntiles] == 1).all(), p
-        rows_total += nrb
-    assert (covered == 1).all()                               # items are a partition of [0, nitems)
+    rows_total = check_pair_plan(plan, nitems, chunks, n1, n2, lambda b: (b + 31) // 32)    # every column takes part
     target = 16 * cus                                         # 4 rounds of a grid of 4 workgroups per CU
     assert bound == 2 * target
     if rows_total >= target:
@@ -104,7 +79,7 @@ def test_match_i8_plan_covers_every_block_once():
     cases += [(rng.integers(-1, 5000, n), rng.integers(-1, 5000, n)) for n in (1, 3, 8, 40, 300, 1500)]
     for cus in (256, 304, 80, 1):
         for n1, n2 in cases:
-            _check(L, cus, n1, n2)
+            _check_i8_plan(L, cus, n1, n2)
 
 
 def test_match_i8_plan_chunks_only_small_calls():

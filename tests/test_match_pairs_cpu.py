@@ -1,11 +1,11 @@
-"""The expected output tests/test_gpu_match_pairs.py holds misift_match_pairs_batch to (expected_pair: the oracle's forward
-match and, with mutual, the oracle's reversed match) against brute force on small hand-made cases with ties.  Descriptors
+"""The expected output tests/test_gpu_match_pairs.py holds misift_match_pairs_batch to (batch_util.expected_pair: the
+oracle's forward match and, with mutual, the oracle's reversed match) against brute force on small hand-made cases with ties.  Descriptors
 are small integers, so every score is exact in fp32 whatever the summation order."""
 import numpy as np
 import pytest
 
+from batch_util import expected_pair
 from synth import descriptors_to_points
-from test_gpu_match_pairs import expected_pair
 
 
 def _points(d):

@@ -13,7 +13,6 @@ import argparse
 import json
 import os
 import sys
-import time
 
 import numpy as np
 
@@ -21,6 +20,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 from cudasift_amd import capi  # noqa: E402
+from bench_common import timed  # noqa: E402
 
 H = np.array([[1.01 * np.cos(0.035), -1.01 * np.sin(0.035), 15.0],
               [1.01 * np.sin(0.035), 1.01 * np.cos(0.035), -8.0],
@@ -67,18 +67,6 @@ def candidates(p1, p2, radius):
     return int(((dx * dx + dy * dy) < np.float32(radius) * np.float32(radius)).sum())
 
 
-def timed(ctx, fn, warmup, reps):
-    for _ in range(warmup):
-        fn()
-    ts = []
-    for _ in range(reps):
-        ctx.sync()
-        t0 = time.perf_counter()
-        fn()
-        ts.append(time.perf_counter() - t0)
-    return float(np.median(ts)) * 1e3
-
-
 def run(ctx, npairs, mean, radii, warmup, reps):
     set1, set2 = pairs_of_frames(npairs, mean, 11 + npairs)
     sizes1 = np.array([len(p) for p in set1], np.int32)
@@ -96,7 +84,7 @@ def run(ctx, npairs, mean, radii, warmup, reps):
         ctx.match_batch(pairs, d1, npairs, c1, o1, 0, d2, npairs, c2, o2, 0)
         ctx.sync()
 
-    batch_ms = timed(ctx, batch, warmup, reps)
+    batch_ms = timed(ctx, batch, warmup, reps, sync_after=False)
     out = []
     for radius in radii:
         def guided():
@@ -104,7 +92,7 @@ def run(ctx, npairs, mean, radii, warmup, reps):
                                    num_found=nf)
             ctx.sync()
 
-        guided_ms = timed(ctx, guided, warmup, reps)
+        guided_ms = timed(ctx, guided, warmup, reps, sync_after=False)
         found = int(ctx.download(nf, (npairs,), np.int32).sum())
         cand = sum(candidates(a, b, radius) for a, b in zip(set1, set2))
         out.append({"pairs": npairs, "mean_records": mean, "radius": radius, "guided_ms": round(guided_ms, 4),

@@ -12,7 +12,6 @@ import ctypes as C
 import json
 import os
 import sys
-import time
 
 import numpy as np
 
@@ -20,6 +19,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 from cudasift_amd import capi  # noqa: E402
+from bench_common import timed  # noqa: E402
 from synth import synth_matches  # noqa: E402
 
 FIND = (0.85, 0.95, 5.0)          # min_score, max_ambiguity, thresh (API defaults)
@@ -31,18 +31,6 @@ def frames(n, mean, seed):
     rng = np.random.default_rng(seed)
     sizes = rng.integers(int(mean * 0.9), int(mean * 1.1), n)
     return [synth_matches(int(s), seed=seed * 1000 + f)[0] for f, s in enumerate(sizes)]
-
-
-def timed(ctx, fn, warmup, reps):
-    for _ in range(warmup):
-        fn()
-    ts = []
-    for _ in range(reps):
-        ctx.sync()
-        t0 = time.perf_counter()
-        fn()
-        ts.append(time.perf_counter() - t0)
-    return float(np.median(ts)) * 1e3
 
 
 def run(ctx, nsel, mean, loops, warmup, reps):
@@ -80,8 +68,9 @@ def run(ctx, nsel, mean, loops, warmup, reps):
         capi.check(L.misift_find_homography(ctx.h, d.ptr, int(sizes[0]), H, C.byref(nm), loops, *FIND),
                    "misift_find_homography")
 
-    t_loop, t_batch = timed(ctx, loop, warmup, reps), timed(ctx, batch, warmup, reps)
-    t_single = timed(ctx, single, warmup, max(reps, 20))
+    t_loop = timed(ctx, loop, warmup, reps, sync_after=False)
+    t_batch = timed(ctx, batch, warmup, reps, sync_after=False)
+    t_single = timed(ctx, single, warmup, max(reps, 20), sync_after=False)
     tests = float(nsel) * ((loops + 15) // 16 * 16) * float(sizes.sum()) / nsel
     return {"entries": nsel, "mean_records": mean, "loops": loops, "loop_ms": round(t_loop, 4),
             "batch_ms": round(t_batch, 4), "speedup": round(t_loop / t_batch, 2),

@@ -10,36 +10,15 @@ import ctypes as C
 import json
 import os
 import sys
-import time
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
 from cudasift_amd import capi  # noqa: E402
-from synth import synth_descriptors  # noqa: E402
+from bench_common import sequence, timed  # noqa: E402
 
 PEAK = 157.3e12
-
-
-def sequence(nframes, mean, seed):
-    rng = np.random.default_rng(seed)
-    sizes = rng.integers(int(mean * 0.9), int(mean * 1.1), nframes)
-    d = synth_descriptors(int(sizes.max()) * 2, seed)
-    frames, cur = [], d[:sizes[0]]
-    for f in range(nframes):
-        n = int(sizes[f])
-        base = cur[rng.permutation(len(cur))[:n]] if len(cur) >= n else np.concatenate([cur, d[:n - len(cur)]])
-        x = np.abs(base + rng.normal(0, 0.003, base.shape).astype(np.float32))
-        x /= np.sqrt((x * x).sum(1, keepdims=True))
-        p = np.zeros(n, capi.POINT_DTYPE)
-        p["data"] = x
-        p["xpos"] = rng.random(n) * 1920
-        p["ypos"] = rng.random(n) * 1080
-        frames.append(p)
-        cur = x
-    return frames
 
 
 def run(ctx, npairs, mean, warmup, reps):
@@ -60,17 +39,8 @@ def run(ctx, npairs, mean, warmup, reps):
         ctx.match_batch(pairs, d, npairs + 1, dc, do, 0)
         ctx.sync()
 
-    out = {}
-    for name, fn in (("loop", loop), ("batch", batch)):
-        for _ in range(warmup):
-            fn()
-        ts = []
-        for _ in range(reps):
-            ctx.sync()
-            t0 = time.perf_counter()
-            fn()
-            ts.append(time.perf_counter() - t0)
-        out[name] = float(np.median(ts)) * 1e3
+    # the timed region ends when fn returns: batch() ends with its own sync, loop() with the last misift_match
+    out = {name: timed(ctx, fn, warmup, reps, sync_after=False) for name, fn in (("loop", loop), ("batch", batch))}
     flop = 256.0 * float((sizes[:-1].astype(np.float64) * sizes[1:]).sum())
     res = {"pairs": npairs, "mean_records": mean, "loop_ms": round(out["loop"], 4), "batch_ms": round(out["batch"], 4),
            "speedup": round(out["loop"] / out["batch"], 2),

@@ -11,51 +11,16 @@ import argparse
 import json
 import os
 import sys
-import time
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
 from cudasift_amd import capi  # noqa: E402
-from synth import synth_descriptors  # noqa: E402
+from bench_common import sequence, timed  # noqa: E402
 
 PEAK_F32 = 157.3e12
 PEAK_I8 = 5.0e15
-
-
-def sequence(nframes, mean, seed):
-    rng = np.random.default_rng(seed)
-    sizes = rng.integers(int(mean * 0.9), int(mean * 1.1), nframes) if nframes > 1 else np.array([mean])
-    d = synth_descriptors(int(sizes.max()) * 2, seed)
-    frames, cur = [], d[:sizes[0]]
-    for f in range(nframes):
-        n = int(sizes[f])
-        base = cur[rng.permutation(len(cur))[:n]] if len(cur) >= n else np.concatenate([cur, d[:n - len(cur)]])
-        x = np.abs(base + rng.normal(0, 0.003, base.shape).astype(np.float32))
-        x /= np.sqrt((x * x).sum(1, keepdims=True))
-        p = np.zeros(n, capi.POINT_DTYPE)
-        p["data"] = x
-        p["xpos"] = rng.random(n) * 1920
-        p["ypos"] = rng.random(n) * 1080
-        frames.append(p)
-        cur = x
-    return frames
-
-
-def timed(ctx, fn, warmup, reps):
-    for _ in range(warmup):
-        fn()
-    ctx.sync()
-    ts = []
-    for _ in range(reps):
-        ctx.sync()
-        t0 = time.perf_counter()
-        fn()
-        ctx.sync()
-        ts.append(time.perf_counter() - t0)
-    return float(np.median(ts)) * 1e3
 
 
 def run(ctx, frames, pairs, warmup, reps, label):
@@ -66,9 +31,9 @@ def run(ctx, frames, pairs, warmup, reps, label):
     dc, do = ctx.upload(sizes), ctx.upload(offs)
     dq = ctx.zeros(128 * int(offs[-1]) + 16)
     pairs = np.asarray(pairs, np.int32)
-    t_q = timed(ctx, lambda: ctx.quantize_batch(d, nf, dc, do, 0, dq), warmup, reps)
-    t_f = timed(ctx, lambda: ctx.match_batch(pairs, d, nf, dc, do, 0), warmup, reps)
-    t_i = timed(ctx, lambda: ctx.match_batch_i8(pairs, d, dq, nf, dc, do, 0), warmup, reps)
+    t_q = timed(ctx, lambda: ctx.quantize_batch(d, nf, dc, do, 0, dq), warmup, reps, sync_after=True)
+    t_f = timed(ctx, lambda: ctx.match_batch(pairs, d, nf, dc, do, 0), warmup, reps, sync_after=True)
+    t_i = timed(ctx, lambda: ctx.match_batch_i8(pairs, d, dq, nf, dc, do, 0), warmup, reps, sync_after=True)
     ops = 256.0 * float(sum(float(sizes[a]) * float(sizes[b]) for a, b in pairs))
     n = len(pairs)
     return {"case": label, "pairs": n, "quantize_ms": round(t_q, 4), "fp32_ms": round(t_f, 4), "i8_ms": round(t_i, 4),

@@ -1,6 +1,6 @@
 """misift_match_pairs_batch against misift_match_batch on one MI355X (matcher: pair-indexed batches).
 
-Frames of the synthetic sequence of tools/match_batch_bench.py (~2000 records each) in one packed device array.
+Frames of the synthetic sequence of tools/bench_common.py (~2000 records each) in one packed device array.
   (a) pairs (f, f + 1), 64 of them: match_pairs_batch mutual = 0 against one misift_match_batch;
   (b) the same pairs with mutual = 1, against mutual = 0 and against the two-call cross-check (a forward
       misift_match_batch, then a reversed one (f + 1, f) in match_full + match_exact_top2 mode; the record copies and the
@@ -13,30 +13,13 @@ import argparse
 import json
 import os
 import sys
-import time
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
 from cudasift_amd import capi  # noqa: E402
-from match_batch_bench import sequence  # noqa: E402
-
-
-def timed(ctx, fn, warmup, reps):
-    for _ in range(warmup):
-        fn()
-    ctx.sync()
-    ts = []
-    for _ in range(reps):
-        ctx.sync()
-        t0 = time.perf_counter()
-        fn()
-        ctx.sync()
-        ts.append(time.perf_counter() - t0)
-    return round(float(np.median(ts)) * 1e3, 4)
+from bench_common import sequence, timed  # noqa: E402
 
 
 def main():
@@ -63,6 +46,9 @@ def main():
     def bufs(n):
         return ctx.zeros(576 * n * mp), ctx.zeros(4 * n), ctx.zeros(4 * n)
 
+    def ms(fn):
+        return round(timed(ctx, fn, a.warmup, a.reps, sync_after=True), 4)
+
     # (a) + (b): 64 pairs (f, f + 1)
     pairs = np.array([(f, f + 1) for f in range(64)], np.int32)
     rev = pairs[:, ::-1].copy()
@@ -74,10 +60,10 @@ def main():
         ctx.match_batch(rev, d, nfr, dc, do, 0)
         ctx.set_options(match_full=0, match_exact_top2=0)
 
-    t = {"match_batch": timed(ctx, lambda: ctx.match_batch(pairs, d, nfr, dc, do, 0), a.warmup, a.reps),
-         "pairs_mutual0": timed(ctx, pairs_call(pairs, 0, out), a.warmup, a.reps),
-         "pairs_mutual1": timed(ctx, pairs_call(pairs, 1, out), a.warmup, a.reps),
-         "two_call_crosscheck": timed(ctx, two_calls, a.warmup, a.reps)}
+    t = {"match_batch": ms(lambda: ctx.match_batch(pairs, d, nfr, dc, do, 0)),
+         "pairs_mutual0": ms(pairs_call(pairs, 0, out)),
+         "pairs_mutual1": ms(pairs_call(pairs, 1, out)),
+         "two_call_crosscheck": ms(two_calls)}
     r = {"case": "64 pairs (f, f+1)", "pairs": 64, "mean_records": a.records, **t,
          "mutual0_vs_batch": round(t["pairs_mutual0"] / t["match_batch"], 4),
          "mutual1_vs_mutual0": round(t["pairs_mutual1"] / t["pairs_mutual0"], 4),
@@ -95,9 +81,9 @@ def main():
         for p in per_k:
             ctx.match_batch(p, d, nfr, dc, do, 0)
 
-    t = {"pairs_one_call": timed(ctx, pairs_call(win, 0, out), a.warmup, a.reps),
-         "pairs_one_call_mutual1": timed(ctx, pairs_call(win, 1, out), a.warmup, a.reps),
-         "match_batch_x4": timed(ctx, four_calls, a.warmup, a.reps)}
+    t = {"pairs_one_call": ms(pairs_call(win, 0, out)),
+         "pairs_one_call_mutual1": ms(pairs_call(win, 1, out)),
+         "match_batch_x4": ms(four_calls)}
     r = {"case": "window W=4 over 64 frames", "pairs": int(len(win)), "mean_records": a.records, **t,
          "one_call_vs_four": round(t["pairs_one_call"] / t["match_batch_x4"], 4)}
     print(json.dumps(r), flush=True)
