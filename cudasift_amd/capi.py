@@ -103,6 +103,8 @@ SIGNATURES = {
     "misift_match_guided_batch": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _f, _i, _vp]),
     "misift_quantize_batch": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp]),
     "misift_match_batch_i8": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i]),
+    "misift_match_pairs_batch_i8": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _i,
+                                         _vp, _vp, _vp]),
     "misift_test_quantize": (_i, [_vp, C.c_long, _vp]),
     "misift_test_match_i8_plan": (_i, [_i, _i, _vp, _vp, _vp, _ip, _ip, _ip]),
     "misift_test_libc_rand": (_i, [C.c_uint, _i, _vp]),
@@ -640,6 +642,32 @@ class Context:
                                           _dptr(counts1), _dptr(offsets1), stride1, _dptr(recs2), _dptr(q2), nframes2,
                                           _dptr(counts2), _dptr(offsets2), stride2),
               "misift_match_batch_i8")
+
+    def match_pairs_batch_i8(self, pairs, recs1, q1, nframes1, counts1, offsets1=None, stride1=0, recs2=None, q2=None,
+                             nframes2=None, counts2=None, offsets2=None, stride2=None, max_pts=8192, mutual=False,
+                             out=None, out_counts=None, num_matched=None):
+        """misift_match_pairs_batch_i8: match_pairs_batch with the scores of match_batch_i8 — pair-indexed output rows
+        (row r of pair i is out[i * max_pts + r]) from the 8-bit descriptors q1 / q2 (quantize_batch's output for recs1
+        / recs2), so frames may repeat across pairs; with `mutual` only rows that are also their match's best row keep
+        the match.  Set 2 (records and q) defaults to set 1.  out, out_counts and num_matched as in match_pairs_batch:
+        device buffers, allocated here when None; returns (out, out_counts, num_matched).  Enqueued on the context
+        stream."""
+        recs2, q2, nframes2, counts2, offsets2, stride2 = _set2((recs1, q1, nframes1, counts1, offsets1, stride1),
+                                                                (recs2, q2, nframes2, counts2, offsets2, stride2))
+        pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        n = max(len(pairs), 1)
+        if out is None:
+            out = self.zeros(POINT_DTYPE.itemsize * n * max(max_pts, 1))
+        if out_counts is None:
+            out_counts = self.zeros(4 * n)
+        if num_matched is None:
+            num_matched = self.zeros(4 * n)
+        check(lib().misift_match_pairs_batch_i8(self.h, len(pairs), pairs.ctypes.data, _dptr(recs1), _dptr(q1),
+                                                nframes1, _dptr(counts1), _dptr(offsets1), stride1, _dptr(recs2),
+                                                _dptr(q2), nframes2, _dptr(counts2), _dptr(offsets2), stride2, max_pts,
+                                                int(mutual), _dptr(out), _dptr(out_counts), _dptr(num_matched)),
+              "misift_match_pairs_batch_i8")
+        return out, out_counts, num_matched
 
     def match_split(self, pts1, n1, pts2, n2, own_tile_begin, own_tile_end):
         """Test hook: misift_match with the column sweep cut into two launches (the sharded matcher's cut)."""

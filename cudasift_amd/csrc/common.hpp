@@ -565,6 +565,11 @@ int launch_quantize_batch(misift_ctx *ctx, const BatchLayout &set, int nframes, 
 int launch_match_pairs_batch(misift_ctx *ctx, int npairs, const int *h_pairs, void *d_plan, const BatchLayout &set1,
                              const BatchLayout &set2, int max_pts, int mutual, void *d_out, int *d_out_counts,
                              int *d_num_matched);
+// misift_match_pairs_batch_i8 (kernels_match_i8.hip): the match_batch_i8 plan and sweep into pair-indexed output rows;
+// temp sized as for misift_match_pairs_batch
+int launch_match_pairs_batch_i8(misift_ctx *ctx, int npairs, const int *h_pairs, void *d_plan, const BatchLayout &set1,
+                                const int8_t *q1, const BatchLayout &set2, const int8_t *q2, int max_pts, int mutual,
+                                void *d_out, int *d_out_counts, int *d_num_matched);
 // misift_find_homography_batch / misift_improve_homography_batch (homography.hip); find takes its temp from
 // misift_ensure_tmp
 size_t find_homography_batch_tmp_bytes(int nsel, int max_pts, int num_loops);

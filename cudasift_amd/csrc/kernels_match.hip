@@ -422,7 +422,7 @@ __global__ __launch_bounds__(1024) void pair_plan_kernel(const int *__restrict__
 #include "pair_plan_body.inc"
 #undef PAIR_PLAN_CAPPED
 }
-// misift_match_pairs_batch: oversized pairs get no work
+// misift_match_pairs_batch and misift_match_pairs_batch_i8: oversized pairs get no work
 __global__ __launch_bounds__(1024) void pair_plan_capped_kernel(const int *__restrict__ pairs, int npairs,
                                                                 BatchLayout set1, BatchLayout set2, PairShape S,
                                                                 int max_pts, int *__restrict__ num_matched,
@@ -442,6 +442,17 @@ int launch_pair_plan(misift_ctx *ctx, const char *name, const PairShape &S, int 
   LaunchScope ls(ctx, name);
   hipLaunchKernelGGL(pair_plan_kernel, dim3(1), dim3(1024), 0, ctx->stream, h_pairs, npairs, set1, set2, S, hdr,
                      reinterpret_cast<PairPlan *>(hdr + PAIR_HDR_INTS));
+  return ls.finish();
+}
+
+int launch_pair_plan_capped(misift_ctx *ctx, const char *name, const PairShape &S, int npairs, const int *h_pairs,
+                            const BatchLayout &set1, const BatchLayout &set2, int max_pts, int *d_num_matched,
+                            void *d_plan)
+{
+  int *hdr = reinterpret_cast<int *>(d_plan);
+  LaunchScope ls(ctx, name);
+  hipLaunchKernelGGL(pair_plan_capped_kernel, dim3(1), dim3(1024), 0, ctx->stream, h_pairs, npairs, set1, set2, S,
+                     max_pts, d_num_matched, hdr, reinterpret_cast<PairPlan *>(hdr + PAIR_HDR_INTS));
   return ls.finish();
 }
 
@@ -873,13 +884,8 @@ int launch_match_pairs_batch(misift_ctx *ctx, int npairs, const int *h_pairs, vo
   unsigned long long *keys = mutual ? reinterpret_cast<unsigned long long *>((char *)ctx->d_match_tmp + part_bytes) : nullptr;
   int *hdr = reinterpret_cast<int *>(d_plan);
   PairPlan *plan = reinterpret_cast<PairPlan *>(hdr + PAIR_HDR_INTS);
-  {
-    LaunchScope ls(ctx, "match_pairs_plan");
-    hipLaunchKernelGGL(pair_plan_capped_kernel, dim3(1), dim3(1024), 0, ctx->stream, h_pairs, npairs, set1, set2, S,
-                       max_pts, d_num_matched, hdr, plan);
-    rc = ls.finish();
-    if (rc) return rc;
-  }
+  rc = launch_pair_plan_capped(ctx, "match_pairs_plan", S, npairs, h_pairs, set1, set2, max_pts, d_num_matched, d_plan);
+  if (rc) return rc;
   if (mutual) HIP_TRY(hipMemsetAsync(keys, 0, key_bytes, ctx->stream));
   const float *f2 = reinterpret_cast<const float *>(set2.recs);
   SiftPointD *out = reinterpret_cast<SiftPointD *>(d_out);

@@ -1,5 +1,5 @@
 // kernels_match_i8.hip — 8-bit descriptors and brute-force matching of many frame pairs on the int8 matrix cores of gfx950
-// (misift_quantize_batch, misift_match_batch_i8).
+// (misift_quantize_batch, misift_match_batch_i8, misift_match_pairs_batch_i8).
 //
 // quantize_i8_kernel   one launch: q[r] = quantize_i8(data of record r) (quantize_i8.hpp), 128 bytes at d_q + 128 r, for
 //                      every record of every frame; eight lanes per record, 16 bytes each.
@@ -19,6 +19,7 @@
 //                      second) per row and chunk, and
 // match_i8_merge_kernel merges them over the chunks (it returns at once when nothing was chunked).
 // Columns are cut into chunks only when the row blocks of the call do not fill I8_TARGET_ROUNDS rounds of the grid.
+// The tile loop is match_i8_sweep.inc; the pair-indexed kernels that share it are described further down.
 //
 // The A and B fragments of the i8 MFMA are loaded by the same code (lane l: row / column l & 31, bytes 64 (l >> 5) + 16 s
 // of k-step s), so the sum over k is right whatever order the hardware pairs the bytes of one k-step in; integer sums do
@@ -52,6 +53,19 @@ struct I8Args {
   int4 *partial;                 // items x I8_ROWS x (best, index, second, 0), chunked calls only
 };
 
+// misift_match_pairs_batch_i8: set 1 is read only, the rows go to out + pair * max_pts
+struct I8PairsArgs {
+  const SiftPointD *recs1, *recs2;
+  const int8_t *q1, *q2;
+  const int *hdr;
+  const PairPlan *plan;
+  int npairs, max_pts;
+  SiftPointD *out;
+  unsigned long long *keys;      // npairs x max_pts column keys, mutual calls only
+  int *num_matched;              // may be NULL
+  int4 *partial;                 // as I8Args
+};
+
 __host__ __device__ __forceinline__ int i8_grid(int ncu) { return I8_WG_PER_CU * (ncu > 0 ? ncu : 256); }
 // the plan's shape: 128-row blocks, 32-column tiles, every column
 PairShape i8_shape(int ncu)
@@ -77,6 +91,43 @@ __device__ __forceinline__ void i8_write_row(SiftPointD *o, const SiftPointD *se
   o->match_xpos = i >= 0 ? set2[i].xpos : 0.0f;
   o->match_ypos = i >= 0 ? set2[i].ypos : 0.0f;
   o->ambiguity = ((float)s * 0x1p-16f) / (score + 1e-6f);
+}
+
+__device__ __forceinline__ void i8_no_match(SiftPointD *o)
+{
+  o->score = 0.0f;
+  o->ambiguity = 0.0f;
+  o->match = -1;
+  o->match_xpos = 0.0f;
+  o->match_ypos = 0.0f;
+}
+
+// Column keys of misift_match_pairs_batch_i8's mutual check (the design of colkey_* in kernels_match.hip on integer
+// scores): key = (S << 32) | (0xFFFFFFFF - row), so that for S > 0 the unsigned order of keys is (larger S, then smaller
+// row), and an atomic max over any cut of the rows and columns leaves the column's best row: the match
+// misift_match_batch_i8 with the sets swapped writes.  0 = no row with S > 0.
+// Of one tile a lane holds 32 scores of its column, acc0[r] and acc1[r], whose rows ascend with k = 16 ai + r (row =
+// row0 + 32 ai + (r & 3) + 8 (r >> 2) + 4 h).  Its best is the maximum of the packed (S << 5) | (31 - k), S <= 2^21: the
+// smaller k of equal S is the larger.  S <= 0 packs to at most 31 or to a negative number and decodes to "none"; rows at
+// or above n1 have zero q, so S = 0.  The two lane halves are combined as (S << 6) | (63 - row within the wave), and the
+// 32 lanes of half 0 issue one 8-byte atomic each: 32 consecutive columns, 256 contiguous bytes.
+__device__ __forceinline__ void i8_colkey_tile(unsigned long long *key, const v16i &acc0, const v16i &acc1, int row0,
+                                               int h)
+{
+  int pk = 0;
+#pragma unroll
+  for (int r = 0; r < 16; r++)
+    pk = max(pk, max((int)((unsigned)acc0[r] << 5) | (31 - r), (int)((unsigned)acc1[r] << 5) | (15 - r)));
+  const int s = pk >> 5, k = 31 - (pk & 31);
+  const int rl = 32 * (k >> 4) + (k & 3) + 8 * ((k & 15) >> 2) + 4 * h;
+  const unsigned mine = s > 0 ? ((unsigned)s << 6) | (unsigned)(63 - rl) : 0u;
+  const auto sw = __builtin_amdgcn_permlane32_swap(mine, mine, false, false);   // [1] in lanes 0-31: lane + 32's value
+  const unsigned best = max(mine, (unsigned)sw[1]);
+  if (h == 0 && best != 0u) {
+    const unsigned row = (unsigned)row0 + 63u - (best & 63u);
+    __hip_atomic_fetch_max(key, ((unsigned long long)(best >> 6) << 32) | (0xFFFFFFFFu - row), __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
+  }
 }
 
 __device__ __forceinline__ unsigned i8_pack4(float4 v)
@@ -126,87 +177,9 @@ __global__ __launch_bounds__(64 * I8_WAVES) void match_i8_kernel(I8Args A)
     const int local = it - P.item0, rb = local / P.nchunks, chunk = local - rb * P.nchunks;
     const int t0 = chunk * P.tpc, t1 = min(t0 + P.tpc, P.ntiles);
     const int row0 = rb * I8_ROWS + wave * 64;
-    v4i a[2][4];
-#pragma unroll
-    for (int ai = 0; ai < 2; ai++) {
-      const int row = row0 + 32 * ai + c;
-      if (row < P.n1) {
-        const v4i *p = reinterpret_cast<const v4i *>(A.q1 + ((size_t)P.off1 + row) * 128 + 64 * h);
-#pragma unroll
-        for (int s = 0; s < 4; s++) a[ai][s] = p[s];
-      } else {
-#pragma unroll
-        for (int s = 0; s < 4; s++) a[ai][s] = (v4i){0, 0, 0, 0};
-      }
-    }
-    const int8_t *q2 = A.q2 + (size_t)P.off2 * 128 + 64 * h;
-    int M = 0, I = -1, S2 = 0;
-    for (int w0 = t0; w0 < t1; w0 += I8_WIN) {
-      const int w1 = min(w0 + I8_WIN, t1);
-      unsigned b1[2][16], b2[2][16];
-#pragma unroll
-      for (int ai = 0; ai < 2; ai++)
-#pragma unroll
-        for (int r = 0; r < 16; r++) { b1[ai][r] = 0u; b2[ai][r] = 0u; }
-      // set-2 tiles ping-pong between two register sets, each loaded one tile ahead of its use.  Only the pair's last
-      // tile can be partial: it runs on its own after the loop, its lanes past the last column zeroed (S = 0 never counts).
-      v4i bA[4], bB[4];
-      auto load = [&](v4i (&b)[4], int t) {
-        const v4i *p = reinterpret_cast<const v4i *>(q2 + (size_t)(t * I8_TILE + c) * 128);
-#pragma unroll
-        for (int s = 0; s < 4; s++) b[s] = p[s];
-      };
-      auto tile = [&](v4i (&b)[4], int t) {
-        v16i acc0 = {}, acc1 = {};
-#pragma unroll
-        for (int s = 0; s < 4; s++) {
-          acc0 = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[0][s], b[s], acc0, 0, 0, 0);
-          acc1 = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[1][s], b[s], acc1, 0, 0, 0);
-        }
-        const unsigned kc = __builtin_amdgcn_readfirstlane(I8_OFF + (unsigned)(I8_WIN - 1 - (t - w0)));
-#pragma unroll
-        for (int r = 0; r < 16; r++) {
-          const unsigned k0 = ((unsigned)acc0[r] << 9) + kc, k1 = ((unsigned)acc1[r] << 9) + kc;
-          b2[0][r] = max(min(b1[0][r], b2[0][r]), min(max(b1[0][r], b2[0][r]), k0));
-          b1[0][r] = max(b1[0][r], k0);
-          b2[1][r] = max(min(b1[1][r], b2[1][r]), min(max(b1[1][r], b2[1][r]), k1));
-          b1[1][r] = max(b1[1][r], k1);
-        }
-      };
-      const int wf = min(w1, P.n2 / I8_TILE);             // tiles [w0, wf) are full
-      if (w0 < wf) load(bA, w0);
-      for (int t = w0; t < wf; t += 2) {           // unconditional loads (the last ones repeat tile wf - 1): static vmcnt
-        load(bB, min(t + 1, wf - 1));
-        tile(bA, t);
-        if (t + 1 >= wf) break;
-        load(bA, min(t + 2, wf - 1));
-        tile(bB, t + 1);
-      }
-      if (wf < w1) {
-        const bool live = wf * I8_TILE + c < P.n2;
-        if (live) load(bA, wf);
-        else {
-#pragma unroll
-          for (int s = 0; s < 4; s++) bA[s] = (v4i){0, 0, 0, 0};
-        }
-        tile(bA, wf);
-      }
-      // fold the window: lane (c, h) reads row register c of the 32 lanes of its half
-#pragma unroll
-      for (int ai = 0; ai < 2; ai++)
-#pragma unroll
-        for (int r = 0; r < 16; r++) red[wave][16 * ai + r][lane] = make_uint2(b1[ai][r], b2[ai][r]);
-      __syncthreads();
-      for (int l = 0; l < 32; l++) {
-        const uint2 e = red[wave][c][32 * h + l];
-        const bool v1 = e.x >= I8_VALID;
-        const int s1 = v1 ? (int)((e.x - I8_OFF) >> 9) : 0;
-        const int j1 = v1 ? (w0 + I8_WIN - 1 - (int)(e.x & (I8_WIN - 1))) * I8_TILE + l : -1;
-        const int s2 = e.y >= I8_VALID ? (int)((e.y - I8_OFF) >> 9) : 0;
-        i8_take(M, I, S2, s1, j1, s2);
-      }
-      __syncthreads();                           // red is rewritten by the next window / item
-    }
+#define I8_COL_KEYS(t, acc0, acc1)
+#include "match_i8_sweep.inc"
+#undef I8_COL_KEYS
     const int row = row0 + own;
     if (row < P.n1) {
       if (C == 1) i8_write_row(A.recs1 + P.off1 + row, A.recs2 + P.off2, M, I, S2);
@@ -231,6 +204,113 @@ __global__ __launch_bounds__(I8_ROWS) void match_i8_merge_kernel(I8Args A)
       i8_take(M, I, S2, v.x, v.y, v.z);
     }
     i8_write_row(A.recs1 + P.off1 + row, A.recs2 + P.off2, M, I, S2);
+  }
+}
+
+// ================================================================ pair-indexed matching (misift_match_pairs_batch_i8)
+// The pairs of misift_match_batch_i8, but every pair writes its own output rows out[i * max_pts + row], so that frames
+// may repeat across pairs, and with `mutual` only the rows that are also their column's best row keep their match.
+//   pair_plan_capped_kernel       the plan of match_i8 (same PairShape), oversized pairs without work (pair_plan.hpp);
+//   (mutual) memset               the column keys of every (pair, column) to 0;
+//   match_pairs_i8_kernel         the sweep of match_i8_kernel (match_i8_sweep.inc); unchunked calls write the seven
+//                                 output fields of their rows (and count them without mutual), chunked ones their
+//                                 partials; with MUTUAL it maintains the column keys (i8_colkey_tile);
+//   match_pairs_i8_final_kernel   per (pair, row): the chunk merge or the row the sweep wrote, the mutual test against
+//                                 the key of its match, the final row, d_num_matched and d_out_counts.
+// recs1 / recs2 and q1 / q2 are read only; each pair may be the same array.
+template <bool MUTUAL>
+__global__ __launch_bounds__(64 * I8_WAVES) void match_pairs_i8_kernel(I8PairsArgs A)
+{
+  __shared__ uint2 red[I8_WAVES][32][64];
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int c = lane & 31, h = lane >> 5;
+  const int nitems = A.hdr[0], C = A.hdr[1];
+  const int own = 32 * (c >> 4) + (c & 3) + 8 * ((c & 15) >> 2) + 4 * h;
+  for (int it = (int)xcd_remap(blockIdx.x, gridDim.x); it < nitems; it += gridDim.x) {
+    const int pi = __builtin_amdgcn_readfirstlane(pair_find<false>(A.plan, A.npairs, it));
+    PairPlan P = A.plan[pi];
+    P.n1 = __builtin_amdgcn_readfirstlane(P.n1); P.n2 = __builtin_amdgcn_readfirstlane(P.n2);
+    P.off1 = __builtin_amdgcn_readfirstlane(P.off1); P.off2 = __builtin_amdgcn_readfirstlane(P.off2);
+    P.ntiles = __builtin_amdgcn_readfirstlane(P.ntiles); P.nchunks = __builtin_amdgcn_readfirstlane(P.nchunks);
+    P.tpc = __builtin_amdgcn_readfirstlane(P.tpc); P.item0 = __builtin_amdgcn_readfirstlane(P.item0);
+    const int local = it - P.item0, rb = local / P.nchunks, chunk = local - rb * P.nchunks;
+    const int t0 = chunk * P.tpc, t1 = min(t0 + P.tpc, P.ntiles);
+    const int row0 = rb * I8_ROWS + wave * 64;
+    unsigned long long *const ck_keys = A.keys + (size_t)pi * A.max_pts;
+#define I8_COL_KEYS(t, acc0, acc1) \
+  if constexpr (MUTUAL) i8_colkey_tile(ck_keys + (size_t)(t) * I8_TILE + c, acc0, acc1, row0, h)
+#include "match_i8_sweep.inc"
+#undef I8_COL_KEYS
+    const int row = row0 + own;
+    bool matched = false;            // unchunked, no filter: the row's final match is known here, and counted here
+    if (row < P.n1) {
+      if (C == 1) {
+        SiftPointD *o = A.out + (size_t)pi * A.max_pts + row;
+        o->xpos = A.recs1[P.off1 + row].xpos;
+        o->ypos = A.recs1[P.off1 + row].ypos;
+        i8_write_row(o, A.recs2 + P.off2, M, I, S2);
+        matched = !MUTUAL && I >= 0;
+      } else {
+        A.partial[(size_t)it * I8_ROWS + wave * 64 + own] = make_int4(M, I, S2, 0);
+      }
+    }
+    if (!MUTUAL && C == 1 && A.num_matched) {
+      const int n = __popcll(__ballot(matched));
+      if (lane == 0 && n > 0) atomicAdd(A.num_matched + pi, n);
+    }
+  }
+}
+
+// A unit is 256 rows of one pair, one thread per row; units of rows at or above n1 and of oversized pairs only write the
+// pair's count.
+__global__ __launch_bounds__(256) void match_pairs_i8_final_kernel(I8PairsArgs A, int mutual,
+                                                                   int *__restrict__ out_counts)
+{
+  const int C = A.hdr[1];
+  const int groups = (A.max_pts + 255) / 256;
+  const long long nunits = (long long)A.npairs * groups;
+  for (long long u = blockIdx.x; u < nunits; u += gridDim.x) {
+    const int pi = (int)(u / groups), g = (int)(u - (long long)pi * groups);
+    const PairPlan P = A.plan[pi];
+    if (g == 0 && threadIdx.x == 0) out_counts[pi] = P.pad ? -1 : P.n1;
+    if (P.pad || g * 256 >= P.n1) continue;                       // uniform over the workgroup
+    if (!mutual && C == 1 && P.n2 > 0) continue;                  // the sweep wrote and counted these rows
+    const int row = g * 256 + threadIdx.x;
+    bool matched = false;
+    if (row < P.n1) {
+      SiftPointD *o = A.out + (size_t)pi * A.max_pts + row;
+      if (P.n2 == 0) {                                            // no column: a no-match row
+        o->xpos = A.recs1[P.off1 + row].xpos;
+        o->ypos = A.recs1[P.off1 + row].ypos;
+        i8_no_match(o);
+      } else {
+        int M = 0, I = -1, S2 = 0;
+        if (C > 1) {
+          const int rb = row / I8_ROWS, rr = row % I8_ROWS;
+          const int4 *q = A.partial + (size_t)(P.item0 + rb * P.nchunks) * I8_ROWS + rr;
+          for (int ch = 0; ch < P.nchunks; ch++, q += I8_ROWS) {
+            const int4 v = *q;
+            i8_take(M, I, S2, v.x, v.y, v.z);
+          }
+        } else {
+          I = o->match;                                           // the row match_pairs_i8_kernel wrote
+        }
+        // the mutual test: the column's key names its best row (0 cannot occur here: S of this row and its match is > 0)
+        const bool reject =
+            mutual && I >= 0 && 0xFFFFFFFFu - (unsigned)A.keys[(size_t)pi * A.max_pts + I] != (unsigned)row;
+        if (C > 1) {
+          o->xpos = A.recs1[P.off1 + row].xpos;
+          o->ypos = A.recs1[P.off1 + row].ypos;
+          if (reject) i8_no_match(o);
+          else i8_write_row(o, A.recs2 + P.off2, M, I, S2);
+        } else if (reject) {
+          i8_no_match(o);                                         // unchunked: xpos / ypos are the sweep's
+        }
+        matched = I >= 0 && !reject;
+      }
+    }
+    const int n = __syncthreads_count(matched);
+    if (A.num_matched && threadIdx.x == 0 && n > 0) atomicAdd(A.num_matched + pi, n);
   }
 }
 
@@ -287,5 +367,42 @@ int launch_match_batch_i8(misift_ctx *ctx, int npairs, const int *h_pairs, void 
   }
   LaunchScope ls(ctx, "match_i8_merge");
   hipLaunchKernelGGL(match_i8_merge_kernel, dim3(grid), dim3(I8_ROWS), 0, ctx->stream, A);
+  return ls.finish();
+}
+
+// Enqueue misift_match_pairs_batch_i8 on the context stream (common.hpp): plan, (mutual) key memset, sweep, finalize.
+int launch_match_pairs_batch_i8(misift_ctx *ctx, int npairs, const int *h_pairs, void *d_plan, const BatchLayout &set1,
+                                const int8_t *q1, const BatchLayout &set2, const int8_t *q2, int max_pts, int mutual,
+                                void *d_out, int *d_out_counts, int *d_num_matched)
+{
+  if (npairs <= 0) return MISIFT_OK;
+  const PairShape S = i8_shape(ctx->num_cus);
+  const size_t part_bytes = (size_t)pair_partial_items(S) * I8_ROWS * sizeof(int4);
+  const size_t key_bytes = mutual ? sizeof(unsigned long long) * (size_t)npairs * max_pts : 0;
+  int rc = misift_ensure_tmp(ctx, part_bytes + key_bytes);
+  if (rc) return rc;
+  rc = launch_pair_plan_capped(ctx, "match_pairs_i8_plan", S, npairs, h_pairs, set1, set2, max_pts, d_num_matched,
+                               d_plan);
+  if (rc) return rc;
+  I8PairsArgs A;
+  A.recs1 = set1.recs; A.recs2 = set2.recs; A.q1 = q1; A.q2 = q2;
+  A.hdr = reinterpret_cast<const int *>(d_plan);
+  A.plan = reinterpret_cast<const PairPlan *>(A.hdr + PAIR_HDR_INTS);
+  A.npairs = npairs; A.max_pts = max_pts;
+  A.out = reinterpret_cast<SiftPointD *>(d_out);
+  A.keys = mutual ? reinterpret_cast<unsigned long long *>((char *)ctx->d_match_tmp + part_bytes) : nullptr;
+  A.num_matched = d_num_matched;
+  A.partial = reinterpret_cast<int4 *>(ctx->d_match_tmp);
+  if (mutual) HIP_TRY(hipMemsetAsync(A.keys, 0, key_bytes, ctx->stream));
+  const int grid = i8_grid(ctx->num_cus);
+  {
+    LaunchScope ls(ctx, "match_pairs_i8_mfma");
+    if (mutual) hipLaunchKernelGGL(match_pairs_i8_kernel<true>, dim3(grid), dim3(64 * I8_WAVES), 0, ctx->stream, A);
+    else hipLaunchKernelGGL(match_pairs_i8_kernel<false>, dim3(grid), dim3(64 * I8_WAVES), 0, ctx->stream, A);
+    rc = ls.finish();
+    if (rc) return rc;
+  }
+  LaunchScope ls(ctx, "match_pairs_i8_final");
+  hipLaunchKernelGGL(match_pairs_i8_final_kernel, dim3(grid), dim3(256), 0, ctx->stream, A, mutual, d_out_counts);
   return ls.finish();
 }

@@ -2310,6 +2310,33 @@ extern "C" int misift_match_batch_i8(misift_ctx *ctx, int npairs, const int *pai
                    });
 }
 
+// misift_match_pairs_batch with the scores of misift_match_batch_i8: pair-indexed output rows, optional mutual check.
+extern "C" int misift_match_pairs_batch_i8(misift_ctx *ctx, int npairs, const int *pairs, const void *d_recs1,
+                                           const int8_t *d_q1, int nframes1, const int *d_counts1,
+                                           const int *d_offsets1, int stride1, const void *d_recs2, const int8_t *d_q2,
+                                           int nframes2, const int *d_counts2, const int *d_offsets2, int stride2,
+                                           int max_pts, int mutual, void *d_out, int *d_out_counts, int *d_num_matched)
+{
+  ARG_CHECK(ctx && npairs >= 0);
+  if (npairs == 0) return MISIFT_OK;
+  ARG_CHECK(pairs && d_recs1 && d_recs2 && d_q1 && d_q2 && d_counts1 && d_counts2 && d_out && d_out_counts &&
+            nframes1 > 0 && nframes2 > 0);
+  ARG_CHECK(((uintptr_t)d_q1 & 15) == 0 && ((uintptr_t)d_q2 & 15) == 0);
+  ARG_CHECK(max_pts >= 1 && (mutual == 0 || mutual == 1));
+  ARG_CHECK(d_out != d_recs1 && d_out != d_recs2);
+  BatchLayout set1, set2;
+  int rc = batch_layout(__func__, d_recs1, d_counts1, d_offsets1, stride1, &set1);
+  if (!rc) rc = batch_layout(__func__, d_recs2, d_counts2, d_offsets2, stride2, &set2);
+  if (!rc) rc = check_frames(__func__, npairs, pairs, 2, nframes1, nframes2, true);
+  if (rc) return rc;
+  RoctxRange range(__func__);
+  return run_batch(ctx, {{pairs, sizeof(int) * 2 * (size_t)npairs}}, pair_plan_bytes(npairs),
+                   [&](int *h_pairs, void *d_plan) {
+                     return launch_match_pairs_batch_i8(ctx, npairs, h_pairs, d_plan, set1, d_q1, set2, d_q2, max_pts,
+                                                        mutual, d_out, d_out_counts, d_num_matched);
+                   });
+}
+
 // ------------------------------------------------------------------- timing
 extern "C" int misift_timer_start(misift_ctx *ctx)
 {

@@ -1,4 +1,5 @@
-// pair_plan.hpp — the work list of the batched pair matchers (misift_match_batch, misift_match_batch_i8).
+// pair_plan.hpp — the work list of the batched pair matchers (misift_match_batch, misift_match_batch_i8,
+// misift_match_pairs_batch, misift_match_pairs_batch_i8).
 //
 // pair_plan_kernel (kernels_match.hip), one workgroup, reads the pairs' counts and offsets on the device and writes a
 // header and one PairPlan per pair: the pair's shape, its column chunking and the exclusive prefix sums of its work
@@ -69,6 +70,11 @@ size_t pair_plan_bytes(int npairs);
 // caller keeps it unchanged until the kernel has run); d_plan: pair_plan_bytes(npairs) bytes.
 int launch_pair_plan(misift_ctx *ctx, const char *name, const PairShape &S, int npairs, const int *h_pairs,
                      const BatchLayout &set1, const BatchLayout &set2, void *d_plan);
+// The capped plan of the pair-indexed matchers (pair_plan_capped_kernel): a pair with more than max_pts records on a
+// side gets no work and pad = 1; d_num_matched (may be NULL) starts at 0, or -1 for such a pair.
+int launch_pair_plan_capped(misift_ctx *ctx, const char *name, const PairShape &S, int npairs, const int *h_pairs,
+                            const BatchLayout &set1, const BatchLayout &set2, int max_pts, int *d_num_matched,
+                            void *d_plan);
 // The same plan on the host for pairs of n1[i] x n2[i] records (the test hooks): plan5[5 i ..] = first item, row blocks,
 // tiles, chunks, tiles per chunk of pair i.
 int pair_plan_host(const PairShape &S, int npairs, const int *n1, const int *n2, int *plan5, int *nitems, int *chunks,

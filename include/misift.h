@@ -403,8 +403,9 @@ int misift_match_pairs_batch(misift_ctx *ctx, int npairs, const int *pairs,
  *     caller's behind the most recent batch), misift_ctx_wait_batch (a stream of the caller's waits for it),
  *     misift_gather_post (marks the most recent batch) or misift_ctx_sync;
  *   - the scratch arena and the output buffers of a call must stay untouched until that batch is done: rotate >= K sets.
- *   - misift_match_batch, misift_find_homography_batch, misift_improve_homography_batch and misift_match_guided_batch
- *     (which run on the context stream) on a batch's packed records: make the context stream wait for that batch first
+ *   - misift_match_batch, misift_match_pairs_batch, misift_quantize_batch, misift_match_batch_i8,
+ *     misift_match_pairs_batch_i8, misift_find_homography_batch, misift_improve_homography_batch and
+ *     misift_match_guided_batch (which run on the context stream) on a batch's packed records: make the context stream wait for that batch first
  *     (misift_ctx_wait_batch(ctx, <the context's stream>), or an event from misift_ctx_record_batch).
  * K = 1 (default) is the plain in-order context.  Also MISIFT_BATCHES_IN_FLIGHT at context creation.  Changing K drains
  * the context. */
@@ -625,6 +626,45 @@ int misift_match_batch_i8(misift_ctx *ctx, int npairs, const int *pairs,
                           int stride1,
                           const void *d_recs2, const int8_t *d_q2, int nframes2, const int *d_counts2,
                           const int *d_offsets2, int stride2);
+/* Pair-indexed batch matching on 8-bit descriptors (no reference counterpart; opt-in: every other call keeps its bits):
+ * misift_match_pairs_batch with the scores of misift_match_batch_i8.  Pairs, frames, layouts (d_offsets or stride),
+ * count -1 = no records, the host `pairs` the library copies, stream order on the context stream with no host
+ * synchronisation and no host read of the counts, and ordering behind batches in flight (K > 1): as
+ * misift_match_pairs_batch.  d_q1 / d_q2 are the 128-byte descriptors of the records of d_recs1 / d_recs2 at the same
+ * record indices (what misift_quantize_batch writes).  For pair i = (f1, f2), n1 = max(count1[f1], 0) and
+ * n2 = max(count2[f2], 0).
+ *   - A set-1 frame and a set-2 frame may appear in any number of pairs; (f, f), d_recs1 == d_recs2 and d_q1 == d_q2 are
+ *     allowed.  Nothing in d_recs1, d_recs2, d_q1 or d_q2 is written.  The call reads only q, set 1's xpos / ypos and
+ *     set 2's xpos / ypos.
+ *   - n1 > max_pts or n2 > max_pts: d_out_counts[i] = -1 and d_num_matched[i] = -1; none of the pair's output bytes is
+ *     written.  Otherwise d_out_counts[i] = n1, and output row r < n1 of pair i is the record d_out + (i * max_pts + r),
+ *     of which exactly seven fields are written: xpos and ypos (set-1 record r's), and score, ambiguity, match,
+ *     match_xpos, match_ypos, byte-identical to what misift_match_batch_i8 on that pair writes into set-1 record r:
+ *     S_rj = sum_k q1[r][k] * q2[j][k], exact in int32, over every column j (whatever match_full / match_exact_top2
+ *     say); only S > 0 counts; m = the smallest frame-local j of the largest S, second = the largest over j != m;
+ *     score = (float)best * 2^-16, ambiguity = ((float)second * 2^-16) / (score + 1e-6f).  n2 == 0: every row is a
+ *     no-match row (score 0, ambiguity 0, match -1, match_xpos 0, match_ypos 0).  Every other byte of d_out is untouched.
+ *   - mutual = 1 (cross-check): a row r with forward match m >= 0 keeps it only if r is the best row of column m over
+ *     all n1 rows — the largest S_rm > 0, the smallest row on a tie: the match misift_match_batch_i8 with the two sets
+ *     swapped writes for set-2 record m; otherwise it becomes a no-match row.  mutual = 0: no filter.
+ *   - d_num_matched (may be NULL): per pair, the output rows with match >= 0 after the filter.
+ *   - The output is a batch the homography calls take as it is: frame i = pair i, d_offsets NULL, stride = max_pts,
+ *     counts = d_out_counts (misift_find_homography_batch, misift_improve_homography_batch).
+ *   - NULL ctx, npairs < 0, a frame index outside [0, nframes) of its set, a NULL records, q, counts, d_out or
+ *     d_out_counts pointer, d_q1 or d_q2 not 16-byte aligned, max_pts < 1, mutual other than 0 or 1, d_out equal to
+ *     d_recs1 or d_recs2, d_offsets NULL with a negative stride: MISIFT_EINVAL, before anything is enqueued.
+ *     npairs == 0: MISIFT_OK, nothing happens.
+ *   - The call returns before the GPU work is done.  Three launches and, with mutual, one memset, whatever npairs (plan,
+ *     sweep, finalize); temp memory is sized from npairs, max_pts and the CU count only. */
+int misift_match_pairs_batch_i8(misift_ctx *ctx, int npairs, const int *pairs,
+                                const void *d_recs1, const int8_t *d_q1, int nframes1, const int *d_counts1,
+                                const int *d_offsets1, int stride1,
+                                const void *d_recs2, const int8_t *d_q2, int nframes2, const int *d_counts2,
+                                const int *d_offsets2, int stride2,
+                                int max_pts, int mutual,
+                                void *d_out,          /* npairs * max_pts records (576 B each), device */
+                                int *d_out_counts,    /* npairs, device */
+                                int *d_num_matched);  /* npairs, device, may be NULL */
 
 /* cudaMallocManaged as used by the reference's MANAGEDMEM build flavour (cudaSiftH.cu:239-240): one pointer valid on
  * host and device (SiftData.m_data). */
