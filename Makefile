@@ -10,7 +10,7 @@ HIPFLAGS := --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Iinclu
             -Wno-unused-result -Wno-unused-value
 HIPSRCS  := $(CSRC)/kernels_pyramid.hip $(CSRC)/kernels_dog.hip $(CSRC)/kernels_points.hip \
             $(CSRC)/kernels_match.hip $(CSRC)/misift_host.hip $(CSRC)/homography.hip $(CSRC)/pipeline.hip \
-            $(CSRC)/multigpu.hip $(CSRC)/kernels_guided.hip $(CSRC)/kernels_match_i8.hip
+            $(CSRC)/multigpu.hip $(CSRC)/kernels_guided.hip $(CSRC)/kernels_match_i8.hip $(CSRC)/kernels_tracks.hip
 HIPOBJS  := $(patsubst $(CSRC)/%.hip,$(BUILD)/%.o,$(HIPSRCS))
 
 all: cudasift_amd/libmisift.so cudasift_amd/libcudasift.so cudasift_amd/libcudasift_managed.so oracle dropin build/pmc_calib build/valu_rates build/scan_rates build/single_call

@@ -105,6 +105,7 @@ SIGNATURES = {
     "misift_match_batch_i8": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i]),
     "misift_match_pairs_batch_i8": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _i,
                                          _vp, _vp, _vp]),
+    "misift_link_tracks_batch": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _f, _f, _f, _vp, _vp, _vp, _vp]),
     "misift_test_quantize": (_i, [_vp, C.c_long, _vp]),
     "misift_test_match_i8_plan": (_i, [_i, _i, _vp, _vp, _vp, _ip, _ip, _ip]),
     "misift_test_libc_rand": (_i, [C.c_uint, _i, _vp]),
@@ -668,6 +669,34 @@ class Context:
                                                 int(mutual), _dptr(out), _dptr(out_counts), _dptr(num_matched)),
               "misift_match_pairs_batch_i8")
         return out, out_counts, num_matched
+
+    def link_tracks_batch(self, pairs, rows, row_counts, max_pts, nframes, counts, offsets=None, stride=0,
+                          max_records=None, min_score=0.85, max_ambiguity=0.95, max_error=float("inf"), track=None,
+                          track_len=None, track_frames=None, summary=None):
+        """misift_link_tracks_batch: the accepted matches of a pair-indexed batch (`rows`, `row_counts`, `max_pts`:
+        match_pairs_batch's out, out_counts and max_pts for `pairs`) joined across pairs into feature tracks over the
+        global record indices of the one record batch (nframes, counts, offsets or stride) both frames of every pair
+        belong to.  A row is an edge when its match is a record of frame f2, score > min_score, ambiguity <
+        max_ambiguity and, with a finite max_error, match_error < max_error.  track, track_len, track_frames
+        (max_records ints each, mirroring the record indices) and summary (8 ints) are device buffers, allocated here
+        when None; returns the four.  Enqueued on the context stream."""
+        pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        assert max_records is not None, "max_records: the length of the record index space"
+        n = 4 * max(max_records, 1)
+        if track is None:
+            track = self.zeros(n)
+        if track_len is None:
+            track_len = self.zeros(n)
+        if track_frames is None:
+            track_frames = self.zeros(n)
+        if summary is None:
+            summary = self.zeros(4 * 8)
+        check(lib().misift_link_tracks_batch(self.h, len(pairs), pairs.ctypes.data if len(pairs) else None,
+                                             _dptr(rows), _dptr(row_counts), max_pts, nframes, _dptr(counts),
+                                             _dptr(offsets), stride, max_records, min_score, max_ambiguity, max_error,
+                                             _dptr(track), _dptr(track_len), _dptr(track_frames), _dptr(summary)),
+              "misift_link_tracks_batch")
+        return track, track_len, track_frames, summary
 
     def match_split(self, pts1, n1, pts2, n2, own_tile_begin, own_tile_end):
         """Test hook: misift_match with the column sweep cut into two launches (the sharded matcher's cut)."""

@@ -585,6 +585,12 @@ size_t match_guided_batch_tmp_bytes(int npairs, int nd, int max_pts);
 int launch_match_guided_batch(misift_ctx *ctx, int npairs, const int *h_pairs, const int *h_pair_d,
                               const int *h_distinct, int nd, const BatchLayout &set1, const BatchLayout &set2,
                               const float *H, float radius, int max_pts, int *num_found);
+// misift_link_tracks_batch (kernels_tracks.hip): one memset + five launches; temp from misift_ensure_tmp, sized from
+// max_records and npairs only
+int launch_link_tracks_batch(misift_ctx *ctx, int npairs, const int *h_pairs, const void *d_rows,
+                             const int *d_row_counts, int max_pts, const BatchLayout &set, int nframes, int max_records,
+                             float min_score, float max_ambiguity, float max_error, int *d_track, int *d_track_len,
+                             int *d_track_frames, int *d_summary);
 int launch_test_exp2(misift_ctx *ctx, const float *x, float *out, int n);
 int launch_test_points_fn(misift_ctx *ctx, int fn, const float *x, const float *y, float *out, float *out2, int n);
 int launch_selftest(misift_ctx *ctx);

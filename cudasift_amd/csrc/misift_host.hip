@@ -2337,6 +2337,35 @@ extern "C" int misift_match_pairs_batch_i8(misift_ctx *ctx, int npairs, const in
                    });
 }
 
+// The accepted matches of a pair-indexed batch joined across pairs into feature tracks: connected components over the
+// global record indices of one batch, labelled by their smallest member.  Only the rows, the counts and the offsets are
+// read.
+extern "C" int misift_link_tracks_batch(misift_ctx *ctx, int npairs, const int *pairs, const void *d_rows,
+                                        const int *d_row_counts, int max_pts, int nframes, const int *d_counts,
+                                        const int *d_offsets, int stride, int max_records, float min_score,
+                                        float max_ambiguity, float max_error, int *d_track, int *d_track_len,
+                                        int *d_track_frames, int *d_summary)
+{
+  ARG_CHECK(ctx && npairs >= 0 && nframes >= 0);
+  ARG_CHECK((pairs || npairs == 0) && d_rows && d_row_counts && d_counts);
+  ARG_CHECK(d_track && d_track_len && d_track_frames && d_summary);
+  ARG_CHECK(max_pts >= 1 && max_records >= 1);
+  ARG_CHECK(min_score == min_score && max_ambiguity == max_ambiguity);      // not NaN
+  ARG_CHECK(max_error > 0.0f);                                              // NaN fails too
+  BatchLayout set;
+  int rc = batch_layout(__func__, nullptr, d_counts, d_offsets, stride, &set);
+  if (!rc) rc = check_frames(__func__, npairs, pairs, 2, nframes, nframes, true);
+  if (rc) return rc;
+  RoctxRange range(__func__);
+  static const int no_pair[2] = {0, 0};                                     // npairs == 0: the list slot is never read
+  const HostList list = npairs ? HostList{pairs, sizeof(int) * 2 * (size_t)npairs} : HostList{no_pair, sizeof(no_pair)};
+  return run_batch(ctx, {list}, 0, [&](int *h_pairs, void *) {
+    return launch_link_tracks_batch(ctx, npairs, h_pairs, d_rows, d_row_counts, max_pts, set, nframes, max_records,
+                                    min_score, max_ambiguity, max_error, d_track, d_track_len, d_track_frames,
+                                    d_summary);
+  });
+}
+
 // ------------------------------------------------------------------- timing
 extern "C" int misift_timer_start(misift_ctx *ctx)
 {

@@ -404,8 +404,8 @@ int misift_match_pairs_batch(misift_ctx *ctx, int npairs, const int *pairs,
  *     misift_gather_post (marks the most recent batch) or misift_ctx_sync;
  *   - the scratch arena and the output buffers of a call must stay untouched until that batch is done: rotate >= K sets.
  *   - misift_match_batch, misift_match_pairs_batch, misift_quantize_batch, misift_match_batch_i8,
- *     misift_match_pairs_batch_i8, misift_find_homography_batch, misift_improve_homography_batch and
- *     misift_match_guided_batch (which run on the context stream) on a batch's packed records: make the context stream wait for that batch first
+ *     misift_match_pairs_batch_i8, misift_find_homography_batch, misift_improve_homography_batch,
+ *     misift_match_guided_batch and misift_link_tracks_batch (which run on the context stream) on a batch's packed records: make the context stream wait for that batch first
  *     (misift_ctx_wait_batch(ctx, <the context's stream>), or an event from misift_ctx_record_batch).
  * K = 1 (default) is the plain in-order context.  Also MISIFT_BATCHES_IN_FLIGHT at context creation.  Changing K drains
  * the context. */
@@ -665,6 +665,54 @@ int misift_match_pairs_batch_i8(misift_ctx *ctx, int npairs, const int *pairs,
                                 void *d_out,          /* npairs * max_pts records (576 B each), device */
                                 int *d_out_counts,    /* npairs, device */
                                 int *d_num_matched);  /* npairs, device, may be NULL */
+
+/* Feature tracks of a pair-indexed batch (no reference counterpart): the accepted matches of every pair of
+ * misift_match_pairs_batch / misift_match_pairs_batch_i8 joined ACROSS pairs into connected components, on the device.
+ * A track is one scene point seen in several frames; it is usable (consistent) iff no two of its records lie in one
+ * frame.  pairs, d_rows, d_row_counts and max_pts are what the pair matcher took and produced (d_out, d_out_counts):
+ * pair i = (f1, f2), its row r is the record d_rows + (i * max_pts + r), d_row_counts[i] its row count or -1.  Both
+ * frames of every pair belong to ONE record batch (the d_recs1 == d_recs2 windows and exhaustive sets), described by
+ * nframes, d_counts and d_offsets (NULL: stride): record r of frame f has the global index
+ * g(f, r) = (d_offsets ? d_offsets[f] : f * stride) + r, and frame f holds max(d_counts[f], 0) records.  The records
+ * themselves are not an argument: nothing but the rows, the counts and the offsets is read.
+ *   - Row r of pair i is an edge g(f1, r) -- g(f2, m) iff r < min(d_row_counts[i], max(d_counts[f1], 0), max_pts), its
+ *     match field m satisfies 0 <= m < max(d_counts[f2], 0), score > min_score and ambiguity < max_ambiguity (the gate
+ *     of matching.cu:1035, as in misift_find_homography_batch) and, when max_error is finite, match_error < max_error
+ *     (what misift_improve_homography_batch writes into those rows).  With max_error = +inf match_error is not read at
+ *     all (the matchers leave it untouched).  A comparison with a NaN field is false.  A pair with d_row_counts[i] < 0
+ *     contributes nothing.  A self edge is a no-op; pairs (f, f) are allowed (they can only make inconsistent tracks).
+ *   - d_track, d_track_len and d_track_frames are max_records ints each and mirror the record index space (as d_q of
+ *     misift_quantize_batch does).  For every valid record g: d_track[g] = the smallest global index of g's component
+ *     (a record with no accepted edge labels itself); d_track_len[g] = the records of the component if d_track[g] == g,
+ *     else 0; d_track_frames[g] = the distinct frames among them if d_track[g] == g, else 0.  A track is consistent iff
+ *     len == frames.  Slots that are no frame's valid record (padding of a strided layout, anything at or above the
+ *     end, frames of count -1) are never written.
+ *   - A frame whose records do not all lie in [0, max_records) takes no part: no labels, and every edge touching it is
+ *     dropped.
+ *   - d_summary (8 ints): [0] accepted edges (rows are counted: duplicates count twice, self edges once), [1] tracks
+ *     with len >= 2, [2] records in those tracks, [3] how many of those tracks are inconsistent, [4] the longest track
+ *     (1 when every record is a singleton, 0 without records), [5] frames dropped for lying outside max_records,
+ *     [6] = [7] = 0.
+ *   - Deterministic: all four outputs are functions of the edge set alone (labels are minima, everything else an
+ *     integer sum), so they are byte-identical from run to run, whatever the dispatch order and whatever
+ *     MISIFT_DETERMINISTIC says.
+ *   - NULL ctx, npairs < 0, nframes < 0, a frame index outside [0, nframes), NULL d_rows, d_row_counts, d_counts or
+ *     output pointer, max_pts < 1, max_records < 1, d_offsets NULL with a negative stride, min_score or max_ambiguity
+ *     NaN, max_error NaN or <= 0: MISIFT_EINVAL, before anything is enqueued.  npairs == 0 is no error: every valid
+ *     record becomes a singleton.  nframes == 0 writes only the summary.
+ *   - The call runs on the context stream and returns before the GPU work is done; `pairs` is host memory the library
+ *     copies; no host synchronisation and no host read of any count.  Ordering behind batches in flight (K > 1): as
+ *     misift_match_batch.
+ *   - One memset and five launches, whatever npairs and whatever the data (init, hook, label, distinct frames,
+ *     summary).  Temp memory is 20 bytes per record of max_records plus 16 per pair, from the library's own allocator;
+ *     nothing is sized by max_records x nframes or by anything read from the device. */
+int misift_link_tracks_batch(misift_ctx *ctx, int npairs, const int *pairs /* host, npairs x 2 */,
+                             const void *d_rows, const int *d_row_counts, int max_pts,
+                             int nframes, const int *d_counts, const int *d_offsets, int stride,
+                             int max_records,
+                             float min_score, float max_ambiguity, float max_error,
+                             int *d_track, int *d_track_len, int *d_track_frames,
+                             int *d_summary /* 8 ints */);
 
 /* cudaMallocManaged as used by the reference's MANAGEDMEM build flavour (cudaSiftH.cu:239-240): one pointer valid on
  * host and device (SiftData.m_data). */
