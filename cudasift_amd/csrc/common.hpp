@@ -120,6 +120,16 @@ __device__ __forceinline__ unsigned xcd_remap(unsigned b, unsigned nb)
   return base + i;
 }
 
+// The five match fields of a row without a match (the batched pair matchers).
+__device__ __forceinline__ void write_no_match(SiftPointD *o)
+{
+  o->score = 0.0f;
+  o->ambiguity = 0.0f;
+  o->match = -1;
+  o->match_xpos = 0.0f;
+  o->match_ypos = 0.0f;
+}
+
 // Exclusive scan of N ints per thread over a 1024-thread workgroup: v[k] becomes the sum of v[k] over the threads before
 // this one, tot[k] the workgroup's total.  s: 16 x N ints of LDS.  Every thread of the workgroup calls it.
 template <int N> __device__ __forceinline__ void block_scan(int (&v)[N], int (&tot)[N], int (*s)[N])
@@ -553,23 +563,26 @@ int launch_match_split(misift_ctx *ctx, SiftPointD *pts1, int row_begin, int row
                        int packed2 = 0);     // packed2: set 2 is an array of MISIFT_MATCH_COLUMN_BYTES match columns, not records
 enum { MATCH_PHASE_ALL = 0, MATCH_PHASE_OWN = 1, MATCH_PHASE_REST = 2 };
 // The batch calls on the context stream.  h_*: pinned host copies of the caller's lists (read by the launches).
-// misift_match_batch / misift_match_batch_i8 (kernels_match.hip, kernels_match_i8.hip): plan + sweep + merge; d_plan:
-// pair_plan_bytes(npairs) bytes of device memory (pair_plan.hpp); partials from misift_ensure_tmp, sized from the CUs
-int launch_match_batch(misift_ctx *ctx, int npairs, const int *h_pairs, void *d_plan, const BatchLayout &set1,
-                       const BatchLayout &set2);
-int launch_match_batch_i8(misift_ctx *ctx, int npairs, const int *h_pairs, void *d_plan, const BatchLayout &set1,
-                          const int8_t *q1, const BatchLayout &set2, const int8_t *q2);
+// The pair matchers (kernels_match.hip, kernels_match_i8.hip): plan + sweep + finish,
+// in place (misift_match_batch, _i8; `rows` unused) or into pair-indexed output rows (misift_match_pairs_batch, _i8).
+// d_plan: pair_plan_bytes(npairs) bytes of device memory; temp from misift_ensure_tmp, sized from npairs, max_pts and the
+// CU count only
+// Where a batched matcher's rows go: into set 1 itself (misift_match_batch, _i8), or pair-indexed to
+// out[pair * max_pts + row] (misift_match_pairs_batch, _i8), there without or with the mutual check.
+enum PairOut { PAIR_OUT_INPLACE = 0, PAIR_OUT_INDEXED = 1, PAIR_OUT_MUTUAL = 2 };
+// the pair-indexed output (unused in place)
+struct PairRows {
+  int max_pts;
+  void *out;
+  int *out_counts;
+  int *num_matched;              // may be NULL
+};
+int launch_match_batch(misift_ctx *ctx, PairOut mode, int npairs, const int *h_pairs, void *d_plan,
+                       const BatchLayout &set1, const BatchLayout &set2, const PairRows &rows);
+int launch_match_batch_i8(misift_ctx *ctx, PairOut mode, int npairs, const int *h_pairs, void *d_plan,
+                          const BatchLayout &set1, const int8_t *q1, const BatchLayout &set2, const int8_t *q2,
+                          const PairRows &rows);
 int launch_quantize_batch(misift_ctx *ctx, const BatchLayout &set, int nframes, int8_t *q);
-// misift_match_pairs_batch (kernels_match.hip): the match_batch plan and sweep into pair-indexed output rows; temp from
-// misift_ensure_tmp, sized from npairs, max_pts and the CU count only
-int launch_match_pairs_batch(misift_ctx *ctx, int npairs, const int *h_pairs, void *d_plan, const BatchLayout &set1,
-                             const BatchLayout &set2, int max_pts, int mutual, void *d_out, int *d_out_counts,
-                             int *d_num_matched);
-// misift_match_pairs_batch_i8 (kernels_match_i8.hip): the match_batch_i8 plan and sweep into pair-indexed output rows;
-// temp sized as for misift_match_pairs_batch
-int launch_match_pairs_batch_i8(misift_ctx *ctx, int npairs, const int *h_pairs, void *d_plan, const BatchLayout &set1,
-                                const int8_t *q1, const BatchLayout &set2, const int8_t *q2, int max_pts, int mutual,
-                                void *d_out, int *d_out_counts, int *d_num_matched);
 // misift_find_homography_batch / misift_improve_homography_batch (homography.hip); find takes its temp from
 // misift_ensure_tmp
 size_t find_homography_batch_tmp_bytes(int nsel, int max_pts, int num_loops);

@@ -15,7 +15,10 @@
 // (matching.cu:375-390) can be reproduced exactly — or replaced by the exact second best.
 // Columns are split into chunks across workgroups to fill 256 CUs; a small merge kernel
 // combines the per-chunk class triples and writes score/match/ambiguity/match_xpos/ypos.
-// match_batch_*: the same sweep over many independent frame pairs whose sizes only the device knows (misift_match_batch).
+// match_batch_kernel<MODE> + match_batch_merge_kernel / match_pairs_final_kernel: the same sweep over many independent
+// frame pairs whose sizes only the device knows, into set 1 itself (misift_match_batch) or into pair-indexed output
+// rows with an optional mutual check (misift_match_pairs_batch); pair_plan_kernel / pair_plan_capped_kernel: their
+// work list, and the int8 matchers'.
 #include <stdlib.h>
 #include <string.h>
 #include <vector>
@@ -82,6 +85,29 @@ __device__ __forceinline__ void top2_merge(float &mx, float &sec, int &ix, float
   sec = take ? sec_take : sec_keep;
   mx = take ? omx : mx;
   ix = take ? oix : ix;
+}
+// The final combination of the eight class summaries of one row: the reference's lossy merge, literally
+// (matching.cu:375-390), or the exact second best under match_exact_top2.
+__device__ __forceinline__ void mb_combine(int exact_top2, const float (&cmax)[8], const float (&csec)[8],
+                                           const int (&cidx)[8], float &max_score, float &sec_score, int &index)
+{
+  if (exact_top2) {
+    max_score = cmax[0]; sec_score = csec[0]; index = cidx[0];
+#pragma unroll
+    for (int c = 1; c < 8; c++) top2_merge(max_score, sec_score, index, cmax[c], csec[c], cidx[c]);
+  } else {
+    max_score = cmax[0]; sec_score = csec[0]; index = cidx[0];
+#pragma unroll
+    for (int y = 0; y < 8; y++)
+      if (index != cidx[y]) {
+        if (cmax[y] > max_score) {
+          sec_score = fmaxf(max_score, sec_score);
+          max_score = cmax[y];
+          index = cidx[y];
+        } else if (cmax[y] > sec_score)
+          sec_score = cmax[y];
+      }
+  }
 }
 // lane ^ 1 / lane ^ 2 within a quad: one DPP move each (quad_perm [1,0,3,2] = 0xB1, [2,3,0,1] = 0x4E), no LDS round trip
 template <int CTRL> __device__ __forceinline__ int quad_xchg(int v)
@@ -231,24 +257,7 @@ __global__ __launch_bounds__(256) void match_merge_kernel(SiftPointD *__restrict
   if (live && (t & 7) == 0) {
     float max_score, sec_score;
     int index;
-    if (exact_top2) {
-      max_score = cmax[0]; sec_score = csec[0]; index = cidx[0];
-  #pragma unroll
-      for (int c = 1; c < 8; c++) top2_merge(max_score, sec_score, index, cmax[c], csec[c], cidx[c]);
-    } else {
-      // the reference's final merge, literally (matching.cu:375-390)
-      max_score = cmax[0]; sec_score = csec[0]; index = cidx[0];
-  #pragma unroll
-      for (int y = 0; y < 8; y++)
-        if (index != cidx[y]) {
-          if (cmax[y] > max_score) {
-            sec_score = fmaxf(max_score, sec_score);
-            max_score = cmax[y];
-            index = cidx[y];
-          } else if (cmax[y] > sec_score)
-            sec_score = cmax[y];
-        }
-    }
+    mb_combine(exact_top2, cmax, csec, cidx, max_score, sec_score, index);
     SiftPointD *o = &pts1[G.row_begin + rl];
     o->score = max_score;
     o->match = index;
@@ -395,16 +404,24 @@ int launch_match(misift_ctx *ctx, SiftPointD *pts1, int row_begin, int row_count
   return launch_match_split(ctx, pts1, row_begin, row_count, pts2, n2, nullptr, 0, 0, nullptr, MATCH_PHASE_ALL, 0);
 }
 
-// ============================================================================ batched pair matching (misift_match_batch)
-// MatchSiftData of many independent (frame of set 1, frame of set 2) pairs in three launches, with the frames' sizes known
-// on the device only:
+// ============================================================================ batched pair matching
+// (misift_match_batch, misift_match_pairs_batch)
+// MatchSiftData of many independent (frame of set 1, frame of set 2) pairs, with the frames' sizes known on the device
+// only.  The rows go into set 1 itself (in place: a frame of set 1 in at most one pair), or pair-indexed to
+// out[i * max_pts + row], where frames may repeat across pairs, and with `mutual` only the rows that are also their
+// column's reversed match keep their match (PairOut, pair_plan.hpp).
 //   pair_plan_kernel          one workgroup: the work list of the pairs (pair_plan.hpp), here with 128-row blocks and
-//                             64-column super-tiles; it serves misift_match_batch_i8 too.
-//   match_batch_kernel        persistent grid of two workgroups per CU; each takes items in a fixed stride and runs the
+//   pair_plan_capped_kernel   64-column super-tiles; they serve the int8 matchers too.  Capped (pair-indexed): oversized
+//                             pairs get no work;
+//   (mutual) memset           the column keys of every (pair, column) to 0;
+//   match_batch_kernel<MODE>  persistent grid of two workgroups per CU; each takes items in a fixed stride and runs the
 //                             same sweep as match_kernel (match_sweep.inc) on them.  With one chunk per row block the
-//                             workgroup merges the eight classes and writes its rows itself; otherwise it stores the
-//                             per-class triples of the item and
-//   match_batch_merge_kernel  merges them over the chunks (it returns at once when nothing was chunked).
+//                             workgroup merges the eight classes and writes its rows itself (pair-indexed: all seven
+//                             output fields, counted unless mutual); otherwise it stores the per-class triples of the
+//                             item.  Mutual: it maintains the column keys;
+//   match_batch_merge_kernel  in place: merges the triples over the chunks (it returns at once when nothing was chunked);
+//   match_pairs_final_kernel  pair-indexed, per (pair, row): the chunk merge or the row the sweep wrote, the mutual test
+//                             against the key of its match, the final row, d_num_matched and d_out_counts.
 // Columns are cut into chunks only when the row blocks of the whole call do not fill one round (two workgroups per CU).
 #define MB_PART_FLOATS (MT_ROWS_PER_BLOCK * 8 * 3)     // per-class (max, second, index) of an item's 128 rows
 
@@ -422,7 +439,7 @@ __global__ __launch_bounds__(1024) void pair_plan_kernel(const int *__restrict__
 #include "pair_plan_body.inc"
 #undef PAIR_PLAN_CAPPED
 }
-// misift_match_pairs_batch and misift_match_pairs_batch_i8: oversized pairs get no work
+// the pair-indexed matchers: oversized pairs get no work
 __global__ __launch_bounds__(1024) void pair_plan_capped_kernel(const int *__restrict__ pairs, int npairs,
                                                                 BatchLayout set1, BatchLayout set2, PairShape S,
                                                                 int max_pts, int *__restrict__ num_matched,
@@ -435,25 +452,28 @@ __global__ __launch_bounds__(1024) void pair_plan_capped_kernel(const int *__res
 
 size_t pair_plan_bytes(int npairs) { return sizeof(int) * PAIR_HDR_INTS + sizeof(PairPlan) * ((size_t)npairs + 1); }
 
-int launch_pair_plan(misift_ctx *ctx, const char *name, const PairShape &S, int npairs, const int *h_pairs,
-                     const BatchLayout &set1, const BatchLayout &set2, void *d_plan)
+int launch_pair_head(misift_ctx *ctx, const char *plan_name, const PairShape &S, PairOut mode, size_t part_bytes,
+                     int npairs, const int *h_pairs, const BatchLayout &set1, const BatchLayout &set2,
+                     const PairRows &rows, void *d_plan, unsigned long long **keys)
 {
+  const size_t key_bytes = mode == PAIR_OUT_MUTUAL ? sizeof(unsigned long long) * (size_t)npairs * rows.max_pts : 0;
+  int rc = misift_ensure_tmp(ctx, part_bytes + key_bytes);
+  if (rc) return rc;
+  *keys = key_bytes ? reinterpret_cast<unsigned long long *>((char *)ctx->d_match_tmp + part_bytes) : nullptr;
   int *hdr = reinterpret_cast<int *>(d_plan);
-  LaunchScope ls(ctx, name);
-  hipLaunchKernelGGL(pair_plan_kernel, dim3(1), dim3(1024), 0, ctx->stream, h_pairs, npairs, set1, set2, S, hdr,
-                     reinterpret_cast<PairPlan *>(hdr + PAIR_HDR_INTS));
-  return ls.finish();
-}
-
-int launch_pair_plan_capped(misift_ctx *ctx, const char *name, const PairShape &S, int npairs, const int *h_pairs,
-                            const BatchLayout &set1, const BatchLayout &set2, int max_pts, int *d_num_matched,
-                            void *d_plan)
-{
-  int *hdr = reinterpret_cast<int *>(d_plan);
-  LaunchScope ls(ctx, name);
-  hipLaunchKernelGGL(pair_plan_capped_kernel, dim3(1), dim3(1024), 0, ctx->stream, h_pairs, npairs, set1, set2, S,
-                     max_pts, d_num_matched, hdr, reinterpret_cast<PairPlan *>(hdr + PAIR_HDR_INTS));
-  return ls.finish();
+  PairPlan *plan = reinterpret_cast<PairPlan *>(hdr + PAIR_HDR_INTS);
+  {
+    LaunchScope ls(ctx, plan_name);
+    if (mode == PAIR_OUT_INPLACE)
+      hipLaunchKernelGGL(pair_plan_kernel, dim3(1), dim3(1024), 0, ctx->stream, h_pairs, npairs, set1, set2, S, hdr, plan);
+    else
+      hipLaunchKernelGGL(pair_plan_capped_kernel, dim3(1), dim3(1024), 0, ctx->stream, h_pairs, npairs, set1, set2, S,
+                         rows.max_pts, rows.num_matched, hdr, plan);
+    rc = ls.finish();
+    if (rc) return rc;
+  }
+  if (key_bytes) HIP_TRY(hipMemsetAsync(*keys, 0, key_bytes, ctx->stream));
+  return MISIFT_OK;
 }
 
 int pair_plan_host(const PairShape &S, int npairs, const int *n1, const int *n2, int *plan5, int *nitems, int *chunks,
@@ -483,53 +503,22 @@ int pair_plan_host(const PairShape &S, int npairs, const int *n1, const int *n2,
   return MISIFT_OK;
 }
 
-// The reference's final combination of the eight class summaries of one row (matching.cu:375-390; exact second best
-// under match_exact_top2) and the row's five match fields — what match_merge_kernel does for a row of misift_match.
-// set2: the pair's set-2 records.  mb_combine: the same combination without the stores (match_pairs_final_kernel; kept
-// apart from mb_write_row, whose callers compile as they did).
-__device__ __forceinline__ void mb_combine(int exact_top2, const float (&cmax)[8], const float (&csec)[8],
-                                           const int (&cidx)[8], float &max_score, float &sec_score, int &index)
+// the sweep's geometry of one pair: all its rows, its own chunks, SiftPoint records
+__device__ __forceinline__ MatchGeom mb_geom(const PairPlan &P)
 {
-  if (exact_top2) {
-    max_score = cmax[0]; sec_score = csec[0]; index = cidx[0];
-#pragma unroll
-    for (int c = 1; c < 8; c++) top2_merge(max_score, sec_score, index, cmax[c], csec[c], cidx[c]);
-  } else {
-    max_score = cmax[0]; sec_score = csec[0]; index = cidx[0];
-#pragma unroll
-    for (int y = 0; y < 8; y++)
-      if (index != cidx[y]) {
-        if (cmax[y] > max_score) {
-          sec_score = fmaxf(max_score, sec_score);
-          max_score = cmax[y];
-          index = cidx[y];
-        } else if (cmax[y] > sec_score)
-          sec_score = cmax[y];
-      }
-  }
+  MatchGeom G;
+  G.row_begin = 0; G.row_count = P.n1; G.n1_total = P.n1;
+  G.n2 = P.n2; G.ncols = P.ncols;
+  G.ntiles = P.ntiles; G.nchunks = P.nchunks; G.tiles_per_chunk = P.tpc;
+  G.tile_base = 0; G.hole_begin = 0x7fffffff; G.hole_len = 0;
+  G.chunk_base = 0; G.nchunks_total = P.nchunks;
+  G.stride2 = MISIFT_POINT_BYTES / 4; G.data_off2 = 16; G.xy_off2 = 0;
+  return G;
 }
-__device__ __forceinline__ void mb_write_row(SiftPointD *o, const float *set2, int exact_top2, const float (&cmax)[8],
-                                             const float (&csec)[8], const int (&cidx)[8])
+// The five match fields of a row from its combined summary — what match_merge_kernel stores for a row of misift_match.
+// set2: the pair's set-2 records.
+__device__ __forceinline__ void mb_store_row(SiftPointD *o, const float *set2, float max_score, float sec_score, int index)
 {
-  float max_score, sec_score;
-  int index;
-  if (exact_top2) {
-    max_score = cmax[0]; sec_score = csec[0]; index = cidx[0];
-#pragma unroll
-    for (int c = 1; c < 8; c++) top2_merge(max_score, sec_score, index, cmax[c], csec[c], cidx[c]);
-  } else {
-    max_score = cmax[0]; sec_score = csec[0]; index = cidx[0];
-#pragma unroll
-    for (int y = 0; y < 8; y++)
-      if (index != cidx[y]) {
-        if (cmax[y] > max_score) {
-          sec_score = fmaxf(max_score, sec_score);
-          max_score = cmax[y];
-          index = cidx[y];
-        } else if (cmax[y] > sec_score)
-          sec_score = cmax[y];
-      }
-  }
   o->score = max_score;
   o->match = index;
   const float *m2 = set2 + (size_t)(index >= 0 ? index : 0) * (MISIFT_POINT_BYTES / 4);
@@ -537,14 +526,44 @@ __device__ __forceinline__ void mb_write_row(SiftPointD *o, const float *set2, i
   o->match_ypos = index >= 0 ? m2[1] : 0.0f;
   o->ambiguity = sec_score / (max_score + 1e-6f);
 }
+__device__ __forceinline__ void mb_write_row(SiftPointD *o, const float *set2, int exact_top2, const float (&cmax)[8],
+                                             const float (&csec)[8], const int (&cidx)[8])
+{
+  float max_score, sec_score;
+  int index;
+  mb_combine(exact_top2, cmax, csec, cidx, max_score, sec_score, index);
+  mb_store_row(o, set2, max_score, sec_score, index);
+}
+// Eight threads per row, one per class: this thread's class merged over the pair's chunks in ascending order, as
+// match_merge_kernel does, then the eight classes of the row in every lane of the group.  q: the class's triple in the
+// row block's first chunk; dead rows (!live) read nothing.
+__device__ __forceinline__ void mb_merge_chunks(bool live, const float *q, int nchunks, float (&cmax)[8],
+                                                float (&csec)[8], int (&cidx)[8])
+{
+  float m = 0.0f, sd = 0.0f;
+  int ixm = -1;
+  if (live)
+    for (int ch = 0; ch < nchunks; ch++, q += MB_PART_FLOATS) top2_merge(m, sd, ixm, q[0], q[1], __float_as_int(q[2]));
+#pragma unroll
+  for (int c = 0; c < 8; c++) {
+    cmax[c] = __shfl(m, c, 8);
+    csec[c] = __shfl(sd, c, 8);
+    cidx[c] = __shfl(ixm, c, 8);
+  }
+}
 
-// recs1 / recs2 may be the same array (frame f against frame f + 1 of one packed batch): the sweep reads descriptors and
-// xpos / ypos only, and the rows written here are the five match fields — never the same bytes.
-__global__ __launch_bounds__(64 * MT_WG_WAVES, 8 / MT_WG_WAVES) void match_batch_kernel(SiftPointD *recs1,
+// recs1 / recs2 are read only (descriptors, xpos / ypos) and may be the same array.  In place, `out` is recs1 again
+// (frame f against frame f + 1 of one packed batch): the rows written are the five match fields — never bytes the sweep
+// reads — so no pointer to the records is __restrict__.
+template <int MODE>
+__global__ __launch_bounds__(64 * MT_WG_WAVES, 8 / MT_WG_WAVES) void match_batch_kernel(const SiftPointD *recs1,
                                                                                         const float *recs2,
                                                                                         const int *__restrict__ hdr,
                                                                                         const PairPlan *__restrict__ plan,
                                                                                         int npairs, int exact_top2,
+                                                                                        int max_pts, SiftPointD *out,
+                                                                                        unsigned long long *keys,
+                                                                                        int *num_matched,
                                                                                         float *__restrict__ partial)
 {
   __shared__ float Bs[2][MT_SUPER * MT_BSTRIDE];
@@ -553,20 +572,20 @@ __global__ __launch_bounds__(64 * MT_WG_WAVES, 8 / MT_WG_WAVES) void match_batch
   const int nitems = hdr[0], C = hdr[1];
   // consecutive items (the row blocks of one pair) go to the workgroups of one XCD: that pair's set 2 stays in its L2
   for (int it = (int)xcd_remap(blockIdx.x, gridDim.x); it < nitems; it += gridDim.x) {
-    const PairPlan P = plan[pair_find<false>(plan, npairs, it)];
+    const int pi = pair_find<false>(plan, npairs, it);
+    const PairPlan P = plan[pi];
     const int local = it - P.item0, rb = local / P.nchunks, chunk = local - rb * P.nchunks;
     const int st0 = chunk * P.tpc, st1 = min(st0 + P.tpc, P.ntiles);
-    MatchGeom G;
-    G.row_begin = 0; G.row_count = P.n1; G.n1_total = P.n1;
-    G.n2 = P.n2; G.ncols = P.ncols;
-    G.ntiles = P.ntiles; G.nchunks = P.nchunks; G.tiles_per_chunk = P.tpc;
-    G.tile_base = 0; G.hole_begin = 0x7fffffff; G.hole_len = 0;
-    G.chunk_base = 0; G.nchunks_total = P.nchunks;
-    G.stride2 = MISIFT_POINT_BYTES / 4; G.data_off2 = 16; G.xy_off2 = 0;
+    const MatchGeom G = mb_geom(P);
     const SiftPointD *pts1 = recs1 + P.off1;
     const float *set2 = recs2 + (size_t)P.off2 * (MISIFT_POINT_BYTES / 4);
+    unsigned long long *const ck_keys = keys + (size_t)pi * max_pts;
+    const int ck_row0 = rb * MT_ROWS_PER_BLOCK + wave * 32 + 4 * half, ck_last = P.n1 - 1;
     // the sweep of match_kernel (match_sweep.inc): leaves mx / sec / ix
+#define MT_COL_KEYS (MODE == PAIR_OUT_MUTUAL)
 #include "match_sweep.inc"
+#undef MT_COL_KEYS
+    bool matched = false;            // unchunked, no filter: the row's final match is known here, and counted here
     if (C == 1) {
       // the item covers all columns: merge the eight classes here, through the first LDS buffer (free after the sweep)
       float *T = &Bs[0][0];
@@ -593,7 +612,13 @@ __global__ __launch_bounds__(64 * MT_WG_WAVES, 8 / MT_WG_WAVES) void match_batch
           top2_merge(m, sd, ixm, q[0], q[1], __float_as_int(q[2]));
           cmax[c] = m; csec[c] = sd; cidx[c] = ixm;
         }
-        mb_write_row(recs1 + P.off1 + row, set2, exact_top2, cmax, csec, cidx);
+        SiftPointD *o = MODE == PAIR_OUT_INPLACE ? out + P.off1 + row : out + (size_t)pi * max_pts + row;
+        if constexpr (MODE != PAIR_OUT_INPLACE) {
+          o->xpos = pts1[row].xpos;
+          o->ypos = pts1[row].ypos;
+        }
+        mb_write_row(o, set2, exact_top2, cmax, csec, cidx);
+        if constexpr (MODE == PAIR_OUT_INDEXED) matched = o->match >= 0;
       }
     } else if ((lane & 3) == 0) {
       float *pb = partial + (size_t)it * MB_PART_FLOATS;
@@ -609,12 +634,17 @@ __global__ __launch_bounds__(64 * MT_WG_WAVES, 8 / MT_WG_WAVES) void match_batch
         }
       }
     }
-    __syncthreads();                 // T / Bs are read no more before the next item's first staging store
+    // T / Bs are read no more before the next item's first staging store
+    if constexpr (MODE == PAIR_OUT_INDEXED) {
+      const int n = __syncthreads_count(matched);
+      if (tid == 0 && n > 0 && num_matched) atomicAdd(num_matched + pi, n);
+    } else {
+      __syncthreads();
+    }
   }
 }
 
-// Chunked calls only: a unit is 32 rows of one row block, eight threads per row (one per class) merging that class over
-// the pair's chunks in ascending order, as match_merge_kernel does.
+// In place, chunked calls only: a unit is 32 rows of one row block, eight threads per row.
 __global__ __launch_bounds__(256) void match_batch_merge_kernel(SiftPointD *recs1, const float *recs2,
                                                                 const int *__restrict__ hdr,
                                                                 const PairPlan *__restrict__ plan, int npairs,
@@ -629,168 +659,17 @@ __global__ __launch_bounds__(256) void match_batch_merge_kernel(SiftPointD *recs
     const int rl = (u % (MT_ROWS_PER_BLOCK / 32)) * 32 + (threadIdx.x >> 3), cls = threadIdx.x & 7;
     const int row = rb * MT_ROWS_PER_BLOCK + rl;
     const bool live = row < P.n1;
-    float m = 0.0f, sd = 0.0f;
-    int ixm = -1;
-    if (live) {
-      const float *q = partial + (size_t)(P.item0 + rb * P.nchunks) * MB_PART_FLOATS + (rl * 8 + cls) * 3;
-      for (int ch = 0; ch < P.nchunks; ch++, q += MB_PART_FLOATS) top2_merge(m, sd, ixm, q[0], q[1], __float_as_int(q[2]));
-    }
     float cmax[8], csec[8];
     int cidx[8];
-#pragma unroll
-    for (int c = 0; c < 8; c++) {
-      cmax[c] = __shfl(m, c, 8);
-      csec[c] = __shfl(sd, c, 8);
-      cidx[c] = __shfl(ixm, c, 8);
-    }
+    mb_merge_chunks(live, partial + (size_t)(P.item0 + rb * P.nchunks) * MB_PART_FLOATS + (rl * 8 + cls) * 3, P.nchunks,
+                    cmax, csec, cidx);
     if (live && cls == 0)
       mb_write_row(recs1 + P.off1 + row, recs2 + (size_t)P.off2 * (MISIFT_POINT_BYTES / 4), exact_top2, cmax, csec, cidx);
   }
 }
 
-// host-only test hook (no device needed): the plan misift_match_batch makes for pairs of n1[i] x n2[i] records on a chip
-// of num_cus CUs (pair_plan_host; tiles are 64-column super-tiles)
-extern "C" int misift_test_match_batch_plan(int num_cus, int match_full, int npairs, const int *n1, const int *n2,
-                                            int *plan5, int *nitems, int *chunks, int *partial_items_bound)
-{
-  return pair_plan_host(mb_shape(num_cus, match_full), npairs, n1, n2, plan5, nitems, chunks, partial_items_bound);
-}
-
-// Enqueue the three launches of misift_match_batch on the context stream (common.hpp).
-int launch_match_batch(misift_ctx *ctx, int npairs, const int *h_pairs, void *d_plan, const BatchLayout &set1,
-                       const BatchLayout &set2)
-{
-  if (npairs <= 0) return MISIFT_OK;
-  const PairShape S = mb_shape(ctx->num_cus, ctx->opt.match_full);
-  int rc = misift_ensure_tmp(ctx, (size_t)pair_partial_items(S) * MB_PART_FLOATS * sizeof(float));
-  if (rc) return rc;
-  rc = launch_pair_plan(ctx, "match_batch_plan", S, npairs, h_pairs, set1, set2, d_plan);
-  if (rc) return rc;
-  const int *hdr = reinterpret_cast<const int *>(d_plan);
-  const PairPlan *plan = reinterpret_cast<const PairPlan *>(hdr + PAIR_HDR_INTS);
-  float *partial = reinterpret_cast<float *>(ctx->d_match_tmp);
-  const float *f2 = reinterpret_cast<const float *>(set2.recs);
-  const int grid = S.target;
-  {
-    LaunchScope ls(ctx, "match_batch_mfma");
-    hipLaunchKernelGGL(match_batch_kernel, dim3(grid), dim3(64 * MT_WG_WAVES), 0, ctx->stream, set1.recs, f2, hdr, plan,
-                       npairs, ctx->opt.match_exact_top2, partial);
-    rc = ls.finish();
-    if (rc) return rc;
-  }
-  LaunchScope ls(ctx, "match_batch_merge");
-  hipLaunchKernelGGL(match_batch_merge_kernel, dim3(grid), dim3(256), 0, ctx->stream, set1.recs, f2, hdr, plan, npairs,
-                     ctx->opt.match_exact_top2, partial);
-  return ls.finish();
-}
-
-// ============================================================================ pair-indexed matching (misift_match_pairs_batch)
-// The pairs of misift_match_batch, but every pair writes its own output rows out[i * max_pts + row], so that frames may
-// repeat across pairs, and with `mutual` only the rows that are also their column's reversed match keep their match.
-//   pair_plan_capped_kernel   the plan of match_batch (same PairShape), oversized pairs without work;
-//   (mutual) memset           the column keys of every (pair, column) to 0;
-//   match_pairs_kernel        the sweep of match_batch_kernel (match_sweep.inc); unchunked calls write the seven output
-//                             fields of their rows (and count them without mutual), chunked ones their partials; with
-//                             MUTUAL it maintains the column keys;
-//   match_pairs_final_kernel  per (pair, row): the chunk merge or the row the sweep wrote, the mutual test against the
-//                             key of its match, the final row, d_num_matched and d_out_counts.
-// recs1 / recs2 are read only; they may be the same array.
-__device__ __forceinline__ void mp_no_match(SiftPointD *o)
-{
-  o->score = 0.0f;
-  o->ambiguity = 0.0f;
-  o->match = -1;
-  o->match_xpos = 0.0f;
-  o->match_ypos = 0.0f;
-}
-
-template <bool MUTUAL>
-__global__ __launch_bounds__(64 * MT_WG_WAVES, 8 / MT_WG_WAVES) void match_pairs_kernel(const SiftPointD *recs1,
-                                                                                        const float *recs2,
-                                                                                        const int *__restrict__ hdr,
-                                                                                        const PairPlan *__restrict__ plan,
-                                                                                        int npairs, int exact_top2,
-                                                                                        int max_pts, SiftPointD *out,
-                                                                                        unsigned long long *keys,
-                                                                                        int *num_matched,
-                                                                                        float *__restrict__ partial)
-{
-  __shared__ float Bs[2][MT_SUPER * MT_BSTRIDE];
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int half = lane >> 5, col = lane & 31;
-  const int nitems = hdr[0], C = hdr[1];
-  for (int it = (int)xcd_remap(blockIdx.x, gridDim.x); it < nitems; it += gridDim.x) {
-    const int pi = pair_find<false>(plan, npairs, it);
-    const PairPlan P = plan[pi];
-    const int local = it - P.item0, rb = local / P.nchunks, chunk = local - rb * P.nchunks;
-    const int st0 = chunk * P.tpc, st1 = min(st0 + P.tpc, P.ntiles);
-    MatchGeom G;
-    G.row_begin = 0; G.row_count = P.n1; G.n1_total = P.n1;
-    G.n2 = P.n2; G.ncols = P.ncols;
-    G.ntiles = P.ntiles; G.nchunks = P.nchunks; G.tiles_per_chunk = P.tpc;
-    G.tile_base = 0; G.hole_begin = 0x7fffffff; G.hole_len = 0;
-    G.chunk_base = 0; G.nchunks_total = P.nchunks;
-    G.stride2 = MISIFT_POINT_BYTES / 4; G.data_off2 = 16; G.xy_off2 = 0;
-    const SiftPointD *pts1 = recs1 + P.off1;
-    const float *set2 = recs2 + (size_t)P.off2 * (MISIFT_POINT_BYTES / 4);
-    unsigned long long *const ck_keys = keys + (size_t)pi * max_pts;
-    const int ck_row0 = rb * MT_ROWS_PER_BLOCK + wave * 32 + 4 * half, ck_last = P.n1 - 1;
-#define MT_COL_KEYS MUTUAL
-#include "match_sweep.inc"
-#undef MT_COL_KEYS
-    bool matched = false;            // unchunked, no filter: the row's final match is known here, and counted here
-    if (C == 1) {
-      float *T = &Bs[0][0];
-      if ((lane & 3) == 0) {
-        const int cls = col >> 2;
-#pragma unroll
-        for (int r = 0; r < 16; r++) {
-          float *q = T + ((wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * half) * 8 + cls) * 3;
-          q[0] = mx[r];
-          q[1] = sec[r];
-          q[2] = __int_as_float(ix[r]);
-        }
-      }
-      __syncthreads();
-      const int row = rb * MT_ROWS_PER_BLOCK + tid;
-      if (tid < MT_ROWS_PER_BLOCK && row < P.n1) {
-        float cmax[8], csec[8];
-        int cidx[8];
-#pragma unroll
-        for (int c = 0; c < 8; c++) {
-          const float *q = T + (tid * 8 + c) * 3;
-          float m = 0.0f, sd = 0.0f;
-          int ixm = -1;
-          top2_merge(m, sd, ixm, q[0], q[1], __float_as_int(q[2]));
-          cmax[c] = m; csec[c] = sd; cidx[c] = ixm;
-        }
-        SiftPointD *o = out + (size_t)pi * max_pts + row;
-        o->xpos = pts1[row].xpos;
-        o->ypos = pts1[row].ypos;
-        mb_write_row(o, set2, exact_top2, cmax, csec, cidx);
-        if (!MUTUAL) matched = o->match >= 0;
-      }
-    } else if ((lane & 3) == 0) {
-      float *pb = partial + (size_t)it * MB_PART_FLOATS;
-      const int cls = col >> 2;
-#pragma unroll
-      for (int r = 0; r < 16; r++) {
-        const int rl = wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-        if (rb * MT_ROWS_PER_BLOCK + rl < P.n1) {
-          float *q = pb + (rl * 8 + cls) * 3;
-          q[0] = mx[r];
-          q[1] = sec[r];
-          reinterpret_cast<int *>(q)[2] = ix[r];
-        }
-      }
-    }
-    const int n = __syncthreads_count(matched);
-    if (!MUTUAL && tid == 0 && n > 0 && num_matched) atomicAdd(num_matched + pi, n);
-  }
-}
-
-// A unit is 32 rows of one pair, eight threads per row (one per class, as match_batch_merge_kernel); units of rows at or
-// above n1 and of oversized pairs only write the pair's count.
+// Pair-indexed: a unit is 32 rows of one pair, eight threads per row; units of rows at or above n1 and of oversized
+// pairs only write the pair's count.
 __global__ __launch_bounds__(256) void match_pairs_final_kernel(const SiftPointD *recs1, const float *recs2,
                                                                 const int *__restrict__ hdr,
                                                                 const PairPlan *__restrict__ plan, int npairs,
@@ -821,27 +700,17 @@ __global__ __launch_bounds__(256) void match_pairs_final_kernel(const SiftPointD
       if (lead) {                                                 // no column: a no-match row
         o->xpos = recs1[P.off1 + row].xpos;
         o->ypos = recs1[P.off1 + row].ypos;
-        mp_no_match(o);
+        write_no_match(o);
       }
     } else if (C > 1) {
       const int rb = row / MT_ROWS_PER_BLOCK, rr = row % MT_ROWS_PER_BLOCK;
-      float m = 0.0f, sd = 0.0f;
-      int ixm = -1;
-      if (live) {
-        const float *q = partial + (size_t)(P.item0 + rb * P.nchunks) * MB_PART_FLOATS + (rr * 8 + cls) * 3;
-        for (int ch = 0; ch < P.nchunks; ch++, q += MB_PART_FLOATS) top2_merge(m, sd, ixm, q[0], q[1], __float_as_int(q[2]));
-      }
       float cmax[8], csec[8];
       int cidx[8];
-#pragma unroll
-      for (int c = 0; c < 8; c++) {
-        cmax[c] = __shfl(m, c, 8);
-        csec[c] = __shfl(sd, c, 8);
-        cidx[c] = __shfl(ixm, c, 8);
-      }
+      mb_merge_chunks(live, partial + (size_t)(P.item0 + rb * P.nchunks) * MB_PART_FLOATS + (rr * 8 + cls) * 3, P.nchunks,
+                      cmax, csec, cidx);
       if (lead) mb_combine(exact_top2, cmax, csec, cidx, max_score, sec_score, index);
     } else if (lead) {
-      index = o->match;                                           // the row match_pairs_kernel wrote
+      index = o->match;                                           // the row match_batch_kernel wrote
     }
     // the mutual test: the column's key names its best row (0 cannot occur here: S of this row and its match is > 0)
     const bool reject = mutual && index >= 0 && 0xFFFFFFFFu - (unsigned)keys[(size_t)pi * max_pts + index] != (unsigned)row;
@@ -849,60 +718,60 @@ __global__ __launch_bounds__(256) void match_pairs_final_kernel(const SiftPointD
     if (lead && P.n2 > 0 && C > 1) {
       o->xpos = recs1[P.off1 + row].xpos;
       o->ypos = recs1[P.off1 + row].ypos;
-      if (reject) {
-        mp_no_match(o);
-      } else {
-        o->score = max_score;
-        o->match = index;
-        const float *m2 = set2 + (size_t)(index >= 0 ? index : 0) * (MISIFT_POINT_BYTES / 4);
-        o->match_xpos = index >= 0 ? m2[0] : 0.0f;
-        o->match_ypos = index >= 0 ? m2[1] : 0.0f;
-        o->ambiguity = sec_score / (max_score + 1e-6f);
-      }
+      if (reject) write_no_match(o);
+      else mb_store_row(o, set2, max_score, sec_score, index);
     } else if (reject) {
-      mp_no_match(o);                                             // unchunked: xpos / ypos are the sweep's
+      write_no_match(o);                                          // unchunked: xpos / ypos are the sweep's
     }
     const int n = __syncthreads_count(lead && index >= 0);
     if (num_matched && threadIdx.x == 0 && n > 0) atomicAdd(num_matched + pi, n);
   }
 }
 
-static size_t mp_keys_bytes(int npairs, int max_pts) { return sizeof(unsigned long long) * (size_t)npairs * max_pts; }
+// host-only test hook (no device needed): the plan misift_match_batch makes for pairs of n1[i] x n2[i] records on a chip
+// of num_cus CUs (pair_plan_host; tiles are 64-column super-tiles)
+extern "C" int misift_test_match_batch_plan(int num_cus, int match_full, int npairs, const int *n1, const int *n2,
+                                            int *plan5, int *nitems, int *chunks, int *partial_items_bound)
+{
+  return pair_plan_host(mb_shape(num_cus, match_full), npairs, n1, n2, plan5, nitems, chunks, partial_items_bound);
+}
 
-// Enqueue misift_match_pairs_batch on the context stream (common.hpp): plan, (mutual) key memset, sweep, finalize.
-int launch_match_pairs_batch(misift_ctx *ctx, int npairs, const int *h_pairs, void *d_plan, const BatchLayout &set1,
-                             const BatchLayout &set2, int max_pts, int mutual, void *d_out, int *d_out_counts,
-                             int *d_num_matched)
+// Enqueue misift_match_batch (in place; `rows` unused) or misift_match_pairs_batch on the context stream (common.hpp):
+// plan, (mutual) key memset, sweep, finish.
+int launch_match_batch(misift_ctx *ctx, PairOut mode, int npairs, const int *h_pairs, void *d_plan,
+                       const BatchLayout &set1, const BatchLayout &set2, const PairRows &rows)
 {
   if (npairs <= 0) return MISIFT_OK;
+  const bool inplace = mode == PAIR_OUT_INPLACE;
   const PairShape S = mb_shape(ctx->num_cus, ctx->opt.match_full);
-  const size_t part_bytes = (size_t)pair_partial_items(S) * MB_PART_FLOATS * sizeof(float);
-  const size_t key_bytes = mutual ? mp_keys_bytes(npairs, max_pts) : 0;
-  int rc = misift_ensure_tmp(ctx, part_bytes + key_bytes);
+  unsigned long long *keys;
+  int rc = launch_pair_head(ctx, inplace ? "match_batch_plan" : "match_pairs_plan", S, mode,
+                            (size_t)pair_partial_items(S) * MB_PART_FLOATS * sizeof(float), npairs, h_pairs, set1, set2,
+                            rows, d_plan, &keys);
   if (rc) return rc;
+  const int *hdr = reinterpret_cast<const int *>(d_plan);
+  const PairPlan *plan = reinterpret_cast<const PairPlan *>(hdr + PAIR_HDR_INTS);
   float *partial = reinterpret_cast<float *>(ctx->d_match_tmp);
-  unsigned long long *keys = mutual ? reinterpret_cast<unsigned long long *>((char *)ctx->d_match_tmp + part_bytes) : nullptr;
-  int *hdr = reinterpret_cast<int *>(d_plan);
-  PairPlan *plan = reinterpret_cast<PairPlan *>(hdr + PAIR_HDR_INTS);
-  rc = launch_pair_plan_capped(ctx, "match_pairs_plan", S, npairs, h_pairs, set1, set2, max_pts, d_num_matched, d_plan);
-  if (rc) return rc;
-  if (mutual) HIP_TRY(hipMemsetAsync(keys, 0, key_bytes, ctx->stream));
   const float *f2 = reinterpret_cast<const float *>(set2.recs);
-  SiftPointD *out = reinterpret_cast<SiftPointD *>(d_out);
+  SiftPointD *out = inplace ? set1.recs : reinterpret_cast<SiftPointD *>(rows.out);
   const int grid = S.target;
   {
-    LaunchScope ls(ctx, "match_pairs_mfma");
-    if (mutual)
-      hipLaunchKernelGGL(match_pairs_kernel<true>, dim3(grid), dim3(64 * MT_WG_WAVES), 0, ctx->stream, set1.recs, f2,
-                         hdr, plan, npairs, ctx->opt.match_exact_top2, max_pts, out, keys, d_num_matched, partial);
-    else
-      hipLaunchKernelGGL(match_pairs_kernel<false>, dim3(grid), dim3(64 * MT_WG_WAVES), 0, ctx->stream, set1.recs, f2,
-                         hdr, plan, npairs, ctx->opt.match_exact_top2, max_pts, out, keys, d_num_matched, partial);
+    LaunchScope ls(ctx, inplace ? "match_batch_mfma" : "match_pairs_mfma");
+    const auto sweep = inplace                    ? match_batch_kernel<PAIR_OUT_INPLACE>
+                       : mode == PAIR_OUT_MUTUAL ? match_batch_kernel<PAIR_OUT_MUTUAL>
+                                                 : match_batch_kernel<PAIR_OUT_INDEXED>;
+    hipLaunchKernelGGL(sweep, dim3(grid), dim3(64 * MT_WG_WAVES), 0, ctx->stream, set1.recs, f2, hdr, plan, npairs,
+                       ctx->opt.match_exact_top2, rows.max_pts, out, keys, rows.num_matched, partial);
     rc = ls.finish();
     if (rc) return rc;
   }
-  LaunchScope ls(ctx, "match_pairs_final");
-  hipLaunchKernelGGL(match_pairs_final_kernel, dim3(grid), dim3(256), 0, ctx->stream, set1.recs, f2, hdr, plan, npairs,
-                     ctx->opt.match_exact_top2, max_pts, mutual, out, d_out_counts, d_num_matched, keys, partial);
+  LaunchScope ls(ctx, inplace ? "match_batch_merge" : "match_pairs_final");
+  if (inplace)
+    hipLaunchKernelGGL(match_batch_merge_kernel, dim3(grid), dim3(256), 0, ctx->stream, out, f2, hdr, plan, npairs,
+                       ctx->opt.match_exact_top2, partial);
+  else
+    hipLaunchKernelGGL(match_pairs_final_kernel, dim3(grid), dim3(256), 0, ctx->stream, set1.recs, f2, hdr, plan, npairs,
+                       ctx->opt.match_exact_top2, rows.max_pts, (int)(mode == PAIR_OUT_MUTUAL), out, rows.out_counts,
+                       rows.num_matched, keys, partial);
   return ls.finish();
 }

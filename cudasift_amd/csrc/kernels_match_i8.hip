@@ -4,8 +4,9 @@
 // quantize_i8_kernel   one launch: q[r] = quantize_i8(data of record r) (quantize_i8.hpp), 128 bytes at d_q + 128 r, for
 //                      every record of every frame; eight lanes per record, 16 bytes each.
 // pair_plan_kernel     the work list of misift_match_batch (pair_plan.hpp), here with 128-row blocks and 32-column tiles
-//                      and every column taking part.
-// match_i8_kernel      persistent grid, two waves per workgroup, 64 rows per wave (128-row blocks).  A wave keeps its
+//                      and every column taking part; pair-indexed calls run pair_plan_capped_kernel (oversized pairs get
+//                      no work), and mutual ones then set the column keys of every (pair, column) to 0.
+// match_i8_kernel<MODE> persistent grid, two waves per workgroup, 64 rows per wave (128-row blocks).  A wave keeps its
 //                      rows' q in VGPRs (two 32-row A tiles x 128 bytes) and sweeps 32-column tiles of set 2, loaded
 //                      straight from global memory one tile ahead: per tile 2 x 4 v_mfma_i32_32x32x32_i8 give the exact
 //                      int32 scores of 64 rows x 32 columns.  Each lane keeps, per row register, the top two of the packed
@@ -15,11 +16,16 @@
 //                      >= 2^30 + 512, and for equal S the earlier tile (the smaller column of that lane) is the larger key.
 //                      At the end of a window the lanes' keys go through LDS to one lane per row, which decodes them into
 //                      (score, frame-local column) and merges them under "score descending, column ascending".
-//                      With one column chunk per row block the wave writes its rows; otherwise it stores (best, index,
-//                      second) per row and chunk, and
-// match_i8_merge_kernel merges them over the chunks (it returns at once when nothing was chunked).
+//                      With one column chunk per row block the wave writes its rows: in place the five match fields of
+//                      set 1 (PairOut, common.hpp), pair-indexed the seven output fields of out[i * max_pts + row], so
+//                      that frames may repeat across pairs (counted unless mutual).  Otherwise it stores (best, index,
+//                      second) per row and chunk.  Mutual: it maintains the column keys (i8_colkey_tile).
+// match_i8_merge_kernel in place: merges them over the chunks (it returns at once when nothing was chunked).
+// match_pairs_i8_final_kernel  pair-indexed, per (pair, row): the chunk merge or the row the sweep wrote, the mutual test
+//                      against the key of its match (only the rows that are also their column's best row keep their
+//                      match), the final row, d_num_matched and d_out_counts.
 // Columns are cut into chunks only when the row blocks of the call do not fill I8_TARGET_ROUNDS rounds of the grid.
-// The tile loop is match_i8_sweep.inc; the pair-indexed kernels that share it are described further down.
+// The tile loop is match_i8_sweep.inc.
 //
 // The A and B fragments of the i8 MFMA are loaded by the same code (lane l: row / column l & 31, bytes 64 (l >> 5) + 16 s
 // of k-step s), so the sum over k is right whatever order the hardware pairs the bytes of one k-step in; integer sums do
@@ -43,27 +49,18 @@ constexpr unsigned I8_VALID = I8_OFF + 512u;     // smallest key with S >= 1
 constexpr int I8_WG_PER_CU = 4;                  // workgroups per CU of the persistent grid (8 waves)
 constexpr int I8_TARGET_ROUNDS = 4;              // items a call is cut into when its row blocks are few, in grid rounds
 
+// recs1 / recs2 and q1 / q2 are read only; each pair may be the same array.  In place, `out` is recs1 again: the rows
+// written are the five match fields of set-1 rows, which the kernels do not read.
 struct I8Args {
-  SiftPointD *recs1;
-  const SiftPointD *recs2;
-  const int8_t *q1, *q2;
-  const int *hdr;
-  const PairPlan *plan;
-  int npairs;
-  int4 *partial;                 // items x I8_ROWS x (best, index, second, 0), chunked calls only
-};
-
-// misift_match_pairs_batch_i8: set 1 is read only, the rows go to out + pair * max_pts
-struct I8PairsArgs {
   const SiftPointD *recs1, *recs2;
   const int8_t *q1, *q2;
   const int *hdr;
   const PairPlan *plan;
-  int npairs, max_pts;
-  SiftPointD *out;
+  int npairs, max_pts;           // max_pts: pair-indexed calls only, as keys and num_matched
+  SiftPointD *out;               // in place: set 1; pair-indexed: the rows of pair i at out + i * max_pts
   unsigned long long *keys;      // npairs x max_pts column keys, mutual calls only
   int *num_matched;              // may be NULL
-  int4 *partial;                 // as I8Args
+  int4 *partial;                 // items x I8_ROWS x (best, index, second, 0), chunked calls only
 };
 
 __host__ __device__ __forceinline__ int i8_grid(int ncu) { return I8_WG_PER_CU * (ncu > 0 ? ncu : 256); }
@@ -93,13 +90,24 @@ __device__ __forceinline__ void i8_write_row(SiftPointD *o, const SiftPointD *se
   o->ambiguity = ((float)s * 0x1p-16f) / (score + 1e-6f);
 }
 
-__device__ __forceinline__ void i8_no_match(SiftPointD *o)
+// wave-uniform: keep the loop bounds and the key constant in SGPRs
+__device__ __forceinline__ void i8_uniform(PairPlan &P)
 {
-  o->score = 0.0f;
-  o->ambiguity = 0.0f;
-  o->match = -1;
-  o->match_xpos = 0.0f;
-  o->match_ypos = 0.0f;
+  P.n1 = __builtin_amdgcn_readfirstlane(P.n1); P.n2 = __builtin_amdgcn_readfirstlane(P.n2);
+  P.off1 = __builtin_amdgcn_readfirstlane(P.off1); P.off2 = __builtin_amdgcn_readfirstlane(P.off2);
+  P.ntiles = __builtin_amdgcn_readfirstlane(P.ntiles); P.nchunks = __builtin_amdgcn_readfirstlane(P.nchunks);
+  P.tpc = __builtin_amdgcn_readfirstlane(P.tpc); P.item0 = __builtin_amdgcn_readfirstlane(P.item0);
+}
+
+// row rr of row block rb of the pair merged over the pair's chunks, in ascending order
+__device__ __forceinline__ void i8_merge_chunks(const int4 *partial, const PairPlan &P, int rb, int rr, int &M, int &I,
+                                                int &S2)
+{
+  const int4 *q = partial + (size_t)(P.item0 + rb * P.nchunks) * I8_ROWS + rr;
+  for (int ch = 0; ch < P.nchunks; ch++, q += I8_ROWS) {
+    const int4 v = *q;
+    i8_take(M, I, S2, v.x, v.y, v.z);
+  }
 }
 
 // Column keys of misift_match_pairs_batch_i8's mutual check (the design of colkey_* in kernels_match.hip on integer
@@ -157,8 +165,7 @@ __global__ __launch_bounds__(256) void quantize_i8_kernel(BatchLayout set, int n
   }
 }
 
-// recs1 / recs2 may be the same array, and q1 / q2 too: the kernel reads q and set 2's xpos / ypos, and writes only the
-// five match fields of set-1 rows.
+template <int MODE>
 __global__ __launch_bounds__(64 * I8_WAVES) void match_i8_kernel(I8Args A)
 {
   __shared__ uint2 red[I8_WAVES][32][64];        // per wave: (b1, b2) of row register rr of lane l at [rr][l]
@@ -168,27 +175,41 @@ __global__ __launch_bounds__(64 * I8_WAVES) void match_i8_kernel(I8Args A)
   // the row this lane owns in the fold and the output: row register c & 15 of A tile c >> 4, lane half h
   const int own = 32 * (c >> 4) + (c & 3) + 8 * ((c & 15) >> 2) + 4 * h;
   for (int it = (int)xcd_remap(blockIdx.x, gridDim.x); it < nitems; it += gridDim.x) {
-    PairPlan P = A.plan[pair_find<false>(A.plan, A.npairs, it)];
-    // wave-uniform: keep the loop bounds and the key constant in SGPRs
-    P.n1 = __builtin_amdgcn_readfirstlane(P.n1); P.n2 = __builtin_amdgcn_readfirstlane(P.n2);
-    P.off1 = __builtin_amdgcn_readfirstlane(P.off1); P.off2 = __builtin_amdgcn_readfirstlane(P.off2);
-    P.ntiles = __builtin_amdgcn_readfirstlane(P.ntiles); P.nchunks = __builtin_amdgcn_readfirstlane(P.nchunks);
-    P.tpc = __builtin_amdgcn_readfirstlane(P.tpc); P.item0 = __builtin_amdgcn_readfirstlane(P.item0);
+    const int pi = __builtin_amdgcn_readfirstlane(pair_find<false>(A.plan, A.npairs, it));
+    PairPlan P = A.plan[pi];
+    i8_uniform(P);
     const int local = it - P.item0, rb = local / P.nchunks, chunk = local - rb * P.nchunks;
     const int t0 = chunk * P.tpc, t1 = min(t0 + P.tpc, P.ntiles);
     const int row0 = rb * I8_ROWS + wave * 64;
-#define I8_COL_KEYS(t, acc0, acc1)
+    unsigned long long *const ck_keys = A.keys + (size_t)pi * A.max_pts;
+#define I8_COL_KEYS(t, acc0, acc1) \
+  if constexpr (MODE == PAIR_OUT_MUTUAL) i8_colkey_tile(ck_keys + (size_t)(t) * I8_TILE + c, acc0, acc1, row0, h)
 #include "match_i8_sweep.inc"
 #undef I8_COL_KEYS
     const int row = row0 + own;
+    bool matched = false;            // unchunked, no filter: the row's final match is known here, and counted here
     if (row < P.n1) {
-      if (C == 1) i8_write_row(A.recs1 + P.off1 + row, A.recs2 + P.off2, M, I, S2);
-      else A.partial[(size_t)it * I8_ROWS + wave * 64 + own] = make_int4(M, I, S2, 0);
+      if (C == 1) {
+        SiftPointD *o = MODE == PAIR_OUT_INPLACE ? A.out + P.off1 + row : A.out + (size_t)pi * A.max_pts + row;
+        if constexpr (MODE != PAIR_OUT_INPLACE) {
+          o->xpos = A.recs1[P.off1 + row].xpos;
+          o->ypos = A.recs1[P.off1 + row].ypos;
+        }
+        i8_write_row(o, A.recs2 + P.off2, M, I, S2);
+        matched = MODE == PAIR_OUT_INDEXED && I >= 0;
+      } else {
+        A.partial[(size_t)it * I8_ROWS + wave * 64 + own] = make_int4(M, I, S2, 0);
+      }
     }
+    if constexpr (MODE == PAIR_OUT_INDEXED)
+      if (C == 1 && A.num_matched) {
+        const int n = __popcll(__ballot(matched));
+        if (lane == 0 && n > 0) atomicAdd(A.num_matched + pi, n);
+      }
   }
 }
 
-// Chunked calls only: one thread per row of a row block merges the row over the pair's chunks.
+// In place, chunked calls only: one thread per row of a row block merges the row over the pair's chunks.
 __global__ __launch_bounds__(I8_ROWS) void match_i8_merge_kernel(I8Args A)
 {
   if (A.hdr[1] <= 1) return;
@@ -198,73 +219,14 @@ __global__ __launch_bounds__(I8_ROWS) void match_i8_merge_kernel(I8Args A)
     const int rb = g - P.rb0, row = rb * I8_ROWS + threadIdx.x;
     if (row >= P.n1) continue;
     int M = 0, I = -1, S2 = 0;
-    const int4 *q = A.partial + (size_t)(P.item0 + rb * P.nchunks) * I8_ROWS + threadIdx.x;
-    for (int ch = 0; ch < P.nchunks; ch++, q += I8_ROWS) {
-      const int4 v = *q;
-      i8_take(M, I, S2, v.x, v.y, v.z);
-    }
-    i8_write_row(A.recs1 + P.off1 + row, A.recs2 + P.off2, M, I, S2);
+    i8_merge_chunks(A.partial, P, rb, threadIdx.x, M, I, S2);
+    i8_write_row(A.out + P.off1 + row, A.recs2 + P.off2, M, I, S2);
   }
 }
 
-// ================================================================ pair-indexed matching (misift_match_pairs_batch_i8)
-// The pairs of misift_match_batch_i8, but every pair writes its own output rows out[i * max_pts + row], so that frames
-// may repeat across pairs, and with `mutual` only the rows that are also their column's best row keep their match.
-//   pair_plan_capped_kernel       the plan of match_i8 (same PairShape), oversized pairs without work (pair_plan.hpp);
-//   (mutual) memset               the column keys of every (pair, column) to 0;
-//   match_pairs_i8_kernel         the sweep of match_i8_kernel (match_i8_sweep.inc); unchunked calls write the seven
-//                                 output fields of their rows (and count them without mutual), chunked ones their
-//                                 partials; with MUTUAL it maintains the column keys (i8_colkey_tile);
-//   match_pairs_i8_final_kernel   per (pair, row): the chunk merge or the row the sweep wrote, the mutual test against
-//                                 the key of its match, the final row, d_num_matched and d_out_counts.
-// recs1 / recs2 and q1 / q2 are read only; each pair may be the same array.
-template <bool MUTUAL>
-__global__ __launch_bounds__(64 * I8_WAVES) void match_pairs_i8_kernel(I8PairsArgs A)
-{
-  __shared__ uint2 red[I8_WAVES][32][64];
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int c = lane & 31, h = lane >> 5;
-  const int nitems = A.hdr[0], C = A.hdr[1];
-  const int own = 32 * (c >> 4) + (c & 3) + 8 * ((c & 15) >> 2) + 4 * h;
-  for (int it = (int)xcd_remap(blockIdx.x, gridDim.x); it < nitems; it += gridDim.x) {
-    const int pi = __builtin_amdgcn_readfirstlane(pair_find<false>(A.plan, A.npairs, it));
-    PairPlan P = A.plan[pi];
-    P.n1 = __builtin_amdgcn_readfirstlane(P.n1); P.n2 = __builtin_amdgcn_readfirstlane(P.n2);
-    P.off1 = __builtin_amdgcn_readfirstlane(P.off1); P.off2 = __builtin_amdgcn_readfirstlane(P.off2);
-    P.ntiles = __builtin_amdgcn_readfirstlane(P.ntiles); P.nchunks = __builtin_amdgcn_readfirstlane(P.nchunks);
-    P.tpc = __builtin_amdgcn_readfirstlane(P.tpc); P.item0 = __builtin_amdgcn_readfirstlane(P.item0);
-    const int local = it - P.item0, rb = local / P.nchunks, chunk = local - rb * P.nchunks;
-    const int t0 = chunk * P.tpc, t1 = min(t0 + P.tpc, P.ntiles);
-    const int row0 = rb * I8_ROWS + wave * 64;
-    unsigned long long *const ck_keys = A.keys + (size_t)pi * A.max_pts;
-#define I8_COL_KEYS(t, acc0, acc1) \
-  if constexpr (MUTUAL) i8_colkey_tile(ck_keys + (size_t)(t) * I8_TILE + c, acc0, acc1, row0, h)
-#include "match_i8_sweep.inc"
-#undef I8_COL_KEYS
-    const int row = row0 + own;
-    bool matched = false;            // unchunked, no filter: the row's final match is known here, and counted here
-    if (row < P.n1) {
-      if (C == 1) {
-        SiftPointD *o = A.out + (size_t)pi * A.max_pts + row;
-        o->xpos = A.recs1[P.off1 + row].xpos;
-        o->ypos = A.recs1[P.off1 + row].ypos;
-        i8_write_row(o, A.recs2 + P.off2, M, I, S2);
-        matched = !MUTUAL && I >= 0;
-      } else {
-        A.partial[(size_t)it * I8_ROWS + wave * 64 + own] = make_int4(M, I, S2, 0);
-      }
-    }
-    if (!MUTUAL && C == 1 && A.num_matched) {
-      const int n = __popcll(__ballot(matched));
-      if (lane == 0 && n > 0) atomicAdd(A.num_matched + pi, n);
-    }
-  }
-}
-
-// A unit is 256 rows of one pair, one thread per row; units of rows at or above n1 and of oversized pairs only write the
-// pair's count.
-__global__ __launch_bounds__(256) void match_pairs_i8_final_kernel(I8PairsArgs A, int mutual,
-                                                                   int *__restrict__ out_counts)
+// Pair-indexed: a unit is 256 rows of one pair, one thread per row; units of rows at or above n1 and of oversized pairs
+// only write the pair's count.
+__global__ __launch_bounds__(256) void match_pairs_i8_final_kernel(I8Args A, int mutual, int *__restrict__ out_counts)
 {
   const int C = A.hdr[1];
   const int groups = (A.max_pts + 255) / 256;
@@ -282,29 +244,21 @@ __global__ __launch_bounds__(256) void match_pairs_i8_final_kernel(I8PairsArgs A
       if (P.n2 == 0) {                                            // no column: a no-match row
         o->xpos = A.recs1[P.off1 + row].xpos;
         o->ypos = A.recs1[P.off1 + row].ypos;
-        i8_no_match(o);
+        write_no_match(o);
       } else {
         int M = 0, I = -1, S2 = 0;
-        if (C > 1) {
-          const int rb = row / I8_ROWS, rr = row % I8_ROWS;
-          const int4 *q = A.partial + (size_t)(P.item0 + rb * P.nchunks) * I8_ROWS + rr;
-          for (int ch = 0; ch < P.nchunks; ch++, q += I8_ROWS) {
-            const int4 v = *q;
-            i8_take(M, I, S2, v.x, v.y, v.z);
-          }
-        } else {
-          I = o->match;                                           // the row match_pairs_i8_kernel wrote
-        }
+        if (C > 1) i8_merge_chunks(A.partial, P, row / I8_ROWS, row % I8_ROWS, M, I, S2);
+        else I = o->match;                                        // the row match_i8_kernel wrote
         // the mutual test: the column's key names its best row (0 cannot occur here: S of this row and its match is > 0)
         const bool reject =
             mutual && I >= 0 && 0xFFFFFFFFu - (unsigned)A.keys[(size_t)pi * A.max_pts + I] != (unsigned)row;
         if (C > 1) {
           o->xpos = A.recs1[P.off1 + row].xpos;
           o->ypos = A.recs1[P.off1 + row].ypos;
-          if (reject) i8_no_match(o);
+          if (reject) write_no_match(o);
           else i8_write_row(o, A.recs2 + P.off2, M, I, S2);
         } else if (reject) {
-          i8_no_match(o);                                         // unchunked: xpos / ypos are the sweep's
+          write_no_match(o);                                      // unchunked: xpos / ypos are the sweep's
         }
         matched = I >= 0 && !reject;
       }
@@ -343,66 +297,41 @@ int launch_quantize_batch(misift_ctx *ctx, const BatchLayout &set, int nframes, 
   return ls.finish();
 }
 
-int launch_match_batch_i8(misift_ctx *ctx, int npairs, const int *h_pairs, void *d_plan, const BatchLayout &set1,
-                          const int8_t *q1, const BatchLayout &set2, const int8_t *q2)
+// Enqueue misift_match_batch_i8 (in place; `rows` unused) or misift_match_pairs_batch_i8 on the context stream
+// (common.hpp): plan, (mutual) key memset, sweep, finish.
+int launch_match_batch_i8(misift_ctx *ctx, PairOut mode, int npairs, const int *h_pairs, void *d_plan,
+                          const BatchLayout &set1, const int8_t *q1, const BatchLayout &set2, const int8_t *q2,
+                          const PairRows &rows)
 {
   if (npairs <= 0) return MISIFT_OK;
+  const bool inplace = mode == PAIR_OUT_INPLACE;
   const PairShape S = i8_shape(ctx->num_cus);
-  int rc = misift_ensure_tmp(ctx, (size_t)pair_partial_items(S) * I8_ROWS * sizeof(int4));
-  if (rc) return rc;
-  rc = launch_pair_plan(ctx, "match_i8_plan", S, npairs, h_pairs, set1, set2, d_plan);
-  if (rc) return rc;
   I8Args A;
+  int rc = launch_pair_head(ctx, inplace ? "match_i8_plan" : "match_pairs_i8_plan", S, mode,
+                            (size_t)pair_partial_items(S) * I8_ROWS * sizeof(int4), npairs, h_pairs, set1, set2, rows,
+                            d_plan, &A.keys);
+  if (rc) return rc;
   A.recs1 = set1.recs; A.recs2 = set2.recs; A.q1 = q1; A.q2 = q2;
   A.hdr = reinterpret_cast<const int *>(d_plan);
   A.plan = reinterpret_cast<const PairPlan *>(A.hdr + PAIR_HDR_INTS);
-  A.npairs = npairs;
+  A.npairs = npairs; A.max_pts = rows.max_pts;
+  A.out = inplace ? set1.recs : reinterpret_cast<SiftPointD *>(rows.out);
+  A.num_matched = rows.num_matched;
   A.partial = reinterpret_cast<int4 *>(ctx->d_match_tmp);
   const int grid = i8_grid(ctx->num_cus);
   {
-    LaunchScope ls(ctx, "match_i8_mfma");
-    hipLaunchKernelGGL(match_i8_kernel, dim3(grid), dim3(64 * I8_WAVES), 0, ctx->stream, A);
+    LaunchScope ls(ctx, inplace ? "match_i8_mfma" : "match_pairs_i8_mfma");
+    const auto sweep = inplace                    ? match_i8_kernel<PAIR_OUT_INPLACE>
+                       : mode == PAIR_OUT_MUTUAL ? match_i8_kernel<PAIR_OUT_MUTUAL>
+                                                 : match_i8_kernel<PAIR_OUT_INDEXED>;
+    hipLaunchKernelGGL(sweep, dim3(grid), dim3(64 * I8_WAVES), 0, ctx->stream, A);
     rc = ls.finish();
     if (rc) return rc;
   }
-  LaunchScope ls(ctx, "match_i8_merge");
-  hipLaunchKernelGGL(match_i8_merge_kernel, dim3(grid), dim3(I8_ROWS), 0, ctx->stream, A);
-  return ls.finish();
-}
-
-// Enqueue misift_match_pairs_batch_i8 on the context stream (common.hpp): plan, (mutual) key memset, sweep, finalize.
-int launch_match_pairs_batch_i8(misift_ctx *ctx, int npairs, const int *h_pairs, void *d_plan, const BatchLayout &set1,
-                                const int8_t *q1, const BatchLayout &set2, const int8_t *q2, int max_pts, int mutual,
-                                void *d_out, int *d_out_counts, int *d_num_matched)
-{
-  if (npairs <= 0) return MISIFT_OK;
-  const PairShape S = i8_shape(ctx->num_cus);
-  const size_t part_bytes = (size_t)pair_partial_items(S) * I8_ROWS * sizeof(int4);
-  const size_t key_bytes = mutual ? sizeof(unsigned long long) * (size_t)npairs * max_pts : 0;
-  int rc = misift_ensure_tmp(ctx, part_bytes + key_bytes);
-  if (rc) return rc;
-  rc = launch_pair_plan_capped(ctx, "match_pairs_i8_plan", S, npairs, h_pairs, set1, set2, max_pts, d_num_matched,
-                               d_plan);
-  if (rc) return rc;
-  I8PairsArgs A;
-  A.recs1 = set1.recs; A.recs2 = set2.recs; A.q1 = q1; A.q2 = q2;
-  A.hdr = reinterpret_cast<const int *>(d_plan);
-  A.plan = reinterpret_cast<const PairPlan *>(A.hdr + PAIR_HDR_INTS);
-  A.npairs = npairs; A.max_pts = max_pts;
-  A.out = reinterpret_cast<SiftPointD *>(d_out);
-  A.keys = mutual ? reinterpret_cast<unsigned long long *>((char *)ctx->d_match_tmp + part_bytes) : nullptr;
-  A.num_matched = d_num_matched;
-  A.partial = reinterpret_cast<int4 *>(ctx->d_match_tmp);
-  if (mutual) HIP_TRY(hipMemsetAsync(A.keys, 0, key_bytes, ctx->stream));
-  const int grid = i8_grid(ctx->num_cus);
-  {
-    LaunchScope ls(ctx, "match_pairs_i8_mfma");
-    if (mutual) hipLaunchKernelGGL(match_pairs_i8_kernel<true>, dim3(grid), dim3(64 * I8_WAVES), 0, ctx->stream, A);
-    else hipLaunchKernelGGL(match_pairs_i8_kernel<false>, dim3(grid), dim3(64 * I8_WAVES), 0, ctx->stream, A);
-    rc = ls.finish();
-    if (rc) return rc;
-  }
-  LaunchScope ls(ctx, "match_pairs_i8_final");
-  hipLaunchKernelGGL(match_pairs_i8_final_kernel, dim3(grid), dim3(256), 0, ctx->stream, A, mutual, d_out_counts);
+  LaunchScope ls(ctx, inplace ? "match_i8_merge" : "match_pairs_i8_final");
+  if (inplace) hipLaunchKernelGGL(match_i8_merge_kernel, dim3(grid), dim3(I8_ROWS), 0, ctx->stream, A);
+  else
+    hipLaunchKernelGGL(match_pairs_i8_final_kernel, dim3(grid), dim3(256), 0, ctx->stream, A,
+                       (int)(mode == PAIR_OUT_MUTUAL), rows.out_counts);
   return ls.finish();
 }

@@ -1,6 +1,5 @@
-// match_i8_sweep.inc — the tile loop of the int8 matchers (kernels_match_i8.hip), included into match_i8_kernel and
-// match_pairs_i8_kernel.  Textual, as match_sweep.inc, so that match_i8_kernel keeps its instruction stream whatever the
-// pair-indexed kernel adds.
+// match_i8_sweep.inc — the tile loop of the int8 matchers (kernels_match_i8.hip), included into match_i8_kernel<MODE>.
+// Textual, as match_sweep.inc: the loop keeps its instruction stream whatever the kernel around it adds.
 //
 // Expects in scope: A (q1, q2), P (the pair's plan, wave-uniform), wave, lane, c, h, row0 (the wave's first row), t0 / t1
 // (the item's tiles) and red.  Leaves (M, I, S2) = (best score, frame-local column, second score) of the row the lane

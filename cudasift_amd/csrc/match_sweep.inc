@@ -1,5 +1,6 @@
 // match_sweep.inc — the column sweep of one matcher workgroup, included into the body of match_kernel (misift_match,
-// misift_match_rows, the sharded matcher) and of match_batch_kernel (misift_match_batch) in kernels_match.hip.
+// misift_match_rows, the sharded matcher) and of match_batch_kernel<MODE> (misift_match_batch, misift_match_pairs_batch)
+// in kernels_match.hip.
 //
 // Textual rather than an inline function: the sweep as a __forceinline__ function compiled into a different instruction
 // stream and register allocation of match_kernel (251 -> 256 VGPRs), and match_kernel's code is measured and must not move.
@@ -9,11 +10,12 @@
 // Bs[2][MT_SUPER * MT_BSTRIDE] (LDS).  Leaves in scope mx[16], sec[16], ix[16]: per lane (4c + j, half) and accumulator
 // row r, the exact top-2 of class c over the swept columns.  Bs is not read any more after the last barrier of the sweep.
 //
-// Column keys (match_pairs_kernel only: MT_COL_KEYS defined, as a constant expression that enables them): for every swept
+// Column keys (match_batch_kernel only: MT_COL_KEYS defined, as a constant expression that enables them in its mutual
+// mode — where it is false nothing of them is compiled): for every swept
 // column c < G.ncols, one vector global_atomic_max_u64 per wavefront of colkey(best score of the wavefront's 32 rows,
 // its smallest row) into ck_keys[c] (kernels_match.hip: colkey_step / colkey_flush).  Expects ck_keys, ck_row0 (the
 // row of accumulator register 0 of this lane: rb * 128 + wave * 32 + 4 * half) and ck_last (n1 - 1) in scope.  Where
-// MT_COL_KEYS is not defined the sweep is the one match_kernel and match_batch_kernel compile.
+// MT_COL_KEYS is not defined the sweep is the one match_kernel compiles.
   // ---- A fragment: row (lane&31) of this wave, k = 2t + half, t = 0..63
   const int row_local = rb * MT_ROWS_PER_BLOCK + wave * 32 + col;          // within [0,row_count)
   const int row_ld = G.row_begin + min(row_local, G.row_count - 1);

@@ -2140,25 +2140,51 @@ static int run_batch(misift_ctx *ctx, std::initializer_list<HostList> lists, siz
   return rc;
 }
 
+// The four pair matchers share everything but the checks that are an entry point's own.  One side of a call:
+struct PairSide {
+  const void *recs;
+  int nframes;
+  const int *counts, *offsets;
+  int stride;
+};
+// own_failed: NULL, or the text of the entry point's own check that failed; it is reported in its place, behind the
+// common NULL and range checks.  Then the layouts, the frames of the pairs (a frame of set 1 in at most one pair unless
+// `repeats`), and launch(h_pairs, d_plan, set1, set2) through run_batch with the pairs' device plan.
+#define OWN_CHECK(cond) ((cond) ? nullptr : #cond)
+template <class Launch>
+static int pair_match_call(const char *who, misift_ctx *ctx, int npairs, const int *pairs, const PairSide &s1,
+                           const PairSide &s2, const char *own_failed, bool repeats, Launch launch)
+{
+  ARG_CHECK_IN(who, ctx && npairs >= 0);
+  if (npairs == 0) return MISIFT_OK;
+  ARG_CHECK_IN(who, pairs && s1.recs && s2.recs && s1.counts && s2.counts && s1.nframes > 0 && s2.nframes > 0);
+  if (own_failed) {
+    misift_set_error("%s: invalid argument: %s", who, own_failed);
+    return MISIFT_EINVAL;
+  }
+  BatchLayout set1, set2;
+  int rc = batch_layout(who, s1.recs, s1.counts, s1.offsets, s1.stride, &set1);
+  if (!rc) rc = batch_layout(who, s2.recs, s2.counts, s2.offsets, s2.stride, &set2);
+  if (!rc) rc = check_frames(who, npairs, pairs, 2, s1.nframes, s2.nframes, repeats);
+  if (rc) return rc;
+  RoctxRange range(who);
+  return run_batch(ctx, {{pairs, sizeof(int) * 2 * (size_t)npairs}}, pair_plan_bytes(npairs),
+                   [&](int *h_pairs, void *d_plan) { return launch(h_pairs, d_plan, set1, set2); });
+}
+
 // Many (frame of set 1, frame of set 2) pairs of device-resident batches in one stream-ordered call: no host wait and no
 // host read of the counts.
 extern "C" int misift_match_batch(misift_ctx *ctx, int npairs, const int *pairs, void *d_recs1, int nframes1,
                                   const int *d_counts1, const int *d_offsets1, int stride1, const void *d_recs2,
                                   int nframes2, const int *d_counts2, const int *d_offsets2, int stride2)
 {
-  ARG_CHECK(ctx && npairs >= 0);
-  if (npairs == 0) return MISIFT_OK;
-  ARG_CHECK(pairs && d_recs1 && d_recs2 && d_counts1 && d_counts2 && nframes1 > 0 && nframes2 > 0);
-  BatchLayout set1, set2;
-  int rc = batch_layout(__func__, d_recs1, d_counts1, d_offsets1, stride1, &set1);
-  if (!rc) rc = batch_layout(__func__, d_recs2, d_counts2, d_offsets2, stride2, &set2);
-  if (!rc) rc = check_frames(__func__, npairs, pairs, 2, nframes1, nframes2);
-  if (rc) return rc;
-  RoctxRange range(__func__);
-  return run_batch(ctx, {{pairs, sizeof(int) * 2 * (size_t)npairs}}, pair_plan_bytes(npairs),
-                   [&](int *h_pairs, void *d_plan) {
-                     return launch_match_batch(ctx, npairs, h_pairs, d_plan, set1, set2);
-                   });
+  const PairSide s1{d_recs1, nframes1, d_counts1, d_offsets1, stride1};
+  const PairSide s2{d_recs2, nframes2, d_counts2, d_offsets2, stride2};
+  return pair_match_call(__func__, ctx, npairs, pairs, s1, s2, nullptr, false,
+                        [&](int *h_pairs, void *d_plan, const BatchLayout &set1, const BatchLayout &set2) {
+                          return launch_match_batch(ctx, PAIR_OUT_INPLACE, npairs, h_pairs, d_plan, set1, set2,
+                                                    PairRows{});
+                        });
 }
 
 // misift_match_batch into pair-indexed output rows, with an optional mutual-nearest-neighbour check: frames may repeat.
@@ -2168,23 +2194,16 @@ extern "C" int misift_match_pairs_batch(misift_ctx *ctx, int npairs, const int *
                                         int stride2, int max_pts, int mutual, void *d_out, int *d_out_counts,
                                         int *d_num_matched)
 {
-  ARG_CHECK(ctx && npairs >= 0);
-  if (npairs == 0) return MISIFT_OK;
-  ARG_CHECK(pairs && d_recs1 && d_recs2 && d_counts1 && d_counts2 && d_out && d_out_counts && nframes1 > 0 &&
-            nframes2 > 0);
-  ARG_CHECK(max_pts >= 1 && (mutual == 0 || mutual == 1));
-  ARG_CHECK(d_out != d_recs1 && d_out != d_recs2);
-  BatchLayout set1, set2;
-  int rc = batch_layout(__func__, d_recs1, d_counts1, d_offsets1, stride1, &set1);
-  if (!rc) rc = batch_layout(__func__, d_recs2, d_counts2, d_offsets2, stride2, &set2);
-  if (!rc) rc = check_frames(__func__, npairs, pairs, 2, nframes1, nframes2, true);
-  if (rc) return rc;
-  RoctxRange range(__func__);
-  return run_batch(ctx, {{pairs, sizeof(int) * 2 * (size_t)npairs}}, pair_plan_bytes(npairs),
-                   [&](int *h_pairs, void *d_plan) {
-                     return launch_match_pairs_batch(ctx, npairs, h_pairs, d_plan, set1, set2, max_pts, mutual, d_out,
-                                                     d_out_counts, d_num_matched);
-                   });
+  const PairSide s1{d_recs1, nframes1, d_counts1, d_offsets1, stride1};
+  const PairSide s2{d_recs2, nframes2, d_counts2, d_offsets2, stride2};
+  const PairRows rows{max_pts, d_out, d_out_counts, d_num_matched};
+  const char *own = OWN_CHECK(d_out && d_out_counts && max_pts >= 1 && (mutual == 0 || mutual == 1) &&
+                              d_out != d_recs1 && d_out != d_recs2);
+  return pair_match_call(__func__, ctx, npairs, pairs, s1, s2, own, true,
+                        [&](int *h_pairs, void *d_plan, const BatchLayout &set1, const BatchLayout &set2) {
+                          return launch_match_batch(ctx, mutual ? PAIR_OUT_MUTUAL : PAIR_OUT_INDEXED, npairs, h_pairs,
+                                                    d_plan, set1, set2, rows);
+                        });
 }
 
 // Many frames of a device-resident batch through FindHomography / ImproveHomography in one stream-ordered call each: no
@@ -2294,20 +2313,14 @@ extern "C" int misift_match_batch_i8(misift_ctx *ctx, int npairs, const int *pai
                                      const void *d_recs2, const int8_t *d_q2, int nframes2, const int *d_counts2,
                                      const int *d_offsets2, int stride2)
 {
-  ARG_CHECK(ctx && npairs >= 0);
-  if (npairs == 0) return MISIFT_OK;
-  ARG_CHECK(pairs && d_recs1 && d_recs2 && d_q1 && d_q2 && d_counts1 && d_counts2 && nframes1 > 0 && nframes2 > 0);
-  ARG_CHECK(((uintptr_t)d_q1 & 15) == 0 && ((uintptr_t)d_q2 & 15) == 0);
-  BatchLayout set1, set2;
-  int rc = batch_layout(__func__, d_recs1, d_counts1, d_offsets1, stride1, &set1);
-  if (!rc) rc = batch_layout(__func__, d_recs2, d_counts2, d_offsets2, stride2, &set2);
-  if (!rc) rc = check_frames(__func__, npairs, pairs, 2, nframes1, nframes2);
-  if (rc) return rc;
-  RoctxRange range(__func__);
-  return run_batch(ctx, {{pairs, sizeof(int) * 2 * (size_t)npairs}}, pair_plan_bytes(npairs),
-                   [&](int *h_pairs, void *d_plan) {
-                     return launch_match_batch_i8(ctx, npairs, h_pairs, d_plan, set1, d_q1, set2, d_q2);
-                   });
+  const PairSide s1{d_recs1, nframes1, d_counts1, d_offsets1, stride1};
+  const PairSide s2{d_recs2, nframes2, d_counts2, d_offsets2, stride2};
+  const char *own = OWN_CHECK(d_q1 && d_q2 && ((uintptr_t)d_q1 & 15) == 0 && ((uintptr_t)d_q2 & 15) == 0);
+  return pair_match_call(__func__, ctx, npairs, pairs, s1, s2, own, false,
+                        [&](int *h_pairs, void *d_plan, const BatchLayout &set1, const BatchLayout &set2) {
+                          return launch_match_batch_i8(ctx, PAIR_OUT_INPLACE, npairs, h_pairs, d_plan, set1, d_q1, set2,
+                                                       d_q2, PairRows{});
+                        });
 }
 
 // misift_match_pairs_batch with the scores of misift_match_batch_i8: pair-indexed output rows, optional mutual check.
@@ -2317,24 +2330,18 @@ extern "C" int misift_match_pairs_batch_i8(misift_ctx *ctx, int npairs, const in
                                            int nframes2, const int *d_counts2, const int *d_offsets2, int stride2,
                                            int max_pts, int mutual, void *d_out, int *d_out_counts, int *d_num_matched)
 {
-  ARG_CHECK(ctx && npairs >= 0);
-  if (npairs == 0) return MISIFT_OK;
-  ARG_CHECK(pairs && d_recs1 && d_recs2 && d_q1 && d_q2 && d_counts1 && d_counts2 && d_out && d_out_counts &&
-            nframes1 > 0 && nframes2 > 0);
-  ARG_CHECK(((uintptr_t)d_q1 & 15) == 0 && ((uintptr_t)d_q2 & 15) == 0);
-  ARG_CHECK(max_pts >= 1 && (mutual == 0 || mutual == 1));
-  ARG_CHECK(d_out != d_recs1 && d_out != d_recs2);
-  BatchLayout set1, set2;
-  int rc = batch_layout(__func__, d_recs1, d_counts1, d_offsets1, stride1, &set1);
-  if (!rc) rc = batch_layout(__func__, d_recs2, d_counts2, d_offsets2, stride2, &set2);
-  if (!rc) rc = check_frames(__func__, npairs, pairs, 2, nframes1, nframes2, true);
-  if (rc) return rc;
-  RoctxRange range(__func__);
-  return run_batch(ctx, {{pairs, sizeof(int) * 2 * (size_t)npairs}}, pair_plan_bytes(npairs),
-                   [&](int *h_pairs, void *d_plan) {
-                     return launch_match_pairs_batch_i8(ctx, npairs, h_pairs, d_plan, set1, d_q1, set2, d_q2, max_pts,
-                                                        mutual, d_out, d_out_counts, d_num_matched);
-                   });
+  const PairSide s1{d_recs1, nframes1, d_counts1, d_offsets1, stride1};
+  const PairSide s2{d_recs2, nframes2, d_counts2, d_offsets2, stride2};
+  const PairRows rows{max_pts, d_out, d_out_counts, d_num_matched};
+  const char *own = OWN_CHECK(d_q1 && d_q2 && ((uintptr_t)d_q1 & 15) == 0 && ((uintptr_t)d_q2 & 15) == 0);
+  if (!own)
+    own = OWN_CHECK(d_out && d_out_counts && max_pts >= 1 && (mutual == 0 || mutual == 1) && d_out != d_recs1 &&
+                    d_out != d_recs2);
+  return pair_match_call(__func__, ctx, npairs, pairs, s1, s2, own, true,
+                        [&](int *h_pairs, void *d_plan, const BatchLayout &set1, const BatchLayout &set2) {
+                          return launch_match_batch_i8(ctx, mutual ? PAIR_OUT_MUTUAL : PAIR_OUT_INDEXED, npairs,
+                                                       h_pairs, d_plan, set1, d_q1, set2, d_q2, rows);
+                        });
 }
 
 // The accepted matches of a pair-indexed batch joined across pairs into feature tracks: connected components over the

@@ -66,15 +66,15 @@ __device__ __forceinline__ int pair_find(const PairPlan *__restrict__ plan, int 
 
 // bytes of the device plan of npairs pairs
 size_t pair_plan_bytes(int npairs);
-// Enqueue the plan kernel on the context stream, profiled as `name`.  h_pairs: pinned host memory the kernel reads (the
-// caller keeps it unchanged until the kernel has run); d_plan: pair_plan_bytes(npairs) bytes.
-int launch_pair_plan(misift_ctx *ctx, const char *name, const PairShape &S, int npairs, const int *h_pairs,
-                     const BatchLayout &set1, const BatchLayout &set2, void *d_plan);
-// The capped plan of the pair-indexed matchers (pair_plan_capped_kernel): a pair with more than max_pts records on a
-// side gets no work and pad = 1; d_num_matched (may be NULL) starts at 0, or -1 for such a pair.
-int launch_pair_plan_capped(misift_ctx *ctx, const char *name, const PairShape &S, int npairs, const int *h_pairs,
-                            const BatchLayout &set1, const BatchLayout &set2, int max_pts, int *d_num_matched,
-                            void *d_plan);
+// The head of a batched matcher's launches on the context stream (PairOut, PairRows: common.hpp): the temp buffer
+// (misift_ensure_tmp: part_bytes of partials, then the mutual check's npairs x max_pts column keys, returned in *keys,
+// else NULL), the plan kernel, profiled as `plan_name`, and the memset of the keys.  h_pairs: pinned host memory the
+// kernel reads (the caller keeps it unchanged until the kernel has run); d_plan: pair_plan_bytes(npairs) bytes.
+// Pair-indexed calls run the capped plan (pair_plan_capped_kernel): a pair with more than max_pts records on a side
+// gets no work and pad = 1; rows.num_matched (may be NULL) starts at 0, or -1 for such a pair.
+int launch_pair_head(misift_ctx *ctx, const char *plan_name, const PairShape &S, PairOut mode, size_t part_bytes,
+                     int npairs, const int *h_pairs, const BatchLayout &set1, const BatchLayout &set2,
+                     const PairRows &rows, void *d_plan, unsigned long long **keys);
 // The same plan on the host for pairs of n1[i] x n2[i] records (the test hooks): plan5[5 i ..] = first item, row blocks,
 // tiles, chunks, tiles per chunk of pair i.
 int pair_plan_host(const PairShape &S, int npairs, const int *n1, const int *n2, int *plan5, int *nitems, int *chunks,

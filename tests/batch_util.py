@@ -10,6 +10,10 @@ import numpy as np
 from synth import descriptors_to_points, synth_descriptors
 
 MATCH_FIELDS = ("score", "ambiguity", "match", "match_xpos", "match_ypos")
+# the pair-indexed matchers: the fields of an output row, and what their output, counts and num_matched are filled with
+OUT_FIELDS = ("xpos", "ypos") + MATCH_FIELDS
+POISON = 0xA5
+POISON_WORD = 0x5A5A5A5A
 
 
 # ---- batch scaffolding
@@ -148,6 +152,29 @@ def i8_records(p1, p2, core):
     out["match_xpos"] = np.where(idx >= 0, p2["xpos"][mm], np.float32(0))
     out["match_ypos"] = np.where(idx >= 0, p2["ypos"][mm], np.float32(0))
     return out
+
+
+def fields_equal(got, exp, what):
+    for k in OUT_FIELDS:
+        a, b = np.ascontiguousarray(got[k]), np.ascontiguousarray(exp[k])
+        if a.tobytes() != b.tobytes():
+            diff = np.nonzero(a.view(np.uint32) != b.view(np.uint32))[0]
+            raise AssertionError("%s: field %s differs in %d rows, first %s" % (what, k, len(diff), diff[:8]))
+
+
+def untouched(got, counts, max_pts):
+    """Every byte outside the seven fields of rows < count stays poisoned; all bytes of an oversized pair too."""
+    from cudasift_amd import capi
+    raw = got.view(np.uint8).reshape(len(got), 576).copy()
+    mask = np.zeros(576, bool)
+    for k in OUT_FIELDS:
+        off = capi.POINT_DTYPE.fields[k][1]
+        mask[off:off + 4] = True
+    for i, n in enumerate(counts):
+        rows = raw[i * max_pts:(i + 1) * max_pts]
+        if n > 0:
+            rows[:n, mask] = POISON
+        assert (rows == POISON).all(), ("bytes outside the output fields written", i, n)
 
 
 def no_match_rows(p1):

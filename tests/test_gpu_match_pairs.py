@@ -9,7 +9,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from batch_util import MATCH_FIELDS, expected_pair, frames, guarded_context, layout, no_match_rows, num_cus, orc, span
+from batch_util import (POISON, POISON_WORD, expected_pair, fields_equal, frames, guarded_context, layout,
+                        no_match_rows, num_cus, orc, span, untouched)
 from synth import descriptors_to_points, synth_descriptors, synth_frame
 
 pytestmark = pytest.mark.gpu
@@ -18,17 +19,7 @@ SIZES1 = [0, 1, 20, 31, 32, 33, 64, 127, 128, 129, 2000, 4100, 50, 77]   # frame
 COUNTS1 = SIZES1[:12] + [-1, 77]
 SIZES2 = [4100, 2000, 129, 128, 127, 64, 33, 32, 31, 20, 1, 0, 300]
 PAIRS = [(i, (5 * i + 2) % 13) for i in range(13)]
-OUT_FIELDS = ("xpos", "ypos") + MATCH_FIELDS
-POISON = 0xA5
 MISIFT_OK, MISIFT_EINVAL = 0, -1
-
-
-def _fields_equal(got, exp, what):
-    for k in OUT_FIELDS:
-        a, b = np.ascontiguousarray(got[k]), np.ascontiguousarray(exp[k])
-        if a.tobytes() != b.tobytes():
-            diff = np.nonzero(a.view(np.uint32) != b.view(np.uint32))[0]
-            raise AssertionError("%s: field %s differs in %d rows, first %s" % (what, k, len(diff), diff[:8]))
 
 
 def _run(ctx, pairs, r1, c1, o1, s1, r2=None, c2=None, o2=None, s2=0, max_pts=4100, mutual=0, same=False):
@@ -45,8 +36,8 @@ def _run(ctx, pairs, r1, c1, o1, s1, r2=None, c2=None, o2=None, s2=0, max_pts=41
         do2 = ctx.upload(o2) if o2 is not None else None
         nf2 = len(c2)
     out = ctx.upload(np.full(npairs * max_pts * 576, POISON, np.uint8))
-    oc = ctx.upload(np.full(npairs, 0x5A5A5A5A, np.int32))
-    nm = ctx.upload(np.full(npairs, 0x5A5A5A5A, np.int32))
+    oc = ctx.upload(np.full(npairs, POISON_WORD, np.int32))
+    nm = ctx.upload(np.full(npairs, POISON_WORD, np.int32))
     ctx.match_pairs_batch(pairs, d1, len(c1), dc1, do1, s1, d2, nf2, dc2, do2, s2, max_pts=max_pts, mutual=mutual,
                           out=out, out_counts=oc, num_matched=nm)
     ctx.sync()
@@ -54,21 +45,6 @@ def _run(ctx, pairs, r1, c1, o1, s1, r2=None, c2=None, o2=None, s2=0, max_pts=41
     a1 = ctx.download(d1, (len(r1),), capi.POINT_DTYPE)
     a2 = None if same else ctx.download(d2, (len(r2),), capi.POINT_DTYPE)
     return got, ctx.download(oc, (npairs,), np.int32), ctx.download(nm, (npairs,), np.int32), a1, a2
-
-
-def _untouched(got, counts, max_pts):
-    """Every byte outside the seven fields of rows < count stays poisoned; all bytes of an oversized pair too."""
-    from cudasift_amd import capi
-    raw = got.view(np.uint8).reshape(len(got), 576).copy()
-    mask = np.zeros(576, bool)
-    for k in OUT_FIELDS:
-        off = capi.POINT_DTYPE.fields[k][1]
-        mask[off:off + 4] = True
-    for i, n in enumerate(counts):
-        rows = raw[i * max_pts:(i + 1) * max_pts]
-        if n > 0:
-            rows[:n, mask] = POISON
-        assert (rows == POISON).all(), ("bytes outside the output fields written", i, n)
 
 
 def _check(ctx, pairs, r1, c1, o1, s1, r2, c2, o2, s2, full, exact, mutual, max_pts=4100, same=False):
@@ -93,9 +69,9 @@ def _check(ctx, pairs, r1, c1, o1, s1, r2, c2, o2, s2, full, exact, mutual, max_
         exp_counts.append(n1)
         p1, p2 = r1[span(o1, s1, f1, n1)], r2[span(o2, s2, f2, n2)]
         e, k = expected_pair(p1, p2, full, exact, mutual)
-        _fields_equal(got[i * max_pts:i * max_pts + n1], e, "pair %d (%d x %d)" % (i, n1, n2))
+        fields_equal(got[i * max_pts:i * max_pts + n1], e, "pair %d (%d x %d)" % (i, n1, n2))
         assert nm[i] == k, (i, nm[i], k)
-    _untouched(got, exp_counts, max_pts)
+    untouched(got, exp_counts, max_pts)
     return got, oc, nm
 
 
@@ -126,9 +102,9 @@ def test_same_answer_as_match_batch(ctx, full, exact, padded):
             continue
         rows = got[i * 4100:i * 4100 + n1]
         if n2 == 0:
-            _fields_equal(rows, no_match_rows(r1[span(o1, s1, a, n1)]), "empty set 2")
+            fields_equal(rows, no_match_rows(r1[span(o1, s1, a, n1)]), "empty set 2")
             continue
-        _fields_equal(rows, mb[span(o1, s1, a, n1)], "pair %d against misift_match_batch" % i)
+        fields_equal(rows, mb[span(o1, s1, a, n1)], "pair %d against misift_match_batch" % i)
 
 
 def _chunked(n1, n2):

@@ -11,7 +11,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from batch_util import MATCH_FIELDS, frames, guarded_context, layout, no_match_rows, num_cus, orc, span
+from batch_util import (POISON, POISON_WORD, fields_equal, frames, guarded_context, layout, no_match_rows, num_cus, orc,
+                        span, untouched)
 from synth import descriptors_to_points, synth_descriptors, synth_frame
 from test_match_pairs_i8_cpu import expected_pair_i8
 
@@ -21,18 +22,7 @@ SIZES1 = [0, 1, 20, 31, 32, 33, 64, 127, 128, 129, 2000, 4100, 50, 77]   # frame
 COUNTS1 = SIZES1[:12] + [-1, 77]
 SIZES2 = [4100, 2000, 129, 128, 127, 64, 33, 32, 31, 20, 1, 0, 300]
 PAIRS = [(i, (5 * i + 2) % 13) for i in range(13)]
-OUT_FIELDS = ("xpos", "ypos") + MATCH_FIELDS
-POISON = 0xA5
-POISON_WORD = 0x5A5A5A5A
 MISIFT_OK, MISIFT_EINVAL = 0, -1
-
-
-def _fields_equal(got, exp, what):
-    for k in OUT_FIELDS:
-        a, b = np.ascontiguousarray(got[k]), np.ascontiguousarray(exp[k])
-        if a.tobytes() != b.tobytes():
-            diff = np.nonzero(a.view(np.uint32) != b.view(np.uint32))[0]
-            raise AssertionError("%s: field %s differs in %d rows, first %s" % (what, k, len(diff), diff[:8]))
 
 
 class _Set:
@@ -76,21 +66,6 @@ def _run(ctx, pairs, s1, s2, max_pts, mutual):
             ctx.download(nm, (npairs,), np.int32))
 
 
-def _untouched(got, counts, max_pts):
-    """Every byte outside the seven fields of rows < count stays poisoned; all bytes of an oversized pair too."""
-    from cudasift_amd import capi
-    raw = got.view(np.uint8).reshape(len(got), 576).copy()
-    mask = np.zeros(576, bool)
-    for k in OUT_FIELDS:
-        off = capi.POINT_DTYPE.fields[k][1]
-        mask[off:off + 4] = True
-    for i, n in enumerate(counts):
-        rows = raw[i * max_pts:(i + 1) * max_pts]
-        if n > 0:
-            rows[:n, mask] = POISON
-        assert (rows == POISON).all(), ("bytes outside the output fields written", i, n)
-
-
 def _check(ctx, pairs, s1, s2, mutual, max_pts=4100, cache=None):
     """Run and compare every pair with the restatement.  cache: expected rows by (f1, f2, mutual), for calls that
     repeat the same frames."""
@@ -115,9 +90,9 @@ def _check(ctx, pairs, s1, s2, mutual, max_pts=4100, cache=None):
                 cache[key] = ek
         else:
             ek = cache[key]
-        _fields_equal(got[i * max_pts:i * max_pts + n1], ek[0], "pair %d (%d x %d)" % (i, n1, n2))
+        fields_equal(got[i * max_pts:i * max_pts + n1], ek[0], "pair %d (%d x %d)" % (i, n1, n2))
         assert nm[i] == ek[1], (i, nm[i], ek[1])
-    _untouched(got, exp_counts, max_pts)
+    untouched(got, exp_counts, max_pts)
     return got, oc, nm
 
 
@@ -149,11 +124,11 @@ def test_same_answer_as_match_batch_i8(ctx, padded):
             continue
         rows = got[i * 4100:i * 4100 + n1]
         if n2 == 0:
-            _fields_equal(rows, no_match_rows(r1[span(o1, st1, a, n1)]), "empty set 2")
+            fields_equal(rows, no_match_rows(r1[span(o1, st1, a, n1)]), "empty set 2")
             assert nm[i] == 0
             seen.add("n2 == 0")
             continue
-        _fields_equal(rows, mb[span(o1, st1, a, n1)], "pair %d against misift_match_batch_i8" % i)
+        fields_equal(rows, mb[span(o1, st1, a, n1)], "pair %d against misift_match_batch_i8" % i)
     assert seen == {"n1 == 0", "n2 == 0"}
 
 
@@ -289,7 +264,7 @@ def test_oversized_pairs_and_argument_errors(ctx):
     rows = ctx.download(out, (2 * 512,), capi.POINT_DTYPE)
     for i, (a, b) in enumerate(ok):
         (p1, q1), (p2, q2) = st.frame(a), st.frame(b)
-        _fields_equal(rows[i * 512:i * 512 + len(p1)], expected_pair_i8(p1, q1, p2, q2, 1)[0], "NULL num_matched")
+        fields_equal(rows[i * 512:i * 512 + len(p1)], expected_pair_i8(p1, q1, p2, q2, 1)[0], "NULL num_matched")
 
 
 def test_chain_with_no_host_read(ctx):
@@ -332,7 +307,7 @@ def test_chain_with_no_host_read(ctx):
         sel = rows[i * mp:i * mp + n].copy()
         a, b = slice(offs[f1], offs[f1] + fc[f1]), slice(offs[f2], offs[f2] + fc[f2])
         e, k = expected_pair_i8(recs[a], q[a], recs[b], q[b], 1)
-        _fields_equal(sel, e, "chain pair %d" % i)
+        fields_equal(sel, e, "chain pair %d" % i)
         assert nmatch[i] == k == int((sel["match"] >= 0).sum()) and 0 < nmatch[i] < n, (i, nmatch[i], n)
         gated = int(((sel["match"] >= 0) & (sel["score"] > FIND["min_score"]) &
                      (sel["ambiguity"] < FIND["max_ambiguity"])).sum())
