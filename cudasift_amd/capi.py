@@ -111,6 +111,7 @@ SIGNATURES = {
     "misift_test_libc_rand": (_i, [C.c_uint, _i, _vp]),
     "misift_test_homography_samples": (_i, [C.c_uint, _i, _i, _vp]),
     "misift_test_frame_shares": (_i, [_i, _i, C.c_void_p, C.c_void_p]),
+    "misift_test_pyramid_layout": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "misift_test_set_knob": (_i, [_vp, C.c_char_p, C.c_double]),
     "misift_test_knob_names": (C.c_char_p, []),
     "misift_test_set_guard": (_i, [_i]),
@@ -180,6 +181,16 @@ def device_count():
 
 def scratch_floats(width, height, num_octaves=5, scale_up=False):
     return int(lib().misift_scratch_floats(width, height, num_octaves, int(scale_up)))
+
+
+def pyramid_layout(width, height, num_octaves=5, scale_up=False):
+    """misift_test_pyramid_layout (host-only): [(float offset inside one frame's arena, w, h, pitch)] of the pyramid levels
+    num_octaves ... 1, finest first."""
+    off = np.zeros(num_octaves, np.int64)
+    w, h, p = (np.zeros(num_octaves, np.int32) for _ in range(3))
+    check(lib().misift_test_pyramid_layout(width, height, num_octaves, int(scale_up), off.ctypes.data, w.ctypes.data,
+                                           h.ctypes.data, p.ctypes.data), "misift_test_pyramid_layout")
+    return [(int(off[i]), int(w[i]), int(h[i]), int(p[i])) for i in range(num_octaves)]
 
 
 def laplace_taps(num_octaves):
@@ -471,6 +482,34 @@ class Context:
                                    int(scale_up), sc.ptr if sc else None, pts.ptr, max_pts, C.byref(n)),
               "misift_extract")
         return self.download(pts, (max_pts,), POINT_DTYPE), n.value, self.get_counters()
+
+    def extract_raw(self, img_ptr, width, height, pitch, scratch_ptr, pts_ptr, num_octaves=5, init_blur=1.0, thresh=3.0,
+                    lowest_scale=0.0, scale_up=False, max_pts=32768):
+        """misift_extract on raw device pointers (ints): an fp32 frame at img_ptr with row stride `pitch` floats, the arena
+        at scratch_ptr (None: the library's own), records to pts_ptr.  Returns (rc, numPts); rc != 0 is NOT raised."""
+        n = C.c_int(-1)
+        rc = lib().misift_extract(self.h, img_ptr, width, height, pitch, num_octaves, init_blur, thresh, lowest_scale,
+                                  int(scale_up), scratch_ptr, pts_ptr, max_pts, C.byref(n))
+        return rc, n.value
+
+    def extract_batch_raw(self, imgs_ptr, src_u8, nframes, frame_stride, width, height, pitch, scratch_ptr, pts_ptr,
+                          num_octaves=5, init_blur=1.0, thresh=3.0, lowest_scale=0.0, scale_up=False, max_pts=32768):
+        """misift_extract_batch_ex on raw device pointers (ints): 8-bit or fp32 frames, pitch and frame_stride in source
+        elements.  Returns (rc, numPts[nframes]); rc != 0 is NOT raised."""
+        n = (C.c_int * nframes)(*([-1] * nframes))
+        rc = lib().misift_extract_batch_ex(self.h, imgs_ptr, int(src_u8), nframes, frame_stride, width, height, pitch,
+                                           num_octaves, init_blur, thresh, lowest_scale, int(scale_up), scratch_ptr,
+                                           pts_ptr, max_pts, n)
+        return rc, np.array(list(n), np.int32)
+
+    def extract_batch_packed_async_raw(self, imgs_ptr, nframes, frame_stride, width, height, pitch, scratch_ptr, pts_ptr,
+                                       counts_ptr, offsets_ptr, packed_ptr, num_octaves=5, init_blur=1.0, thresh=3.0,
+                                       lowest_scale=0.0, max_pts=32768):
+        """misift_extract_batch_packed_async on raw device pointers (ints); enqueued on the context stream.  Returns rc
+        (not raised)."""
+        return lib().misift_extract_batch_packed_async(self.h, imgs_ptr, nframes, frame_stride, width, height, pitch,
+                                                       num_octaves, init_blur, thresh, lowest_scale, scratch_ptr, pts_ptr,
+                                                       max_pts, counts_ptr, offsets_ptr, packed_ptr)
 
     def extract_batch(self, imgs, num_octaves=5, init_blur=1.0, thresh=3.0, lowest_scale=0.0, max_pts=32768):
         """imgs: [B,h,w] host array.  Returns (points[B,max_pts], numPts[B])."""

@@ -1162,11 +1162,11 @@ __global__ __launch_bounds__(256, SCAN_OCC) void dog_scan_all_kernel(const float
 #endif
 #if SCAN_RING
     scan_strip_ring<FAST>(scratch + (long long)frame * G.frame_stride + L.img_off, L.w, L.h, L.p, q, lane, y0,
-                          min(y0 + L.seg_rows, L.h), tsrc, thresh, cnt, list, cand_cap, octave, true,
+                          min(y0 + L.seg_rows, L.h), tsrc, thresh, cnt, list, cand_cap, octave, FAST != 0,
                           &s_win[wave][lane], s_cq[wave], qn, xch);
 #else
     scan_strip<FAST>(scratch + (long long)frame * G.frame_stride + L.img_off, L.w, L.h, L.p, q, lane, y0,
-                     min(y0 + L.seg_rows, L.h), tsrc, thresh, cnt, list, cand_cap, octave, true,
+                     min(y0 + L.seg_rows, L.h), tsrc, thresh, cnt, list, cand_cap, octave, FAST != 0,
                      s_cq[wave], qn, xch);
 #endif
   }

@@ -253,6 +253,9 @@ __device__ __forceinline__ void lowpass_down_item(const SRC *__restrict__ src, c
     o.y = conv9_expr(k0, k1, k2, k3, k4, W4.y, W3.y + W5.y, W2.y + W6.y, W1.y + W7.y, W0.y + W8.y);
     o.z = conv9_expr(k0, k1, k2, k3, k4, W4.z, W3.z + W5.z, W2.z + W6.z, W1.z + W7.z, W0.z + W8.z);
     o.w = conv9_expr(k0, k1, k2, k3, k4, W4.w, W3.w + W5.w, W2.w + W6.w, W1.w + W7.w, W0.w + W8.w);
+    if (MODE == 2 && qc.edge == 2) {                       // the ragged last quad: its columns inside the image only
+      if (writer && y >= y0 && y < y1) store_quad(out + (size_t)y * dpitch, q, g.width, false, o);
+    } else
 #if LPD_NT
     if (writer && y >= y0 && y < y1) {
       typedef float lpd_v4f __attribute__((ext_vector_type(4)));
@@ -551,7 +554,7 @@ __global__ __launch_bounds__(1024) void scaledown_chain_kernel(float *__restrict
 template <typename SRC>
 __global__ __launch_bounds__(256) void scaleup_kernel(const SRC *__restrict__ src0, int w, int h, int spitch,
                                                       long long src_frame_stride, float *__restrict__ dst0, int dpitch,
-                                                      long long dst_frame_stride)
+                                                      long long dst_frame_stride, int dst_al8)
 {
   const int x = blockIdx.x * 64 + (threadIdx.x & 63);
   const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
@@ -563,8 +566,14 @@ __global__ __launch_bounds__(256) void scaleup_kernel(const SRC *__restrict__ sr
   const float vdl = (float)src[(size_t)yd * spitch + x], vdr = (float)src[(size_t)yd * spitch + xr];
   float2 top = make_float2(vul, 0.50f * (vul + vur));
   float2 bot = make_float2(0.50f * (vul + vdl), 0.25f * (vul + vur + vdl + vdr));
-  *reinterpret_cast<float2 *>(dst + (size_t)(2 * y) * dpitch + 2 * x) = top;
-  *reinterpret_cast<float2 *>(dst + (size_t)(2 * y + 1) * dpitch + 2 * x) = bot;
+  float *r0 = dst + (size_t)(2 * y) * dpitch + 2 * x, *r1 = r0 + dpitch;
+  if (dst_al8) {
+    *reinterpret_cast<float2 *>(r0) = top;
+    *reinterpret_cast<float2 *>(r1) = bot;
+  } else {                                  // a caller's destination at an odd float offset: scalar stores
+    r0[0] = top.x; r0[1] = top.y;
+    r1[0] = bot.x; r1[1] = bot.y;
+  }
 }
 
 // ------------------------------------------------------------- host wrappers
@@ -724,12 +733,14 @@ int launch_scaleup(misift_ctx *ctx, const void *src, int src_u8, int w, int h, i
 {
   LaunchScope ls(ctx, "scaleup");
   const dim3 grid((w + 63) / 64, (h + 3) / 4, nframes);
+  // the pair stores need 8-byte aligned rows, as in launch_lowpass_down_tile
+  const int dst_al8 = (((uintptr_t)dst) & 7) == 0 && (dpitch & 1) == 0 && (dst_frame_stride & 1) == 0;
   if (src_u8)
     hipLaunchKernelGGL(scaleup_kernel<unsigned char>, grid, dim3(256), 0, ctx->stream,
                        static_cast<const unsigned char *>(src), w, h, spitch, src_frame_stride, dst, dpitch,
-                       dst_frame_stride);
+                       dst_frame_stride, dst_al8);
   else
     hipLaunchKernelGGL(scaleup_kernel<float>, grid, dim3(256), 0, ctx->stream, static_cast<const float *>(src), w, h,
-                       spitch, src_frame_stride, dst, dpitch, dst_frame_stride);
+                       spitch, src_frame_stride, dst, dpitch, dst_frame_stride, dst_al8);
   return ls.finish();
 }

@@ -1135,6 +1135,35 @@ int launch_selftest(misift_ctx *ctx)
 // -------------------------------------------------------------- extraction
 struct Level { int w, h, p; float *img; };   // img = frame-0 pointer of that pyramid level
 
+// Arena layout of cudaSiftH.cu:104-107, :151-159, :179-184 inside one frame's arena: size_tmp floats of DoG space, then the
+// pyramid levels, finest (num_octaves) first, each with rows padded to 128 floats.  off[o] = float offset of level o.
+struct LevelDim { int w, h, p; long long off; };
+static void pyramid_levels(int width, int height, int num_octaves, int scale_up, LevelDim *lv /* [num_octaves + 1] */)
+{
+  size_t size_img, size_tmp;
+  scratch_sizes(width, height, num_octaves, scale_up, &size_img, &size_tmp);
+  int w = width * (scale_up ? 2 : 1), h = height * (scale_up ? 2 : 1);
+  long long off = (long long)size_tmp;
+  for (int o = num_octaves; o >= 1; o--) {
+    lv[o].w = w; lv[o].h = h; lv[o].p = ialign_up(w, 128); lv[o].off = off;
+    off += (long long)h * lv[o].p;
+    w /= 2; h /= 2;
+  }
+}
+
+extern "C" int misift_test_pyramid_layout(int width, int height, int num_octaves, int scale_up, long long *offsets,
+                                          int *widths, int *heights, int *pitches)
+{
+  ARG_CHECK(width >= 1 && height >= 1 && num_octaves >= 1 && num_octaves <= MISIFT_MAX_OCTAVES);
+  ARG_CHECK(offsets && widths && heights && pitches);
+  LevelDim lv[MISIFT_MAX_OCTAVES + 1];
+  pyramid_levels(width, height, num_octaves, scale_up ? 1 : 0, lv);
+  for (int o = num_octaves, i = 0; o >= 1; o--, i++) {
+    offsets[i] = lv[o].off; widths[i] = lv[o].w; heights[i] = lv[o].h; pitches[i] = lv[o].p;
+  }
+  return MISIFT_OK;
+}
+
 // Images under 16 x 16, or whose coarsest pyramid level is under 8 px: the reference runs them (levels shrink to a few
 // pixels, every access clamped: cudaSiftH.cu:72-167) and so do we — on the dense per-level kernels, whose quad loads clamp
 // at any width >= 1.  The merged-octave kernels (tiled prefilter, cone chain, strips sized for whole wavefronts) are
@@ -1209,20 +1238,15 @@ int misift_extract_enqueue(misift_ctx *ctx, const void *d_imgs, int src_u8, int 
   }
   const float *table = xt->taps_table, *k9 = xt->k9, *k5 = xt->k5;
 
-  // arena layout of cudaSiftH.cu:104-107, :151-159, :179-184 (per frame, frame stride S)
-  size_t size_img, size_tmp;
-  scratch_sizes(width, height, num_octaves, scale_up, &size_img, &size_tmp);
+  // arena layout (per frame, frame stride S): pyramid_levels
   const int W = width * (scale_up ? 2 : 1), H = height * (scale_up ? 2 : 1);
   float *memoryTmp = d_scratch;
-  float *memorySub = d_scratch + size_tmp;
   std::vector<Level> lv(num_octaves + 1);
   {
-    int w = W, h = H;
-    float *ptr = memorySub;
+    LevelDim dims[MISIFT_MAX_OCTAVES + 1];
+    pyramid_levels(width, height, num_octaves, scale_up, dims);
     for (int o = num_octaves; o >= 1; o--) {
-      lv[o].w = w; lv[o].h = h; lv[o].p = ialign_up(w, 128); lv[o].img = ptr;
-      ptr += (size_t)h * lv[o].p;
-      w /= 2; h /= 2;
+      lv[o].w = dims[o].w; lv[o].h = dims[o].h; lv[o].p = dims[o].p; lv[o].img = d_scratch + dims[o].off;
     }
   }
   const long long SS = (long long)S;
@@ -1851,7 +1875,8 @@ extern "C" int misift_lowpass(misift_ctx *ctx, const float *d_src, int width, in
 extern "C" int misift_lowpass_scaledown(misift_ctx *ctx, const float *d_src, int width, int height, int spitch,
                                         float *d_dst, int dpitch, float sigma, float *d_dst2, int dpitch2)
 {
-  ARG_CHECK(ctx && d_src && d_dst && d_dst2 && width >= 4 && height >= 8);
+  ARG_CHECK(ctx && d_src && d_dst && d_dst2 && width >= 4 && height >= 8 && spitch >= width && dpitch >= width &&
+            dpitch2 >= width / 2);
   HIP_TRY(hipSetDevice(ctx->device));
   float k9[9], k5[5];
   lowpass_taps(sigma, k9);

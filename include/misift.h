@@ -169,8 +169,15 @@ size_t misift_scratch_floats(int width, int height, int num_octaves, int scale_u
 /* --------------------------------------------------------------- extraction */
 
 /* cudaSiftH.cu:72-144 (ExtractSift) for one device-resident frame.
- * d_img: width x height floats, row stride `pitch` floats.
- * d_scratch: misift_scratch_floats() floats, or NULL to allocate per call.
+ * d_img: width x height floats, row stride `pitch` floats.  Any float-aligned base and any pitch >= width are accepted —
+ *   a sub-rectangle &img[y0 * pitch + x0] of a larger image with the parent's pitch, an odd pitch — and nothing outside
+ *   the width x height pixels influences the result (the source is only read, and never past the end of a row's pitch).
+ *   A base aligned to 16 bytes with a pitch that is a multiple of 4 floats selects the vector-load kernels; anything else
+ *   runs the generic ones: same records, bit for bit.
+ * d_scratch: misift_scratch_floats() floats, or NULL to allocate per call.  Any float-aligned pointer is accepted (an
+ *   arena carved out of a pool at any offset); a 16-byte aligned one (any hipMalloc pointer, or one at a multiple of 4
+ *   floats inside a pool) selects the vector kernels inside the arena, anything else the generic ones: same pyramid and
+ *   same records, bit for bit.  Nothing is written in front of d_scratch or behind its misift_scratch_floats() floats.
  * d_pts: max_pts records.  *num_pts_out follows the reference's rule
  * numPts = min(counter[2*num_octaves], max_pts) (cudaSiftH.cu:115-116).
  * One host<->device sync (the count read-back), like the reference.
@@ -193,8 +200,12 @@ int misift_extract(misift_ctx *ctx, const float *d_img, int width, int height, i
 
 /* Same pipeline over a batch of independent frames in one launch sequence
  * (BASELINE config 4: frames shard across GPUs, one batch per device).
- * d_imgs: nframes images, frame stride `frame_stride` floats.
- * d_scratch: nframes * misift_scratch_floats() floats (or NULL).
+ * d_imgs: nframes images, frame stride `frame_stride` floats.  Base and pitch as for misift_extract; any frame_stride is
+ *   accepted (frames with a gap between them, frames of a larger parent, a stride that is no multiple of 4).  The
+ *   vector-load kernels need a 16-byte aligned base and pitch and frame_stride multiples of 4 floats — for 8-bit frames
+ *   (misift_extract_batch_u8 / _ex) a 4-byte aligned base and pitch and frame_stride multiples of 4 bytes; anything else
+ *   runs the generic kernels with the same records, bit for bit.  The same holds for every batch call below.
+ * d_scratch: nframes * misift_scratch_floats() floats (or NULL); any float-aligned pointer, as for misift_extract.
  * d_pts: nframes * max_pts records, frame f at d_pts + f*max_pts.
  * num_pts_out: host array of nframes ints. */
 int misift_extract_batch(misift_ctx *ctx, const float *d_imgs, int nframes,
@@ -290,14 +301,17 @@ int misift_lowpass(misift_ctx *ctx, const float *d_src, int width, int height, i
                    float *d_dst, int dpitch, float sigma);
 /* LowPass and the first ScaleDown of the pyramid in one pass (what ExtractSift does
  * back to back, cudaSiftH.cu:112 + :153-154): dst = LowPass(src), dst2 = ScaleDown(dst),
- * bit-identical to the two separate calls.  Needs width % 4 == 0 and 16-byte aligned rows
- * (MISIFT_EINVAL otherwise; misift_extract falls back to the separate kernels by itself). */
+ * bit-identical to the two separate calls.  Needs 16-byte aligned rows of d_src and d_dst (base, and pitch % 4 == 0) and
+ * 8-byte aligned rows of d_dst2 (base, and dpitch2 % 2 == 0): MISIFT_EINVAL otherwise, nothing is written
+ * (misift_extract falls back to the separate kernels by itself).  Any width >= 4 (since r03) and height >= 8; only the
+ * width x height and (width/2) x (height/2) pixels of the destinations are written. */
 int misift_lowpass_scaledown(misift_ctx *ctx, const float *d_src, int width, int height, int spitch,
                              float *d_dst, int dpitch, float sigma, float *d_dst2, int dpitch2);
 /* ScaleDown (cudaSiftH.cu:308-338, cudaSiftD.cu:84-168): dst is (w/2,h/2). */
 int misift_scaledown(misift_ctx *ctx, const float *d_src, int width, int height,
                      int spitch, float *d_dst, int dpitch);
-/* ScaleUp (cudaSiftH.cu:340-351, cudaSiftD.cu:170-190): dst is (2w,2h). */
+/* ScaleUp (cudaSiftH.cu:340-351, cudaSiftD.cu:170-190): dst is (2w,2h).  dpitch must be even (MISIFT_EINVAL otherwise);
+ * d_dst itself may sit at any float offset. */
 int misift_scaleup(misift_ctx *ctx, const float *d_src, int width, int height, int spitch,
                    float *d_dst, int dpitch);
 /* PrepareLaplaceKernels (cudaSiftH.cu:439-458): fills 8*12*16 floats. */
@@ -750,6 +764,14 @@ int misift_test_homography_samples(unsigned seed, int num_valid, int num_loops, 
 int misift_test_quantize(const float *src, long n, int8_t *dst);
 int misift_test_match_i8_plan(int num_cus, int npairs, const int *n1, const int *n2, int *plan5, int *nitems,
                               int *chunks, int *partial_items_bound);
+
+/* Test-only, host-only: where the extraction calls put the pyramid inside ONE frame's arena (frame f of a batch: add
+ * f * misift_scratch_floats()).  Entry i = pyramid level num_octaves - i (i = 0: the prefiltered image, or its doubled
+ * form under scale_up; every next one its ScaleDown): offsets[i] = float offset of the level's first pixel, widths[i] x
+ * heights[i] its size, pitches[i] its row stride in floats.  Arrays of num_octaves entries.  The table the launch sequence
+ * itself is built from; the levels are still there when an extraction call has returned. */
+int misift_test_pyramid_layout(int width, int height, int num_octaves, int scale_up, long long *offsets, int *widths,
+                               int *heights, int *pitches);
 
 /* Test-only, host-only: how the balanced per-keypoint launches (MISIFT_BALANCE=1) split `nblocks` workgroups among
  * `nframes` frames holding points[f] keypoints: shares[f] = 1 + floor((nblocks - nframes) * points[f] / sum), the formula
