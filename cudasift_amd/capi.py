@@ -22,6 +22,11 @@ POINT_DTYPE = np.dtype([
 assert POINT_DTYPE.itemsize == 576
 
 
+# misift_track_obs: one observation of an exported track (misift_export_tracks_batch)
+TRACK_OBS_DTYPE = np.dtype([("frame", "<i4"), ("record", "<i4"), ("xpos", "<f4"), ("ypos", "<f4")])
+assert TRACK_OBS_DTYPE.itemsize == 16
+
+
 class Options(C.Structure):
     _fields_ = [("texfrac_bits", C.c_int), ("fix_numpts", C.c_int), ("match_full", C.c_int),
                 ("match_exact_top2", C.c_int), ("quiet", C.c_int), ("fused", C.c_int), ("deterministic", C.c_int),
@@ -106,6 +111,8 @@ SIGNATURES = {
     "misift_match_pairs_batch_i8": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _i,
                                          _vp, _vp, _vp]),
     "misift_link_tracks_batch": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _f, _f, _f, _vp, _vp, _vp, _vp]),
+    "misift_export_tracks_batch": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp,
+                                        _vp]),
     "misift_test_quantize": (_i, [_vp, C.c_long, _vp]),
     "misift_test_match_i8_plan": (_i, [_i, _i, _vp, _vp, _vp, _ip, _ip, _ip]),
     "misift_test_libc_rand": (_i, [C.c_uint, _i, _vp]),
@@ -736,6 +743,38 @@ class Context:
                                              _dptr(track), _dptr(track_len), _dptr(track_frames), _dptr(summary)),
               "misift_link_tracks_batch")
         return track, track_len, track_frames, summary
+
+    def export_tracks_batch(self, recs, nframes, counts, offsets=None, stride=0, max_records=None, track=None,
+                            track_len=None, track_frames=None, min_len=2, consistent_only=True, max_tracks=None,
+                            max_obs=None, track_offsets=None, track_root=None, obs=None, record_obs=True, summary=None):
+        """misift_export_tracks_batch: the labels link_tracks_batch wrote (track, track_len, track_frames, for the same
+        layout and max_records) as compact observation lists.  The roots with track_len >= min_len (and, with
+        consistent_only, track_len == track_frames) are numbered in ascending order; track t's observations
+        (TRACK_OBS_DTYPE: frame, record, xpos, ypos) are obs[track_offsets[t]:track_offsets[t + 1]], in ascending order
+        of the global index; a track that does not fit max_tracks / max_obs (default: max_records each) is left out
+        whole, with everything behind it.  track_offsets (max_tracks + 1 ints), track_root (max_tracks ints), obs
+        (max_obs entries), record_obs (max_records ints: each record's slot in obs or -1; True allocates it, None
+        leaves it out) and summary (8 ints) are device buffers, allocated here when not passed; returns the five.
+        Enqueued on the context stream."""
+        assert max_records is not None, "max_records: the length of the record index space"
+        max_tracks = max_records if max_tracks is None else max_tracks
+        max_obs = max_records if max_obs is None else max_obs
+        if track_offsets is None:
+            track_offsets = self.zeros(4 * (max(max_tracks, 1) + 1))
+        if track_root is None:
+            track_root = self.zeros(4 * max(max_tracks, 1))
+        if obs is None:
+            obs = self.zeros(TRACK_OBS_DTYPE.itemsize * max(max_obs, 1))
+        if record_obs is True:
+            record_obs = self.zeros(4 * max(max_records, 1))
+        if summary is None:
+            summary = self.zeros(4 * 8)
+        check(lib().misift_export_tracks_batch(self.h, _dptr(recs), nframes, _dptr(counts), _dptr(offsets), stride,
+                                               max_records, _dptr(track), _dptr(track_len), _dptr(track_frames),
+                                               min_len, int(consistent_only), max_tracks, max_obs,
+                                               _dptr(track_offsets), _dptr(track_root), _dptr(obs), _dptr(record_obs),
+                                               _dptr(summary)), "misift_export_tracks_batch")
+        return track_offsets, track_root, obs, record_obs, summary
 
     def match_split(self, pts1, n1, pts2, n2, own_tile_begin, own_tile_end):
         """Test hook: misift_match with the column sweep cut into two launches (the sharded matcher's cut)."""

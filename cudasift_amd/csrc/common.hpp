@@ -604,6 +604,12 @@ int launch_link_tracks_batch(misift_ctx *ctx, int npairs, const int *h_pairs, co
                              const int *d_row_counts, int max_pts, const BatchLayout &set, int nframes, int max_records,
                              float min_score, float max_ambiguity, float max_error, int *d_track, int *d_track_len,
                              int *d_track_frames, int *d_summary);
+// misift_export_tracks_batch (kernels_tracks.hip): one memset + six launches; temp from misift_ensure_tmp, sized from
+// max_records only
+int launch_export_tracks_batch(misift_ctx *ctx, const BatchLayout &set, int nframes, int max_records, const int *d_track,
+                               const int *d_track_len, const int *d_track_frames, int min_len, int consistent_only,
+                               int max_tracks, int max_obs, int *d_track_offsets, int *d_track_root, void *d_obs,
+                               int *d_record_obs, int *d_summary);
 int launch_test_exp2(misift_ctx *ctx, const float *x, float *out, int n);
 int launch_test_points_fn(misift_ctx *ctx, int fn, const float *x, const float *y, float *out, float *out2, int n);
 int launch_selftest(misift_ctx *ctx);

@@ -1,5 +1,6 @@
 // kernels_tracks.hip — feature tracks of a pair-indexed match batch (misift_link_tracks_batch): the connected components
 // of the accepted matches over all pairs, as a lock-free union-find on the global record index g(f, r) = base(f) + r.
+// Further down: misift_export_tracks_batch, which turns the labels into compact observation lists.
 //
 // One memset and five launches, whatever npairs and whatever the data:
 //   memset                    the (root, frame) table of tracks_frames_kernel to all-ones (= empty);
@@ -244,6 +245,274 @@ __global__ __launch_bounds__(256) void tracks_summary_kernel(TrkArgs A)
 
 size_t trk_align16(size_t v) { return (v + 15) / 16 * 16; }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// misift_export_tracks_batch: the labels of misift_link_tracks_batch turned into a compact array of tracks, each with its
+// observations (frame, record, xpos, ypos) stored contiguously in ascending order of the global index.
+//
+// One memset and six launches, whatever the data:
+//   memset                        sel[] and cursor[] (8 bytes per record of max_records) to 0: a slot that is no frame's
+//                                 valid record contributes zeros to the scan;
+//   tracks_export_select_kernel   per valid record g: sel[g] = len if g is a selected root (track[g] == g, len >= min_len,
+//                                 len == frames when consistent_only), else 0.  One array carries both scanned values:
+//                                 min_len >= 1, so sel[g] > 0 is the "selected" flag;
+//   tracks_export_reduce_kernel   per tile of 2048 indices: (selected roots, their lengths) summed into tile[];
+//   tracks_export_scan_kernel     ONE workgroup: the exclusive prefix sum of tile[] in place, 1024 tiles per step with a
+//                                 running carry, so any max_records is covered; then summary[0..7] (the totals, the
+//                                 dropped frames, zeros for the words the next launch adds to) and track_offsets[0] = 0;
+//   tracks_export_apply_kernel    per tile: the exclusive scan inside the tile on top of tile[], which gives every
+//                                 selected root its number t and its offset off.  The root tests the capacity rule on
+//                                 its own (t < max_tracks, off + len <= max_obs); a written root stores track_root[t],
+//                                 track_offsets[t + 1] = off + len and place[g] = off, every other index place[g] = -1.
+//                                 summary[2..4] are integer sums / a maximum, reduced per workgroup through LDS first;
+//   tracks_export_place_kernel    per valid record of a written track: members[off + cursor[root]++] = g.  The order
+//                                 inside a segment is whatever the atomics gave;
+//   tracks_export_write_kernel    per valid record of a written track: its rank = the entries of its track's segment
+//                                 that are smaller than g, which no longer depends on that order; the observation goes
+//                                 to obs[off + rank] as one 16-byte store and record_obs[g] = off + rank; every other
+//                                 valid record gets record_obs[g] = -1.  A consistent track is at most nframes long, so
+//                                 the count is short where it matters; an inconsistent track of len records costs
+//                                 len * len compares (4097 records: 17 M, still far below a millisecond of the chip).
+// The scan is reduce / scan of the tile sums / apply in separate launches: no workgroup waits for another one.
+//
+// Arrays that no misift_link_tracks_batch call wrote: a length is accepted only in [1, max_records], a root index only
+// in [0, max_records), a track is written only if its whole segment lies in [0, min(max_obs, max_records)), a member is
+// placed only below its track's length, and a rank is used only below it.  The sums are unsigned (they wrap instead of
+// overflowing), and every loop is bounded by a capacity.  So such arrays give unspecified contents inside the
+// capacities and nothing else.
+constexpr int EXP_TILE = 2048;      // indices per scan tile: 256 lanes x 8
+constexpr int EXP_SCAN_WG = 1024;   // tile sums per step of the one-workgroup scan
+
+struct ExpArgs {
+  TrkArgs T;              // set (recs: xpos / ypos of the written records), nframes, max_records, track, len, frames, summary
+  int min_len, consistent_only, max_tracks, max_obs;
+  int cap;                // min(max_obs, max_records): the members array holds max_records entries
+  int ntiles;
+  int *sel;               // temp, max_records: len of a selected root, else 0
+  int *cursor;            // temp, max_records: members placed so far, per root
+  int *place;             // temp, max_records: off of a written root, else -1
+  int *members;           // temp, max_records: the global indices of the written tracks' members, one segment per track
+  uint2 *tile;            // temp, ntiles: (selected roots, their lengths) per tile, then their exclusive prefix sums
+  int *track_offsets, *track_root, *record_obs;
+  int4 *obs;
+};
+
+// Inclusive prefix sum over the wavefront.
+__device__ __forceinline__ uint2 exp_wave_scan(uint2 v)
+{
+  const int lane = threadIdx.x & 63;
+  for (int o = 1; o < 64; o <<= 1) {
+    const unsigned x = __shfl_up(v.x, o), y = __shfl_up(v.y, o);
+    if (lane >= o) { v.x += x; v.y += y; }
+  }
+  return v;
+}
+
+// Exclusive prefix sum of v over a workgroup of NW wavefronts; total = the workgroup's sum.  red: NW entries of LDS.
+template <int NW>
+__device__ __forceinline__ uint2 exp_block_scan(uint2 v, uint2 *red, uint2 &total)
+{
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const uint2 inc = exp_wave_scan(v);
+  __syncthreads();                                               // red[] of an earlier round has been read
+  if (lane == 63) red[wave] = inc;
+  __syncthreads();
+  uint2 before = make_uint2(0, 0);
+  total = make_uint2(0, 0);
+  for (int w = 0; w < NW; w++) {
+    const uint2 r = red[w];
+    if (w < wave) { before.x += r.x; before.y += r.y; }
+    total.x += r.x; total.y += r.y;
+  }
+  return make_uint2(before.x + inc.x - v.x, before.y + inc.y - v.y);
+}
+
+__global__ __launch_bounds__(256) void tracks_export_select_kernel(ExpArgs E)
+{
+  const TrkArgs &A = E.T;
+  for (int f = blockIdx.y; f < A.nframes; f += gridDim.y) {
+    int base, n;
+    if (!trk_frame(A, f, base, n)) continue;
+    for (int r = blockIdx.x * 256 + threadIdx.x; r < n; r += gridDim.x * 256) {
+      const int g = base + r;
+      if (A.track[g] != g) continue;
+      const int len = A.len[g];
+      if (len < E.min_len || len > A.max_records) continue;
+      if (E.consistent_only && len != A.frames[g]) continue;
+      E.sel[g] = len;
+    }
+  }
+}
+
+// The 8 entries of sel[] a lane owns in tile `tile`; zeros beyond max_records.
+__device__ __forceinline__ void exp_load8(const ExpArgs &E, int tile, int v[8])
+{
+  const long long i0 = (long long)tile * EXP_TILE + threadIdx.x * 8;
+  if (i0 + 8 <= E.T.max_records) {
+    const int4 a = *reinterpret_cast<const int4 *>(E.sel + i0), b = *reinterpret_cast<const int4 *>(E.sel + i0 + 4);
+    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+  } else {
+    for (int k = 0; k < 8; k++) v[k] = i0 + k < E.T.max_records ? E.sel[i0 + k] : 0;
+  }
+}
+
+__global__ __launch_bounds__(256) void tracks_export_reduce_kernel(ExpArgs E)
+{
+  __shared__ uint2 red[4];
+  for (int tile = blockIdx.x; tile < E.ntiles; tile += gridDim.x) {
+    int v[8];
+    exp_load8(E, tile, v);
+    uint2 s = make_uint2(0, 0);
+    for (int k = 0; k < 8; k++) { s.x += v[k] > 0; s.y += (unsigned)v[k]; }
+    for (int o = 32; o > 0; o >>= 1) { s.x += __shfl_xor(s.x, o); s.y += __shfl_xor(s.y, o); }
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0)
+      E.tile[tile] = make_uint2(red[0].x + red[1].x + red[2].x + red[3].x, red[0].y + red[1].y + red[2].y + red[3].y);
+  }
+}
+
+__global__ __launch_bounds__(EXP_SCAN_WG) void tracks_export_scan_kernel(ExpArgs E)
+{
+  __shared__ uint2 red[EXP_SCAN_WG / 64];
+  __shared__ int dropped_by_wave[EXP_SCAN_WG / 64];
+  const TrkArgs &A = E.T;
+  uint2 carry = make_uint2(0, 0);
+  for (int t0 = 0; t0 < E.ntiles; t0 += EXP_SCAN_WG) {
+    const int t = t0 + threadIdx.x;
+    const uint2 v = t < E.ntiles ? E.tile[t] : make_uint2(0, 0);
+    uint2 total;
+    const uint2 ex = exp_block_scan<EXP_SCAN_WG / 64>(v, red, total);
+    if (t < E.ntiles) E.tile[t] = make_uint2(carry.x + ex.x, carry.y + ex.y);
+    carry.x += total.x; carry.y += total.y;
+  }
+  int dropped = 0;
+  for (int f = threadIdx.x; f < A.nframes; f += EXP_SCAN_WG) {
+    int base, n;
+    dropped += !trk_frame(A, f, base, n);
+  }
+  for (int o = 32; o > 0; o >>= 1) dropped += __shfl_xor(dropped, o);
+  if ((threadIdx.x & 63) == 0) dropped_by_wave[threadIdx.x >> 6] = dropped;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    dropped = 0;
+    for (int w = 0; w < EXP_SCAN_WG / 64; w++) dropped += dropped_by_wave[w];
+    A.summary[0] = (int)carry.x;
+    A.summary[1] = (int)carry.y;
+    A.summary[2] = A.summary[3] = A.summary[4] = 0;
+    A.summary[5] = dropped;
+    A.summary[6] = A.summary[7] = 0;
+    E.track_offsets[0] = 0;
+  }
+}
+
+__global__ __launch_bounds__(256) void tracks_export_apply_kernel(ExpArgs E)
+{
+  __shared__ uint2 red[4];
+  __shared__ int stat[4][3];
+  int tracks = 0, obs = 0, longest = 0;
+  for (int tile = blockIdx.x; tile < E.ntiles; tile += gridDim.x) {
+    int v[8];
+    exp_load8(E, tile, v);
+    uint2 mine = make_uint2(0, 0);
+    for (int k = 0; k < 8; k++) { mine.x += v[k] > 0; mine.y += (unsigned)v[k]; }
+    uint2 total;
+    uint2 ex = exp_block_scan<4>(mine, red, total);
+    const uint2 before = E.tile[tile];
+    ex.x += before.x; ex.y += before.y;
+    const long long i0 = (long long)tile * EXP_TILE + threadIdx.x * 8;
+    for (int k = 0; k < 8; k++) {
+      if (i0 + k >= E.T.max_records) break;
+      const int len = v[k];
+      int at = -1;
+      if (len > 0) {
+        const int t = (int)ex.x, off = (int)ex.y;
+        if (t >= 0 && t < E.max_tracks && off >= 0 && (long long)off + len <= (long long)E.cap) {
+          at = off;
+          E.track_root[t] = (int)(i0 + k);
+          E.track_offsets[t + 1] = off + len;
+          tracks++;
+          obs += len;
+          longest = max(longest, len);
+        }
+        ex.x += 1; ex.y += (unsigned)len;
+      }
+      E.place[i0 + k] = at;
+    }
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    tracks += __shfl_xor(tracks, o);
+    obs += __shfl_xor(obs, o);
+    longest = max(longest, __shfl_xor(longest, o));
+  }
+  const int wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) { stat[wave][0] = tracks; stat[wave][1] = obs; stat[wave][2] = longest; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < 4; w++) {
+      tracks += stat[w][0]; obs += stat[w][1];
+      longest = max(longest, stat[w][2]);
+    }
+    if (tracks) atomicAdd(E.T.summary + 2, tracks);
+    if (obs) atomicAdd(E.T.summary + 3, obs);
+    if (longest) atomicMax(E.T.summary + 4, longest);
+  }
+}
+
+// The offset of the written track record g belongs to and its length, or -1: its label is no index, or its root is not
+// written.
+__device__ __forceinline__ int exp_segment(const ExpArgs &E, int g, int &root, int &len)
+{
+  root = E.T.track[g];
+  if (root < 0 || root >= E.T.max_records) return -1;
+  const int at = E.place[root];
+  len = at >= 0 ? E.sel[root] : 0;          // place[root] >= 0 only where apply saw sel[root] = len in [1, max_records]
+  return at;
+}
+
+__global__ __launch_bounds__(256) void tracks_export_place_kernel(ExpArgs E)
+{
+  const TrkArgs &A = E.T;
+  for (int f = blockIdx.y; f < A.nframes; f += gridDim.y) {
+    int base, n;
+    if (!trk_frame(A, f, base, n)) continue;
+    for (int r = blockIdx.x * 256 + threadIdx.x; r < n; r += gridDim.x * 256) {
+      const int g = base + r;
+      int root, len;
+      const int at = exp_segment(E, g, root, len);
+      if (at < 0) continue;
+      const int k = atomicAdd(E.cursor + root, 1);
+      if (k >= 0 && k < len) E.members[at + k] = g;              // at + len <= cap, by the apply launch
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void tracks_export_write_kernel(ExpArgs E)
+{
+  const TrkArgs &A = E.T;
+  for (int f = blockIdx.y; f < A.nframes; f += gridDim.y) {
+    int base, n;
+    if (!trk_frame(A, f, base, n)) continue;
+    for (int r = blockIdx.x * 256 + threadIdx.x; r < n; r += gridDim.x * 256) {
+      const int g = base + r;
+      int root, len;
+      const int at = exp_segment(E, g, root, len);
+      int slot = -1;
+      if (at >= 0) {
+        const int placed = min(max(E.cursor[root], 0), len);     // == len for arrays the linker wrote
+        int rank = 0;
+        for (int k = 0; k < placed; k++) rank += E.members[at + k] < g;
+        if (rank < len) slot = at + rank;
+      }
+      if (slot >= 0) {
+        const SiftPointD &rec = A.set.recs[g];
+        E.obs[slot] = make_int4(f, r, __float_as_int(rec.xpos), __float_as_int(rec.ypos));
+      }
+      if (E.record_obs) E.record_obs[g] = slot;
+    }
+  }
+}
+
 }  // namespace
 
 // Enqueue misift_link_tracks_batch on the context stream (common.hpp): one memset, five launches.
@@ -306,5 +575,74 @@ int launch_link_tracks_batch(misift_ctx *ctx, int npairs, const int *h_pairs, co
   }
   LaunchScope ls(ctx, "tracks_summary");
   hipLaunchKernelGGL(tracks_summary_kernel, fgrid, dim3(256), 0, ctx->stream, A);
+  return ls.finish();
+}
+
+// Enqueue misift_export_tracks_batch on the context stream (common.hpp): one memset, six launches.
+int launch_export_tracks_batch(misift_ctx *ctx, const BatchLayout &set, int nframes, int max_records, const int *d_track,
+                               const int *d_track_len, const int *d_track_frames, int min_len, int consistent_only,
+                               int max_tracks, int max_obs, int *d_track_offsets, int *d_track_root, void *d_obs,
+                               int *d_record_obs, int *d_summary)
+{
+  const size_t ints_bytes = trk_align16(sizeof(int) * (size_t)max_records);
+  const int ntiles = (int)(((long long)max_records + EXP_TILE - 1) / EXP_TILE);
+  int rc = misift_ensure_tmp(ctx, 4 * ints_bytes + sizeof(uint2) * (size_t)ntiles);
+  if (rc) return rc;
+  ExpArgs E;
+  E.T = TrkArgs{};
+  E.T.set = set; E.T.nframes = nframes; E.T.max_records = max_records;
+  E.T.track = const_cast<int *>(d_track); E.T.len = const_cast<int *>(d_track_len);     // read only here
+  E.T.frames = const_cast<int *>(d_track_frames);
+  E.T.summary = d_summary;
+  E.min_len = min_len; E.consistent_only = consistent_only; E.max_tracks = max_tracks; E.max_obs = max_obs;
+  E.cap = max_obs < max_records ? max_obs : max_records;
+  E.ntiles = ntiles;
+  char *t = reinterpret_cast<char *>(ctx->d_match_tmp);
+  E.sel = reinterpret_cast<int *>(t);
+  E.cursor = reinterpret_cast<int *>(t + ints_bytes);
+  E.place = reinterpret_cast<int *>(t + 2 * ints_bytes);
+  E.members = reinterpret_cast<int *>(t + 3 * ints_bytes);
+  E.tile = reinterpret_cast<uint2 *>(t + 4 * ints_bytes);
+  E.track_offsets = d_track_offsets; E.track_root = d_track_root; E.record_obs = d_record_obs;
+  E.obs = reinterpret_cast<int4 *>(d_obs);
+  HIP_TRY(hipMemsetAsync(E.sel, 0, 2 * ints_bytes, ctx->stream));
+  const int ncu = ctx->num_cus > 0 ? ctx->num_cus : 256;
+  const int gy = nframes < 1 ? 1 : (nframes < 65535 ? nframes : 65535);
+  int gx = 8 * ncu / gy;
+  gx = gx < 1 ? 1 : (gx > 1024 ? 1024 : gx);
+  const dim3 fgrid(gx, gy);                                       // per frame, as the linker's
+  const dim3 tgrid(ntiles < 8 * ncu ? ntiles : 8 * ncu);          // per tile of the index space
+  {
+    LaunchScope ls(ctx, "tracks_export_select");
+    hipLaunchKernelGGL(tracks_export_select_kernel, fgrid, dim3(256), 0, ctx->stream, E);
+    rc = ls.finish();
+    if (rc) return rc;
+  }
+  {
+    LaunchScope ls(ctx, "tracks_export_reduce");
+    hipLaunchKernelGGL(tracks_export_reduce_kernel, tgrid, dim3(256), 0, ctx->stream, E);
+    rc = ls.finish();
+    if (rc) return rc;
+  }
+  {
+    LaunchScope ls(ctx, "tracks_export_scan");
+    hipLaunchKernelGGL(tracks_export_scan_kernel, dim3(1), dim3(EXP_SCAN_WG), 0, ctx->stream, E);
+    rc = ls.finish();
+    if (rc) return rc;
+  }
+  {
+    LaunchScope ls(ctx, "tracks_export_apply");
+    hipLaunchKernelGGL(tracks_export_apply_kernel, tgrid, dim3(256), 0, ctx->stream, E);
+    rc = ls.finish();
+    if (rc) return rc;
+  }
+  {
+    LaunchScope ls(ctx, "tracks_export_place");
+    hipLaunchKernelGGL(tracks_export_place_kernel, fgrid, dim3(256), 0, ctx->stream, E);
+    rc = ls.finish();
+    if (rc) return rc;
+  }
+  LaunchScope ls(ctx, "tracks_export_write");
+  hipLaunchKernelGGL(tracks_export_write_kernel, fgrid, dim3(256), 0, ctx->stream, E);
   return ls.finish();
 }

@@ -2398,6 +2398,33 @@ extern "C" int misift_link_tracks_batch(misift_ctx *ctx, int npairs, const int *
   });
 }
 
+// The labels misift_link_tracks_batch wrote, turned into a compact array of tracks with their observations stored
+// contiguously: select and number the roots, prefix-sum their lengths, scatter the members in index order.  All on the
+// context stream, no host read.
+extern "C" int misift_export_tracks_batch(misift_ctx *ctx, const void *d_recs, int nframes, const int *d_counts,
+                                          const int *d_offsets, int stride, int max_records, const int *d_track,
+                                          const int *d_track_len, const int *d_track_frames, int min_len,
+                                          int consistent_only, int max_tracks, int max_obs, int *d_track_offsets,
+                                          int *d_track_root, misift_track_obs *d_obs, int *d_record_obs, int *d_summary)
+{
+  ARG_CHECK(ctx && nframes >= 0);
+  ARG_CHECK(d_recs && d_counts && d_track && d_track_len && d_track_frames);
+  ARG_CHECK(d_track_offsets && d_track_root && d_obs && d_summary);
+  ARG_CHECK(((uintptr_t)d_obs & 15) == 0);
+  ARG_CHECK(max_records >= 1 && min_len >= 1 && max_tracks >= 1 && max_obs >= 1);
+  ARG_CHECK(consistent_only == 0 || consistent_only == 1);
+  BatchLayout set;
+  int rc = batch_layout(__func__, d_recs, d_counts, d_offsets, stride, &set);
+  if (rc) return rc;
+  ARG_CHECK(!d_record_obs || (d_record_obs != d_track && d_record_obs != d_track_len && d_record_obs != d_track_frames));
+  RoctxRange range(__func__);
+  return run_batch(ctx, {}, 0, [&](int *, void *) {
+    return launch_export_tracks_batch(ctx, set, nframes, max_records, d_track, d_track_len, d_track_frames, min_len,
+                                      consistent_only, max_tracks, max_obs, d_track_offsets, d_track_root, d_obs,
+                                      d_record_obs, d_summary);
+  });
+}
+
 // ------------------------------------------------------------------- timing
 extern "C" int misift_timer_start(misift_ctx *ctx)
 {

@@ -419,7 +419,8 @@ int misift_match_pairs_batch(misift_ctx *ctx, int npairs, const int *pairs,
  *   - the scratch arena and the output buffers of a call must stay untouched until that batch is done: rotate >= K sets.
  *   - misift_match_batch, misift_match_pairs_batch, misift_quantize_batch, misift_match_batch_i8,
  *     misift_match_pairs_batch_i8, misift_find_homography_batch, misift_improve_homography_batch,
- *     misift_match_guided_batch and misift_link_tracks_batch (which run on the context stream) on a batch's packed records: make the context stream wait for that batch first
+ *     misift_match_guided_batch, misift_link_tracks_batch and misift_export_tracks_batch (which run on the context
+ *     stream) on a batch's packed records: make the context stream wait for that batch first
  *     (misift_ctx_wait_batch(ctx, <the context's stream>), or an event from misift_ctx_record_batch).
  * K = 1 (default) is the plain in-order context.  Also MISIFT_BATCHES_IN_FLIGHT at context creation.  Changing K drains
  * the context. */
@@ -727,6 +728,62 @@ int misift_link_tracks_batch(misift_ctx *ctx, int npairs, const int *pairs /* ho
                              float min_score, float max_ambiguity, float max_error,
                              int *d_track, int *d_track_len, int *d_track_frames,
                              int *d_summary /* 8 ints */);
+
+/* The feature tracks of misift_link_tracks_batch as compact observation lists (no reference counterpart): the selected
+ * tracks numbered in ascending order of their root, each with its observations (frame, record, xpos, ypos) stored
+ * contiguously in ascending order of the global index, on the device.  It is the last call of the device-batch chain
+ * extract -> quantize -> match -> find -> improve -> link -> export.
+ *   - Frames, layouts (d_offsets, or stride when d_offsets is NULL), max(d_counts[f], 0) records per frame, the global
+ *     index g(f, r), max_records and the rule "a frame whose records do not all lie in [0, max_records) takes no part"
+ *     are exactly those of misift_link_tracks_batch.  d_track, d_track_len and d_track_frames are what that call wrote
+ *     for the same layout and max_records.  Of d_recs only xpos and ypos are read, and only for records that are
+ *     written out.
+ *   - A valid record g is a root iff d_track[g] == g.  A root is selected iff d_track_len[g] >= min_len and, with
+ *     consistent_only, d_track_len[g] == d_track_frames[g].  Selected tracks are numbered t = 0, 1, ... in ascending
+ *     order of their root; off[t] = the sum of the lengths of the selected tracks before t.
+ *   - Capacity: track t is written iff t < max_tracks and off[t] + len[t] <= max_obs.  off is increasing, so the
+ *     written tracks are a prefix of T tracks holding O observations; no track is ever cut in the middle.
+ *   - d_track_offsets[0 .. T] = off[0 .. T] (d_track_offsets[0] = 0 always); d_track_root[t] = the root, t < T;
+ *     d_obs[off[t] + k], k < len[t] = the member of track t with the k-th smallest global index: its frame, its
+ *     frame-local record index, and the bits of its xpos / ypos.  d_record_obs[g], when the pointer is given, is written
+ *     for every valid record: that record's slot in d_obs, or -1 if its track is not written.  Every other byte of the
+ *     four arrays stays untouched: entries at or beyond T + 1, T and O, slots that are no frame's valid record, frames
+ *     that take no part.
+ *   - d_summary (8 ints): [0] selected tracks, before the capacity rule, [1] their observations, [2] T, the tracks
+ *     written, [3] O, the observations written, [4] the longest written track (0 if none), [5] frames dropped for lying
+ *     outside max_records, [6] = [7] = 0.  [0] != [2] tells that something was cut.
+ *   - Deterministic: every output is a function of the inputs alone (numbers and offsets are prefix sums of integers,
+ *     a member's place is its rank by index), byte-identical from run to run whatever the dispatch order.
+ *   - Every index that comes from device memory (counts, offsets, labels, lengths) is range-checked before it is used
+ *     as an address.  Label arrays that no misift_link_tracks_batch call produced give unspecified contents, but never
+ *     a write outside the capacities given nor a read outside [0, max_records) of the label arrays.
+ *   - NULL ctx, nframes < 0, NULL d_recs, d_counts, label array, d_track_offsets, d_track_root, d_obs or d_summary,
+ *     d_obs not 16-byte aligned, max_records < 1, min_len < 1, max_tracks < 1, max_obs < 1, consistent_only other than
+ *     0 or 1, d_offsets NULL with a negative stride, d_record_obs equal to one of the three label arrays:
+ *     MISIFT_EINVAL, before anything is enqueued.  nframes == 0 is no error: only d_summary and d_track_offsets[0] are
+ *     written.
+ *   - The call runs on the context stream and returns before the GPU work is done; no host synchronisation and no host
+ *     read of any count.  Ordering behind batches in flight (K > 1): as misift_match_batch.
+ *   - One memset and six launches, whatever the data (select, reduce per tile, scan of the tile sums, apply, place,
+ *     write); no workgroup waits for another.  Temp memory is 16 bytes per record of max_records plus 8 per 2048
+ *     records, from the library's own allocator; nothing is sized by anything read from the device. */
+typedef struct misift_track_obs {   /* 16 bytes */
+  int32_t frame;                    /* frame of the batch */
+  int32_t record;                   /* frame-local record index r: global index g = base(frame) + r */
+  float   xpos, ypos;               /* the record's xpos / ypos, bits copied */
+} misift_track_obs;
+
+int misift_export_tracks_batch(misift_ctx *ctx,
+                               const void *d_recs, int nframes, const int *d_counts, const int *d_offsets, int stride,
+                               int max_records,
+                               const int *d_track, const int *d_track_len, const int *d_track_frames,
+                               int min_len, int consistent_only,
+                               int max_tracks, int max_obs,
+                               int *d_track_offsets,        /* max_tracks + 1 ints */
+                               int *d_track_root,           /* max_tracks ints */
+                               misift_track_obs *d_obs,     /* max_obs entries, 16-byte aligned */
+                               int *d_record_obs,           /* max_records ints, may be NULL */
+                               int *d_summary);             /* 8 ints */
 
 /* cudaMallocManaged as used by the reference's MANAGEDMEM build flavour (cudaSiftH.cu:239-240): one pointer valid on
  * host and device (SiftData.m_data). */
