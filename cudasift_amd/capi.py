@@ -105,6 +105,8 @@ SIGNATURES = {
                                       _vp]),
     "misift_find_homography_batch": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _f, _f, _f, _vp, _vp]),
     "misift_improve_homography_batch": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _f, _f, _f, _vp, _vp]),
+    "misift_find_fundamental_batch": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _f, _f, _f, _vp, _vp]),
+    "misift_score_fundamental_batch": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _i, _f, _f, _f, _vp, _vp]),
     "misift_match_guided_batch": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _f, _i, _vp]),
     "misift_quantize_batch": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp]),
     "misift_match_batch_i8": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i]),
@@ -117,6 +119,9 @@ SIGNATURES = {
     "misift_test_match_i8_plan": (_i, [_i, _i, _vp, _vp, _vp, _ip, _ip, _ip]),
     "misift_test_libc_rand": (_i, [C.c_uint, _i, _vp]),
     "misift_test_homography_samples": (_i, [C.c_uint, _i, _i, _vp]),
+    "misift_test_fundamental_samples": (_i, [C.c_uint, _i, _i, _vp]),
+    "misift_test_fundamental_solve": (_i, [_vp, _vp, _vp]),
+    "misift_test_fundamental_sampson": (_i, [_vp, _vp, _i, _vp, _vp]),
     "misift_test_frame_shares": (_i, [_i, _i, C.c_void_p, C.c_void_p]),
     "misift_test_pyramid_layout": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "misift_test_set_knob": (_i, [_vp, C.c_char_p, C.c_double]),
@@ -644,6 +649,43 @@ class Context:
                                                     _dptr(counts), _dptr(offsets), stride, num_loops, min_score,
                                                     max_ambiguity, thresh, _dptr(homography), _dptr(num_fit)),
               "misift_improve_homography_batch")
+        return num_fit
+
+    def find_fundamental_batch(self, frames, seeds, recs, nframes, counts, offsets=None, stride=0, max_pts=8192,
+                               num_loops=1000, min_score=0.85, max_ambiguity=0.95, thresh=1.0, fundamental=None,
+                               num_inliers=None):
+        """misift_find_fundamental_batch: a RANSAC fundamental matrix (normalised 8-point samples drawn from seeds[i],
+        inliers by Sampson distance < thresh) of the stored matches of frame frames[i] of a device-resident record
+        batch, into slot i of the device buffers `fundamental` (nsel x 9 floats, (x2, y2, 1) F (x1, y1, 1)^T = 0) and
+        `num_inliers` (nsel ints; -1 over max_pts), allocated here when None and returned.  Frames as in match_batch.
+        Enqueued on the context stream."""
+        frames = np.ascontiguousarray(frames, np.int32).reshape(-1)
+        seeds = np.ascontiguousarray(seeds, np.uint32).reshape(-1)
+        assert len(seeds) == len(frames)
+        if fundamental is None:
+            fundamental = self.zeros(4 * 9 * max(len(frames), 1))
+        if num_inliers is None:
+            num_inliers = self.zeros(4 * max(len(frames), 1))
+        check(lib().misift_find_fundamental_batch(self.h, len(frames), frames.ctypes.data, seeds.ctypes.data,
+                                                  _dptr(recs), nframes, _dptr(counts), _dptr(offsets), stride, max_pts,
+                                                  num_loops, min_score, max_ambiguity, thresh, _dptr(fundamental),
+                                                  _dptr(num_inliers)),
+              "misift_find_fundamental_batch")
+        return fundamental, num_inliers
+
+    def score_fundamental_batch(self, frames, recs, nframes, counts, fundamental, offsets=None, stride=0, num_fit=None,
+                                min_score=0.85, max_ambiguity=0.95, thresh=1.0):
+        """misift_score_fundamental_batch: the Sampson distance of every record of frame frames[i] under
+        fundamental[9i..9i+8] (device, e.g. find_fundamental_batch's result) into its match_error, which
+        link_tracks_batch gates on through max_error; num_fit[i] (device, nsel ints, allocated here when None and
+        returned) = the records that pass the gates and lie within thresh.  Enqueued on the context stream."""
+        frames = np.ascontiguousarray(frames, np.int32).reshape(-1)
+        if num_fit is None:
+            num_fit = self.zeros(4 * max(len(frames), 1))
+        check(lib().misift_score_fundamental_batch(self.h, len(frames), frames.ctypes.data, _dptr(recs), nframes,
+                                                   _dptr(counts), _dptr(offsets), stride, min_score, max_ambiguity,
+                                                   thresh, _dptr(fundamental), _dptr(num_fit)),
+              "misift_score_fundamental_batch")
         return num_fit
 
     def match_guided_batch(self, pairs, recs1, nframes1, counts1, homography, radius, offsets1=None, stride1=0,

@@ -341,14 +341,6 @@ namespace {
 
 constexpr int HB_CHUNK = 512;                  // points per count workgroup (8 KiB of LDS)
 
-// the ring of the device rand(): word `slot` is the register of lane `slot` of a wavefront; all 64 lanes run the draw
-// (every index is wave-uniform)
-struct LibcRandWaveRing {
-  uint32_t w;
-  __device__ uint32_t get(uint32_t slot) const { return (uint32_t)__builtin_amdgcn_readlane((int)w, (int)slot); }
-  __device__ void set(uint32_t slot, uint32_t v) { w = (threadIdx.x & 63) == slot ? v : w; }
-};
-
 struct HbArgs {
   BatchLayout set;
   const int *frames;                           // pinned host copies of the caller's lists

@@ -7,8 +7,8 @@
 //   r[31..33] = r[0..2];   r[i] = r[i-31] + r[i-3] mod 2^32;   the k-th rand() is r[344 + k] >> 1.
 // The recurrence needs the last 31 words only, so the state is a ring of 32 words (word i lives in slot i & 31).  Where the
 // ring is stored is a parameter: an array on the host (the test hooks misift_test_libc_rand and
-// misift_test_homography_samples), one word per lane of a wavefront on the device (homography.hip), so the code a CPU test
-// pins is the code the kernel runs.
+// misift_test_homography_samples, misift_test_fundamental_samples), one word per lane of a wavefront on the device
+// (homography.hip, kernels_fundamental.hip), so the code a CPU test pins is the code the kernel runs.
 #pragma once
 #include <stdint.h>
 
@@ -24,6 +24,16 @@ struct LibcRandArrayRing {
   LIBC_RAND_HD uint32_t get(uint32_t slot) const { return w[slot]; }
   LIBC_RAND_HD void set(uint32_t slot, uint32_t v) { w[slot] = v; }
 };
+
+#if defined(__HIPCC__)
+// device storage of the ring: word `slot` is the register of lane `slot` of a wavefront; all 64 lanes run the draw (every
+// index is wave-uniform)
+struct LibcRandWaveRing {
+  uint32_t w;
+  __device__ uint32_t get(uint32_t slot) const { return (uint32_t)__builtin_amdgcn_readlane((int)w, (int)slot); }
+  __device__ void set(uint32_t slot, uint32_t v) { w = (threadIdx.x & 63) == slot ? v : w; }
+};
+#endif
 
 template <class Ring>
 struct LibcRand {
@@ -87,4 +97,24 @@ LIBC_RAND_HD void homography_draw4(LibcRand<Ring> &g, const FastMod31 &fm, int (
   while (p3 == p1 || p3 == p2) p3 = (int)fm.mod((uint32_t)g.next());
   while (p4 == p1 || p4 == p2 || p4 == p3) p4 = (int)fm.mod((uint32_t)g.next());
   p[0] = p1; p[1] = p2; p[2] = p3; p[3] = p4;
+}
+
+// One fundamental-matrix hypothesis' eight distinct positions in the ordered list of valid points: eight draws first,
+// then p[1] .. p[7] in turn are redrawn while they repeat an earlier position.  num_valid >= 8.
+template <class Ring>
+LIBC_RAND_HD void fundamental_draw8(LibcRand<Ring> &g, const FastMod31 &fm, int (&p)[8])
+{
+  int p0 = (int)fm.mod((uint32_t)g.next()), p1 = (int)fm.mod((uint32_t)g.next());
+  int p2 = (int)fm.mod((uint32_t)g.next()), p3 = (int)fm.mod((uint32_t)g.next());
+  int p4 = (int)fm.mod((uint32_t)g.next()), p5 = (int)fm.mod((uint32_t)g.next());
+  int p6 = (int)fm.mod((uint32_t)g.next()), p7 = (int)fm.mod((uint32_t)g.next());
+  while (p1 == p0) p1 = (int)fm.mod((uint32_t)g.next());
+  while (p2 == p0 || p2 == p1) p2 = (int)fm.mod((uint32_t)g.next());
+  while (p3 == p0 || p3 == p1 || p3 == p2) p3 = (int)fm.mod((uint32_t)g.next());
+  while (p4 == p0 || p4 == p1 || p4 == p2 || p4 == p3) p4 = (int)fm.mod((uint32_t)g.next());
+  while (p5 == p0 || p5 == p1 || p5 == p2 || p5 == p3 || p5 == p4) p5 = (int)fm.mod((uint32_t)g.next());
+  while (p6 == p0 || p6 == p1 || p6 == p2 || p6 == p3 || p6 == p4 || p6 == p5) p6 = (int)fm.mod((uint32_t)g.next());
+  while (p7 == p0 || p7 == p1 || p7 == p2 || p7 == p3 || p7 == p4 || p7 == p5 || p7 == p6)
+    p7 = (int)fm.mod((uint32_t)g.next());
+  p[0] = p0; p[1] = p1; p[2] = p2; p[3] = p3; p[4] = p4; p[5] = p5; p[6] = p6; p[7] = p7;
 }

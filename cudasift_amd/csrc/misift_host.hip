@@ -2277,6 +2277,53 @@ extern "C" int misift_improve_homography_batch(misift_ctx *ctx, int nsel, const 
   });
 }
 
+// The epipolar counterpart: a RANSAC fundamental matrix per frame, and the Sampson distance of every record under a
+// given F into match_error, in one stream-ordered call each.
+extern "C" int misift_find_fundamental_batch(misift_ctx *ctx, int nsel, const int *frames, const unsigned *seeds,
+                                             const void *d_recs, int nframes, const int *d_counts, const int *d_offsets,
+                                             int stride, int max_pts, int num_loops, float min_score,
+                                             float max_ambiguity, float thresh, float *d_fundamental,
+                                             int *d_num_inliers)
+{
+  ARG_CHECK(ctx && nsel >= 0);
+  if (nsel == 0) return MISIFT_OK;
+  ARG_CHECK(frames && seeds && d_recs && d_counts && nframes > 0 && d_fundamental && d_num_inliers);
+  BatchLayout set;
+  int rc = batch_layout(__func__, d_recs, d_counts, d_offsets, stride, &set);
+  if (rc) return rc;
+  ARG_CHECK(num_loops >= 1 && max_pts >= 1 && thresh > 0.0f);
+  rc = check_frames(__func__, nsel, frames, 1, nframes, 0);
+  if (rc) return rc;
+  RoctxRange range(__func__);
+  return run_batch(ctx, {{frames, sizeof(int) * (size_t)nsel}, {seeds, sizeof(unsigned) * (size_t)nsel}}, 0,
+                   [&](int *h_frames, void *) {
+                     return launch_find_fundamental_batch(ctx, nsel, h_frames, (const unsigned *)(h_frames + nsel), set,
+                                                          max_pts, num_loops, min_score, max_ambiguity, thresh,
+                                                          d_fundamental, d_num_inliers);
+                   });
+}
+
+extern "C" int misift_score_fundamental_batch(misift_ctx *ctx, int nsel, const int *frames, void *d_recs, int nframes,
+                                              const int *d_counts, const int *d_offsets, int stride, float min_score,
+                                              float max_ambiguity, float thresh, const float *d_fundamental,
+                                              int *d_num_fit)
+{
+  ARG_CHECK(ctx && nsel >= 0);
+  if (nsel == 0) return MISIFT_OK;
+  ARG_CHECK(frames && d_recs && d_counts && nframes > 0 && d_fundamental && d_num_fit);
+  BatchLayout set;
+  int rc = batch_layout(__func__, d_recs, d_counts, d_offsets, stride, &set);
+  if (rc) return rc;
+  ARG_CHECK(thresh > 0.0f);
+  rc = check_frames(__func__, nsel, frames, 1, nframes, 0);
+  if (rc) return rc;
+  RoctxRange range(__func__);
+  return run_batch(ctx, {{frames, sizeof(int) * (size_t)nsel}}, 0, [&](int *h_frames, void *) {
+    return launch_score_fundamental_batch(ctx, nsel, h_frames, set, min_score, max_ambiguity, thresh, d_fundamental,
+                                          d_num_fit);
+  });
+}
+
 // Homography-guided matching of many frame pairs in one stream-ordered call: no host wait and no host read of the counts.
 // The host lists: the pairs, each pair's index among the distinct set-2 frames, and those frames.
 extern "C" int misift_match_guided_batch(misift_ctx *ctx, int npairs, const int *pairs, void *d_recs1, int nframes1,

@@ -419,8 +419,9 @@ int misift_match_pairs_batch(misift_ctx *ctx, int npairs, const int *pairs,
  *   - the scratch arena and the output buffers of a call must stay untouched until that batch is done: rotate >= K sets.
  *   - misift_match_batch, misift_match_pairs_batch, misift_quantize_batch, misift_match_batch_i8,
  *     misift_match_pairs_batch_i8, misift_find_homography_batch, misift_improve_homography_batch,
- *     misift_match_guided_batch, misift_link_tracks_batch and misift_export_tracks_batch (which run on the context
- *     stream) on a batch's packed records: make the context stream wait for that batch first
+ *     misift_find_fundamental_batch, misift_score_fundamental_batch, misift_match_guided_batch,
+ *     misift_link_tracks_batch and misift_export_tracks_batch (which run on the context stream) on a batch's packed
+ *     records: make the context stream wait for that batch first
  *     (misift_ctx_wait_batch(ctx, <the context's stream>), or an event from misift_ctx_record_batch).
  * K = 1 (default) is the plain in-order context.  Also MISIFT_BATCHES_IN_FLIGHT at context creation.  Changing K drains
  * the context. */
@@ -569,6 +570,60 @@ int misift_improve_homography_batch(misift_ctx *ctx, int nsel, const int *frames
                                     void *d_recs, int nframes, const int *d_counts, const int *d_offsets, int stride,
                                     int num_loops, float min_score, float max_ambiguity, float thresh,
                                     float *d_homography /* in/out, nsel x 9 */, int *d_num_fit /* nsel */);
+/* Batched fundamental-matrix estimation (no reference counterpart: the reference's only geometric model is the
+ * homography, which fits a plane or a pure rotation; the C++ drop-in headers, cudaSift.h, do not change): the epipolar
+ * counterpart of the two calls above, for general moving-camera scenes.  Frames, layouts (d_offsets or stride, count -1 =
+ * no records), the host lists `frames` and `seeds` the library copies, stream order on the context stream with no host
+ * synchronisation and no host read of the counts: as misift_find_homography_batch / misift_improve_homography_batch.
+ * Convention: (x2, y2, 1) . F . (x1, y1, 1)^T = 0 with (x1, y1) = xpos, ypos and (x2, y2) = match_xpos, match_ypos of a
+ * record; F is row-major in 9 floats.  All arithmetic is fp32 with every operation rounded (+ - * /, sqrtf, fabsf; no
+ * fused multiply-add), so a restatement in numpy float32 reproduces every output bit.
+ *   find, entry i with frame f = frames[i] and n = d_counts[f]:
+ *   - A record is valid iff score > min_score && ambiguity < max_ambiguity (the gate of matching.cu:1035); the valid
+ *     records keep index order.  n > max_pts: F = nine zeros and d_num_inliers[i] = -1, nothing of the frame is read.
+ *     n < 8 (count -1 included) or fewer than 8 valid records: nine zeros and 0.  Nothing in d_recs is written.
+ *   - Hypothesis h < num_loops (exactly num_loops hypotheses; temp memory rounds it up to 16) takes 8 distinct positions
+ *     in the valid list from glibc's rand() restated on the device, seeded with seeds[i], the hypotheses drawing one
+ *     after another from the one stream: p[0..7] = rand() % num_valid first, then for k = 1..7 in turn p[k] is redrawn
+ *     while it equals some p[j], j < k.  The process's rand() state is neither read nor changed.
+ *   - Normalisation per sample, for each of the two point sets: centroid = the sum in sample order times 0.125f,
+ *     d = the sum in sample order of sqrtf(dx*dx + dy*dy), s = 11.3137085f / d, coordinates (x - cx) * s.
+ *   - Solve: row k of the 8x9 system is (u2 u1, u2 v1, u2, v2 u1, v2 v1, v2, u1, v1, 1).  Gaussian elimination with
+ *     complete pivoting: at step k the pivot is the entry of rows k..7 x columns k..8 with the largest fabsf, searched
+ *     row-major with a strict '>' (the first maximum wins, a NaN never wins); rows and columns are swapped, row r > k
+ *     becomes row r - (A[r][k] / pivot) * row k.  The remaining free column gets 1; back-substitution
+ *     z[k] = -(sum over c > k, ascending, of A[k][c] * z[c]) / A[k][k]; the column permutation undone gives Fn, and
+ *     F = T2^T . Fn . T1 with T = [s 0 -s*cx; 0 s -s*cy; 0 0 1], stored as computed: no rescaling, no rank-2 projection.
+ *     A hypothesis is invalid iff a pivot is 0 or non-finite, or an entry of F is non-finite: its F is nine zeros and
+ *     its count 0.
+ *   - Count, over the valid records only: with a = F (x1, y1, 1)^T, b = F^T (x2, y2, 1)^T, e = x2*a0 + y2*a1 + a2 and
+ *     den = a0*a0 + a1*a1 + b0*b0 + b1*b1, each summed left to right, a record is an inlier iff
+ *     e*e < (thresh*thresh) * den: the squared Sampson distance against thresh^2, without the division.  A comparison
+ *     with a NaN is false.
+ *   - Pick: the largest count at the smallest hypothesis index; its F and count are d_fundamental[9i..9i+8] and
+ *     d_num_inliers[i].  When every count is 0 that is hypothesis 0's F (zeros if it is invalid).
+ *   - Four launches whatever nsel (gather + device draw, solve, count, pick); temp memory is sized from nsel, max_pts and
+ *     num_loops (rounded up to 16) only.
+ *   score, entry i: for EVERY record r < max(n, 0) of the frame, match_error = sqrtf((e*e) / den) under
+ *   d_fundamental[9i..9i+8], +inf where den > 0 is false; d_num_fit[i] = the records that pass the gate above and the
+ *   inlier test.  Only match_error is written.  One launch whatever nsel; an F of nine zeros gives +inf everywhere and 0.
+ *   The rows of misift_match_pairs_batch(_i8) scored this way (frame i = pair i, d_offsets NULL, stride = max_pts,
+ *   counts = d_out_counts) feed misift_link_tracks_batch through its max_error argument.
+ *   - nsel < 0, a frame index outside [0, nframes), a repeated frame, a NULL ctx, records, counts or output pointer,
+ *     max_pts < 1 or num_loops < 1 (find), thresh NaN or <= 0, d_offsets NULL with a negative stride: MISIFT_EINVAL,
+ *     before anything is enqueued.  nsel == 0: nothing happens.
+ *   - The calls return before the GPU work is done.  Ordering behind batches in flight (K > 1): as
+ *     misift_find_homography_batch.
+ *   - Out of scope: least-squares refinement over the inliers, rank-2 enforcement, essential-matrix or pose recovery. */
+int misift_find_fundamental_batch(misift_ctx *ctx, int nsel, const int *frames, const unsigned *seeds,
+                                  const void *d_recs, int nframes, const int *d_counts, const int *d_offsets,
+                                  int stride, int max_pts, int num_loops, float min_score, float max_ambiguity,
+                                  float thresh, float *d_fundamental /* nsel x 9, row-major */,
+                                  int *d_num_inliers /* nsel */);
+int misift_score_fundamental_batch(misift_ctx *ctx, int nsel, const int *frames,
+                                   void *d_recs, int nframes, const int *d_counts, const int *d_offsets, int stride,
+                                   float min_score, float max_ambiguity, float thresh,
+                                   const float *d_fundamental /* nsel x 9 */, int *d_num_fit /* nsel */);
 /* Homography-guided matching (no reference counterpart as an API: MatchAll, mainSift.cpp:95-147, does it as a host
  * diagnostic; the C++ drop-in headers, cudaSift.h, do not change): for each pair i = (f1, f2) = (pairs[2i], pairs[2i+1]),
  * every record of frame f1 of set 1 is matched only against the records of frame f2 of set 2 that lie within `radius`
@@ -814,6 +869,14 @@ int misift_test_match_batch_plan(int num_cus, int match_full, int npairs, const 
  * num_valid >= 8 valid points) of hypothesis loop, in the reference's rejection-loop order (matching.cu:1041-1053). */
 int misift_test_libc_rand(unsigned seed, int n, int *out);
 int misift_test_homography_samples(unsigned seed, int num_valid, int num_loops, int *out);
+/* Test-only, host-only: what misift_find_fundamental_batch / misift_score_fundamental_batch run on the device, compiled
+ * from the same headers.  The sample positions: out[8 * loop + j] = position j (in the ordered list of num_valid >= 8
+ * valid records) of hypothesis loop after srand(seed).  The 8-point solve of one sample xy[4k..4k+3] = x1 y1 x2 y2 of
+ * match k < 8: F9 (nine zeros when invalid) and *valid = 0 / 1.  And the Sampson terms of n matches under F9:
+ * e2_out[i] = e*e, den_out[i] = den. */
+int misift_test_fundamental_samples(unsigned seed, int num_valid, int num_loops, int *out);
+int misift_test_fundamental_solve(const float *xy, float *F9, int *valid);
+int misift_test_fundamental_sampson(const float *F9, const float *xy, int n, float *e2_out, float *den_out);
 /* Test-only, host-only: misift_quantize_batch's rule on n floats, dst[i] = rule(src[i]).  And the work list
  * misift_match_batch_i8's plan kernel builds for pairs of n1[i] x n2[i] records on a chip of num_cus CUs: plan5[5i..5i+4] =
  * first work item, 128-row blocks, 32-column tiles, column chunks, tiles per chunk of pair i; *nitems, *chunks and
