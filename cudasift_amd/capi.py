@@ -108,6 +108,7 @@ SIGNATURES = {
     "misift_find_fundamental_batch": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _f, _f, _f, _vp, _vp]),
     "misift_score_fundamental_batch": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _i, _f, _f, _f, _vp, _vp]),
     "misift_match_guided_batch": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _f, _i, _vp]),
+    "misift_match_epipolar_batch": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _f, _i, _vp]),
     "misift_quantize_batch": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp]),
     "misift_match_batch_i8": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i]),
     "misift_match_pairs_batch_i8": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _i,
@@ -122,6 +123,8 @@ SIGNATURES = {
     "misift_test_fundamental_samples": (_i, [C.c_uint, _i, _i, _vp]),
     "misift_test_fundamental_solve": (_i, [_vp, _vp, _vp]),
     "misift_test_fundamental_sampson": (_i, [_vp, _vp, _i, _vp, _vp]),
+    "misift_test_epipolar_gate": (_i, [_vp, _vp, _i, _vp, _i, _f, _vp]),
+    "misift_test_epipolar_gather": (_i, [_vp, _vp, _i, _vp, _i, _f, _vp, _vp]),
     "misift_test_frame_shares": (_i, [_i, _i, C.c_void_p, C.c_void_p]),
     "misift_test_pyramid_layout": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "misift_test_set_knob": (_i, [_vp, C.c_char_p, C.c_double]),
@@ -705,6 +708,24 @@ class Context:
                                               _dptr(counts1), _dptr(offsets1), stride1, _dptr(recs2), nframes2,
                                               _dptr(counts2), _dptr(offsets2), stride2, _dptr(homography), radius,
                                               max_pts, _dptr(num_found)), "misift_match_guided_batch")
+        return num_found
+
+    def match_epipolar_batch(self, pairs, recs1, nframes1, counts1, fundamental, radius, offsets1=None, stride1=0,
+                             recs2=None, nframes2=None, counts2=None, offsets2=None, stride2=None, max_pts=8192,
+                             num_found=None):
+        """misift_match_epipolar_batch: for each row (f1, f2) of `pairs`, every record of frame f1 of set 1 matched
+        against the records of frame f2 of set 2 within `radius` of its epipolar line under fundamental[9i..9i+8] (device,
+        npairs x 9 floats, (x2, y2, 1) F (x1, y1, 1)^T = 0, e.g. find_fundamental_batch's result).  Frames, the set-2
+        default and num_found as in match_guided_batch.  Enqueued on the context stream."""
+        recs2, nframes2, counts2, offsets2, stride2 = _set2((recs1, nframes1, counts1, offsets1, stride1),
+                                                            (recs2, nframes2, counts2, offsets2, stride2))
+        pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        if num_found is None:
+            num_found = self.zeros(4 * max(len(pairs), 1))
+        check(lib().misift_match_epipolar_batch(self.h, len(pairs), pairs.ctypes.data, _dptr(recs1), nframes1,
+                                                _dptr(counts1), _dptr(offsets1), stride1, _dptr(recs2), nframes2,
+                                                _dptr(counts2), _dptr(offsets2), stride2, _dptr(fundamental), radius,
+                                                max_pts, _dptr(num_found)), "misift_match_epipolar_batch")
         return num_found
 
     def quantize_batch(self, recs, nframes, counts, offsets=None, stride=0, q=None):

@@ -606,6 +606,10 @@ size_t match_guided_batch_tmp_bytes(int npairs, int nd, int max_pts);
 int launch_match_guided_batch(misift_ctx *ctx, int npairs, const int *h_pairs, const int *h_pair_d,
                               const int *h_distinct, int nd, const BatchLayout &set1, const BatchLayout &set2,
                               const float *H, float radius, int max_pts, int *num_found);
+// misift_match_epipolar_batch (kernels_guided.hip): the same bin launch and temp, then the epipolar match kernel
+int launch_match_epipolar_batch(misift_ctx *ctx, int npairs, const int *h_pairs, const int *h_pair_d,
+                                const int *h_distinct, int nd, const BatchLayout &set1, const BatchLayout &set2,
+                                const float *F, float radius, int max_pts, int *num_found);
 // misift_link_tracks_batch (kernels_tracks.hip): one memset + five launches; temp from misift_ensure_tmp, sized from
 // max_records and npairs only
 int launch_link_tracks_batch(misift_ctx *ctx, int npairs, const int *h_pairs, const void *d_rows,

@@ -2324,23 +2324,24 @@ extern "C" int misift_score_fundamental_batch(misift_ctx *ctx, int nsel, const i
   });
 }
 
-// Homography-guided matching of many frame pairs in one stream-ordered call: no host wait and no host read of the counts.
-// The host lists: the pairs, each pair's index among the distinct set-2 frames, and those frames.
-extern "C" int misift_match_guided_batch(misift_ctx *ctx, int npairs, const int *pairs, void *d_recs1, int nframes1,
-                                         const int *d_counts1, const int *d_offsets1, int stride1, const void *d_recs2,
-                                         int nframes2, const int *d_counts2, const int *d_offsets2, int stride2,
-                                         const float *d_homography, float radius, int max_pts, int *d_num_found)
+// Homography- and epipolar-guided matching of many frame pairs in one stream-ordered call each: no host wait and no host
+// read of the counts.  The host lists: the pairs, each pair's index among the distinct set-2 frames, and those frames.
+// d_model: the pairs' homographies (epipolar false) or fundamental matrices (true).
+static int match_gated_batch(const char *fn, bool epipolar, misift_ctx *ctx, int npairs, const int *pairs, void *d_recs1,
+                             int nframes1, const int *d_counts1, const int *d_offsets1, int stride1,
+                             const void *d_recs2, int nframes2, const int *d_counts2, const int *d_offsets2,
+                             int stride2, const float *d_model, float radius, int max_pts, int *d_num_found)
 {
-  ARG_CHECK(ctx && npairs >= 0);
+  ARG_CHECK_IN(fn, ctx && npairs >= 0);
   if (npairs == 0) return MISIFT_OK;
-  ARG_CHECK(pairs && d_recs1 && d_recs2 && d_counts1 && d_counts2 && d_homography && nframes1 > 0 && nframes2 > 0);
+  ARG_CHECK_IN(fn, pairs && d_recs1 && d_recs2 && d_counts1 && d_counts2 && d_model && nframes1 > 0 && nframes2 > 0);
   BatchLayout set1, set2;
-  int rc = batch_layout(__func__, d_recs1, d_counts1, d_offsets1, stride1, &set1);
-  if (!rc) rc = batch_layout(__func__, d_recs2, d_counts2, d_offsets2, stride2, &set2);
+  int rc = batch_layout(fn, d_recs1, d_counts1, d_offsets1, stride1, &set1);
+  if (!rc) rc = batch_layout(fn, d_recs2, d_counts2, d_offsets2, stride2, &set2);
   if (rc) return rc;
-  ARG_CHECK(radius > 0.0f);                                // NaN fails too
-  ARG_CHECK(max_pts >= 1);
-  rc = check_frames(__func__, npairs, pairs, 2, nframes1, nframes2);
+  ARG_CHECK_IN(fn, radius > 0.0f);                                // NaN fails too
+  ARG_CHECK_IN(fn, max_pts >= 1);
+  rc = check_frames(fn, npairs, pairs, 2, nframes1, nframes2);
   if (rc) return rc;
   std::vector<int> dindex((size_t)nframes2, -1), pair_d((size_t)npairs), distinct;
   for (int p = 0; p < npairs; p++) {
@@ -2352,16 +2353,36 @@ extern "C" int misift_match_guided_batch(misift_ctx *ctx, int npairs, const int 
     pair_d[p] = dindex[f2];
   }
   const int nd = (int)distinct.size();
-  RoctxRange range(__func__);
+  RoctxRange range(fn);
   return run_batch(ctx,
                    {{pairs, sizeof(int) * 2 * (size_t)npairs},
                     {pair_d.data(), sizeof(int) * (size_t)npairs},
                     {distinct.data(), sizeof(int) * (size_t)nd}},
                    0, [&](int *h_pairs, void *) {
                      const int *h_pair_d = h_pairs + 2 * (size_t)npairs;
-                     return launch_match_guided_batch(ctx, npairs, h_pairs, h_pair_d, h_pair_d + npairs, nd, set1,
-                                                      set2, d_homography, radius, max_pts, d_num_found);
+                     return (epipolar ? launch_match_epipolar_batch : launch_match_guided_batch)(
+                         ctx, npairs, h_pairs, h_pair_d, h_pair_d + npairs, nd, set1, set2, d_model, radius, max_pts,
+                         d_num_found);
                    });
+}
+
+extern "C" int misift_match_guided_batch(misift_ctx *ctx, int npairs, const int *pairs, void *d_recs1, int nframes1,
+                                         const int *d_counts1, const int *d_offsets1, int stride1, const void *d_recs2,
+                                         int nframes2, const int *d_counts2, const int *d_offsets2, int stride2,
+                                         const float *d_homography, float radius, int max_pts, int *d_num_found)
+{
+  return match_gated_batch(__func__, false, ctx, npairs, pairs, d_recs1, nframes1, d_counts1, d_offsets1, stride1,
+                           d_recs2, nframes2, d_counts2, d_offsets2, stride2, d_homography, radius, max_pts, d_num_found);
+}
+
+extern "C" int misift_match_epipolar_batch(misift_ctx *ctx, int npairs, const int *pairs, void *d_recs1, int nframes1,
+                                           const int *d_counts1, const int *d_offsets1, int stride1, const void *d_recs2,
+                                           int nframes2, const int *d_counts2, const int *d_offsets2, int stride2,
+                                           const float *d_fundamental, float radius, int max_pts, int *d_num_found)
+{
+  return match_gated_batch(__func__, true, ctx, npairs, pairs, d_recs1, nframes1, d_counts1, d_offsets1, stride1,
+                           d_recs2, nframes2, d_counts2, d_offsets2, stride2, d_fundamental, radius, max_pts,
+                           d_num_found);
 }
 
 // 8-bit descriptors of every record of a device-resident batch, one stream-ordered launch with the counts on the device.

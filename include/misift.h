@@ -420,7 +420,8 @@ int misift_match_pairs_batch(misift_ctx *ctx, int npairs, const int *pairs,
  *   - misift_match_batch, misift_match_pairs_batch, misift_quantize_batch, misift_match_batch_i8,
  *     misift_match_pairs_batch_i8, misift_find_homography_batch, misift_improve_homography_batch,
  *     misift_find_fundamental_batch, misift_score_fundamental_batch, misift_match_guided_batch,
- *     misift_link_tracks_batch and misift_export_tracks_batch (which run on the context stream) on a batch's packed
+ *     misift_match_epipolar_batch, misift_link_tracks_batch and misift_export_tracks_batch (which run on the context
+ *     stream) on a batch's packed
  *     records: make the context stream wait for that batch first
  *     (misift_ctx_wait_batch(ctx, <the context's stream>), or an event from misift_ctx_record_batch).
  * K = 1 (default) is the plain in-order context.  Also MISIFT_BATCHES_IN_FLIGHT at context creation.  Changing K drains
@@ -658,6 +659,37 @@ int misift_match_guided_batch(misift_ctx *ctx, int npairs, const int *pairs,
                               const void *d_recs2, int nframes2, const int *d_counts2, const int *d_offsets2, int stride2,
                               const float *d_homography /* npairs x 9, device */, float radius, int max_pts,
                               int *d_num_found /* npairs, device, may be NULL */);
+/* Epipolar-guided matching (no reference counterpart; the C++ drop-in headers do not change): the moving-camera
+ * counterpart of misift_match_guided_batch.  For each pair i, every record of frame f1 of set 1 is matched only against
+ * the records of frame f2 of set 2 that lie within `radius` of its epipolar line under d_fundamental[9i..9i+8], in the
+ * convention of misift_find_fundamental_batch, (x2, y2, 1) . F . (x1, y1, 1)^T = 0 (the layout of its output when
+ * frames[i] is pair i's set-1 frame; all nine entries used as given).  In the chain: misift_match_batch ->
+ * misift_find_fundamental_batch -> misift_match_epipolar_batch -> misift_score_fundamental_batch -> link -> export.
+ * Everything not said here is the contract of misift_match_guided_batch, word for word: pairs and layouts, count -1,
+ * a set-1 frame in at most one pair and a set-2 frame in any number, d_recs1 == d_recs2, max_pts (-1, untouched) and
+ * empty sides (0, untouched), the five fields written, the copied `pairs`, the stream order with no host
+ * synchronisation and no host read, the two launches (the same bin launch, then the epipolar match kernel), the temp
+ * memory, the MISIFT_EINVAL list with d_fundamental in the place of d_homography, and npairs == 0.
+ *   - The gate, for row (x, y) of set 1, in fp32 with every operation rounded (no contraction), sums left to right:
+ *     a0 = F0*x + F1*y + F2, a1 = F3*x + F4*y + F5, a2 = F6*x + F7*y + F8, n2 = a0*a0 + a1*a1 (the `a` terms of the
+ *     Sampson test); record j of set 2 at (x2, y2) is a candidate iff, with e = x2*a0 + y2*a1 + a2,
+ *     e*e < (radius*radius) * n2: the squared point-to-line distance in image 2 against radius^2, without the division;
+ *     radius*radius is rounded to fp32 once on the host.
+ *   - A row whose a0, a1, a2 or n2 is non-finite (an overflowing n2 included) has no candidate.  Otherwise the
+ *     comparison decides as written: a NaN comparison is false, n2 == 0 admits nothing, a right-hand side of +inf
+ *     (radius = +inf, or an overflowing finite product) admits every record whose e*e is finite.  A set-2 record with a
+ *     non-finite position is never a candidate.
+ *   - The row gets the exact top-2 over its candidates (k-ordered fmaf chain; only scores > 0 count; match = the smallest
+ *     frame-local index that attains the best score; a second copy of the best score is the runner-up); a row with no
+ *     candidate gets match -1, score 0, ambiguity 0 and match positions 0; whatever the options of the context.
+ *     radius = +inf with a finite non-zero F equals misift_match with match_full = 1, match_exact_top2 = 1, byte for byte.
+ *   - The result is the gate's alone: the walk that finds the candidates (a band across the cell grid) is conservative
+ *     and leaves no trace in the output. */
+int misift_match_epipolar_batch(misift_ctx *ctx, int npairs, const int *pairs,
+                                void *d_recs1, int nframes1, const int *d_counts1, const int *d_offsets1, int stride1,
+                                const void *d_recs2, int nframes2, const int *d_counts2, const int *d_offsets2, int stride2,
+                                const float *d_fundamental /* npairs x 9, row-major, device */, float radius, int max_pts,
+                                int *d_num_found /* npairs, device, may be NULL */);
 
 /* 8-bit descriptors (no reference counterpart; the C++ drop-in headers do not change): for every record r of every frame
  * of a device-resident batch (frames as in misift_match_batch: d_offsets or stride, max(d_counts[f], 0) records),
@@ -877,6 +909,16 @@ int misift_test_homography_samples(unsigned seed, int num_valid, int num_loops, 
 int misift_test_fundamental_samples(unsigned seed, int num_valid, int num_loops, int *out);
 int misift_test_fundamental_solve(const float *xy, float *F9, int *valid);
 int misift_test_fundamental_sampson(const float *F9, const float *xy, int n, float *e2_out, float *den_out);
+/* Test-only, host-only: the gate and the gather of misift_match_epipolar_batch, compiled from the same headers and
+ * functions as the kernel.  xy1: n1 set-1 positions (x, y), xy2: n2 set-2 positions.  gate: pass[i * n2 + j] = 1 iff
+ * record j is a candidate of row i under F9 and radius.  gather: builds the cell grid of xy2 as the bin launch does
+ * (grid2[0..1] = cells per axis), walks every row's band with the kernel's span functions, and sets
+ * visited[i * n2 + j] = 1 iff record j lies in a cell that row i visits (0 for a non-finite position, which no cell
+ * holds).  The gather is conservative iff pass & ~visited is empty. */
+int misift_test_epipolar_gate(const float *F9, const float *xy1, int n1, const float *xy2, int n2, float radius,
+                              unsigned char *pass);
+int misift_test_epipolar_gather(const float *F9, const float *xy1, int n1, const float *xy2, int n2, float radius,
+                                unsigned char *visited, int *grid2);
 /* Test-only, host-only: misift_quantize_batch's rule on n floats, dst[i] = rule(src[i]).  And the work list
  * misift_match_batch_i8's plan kernel builds for pairs of n1[i] x n2[i] records on a chip of num_cus CUs: plan5[5i..5i+4] =
  * first work item, 128-row blocks, 32-column tiles, column chunks, tiles per chunk of pair i; *nitems, *chunks and
