@@ -123,6 +123,7 @@ SIGNATURES = {
     "misift_test_fundamental_samples": (_i, [C.c_uint, _i, _i, _vp]),
     "misift_test_fundamental_solve": (_i, [_vp, _vp, _vp]),
     "misift_test_fundamental_sampson": (_i, [_vp, _vp, _i, _vp, _vp]),
+    "misift_test_fundamental_error": (_i, [_vp, _vp, _i, _vp]),
     "misift_test_epipolar_gate": (_i, [_vp, _vp, _i, _vp, _i, _f, _vp]),
     "misift_test_epipolar_gather": (_i, [_vp, _vp, _i, _vp, _i, _f, _vp, _vp]),
     "misift_test_frame_shares": (_i, [_i, _i, C.c_void_p, C.c_void_p]),

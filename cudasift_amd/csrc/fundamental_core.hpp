@@ -1,7 +1,7 @@
 // fundamental_core.hpp — the arithmetic of misift_find_fundamental_batch / misift_score_fundamental_batch, for host and
 // device: the normalised 8-point solve of one RANSAC hypothesis and the Sampson test of one stored match.  The kernels
-// (kernels_fundamental.hip) and the host-only test hooks (misift_test_fundamental_solve, _sampson) compile these same
-// functions, so what a CPU test pins is what the device runs.
+// (kernels_fundamental.hip) and the host-only test hooks (misift_test_fundamental_solve, _sampson, _error) compile these
+// same functions, so what a CPU test pins is what the device runs.
 //
 // Everything is fp32 with every operation rounded: only + - * /, sqrtf and fabsf, no fmaf, and the build's
 // -ffp-contract=off keeps the compiler from fusing.  The order of every sum is written out; tests restate it in numpy.
@@ -158,5 +158,16 @@ FUND_HD float fundamental_sampson(const float (&F)[9], float x1, float y1, float
 // a match is an inlier iff e^2 < thresh^2 * den (a comparison with a NaN is false)
 FUND_HD bool fundamental_inlier(float e2, float den, float thresh2) { return e2 < thresh2 * den; }
 
-// match_error: the Sampson distance, +inf where den > 0 is false
-FUND_HD float fundamental_error(float e2, float den) { return den > 0.0f ? sqrtf(e2 / den) : INFINITY; }
+// match_error: the Sampson distance, +inf where den > 0 is false.  A NaN result (e2 NaN, or inf / inf) is stored as the
+// one quiet NaN 0x7fc00000: the sign and payload an operation gives a NaN differ from processor to processor (inf - inf
+// is 0xffc00000 on x86 and 0x7fc00000 on the GPU), and match_error is the only output of the two calls that can hold one.
+FUND_HD float fundamental_error(float e2, float den)
+{
+  if (!(den > 0.0f)) return INFINITY;
+  float d = sqrtf(e2 / den);
+  unsigned u;                                  // on the bits: a float select of a NaN for a NaN may be folded away
+  __builtin_memcpy(&u, &d, sizeof u);
+  if ((u & 0x7fffffffu) > 0x7f800000u) u = 0x7fc00000u;
+  __builtin_memcpy(&d, &u, sizeof u);
+  return d;
+}

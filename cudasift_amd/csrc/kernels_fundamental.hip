@@ -297,8 +297,8 @@ int launch_score_fundamental_batch(misift_ctx *ctx, int nsel, const int *h_frame
   return ls.finish();
 }
 
-// Test-only, host-only: the sample draw, the 8-point solve and the Sampson terms the kernels run (libc_rand.hpp,
-// fundamental_core.hpp).
+// Test-only, host-only: the sample draw, the 8-point solve, the Sampson terms and match_error as the kernels compute
+// them (libc_rand.hpp, fundamental_core.hpp).
 extern "C" int misift_test_fundamental_samples(unsigned seed, int num_valid, int num_loops, int *out)
 {
   if (num_valid < 8 || num_loops < 0 || (num_loops > 0 && !out)) {
@@ -340,5 +340,15 @@ extern "C" int misift_test_fundamental_sampson(const float *F9, const float *xy,
   for (int k = 0; k < 9; k++) F[k] = F9[k];
   for (int i = 0; i < n; i++)
     e2_out[i] = fundamental_sampson(F, xy[4 * i], xy[4 * i + 1], xy[4 * i + 2], xy[4 * i + 3], den_out[i]);
+  return MISIFT_OK;
+}
+
+extern "C" int misift_test_fundamental_error(const float *e2, const float *den, int n, float *out)
+{
+  if (n < 0 || (n > 0 && (!e2 || !den || !out))) {
+    misift_set_error("misift_test_fundamental_error: invalid argument");
+    return MISIFT_EINVAL;
+  }
+  for (int i = 0; i < n; i++) out[i] = fundamental_error(e2[i], den[i]);
   return MISIFT_OK;
 }

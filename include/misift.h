@@ -606,8 +606,10 @@ int misift_improve_homography_batch(misift_ctx *ctx, int nsel, const int *frames
  *   - Four launches whatever nsel (gather + device draw, solve, count, pick); temp memory is sized from nsel, max_pts and
  *     num_loops (rounded up to 16) only.
  *   score, entry i: for EVERY record r < max(n, 0) of the frame, match_error = sqrtf((e*e) / den) under
- *   d_fundamental[9i..9i+8], +inf where den > 0 is false; d_num_fit[i] = the records that pass the gate above and the
- *   inlier test.  Only match_error is written.  One launch whatever nsel; an F of nine zeros gives +inf everywhere and 0.
+ *   d_fundamental[9i..9i+8], +inf where den > 0 is false, and the quiet NaN 0x7fc00000 where that square root is a NaN
+ *   (e*e NaN, or inf / inf: the sign and payload of a computed NaN are the processor's choice, so none is stored);
+ *   d_num_fit[i] = the records that pass the gate above and the inlier test.  Only match_error is written.  One launch
+ *   whatever nsel; an F of nine zeros gives +inf everywhere and 0.
  *   The rows of misift_match_pairs_batch(_i8) scored this way (frame i = pair i, d_offsets NULL, stride = max_pts,
  *   counts = d_out_counts) feed misift_link_tracks_batch through its max_error argument.
  *   - nsel < 0, a frame index outside [0, nframes), a repeated frame, a NULL ctx, records, counts or output pointer,
@@ -905,10 +907,11 @@ int misift_test_homography_samples(unsigned seed, int num_valid, int num_loops, 
  * from the same headers.  The sample positions: out[8 * loop + j] = position j (in the ordered list of num_valid >= 8
  * valid records) of hypothesis loop after srand(seed).  The 8-point solve of one sample xy[4k..4k+3] = x1 y1 x2 y2 of
  * match k < 8: F9 (nine zeros when invalid) and *valid = 0 / 1.  And the Sampson terms of n matches under F9:
- * e2_out[i] = e*e, den_out[i] = den. */
+ * e2_out[i] = e*e, den_out[i] = den.  And match_error as score stores it: out[i] from e2[i] and den[i]. */
 int misift_test_fundamental_samples(unsigned seed, int num_valid, int num_loops, int *out);
 int misift_test_fundamental_solve(const float *xy, float *F9, int *valid);
 int misift_test_fundamental_sampson(const float *F9, const float *xy, int n, float *e2_out, float *den_out);
+int misift_test_fundamental_error(const float *e2, const float *den, int n, float *out);
 /* Test-only, host-only: the gate and the gather of misift_match_epipolar_batch, compiled from the same headers and
  * functions as the kernel.  xy1: n1 set-1 positions (x, y), xy2: n2 set-2 positions.  gate: pass[i * n2 + j] = 1 iff
  * record j is a candidate of row i under F9 and radius.  gather: builds the cell grid of xy2 as the bin launch does

@@ -162,6 +162,14 @@ def expected_find(recs, n, seed, num_loops, min_score, max_ambiguity, thresh, ma
     return F[best].copy(), int(counts[best])
 
 
+def fundamental_error(e2, den):
+    """match_error from the Sampson terms: +inf where den > 0 is false, and the one quiet NaN 0x7fc00000 for a NaN."""
+    with np.errstate(all="ignore"):
+        d = np.sqrt(np.asarray(e2, f32) / np.asarray(den, f32))
+        d = np.where(np.isnan(d), np.uint32(0x7FC00000).view(f32), d)
+        return np.where(den > 0, d, f32(np.inf)).astype(f32)
+
+
 def expected_score(recs, n, F, min_score, max_ambiguity, thresh):
     """(the frame's records with match_error of rows < max(n, 0) rewritten, num_fit)."""
     out = recs.copy()
@@ -171,7 +179,7 @@ def expected_score(recs, n, F, min_score, max_ambiguity, thresh):
     e2, den = e2[0], den[0]
     t2 = f32(thresh) * f32(thresh)
     with np.errstate(all="ignore"):
-        err = np.where(den > 0, np.sqrt(e2 / den), f32(np.inf)).astype(f32)
+        err = fundamental_error(e2, den)
         fit = gate(p, min_score, max_ambiguity) & (e2 < t2 * den)
     out["match_error"][:n] = err
     return out, int(fit.sum())
@@ -231,7 +239,7 @@ def test_library_exports_the_calls():
     from cudasift_amd import capi
     L = capi.lib()
     for name in ("misift_find_fundamental_batch", "misift_score_fundamental_batch", "misift_test_fundamental_samples",
-                 "misift_test_fundamental_solve", "misift_test_fundamental_sampson"):
+                 "misift_test_fundamental_solve", "misift_test_fundamental_sampson", "misift_test_fundamental_error"):
         assert name in capi.SIGNATURES and hasattr(L, name), name
     assert hasattr(capi.Context, "find_fundamental_batch") and hasattr(capi.Context, "score_fundamental_batch")
     fr, sd = np.zeros(1, np.int32), np.ones(1, np.uint32)

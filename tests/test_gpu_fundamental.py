@@ -51,10 +51,14 @@ def _records(n, seed, keep=None):
     return recs
 
 
-@pytest.fixture(scope="module")
-def batch():
+def make_batch():
     keep = {12: 7, 13: 8, 14: 9}
     return [_records(n, f, keep.get(f)) for f, n in enumerate(SIZES)]
+
+
+@pytest.fixture(scope="module")
+def batch():
+    return make_batch()
 
 
 def _poisoned(ctx, words):
