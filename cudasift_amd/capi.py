@@ -126,6 +126,7 @@ SIGNATURES = {
     "misift_test_fundamental_error": (_i, [_vp, _vp, _i, _vp]),
     "misift_test_epipolar_gate": (_i, [_vp, _vp, _i, _vp, _i, _f, _vp]),
     "misift_test_epipolar_gather": (_i, [_vp, _vp, _i, _vp, _i, _f, _vp, _vp]),
+    "misift_test_guided_gather": (_i, [_vp, _vp, _i, _vp, _i, _f, _vp, _vp, _vp]),
     "misift_test_frame_shares": (_i, [_i, _i, C.c_void_p, C.c_void_p]),
     "misift_test_pyramid_layout": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "misift_test_set_knob": (_i, [_vp, C.c_char_p, C.c_double]),

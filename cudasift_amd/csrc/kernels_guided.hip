@@ -135,7 +135,23 @@ __host__ __device__ __forceinline__ GmGrid gm_make_grid(float xmin, float xmax, 
   return G;
 }
 
-__device__ __forceinline__ bool gm_finite(float v) { return __builtin_isfinite(v); }
+__host__ __device__ __forceinline__ bool gm_finite(float v) { return __builtin_isfinite(v); }
+
+// The disc walk of the homography-guided call: the cell rectangle [cx0, cx1] x [cy0, cy1] of fl(px - r') .. fl(px + r')
+// (cx1 < cx0 and cy1 < cy0, an empty range, and false for a non-finite projection).  The match kernel and the host-only
+// gather hook walk the rectangle this one function gives.
+__host__ __device__ __forceinline__ bool gm_disc(const GmGrid &G, float px, float py, double rp, int &cx0, int &cx1,
+                                                 int &cy0, int &cy1)
+{
+  cx0 = 0; cx1 = -1; cy0 = 0; cy1 = -1;
+  if (!(gm_finite(px) && gm_finite(py))) return false;
+  const double dx = (double)px, dy = (double)py;
+  cx0 = gm_cell((dx - rp - G.x0) * G.ix, G.gx);
+  cx1 = gm_cell((dx + rp - G.x0) * G.ix, G.gx);
+  cy0 = gm_cell((dy - rp - G.y0) * G.iy, G.gy);
+  cy1 = gm_cell((dy + rp - G.y0) * G.iy, G.gy);
+  return true;
+}
 
 // The work list: item0[p] = first (pair, 64-row group) item of pair p.  A pair over max_pts on either side gets
 // num_found -1 and no items, a pair with an empty side 0 and no items.
@@ -379,12 +395,7 @@ __global__ __launch_bounds__(64) void guided_match_kernel(GmArgs A)
     }
     // the cells of fl(px - r') .. fl(px + r') (an empty range for an inactive row or a non-finite projection)
     int cx0 = 0, cx1 = -1, cy = 0, cy1 = -1, pos = 0, end = 0;
-    if (active && gm_finite(px) && gm_finite(py)) {
-      const double dx = (double)px, dy = (double)py;
-      cx0 = gm_cell((dx - A.rp - G.x0) * G.ix, G.gx);
-      cx1 = gm_cell((dx + A.rp - G.x0) * G.ix, G.gx);
-      cy = gm_cell((dy - A.rp - G.y0) * G.iy, G.gy);
-      cy1 = gm_cell((dy + A.rp - G.y0) * G.iy, G.gy);
+    if (active && gm_disc(G, px, py, A.rp, cx0, cx1, cy, cy1)) {
       pos = starts[cy * G.gx + cx0];
       end = starts[cy * G.gx + cx1 + 1];
     }
@@ -574,6 +585,55 @@ int launch_match_epipolar_batch(misift_ctx *ctx, int npairs, const int *h_pairs,
                                 const float *F, float radius, int max_pts, int *num_found)
 {
   return launch_gm(ctx, true, npairs, h_pairs, h_pair_d, h_distinct, nd, set1, set2, F, radius, max_pts, num_found);
+}
+
+// Test-only, host-only: the gate and the gather of misift_match_guided_batch as the device runs them (gm_make_grid,
+// gm_cell, gm_disc; the gate is the match kernel's, operation by operation).
+extern "C" int misift_test_guided_gather(const float *H9, const float *xy1, int n1, const float *xy2, int n2,
+                                         float radius, unsigned char *pass, unsigned char *visited, int *grid2)
+{
+  if (!H9 || n1 < 0 || n2 < 0 || (n1 > 0 && !xy1) || (n2 > 0 && !xy2) ||
+      (n1 > 0 && n2 > 0 && (!pass || !visited)) || !grid2 || !(radius > 0.0f)) {
+    misift_set_error("misift_test_guided_gather: invalid argument");
+    return MISIFT_EINVAL;
+  }
+  // the bin: bounding box of the finite positions, the grid, each record's cell (-1: left out)
+  float xmin = INFINITY, ymin = INFINITY, xmax = -INFINITY, ymax = -INFINITY;
+  for (int j = 0; j < n2; j++) {
+    const float x = xy2[2 * j], y = xy2[2 * j + 1];
+    if (gm_finite(x) && gm_finite(y)) {
+      xmin = fminf(xmin, x); xmax = fmaxf(xmax, x);
+      ymin = fminf(ymin, y); ymax = fmaxf(ymax, y);
+    }
+  }
+  const double rp = (double)radius * (1.0 + 1.0 / 1024) + 1e-20;
+  const float r2 = radius * radius;
+  const GmGrid G = gm_make_grid(xmin, xmax, ymin, ymax, rp, 0);
+  grid2[0] = G.gx;
+  grid2[1] = G.gy;
+  std::vector<int> ccx((size_t)n2, -1), ccy((size_t)n2, -1);
+  for (int j = 0; j < n2; j++) {
+    const float x = xy2[2 * j], y = xy2[2 * j + 1];
+    if (gm_finite(x) && gm_finite(y)) {
+      ccx[j] = gm_cell(((double)x - G.x0) * G.ix, G.gx);
+      ccy[j] = gm_cell(((double)y - G.y0) * G.iy, G.gy);
+    }
+  }
+  for (int i = 0; i < n1; i++) {
+    // projection, in MatchAll's order, no contraction
+    const float x = xy1[2 * i], y = xy1[2 * i + 1];
+    const float den = H9[6] * x + H9[7] * y + H9[8];
+    const float px = (H9[0] * x + H9[1] * y + H9[2]) / den;
+    const float py = (H9[3] * x + H9[4] * y + H9[5]) / den;
+    int cx0, cx1, cy0, cy1;
+    gm_disc(G, px, py, rp, cx0, cx1, cy0, cy1);
+    for (int j = 0; j < n2; j++) {
+      const float ddx = px - xy2[2 * j], ddy = py - xy2[2 * j + 1];
+      pass[(size_t)i * n2 + j] = ddx * ddx + ddy * ddy < r2 ? 1 : 0;
+      visited[(size_t)i * n2 + j] = ccx[j] >= cx0 && ccx[j] <= cx1 && ccy[j] >= cy0 && ccy[j] <= cy1 ? 1 : 0;
+    }
+  }
+  return MISIFT_OK;
 }
 
 // Test-only, host-only: the gate and the gather of misift_match_epipolar_batch as the device runs them

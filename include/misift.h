@@ -922,6 +922,14 @@ int misift_test_epipolar_gate(const float *F9, const float *xy1, int n1, const f
                               unsigned char *pass);
 int misift_test_epipolar_gather(const float *F9, const float *xy1, int n1, const float *xy2, int n2, float radius,
                                 unsigned char *visited, int *grid2);
+/* Test-only, host-only: the gate and the disc walk of misift_match_guided_batch, the walk compiled from the function
+ * the kernel calls.  H9: one homography; xy1, xy2 as above.  pass[i * n2 + j] = 1 iff record j is a candidate of row i
+ * (the projection in the contract's order, then ddx*ddx + ddy*ddy < fl(radius*radius)).  The cell grid of xy2 is built
+ * as the bin launch builds it (grid2[0..1] = cells per axis); visited[i * n2 + j] = 1 iff record j's cell lies in the
+ * cell rectangle row i walks (0 for a non-finite position, which no cell holds, and for a non-finite projection, which
+ * walks nothing).  The walk is conservative iff pass & ~visited is empty. */
+int misift_test_guided_gather(const float *H9, const float *xy1, int n1, const float *xy2, int n2, float radius,
+                              unsigned char *pass, unsigned char *visited, int *grid2);
 /* Test-only, host-only: misift_quantize_batch's rule on n floats, dst[i] = rule(src[i]).  And the work list
  * misift_match_batch_i8's plan kernel builds for pairs of n1[i] x n2[i] records on a chip of num_cus CUs: plan5[5i..5i+4] =
  * first work item, 128-row blocks, 32-column tiles, column chunks, tiles per chunk of pair i; *nitems, *chunks and
