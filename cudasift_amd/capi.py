@@ -107,6 +107,7 @@ SIGNATURES = {
     "misift_improve_homography_batch": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _f, _f, _f, _vp, _vp]),
     "misift_find_fundamental_batch": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _f, _f, _f, _vp, _vp]),
     "misift_score_fundamental_batch": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _i, _f, _f, _f, _vp, _vp]),
+    "misift_improve_fundamental_batch": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _f, _f, _f, _vp, _vp, _vp]),
     "misift_match_guided_batch": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _f, _i, _vp]),
     "misift_match_epipolar_batch": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _f, _i, _vp]),
     "misift_quantize_batch": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp]),
@@ -124,6 +125,9 @@ SIGNATURES = {
     "misift_test_fundamental_solve": (_i, [_vp, _vp, _vp]),
     "misift_test_fundamental_sampson": (_i, [_vp, _vp, _i, _vp, _vp]),
     "misift_test_fundamental_error": (_i, [_vp, _vp, _i, _vp]),
+    "misift_test_fundamental_refine": (_i, [_vp, _vp, _i, _vp, _f, _i, _vp, _vp, _vp]),
+    "misift_test_fundamental_refine_capacity": (_i, []),
+    "misift_test_fundamental_solve9": (_i, [_vp, _i, _vp, _vp]),
     "misift_test_epipolar_gate": (_i, [_vp, _vp, _i, _vp, _i, _f, _vp]),
     "misift_test_epipolar_gather": (_i, [_vp, _vp, _i, _vp, _i, _f, _vp, _vp]),
     "misift_test_guided_gather": (_i, [_vp, _vp, _i, _vp, _i, _f, _vp, _vp, _vp]),
@@ -691,6 +695,25 @@ class Context:
                                                    _dptr(counts), _dptr(offsets), stride, min_score, max_ambiguity,
                                                    thresh, _dptr(fundamental), _dptr(num_fit)),
               "misift_score_fundamental_batch")
+        return num_fit
+
+    def improve_fundamental_batch(self, frames, recs, nframes, counts, fundamental, offsets=None, stride=0,
+                                  num_fit=None, num_rounds=None, num_loops=5, min_score=0.85, max_ambiguity=0.95,
+                                  thresh=1.0):
+        """misift_improve_fundamental_batch: up to num_loops refits of fundamental[9i..9i+8] (device, e.g.
+        find_fundamental_batch's result, refined in place) over the records of frame frames[i] that pass the gates and lie
+        within thresh of it, each kept only if it loses no inlier; then match_error of every record of the frame under
+        the result, as score_fundamental_batch writes it (num_loops = 0 is that call).  num_fit[i] (device, nsel ints,
+        allocated here when None and returned) = the inliers of the result; num_rounds (device, nsel ints, optional) =
+        the refits kept.  Enqueued on the context stream."""
+        frames = np.ascontiguousarray(frames, np.int32).reshape(-1)
+        if num_fit is None:
+            num_fit = self.zeros(4 * max(len(frames), 1))
+        check(lib().misift_improve_fundamental_batch(self.h, len(frames), frames.ctypes.data, _dptr(recs), nframes,
+                                                     _dptr(counts), _dptr(offsets), stride, num_loops, min_score,
+                                                     max_ambiguity, thresh, _dptr(fundamental), _dptr(num_fit),
+                                                     _dptr(num_rounds)),
+              "misift_improve_fundamental_batch")
         return num_fit
 
     def match_guided_batch(self, pairs, recs1, nframes1, counts1, homography, radius, offsets1=None, stride1=0,

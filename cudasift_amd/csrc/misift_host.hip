@@ -2324,6 +2324,29 @@ extern "C" int misift_score_fundamental_batch(misift_ctx *ctx, int nsel, const i
   });
 }
 
+// Refits of each frame's F over its inliers, then match_error under the result: the epipolar counterpart of
+// misift_improve_homography_batch.
+extern "C" int misift_improve_fundamental_batch(misift_ctx *ctx, int nsel, const int *frames, void *d_recs, int nframes,
+                                                const int *d_counts, const int *d_offsets, int stride, int num_loops,
+                                                float min_score, float max_ambiguity, float thresh,
+                                                float *d_fundamental, int *d_num_fit, int *d_num_rounds)
+{
+  ARG_CHECK(ctx && nsel >= 0);
+  if (nsel == 0) return MISIFT_OK;
+  ARG_CHECK(frames && d_recs && d_counts && nframes > 0 && d_fundamental && d_num_fit);
+  BatchLayout set;
+  int rc = batch_layout(__func__, d_recs, d_counts, d_offsets, stride, &set);
+  if (rc) return rc;
+  ARG_CHECK(num_loops >= 0 && thresh > 0.0f);
+  rc = check_frames(__func__, nsel, frames, 1, nframes, 0);
+  if (rc) return rc;
+  RoctxRange range(__func__);
+  return run_batch(ctx, {{frames, sizeof(int) * (size_t)nsel}}, 0, [&](int *h_frames, void *) {
+    return launch_improve_fundamental_batch(ctx, nsel, h_frames, set, num_loops, min_score, max_ambiguity, thresh,
+                                            d_fundamental, d_num_fit, d_num_rounds);
+  });
+}
+
 // Homography- and epipolar-guided matching of many frame pairs in one stream-ordered call each: no host wait and no host
 // read of the counts.  The host lists: the pairs, each pair's index among the distinct set-2 frames, and those frames.
 // d_model: the pairs' homographies (epipolar false) or fundamental matrices (true).

@@ -419,7 +419,8 @@ int misift_match_pairs_batch(misift_ctx *ctx, int npairs, const int *pairs,
  *   - the scratch arena and the output buffers of a call must stay untouched until that batch is done: rotate >= K sets.
  *   - misift_match_batch, misift_match_pairs_batch, misift_quantize_batch, misift_match_batch_i8,
  *     misift_match_pairs_batch_i8, misift_find_homography_batch, misift_improve_homography_batch,
- *     misift_find_fundamental_batch, misift_score_fundamental_batch, misift_match_guided_batch,
+ *     misift_find_fundamental_batch, misift_score_fundamental_batch, misift_improve_fundamental_batch,
+ *     misift_match_guided_batch,
  *     misift_match_epipolar_batch, misift_link_tracks_batch and misift_export_tracks_batch (which run on the context
  *     stream) on a batch's packed
  *     records: make the context stream wait for that batch first
@@ -617,7 +618,8 @@ int misift_improve_homography_batch(misift_ctx *ctx, int nsel, const int *frames
  *     before anything is enqueued.  nsel == 0: nothing happens.
  *   - The calls return before the GPU work is done.  Ordering behind batches in flight (K > 1): as
  *     misift_find_homography_batch.
- *   - Out of scope: least-squares refinement over the inliers, rank-2 enforcement, essential-matrix or pose recovery. */
+ *   - Least-squares refinement over the inliers: misift_improve_fundamental_batch, below.  Out of scope: rank-2
+ *     enforcement, essential-matrix or pose recovery. */
 int misift_find_fundamental_batch(misift_ctx *ctx, int nsel, const int *frames, const unsigned *seeds,
                                   const void *d_recs, int nframes, const int *d_counts, const int *d_offsets,
                                   int stride, int max_pts, int num_loops, float min_score, float max_ambiguity,
@@ -627,6 +629,57 @@ int misift_score_fundamental_batch(misift_ctx *ctx, int nsel, const int *frames,
                                    void *d_recs, int nframes, const int *d_counts, const int *d_offsets, int stride,
                                    float min_score, float max_ambiguity, float thresh,
                                    const float *d_fundamental /* nsel x 9 */, int *d_num_fit /* nsel */);
+/* Refinement of batch fundamental matrices over their inliers (no reference counterpart): the epipolar counterpart of
+ * misift_improve_homography_batch.  Entry i refits d_fundamental[9i..9i+8] up to num_loops times over the records of
+ * frame frames[i] that pass the gate and currently lie within thresh, keeps a refit only if it loses no inlier, and then
+ * writes match_error of every record under the result.  In the chain: find -> improve -> misift_match_epipolar_batch ->
+ * improve (num_loops 0 or more) -> link.  Exactly as in misift_score_fundamental_batch: frames, layouts and count -1, the
+ * copied host list `frames` with no frame repeated, stream order on the context stream with no host synchronisation and
+ * no host read, ordering behind batches in flight, the convention (x2, y2, 1) . F . (x1, y1, 1)^T = 0, the gate
+ * score > min_score && ambiguity < max_ambiguity, and the arithmetic rules: fp32, every operation rounded, only
+ * + - * /, sqrtf and fabsf, no contraction, a comparison with a NaN is false.  No max_pts, no temp memory, one launch
+ * whatever nsel.  Only match_error, d_fundamental, d_num_fit and d_num_rounds are written.
+ *   Entry i has frame f and n = max(d_counts[f], 0) records.
+ *   - The sum of the call.  Every floating-point sum of a quantity v over a record set S within [0, n) is taken in this
+ *     order and no other: p[t], t < 256, starts at +0.0f and adds v(r) for the members r of S with r = t (mod 256), in
+ *     ascending r (records that are no members are skipped, they do not add zero); then for off = 128, 64, ..., 1:
+ *     p[t] = p[t] + p[t + off] for every t < off; the sum is p[0].
+ *   - Setup.  F = d_fundamental[9i..9i+8] as given, all nine entries.  With G the records that pass the gate, inl(F) = the
+ *     records of G with e*e < (thresh*thresh) * den (the inlier test of find, thresh*thresh rounded once on the host);
+ *     c = |inl(F)|, rounds = 0.
+ *   - Round, at most num_loops times:
+ *     1. S = inl(F).  c < 8: stop.
+ *     2. Normalise each of the two point sets over S: cx = SUM(x) / (float)c and cy likewise,
+ *        d = SUM(sqrtf(dx*dx + dy*dy)) with dx = x - cx and dy = y - cy, s = ((float)c * 1.41421354f) / d, coordinates
+ *        (x - cx) * s.
+ *     3. Moments.  With a = (u2 u1, u2 v1, u2, v2 u1, v2 v1, v2, u1, v1, 1) the row of a record as in find:
+ *        M[r][c'] = SUM(a[r] * a[c']) for r <= c' (45 sums), M[c'][r] = M[r][c'].
+ *     4. Solve.  Gaussian elimination with complete pivoting on the 9x9 M, eight steps, by the rules of find's solve: at
+ *        step k the pivot is the entry of rows k..8 x columns k..8 with the largest fabsf, searched row-major with a
+ *        strict '>' (the first maximum wins, a NaN never wins); rows and columns are swapped, row r > k becomes
+ *        row r - (A[r][k] / pivot) * row k.  The remaining free column gets 1; back-substitution of rows 7..0,
+ *        z[k] = -(sum over c > k, ascending, of A[k][c] * z[c]) / A[k][k]; the column permutation undone gives Fn, and
+ *        F' = T2^T . Fn . T1 with the expressions of find.  A pivot that is 0 or non-finite, or a non-finite entry of
+ *        F': stop, F is kept.  For a symmetric positive semi-definite M this is the algebraic least squares
+ *        min z^T M z with one component of z fixed to 1, and the pivoting leaves the best-determined component for
+ *        that role.
+ *     5. Accept.  c' = |inl(F')|.  c' >= c: F = F', c = c', rounds += 1.  Otherwise stop, F is kept.
+ *   - End.  For EVERY record r < n, match_error under the final F as misift_score_fundamental_batch writes it (+inf
+ *     where den > 0 is false, the quiet NaN 0x7fc00000 for a NaN).  d_fundamental[9i..9i+8] = F, d_num_fit[i] = c,
+ *     d_num_rounds[i] = rounds (d_num_rounds may be NULL).
+ *   - Consequences.  num_loops = 0 is misift_score_fundamental_batch, byte for byte.  Whatever num_loops is, the records
+ *     and d_num_fit equal what misift_score_fundamental_batch writes under the returned F.  d_num_fit is never below
+ *     the count of the start F.  An F of nine zeros, a frame with fewer than 8 inliers and a frame of count -1 leave F
+ *     as it was.
+ *   - NULL ctx, nsel < 0, a frame index outside [0, nframes), a repeated frame, NULL records, counts, d_fundamental or
+ *     d_num_fit, num_loops < 0, thresh NaN or <= 0, d_offsets NULL with a negative stride: MISIFT_EINVAL, before
+ *     anything is enqueued.  nsel == 0: nothing happens.
+ *   - Out of scope: rank-2 enforcement, a geometric (Sampson) cost, essential-matrix or pose recovery. */
+int misift_improve_fundamental_batch(misift_ctx *ctx, int nsel, const int *frames,
+                                     void *d_recs, int nframes, const int *d_counts, const int *d_offsets, int stride,
+                                     int num_loops, float min_score, float max_ambiguity, float thresh,
+                                     float *d_fundamental /* in/out, nsel x 9, row-major */,
+                                     int *d_num_fit /* nsel */, int *d_num_rounds /* nsel, may be NULL */);
 /* Homography-guided matching (no reference counterpart as an API: MatchAll, mainSift.cpp:95-147, does it as a host
  * diagnostic; the C++ drop-in headers, cudaSift.h, do not change): for each pair i = (f1, f2) = (pairs[2i], pairs[2i+1]),
  * every record of frame f1 of set 1 is matched only against the records of frame f2 of set 2 that lie within `radius`
@@ -912,6 +965,18 @@ int misift_test_fundamental_samples(unsigned seed, int num_valid, int num_loops,
 int misift_test_fundamental_solve(const float *xy, float *F9, int *valid);
 int misift_test_fundamental_sampson(const float *F9, const float *xy, int n, float *e2_out, float *den_out);
 int misift_test_fundamental_error(const float *e2, const float *den, int n, float *out);
+/* Test-only, host-only: the rounds of misift_improve_fundamental_batch on plain arrays, compiled from the function the
+ * kernel runs (the 256 slots of the call's sum one after another).  xy[4r..4r+3] = x1 y1 x2 y2 of record r < n, gate[r]
+ * != 0 iff it passes the gate; F9_in the start; F9_out, *num_fit and *num_rounds as the call returns them.  And the
+ * records of a frame the kernel stages on chip; a frame may hold more. */
+int misift_test_fundamental_refine(const float *xy, const unsigned char *gate, int n, const float *F9_in, float thresh,
+                                   int num_loops, float *F9_out, int *num_fit, int *num_rounds);
+int misift_test_fundamental_refine_capacity(void);
+/* Test-only, host-only: the eight elimination steps, the back-substitution and the permutation undone on the 9x9 matrix
+ * M81 (row-major): n9 = Fn, *valid = whether every pivot was non-zero and finite.  lanes = 0: the serial form, the
+ * template of the 8-point solve at nine rows; lanes = 1: the form the kernel spreads over 81 threads and the hook above
+ * runs, its lanes one after another.  Equal bits. */
+int misift_test_fundamental_solve9(const float *M81, int lanes, float *n9, int *valid);
 /* Test-only, host-only: the gate and the gather of misift_match_epipolar_batch, compiled from the same headers and
  * functions as the kernel.  xy1: n1 set-1 positions (x, y), xy2: n2 set-2 positions.  gate: pass[i * n2 + j] = 1 iff
  * record j is a candidate of row i under F9 and radius.  gather: builds the cell grid of xy2 as the bin launch does
