@@ -108,6 +108,7 @@ SIGNATURES = {
     "misift_find_fundamental_batch": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _f, _f, _f, _vp, _vp]),
     "misift_score_fundamental_batch": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _i, _f, _f, _f, _vp, _vp]),
     "misift_improve_fundamental_batch": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _f, _f, _f, _vp, _vp, _vp]),
+    "misift_recover_pose_batch": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _f, _f, _f, _vp, _vp, _vp, _vp, _vp]),
     "misift_match_guided_batch": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _f, _i, _vp]),
     "misift_match_epipolar_batch": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _f, _i, _vp]),
     "misift_quantize_batch": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp]),
@@ -128,6 +129,8 @@ SIGNATURES = {
     "misift_test_fundamental_refine": (_i, [_vp, _vp, _i, _vp, _f, _i, _vp, _vp, _vp]),
     "misift_test_fundamental_refine_capacity": (_i, []),
     "misift_test_fundamental_solve9": (_i, [_vp, _i, _vp, _vp]),
+    "misift_test_pose_decompose": (_i, [_vp, _vp, _vp, _vp]),
+    "misift_test_pose_vote": (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
     "misift_test_epipolar_gate": (_i, [_vp, _vp, _i, _vp, _i, _f, _vp]),
     "misift_test_epipolar_gather": (_i, [_vp, _vp, _i, _vp, _i, _f, _vp, _vp]),
     "misift_test_guided_gather": (_i, [_vp, _vp, _i, _vp, _i, _f, _vp, _vp, _vp]),
@@ -715,6 +718,30 @@ class Context:
                                                      _dptr(num_rounds)),
               "misift_improve_fundamental_batch")
         return num_fit
+
+    def recover_pose_batch(self, frames, intrinsics, recs, nframes, counts, fundamental, offsets=None, stride=0,
+                           pose=None, num_front=None, votes=None, xyz=None, min_score=0.85, max_ambiguity=0.95,
+                           thresh=1.0):
+        """misift_recover_pose_batch: the relative pose X2 = R X1 + t, |t| = 1, of frame frames[i] from
+        fundamental[9i..9i+8] (device, e.g. improve_fundamental_batch's result) and intrinsics[i] = fx1 fy1 cx1 cy1 fx2
+        fy2 cx2 cy2 (host, nsel x 8): the decomposition of E = K2^T F K1 that puts the most records that pass the gates
+        and lie within thresh of F in front of both cameras.  pose (device, nsel x 12 floats: R row-major, then t) and
+        num_front (device, nsel ints: the winner's vote) are allocated here when None and returned.  votes (device, nsel
+        x 4 ints) and xyz (device, 4 floats per record of `recs`, indexed like it: the point in camera 1 and its depth in
+        camera 2) are optional.  The records are not written.  Enqueued on the context stream."""
+        frames = np.ascontiguousarray(frames, np.int32).reshape(-1)
+        intrinsics = np.ascontiguousarray(intrinsics, np.float32).reshape(-1, 8)
+        assert len(intrinsics) == len(frames)
+        if pose is None:
+            pose = self.zeros(4 * 12 * max(len(frames), 1))
+        if num_front is None:
+            num_front = self.zeros(4 * max(len(frames), 1))
+        check(lib().misift_recover_pose_batch(self.h, len(frames), frames.ctypes.data, intrinsics.ctypes.data,
+                                              _dptr(recs), nframes, _dptr(counts), _dptr(offsets), stride, min_score,
+                                              max_ambiguity, thresh, _dptr(fundamental), _dptr(pose), _dptr(num_front),
+                                              _dptr(votes), _dptr(xyz)),
+              "misift_recover_pose_batch")
+        return pose, num_front
 
     def match_guided_batch(self, pairs, recs1, nframes1, counts1, homography, radius, offsets1=None, stride1=0,
                            recs2=None, nframes2=None, counts2=None, offsets2=None, stride2=None, max_pts=8192,

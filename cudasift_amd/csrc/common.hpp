@@ -604,6 +604,10 @@ int launch_score_fundamental_batch(misift_ctx *ctx, int nsel, const int *h_frame
 int launch_improve_fundamental_batch(misift_ctx *ctx, int nsel, const int *h_frames, const BatchLayout &set,
                                      int num_loops, float min_score, float max_ambiguity, float thresh, float *F,
                                      int *num_fit, int *num_rounds);
+// misift_recover_pose_batch (kernels_pose.hip): one launch, no temp; h_intrinsics: nsel x 8 behind the frames
+int launch_recover_pose_batch(misift_ctx *ctx, int nsel, const int *h_frames, const float *h_intrinsics,
+                              const BatchLayout &set, float min_score, float max_ambiguity, float thresh,
+                              const float *F, float *pose, int *num_front, int *votes, float *xyz);
 // misift_match_guided_batch (kernels_guided.hip): bin + match.  h_pair_d: the index of each pair's set-2 frame among
 // the nd distinct ones, h_distinct; temp from misift_ensure_tmp, sized from npairs, nd and max_pts only
 size_t match_guided_batch_tmp_bytes(int npairs, int nd, int max_pts);

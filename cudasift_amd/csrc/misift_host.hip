@@ -2347,6 +2347,43 @@ extern "C" int misift_improve_fundamental_batch(misift_ctx *ctx, int nsel, const
   });
 }
 
+// fx fy cx cy of both cameras: focal lengths finite and > 0, principal points finite
+static bool intrinsics_usable(const float *k)
+{
+  for (int c = 0; c < 8; c += 4) {
+    if (!(k[c] > 0.0f && k[c + 1] > 0.0f && std::isfinite(k[c]) && std::isfinite(k[c + 1]))) return false;
+    if (!(std::isfinite(k[c + 2]) && std::isfinite(k[c + 3]))) return false;
+  }
+  return true;
+}
+
+// The relative pose of each frame pair from its F and its intrinsics, and the two-view depth of every record: the pose
+// counterpart of misift_score_fundamental_batch.
+extern "C" int misift_recover_pose_batch(misift_ctx *ctx, int nsel, const int *frames, const float *intrinsics,
+                                         const void *d_recs, int nframes, const int *d_counts, const int *d_offsets,
+                                         int stride, float min_score, float max_ambiguity, float thresh,
+                                         const float *d_fundamental, float *d_pose, int *d_num_front, int *d_votes,
+                                         float *d_xyz)
+{
+  ARG_CHECK(ctx && nsel >= 0);
+  if (nsel == 0) return MISIFT_OK;
+  ARG_CHECK(frames && intrinsics && d_recs && d_counts && nframes > 0 && d_fundamental && d_pose && d_num_front);
+  BatchLayout set;
+  int rc = batch_layout(__func__, d_recs, d_counts, d_offsets, stride, &set);
+  if (rc) return rc;
+  ARG_CHECK(thresh > 0.0f);
+  rc = check_frames(__func__, nsel, frames, 1, nframes, 0);
+  if (rc) return rc;
+  for (int i = 0; i < nsel; i++) ARG_CHECK(intrinsics_usable(intrinsics + (size_t)8 * i));
+  RoctxRange range(__func__);
+  return run_batch(ctx, {{frames, sizeof(int) * (size_t)nsel}, {intrinsics, sizeof(float) * 8 * (size_t)nsel}}, 0,
+                   [&](int *h_frames, void *) {
+                     return launch_recover_pose_batch(ctx, nsel, h_frames, (const float *)(h_frames + nsel), set,
+                                                      min_score, max_ambiguity, thresh, d_fundamental, d_pose,
+                                                      d_num_front, d_votes, d_xyz);
+                   });
+}
+
 // Homography- and epipolar-guided matching of many frame pairs in one stream-ordered call each: no host wait and no host
 // read of the counts.  The host lists: the pairs, each pair's index among the distinct set-2 frames, and those frames.
 // d_model: the pairs' homographies (epipolar false) or fundamental matrices (true).

@@ -420,7 +420,7 @@ int misift_match_pairs_batch(misift_ctx *ctx, int npairs, const int *pairs,
  *   - misift_match_batch, misift_match_pairs_batch, misift_quantize_batch, misift_match_batch_i8,
  *     misift_match_pairs_batch_i8, misift_find_homography_batch, misift_improve_homography_batch,
  *     misift_find_fundamental_batch, misift_score_fundamental_batch, misift_improve_fundamental_batch,
- *     misift_match_guided_batch,
+ *     misift_recover_pose_batch, misift_match_guided_batch,
  *     misift_match_epipolar_batch, misift_link_tracks_batch and misift_export_tracks_batch (which run on the context
  *     stream) on a batch's packed
  *     records: make the context stream wait for that batch first
@@ -618,8 +618,8 @@ int misift_improve_homography_batch(misift_ctx *ctx, int nsel, const int *frames
  *     before anything is enqueued.  nsel == 0: nothing happens.
  *   - The calls return before the GPU work is done.  Ordering behind batches in flight (K > 1): as
  *     misift_find_homography_batch.
- *   - Least-squares refinement over the inliers: misift_improve_fundamental_batch, below.  Out of scope: rank-2
- *     enforcement, essential-matrix or pose recovery. */
+ *   - Least-squares refinement over the inliers: misift_improve_fundamental_batch, below; the relative pose of a pair
+ *     from its F: misift_recover_pose_batch, below.  Out of scope: rank-2 enforcement. */
 int misift_find_fundamental_batch(misift_ctx *ctx, int nsel, const int *frames, const unsigned *seeds,
                                   const void *d_recs, int nframes, const int *d_counts, const int *d_offsets,
                                   int stride, int max_pts, int num_loops, float min_score, float max_ambiguity,
@@ -674,12 +674,69 @@ int misift_score_fundamental_batch(misift_ctx *ctx, int nsel, const int *frames,
  *   - NULL ctx, nsel < 0, a frame index outside [0, nframes), a repeated frame, NULL records, counts, d_fundamental or
  *     d_num_fit, num_loops < 0, thresh NaN or <= 0, d_offsets NULL with a negative stride: MISIFT_EINVAL, before
  *     anything is enqueued.  nsel == 0: nothing happens.
- *   - Out of scope: rank-2 enforcement, a geometric (Sampson) cost, essential-matrix or pose recovery. */
+ *   - Out of scope: rank-2 enforcement, a geometric (Sampson) cost. */
 int misift_improve_fundamental_batch(misift_ctx *ctx, int nsel, const int *frames,
                                      void *d_recs, int nframes, const int *d_counts, const int *d_offsets, int stride,
                                      int num_loops, float min_score, float max_ambiguity, float thresh,
                                      float *d_fundamental /* in/out, nsel x 9, row-major */,
                                      int *d_num_fit /* nsel */, int *d_num_rounds /* nsel, may be NULL */);
+/* Relative camera pose per pair from batch fundamental matrices (no reference counterpart): the pose counterpart of
+ * misift_score_fundamental_batch.  Entry i turns d_fundamental[9i..9i+8] and the two cameras' intrinsics into the
+ * essential matrix, takes its four (R, t) decompositions, lets the inliers of frame frames[i] under F vote for the one
+ * that puts them in front of both cameras, and triangulates every record of the frame under the winner.  In the chain:
+ * find -> improve -> misift_match_epipolar_batch -> improve -> recover_pose -> link.  Exactly as in
+ * misift_score_fundamental_batch / misift_improve_fundamental_batch: frames, layouts and count -1, the copied host lists
+ * (`frames`, and `intrinsics` with it) with no frame repeated, stream order on the context stream with no host
+ * synchronisation and no host read, ordering behind batches in flight, the convention
+ * (x2, y2, 1) . F . (x1, y1, 1)^T = 0, the gate score > min_score && ambiguity < max_ambiguity and the inlier test
+ * e*e < (thresh*thresh) * den, the arithmetic rules (fp32, every operation rounded, only + - * /, sqrtf and fabsf, no
+ * contraction, a comparison with a NaN is false) and the MISIFT_EINVAL list, with d_pose and d_num_front the outputs that
+ * must not be NULL.  Two more cases are MISIFT_EINVAL, checked on the host before anything is enqueued: a NULL
+ * `intrinsics`, and an fx or fy that is not finite and > 0 or a cx or cy that is not finite.  d_recs is not written.  One
+ * launch whatever nsel, no temp memory.  The pose convention is X2 = R . X1 + t with |t| = 1: the scale of the scene is
+ * not observable from two views.
+ *   intrinsics[8i..8i+7] = fx1 fy1 cx1 cy1 fx2 fy2 cx2 cy2: K1 of the image that holds (x1, y1), K2 of the other.
+ *   Entry i has frame f and n = max(d_counts[f], 0) records.  Every sum of products is taken left to right as written.
+ *   1. E = K2^T . F . K1.  G[r][0] = F[r][0]*fx1, G[r][1] = F[r][1]*fy1, G[r][2] = (F[r][0]*cx1 + F[r][1]*cy1) + F[r][2];
+ *      E[0][c] = fx2*G[0][c], E[1][c] = fy2*G[1][c], E[2][c] = (cx2*G[0][c] + cy2*G[1][c]) + G[2][c].  m = the largest
+ *      fabsf of E.  The entry is INVALID if an entry of E is non-finite or m is 0.  Otherwise A = E / m entry by entry, and
+ *      V = I.
+ *   2. Six sweeps of one-sided Jacobi over the column pairs (0,1), (0,2), (1,2) in that order.  For a pair (p, q):
+ *      alpha = A.p . A.p, beta = A.q . A.q, gamma = A.p . A.q (three-term sums over the rows).  gamma == 0: no rotation.
+ *      Otherwise zeta = (beta - alpha) / (2*gamma), tau = 1 / (fabsf(zeta) + sqrtf(1 + zeta*zeta)), negated when
+ *      zeta < 0, c = 1 / sqrtf(1 + tau*tau), s = c*tau; new column p = c * old p - s * old q, new column q =
+ *      s * old p + c * old q, for A and V alike.  The count is fixed: there is no convergence test, every entry runs the
+ *      same instructions.
+ *   3. Bases.  w[j] = the squared norm of column j of A.  i1 = the index of the largest w, searched with a strict '>'
+ *      (the first maximum wins); i2 = the larger of the other two (again the first wins).  The entry is INVALID unless
+ *      w[i2] > 0.  u1 = A.i1 / sqrtf(w[i1]), u2 = A.i2 / sqrtf(w[i2]), u3 = u1 x u2; v1 = V.i1, v2 = V.i2, v3 = v1 x v2;
+ *      every component of a cross product is (a*b) - (c*d).  The null direction is never taken from the near-zero column,
+ *      and both bases are right-handed by construction.
+ *   4. Hypotheses k = 0..3.  Ra[r][c] = (u2[r]*v1[c] - u1[r]*v2[c]) + u3[r]*v3[c], Rb[r][c] = (u1[r]*v2[c] -
+ *      u2[r]*v1[c]) + u3[r]*v3[c]; R = Ra for k < 2, otherwise Rb; t = u3 for even k, -u3 for odd k.
+ *   5. Vote, over the records that pass the gate and the inlier test under F as given (inl(F) of improve).  For such a
+ *      record and a hypothesis: p1 = ((x1 - cx1) / fx1, (y1 - cy1) / fy1, 1) and p2 likewise from K2; a = R . p1 (each
+ *      row a three-term sum), n = a x p2, den = n . n, n1 = (p2 x t) . n, n2 = (a x t) . n.  The record is IN FRONT iff
+ *      den > 0 && n1 > 0 && n2 > 0.  n1 / den and n2 / den are the least-squares depths z1, z2 of z1 a - z2 p2 = -t; the
+ *      cross-product form keeps its digits at the parallax of neighbouring video frames, where aa*bb - ab*ab cancels.
+ *      votes[k] = the records in front under hypothesis k.
+ *   6. Pick: the largest vote at the smallest k.  d_pose[12i..12i+11] = its R, row-major, then its t; d_num_front[i] =
+ *      its vote; d_votes[4i..4i+3] = the four votes (d_votes may be NULL).  An INVALID entry gives twelve zeros, 0 and
+ *      four zeros.  A valid F with no inlier (count -1 and count 0 included) gives hypothesis 0 and 0.
+ *   7. d_xyz, when not NULL: for EVERY record r < n of the frame, the four floats at its global record index (the index it
+ *      has in d_recs) are (z1*p1x, z1*p1y, z1, z2) under the picked pose: the point in the frame of camera 1, and its
+ *      depth in camera 2.  The four are the quiet NaN 0x7fc00000 where den > 0 is false and for every record of an INVALID
+ *      entry; a single result that is a NaN is stored as 0x7fc00000 (see match_error above).  Negative depths are stored
+ *      as computed.  Records of frames that are not selected are not touched. */
+int misift_recover_pose_batch(misift_ctx *ctx, int nsel, const int *frames,
+                              const float *intrinsics /* host, nsel x 8: fx1 fy1 cx1 cy1 fx2 fy2 cx2 cy2, copied */,
+                              const void *d_recs, int nframes, const int *d_counts, const int *d_offsets, int stride,
+                              float min_score, float max_ambiguity, float thresh,
+                              const float *d_fundamental /* nsel x 9 */,
+                              float *d_pose      /* nsel x 12: R row-major, then t */,
+                              int   *d_num_front /* nsel */,
+                              int   *d_votes     /* nsel x 4, may be NULL */,
+                              float *d_xyz       /* 4 floats per record, indexed like d_recs, may be NULL */);
 /* Homography-guided matching (no reference counterpart as an API: MatchAll, mainSift.cpp:95-147, does it as a host
  * diagnostic; the C++ drop-in headers, cudaSift.h, do not change): for each pair i = (f1, f2) = (pairs[2i], pairs[2i+1]),
  * every record of frame f1 of set 1 is matched only against the records of frame f2 of set 2 that lie within `radius`
@@ -977,6 +1034,13 @@ int misift_test_fundamental_refine_capacity(void);
  * template of the 8-point solve at nine rows; lanes = 1: the form the kernel spreads over 81 threads and the hook above
  * runs, its lanes one after another.  Equal bits. */
 int misift_test_fundamental_solve9(const float *M81, int lanes, float *n9, int *valid);
+/* Test-only, host-only: steps 1-4 and steps 5 and 7 of misift_recover_pose_batch, compiled from the functions the kernel
+ * runs.  decompose: out48[12k..12k+11] = R and t of hypothesis k of F9 under K8 (fx1 fy1 cx1 cy1 fx2 fy2 cx2 cy2), and
+ * *valid = 1; an invalid entry gives 48 zeros and 0.  vote: for record r < n with xy[4r..4r+3] = x1 y1 x2 y2, under
+ * pose12 = R then t: front_out[r] = 1 iff it is in front, xyz_out[4r..4r+3] = what d_xyz gets. */
+int misift_test_pose_decompose(const float *F9, const float *K8, float *out48, int *valid);
+int misift_test_pose_vote(const float *pose12, const float *K8, const float *xy, int n, unsigned char *front_out,
+                          float *xyz_out);
 /* Test-only, host-only: the gate and the gather of misift_match_epipolar_batch, compiled from the same headers and
  * functions as the kernel.  xy1: n1 set-1 positions (x, y), xy2: n2 set-2 positions.  gate: pass[i * n2 + j] = 1 iff
  * record j is a candidate of row i under F9 and radius.  gather: builds the cell grid of xy2 as the bin launch does
