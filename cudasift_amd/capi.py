@@ -109,6 +109,8 @@ SIGNATURES = {
     "misift_score_fundamental_batch": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _i, _f, _f, _f, _vp, _vp]),
     "misift_improve_fundamental_batch": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _f, _f, _f, _vp, _vp, _vp]),
     "misift_recover_pose_batch": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _f, _f, _f, _vp, _vp, _vp, _vp, _vp]),
+    "misift_link_poses_batch": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _f, _f, _f, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i,
+                                     _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "misift_match_guided_batch": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _f, _i, _vp]),
     "misift_match_epipolar_batch": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _f, _i, _vp]),
     "misift_quantize_batch": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp]),
@@ -131,6 +133,9 @@ SIGNATURES = {
     "misift_test_fundamental_solve9": (_i, [_vp, _i, _vp, _vp]),
     "misift_test_pose_decompose": (_i, [_vp, _vp, _vp, _vp]),
     "misift_test_pose_vote": (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
+    "misift_test_posegraph_ratio": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _f, _f, _f, _i, _vp, _vp]),
+    "misift_test_posegraph_compose": (_i, [_i, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "misift_test_posegraph_capacity": (_i, [_i]),
     "misift_test_epipolar_gate": (_i, [_vp, _vp, _i, _vp, _i, _f, _vp]),
     "misift_test_epipolar_gather": (_i, [_vp, _vp, _i, _vp, _i, _f, _vp, _vp]),
     "misift_test_guided_gather": (_i, [_vp, _vp, _i, _vp, _i, _f, _vp, _vp, _vp]),
@@ -742,6 +747,40 @@ class Context:
                                               _dptr(votes), _dptr(xyz)),
               "misift_recover_pose_batch")
         return pose, num_front
+
+    def link_poses_batch(self, pairs, nimages, rows, row_counts, max_pts, pose, num_front, xyz, links, seed_pair,
+                         root_image, walk, min_common=8, link_ratio=None, link_common=None, pair_scale=None, cam=None,
+                         cam_pair=None, summary=None, min_score=0.85, max_ambiguity=0.95, max_error=float("inf")):
+        """misift_link_poses_batch: the pair poses of recover_pose_batch (pose, num_front, xyz for the rows of
+        match_pairs_batch, frame i = pair i) joined into one frame.  links (host, nlinks x 3: p, q, kind with 0 = CHAIN,
+        p's set-2 image is q's set-1 image, 1 = FAN, the same set-1 image) each get the lower median of the depth ratios of
+        their common points; the scales spread from seed_pair over the links in the order given; walk (host, pair
+        indices) places a camera X_i = R_i X_world + t_i per image from root_image on.  The six outputs (device:
+        link_ratio and link_common per link, pair_scale per pair, cam nimages x 12, cam_pair per image, summary 8 ints)
+        are allocated here when None and returned in that order.  Enqueued on the context stream."""
+        pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        links = np.ascontiguousarray(links, np.int32).reshape(-1, 3)
+        walk = np.ascontiguousarray(walk, np.int32).reshape(-1)
+        if link_ratio is None:
+            link_ratio = self.zeros(4 * max(len(links), 1))
+        if link_common is None:
+            link_common = self.zeros(4 * max(len(links), 1))
+        if pair_scale is None:
+            pair_scale = self.zeros(4 * max(len(pairs), 1))
+        if cam is None:
+            cam = self.zeros(4 * 12 * max(nimages, 1))
+        if cam_pair is None:
+            cam_pair = self.zeros(4 * max(nimages, 1))
+        if summary is None:
+            summary = self.zeros(4 * 8)
+        check(lib().misift_link_poses_batch(self.h, len(pairs), pairs.ctypes.data, nimages, _dptr(rows),
+                                            _dptr(row_counts), max_pts, min_score, max_ambiguity, max_error,
+                                            _dptr(pose), _dptr(num_front), _dptr(xyz), len(links), links.ctypes.data,
+                                            seed_pair, root_image, min_common, len(walk), walk.ctypes.data,
+                                            _dptr(link_ratio), _dptr(link_common), _dptr(pair_scale), _dptr(cam),
+                                            _dptr(cam_pair), _dptr(summary)),
+              "misift_link_poses_batch")
+        return link_ratio, link_common, pair_scale, cam, cam_pair, summary
 
     def match_guided_batch(self, pairs, recs1, nframes1, counts1, homography, radius, offsets1=None, stride1=0,
                            recs2=None, nframes2=None, counts2=None, offsets2=None, stride2=None, max_pts=8192,

@@ -630,6 +630,14 @@ int launch_export_tracks_batch(misift_ctx *ctx, const BatchLayout &set, int nfra
                                const int *d_track_len, const int *d_track_frames, int min_len, int consistent_only,
                                int max_tracks, int max_obs, int *d_track_offsets, int *d_track_root, void *d_obs,
                                int *d_record_obs, int *d_summary);
+// misift_link_poses_batch (kernels_posegraph.hip): two launches; temp from misift_ensure_tmp, sized from npairs, nlinks
+// and nwalk only.  h_lists: the links (nlinks x 3), the pairs (npairs x 2) and the walk (nwalk), in that order
+size_t link_poses_batch_tmp_bytes(int npairs, int nlinks, int nwalk);
+int launch_link_poses_batch(misift_ctx *ctx, int npairs, int nimages, int nlinks, int nwalk, const int *h_lists,
+                            const void *d_rows, const int *d_row_counts, int max_pts, float min_score,
+                            float max_ambiguity, float max_error, const float *d_pose, const int *d_num_front,
+                            const float *d_xyz, int seed_pair, int root_image, int min_common, float *d_link_ratio,
+                            int *d_link_common, float *d_pair_scale, float *d_cam, int *d_cam_pair, int *d_summary);
 int launch_test_exp2(misift_ctx *ctx, const float *x, float *out, int n);
 int launch_test_points_fn(misift_ctx *ctx, int fn, const float *x, const float *y, float *out, float *out2, int n);
 int launch_selftest(misift_ctx *ctx);

@@ -2526,6 +2526,44 @@ extern "C" int misift_link_tracks_batch(misift_ctx *ctx, int npairs, const int *
   });
 }
 
+// The pair poses of misift_recover_pose_batch joined into one frame: a relative scale per link, the scales propagated
+// from a seed pair, a camera per image along a walk.  The three host lists go to the pinned slot: links, pairs, walk.
+extern "C" int misift_link_poses_batch(misift_ctx *ctx, int npairs, const int *pairs, int nimages, const void *d_rows,
+                                       const int *d_row_counts, int max_pts, float min_score, float max_ambiguity,
+                                       float max_error, const float *d_pose, const int *d_num_front, const float *d_xyz,
+                                       int nlinks, const int *links, int seed_pair, int root_image, int min_common,
+                                       int nwalk, const int *walk, float *d_link_ratio, int *d_link_common,
+                                       float *d_pair_scale, float *d_cam, int *d_cam_pair, int *d_summary)
+{
+  ARG_CHECK(ctx && npairs >= 0 && nimages >= 1 && nlinks >= 0 && nwalk >= 0);
+  ARG_CHECK(root_image >= 0 && root_image < nimages && min_common >= 1 && max_pts >= 1);
+  ARG_CHECK(d_pair_scale && d_cam && d_cam_pair && d_summary);
+  ARG_CHECK(nlinks == 0 || (links && d_link_ratio && d_link_common));
+  ARG_CHECK(nwalk == 0 || walk);
+  ARG_CHECK(npairs == 0 || (pairs && d_rows && d_row_counts && d_pose && d_num_front && d_xyz));
+  ARG_CHECK(npairs == 0 || (seed_pair >= 0 && seed_pair < npairs));
+  ARG_CHECK(min_score == min_score && max_ambiguity == max_ambiguity);      // not NaN
+  ARG_CHECK(max_error > 0.0f);                                              // NaN fails too
+  for (int i = 0; i < 2 * npairs; i++) ARG_CHECK(pairs[i] >= 0 && pairs[i] < nimages);
+  for (int l = 0; l < nlinks; l++) {
+    const int p = links[3 * l], q = links[3 * l + 1], kind = links[3 * l + 2];
+    ARG_CHECK(p >= 0 && p < npairs && q >= 0 && q < npairs && (kind == 0 || kind == 1));
+    ARG_CHECK(kind == 0 ? pairs[2 * p + 1] == pairs[2 * q] : pairs[2 * p] == pairs[2 * q]);
+  }
+  for (int w = 0; w < nwalk; w++) ARG_CHECK(walk[w] >= 0 && walk[w] < npairs);
+  RoctxRange range(__func__);
+  static const int none[1] = {0};                                           // an empty list's slot is never read
+  return run_batch(ctx, {HostList{nlinks ? links : none, sizeof(int) * 3 * (size_t)nlinks},
+                         HostList{npairs ? pairs : none, sizeof(int) * 2 * (size_t)npairs},
+                         HostList{nwalk ? walk : none, sizeof(int) * (size_t)nwalk}, HostList{none, sizeof(none)}},
+                   0, [&](int *h_lists, void *) {
+                     return launch_link_poses_batch(ctx, npairs, nimages, nlinks, nwalk, h_lists, d_rows, d_row_counts,
+                                                    max_pts, min_score, max_ambiguity, max_error, d_pose, d_num_front,
+                                                    d_xyz, seed_pair, root_image, min_common, d_link_ratio,
+                                                    d_link_common, d_pair_scale, d_cam, d_cam_pair, d_summary);
+                   });
+}
+
 // The labels misift_link_tracks_batch wrote, turned into a compact array of tracks with their observations stored
 // contiguously: select and number the roots, prefix-sum their lengths, scatter the members in index order.  All on the
 // context stream, no host read.

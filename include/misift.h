@@ -420,7 +420,7 @@ int misift_match_pairs_batch(misift_ctx *ctx, int npairs, const int *pairs,
  *   - misift_match_batch, misift_match_pairs_batch, misift_quantize_batch, misift_match_batch_i8,
  *     misift_match_pairs_batch_i8, misift_find_homography_batch, misift_improve_homography_batch,
  *     misift_find_fundamental_batch, misift_score_fundamental_batch, misift_improve_fundamental_batch,
- *     misift_recover_pose_batch, misift_match_guided_batch,
+ *     misift_recover_pose_batch, misift_link_poses_batch, misift_match_guided_batch,
  *     misift_match_epipolar_batch, misift_link_tracks_batch and misift_export_tracks_batch (which run on the context
  *     stream) on a batch's packed
  *     records: make the context stream wait for that batch first
@@ -928,6 +928,77 @@ int misift_link_tracks_batch(misift_ctx *ctx, int npairs, const int *pairs /* ho
                              int *d_track, int *d_track_len, int *d_track_frames,
                              int *d_summary /* 8 ints */);
 
+/* Pair poses linked into one frame (no reference counterpart): the pose counterpart of misift_link_tracks_batch.
+ * misift_recover_pose_batch gives every pair its own (R, t) with |t| = 1 and depths in that pair's private unit.  Two
+ * pairs that share an image see a common point at ONE depth in the shared camera, in two units: the ratio of the two
+ * depths is the ratio of the two baselines.  This call takes a robust ratio per link of two pairs, propagates the scales
+ * from a seed pair, and composes the scaled poses along a walk into a camera per image, X_i = R_i . X_world + t_i.  In the
+ * chain: find -> improve -> misift_match_epipolar_batch -> improve -> recover_pose -> link_poses.
+ *   pairs, d_rows, d_row_counts and max_pts are those of misift_match_pairs_batch / misift_link_tracks_batch: pair p =
+ *   (pairs[2p], pairs[2p+1]), two image indices in [0, nimages); its row r is the record p * max_pts + r, indexed by the
+ *   set-1 record, and the row's `match` field is the set-2 record.  d_pose (npairs x 12), d_num_front (npairs) and d_xyz
+ *   (4 floats per row, indexed like the rows) are what misift_recover_pose_batch wrote for those rows with frame i = pair
+ *   i.  n(p) = min(max(d_row_counts[p], 0), max_pts) rows of pair p take part.
+ *   A row is ACCEPTED under the edge rule of misift_link_tracks_batch: match >= 0, score > min_score, ambiguity <
+ *   max_ambiguity and, when max_error is finite, match_error < max_error; with max_error = +inf match_error is not read.
+ *   A comparison with a NaN is false.
+ *   links[3l..3l+2] = (p, q, kind).  Kind 0, CHAIN: pairs[2p+1] == pairs[2q], p's set-2 image is q's set-1 image, and row
+ *   r of p points at row r' = match[r] of q.  Kind 1, FAN: pairs[2p] == pairs[2q], the pairs have the same set-1 image,
+ *   and r' = r.  Two pairs that share only their set-2 image would need an inverse map of the matches: out of scope.
+ *   The arithmetic is that of misift_recover_pose_batch: fp32, every operation rounded, only + - * /, no contraction,
+ *   every three-term sum taken left to right as written.
+ *   1. Ratio per link.  Row r < n(p) of link l is a SAMPLE iff 0 <= r' < n(q), both rows are accepted, z1 > 0 && z2 > 0
+ *      (components 2 and 3 of d_xyz) for both rows, and rho = zq / zp (one division) is finite and > 0, where zq = z1 of
+ *      row r' and zp = z2 of row r (CHAIN: the depth in the shared camera, in p's unit) or z1 of row r (FAN).  rho
+ *      estimates |T_p| / |T_q|.  c = the number of samples; d_link_common[l] = c; d_link_ratio[l] = the sample of rank
+ *      (c - 1) >> 1 in ascending order (the lower median; equal samples are equal bits, so ties need no rule) if c >=
+ *      min_common, otherwise 0.  The result is one of the samples: it depends on the sample set alone and is
+ *      byte-identical from run to run.  r' comes from device memory and is range-checked before it addresses anything.
+ *   2. Usable pairs and scales.  Pair p is USABLE iff d_num_front[p] > 0 and its twelve pose floats are finite.
+ *      scale[.] = 0; scale[seed_pair] = 1 if that pair is usable.  The links are taken ONCE each, in the order given.  A
+ *      link whose ratio is 0 or one of whose pairs is not usable is skipped.  Otherwise: scale[p] > 0 && scale[q] == 0:
+ *      scale[q] = scale[p] / rho; scale[q] > 0 && scale[p] == 0: scale[p] = scale[q] * rho; anything else: nothing.  A
+ *      result that is not finite and > 0 is left at 0.  The caller orders the links outwards from the seed: a link met
+ *      before either of its pairs has a scale is LOST, it is not visited again.  A cycle's closing link does nothing.
+ *   3. Cameras.  The root image gets the identity and t = 0, d_cam_pair[root_image] = -1.  Every other image starts
+ *      unset: twelve zeros and d_cam_pair = -2.  `walk` is visited once, in order.  For walk entry p = (a, b) with s =
+ *      scale[p] > 0, a != b and pose (R, t):  a set and b unset: R_b = R . R_a, t_b = (R . t_a) + s*t, d_cam_pair[b] = p;
+ *      b set and a unset: R_a = R^T . R_b, t_a = R^T . (t_b - s*t), d_cam_pair[a] = p; otherwise nothing (both set: the
+ *      first placement wins; a pair listed twice places nothing the second time).  Each entry of a product is
+ *      (m0*n0 + m1*n1) + m2*n2 over the summed index.  There is no re-orthonormalisation: drift is the caller's to
+ *      measure (DESIGN.md gives it for a chain of 64).  A NaN result is stored as 0x7fc00000.
+ *   - Outputs: d_link_ratio, d_link_common (nlinks each), d_pair_scale (npairs), d_cam (nimages x 12: R row-major, then
+ *     t), d_cam_pair (nimages), d_summary (8 ints): [0] links with c >= min_common, [1] pairs with scale > 0, [2] images
+ *     with a camera (the root included), [3] the smallest c among the links of [0], 0 if there is none, [4..7] = 0.
+ *     d_rows, d_pose, d_num_front and d_xyz are not written.
+ *   - NULL ctx; npairs, nlinks or nwalk < 0; nimages < 1; root_image outside [0, nimages); min_common < 1; max_pts < 1;
+ *     min_score or max_ambiguity NaN; max_error NaN or <= 0; NULL d_pair_scale, d_cam, d_cam_pair or d_summary; with
+ *     nlinks > 0 a NULL links, d_link_ratio or d_link_common; with nwalk > 0 a NULL walk; with npairs > 0 a NULL pairs,
+ *     d_rows, d_row_counts, d_pose, d_num_front or d_xyz, an image index outside [0, nimages) or seed_pair outside
+ *     [0, npairs); a link whose p or q is outside [0, npairs), whose kind is neither 0 nor 1 or whose image indices do
+ *     not agree with its kind; a walk entry outside [0, npairs): MISIFT_EINVAL, before anything is enqueued.  npairs ==
+ *     0 (seed_pair is then not looked at) and nlinks == 0 are no errors: the root, and with a usable seed whatever the
+ *     walk reaches through it, are placed.
+ *   - The call runs on the context stream and returns before the GPU work is done; the three host lists are copied; no
+ *     host synchronisation and no host read.  Ordering behind batches in flight (K > 1): as misift_match_batch.
+ *   - Two launches whatever the data: one 256-thread workgroup per link (a radix select over the 32 bits of rho, 8 bits
+ *     per pass) plus one that prepares step 2, then one wavefront for steps 2 and 3.  Temp memory is 12 bytes per link,
+ *     12 per pair and 4 per walk entry, plus 16, from the library's own allocator. */
+int misift_link_poses_batch(misift_ctx *ctx, int npairs, const int *pairs /* host, npairs x 2 */, int nimages,
+                            const void *d_rows, const int *d_row_counts, int max_pts,
+                            float min_score, float max_ambiguity, float max_error,
+                            const float *d_pose /* npairs x 12 */, const int *d_num_front /* npairs */,
+                            const float *d_xyz /* 4 floats per row */,
+                            int nlinks, const int *links /* host, nlinks x 3: p, q, kind */,
+                            int seed_pair, int root_image, int min_common,
+                            int nwalk, const int *walk /* host, nwalk pair indices */,
+                            float *d_link_ratio  /* nlinks */,
+                            int   *d_link_common /* nlinks */,
+                            float *d_pair_scale  /* npairs */,
+                            float *d_cam         /* nimages x 12 */,
+                            int   *d_cam_pair    /* nimages */,
+                            int   *d_summary     /* 8 ints */);
+
 /* The feature tracks of misift_link_tracks_batch as compact observation lists (no reference counterpart): the selected
  * tracks numbered in ascending order of their root, each with its observations (frame, record, xpos, ypos) stored
  * contiguously in ascending order of the global index, on the device.  It is the last call of the device-batch chain
@@ -1041,6 +1112,20 @@ int misift_test_fundamental_solve9(const float *M81, int lanes, float *n9, int *
 int misift_test_pose_decompose(const float *F9, const float *K8, float *out48, int *valid);
 int misift_test_pose_vote(const float *pose12, const float *K8, const float *xy, int n, unsigned char *front_out,
                           float *xyz_out);
+/* Test-only, host-only: step 1 of misift_link_poses_batch for one link and steps 2 and 3 for a whole graph, compiled from
+ * the functions the kernels run.  ratio: rows_p / rows_q are row 0 of the two pairs (host memory, 576-byte records),
+ * xyz_p / xyz_q their d_xyz rows, count_p / count_q their row counts as d_row_counts holds them; *ratio and *common = what
+ * d_link_ratio and d_link_common get (the median taken from a sorted copy).  compose: everything on the host, ratio = the
+ * links' d_link_ratio; pair_scale, cam and cam_pair as the call writes them, counts2 = summary [1] and [2].  capacity:
+ * which = 0: the rows of a link whose rho bits the ratio kernel stages on chip; which = 1: the words of lists and state
+ * (4 per link, 4 per pair, 1 per walk entry, 13 per image) up to which the second kernel works on chip. */
+int misift_test_posegraph_ratio(const void *rows_p, const float *xyz_p, int count_p, const void *rows_q,
+                                const float *xyz_q, int count_q, int max_pts, int kind, float min_score,
+                                float max_ambiguity, float max_error, int min_common, float *ratio, int *common);
+int misift_test_posegraph_compose(int npairs, const int *pairs, int nimages, const float *pose, const int *num_front,
+                                  int nlinks, const int *links, const float *ratio, int seed_pair, int root_image,
+                                  int nwalk, const int *walk, float *pair_scale, float *cam, int *cam_pair, int *counts2);
+int misift_test_posegraph_capacity(int which);
 /* Test-only, host-only: the gate and the gather of misift_match_epipolar_batch, compiled from the same headers and
  * functions as the kernel.  xy1: n1 set-1 positions (x, y), xy2: n2 set-2 positions.  gate: pass[i * n2 + j] = 1 iff
  * record j is a candidate of row i under F9 and radius.  gather: builds the cell grid of xy2 as the bin launch does
