@@ -120,6 +120,10 @@ SIGNATURES = {
     "misift_link_tracks_batch": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _f, _f, _f, _vp, _vp, _vp, _vp]),
     "misift_export_tracks_batch": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp,
                                         _vp]),
+    "misift_triangulate_tracks_batch": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp,
+                                             _vp]),
+    "misift_test_triangulate_track": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "misift_test_triangulate_capacity": (_i, []),
     "misift_test_quantize": (_i, [_vp, C.c_long, _vp]),
     "misift_test_match_i8_plan": (_i, [_i, _i, _vp, _vp, _vp, _ip, _ip, _ip]),
     "misift_test_libc_rand": (_i, [C.c_uint, _i, _vp]),
@@ -929,6 +933,37 @@ class Context:
                                                _dptr(track_offsets), _dptr(track_root), _dptr(obs), _dptr(record_obs),
                                                _dptr(summary)), "misift_export_tracks_batch")
         return track_offsets, track_root, obs, record_obs, summary
+
+    def triangulate_tracks_batch(self, max_tracks, max_obs, track_offsets, obs, export_summary, nimages, cam, cam_pair,
+                                 intrinsics, min_views=2, num_loops=5, points=None, point_views=None,
+                                 point_status=None, obs_error=True, summary=None):
+        """misift_triangulate_tracks_batch: one world point per track that export_tracks_batch wrote (track_offsets, obs,
+        export_summary: its outputs for max_tracks and max_obs) under the cameras of link_poses_batch (cam, cam_pair, for
+        nimages images; obs.frame is the image index) and intrinsics (host, nimages x 4: fx fy cx cy).  A linear start
+        over the views whose image has a camera, then up to num_loops Gauss-Newton steps on the reprojection error, each
+        kept only if it lowers it.  points (max_tracks x 4 floats: X Y Z in the world frame, rms reprojection error in
+        px), point_views and point_status (max_tracks ints: the views used; 0 ok, 1 fewer than min_views, 2 singular, 3
+        behind a camera, 4 a bad range), obs_error (max_obs floats: each observation's residual in px; True allocates
+        it, None leaves it out) and summary (8 ints) are device buffers, allocated here when not passed; returns the
+        five.  Enqueued on the context stream."""
+        intrinsics = np.ascontiguousarray(intrinsics, np.float32).reshape(-1, 4)
+        assert len(intrinsics) == nimages
+        if points is None:
+            points = self.zeros(16 * max(max_tracks, 1))
+        if point_views is None:
+            point_views = self.zeros(4 * max(max_tracks, 1))
+        if point_status is None:
+            point_status = self.zeros(4 * max(max_tracks, 1))
+        if obs_error is True:
+            obs_error = self.zeros(4 * max(max_obs, 1))
+        if summary is None:
+            summary = self.zeros(4 * 8)
+        check(lib().misift_triangulate_tracks_batch(self.h, max_tracks, max_obs, _dptr(track_offsets), _dptr(obs),
+                                                    _dptr(export_summary), nimages, _dptr(cam), _dptr(cam_pair),
+                                                    intrinsics.ctypes.data, min_views, num_loops, _dptr(points),
+                                                    _dptr(point_views), _dptr(point_status), _dptr(obs_error),
+                                                    _dptr(summary)), "misift_triangulate_tracks_batch")
+        return points, point_views, point_status, obs_error, summary
 
     def match_split(self, pts1, n1, pts2, n2, own_tile_begin, own_tile_end):
         """Test hook: misift_match with the column sweep cut into two launches (the sharded matcher's cut)."""

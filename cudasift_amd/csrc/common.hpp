@@ -638,6 +638,14 @@ int launch_link_poses_batch(misift_ctx *ctx, int npairs, int nimages, int nlinks
                             float max_ambiguity, float max_error, const float *d_pose, const int *d_num_front,
                             const float *d_xyz, int seed_pair, int root_image, int min_common, float *d_link_ratio,
                             int *d_link_common, float *d_pair_scale, float *d_cam, int *d_cam_pair, int *d_summary);
+// misift_triangulate_tracks_batch (kernels_triangulate.hip): one memset + one launch; h_intrinsics: nimages x 4.  Temp
+// from misift_ensure_tmp only beyond the staging capacity, sized from nimages only (a device copy of the intrinsics)
+size_t triangulate_tracks_batch_tmp_bytes(int nimages);
+int launch_triangulate_tracks_batch(misift_ctx *ctx, int max_tracks, int max_obs, const int *d_track_offsets,
+                                    const void *d_obs, const int *d_export_summary, int nimages, const float *d_cam,
+                                    const int *d_cam_pair, const float *h_intrinsics, int min_views, int num_loops,
+                                    float *d_points, int *d_point_views, int *d_point_status, float *d_obs_error,
+                                    int *d_summary);
 int launch_test_exp2(misift_ctx *ctx, const float *x, float *out, int n);
 int launch_test_points_fn(misift_ctx *ctx, int fn, const float *x, const float *y, float *out, float *out2, int n);
 int launch_selftest(misift_ctx *ctx);

@@ -2347,10 +2347,10 @@ extern "C" int misift_improve_fundamental_batch(misift_ctx *ctx, int nsel, const
   });
 }
 
-// fx fy cx cy of both cameras: focal lengths finite and > 0, principal points finite
-static bool intrinsics_usable(const float *k)
+// fx fy cx cy of `cameras` cameras: focal lengths finite and > 0, principal points finite
+static bool intrinsics_usable(const float *k, int cameras = 2)
 {
-  for (int c = 0; c < 8; c += 4) {
+  for (int c = 0; c < 4 * cameras; c += 4) {
     if (!(k[c] > 0.0f && k[c + 1] > 0.0f && std::isfinite(k[c]) && std::isfinite(k[c + 1]))) return false;
     if (!(std::isfinite(k[c + 2]) && std::isfinite(k[c + 3]))) return false;
   }
@@ -2588,6 +2588,28 @@ extern "C" int misift_export_tracks_batch(misift_ctx *ctx, const void *d_recs, i
     return launch_export_tracks_batch(ctx, set, nframes, max_records, d_track, d_track_len, d_track_frames, min_len,
                                       consistent_only, max_tracks, max_obs, d_track_offsets, d_track_root, d_obs,
                                       d_record_obs, d_summary);
+  });
+}
+
+// One world point per exported track under the cameras of misift_link_poses_batch: the call that joins the track chain
+// to the pose chain.  The intrinsics go to the pinned slot.
+extern "C" int misift_triangulate_tracks_batch(misift_ctx *ctx, int max_tracks, int max_obs, const int *d_track_offsets,
+                                               const misift_track_obs *d_obs, const int *d_export_summary, int nimages,
+                                               const float *d_cam, const int *d_cam_pair, const float *intrinsics,
+                                               int min_views, int num_loops, float *d_points, int *d_point_views,
+                                               int *d_point_status, float *d_obs_error, int *d_summary)
+{
+  ARG_CHECK(ctx && max_tracks >= 1 && max_obs >= 1 && nimages >= 1);
+  ARG_CHECK(d_track_offsets && d_obs && d_export_summary && d_cam && d_cam_pair && intrinsics);
+  ARG_CHECK(d_points && d_point_views && d_point_status && d_summary);
+  ARG_CHECK(((uintptr_t)d_obs & 15) == 0);
+  ARG_CHECK(min_views >= 2 && num_loops >= 0);
+  for (int i = 0; i < nimages; i++) ARG_CHECK(intrinsics_usable(intrinsics + 4 * (size_t)i, 1));
+  RoctxRange range(__func__);
+  return run_batch(ctx, {{intrinsics, sizeof(float) * 4 * (size_t)nimages}}, 0, [&](int *h_lists, void *) {
+    return launch_triangulate_tracks_batch(ctx, max_tracks, max_obs, d_track_offsets, d_obs, d_export_summary, nimages,
+                                           d_cam, d_cam_pair, reinterpret_cast<const float *>(h_lists), min_views,
+                                           num_loops, d_points, d_point_views, d_point_status, d_obs_error, d_summary);
   });
 }
 

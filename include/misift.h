@@ -421,8 +421,8 @@ int misift_match_pairs_batch(misift_ctx *ctx, int npairs, const int *pairs,
  *     misift_match_pairs_batch_i8, misift_find_homography_batch, misift_improve_homography_batch,
  *     misift_find_fundamental_batch, misift_score_fundamental_batch, misift_improve_fundamental_batch,
  *     misift_recover_pose_batch, misift_link_poses_batch, misift_match_guided_batch,
- *     misift_match_epipolar_batch, misift_link_tracks_batch and misift_export_tracks_batch (which run on the context
- *     stream) on a batch's packed
+ *     misift_match_epipolar_batch, misift_link_tracks_batch, misift_export_tracks_batch and
+ *     misift_triangulate_tracks_batch (which run on the context stream) on a batch's packed
  *     records: make the context stream wait for that batch first
  *     (misift_ctx_wait_batch(ctx, <the context's stream>), or an event from misift_ctx_record_batch).
  * K = 1 (default) is the plain in-order context.  Also MISIFT_BATCHES_IN_FLIGHT at context creation.  Changing K drains
@@ -1055,6 +1055,77 @@ int misift_export_tracks_batch(misift_ctx *ctx,
                                int *d_record_obs,           /* max_records ints, may be NULL */
                                int *d_summary);             /* 8 ints */
 
+/* The exported tracks triangulated under the linked cameras (no reference counterpart): the call that joins the track
+ * chain (... -> link_tracks -> export_tracks) to the pose chain (... -> recover_pose -> link_poses).  For every track
+ * that misift_export_tracks_batch wrote, one world point from all of its views at once, refined on reprojection error,
+ * and each observation's residual.  d_xyz of misift_recover_pose_batch is two-view, per pair and in the pair's own unit
+ * and frame; d_points is N-view, in the frame and unit of d_cam.
+ *   d_track_offsets, d_obs and d_export_summary are what misift_export_tracks_batch wrote for max_tracks and max_obs;
+ *   obs.frame is the image index, so the batch's frames are the images of misift_link_poses_batch, whose d_cam
+ *   (X_i = R_i . X_world + t_i, R row-major, then t) and d_cam_pair (-2 = the image has no camera) are read as written.
+ *   intrinsics[4i..4i+3] = fx fy cx cy of image i.  obs.record is not read.
+ *   The arithmetic is that of misift_recover_pose_batch: fp32, every operation rounded, only + - * / and sqrtf, no
+ *   contraction, a comparison with a NaN is false.  Every sum over the observations runs in ascending k, starts at 0 and
+ *   adds one term at a time; everything else is taken left to right as written.
+ *   T = min(max(d_export_summary[2], 0), max_tracks), read on the device.  Entries at or beyond T of d_points,
+ *   d_point_views and d_point_status, and entries of d_obs_error that belong to no track t < T, stay untouched.
+ *   Track t < T has off = d_track_offsets[t] and end = d_track_offsets[t + 1], range-checked before they address
+ *   anything: unless 0 <= off <= end <= max_obs the track gets status 4, four quiet NaNs and 0 views, and nothing of
+ *   d_obs_error.  Otherwise its observations are o_k = d_obs[off + k], k < end - off.
+ *   1. Usable views.  o_k is USABLE iff its frame f lies in [0, nimages), d_cam_pair[f] != -2, the twelve floats of
+ *      d_cam[12f..] are finite, and x and y are finite.  m = the number of usable views; m < min_views: status 1.  Two
+ *      observations from one frame (an inconsistent track) are both used.  Only usable views enter steps 2 - 4.
+ *   2. Linear start.  With r0, r1, r2 the rows of R_f and (fx, fy, cx, cy) of image f: u = (x - cx) / fx, v =
+ *      (y - cy) / fy; the first row is a = r0 - u*r2 (per component) with rhs = u*t2 - t0, the second a = r1 - v*r2 with
+ *      rhs = v*t2 - t1.  Per row, in this order: M00 += a0*a0, M01 += a0*a1, M02 += a0*a2, M11 += a1*a1, M12 += a1*a2,
+ *      M22 += a2*a2, g0 += a0*rhs, g1 += a1*rhs, g2 += a2*rhs; the u row before the v row.  SOLVE (M, g) -> X by LDL^T
+ *      without pivoting: d0 = M00; l10 = M01/d0, l20 = M02/d0; d1 = M11 - l10*M01; e = M12 - l20*M01, l21 = e/d1;
+ *      d2 = (M22 - l20*M02) - l21*e; y0 = g0, y1 = g1 - l10*y0, y2 = (g2 - l20*y0) - l21*y1; X2 = y2/d2,
+ *      X1 = y1/d1 - l21*X2, X0 = (y0/d0 - l10*X1) - l20*X2.  The solve FAILS at the first pivot d0, d1, d2 that is not
+ *      finite and > 0 (nothing is divided by it), or when a component of X is not finite.  A failed solve here: status 2.
+ *   3. Residuals under X.  Per usable view: Xc.x = ((r00*X0 + r01*X1) + r02*X2) + t0, Xc.y and Xc.z likewise from r1, t1
+ *      and r2, t2.  If Xc.z > 0 is false for a view, the point is NOT IN FRONT; after the linear start that is status 3.
+ *      iz = 1/Xc.z, a = Xc.x*iz, b = Xc.y*iz; ru = x - (fx*a + cx), rv = y - (fy*b + cy); c += (ru*ru + rv*rv);
+ *      Ju = (fx*iz) * (r0 - a*r2), Jv = (fy*iz) * (r1 - b*r2), per component; M and g take the row Ju with rhs ru, then
+ *      the row Jv with rhs rv, as in step 2.
+ *   4. Gauss-Newton, num_loops times at the most: SOLVE (M, g) -> delta; X' = X + delta per component; step 3 under X'
+ *      gives c', M', g'.  X' is kept (with c', M', g') iff the solve did not fail, every usable view is in front under X'
+ *      and c' < c; otherwise the loop ends there: "kept only if not worse", as misift_improve_fundamental_batch.
+ *      num_loops = 0 gives the linear start.
+ *   5. Outputs.  Status 0: d_points[4t..4t+3] = X0, X1, X2, sqrtf(c / (float)m), the rms reprojection error in pixels;
+ *      d_point_views[t] = m; d_obs_error[off + k] = sqrtf(ru*ru + rv*rv) under the final X for a usable view, the quiet
+ *      NaN 0x7fc00000 for any other.  Status 1, 2, 3: four quiet NaNs, d_point_views[t] = m, and the NaN for all of the
+ *      track's d_obs_error.  d_point_status[t] = the status.  A single result that is a NaN is stored as 0x7fc00000.
+ *      d_summary (8 ints, integer sums, so deterministic): [0] T, [1] tracks with status 0, [2] their usable views,
+ *      [3] tracks with status 1, [4] with status 2, [5] with status 3, [6] Gauss-Newton steps kept, [7] tracks with
+ *      status 4.
+ *   - Not done here: no view is rejected as an outlier (gate on d_obs_error and call again, or leave it to the bundle
+ *     adjustment), the cameras are not adjusted, and d_cam is used as it is, without re-orthonormalising its rotations.
+ *   - NULL ctx; max_tracks, max_obs or nimages < 1; NULL d_track_offsets, d_obs, d_export_summary, d_cam, d_cam_pair,
+ *     intrinsics, d_points, d_point_views, d_point_status or d_summary; d_obs not 16-byte aligned; min_views < 2;
+ *     num_loops < 0; an fx or fy that is not finite and > 0 or a cx or cy that is not finite: MISIFT_EINVAL, before
+ *     anything is enqueued.  d_obs_error may be NULL.  None of the inputs is written.
+ *   - The call runs on the context stream and returns before the GPU work is done; `intrinsics` is copied; no host
+ *     synchronisation and no host read.  Ordering behind batches in flight (K > 1): as misift_match_batch.
+ *   - One memset and one launch whatever the data: one lane per track, the grid sized from max_tracks.  The cameras and
+ *     intrinsics are held on chip for up to 512 images; beyond that they are read from device memory, the intrinsics
+ *     from a copy in 16 bytes per image of temp memory from the library's own allocator. */
+int misift_triangulate_tracks_batch(misift_ctx *ctx,
+                                    int max_tracks, int max_obs,
+                                    const int *d_track_offsets,     /* max_tracks + 1, from export */
+                                    const misift_track_obs *d_obs,  /* max_obs, from export, 16-byte aligned */
+                                    const int *d_export_summary,    /* 8 ints, from export: [2] = T */
+                                    int nimages,
+                                    const float *d_cam,             /* nimages x 12, from link_poses */
+                                    const int *d_cam_pair,          /* nimages, from link_poses */
+                                    const float *intrinsics,        /* host, nimages x 4: fx fy cx cy, copied */
+                                    int min_views, int num_loops,
+                                    float *d_points,                /* max_tracks x 4: X Y Z, rms error in px */
+                                    int   *d_point_views,           /* max_tracks */
+                                    int   *d_point_status,          /* max_tracks */
+                                    float *d_obs_error,             /* max_obs, may be NULL */
+                                    int   *d_summary);              /* 8 ints */
+
 /* cudaMallocManaged as used by the reference's MANAGEDMEM build flavour (cudaSiftH.cu:239-240): one pointer valid on
  * host and device (SiftData.m_data). */
 int misift_malloc_managed(size_t bytes, void **out);
@@ -1126,6 +1197,15 @@ int misift_test_posegraph_compose(int npairs, const int *pairs, int nimages, con
                                   int nlinks, const int *links, const float *ratio, int seed_pair, int root_image,
                                   int nwalk, const int *walk, float *pair_scale, float *cam, int *cam_pair, int *counts2);
 int misift_test_posegraph_capacity(int which);
+/* Test-only, host-only: steps 1-5 of misift_triangulate_tracks_batch for one track, compiled from the function a lane of
+ * the kernel runs.  cams (nimages x 12), cam_pair (nimages) and intrinsics (nimages x 4) on the host, obs the track's nobs
+ * observations; point4, *views, *status and obs_error (nobs floats, may be NULL) as the call writes them for a track
+ * whose range is valid, *gn_accepted = the Gauss-Newton steps kept.  capacity: the images whose cameras and intrinsics
+ * the kernel holds on chip; a call may have more. */
+int misift_test_triangulate_track(const float *cams, const int *cam_pair, const float *intrinsics, int nimages,
+                                  const misift_track_obs *obs, int nobs, int min_views, int num_loops, float *point4,
+                                  int *views, int *status, float *obs_error, int *gn_accepted);
+int misift_test_triangulate_capacity(void);
 /* Test-only, host-only: the gate and the gather of misift_match_epipolar_batch, compiled from the same headers and
  * functions as the kernel.  xy1: n1 set-1 positions (x, y), xy2: n2 set-2 positions.  gate: pass[i * n2 + j] = 1 iff
  * record j is a candidate of row i under F9 and radius.  gather: builds the cell grid of xy2 as the bin launch does
