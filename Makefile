@@ -18,7 +18,7 @@ HIPOBJS  := $(patsubst $(CSRC)/%.hip,$(BUILD)/%.o,$(HIPSRCS))
 all: cudasift_amd/libmisift.so cudasift_amd/libcudasift.so cudasift_amd/libcudasift_managed.so oracle dropin build/pmc_calib build/valu_rates build/scan_rates build/single_call
 
 $(BUILD)/%.o: $(CSRC)/%.hip $(CSRC)/common.hpp $(CSRC)/chain.hpp $(CSRC)/match_sweep.inc $(CSRC)/match_i8_sweep.inc \
-            $(CSRC)/homography_core.inc $(CSRC)/fundamental_core.hpp $(CSRC)/pose_core.hpp $(CSRC)/posegraph_core.hpp \
+            $(CSRC)/homography_core.inc $(CSRC)/ransac_batch.hpp $(CSRC)/fundamental_core.hpp $(CSRC)/pose_core.hpp $(CSRC)/posegraph_core.hpp \
             $(CSRC)/epipolar_core.hpp $(CSRC)/triangulate_core.hpp \
             $(CSRC)/libc_rand.hpp $(CSRC)/quantize_i8.hpp $(CSRC)/pair_plan.hpp $(CSRC)/pair_plan_body.inc include/misift.h
 	@mkdir -p $(BUILD)

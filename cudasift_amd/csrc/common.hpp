@@ -585,7 +585,6 @@ int launch_match_batch_i8(misift_ctx *ctx, PairOut mode, int npairs, const int *
 int launch_quantize_batch(misift_ctx *ctx, const BatchLayout &set, int nframes, int8_t *q);
 // misift_find_homography_batch / misift_improve_homography_batch (homography.hip); find takes its temp from
 // misift_ensure_tmp
-size_t find_homography_batch_tmp_bytes(int nsel, int max_pts, int num_loops);
 int launch_find_homography_batch(misift_ctx *ctx, int nsel, const int *h_frames, const unsigned *h_seeds,
                                  const BatchLayout &set, int max_pts, int num_loops, float min_score,
                                  float max_ambiguity, float thresh, float *H, int *num);
@@ -594,7 +593,6 @@ int launch_improve_homography_batch(misift_ctx *ctx, int nsel, const int *h_fram
                                     int *num_fit);
 // misift_find_fundamental_batch / misift_score_fundamental_batch (kernels_fundamental.hip); find takes its temp from
 // misift_ensure_tmp
-size_t find_fundamental_batch_tmp_bytes(int nsel, int max_pts, int num_loops);
 int launch_find_fundamental_batch(misift_ctx *ctx, int nsel, const int *h_frames, const unsigned *h_seeds,
                                   const BatchLayout &set, int max_pts, int num_loops, float min_score,
                                   float max_ambiguity, float thresh, float *F, int *num);

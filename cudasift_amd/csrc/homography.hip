@@ -19,6 +19,10 @@
 //            resident), ballot+popcount accumulate -> count[hyp].
 //   pick     one workgroup: first hypothesis with the largest count; 8 floats + count D2H.
 //
+// What the single call shares with the batch search (ransac_batch.hpp, second half of this file) is written once: the
+// gather (ransac_gather) and the pick (ransac_pick) are that header's functions, the inlier test is homography_inlier
+// below, and the solve is the HOMO_CORE_SOLVE fragment of homography_core.inc.
+//
 // Deviation: the reference counts inliers over numPts rounded up to 16
 // and so reads up to 15 uninitialised coordinates; here exactly numPts points are tested.
 #include <math.h>
@@ -27,11 +31,9 @@
 #include <vector>
 #include "common.hpp"
 #include "libc_rand.hpp"
+#include "ransac_batch.hpp"
 
 namespace {
-
-constexpr int OFF_XPOS = 0, OFF_YPOS = 1, OFF_SCORE = 6, OFF_AMBIG = 7, OFF_MXPOS = 9, OFF_MYPOS = 10;
-constexpr int PT_WORDS = (int)(sizeof(SiftPointD) / sizeof(float));
 
 __device__ __forceinline__ float mul_rz(float a, float b)
 {
@@ -43,16 +45,28 @@ __device__ __forceinline__ float mul_rz(float a, float b)
   return away ? __uint_as_float(__float_as_uint(p) - 1u) : p;
 }
 
+// The inlier test of TestHomographies (matching.cu:975-990) with its round-toward-zero products: hypothesis a on the
+// stored match (x1, y1) -> (x2, y2).
+__device__ __forceinline__ bool homography_inlier(const float (&a)[8], float x1, float y1, float x2, float y2,
+                                                  float thresh2)
+{
+  const float nomx = mul_rz(a[0], x1) + mul_rz(a[1], y1) + a[2];
+  const float nomy = mul_rz(a[3], x1) + mul_rz(a[4], y1) + a[5];
+  const float deno = mul_rz(a[6], x1) + mul_rz(a[7], y1) + 1.0f;
+  const float errx = mul_rz(x2, deno) - nomx;
+  const float erry = mul_rz(y2, deno) - nomy;
+  const float err2 = mul_rz(errx, errx) + mul_rz(erry, erry);
+  return err2 < mul_rz(thresh2, mul_rz(deno, deno));
+}
+
 // ---- gather: SoA coordinates + ordered compaction of the valid points -------------------------
 __global__ __launch_bounds__(1024) void homo_gather_kernel(const float *__restrict__ pts, int npts, int stride,
                                                              float min_score, float max_ambiguity,
                                                              float *__restrict__ coord, int *__restrict__ valid,
                                                              int *__restrict__ num_valid)
 {
-#define HOMO_CORE_GATHER
-#include "homography_core.inc"
-#undef HOMO_CORE_GATHER
-  if (tid == 0) *num_valid = base_s;
+  const int nv = ransac_gather(pts, npts, stride, min_score, max_ambiguity, coord, valid);
+  if (threadIdx.x == 0) *num_valid = nv;
 }
 
 // ---- solve: one lane per hypothesis -------------------------------------------------------------
@@ -142,9 +156,7 @@ __global__ __launch_bounds__(256) void homo_count_kernel(const float *__restrict
   for (int i = lane; i < npts; i += 64) {
     const float x1 = coord[0 * stride + i], y1 = coord[1 * stride + i];
     const float x2 = coord[2 * stride + i], y2 = coord[3 * stride + i];
-#define HOMO_CORE_INLIER
-#include "homography_core.inc"
-#undef HOMO_CORE_INLIER
+    cnt += homography_inlier(a, x1, y1, x2, y2, thresh2) ? 1 : 0;
   }
   for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
   if (lane == 0) counts[hyp] = cnt;
@@ -154,13 +166,11 @@ __global__ __launch_bounds__(256) void homo_count_kernel(const float *__restrict
 __global__ __launch_bounds__(1024) void homo_pick_kernel(const int *__restrict__ counts, const float *__restrict__ homo,
                                                            int num_loops, float *__restrict__ result)
 {
-#define HOMO_CORE_PICK
-#include "homography_core.inc"
-#undef HOMO_CORE_PICK
-  if (tid == 0) {
-    const int idx = 0x7fffffff - (int)(unsigned)(best & 0xffffffffull);
+  const unsigned long long best = ransac_pick(counts, num_loops);
+  if (threadIdx.x == 0) {
+    const int idx = ransac_pick_index(best);
     for (int k = 0; k < 8; k++) result[k] = homo[k * num_loops + idx];
-    reinterpret_cast<int *>(result)[8] = (int)(best >> 32);
+    reinterpret_cast<int *>(result)[8] = ransac_pick_count(best);
     reinterpret_cast<int *>(result)[9] = idx;
   }
 }
@@ -324,145 +334,46 @@ extern "C" int misift_improve_homography(misift_ctx *ctx, void *d_pts, int npts,
 // ------------------------------------------------------------------------------------------------------------------
 // Batches: misift_find_homography_batch / misift_improve_homography_batch.  Entry e works on frame frames[e] of a
 // device-resident record batch (counts and offsets read on the device) and writes result slot e; no host round trip.
-// Find, four launches whatever the number of entries (L = num_loops rounded up to 16):
-//   gather  one 1024-thread workgroup per entry: the gather of homo_gather_kernel into the entry's temp, then wave 0 draws
-//           the entry's L x 4 sample positions from libc rand() restated on the device (libc_rand.hpp), seeded with
-//           seeds[e]: the same draws as srand(seeds[e]) followed by the single call.  Entries with fewer than 8 records,
-//           fewer than 8 valid points, or more than max_pts records are marked done here.
-//   solve   one lane per (entry, hypothesis): the single call's solve; also zeroes the entry's counts.
-//   count   the hot path: one 64-lane workgroup per (entry, 64 hypotheses, 512-point chunk).  The chunk's coordinates
-//           are staged once in LDS and read by broadcast; each lane holds one hypothesis in registers and tests every
-//           point of the chunk with the single call's inlier test, then adds its count atomically (an integer sum, so
-//           the order of the chunks does not matter).
-//   pick    one 1024-thread workgroup per entry: the single call's pick -> H (H[8] = 1) and the count; identity H and
-//           0 (or -1 over max_pts) for the entries the gather marked done.
+// Find is the shared batch search of ransac_batch.hpp (gather + draw, solve, count, pick) with the model below: it works
+// over num_loops rounded up to 16, as the single call does, draws in the reference's order (the same draws as
+// srand(seeds[e]) followed by the single call), counts with the single call's inlier test over all records of the frame,
+// and gives the identity to the entries the gather marked done.  The solve is this file's: one lane per (entry,
+// hypothesis) runs the single call's solve.
 // Improve, one launch: one 64-lane workgroup per entry runs the single call's rounds on the frame's records in place.
 namespace {
 
-constexpr int HB_CHUNK = 512;                  // points per count workgroup (8 KiB of LDS)
-
-struct HbArgs {
-  BatchLayout set;
-  const int *frames;                           // pinned host copies of the caller's lists
-  const unsigned *seeds;
-  int max_pts, mp16, num_loops;                // mp16 = max_pts rounded up to 16; num_loops rounded up to 16
-  float min_score, max_ambiguity, thresh2;
-  // temp, per entry e: coord[4 x mp16] | valid[mp16] | sample[4 x L] | homo[8 x L] | hcount[L] | meta[2]
-  float *coord;
-  int *valid, *sample;
-  float *homo;
-  int *hcount, *meta;                          // meta[2e] = points to count (0: entry done), meta[2e+1] = its result
-  float *H;                                    // out: nsel x 9
-  int *num;                                    // out: nsel
+struct HomographyModel {
+  static constexpr int SAMPLE = 4, PARAMS = 8;
+  static constexpr bool COUNT_ALL = true;      // TestHomographies tests every record, valid or not
+  template <class Ring>
+  static __device__ __forceinline__ void draw(LibcRand<Ring> &g, const FastMod31 &fm, int (&p)[4])
+  {
+    homography_draw4(g, fm, p);
+  }
+  static __device__ __forceinline__ bool inlier(const float (&a)[8], float x1, float y1, float x2, float y2,
+                                                float thresh2)
+  {
+    return homography_inlier(a, x1, y1, x2, y2, thresh2);
+  }
+  static __device__ __forceinline__ float done(int k) { return k % 4 == 0 ? 1.0f : 0.0f; }      // the identity
+  static __device__ __forceinline__ void picked(float *H) { H[8] = 1.0f; }
 };
 
-__global__ __launch_bounds__(1024) void homo_batch_gather_kernel(HbArgs G)
-{
-  const int e = blockIdx.x;
-  const int f = G.frames[e];
-  const int n = G.set.counts[f];
-  if (n < 8 || n > G.max_pts) {                // matching.cu:1016-1017 (count -1 included); over max_pts: -1, nothing read
-    if (threadIdx.x == 0) { G.meta[2 * e] = 0; G.meta[2 * e + 1] = n > G.max_pts ? -1 : 0; }
-    return;
-  }
-  const float *pts = reinterpret_cast<const float *>(G.set.recs + G.set.base(f));
-  const int npts = n, stride = G.mp16;
-  const float min_score = G.min_score, max_ambiguity = G.max_ambiguity;
-  float *coord = G.coord + (size_t)e * 4 * G.mp16;
-  int *valid = G.valid + (size_t)e * G.mp16;
-#define HOMO_CORE_GATHER
-#include "homography_core.inc"
-#undef HOMO_CORE_GATHER
-  const int num_valid = base_s;
-  if (num_valid < 8) {
-    if (tid == 0) { G.meta[2 * e] = 0; G.meta[2 * e + 1] = 0; }
-    return;
-  }
-  if (tid < 64) {                              // wave 0: the entry's rand() stream, in the reference's draw order
-    const int L = G.num_loops;
-    int *sample = G.sample + (size_t)e * 4 * L;
-    LibcRand<LibcRandWaveRing> g;
-    g.seed(G.seeds[e]);
-    const FastMod31 fm((uint32_t)num_valid);
-    for (int loop = 0; loop < L; loop++) {
-      int p[4];
-      homography_draw4(g, fm, p);
-      if (tid == 0)
-        for (int k = 0; k < 4; k++) sample[k * L + loop] = p[k];
-    }
-    if (tid == 0) { G.meta[2 * e] = npts; G.meta[2 * e + 1] = 0; }
-  }
-}
-
-__global__ __launch_bounds__(64) void homo_batch_solve_kernel(HbArgs G, int hblocks)
+__global__ __launch_bounds__(64) void homo_batch_solve_kernel(RansacArgs G, int hblocks)
 {
   const int e = blockIdx.x / hblocks;
   const int idx = (blockIdx.x % hblocks) * 64 + threadIdx.x;
-  const int num_loops = G.num_loops;
-  if (G.meta[2 * e] == 0 || idx >= num_loops) return;
+  if (G.meta[RANSAC_META * e] == 0 || idx >= G.num_loops) return;
+  const int num_loops = G.lp;                  // the fragment's stride of sample and homo
   const float *coord = G.coord + (size_t)e * 4 * G.mp16;
   const int stride = G.mp16;
   const int *valid = G.valid + (size_t)e * G.mp16;
   const int *sample = G.sample + (size_t)e * 4 * num_loops;
-  float *homo = G.homo + (size_t)e * 8 * num_loops;
+  float *homo = G.hyp + (size_t)e * 8 * num_loops;
   G.hcount[(size_t)e * num_loops + idx] = 0;
 #define HOMO_CORE_SOLVE
 #include "homography_core.inc"
 #undef HOMO_CORE_SOLVE
-}
-
-__global__ __launch_bounds__(64) void homo_batch_count_kernel(HbArgs G, int hblocks, int chunks)
-{
-  __shared__ float4 s_pt[HB_CHUNK];
-  const int c = blockIdx.x % chunks, eh = blockIdx.x / chunks;
-  const int e = eh / hblocks, hb = eh % hblocks;
-  const int npts = G.meta[2 * e];
-  const int i0 = c * HB_CHUNK;
-  if (i0 >= npts) return;                      // beyond the frame, or an entry already done (npts 0)
-  const int n = min(HB_CHUNK, npts - i0);
-  const int L = G.num_loops, mp = G.mp16;
-  const float *coord = G.coord + (size_t)e * 4 * mp + i0;
-  for (int i = threadIdx.x; i < n; i += 64)
-    s_pt[i] = make_float4(coord[i], coord[mp + i], coord[2 * mp + i], coord[3 * mp + i]);
-  __syncthreads();
-  const int hyp = hb * 64 + threadIdx.x;
-  if (hyp >= L) return;
-  const float *homo = G.homo + (size_t)e * 8 * L;
-  float a[8];
-  for (int k = 0; k < 8; k++) a[k] = homo[k * L + hyp];
-  const float thresh2 = G.thresh2;
-  int cnt = 0;
-  for (int i = 0; i < n; i++) {
-    const float4 q = s_pt[i];
-    const float x1 = q.x, y1 = q.y, x2 = q.z, y2 = q.w;
-#define HOMO_CORE_INLIER
-#include "homography_core.inc"
-#undef HOMO_CORE_INLIER
-  }
-  atomicAdd(&G.hcount[(size_t)e * L + hyp], cnt);
-}
-
-__global__ __launch_bounds__(1024) void homo_batch_pick_kernel(HbArgs G)
-{
-  const int e = blockIdx.x;
-  float *H = G.H + (size_t)9 * e;
-  if (G.meta[2 * e] == 0) {                    // identity and 0, or -1 for a frame over max_pts
-    if (threadIdx.x < 9) H[threadIdx.x] = threadIdx.x % 4 == 0 ? 1.0f : 0.0f;
-    if (threadIdx.x == 0) G.num[e] = G.meta[2 * e + 1];
-    return;
-  }
-  const int num_loops = G.num_loops;
-  const int *counts = G.hcount + (size_t)e * num_loops;
-#define HOMO_CORE_PICK
-#include "homography_core.inc"
-#undef HOMO_CORE_PICK
-  if (tid == 0) {
-    const int idx = 0x7fffffff - (int)(unsigned)(best & 0xffffffffull);
-    const float *homo = G.homo + (size_t)e * 8 * num_loops;
-    for (int k = 0; k < 8; k++) H[k] = homo[k * num_loops + idx];
-    H[8] = 1.0f;
-    G.num[e] = (int)(best >> 32);
-  }
 }
 
 struct HbImproveArgs {
@@ -497,66 +408,19 @@ __global__ __launch_bounds__(64) void improve_homography_batch_kernel(HbImproveA
   }
 }
 
-size_t round16(size_t v) { return (v + 15) / 16 * 16; }
-
 }  // namespace
-
-size_t find_homography_batch_tmp_bytes(int nsel, int max_pts, int num_loops)
-{
-  const size_t mp = round16((size_t)max_pts), L = round16((size_t)num_loops);
-  return (size_t)nsel * (sizeof(float) * 4 * mp + sizeof(int) * mp + sizeof(int) * 4 * L + sizeof(float) * 8 * L +
-                         sizeof(int) * L + sizeof(int) * 2);
-}
 
 int launch_find_homography_batch(misift_ctx *ctx, int nsel, const int *h_frames, const unsigned *h_seeds,
                                  const BatchLayout &set, int max_pts, int num_loops, float min_score,
                                  float max_ambiguity, float thresh, float *H, int *num)
 {
-  HbArgs G;
-  G.set = set;
-  G.frames = h_frames; G.seeds = h_seeds;
-  G.max_pts = max_pts;
-  G.mp16 = (int)round16((size_t)max_pts);
-  G.num_loops = (int)round16((size_t)num_loops);
-  G.min_score = min_score; G.max_ambiguity = max_ambiguity; G.thresh2 = thresh * thresh;
-  const size_t mp = (size_t)G.mp16, L = (size_t)G.num_loops, ns = (size_t)nsel;
-  const int hblocks = (G.num_loops + 63) / 64, chunks = (int)((mp + HB_CHUNK - 1) / HB_CHUNK);
-  if ((long long)nsel * hblocks * chunks > 0x7fffffffLL) {
-    misift_set_error("misift_find_homography_batch: %d entries x %d loops x %d points is beyond one launch", nsel,
-                     num_loops, max_pts);
-    return MISIFT_EINVAL;
-  }
-  int rc = misift_ensure_tmp(ctx, find_homography_batch_tmp_bytes(nsel, max_pts, num_loops));
-  if (rc) return rc;
-  G.coord = reinterpret_cast<float *>(ctx->d_match_tmp);
-  G.valid = reinterpret_cast<int *>(G.coord + ns * 4 * mp);
-  G.sample = G.valid + ns * mp;
-  G.homo = reinterpret_cast<float *>(G.sample + ns * 4 * L);
-  G.hcount = reinterpret_cast<int *>(G.homo + ns * 8 * L);
-  G.meta = G.hcount + ns * L;
-  G.H = H; G.num = num;
-  {
-    LaunchScope ls(ctx, "homo_batch_gather");
-    hipLaunchKernelGGL(homo_batch_gather_kernel, dim3(nsel), dim3(1024), 0, ctx->stream, G);
-    rc = ls.finish();
-    if (rc) return rc;
-  }
-  {
-    LaunchScope ls(ctx, "homo_batch_solve");
-    hipLaunchKernelGGL(homo_batch_solve_kernel, dim3(nsel * hblocks), dim3(64), 0, ctx->stream, G, hblocks);
-    rc = ls.finish();
-    if (rc) return rc;
-  }
-  {
-    LaunchScope ls(ctx, "homo_batch_count");
-    hipLaunchKernelGGL(homo_batch_count_kernel, dim3(nsel * hblocks * chunks), dim3(64), 0, ctx->stream, G, hblocks,
-                       chunks);
-    rc = ls.finish();
-    if (rc) return rc;
-  }
-  LaunchScope ls(ctx, "homo_batch_pick");
-  hipLaunchKernelGGL(homo_batch_pick_kernel, dim3(nsel), dim3(1024), 0, ctx->stream, G);
-  return ls.finish();
+  const RansacNames names{"misift_find_homography_batch", "homo_batch_gather", "homo_batch_solve", "homo_batch_count",
+                          "homo_batch_pick"};
+  const RansacArgs G = ransac_args(h_frames, h_seeds, set, max_pts, ransac_round16(num_loops), min_score, max_ambiguity,
+                                   thresh, H, num);
+  return ransac_batch_run<HomographyModel>(ctx, names, nsel, G, [&](const RansacArgs &A, int hblocks) {
+    hipLaunchKernelGGL(homo_batch_solve_kernel, dim3(nsel * hblocks), dim3(64), 0, ctx->stream, A, hblocks);
+  });
 }
 
 int launch_improve_homography_batch(misift_ctx *ctx, int nsel, const int *h_frames, const BatchLayout &set,

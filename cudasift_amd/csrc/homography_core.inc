@@ -1,48 +1,15 @@
-// homography_core.inc — the arithmetic FindHomography and ImproveHomography share between the single-call kernels
-// (misift_find_homography, misift_improve_homography) and the batch kernels (misift_find_homography_batch,
-// misift_improve_homography_batch) in homography.hip.  Each inclusion defines exactly one of the HOMO_CORE_* macros and
-// gets that fragment, in place, inside a kernel body.
+// homography_core.inc — the two bodies that the single-call kernels (misift_find_homography,
+// misift_improve_homography) and the batch kernels (misift_find_homography_batch, misift_improve_homography_batch) of
+// homography.hip share as text: the hypothesis solve and the improve rounds.  Each inclusion defines exactly one of the
+// HOMO_CORE_* macros and gets that fragment, in place, inside a kernel body, with the variable names the fragment's
+// comment lists.  Everything else the kernels share is a function: the gather and the pick in ransac_batch.hpp, the
+// inlier test in homography.hip.
 //
-// Textual rather than inline functions: written as __forceinline__ functions, the single-call gather, solve, count and
-// improve kernels compiled into a different instruction stream (homo_solve_kernel 127 -> 90 VGPRs, 272 -> 560 bytes of
-// scratch); with the fragments their disassembly is unchanged.
+// Textual rather than inline functions: written as __forceinline__ functions, these two compiled into a different
+// instruction stream (homo_solve_kernel 127 -> 90 VGPRs, 272 -> 560 bytes of scratch); with the fragments their
+// disassembly is unchanged.
 
-#if defined(HOMO_CORE_GATHER)
-// One 1024-thread workgroup: SoA coordinates coord[k * stride + i] of the npts records at pts, and the ORDERED list of the
-// valid ones (ballot/popcount compaction keeps index order, which the rand() % numValid sampling depends on).  Expects pts,
-// npts, stride, min_score, max_ambiguity, coord, valid; leaves tid and base_s (LDS) = the number of valid points.
-  __shared__ int wave_cnt[16];
-  __shared__ int base_s;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (tid == 0) base_s = 0;
-  __syncthreads();
-  for (int i0 = 0; i0 < npts; i0 += 1024) {
-    const int i = i0 + tid;
-    bool ok = false;
-    if (i < npts) {
-      const float *p = pts + (size_t)i * PT_WORDS;
-      coord[0 * stride + i] = p[OFF_XPOS];
-      coord[1 * stride + i] = p[OFF_YPOS];
-      coord[2 * stride + i] = p[OFF_MXPOS];
-      coord[3 * stride + i] = p[OFF_MYPOS];
-      ok = p[OFF_SCORE] > min_score && p[OFF_AMBIG] < max_ambiguity;      // matching.cu:1035
-    }
-    const unsigned long long m = __ballot(ok);
-    if (lane == 0) wave_cnt[wave] = __popcll(m);
-    __syncthreads();
-    int off = base_s;
-    for (int w = 0; w < wave; w++) off += wave_cnt[w];
-    if (ok) valid[off + __popcll(m & ((1ull << lane) - 1ull))] = i;
-    __syncthreads();
-    if (tid == 0) {
-      int s = 0;
-      for (int w = 0; w < 16; w++) s += wave_cnt[w];
-      base_s += s;
-    }
-    __syncthreads();
-  }
-
-#elif defined(HOMO_CORE_SOLVE)
+#if defined(HOMO_CORE_SOLVE)
 // Hypothesis idx (one lane): the 4 points valid[sample[k * num_loops + idx]], A h = b by the 8x8 Crout LU (lu8) and the
 // inverse (lu8_unit_solve), h -> homo[r * num_loops + idx].  Expects coord, stride, valid, sample, num_loops, idx, homo.
   float m[8][8], inv[8][8], rhs[8], x[8];
@@ -69,37 +36,6 @@
     for (int k = 0; k < 8; k++) s = fmaf(inv[r][k], rhs[k], s);
     homo[r * num_loops + idx] = s;
   }
-
-#elif defined(HOMO_CORE_INLIER)
-// The inlier test of TestHomographies (matching.cu:975-990) with its round-toward-zero products.  Expects a[8] (the
-// hypothesis), x1, y1, x2, y2 (one stored match), thresh2, cnt; adds 1 to cnt for an inlier.
-    const float nomx = mul_rz(a[0], x1) + mul_rz(a[1], y1) + a[2];
-    const float nomy = mul_rz(a[3], x1) + mul_rz(a[4], y1) + a[5];
-    const float deno = mul_rz(a[6], x1) + mul_rz(a[7], y1) + 1.0f;
-    const float errx = mul_rz(x2, deno) - nomx;
-    const float erry = mul_rz(y2, deno) - nomy;
-    const float err2 = mul_rz(errx, errx) + mul_rz(erry, erry);
-    cnt += err2 < mul_rz(thresh2, mul_rz(deno, deno)) ? 1 : 0;
-
-#elif defined(HOMO_CORE_PICK)
-// One 1024-thread workgroup: the first hypothesis with the largest count (strict '>' scan of matching.cu:1063-1068).
-// Expects counts, num_loops; leaves tid and, in thread 0, best = count in the high word, (INT_MAX - index) in the low word
-// (the max key is the largest count at the smallest index).
-  __shared__ unsigned long long best_s[16];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  unsigned long long best = 0;
-  for (int i = tid; i < num_loops; i += 1024) {
-    const unsigned long long key = ((unsigned long long)(unsigned)counts[i] << 32) | (unsigned)(0x7fffffff - i);
-    best = key > best ? key : best;
-  }
-  for (int off = 32; off > 0; off >>= 1) {
-    const unsigned long long o = __shfl_xor(best, off, 64);
-    best = o > best ? o : best;
-  }
-  if (lane == 0) best_s[wave] = best;
-  __syncthreads();
-  if (tid == 0)
-    for (int w = 1; w < 16; w++) best = best_s[w] > best ? best_s[w] : best;
 
 #elif defined(HOMO_CORE_IMPROVE)
 // One 64-lane workgroup: P.num_loops rounds of ImproveHomography from the start P.a0 over the P.npts records at P.pts,

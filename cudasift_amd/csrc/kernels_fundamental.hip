@@ -1,25 +1,15 @@
 // kernels_fundamental.hip — misift_find_fundamental_batch / misift_score_fundamental_batch /
 // misift_improve_fundamental_batch: the epipolar counterpart of the homography batch calls (homography.hip).  Entry e
 // works on frame frames[e] of a device-resident record batch (counts and offsets read on the device) and writes result
-// slot e; no host round trip.  No reference counterpart: the
-// reference's only geometric model is the homography.  The arithmetic is fundamental_core.hpp, shared with the host-only
-// test hooks at the end of this file.
+// slot e; no host round trip.  No reference counterpart: the reference's only geometric model is the homography.  The
+// arithmetic is fundamental_core.hpp, shared with the host-only test hooks at the end of this file.
 //
-// Find, four launches whatever the number of entries (L = num_loops, Lp = L rounded up to 16):
-//   gather  one 1024-thread workgroup per entry: the gather of homo_gather_kernel (SoA coordinates, ordered list of the
-//           valid records) into the entry's temp, then wave 0 draws the entry's L x 8 sample positions from libc rand()
-//           restated on the device (libc_rand.hpp), seeded with seeds[e].  Entries with fewer than 8 records, fewer than
-//           8 valid records, or more than max_pts records are marked done here.
-//   solve   one lane per (entry, hypothesis): the normalised 8-point solve with complete pivoting; each lane's 8x9
-//           system lives in LDS (72 floats x 64 lanes = 18 KiB, word (r, c) of lane l at (9 r + c) * 64 + l: every
-//           access of a wavefront hits 64 consecutive words whatever rows and columns the lanes have pivoted to).  Also
-//           zeroes the entry's counts.
-//   count   the hot path: one 64-lane workgroup per (entry, 64 hypotheses, 512-point chunk of the VALID records).  The
-//           chunk's coordinates are staged once in LDS and read by broadcast; each lane holds one F in 9 registers and
-//           tests every point of the chunk, then adds its count atomically (an integer sum: the order of the chunks does
-//           not matter).
-//   pick    one 1024-thread workgroup per entry: the largest count at the smallest hypothesis index -> F and the count;
-//           nine zeros and 0 (or -1 over max_pts) for the entries the gather marked done.
+// Find is the shared batch search of ransac_batch.hpp (gather + draw, solve, count, pick) with the model below: it works
+// over exactly num_loops hypotheses of 8 positions each, counts with the Sampson test over the VALID records only, and
+// gives nine zeros to the entries the gather marked done.  The solve is this file's: one lane per (entry, hypothesis)
+// runs the normalised 8-point solve with complete pivoting; each lane's 8x9 system lives in LDS (72 floats x 64 lanes =
+// 18 KiB, word (r, c) of lane l at (9 r + c) * 64 + l: every access of a wavefront hits 64 consecutive words whatever
+// rows and columns the lanes have pivoted to).
 // Score, one launch: one 256-thread workgroup per entry writes match_error of every record of the frame and counts the
 // records that pass the gate and the inlier test.
 // Improve, one launch: one 256-thread workgroup per entry refits F over its inliers (fundamental_refine), then writes what
@@ -28,70 +18,28 @@
 #include "common.hpp"
 #include "fundamental_core.hpp"
 #include "libc_rand.hpp"
+#include "ransac_batch.hpp"
 
 namespace {
 
-// what HOMO_CORE_GATHER (homography_core.inc) reads of a record
-constexpr int OFF_XPOS = 0, OFF_YPOS = 1, OFF_SCORE = 6, OFF_AMBIG = 7, OFF_MXPOS = 9, OFF_MYPOS = 10;
-constexpr int PT_WORDS = (int)(sizeof(SiftPointD) / sizeof(float));
-
-constexpr int FB_CHUNK = 512;                  // valid points per count workgroup (8 KiB of LDS)
-constexpr int FB_META = 4;                     // ints of meta per entry
-
-struct FbArgs {
-  BatchLayout set;
-  const int *frames;                           // pinned host copies of the caller's lists
-  const unsigned *seeds;
-  int max_pts, mp16, num_loops, lp;            // mp16 = max_pts rounded up to 16; lp = num_loops rounded up to 16
-  float min_score, max_ambiguity, thresh2;
-  // temp, per entry e: coord[4 x mp16] | valid[mp16] | sample[8 x lp] | hyp[9 x lp] | hcount[lp] | meta[FB_META]
-  float *coord;
-  int *valid, *sample;
-  float *hyp;
-  int *hcount;
-  int *meta;                                   // [0] valid records to count (0: entry done), [1] its result, [2] records
-  float *F;                                    // out: nsel x 9
-  int *num;                                    // out: nsel
+struct FundamentalModel {
+  static constexpr int SAMPLE = 8, PARAMS = 9;
+  static constexpr bool COUNT_ALL = false;     // only the records that pass the gate vote
+  template <class Ring>
+  static __device__ __forceinline__ void draw(LibcRand<Ring> &g, const FastMod31 &fm, int (&p)[8])
+  {
+    fundamental_draw8(g, fm, p);
+  }
+  static __device__ __forceinline__ bool inlier(const float (&F)[9], float x1, float y1, float x2, float y2,
+                                                float thresh2)
+  {
+    float den;
+    const float e2 = fundamental_sampson(F, x1, y1, x2, y2, den);
+    return fundamental_inlier(e2, den, thresh2);
+  }
+  static __device__ __forceinline__ float done(int) { return 0.0f; }
+  static __device__ __forceinline__ void picked(float *) {}
 };
-
-__global__ __launch_bounds__(1024) void fund_batch_gather_kernel(FbArgs G)
-{
-  const int e = blockIdx.x;
-  const int f = G.frames[e];
-  const int n = G.set.counts[f];
-  int *meta = G.meta + (size_t)FB_META * e;
-  if (n < 8 || n > G.max_pts) {                // count -1 included; over max_pts: -1, nothing of the frame is read
-    if (threadIdx.x == 0) { meta[0] = 0; meta[1] = n > G.max_pts ? -1 : 0; meta[2] = 0; }
-    return;
-  }
-  const float *pts = reinterpret_cast<const float *>(G.set.recs + G.set.base(f));
-  const int npts = n, stride = G.mp16;
-  const float min_score = G.min_score, max_ambiguity = G.max_ambiguity;
-  float *coord = G.coord + (size_t)e * 4 * G.mp16;
-  int *valid = G.valid + (size_t)e * G.mp16;
-#define HOMO_CORE_GATHER
-#include "homography_core.inc"
-#undef HOMO_CORE_GATHER
-  const int num_valid = base_s;
-  if (num_valid < 8) {
-    if (tid == 0) { meta[0] = 0; meta[1] = 0; meta[2] = 0; }
-    return;
-  }
-  if (tid < 64) {                              // wave 0: the entry's rand() stream, hypotheses one after another
-    const int L = G.num_loops, lp = G.lp;
-    int *sample = G.sample + (size_t)e * 8 * lp;
-    LibcRand<LibcRandWaveRing> g;
-    g.seed(G.seeds[e]);
-    const FastMod31 fm((uint32_t)num_valid);
-    for (int loop = 0; loop < L; loop++) {
-      int p[8];
-      fundamental_draw8(g, fm, p);
-      if (tid == 0)
-        for (int k = 0; k < 8; k++) sample[k * lp + loop] = p[k];
-    }
-    if (tid == 0) { meta[0] = num_valid; meta[1] = 0; meta[2] = npts; }
-  }
-}
 
 // a lane's 8x9 system in LDS: word (r, c) at (9 r + c) * 64 from the lane's base
 struct FundamentalLdsMat {
@@ -100,12 +48,12 @@ struct FundamentalLdsMat {
   __device__ void set(int r, int c, float v) { base[(9 * r + c) * 64] = v; }
 };
 
-__global__ __launch_bounds__(64) void fund_batch_solve_kernel(FbArgs G, int hblocks)
+__global__ __launch_bounds__(64) void fund_batch_solve_kernel(RansacArgs G, int hblocks)
 {
   __shared__ float s_m[72 * 64];
   const int e = blockIdx.x / hblocks;
   const int idx = (blockIdx.x % hblocks) * 64 + threadIdx.x;
-  const int *meta = G.meta + (size_t)FB_META * e;
+  const int *meta = G.meta + (size_t)RANSAC_META * e;
   const int num_valid = meta[0], npts = meta[2];
   if (num_valid == 0 || idx >= G.num_loops) return;
   const int lp = G.lp, mp = G.mp16;
@@ -131,65 +79,6 @@ __global__ __launch_bounds__(64) void fund_batch_solve_kernel(FbArgs G, int hblo
   float *hyp = G.hyp + (size_t)e * 9 * lp;
 #pragma unroll
   for (int k = 0; k < 9; k++) hyp[k * lp + idx] = in_range ? F[k] : 0.0f;
-}
-
-__global__ __launch_bounds__(64) void fund_batch_count_kernel(FbArgs G, int hblocks, int chunks)
-{
-  __shared__ float4 s_pt[FB_CHUNK];
-  const int c = blockIdx.x % chunks, eh = blockIdx.x / chunks;
-  const int e = eh / hblocks, hb = eh % hblocks;
-  const int *meta = G.meta + (size_t)FB_META * e;
-  const int num_valid = min(meta[0], G.mp16), npts = meta[2];
-  const int i0 = c * FB_CHUNK;
-  if (i0 >= num_valid) return;                 // beyond the valid records, or an entry already done (0)
-  const int n = min(FB_CHUNK, num_valid - i0);
-  const int lp = G.lp, mp = G.mp16;
-  const float *coord = G.coord + (size_t)e * 4 * mp;
-  const int *valid = G.valid + (size_t)e * mp + i0;
-  for (int i = threadIdx.x; i < n; i += 64) {
-    const int pt = valid[i];
-    const int j = (unsigned)pt < (unsigned)npts ? pt : 0;
-    s_pt[i] = make_float4(coord[j], coord[mp + j], coord[2 * mp + j], coord[3 * mp + j]);
-  }
-  __syncthreads();
-  const int h = hb * 64 + threadIdx.x;
-  if (h >= G.num_loops) return;
-  const float *hyp = G.hyp + (size_t)e * 9 * lp;
-  float F[9];
-#pragma unroll
-  for (int k = 0; k < 9; k++) F[k] = hyp[k * lp + h];
-  const float thresh2 = G.thresh2;
-  int cnt = 0;
-  for (int i = 0; i < n; i++) {
-    const float4 q = s_pt[i];
-    float den;
-    const float e2 = fundamental_sampson(F, q.x, q.y, q.z, q.w, den);
-    cnt += fundamental_inlier(e2, den, thresh2) ? 1 : 0;
-  }
-  atomicAdd(&G.hcount[(size_t)e * lp + h], cnt);
-}
-
-__global__ __launch_bounds__(1024) void fund_batch_pick_kernel(FbArgs G)
-{
-  const int e = blockIdx.x;
-  float *F = G.F + (size_t)9 * e;
-  const int *meta = G.meta + (size_t)FB_META * e;
-  if (meta[0] == 0) {                          // nine zeros and 0, or -1 for a frame over max_pts
-    if (threadIdx.x < 9) F[threadIdx.x] = 0.0f;
-    if (threadIdx.x == 0) G.num[e] = meta[1];
-    return;
-  }
-  const int num_loops = G.num_loops;
-  const int *counts = G.hcount + (size_t)e * G.lp;
-#define HOMO_CORE_PICK
-#include "homography_core.inc"
-#undef HOMO_CORE_PICK
-  if (tid == 0) {
-    const int idx = 0x7fffffff - (int)(unsigned)(best & 0xffffffffull);
-    const float *hyp = G.hyp + (size_t)e * 9 * G.lp;
-    for (int k = 0; k < 9; k++) F[k] = hyp[k * G.lp + idx];
-    G.num[e] = (int)(best >> 32);
-  }
 }
 
 struct FbScoreArgs {
@@ -376,67 +265,18 @@ __global__ __launch_bounds__(FUND_SLOTS) void fund_batch_improve_kernel(FbImprov
   }
 }
 
-size_t round16(size_t v) { return (v + 15) / 16 * 16; }
-
 }  // namespace
-
-size_t find_fundamental_batch_tmp_bytes(int nsel, int max_pts, int num_loops)
-{
-  const size_t mp = round16((size_t)max_pts), lp = round16((size_t)num_loops);
-  return (size_t)nsel * (sizeof(float) * 4 * mp + sizeof(int) * mp + sizeof(int) * 8 * lp + sizeof(float) * 9 * lp +
-                         sizeof(int) * lp + sizeof(int) * FB_META);
-}
 
 int launch_find_fundamental_batch(misift_ctx *ctx, int nsel, const int *h_frames, const unsigned *h_seeds,
                                   const BatchLayout &set, int max_pts, int num_loops, float min_score,
                                   float max_ambiguity, float thresh, float *F, int *num)
 {
-  FbArgs G;
-  G.set = set;
-  G.frames = h_frames; G.seeds = h_seeds;
-  G.max_pts = max_pts;
-  G.mp16 = (int)round16((size_t)max_pts);
-  G.num_loops = num_loops;
-  G.lp = (int)round16((size_t)num_loops);
-  G.min_score = min_score; G.max_ambiguity = max_ambiguity; G.thresh2 = thresh * thresh;
-  const size_t mp = (size_t)G.mp16, lp = (size_t)G.lp, ns = (size_t)nsel;
-  const int hblocks = (num_loops + 63) / 64, chunks = (int)((mp + FB_CHUNK - 1) / FB_CHUNK);
-  if ((long long)nsel * hblocks * chunks > 0x7fffffffLL) {
-    misift_set_error("misift_find_fundamental_batch: %d entries x %d loops x %d points is beyond one launch", nsel,
-                     num_loops, max_pts);
-    return MISIFT_EINVAL;
-  }
-  int rc = misift_ensure_tmp(ctx, find_fundamental_batch_tmp_bytes(nsel, max_pts, num_loops));
-  if (rc) return rc;
-  G.coord = reinterpret_cast<float *>(ctx->d_match_tmp);
-  G.valid = reinterpret_cast<int *>(G.coord + ns * 4 * mp);
-  G.sample = G.valid + ns * mp;
-  G.hyp = reinterpret_cast<float *>(G.sample + ns * 8 * lp);
-  G.hcount = reinterpret_cast<int *>(G.hyp + ns * 9 * lp);
-  G.meta = G.hcount + ns * lp;
-  G.F = F; G.num = num;
-  {
-    LaunchScope ls(ctx, "fund_batch_gather");
-    hipLaunchKernelGGL(fund_batch_gather_kernel, dim3(nsel), dim3(1024), 0, ctx->stream, G);
-    rc = ls.finish();
-    if (rc) return rc;
-  }
-  {
-    LaunchScope ls(ctx, "fund_batch_solve");
-    hipLaunchKernelGGL(fund_batch_solve_kernel, dim3(nsel * hblocks), dim3(64), 0, ctx->stream, G, hblocks);
-    rc = ls.finish();
-    if (rc) return rc;
-  }
-  {
-    LaunchScope ls(ctx, "fund_batch_count");
-    hipLaunchKernelGGL(fund_batch_count_kernel, dim3(nsel * hblocks * chunks), dim3(64), 0, ctx->stream, G, hblocks,
-                       chunks);
-    rc = ls.finish();
-    if (rc) return rc;
-  }
-  LaunchScope ls(ctx, "fund_batch_pick");
-  hipLaunchKernelGGL(fund_batch_pick_kernel, dim3(nsel), dim3(1024), 0, ctx->stream, G);
-  return ls.finish();
+  const RansacNames names{"misift_find_fundamental_batch", "fund_batch_gather", "fund_batch_solve", "fund_batch_count",
+                          "fund_batch_pick"};
+  const RansacArgs G = ransac_args(h_frames, h_seeds, set, max_pts, num_loops, min_score, max_ambiguity, thresh, F, num);
+  return ransac_batch_run<FundamentalModel>(ctx, names, nsel, G, [&](const RansacArgs &A, int hblocks) {
+    hipLaunchKernelGGL(fund_batch_solve_kernel, dim3(nsel * hblocks), dim3(64), 0, ctx->stream, A, hblocks);
+  });
 }
 
 int launch_score_fundamental_batch(misift_ctx *ctx, int nsel, const int *h_frames, const BatchLayout &set,

@@ -2153,7 +2153,7 @@ static int run_batch(misift_ctx *ctx, std::initializer_list<HostList> lists, siz
   if (rc) return rc;
   char *h = reinterpret_cast<char *>(x->mb_pairs[slot]);
   for (const HostList &l : lists) {
-    memcpy(h, l.src, l.bytes);
+    if (l.bytes) memcpy(h, l.src, l.bytes);
     h += l.bytes;
   }
   if (plan_bytes) {
@@ -2176,6 +2176,11 @@ struct PairSide {
 // common NULL and range checks.  Then the layouts, the frames of the pairs (a frame of set 1 in at most one pair unless
 // `repeats`), and launch(h_pairs, d_plan, set1, set2) through run_batch with the pairs' device plan.
 #define OWN_CHECK(cond) ((cond) ? nullptr : #cond)
+static int own_check_failed(const char *who, const char *text)
+{
+  misift_set_error("%s: invalid argument: %s", who, text);
+  return MISIFT_EINVAL;
+}
 template <class Launch>
 static int pair_match_call(const char *who, misift_ctx *ctx, int npairs, const int *pairs, const PairSide &s1,
                            const PairSide &s2, const char *own_failed, bool repeats, Launch launch)
@@ -2183,10 +2188,7 @@ static int pair_match_call(const char *who, misift_ctx *ctx, int npairs, const i
   ARG_CHECK_IN(who, ctx && npairs >= 0);
   if (npairs == 0) return MISIFT_OK;
   ARG_CHECK_IN(who, pairs && s1.recs && s2.recs && s1.counts && s2.counts && s1.nframes > 0 && s2.nframes > 0);
-  if (own_failed) {
-    misift_set_error("%s: invalid argument: %s", who, own_failed);
-    return MISIFT_EINVAL;
-  }
+  if (own_failed) return own_check_failed(who, own_failed);
   BatchLayout set1, set2;
   int rc = batch_layout(who, s1.recs, s1.counts, s1.offsets, s1.stride, &set1);
   if (!rc) rc = batch_layout(who, s2.recs, s2.counts, s2.offsets, s2.stride, &set2);
@@ -2231,6 +2233,30 @@ extern "C" int misift_match_pairs_batch(misift_ctx *ctx, int npairs, const int *
                         });
 }
 
+// The six frame-list calls (one entry per selected frame of one set of records) share everything but the checks that are
+// an entry point's own; the counterpart of pair_match_call.  null_failed: NULL, or the text of the entry point's own NULL
+// check that failed.  own(): evaluated behind the NULL checks and the layout only, NULL or the text of the entry point's
+// own check that failed.  Then the frames of the list (each frame in at most one entry), and launch(h_frames, h_extra,
+// set) through run_batch, h_extra being the pinned copy of the entry point's second host list `extra` (may be empty).
+template <class Own, class Launch>
+static int frame_list_call(const char *who, misift_ctx *ctx, int nsel, const int *frames, const PairSide &s,
+                           const char *null_failed, HostList extra, Own own, Launch launch)
+{
+  ARG_CHECK_IN(who, ctx && nsel >= 0);
+  if (nsel == 0) return MISIFT_OK;
+  ARG_CHECK_IN(who, frames && s.recs && s.counts && s.nframes > 0);
+  if (null_failed) return own_check_failed(who, null_failed);
+  BatchLayout set;
+  int rc = batch_layout(who, s.recs, s.counts, s.offsets, s.stride, &set);
+  if (rc) return rc;
+  if (const char *failed = own()) return own_check_failed(who, failed);
+  rc = check_frames(who, nsel, frames, 1, s.nframes, 0);
+  if (rc) return rc;
+  RoctxRange range(who);
+  return run_batch(ctx, {{frames, sizeof(int) * (size_t)nsel}, extra}, 0,
+                   [&](int *h_frames, void *) { return launch(h_frames, (const void *)(h_frames + nsel), set); });
+}
+
 // Many frames of a device-resident batch through FindHomography / ImproveHomography in one stream-ordered call each: no
 // host wait and no host read of the counts.
 extern "C" int misift_find_homography_batch(misift_ctx *ctx, int nsel, const int *frames, const unsigned *seeds,
@@ -2238,22 +2264,14 @@ extern "C" int misift_find_homography_batch(misift_ctx *ctx, int nsel, const int
                                             int stride, int max_pts, int num_loops, float min_score,
                                             float max_ambiguity, float thresh, float *d_homography, int *d_num_matches)
 {
-  ARG_CHECK(ctx && nsel >= 0);
-  if (nsel == 0) return MISIFT_OK;
-  ARG_CHECK(frames && seeds && d_recs && d_counts && nframes > 0 && d_homography && d_num_matches);
-  BatchLayout set;
-  int rc = batch_layout(__func__, d_recs, d_counts, d_offsets, stride, &set);
-  if (rc) return rc;
-  ARG_CHECK(num_loops >= 1 && max_pts >= 1);
-  rc = check_frames(__func__, nsel, frames, 1, nframes, 0);
-  if (rc) return rc;
-  RoctxRange range(__func__);
-  return run_batch(ctx, {{frames, sizeof(int) * (size_t)nsel}, {seeds, sizeof(unsigned) * (size_t)nsel}}, 0,
-                   [&](int *h_frames, void *) {
-                     return launch_find_homography_batch(ctx, nsel, h_frames, (const unsigned *)(h_frames + nsel), set,
-                                                         max_pts, num_loops, min_score, max_ambiguity, thresh,
-                                                         d_homography, d_num_matches);
-                   });
+  const PairSide s{d_recs, nframes, d_counts, d_offsets, stride};
+  return frame_list_call(
+      __func__, ctx, nsel, frames, s, OWN_CHECK(seeds && d_homography && d_num_matches),
+      HostList{seeds, sizeof(unsigned) * (size_t)nsel}, [&] { return OWN_CHECK(num_loops >= 1 && max_pts >= 1); },
+      [&](const int *h_frames, const void *h_seeds, const BatchLayout &set) {
+        return launch_find_homography_batch(ctx, nsel, h_frames, (const unsigned *)h_seeds, set, max_pts, num_loops,
+                                            min_score, max_ambiguity, thresh, d_homography, d_num_matches);
+      });
 }
 
 extern "C" int misift_improve_homography_batch(misift_ctx *ctx, int nsel, const int *frames, void *d_recs, int nframes,
@@ -2261,20 +2279,14 @@ extern "C" int misift_improve_homography_batch(misift_ctx *ctx, int nsel, const 
                                                float min_score, float max_ambiguity, float thresh, float *d_homography,
                                                int *d_num_fit)
 {
-  ARG_CHECK(ctx && nsel >= 0);
-  if (nsel == 0) return MISIFT_OK;
-  ARG_CHECK(frames && d_recs && d_counts && nframes > 0 && d_homography && d_num_fit);
-  BatchLayout set;
-  int rc = batch_layout(__func__, d_recs, d_counts, d_offsets, stride, &set);
-  if (rc) return rc;
-  ARG_CHECK(num_loops >= 0);
-  rc = check_frames(__func__, nsel, frames, 1, nframes, 0);
-  if (rc) return rc;
-  RoctxRange range(__func__);
-  return run_batch(ctx, {{frames, sizeof(int) * (size_t)nsel}}, 0, [&](int *h_frames, void *) {
-    return launch_improve_homography_batch(ctx, nsel, h_frames, set, num_loops, min_score, max_ambiguity, thresh,
-                                           d_homography, d_num_fit);
-  });
+  const PairSide s{d_recs, nframes, d_counts, d_offsets, stride};
+  return frame_list_call(
+      __func__, ctx, nsel, frames, s, OWN_CHECK(d_homography && d_num_fit), HostList{},
+      [&] { return OWN_CHECK(num_loops >= 0); },
+      [&](const int *h_frames, const void *, const BatchLayout &set) {
+        return launch_improve_homography_batch(ctx, nsel, h_frames, set, num_loops, min_score, max_ambiguity, thresh,
+                                               d_homography, d_num_fit);
+      });
 }
 
 // The epipolar counterpart: a RANSAC fundamental matrix per frame, and the Sampson distance of every record under a
@@ -2285,22 +2297,15 @@ extern "C" int misift_find_fundamental_batch(misift_ctx *ctx, int nsel, const in
                                              float max_ambiguity, float thresh, float *d_fundamental,
                                              int *d_num_inliers)
 {
-  ARG_CHECK(ctx && nsel >= 0);
-  if (nsel == 0) return MISIFT_OK;
-  ARG_CHECK(frames && seeds && d_recs && d_counts && nframes > 0 && d_fundamental && d_num_inliers);
-  BatchLayout set;
-  int rc = batch_layout(__func__, d_recs, d_counts, d_offsets, stride, &set);
-  if (rc) return rc;
-  ARG_CHECK(num_loops >= 1 && max_pts >= 1 && thresh > 0.0f);
-  rc = check_frames(__func__, nsel, frames, 1, nframes, 0);
-  if (rc) return rc;
-  RoctxRange range(__func__);
-  return run_batch(ctx, {{frames, sizeof(int) * (size_t)nsel}, {seeds, sizeof(unsigned) * (size_t)nsel}}, 0,
-                   [&](int *h_frames, void *) {
-                     return launch_find_fundamental_batch(ctx, nsel, h_frames, (const unsigned *)(h_frames + nsel), set,
-                                                          max_pts, num_loops, min_score, max_ambiguity, thresh,
-                                                          d_fundamental, d_num_inliers);
-                   });
+  const PairSide s{d_recs, nframes, d_counts, d_offsets, stride};
+  return frame_list_call(
+      __func__, ctx, nsel, frames, s, OWN_CHECK(seeds && d_fundamental && d_num_inliers),
+      HostList{seeds, sizeof(unsigned) * (size_t)nsel},
+      [&] { return OWN_CHECK(num_loops >= 1 && max_pts >= 1 && thresh > 0.0f); },
+      [&](const int *h_frames, const void *h_seeds, const BatchLayout &set) {
+        return launch_find_fundamental_batch(ctx, nsel, h_frames, (const unsigned *)h_seeds, set, max_pts, num_loops,
+                                             min_score, max_ambiguity, thresh, d_fundamental, d_num_inliers);
+      });
 }
 
 extern "C" int misift_score_fundamental_batch(misift_ctx *ctx, int nsel, const int *frames, void *d_recs, int nframes,
@@ -2308,20 +2313,14 @@ extern "C" int misift_score_fundamental_batch(misift_ctx *ctx, int nsel, const i
                                               float max_ambiguity, float thresh, const float *d_fundamental,
                                               int *d_num_fit)
 {
-  ARG_CHECK(ctx && nsel >= 0);
-  if (nsel == 0) return MISIFT_OK;
-  ARG_CHECK(frames && d_recs && d_counts && nframes > 0 && d_fundamental && d_num_fit);
-  BatchLayout set;
-  int rc = batch_layout(__func__, d_recs, d_counts, d_offsets, stride, &set);
-  if (rc) return rc;
-  ARG_CHECK(thresh > 0.0f);
-  rc = check_frames(__func__, nsel, frames, 1, nframes, 0);
-  if (rc) return rc;
-  RoctxRange range(__func__);
-  return run_batch(ctx, {{frames, sizeof(int) * (size_t)nsel}}, 0, [&](int *h_frames, void *) {
-    return launch_score_fundamental_batch(ctx, nsel, h_frames, set, min_score, max_ambiguity, thresh, d_fundamental,
-                                          d_num_fit);
-  });
+  const PairSide s{d_recs, nframes, d_counts, d_offsets, stride};
+  return frame_list_call(
+      __func__, ctx, nsel, frames, s, OWN_CHECK(d_fundamental && d_num_fit), HostList{},
+      [&] { return OWN_CHECK(thresh > 0.0f); },
+      [&](const int *h_frames, const void *, const BatchLayout &set) {
+        return launch_score_fundamental_batch(ctx, nsel, h_frames, set, min_score, max_ambiguity, thresh,
+                                              d_fundamental, d_num_fit);
+      });
 }
 
 // Refits of each frame's F over its inliers, then match_error under the result: the epipolar counterpart of
@@ -2331,20 +2330,14 @@ extern "C" int misift_improve_fundamental_batch(misift_ctx *ctx, int nsel, const
                                                 float min_score, float max_ambiguity, float thresh,
                                                 float *d_fundamental, int *d_num_fit, int *d_num_rounds)
 {
-  ARG_CHECK(ctx && nsel >= 0);
-  if (nsel == 0) return MISIFT_OK;
-  ARG_CHECK(frames && d_recs && d_counts && nframes > 0 && d_fundamental && d_num_fit);
-  BatchLayout set;
-  int rc = batch_layout(__func__, d_recs, d_counts, d_offsets, stride, &set);
-  if (rc) return rc;
-  ARG_CHECK(num_loops >= 0 && thresh > 0.0f);
-  rc = check_frames(__func__, nsel, frames, 1, nframes, 0);
-  if (rc) return rc;
-  RoctxRange range(__func__);
-  return run_batch(ctx, {{frames, sizeof(int) * (size_t)nsel}}, 0, [&](int *h_frames, void *) {
-    return launch_improve_fundamental_batch(ctx, nsel, h_frames, set, num_loops, min_score, max_ambiguity, thresh,
-                                            d_fundamental, d_num_fit, d_num_rounds);
-  });
+  const PairSide s{d_recs, nframes, d_counts, d_offsets, stride};
+  return frame_list_call(
+      __func__, ctx, nsel, frames, s, OWN_CHECK(d_fundamental && d_num_fit), HostList{},
+      [&] { return OWN_CHECK(num_loops >= 0 && thresh > 0.0f); },
+      [&](const int *h_frames, const void *, const BatchLayout &set) {
+        return launch_improve_fundamental_batch(ctx, nsel, h_frames, set, num_loops, min_score, max_ambiguity, thresh,
+                                                d_fundamental, d_num_fit, d_num_rounds);
+      });
 }
 
 // fx fy cx cy of `cameras` cameras: focal lengths finite and > 0, principal points finite
@@ -2365,23 +2358,19 @@ extern "C" int misift_recover_pose_batch(misift_ctx *ctx, int nsel, const int *f
                                          const float *d_fundamental, float *d_pose, int *d_num_front, int *d_votes,
                                          float *d_xyz)
 {
-  ARG_CHECK(ctx && nsel >= 0);
-  if (nsel == 0) return MISIFT_OK;
-  ARG_CHECK(frames && intrinsics && d_recs && d_counts && nframes > 0 && d_fundamental && d_pose && d_num_front);
-  BatchLayout set;
-  int rc = batch_layout(__func__, d_recs, d_counts, d_offsets, stride, &set);
-  if (rc) return rc;
-  ARG_CHECK(thresh > 0.0f);
-  rc = check_frames(__func__, nsel, frames, 1, nframes, 0);
-  if (rc) return rc;
-  for (int i = 0; i < nsel; i++) ARG_CHECK(intrinsics_usable(intrinsics + (size_t)8 * i));
-  RoctxRange range(__func__);
-  return run_batch(ctx, {{frames, sizeof(int) * (size_t)nsel}, {intrinsics, sizeof(float) * 8 * (size_t)nsel}}, 0,
-                   [&](int *h_frames, void *) {
-                     return launch_recover_pose_batch(ctx, nsel, h_frames, (const float *)(h_frames + nsel), set,
-                                                      min_score, max_ambiguity, thresh, d_fundamental, d_pose,
-                                                      d_num_front, d_votes, d_xyz);
-                   });
+  const PairSide s{d_recs, nframes, d_counts, d_offsets, stride};
+  return frame_list_call(
+      __func__, ctx, nsel, frames, s, OWN_CHECK(intrinsics && d_fundamental && d_pose && d_num_front),
+      HostList{intrinsics, sizeof(float) * 8 * (size_t)nsel},
+      [&]() -> const char * {
+        for (int i = 0; i < nsel; i++)
+          if (!intrinsics_usable(intrinsics + (size_t)8 * i)) return "intrinsics_usable(intrinsics + (size_t)8 * i)";
+        return OWN_CHECK(thresh > 0.0f);
+      },
+      [&](const int *h_frames, const void *h_intrinsics, const BatchLayout &set) {
+        return launch_recover_pose_batch(ctx, nsel, h_frames, (const float *)h_intrinsics, set, min_score,
+                                         max_ambiguity, thresh, d_fundamental, d_pose, d_num_front, d_votes, d_xyz);
+      });
 }
 
 // Homography- and epipolar-guided matching of many frame pairs in one stream-ordered call each: no host wait and no host

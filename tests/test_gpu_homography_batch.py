@@ -174,6 +174,86 @@ def test_count_above_max_pts_guarded(ctx):
         assert nm[i] == ne and np.array_equal(_bits(H[i]), _bits(He)), (i, nm[i], ne)
 
 
+def _gated(n, seed, valid):
+    """n records of which exactly `valid` pass FIND's gate; the others (spread over the frame) have score 0."""
+    p = synth_matches(n, seed=seed)[0]
+    p["score"], p["ambiguity"] = 0.99, 0.5
+    p["score"][np.linspace(0, n - 1, n - valid).astype(int)] = 0.0
+    return p
+
+
+def _same_as_single(g, got, sel, seeds, recs, counts, offs, stride, max_pts, loops, what, oracle=True):
+    """The way _check_find compares, with the frames over max_pts expected as -1 and the identity."""
+    H, nm = g.download(got[0], (len(sel), 3, 3), np.float32), g.download(got[1], (len(sel),), np.int32)
+    for i, (f, s) in enumerate(zip(sel, seeds)):
+        n = max(int(counts[f]), 0)
+        He, ne = (IDENTITY, -1) if n > max_pts else _single_find(g, recs[span(offs, stride, f, n)].copy(), n, s, loops,
+                                                                 oracle)
+        assert nm[i] == ne and np.array_equal(_bits(H[i]), _bits(He)), (what, i, f, n, nm[i], ne)
+    return nm
+
+
+@pytest.mark.parametrize("padded", [False, True], ids=["packed", "padded"])
+def test_find_off_16_shapes(padded):
+    """Frames of 9, 8, 7 and 40 records (one with exactly 8 valid records, one with 7), max_pts 9 and 40 (neither a
+    multiple of 16; at 9 the 40-record frame is over it), 1 and 17 loops (worked over as 16 and 32): every stride of the
+    temp is a rounded-up size, and every entry still equals the single call bit for bit."""
+    sizes = [9, 8, 7, 40, 9]
+    fr = [_gated(9, 31, 8), _gated(8, 32, 8), _gated(7, 33, 7), _gated(40, 34, 33), _gated(9, 35, 7)]
+    recs, offs, stride = layout(fr, sizes, padded, min_stride=1, pad_error=-7.0)
+    sel, seeds = [3, 0, 4, 2, 1], [5, 2**32 - 1, 7, 8, 0]
+    with guarded_context(3) as g:
+        d, dc = g.upload(recs), g.upload(np.asarray(sizes, np.int32))
+        do = g.upload(offs) if offs is not None else None
+        for max_pts in (9, 40):
+            for loops in (1, 17):
+                got = g.find_homography_batch(sel, seeds, d, len(sizes), dc, do, stride, max_pts=max_pts,
+                                              num_loops=loops, **FIND)
+                g.sync()
+                nm = _same_as_single(g, got, sel, seeds, recs, sizes, offs, stride, max_pts, loops, (max_pts, loops))
+                assert (nm[0] == -1) == (max_pts == 9) and nm[1] >= 4 and nm[4] >= 4, nm
+                assert nm[2] == 0 and nm[3] == 0, nm              # 7 valid records; 7 records
+
+
+def test_find_stale_temp():
+    """The mirror of test_gpu_fundamental_edges.test_stale_temp with the homography search as the checked call.  The
+    grow-only temp is shared: a 15-entry fundamental search at 200 loops and a brute-force match on other buffers, the
+    2-entry homography search (9 and 8 records, 1 loop), a larger one (256 loops, max_pts 2048), the 2-entry one again;
+    meta, hcount and sample of the small layout lie in bytes the other calls wrote in theirs.  Every buffer is uploaded
+    first; the steps are then library calls only, with no synchronisation by the test until all are enqueued."""
+    from batch_util import frames as match_frames
+    from test_gpu_fundamental import COUNTS, MAX_PTS, SEEDS, SEL, make_batch
+    big, boffs, bstride = layout(make_batch(), COUNTS, False, min_stride=2048, pad_error=-7.0)
+    small_sizes = [9, 8]
+    small, soffs, sstride = layout([_gated(9, 41, 8), _gated(8, 42, 8)], small_sizes, False, min_stride=1, pad_error=0.0)
+    mrecs, moffs, _ = layout(match_frames([300, 280], 5, True), [300, 280], False, min_stride=0, pad_error=0.0)
+    ssel, sseeds = [1, 0], [7, 2**32 - 1]
+    with guarded_context(3) as g:
+        d_big, d_bc, d_bo = g.upload(big), g.upload(np.asarray(COUNTS, np.int32)), g.upload(boffs)
+        d_small, d_sc, d_so = g.upload(small), g.upload(np.asarray(small_sizes, np.int32)), g.upload(soffs)
+        d_m, d_mc, d_mo = g.upload(mrecs), g.upload(np.array([300, 280], np.int32)), g.upload(moffs)
+        dF, dFn = g.zeros(4 * 9 * len(SEL)), g.zeros(4 * len(SEL))
+        outs = [(g.zeros(4 * 9 * n), g.zeros(4 * n)) for n in (2, len(SEL), 2)]
+        g.sync()
+        g.find_fundamental_batch(SEL, SEEDS, d_big, len(COUNTS), d_bc, d_bo, bstride, max_pts=MAX_PTS, num_loops=200,
+                                 fundamental=dF, num_inliers=dFn)         # library calls only from here to the sync
+        g.match_batch([(0, 1)], d_m, 2, d_mc, d_mo, 0)
+        g.find_homography_batch(ssel, sseeds, d_small, 2, d_sc, d_so, sstride, max_pts=9, num_loops=1,
+                                homography=outs[0][0], num_matches=outs[0][1], **FIND)
+        g.find_homography_batch(SEL, SEEDS, d_big, len(COUNTS), d_bc, d_bo, bstride, max_pts=2048, num_loops=256,
+                                homography=outs[1][0], num_matches=outs[1][1], **FIND)
+        g.find_homography_batch(ssel, sseeds, d_small, 2, d_sc, d_so, sstride, max_pts=9, num_loops=1,
+                                homography=outs[2][0], num_matches=outs[2][1], **FIND)
+        g.sync()
+        assert g.download(dFn, (len(SEL),), np.int32).max() >= 8     # the fundamental search ran
+        for step, o in ((1, outs[0]), (3, outs[2])):
+            nm = _same_as_single(g, o, ssel, sseeds, small, small_sizes, soffs, sstride, 9, 1, ("step", step))
+            assert (nm >= 4).all(), nm
+        nm = _same_as_single(g, outs[1], SEL, SEEDS, big, COUNTS, boffs, bstride, 2048, 256, ("step", 2),
+                             oracle=False)
+        assert (nm > 0).sum() >= 8, nm
+
+
 def test_argument_errors(ctx):
     from cudasift_amd import capi
     L = capi.lib()
