@@ -124,6 +124,9 @@ SIGNATURES = {
                                              _vp]),
     "misift_test_triangulate_track": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "misift_test_triangulate_capacity": (_i, []),
+    "misift_refine_cameras_batch": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _f, _i,
+                                         _vp, _vp, _vp, _vp, _vp, _vp]),
+    "misift_test_refine_camera": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _vp]),
     "misift_test_quantize": (_i, [_vp, C.c_long, _vp]),
     "misift_test_match_i8_plan": (_i, [_i, _i, _vp, _vp, _vp, _ip, _ip, _ip]),
     "misift_test_libc_rand": (_i, [C.c_uint, _i, _vp]),
@@ -964,6 +967,45 @@ class Context:
                                                     _dptr(point_views), _dptr(point_status), _dptr(obs_error),
                                                     _dptr(summary)), "misift_triangulate_tracks_batch")
         return points, point_views, point_status, obs_error, summary
+
+    def refine_cameras_batch(self, max_tracks, max_obs, track_offsets, obs, export_summary, points, point_status,
+                             nimages, cam, cam_pair, intrinsics, hold=(), min_obs=6, num_loops=5, max_error=np.inf,
+                             orthonormalise=True, cam_out=None, cam_obs=None, cam_rms=None, cam_steps=None,
+                             cam_status=None, summary=None):
+        """misift_refine_cameras_batch: every camera of link_poses_batch (cam, cam_pair, for nimages images) moved to
+        minimise the reprojection error of the observations its image makes (track_offsets, obs, export_summary: the
+        outputs of export_tracks_batch for max_tracks and max_obs) of the points of triangulate_tracks_batch (points,
+        point_status), the points held.  intrinsics: host, nimages x 4 (fx fy cx cy); hold: host, the images kept as
+        they are besides the root.  The rotation is re-orthonormalised first when orthonormalise is set; an observation
+        is used when its point is in front and within max_error px; an image with fewer than min_obs of them keeps its
+        camera; then up to num_loops Gauss-Newton steps, each kept only if it lowers the error.  cam_out (nimages x 12
+        floats; may be cam itself), cam_obs, cam_steps and cam_status (nimages ints: the observations used, the steps
+        kept; 0 ok, 1 fewer than min_obs, 2 singular, 3 root or held, 4 no camera), cam_rms (nimages x 2 floats: rms
+        reprojection error in px before and after) and summary (8 ints) are device buffers, allocated here when not
+        passed; returns the six.  Enqueued on the context stream."""
+        intrinsics = np.ascontiguousarray(intrinsics, np.float32).reshape(-1, 4)
+        assert len(intrinsics) == nimages
+        hold = np.ascontiguousarray(hold, np.int32).reshape(-1)
+        if cam_out is None:
+            cam_out = self.zeros(48 * max(nimages, 1))
+        if cam_obs is None:
+            cam_obs = self.zeros(4 * max(nimages, 1))
+        if cam_rms is None:
+            cam_rms = self.zeros(8 * max(nimages, 1))
+        if cam_steps is None:
+            cam_steps = self.zeros(4 * max(nimages, 1))
+        if cam_status is None:
+            cam_status = self.zeros(4 * max(nimages, 1))
+        if summary is None:
+            summary = self.zeros(4 * 8)
+        check(lib().misift_refine_cameras_batch(self.h, max_tracks, max_obs, _dptr(track_offsets), _dptr(obs),
+                                                _dptr(export_summary), _dptr(points), _dptr(point_status), nimages,
+                                                _dptr(cam), _dptr(cam_pair), intrinsics.ctypes.data, len(hold),
+                                                hold.ctypes.data if len(hold) else None, int(min_obs), int(num_loops),
+                                                float(max_error), int(orthonormalise), _dptr(cam_out), _dptr(cam_obs),
+                                                _dptr(cam_rms), _dptr(cam_steps), _dptr(cam_status), _dptr(summary)),
+              "misift_refine_cameras_batch")
+        return cam_out, cam_obs, cam_rms, cam_steps, cam_status, summary
 
     def match_split(self, pts1, n1, pts2, n2, own_tile_begin, own_tile_end):
         """Test hook: misift_match with the column sweep cut into two launches (the sharded matcher's cut)."""

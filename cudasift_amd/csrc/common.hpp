@@ -644,6 +644,15 @@ int launch_triangulate_tracks_batch(misift_ctx *ctx, int max_tracks, int max_obs
                                     const int *d_cam_pair, const float *h_intrinsics, int min_views, int num_loops,
                                     float *d_points, int *d_point_views, int *d_point_status, float *d_obs_error,
                                     int *d_summary);
+// misift_refine_cameras_batch (kernels_refine.hip): two memsets + three launches; temp from misift_ensure_tmp, sized from
+// max_obs only (an owner and a key per slot).  h_lists: the intrinsics (nimages x 4 floats), then a held flag per image
+size_t refine_cameras_batch_tmp_bytes(int max_obs);
+int launch_refine_cameras_batch(misift_ctx *ctx, int max_tracks, int max_obs, const int *d_track_offsets,
+                                const void *d_obs, const int *d_export_summary, const float *d_points,
+                                const int *d_point_status, int nimages, const float *d_cam, const int *d_cam_pair,
+                                const void *h_lists, int min_obs, int num_loops, float thresh2, int orthonormalise,
+                                float *d_cam_out, int *d_cam_obs, float *d_cam_rms, int *d_cam_steps, int *d_cam_status,
+                                int *d_summary);
 int launch_test_exp2(misift_ctx *ctx, const float *x, float *out, int n);
 int launch_test_points_fn(misift_ctx *ctx, int fn, const float *x, const float *y, float *out, float *out2, int n);
 int launch_selftest(misift_ctx *ctx);

@@ -1,0 +1,260 @@
+// kernels_refine.hip — misift_refine_cameras_batch: every linked camera moved to minimise the reprojection error of the
+// observations its image makes of the triangulated track points, the points held (motion-only bundle adjustment).  It
+// is the other half of misift_triangulate_tracks_batch's minimisation; the two alternated are block-coordinate bundle
+// adjustment.  No reference counterpart.  The arithmetic is refine_core.hpp, shared with the host-only test hook at the
+// end of this file.
+//
+// Two memsets (the owners, the summary) and three launches, whatever the data:
+//   refine_owner_kernel    256-thread workgroups, one lane per track, the grid sized from max_tracks.  T and O are read
+//                          from the export summary on the device.  A lane whose track is valid walks its range with
+//                          atomicMax(owner[o], t), so a slot ends with the largest valid track that holds it.
+//   refine_key_kernel      one lane per slot, the grid sized from max_obs: key[o] = the observation's frame when slot o
+//                          is a candidate of that image (it has an owner of status 0 with a finite point, its position is
+//                          finite and its frame lies in [0, nimages)), otherwise -1.
+//   refine_cameras_kernel  one 256-thread workgroup per image, thread s being slot s of the call's sum.  A pass walks the
+//                          keys o = s, s + 256, ... < O with coalesced 4-byte loads, eight ahead; for a key that names its
+//                          image the lane loads the owner, the 16-byte observation and the point, decides membership under
+//                          the camera of step 1 (recomputed in every pass: some twenty operations, and no member list
+//                          has to be kept anywhere), and adds the 28 terms in registers.  The tree runs through 28 KiB of
+//                          LDS.  The solve and the update are a few hundred operations that every lane runs on the
+//                          same values.  num_loops + 1 passes at the most; a workgroup reads O x 4 bytes of keys per
+//                          pass, from the L2 after the first image has read them.
+// Not built: member lists kept in LDS after the first pass, and a form that spreads the terms of an image
+// whose slots fall into a few lanes over all lanes before they are added in the order of the sum.
+#include <stdint.h>
+#include <string.h>
+#include "common.hpp"
+#include "refine_core.hpp"
+
+namespace {
+
+constexpr int REFINE_THREADS = FUND_SLOTS;
+constexpr int REFINE_AHEAD = 8;                // slot keys a lane loads before it looks at the first
+
+struct alignas(16) RefineObs {                 // misift_track_obs, read with one 16-byte load
+  int frame, record;
+  float xpos, ypos;
+};
+static_assert(sizeof(RefineObs) == sizeof(misift_track_obs), "RefineObs mirrors misift_track_obs");
+
+struct RefineArgs {
+  int max_tracks, max_obs, nimages, min_obs, num_loops, orthonormalise;
+  float thresh2;
+  const int *track_offsets;
+  const RefineObs *obs;
+  const int *export_summary;
+  const float *points;                         // max_tracks x 4
+  const int *point_status;
+  const float *cam;
+  const int *cam_pair;
+  const float *intrinsics;                     // the pinned host copy: nimages x 4
+  const int *held;                             // the pinned host copy: nimages flags
+  int *owner, *key;                            // temp: max_obs each
+  float *cam_out;
+  int *cam_obs;
+  float *cam_rms;
+  int *cam_steps, *cam_status, *summary;
+};
+
+__device__ __forceinline__ int refine_T(const RefineArgs &A) { return min(max(A.export_summary[2], 0), A.max_tracks); }
+__device__ __forceinline__ int refine_O(const RefineArgs &A) { return min(max(A.export_summary[3], 0), A.max_obs); }
+
+__global__ __launch_bounds__(REFINE_THREADS) void refine_owner_kernel(RefineArgs A)
+{
+  const int t = blockIdx.x * REFINE_THREADS + threadIdx.x;   // below max_tracks + 256: no overflow
+  if (t >= refine_T(A)) return;
+  const int off = A.track_offsets[t], end = A.track_offsets[t + 1];
+  if (!tri_range_ok(off, end, refine_O(A))) return;          // before it addresses anything
+  for (int o = off; o < end; o++) atomicMax(&A.owner[o], t);
+}
+
+__global__ __launch_bounds__(REFINE_THREADS) void refine_key_kernel(RefineArgs A)
+{
+  const int o = blockIdx.x * REFINE_THREADS + threadIdx.x;
+  if (o >= refine_O(A)) return;
+  const int t = A.owner[o];
+  int key = -1;
+  if (t >= 0 && A.point_status[t] == TRI_OK) {
+    const float *X = A.points + 4 * (size_t)t;
+    const RefineObs ob = A.obs[o];
+    if (fundamental_finite(X[0]) && fundamental_finite(X[1]) && fundamental_finite(X[2]) && fundamental_finite(ob.xpos) &&
+        fundamental_finite(ob.ypos) && ob.frame >= 0 && ob.frame < A.nimages)
+      key = ob.frame;
+  }
+  A.key[o] = key;
+}
+
+// the workgroup as the Exec of refine_camera
+struct RefineBlockExec {
+  const RefineArgs &A;
+  float *p;                                    // LDS: REFINE_SUMS x FUND_SLOTS
+  int *cnt;                                    // LDS: 8 ints
+  int image, O;
+  const float *k;                              // fx fy cx cy in registers
+
+  // slot o, known to be a candidate of this image: false when it is no member; its terms, or `behind`
+  __device__ __forceinline__ bool terms(int o, const float (&cam1)[12], const float (&cam)[12], float thresh2,
+                                        float (&x)[REFINE_SUMS], int &n, bool &behind) const
+  {
+    const float *P = A.points + 4 * (size_t)A.owner[o];
+    const RefineObs ob = A.obs[o];
+    const float X[3] = {P[0], P[1], P[2]};
+    if (!refine_member(cam1, k, X, ob.xpos, ob.ypos, thresh2)) return false;
+    n++;
+    if (refine_terms(cam, k, X, ob.xpos, ob.ypos, x)) return true;
+    behind = true;
+    return false;
+  }
+
+  __device__ void pass(const float (&cam1)[12], const float (&cam)[12], float thresh2, float (&S)[REFINE_SUMS], int &n,
+                       bool &behind)
+  {
+    const int t = threadIdx.x;
+    int mine = 0;
+    bool back = false;
+    // slot t's partial sums as fundamental_slot_partial forms them: the members o = t, t + 256, ... in ascending order
+    // from +0.  The keys of REFINE_AHEAD slots are loaded before the first is looked at: a load per iteration left the
+    // walk waiting on each in turn.
+    float acc[REFINE_SUMS];
+#pragma unroll
+    for (int j = 0; j < REFINE_SUMS; j++) acc[j] = 0.0f;
+    for (long long base = t; base < O; base += (long long)REFINE_AHEAD * FUND_SLOTS) {
+      int key[REFINE_AHEAD];
+#pragma unroll
+      for (int u = 0; u < REFINE_AHEAD; u++) {
+        const long long o = base + u * FUND_SLOTS;
+        key[u] = o < O ? A.key[o] : -1;
+      }
+#pragma unroll
+      for (int u = 0; u < REFINE_AHEAD; u++) {
+        if (key[u] != image) continue;
+        float x[REFINE_SUMS];
+        if (!terms((int)(base + u * FUND_SLOTS), cam1, cam, thresh2, x, mine, back)) continue;
+#pragma unroll
+        for (int j = 0; j < REFINE_SUMS; j++) acc[j] = acc[j] + x[j];
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < REFINE_SUMS; j++) p[j * FUND_SLOTS + t] = acc[j];
+    int c = mine, b = back ? 1 : 0;
+    for (int off = 32; off > 0; off >>= 1) {
+      c += __shfl_xor(c, off, 64);
+      b |= __shfl_xor(b, off, 64);
+    }
+    if ((t & 63) == 0) {
+      cnt[t >> 6] = c;
+      cnt[4 + (t >> 6)] = b;
+    }
+    for (int off = FUND_SLOTS / 2; off > 0; off >>= 1) {
+      __syncthreads();
+      if (t < off) fundamental_tree_step<REFINE_SUMS>(p, t, off);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < REFINE_SUMS; j++) S[j] = p[j * FUND_SLOTS];
+    n = cnt[0] + cnt[1] + cnt[2] + cnt[3];
+    behind = (cnt[4] | cnt[5] | cnt[6] | cnt[7]) != 0;
+    __syncthreads();                           // p and cnt are free again
+  }
+};
+
+__global__ __launch_bounds__(REFINE_THREADS) void refine_cameras_kernel(RefineArgs A)
+{
+  __shared__ float s_p[REFINE_SUMS * FUND_SLOTS];
+  __shared__ int s_cnt[8];
+  const int i = blockIdx.x, tid = threadIdx.x;
+  if (i == 0 && tid == 0) A.summary[0] = refine_T(A);
+  const unsigned *bits = reinterpret_cast<const unsigned *>(A.cam) + 12 * (size_t)i;
+  unsigned given[12];
+  float cam_in[12];
+#pragma unroll
+  for (int j = 0; j < 12; j++) {
+    given[j] = bits[j];
+    cam_in[j] = __uint_as_float(given[j]);
+  }
+  const int pair = A.cam_pair[i];
+  const float k[4] = {A.intrinsics[4 * (size_t)i], A.intrinsics[4 * (size_t)i + 1], A.intrinsics[4 * (size_t)i + 2],
+                      A.intrinsics[4 * (size_t)i + 3]};
+  const bool fixed = pair == POSEGRAPH_ROOT || A.held[i] != 0;
+  RefineBlockExec ex{A, s_p, s_cnt, i, refine_O(A), k};
+  RefineResult r;
+  refine_camera(ex, cam_in, pair == POSEGRAPH_UNSET, fixed, k, A.orthonormalise, A.min_obs, A.num_loops, A.thresh2, r);
+  if (tid != 0) return;                        // every thread holds the same result; the input was read above
+  unsigned *out = reinterpret_cast<unsigned *>(A.cam_out) + 12 * (size_t)i;
+#pragma unroll
+  for (int j = 0; j < 12; j++) out[j] = r.as_given ? given[j] : __float_as_uint(r.cam[j]);
+  A.cam_obs[i] = r.nobs;
+  A.cam_rms[2 * (size_t)i] = r.rms0;
+  A.cam_rms[2 * (size_t)i + 1] = r.rms1;
+  A.cam_steps[i] = r.steps;
+  A.cam_status[i] = r.status;
+  atomicAdd(&A.summary[r.status == REFINE_OK ? 1 : r.status == REFINE_NO_CAMERA ? 7 : r.status + 2], 1);
+  if (r.status == REFINE_OK && r.nobs) atomicAdd(&A.summary[2], r.nobs);
+  if (r.steps) atomicAdd(&A.summary[6], r.steps);
+}
+
+}  // namespace
+
+size_t refine_cameras_batch_tmp_bytes(int max_obs) { return 2 * sizeof(int) * (size_t)max_obs; }
+
+// Enqueue misift_refine_cameras_batch on the context stream (common.hpp): two memsets and three launches.  h_lists: the
+// pinned copies, nimages x 4 intrinsics and then nimages held flags.
+int launch_refine_cameras_batch(misift_ctx *ctx, int max_tracks, int max_obs, const int *d_track_offsets,
+                                const void *d_obs, const int *d_export_summary, const float *d_points,
+                                const int *d_point_status, int nimages, const float *d_cam, const int *d_cam_pair,
+                                const void *h_lists, int min_obs, int num_loops, float thresh2, int orthonormalise,
+                                float *d_cam_out, int *d_cam_obs, float *d_cam_rms, int *d_cam_steps, int *d_cam_status,
+                                int *d_summary)
+{
+  const int rc = misift_ensure_tmp(ctx, refine_cameras_batch_tmp_bytes(max_obs));
+  if (rc) return rc;
+  RefineArgs A;
+  A.max_tracks = max_tracks; A.max_obs = max_obs; A.nimages = nimages; A.min_obs = min_obs; A.num_loops = num_loops;
+  A.orthonormalise = orthonormalise; A.thresh2 = thresh2;
+  A.track_offsets = d_track_offsets; A.obs = reinterpret_cast<const RefineObs *>(d_obs);
+  A.export_summary = d_export_summary; A.points = d_points;
+  A.point_status = d_point_status; A.cam = d_cam; A.cam_pair = d_cam_pair;
+  A.intrinsics = reinterpret_cast<const float *>(h_lists);
+  A.held = reinterpret_cast<const int *>(A.intrinsics + 4 * (size_t)nimages);
+  A.owner = reinterpret_cast<int *>(ctx->d_match_tmp);
+  A.key = A.owner + max_obs;
+  A.cam_out = d_cam_out; A.cam_obs = d_cam_obs; A.cam_rms = d_cam_rms; A.cam_steps = d_cam_steps;
+  A.cam_status = d_cam_status; A.summary = d_summary;
+  HIP_TRY(hipMemsetAsync(A.owner, 0xff, sizeof(int) * (size_t)max_obs, ctx->stream));
+  HIP_TRY(hipMemsetAsync(d_summary, 0, 8 * sizeof(int), ctx->stream));
+  const auto blocks = [](int n) { return dim3((unsigned)(((long long)n + REFINE_THREADS - 1) / REFINE_THREADS)); };
+  LaunchScope ls(ctx, "refine_cameras");
+  hipLaunchKernelGGL(refine_owner_kernel, blocks(max_tracks), dim3(REFINE_THREADS), 0, ctx->stream, A);
+  hipLaunchKernelGGL(refine_key_kernel, blocks(max_obs), dim3(REFINE_THREADS), 0, ctx->stream, A);
+  hipLaunchKernelGGL(refine_cameras_kernel, dim3(nimages), dim3(REFINE_THREADS), 0, ctx->stream, A);
+  return ls.finish();
+}
+
+// Test-only, host-only: one image as its workgroup computes it (refine_core.hpp).
+extern "C" int misift_test_refine_camera(const float *cam12, int cam_pair, int held, const float *intrinsics4, int ncand,
+                                         const int *slot, const float *X, const float *xy, int min_obs, int num_loops,
+                                         float max_error, int orthonormalise, float *cam_out12, int *nobs, float *rms2,
+                                         int *steps, int *status)
+{
+  bool ok = cam12 && intrinsics4 && ncand >= 0 && (ncand == 0 || (slot && X && xy)) && min_obs >= 3 && num_loops >= 0 &&
+            max_error > 0.0f && (orthonormalise == 0 || orthonormalise == 1) && cam_out12 && nobs && rms2 && steps && status;
+  for (int i = 0; ok && i < ncand; i++) ok = slot[i] >= 0 && (i == 0 || slot[i] > slot[i - 1]);
+  if (!ok) {
+    misift_set_error("misift_test_refine_camera: invalid argument");
+    return MISIFT_EINVAL;
+  }
+  float cam_in[12];
+  memcpy(cam_in, cam12, sizeof cam_in);
+  RefineHostExec ex;
+  ex.ncand = ncand; ex.slot = slot; ex.X = X; ex.xy = xy; ex.k = intrinsics4;
+  RefineResult r;
+  refine_camera(ex, cam_in, cam_pair == POSEGRAPH_UNSET, cam_pair == POSEGRAPH_ROOT || held != 0, intrinsics4,
+                orthonormalise, min_obs, num_loops, max_error * max_error, r);
+  if (r.as_given) memmove(cam_out12, cam12, 12 * sizeof(float));
+  else memcpy(cam_out12, r.cam, 12 * sizeof(float));
+  *nobs = r.nobs;
+  rms2[0] = r.rms0; rms2[1] = r.rms1;
+  *steps = r.steps;
+  *status = r.status;
+  return MISIFT_OK;
+}

@@ -2602,6 +2602,43 @@ extern "C" int misift_triangulate_tracks_batch(misift_ctx *ctx, int max_tracks, 
   });
 }
 
+// Every linked camera moved to minimise the reprojection error of its image's observations of the triangulated points:
+// the other half of misift_triangulate_tracks_batch's minimisation.  The intrinsics and a flag per image (1 = held) go
+// to the pinned slot.
+extern "C" int misift_refine_cameras_batch(misift_ctx *ctx, int max_tracks, int max_obs, const int *d_track_offsets,
+                                           const misift_track_obs *d_obs, const int *d_export_summary,
+                                           const float *d_points, const int *d_point_status, int nimages,
+                                           const float *d_cam, const int *d_cam_pair, const float *intrinsics, int nhold,
+                                           const int *hold, int min_obs, int num_loops, float max_error,
+                                           int orthonormalise, float *d_cam_out, int *d_cam_obs, float *d_cam_rms,
+                                           int *d_cam_steps, int *d_cam_status, int *d_summary)
+{
+  ARG_CHECK(ctx && max_tracks >= 1 && max_obs >= 1 && nimages >= 1);
+  ARG_CHECK(d_track_offsets && d_obs && d_export_summary && d_points && d_point_status && d_cam && d_cam_pair);
+  ARG_CHECK(intrinsics && d_cam_out && d_cam_obs && d_cam_rms && d_cam_steps && d_cam_status && d_summary);
+  ARG_CHECK(((uintptr_t)d_obs & 15) == 0);
+  ARG_CHECK(min_obs >= 3 && num_loops >= 0);
+  ARG_CHECK(max_error > 0.0f);                                              // NaN fails too
+  ARG_CHECK(orthonormalise == 0 || orthonormalise == 1);
+  ARG_CHECK(nhold >= 0 && (nhold == 0 || hold));
+  for (int j = 0; j < nhold; j++) ARG_CHECK(hold[j] >= 0 && hold[j] < nimages);
+  for (int i = 0; i < nimages; i++) ARG_CHECK(intrinsics_usable(intrinsics + 4 * (size_t)i, 1));
+  const uintptr_t in = (uintptr_t)d_cam, out = (uintptr_t)d_cam_out, span = sizeof(float) * 12 * (size_t)nimages;
+  ARG_CHECK(in == out || in + span <= out || out + span <= in);
+  std::vector<int> held(nimages, 0);
+  for (int j = 0; j < nhold; j++) held[hold[j]] = 1;
+  const float thresh2 = max_error * max_error;                              // rounded once, here
+  RoctxRange range(__func__);
+  return run_batch(ctx, {{intrinsics, sizeof(float) * 4 * (size_t)nimages}, {held.data(), sizeof(int) * (size_t)nimages}},
+                   0, [&](int *h_lists, void *) {
+                     return launch_refine_cameras_batch(ctx, max_tracks, max_obs, d_track_offsets, d_obs,
+                                                        d_export_summary, d_points, d_point_status, nimages, d_cam,
+                                                        d_cam_pair, h_lists, min_obs, num_loops, thresh2, orthonormalise,
+                                                        d_cam_out, d_cam_obs, d_cam_rms, d_cam_steps, d_cam_status,
+                                                        d_summary);
+                   });
+}
+
 // ------------------------------------------------------------------- timing
 extern "C" int misift_timer_start(misift_ctx *ctx)
 {

@@ -421,9 +421,9 @@ int misift_match_pairs_batch(misift_ctx *ctx, int npairs, const int *pairs,
  *     misift_match_pairs_batch_i8, misift_find_homography_batch, misift_improve_homography_batch,
  *     misift_find_fundamental_batch, misift_score_fundamental_batch, misift_improve_fundamental_batch,
  *     misift_recover_pose_batch, misift_link_poses_batch, misift_match_guided_batch,
- *     misift_match_epipolar_batch, misift_link_tracks_batch, misift_export_tracks_batch and
- *     misift_triangulate_tracks_batch (which run on the context stream) on a batch's packed
- *     records: make the context stream wait for that batch first
+ *     misift_match_epipolar_batch, misift_link_tracks_batch, misift_export_tracks_batch,
+ *     misift_triangulate_tracks_batch and misift_refine_cameras_batch (which run on the context stream) on a batch's
+ *     packed records: make the context stream wait for that batch first
  *     (misift_ctx_wait_batch(ctx, <the context's stream>), or an event from misift_ctx_record_batch).
  * K = 1 (default) is the plain in-order context.  Also MISIFT_BATCHES_IN_FLIGHT at context creation.  Changing K drains
  * the context. */
@@ -1099,8 +1099,9 @@ int misift_export_tracks_batch(misift_ctx *ctx,
  *      d_summary (8 ints, integer sums, so deterministic): [0] T, [1] tracks with status 0, [2] their usable views,
  *      [3] tracks with status 1, [4] with status 2, [5] with status 3, [6] Gauss-Newton steps kept, [7] tracks with
  *      status 4.
- *   - Not done here: no view is rejected as an outlier (gate on d_obs_error and call again, or leave it to the bundle
- *     adjustment), the cameras are not adjusted, and d_cam is used as it is, without re-orthonormalising its rotations.
+ *   - Not done here: no view is rejected as an outlier (gate on d_obs_error and call again), the cameras are not
+ *     adjusted, and d_cam is used as it is, without re-orthonormalising its rotations: misift_refine_cameras_batch does
+ *     both and hands back cameras for the next call of this one.
  *   - NULL ctx; max_tracks, max_obs or nimages < 1; NULL d_track_offsets, d_obs, d_export_summary, d_cam, d_cam_pair,
  *     intrinsics, d_points, d_point_views, d_point_status or d_summary; d_obs not 16-byte aligned; min_views < 2;
  *     num_loops < 0; an fx or fy that is not finite and > 0 or a cx or cy that is not finite: MISIFT_EINVAL, before
@@ -1125,6 +1126,110 @@ int misift_triangulate_tracks_batch(misift_ctx *ctx,
                                     int   *d_point_status,          /* max_tracks */
                                     float *d_obs_error,             /* max_obs, may be NULL */
                                     int   *d_summary);              /* 8 ints */
+
+/* The linked cameras refined against the triangulated track points (no reference counterpart): the other half of the
+ * minimisation of misift_triangulate_tracks_batch.  With the points held, each camera is moved to minimise the
+ * reprojection error of the observations its image makes (motion-only bundle adjustment, resection refinement).
+ * Alternated with misift_triangulate_tracks_batch this is block-coordinate bundle adjustment, all of it on the device.
+ *   d_track_offsets, d_obs and d_export_summary are what misift_export_tracks_batch wrote for max_tracks and max_obs,
+ *   d_points and d_point_status what misift_triangulate_tracks_batch wrote for them, d_cam and d_cam_pair what
+ *   misift_link_poses_batch (or an earlier call of this one) wrote; intrinsics[4i..4i+3] = fx fy cx cy of image i.
+ *   `hold` lists nhold image indices whose cameras are kept as they are (an index may repeat).  Held cameras fix the
+ *   gauge: the root is always kept, and the caller normally holds the other image of the seed pair as well, so that the
+ *   scale cannot creep when this call and triangulate alternate.  obs.record and d_points[4t+3] are not read.
+ *   The arithmetic is that of misift_triangulate_tracks_batch: fp32, every operation rounded, only + - * / and sqrtf, no
+ *   contraction, a comparison with a NaN is false, everything taken left to right as written; a . b of two 3-vectors is
+ *   (a0*b0 + a1*b1) + a2*b2.  A single result that is a NaN is stored as 0x7fc00000.
+ *   Owner of a slot.  T = min(max(d_export_summary[2], 0), max_tracks) and O = min(max(d_export_summary[3], 0), max_obs),
+ *   both read on the device.  Track t < T is VALID iff 0 <= off[t] <= off[t + 1] <= O, checked before it addresses
+ *   anything.  The OWNER of slot o < O is the largest valid t with off[t] <= o < off[t + 1], or none.  Under export's own
+ *   output the ranges are disjoint; the rule only makes hostile offsets deterministic.
+ *   Candidates.  Slot o < O is a CANDIDATE of image i iff it has an owner t, d_obs[o].frame == i, d_point_status[t] == 0,
+ *   X = d_points[4t..4t+2] is finite, and d_obs[o].xpos and .ypos (x, y below) are finite.
+ *   The sum of the call is the rule of misift_improve_fundamental_batch with the slot index o in place of the record
+ *   index: p[s], s < 256, starts at +0 and adds the terms of the members with o = s (mod 256) in ascending o, one at a
+ *   time (a slot that is no member is skipped); then for off = 128, 64 ... 1: p[s] = p[s] + p[s + off] for s < off; the
+ *   sum is p[0].
+ *   Per image i, independently of every other image:
+ *   0. Status without work.  d_cam_pair[i] == -2, or one of the twelve floats d_cam[12i..] not finite: status 4.
+ *      Otherwise d_cam_pair[i] == -1 (the root) or i in `hold`: status 3.  Either way d_cam_out[12i..] gets the twelve
+ *      floats bit for bit, d_cam_obs[i] = 0, d_cam_steps[i] = 0 and both d_cam_rms entries the quiet NaN.
+ *   1. Orthonormalise, when orthonormalise == 1.  With r0, r1, r2 the rows of R: n0 = sqrtf(r0 . r0), r0 <- r0 / n0 per
+ *      component; d = r1 . r0 (the new r0), w = r1 - d*r0 per component, n1 = sqrtf(w . w), r1 <- w / n1; r2 <- r0 x r1
+ *      with components r0[1]*r1[2] - r0[2]*r1[1], r0[2]*r1[0] - r0[0]*r1[2], r0[0]*r1[1] - r0[1]*r1[0].  t is unchanged.
+ *      A non-finite result: status 4, with the outputs of step 0.  With orthonormalise == 0 the camera is as given.
+ *   2. Members, under the camera (R, t) of step 1.  Per candidate, as step 3 of misift_triangulate_tracks_batch:
+ *      Xc.x = ((r00*X0 + r01*X1) + r02*X2) + t0, Xc.y and Xc.z likewise; iz = 1/Xc.z, a = Xc.x*iz, b = Xc.y*iz;
+ *      ru = x - (fx*a + cx), rv = y - (fy*b + cy).  The candidate is a MEMBER iff Xc.z > 0 and ru*ru + rv*rv < E2, where
+ *      E2 = max_error*max_error is rounded once on the host; when E2 is +inf the test is Xc.z > 0 alone.  The member set
+ *      is fixed here and does not change in the loops.  n = its size.  n < min_obs: status 1; the camera of step 1 is
+ *      written, d_cam_obs[i] = n, both d_cam_rms entries are the quiet NaN and d_cam_steps[i] = 0.
+ *   3. Cost and normal equations under a camera (R, t), over the members.  Xc, iz, a, b, ru, rv as in step 2 under
+ *      (R, t); gx = fx*iz, gy = fy*iz; the parameters are (wx wy wz ux uy uz), a rotation and a translation of the
+ *      camera frame:
+ *        Ju = ( gx*(-(a*Xc.y)), gx*(Xc.z + a*Xc.x), gx*(-Xc.y), gx*1, gx*0, gx*(-a) )
+ *        Jv = ( gy*(-(Xc.z + b*Xc.y)), gy*(b*Xc.x), gy*Xc.x, gy*0, gy*1, gy*(-b) )
+ *      28 sums of the call: c with the term ru*ru + rv*rv; M[r][q] for r <= q < 6 with the term Ju[r]*Ju[q] + Jv[r]*Jv[q]
+ *      (M[q][r] = M[r][q]); g[r] with the term Ju[r]*ru + Jv[r]*rv.  A member with Xc.z > 0 false makes the camera NOT IN
+ *      FRONT; its sums are not used.
+ *   4. SOLVE M delta = g by LDL^T without pivoting.  For j = 0 ... 5 in turn: v_k = L[j][k]*d_k for k < j;
+ *      d_j = M[j][j] - L[j][0]*v_0 - ... - L[j][j-1]*v_(j-1), one subtraction at a time in ascending k; then for every
+ *      i > j: L[i][j] = (M[i][j] - L[i][0]*v_0 - ... - L[i][j-1]*v_(j-1)) / d_j, the same way.  y_i = g[i] - L[i][0]*y_0
+ *      - ... - L[i][i-1]*y_(i-1) for i = 0 ... 5; delta_i = y_i/d_i - L[i+1][i]*delta_(i+1) - ... - L[5][i]*delta_5 for
+ *      i = 5 ... 0, the quotient first, then ascending k.  The solve FAILS at the first pivot d_j that is not finite and
+ *      > 0 (nothing is divided by it), or when a component of delta is not finite.
+ *   5. Update by the Cayley map, which is rational and, in exact arithmetic, orthogonal.  h = 0.5*(wx, wy, wz) per
+ *      component, s = h . h, e = 1 - s, q = 1 + s;
+ *        C00 = (e + 2*(h0*h0))/q        C01 = (2*(h0*h1) - 2*h2)/q     C02 = (2*(h0*h2) + 2*h1)/q
+ *        C10 = (2*(h0*h1) + 2*h2)/q     C11 = (e + 2*(h1*h1))/q        C12 = (2*(h1*h2) - 2*h0)/q
+ *        C20 = (2*(h0*h2) - 2*h1)/q     C21 = (2*(h1*h2) + 2*h0)/q     C22 = (e + 2*(h2*h2))/q
+ *      R'[r][c] = (C[r][0]*R[0][c] + C[r][1]*R[1][c]) + C[r][2]*R[2][c];
+ *      t'[r] = ((C[r][0]*t0 + C[r][1]*t1) + C[r][2]*t2) + u_r.
+ *   6. Gauss-Newton.  Step 3 under the camera of step 1 gives c0 = c, M, g.  Then num_loops times at the most: SOLVE,
+ *      update, step 3 under (R', t') gives c', M', g'.  (R', t') is kept (with c', M', g') iff the solve did not fail,
+ *      the camera is in front of every member and c' < c; otherwise the loop ends there.  Status 2 iff the first solve
+ *      fails; the camera of step 1 is written.  Otherwise status 0.  num_loops = 0 solves nothing.
+ *   7. Outputs.  d_cam_out[12i..12i+11] = the last camera kept (the twelve input floats bit for bit when nothing was
+ *      kept and orthonormalise == 0); d_cam_obs[i] = n; d_cam_rms[2i] = sqrtf(c0 / (float)n) and d_cam_rms[2i + 1] =
+ *      sqrtf(c / (float)n) under the camera written, in pixels; d_cam_steps[i] = the steps kept; d_cam_status[i].
+ *      d_summary (8 ints, integer sums, so deterministic): [0] T, [1] cameras with status 0, [2] their members,
+ *      [3] cameras with status 1, [4] with status 2, [5] with status 3, [6] steps kept, [7] cameras with status 4.
+ *   - With num_loops == 0 and orthonormalise == 0 every camera comes back bit for bit, and d_cam_rms[2i] is the
+ *     per-image rms that d_obs_error of misift_triangulate_tracks_batch implies (over the members, under max_error).
+ *   - Not done here: camera and point steps are not taken jointly (no Schur complement; alternate with triangulate
+ *     instead), no robust kernel re-weights a residual (max_error is a hard gate, decided once), and the intrinsics are
+ *     not refined.
+ *   - NULL ctx; max_tracks, max_obs or nimages < 1; NULL d_track_offsets, d_obs, d_export_summary, d_points,
+ *     d_point_status, d_cam, d_cam_pair, intrinsics, d_cam_out, d_cam_obs, d_cam_rms, d_cam_steps, d_cam_status or
+ *     d_summary; d_obs not 16-byte aligned; min_obs < 3; num_loops < 0; max_error NaN or <= 0; orthonormalise other than
+ *     0 or 1; nhold < 0, nhold > 0 with NULL hold, a hold index outside [0, nimages); an fx or fy that is not finite and
+ *     > 0 or a cx or cy that is not finite; d_cam_out overlapping d_cam without being equal to it: MISIFT_EINVAL, before
+ *     anything is enqueued.  hold may be NULL when nhold == 0.  None of the inputs is written, except d_cam when it is
+ *     d_cam_out.
+ *   - The call runs on the context stream and returns before the GPU work is done; `intrinsics` and `hold` are copied;
+ *     no host synchronisation and no host read.  Ordering behind batches in flight (K > 1): as misift_match_batch.
+ *   - Two memsets and three launches whatever the data: one lane per track finds the owners, one lane per slot the
+ *     candidates, then one 256-thread workgroup per image, its thread s being slot s of the sum.  8 bytes per slot of
+ *     temp memory from the library's own allocator, sized from max_obs only. */
+int misift_refine_cameras_batch(misift_ctx *ctx,
+                                int max_tracks, int max_obs,
+                                const int *d_track_offsets,     /* max_tracks + 1, from export */
+                                const misift_track_obs *d_obs,  /* max_obs, from export, 16-byte aligned */
+                                const int *d_export_summary,    /* 8 ints, from export: [2] = T, [3] = O */
+                                const float *d_points,          /* max_tracks x 4, from triangulate */
+                                const int *d_point_status,      /* max_tracks, from triangulate */
+                                int nimages,
+                                const float *d_cam,             /* nimages x 12, from link_poses */
+                                const int *d_cam_pair,          /* nimages, from link_poses */
+                                const float *intrinsics,        /* host, nimages x 4: fx fy cx cy, copied */
+                                int nhold, const int *hold,     /* host, images kept as they are, copied; may be NULL */
+                                int min_obs, int num_loops, float max_error, int orthonormalise,
+                                float *d_cam_out,               /* nimages x 12; may be d_cam itself */
+                                int   *d_cam_obs,               /* nimages */
+                                float *d_cam_rms,               /* nimages x 2: before, after */
+                                int   *d_cam_steps,             /* nimages */
+                                int   *d_cam_status,            /* nimages */
+                                int   *d_summary);              /* 8 ints */
 
 /* cudaMallocManaged as used by the reference's MANAGEDMEM build flavour (cudaSiftH.cu:239-240): one pointer valid on
  * host and device (SiftData.m_data). */
@@ -1206,6 +1311,14 @@ int misift_test_triangulate_track(const float *cams, const int *cam_pair, const 
                                   const misift_track_obs *obs, int nobs, int min_views, int num_loops, float *point4,
                                   int *views, int *status, float *obs_error, int *gn_accepted);
 int misift_test_triangulate_capacity(void);
+/* Test-only, host-only: steps 0-7 of misift_refine_cameras_batch for one image, compiled from the function its workgroup
+ * runs, the 256 slots of the sum one after another.  cam12 its camera, cam_pair its d_cam_pair entry, held != 0 iff it is
+ * in `hold`, intrinsics4 its fx fy cx cy; its ncand candidates as slot[] (their slot indices o, >= 0 and ascending),
+ * X[3k..3k+2] and xy[2k..2k+1].  cam_out12 (may be cam12), *nobs, rms2[0..1], *steps and *status as the call writes them. */
+int misift_test_refine_camera(const float *cam12, int cam_pair, int held, const float *intrinsics4, int ncand,
+                              const int *slot, const float *X, const float *xy, int min_obs, int num_loops,
+                              float max_error, int orthonormalise, float *cam_out12, int *nobs, float *rms2, int *steps,
+                              int *status);
 /* Test-only, host-only: the gate and the gather of misift_match_epipolar_batch, compiled from the same headers and
  * functions as the kernel.  xy1: n1 set-1 positions (x, y), xy2: n2 set-2 positions.  gate: pass[i * n2 + j] = 1 iff
  * record j is a candidate of row i under F9 and radius.  gather: builds the cell grid of xy2 as the bin launch does
