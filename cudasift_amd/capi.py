@@ -24,6 +24,7 @@ assert POINT_DTYPE.itemsize == 576
 
 # misift_track_obs: one observation of an exported track (misift_export_tracks_batch)
 TRACK_OBS_DTYPE = np.dtype([("frame", "<i4"), ("record", "<i4"), ("xpos", "<f4"), ("ypos", "<f4")])
+CAM_UNSET, CAM_ROOT, CAM_RESECTED = -2, -1, -3                 # cam_pair values that are no pair index
 assert TRACK_OBS_DTYPE.itemsize == 16
 
 
@@ -127,6 +128,10 @@ SIGNATURES = {
     "misift_refine_cameras_batch": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _f, _i,
                                          _vp, _vp, _vp, _vp, _vp, _vp]),
     "misift_test_refine_camera": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _vp]),
+    "misift_resect_cameras_batch": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _f, _i, _i,
+                                         _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "misift_test_resect_samples": (_i, [C.c_uint, _i, _i, _vp]),
+    "misift_test_resect_solve": (_i, [_vp, _vp, _vp, _vp]),
     "misift_test_quantize": (_i, [_vp, C.c_long, _vp]),
     "misift_test_match_i8_plan": (_i, [_i, _i, _vp, _vp, _vp, _ip, _ip, _ip]),
     "misift_test_libc_rand": (_i, [C.c_uint, _i, _vp]),
@@ -1006,6 +1011,46 @@ class Context:
                                                 _dptr(cam_rms), _dptr(cam_steps), _dptr(cam_status), _dptr(summary)),
               "misift_refine_cameras_batch")
         return cam_out, cam_obs, cam_rms, cam_steps, cam_status, summary
+
+    def resect_cameras_batch(self, max_tracks, max_obs, track_offsets, obs, export_summary, points, point_status,
+                             nimages, intrinsics, images, seeds, max_cand, num_loops=1024, thresh=4.0, min_inliers=12,
+                             only_unset=False, install=False, cam=None, cam_pair=None, res_cam=None, res_cand=None,
+                             res_inliers=None, res_status=None, summary=None):
+        """misift_resect_cameras_batch: the camera of each image in `images` (host, distinct indices; seeds: host, one
+        rand() seed per entry) estimated from the observations its image makes (track_offsets, obs, export_summary: the
+        outputs of export_tracks_batch for max_tracks and max_obs) of the points of triangulate_tracks_batch (points,
+        point_status), by RANSAC over num_loops calibrated six-point solves; a candidate is an inlier when its point is
+        in front and within thresh px.  intrinsics: host, nimages x 4 (fx fy cx cy).  An image with more than max_cand
+        candidates is not searched.  With only_unset, an image whose cam_pair entry is not -2 is skipped; with install,
+        a camera found goes into cam (nimages x 12) and cam_pair (CAM_RESECTED).  res_cam (nsel x 12 floats), res_cand,
+        res_inliers and res_status (nsel ints: the candidates, the inliers of the picked hypothesis; 0 ok, 1 too few
+        candidates, 2 fewer than min_inliers inliers, 3 skipped, 4 more than max_cand candidates) and summary (8 ints)
+        are device buffers, allocated here when not passed; returns the five.  Enqueued on the context stream."""
+        intrinsics = np.ascontiguousarray(intrinsics, np.float32).reshape(-1, 4)
+        assert len(intrinsics) == nimages
+        images = np.ascontiguousarray(images, np.int32).reshape(-1)
+        seeds = np.ascontiguousarray(seeds, np.uint32).reshape(-1)
+        nsel = len(images)
+        assert len(seeds) == nsel
+        if res_cam is None:
+            res_cam = self.zeros(48 * max(nsel, 1))
+        if res_cand is None:
+            res_cand = self.zeros(4 * max(nsel, 1))
+        if res_inliers is None:
+            res_inliers = self.zeros(4 * max(nsel, 1))
+        if res_status is None:
+            res_status = self.zeros(4 * max(nsel, 1))
+        if summary is None:
+            summary = self.zeros(4 * 8)
+        check(lib().misift_resect_cameras_batch(self.h, max_tracks, max_obs, _dptr(track_offsets), _dptr(obs),
+                                                _dptr(export_summary), _dptr(points), _dptr(point_status), nimages,
+                                                intrinsics.ctypes.data, nsel, images.ctypes.data if nsel else None,
+                                                seeds.ctypes.data if nsel else None, int(max_cand), int(num_loops),
+                                                float(thresh), int(min_inliers), int(only_unset), int(install),
+                                                _dptr(cam), _dptr(cam_pair), _dptr(res_cam), _dptr(res_cand),
+                                                _dptr(res_inliers), _dptr(res_status), _dptr(summary)),
+              "misift_resect_cameras_batch")
+        return res_cam, res_cand, res_inliers, res_status, summary
 
     def match_split(self, pts1, n1, pts2, n2, own_tile_begin, own_tile_end):
         """Test hook: misift_match with the column sweep cut into two launches (the sharded matcher's cut)."""

@@ -653,6 +653,17 @@ int launch_refine_cameras_batch(misift_ctx *ctx, int max_tracks, int max_obs, co
                                 const void *h_lists, int min_obs, int num_loops, float thresh2, int orthonormalise,
                                 float *d_cam_out, int *d_cam_obs, float *d_cam_rms, int *d_cam_steps, int *d_cam_status,
                                 int *d_summary);
+// misift_resect_cameras_batch (kernels_resect.hip): two memsets + six launches; temp from misift_ensure_tmp, sized from
+// max_obs, nsel, max_cand and num_loops only.  h_lists: the intrinsics (nimages x 4 floats), the images (nsel ints), the
+// seeds (nsel)
+size_t resect_cameras_batch_tmp_bytes(int max_obs, int nsel, int max_cand, int num_loops);
+bool resect_cameras_batch_one_launch(int max_obs, int nsel, int max_cand, int num_loops);
+int launch_resect_cameras_batch(misift_ctx *ctx, int max_tracks, int max_obs, const int *d_track_offsets,
+                                const void *d_obs, const int *d_export_summary, const float *d_points,
+                                const int *d_point_status, int nimages, int nsel, const void *h_lists, int max_cand,
+                                int num_loops, float thresh2, int min_inliers, int only_unset, int install, float *d_cam,
+                                int *d_cam_pair, float *d_res_cam, int *d_res_cand, int *d_res_inliers,
+                                int *d_res_status, int *d_summary);
 int launch_test_exp2(misift_ctx *ctx, const float *x, float *out, int n);
 int launch_test_points_fn(misift_ctx *ctx, int fn, const float *x, const float *y, float *out, float *out2, int n);
 int launch_selftest(misift_ctx *ctx);

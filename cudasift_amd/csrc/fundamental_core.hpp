@@ -47,57 +47,60 @@ struct FundamentalArrayMat {
 };
 
 // col[j] = the original column now at position j, indexed statically: positions k and pc change places
-FUND_HD void fundamental_swap_columns(int (&col)[9], int k, int pc)
+template <int C>
+FUND_HD void fundamental_swap_columns(int (&col)[C], int k, int pc)
 {
   int ck = 0, cp = 0;
 #pragma unroll
-  for (int j = 0; j < 9; j++) { ck = j == k ? col[j] : ck; cp = j == pc ? col[j] : cp; }
+  for (int j = 0; j < C; j++) { ck = j == k ? col[j] : ck; cp = j == pc ? col[j] : cp; }
 #pragma unroll
-  for (int j = 0; j < 9; j++) col[j] = j == k ? cp : (j == pc ? ck : col[j]);
+  for (int j = 0; j < C; j++) col[j] = j == k ? cp : (j == pc ? ck : col[j]);
 }
 
-// the one free column = 1, back-substitution of rows 7..0 of the eliminated system, the column permutation undone -> n
-template <class Mat>
-FUND_HD void fundamental_back_substitute(const Mat &m, const int (&col)[9], float (&n)[9])
+// the one free column = 1, back-substitution of rows C-2..0 of the eliminated system, the column permutation undone -> n
+template <class Mat, int C>
+FUND_HD void fundamental_back_substitute(const Mat &m, const int (&col)[C], float (&n)[C])
 {
-  float z[9];
-  z[8] = 1.0f;
+  float z[C];
+  z[C - 1] = 1.0f;
 #pragma unroll
-  for (int k = 7; k >= 0; k--) {
+  for (int k = C - 2; k >= 0; k--) {
     float s = 0.0f;
 #pragma unroll
-    for (int c = k + 1; c < 9; c++) s = s + m.get(k, c) * z[c];
+    for (int c = k + 1; c < C; c++) s = s + m.get(k, c) * z[c];
     z[k] = (-s) / m.get(k, k);
   }
 #pragma unroll
-  for (int j = 0; j < 9; j++) n[j] = 0.0f;
+  for (int j = 0; j < C; j++) n[j] = 0.0f;
 #pragma unroll
-  for (int i = 0; i < 9; i++)
+  for (int i = 0; i < C; i++)
 #pragma unroll
-    for (int j = 0; j < 9; j++) n[j] = col[i] == j ? z[i] : n[j];
+    for (int j = 0; j < C; j++) n[j] = col[i] == j ? z[i] : n[j];
 }
 
-// The elimination and the solve of an R x 9 system (R = 8: one hypothesis; R = 9: the moment matrix of a refinement),
-// eight steps either way; returns whether every pivot was non-zero and finite.  n = the solution, 9 floats.
-//   eliminate Gaussian elimination with complete pivoting: at step k the entry of rows k..R-1 x columns k..8 with the
+// The elimination and the solve of an R x C system, C taken from n (C = 9 with R = 8: one hypothesis, R = 9: the moment
+// matrix of a refinement; C = 12 with R = 11: the six-point resection of resect_core.hpp), C - 1 steps whatever R;
+// returns whether every pivot was non-zero and finite.  n = the solution, C floats.
+//   eliminate Gaussian elimination with complete pivoting: at step k the entry of rows k..R-1 x columns k..C-1 with the
 //             largest fabsf, searched row-major with a strict '>' (the first maximum wins, a NaN never does)
-//   solve     the one free column = 1, back-substitution of rows 7..0, the column permutation undone -> n
-template <int R, class Mat>
-FUND_HD bool fundamental_eliminate(Mat &m, float (&n)[9])
+//   solve     the one free column = 1, back-substitution of rows C-2..0, the column permutation undone -> n
+template <int R, class Mat, int C>
+FUND_HD bool fundamental_eliminate(Mat &m, float (&n)[C])
 {
-  int col[9];                                  // col[j] = the original column now at position j; indexed statically
+  static_assert(R >= C - 1, "a row per elimination step");
+  int col[C];                                  // col[j] = the original column now at position j; indexed statically
 #pragma unroll
-  for (int j = 0; j < 9; j++) col[j] = j;
+  for (int j = 0; j < C; j++) col[j] = j;
   bool ok = true;
-  for (int k = 0; k < 8; k++) {
+  for (int k = 0; k < C - 1; k++) {
     int pr = k, pc = k;
     float best = -1.0f;
     for (int r = k; r < R; r++)
-      for (int c = k; c < 9; c++) {
+      for (int c = k; c < C; c++) {
         const float v = fabsf(m.get(r, c));
         if (v > best) { best = v; pr = r; pc = c; }
       }
-    for (int c = k; c < 9; c++) {              // rows k <-> pr (the columns left of k are dead)
+    for (int c = k; c < C; c++) {              // rows k <-> pr (the columns left of k are dead)
       const float t = m.get(k, c);
       m.set(k, c, m.get(pr, c));
       m.set(pr, c, t);
@@ -112,7 +115,7 @@ FUND_HD bool fundamental_eliminate(Mat &m, float (&n)[9])
     ok = ok && piv != 0.0f && fundamental_finite(piv);
     for (int r = k + 1; r < R; r++) {
       const float f = m.get(r, k) / piv;
-      for (int c = k + 1; c < 9; c++) m.set(r, c, m.get(r, c) - f * m.get(k, c));
+      for (int c = k + 1; c < C; c++) m.set(r, c, m.get(r, c) - f * m.get(k, c));
     }
   }
   fundamental_back_substitute(m, col, n);

@@ -5,12 +5,8 @@
 // end of this file.
 //
 // Two memsets (the owners, the summary) and three launches, whatever the data:
-//   refine_owner_kernel    256-thread workgroups, one lane per track, the grid sized from max_tracks.  T and O are read
-//                          from the export summary on the device.  A lane whose track is valid walks its range with
-//                          atomicMax(owner[o], t), so a slot ends with the largest valid track that holds it.
-//   refine_key_kernel      one lane per slot, the grid sized from max_obs: key[o] = the observation's frame when slot o
-//                          is a candidate of that image (it has an owner of status 0 with a finite point, its position is
-//                          finite and its frame lies in [0, nimages)), otherwise -1.
+//   cand_owner_kernel      the owner of every slot and
+//   cand_key_kernel        the image every slot is a candidate of: track_candidates.hpp, shared with kernels_resect.hip.
 //   refine_cameras_kernel  one 256-thread workgroup per image, thread s being slot s of the call's sum.  A pass walks the
 //                          keys o = s, s + 256, ... < O with coalesced 4-byte loads, eight ahead; for a key that names its
 //                          image the lane loads the owner, the 16-byte observation and the point, decides membership under
@@ -25,64 +21,26 @@
 #include <string.h>
 #include "common.hpp"
 #include "refine_core.hpp"
+#include "track_candidates.hpp"
 
 namespace {
 
 constexpr int REFINE_THREADS = FUND_SLOTS;
 constexpr int REFINE_AHEAD = 8;                // slot keys a lane loads before it looks at the first
 
-struct alignas(16) RefineObs {                 // misift_track_obs, read with one 16-byte load
-  int frame, record;
-  float xpos, ypos;
-};
-static_assert(sizeof(RefineObs) == sizeof(misift_track_obs), "RefineObs mirrors misift_track_obs");
-
 struct RefineArgs {
-  int max_tracks, max_obs, nimages, min_obs, num_loops, orthonormalise;
+  int min_obs, num_loops, orthonormalise;
   float thresh2;
-  const int *track_offsets;
-  const RefineObs *obs;
-  const int *export_summary;
-  const float *points;                         // max_tracks x 4
-  const int *point_status;
+  CandArgs c;                                  // the tracks, the observations, the points; owner and key in temp
   const float *cam;
   const int *cam_pair;
   const float *intrinsics;                     // the pinned host copy: nimages x 4
   const int *held;                             // the pinned host copy: nimages flags
-  int *owner, *key;                            // temp: max_obs each
   float *cam_out;
   int *cam_obs;
   float *cam_rms;
   int *cam_steps, *cam_status, *summary;
 };
-
-__device__ __forceinline__ int refine_T(const RefineArgs &A) { return min(max(A.export_summary[2], 0), A.max_tracks); }
-__device__ __forceinline__ int refine_O(const RefineArgs &A) { return min(max(A.export_summary[3], 0), A.max_obs); }
-
-__global__ __launch_bounds__(REFINE_THREADS) void refine_owner_kernel(RefineArgs A)
-{
-  const int t = blockIdx.x * REFINE_THREADS + threadIdx.x;   // below max_tracks + 256: no overflow
-  if (t >= refine_T(A)) return;
-  const int off = A.track_offsets[t], end = A.track_offsets[t + 1];
-  if (!tri_range_ok(off, end, refine_O(A))) return;          // before it addresses anything
-  for (int o = off; o < end; o++) atomicMax(&A.owner[o], t);
-}
-
-__global__ __launch_bounds__(REFINE_THREADS) void refine_key_kernel(RefineArgs A)
-{
-  const int o = blockIdx.x * REFINE_THREADS + threadIdx.x;
-  if (o >= refine_O(A)) return;
-  const int t = A.owner[o];
-  int key = -1;
-  if (t >= 0 && A.point_status[t] == TRI_OK) {
-    const float *X = A.points + 4 * (size_t)t;
-    const RefineObs ob = A.obs[o];
-    if (fundamental_finite(X[0]) && fundamental_finite(X[1]) && fundamental_finite(X[2]) && fundamental_finite(ob.xpos) &&
-        fundamental_finite(ob.ypos) && ob.frame >= 0 && ob.frame < A.nimages)
-      key = ob.frame;
-  }
-  A.key[o] = key;
-}
 
 // the workgroup as the Exec of refine_camera
 struct RefineBlockExec {
@@ -96,8 +54,8 @@ struct RefineBlockExec {
   __device__ __forceinline__ bool terms(int o, const float (&cam1)[12], const float (&cam)[12], float thresh2,
                                         float (&x)[REFINE_SUMS], int &n, bool &behind) const
   {
-    const float *P = A.points + 4 * (size_t)A.owner[o];
-    const RefineObs ob = A.obs[o];
+    const float *P = A.c.points + 4 * (size_t)A.c.owner[o];
+    const CandObs ob = A.c.obs[o];
     const float X[3] = {P[0], P[1], P[2]};
     if (!refine_member(cam1, k, X, ob.xpos, ob.ypos, thresh2)) return false;
     n++;
@@ -123,7 +81,7 @@ struct RefineBlockExec {
 #pragma unroll
       for (int u = 0; u < REFINE_AHEAD; u++) {
         const long long o = base + u * FUND_SLOTS;
-        key[u] = o < O ? A.key[o] : -1;
+        key[u] = o < O ? A.c.key[o] : -1;
       }
 #pragma unroll
       for (int u = 0; u < REFINE_AHEAD; u++) {
@@ -163,7 +121,7 @@ __global__ __launch_bounds__(REFINE_THREADS) void refine_cameras_kernel(RefineAr
   __shared__ float s_p[REFINE_SUMS * FUND_SLOTS];
   __shared__ int s_cnt[8];
   const int i = blockIdx.x, tid = threadIdx.x;
-  if (i == 0 && tid == 0) A.summary[0] = refine_T(A);
+  if (i == 0 && tid == 0) A.summary[0] = cand_T(A.c);
   const unsigned *bits = reinterpret_cast<const unsigned *>(A.cam) + 12 * (size_t)i;
   unsigned given[12];
   float cam_in[12];
@@ -176,7 +134,7 @@ __global__ __launch_bounds__(REFINE_THREADS) void refine_cameras_kernel(RefineAr
   const float k[4] = {A.intrinsics[4 * (size_t)i], A.intrinsics[4 * (size_t)i + 1], A.intrinsics[4 * (size_t)i + 2],
                       A.intrinsics[4 * (size_t)i + 3]};
   const bool fixed = pair == POSEGRAPH_ROOT || A.held[i] != 0;
-  RefineBlockExec ex{A, s_p, s_cnt, i, refine_O(A), k};
+  RefineBlockExec ex{A, s_p, s_cnt, i, cand_O(A.c), k};
   RefineResult r;
   refine_camera(ex, cam_in, pair == POSEGRAPH_UNSET, fixed, k, A.orthonormalise, A.min_obs, A.num_loops, A.thresh2, r);
   if (tid != 0) return;                        // every thread holds the same result; the input was read above
@@ -209,23 +167,22 @@ int launch_refine_cameras_batch(misift_ctx *ctx, int max_tracks, int max_obs, co
   const int rc = misift_ensure_tmp(ctx, refine_cameras_batch_tmp_bytes(max_obs));
   if (rc) return rc;
   RefineArgs A;
-  A.max_tracks = max_tracks; A.max_obs = max_obs; A.nimages = nimages; A.min_obs = min_obs; A.num_loops = num_loops;
-  A.orthonormalise = orthonormalise; A.thresh2 = thresh2;
-  A.track_offsets = d_track_offsets; A.obs = reinterpret_cast<const RefineObs *>(d_obs);
-  A.export_summary = d_export_summary; A.points = d_points;
-  A.point_status = d_point_status; A.cam = d_cam; A.cam_pair = d_cam_pair;
+  A.min_obs = min_obs; A.num_loops = num_loops; A.orthonormalise = orthonormalise; A.thresh2 = thresh2;
+  A.c.max_tracks = max_tracks; A.c.max_obs = max_obs; A.c.nimages = nimages;
+  A.c.track_offsets = d_track_offsets; A.c.obs = reinterpret_cast<const CandObs *>(d_obs);
+  A.c.export_summary = d_export_summary; A.c.points = d_points;
+  A.c.point_status = d_point_status; A.cam = d_cam; A.cam_pair = d_cam_pair;
   A.intrinsics = reinterpret_cast<const float *>(h_lists);
   A.held = reinterpret_cast<const int *>(A.intrinsics + 4 * (size_t)nimages);
-  A.owner = reinterpret_cast<int *>(ctx->d_match_tmp);
-  A.key = A.owner + max_obs;
+  A.c.owner = reinterpret_cast<int *>(ctx->d_match_tmp);
+  A.c.key = A.c.owner + max_obs;
   A.cam_out = d_cam_out; A.cam_obs = d_cam_obs; A.cam_rms = d_cam_rms; A.cam_steps = d_cam_steps;
   A.cam_status = d_cam_status; A.summary = d_summary;
-  HIP_TRY(hipMemsetAsync(A.owner, 0xff, sizeof(int) * (size_t)max_obs, ctx->stream));
+  HIP_TRY(hipMemsetAsync(A.c.owner, 0xff, sizeof(int) * (size_t)max_obs, ctx->stream));
   HIP_TRY(hipMemsetAsync(d_summary, 0, 8 * sizeof(int), ctx->stream));
-  const auto blocks = [](int n) { return dim3((unsigned)(((long long)n + REFINE_THREADS - 1) / REFINE_THREADS)); };
   LaunchScope ls(ctx, "refine_cameras");
-  hipLaunchKernelGGL(refine_owner_kernel, blocks(max_tracks), dim3(REFINE_THREADS), 0, ctx->stream, A);
-  hipLaunchKernelGGL(refine_key_kernel, blocks(max_obs), dim3(REFINE_THREADS), 0, ctx->stream, A);
+  hipLaunchKernelGGL(cand_owner_kernel, cand_blocks(max_tracks), dim3(CAND_THREADS), 0, ctx->stream, A.c);
+  hipLaunchKernelGGL(cand_key_kernel, cand_blocks(max_obs), dim3(CAND_THREADS), 0, ctx->stream, A.c);
   hipLaunchKernelGGL(refine_cameras_kernel, dim3(nimages), dim3(REFINE_THREADS), 0, ctx->stream, A);
   return ls.finish();
 }

@@ -2639,6 +2639,44 @@ extern "C" int misift_refine_cameras_batch(misift_ctx *ctx, int max_tracks, int 
                    });
 }
 
+// The camera of each selected image straight from its observations of the triangulated points, by batch RANSAC over
+// six-point solves: for the images the walk of misift_link_poses_batch did not reach, or as a second opinion.  The
+// intrinsics, the images and the seeds go to the pinned slot, in that order.
+extern "C" int misift_resect_cameras_batch(misift_ctx *ctx, int max_tracks, int max_obs, const int *d_track_offsets,
+                                           const misift_track_obs *d_obs, const int *d_export_summary,
+                                           const float *d_points, const int *d_point_status, int nimages,
+                                           const float *intrinsics, int nsel, const int *images, const unsigned *seeds,
+                                           int max_cand, int num_loops, float thresh, int min_inliers, int only_unset,
+                                           int install, float *d_cam, int *d_cam_pair, float *d_res_cam, int *d_res_cand,
+                                           int *d_res_inliers, int *d_res_status, int *d_summary)
+{
+  ARG_CHECK(ctx && max_tracks >= 1 && max_obs >= 1 && nimages >= 1);
+  ARG_CHECK(d_track_offsets && d_obs && d_export_summary && d_points && d_point_status && intrinsics);
+  ARG_CHECK(d_res_cam && d_res_cand && d_res_inliers && d_res_status && d_summary);
+  ARG_CHECK(((uintptr_t)d_obs & 15) == 0);
+  ARG_CHECK(nsel >= 0 && (nsel == 0 || (images && seeds)));
+  ARG_CHECK(max_cand >= 6 && num_loops >= 1 && min_inliers >= 6);
+  ARG_CHECK(thresh > 0.0f);                                                 // NaN fails too
+  ARG_CHECK((only_unset == 0 || only_unset == 1) && (install == 0 || install == 1));
+  ARG_CHECK(d_cam_pair || !(only_unset || install));
+  ARG_CHECK(d_cam || !install);
+  for (int i = 0; i < nimages; i++) ARG_CHECK(intrinsics_usable(intrinsics + 4 * (size_t)i, 1));
+  int rc = check_frames(__func__, nsel, images, 1, nimages, 0);
+  if (rc) return rc;
+  ARG_CHECK(resect_cameras_batch_one_launch(max_obs, nsel, max_cand, num_loops));
+  const float thresh2 = thresh * thresh;                                    // rounded once, here
+  RoctxRange range(__func__);
+  return run_batch(ctx, {{intrinsics, sizeof(float) * 4 * (size_t)nimages}, {images, sizeof(int) * (size_t)nsel},
+                         {seeds, sizeof(unsigned) * (size_t)nsel}},
+                   0, [&](int *h_lists, void *) {
+                     return launch_resect_cameras_batch(ctx, max_tracks, max_obs, d_track_offsets, d_obs,
+                                                        d_export_summary, d_points, d_point_status, nimages, nsel,
+                                                        h_lists, max_cand, num_loops, thresh2, min_inliers, only_unset,
+                                                        install, d_cam, d_cam_pair, d_res_cam, d_res_cand, d_res_inliers,
+                                                        d_res_status, d_summary);
+                   });
+}
+
 // ------------------------------------------------------------------- timing
 extern "C" int misift_timer_start(misift_ctx *ctx)
 {

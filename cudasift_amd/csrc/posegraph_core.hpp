@@ -11,6 +11,8 @@
 
 enum { POSEGRAPH_CHAIN = 0, POSEGRAPH_FAN = 1 };
 constexpr int POSEGRAPH_UNSET = -2, POSEGRAPH_ROOT = -1;
+// what misift_resect_cameras_batch (resect_core.hpp) puts into d_cam_pair: a camera placed by resection, not by a pair
+constexpr int POSEGRAPH_RESECTED = -3;
 
 // the rows of a pair that take part: min(max(count, 0), max_pts)
 FUND_HD int posegraph_rows(int count, int max_pts)

@@ -1231,6 +1231,112 @@ int misift_refine_cameras_batch(misift_ctx *ctx,
                                 int   *d_cam_status,            /* nimages */
                                 int   *d_summary);              /* 8 ints */
 
+/* The camera of an image estimated directly from the observations it makes of the triangulated track points, robustly
+ * (resection; no reference counterpart).  misift_link_poses_batch is the only other origin of a camera: an image its walk
+ * does not reach stays at d_cam_pair == -2 although its observations of known points sit in d_obs, and a camera it does
+ * place rests on one chain of two-view estimates, which misift_refine_cameras_batch can polish but not replace.  This call
+ * runs, per selected image, a RANSAC search over calibrated six-point solves and counts inliers with the member test of
+ * misift_refine_cameras_batch.  In the chain: ... export -> triangulate -> resect -> triangulate -> refine <-> triangulate.
+ *   d_track_offsets, d_obs and d_export_summary are what misift_export_tracks_batch wrote for max_tracks and max_obs,
+ *   d_points and d_point_status what misift_triangulate_tracks_batch wrote for them; intrinsics[4i..4i+3] = fx fy cx cy
+ *   of image i.  Entry e < nsel works on image i = images[e] with the seed seeds[e] and writes result slot e.
+ *   obs.record and d_points[4t+3] are not read.
+ *   The arithmetic is that of misift_refine_cameras_batch: fp32, every operation rounded, only + - * /, sqrtf and fabsf,
+ *   no contraction, a comparison with a NaN is false, everything taken left to right as written.  A single result that
+ *   is a NaN is stored as 0x7fc00000.  FINITE means fabsf(v) <= FLT_MAX.
+ *   T, O, valid tracks, the OWNER of a slot and the CANDIDATES of an image are those of misift_refine_cameras_batch,
+ *   word for word.
+ *   Per entry e, independently of every other entry:
+ *   1. Skip.  only_unset == 1 and d_cam_pair[i] != -2 (read on the device): status 3; d_res_cam[12e..] gets twelve zeros,
+ *      d_res_cand[e] = 0, d_res_inliers[e] = 0, and nothing else is done.
+ *   2. Candidates.  The candidates of image i in ascending slot index o; candidate p < n has (x, y) = d_obs[o_p].xpos,
+ *      .ypos and (X, Y, Z) = d_points[4t..4t+2] of the owner t of o_p.  d_res_cand[e] = n.  n > max_cand: status 4;
+ *      n < max(6, min_inliers): status 1.  Either way twelve zeros and d_res_inliers[e] = 0.
+ *   3. Draw.  rand() is glibc's after srand(seeds[e]) (as misift_find_homography_batch restates it).  The num_loops
+ *      hypotheses are drawn one after another from the one stream.  A hypothesis is six positions p_0 .. p_5: first
+ *      p_k = rand() % n for k = 0 .. 5; then for k = 1 .. 5 in turn, while p_k equals one of p_0 .. p_(k-1):
+ *      p_k = rand() % n.
+ *   4. Solve, per hypothesis, with (x_k, y_k, X_k, Y_k, Z_k) the candidate at position p_k:
+ *      a. u_k = (x_k - cx) / fx, v_k = (y_k - cy) / fy.  World normalisation: SX = 0 + X_0 + ... + X_5 one at a time,
+ *         SY and SZ likewise; c = (SX / 6, SY / 6, SZ / 6); dX = X_k - c0, dY = Y_k - c1, dZ = Z_k - c2;
+ *         d = 0 + sqrtf((dX*dX + dY*dY) + dZ*dZ) over k = 0 .. 5 one at a time; s = 10.3923048f / d (6 sqrt(3): the mean
+ *         distance to c becomes sqrt(3)); a_k = dX * s, b_k = dY * s, w_k = dZ * s.
+ *      b. The 11 x 12 system in the entries of P = [M | p], row-major 3 x 4 (column 4r + q holds P[r][q]).  Row 2k, the
+ *         u-row of point k = 0 .. 5:  ( a_k  b_k  w_k  1   0 0 0 0   -(u_k*a_k)  -(u_k*b_k)  -(u_k*w_k)  -u_k );
+ *         row 2k + 1, the v-row of point k = 0 .. 4:  ( 0 0 0 0   a_k  b_k  w_k  1   -(v_k*a_k)  -(v_k*b_k)  -(v_k*w_k)
+ *         -v_k ).  Point 5 has no v-row.  The null vector by the rule of step 2 of misift_find_fundamental_batch at
+ *         11 x 12: Gaussian elimination with complete pivoting, eleven steps; at step j the pivot is the entry of rows
+ *         j..10 x columns j..11 with the largest fabsf, searched row-major with a strict '>' (the first maximum wins, a
+ *         NaN never does; when nothing wins, the entry (j, j)); rows j and the pivot's change places, then the columns;
+ *         for every row r > j: f = A[r][j] / A[j][j], A[r][q] = A[r][q] - f * A[j][q] for q > j.  Then z_11 = 1 and, for
+ *         j = 10 .. 0, z_j = (-(0 + A[j][j+1]*z_(j+1) + ... + A[j][11]*z_11)) / A[j][j], the sum one term at a time in
+ *         ascending q; P = z with the column permutation undone.  A pivot that is zero or not FINITE makes the
+ *         hypothesis INVALID.
+ *      c. m = the largest fabsf of the twelve entries of P; an entry that is not FINITE, or m == 0: INVALID.
+ *         P = P / m per entry.  det = (P00*(P11*P22 - P12*P21) - P01*(P10*P22 - P12*P20)) + P02*(P10*P21 - P11*P20);
+ *         det == 0 or not FINITE: INVALID; det < 0: every entry of P is negated.
+ *         A = M (the left 3 x 3 of P), V = I; six sweeps of the one-sided Jacobi rotation of step 2 of
+ *         misift_recover_pose_batch over the column pairs (0,1), (0,2), (1,2), applied to A and V alike.
+ *         sigma_j = sqrtf(A0j*A0j + A1j*A1j + A2j*A2j); a sigma_j that is not FINITE and > 0: INVALID.
+ *         U[r][j] = A[r][j] / sigma_j; R[r][q] = (U[r][0]*V[q][0] + U[r][1]*V[q][1]) + U[r][2]*V[q][2], the nearest
+ *         rotation to M.  lambda = ((sigma_0 + sigma_1) + sigma_2) / 3; tn_r = P[r][3] / lambda;
+ *         t_r = tn_r / s - ((R[r][0]*c0 + R[r][1]*c1) + R[r][2]*c2), which undoes the world normalisation.
+ *         A component of (R, t) that is not FINITE: INVALID.
+ *      An INVALID hypothesis is twelve zeros, which no candidate fits (step 5 needs Xc.z > 0).
+ *   5. Count.  A candidate is an INLIER of a hypothesis (R, t) iff it is a MEMBER under it by step 2 of
+ *      misift_refine_cameras_batch with E2 = thresh*thresh rounded once on the host: Xc.z > 0 and ru*ru + rv*rv < E2
+ *      (E2 = +inf: Xc.z > 0 alone).  The count of a hypothesis runs over all n candidates.
+ *   6. Pick.  The hypothesis with the largest count, the smallest index among equals.  d_res_inliers[e] = its count.
+ *      count < min_inliers: status 2 and twelve zeros.  Otherwise status 0 and d_res_cam[12e..12e+11] = its R row-major,
+ *      then t (X_i = R . X_world + t, as d_cam).
+ *   7. Install.  install == 1 and status 0: d_cam[12i..12i+11] = the twelve floats and d_cam_pair[i] = -3,
+ *      MISIFT_CAM_RESECTED ("placed by resection").  misift_triangulate_tracks_batch and misift_refine_cameras_batch
+ *      treat every value but -2 as "has a camera" and only -1 as the root.  With any other status, or install == 0,
+ *      d_cam and d_cam_pair are not written.
+ *   d_res_status[e] = the status.  d_summary (8 ints, integer sums, so deterministic): [0] T, [1] entries with status 0,
+ *   [2] their inliers, [3] entries with status 1, [4] with status 2, [5] with status 3, [6] with status 4, [7] 0.
+ *   - Not done here: no minimal (P3P) solver: the six-point solve is degenerate for coplanar points, so a scene whose
+ *     points lie in a plane ends in status 2, and an image that sees the scene mostly through a plane may do so too.  No
+ *     local optimisation inside the search: misift_refine_cameras_batch with max_error = thresh is the polish.  The
+ *     intrinsics are taken as given.
+ *   - NULL ctx; max_tracks, max_obs or nimages < 1; NULL d_track_offsets, d_obs, d_export_summary, d_points,
+ *     d_point_status, intrinsics, d_res_cam, d_res_cand, d_res_inliers, d_res_status or d_summary; NULL d_cam_pair with
+ *     only_unset or install set, NULL d_cam with install set; d_obs not 16-byte aligned; nsel < 0, nsel > 0 with NULL
+ *     images or seeds, an image index outside [0, nimages) or listed twice; max_cand < 6; num_loops < 1; thresh NaN or
+ *     <= 0; min_inliers < 6; only_unset or install other than 0 or 1; an fx or fy that is not finite and > 0 or a cx or
+ *     cy that is not finite; nsel x ceil(num_loops / 64) x ceil(min(max_cand, max_obs) / 512) beyond 2^31 - 1 (one
+ *     launch), or num_loops beyond 2^31 - 16: MISIFT_EINVAL, before anything is enqueued.  nsel == 0 is no error: only
+ *     d_summary is written.  None of the inputs is written, except d_cam and d_cam_pair under install.
+ *   - The call runs on the context stream and returns before the GPU work is done; `intrinsics`, `images` and `seeds`
+ *     are copied; no host synchronisation and no host read.  Ordering behind batches in flight (K > 1): as
+ *     misift_match_batch.
+ *   - Two memsets and six launches whatever the data: the owners and the candidates as misift_refine_cameras_batch finds
+ *     them, then per entry the ordered candidate list and the draw, one lane per (entry, hypothesis) for the solve, one
+ *     64-lane workgroup per (entry, 64 hypotheses, 512 candidates) for the count, and the pick.  Temp memory from the
+ *     library's own allocator, sized from max_obs, nsel, max_cand and num_loops only: 8 bytes per slot, and per entry
+ *     20 bytes per candidate of min(max_cand, max_obs) and 76 bytes per hypothesis (both rounded up to 16). */
+#define MISIFT_CAM_RESECTED (-3)
+int misift_resect_cameras_batch(misift_ctx *ctx,
+                                int max_tracks, int max_obs,
+                                const int *d_track_offsets,     /* max_tracks + 1, from export */
+                                const misift_track_obs *d_obs,  /* max_obs, from export, 16-byte aligned */
+                                const int *d_export_summary,    /* 8 ints, from export: [2] = T, [3] = O */
+                                const float *d_points,          /* max_tracks x 4, from triangulate */
+                                const int *d_point_status,      /* max_tracks, from triangulate */
+                                int nimages,
+                                const float *intrinsics,        /* host, nimages x 4: fx fy cx cy, copied */
+                                int nsel, const int *images,    /* host, nsel distinct image indices, copied */
+                                const unsigned *seeds,          /* host, nsel, copied */
+                                int max_cand, int num_loops, float thresh /* px */, int min_inliers,
+                                int only_unset, int install,
+                                float *d_cam,                   /* nimages x 12: written when install */
+                                int   *d_cam_pair,              /* nimages: read when only_unset, written when install */
+                                float *d_res_cam,               /* nsel x 12 */
+                                int   *d_res_cand,              /* nsel */
+                                int   *d_res_inliers,           /* nsel */
+                                int   *d_res_status,            /* nsel */
+                                int   *d_summary);              /* 8 ints */
+
 /* cudaMallocManaged as used by the reference's MANAGEDMEM build flavour (cudaSiftH.cu:239-240): one pointer valid on
  * host and device (SiftData.m_data). */
 int misift_malloc_managed(size_t bytes, void **out);
@@ -1319,6 +1425,12 @@ int misift_test_refine_camera(const float *cam12, int cam_pair, int held, const 
                               const int *slot, const float *X, const float *xy, int min_obs, int num_loops,
                               float max_error, int orthonormalise, float *cam_out12, int *nobs, float *rms2, int *steps,
                               int *status);
+/* Test-only, host-only: steps 3 and 4 of misift_resect_cameras_batch, compiled from the functions its kernels run.  The
+ * sample positions: out[6 * loop + j] = position j (in the ordered list of n >= 6 candidates) of hypothesis loop after
+ * srand(seed).  The six-point solve of one sample xyXYZ[5k..5k+4] = x y X Y Z of point k < 6 under intrinsics4 = fx fy cx
+ * cy: cam12 = R row-major then t (twelve zeros when invalid) and *valid = 0 / 1. */
+int misift_test_resect_samples(unsigned seed, int n, int num_loops, int *out);
+int misift_test_resect_solve(const float *xyXYZ, const float *intrinsics4, float *cam12, int *valid);
 /* Test-only, host-only: the gate and the gather of misift_match_epipolar_batch, compiled from the same headers and
  * functions as the kernel.  xy1: n1 set-1 positions (x, y), xy2: n2 set-2 positions.  gate: pass[i * n2 + j] = 1 iff
  * record j is a candidate of row i under F9 and radius.  gather: builds the cell grid of xy2 as the bin launch does
