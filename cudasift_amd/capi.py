@@ -157,6 +157,7 @@ SIGNATURES = {
     "misift_test_knob_names": (C.c_char_p, []),
     "misift_test_set_guard": (_i, [_i]),
     "misift_test_check_guards": (_i, [C.POINTER(_i)]),
+    "misift_test_ctx_state": (C.c_longlong, [_vp, _i]),
     "misift_comm_unique_id": (_i, [_vp]),
     "misift_comm_create": (_i, [_vp, _i, _i, _vp, C.POINTER(_vp)]),
     "misift_comm_adopt": (_i, [_vp, _vp, C.POINTER(_vp)]),
@@ -343,6 +344,14 @@ class Context:
     def set_knob(self, name, value):
         """Developer / test knob of this context (misift_test_set_knob; capi.knob_names() lists them)."""
         check(lib().misift_test_set_knob(self.h, name.encode(), float(value)), "misift_test_set_knob")
+
+    def test_state(self, which):
+        """Host state of this context (misift_test_ctx_state; no HIP call): 0 the bytes of the shared temp, 1 the slots of
+        the pinned ring of host lists, 2 the slots handed out so far."""
+        v = lib().misift_test_ctx_state(self.h, which)
+        if v < 0:
+            raise MisiftError("misift_test_ctx_state(%d): %s" % (which, lib().misift_last_error().decode()))
+        return int(v)
 
     def set_early_return(self, on=True):
         """Synchronous calls return at the last kernel's completion flag instead of after a stream synchronisation."""

@@ -2092,6 +2092,18 @@ static int mb_ring_slot(misift_ctx *ctx, size_t bytes, int *slot_out)
   return MISIFT_OK;
 }
 
+// Test-only, host state only (no HIP call, no sync): what a test of the shared temp and the ring reasons about.
+extern "C" long long misift_test_ctx_state(misift_ctx *ctx, int which)
+{
+  if (!ctx || which < 0 || which > 2) {
+    misift_set_error("misift_test_ctx_state: invalid argument");
+    return MISIFT_EINVAL;
+  }
+  if (which == 0) return (long long)ctx->match_tmp_bytes;
+  if (which == 1) return CtxExtra::MB_RING;
+  return (long long)extra(ctx)->mb_next;
+}
+
 // The device plan of misift_match_batch / misift_match_batch_i8 (grow-only, stream-ordered like the calls that use it).
 static int ensure_mb_plan(misift_ctx *ctx, size_t bytes)
 {

@@ -1491,6 +1491,11 @@ const char *misift_test_knob_names(void);
 int misift_test_set_guard(int on);                 /* returns the previous mode */
 int misift_test_check_guards(int *allocations);    /* allocations (optional): how many were checked */
 
+/* Test-only, host state only (no HIP call, no synchronisation): which = 0: the bytes of the context's shared temporary
+ * buffer as it stands (it only grows); which = 1: the slots of the pinned ring the batch calls copy their host lists
+ * to; which = 2: the slots handed out so far (every batch call takes one, a call without a list an empty one).  MISIFT_EINVAL otherwise. */
+long long misift_test_ctx_state(misift_ctx *ctx, int which);
+
 /* ------------------------------------------------------------------- timing */
 
 /* TimerGPU (cudautils.h:61-81): event pair on the context stream. */

@@ -7,7 +7,7 @@ import ctypes as C
 
 import numpy as np
 
-from synth import descriptors_to_points, synth_descriptors
+from synth import descriptors_to_points, synth_descriptors, synth_matches
 
 MATCH_FIELDS = ("score", "ambiguity", "match", "match_xpos", "match_ypos")
 # the pair-indexed matchers: the fields of an output row, and what their output, counts and num_matched are filled with
@@ -111,6 +111,55 @@ def guarded_context(min_checked):
             g.close()
     finally:
         capi.set_guard(old)
+
+
+# ---- fabricated tracks and records (misift_link_tracks_batch, misift_export_tracks_batch)
+
+def planted_members(sizes, usable, lengths, rng):
+    """Planted tracks: track t visits lengths[t] consecutive usable frames from a random start, taking one record nobody
+    else has in each frame that still has one."""
+    free = {f: list(rng.permutation(sizes[f])) for f in usable}
+    out = []
+    for L in lengths:
+        a = int(rng.integers(0, max(len(usable) - L, 0) + 1))
+        t = {}
+        for f in usable[a:a + L]:
+            if free[f]:
+                t[f] = int(free[f].pop())
+        out.append(t)
+    return out
+
+
+def fabricated_records(n, seed):
+    """n records whose xpos / ypos are random bit patterns (NaN payloads, infinities, denormals); the rest zero."""
+    from cudasift_amd import capi
+    recs = np.zeros(max(n, 1), capi.POINT_DTYPE)
+    bits = np.random.default_rng(seed).integers(0, 2 ** 32, (2, len(recs)), dtype=np.uint64).astype(np.uint32)
+    recs["xpos"], recs["ypos"] = bits[0].view(np.float32), bits[1].view(np.float32)
+    return recs
+
+
+def xy_bits(recs):
+    """What expected_export takes: the bits of xpos / ypos per record, as they sit in the array that is uploaded."""
+    return np.stack([np.ascontiguousarray(recs[k]).view(np.uint32) for k in ("xpos", "ypos")], 1)
+
+
+# ---- frames of stored matches (the homography batches)
+
+def matched_frames(sizes, seed):
+    from cudasift_amd import capi
+    out = []
+    for f, n in enumerate(sizes):
+        out.append(synth_matches(n, seed=seed * 100 + f)[0] if n else np.zeros(0, capi.POINT_DTYPE))
+    return out
+
+
+def gated_frame(n, seed, valid):
+    """n records of which exactly `valid` pass the gate 0.85 / 0.95; the others (spread over the frame) have score 0."""
+    p = synth_matches(n, seed=seed)[0]
+    p["score"], p["ambiguity"] = 0.99, 0.5
+    p["score"][np.linspace(0, n - 1, n - valid).astype(int)] = 0.0
+    return p
 
 
 # ---- expected answers, restated in numpy

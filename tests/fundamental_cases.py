@@ -7,7 +7,8 @@ distance underflows to where every product overflows, F matrices a caller may ha
 leaves the float range, and scenes in which a tenth of the records carry a hostile position."""
 import numpy as np
 
-from test_fundamental_cpu import f32, planted_scene, solve8
+from batch_util import span
+from test_fundamental_cpu import GATES, expected_find, expected_score, f32, planted_scene, solve8
 
 POS = ("xpos", "ypos", "match_xpos", "match_ypos")
 TINY = np.finfo(np.float32).tiny                                 # the smallest normal float32
@@ -209,3 +210,78 @@ def mixed_scene(seed, n=600):
     for i, r in enumerate(rows):
         recs[POS[int(rng.integers(0, 4))]][r] = HOSTILE[i % len(HOSTILE)]
     return recs, inl, hostile
+
+
+# ---- the batches of test_gpu_fundamental.py and test_gpu_fundamental_refine.py
+
+NOISE = 0.5                                                      # px, on the positions of the refinement's scenes
+
+MAX_PTS = 2000
+# frame -> records held; frame 10 has count -1, frame 11 one record more than max_pts, frames 12..14 are gated down to
+# 7, 8 and 9 valid records; frame 15 is in no entry
+SIZES = [0, 7, 8, 9, 63, 64, 65, 512, 513, 2000, 40, MAX_PTS + 1, 100, 100, 100, 30]
+COUNTS = SIZES[:10] + [-1] + SIZES[11:]
+SEL = [9, 3, 12, 0, 14, 7, 11, 1, 13, 5, 10, 2, 8, 4, 6]         # not in frame order
+SEEDS = [1, 2, 3, 0, 2**32 - 1, 12345, 7, 8, 9, 10, 11, 2**31, 13, 14, 15]
+
+
+def batch_records(n, seed, keep=None):
+    """n records of a planted scene with every byte outside the fields in play random; from 10 records on a fifth of them
+    fails the gate (keep: exactly that many pass)."""
+    rng = np.random.default_rng(1000 + seed)
+    from cudasift_amd import capi
+    recs = np.frombuffer(rng.bytes(576 * n), capi.POINT_DTYPE).copy()
+    if n == 0:
+        return recs
+    scene, _, _ = planted_scene(seed, n=n)
+    for k in ("xpos", "ypos", "match_xpos", "match_ypos", "score", "ambiguity", "match", "match_error"):
+        recs[k] = scene[k]
+    if keep is None:
+        fail = (rng.random(n) < 0.2) & (n >= 10)                 # the frames of 8 and 9 records keep them all
+    else:
+        fail = np.ones(n, bool)
+        fail[rng.choice(n, keep, replace=False)] = False
+    recs["score"][fail & (rng.random(n) < 0.5)] = 0.85           # score == min_score: rejected
+    recs["ambiguity"][fail & (recs["score"] > 0.85)] = 0.95      # ambiguity == max_ambiguity: rejected
+    return recs
+
+
+def make_batch():
+    keep = {12: 7, 13: 8, 14: 9}
+    return [batch_records(n, f, keep.get(f)) for f, n in enumerate(SIZES)]
+
+
+def expected_find_score(sel, seeds, recs, counts, offs, stride, loops, thresh, max_pts):
+    F, num, fit = np.zeros((len(sel), 9), np.float32), np.zeros(len(sel), np.int32), np.zeros(len(sel), np.int32)
+    after = recs.copy()
+    for i, (f, s) in enumerate(zip(sel, seeds)):
+        n = int(counts[f])
+        sl = span(offs, stride, f, max(n, 0))
+        F[i], num[i] = expected_find(recs[sl], n, s, loops, *GATES, thresh, max_pts)
+        after[sl], fit[i] = expected_score(recs[sl], n, F[i], *GATES, thresh)
+    return F, num, after, fit
+
+
+def noisy_records(n, seed):
+    """n records of a noisy planted scene with every byte outside the fields in play random; from 10 records on a fifth
+    of them fails the gate."""
+    from cudasift_amd import capi
+    rng = np.random.default_rng(2000 + seed)
+    recs = np.frombuffer(rng.bytes(576 * n), capi.POINT_DTYPE).copy()
+    if n == 0:
+        return recs
+    scene, _, _ = planted_scene(seed, n=n, noise=NOISE)
+    for k in ("xpos", "ypos", "match_xpos", "match_ypos", "score", "ambiguity", "match", "match_error"):
+        recs[k] = scene[k]
+    fail = (rng.random(n) < 0.2) & (n >= 10)
+    recs["score"][fail & (rng.random(n) < 0.5)] = 0.85           # score == min_score: rejected
+    recs["ambiguity"][fail & (recs["score"] > 0.85)] = 0.95      # ambiguity == max_ambiguity: rejected
+    return recs
+
+
+def start_F(recs, seed):
+    """A start F: the best of 32 hypotheses; below 8 records (find gives zeros) the scene's ground truth."""
+    if len(recs) >= 8:
+        return expected_find(recs, len(recs), seed, 32, *GATES, 1.0, max_pts=len(recs))[0]
+    Fgt = planted_scene(seed, n=8)[2]
+    return (Fgt / np.abs(Fgt).max()).astype(np.float32).reshape(9)

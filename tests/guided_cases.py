@@ -574,17 +574,89 @@ def scene(kind, name):
             "leaving": _leaving, "radius_small": _radius_small, "radius_huge": _radius_huge}[name](kind)
 
 
+# ---- the calls restated from their contracts (what test_gpu_guided_match.py and test_gpu_epipolar_match.py hold the
+# device to): the gate in numpy float32, then the oracle's exact, full matcher on the candidates in index order
+
+def expected_guided(pairs, Hs, radius, max_pts, recs1, counts1, offs1, stride1, recs2, counts2, offs2, stride2):
+    """Set 1 and num_found after misift_match_guided_batch, restated from the contract with the oracle's matcher."""
+    from batch_util import orc, span
+    o = orc()
+    exp = recs1.copy()
+    nf = np.zeros(len(pairs), np.int32)
+    r2 = np.float32(radius) * np.float32(radius)
+    for i, (f1, f2) in enumerate(pairs):
+        n1, n2 = max(int(counts1[f1]), 0), max(int(counts2[f2]), 0)
+        if n1 > max_pts or n2 > max_pts:
+            nf[i] = -1
+            continue
+        if n1 == 0 or n2 == 0:
+            continue
+        s1 = span(offs1, stride1, f1, n1)
+        p1 = exp[s1].copy()
+        p2 = recs2[span(offs2, stride2, f2, n2)]
+        h = np.asarray(Hs[i], np.float32).reshape(9)
+        x, y = p1["xpos"], p1["ypos"]
+        with np.errstate(all="ignore"):
+            den = h[6] * x + h[7] * y + h[8]
+            px = (h[0] * x + h[1] * y + h[2]) / den
+            py = (h[3] * x + h[4] * y + h[5]) / den
+            for r in range(n1):
+                dx = px[r] - p2["xpos"]
+                dy = py[r] - p2["ypos"]
+                cand = np.nonzero(dx * dx + dy * dy < r2)[0]
+                row = p1[r:r + 1]
+                if len(cand) == 0:
+                    row["score"], row["ambiguity"], row["match"] = 0.0, 0.0, -1
+                    row["match_xpos"], row["match_ypos"] = 0.0, 0.0
+                    continue
+                o.match(row, 1, p2[cand].copy(), len(cand), full=True, exact=True)
+                if row["match"][0] >= 0:
+                    row["match"] = cand[row["match"][0]]
+                    nf[i] += 1
+        exp[s1] = p1
+    return exp, nf
+
+
+def expected_epipolar(pairs, Fs, radius, max_pts, recs1, counts1, offs1, stride1, recs2, counts2, offs2, stride2):
+    """Set 1 and num_found after misift_match_epipolar_batch, restated from the contract with the oracle's matcher."""
+    from batch_util import orc, span
+    o = orc()
+    exp = recs1.copy()
+    nf = np.zeros(len(pairs), np.int32)
+    for i, (f1, f2) in enumerate(pairs):
+        n1, n2 = max(int(counts1[f1]), 0), max(int(counts2[f2]), 0)
+        if n1 > max_pts or n2 > max_pts:
+            nf[i] = -1
+            continue
+        if n1 == 0 or n2 == 0:
+            continue
+        s1 = span(offs1, stride1, f1, n1)
+        p1 = exp[s1].copy()
+        p2 = recs2[span(offs2, stride2, f2, n2)]
+        gate = gate_np(Fs[i], p1["xpos"], p1["ypos"], p2["xpos"], p2["ypos"], radius)
+        for r in range(n1):
+            cand = np.nonzero(gate[r])[0]
+            row = p1[r:r + 1]
+            if len(cand) == 0:
+                row["score"], row["ambiguity"], row["match"] = 0.0, 0.0, -1
+                row["match_xpos"], row["match_ypos"] = 0.0, 0.0
+                continue
+            o.match(row, 1, p2[cand], len(cand), full=True, exact=True)      # p2[cand] is a fresh array
+            if row["match"][0] >= 0:
+                row["match"] = cand[row["match"][0]]
+                nf[i] += 1
+        exp[s1] = p1
+    return exp, nf
+
+
 # ---- the expected answers, computed once per scene
 
 @functools.lru_cache(maxsize=None)
 def expected(kind, name):
-    """(scene, packed set 1, its offsets, packed set 2, its offsets, expected set-1 frames, expected num_found) from the
-    restatement of test_gpu_guided_match.py or test_gpu_epipolar_match.py; the arrays are shared: leave them unchanged."""
+    """(scene, packed set 1, its offsets, packed set 2, its offsets, expected set-1 frames, expected num_found) from
+    expected_guided or expected_epipolar; the arrays are shared: leave them unchanged."""
     from batch_util import layout, span
-    if kind == "guided":
-        from test_gpu_guided_match import _expected
-    else:
-        from test_gpu_epipolar_match import _expected
+    _expected = expected_guided if kind == "guided" else expected_epipolar
     s = scene(kind, name)
     r1, o1, _ = layout(s.fr1, s.counts1, False, min_stride=0, pad_error=0.0)
     r2, o2, _ = layout(s.fr2, s.counts2, False, min_stride=0, pad_error=0.0)

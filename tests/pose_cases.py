@@ -235,6 +235,14 @@ def planted(seed, n=64, k2=K_A, angle=0.3, tscale=1.0, fit=False, fscale=1.0, no
     return dict(recs=records(xy, seed), F=F, K8=np.array(K_A + tuple(k2), f32), R=R, t=t, inl=inl, xy=xy)
 
 
+def planted_frame(n, seed, k2):
+    """n records of a planted scene, a fifth of them wrong matches and (from 10 records on) a tenth failing the gate, with
+    the scene's exact F and intrinsics."""
+    s = planted(seed=seed, n=max(n, 1), k2=k2, outliers=0.2 if n >= 10 else 0.0)
+    recs = records(s["xy"], seed, fail=0.1 if n >= 10 else 0.0)[:n]
+    return recs, s["F"], s["K8"]
+
+
 def scenes():
     """The grid of the planted scenes, three seeds each: K2 = K1 or not, 0.01 or 0.3 rad, |t| 0.05 or 1, F exact or fitted,
     and the scale of F from 1e-3 to 1e3.  (name, keyword arguments of planted())."""

@@ -12,7 +12,7 @@ from test_fundamental_cpu import (GATES, SCENE_FIND_SEED, SCENE_LOOPS, SCENE_SEE
 
 SLOTS = 256
 SQRT2 = f32(1.41421354)                                          # as the header writes it
-NOISE = 0.5
+NOISE = FC.NOISE
 LOOPS = (0, 1, 2, 5)
 COUNTS = (0, 7, 8, 9, 255, 256, 257, 511, 512, 513, 1025)
 POS = FC.POS

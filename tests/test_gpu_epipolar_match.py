@@ -1,16 +1,17 @@
 """misift_match_epipolar_batch: epipolar-guided matching of many frame pairs of device-resident batches.
 
 Every row of set 1 is matched only against the set-2 records within `radius` of its epipolar line under the pair's F.
-The expected records are restated here from the contract: the gate in numpy float32 (epipolar_util.gate_np: every
-operation rounded, sums left to right), then the oracle's exact, full matcher on the row's candidates in ascending index
+The expected records are restated from the contract (guided_cases.expected_epipolar): the gate in numpy float32
+(epipolar_util.gate_np: every operation rounded, sums left to right), then the oracle's exact, full matcher on the row's candidates in ascending index
 order.  All bytes of both sets are compared: only the five match fields of set-1 rows of some pair may change."""
 import functools
 
 import numpy as np
 import pytest
 
-from batch_util import MATCH_FIELDS, frames, guarded_context, layout, orc, same_bytes, span
-from epipolar_util import STEREO, STEREO_V, f32, gate_np, planted_F, points_on_lines
+from batch_util import MATCH_FIELDS, frames, guarded_context, layout, same_bytes, span
+from epipolar_util import STEREO, STEREO_V, f32, planted_F, points_on_lines
+from guided_cases import expected_epipolar as _expected
 from synth import descriptors_to_points, synth_descriptors
 
 pytestmark = pytest.mark.gpu
@@ -47,37 +48,6 @@ def _plant(fr1, fr2, pairs, Fs, seed):
         dup = dup[dup + 1 < len(b)]
         for k2 in ("xpos", "ypos", "data"):
             b[k2][dup + 1] = b[k2][dup]
-
-
-def _expected(pairs, Fs, radius, max_pts, recs1, counts1, offs1, stride1, recs2, counts2, offs2, stride2):
-    """Set 1 and num_found after misift_match_epipolar_batch, restated from the contract with the oracle's matcher."""
-    o = orc()
-    exp = recs1.copy()
-    nf = np.zeros(len(pairs), np.int32)
-    for i, (f1, f2) in enumerate(pairs):
-        n1, n2 = max(int(counts1[f1]), 0), max(int(counts2[f2]), 0)
-        if n1 > max_pts or n2 > max_pts:
-            nf[i] = -1
-            continue
-        if n1 == 0 or n2 == 0:
-            continue
-        s1 = span(offs1, stride1, f1, n1)
-        p1 = exp[s1].copy()
-        p2 = recs2[span(offs2, stride2, f2, n2)]
-        gate = gate_np(Fs[i], p1["xpos"], p1["ypos"], p2["xpos"], p2["ypos"], radius)
-        for r in range(n1):
-            cand = np.nonzero(gate[r])[0]
-            row = p1[r:r + 1]
-            if len(cand) == 0:
-                row["score"], row["ambiguity"], row["match"] = 0.0, 0.0, -1
-                row["match_xpos"], row["match_ypos"] = 0.0, 0.0
-                continue
-            o.match(row, 1, p2[cand], len(cand), full=True, exact=True)      # p2[cand] is a fresh array
-            if row["match"][0] >= 0:
-                row["match"] = cand[row["match"][0]]
-                nf[i] += 1
-        exp[s1] = p1
-    return exp, nf
 
 
 def _run(c, pairs, Fs, radius, recs1, counts1, offs1, stride1, recs2=None, counts2=None, offs2=None, stride2=0,

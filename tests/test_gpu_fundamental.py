@@ -8,6 +8,8 @@ import numpy as np
 import pytest
 
 from batch_util import POISON_WORD, guarded_context, layout, span
+from fundamental_cases import (COUNTS, MAX_PTS, SEEDS, SEL, SIZES, batch_records as _records,
+                               expected_find_score as _expected, make_batch)
 from test_fundamental_cpu import (GATES, SCENE_FIND_SEED, SCENE_LOOPS, SCENE_SEEDS, expected_find, expected_score,
                                   planted_scene)
 from test_tracks_cpu import INF, blank_rows, expected_tracks, plant, set_edge, window_pairs
@@ -15,45 +17,12 @@ from test_tracks_cpu import INF, blank_rows, expected_tracks, plant, set_edge, w
 pytestmark = pytest.mark.gpu
 
 MISIFT_OK, MISIFT_EINVAL = 0, -1
-MAX_PTS = 2000
-# frame -> records held; frame 10 has count -1, frame 11 one record more than max_pts, frames 12..14 are gated down to
-# 7, 8 and 9 valid records; frame 15 is in no entry
-SIZES = [0, 7, 8, 9, 63, 64, 65, 512, 513, 2000, 40, MAX_PTS + 1, 100, 100, 100, 30]
-COUNTS = SIZES[:10] + [-1] + SIZES[11:]
-SEL = [9, 3, 12, 0, 14, 7, 11, 1, 13, 5, 10, 2, 8, 4, 6]         # not in frame order
-SEEDS = [1, 2, 3, 0, 2**32 - 1, 12345, 7, 8, 9, 10, 11, 2**31, 13, 14, 15]
 
 
 @pytest.fixture(scope="module")
 def g():
     with guarded_context(1) as c:
         yield c
-
-
-def _records(n, seed, keep=None):
-    """n records of a planted scene with every byte outside the fields in play random; from 10 records on a fifth of them
-    fails the gate (keep: exactly that many pass)."""
-    rng = np.random.default_rng(1000 + seed)
-    from cudasift_amd import capi
-    recs = np.frombuffer(rng.bytes(576 * n), capi.POINT_DTYPE).copy()
-    if n == 0:
-        return recs
-    scene, _, _ = planted_scene(seed, n=n)
-    for k in ("xpos", "ypos", "match_xpos", "match_ypos", "score", "ambiguity", "match", "match_error"):
-        recs[k] = scene[k]
-    if keep is None:
-        fail = (rng.random(n) < 0.2) & (n >= 10)                 # the frames of 8 and 9 records keep them all
-    else:
-        fail = np.ones(n, bool)
-        fail[rng.choice(n, keep, replace=False)] = False
-    recs["score"][fail & (rng.random(n) < 0.5)] = 0.85           # score == min_score: rejected
-    recs["ambiguity"][fail & (recs["score"] > 0.85)] = 0.95      # ambiguity == max_ambiguity: rejected
-    return recs
-
-
-def make_batch():
-    keep = {12: 7, 13: 8, 14: 9}
-    return [_records(n, f, keep.get(f)) for f, n in enumerate(SIZES)]
 
 
 @pytest.fixture(scope="module")
@@ -83,17 +52,6 @@ def _find_score(ctx, sel, seeds, recs, counts, offs, stride, loops, thresh, max_
     ctx.sync()
     return (ctx.download(dF, (len(sel), 9), np.float32), ctx.download(dn, (len(sel),), np.int32), mid,
             ctx.download(d, (len(recs),), capi.POINT_DTYPE), ctx.download(dfit, (len(sel),), np.int32))
-
-
-def _expected(sel, seeds, recs, counts, offs, stride, loops, thresh, max_pts):
-    F, num, fit = np.zeros((len(sel), 9), np.float32), np.zeros(len(sel), np.int32), np.zeros(len(sel), np.int32)
-    after = recs.copy()
-    for i, (f, s) in enumerate(zip(sel, seeds)):
-        n = int(counts[f])
-        sl = span(offs, stride, f, max(n, 0))
-        F[i], num[i] = expected_find(recs[sl], n, s, loops, *GATES, thresh, max_pts)
-        after[sl], fit[i] = expected_score(recs[sl], n, F[i], *GATES, thresh)
-    return F, num, after, fit
 
 
 def _check(ctx, sel, seeds, recs, counts, offs, stride, loops, thresh=1.0, max_pts=MAX_PTS, what=""):

@@ -10,7 +10,8 @@ import numpy as np
 import pytest
 
 from batch_util import POISON_WORD, guarded_context, layout, span
-from test_fundamental_cpu import GATES, expected_find, planted_scene
+from fundamental_cases import noisy_records as _records, start_F as _start
+from test_fundamental_cpu import GATES, expected_find
 from test_fundamental_refine_cpu import LOOPS, NOISE, expected_improve, hostile_cases
 from test_gpu_fundamental import _multi_view
 from test_tracks_cpu import INF, blank_rows, expected_tracks, plant, set_edge, window_pairs
@@ -29,31 +30,6 @@ def capacity():
 def g():
     with guarded_context(1) as c:
         yield c
-
-
-def _records(n, seed):
-    """n records of a noisy planted scene with every byte outside the fields in play random; from 10 records on a fifth
-    of them fails the gate."""
-    from cudasift_amd import capi
-    rng = np.random.default_rng(2000 + seed)
-    recs = np.frombuffer(rng.bytes(576 * n), capi.POINT_DTYPE).copy()
-    if n == 0:
-        return recs
-    scene, _, _ = planted_scene(seed, n=n, noise=NOISE)
-    for k in ("xpos", "ypos", "match_xpos", "match_ypos", "score", "ambiguity", "match", "match_error"):
-        recs[k] = scene[k]
-    fail = (rng.random(n) < 0.2) & (n >= 10)
-    recs["score"][fail & (rng.random(n) < 0.5)] = 0.85           # score == min_score: rejected
-    recs["ambiguity"][fail & (recs["score"] > 0.85)] = 0.95      # ambiguity == max_ambiguity: rejected
-    return recs
-
-
-def _start(recs, seed):
-    """A start F: the best of 32 hypotheses; below 8 records (find gives zeros) the scene's ground truth."""
-    if len(recs) >= 8:
-        return expected_find(recs, len(recs), seed, 32, *GATES, 1.0, max_pts=len(recs))[0]
-    Fgt = planted_scene(seed, n=8)[2]
-    return (Fgt / np.abs(Fgt).max()).astype(np.float32).reshape(9)
 
 
 @pytest.fixture(scope="module")

@@ -1,13 +1,14 @@
 """misift_match_guided_batch: homography-guided matching of many frame pairs of device-resident batches.
 
 Every row of set 1 is matched only against the set-2 records within `radius` of its projection through the pair's H.
-The expected records are restated here from the contract: the gate in numpy float32 (every operation rounded, C's
-left-to-right order), then the oracle's exact, full matcher on the row's candidates in ascending index order.  All bytes
+The expected records are restated from the contract (guided_cases.expected_guided): the gate in numpy float32 (every
+operation rounded, C's left-to-right order), then the oracle's exact, full matcher on the row's candidates in ascending index order.  All bytes
 of both sets are compared: only the five match fields of set-1 rows of some pair may change."""
 import numpy as np
 import pytest
 
-from batch_util import MATCH_FIELDS, frames, guarded_context, layout, orc, same_bytes, span
+from batch_util import MATCH_FIELDS, frames, guarded_context, layout, same_bytes, span
+from guided_cases import expected_guided as _expected
 from synth import descriptors_to_points, synth_descriptors, synth_frame
 
 pytestmark = pytest.mark.gpu
@@ -50,45 +51,6 @@ def _plant(fr1, fr2, pairs, Hs, seed):
         dup = dup[dup + 1 < len(b)]
         for k2 in ("xpos", "ypos", "data"):
             b[k2][dup + 1] = b[k2][dup]
-
-
-def _expected(pairs, Hs, radius, max_pts, recs1, counts1, offs1, stride1, recs2, counts2, offs2, stride2):
-    """Set 1 and num_found after misift_match_guided_batch, restated from the contract with the oracle's matcher."""
-    o = orc()
-    exp = recs1.copy()
-    nf = np.zeros(len(pairs), np.int32)
-    r2 = np.float32(radius) * np.float32(radius)
-    for i, (f1, f2) in enumerate(pairs):
-        n1, n2 = max(int(counts1[f1]), 0), max(int(counts2[f2]), 0)
-        if n1 > max_pts or n2 > max_pts:
-            nf[i] = -1
-            continue
-        if n1 == 0 or n2 == 0:
-            continue
-        s1 = span(offs1, stride1, f1, n1)
-        p1 = exp[s1].copy()
-        p2 = recs2[span(offs2, stride2, f2, n2)]
-        h = np.asarray(Hs[i], np.float32).reshape(9)
-        x, y = p1["xpos"], p1["ypos"]
-        with np.errstate(all="ignore"):
-            den = h[6] * x + h[7] * y + h[8]
-            px = (h[0] * x + h[1] * y + h[2]) / den
-            py = (h[3] * x + h[4] * y + h[5]) / den
-            for r in range(n1):
-                dx = px[r] - p2["xpos"]
-                dy = py[r] - p2["ypos"]
-                cand = np.nonzero(dx * dx + dy * dy < r2)[0]
-                row = p1[r:r + 1]
-                if len(cand) == 0:
-                    row["score"], row["ambiguity"], row["match"] = 0.0, 0.0, -1
-                    row["match_xpos"], row["match_ypos"] = 0.0, 0.0
-                    continue
-                o.match(row, 1, p2[cand].copy(), len(cand), full=True, exact=True)
-                if row["match"][0] >= 0:
-                    row["match"] = cand[row["match"][0]]
-                    nf[i] += 1
-        exp[s1] = p1
-    return exp, nf
 
 
 def _run(c, pairs, Hs, radius, recs1, counts1, offs1, stride1, recs2=None, counts2=None, offs2=None, stride2=0,

@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from batch_util import guarded_context, layout, orc, span
+from batch_util import gated_frame as _gated, guarded_context, layout, matched_frames as _frames, orc, span
 from synth import synth_frame, synth_matches
 
 pytestmark = pytest.mark.gpu
@@ -18,14 +18,6 @@ SIZES = [0, 7, 8, 40, 777, 1500, 5000]
 FIND = dict(min_score=0.85, max_ambiguity=0.95, thresh=5.0)
 IMPROVE = dict(min_score=0.0, max_ambiguity=0.80, thresh=3.0)
 IDENTITY = np.eye(3, dtype=np.float32)
-
-
-def _frames(sizes, seed):
-    from cudasift_amd import capi
-    out = []
-    for f, n in enumerate(sizes):
-        out.append(synth_matches(n, seed=seed * 100 + f)[0] if n else np.zeros(0, capi.POINT_DTYPE))
-    return out
 
 
 def _bits(a):
@@ -172,14 +164,6 @@ def test_count_above_max_pts_guarded(ctx):
         He, ne = _single_find(ctx, recs[span(offs, 0, f, int(counts[f]))].copy(), int(counts[f]), i + 1, 1000,
                               oracle=False)
         assert nm[i] == ne and np.array_equal(_bits(H[i]), _bits(He)), (i, nm[i], ne)
-
-
-def _gated(n, seed, valid):
-    """n records of which exactly `valid` pass FIND's gate; the others (spread over the frame) have score 0."""
-    p = synth_matches(n, seed=seed)[0]
-    p["score"], p["ambiguity"] = 0.99, 0.5
-    p["score"][np.linspace(0, n - 1, n - valid).astype(int)] = 0.0
-    return p
 
 
 def _same_as_single(g, got, sel, seeds, recs, counts, offs, stride, max_pts, loops, what, oracle=True):

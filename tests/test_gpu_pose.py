@@ -29,12 +29,7 @@ def _poisoned(ctx, words):
     return ctx.upload(np.full(max(words, 1), POISON_WORD, np.uint32))
 
 
-def _frame(n, seed, k2):
-    """n records of a planted scene, a fifth of them wrong matches and (from 10 records on) a tenth failing the gate, with
-    the scene's exact F and intrinsics."""
-    s = PC.planted(seed=seed, n=max(n, 1), k2=k2, outliers=0.2 if n >= 10 else 0.0)
-    recs = PC.records(s["xy"], seed, fail=0.1 if n >= 10 else 0.0)[:n]
-    return recs, s["F"], s["K8"]
+_frame = PC.planted_frame
 
 
 @pytest.fixture(scope="module")

@@ -7,7 +7,7 @@ union-find): labels are minima and every other output an integer sum, so nothing
 import numpy as np
 import pytest
 
-from batch_util import frames, guarded_context, layout, span
+from batch_util import frames, guarded_context, layout, planted_members as _members, span
 from synth import synth_frame
 from test_tracks_cpu import (GATES, INF, blank_rows, expected_tracks, gate_rows, plant, set_edge, window_pairs)
 
@@ -45,21 +45,6 @@ def _check(ctx, pairs, rows, row_counts, max_pts, counts, offs, stride, max_reco
             raise AssertionError("%s %s: %d ints differ, first at %s: got %s, expected %s"
                                  % (what, name, len(bad), bad[:8], g[bad[:8]], e[bad[:8]]))
     return got
-
-
-def _members(sizes, usable, lengths, rng):
-    """Planted tracks: track t visits lengths[t] consecutive usable frames from a random start, taking one record nobody
-    else has in each frame that still has one."""
-    free = {f: list(rng.permutation(sizes[f])) for f in usable}
-    out = []
-    for L in lengths:
-        a = int(rng.integers(0, max(len(usable) - L, 0) + 1))
-        t = {}
-        for f in usable[a:a + L]:
-            if free[f]:
-                t[f] = int(free[f].pop())
-        out.append(t)
-    return out
 
 
 SIZES = [300, 64, 2000, 0, 65, 1, 63, 300, 2000, 64, 65, 300]     # frame 7: count -1; frame 11: in no pair

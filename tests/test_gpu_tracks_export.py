@@ -11,7 +11,7 @@ import functools
 import numpy as np
 import pytest
 
-from batch_util import guarded_context
+from batch_util import fabricated_records, guarded_context, xy_bits
 from synth import synth_frame
 from test_gpu_tracks import COUNTS, SIZES, _members
 from test_tracks_cpu import GATES, blank_rows, expected_tracks, plant, set_edge, window_pairs
@@ -26,20 +26,6 @@ LAUNCHES = 6                                                     # include/misif
 
 def _poisoned(ctx, nints):
     return ctx.upload(np.full(max(nints, 1), POISON, np.uint32))
-
-
-def fabricated_records(n, seed):
-    """n records whose xpos / ypos are random bit patterns (NaN payloads, infinities, denormals); the rest zero."""
-    from cudasift_amd import capi
-    recs = np.zeros(max(n, 1), capi.POINT_DTYPE)
-    bits = np.random.default_rng(seed).integers(0, 2 ** 32, (2, len(recs)), dtype=np.uint64).astype(np.uint32)
-    recs["xpos"], recs["ypos"] = bits[0].view(np.float32), bits[1].view(np.float32)
-    return recs
-
-
-def xy_bits(recs):
-    """What expected_export takes: the bits of xpos / ypos per record, as they sit in the array that is uploaded."""
-    return np.stack([np.ascontiguousarray(recs[k]).view(np.uint32) for k in ("xpos", "ypos")], 1)
 
 
 class Batch:
