@@ -128,6 +128,10 @@ SIGNATURES = {
     "misift_refine_cameras_batch": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _f, _i,
                                          _vp, _vp, _vp, _vp, _vp, _vp]),
     "misift_test_refine_camera": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _vp]),
+    "misift_adjust_bundle_batch": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i,
+                                        _f, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "misift_test_adjust_bundle": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _f, _f,
+                                       _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "misift_resect_cameras_batch": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _f, _i, _i,
                                          _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "misift_test_resect_samples": (_i, [C.c_uint, _i, _i, _vp]),
@@ -1020,6 +1024,55 @@ class Context:
                                                 _dptr(cam_rms), _dptr(cam_steps), _dptr(cam_status), _dptr(summary)),
               "misift_refine_cameras_batch")
         return cam_out, cam_obs, cam_rms, cam_steps, cam_status, summary
+
+    def adjust_bundle_batch(self, max_tracks, max_obs, track_offsets, obs, export_summary, points, point_status,
+                            nimages, cam, cam_pair, intrinsics, hold=(), min_views=2, min_obs=6, num_loops=5,
+                            cg_iters=10, max_error=np.inf, lambda0=1e-3, orthonormalise=True, cam_out=None,
+                            points_out=None, cam_obs=None, cam_status=None, cam_rms=None, point_obs=None, history=None,
+                            cost=None, summary=None):
+        """misift_adjust_bundle_batch: the cameras (cam, cam_pair, for nimages images) and the points of
+        triangulate_tracks_batch (points, point_status) adjusted jointly against the observations (track_offsets, obs,
+        export_summary: the outputs of export_tracks_batch for max_tracks and max_obs): num_loops Levenberg-Marquardt
+        steps from damping lambda0, the points eliminated in each, the cameras solved by cg_iters preconditioned
+        conjugate-gradient iterations, each step kept only if it lowers the error.  intrinsics: host, nimages x 4 (fx fy
+        cx cy); hold: host, the images kept as they are besides the root.  An observation is used when its point is in
+        front and within max_error px; a track with fewer than min_views of them keeps its point, a camera with fewer
+        than min_obs stays as it is.  cam_out (nimages x 12 floats; may be cam itself), points_out (max_tracks x 4
+        floats; may be points itself), cam_obs and cam_status (nimages ints: the observations used; 0 adjusted, 1 fewer
+        than min_obs, 3 root or held, 4 no camera), cam_rms (nimages x 2 floats: rms reprojection error in px before and
+        after), point_obs (max_tracks ints), history (num_loops x 4 words: the trial cost, the damping, kept, CG
+        iterations), cost (2 floats: before, after) and summary (8 ints) are device buffers, allocated here when not
+        passed; returns the nine.  Enqueued on the context stream."""
+        intrinsics = np.ascontiguousarray(intrinsics, np.float32).reshape(-1, 4)
+        assert len(intrinsics) == nimages
+        hold = np.ascontiguousarray(hold, np.int32).reshape(-1)
+        if cam_out is None:
+            cam_out = self.zeros(48 * max(nimages, 1))
+        if points_out is None:
+            points_out = self.zeros(16 * max(max_tracks, 1))
+        if cam_obs is None:
+            cam_obs = self.zeros(4 * max(nimages, 1))
+        if cam_status is None:
+            cam_status = self.zeros(4 * max(nimages, 1))
+        if cam_rms is None:
+            cam_rms = self.zeros(8 * max(nimages, 1))
+        if point_obs is None:
+            point_obs = self.zeros(4 * max(max_tracks, 1))
+        if history is None:
+            history = self.zeros(16 * max(int(num_loops), 1))
+        if cost is None:
+            cost = self.zeros(8)
+        if summary is None:
+            summary = self.zeros(4 * 8)
+        check(lib().misift_adjust_bundle_batch(self.h, max_tracks, max_obs, _dptr(track_offsets), _dptr(obs),
+                                               _dptr(export_summary), _dptr(points), _dptr(point_status), nimages,
+                                               _dptr(cam), _dptr(cam_pair), intrinsics.ctypes.data, len(hold),
+                                               hold.ctypes.data if len(hold) else None, int(min_views), int(min_obs),
+                                               int(num_loops), int(cg_iters), float(max_error), float(lambda0),
+                                               int(orthonormalise), _dptr(cam_out), _dptr(points_out), _dptr(cam_obs),
+                                               _dptr(cam_status), _dptr(cam_rms), _dptr(point_obs), _dptr(history),
+                                               _dptr(cost), _dptr(summary)), "misift_adjust_bundle_batch")
+        return cam_out, points_out, cam_obs, cam_status, cam_rms, point_obs, history, cost, summary
 
     def resect_cameras_batch(self, max_tracks, max_obs, track_offsets, obs, export_summary, points, point_status,
                              nimages, intrinsics, images, seeds, max_cand, num_loops=1024, thresh=4.0, min_inliers=12,

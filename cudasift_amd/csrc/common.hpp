@@ -664,6 +664,16 @@ int launch_resect_cameras_batch(misift_ctx *ctx, int max_tracks, int max_obs, co
                                 int num_loops, float thresh2, int min_inliers, int only_unset, int install, float *d_cam,
                                 int *d_cam_pair, float *d_res_cam, int *d_res_cand, int *d_res_inliers,
                                 int *d_res_status, int *d_summary);
+// misift_adjust_bundle_batch (kernels_bundle.hip): three memsets + 11 + num_loops * (8 + 3 * cg_iters) launches; temp
+// from misift_ensure_tmp, sized from max_tracks, max_obs and nimages only.  h_lists: as launch_refine_cameras_batch
+size_t adjust_bundle_batch_tmp_bytes(int max_tracks, int max_obs, int nimages);
+int launch_adjust_bundle_batch(misift_ctx *ctx, int max_tracks, int max_obs, const int *d_track_offsets,
+                               const void *d_obs, const int *d_export_summary, const float *d_points,
+                               const int *d_point_status, int nimages, const float *d_cam, const int *d_cam_pair,
+                               const void *h_lists, int min_views, int min_obs, int num_loops, int cg_iters,
+                               float thresh2, float lambda0, int orthonormalise, float *d_cam_out, float *d_points_out,
+                               int *d_cam_obs, int *d_cam_status, float *d_cam_rms, int *d_point_obs, float *d_history,
+                               float *d_cost, int *d_summary);
 int launch_test_exp2(misift_ctx *ctx, const float *x, float *out, int n);
 int launch_test_points_fn(misift_ctx *ctx, int fn, const float *x, const float *y, float *out, float *out2, int n);
 int launch_selftest(misift_ctx *ctx);

@@ -1,0 +1,429 @@
+// kernels_bundle.hip — misift_adjust_bundle_batch: Levenberg-Marquardt over all free cameras and all active track points
+// at once.  Each step eliminates the points (Schur complement), solves the reduced camera system matrix-free by a fixed
+// number of block-Jacobi preconditioned conjugate-gradient iterations, back-substitutes the points and is kept or turned
+// away on the device.  No reference counterpart.  The arithmetic is bundle_core.hpp: every kernel here is a few lines
+// that hand one work item to the function of its phase, the same function the host-only test hook at the end of this
+// file runs in a loop.
+//
+// Three memsets (the owners, the control words, the summary) and 11 + num_loops * (8 + 3 * cg_iters) launches, whatever
+// the data.  A dispatch boundary is the only barrier between workgroups: nothing in here waits for another workgroup.
+//   cand_owner_kernel, cand_key_kernel     track_candidates.hpp: the owner of every slot, the image it is a candidate of
+//   bundle_image_init_kernel    lane per image: usable / held / free, the camera of refine's step 1 into both buffers
+//   bundle_premember_kernel     lane per slot: refine's member test under that camera
+//   bundle_activate_kernel      lane per track: its pre-members counted; an inactive track's leave the keys
+//   bundle_gather_kernel        256-thread workgroup per image, two walks over the keys: the members of lower images
+//                               counted (the start of its list), then its members listed in ascending slot (ballot and
+//                               popcount keep the order, as resect's gather); demotion
+//   bundle_eval_kernel          lane per slot: a member's squared residual under a state buffer
+//   bundle_cost_kernel          workgroup per image: its cost by the position rule
+//   bundle_start_kernel         the scalar workgroup: the cost of the start, lambda0
+//   per LM step:
+//   bundle_track_normal_kernel  lane per track: Jc, Jp, r of its members into temp, V, gp, V', V'^-1 gp
+//   bundle_image_normal_kernel  workgroup per image: U, gc, sum W y (33 sums, 33 KiB of LDS), U', b, the LDL^T checked
+//   bundle_cg_start_kernel      the scalar workgroup: x, r, z, p, rho
+//   per CG iteration: bundle_cg_track_kernel (lane per track), bundle_cg_image_kernel (workgroup per image, 6 sums),
+//                     bundle_cg_scalar_kernel (the scalar workgroup)
+//   bundle_track_trial_kernel, bundle_image_trial_kernel   lane per track / per image: the trial state
+//   bundle_eval_kernel, bundle_cost_kernel                 under the trial state
+//   bundle_decide_kernel        the scalar workgroup: kept or not, lambda, the history
+//   then bundle_image_out_kernel and bundle_track_out_kernel write the outputs.
+// Jc, Jp and r are written once per LM step and read by both views: recomputing them in each CG pass instead gives the
+// same bits and measured 10 to 13 % slower.
+#include <stdint.h>
+#include <string.h>
+#include <vector>
+#include "common.hpp"
+#include "bundle_core.hpp"
+#include "track_candidates.hpp"
+
+namespace {
+
+static_assert(sizeof(BundleObs) == sizeof(misift_track_obs), "BundleObs mirrors misift_track_obs");
+constexpr int BUNDLE_THREADS = FUND_SLOTS;
+
+// the workgroup as the Sum of bundle_core.hpp: thread s is slot s, the tree runs through LDS
+struct BundleBlockSum {
+  float *p;                                    // LDS: K x FUND_SLOTS
+  __device__ void fence() { __syncthreads(); }
+  template <int K, class V>
+  __device__ void sum(int n, V &v, float (&out)[K])
+  {
+    const int t = threadIdx.x;
+    float acc[K];
+    fundamental_slot_partial<K>(t, n, v, acc);
+#pragma unroll
+    for (int k = 0; k < K; k++) p[k * FUND_SLOTS + t] = acc[k];
+    for (int off = FUND_SLOTS / 2; off > 0; off >>= 1) {
+      __syncthreads();
+      if (t < off) fundamental_tree_step<K>(p, t, off);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < K; k++) out[k] = p[k * FUND_SLOTS];
+    __syncthreads();                           // p is free again
+  }
+};
+
+inline dim3 bundle_blocks(int n) { return dim3((unsigned)(((long long)n + BUNDLE_THREADS - 1) / BUNDLE_THREADS)); }
+
+__global__ __launch_bounds__(BUNDLE_THREADS) void bundle_image_init_kernel(BundleData D)
+{
+  const int i = blockIdx.x * BUNDLE_THREADS + threadIdx.x;
+  if (i < D.nimages) bundle_image_init(D, i);
+}
+
+__global__ __launch_bounds__(BUNDLE_THREADS) void bundle_premember_kernel(BundleData D)
+{
+  const int o = blockIdx.x * BUNDLE_THREADS + threadIdx.x;
+  if (o < bundle_O(D)) bundle_slot_premember(D, o);
+}
+
+__global__ __launch_bounds__(BUNDLE_THREADS) void bundle_activate_kernel(BundleData D)
+{
+  const int t = blockIdx.x * BUNDLE_THREADS + threadIdx.x;
+  if (t < bundle_T(D)) bundle_track_activate(D, t);
+}
+
+__global__ __launch_bounds__(BUNDLE_THREADS) void bundle_gather_kernel(BundleData D)
+{
+  __shared__ int wave_cnt[2][4];
+  __shared__ int base_s[2];
+  const int i = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int O = bundle_O(D);
+  // first walk: the members of lower images come first in `list`, so count them, and this image's own
+  int mine = 0, lower = 0;
+  for (long long o = tid; o < O; o += BUNDLE_THREADS) {
+    const int key = D.key[o];
+    mine += key == i ? 1 : 0;
+    lower += (key >= 0 && key < i) ? 1 : 0;
+  }
+  for (int off = 32; off > 0; off >>= 1) {
+    mine += __shfl_xor(mine, off, 64);
+    lower += __shfl_xor(lower, off, 64);
+  }
+  if (lane == 0) {
+    wave_cnt[0][wave] = mine;
+    wave_cnt[1][wave] = lower;
+  }
+  __syncthreads();
+  const int n = wave_cnt[0][0] + wave_cnt[0][1] + wave_cnt[0][2] + wave_cnt[0][3];
+  const int start = wave_cnt[1][0] + wave_cnt[1][1] + wave_cnt[1][2] + wave_cnt[1][3];   // start + n <= O
+  if (tid == 0) base_s[0] = 0;
+  __syncthreads();
+  // second walk: the image's members in ascending slot; ballot and popcount keep the order
+  for (long long o0 = 0; o0 < O; o0 += BUNDLE_THREADS) {
+    const long long o = o0 + tid;
+    const bool ok = o < O && D.key[o] == i;
+    const unsigned long long m = __ballot(ok);
+    if (lane == 0) wave_cnt[0][wave] = __popcll(m);
+    __syncthreads();
+    int pos = base_s[0];
+    for (int w = 0; w < wave; w++) pos += wave_cnt[0][w];
+    pos += __popcll(m & ((1ull << lane) - 1ull));
+    if (ok && pos < n) D.list[start + pos] = (int)o;
+    __syncthreads();
+    if (tid == 0) base_s[0] += wave_cnt[0][0] + wave_cnt[0][1] + wave_cnt[0][2] + wave_cnt[0][3];
+    __syncthreads();
+  }
+  if (tid == 0) {
+    D.icount[i] = n;
+    D.istart[i] = start;
+    if (D.istate[i] == BUNDLE_ADJUSTED && n < D.min_obs) D.istate[i] = BUNDLE_FEW_OBS;
+  }
+}
+
+__global__ __launch_bounds__(BUNDLE_THREADS) void bundle_eval_kernel(BundleData D, int trial)
+{
+  const int o = blockIdx.x * BUNDLE_THREADS + threadIdx.x;
+  if (o < bundle_O(D)) bundle_eval_slot(D, o, trial != 0);
+}
+
+__global__ __launch_bounds__(BUNDLE_THREADS) void bundle_cost_kernel(BundleData D, int trial)
+{
+  __shared__ float s_p[FUND_SLOTS];
+  BundleBlockSum S{s_p};
+  bundle_image_cost(D, S, blockIdx.x, trial != 0, threadIdx.x == 0);
+}
+
+__global__ __launch_bounds__(BUNDLE_THREADS) void bundle_start_kernel(BundleData D)
+{
+  __shared__ float s_p[FUND_SLOTS];
+  BundleBlockSum S{s_p};
+  bundle_scalar_init(D, S, threadIdx.x == 0);
+}
+
+__global__ __launch_bounds__(BUNDLE_THREADS) void bundle_track_normal_kernel(BundleData D)
+{
+  const int t = blockIdx.x * BUNDLE_THREADS + threadIdx.x;
+  if (t < bundle_T(D)) bundle_track_normal(D, t);
+}
+
+__global__ __launch_bounds__(BUNDLE_THREADS) void bundle_image_normal_kernel(BundleData D)
+{
+  __shared__ float s_p[BUNDLE_NORMAL * FUND_SLOTS];
+  BundleBlockSum S{s_p};
+  bundle_image_normal(D, S, blockIdx.x, threadIdx.x == 0);
+}
+
+__global__ __launch_bounds__(BUNDLE_THREADS) void bundle_cg_start_kernel(BundleData D)
+{
+  __shared__ float s_p[FUND_SLOTS];
+  BundleBlockSum S{s_p};
+  bundle_cg_start(D, S, threadIdx.x, BUNDLE_THREADS, threadIdx.x == 0);
+}
+
+__global__ __launch_bounds__(BUNDLE_THREADS) void bundle_cg_track_kernel(BundleData D)
+{
+  const int t = blockIdx.x * BUNDLE_THREADS + threadIdx.x;
+  if (t < bundle_T(D)) bundle_cg_track(D, t);
+}
+
+__global__ __launch_bounds__(BUNDLE_THREADS) void bundle_cg_image_kernel(BundleData D)
+{
+  __shared__ float s_p[6 * FUND_SLOTS];
+  BundleBlockSum S{s_p};
+  bundle_cg_image(D, S, blockIdx.x, threadIdx.x == 0);
+}
+
+__global__ __launch_bounds__(BUNDLE_THREADS) void bundle_cg_scalar_kernel(BundleData D)
+{
+  __shared__ float s_p[FUND_SLOTS];
+  BundleBlockSum S{s_p};
+  bundle_cg_scalar(D, S, threadIdx.x, BUNDLE_THREADS, threadIdx.x == 0);
+}
+
+__global__ __launch_bounds__(BUNDLE_THREADS) void bundle_track_trial_kernel(BundleData D)
+{
+  const int t = blockIdx.x * BUNDLE_THREADS + threadIdx.x;
+  if (t < bundle_T(D)) bundle_track_trial(D, t);
+}
+
+__global__ __launch_bounds__(BUNDLE_THREADS) void bundle_image_trial_kernel(BundleData D)
+{
+  const int i = blockIdx.x * BUNDLE_THREADS + threadIdx.x;
+  if (i < D.nimages) bundle_image_trial(D, i);
+}
+
+__global__ __launch_bounds__(BUNDLE_THREADS) void bundle_decide_kernel(BundleData D)
+{
+  __shared__ float s_p[FUND_SLOTS];
+  BundleBlockSum S{s_p};
+  bundle_decide(D, S, threadIdx.x, BUNDLE_THREADS, threadIdx.x == 0);
+}
+
+__global__ __launch_bounds__(BUNDLE_THREADS) void bundle_image_out_kernel(BundleData D)
+{
+  const int i = blockIdx.x * BUNDLE_THREADS + threadIdx.x;
+  if (i < D.nimages) bundle_image_out(D, i);
+}
+
+__global__ __launch_bounds__(BUNDLE_THREADS) void bundle_track_out_kernel(BundleData D)
+{
+  const int t = blockIdx.x * BUNDLE_THREADS + threadIdx.x;
+  if (t < bundle_T(D)) bundle_track_out(D, t);
+}
+
+// the temp of the call laid out behind `base` (NULL: only the size is wanted); every array starts 16-byte aligned
+size_t bundle_layout(BundleData &D, char *base)
+{
+  size_t at = 0;
+  auto take = [&](size_t bytes) {
+    char *p = base ? base + at : nullptr;
+    at += (bytes + 15) & ~(size_t)15;
+    return p;
+  };
+  const size_t mo = (size_t)D.max_obs, mt = (size_t)D.max_tracks, n = (size_t)D.nimages;
+  D.owner = reinterpret_cast<int *>(take(4 * mo));
+  D.key = reinterpret_cast<int *>(take(4 * mo));
+  D.list = reinterpret_cast<int *>(take(4 * mo));
+  D.istart = reinterpret_cast<int *>(take(4 * n));
+  D.icount = reinterpret_cast<int *>(take(4 * n));
+  D.istate = reinterpret_cast<int *>(take(4 * n));
+  D.tcount = reinterpret_cast<int *>(take(4 * mt));
+  D.ctl = reinterpret_cast<int *>(take(4 * BUNDLE_CTL));
+  D.fctl = reinterpret_cast<float *>(take(4 * BUNDLE_FCTL));
+  D.lin = reinterpret_cast<float *>(take(4 * BUNDLE_LIN * mo));
+  D.eterm = reinterpret_cast<float *>(take(4 * 2 * mo));
+  D.cams = reinterpret_cast<float *>(take(4 * 2 * 12 * n));
+  D.pts = reinterpret_cast<float *>(take(4 * 2 * 3 * mt));
+  D.tv = reinterpret_cast<float *>(take(4 * 9 * mt));
+  D.tq = reinterpret_cast<float *>(take(4 * 3 * mt));
+  D.iu = reinterpret_cast<float *>(take(4 * REFINE_SUMS * n));
+  D.ivec = reinterpret_cast<float *>(take(4 * 5 * 6 * n));
+  D.icost = reinterpret_cast<float *>(take(4 * 3 * n));
+  return at;
+}
+
+}  // namespace
+
+size_t adjust_bundle_batch_tmp_bytes(int max_tracks, int max_obs, int nimages)
+{
+  BundleData D;
+  D.max_tracks = max_tracks; D.max_obs = max_obs; D.nimages = nimages;
+  return bundle_layout(D, nullptr);
+}
+
+// Enqueue misift_adjust_bundle_batch on the context stream (common.hpp).  h_lists: the pinned copies, nimages x 4
+// intrinsics and then nimages held flags.
+int launch_adjust_bundle_batch(misift_ctx *ctx, int max_tracks, int max_obs, const int *d_track_offsets,
+                               const void *d_obs, const int *d_export_summary, const float *d_points,
+                               const int *d_point_status, int nimages, const float *d_cam, const int *d_cam_pair,
+                               const void *h_lists, int min_views, int min_obs, int num_loops, int cg_iters,
+                               float thresh2, float lambda0, int orthonormalise, float *d_cam_out, float *d_points_out,
+                               int *d_cam_obs, int *d_cam_status, float *d_cam_rms, int *d_point_obs, float *d_history,
+                               float *d_cost, int *d_summary)
+{
+  const int rc = misift_ensure_tmp(ctx, adjust_bundle_batch_tmp_bytes(max_tracks, max_obs, nimages));
+  if (rc) return rc;
+  BundleData D;
+  D.max_tracks = max_tracks; D.max_obs = max_obs; D.nimages = nimages; D.min_views = min_views; D.min_obs = min_obs;
+  D.num_loops = num_loops; D.cg_iters = cg_iters; D.orthonormalise = orthonormalise; D.thresh2 = thresh2;
+  D.lambda0 = lambda0;
+  D.track_offsets = d_track_offsets; D.obs = reinterpret_cast<const BundleObs *>(d_obs);
+  D.export_summary = d_export_summary; D.points = d_points; D.point_status = d_point_status; D.cam = d_cam;
+  D.cam_pair = d_cam_pair;
+  D.intrinsics = reinterpret_cast<const float *>(h_lists);
+  D.held = reinterpret_cast<const int *>(D.intrinsics + 4 * (size_t)nimages);
+  bundle_layout(D, reinterpret_cast<char *>(ctx->d_match_tmp));
+  D.cam_out = d_cam_out; D.points_out = d_points_out; D.cam_rms = d_cam_rms; D.history = d_history; D.cost = d_cost;
+  D.cam_obs = d_cam_obs; D.cam_status = d_cam_status; D.point_obs = d_point_obs; D.summary = d_summary;
+  CandArgs C;
+  C.max_tracks = max_tracks; C.max_obs = max_obs; C.nimages = nimages; C.track_offsets = d_track_offsets;
+  C.obs = reinterpret_cast<const CandObs *>(d_obs); C.export_summary = d_export_summary; C.points = d_points;
+  C.point_status = d_point_status; C.owner = D.owner; C.key = D.key;
+  HIP_TRY(hipMemsetAsync(D.owner, 0xff, sizeof(int) * (size_t)max_obs, ctx->stream));
+  HIP_TRY(hipMemsetAsync(D.ctl, 0, sizeof(int) * BUNDLE_CTL, ctx->stream));
+  HIP_TRY(hipMemsetAsync(d_summary, 0, 8 * sizeof(int), ctx->stream));
+  hipStream_t s = ctx->stream;
+  const dim3 th(BUNDLE_THREADS), per_track = bundle_blocks(max_tracks), per_slot = bundle_blocks(max_obs),
+             per_image = bundle_blocks(nimages), image_wg((unsigned)nimages), one(1);
+  // a profile entry per kind of launch (misift_profile_read): tools/bundle_time.py reports their shares
+  auto scope = [&](const char *name, auto launches) {
+    LaunchScope ls(ctx, name);
+    launches();
+    return ls.finish();
+  };
+  int r = scope("bundle_setup", [&] {
+    hipLaunchKernelGGL(cand_owner_kernel, cand_blocks(max_tracks), dim3(CAND_THREADS), 0, s, C);
+    hipLaunchKernelGGL(cand_key_kernel, cand_blocks(max_obs), dim3(CAND_THREADS), 0, s, C);
+    hipLaunchKernelGGL(bundle_image_init_kernel, per_image, th, 0, s, D);
+    hipLaunchKernelGGL(bundle_premember_kernel, per_slot, th, 0, s, D);
+    hipLaunchKernelGGL(bundle_activate_kernel, per_track, th, 0, s, D);
+    hipLaunchKernelGGL(bundle_gather_kernel, image_wg, th, 0, s, D);
+    hipLaunchKernelGGL(bundle_eval_kernel, per_slot, th, 0, s, D, 0);
+    hipLaunchKernelGGL(bundle_cost_kernel, image_wg, th, 0, s, D, 0);
+    hipLaunchKernelGGL(bundle_start_kernel, one, th, 0, s, D);
+  });
+  for (int loop = 0; loop < num_loops && !r; loop++) {
+    r = scope("bundle_track", [&] { hipLaunchKernelGGL(bundle_track_normal_kernel, per_track, th, 0, s, D); });
+    if (!r) r = scope("bundle_image", [&] { hipLaunchKernelGGL(bundle_image_normal_kernel, image_wg, th, 0, s, D); });
+    if (!r) r = scope("bundle_scalar", [&] { hipLaunchKernelGGL(bundle_cg_start_kernel, one, th, 0, s, D); });
+    for (int it = 0; it < cg_iters && !r; it++) {
+      r = scope("bundle_track", [&] { hipLaunchKernelGGL(bundle_cg_track_kernel, per_track, th, 0, s, D); });
+      if (!r) r = scope("bundle_image", [&] { hipLaunchKernelGGL(bundle_cg_image_kernel, image_wg, th, 0, s, D); });
+      if (!r) r = scope("bundle_scalar", [&] { hipLaunchKernelGGL(bundle_cg_scalar_kernel, one, th, 0, s, D); });
+    }
+    if (!r) r = scope("bundle_track", [&] { hipLaunchKernelGGL(bundle_track_trial_kernel, per_track, th, 0, s, D); });
+    if (!r) r = scope("bundle_trial", [&] {
+      hipLaunchKernelGGL(bundle_image_trial_kernel, per_image, th, 0, s, D);
+      hipLaunchKernelGGL(bundle_eval_kernel, per_slot, th, 0, s, D, 1);
+    });
+    if (!r) r = scope("bundle_image", [&] { hipLaunchKernelGGL(bundle_cost_kernel, image_wg, th, 0, s, D, 1); });
+    if (!r) r = scope("bundle_scalar", [&] { hipLaunchKernelGGL(bundle_decide_kernel, one, th, 0, s, D); });
+  }
+  if (r) return r;
+  return scope("bundle_out", [&] {
+    hipLaunchKernelGGL(bundle_image_out_kernel, per_image, th, 0, s, D);
+    hipLaunchKernelGGL(bundle_track_out_kernel, per_track, th, 0, s, D);
+  });
+}
+
+// Test-only, host-only: the whole call on host arrays, phase after phase through bundle_core.hpp.
+extern "C" int misift_test_adjust_bundle(int max_tracks, int max_obs, const int *track_offsets, const misift_track_obs *obs,
+                                         const int *export_summary, const float *points, const int *point_status,
+                                         int nimages, const float *cam, const int *cam_pair, const float *intrinsics,
+                                         int nhold, const int *hold, int min_views, int min_obs, int num_loops,
+                                         int cg_iters, float max_error, float lambda0, int orthonormalise,
+                                         float *cam_out, float *points_out, int *cam_obs, int *cam_status,
+                                         float *cam_rms, int *point_obs, float *history, float *cost, int *summary)
+{
+  bool ok = max_tracks >= 1 && max_obs >= 1 && nimages >= 1 && track_offsets && obs && export_summary && points &&
+            point_status && cam && cam_pair && intrinsics && nhold >= 0 && (nhold == 0 || hold) && min_views >= 2 &&
+            min_obs >= 3 && num_loops >= 0 && cg_iters >= 0 && max_error > 0.0f && lambda0 > 0.0f &&
+            fundamental_finite(lambda0) && (orthonormalise == 0 || orthonormalise == 1) && cam_out && points_out &&
+            cam_obs && cam_status && cam_rms && point_obs && (history || num_loops == 0) && cost && summary;
+  for (int j = 0; ok && j < nhold; j++) ok = hold[j] >= 0 && hold[j] < nimages;
+  if (!ok) {
+    misift_set_error("misift_test_adjust_bundle: invalid argument");
+    return MISIFT_EINVAL;
+  }
+  BundleData D;
+  D.max_tracks = max_tracks; D.max_obs = max_obs; D.nimages = nimages; D.min_views = min_views; D.min_obs = min_obs;
+  D.num_loops = num_loops; D.cg_iters = cg_iters; D.orthonormalise = orthonormalise;
+  D.thresh2 = max_error * max_error; D.lambda0 = lambda0;
+  D.track_offsets = track_offsets; D.obs = reinterpret_cast<const BundleObs *>(obs); D.export_summary = export_summary;
+  D.points = points; D.point_status = point_status; D.cam = cam; D.cam_pair = cam_pair; D.intrinsics = intrinsics;
+  std::vector<int> held(nimages, 0);
+  for (int j = 0; j < nhold; j++) held[hold[j]] = 1;
+  D.held = held.data();
+  std::vector<char> tmp(bundle_layout(D, nullptr) + 16, 0);
+  bundle_layout(D, reinterpret_cast<char *>(((uintptr_t)tmp.data() + 15) & ~(uintptr_t)15));
+  D.cam_out = cam_out; D.points_out = points_out; D.cam_rms = cam_rms; D.history = history; D.cost = cost;
+  D.cam_obs = cam_obs; D.cam_status = cam_status; D.point_obs = point_obs; D.summary = summary;
+  const int T = bundle_T(D), O = bundle_O(D);
+  // the owners and the candidates, as track_candidates.hpp
+  for (int o = 0; o < max_obs; o++) D.owner[o] = -1;
+  for (int t = 0; t < T; t++) {
+    const int off = track_offsets[t], end = track_offsets[t + 1];
+    if (!tri_range_ok(off, end, O)) continue;
+    for (int o = off; o < end; o++) D.owner[o] = t > D.owner[o] ? t : D.owner[o];
+  }
+  for (int o = 0; o < O; o++) {
+    const int t = D.owner[o];
+    int key = -1;
+    if (t >= 0 && point_status[t] == TRI_OK) {
+      const float *X = points + 4 * (size_t)t;
+      const BundleObs ob = D.obs[o];
+      if (fundamental_finite(X[0]) && fundamental_finite(X[1]) && fundamental_finite(X[2]) && fundamental_finite(ob.xpos) &&
+          fundamental_finite(ob.ypos) && ob.frame >= 0 && ob.frame < nimages)
+        key = ob.frame;
+    }
+    D.key[o] = key;
+  }
+  for (int j = 0; j < 8; j++) summary[j] = 0;
+  for (int i = 0; i < nimages; i++) bundle_image_init(D, i);
+  for (int o = 0; o < O; o++) bundle_slot_premember(D, o);
+  for (int t = 0; t < T; t++) bundle_track_activate(D, t);
+  {
+    int at = 0;
+    for (int i = 0; i < nimages; i++) {
+      D.istart[i] = at;
+      for (int o = 0; o < O; o++)
+        if (D.key[o] == i) D.list[at++] = o;
+      D.icount[i] = at - D.istart[i];
+      if (D.istate[i] == BUNDLE_ADJUSTED && D.icount[i] < min_obs) D.istate[i] = BUNDLE_FEW_OBS;
+    }
+  }
+  BundleHostSum S;
+  for (int o = 0; o < O; o++) bundle_eval_slot(D, o, false);
+  for (int i = 0; i < nimages; i++) bundle_image_cost(D, S, i, false, true);
+  bundle_scalar_init(D, S, true);
+  for (int loop = 0; loop < num_loops; loop++) {
+    for (int t = 0; t < T; t++) bundle_track_normal(D, t);
+    for (int i = 0; i < nimages; i++) bundle_image_normal(D, S, i, true);
+    bundle_cg_start(D, S, 0, 1, true);
+    for (int it = 0; it < cg_iters; it++) {
+      for (int t = 0; t < T; t++) bundle_cg_track(D, t);
+      for (int i = 0; i < nimages; i++) bundle_cg_image(D, S, i, true);
+      bundle_cg_scalar(D, S, 0, 1, true);
+    }
+    for (int t = 0; t < T; t++) bundle_track_trial(D, t);
+    for (int i = 0; i < nimages; i++) bundle_image_trial(D, i);
+    for (int o = 0; o < O; o++) bundle_eval_slot(D, o, true);
+    for (int i = 0; i < nimages; i++) bundle_image_cost(D, S, i, true, true);
+    bundle_decide(D, S, 0, 1, true);
+  }
+  for (int i = 0; i < nimages; i++) bundle_image_out(D, i);
+  for (int t = 0; t < T; t++) bundle_track_out(D, t);
+  return MISIFT_OK;
+}

@@ -2689,6 +2689,53 @@ extern "C" int misift_resect_cameras_batch(misift_ctx *ctx, int max_tracks, int 
                    });
 }
 
+// Levenberg-Marquardt over all free cameras and all active track points at once, the points eliminated in every step:
+// what misift_refine_cameras_batch and misift_triangulate_tracks_batch do in turns, done jointly.  The intrinsics and a
+// flag per image (1 = held) go to the pinned slot.
+extern "C" int misift_adjust_bundle_batch(misift_ctx *ctx, int max_tracks, int max_obs, const int *d_track_offsets,
+                                          const misift_track_obs *d_obs, const int *d_export_summary,
+                                          const float *d_points, const int *d_point_status, int nimages,
+                                          const float *d_cam, const int *d_cam_pair, const float *intrinsics, int nhold,
+                                          const int *hold, int min_views, int min_obs, int num_loops, int cg_iters,
+                                          float max_error, float lambda0, int orthonormalise, float *d_cam_out,
+                                          float *d_points_out, int *d_cam_obs, int *d_cam_status, float *d_cam_rms,
+                                          int *d_point_obs, float *d_history, float *d_cost, int *d_summary)
+{
+  ARG_CHECK(ctx && max_tracks >= 1 && max_obs >= 1 && nimages >= 1);
+  ARG_CHECK(d_track_offsets && d_obs && d_export_summary && d_points && d_point_status && d_cam && d_cam_pair);
+  ARG_CHECK(intrinsics && d_cam_out && d_points_out && d_cam_obs && d_cam_status && d_cam_rms && d_point_obs);
+  ARG_CHECK(d_cost && d_summary && (d_history || num_loops == 0));
+  ARG_CHECK(((uintptr_t)d_obs & 15) == 0);
+  ARG_CHECK(min_views >= 2 && min_obs >= 3 && num_loops >= 0 && cg_iters >= 0);
+  ARG_CHECK(max_error > 0.0f);                                              // NaN fails too
+  ARG_CHECK(lambda0 > 0.0f && lambda0 <= 3.402823466e+38f);
+  ARG_CHECK(orthonormalise == 0 || orthonormalise == 1);
+  ARG_CHECK(nhold >= 0 && (nhold == 0 || hold));
+  for (int j = 0; j < nhold; j++) ARG_CHECK(hold[j] >= 0 && hold[j] < nimages);
+  for (int i = 0; i < nimages; i++) ARG_CHECK(intrinsics_usable(intrinsics + 4 * (size_t)i, 1));
+  {
+    const uintptr_t in = (uintptr_t)d_cam, out = (uintptr_t)d_cam_out, span = sizeof(float) * 12 * (size_t)nimages;
+    ARG_CHECK(in == out || in + span <= out || out + span <= in);
+  }
+  {
+    const uintptr_t in = (uintptr_t)d_points, out = (uintptr_t)d_points_out, span = sizeof(float) * 4 * (size_t)max_tracks;
+    ARG_CHECK(in == out || in + span <= out || out + span <= in);
+  }
+  std::vector<int> held(nimages, 0);
+  for (int j = 0; j < nhold; j++) held[hold[j]] = 1;
+  const float thresh2 = max_error * max_error;                              // rounded once, here
+  RoctxRange range(__func__);
+  return run_batch(ctx, {{intrinsics, sizeof(float) * 4 * (size_t)nimages}, {held.data(), sizeof(int) * (size_t)nimages}},
+                   0, [&](int *h_lists, void *) {
+                     return launch_adjust_bundle_batch(ctx, max_tracks, max_obs, d_track_offsets, d_obs,
+                                                       d_export_summary, d_points, d_point_status, nimages, d_cam,
+                                                       d_cam_pair, h_lists, min_views, min_obs, num_loops, cg_iters,
+                                                       thresh2, lambda0, orthonormalise, d_cam_out, d_points_out,
+                                                       d_cam_obs, d_cam_status, d_cam_rms, d_point_obs, d_history,
+                                                       d_cost, d_summary);
+                   });
+}
+
 // ------------------------------------------------------------------- timing
 extern "C" int misift_timer_start(misift_ctx *ctx)
 {

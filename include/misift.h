@@ -1196,8 +1196,8 @@ int misift_triangulate_tracks_batch(misift_ctx *ctx,
  *      [3] cameras with status 1, [4] with status 2, [5] with status 3, [6] steps kept, [7] cameras with status 4.
  *   - With num_loops == 0 and orthonormalise == 0 every camera comes back bit for bit, and d_cam_rms[2i] is the
  *     per-image rms that d_obs_error of misift_triangulate_tracks_batch implies (over the members, under max_error).
- *   - Not done here: camera and point steps are not taken jointly (no Schur complement; alternate with triangulate
- *     instead), no robust kernel re-weights a residual (max_error is a hard gate, decided once), and the intrinsics are
+ *   - Not done here: camera and point steps are not taken jointly (no Schur complement: misift_adjust_bundle_batch does
+ *     that; or alternate with triangulate), no robust kernel re-weights a residual (max_error is a hard gate, decided once), and the intrinsics are
  *     not refined.
  *   - NULL ctx; max_tracks, max_obs or nimages < 1; NULL d_track_offsets, d_obs, d_export_summary, d_points,
  *     d_point_status, d_cam, d_cam_pair, intrinsics, d_cam_out, d_cam_obs, d_cam_rms, d_cam_steps, d_cam_status or
@@ -1337,6 +1337,123 @@ int misift_resect_cameras_batch(misift_ctx *ctx,
                                 int   *d_res_status,            /* nsel */
                                 int   *d_summary);              /* 8 ints */
 
+/* The cameras and the track points adjusted jointly (bundle adjustment; no reference counterpart): what
+ * misift_refine_cameras_batch and misift_triangulate_tracks_batch do in turns, done in one Levenberg-Marquardt step over
+ * all free cameras (6 parameters each) and all active track points (3 each).  Each step eliminates the points (Schur
+ * complement), solves the reduced camera system matrix-free by cg_iters block-Jacobi preconditioned conjugate-gradient
+ * iterations, back-substitutes the points, and is kept or turned away on the device.  In the chain: ... export ->
+ * triangulate -> resect -> triangulate -> refine -> adjust.
+ *   The inputs are those of misift_refine_cameras_batch, read the same way; d_points[4t+3] and obs.record are not read.
+ *   The arithmetic is that of misift_refine_cameras_batch: fp32, every operation rounded, only + - * / sqrtf and fabsf,
+ *   no contraction, a comparison with a NaN is false, everything taken left to right as written.  a . b of two
+ *   6-vectors is ((((a0*b0 + a1*b1) + a2*b2) + a3*b3) + a4*b4) + a5*b5.
+ *   T, O, valid tracks, the OWNER of a slot and the CANDIDATES of an image are those of misift_refine_cameras_batch.
+ *   Sets, decided once under the starting cameras and points:
+ *   - Image i has NO CAMERA (status 4) iff d_cam_pair[i] == -2 or one of its twelve floats is not finite; otherwise it is
+ *     HELD (status 3) iff d_cam_pair[i] == -1 or i is in `hold`; otherwise it is FREE.  With orthonormalise == 1 a free
+ *     camera goes through step 1 of misift_refine_cameras_batch first; a non-finite result makes it status 4 (its
+ *     twelve floats as given).  An image is USABLE iff its status is not 4.
+ *   - A candidate is a PRE-MEMBER iff its image is usable and the member test of misift_refine_cameras_batch holds under
+ *     that camera: Xc.z > 0 and ru*ru + rv*rv < E2, E2 = max_error*max_error rounded once on the host (+inf: in front
+ *     alone).  A valid track is ACTIVE iff it owns at least min_views pre-members.  The MEMBERS are the pre-members of
+ *     active tracks; the set does not change afterwards.  n_i = the members of image i, n_t = those of track t.
+ *   - A free image with n_i < min_obs is demoted: status 1, its camera (of step 1) constant.  There is no cascade: its
+ *     members, like those of held images, still constrain their points.  That is how held cameras fix the gauge.
+ *   Sums.  A PER-TRACK sum runs over the track's members in ascending slot, from +0, one term at a time.  A PER-IMAGE
+ *   sum runs over the image's members listed in ascending slot, by the 256-slot rule of
+ *   misift_improve_fundamental_batch on the position in that list: p[s], s < 256, starts at +0 and adds the terms of
+ *   positions s, s + 256, ... in ascending order; then for off = 128 ... 1: p[s] = p[s] + p[s + off] for s < off; the sum
+ *   is p[0].  A CROSS-IMAGE sum is the same rule on the image index; an image that does not take part is skipped.
+ *   The COST of a state (cameras, points): per member, Xc, iz, a, b, ru, rv as in step 2 of
+ *   misift_refine_cameras_batch; the image's cost c_i is the per-image sum of ru*ru + rv*rv, and c the cross-image sum
+ *   of c_i over all images.  A state with a member whose Xc.z > 0 is false is NOT IN FRONT.
+ *   One LM step at damping lambda (lambda = lambda0 at first), l1 = 1 + lambda:
+ *   1. Per member under the state: Ju, Jv (camera, 6 each) as step 3 of misift_refine_cameras_batch; the point's
+ *      Pu = gx * (r0 - a*r2), Pv = gy * (r1 - b*r2) per component with gx = fx*iz, gy = fy*iz;
+ *      W[r][q] = Ju[r]*Pu[q] + Jv[r]*Pv[q].  (W v)[r] = (W[r][0]*v0 + W[r][1]*v1) + W[r][2]*v2 for a 3-vector v and
+ *      (W^T v)[q] = ((((W[0][q]*v0 + W[1][q]*v1) + W[2][q]*v2) + W[3][q]*v3) + W[4][q]*v4) + W[5][q]*v5 for a 6-vector.
+ *   2. Per active track, per-track sums in the order of step 3 of misift_triangulate_tracks_batch (the row Pu with rhs
+ *      ru, then the row Pv with rhs rv): V (M00 M01 M02 M11 M12 M22) and gp.  V' = V with M00, M11, M22 each multiplied
+ *      by l1.  y_t = SOLVE(V', gp) of misift_triangulate_tracks_batch.
+ *   3. Per free image, 33 per-image sums: U[r][q], r <= q, with the term Ju[r]*Ju[q] + Jv[r]*Jv[q]; gc[r] with
+ *      Ju[r]*ru + Jv[r]*rv; s[r] with (W y_t)[r], t the member's track.  U' = U with each diagonal entry multiplied by
+ *      l1; b[r] = gc[r] - s[r].  M^-1 v is the SOLVE of step 4 of misift_refine_cameras_batch with U' and v.
+ *      A SOLVE of step 2 or 3 that fails (a pivot that is not finite and > 0, a result that is not finite; step 3 checks
+ *      M^-1 b) makes the step FAIL: nothing below is computed, c' is the quiet NaN and the CG iterations are 0.
+ *   4. PCG over the free images.  x = 0, r = b, z = M^-1 r, p = z, rho = the cross-image sum of r_i . z_i; rho not
+ *      finite: no iteration runs.  Then cg_iters times at the most:
+ *        per active track q_t = SOLVE(V', the per-track sum of (W^T p_i) over its members in free images);
+ *        per free image y_i[r] = U'[r] . p_i - (the per-image sum of (W q_t)[r]);
+ *        sigma = the cross-image sum of p_i . y_i; unless sigma is finite and > 0, CG ends here with x as it stands;
+ *        alpha = rho / sigma; x += alpha*p, r -= alpha*y per component; z = M^-1 r; rho' = the cross-image sum of
+ *        r_i . z_i; the iteration counts; rho' not finite: CG ends here; beta = rho' / rho, p = z + beta*p, rho = rho'.
+ *      A SOLVE or M^-1 whose result is not finite gives zeros.  cg_iters == 0 or no free image leaves x = 0: the step
+ *      then moves the points only.
+ *   5. Per active track delta_t = SOLVE(V', gp - the per-track sum of (W^T x_i) over its members in free images),
+ *      X' = X + delta_t per component; per free image the Cayley update of step 5 of misift_refine_cameras_batch with
+ *      x_i.
+ *   6. c' = the cost of the trial state.  The step is KEPT iff it did not fail, every trial camera and point is finite,
+ *      the trial state is in front and c' < c.  Kept: the trial state becomes the state, lambda <- max(lambda / 10, 1e-7).
+ *      Otherwise the state stays and lambda <- 10 * lambda: the raised lambda is the retry, so, unlike
+ *      misift_refine_cameras_batch, the loop does not end there.  All num_loops steps are always enqueued.
+ *      d_history[4k..4k+3] of step k: c' (the quiet NaN unless the trial state is finite and in front), the lambda used,
+ *      1 if kept else 0 (int), the CG iterations that counted (int).
+ *   Outputs.  d_cam_out[12i..]: the camera of the final state for a free or demoted image, the twelve input floats bit
+ *   for bit for any other.  d_cam_obs[i] = n_i; d_cam_status[i] = 0 adjusted (free), 1 demoted, 3 held or root, 4 no
+ *   camera; d_cam_rms[2i], [2i + 1] = sqrtf(c_i / (float)n_i) under the starting and the final state (the quiet NaN when
+ *   n_i == 0).  For t < T: d_point_obs[t] = the pre-members track t owns (0 for a track that is not valid); an active
+ *   track gets d_points_out[4t..4t+2] = its point of the final state and [4t+3] = sqrtf(ct / (float)n_t), ct the
+ *   per-track sum of ru*ru + rv*rv; every other track t < T gets its four input words bit for bit.  Entries at or beyond
+ *   T stay untouched.  d_cost[0], [1] = c of the starting and of the final state.  d_summary (8 ints, integer sums):
+ *   [0] T, [1] images with status 0, [2] members, [3] images with status 1, [4] active tracks, [5] images with status 3,
+ *   [6] steps kept, [7] images with status 4.  A single result that is a NaN is stored as 0x7fc00000.
+ *   - With num_loops == 0 and orthonormalise == 0 every camera and point comes back bit for bit, and d_cost[0] ==
+ *     d_cost[1].  On planted scenes with 0.5 px noise the fp32 result stays within the figures of
+ *     tests/test_bundle_cpu.py (MEASURED) of the same algorithm in float64.
+ *   - Departures from a textbook statement: the cost of a state is evaluated in a pass of its own (per slot, then per
+ *     image), not with the linearisation, so that num_loops == 0 and the trial evaluation share one code path; the
+ *     preconditioner is the damped U' of each camera, not the Schur diagonal block.
+ *   - Not done here: no robust kernel re-weights a residual (max_error is a hard gate, decided once), the intrinsics are
+ *     not refined, the member set is not revised between steps, and no Schur-diagonal preconditioner is formed.
+ *   - NULL ctx; max_tracks, max_obs or nimages < 1; NULL d_track_offsets, d_obs, d_export_summary, d_points,
+ *     d_point_status, d_cam, d_cam_pair, intrinsics, d_cam_out, d_points_out, d_cam_obs, d_cam_status, d_cam_rms,
+ *     d_point_obs, d_cost or d_summary, NULL d_history with num_loops > 0; d_obs not 16-byte aligned; min_views < 2;
+ *     min_obs < 3; num_loops < 0; cg_iters < 0; max_error NaN or <= 0; lambda0 not finite or <= 0; orthonormalise other
+ *     than 0 or 1; nhold < 0, nhold > 0 with NULL hold, a hold index outside [0, nimages); an fx or fy that is not
+ *     finite and > 0 or a cx or cy that is not finite; d_cam_out overlapping d_cam, or d_points_out overlapping
+ *     d_points, without being equal to it: MISIFT_EINVAL, before anything is enqueued.  None of the inputs is written,
+ *     except d_cam and d_points when they are the outputs.
+ *   - The call runs on the context stream and returns before the GPU work is done; `intrinsics` and `hold` are copied;
+ *     no host synchronisation and no host read.  Ordering behind batches in flight (K > 1): as misift_match_batch.
+ *   - Three memsets and 11 + num_loops * (8 + 3 * cg_iters) launches whatever the data: per-track work one lane per
+ *     track, per-image work one 256-thread workgroup per image (thread s = slot s of the sum), the cross-image scalars
+ *     and the 6-vector updates in one workgroup; a dispatch boundary is the only barrier between workgroups.  Temp
+ *     memory from the library's own allocator, sized from the capacities only: 100 bytes per slot, 76 per track and
+ *     352 per image, each array rounded up to 16. */
+int misift_adjust_bundle_batch(misift_ctx *ctx,
+                               int max_tracks, int max_obs,
+                               const int *d_track_offsets,     /* max_tracks + 1, from export */
+                               const misift_track_obs *d_obs,  /* max_obs, from export, 16-byte aligned */
+                               const int *d_export_summary,    /* 8 ints, from export: [2] = T, [3] = O */
+                               const float *d_points,          /* max_tracks x 4, from triangulate */
+                               const int *d_point_status,      /* max_tracks, from triangulate */
+                               int nimages,
+                               const float *d_cam,             /* nimages x 12 */
+                               const int *d_cam_pair,          /* nimages */
+                               const float *intrinsics,        /* host, nimages x 4: fx fy cx cy, copied */
+                               int nhold, const int *hold,     /* host, images kept as they are, copied; may be NULL */
+                               int min_views, int min_obs, int num_loops, int cg_iters,
+                               float max_error, float lambda0, int orthonormalise,
+                               float *d_cam_out,               /* nimages x 12; may be d_cam itself */
+                               float *d_points_out,            /* max_tracks x 4; may be d_points itself */
+                               int   *d_cam_obs,               /* nimages */
+                               int   *d_cam_status,            /* nimages */
+                               float *d_cam_rms,               /* nimages x 2: before, after */
+                               int   *d_point_obs,             /* max_tracks */
+                               float *d_history,               /* num_loops x 4 words */
+                               float *d_cost,                  /* 2: before, after */
+                               int   *d_summary);              /* 8 ints */
+
 /* cudaMallocManaged as used by the reference's MANAGEDMEM build flavour (cudaSiftH.cu:239-240): one pointer valid on
  * host and device (SiftData.m_data). */
 int misift_malloc_managed(size_t bytes, void **out);
@@ -1425,6 +1542,15 @@ int misift_test_refine_camera(const float *cam12, int cam_pair, int held, const 
                               const int *slot, const float *X, const float *xy, int min_obs, int num_loops,
                               float max_error, int orthonormalise, float *cam_out12, int *nobs, float *rms2, int *steps,
                               int *status);
+/* Test-only, host-only: the whole of misift_adjust_bundle_batch on host arrays, every phase compiled from the function
+ * its kernel runs (bundle_core.hpp).  The arguments are those of the call without the context; all pointers are host. */
+int misift_test_adjust_bundle(int max_tracks, int max_obs, const int *track_offsets, const misift_track_obs *obs,
+                              const int *export_summary, const float *points, const int *point_status, int nimages,
+                              const float *cam, const int *cam_pair, const float *intrinsics, int nhold, const int *hold,
+                              int min_views, int min_obs, int num_loops, int cg_iters, float max_error, float lambda0,
+                              int orthonormalise, float *cam_out, float *points_out, int *cam_obs, int *cam_status,
+                              float *cam_rms, int *point_obs, float *history, float *cost, int *summary);
+
 /* Test-only, host-only: steps 3 and 4 of misift_resect_cameras_batch, compiled from the functions its kernels run.  The
  * sample positions: out[6 * loop + j] = position j (in the ordered list of n >= 6 candidates) of hypothesis loop after
  * srand(seed).  The six-point solve of one sample xyXYZ[5k..5k+4] = x y X Y Z of point k < 6 under intrinsics4 = fx fy cx

@@ -1,0 +1,186 @@
+"""misift_adjust_bundle_batch beside what it replaces, one round of triangulate + refine, on one MI355X (README: device
+batches, bundle adjustment).
+
+The README's window: W = 4 over 64 frames, 246 pairs (i, i + k) at max_pts 2048, on the planted path of 64 cameras of
+tools/link_poses_time.py (2000 points, a quarter of the matches wrong, 0.5 px noise; each pair's F is the exact one of its
+planted pose).  Both chains and misift_triangulate_tracks_batch run on the device first, as in
+tools/refine_cameras_time.py: d_cam and d_cam_pair, the offsets, d_obs and the export summary, d_points and
+d_point_status.  The root and the other image of the seed pair are held.
+  (a) one LM step (num_loops 1) at cg_iters 0, 5 and 10, and num_loops 5 at cg_iters 10: HIP events on the context stream
+      around the call (misift_timer_start / misift_timer_stop_ms).
+  (b) one round of the parent's method: triangulate, then refine at num_loops 5 in place, events around the two.
+The five take turns within every repetition, so a drift of the machine meets all alike.  Every figure is the median over
+--reps repetitions after --warmup.  kernels_ms is the time per call of each kind of launch (per-track, per-image, the
+scalar workgroup, the trial state, setup and outputs), the mean over ten more calls at num_loops 5 and cg_iters 10 with
+events around every launch; shares are of their sum.  All nine outputs are compared with the numpy restatement
+(tests/bundle_cases.expected_bundle) at this size before anything is timed.  Prints one JSON line; --out FILE also writes
+it there."""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+from cudasift_amd import capi  # noqa: E402
+import bench_common  # noqa: E402,F401  (puts tests/ on the path)
+import bundle_cases as BC  # noqa: E402
+import pose_cases as PC  # noqa: E402
+import posegraph_cases as G  # noqa: E402
+import triangulate_cases as TC  # noqa: E402
+from link_poses_time import GATES, window  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--frames", type=int, default=64)
+    ap.add_argument("--window", type=int, default=4)
+    ap.add_argument("--records", type=int, default=2000)
+    ap.add_argument("--max-pts", type=int, default=2048)
+    ap.add_argument("--min-common", type=int, default=8)
+    ap.add_argument("--max-error", type=float, default=2.0)
+    ap.add_argument("--min-len", type=int, default=3)
+    ap.add_argument("--num-loops", type=int, default=5)
+    ap.add_argument("--min-obs", type=int, default=6)
+    ap.add_argument("--cg-iters", type=int, default=10)
+    ap.add_argument("--lambda0", type=float, default=1e-3)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--reps", type=int, default=40)
+    ap.add_argument("--out", default="")
+    a = ap.parse_args()
+    L = capi.lib()
+    ctx = capi.Context(0)
+    mp, n, nf = a.max_pts, a.records, a.frames
+    pairs, links, walk = window(nf, a.window)
+    npairs = len(pairs)
+    rng = np.random.default_rng(64)
+    cams = G.camera_path(nf, rng, steps=rng.uniform(0.12, 0.6, nf - 1), turn=lambda i: 0.25 * np.sin(0.3 * i))
+    centre = np.mean([-r.T @ t for r, t in cams], 0)
+    X = centre + rng.uniform([-6, -3, 9], [6, 3, 18], (n, 3))
+    raw, _ = G.scene_rows(cams, X, rng, 0.5, 0.25, pairs)
+    rows = np.zeros(npairs * mp, capi.POINT_DTYPE)
+    F, K8 = np.zeros((npairs, 9), np.float32), np.tile(np.array(PC.K_A + PC.K_A, np.float32), (npairs, 1))
+    Km = PC.kmat(PC.K_A)
+    recs = np.zeros(nf * n, capi.POINT_DTYPE)                    # the record batch the rows index: n records per image
+    for p, (i, j) in enumerate(pairs):
+        (Ra, ta), (Rb, tb) = cams[i], cams[j]
+        R, t = Rb @ Ra.T, tb - Rb @ Ra.T @ ta
+        f = np.linalg.inv(Km).T @ PC.skew(t) @ R @ np.linalg.inv(Km)
+        F[p] = (f / np.abs(f).max()).reshape(9)
+        rows[p * mp:p * mp + n] = raw[p]
+        for k, mk in (("xpos", "match_xpos"), ("ypos", "match_ypos")):
+            recs[k][i * n:(i + 1) * n] = raw[p][k]
+            recs[k][j * n + raw[p]["match"]] = raw[p][mk]
+    d_rows, rc, dF = ctx.upload(rows), ctx.upload(np.full(npairs, n, np.int32)), ctx.upload(F)
+    sel = np.arange(npairs, dtype=np.int32)
+    gates = dict(min_score=GATES[0], max_ambiguity=GATES[1])
+    # the pose chain: match_error under F, the poses and the depths, the cameras
+    ctx.improve_fundamental_batch(sel, d_rows, npairs, rc, dF, None, mp, num_loops=0, thresh=1.0, **gates)
+    dxyz = ctx.zeros(16 * npairs * mp)
+    dpose, dfront = ctx.recover_pose_batch(sel, K8, d_rows, npairs, rc, dF, None, mp, thresh=1.0, xyz=dxyz, **gates)
+    _, _, _, dcam, dcam_pair, _ = ctx.link_poses_batch(pairs, nf, d_rows, rc, mp, dpose, dfront, dxyz, links, 0, 0, walk,
+                                                       min_common=a.min_common, max_error=a.max_error, **gates)
+    # the track chain
+    total = nf * n
+    d_recs, d_cnt = ctx.upload(recs), ctx.upload(np.full(nf, n, np.int32))
+    lab = ctx.link_tracks_batch(pairs, d_rows, rc, mp, nf, d_cnt, None, n, max_records=total,
+                                max_error=a.max_error, **gates)
+    max_tracks, max_obs = total // a.min_len + 1, total
+    doff, _, dobs, _, dsum = ctx.export_tracks_batch(d_recs, nf, d_cnt, None, n, max_records=total, track=lab[0],
+                                                     track_len=lab[1], track_frames=lab[2], min_len=a.min_len,
+                                                     consistent_only=1, max_tracks=max_tracks, max_obs=max_obs,
+                                                     record_obs=None)
+    K = np.tile(np.array(PC.K_A, np.float32), (nf, 1))
+    hold = [pairs[0][1]]                                         # the seed pair is pair 0, the root its first image
+    tri = ctx.triangulate_tracks_batch(max_tracks, max_obs, doff, dobs, dsum, nf, dcam, dcam_pair, K, min_views=2,
+                                       num_loops=a.num_loops)
+    dpts, dstatus = tri[0], tri[2]
+    sizes = BC.sizes(dict(nimages=nf, max_tracks=max_tracks, num_loops=a.num_loops))
+    outs = {k: ctx.upload(np.full(m, TC.POISON_WORD, np.uint32)) for k, m in sizes.items()}
+    args = dict(min_views=2, min_obs=a.min_obs, max_error=np.inf, lambda0=a.lambda0, orthonormalise=1)
+
+    def adjust(num_loops, cg_iters):
+        ctx.adjust_bundle_batch(max_tracks, max_obs, doff, dobs, dsum, dpts, dstatus, nf, dcam, dcam_pair, K, hold=hold,
+                                num_loops=num_loops, cg_iters=cg_iters, **args, **outs)
+
+    # the same answer as the restatement at this size, before anything is timed
+    adjust(a.num_loops, a.cg_iters)
+    ctx.sync()
+    case = dict(max_tracks=max_tracks, max_obs=max_obs, track_offsets=ctx.download(doff, (max_tracks + 1,), np.int32),
+                obs=ctx.download(dobs, (max_obs,), TC.OBS_DTYPE), export_summary=ctx.download(dsum, (8,), np.int32),
+                nimages=nf, cam=ctx.download(dcam, (nf, 12), np.float32),
+                cam_pair=ctx.download(dcam_pair, (nf,), np.int32), intrinsics=K,
+                points=ctx.download(dpts, (max_tracks, 4), np.float32),
+                point_status=ctx.download(dstatus, (max_tracks,), np.int32), hold=tuple(hold), num_loops=a.num_loops,
+                cg_iters=a.cg_iters, **args)
+    e = BC.expected_bundle(case)
+    for k in BC.OUTPUTS:
+        assert ctx.download(outs[k], (sizes[k],), np.uint32).tobytes() == e[k].tobytes(), k
+    P = e["res"]["problem"]
+
+    def events(fn):
+        ms = C.c_float()
+        ctx.sync()
+        capi.check(L.misift_timer_start(ctx.h), "misift_timer_start")
+        fn()
+        capi.check(L.misift_timer_stop_ms(ctx.h, C.byref(ms)), "misift_timer_stop_ms")
+        return ms.value
+
+    dround = ctx.upload(case["cam"])                             # the round works in place on a copy of the cameras
+    tri_outs = dict(points=ctx.zeros(16 * max_tracks), point_views=ctx.zeros(4 * max_tracks),
+                    point_status=ctx.zeros(4 * max_tracks), obs_error=None, summary=ctx.zeros(32))
+    ref_outs = dict(cam_obs=ctx.zeros(4 * nf), cam_rms=ctx.zeros(8 * nf), cam_steps=ctx.zeros(4 * nf),
+                    cam_status=ctx.zeros(4 * nf), summary=ctx.zeros(32))
+
+    def full_round():
+        ctx.triangulate_tracks_batch(max_tracks, max_obs, doff, dobs, dsum, nf, dround, dcam_pair, K, min_views=2,
+                                     num_loops=5, **tri_outs)
+        ctx.refine_cameras_batch(max_tracks, max_obs, doff, dobs, dsum, tri_outs["points"], tri_outs["point_status"], nf,
+                                 dround, dcam_pair, K, hold=hold, min_obs=a.min_obs, num_loops=5, max_error=np.inf,
+                                 orthonormalise=1, cam_out=dround, **ref_outs)
+
+    times = {"adjust_loops1_cg0_events_ms": [], "adjust_loops1_cg5_events_ms": [], "adjust_loops1_cg10_events_ms": [],
+             "adjust_loops5_cg10_events_ms": [], "round_events_ms": []}
+    for rep in range(a.warmup + a.reps):                         # the five take turns
+        t = (events(lambda: adjust(1, 0)), events(lambda: adjust(1, 5)), events(lambda: adjust(1, 10)),
+             events(lambda: adjust(5, 10)), events(full_round))
+        if rep >= a.warmup:
+            for k, v in zip(times, t):
+                times[k].append(v)
+    ctx.profile_enable(True)                                     # the launches alone: events around each, a run of its own
+    ctx.profile_reset()                                          # behind the timed ones
+    for _ in range(10):
+        adjust(5, 10)
+    ctx.sync()
+    kernels = {k: round(v["total_ms"] / 10, 4) for k, v in ctx.profile_read().items() if k.startswith("bundle_")}
+    launches = {k: v["calls"] // 10 for k, v in ctx.profile_read().items() if k.startswith("bundle_")}
+    ctx.profile_enable(False)
+    total_k = sum(kernels.values())
+    cost = e["cost"].view(np.float32)
+    r = {"case": "window %d over %d frames, %d matches per pair, 25 %% wrong, 0.5 px noise, tracks of %d and more" % (
+        a.window, nf, n, a.min_len), "pairs": npairs, "tracks": int(P.T), "observations": int(P.O), "images": nf,
+        "held": hold, "min_obs": a.min_obs, "lambda0": a.lambda0, "summary": e["summary"].view(np.int32).tolist(),
+        "reps": a.reps, "steps": e["res"]["trace"], "cg_iterations": [h[3] for h in e["res"]["history"]],
+        "rms_px_before_after": [round(float(np.sqrt(c / max(len(P.slot), 1))), 4) for c in cost]}
+    for k, v in times.items():
+        r[k] = round(float(np.median(v)), 4)
+        r[k.replace("_ms", "_min_ms")] = round(float(np.min(v)), 4)
+        r[k.replace("_ms", "_p10_p90_ms")] = [round(float(x), 4) for x in np.percentile(v, [10, 90])]
+    r["kernels_ms"] = kernels
+    r["launches_per_call"] = launches
+    r["kernel_shares"] = {k: round(v / total_k, 4) for k, v in kernels.items()} if total_k else {}
+    r["adjust_loops1_cg10_vs_round"] = round(r["adjust_loops1_cg10_events_ms"] / r["round_events_ms"], 4)
+    print(json.dumps(r), flush=True)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(r, f, indent=1)
+    ctx.close()
+
+
+if __name__ == "__main__":
+    main()
