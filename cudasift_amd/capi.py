@@ -132,6 +132,11 @@ SIGNATURES = {
                                         _f, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "misift_test_adjust_bundle": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _f, _f,
                                        _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "misift_filter_tracks_batch": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _f, _f, _i, _i, _vp, _vp,
+                                        _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "misift_test_filter_tracks": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _f, _f, _i, _i, _vp, _vp, _vp,
+                                       _vp, _vp, _vp, _vp, _vp, _vp]),
+    "misift_test_filter_stage": (_i, []),
     "misift_resect_cameras_batch": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _f, _i, _i,
                                          _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "misift_test_resect_samples": (_i, [C.c_uint, _i, _i, _vp]),
@@ -1073,6 +1078,57 @@ class Context:
                                                _dptr(cam_status), _dptr(cam_rms), _dptr(point_obs), _dptr(history),
                                                _dptr(cost), _dptr(summary)), "misift_adjust_bundle_batch")
         return cam_out, points_out, cam_obs, cam_status, cam_rms, point_obs, history, cost, summary
+
+    def filter_tracks_batch(self, max_tracks, max_obs, track_offsets, obs, export_summary, points, point_status,
+                            nimages, cam, cam_pair, intrinsics, max_error=np.inf, max_cos=np.inf, min_angle_deg=None,
+                            min_views=2, unique_frames=True, track_offsets_out=None, obs_out=None,
+                            export_summary_out=None, points_out=None, point_views_out=None, point_status_out=None,
+                            track_map=None, obs_map=True, summary=None):
+        """misift_filter_tracks_batch: the observation lists (track_offsets, obs, export_summary: the outputs of
+        export_tracks_batch for max_tracks and max_obs, or of an earlier call of this one) gated against the points
+        (points, point_status) and the cameras (cam, cam_pair, for nimages images; intrinsics: host, nimages x 4) and
+        written out again in export's format.  A view is dropped when its point is bad or behind its camera or its
+        reprojection error reaches max_error px; with unique_frames, of several views of one frame only the one with the
+        smallest error stays; a track is dropped when fewer than min_views views stay or when no two of their rays are
+        further apart than the angle whose cosine is max_cos (min_angle_deg gives it in degrees instead; +inf: no
+        test).  track_offsets_out, obs_out, export_summary_out, points_out (the points copied, the rms of the kept views
+        in the fourth word), point_views_out, point_status_out go to triangulate, refine, resect and adjust as they are;
+        track_map (max_tracks ints: the new number or the reason), obs_map (max_obs ints: the new slot or the reason;
+        True allocates it, None leaves it out) and summary (8 ints) tell what became of what.  All are device buffers,
+        allocated here when not passed; returns the nine.  Nothing may overlap.  Enqueued on the context stream."""
+        intrinsics = np.ascontiguousarray(intrinsics, np.float32).reshape(-1, 4)
+        assert len(intrinsics) == nimages
+        if min_angle_deg is not None:
+            max_cos = float(np.float32(np.cos(np.deg2rad(min_angle_deg))))
+        mt, mo = max(max_tracks, 1), max(max_obs, 1)
+        if track_offsets_out is None:
+            track_offsets_out = self.zeros(4 * (mt + 1))
+        if obs_out is None:
+            obs_out = self.zeros(16 * mo)
+        if export_summary_out is None:
+            export_summary_out = self.zeros(4 * 8)
+        if points_out is None:
+            points_out = self.zeros(16 * mt)
+        if point_views_out is None:
+            point_views_out = self.zeros(4 * mt)
+        if point_status_out is None:
+            point_status_out = self.zeros(4 * mt)
+        if track_map is None:
+            track_map = self.zeros(4 * mt)
+        if obs_map is True:
+            obs_map = self.zeros(4 * mo)
+        if summary is None:
+            summary = self.zeros(4 * 8)
+        check(lib().misift_filter_tracks_batch(self.h, max_tracks, max_obs, _dptr(track_offsets), _dptr(obs),
+                                               _dptr(export_summary), _dptr(points), _dptr(point_status), nimages,
+                                               _dptr(cam), _dptr(cam_pair), intrinsics.ctypes.data, float(max_error),
+                                               float(max_cos), int(min_views), int(unique_frames),
+                                               _dptr(track_offsets_out), _dptr(obs_out), _dptr(export_summary_out),
+                                               _dptr(points_out), _dptr(point_views_out), _dptr(point_status_out),
+                                               _dptr(track_map), _dptr(obs_map), _dptr(summary)),
+              "misift_filter_tracks_batch")
+        return (track_offsets_out, obs_out, export_summary_out, points_out, point_views_out, point_status_out,
+                track_map, obs_map, summary)
 
     def resect_cameras_batch(self, max_tracks, max_obs, track_offsets, obs, export_summary, points, point_status,
                              nimages, intrinsics, images, seeds, max_cand, num_loops=1024, thresh=4.0, min_inliers=12,

@@ -674,6 +674,16 @@ int launch_adjust_bundle_batch(misift_ctx *ctx, int max_tracks, int max_obs, con
                                float thresh2, float lambda0, int orthonormalise, float *d_cam_out, float *d_points_out,
                                int *d_cam_obs, int *d_cam_status, float *d_cam_rms, int *d_point_obs, float *d_history,
                                float *d_cost, int *d_summary);
+// misift_filter_tracks_batch (kernels_filter.hip): a copy, three memsets + six launches; temp from misift_ensure_tmp,
+// sized from max_tracks, max_obs and nimages only.  h_intrinsics: nimages x 4
+size_t filter_tracks_batch_tmp_bytes(int max_tracks, int max_obs, int nimages);
+int launch_filter_tracks_batch(misift_ctx *ctx, int max_tracks, int max_obs, const int *d_track_offsets,
+                               const void *d_obs, const int *d_export_summary, const float *d_points,
+                               const int *d_point_status, int nimages, const float *d_cam, const int *d_cam_pair,
+                               const float *h_intrinsics, float thresh2, float max_cos, int min_views, int unique_frames,
+                               int *d_track_offsets_out, void *d_obs_out, int *d_export_summary_out, float *d_points_out,
+                               int *d_point_views_out, int *d_point_status_out, int *d_track_map, int *d_obs_map,
+                               int *d_summary);
 int launch_test_exp2(misift_ctx *ctx, const float *x, float *out, int n);
 int launch_test_points_fn(misift_ctx *ctx, int fn, const float *x, const float *y, float *out, float *out2, int n);
 int launch_selftest(misift_ctx *ctx);

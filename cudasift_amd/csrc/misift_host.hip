@@ -2736,6 +2736,54 @@ extern "C" int misift_adjust_bundle_batch(misift_ctx *ctx, int max_tracks, int m
                    });
 }
 
+// The observation lists gated against the current points and cameras and written out again in export's format: per
+// slot the reprojection gate, per track the duplicate frames, the view count and the widest angle.  The intrinsics go to
+// the pinned slot.
+extern "C" int misift_filter_tracks_batch(misift_ctx *ctx, int max_tracks, int max_obs, const int *d_track_offsets,
+                                          const misift_track_obs *d_obs, const int *d_export_summary,
+                                          const float *d_points, const int *d_point_status, int nimages,
+                                          const float *d_cam, const int *d_cam_pair, const float *intrinsics,
+                                          float max_error, float max_cos, int min_views, int unique_frames,
+                                          int *d_track_offsets_out, misift_track_obs *d_obs_out,
+                                          int *d_export_summary_out, float *d_points_out, int *d_point_views_out,
+                                          int *d_point_status_out, int *d_track_map, int *d_obs_map, int *d_summary)
+{
+  ARG_CHECK(ctx && max_tracks >= 1 && max_obs >= 1 && nimages >= 1);
+  ARG_CHECK(d_track_offsets && d_obs && d_export_summary && d_points && d_point_status && d_cam && d_cam_pair);
+  ARG_CHECK(intrinsics && d_track_offsets_out && d_obs_out && d_export_summary_out && d_points_out);
+  ARG_CHECK(d_point_views_out && d_point_status_out && d_track_map && d_summary);
+  ARG_CHECK(((uintptr_t)d_obs & 15) == 0 && ((uintptr_t)d_obs_out & 15) == 0);
+  ARG_CHECK(min_views >= 2 && (unique_frames == 0 || unique_frames == 1));
+  ARG_CHECK(max_error > 0.0f);                                              // NaN fails too
+  ARG_CHECK(max_cos == max_cos);
+  for (int i = 0; i < nimages; i++) ARG_CHECK(intrinsics_usable(intrinsics + 4 * (size_t)i, 1));
+  {
+    // compaction moves entries across workgroups: no output may share a byte with an input or with another output
+    const size_t mt = (size_t)max_tracks, mo = (size_t)max_obs, n = (size_t)nimages;
+    const struct { const void *p; size_t bytes; } span[16] = {
+        {d_track_offsets_out, 4 * (mt + 1)}, {d_obs_out, 16 * mo}, {d_export_summary_out, 32}, {d_points_out, 16 * mt},
+        {d_point_views_out, 4 * mt}, {d_point_status_out, 4 * mt}, {d_track_map, 4 * mt}, {d_obs_map, 4 * mo},
+        {d_summary, 32},
+        {d_track_offsets, 4 * (mt + 1)}, {d_obs, 16 * mo}, {d_export_summary, 32}, {d_points, 16 * mt},
+        {d_point_status, 4 * mt}, {d_cam, 48 * n}, {d_cam_pair, 4 * n}};
+    for (int a = 0; a < 9; a++)
+      for (int b = a + 1; b < 16; b++) {
+        if (!span[a].p || !span[b].p) continue;                             // d_obs_map may be NULL
+        const uintptr_t pa = (uintptr_t)span[a].p, pb = (uintptr_t)span[b].p;
+        ARG_CHECK(pa + span[a].bytes <= pb || pb + span[b].bytes <= pa);
+      }
+  }
+  const float thresh2 = max_error * max_error;                              // rounded once, here
+  RoctxRange range(__func__);
+  return run_batch(ctx, {{intrinsics, sizeof(float) * 4 * (size_t)nimages}}, 0, [&](int *h_lists, void *) {
+    return launch_filter_tracks_batch(ctx, max_tracks, max_obs, d_track_offsets, d_obs, d_export_summary, d_points,
+                                      d_point_status, nimages, d_cam, d_cam_pair,
+                                      reinterpret_cast<const float *>(h_lists), thresh2, max_cos, min_views,
+                                      unique_frames, d_track_offsets_out, d_obs_out, d_export_summary_out, d_points_out,
+                                      d_point_views_out, d_point_status_out, d_track_map, d_obs_map, d_summary);
+  });
+}
+
 // ------------------------------------------------------------------- timing
 extern "C" int misift_timer_start(misift_ctx *ctx)
 {

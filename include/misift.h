@@ -1099,7 +1099,8 @@ int misift_export_tracks_batch(misift_ctx *ctx,
  *      d_summary (8 ints, integer sums, so deterministic): [0] T, [1] tracks with status 0, [2] their usable views,
  *      [3] tracks with status 1, [4] with status 2, [5] with status 3, [6] Gauss-Newton steps kept, [7] tracks with
  *      status 4.
- *   - Not done here: no view is rejected as an outlier (gate on d_obs_error and call again), the cameras are not
+ *   - Not done here: no view is rejected as an outlier (misift_filter_tracks_batch does that on the device, then call
+ *     this again), the cameras are not
  *     adjusted, and d_cam is used as it is, without re-orthonormalising its rotations: misift_refine_cameras_batch does
  *     both and hands back cameras for the next call of this one.
  *   - NULL ctx; max_tracks, max_obs or nimages < 1; NULL d_track_offsets, d_obs, d_export_summary, d_cam, d_cam_pair,
@@ -1197,7 +1198,8 @@ int misift_triangulate_tracks_batch(misift_ctx *ctx,
  *   - With num_loops == 0 and orthonormalise == 0 every camera comes back bit for bit, and d_cam_rms[2i] is the
  *     per-image rms that d_obs_error of misift_triangulate_tracks_batch implies (over the members, under max_error).
  *   - Not done here: camera and point steps are not taken jointly (no Schur complement: misift_adjust_bundle_batch does
- *     that; or alternate with triangulate), no robust kernel re-weights a residual (max_error is a hard gate, decided once), and the intrinsics are
+ *     that; or alternate with triangulate), no robust kernel re-weights a residual (max_error is a hard gate, decided once;
+ *     misift_filter_tracks_batch revises the lists between calls), and the intrinsics are
  *     not refined.
  *   - NULL ctx; max_tracks, max_obs or nimages < 1; NULL d_track_offsets, d_obs, d_export_summary, d_points,
  *     d_point_status, d_cam, d_cam_pair, intrinsics, d_cam_out, d_cam_obs, d_cam_rms, d_cam_steps, d_cam_status or
@@ -1454,6 +1456,95 @@ int misift_adjust_bundle_batch(misift_ctx *ctx,
                                float *d_cost,                  /* 2: before, after */
                                int   *d_summary);              /* 8 ints */
 
+/* The observation lists of misift_export_tracks_batch gated against the current points and cameras and written out
+ * again, compact and in export's own format (no reference counterpart): per observation the reprojection error, per
+ * track the duplicate frames, the number of views and the triangulation angle.  It is what "gate on d_obs_error and call
+ * again" (triangulate), "a hard gate, decided once" (refine) and "the member set is not revised between steps" (adjust)
+ * leave to the caller, done on the device: adjust -> filter -> triangulate or adjust on the filter's outputs, with no
+ * list read back.  Every later call (triangulate, refine, resect, adjust) takes the outputs unchanged.
+ *   The inputs are those of misift_refine_cameras_batch and are read as there: d_track_offsets, d_obs and
+ *   d_export_summary from export (or from an earlier call of this one), d_points and d_point_status from triangulate or
+ *   adjust, d_cam and d_cam_pair, intrinsics[4i..4i+3] = fx fy cx cy.  obs.record and d_points[4t+3] are not read.
+ *   The arithmetic is that of misift_refine_cameras_batch: fp32, every operation rounded, only + - * / and sqrtf, no
+ *   contraction, a comparison with a NaN is false, everything left to right as written; a . b = (a0*b0 + a1*b1) + a2*b2.
+ *   T, O, VALID tracks and the OWNER of a slot are those of misift_refine_cameras_batch.
+ *   1. Per slot o < O, the first reason that applies:
+ *        -1  the slot has no owner;
+ *        -2  its owner t has d_point_status[t] != 0 or a non-finite X = d_points[4t..4t+2];
+ *        -3  the view is not USABLE in the sense of step 1 of misift_triangulate_tracks_batch: its frame f outside
+ *            [0, nimages), d_cam_pair[f] == -2, a non-finite float among d_cam[12f..], or a non-finite x or y;
+ *        -4  Xc.z > 0 is false;
+ *        -5  e2 < E2 is false, with e2 = ru*ru + rv*rv exactly as in step 2 of misift_refine_cameras_batch and
+ *            E2 = max_error*max_error rounded once on the host.  The test is plain: there is no special case for +inf,
+ *            so a NaN or +inf e2 never passes.
+ *      A slot with none of these reasons is a SURVIVOR with its e2.
+ *   2. Duplicates, with unique_frames == 1.  Survivor o LOSES (-6) iff another survivor o' of the same track and frame has
+ *      e2' < e2, or e2' == e2 and o' < o.  The KEPT views of track t are its survivors that did not lose (all of them
+ *      with unique_frames == 0); m = their number.
+ *   3. Per track t < T: d_track_map[t] = -1 if the track is not valid; -2 if its point is bad as in rule 1; -7 if
+ *      m < min_views; -8 if max_cos < +inf and NO pair k < l of its kept views has u_k . u_l < max_cos.  Per kept view,
+ *      with r0, r1, r2 the rows of R_f: C[c] = -((r0[c]*t0 + r1[c]*t1) + r2[c]*t2), d = X - C per component,
+ *      n = sqrtf(d . d), u = d / n per component: the unit ray from the camera centre to the point.  max_cos is the
+ *      cosine of the smallest triangulation angle the caller accepts, passed as a float so that no cosf stands between
+ *      this text and its restatement; +inf switches the test off.  "A pair exists" does not depend on an order, so the
+ *      decision is pinned without pinning a reduction order.  A point on a camera centre gives n = 0 and a NaN ray,
+ *      which is wide apart from nothing.  The kept views of a track dropped with -7 or -8 get that code in d_obs_map;
+ *      every other slot keeps its own reason.
+ *   4. Numbering.  The surviving tracks are numbered t' = 0, 1, ... in ascending t; off'[t'] = the sum of m over the
+ *      surviving tracks before it; within a track the kept views go in ascending slot.  d_obs_out[off' + k] = the 16
+ *      input bytes of the k-th kept view, bit for bit; d_track_offsets_out[0 .. T'] = off' ([0] = 0 always);
+ *      d_points_out[4t' .. 4t'+2] = the three input words, bit for bit; d_points_out[4t'+3] = sqrtf(s / (float)m), s the
+ *      sum of the kept e2 in ascending slot, from +0, one term at a time; d_point_views_out[t'] = m;
+ *      d_point_status_out[t'] = 0; d_track_map[t] = t'; d_obs_map[o] = the new slot.  Entries at or beyond T' (beyond
+ *      T' + 1 of the offsets) and O', beyond T of d_track_map and beyond O of d_obs_map stay untouched.
+ *   5. d_export_summary_out (8 ints) has export's layout; the result is never larger than the input, so nothing is cut:
+ *      [0] = [2] = T', [1] = [3] = O', [4] = the largest m kept (0 if none), [5] = [6] = [7] = 0.
+ *   6. d_summary (8 ints, integer sums): [0] T', [1] O', [2] slots with -4, [3] with -5, [4] with -6, [5] tracks with
+ *      -7, [6] tracks with -8, [7] slots with -1, -2 or -3.
+ *   - Deterministic: byte-identical from run to run.  Every index read from device memory (T, O, offsets, frames) is
+ *     range-checked before it addresses anything.
+ *   - Idempotent: run on its own outputs with the same arguments it keeps everything: T'' = T', O'' = O', the same bytes.
+ *   - With max_error = +inf, max_cos = +inf, unique_frames = 0 and min_views = 2 on export's and triangulate's own output
+ *     it drops exactly the tracks triangulate did not give status 0, and the views triangulate did not use or that lie
+ *     behind a camera.
+ *   - Not done here: no robust re-weighting (the gate is hard); the records it removes are not merged into new tracks;
+ *     the points are not re-estimated (d_points_out[4t'+3] is the rms of the kept views under the OLD point), so call
+ *     triangulate or adjust afterwards.
+ *   - NULL ctx; max_tracks, max_obs or nimages < 1; a NULL pointer other than d_obs_map; d_obs or d_obs_out not 16-byte
+ *     aligned; min_views < 2; unique_frames other than 0 or 1; max_error NaN or <= 0; max_cos NaN; an fx or fy that is
+ *     not finite and > 0 or a cx or cy that is not finite; an output overlapping an input or another output, each taken
+ *     at its stated size (in place is NOT supported: compaction moves entries across workgroups): MISIFT_EINVAL, before
+ *     anything is enqueued.  None of the inputs is written.
+ *   - The call runs on the context stream and returns before the GPU work is done; `intrinsics` is copied; no host
+ *     synchronisation and no host read.  Ordering behind batches in flight (K > 1): as misift_match_batch.
+ *   - One copy, three memsets and six launches whatever the data: the owners, one lane per slot for rule 1, one wavefront
+ *     per track for rules 2 and 3 (its first 256 views staged on chip, a longer track reads the rest from temp memory),
+ *     the scan of 2048-track tile sums in one workgroup, one lane per track for the numbering, one wavefront per track
+ *     for the copy; no workgroup waits for another.  Temp memory from the library's own allocator, sized from the
+ *     capacities only: 24 bytes per slot, 8 per track plus 8 per 2048 tracks, and 16 per image, each array rounded up
+ *     to 16. */
+int misift_filter_tracks_batch(misift_ctx *ctx,
+                               int max_tracks, int max_obs,
+                               const int *d_track_offsets,     /* max_tracks + 1, from export */
+                               const misift_track_obs *d_obs,  /* max_obs, from export, 16-byte aligned */
+                               const int *d_export_summary,    /* 8 ints, from export: [2] = T, [3] = O */
+                               const float *d_points,          /* max_tracks x 4, from triangulate or adjust */
+                               const int *d_point_status,      /* max_tracks, from triangulate */
+                               int nimages,
+                               const float *d_cam,             /* nimages x 12 */
+                               const int *d_cam_pair,          /* nimages */
+                               const float *intrinsics,        /* host, nimages x 4: fx fy cx cy, copied */
+                               float max_error, float max_cos, int min_views, int unique_frames,
+                               int *d_track_offsets_out,       /* max_tracks + 1 */
+                               misift_track_obs *d_obs_out,    /* max_obs, 16-byte aligned */
+                               int *d_export_summary_out,      /* 8 ints, export's layout */
+                               float *d_points_out,            /* max_tracks x 4 */
+                               int *d_point_views_out,         /* max_tracks */
+                               int *d_point_status_out,        /* max_tracks */
+                               int *d_track_map,               /* max_tracks: t' or the reason */
+                               int *d_obs_map,                 /* max_obs: the new slot or the reason; may be NULL */
+                               int *d_summary);                /* 8 ints */
+
 /* cudaMallocManaged as used by the reference's MANAGEDMEM build flavour (cudaSiftH.cu:239-240): one pointer valid on
  * host and device (SiftData.m_data). */
 int misift_malloc_managed(size_t bytes, void **out);
@@ -1550,6 +1641,17 @@ int misift_test_adjust_bundle(int max_tracks, int max_obs, const int *track_offs
                               int min_views, int min_obs, int num_loops, int cg_iters, float max_error, float lambda0,
                               int orthonormalise, float *cam_out, float *points_out, int *cam_obs, int *cam_status,
                               float *cam_rms, int *point_obs, float *history, float *cost, int *summary);
+
+/* Test-only, host-only: the whole of misift_filter_tracks_batch on host arrays, every rule compiled from the function
+ * its kernels run (filter_core.hpp).  The arguments are those of the call without the context; all pointers are host;
+ * no overlap check.  misift_test_filter_stage: the views of a track its wavefront stages on chip. */
+int misift_test_filter_tracks(int max_tracks, int max_obs, const int *track_offsets, const misift_track_obs *obs,
+                              const int *export_summary, const float *points, const int *point_status, int nimages,
+                              const float *cam, const int *cam_pair, const float *intrinsics, float max_error,
+                              float max_cos, int min_views, int unique_frames, int *track_offsets_out,
+                              misift_track_obs *obs_out, int *export_summary_out, float *points_out,
+                              int *point_views_out, int *point_status_out, int *track_map, int *obs_map, int *summary);
+int misift_test_filter_stage(void);
 
 /* Test-only, host-only: steps 3 and 4 of misift_resect_cameras_batch, compiled from the functions its kernels run.  The
  * sample positions: out[6 * loop + j] = position j (in the ordered list of n >= 6 candidates) of hypothesis loop after
