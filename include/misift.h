@@ -180,6 +180,28 @@ size_t misift_scratch_floats(int width, int height, int num_octaves, int scale_u
  *   same records, bit for bit.  Nothing is written in front of d_scratch or behind its misift_scratch_floats() floats.
  * d_pts: max_pts records.  *num_pts_out follows the reference's rule
  * numPts = min(counter[2*num_octaves], max_pts) (cudaSiftH.cu:115-116).
+ * max_pts is a capacity, not a selection.  Let c be the 17 counters an unlimited call would leave (misift_get_counters:
+ *   the detections of octave k, coarsest k = 1, are the rows [c[2k-1], c[2k]), its second orientations the rows
+ *   [c[2k], c[2k+1])).  With any max_pts >= 1, and for every frame of every batch call below alike:
+ *   - numPts = min(c[2*num_octaves], max_pts), with options.fix_numpts min(c[2*num_octaves+1], max_pts); the packed
+ *     call's d_counts_out[f] is the same number.
+ *   - The rows [0, min(c[2*num_octaves+1], max_pts)) of d_pts hold records — this includes the finest octave's second
+ *     orientations behind numPts when fix_numpts is 0 — and no row behind them, no row of another frame and no packed
+ *     record behind d_offsets_out[nframes] is written.  A segment that ends at or below max_pts holds exactly the records
+ *     it holds in the unlimited call.  The one segment that contains row max_pts holds max_pts - start distinct records of
+ *     that same segment of the unlimited call, each complete and equal to what it is there (scale_up: halved exactly once
+ *     inside numPts); WHICH of the segment's records they are follows the append order and may differ from run to run
+ *     and from the reference's choice.  Everything behind row max_pts is dropped, never moved forward.
+ *   - A dropped record is still counted: every counter word whose unlimited value is below max_pts has that value, every
+ *     other word is >= max_pts, and the per-octave detection counts c[2k] - c[2k-1] are those of the unlimited call.  The
+ *     duplicate counts from the cut on are not specified: a dropped detection may get no orientation.
+ *   - options.deterministic = 1 at capacity: repeated calls are byte-identical over [0, numPts) on every frame whose
+ *     per-octave detection counts are all <= max_pts (the fused path stages each octave's detections in a list of
+ *     max_pts entries and orders the list before anything is cut).  Where an octave's list itself overflows, which
+ *     detections it keeps is the append order again and only the rule above holds.  The dense kernels (fused = 0, or the
+ *     exact re-run after a candidate-list overflow) have no staging list — they append to d_pts itself and order its
+ *     segments afterwards — so there the promise covers the frames in which no segment inside numPts is cut, i.e. whose
+ *     unlimited numPts is <= max_pts.
  * One host<->device sync (the count read-back), like the reference.
  * Completion: the call returns after the context's stream has been synchronised — every record is written and visible
  * to any stream, device or host copy, like the reference's blocking ExtractSift.  misift_ctx_set_early_return(ctx, 1)
