@@ -110,6 +110,17 @@ __device__ __forceinline__ float4 quad_from_right(float4 v)
   return make_float4(lane_from_right(v.x), lane_from_right(v.y), lane_from_right(v.z), lane_from_right(v.w));
 }
 
+// Packed fp32 (v_pk_mul/add/fma_f32): a v2f is an even-aligned VGPR pair.  __builtin_elementwise_fma is llvm.fma, one
+// rounding per element, so a chain written on v2f has the bits of the same chain written on floats.
+typedef float v2f __attribute__((ext_vector_type(2)));
+struct Quad2 { v2f lo, hi; };                 // pixels (x,y) and (z,w) of a quad
+
+__device__ __forceinline__ v2f pk_fma(v2f a, v2f b, v2f c) { return __builtin_elementwise_fma(a, b, c); }
+__device__ __forceinline__ v2f mk2(float a, float b) { v2f r; r.x = a; r.y = b; return r; }
+__device__ __forceinline__ Quad2 q2(float4 v) { Quad2 r; r.lo = mk2(v.x, v.y); r.hi = mk2(v.z, v.w); return r; }
+__device__ __forceinline__ v2f lane_from_left2(v2f v) { return mk2(lane_from_left(v.x), lane_from_left(v.y)); }
+__device__ __forceinline__ v2f lane_from_right2(v2f v) { return mk2(lane_from_right(v.x), lane_from_right(v.y)); }
+
 // The dispatcher places workgroup b on XCD b % 8 (MI355X_MICROARCH.md).  Remap so
 // that the blocks sharing an XCD (and its private 4 MiB L2) are consecutive
 // logical blocks, i.e. spatial neighbours.  Bijective for any nb; speed only.
@@ -171,6 +182,15 @@ __device__ __forceinline__ float conv9_expr(const float k0, const float k1, cons
   s = __builtin_fmaf(k2, p2, s);
   s = __builtin_fmaf(k3, p3, s);
   s = __builtin_fmaf(k4, p4, s);
+  return s;
+}
+// conv9_expr on two pixels at once: one v_pk_mul_f32 and four v_pk_fma_f32 (t.k[0] = centre tap).
+__device__ __forceinline__ v2f conv9_expr2(const Taps5 &t, v2f c, v2f p1, v2f p2, v2f p3, v2f p4)
+{
+  v2f s = pk_fma(mk2(t.k[0], t.k[0]), c, mk2(t.k[1], t.k[1]) * p1);
+  s = pk_fma(mk2(t.k[2], t.k[2]), p2, s);
+  s = pk_fma(mk2(t.k[3], t.k[3]), p3, s);
+  s = pk_fma(mk2(t.k[4], t.k[4]), p4, s);
   return s;
 }
 

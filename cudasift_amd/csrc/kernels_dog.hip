@@ -96,12 +96,7 @@ __device__ __forceinline__ float4 blur_quad(const float *k, float4 c, float4 p1,
 // dog_scan_kernel: with the taps as SGPR pairs (80 SGPRs) the detection code runs out of scalar
 // registers and the compiler spills them through v_readlane/v_writelane inside the row loop.  Same
 // fmaf chains (__builtin_elementwise_fma is llvm.fma — one rounding), hence the same bits as blur_quad().
-typedef float v2f __attribute__((ext_vector_type(2)));
-struct Quad2 { v2f lo, hi; };                 // pixels (x,y) and (z,w) of a quad
-
-__device__ __forceinline__ v2f pk_fma(v2f a, v2f b, v2f c) { return __builtin_elementwise_fma(a, b, c); }
-__device__ __forceinline__ v2f mk2(float a, float b) { v2f r; r.x = a; r.y = b; return r; }
-
+// (v2f, Quad2, pk_fma, mk2: common.hpp)
 __device__ __forceinline__ void fill_lds_taps(v2f *s_taps, const LaplaceTaps &taps)
 {
   for (int i = threadIdx.x; i < NUM_BLURS * 5; i += blockDim.x) {
@@ -139,7 +134,6 @@ __device__ __forceinline__ Quad2 blur_quad2(const Taps2 &t, Quad2 c, Quad2 p1, Q
   o.lo = h0; o.hi = h1;
   return o;
 }
-__device__ __forceinline__ Quad2 q2(float4 v) { Quad2 r; r.lo = mk2(v.x, v.y); r.hi = mk2(v.z, v.w); return r; }
 __device__ __forceinline__ Quad2 add_q2(Quad2 a, Quad2 b) { Quad2 r; r.lo = a.lo + b.lo; r.hi = a.hi + b.hi; return r; }
 __device__ __forceinline__ float4 add4p(float4 a, float4 b)      // two v_pk_add_f32
 {
@@ -158,8 +152,6 @@ __device__ __forceinline__ float4 sub_q2(Quad2 a, Quad2 b)
 // (w, right.x) that straddle the quad's pairs and cost ~50 v_mov/v_pk_mov per row to assemble.  Same fmaf
 // chain per value as blur_quad().
 struct Pair4 { v2f x, y, z, w; };
-__device__ __forceinline__ v2f lane_from_left2(v2f v) { return mk2(lane_from_left(v.x), lane_from_left(v.y)); }
-__device__ __forceinline__ v2f lane_from_right2(v2f v) { return mk2(lane_from_right(v.x), lane_from_right(v.y)); }
 __device__ __forceinline__ v2f conv9p(const Taps2 &t, v2f c, v2f p1, v2f p2, v2f p3, v2f p4)
 {
   v2f s = t.k0 * c;

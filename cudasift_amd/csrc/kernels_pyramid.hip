@@ -77,6 +77,73 @@ __device__ __forceinline__ void store_quad(float *row, int q, int width, bool al
   }
 }
 
+// The row loops below compute on pixel pairs (Quad2: (x, y) and (z, w) of the lane's quad), one v_pk_* instruction per
+// pair.  gfx950 wants the 64-bit operands of packed math in even-aligned register pairs, so what matters is WHERE a
+// value is born: every pair here is either an aligned half of a quad as it stands or the destination of the instructions
+// that compute it.  Left to pair float4 code up by itself the compiler packs the same arithmetic but assembles the
+// operands that straddle the quad's pairs — (c.y + l.w, c.z + c.x) and the like — with moves: a third of the
+// instructions of a lowpass_down row (r07, profiles/r07_pyramid_rowloop.md).
+__device__ __forceinline__ float4 f4(const Quad2 &v) { return make_float4(v.lo.x, v.lo.y, v.hi.x, v.hi.y); }
+// a + b as ONE v_add_f32, fmaf(k, c, s) as ONE v_fmac_f32 (k wave-uniform).  Written as asm, like sub1() of
+// kernels_dog.hip, because the SLP vectoriser otherwise pairs two of them whose operands straddle register pairs into a
+// packed instruction and assembles its operands with up to four v_mov (a packed instruction issues in 4.4 - 4.8 cycles,
+// two single ones in 5.6: profiles/r02_valu_rates.txt — the moves are the loss).  Same IEEE operations.
+__device__ __forceinline__ float add1(float a, float b)
+{
+  float r;
+  asm("v_add_f32_e32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+}
+__device__ __forceinline__ float fmac1(float k, float c, float s)
+{
+  asm("v_fmac_f32_e32 %0, %1, %2" : "+v"(s) : "s"(k), "v"(c));
+  return s;
+}
+// Compute v here.  Without it the compiler sinks the packed half of a window row's horizontal filter from the prologue to
+// the row's first use, past the asm sums that stay behind: the sums of all eight rows then wait in registers and spill.
+__device__ __forceinline__ void pin_here(Quad2 &v) { asm volatile("" : "+v"(v.lo), "+v"(v.hi)); }
+
+// Horizontal 9-tap of a quad; l / r = the neighbour lanes' quads (DPP).  conv9_expr's chain per pixel.  The pair sums
+// at even tap offsets are aligned pairs (v_pk_add_f32); those at odd offsets straddle them and are single v_add_f32
+// whose destinations are the two halves of one pair.  4 pk_add + 8 add + 2 pk_mul + 8 pk_fma per quad.
+__device__ __forceinline__ Quad2 hfilt9(const Taps5 &t, const Quad2 &c)
+{
+  const v2f ll = lane_from_left2(c.lo), lh = lane_from_left2(c.hi);
+  const v2f rl = lane_from_right2(c.lo), rh = lane_from_right2(c.hi);
+  Quad2 h;
+  h.lo = conv9_expr2(t, c.lo, mk2(add1(c.lo.y, lh.y), add1(c.hi.x, c.lo.x)), c.hi + lh,
+                     mk2(add1(c.hi.y, ll.y), add1(rl.x, lh.x)), rl + ll);
+  h.hi = conv9_expr2(t, c.hi, mk2(add1(c.hi.y, c.lo.y), add1(rl.x, c.hi.x)), rl + c.lo,
+                     mk2(add1(rl.y, lh.y), add1(rh.x, c.lo.x)), rh + lh);
+  return h;
+}
+// Vertical 9-tap: rows y-4 .. y+4 of the horizontally filtered image.
+__device__ __forceinline__ Quad2 vfilt9(const Taps5 &t, const Quad2 &w0, const Quad2 &w1, const Quad2 &w2, const Quad2 &w3,
+                                        const Quad2 &w4, const Quad2 &w5, const Quad2 &w6, const Quad2 &w7, const Quad2 &w8)
+{
+  Quad2 o;
+  o.lo = conv9_expr2(t, w4.lo, w3.lo + w5.lo, w2.lo + w6.lo, w1.lo + w7.lo, w0.lo + w8.lo);
+  o.hi = conv9_expr2(t, w4.hi, w3.hi + w5.hi, w2.hi + w6.hi, w1.hi + w7.hi, w0.hi + w8.hi);
+  return o;
+}
+// Two outputs A, B of ScaleDown's horizontal 5-tap, each from the pixels m2 m1 c p1 p2 around its centre:
+// fmaf(k2, c, fmaf(k0, m2 + p2, k1 * (m1 + p1))), t.k[2] = centre tap (reference order).  The centres of neighbouring
+// outputs lie two pixels apart — never an aligned pair — so the last fmaf stays single; the rest is packed.
+__device__ __forceinline__ v2f dec5_pair(const Taps5 &t, float m2a, float m1a, float ca, float p1a, float p2a,
+                                         float m2b, float m1b, float cb, float p1b, float p2b)
+{
+  const v2f s = pk_fma(mk2(t.k[0], t.k[0]), mk2(add1(m2a, p2a), add1(m2b, p2b)),
+                       mk2(t.k[1], t.k[1]) * mk2(add1(m1a, p1a), add1(m1b, p1b)));
+  return mk2(fmac1(t.k[2], ca, s.x), fmac1(t.k[2], cb, s.y));
+}
+// ScaleDown's vertical 5-tap on a pair of columns: rows 2Y-2 .. 2Y+2 of the horizontally decimated image.
+__device__ __forceinline__ v2f vdec5(const Taps5 &t, v2f a0, v2f a1, v2f a2, v2f a3, v2f a4)
+{
+  v2f s = pk_fma(mk2(t.k[2], t.k[2]), a2, mk2(t.k[0], t.k[0]) * (a0 + a4));
+  s = pk_fma(mk2(t.k[1], t.k[1]), a1 + a3, s);
+  return s;
+}
+
 // ------------------------------------------------------------------ LowPass
 // out = G9^T (vertical) applied to G9 (horizontal) applied to in, clamp-to-edge.
 template <bool FAST, typename SRC>
@@ -94,41 +161,24 @@ __global__ __launch_bounds__(256, 4) void lowpass_kernel(const SRC *__restrict__
   float *out = dst + (long long)it.frame * dst_frame_stride;
   const int y0 = it.seg * g.seg_rows;
   const int y1 = min(y0 + g.seg_rows, g.height);
-  const float k0 = t.k[0], k1 = t.k[1], k2 = t.k[2], k3 = t.k[3], k4 = t.k[4];
   const bool sal = src_aligned != 0, dal = dst_aligned != 0;
   const QuadCol qc = make_quadcol(q, g.width);
   auto ldraw = [&](int y) -> float4 {
     return load_quad_t<FAST>(img + (size_t)clampi(y, 0, g.height - 1) * g.pitch, q, g.width, sal, qc);
   };
-
-  auto hfilt = [&](const float4 c) -> float4 {
-    const float4 l = quad_from_left(c);
-    const float4 r = quad_from_right(c);
-    float4 h;
-    h.x = conv9_expr(k0, k1, k2, k3, k4, c.x, c.y + l.w, c.z + l.z, c.w + l.y, r.x + l.x);
-    h.y = conv9_expr(k0, k1, k2, k3, k4, c.y, c.z + c.x, c.w + l.w, r.x + l.z, r.y + l.y);
-    h.z = conv9_expr(k0, k1, k2, k3, k4, c.z, c.w + c.y, r.x + c.x, r.y + l.w, r.z + l.z);
-    h.w = conv9_expr(k0, k1, k2, k3, k4, c.w, r.x + c.z, r.y + c.y, r.z + c.x, r.w + l.w);
-    return h;
-  };
-  auto hrow = [&](int y) -> float4 { return hfilt(ldraw(y)); };
-
-  float4 w0 = hrow(y0 - 4), w1 = hrow(y0 - 3), w2 = hrow(y0 - 2), w3 = hrow(y0 - 1), w4 = hrow(y0);
-  float4 w5 = hrow(y0 + 1), w6 = hrow(y0 + 2), w7 = hrow(y0 + 3), w8;
+  auto hrow = [&](int y) -> Quad2 { Quad2 h = hfilt9(t, q2(ldraw(y))); pin_here(h); return h; };
+  Quad2 w0 = hrow(y0 - 4), w1 = hrow(y0 - 3), w2 = hrow(y0 - 2), w3 = hrow(y0 - 1), w4 = hrow(y0);
+  Quad2 w5 = hrow(y0 + 1), w6 = hrow(y0 + 2), w7 = hrow(y0 + 3), w8;
   // two rows of loads stay in flight per wavefront: with ~4 resident waves per SIMD one row ahead only
   // keeps ~4 MB in flight chip-wide, which caps the stream near 4 TB/s at ~1 us of HBM latency
   float4 raw = ldraw(y0 + 4), raw1 = ldraw(y0 + 5);
   const bool writer = lane >= 1 && lane <= OUT_LANES && 4 * q < g.width;
   for (int y = y0; y < y1; y++) {
     const float4 rawnext = ldraw(y + 6);
-    w8 = hfilt(raw);
+    w8 = hfilt9(t, q2(raw));
     raw = raw1;
     raw1 = rawnext;
-    float4 o;
-    o.x = conv9_expr(k0, k1, k2, k3, k4, w4.x, w3.x + w5.x, w2.x + w6.x, w1.x + w7.x, w0.x + w8.x);
-    o.y = conv9_expr(k0, k1, k2, k3, k4, w4.y, w3.y + w5.y, w2.y + w6.y, w1.y + w7.y, w0.y + w8.y);
-    o.z = conv9_expr(k0, k1, k2, k3, k4, w4.z, w3.z + w5.z, w2.z + w6.z, w1.z + w7.z, w0.z + w8.z);
-    o.w = conv9_expr(k0, k1, k2, k3, k4, w4.w, w3.w + w5.w, w2.w + w6.w, w1.w + w7.w, w0.w + w8.w);
+    const float4 o = f4(vfilt9(t, w0, w1, w2, w3, w4, w5, w6, w7, w8));
     if (writer) {
       if (FAST) *reinterpret_cast<float4 *>(out + (size_t)y * dpitch + 4 * q) = o;
       else store_quad(out + (size_t)y * dpitch, q, g.width, dal, o);
@@ -173,59 +223,34 @@ __device__ __forceinline__ void lowpass_down_item(const SRC *__restrict__ src, c
   float *out2 = dst2 + (long long)it.frame * dst2_frame_stride;
   const int y0 = it.seg * g.seg_rows;                      // seg_rows is even
   const int y1 = min(y0 + g.seg_rows, g.height);
-  const int h2 = g.height / 2;
-  const float k0 = t.k[0], k1 = t.k[1], k2 = t.k[2], k3 = t.k[3], k4 = t.k[4];
-  const float d0 = t5.k[0], d1 = t5.k[1], d2 = t5.k[2];   // t5.k[2] = centre tap (reference order)
   const QuadCol qc = make_quadcol(q, g.width);
-  auto ldraw = [&](int y) -> float4 {
-    return load_quad_t<MODE>(img + (size_t)clampi(y, 0, g.height - 1) * g.pitch, q, g.width, true, qc);
+  auto ldraw = [&](int y, const QuadCol &c) -> float4 {
+    return load_quad_t<MODE>(img + (size_t)clampi(y, 0, g.height - 1) * g.pitch, q, g.width, true, c);
   };
-  auto hfilt = [&](const float4 c) -> float4 {
-    const float4 l = quad_from_left(c);
-    const float4 r = quad_from_right(c);
-    float4 h;
-    h.x = conv9_expr(k0, k1, k2, k3, k4, c.x, c.y + l.w, c.z + l.z, c.w + l.y, r.x + l.x);
-    h.y = conv9_expr(k0, k1, k2, k3, k4, c.y, c.z + c.x, c.w + l.w, r.x + l.z, r.y + l.y);
-    h.z = conv9_expr(k0, k1, k2, k3, k4, c.z, c.w + c.y, r.x + c.x, r.y + l.w, r.z + l.z);
-    h.w = conv9_expr(k0, k1, k2, k3, k4, c.w, r.x + c.z, r.y + c.y, r.z + c.x, r.w + l.w);
-    return h;
-  };
-  auto hrow = [&](int y) -> float4 { return hfilt(ldraw(y)); };
+  auto hrow = [&](int y) -> Quad2 { return hfilt9(t, q2(ldraw(y, qc))); };
   const bool first_quad = q == 0, last_quad = 4 * q + 4 >= g.width;
   // horizontal 5-tap decimation of a prefiltered row (scaledown_kernel's hfilt, clamp-to-edge in image space)
-  auto hdec = [&](const float4 o) -> float2 {
-    float lz = lane_from_left(o.z), lw = lane_from_left(o.w), rx = lane_from_right(o.x);
-    if (first_quad) { lz = o.x; lw = o.x; }
-    if (last_quad) rx = o.w;
-    float2 h;
-    float s;
-    s = __builtin_fmaf(d0, lz + o.z, d1 * (lw + o.y));  h.x = __builtin_fmaf(d2, o.x, s);
-    s = __builtin_fmaf(d0, o.x + rx, d1 * (o.y + o.w)); h.y = __builtin_fmaf(d2, o.z, s);
-    return h;
-  };
-  auto vcomb = [&](float a0, float a1, float a2, float a3, float a4) -> float {
-    float s = __builtin_fmaf(d2, a2, d0 * (a0 + a4));
-    s = __builtin_fmaf(d1, a1 + a3, s);
-    return s;
+  auto hdec = [&](const Quad2 &o) -> v2f {
+    float lz = lane_from_left(o.hi.x), lw = lane_from_left(o.hi.y), rx = lane_from_right(o.lo.x);
+    if (first_quad) { lz = o.lo.x; lw = o.lo.x; }
+    if (last_quad) rx = o.hi.y;
+    return dec5_pair(t5, lz, lw, o.lo.x, o.lo.y, o.hi.x, o.lo.x, o.lo.y, o.hi.x, o.hi.y, rx);
   };
   const bool writer = lane >= 2 && lane <= FUSED_OUT_LANES + 1 && 4 * q < g.width;
-  auto emit = [&](int Y, float2 a0, float2 a1, float2 a2, float2 a3, float2 a4) {
-    if (writer && Y < h2) {
-      float2 o;
-      o.x = vcomb(a0.x, a1.x, a2.x, a3.x, a4.x);
-      o.y = vcomb(a0.y, a1.y, a2.y, a3.y, a4.y);
+  // decimated row Y from the ring rows 2Y-2 .. 2Y+2 (every caller's Y lies below height / 2)
+  auto emit = [&](int Y, v2f a0, v2f a1, v2f a2, v2f a3, v2f a4) {
+    if (writer) {
+      const v2f o = vdec5(t5, a0, a1, a2, a3, a4);
       float *d2 = out2 + (size_t)Y * dpitch2 + 2 * q;
       if (MODE == 2) {               // ragged width: the lane of the last quad may own only one (or no) decimated column,
         const int w2o = g.width >> 1;     // and the next one may already be the neighbouring row (pitch == width/2)
-        if (2 * q + 1 < w2o) *reinterpret_cast<float2 *>(d2) = o;
+        if (2 * q + 1 < w2o) *reinterpret_cast<v2f *>(d2) = o;
         else if (2 * q < w2o) d2[0] = o.x;
       } else {
 #if LPD_NT >= 2
-        typedef float lpd_v2f __attribute__((ext_vector_type(2)));
-        lpd_v2f o2; o2.x = o.x; o2.y = o.y;
-        __builtin_nontemporal_store(o2, reinterpret_cast<lpd_v2f *>(d2));
+        __builtin_nontemporal_store(o, reinterpret_cast<v2f *>(d2));
 #else
-        *reinterpret_cast<float2 *>(d2) = o;
+        *reinterpret_cast<v2f *>(d2) = o;
 #endif
       }
     }
@@ -236,61 +261,73 @@ __device__ __forceinline__ void lowpass_down_item(const SRC *__restrict__ src, c
   // The 9-row window of horizontally filtered rows and the three raw rows in flight rotate by NAME: the row loop is
   // unrolled nine times (window slot of row y+k = (j+k) % 9, compile-time), so no register is ever moved.  r02's loop
   // rotated them with 48 v_mov per row — 37 % of its 130 VALU instructions (r03: ISA count of the loop body).
-  float4 w[9], rw[3];
+  Quad2 w[9];
+  float4 rw[3];
 #pragma unroll
-  for (int k = 0; k < 8; k++) w[k] = hrow(rs - 4 + k);
-  rw[0] = ldraw(rs + 4);
-  rw[1] = ldraw(rs + 5);
-  float2 a0 = make_float2(0.f, 0.f), a1 = a0, a2 = a0, a3 = a0, a4 = a0;
-  // one row: window rows y-4 .. y+3 in W0..W7, W8 receives row y+4 (= hfilt of RCUR); RNEXT receives the raw row y+6
-  auto row = [&](const int y, const float4 &W0, const float4 &W1, const float4 &W2, const float4 &W3, const float4 &W4,
-                 const float4 &W5, const float4 &W6, const float4 &W7, float4 &W8, const float4 &RCUR,
-                 float4 &RNEXT) __attribute__((always_inline)) {
-    RNEXT = ldraw(y + 6);
-    W8 = hfilt(RCUR);
-    float4 o;
-    o.x = conv9_expr(k0, k1, k2, k3, k4, W4.x, W3.x + W5.x, W2.x + W6.x, W1.x + W7.x, W0.x + W8.x);
-    o.y = conv9_expr(k0, k1, k2, k3, k4, W4.y, W3.y + W5.y, W2.y + W6.y, W1.y + W7.y, W0.y + W8.y);
-    o.z = conv9_expr(k0, k1, k2, k3, k4, W4.z, W3.z + W5.z, W2.z + W6.z, W1.z + W7.z, W0.z + W8.z);
-    o.w = conv9_expr(k0, k1, k2, k3, k4, W4.w, W3.w + W5.w, W2.w + W6.w, W1.w + W7.w, W0.w + W8.w);
+  for (int k = 0; k < 8; k++) { w[k] = hrow(rs - 4 + k); pin_here(w[k]); }
+  rw[0] = ldraw(rs + 4, qc);
+  rw[1] = ldraw(rs + 5, qc);
+  v2f a0 = mk2(0.f, 0.f), a1 = a0, a2 = a0, a3 = a0, a4 = a0;
+  // one row: window rows y-4 .. y+3 in W0..W7, W8 receives row y+4 (= hfilt9 of RCUR); RNEXT receives the raw row y+6.
+  // ROW0 (a literal at every call): y may be row 0 of the image, whose decimation ring takes four selects.  The turns of
+  // nine rows never see that row, so their body keeps hdec's three lane-varying selects a row and no other; the row
+  // tests that remain (stored? decimated row due?) are wave-uniform and cost scalar instructions only.
+  auto row = [&](const bool ROW0, const QuadCol &QC, const int y, const Quad2 &W0, const Quad2 &W1, const Quad2 &W2,
+                 const Quad2 &W3, const Quad2 &W4, const Quad2 &W5, const Quad2 &W6, const Quad2 &W7, Quad2 &W8,
+                 const float4 &RCUR, float4 &RNEXT) __attribute__((always_inline)) {
+    RNEXT = ldraw(y + 6, QC);
+    W8 = hfilt9(t, q2(RCUR));
+    const Quad2 o = vfilt9(t, W0, W1, W2, W3, W4, W5, W6, W7, W8);
+    const bool stored = writer && y >= y0 && y < y1;
     if (MODE == 2 && qc.edge == 2) {                       // the ragged last quad: its columns inside the image only
-      if (writer && y >= y0 && y < y1) store_quad(out + (size_t)y * dpitch, q, g.width, false, o);
-    } else
-#if LPD_NT
-    if (writer && y >= y0 && y < y1) {
+      if (stored) store_quad(out + (size_t)y * dpitch, q, g.width, false, f4(o));
+    } else if (stored) {
       typedef float lpd_v4f __attribute__((ext_vector_type(4)));
-      lpd_v4f o4; o4.x = o.x; o4.y = o.y; o4.z = o.z; o4.w = o.w;
-      __builtin_nontemporal_store(o4, reinterpret_cast<lpd_v4f *>(out + (size_t)y * dpitch + 4 * q));
-    }
+      lpd_v4f *p = reinterpret_cast<lpd_v4f *>(out + (size_t)y * dpitch + 4 * q);
+      const lpd_v4f o4 = __builtin_shufflevector(o.lo, o.hi, 0, 1, 2, 3);
+#if LPD_NT
+      __builtin_nontemporal_store(o4, p);
 #else
-    if (writer && y >= y0 && y < y1) *reinterpret_cast<float4 *>(out + (size_t)y * dpitch + 4 * q) = o;
+      *p = o4;
 #endif
-    float4 oc = o;                                         // the prefiltered row as ScaleDown's clamped reads see it:
-    if (MODE == 2 && qc.edge == 2) {                       // columns past width-1 take the value of column width-1
-      const float e = qc.rem == 1 ? o.x : (qc.rem == 2 ? o.y : o.z);
-      if (qc.rem < 2) oc.y = e;
-      if (qc.rem < 3) oc.z = e;
-      oc.w = e;
     }
-    const float2 hd = hdec(oc);
+    Quad2 oc = o;                                          // the prefiltered row as ScaleDown's clamped reads see it:
+    if (MODE == 2 && qc.edge == 2) {                       // columns past width-1 take the value of column width-1
+      const float e = qc.rem == 1 ? o.lo.x : (qc.rem == 2 ? o.lo.y : o.hi.x);
+      if (qc.rem < 2) oc.lo.y = e;
+      if (qc.rem < 3) oc.hi.x = e;
+      oc.hi.y = e;
+    }
+    const v2f hd = hdec(oc);
     a0 = a1; a1 = a2; a2 = a3; a3 = a4; a4 = hd;
-    if (y == 0) { a2 = hd; a3 = hd; }                     // rows -2, -1 clamp to row 0
+    if (ROW0 && y == 0) { a2 = hd; a3 = hd; }             // rows -2, -1 clamp to row 0
     if ((y & 1) == 0 && y >= y0 + 2) emit((y - 2) >> 1, a0, a1, a2, a3, a4);
   };
-  int y = rs;
-  for (; y + 8 <= re; y += 9) {
-#pragma unroll
-    for (int j = 0; j < 9; j++)
-      row(y + j, w[j % 9], w[(j + 1) % 9], w[(j + 2) % 9], w[(j + 3) % 9], w[(j + 4) % 9], w[(j + 5) % 9],
-          w[(j + 6) % 9], w[(j + 7) % 9], w[(j + 8) % 9], rw[j % 3], rw[(j + 2) % 3]);
-  }
-  for (; y <= re; y++) {                                   // fewer than nine rows left: rotate the registers
-    row(y, w[0], w[1], w[2], w[3], w[4], w[5], w[6], w[7], w[8], rw[0], rw[2]);
+  // the rows outside the turns, one at a time: rotate the registers
+  auto row_any = [&](const int y) __attribute__((always_inline)) {
+    row(true, qc, y, w[0], w[1], w[2], w[3], w[4], w[5], w[6], w[7], w[8], rw[0], rw[2]);
 #pragma unroll
     for (int k = 0; k < 8; k++) w[k] = w[k + 1];
     rw[0] = rw[1];
     rw[1] = rw[2];
-  }
+  };
+  int y = rs;
+  if (y == 0) row_any(y++);                                // row 0 of the image
+  // The turns of nine rows, in two copies: wave_has_edge is fixed for the item, and tested once here the
+  // clamp-to-edge selects of the raw rows (6 v_cndmask + 2 v_mov a row behind a scalar branch) exist only in the copy
+  // that the first and the last strip of a frame run.
+  auto turns = [&](const bool EDGE) __attribute__((always_inline)) {
+    QuadCol qe = qc;
+    qe.wave_has_edge = EDGE ? 1 : 0;
+    for (; y + 8 <= re; y += 9) {
+#pragma unroll
+      for (int j = 0; j < 9; j++)
+        row(false, qe, y + j, w[j % 9], w[(j + 1) % 9], w[(j + 2) % 9], w[(j + 3) % 9], w[(j + 4) % 9], w[(j + 5) % 9],
+            w[(j + 6) % 9], w[(j + 7) % 9], w[(j + 8) % 9], rw[j % 3], rw[(j + 2) % 3]);
+    }
+  };
+  if (qc.wave_has_edge) turns(true); else turns(false);
+  for (; y <= re; y++) row_any(y);                         // fewer than nine rows left
   // last segment of an even-height image: row `height` clamps to row height-1
   if (y1 == g.height && (g.height & 1) == 0) emit((g.height - 2) >> 1, a1, a2, a3, a4, a4);
 }
@@ -490,7 +527,6 @@ __global__ __launch_bounds__(256) void scaledown_kernel(const float *__restrict_
   float *out = dst + (long long)it.frame * dst_frame_stride;
   const int y0 = it.seg * g.seg_rows;                     // output rows
   const int y1 = min(y0 + g.seg_rows, h2);
-  const float k0 = t.k[0], k1 = t.k[1], k2 = t.k[2];      // t.k[2] = centre tap here (reference order)
   const bool sal = src_aligned != 0, dal = dst_aligned != 0;
 
   const QuadCol qa = make_quadcol(2 * q, g.width), qb = make_quadcol(2 * q + 1, g.width);
@@ -502,39 +538,29 @@ __global__ __launch_bounds__(256) void scaledown_kernel(const float *__restrict_
     r.B = load_quad_t<FAST>(row, 2 * q + 1, g.width, sal, qb);   // input px 8q+4 .. 8q+7
     return r;
   };
-  auto hfilt = [&](const Raw2 &rw) -> float4 {
+  auto hfilt = [&](const Raw2 &rw) -> Quad2 {                          // outputs centred on px 8q, 8q+2, 8q+4, 8q+6
     const float4 A = rw.A, B = rw.B;
     const float lz = lane_from_left(B.z), lw = lane_from_left(B.w);   // px 8q-2, 8q-1
     const float rx = lane_from_right(A.x);                             // px 8q+8
-    float4 h;
-    float s;
-    s = __builtin_fmaf(k0, lz + A.z, k1 * (lw + A.y));  h.x = __builtin_fmaf(k2, A.x, s);
-    s = __builtin_fmaf(k0, A.x + B.x, k1 * (A.y + A.w)); h.y = __builtin_fmaf(k2, A.z, s);
-    s = __builtin_fmaf(k0, A.z + B.z, k1 * (A.w + B.y)); h.z = __builtin_fmaf(k2, B.x, s);
-    s = __builtin_fmaf(k0, B.x + rx, k1 * (B.y + B.w)); h.w = __builtin_fmaf(k2, B.z, s);
+    Quad2 h;
+    h.lo = dec5_pair(t, lz, lw, A.x, A.y, A.z, A.x, A.y, A.z, A.w, B.x);
+    h.hi = dec5_pair(t, A.z, A.w, B.x, B.y, B.z, B.x, B.y, B.z, B.w, rx);
     return h;
   };
-  auto vcomb = [&](float a0, float a1, float a2, float a3, float a4) -> float {
-    float s = __builtin_fmaf(k2, a2, k0 * (a0 + a4));
-    s = __builtin_fmaf(k1, a1 + a3, s);
-    return s;
-  };
-
-  auto hrow = [&](int y) -> float4 { return hfilt(ldraw(y)); };
+  auto hrow = [&](int y) -> Quad2 { Quad2 h = hfilt(ldraw(y)); pin_here(h); return h; };
   const bool writer = lane >= 1 && lane <= OUT_LANES && 4 * q < w2;
   const bool fast_store = FAST && (w2 & 3) == 0 && dal;
-  float4 t0 = hrow(2 * y0 - 2), t1 = hrow(2 * y0 - 1), t2 = hrow(2 * y0), t3, t4;
+  Quad2 t0 = hrow(2 * y0 - 2), t1 = hrow(2 * y0 - 1), t2 = hrow(2 * y0), t3, t4;
   Raw2 ra = ldraw(2 * y0 + 1), rb = ldraw(2 * y0 + 2), rc = ldraw(2 * y0 + 3), rd = ldraw(2 * y0 + 4);
   for (int y = y0; y < y1; y++) {
     const Raw2 na = ldraw(2 * y + 5), nb = ldraw(2 * y + 6);    // prefetch two output rows (four input rows) ahead
     t3 = hfilt(ra);
     t4 = hfilt(rb);
     ra = rc; rb = rd; rc = na; rd = nb;
-    float4 o;
-    o.x = vcomb(t0.x, t1.x, t2.x, t3.x, t4.x);
-    o.y = vcomb(t0.y, t1.y, t2.y, t3.y, t4.y);
-    o.z = vcomb(t0.z, t1.z, t2.z, t3.z, t4.z);
-    o.w = vcomb(t0.w, t1.w, t2.w, t3.w, t4.w);
+    Quad2 o2;
+    o2.lo = vdec5(t, t0.lo, t1.lo, t2.lo, t3.lo, t4.lo);
+    o2.hi = vdec5(t, t0.hi, t1.hi, t2.hi, t3.hi, t4.hi);
+    const float4 o = f4(o2);
     if (writer) {
       if (fast_store) *reinterpret_cast<float4 *>(out + (size_t)y * dpitch + 4 * q) = o;
       else store_quad(out + (size_t)y * dpitch, q, w2, dal, o);
