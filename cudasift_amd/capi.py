@@ -25,6 +25,7 @@ assert POINT_DTYPE.itemsize == 576
 # misift_track_obs: one observation of an exported track (misift_export_tracks_batch)
 TRACK_OBS_DTYPE = np.dtype([("frame", "<i4"), ("record", "<i4"), ("xpos", "<f4"), ("ypos", "<f4")])
 CAM_UNSET, CAM_ROOT, CAM_RESECTED = -2, -1, -3                 # cam_pair values that are no pair index
+LOSS_NONE, LOSS_HUBER, LOSS_GEMAN_MCCLURE = 0, 1, 2            # MISIFT_LOSS_*: adjust_bundle_robust_batch
 assert TRACK_OBS_DTYPE.itemsize == 16
 
 
@@ -130,6 +131,10 @@ SIGNATURES = {
     "misift_test_refine_camera": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _vp]),
     "misift_adjust_bundle_batch": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i,
                                         _f, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "misift_adjust_bundle_robust_batch": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _i,
+                                               _i, _f, _f, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "misift_test_adjust_bundle_robust": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i,
+                                              _f, _f, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "misift_test_adjust_bundle": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _f, _f,
                                        _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "misift_filter_tracks_batch": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _f, _f, _i, _i, _vp, _vp,
@@ -1078,6 +1083,53 @@ class Context:
                                                _dptr(cam_status), _dptr(cam_rms), _dptr(point_obs), _dptr(history),
                                                _dptr(cost), _dptr(summary)), "misift_adjust_bundle_batch")
         return cam_out, points_out, cam_obs, cam_status, cam_rms, point_obs, history, cost, summary
+
+    def adjust_bundle_robust_batch(self, max_tracks, max_obs, track_offsets, obs, export_summary, points, point_status,
+                                   nimages, cam, cam_pair, intrinsics, hold=(), min_views=2, min_obs=6, num_loops=5,
+                                   cg_iters=10, max_error=np.inf, lambda0=1e-3, orthonormalise=True, loss=LOSS_HUBER,
+                                   loss_scale=2.0, cam_out=None, points_out=None, cam_obs=None, cam_status=None,
+                                   cam_rms=None, point_obs=None, history=None, cost=None, obs_weight=True, summary=None):
+        """misift_adjust_bundle_robust_batch: adjust_bundle_batch under a robust loss (LOSS_NONE, LOSS_HUBER,
+        LOSS_GEMAN_MCCLURE) of scale loss_scale px: an observation far off its point is weighed down afresh in every
+        step instead of pulling with its full square.  The arguments and the nine outputs are those of
+        adjust_bundle_batch, where cam_rms, points_out[4t+3], history and cost now speak of the loss, not of the squared
+        error; obs_weight (max_obs floats: the weight of each observation used under the final state, -1 for one not
+        used) is a device buffer, allocated here when True, left out when None or False; returns the ten (obs_weight
+        None when left out).  Enqueued on the context stream."""
+        if obs_weight is True:
+            obs_weight = self.zeros(4 * max(max_obs, 1))
+        elif obs_weight is False:
+            obs_weight = None
+        intrinsics = np.ascontiguousarray(intrinsics, np.float32).reshape(-1, 4)
+        assert len(intrinsics) == nimages
+        hold = np.ascontiguousarray(hold, np.int32).reshape(-1)
+        if cam_out is None:
+            cam_out = self.zeros(48 * max(nimages, 1))
+        if points_out is None:
+            points_out = self.zeros(16 * max(max_tracks, 1))
+        if cam_obs is None:
+            cam_obs = self.zeros(4 * max(nimages, 1))
+        if cam_status is None:
+            cam_status = self.zeros(4 * max(nimages, 1))
+        if cam_rms is None:
+            cam_rms = self.zeros(8 * max(nimages, 1))
+        if point_obs is None:
+            point_obs = self.zeros(4 * max(max_tracks, 1))
+        if history is None:
+            history = self.zeros(16 * max(int(num_loops), 1))
+        if cost is None:
+            cost = self.zeros(8)
+        if summary is None:
+            summary = self.zeros(4 * 8)
+        check(lib().misift_adjust_bundle_robust_batch(
+            self.h, max_tracks, max_obs, _dptr(track_offsets), _dptr(obs), _dptr(export_summary), _dptr(points),
+            _dptr(point_status), nimages, _dptr(cam), _dptr(cam_pair), intrinsics.ctypes.data, len(hold),
+            hold.ctypes.data if len(hold) else None, int(min_views), int(min_obs), int(num_loops), int(cg_iters),
+            float(max_error), float(lambda0), int(orthonormalise), int(loss), float(loss_scale), _dptr(cam_out),
+            _dptr(points_out), _dptr(cam_obs), _dptr(cam_status), _dptr(cam_rms), _dptr(point_obs), _dptr(history),
+            _dptr(cost), _dptr(obs_weight) if obs_weight is not None else None, _dptr(summary)),
+            "misift_adjust_bundle_robust_batch")
+        return cam_out, points_out, cam_obs, cam_status, cam_rms, point_obs, history, cost, obs_weight, summary
 
     def filter_tracks_batch(self, max_tracks, max_obs, track_offsets, obs, export_summary, points, point_status,
                             nimages, cam, cam_pair, intrinsics, max_error=np.inf, max_cos=np.inf, min_angle_deg=None,

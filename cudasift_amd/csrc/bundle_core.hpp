@@ -3,7 +3,10 @@
 // (kernels_bundle.hip) hand in the call's arguments and temp memory and run one work item per lane or per workgroup; the
 // host-only test hook (misift_test_adjust_bundle) hands in host arrays and runs the same functions in loops, phase after
 // phase in the order of the launches.  So what a CPU test pins is what the device runs.  The definition, step by step,
-// is in include/misift.h.
+// is in include/misift.h.  misift_adjust_bundle_robust_batch is the same call with a loss: bundle_loss gives rho, w and
+// sqrt(w) of a member's squared residual, step 1 scales the member's 20 values by sqrt(w) where it writes them, the cost
+// pass stores rho in place of the squared residual, and every phase downstream reads what those two wrote.  ROBUST is a
+// template argument of the two, so the plain call compiles to what it was.
 //
 // The rules of refine_core.hpp hold: fp32 with every operation rounded, only + - * / sqrtf and fabsf, no fmaf, and the
 // build's -ffp-contract=off.  A per-track sum is taken by one work item in ascending slot.  A per-image or cross-image
@@ -22,6 +25,7 @@ enum { BUNDLE_LAM = 0, BUNDLE_COST = 1, BUNDLE_RHO = 2, BUNDLE_COST0 = 3, BUNDLE
 constexpr int BUNDLE_LIN = 20;                 // per slot: Ju_c (6), Jv_c (6), Ju_p (3), Jv_p (3), ru, rv
 constexpr int BUNDLE_NORMAL = 33;              // per image: U (21, row-major upper triangle), gc (6), sum of W y (6)
 constexpr float BUNDLE_LAMBDA_FLOOR = 1e-7f;   // below it 1 + lambda is 1 in fp32
+enum { BUNDLE_LOSS_NONE = 0, BUNDLE_LOSS_HUBER = 1, BUNDLE_LOSS_GEMAN_MCCLURE = 2 };   // MISIFT_LOSS_*
 
 struct alignas(16) BundleObs {                 // misift_track_obs
   int frame, record;
@@ -31,6 +35,8 @@ struct alignas(16) BundleObs {                 // misift_track_obs
 struct BundleData {
   int max_tracks, max_obs, nimages, min_views, min_obs, num_loops, cg_iters, orthonormalise;
   float thresh2, lambda0;
+  int loss;                                    // BUNDLE_LOSS_*, the same for the whole call
+  float loss_scale, loss_scale2;               // c, and c*c rounded once on the host; not read with loss 0
   // the call's inputs
   const int *track_offsets;
   const BundleObs *obs;
@@ -59,6 +65,7 @@ struct BundleData {
   // outputs
   float *cam_out, *points_out, *cam_rms, *history, *cost;
   int *cam_obs, *cam_status, *point_obs, *summary;
+  float *obs_weight;                           // max_obs, or NULL
 };
 
 FUND_HD int bundle_T(const BundleData &D) { const int v = D.export_summary[2]; return v < 0 ? 0 : (v > D.max_tracks ? D.max_tracks : v); }
@@ -199,7 +206,33 @@ FUND_HD float bundle_wt6(const float *l, int q, const float *v)
           bundle_w(l, 4, q) * v[4]) + bundle_w(l, 5, q) * v[5];
 }
 
-// a member's squared residual under state buffer b (trial: the buffer the state is not in); one not in front raises BAD
+// the loss of a member: rho, w and sw = sqrt(w) of s = ru*ru + rv*rv
+struct BundleLoss {
+  float rho, w, sw;
+};
+FUND_HD BundleLoss bundle_loss(int loss, float c, float c2, float s)
+{
+  BundleLoss L;
+  L.rho = s;
+  L.w = L.sw = 1.0f;
+  if (loss == BUNDLE_LOSS_HUBER) {
+    if (!(s <= c2)) {                          // a NaN s comes here
+      const float n = sqrtf(s);
+      L.rho = (c + c) * n - c2;
+      L.w = c / n;
+      L.sw = sqrtf(L.w);
+    }
+  } else if (loss == BUNDLE_LOSS_GEMAN_MCCLURE) {
+    const float d = c2 + s, q = c2 / d;
+    L.rho = (s * c2) / d;
+    L.w = q * q;
+    L.sw = q;
+  }
+  return L;
+}
+
+// a member's squared residual, or its rho, under state buffer b (trial: the buffer the state is not in); one not in front raises BAD
+template <bool ROBUST>
 FUND_HD void bundle_eval_slot(const BundleData &D, int o, bool trial)
 {
   const int k = D.key[o];
@@ -213,8 +246,12 @@ FUND_HD void bundle_eval_slot(const BundleData &D, int o, bool trial)
   const BundleObs ob = D.obs[o];
   RefineView v;
   float e = 0.0f;
-  if (refine_view(c, D.intrinsics + 4 * (size_t)k, X, ob.xpos, ob.ypos, v)) e = v.ru * v.ru + v.rv * v.rv;
-  else bundle_raise(&D.ctl[BUNDLE_BAD]);
+  if (refine_view(c, D.intrinsics + 4 * (size_t)k, X, ob.xpos, ob.ypos, v)) {
+    e = v.ru * v.ru + v.rv * v.rv;
+    if (ROBUST) e = bundle_loss(D.loss, D.loss_scale, D.loss_scale2, e).rho;
+  } else {
+    bundle_raise(&D.ctl[BUNDLE_BAD]);
+  }
   D.eterm[(size_t)b * D.max_obs + o] = e;
 }
 
@@ -270,7 +307,9 @@ FUND_HD void bundle_scalar_init(const BundleData &D, Sum &S, bool lead)
 
 // ---- one LM step
 
-// step 1 and 2 for an active track: its members linearised under the state, V, gp, V' and V'^-1 gp
+// step 1 and 2 for an active track: its members linearised under the state (ROBUST: each of the 20 values times sw,
+// s taken from the unscaled ru, rv), V, gp, V' and V'^-1 gp
+template <bool ROBUST>
 FUND_HD void bundle_track_normal(const BundleData &D, int t)
 {
   if (!bundle_active(D, t)) return;
@@ -291,6 +330,11 @@ FUND_HD void bundle_track_normal(const BundleData &D, int t)
       bundle_raise(&D.ctl[BUNDLE_FAIL]);       // the state has every member in front: not reached
 #pragma unroll
       for (int j = 0; j < BUNDLE_LIN; j++) l[j] = 0.0f;
+    }
+    if (ROBUST) {
+      const float sw = bundle_loss(D.loss, D.loss_scale, D.loss_scale2, l[18] * l[18] + l[19] * l[19]).sw;
+#pragma unroll
+      for (int j = 0; j < BUNDLE_LIN; j++) l[j] = sw * l[j];
     }
     float *dst = D.lin + (size_t)BUNDLE_LIN * o;
 #pragma unroll
@@ -635,6 +679,27 @@ FUND_HD void bundle_track_out(const BundleData &D, int t)
   unsigned *out = reinterpret_cast<unsigned *>(D.points_out) + 4 * (size_t)t;
   out[0] = w[0]; out[1] = w[1]; out[2] = w[2]; out[3] = w[3];
   D.point_obs[t] = n;
+}
+
+// d_obs_weight for slot o < O: -1 for a slot that is no member, w of a member under the final state
+FUND_HD void bundle_weight_slot(const BundleData &D, int o)
+{
+  const int k = D.key[o];
+  float w = -1.0f;
+  if (k >= 0) {
+    const int b = D.ctl[BUNDLE_CUR];
+    float c[12];
+    bundle_load_cam(D.cams + 12 * ((size_t)b * D.nimages + k), c);
+    const float *P = D.pts + 3 * ((size_t)b * D.max_tracks + D.owner[o]);
+    const float X[3] = {P[0], P[1], P[2]};
+    const BundleObs ob = D.obs[o];
+    RefineView v;
+    if (refine_view(c, D.intrinsics + 4 * (size_t)k, X, ob.xpos, ob.ypos, v))
+      w = pose_one_nan(bundle_loss(D.loss, D.loss_scale, D.loss_scale2, v.ru * v.ru + v.rv * v.rv).w);
+    else
+      w = pose_one_nan(NAN);                   // the final state has every member in front: not reached
+  }
+  D.obs_weight[o] = w;
 }
 
 // ---- the host's side: the Sum as a loop, the phases in the order of the launches

@@ -684,16 +684,18 @@ int launch_resect_cameras_batch(misift_ctx *ctx, int max_tracks, int max_obs, co
                                 int num_loops, float thresh2, int min_inliers, int only_unset, int install, float *d_cam,
                                 int *d_cam_pair, float *d_res_cam, int *d_res_cand, int *d_res_inliers,
                                 int *d_res_status, int *d_summary);
-// misift_adjust_bundle_batch (kernels_bundle.hip): three memsets + 11 + num_loops * (8 + 3 * cg_iters) launches; temp
-// from misift_ensure_tmp, sized from max_tracks, max_obs and nimages only.  h_lists: as launch_refine_cameras_batch
+// misift_adjust_bundle_batch and misift_adjust_bundle_robust_batch (kernels_bundle.hip): three memsets + 11 + num_loops *
+// (8 + 3 * cg_iters) launches, one more with d_obs_weight; temp from misift_ensure_tmp, sized from max_tracks, max_obs
+// and nimages only.  h_lists: as launch_refine_cameras_batch.  loss 0 and a NULL d_obs_weight is the plain call
 size_t adjust_bundle_batch_tmp_bytes(int max_tracks, int max_obs, int nimages);
 int launch_adjust_bundle_batch(misift_ctx *ctx, int max_tracks, int max_obs, const int *d_track_offsets,
                                const void *d_obs, const int *d_export_summary, const float *d_points,
                                const int *d_point_status, int nimages, const float *d_cam, const int *d_cam_pair,
                                const void *h_lists, int min_views, int min_obs, int num_loops, int cg_iters,
-                               float thresh2, float lambda0, int orthonormalise, float *d_cam_out, float *d_points_out,
-                               int *d_cam_obs, int *d_cam_status, float *d_cam_rms, int *d_point_obs, float *d_history,
-                               float *d_cost, int *d_summary);
+                               float thresh2, float lambda0, int orthonormalise, int loss, float loss_scale,
+                               float loss_scale2, float *d_cam_out, float *d_points_out, int *d_cam_obs,
+                               int *d_cam_status, float *d_cam_rms, int *d_point_obs, float *d_history, float *d_cost,
+                               float *d_obs_weight, int *d_summary);
 // misift_filter_tracks_batch (kernels_filter.hip): a copy, three memsets + six launches; temp from misift_ensure_tmp,
 // sized from max_tracks, max_obs and nimages only.  h_intrinsics: nimages x 4
 size_t filter_tracks_batch_tmp_bytes(int max_tracks, int max_obs, int nimages);

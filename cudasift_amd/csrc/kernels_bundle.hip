@@ -27,6 +27,10 @@
 //   bundle_eval_kernel, bundle_cost_kernel                 under the trial state
 //   bundle_decide_kernel        the scalar workgroup: kept or not, lambda, the history
 //   then bundle_image_out_kernel and bundle_track_out_kernel write the outputs.
+// misift_adjust_bundle_robust_batch is the same sequence with a loss (bundle_loss): bundle_track_normal_kernel<true>
+// scales a member's 20 values by sqrt(w) where it writes them and bundle_eval_kernel<true> stores rho; the plain call
+// launches the <false> instances, which hold no trace of the loss.  With d_obs_weight one launch more at the end,
+//   bundle_weight_out_kernel    lane per slot: w of a member under the final state, -1 for any other slot
 // Jc, Jp and r are written once per LM step and read by both views: recomputing them in each CG pass instead gives the
 // same bits and measured 10 to 13 % slower.
 #include <stdint.h>
@@ -132,10 +136,11 @@ __global__ __launch_bounds__(BUNDLE_THREADS) void bundle_gather_kernel(BundleDat
   }
 }
 
+template <bool ROBUST>
 __global__ __launch_bounds__(BUNDLE_THREADS) void bundle_eval_kernel(BundleData D, int trial)
 {
   const int o = blockIdx.x * BUNDLE_THREADS + threadIdx.x;
-  if (o < bundle_O(D)) bundle_eval_slot(D, o, trial != 0);
+  if (o < bundle_O(D)) bundle_eval_slot<ROBUST>(D, o, trial != 0);
 }
 
 __global__ __launch_bounds__(BUNDLE_THREADS) void bundle_cost_kernel(BundleData D, int trial)
@@ -152,10 +157,11 @@ __global__ __launch_bounds__(BUNDLE_THREADS) void bundle_start_kernel(BundleData
   bundle_scalar_init(D, S, threadIdx.x == 0);
 }
 
+template <bool ROBUST>
 __global__ __launch_bounds__(BUNDLE_THREADS) void bundle_track_normal_kernel(BundleData D)
 {
   const int t = blockIdx.x * BUNDLE_THREADS + threadIdx.x;
-  if (t < bundle_T(D)) bundle_track_normal(D, t);
+  if (t < bundle_T(D)) bundle_track_normal<ROBUST>(D, t);
 }
 
 __global__ __launch_bounds__(BUNDLE_THREADS) void bundle_image_normal_kernel(BundleData D)
@@ -223,6 +229,12 @@ __global__ __launch_bounds__(BUNDLE_THREADS) void bundle_track_out_kernel(Bundle
   if (t < bundle_T(D)) bundle_track_out(D, t);
 }
 
+__global__ __launch_bounds__(BUNDLE_THREADS) void bundle_weight_out_kernel(BundleData D)
+{
+  const int o = blockIdx.x * BUNDLE_THREADS + threadIdx.x;
+  if (o < bundle_O(D)) bundle_weight_slot(D, o);
+}
+
 // the temp of the call laid out behind `base` (NULL: only the size is wanted); every array starts 16-byte aligned
 size_t bundle_layout(BundleData &D, char *base)
 {
@@ -263,15 +275,16 @@ size_t adjust_bundle_batch_tmp_bytes(int max_tracks, int max_obs, int nimages)
   return bundle_layout(D, nullptr);
 }
 
-// Enqueue misift_adjust_bundle_batch on the context stream (common.hpp).  h_lists: the pinned copies, nimages x 4
-// intrinsics and then nimages held flags.
+// Enqueue misift_adjust_bundle_robust_batch on the context stream (common.hpp); misift_adjust_bundle_batch is loss 0 and
+// no d_obs_weight.  h_lists: the pinned copies, nimages x 4 intrinsics and then nimages held flags.
 int launch_adjust_bundle_batch(misift_ctx *ctx, int max_tracks, int max_obs, const int *d_track_offsets,
                                const void *d_obs, const int *d_export_summary, const float *d_points,
                                const int *d_point_status, int nimages, const float *d_cam, const int *d_cam_pair,
                                const void *h_lists, int min_views, int min_obs, int num_loops, int cg_iters,
-                               float thresh2, float lambda0, int orthonormalise, float *d_cam_out, float *d_points_out,
-                               int *d_cam_obs, int *d_cam_status, float *d_cam_rms, int *d_point_obs, float *d_history,
-                               float *d_cost, int *d_summary)
+                               float thresh2, float lambda0, int orthonormalise, int loss, float loss_scale,
+                               float loss_scale2, float *d_cam_out, float *d_points_out, int *d_cam_obs,
+                               int *d_cam_status, float *d_cam_rms, int *d_point_obs, float *d_history, float *d_cost,
+                               float *d_obs_weight, int *d_summary)
 {
   const int rc = misift_ensure_tmp(ctx, adjust_bundle_batch_tmp_bytes(max_tracks, max_obs, nimages));
   if (rc) return rc;
@@ -279,6 +292,7 @@ int launch_adjust_bundle_batch(misift_ctx *ctx, int max_tracks, int max_obs, con
   D.max_tracks = max_tracks; D.max_obs = max_obs; D.nimages = nimages; D.min_views = min_views; D.min_obs = min_obs;
   D.num_loops = num_loops; D.cg_iters = cg_iters; D.orthonormalise = orthonormalise; D.thresh2 = thresh2;
   D.lambda0 = lambda0;
+  D.loss = loss; D.loss_scale = loss_scale; D.loss_scale2 = loss_scale2;
   D.track_offsets = d_track_offsets; D.obs = reinterpret_cast<const BundleObs *>(d_obs);
   D.export_summary = d_export_summary; D.points = d_points; D.point_status = d_point_status; D.cam = d_cam;
   D.cam_pair = d_cam_pair;
@@ -287,6 +301,7 @@ int launch_adjust_bundle_batch(misift_ctx *ctx, int max_tracks, int max_obs, con
   bundle_layout(D, reinterpret_cast<char *>(ctx->d_match_tmp));
   D.cam_out = d_cam_out; D.points_out = d_points_out; D.cam_rms = d_cam_rms; D.history = d_history; D.cost = d_cost;
   D.cam_obs = d_cam_obs; D.cam_status = d_cam_status; D.point_obs = d_point_obs; D.summary = d_summary;
+  D.obs_weight = d_obs_weight;
   CandArgs C;
   C.max_tracks = max_tracks; C.max_obs = max_obs; C.nimages = nimages; C.track_offsets = d_track_offsets;
   C.obs = reinterpret_cast<const CandObs *>(d_obs); C.export_summary = d_export_summary; C.points = d_points;
@@ -303,6 +318,16 @@ int launch_adjust_bundle_batch(misift_ctx *ctx, int max_tracks, int max_obs, con
     launches();
     return ls.finish();
   };
+  // the loss is the same for the whole call: the two kernels that read it are picked here
+  const bool robust = loss != BUNDLE_LOSS_NONE;
+  auto eval = [&](int trial) {
+    if (robust) hipLaunchKernelGGL(bundle_eval_kernel<true>, per_slot, th, 0, s, D, trial);
+    else hipLaunchKernelGGL(bundle_eval_kernel<false>, per_slot, th, 0, s, D, trial);
+  };
+  auto track_normal = [&] {
+    if (robust) hipLaunchKernelGGL(bundle_track_normal_kernel<true>, per_track, th, 0, s, D);
+    else hipLaunchKernelGGL(bundle_track_normal_kernel<false>, per_track, th, 0, s, D);
+  };
   int r = scope("bundle_setup", [&] {
     hipLaunchKernelGGL(cand_owner_kernel, cand_blocks(max_tracks), dim3(CAND_THREADS), 0, s, C);
     hipLaunchKernelGGL(cand_key_kernel, cand_blocks(max_obs), dim3(CAND_THREADS), 0, s, C);
@@ -310,12 +335,12 @@ int launch_adjust_bundle_batch(misift_ctx *ctx, int max_tracks, int max_obs, con
     hipLaunchKernelGGL(bundle_premember_kernel, per_slot, th, 0, s, D);
     hipLaunchKernelGGL(bundle_activate_kernel, per_track, th, 0, s, D);
     hipLaunchKernelGGL(bundle_gather_kernel, image_wg, th, 0, s, D);
-    hipLaunchKernelGGL(bundle_eval_kernel, per_slot, th, 0, s, D, 0);
+    eval(0);
     hipLaunchKernelGGL(bundle_cost_kernel, image_wg, th, 0, s, D, 0);
     hipLaunchKernelGGL(bundle_start_kernel, one, th, 0, s, D);
   });
   for (int loop = 0; loop < num_loops && !r; loop++) {
-    r = scope("bundle_track", [&] { hipLaunchKernelGGL(bundle_track_normal_kernel, per_track, th, 0, s, D); });
+    r = scope("bundle_track", [&] { track_normal(); });
     if (!r) r = scope("bundle_image", [&] { hipLaunchKernelGGL(bundle_image_normal_kernel, image_wg, th, 0, s, D); });
     if (!r) r = scope("bundle_scalar", [&] { hipLaunchKernelGGL(bundle_cg_start_kernel, one, th, 0, s, D); });
     for (int it = 0; it < cg_iters && !r; it++) {
@@ -326,7 +351,7 @@ int launch_adjust_bundle_batch(misift_ctx *ctx, int max_tracks, int max_obs, con
     if (!r) r = scope("bundle_track", [&] { hipLaunchKernelGGL(bundle_track_trial_kernel, per_track, th, 0, s, D); });
     if (!r) r = scope("bundle_trial", [&] {
       hipLaunchKernelGGL(bundle_image_trial_kernel, per_image, th, 0, s, D);
-      hipLaunchKernelGGL(bundle_eval_kernel, per_slot, th, 0, s, D, 1);
+      eval(1);
     });
     if (!r) r = scope("bundle_image", [&] { hipLaunchKernelGGL(bundle_cost_kernel, image_wg, th, 0, s, D, 1); });
     if (!r) r = scope("bundle_scalar", [&] { hipLaunchKernelGGL(bundle_decide_kernel, one, th, 0, s, D); });
@@ -335,32 +360,55 @@ int launch_adjust_bundle_batch(misift_ctx *ctx, int max_tracks, int max_obs, con
   return scope("bundle_out", [&] {
     hipLaunchKernelGGL(bundle_image_out_kernel, per_image, th, 0, s, D);
     hipLaunchKernelGGL(bundle_track_out_kernel, per_track, th, 0, s, D);
+    if (d_obs_weight) hipLaunchKernelGGL(bundle_weight_out_kernel, per_slot, th, 0, s, D);
   });
 }
 
+namespace {
+
+// the phases of the host hook that read the loss
+template <bool ROBUST>
+void bundle_host_eval(const BundleData &D, int O, bool trial)
+{
+  for (int o = 0; o < O; o++) bundle_eval_slot<ROBUST>(D, o, trial);
+}
+template <bool ROBUST>
+void bundle_host_track_normal(const BundleData &D, int T)
+{
+  for (int t = 0; t < T; t++) bundle_track_normal<ROBUST>(D, t);
+}
+
+}  // namespace
+
 // Test-only, host-only: the whole call on host arrays, phase after phase through bundle_core.hpp.
-extern "C" int misift_test_adjust_bundle(int max_tracks, int max_obs, const int *track_offsets, const misift_track_obs *obs,
-                                         const int *export_summary, const float *points, const int *point_status,
-                                         int nimages, const float *cam, const int *cam_pair, const float *intrinsics,
-                                         int nhold, const int *hold, int min_views, int min_obs, int num_loops,
-                                         int cg_iters, float max_error, float lambda0, int orthonormalise,
-                                         float *cam_out, float *points_out, int *cam_obs, int *cam_status,
-                                         float *cam_rms, int *point_obs, float *history, float *cost, int *summary)
+extern "C" int misift_test_adjust_bundle_robust(int max_tracks, int max_obs, const int *track_offsets,
+                                                const misift_track_obs *obs, const int *export_summary,
+                                                const float *points, const int *point_status, int nimages,
+                                                const float *cam, const int *cam_pair, const float *intrinsics,
+                                                int nhold, const int *hold, int min_views, int min_obs, int num_loops,
+                                                int cg_iters, float max_error, float lambda0, int orthonormalise,
+                                                int loss, float loss_scale, float *cam_out, float *points_out,
+                                                int *cam_obs, int *cam_status, float *cam_rms, int *point_obs,
+                                                float *history, float *cost, float *obs_weight, int *summary)
 {
   bool ok = max_tracks >= 1 && max_obs >= 1 && nimages >= 1 && track_offsets && obs && export_summary && points &&
             point_status && cam && cam_pair && intrinsics && nhold >= 0 && (nhold == 0 || hold) && min_views >= 2 &&
             min_obs >= 3 && num_loops >= 0 && cg_iters >= 0 && max_error > 0.0f && lambda0 > 0.0f &&
             fundamental_finite(lambda0) && (orthonormalise == 0 || orthonormalise == 1) && cam_out && points_out &&
-            cam_obs && cam_status && cam_rms && point_obs && (history || num_loops == 0) && cost && summary;
+            cam_obs && cam_status && cam_rms && point_obs && (history || num_loops == 0) && cost && summary &&
+            loss >= BUNDLE_LOSS_NONE && loss <= BUNDLE_LOSS_GEMAN_MCCLURE &&
+            (loss == BUNDLE_LOSS_NONE || (loss_scale > 0.0f && fundamental_finite(loss_scale)));
   for (int j = 0; ok && j < nhold; j++) ok = hold[j] >= 0 && hold[j] < nimages;
   if (!ok) {
-    misift_set_error("misift_test_adjust_bundle: invalid argument");
+    misift_set_error("misift_test_adjust_bundle_robust: invalid argument");
     return MISIFT_EINVAL;
   }
   BundleData D;
   D.max_tracks = max_tracks; D.max_obs = max_obs; D.nimages = nimages; D.min_views = min_views; D.min_obs = min_obs;
   D.num_loops = num_loops; D.cg_iters = cg_iters; D.orthonormalise = orthonormalise;
   D.thresh2 = max_error * max_error; D.lambda0 = lambda0;
+  const bool robust = loss != BUNDLE_LOSS_NONE;
+  D.loss = loss; D.loss_scale = robust ? loss_scale : 0.0f; D.loss_scale2 = D.loss_scale * D.loss_scale;
   D.track_offsets = track_offsets; D.obs = reinterpret_cast<const BundleObs *>(obs); D.export_summary = export_summary;
   D.points = points; D.point_status = point_status; D.cam = cam; D.cam_pair = cam_pair; D.intrinsics = intrinsics;
   std::vector<int> held(nimages, 0);
@@ -370,6 +418,7 @@ extern "C" int misift_test_adjust_bundle(int max_tracks, int max_obs, const int 
   bundle_layout(D, reinterpret_cast<char *>(((uintptr_t)tmp.data() + 15) & ~(uintptr_t)15));
   D.cam_out = cam_out; D.points_out = points_out; D.cam_rms = cam_rms; D.history = history; D.cost = cost;
   D.cam_obs = cam_obs; D.cam_status = cam_status; D.point_obs = point_obs; D.summary = summary;
+  D.obs_weight = obs_weight;
   const int T = bundle_T(D), O = bundle_O(D);
   // the owners and the candidates, as track_candidates.hpp
   for (int o = 0; o < max_obs; o++) D.owner[o] = -1;
@@ -405,11 +454,11 @@ extern "C" int misift_test_adjust_bundle(int max_tracks, int max_obs, const int 
     }
   }
   BundleHostSum S;
-  for (int o = 0; o < O; o++) bundle_eval_slot(D, o, false);
+  robust ? bundle_host_eval<true>(D, O, false) : bundle_host_eval<false>(D, O, false);
   for (int i = 0; i < nimages; i++) bundle_image_cost(D, S, i, false, true);
   bundle_scalar_init(D, S, true);
   for (int loop = 0; loop < num_loops; loop++) {
-    for (int t = 0; t < T; t++) bundle_track_normal(D, t);
+    robust ? bundle_host_track_normal<true>(D, T) : bundle_host_track_normal<false>(D, T);
     for (int i = 0; i < nimages; i++) bundle_image_normal(D, S, i, true);
     bundle_cg_start(D, S, 0, 1, true);
     for (int it = 0; it < cg_iters; it++) {
@@ -419,11 +468,28 @@ extern "C" int misift_test_adjust_bundle(int max_tracks, int max_obs, const int 
     }
     for (int t = 0; t < T; t++) bundle_track_trial(D, t);
     for (int i = 0; i < nimages; i++) bundle_image_trial(D, i);
-    for (int o = 0; o < O; o++) bundle_eval_slot(D, o, true);
+    robust ? bundle_host_eval<true>(D, O, true) : bundle_host_eval<false>(D, O, true);
     for (int i = 0; i < nimages; i++) bundle_image_cost(D, S, i, true, true);
     bundle_decide(D, S, 0, 1, true);
   }
   for (int i = 0; i < nimages; i++) bundle_image_out(D, i);
   for (int t = 0; t < T; t++) bundle_track_out(D, t);
+  if (obs_weight)
+    for (int o = 0; o < O; o++) bundle_weight_slot(D, o);
   return MISIFT_OK;
+}
+
+extern "C" int misift_test_adjust_bundle(int max_tracks, int max_obs, const int *track_offsets, const misift_track_obs *obs,
+                                         const int *export_summary, const float *points, const int *point_status,
+                                         int nimages, const float *cam, const int *cam_pair, const float *intrinsics,
+                                         int nhold, const int *hold, int min_views, int min_obs, int num_loops,
+                                         int cg_iters, float max_error, float lambda0, int orthonormalise,
+                                         float *cam_out, float *points_out, int *cam_obs, int *cam_status,
+                                         float *cam_rms, int *point_obs, float *history, float *cost, int *summary)
+{
+  return misift_test_adjust_bundle_robust(max_tracks, max_obs, track_offsets, obs, export_summary, points, point_status,
+                                          nimages, cam, cam_pair, intrinsics, nhold, hold, min_views, min_obs, num_loops,
+                                          cg_iters, max_error, lambda0, orthonormalise, MISIFT_LOSS_NONE, 0.0f, cam_out,
+                                          points_out, cam_obs, cam_status, cam_rms, point_obs, history, cost, nullptr,
+                                          summary);
 }

@@ -2690,16 +2690,17 @@ extern "C" int misift_resect_cameras_batch(misift_ctx *ctx, int max_tracks, int 
 }
 
 // Levenberg-Marquardt over all free cameras and all active track points at once, the points eliminated in every step:
-// what misift_refine_cameras_batch and misift_triangulate_tracks_batch do in turns, done jointly.  The intrinsics and a
-// flag per image (1 = held) go to the pinned slot.
-extern "C" int misift_adjust_bundle_batch(misift_ctx *ctx, int max_tracks, int max_obs, const int *d_track_offsets,
-                                          const misift_track_obs *d_obs, const int *d_export_summary,
-                                          const float *d_points, const int *d_point_status, int nimages,
-                                          const float *d_cam, const int *d_cam_pair, const float *intrinsics, int nhold,
-                                          const int *hold, int min_views, int min_obs, int num_loops, int cg_iters,
-                                          float max_error, float lambda0, int orthonormalise, float *d_cam_out,
-                                          float *d_points_out, int *d_cam_obs, int *d_cam_status, float *d_cam_rms,
-                                          int *d_point_obs, float *d_history, float *d_cost, int *d_summary)
+// what misift_refine_cameras_batch and misift_triangulate_tracks_batch do in turns, done jointly, under a loss (0: the
+// plain sum of squares).  The intrinsics and a flag per image (1 = held) go to the pinned slot.
+extern "C" int misift_adjust_bundle_robust_batch(misift_ctx *ctx, int max_tracks, int max_obs, const int *d_track_offsets,
+                                                 const misift_track_obs *d_obs, const int *d_export_summary,
+                                                 const float *d_points, const int *d_point_status, int nimages,
+                                                 const float *d_cam, const int *d_cam_pair, const float *intrinsics,
+                                                 int nhold, const int *hold, int min_views, int min_obs, int num_loops,
+                                                 int cg_iters, float max_error, float lambda0, int orthonormalise,
+                                                 int loss, float loss_scale, float *d_cam_out, float *d_points_out,
+                                                 int *d_cam_obs, int *d_cam_status, float *d_cam_rms, int *d_point_obs,
+                                                 float *d_history, float *d_cost, float *d_obs_weight, int *d_summary)
 {
   ARG_CHECK(ctx && max_tracks >= 1 && max_obs >= 1 && nimages >= 1);
   ARG_CHECK(d_track_offsets && d_obs && d_export_summary && d_points && d_point_status && d_cam && d_cam_pair);
@@ -2710,6 +2711,8 @@ extern "C" int misift_adjust_bundle_batch(misift_ctx *ctx, int max_tracks, int m
   ARG_CHECK(max_error > 0.0f);                                              // NaN fails too
   ARG_CHECK(lambda0 > 0.0f && lambda0 <= 3.402823466e+38f);
   ARG_CHECK(orthonormalise == 0 || orthonormalise == 1);
+  ARG_CHECK(loss == MISIFT_LOSS_NONE || loss == MISIFT_LOSS_HUBER || loss == MISIFT_LOSS_GEMAN_MCCLURE);
+  if (loss != MISIFT_LOSS_NONE) ARG_CHECK(loss_scale > 0.0f && loss_scale <= 3.402823466e+38f);   // not read with loss 0
   ARG_CHECK(nhold >= 0 && (nhold == 0 || hold));
   for (int j = 0; j < nhold; j++) ARG_CHECK(hold[j] >= 0 && hold[j] < nimages);
   for (int i = 0; i < nimages; i++) ARG_CHECK(intrinsics_usable(intrinsics + 4 * (size_t)i, 1));
@@ -2724,16 +2727,35 @@ extern "C" int misift_adjust_bundle_batch(misift_ctx *ctx, int max_tracks, int m
   std::vector<int> held(nimages, 0);
   for (int j = 0; j < nhold; j++) held[hold[j]] = 1;
   const float thresh2 = max_error * max_error;                              // rounded once, here
+  const float c = loss != MISIFT_LOSS_NONE ? loss_scale : 0.0f;
+  const float c2 = c * c;                                                   // and so is this
   RoctxRange range(__func__);
   return run_batch(ctx, {{intrinsics, sizeof(float) * 4 * (size_t)nimages}, {held.data(), sizeof(int) * (size_t)nimages}},
                    0, [&](int *h_lists, void *) {
                      return launch_adjust_bundle_batch(ctx, max_tracks, max_obs, d_track_offsets, d_obs,
                                                        d_export_summary, d_points, d_point_status, nimages, d_cam,
                                                        d_cam_pair, h_lists, min_views, min_obs, num_loops, cg_iters,
-                                                       thresh2, lambda0, orthonormalise, d_cam_out, d_points_out,
-                                                       d_cam_obs, d_cam_status, d_cam_rms, d_point_obs, d_history,
-                                                       d_cost, d_summary);
+                                                       thresh2, lambda0, orthonormalise, loss, c, c2, d_cam_out,
+                                                       d_points_out, d_cam_obs, d_cam_status, d_cam_rms, d_point_obs,
+                                                       d_history, d_cost, d_obs_weight, d_summary);
                    });
+}
+
+// The plain sum of squares: loss 0 and no weights.
+extern "C" int misift_adjust_bundle_batch(misift_ctx *ctx, int max_tracks, int max_obs, const int *d_track_offsets,
+                                          const misift_track_obs *d_obs, const int *d_export_summary,
+                                          const float *d_points, const int *d_point_status, int nimages,
+                                          const float *d_cam, const int *d_cam_pair, const float *intrinsics, int nhold,
+                                          const int *hold, int min_views, int min_obs, int num_loops, int cg_iters,
+                                          float max_error, float lambda0, int orthonormalise, float *d_cam_out,
+                                          float *d_points_out, int *d_cam_obs, int *d_cam_status, float *d_cam_rms,
+                                          int *d_point_obs, float *d_history, float *d_cost, int *d_summary)
+{
+  return misift_adjust_bundle_robust_batch(ctx, max_tracks, max_obs, d_track_offsets, d_obs, d_export_summary, d_points,
+                                           d_point_status, nimages, d_cam, d_cam_pair, intrinsics, nhold, hold, min_views,
+                                           min_obs, num_loops, cg_iters, max_error, lambda0, orthonormalise,
+                                           MISIFT_LOSS_NONE, 0.0f, d_cam_out, d_points_out, d_cam_obs, d_cam_status,
+                                           d_cam_rms, d_point_obs, d_history, d_cost, nullptr, d_summary);
 }
 
 // The observation lists gated against the current points and cameras and written out again in export's format: per

@@ -1437,8 +1437,9 @@ int misift_resect_cameras_batch(misift_ctx *ctx,
  *   - Departures from a textbook statement: the cost of a state is evaluated in a pass of its own (per slot, then per
  *     image), not with the linearisation, so that num_loops == 0 and the trial evaluation share one code path; the
  *     preconditioner is the damped U' of each camera, not the Schur diagonal block.
- *   - Not done here: no robust kernel re-weights a residual (max_error is a hard gate, decided once), the intrinsics are
- *     not refined, the member set is not revised between steps, and no Schur-diagonal preconditioner is formed.
+ *   - Not done here: no robust kernel re-weights a residual in this call (max_error is a hard gate, decided once:
+ *     misift_adjust_bundle_robust_batch is this call under a Huber or a Geman-McClure loss), the intrinsics are not
+ *     refined, the member set is not revised between steps, and no Schur-diagonal preconditioner is formed.
  *   - NULL ctx; max_tracks, max_obs or nimages < 1; NULL d_track_offsets, d_obs, d_export_summary, d_points,
  *     d_point_status, d_cam, d_cam_pair, intrinsics, d_cam_out, d_points_out, d_cam_obs, d_cam_status, d_cam_rms,
  *     d_point_obs, d_cost or d_summary, NULL d_history with num_loops > 0; d_obs not 16-byte aligned; min_views < 2;
@@ -1477,6 +1478,78 @@ int misift_adjust_bundle_batch(misift_ctx *ctx,
                                float *d_history,               /* num_loops x 4 words */
                                float *d_cost,                  /* 2: before, after */
                                int   *d_summary);              /* 8 ints */
+
+/* misift_adjust_bundle_batch under a robust loss (no reference counterpart): iteratively re-weighted least squares, the
+ * weight of a member taken afresh from its residual under the state of every step.  Where the plain call minimises the
+ * sum of ru*ru + rv*rv, this one minimises the sum of rho(ru*ru + rv*rv), so that an observation far off its point pulls
+ * with a bounded (Huber) or a vanishing (Geman-McClure) force instead of a growing one, and nothing has to be removed
+ * first.  In the chain it stands where adjust stands.
+ *   The arguments are those of misift_adjust_bundle_batch in the same order, with `loss` and `loss_scale` after
+ *   `orthonormalise` and `d_obs_weight` between `d_cost` and `d_summary`.  The definition is that of
+ *   misift_adjust_bundle_batch, every word of it, the arithmetic rules included (fp32, every operation rounded, only
+ *   + - * / sqrtf and fabsf, no contraction, a comparison with a NaN is false, left to right as written), with three
+ *   amendments.
+ *   The loss.  c = loss_scale, c2 = c*c rounded once on the host, s = ru*ru + rv*rv of a member.
+ *     loss 0 (MISIFT_LOSS_NONE): rho = s, w = 1; the rows are not touched and loss_scale is not read.
+ *     loss 1 (MISIFT_LOSS_HUBER): if s <= c2 then rho = s and w = sw = 1; otherwise (a NaN s too) n = sqrtf(s),
+ *       rho = (c + c) * n - c2, w = c / n, sw = sqrtf(w).
+ *     loss 2 (MISIFT_LOSS_GEMAN_MCCLURE): d = c2 + s, q = c2 / d, rho = (s * c2) / d, w = q * q, sw = q.
+ *   Step 1.  The 20 values Ju, Jv (camera), Pu, Pv, ru, rv of a member are computed as there; s is taken from the
+ *   unscaled ru, rv.  With loss != 0 each of the 20 values v then becomes sw * v, always, also when sw == 1.  Steps 2 to 5
+ *   are unchanged and read the scaled values: W, V, gp, U, gc carry w = sw*sw through the products they are made of.
+ *   There is no second-order (Triggs) correction.
+ *   The cost.  Wherever that definition sums ru*ru + rv*rv it sums rho(s) instead: c_i, c, c' and the per-track ct.  The
+ *   step is kept iff c' < c on that cost.  d_cam_rms[2i], [2i + 1] and d_points_out[4t+3] so become sqrtf of the mean
+ *   rho, which is the rms reprojection error only with loss 0 (or while every member is a Huber inlier); d_cost and
+ *   d_history[4k] are sums of rho.
+ *   d_obs_weight, when not NULL, for o < O: -1.0f for a slot that is not a member; for a member, w under the final state
+ *   (1.0f with loss 0), or 0x7fc00000 if the member is not in front there, which the definition rules out.  A w that is a
+ *   NaN is stored as 0x7fc00000.  Entries at or beyond O stay untouched.
+ *   - With loss 0 the nine shared outputs equal those of misift_adjust_bundle_batch byte for byte.  With loss 1 and
+ *     every member's s <= c2 at every state visited (the states and the trial states) the same holds, and every member's
+ *     weight is 1.0f.
+ *   - An s that overflows to +inf: Huber gives w = 0 and rho = +inf, Geman-McClure gives w = 0 and a NaN rho; either way
+ *     c is not finite and no step is kept.  Gate such observations out with max_error.
+ *   - On the outlier scene of tests/test_filter_cpu.py one call with Huber at 2 px or Geman-McClure at 4 px brings the
+ *     clean observations to the figures of tests/test_bundle_robust_cpu.py (MEASURED), where the plain call is held off
+ *     by the outliers and adjust -> filter -> adjust removes clean observations with them.
+ *   - Not done here: no robust loss in misift_refine_cameras_batch or misift_triangulate_tracks_batch, no Cauchy loss
+ *     (its cost needs logf, which the arithmetic rules exclude), no second-order correction, the intrinsics are not
+ *     refined, the member set is not revised between steps (max_error is still the hard gate, decided once).
+ *   - The argument errors of misift_adjust_bundle_batch; a loss other than 0, 1 or 2; with loss != 0 a loss_scale that
+ *     is not finite and > 0: MISIFT_EINVAL, before anything is enqueued.  A d_obs_weight overlapping another buffer is
+ *     the caller's error and is not checked.
+ *   - Stream, copies and ordering as misift_adjust_bundle_batch.  The same memsets and launches, and one launch more
+ *     with d_obs_weight (one lane per slot); the loss is uniform over the call, and loss 0 runs the kernels of the plain
+ *     call.  The same temp memory: 100 bytes per slot, 76 per track and 352 per image, each array rounded up to 16. */
+#define MISIFT_LOSS_NONE 0
+#define MISIFT_LOSS_HUBER 1
+#define MISIFT_LOSS_GEMAN_MCCLURE 2
+int misift_adjust_bundle_robust_batch(misift_ctx *ctx,
+                                      int max_tracks, int max_obs,
+                                      const int *d_track_offsets,     /* max_tracks + 1, from export */
+                                      const misift_track_obs *d_obs,  /* max_obs, from export, 16-byte aligned */
+                                      const int *d_export_summary,    /* 8 ints, from export: [2] = T, [3] = O */
+                                      const float *d_points,          /* max_tracks x 4, from triangulate */
+                                      const int *d_point_status,      /* max_tracks, from triangulate */
+                                      int nimages,
+                                      const float *d_cam,             /* nimages x 12 */
+                                      const int *d_cam_pair,          /* nimages */
+                                      const float *intrinsics,        /* host, nimages x 4: fx fy cx cy, copied */
+                                      int nhold, const int *hold,     /* host, images kept as they are, copied; may be NULL */
+                                      int min_views, int min_obs, int num_loops, int cg_iters,
+                                      float max_error, float lambda0, int orthonormalise,
+                                      int loss, float loss_scale /* px */,
+                                      float *d_cam_out,               /* nimages x 12; may be d_cam itself */
+                                      float *d_points_out,            /* max_tracks x 4; may be d_points itself */
+                                      int   *d_cam_obs,               /* nimages */
+                                      int   *d_cam_status,            /* nimages */
+                                      float *d_cam_rms,               /* nimages x 2: before, after */
+                                      int   *d_point_obs,             /* max_tracks */
+                                      float *d_history,               /* num_loops x 4 words */
+                                      float *d_cost,                  /* 2: before, after */
+                                      float *d_obs_weight,            /* max_obs; may be NULL */
+                                      int   *d_summary);              /* 8 ints */
 
 /* The observation lists of misift_export_tracks_batch gated against the current points and cameras and written out
  * again, compact and in export's own format (no reference counterpart): per observation the reprojection error, per
@@ -1529,7 +1602,8 @@ int misift_adjust_bundle_batch(misift_ctx *ctx,
  *   - With max_error = +inf, max_cos = +inf, unique_frames = 0 and min_views = 2 on export's and triangulate's own output
  *     it drops exactly the tracks triangulate did not give status 0, and the views triangulate did not use or that lie
  *     behind a camera.
- *   - Not done here: no robust re-weighting (the gate is hard); the records it removes are not merged into new tracks;
+ *   - Not done here: no robust re-weighting (the gate is hard: misift_adjust_bundle_robust_batch weighs the observations
+ *     down instead of removing them); the records it removes are not merged into new tracks;
  *     the points are not re-estimated (d_points_out[4t'+3] is the rms of the kept views under the OLD point), so call
  *     triangulate or adjust afterwards.
  *   - NULL ctx; max_tracks, max_obs or nimages < 1; a NULL pointer other than d_obs_map; d_obs or d_obs_out not 16-byte
@@ -1663,6 +1737,14 @@ int misift_test_adjust_bundle(int max_tracks, int max_obs, const int *track_offs
                               int min_views, int min_obs, int num_loops, int cg_iters, float max_error, float lambda0,
                               int orthonormalise, float *cam_out, float *points_out, int *cam_obs, int *cam_status,
                               float *cam_rms, int *point_obs, float *history, float *cost, int *summary);
+/* The same for misift_adjust_bundle_robust_batch; misift_test_adjust_bundle is this one with loss 0 and no obs_weight. */
+int misift_test_adjust_bundle_robust(int max_tracks, int max_obs, const int *track_offsets, const misift_track_obs *obs,
+                                     const int *export_summary, const float *points, const int *point_status,
+                                     int nimages, const float *cam, const int *cam_pair, const float *intrinsics,
+                                     int nhold, const int *hold, int min_views, int min_obs, int num_loops, int cg_iters,
+                                     float max_error, float lambda0, int orthonormalise, int loss, float loss_scale,
+                                     float *cam_out, float *points_out, int *cam_obs, int *cam_status, float *cam_rms,
+                                     int *point_obs, float *history, float *cost, float *obs_weight, int *summary);
 
 /* Test-only, host-only: the whole of misift_filter_tracks_batch on host arrays, every rule compiled from the function
  * its kernels run (filter_core.hpp).  The arguments are those of the call without the context; all pointers are host;

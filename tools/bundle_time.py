@@ -14,7 +14,13 @@ The five take turns within every repetition, so a drift of the machine meets all
 scalar workgroup, the trial state, setup and outputs), the mean over ten more calls at num_loops 5 and cg_iters 10 with
 events around every launch; shares are of their sum.  All nine outputs are compared with the numpy restatement
 (tests/bundle_cases.expected_bundle) at this size before anything is timed.  Prints one JSON line; --out FILE also writes
-it there."""
+it there.
+
+--losses times misift_adjust_bundle_robust_batch instead of (a) and (b): the plain call, loss 0 through the new call,
+Huber at --huber px and Geman-McClure at --geman-mcclure px without d_obs_weight, and Huber with it (one launch more),
+each at num_loops 1 and --num-loops, cg_iters --cg-iters.  The ten take turns within every repetition in one process.  The
+two losses are compared with their restatement (tests/bundle_robust_cases.expected_bundle), all ten outputs, and loss 0
+with the plain call's, before anything is timed; kernels_ms is then given for the plain call and for each loss."""
 import argparse
 import ctypes as C
 import json
@@ -29,6 +35,7 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 from cudasift_amd import capi  # noqa: E402
 import bench_common  # noqa: E402,F401  (puts tests/ on the path)
 import bundle_cases as BC  # noqa: E402
+import bundle_robust_cases as BR  # noqa: E402
 import pose_cases as PC  # noqa: E402
 import posegraph_cases as G  # noqa: E402
 import triangulate_cases as TC  # noqa: E402
@@ -50,6 +57,9 @@ def main():
     ap.add_argument("--lambda0", type=float, default=1e-3)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--reps", type=int, default=40)
+    ap.add_argument("--losses", action="store_true")
+    ap.add_argument("--huber", type=float, default=2.0)
+    ap.add_argument("--geman-mcclure", type=float, default=4.0)
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     L = capi.lib()
@@ -103,9 +113,16 @@ def main():
     outs = {k: ctx.upload(np.full(m, TC.POISON_WORD, np.uint32)) for k, m in sizes.items()}
     args = dict(min_views=2, min_obs=a.min_obs, max_error=np.inf, lambda0=a.lambda0, orthonormalise=1)
 
-    def adjust(num_loops, cg_iters):
-        ctx.adjust_bundle_batch(max_tracks, max_obs, doff, dobs, dsum, dpts, dstatus, nf, dcam, dcam_pair, K, hold=hold,
-                                num_loops=num_loops, cg_iters=cg_iters, **args, **outs)
+    dweight = ctx.upload(np.full(max_obs, TC.POISON_WORD, np.uint32))
+
+    def adjust(num_loops, cg_iters, loss=None, scale=0.0, weights=False):
+        if loss is None:
+            ctx.adjust_bundle_batch(max_tracks, max_obs, doff, dobs, dsum, dpts, dstatus, nf, dcam, dcam_pair, K,
+                                    hold=hold, num_loops=num_loops, cg_iters=cg_iters, **args, **outs)
+        else:
+            ctx.adjust_bundle_robust_batch(max_tracks, max_obs, doff, dobs, dsum, dpts, dstatus, nf, dcam, dcam_pair, K,
+                                           hold=hold, num_loops=num_loops, cg_iters=cg_iters, loss=loss, loss_scale=scale,
+                                           obs_weight=dweight if weights else None, **args, **outs)
 
     # the same answer as the restatement at this size, before anything is timed
     adjust(a.num_loops, a.cg_iters)
@@ -130,6 +147,76 @@ def main():
         capi.check(L.misift_timer_stop_ms(ctx.h, C.byref(ms)), "misift_timer_stop_ms")
         return ms.value
 
+    def percentiles(r, times):
+        for k, v in times.items():
+            r[k] = round(float(np.median(v)), 4)
+            r[k.replace("_ms", "_min_ms")] = round(float(np.min(v)), 4)
+            r[k.replace("_ms", "_p10_p90_ms")] = [round(float(x), 4) for x in np.percentile(v, [10, 90])]
+
+    def launches_of(fn):
+        ctx.profile_enable(True)                                 # the launches alone: events around each, a run of its own
+        ctx.profile_reset()                                      # behind the timed ones
+        for _ in range(10):
+            fn()
+        ctx.sync()
+        read = {k: v for k, v in ctx.profile_read().items() if k.startswith("bundle_")}
+        ctx.profile_enable(False)
+        return {k: round(v["total_ms"] / 10, 4) for k, v in read.items()}, {k: v["calls"] // 10 for k, v in read.items()}
+
+    r = {"case": "window %d over %d frames, %d matches per pair, 25 %% wrong, 0.5 px noise, tracks of %d and more" % (
+        a.window, nf, n, a.min_len), "pairs": npairs, "tracks": int(P.T), "observations": int(P.O), "images": nf,
+        "held": hold, "min_obs": a.min_obs, "lambda0": a.lambda0, "summary": e["summary"].view(np.int32).tolist(),
+        "reps": a.reps}
+    if a.losses:
+        variants = (("plain", None, 0.0, False), ("loss0", BR.NONE, 0.0, False), ("huber", BR.HUBER, a.huber, False),
+                    ("geman_mcclure", BR.GEMAN_MCCLURE, a.geman_mcclure, False),
+                    ("huber_weights", BR.HUBER, a.huber, True))
+        r["losses"] = {"huber_px": a.huber, "geman_mcclure_px": a.geman_mcclure, "cg_iters": a.cg_iters}
+        # the same answers as the restatements at this size, before anything is timed
+        plain = {k: ctx.download(outs[k], (sizes[k],), np.uint32).tobytes() for k in BC.OUTPUTS}
+        for name, loss, scale, _ in variants[1:4]:
+            adjust(a.num_loops, a.cg_iters, loss, scale, True)
+            ctx.sync()
+            got = {k: ctx.download(outs[k], (sizes[k],), np.uint32) for k in BC.OUTPUTS}
+            got["obs_weight"] = ctx.download(dweight, (max_obs,), np.uint32)
+            if loss == BR.NONE:
+                assert all(got[k].tobytes() == plain[k] for k in BC.OUTPUTS), name
+                continue
+            x = BR.expected_bundle(BR.robust(case, loss, scale))
+            BR.compare_all(got, x, name)
+            w = x["res"]["w"]
+            r["losses"][name] = {"steps": x["res"]["trace"], "cg_iterations": [h[3] for h in x["res"]["history"]],
+                                 "members_with_w_below_half": int((w < 0.5).sum()),
+                                 "rms_px_after": round(BR.pooled_rms(x["res"]), 4)}
+        names = ["adjust_%s_loops%d_cg%d_events_ms" % (v[0], loops, a.cg_iters) for loops in (1, a.num_loops)
+                 for v in variants]
+        times = {k: [] for k in names}
+        for rep in range(a.warmup + a.reps):                     # the ten take turns
+            t = [events(lambda: adjust(loops, a.cg_iters, v[1], v[2], v[3])) for loops in (1, a.num_loops)
+                 for v in variants]
+            if rep >= a.warmup:
+                for k, v in zip(names, t):
+                    times[k].append(v)
+        percentiles(r, times)
+        r["kernels_ms"], r["launches_per_call"] = {}, {}
+        for v in variants:
+            r["kernels_ms"][v[0]], r["launches_per_call"][v[0]] = launches_of(
+                lambda: adjust(a.num_loops, a.cg_iters, v[1], v[2], v[3]))
+        for loops in (1, a.num_loops):
+            key = "adjust_%%s_loops%d_cg%d_events_ms" % (loops, a.cg_iters)
+            r["ratios_loops%d" % loops] = {
+                "loss0_vs_plain": round(r[key % "loss0"] / r[key % "plain"], 4),
+                "huber_vs_loss0": round(r[key % "huber"] / r[key % "loss0"], 4),
+                "geman_mcclure_vs_loss0": round(r[key % "geman_mcclure"] / r[key % "loss0"], 4),
+                "huber_weights_vs_huber": round(r[key % "huber_weights"] / r[key % "huber"], 4)}
+        print(json.dumps(r), flush=True)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                json.dump(r, f, indent=1)
+        ctx.close()
+        return
+
     dround = ctx.upload(case["cam"])                             # the round works in place on a copy of the cameras
     tri_outs = dict(points=ctx.zeros(16 * max_tracks), point_views=ctx.zeros(4 * max_tracks),
                     point_status=ctx.zeros(4 * max_tracks), obs_error=None, summary=ctx.zeros(32))
@@ -151,25 +238,12 @@ def main():
         if rep >= a.warmup:
             for k, v in zip(times, t):
                 times[k].append(v)
-    ctx.profile_enable(True)                                     # the launches alone: events around each, a run of its own
-    ctx.profile_reset()                                          # behind the timed ones
-    for _ in range(10):
-        adjust(5, 10)
-    ctx.sync()
-    kernels = {k: round(v["total_ms"] / 10, 4) for k, v in ctx.profile_read().items() if k.startswith("bundle_")}
-    launches = {k: v["calls"] // 10 for k, v in ctx.profile_read().items() if k.startswith("bundle_")}
-    ctx.profile_enable(False)
+    kernels, launches = launches_of(lambda: adjust(5, 10))
     total_k = sum(kernels.values())
     cost = e["cost"].view(np.float32)
-    r = {"case": "window %d over %d frames, %d matches per pair, 25 %% wrong, 0.5 px noise, tracks of %d and more" % (
-        a.window, nf, n, a.min_len), "pairs": npairs, "tracks": int(P.T), "observations": int(P.O), "images": nf,
-        "held": hold, "min_obs": a.min_obs, "lambda0": a.lambda0, "summary": e["summary"].view(np.int32).tolist(),
-        "reps": a.reps, "steps": e["res"]["trace"], "cg_iterations": [h[3] for h in e["res"]["history"]],
-        "rms_px_before_after": [round(float(np.sqrt(c / max(len(P.slot), 1))), 4) for c in cost]}
-    for k, v in times.items():
-        r[k] = round(float(np.median(v)), 4)
-        r[k.replace("_ms", "_min_ms")] = round(float(np.min(v)), 4)
-        r[k.replace("_ms", "_p10_p90_ms")] = [round(float(x), 4) for x in np.percentile(v, [10, 90])]
+    r.update({"steps": e["res"]["trace"], "cg_iterations": [h[3] for h in e["res"]["history"]],
+              "rms_px_before_after": [round(float(np.sqrt(c / max(len(P.slot), 1))), 4) for c in cost]})
+    percentiles(r, times)
     r["kernels_ms"] = kernels
     r["launches_per_call"] = launches
     r["kernel_shares"] = {k: round(v / total_k, 4) for k, v in kernels.items()} if total_k else {}
