@@ -13,7 +13,8 @@ HIPSRCS  := $(CSRC)/kernels_pyramid.hip $(CSRC)/kernels_dog.hip $(CSRC)/kernels_
             $(CSRC)/multigpu.hip $(CSRC)/kernels_guided.hip $(CSRC)/kernels_match_i8.hip $(CSRC)/kernels_tracks.hip \
             $(CSRC)/kernels_fundamental.hip $(CSRC)/kernels_pose.hip \
             $(CSRC)/kernels_posegraph.hip $(CSRC)/kernels_triangulate.hip $(CSRC)/kernels_refine.hip \
-            $(CSRC)/kernels_resect.hip $(CSRC)/kernels_bundle.hip $(CSRC)/kernels_filter.hip
+            $(CSRC)/kernels_resect.hip $(CSRC)/kernels_bundle.hip $(CSRC)/kernels_filter.hip \
+            $(CSRC)/kernels_track_candidates.hip
 HIPOBJS  := $(patsubst $(CSRC)/%.hip,$(BUILD)/%.o,$(HIPSRCS))
 
 all: cudasift_amd/libmisift.so cudasift_amd/libcudasift.so cudasift_amd/libcudasift_managed.so oracle dropin build/pmc_calib build/valu_rates build/scan_rates build/single_call

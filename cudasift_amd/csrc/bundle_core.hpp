@@ -27,25 +27,12 @@ constexpr int BUNDLE_NORMAL = 33;              // per image: U (21, row-major up
 constexpr float BUNDLE_LAMBDA_FLOOR = 1e-7f;   // below it 1 + lambda is 1 in fp32
 enum { BUNDLE_LOSS_NONE = 0, BUNDLE_LOSS_HUBER = 1, BUNDLE_LOSS_GEMAN_MCCLURE = 2 };   // MISIFT_LOSS_*
 
-struct alignas(16) BundleObs {                 // misift_track_obs
-  int frame, record;
-  float xpos, ypos;
-};
-
 struct BundleData {
-  int max_tracks, max_obs, nimages, min_views, min_obs, num_loops, cg_iters, orthonormalise;
+  TrackScene s;                                // the call's inputs
+  int min_views, min_obs, num_loops, cg_iters, orthonormalise;
   float thresh2, lambda0;
   int loss;                                    // BUNDLE_LOSS_*, the same for the whole call
   float loss_scale, loss_scale2;               // c, and c*c rounded once on the host; not read with loss 0
-  // the call's inputs
-  const int *track_offsets;
-  const BundleObs *obs;
-  const int *export_summary;
-  const float *points;                         // max_tracks x 4
-  const int *point_status;
-  const float *cam;                            // nimages x 12
-  const int *cam_pair;
-  const float *intrinsics;                     // nimages x 4
   const int *held;                             // nimages flags
   // temp
   int *owner, *key, *list;                     // max_obs each; key[o] = the image slot o is a member of, or -1
@@ -67,9 +54,6 @@ struct BundleData {
   int *cam_obs, *cam_status, *point_obs, *summary;
   float *obs_weight;                           // max_obs, or NULL
 };
-
-FUND_HD int bundle_T(const BundleData &D) { const int v = D.export_summary[2]; return v < 0 ? 0 : (v > D.max_tracks ? D.max_tracks : v); }
-FUND_HD int bundle_O(const BundleData &D) { const int v = D.export_summary[3]; return v < 0 ? 0 : (v > D.max_obs ? D.max_obs : v); }
 
 FUND_HD void bundle_raise(int *flag)
 {
@@ -93,7 +77,7 @@ FUND_HD float bundle_dot6(const float *a, const float *b)
   return ((((a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]) + a[3] * b[3]) + a[4] * b[4]) + a[5] * b[5];
 }
 
-FUND_HD float *bundle_vec(const BundleData &D, int which, int i) { return D.ivec + 6 * ((size_t)which * D.nimages + i); }
+FUND_HD float *bundle_vec(const BundleData &D, int which, int i) { return D.ivec + 6 * ((size_t)which * D.s.nimages + i); }
 enum { BUNDLE_X = 0, BUNDLE_R = 1, BUNDLE_Z = 2, BUNDLE_P = 3, BUNDLE_Y = 4 };
 
 FUND_HD void bundle_load_cam(const float *src, float (&c)[12])
@@ -108,14 +92,14 @@ FUND_HD void bundle_load_cam(const float *src, float (&c)[12])
 FUND_HD void bundle_image_init(const BundleData &D, int i)
 {
   float c[12];
-  bundle_load_cam(D.cam + 12 * (size_t)i, c);
-  const int pair = D.cam_pair[i];
+  bundle_load_cam(D.s.cam + 12 * (size_t)i, c);
+  const int pair = D.s.cam_pair[i];
   int state = BUNDLE_ADJUSTED;
   if (pair == POSEGRAPH_UNSET || !refine_finite12(c)) state = BUNDLE_NO_CAMERA;
   else if (pair == POSEGRAPH_ROOT || D.held[i] != 0) state = BUNDLE_HELD;
   else if (D.orthonormalise) {
     float o[12];
-    bundle_load_cam(D.cam + 12 * (size_t)i, o);
+    bundle_load_cam(D.s.cam + 12 * (size_t)i, o);
     if (refine_orthonormalise(o)) {
 #pragma unroll
       for (int j = 0; j < 12; j++) c[j] = o[j];
@@ -127,7 +111,7 @@ FUND_HD void bundle_image_init(const BundleData &D, int i)
 #pragma unroll
   for (int j = 0; j < 12; j++) {
     D.cams[12 * (size_t)i + j] = c[j];
-    D.cams[12 * ((size_t)D.nimages + i) + j] = c[j];
+    D.cams[12 * ((size_t)D.s.nimages + i) + j] = c[j];
   }
 }
 
@@ -140,10 +124,10 @@ FUND_HD void bundle_slot_premember(const BundleData &D, int o)
   if (in) {
     float c[12];
     bundle_load_cam(D.cams + 12 * (size_t)k, c);
-    const float *P = D.points + 4 * (size_t)D.owner[o];
+    const float *P = D.s.points + 4 * (size_t)D.owner[o];
     const float X[3] = {P[0], P[1], P[2]};
-    const BundleObs ob = D.obs[o];
-    in = refine_member(c, D.intrinsics + 4 * (size_t)k, X, ob.xpos, ob.ypos, D.thresh2);
+    const TrackObs ob = track_obs_load(D.s.obs + o);
+    in = refine_member(c, D.s.intrinsics + 4 * (size_t)k, X, ob.xpos, ob.ypos, D.thresh2);
   }
   if (!in) D.key[o] = -1;
 }
@@ -151,9 +135,9 @@ FUND_HD void bundle_slot_premember(const BundleData &D, int o)
 // track t < T: its pre-members counted; an inactive track's leave `key`, an active track's point enters both buffers
 FUND_HD void bundle_track_activate(const BundleData &D, int t)
 {
-  const int off = D.track_offsets[t], end = D.track_offsets[t + 1];
+  const int off = D.s.track_offsets[t], end = D.s.track_offsets[t + 1];
   int n = 0;
-  const bool valid = tri_range_ok(off, end, bundle_O(D));
+  const bool valid = tri_range_ok(off, end, scene_O(D.s));
   if (valid)
     for (int o = off; o < end; o++) n += (D.owner[o] == t && D.key[o] >= 0) ? 1 : 0;
   D.tcount[t] = n;
@@ -165,9 +149,9 @@ FUND_HD void bundle_track_activate(const BundleData &D, int t)
   }
 #pragma unroll
   for (int j = 0; j < 3; j++) {
-    const float v = D.points[4 * (size_t)t + j];
+    const float v = D.s.points[4 * (size_t)t + j];
     D.pts[3 * (size_t)t + j] = v;
-    D.pts[3 * ((size_t)D.max_tracks + t) + j] = v;
+    D.pts[3 * ((size_t)D.s.max_tracks + t) + j] = v;
   }
 }
 
@@ -240,19 +224,19 @@ FUND_HD void bundle_eval_slot(const BundleData &D, int o, bool trial)
   if (trial && D.ctl[BUNDLE_FAIL]) return;
   const int b = trial ? 1 - D.ctl[BUNDLE_CUR] : D.ctl[BUNDLE_CUR];
   float c[12];
-  bundle_load_cam(D.cams + 12 * ((size_t)b * D.nimages + k), c);
-  const float *P = D.pts + 3 * ((size_t)b * D.max_tracks + D.owner[o]);
+  bundle_load_cam(D.cams + 12 * ((size_t)b * D.s.nimages + k), c);
+  const float *P = D.pts + 3 * ((size_t)b * D.s.max_tracks + D.owner[o]);
   const float X[3] = {P[0], P[1], P[2]};
-  const BundleObs ob = D.obs[o];
+  const TrackObs ob = track_obs_load(D.s.obs + o);
   RefineView v;
   float e = 0.0f;
-  if (refine_view(c, D.intrinsics + 4 * (size_t)k, X, ob.xpos, ob.ypos, v)) {
+  if (refine_view(c, D.s.intrinsics + 4 * (size_t)k, X, ob.xpos, ob.ypos, v)) {
     e = v.ru * v.ru + v.rv * v.rv;
     if (ROBUST) e = bundle_loss(D.loss, D.loss_scale, D.loss_scale2, e).rho;
   } else {
     bundle_raise(&D.ctl[BUNDLE_BAD]);
   }
-  D.eterm[(size_t)b * D.max_obs + o] = e;
+  D.eterm[(size_t)b * D.s.max_obs + o] = e;
 }
 
 // an image's cost under that buffer: the position rule over its list
@@ -266,12 +250,12 @@ FUND_HD void bundle_image_cost(const BundleData &D, Sum &S, int i, bool trial, b
 {
   if (trial && D.ctl[BUNDLE_FAIL]) return;
   const int b = trial ? 1 - D.ctl[BUNDLE_CUR] : D.ctl[BUNDLE_CUR];
-  BundleCostTerm term{D.eterm + (size_t)b * D.max_obs, D.list + D.istart[i]};
+  BundleCostTerm term{D.eterm + (size_t)b * D.s.max_obs, D.list + D.istart[i]};
   float c[1];
   S.template sum<1>(D.icount[i], term, c);
   if (!lead) return;
-  if (trial) D.icost[2 * (size_t)D.nimages + i] = c[0];
-  else D.icost[i] = D.icost[(size_t)D.nimages + i] = c[0];
+  if (trial) D.icost[2 * (size_t)D.s.nimages + i] = c[0];
+  else D.icost[i] = D.icost[(size_t)D.s.nimages + i] = c[0];
 }
 
 // a cross-image sum: the 256-slot rule over the image index
@@ -297,7 +281,7 @@ FUND_HD void bundle_scalar_init(const BundleData &D, Sum &S, bool lead)
 {
   BundleImageCostTerm term{D.icost};
   float c[1];
-  S.template sum<1>(D.nimages, term, c);
+  S.template sum<1>(D.s.nimages, term, c);
   if (!lead) return;
   for (int j = 0; j < BUNDLE_CTL; j++) D.ctl[j] = 0;
   D.fctl[BUNDLE_LAM] = D.lambda0;
@@ -315,18 +299,18 @@ FUND_HD void bundle_track_normal(const BundleData &D, int t)
   if (!bundle_active(D, t)) return;
   const int b = D.ctl[BUNDLE_CUR];
   const float lam1 = 1.0f + D.fctl[BUNDLE_LAM];
-  const float *P = D.pts + 3 * ((size_t)b * D.max_tracks + t);
+  const float *P = D.pts + 3 * ((size_t)b * D.s.max_tracks + t);
   const float X[3] = {P[0], P[1], P[2]};
   TriNormal N;
   tri_clear(N);
-  const int off = D.track_offsets[t], end = D.track_offsets[t + 1];
+  const int off = D.s.track_offsets[t], end = D.s.track_offsets[t + 1];
   for (int o = off; o < end; o++) {
     const int k = D.key[o];
     if (D.owner[o] != t || k < 0) continue;
     float c[12], l[BUNDLE_LIN];
-    bundle_load_cam(D.cams + 12 * ((size_t)b * D.nimages + k), c);
-    const BundleObs ob = D.obs[o];
-    if (!bundle_linearise(c, D.intrinsics + 4 * (size_t)k, X, ob.xpos, ob.ypos, l)) {
+    bundle_load_cam(D.cams + 12 * ((size_t)b * D.s.nimages + k), c);
+    const TrackObs ob = track_obs_load(D.s.obs + o);
+    if (!bundle_linearise(c, D.s.intrinsics + 4 * (size_t)k, X, ob.xpos, ob.ypos, l)) {
       bundle_raise(&D.ctl[BUNDLE_FAIL]);       // the state has every member in front: not reached
 #pragma unroll
       for (int j = 0; j < BUNDLE_LIN; j++) l[j] = 0.0f;
@@ -365,7 +349,7 @@ FUND_HD void bundle_track_solve(const BundleData &D, int t, const float (&rhs)[3
 FUND_HD void bundle_track_gather(const BundleData &D, int t, int which, float (&s)[3])
 {
   s[0] = s[1] = s[2] = 0.0f;
-  const int off = D.track_offsets[t], end = D.track_offsets[t + 1];
+  const int off = D.s.track_offsets[t], end = D.s.track_offsets[t + 1];
   for (int o = off; o < end; o++) {
     const int k = D.key[o];
     if (D.owner[o] != t || k < 0 || D.istate[k] != BUNDLE_ADJUSTED) continue;
@@ -441,7 +425,7 @@ template <class Sum>
 FUND_HD void bundle_cg_start(const BundleData &D, Sum &S, int lane, int lanes, bool lead)
 {
   const bool fail = D.ctl[BUNDLE_FAIL] != 0;
-  for (int i = lane; i < D.nimages; i += lanes) {
+  for (int i = lane; i < D.s.nimages; i += lanes) {
     if (D.istate[i] != BUNDLE_ADJUSTED) continue;
     float *x = bundle_vec(D, BUNDLE_X, i), *r = bundle_vec(D, BUNDLE_R, i), *z = bundle_vec(D, BUNDLE_Z, i),
           *p = bundle_vec(D, BUNDLE_P, i);
@@ -454,8 +438,8 @@ FUND_HD void bundle_cg_start(const BundleData &D, Sum &S, int lane, int lanes, b
   float rho[1] = {0.0f};
   if (!fail) {                                 // the same in every thread
     S.fence();
-    BundleDotTerm term{D.istate, D.ivec + 6 * (size_t)BUNDLE_R * D.nimages, D.ivec + 6 * (size_t)BUNDLE_Z * D.nimages};
-    S.template sum<1>(D.nimages, term, rho);
+    BundleDotTerm term{D.istate, D.ivec + 6 * (size_t)BUNDLE_R * D.s.nimages, D.ivec + 6 * (size_t)BUNDLE_Z * D.s.nimages};
+    S.template sum<1>(D.s.nimages, term, rho);
   }
   if (!lead) return;
   D.fctl[BUNDLE_RHO] = rho[0];
@@ -516,17 +500,17 @@ FUND_HD void bundle_cg_scalar(const BundleData &D, Sum &S, int lane, int lanes, 
 {
   if (!D.ctl[BUNDLE_ALIVE]) return;            // the same in every thread
   const float rho = D.fctl[BUNDLE_RHO];
-  const size_t n6 = 6 * (size_t)D.nimages;
+  const size_t n6 = 6 * (size_t)D.s.nimages;
   BundleDotTerm sterm{D.istate, D.ivec + BUNDLE_P * n6, D.ivec + BUNDLE_Y * n6};
   float sigma[1], rho2[1];
-  S.template sum<1>(D.nimages, sterm, sigma);
+  S.template sum<1>(D.s.nimages, sterm, sigma);
   if (!(fundamental_finite(sigma[0]) && sigma[0] > 0.0f)) {
     S.fence();                                 // every thread has read ALIVE
     if (lead) D.ctl[BUNDLE_ALIVE] = 0;
     return;
   }
   const float alpha = rho / sigma[0];
-  for (int i = lane; i < D.nimages; i += lanes) {
+  for (int i = lane; i < D.s.nimages; i += lanes) {
     if (D.istate[i] != BUNDLE_ADJUSTED) continue;
     float *x = bundle_vec(D, BUNDLE_X, i), *r = bundle_vec(D, BUNDLE_R, i), *z = bundle_vec(D, BUNDLE_Z, i);
     const float *p = bundle_vec(D, BUNDLE_P, i), *y = bundle_vec(D, BUNDLE_Y, i);
@@ -536,11 +520,11 @@ FUND_HD void bundle_cg_scalar(const BundleData &D, Sum &S, int lane, int lanes, 
   }
   S.fence();
   BundleDotTerm rterm{D.istate, D.ivec + BUNDLE_R * n6, D.ivec + BUNDLE_Z * n6};
-  S.template sum<1>(D.nimages, rterm, rho2);
+  S.template sum<1>(D.s.nimages, rterm, rho2);
   const bool on = fundamental_finite(rho2[0]);
   if (on) {
     const float beta = rho2[0] / rho;
-    for (int i = lane; i < D.nimages; i += lanes) {
+    for (int i = lane; i < D.s.nimages; i += lanes) {
       if (D.istate[i] != BUNDLE_ADJUSTED) continue;
       float *p = bundle_vec(D, BUNDLE_P, i);
       const float *z = bundle_vec(D, BUNDLE_Z, i);
@@ -564,8 +548,8 @@ FUND_HD void bundle_track_trial(const BundleData &D, int t)
   const float *v = D.tv + 9 * (size_t)t;
   const float rhs[3] = {v[6] - s[0], v[7] - s[1], v[8] - s[2]};
   bundle_track_solve(D, t, rhs, d);
-  const float *X = D.pts + 3 * ((size_t)b * D.max_tracks + t);
-  float *Y = D.pts + 3 * ((size_t)(1 - b) * D.max_tracks + t);
+  const float *X = D.pts + 3 * ((size_t)b * D.s.max_tracks + t);
+  float *Y = D.pts + 3 * ((size_t)(1 - b) * D.s.max_tracks + t);
   bool ok = true;
 #pragma unroll
   for (int j = 0; j < 3; j++) {
@@ -582,11 +566,11 @@ FUND_HD void bundle_image_trial(const BundleData &D, int i)
   if (D.ctl[BUNDLE_FAIL] || D.istate[i] != BUNDLE_ADJUSTED) return;
   const int b = D.ctl[BUNDLE_CUR];
   float c[12], out[12], x[6];
-  bundle_load_cam(D.cams + 12 * ((size_t)b * D.nimages + i), c);
+  bundle_load_cam(D.cams + 12 * ((size_t)b * D.s.nimages + i), c);
 #pragma unroll
   for (int j = 0; j < 6; j++) x[j] = bundle_vec(D, BUNDLE_X, i)[j];
   refine_update(c, x, out);
-  float *dst = D.cams + 12 * ((size_t)(1 - b) * D.nimages + i);
+  float *dst = D.cams + 12 * ((size_t)(1 - b) * D.s.nimages + i);
 #pragma unroll
   for (int j = 0; j < 12; j++) dst[j] = out[j];
   if (!refine_finite12(out)) bundle_raise(&D.ctl[BUNDLE_BAD]);
@@ -600,12 +584,12 @@ FUND_HD void bundle_decide(const BundleData &D, Sum &S, int lane, int lanes, boo
   const float c = D.fctl[BUNDLE_COST], lam = D.fctl[BUNDLE_LAM];
   float c2[1] = {0.0f};
   if (!broken) {
-    BundleImageCostTerm term{D.icost + 2 * (size_t)D.nimages};
-    S.template sum<1>(D.nimages, term, c2);
+    BundleImageCostTerm term{D.icost + 2 * (size_t)D.s.nimages};
+    S.template sum<1>(D.s.nimages, term, c2);
   }
   const bool kept = !broken && c2[0] < c;
   if (kept)
-    for (int i = lane; i < D.nimages; i += lanes) D.icost[(size_t)D.nimages + i] = D.icost[2 * (size_t)D.nimages + i];
+    for (int i = lane; i < D.s.nimages; i += lanes) D.icost[(size_t)D.s.nimages + i] = D.icost[2 * (size_t)D.s.nimages + i];
   S.fence();                                   // every thread has read the flags
   if (!lead) return;
   const int step = D.ctl[BUNDLE_STEP];
@@ -635,8 +619,8 @@ FUND_HD float bundle_rms(float cost, int n) { return n > 0 ? pose_one_nan(sqrtf(
 FUND_HD void bundle_image_out(const BundleData &D, int i)
 {
   const int state = D.istate[i], n = D.icount[i];
-  const unsigned *given = reinterpret_cast<const unsigned *>(D.cam) + 12 * (size_t)i;
-  const unsigned *mine = reinterpret_cast<const unsigned *>(D.cams) + 12 * ((size_t)D.ctl[BUNDLE_CUR] * D.nimages + i);
+  const unsigned *given = reinterpret_cast<const unsigned *>(D.s.cam) + 12 * (size_t)i;
+  const unsigned *mine = reinterpret_cast<const unsigned *>(D.cams) + 12 * ((size_t)D.ctl[BUNDLE_CUR] * D.s.nimages + i);
   const bool own = state == BUNDLE_ADJUSTED || state == BUNDLE_FEW_OBS;
   unsigned w[12];
 #pragma unroll
@@ -647,11 +631,11 @@ FUND_HD void bundle_image_out(const BundleData &D, int i)
   D.cam_obs[i] = n;
   D.cam_status[i] = state;
   D.cam_rms[2 * (size_t)i] = bundle_rms(D.icost[i], n);
-  D.cam_rms[2 * (size_t)i + 1] = bundle_rms(D.icost[(size_t)D.nimages + i], n);
+  D.cam_rms[2 * (size_t)i + 1] = bundle_rms(D.icost[(size_t)D.s.nimages + i], n);
   bundle_count(&D.summary[state == BUNDLE_ADJUSTED ? 1 : state == BUNDLE_FEW_OBS ? 3 : state == BUNDLE_HELD ? 5 : 7], 1);
   if (n) bundle_count(&D.summary[2], n);
   if (i == 0) {
-    D.summary[0] = bundle_T(D);
+    D.summary[0] = scene_T(D.s);
     D.summary[6] = D.ctl[BUNDLE_KEPT];
     D.cost[0] = pose_one_nan(D.fctl[BUNDLE_COST0]);
     D.cost[1] = pose_one_nan(D.fctl[BUNDLE_COST]);
@@ -661,14 +645,14 @@ FUND_HD void bundle_image_out(const BundleData &D, int i)
 FUND_HD void bundle_track_out(const BundleData &D, int t)
 {
   const int n = D.tcount[t];
-  const unsigned *given = reinterpret_cast<const unsigned *>(D.points) + 4 * (size_t)t;
+  const unsigned *given = reinterpret_cast<const unsigned *>(D.s.points) + 4 * (size_t)t;
   unsigned w[4] = {given[0], given[1], given[2], given[3]};
   if (bundle_active(D, t)) {
     const int b = D.ctl[BUNDLE_CUR];
-    const unsigned *mine = reinterpret_cast<const unsigned *>(D.pts) + 3 * ((size_t)b * D.max_tracks + t);
-    const float *e = D.eterm + (size_t)b * D.max_obs;
+    const unsigned *mine = reinterpret_cast<const unsigned *>(D.pts) + 3 * ((size_t)b * D.s.max_tracks + t);
+    const float *e = D.eterm + (size_t)b * D.s.max_obs;
     float c = 0.0f;
-    const int off = D.track_offsets[t], end = D.track_offsets[t + 1];
+    const int off = D.s.track_offsets[t], end = D.s.track_offsets[t + 1];
     for (int o = off; o < end; o++)
       if (D.owner[o] == t && D.key[o] >= 0) c = c + e[o];
     const float rms = bundle_rms(c, n);
@@ -689,12 +673,12 @@ FUND_HD void bundle_weight_slot(const BundleData &D, int o)
   if (k >= 0) {
     const int b = D.ctl[BUNDLE_CUR];
     float c[12];
-    bundle_load_cam(D.cams + 12 * ((size_t)b * D.nimages + k), c);
-    const float *P = D.pts + 3 * ((size_t)b * D.max_tracks + D.owner[o]);
+    bundle_load_cam(D.cams + 12 * ((size_t)b * D.s.nimages + k), c);
+    const float *P = D.pts + 3 * ((size_t)b * D.s.max_tracks + D.owner[o]);
     const float X[3] = {P[0], P[1], P[2]};
-    const BundleObs ob = D.obs[o];
+    const TrackObs ob = track_obs_load(D.s.obs + o);
     RefineView v;
-    if (refine_view(c, D.intrinsics + 4 * (size_t)k, X, ob.xpos, ob.ypos, v))
+    if (refine_view(c, D.s.intrinsics + 4 * (size_t)k, X, ob.xpos, ob.ypos, v))
       w = pose_one_nan(bundle_loss(D.loss, D.loss_scale, D.loss_scale2, v.ru * v.ru + v.rv * v.rv).w);
     else
       w = pose_one_nan(NAN);                   // the final state has every member in front: not reached

@@ -13,6 +13,10 @@
 #include <stdint.h>
 #include <stddef.h>
 #include "misift.h"
+#include "triangulate_core.hpp"   // TrackObs, TrackScene: what the track-chain launches below are given
+
+static_assert(sizeof(TrackObs) == sizeof(misift_track_obs) && alignof(TrackObs) == alignof(misift_track_obs),
+              "TrackObs mirrors misift_track_obs");
 
 #define NUM_SCALES 5
 #define NUM_BLURS  8          // NUM_SCALES + 3 (cudaSiftD.h:33 LAPLACE_S)
@@ -656,56 +660,45 @@ int launch_link_poses_batch(misift_ctx *ctx, int npairs, int nimages, int nlinks
                             float max_ambiguity, float max_error, const float *d_pose, const int *d_num_front,
                             const float *d_xyz, int seed_pair, int root_image, int min_common, float *d_link_ratio,
                             int *d_link_common, float *d_pair_scale, float *d_cam, int *d_cam_pair, int *d_summary);
-// misift_triangulate_tracks_batch (kernels_triangulate.hip): one memset + one launch; h_intrinsics: nimages x 4.  Temp
-// from misift_ensure_tmp only beyond the staging capacity, sized from nimages only (a device copy of the intrinsics)
+// The five track-chain calls take the scene they share as one TrackScene (triangulate_core.hpp), filled and checked by
+// check_scene (misift_host.hip); scene.intrinsics is the pinned copy, nimages x 4.
+// misift_triangulate_tracks_batch (kernels_triangulate.hip): one memset + one launch.  Temp from misift_ensure_tmp only
+// beyond the staging capacity, sized from nimages only (a device copy of the intrinsics)
 size_t triangulate_tracks_batch_tmp_bytes(int nimages);
-int launch_triangulate_tracks_batch(misift_ctx *ctx, int max_tracks, int max_obs, const int *d_track_offsets,
-                                    const void *d_obs, const int *d_export_summary, int nimages, const float *d_cam,
-                                    const int *d_cam_pair, const float *h_intrinsics, int min_views, int num_loops,
+int launch_triangulate_tracks_batch(misift_ctx *ctx, const TrackScene &scene, int min_views, int num_loops,
                                     float *d_points, int *d_point_views, int *d_point_status, float *d_obs_error,
                                     int *d_summary);
 // misift_refine_cameras_batch (kernels_refine.hip): two memsets + three launches; temp from misift_ensure_tmp, sized from
-// max_obs only (an owner and a key per slot).  h_lists: the intrinsics (nimages x 4 floats), then a held flag per image
+// max_obs only (an owner and a key per slot).  h_held: the pinned copy, a held flag per image
 size_t refine_cameras_batch_tmp_bytes(int max_obs);
-int launch_refine_cameras_batch(misift_ctx *ctx, int max_tracks, int max_obs, const int *d_track_offsets,
-                                const void *d_obs, const int *d_export_summary, const float *d_points,
-                                const int *d_point_status, int nimages, const float *d_cam, const int *d_cam_pair,
-                                const void *h_lists, int min_obs, int num_loops, float thresh2, int orthonormalise,
-                                float *d_cam_out, int *d_cam_obs, float *d_cam_rms, int *d_cam_steps, int *d_cam_status,
-                                int *d_summary);
+int launch_refine_cameras_batch(misift_ctx *ctx, const TrackScene &scene, const int *h_held, int min_obs, int num_loops,
+                                float thresh2, int orthonormalise, float *d_cam_out, int *d_cam_obs, float *d_cam_rms,
+                                int *d_cam_steps, int *d_cam_status, int *d_summary);
 // misift_resect_cameras_batch (kernels_resect.hip): two memsets + six launches; temp from misift_ensure_tmp, sized from
-// max_obs, nsel, max_cand and num_loops only.  h_lists: the intrinsics (nimages x 4 floats), the images (nsel ints), the
-// seeds (nsel)
+// max_obs, nsel, max_cand and num_loops only.  h_images, h_seeds: the pinned copies, nsel each.  scene.cam and
+// scene.cam_pair are d_cam and d_cam_pair, which may be NULL as the header states
 size_t resect_cameras_batch_tmp_bytes(int max_obs, int nsel, int max_cand, int num_loops);
 bool resect_cameras_batch_one_launch(int max_obs, int nsel, int max_cand, int num_loops);
-int launch_resect_cameras_batch(misift_ctx *ctx, int max_tracks, int max_obs, const int *d_track_offsets,
-                                const void *d_obs, const int *d_export_summary, const float *d_points,
-                                const int *d_point_status, int nimages, int nsel, const void *h_lists, int max_cand,
-                                int num_loops, float thresh2, int min_inliers, int only_unset, int install, float *d_cam,
-                                int *d_cam_pair, float *d_res_cam, int *d_res_cand, int *d_res_inliers,
-                                int *d_res_status, int *d_summary);
+int launch_resect_cameras_batch(misift_ctx *ctx, const TrackScene &scene, int nsel, const int *h_images,
+                                const unsigned *h_seeds, int max_cand, int num_loops, float thresh2, int min_inliers,
+                                int only_unset, int install, float *d_cam, int *d_cam_pair, float *d_res_cam,
+                                int *d_res_cand, int *d_res_inliers, int *d_res_status, int *d_summary);
 // misift_adjust_bundle_batch and misift_adjust_bundle_robust_batch (kernels_bundle.hip): three memsets + 11 + num_loops *
 // (8 + 3 * cg_iters) launches, one more with d_obs_weight; temp from misift_ensure_tmp, sized from max_tracks, max_obs
-// and nimages only.  h_lists: as launch_refine_cameras_batch.  loss 0 and a NULL d_obs_weight is the plain call
+// and nimages only.  h_held: as launch_refine_cameras_batch.  loss 0 and a NULL d_obs_weight is the plain call
 size_t adjust_bundle_batch_tmp_bytes(int max_tracks, int max_obs, int nimages);
-int launch_adjust_bundle_batch(misift_ctx *ctx, int max_tracks, int max_obs, const int *d_track_offsets,
-                               const void *d_obs, const int *d_export_summary, const float *d_points,
-                               const int *d_point_status, int nimages, const float *d_cam, const int *d_cam_pair,
-                               const void *h_lists, int min_views, int min_obs, int num_loops, int cg_iters,
-                               float thresh2, float lambda0, int orthonormalise, int loss, float loss_scale,
-                               float loss_scale2, float *d_cam_out, float *d_points_out, int *d_cam_obs,
+int launch_adjust_bundle_batch(misift_ctx *ctx, const TrackScene &scene, const int *h_held, int min_views, int min_obs,
+                               int num_loops, int cg_iters, float thresh2, float lambda0, int orthonormalise, int loss,
+                               float loss_scale, float loss_scale2, float *d_cam_out, float *d_points_out, int *d_cam_obs,
                                int *d_cam_status, float *d_cam_rms, int *d_point_obs, float *d_history, float *d_cost,
                                float *d_obs_weight, int *d_summary);
 // misift_filter_tracks_batch (kernels_filter.hip): a copy, three memsets + six launches; temp from misift_ensure_tmp,
-// sized from max_tracks, max_obs and nimages only.  h_intrinsics: nimages x 4
+// sized from max_tracks, max_obs and nimages only
 size_t filter_tracks_batch_tmp_bytes(int max_tracks, int max_obs, int nimages);
-int launch_filter_tracks_batch(misift_ctx *ctx, int max_tracks, int max_obs, const int *d_track_offsets,
-                               const void *d_obs, const int *d_export_summary, const float *d_points,
-                               const int *d_point_status, int nimages, const float *d_cam, const int *d_cam_pair,
-                               const float *h_intrinsics, float thresh2, float max_cos, int min_views, int unique_frames,
-                               int *d_track_offsets_out, void *d_obs_out, int *d_export_summary_out, float *d_points_out,
-                               int *d_point_views_out, int *d_point_status_out, int *d_track_map, int *d_obs_map,
-                               int *d_summary);
+int launch_filter_tracks_batch(misift_ctx *ctx, const TrackScene &scene, float thresh2, float max_cos, int min_views,
+                               int unique_frames, int *d_track_offsets_out, void *d_obs_out, int *d_export_summary_out,
+                               float *d_points_out, int *d_point_views_out, int *d_point_status_out, int *d_track_map,
+                               int *d_obs_map, int *d_summary);
 int launch_test_exp2(misift_ctx *ctx, const float *x, float *out, int n);
 int launch_test_points_fn(misift_ctx *ctx, int fn, const float *x, const float *y, float *out, float *out2, int n);
 int launch_selftest(misift_ctx *ctx);

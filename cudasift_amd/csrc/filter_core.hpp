@@ -38,9 +38,9 @@ FUND_HD void filter_ray(const float (&c)[12], const float (&X)[3], float (&u)[3]
 }
 
 // rule 1: 0 for a SURVIVOR (with e2 and its ray), otherwise the first reason that applies.  owner < 0: no owner.
-template <class Cams, class Obs>
+template <class Cams>
 FUND_HD int filter_classify(const Cams &C, int nimages, int owner, const int *point_status, const float *points,
-                            const Obs &ob, float E2, float &e2, float (&u)[3])
+                            const TrackObs &ob, float E2, float &e2, float (&u)[3])
 {
   e2 = 0.0f;
   u[0] = u[1] = u[2] = 0.0f;
@@ -70,29 +70,19 @@ FUND_HD bool filter_pair_wide(const float (&a)[3], const float (&b)[3], float ma
 // rule 4: the fourth word of a surviving point
 FUND_HD float filter_rms(float s, int m) { return sqrtf(s / (float)m); }
 
-struct FilterHostObs {
-  int frame, record;
-  float xpos, ypos;
-};
-
 // The whole call on host arrays, one slot and one track after the other.  obs_map may be NULL.
-inline void filter_tracks_host(int max_tracks, int max_obs, const int *track_offsets, const FilterHostObs *obs,
-                               const int *export_summary, const float *points, const int *point_status, int nimages,
-                               const float *cam, const int *cam_pair, const float *intrinsics, float E2, float max_cos,
-                               int min_views, int unique_frames, int *track_offsets_out, FilterHostObs *obs_out,
-                               int *export_summary_out, float *points_out, int *point_views_out, int *point_status_out,
-                               int *track_map, int *obs_map, int *summary)
+inline void filter_tracks_host(const TrackScene &S, float E2, float max_cos, int min_views, int unique_frames,
+                               int *track_offsets_out, TrackObs *obs_out, int *export_summary_out, float *points_out,
+                               int *point_views_out, int *point_status_out, int *track_map, int *obs_map, int *summary)
 {
-  const int T = std::min(std::max(export_summary[2], 0), max_tracks);
-  const int O = std::min(std::max(export_summary[3], 0), max_obs);
-  const TriCamsPlain C{cam, cam_pair, intrinsics};
+  const int T = scene_T(S), O = scene_O(S), nimages = S.nimages;
+  const int *track_offsets = S.track_offsets, *point_status = S.point_status;
+  const TrackObs *obs = S.obs;
+  const float *points = S.points;
+  const TriCamsPlain C{S.cam, S.cam_pair, S.intrinsics};
   std::vector<int> owner(O, -1), code(O, 0);
   std::vector<float> e2(O, 0.0f), ray(3 * (size_t)O, 0.0f);
-  for (int t = 0; t < T; t++) {
-    const int off = track_offsets[t], end = track_offsets[t + 1];
-    if (!tri_range_ok(off, end, O)) continue;
-    for (int o = off; o < end; o++) owner[o] = std::max(owner[o], t);
-  }
+  for (int t = 0; t < T; t++) scene_track_owns(S, owner.data(), t);
   int sum[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   for (int o = 0; o < O; o++) {
     float u[3];

@@ -7,7 +7,7 @@
 //
 // Three memsets (the owners, the control words, the summary) and 11 + num_loops * (8 + 3 * cg_iters) launches, whatever
 // the data.  A dispatch boundary is the only barrier between workgroups: nothing in here waits for another workgroup.
-//   cand_owner_kernel, cand_key_kernel     track_candidates.hpp: the owner of every slot, the image it is a candidate of
+//   cand_owner_kernel, cand_key_kernel     launch_track_candidates: the owner of every slot, the image it is a candidate of
 //   bundle_image_init_kernel    lane per image: usable / held / free, the camera of refine's step 1 into both buffers
 //   bundle_premember_kernel     lane per slot: refine's member test under that camera
 //   bundle_activate_kernel      lane per track: its pre-members counted; an inactive track's leave the keys
@@ -42,7 +42,6 @@
 
 namespace {
 
-static_assert(sizeof(BundleObs) == sizeof(misift_track_obs), "BundleObs mirrors misift_track_obs");
 constexpr int BUNDLE_THREADS = FUND_SLOTS;
 
 // the workgroup as the Sum of bundle_core.hpp: thread s is slot s, the tree runs through LDS
@@ -73,19 +72,19 @@ inline dim3 bundle_blocks(int n) { return dim3((unsigned)(((long long)n + BUNDLE
 __global__ __launch_bounds__(BUNDLE_THREADS) void bundle_image_init_kernel(BundleData D)
 {
   const int i = blockIdx.x * BUNDLE_THREADS + threadIdx.x;
-  if (i < D.nimages) bundle_image_init(D, i);
+  if (i < D.s.nimages) bundle_image_init(D, i);
 }
 
 __global__ __launch_bounds__(BUNDLE_THREADS) void bundle_premember_kernel(BundleData D)
 {
   const int o = blockIdx.x * BUNDLE_THREADS + threadIdx.x;
-  if (o < bundle_O(D)) bundle_slot_premember(D, o);
+  if (o < scene_O(D.s)) bundle_slot_premember(D, o);
 }
 
 __global__ __launch_bounds__(BUNDLE_THREADS) void bundle_activate_kernel(BundleData D)
 {
   const int t = blockIdx.x * BUNDLE_THREADS + threadIdx.x;
-  if (t < bundle_T(D)) bundle_track_activate(D, t);
+  if (t < scene_T(D.s)) bundle_track_activate(D, t);
 }
 
 __global__ __launch_bounds__(BUNDLE_THREADS) void bundle_gather_kernel(BundleData D)
@@ -93,7 +92,7 @@ __global__ __launch_bounds__(BUNDLE_THREADS) void bundle_gather_kernel(BundleDat
   __shared__ int wave_cnt[2][4];
   __shared__ int base_s[2];
   const int i = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int O = bundle_O(D);
+  const int O = scene_O(D.s);
   // first walk: the members of lower images come first in `list`, so count them, and this image's own
   int mine = 0, lower = 0;
   for (long long o = tid; o < O; o += BUNDLE_THREADS) {
@@ -140,7 +139,7 @@ template <bool ROBUST>
 __global__ __launch_bounds__(BUNDLE_THREADS) void bundle_eval_kernel(BundleData D, int trial)
 {
   const int o = blockIdx.x * BUNDLE_THREADS + threadIdx.x;
-  if (o < bundle_O(D)) bundle_eval_slot<ROBUST>(D, o, trial != 0);
+  if (o < scene_O(D.s)) bundle_eval_slot<ROBUST>(D, o, trial != 0);
 }
 
 __global__ __launch_bounds__(BUNDLE_THREADS) void bundle_cost_kernel(BundleData D, int trial)
@@ -161,7 +160,7 @@ template <bool ROBUST>
 __global__ __launch_bounds__(BUNDLE_THREADS) void bundle_track_normal_kernel(BundleData D)
 {
   const int t = blockIdx.x * BUNDLE_THREADS + threadIdx.x;
-  if (t < bundle_T(D)) bundle_track_normal<ROBUST>(D, t);
+  if (t < scene_T(D.s)) bundle_track_normal<ROBUST>(D, t);
 }
 
 __global__ __launch_bounds__(BUNDLE_THREADS) void bundle_image_normal_kernel(BundleData D)
@@ -181,7 +180,7 @@ __global__ __launch_bounds__(BUNDLE_THREADS) void bundle_cg_start_kernel(BundleD
 __global__ __launch_bounds__(BUNDLE_THREADS) void bundle_cg_track_kernel(BundleData D)
 {
   const int t = blockIdx.x * BUNDLE_THREADS + threadIdx.x;
-  if (t < bundle_T(D)) bundle_cg_track(D, t);
+  if (t < scene_T(D.s)) bundle_cg_track(D, t);
 }
 
 __global__ __launch_bounds__(BUNDLE_THREADS) void bundle_cg_image_kernel(BundleData D)
@@ -201,13 +200,13 @@ __global__ __launch_bounds__(BUNDLE_THREADS) void bundle_cg_scalar_kernel(Bundle
 __global__ __launch_bounds__(BUNDLE_THREADS) void bundle_track_trial_kernel(BundleData D)
 {
   const int t = blockIdx.x * BUNDLE_THREADS + threadIdx.x;
-  if (t < bundle_T(D)) bundle_track_trial(D, t);
+  if (t < scene_T(D.s)) bundle_track_trial(D, t);
 }
 
 __global__ __launch_bounds__(BUNDLE_THREADS) void bundle_image_trial_kernel(BundleData D)
 {
   const int i = blockIdx.x * BUNDLE_THREADS + threadIdx.x;
-  if (i < D.nimages) bundle_image_trial(D, i);
+  if (i < D.s.nimages) bundle_image_trial(D, i);
 }
 
 __global__ __launch_bounds__(BUNDLE_THREADS) void bundle_decide_kernel(BundleData D)
@@ -220,19 +219,19 @@ __global__ __launch_bounds__(BUNDLE_THREADS) void bundle_decide_kernel(BundleDat
 __global__ __launch_bounds__(BUNDLE_THREADS) void bundle_image_out_kernel(BundleData D)
 {
   const int i = blockIdx.x * BUNDLE_THREADS + threadIdx.x;
-  if (i < D.nimages) bundle_image_out(D, i);
+  if (i < D.s.nimages) bundle_image_out(D, i);
 }
 
 __global__ __launch_bounds__(BUNDLE_THREADS) void bundle_track_out_kernel(BundleData D)
 {
   const int t = blockIdx.x * BUNDLE_THREADS + threadIdx.x;
-  if (t < bundle_T(D)) bundle_track_out(D, t);
+  if (t < scene_T(D.s)) bundle_track_out(D, t);
 }
 
 __global__ __launch_bounds__(BUNDLE_THREADS) void bundle_weight_out_kernel(BundleData D)
 {
   const int o = blockIdx.x * BUNDLE_THREADS + threadIdx.x;
-  if (o < bundle_O(D)) bundle_weight_slot(D, o);
+  if (o < scene_O(D.s)) bundle_weight_slot(D, o);
 }
 
 // the temp of the call laid out behind `base` (NULL: only the size is wanted); every array starts 16-byte aligned
@@ -244,7 +243,7 @@ size_t bundle_layout(BundleData &D, char *base)
     at += (bytes + 15) & ~(size_t)15;
     return p;
   };
-  const size_t mo = (size_t)D.max_obs, mt = (size_t)D.max_tracks, n = (size_t)D.nimages;
+  const size_t mo = (size_t)D.s.max_obs, mt = (size_t)D.s.max_tracks, n = (size_t)D.s.nimages;
   D.owner = reinterpret_cast<int *>(take(4 * mo));
   D.key = reinterpret_cast<int *>(take(4 * mo));
   D.list = reinterpret_cast<int *>(take(4 * mo));
@@ -271,41 +270,31 @@ size_t bundle_layout(BundleData &D, char *base)
 size_t adjust_bundle_batch_tmp_bytes(int max_tracks, int max_obs, int nimages)
 {
   BundleData D;
-  D.max_tracks = max_tracks; D.max_obs = max_obs; D.nimages = nimages;
+  D.s.max_tracks = max_tracks; D.s.max_obs = max_obs; D.s.nimages = nimages;
   return bundle_layout(D, nullptr);
 }
 
 // Enqueue misift_adjust_bundle_robust_batch on the context stream (common.hpp); misift_adjust_bundle_batch is loss 0 and
-// no d_obs_weight.  h_lists: the pinned copies, nimages x 4 intrinsics and then nimages held flags.
-int launch_adjust_bundle_batch(misift_ctx *ctx, int max_tracks, int max_obs, const int *d_track_offsets,
-                               const void *d_obs, const int *d_export_summary, const float *d_points,
-                               const int *d_point_status, int nimages, const float *d_cam, const int *d_cam_pair,
-                               const void *h_lists, int min_views, int min_obs, int num_loops, int cg_iters,
-                               float thresh2, float lambda0, int orthonormalise, int loss, float loss_scale,
-                               float loss_scale2, float *d_cam_out, float *d_points_out, int *d_cam_obs,
+// no d_obs_weight.
+int launch_adjust_bundle_batch(misift_ctx *ctx, const TrackScene &scene, const int *h_held, int min_views, int min_obs,
+                               int num_loops, int cg_iters, float thresh2, float lambda0, int orthonormalise, int loss,
+                               float loss_scale, float loss_scale2, float *d_cam_out, float *d_points_out, int *d_cam_obs,
                                int *d_cam_status, float *d_cam_rms, int *d_point_obs, float *d_history, float *d_cost,
                                float *d_obs_weight, int *d_summary)
 {
+  const int max_tracks = scene.max_tracks, max_obs = scene.max_obs, nimages = scene.nimages;
   const int rc = misift_ensure_tmp(ctx, adjust_bundle_batch_tmp_bytes(max_tracks, max_obs, nimages));
   if (rc) return rc;
   BundleData D;
-  D.max_tracks = max_tracks; D.max_obs = max_obs; D.nimages = nimages; D.min_views = min_views; D.min_obs = min_obs;
+  D.s = scene; D.min_views = min_views; D.min_obs = min_obs;
   D.num_loops = num_loops; D.cg_iters = cg_iters; D.orthonormalise = orthonormalise; D.thresh2 = thresh2;
   D.lambda0 = lambda0;
   D.loss = loss; D.loss_scale = loss_scale; D.loss_scale2 = loss_scale2;
-  D.track_offsets = d_track_offsets; D.obs = reinterpret_cast<const BundleObs *>(d_obs);
-  D.export_summary = d_export_summary; D.points = d_points; D.point_status = d_point_status; D.cam = d_cam;
-  D.cam_pair = d_cam_pair;
-  D.intrinsics = reinterpret_cast<const float *>(h_lists);
-  D.held = reinterpret_cast<const int *>(D.intrinsics + 4 * (size_t)nimages);
+  D.held = h_held;
   bundle_layout(D, reinterpret_cast<char *>(ctx->d_match_tmp));
   D.cam_out = d_cam_out; D.points_out = d_points_out; D.cam_rms = d_cam_rms; D.history = d_history; D.cost = d_cost;
   D.cam_obs = d_cam_obs; D.cam_status = d_cam_status; D.point_obs = d_point_obs; D.summary = d_summary;
   D.obs_weight = d_obs_weight;
-  CandArgs C;
-  C.max_tracks = max_tracks; C.max_obs = max_obs; C.nimages = nimages; C.track_offsets = d_track_offsets;
-  C.obs = reinterpret_cast<const CandObs *>(d_obs); C.export_summary = d_export_summary; C.points = d_points;
-  C.point_status = d_point_status; C.owner = D.owner; C.key = D.key;
   HIP_TRY(hipMemsetAsync(D.owner, 0xff, sizeof(int) * (size_t)max_obs, ctx->stream));
   HIP_TRY(hipMemsetAsync(D.ctl, 0, sizeof(int) * BUNDLE_CTL, ctx->stream));
   HIP_TRY(hipMemsetAsync(d_summary, 0, 8 * sizeof(int), ctx->stream));
@@ -329,8 +318,7 @@ int launch_adjust_bundle_batch(misift_ctx *ctx, int max_tracks, int max_obs, con
     else hipLaunchKernelGGL(bundle_track_normal_kernel<false>, per_track, th, 0, s, D);
   };
   int r = scope("bundle_setup", [&] {
-    hipLaunchKernelGGL(cand_owner_kernel, cand_blocks(max_tracks), dim3(CAND_THREADS), 0, s, C);
-    hipLaunchKernelGGL(cand_key_kernel, cand_blocks(max_obs), dim3(CAND_THREADS), 0, s, C);
+    launch_track_candidates(ctx, scene, D.owner, D.key);
     hipLaunchKernelGGL(bundle_image_init_kernel, per_image, th, 0, s, D);
     hipLaunchKernelGGL(bundle_premember_kernel, per_slot, th, 0, s, D);
     hipLaunchKernelGGL(bundle_activate_kernel, per_track, th, 0, s, D);
@@ -404,13 +392,13 @@ extern "C" int misift_test_adjust_bundle_robust(int max_tracks, int max_obs, con
     return MISIFT_EINVAL;
   }
   BundleData D;
-  D.max_tracks = max_tracks; D.max_obs = max_obs; D.nimages = nimages; D.min_views = min_views; D.min_obs = min_obs;
-  D.num_loops = num_loops; D.cg_iters = cg_iters; D.orthonormalise = orthonormalise;
+  D.s = TrackScene{max_tracks, max_obs, nimages, track_offsets, reinterpret_cast<const TrackObs *>(obs), export_summary,
+                   points, point_status, cam, cam_pair, intrinsics};
+  D.min_views = min_views; D.min_obs = min_obs; D.num_loops = num_loops; D.cg_iters = cg_iters;
+  D.orthonormalise = orthonormalise;
   D.thresh2 = max_error * max_error; D.lambda0 = lambda0;
   const bool robust = loss != BUNDLE_LOSS_NONE;
   D.loss = loss; D.loss_scale = robust ? loss_scale : 0.0f; D.loss_scale2 = D.loss_scale * D.loss_scale;
-  D.track_offsets = track_offsets; D.obs = reinterpret_cast<const BundleObs *>(obs); D.export_summary = export_summary;
-  D.points = points; D.point_status = point_status; D.cam = cam; D.cam_pair = cam_pair; D.intrinsics = intrinsics;
   std::vector<int> held(nimages, 0);
   for (int j = 0; j < nhold; j++) held[hold[j]] = 1;
   D.held = held.data();
@@ -419,26 +407,11 @@ extern "C" int misift_test_adjust_bundle_robust(int max_tracks, int max_obs, con
   D.cam_out = cam_out; D.points_out = points_out; D.cam_rms = cam_rms; D.history = history; D.cost = cost;
   D.cam_obs = cam_obs; D.cam_status = cam_status; D.point_obs = point_obs; D.summary = summary;
   D.obs_weight = obs_weight;
-  const int T = bundle_T(D), O = bundle_O(D);
-  // the owners and the candidates, as track_candidates.hpp
+  const int T = scene_T(D.s), O = scene_O(D.s);
+  // the owners and the candidates, as launch_track_candidates
   for (int o = 0; o < max_obs; o++) D.owner[o] = -1;
-  for (int t = 0; t < T; t++) {
-    const int off = track_offsets[t], end = track_offsets[t + 1];
-    if (!tri_range_ok(off, end, O)) continue;
-    for (int o = off; o < end; o++) D.owner[o] = t > D.owner[o] ? t : D.owner[o];
-  }
-  for (int o = 0; o < O; o++) {
-    const int t = D.owner[o];
-    int key = -1;
-    if (t >= 0 && point_status[t] == TRI_OK) {
-      const float *X = points + 4 * (size_t)t;
-      const BundleObs ob = D.obs[o];
-      if (fundamental_finite(X[0]) && fundamental_finite(X[1]) && fundamental_finite(X[2]) && fundamental_finite(ob.xpos) &&
-          fundamental_finite(ob.ypos) && ob.frame >= 0 && ob.frame < nimages)
-        key = ob.frame;
-    }
-    D.key[o] = key;
-  }
+  for (int t = 0; t < T; t++) scene_track_owns(D.s, D.owner, t);
+  for (int o = 0; o < O; o++) D.key[o] = scene_slot_key(D.s, D.owner, o);
   for (int j = 0; j < 8; j++) summary[j] = 0;
   for (int i = 0; i < nimages; i++) bundle_image_init(D, i);
   for (int o = 0; o < O; o++) bundle_slot_premember(D, o);

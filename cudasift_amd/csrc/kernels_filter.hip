@@ -5,7 +5,7 @@
 //
 // One copy (the intrinsics into temp), three memsets (the owners, the tile sums, the summary) and six launches, whatever
 // the data:
-//   cand_owner_kernel        the owner of every slot: track_candidates.hpp, shared with kernels_refine.hip.
+//   cand_owner_kernel        the owner of every slot: launch_track_candidates (track_candidates.hpp) without the keys.
 //   filter_classify_kernel   one lane per slot: rule 1.  The reason goes to code[] and, where d_obs_map is given, there; a
 //                            survivor's unit ray and e2 go to ray[] as one 16-byte store.
 //   filter_track_kernel      one wavefront per track, four to a workgroup: the two pairwise rules.  The lanes stride over
@@ -40,10 +40,8 @@ constexpr int FILTER_TILE = 2048;              // tracks per scan tile: 256 lane
 constexpr int FILTER_SCAN_WG = 1024;
 
 struct FilterArgs {
-  CandArgs c;                                  // the tracks, the observations, the points; owner in temp (key unused)
-  const float *cam;
-  const int *cam_pair;
-  const float *intrinsics;                     // temp: the device copy, nimages x 4
+  TrackScene s;                                // intrinsics: the device copy in temp
+  const int *owner;                            // temp, max_obs
   float E2, max_cos;
   int min_views, unique_frames, ntiles;
   float4 *ray;                                 // temp, max_obs: a survivor's unit ray and e2
@@ -64,16 +62,16 @@ __device__ __forceinline__ int wave_sum(int v)
   return v;
 }
 
-__global__ __launch_bounds__(CAND_THREADS) void filter_classify_kernel(FilterArgs A)
+__global__ __launch_bounds__(FILTER_THREADS) void filter_classify_kernel(FilterArgs A)
 {
-  const int o = blockIdx.x * CAND_THREADS + threadIdx.x;     // below max_obs + 256: no overflow
+  const int o = blockIdx.x * FILTER_THREADS + threadIdx.x;   // below max_obs + 256: no overflow
   int code = 0;
-  const bool live = o < cand_O(A.c);
+  const bool live = o < scene_O(A.s);
   if (live) {
     float e2, u[3];
-    const CandObs ob = A.c.obs[o];
-    code = filter_classify(TriCamsPlain{A.cam, A.cam_pair, A.intrinsics}, A.c.nimages, A.c.owner[o], A.c.point_status,
-                           A.c.points, ob, A.E2, e2, u);
+    const TrackObs ob = track_obs_load(A.s.obs + o);
+    code = filter_classify(TriCamsPlain{A.s.cam, A.s.cam_pair, A.s.intrinsics}, A.s.nimages, A.owner[o], A.s.point_status,
+                           A.s.points, ob, A.E2, e2, u);
     A.code[o] = code;
     A.ray[o] = make_float4(u[0], u[1], u[2], e2);
     if (A.obs_map && code < 0) A.obs_map[o] = code;
@@ -102,9 +100,9 @@ struct FilterTrackView {
     }
     const int o = off + j;
     r = A.ray[o];
-    if (A.c.owner[o] != t) return -1;
+    if (A.owner[o] != t) return -1;
     const int c = A.code[o];
-    return c == 0 || (with_lost && c == FILTER_DUPLICATE) ? A.c.obs[o].frame : -1;
+    return c == 0 || (with_lost && c == FILTER_DUPLICATE) ? A.s.obs[o].frame : -1;
   }
 };
 
@@ -114,12 +112,12 @@ __global__ __launch_bounds__(FILTER_THREADS) void filter_track_kernel(FilterArgs
   __shared__ int s_fr[FILTER_WAVES][FILTER_STAGE];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const long long tl = (long long)blockIdx.x * FILTER_WAVES + wave;
-  if (tl >= cand_T(A.c)) return;               // the same in every lane of the wavefront; no workgroup barrier below
-  const int t = (int)tl, O = cand_O(A.c);
-  const int off = A.c.track_offsets[t], end = A.c.track_offsets[t + 1];
+  if (tl >= scene_T(A.s)) return;               // the same in every lane of the wavefront; no workgroup barrier below
+  const int t = (int)tl, O = scene_O(A.s);
+  const int off = A.s.track_offsets[t], end = A.s.track_offsets[t + 1];
   int result = 0;
   if (!tri_range_ok(off, end, O)) result = FILTER_NO_OWNER;    // before it addresses anything
-  else if (filter_bad_point(A.c.point_status[t], A.c.points + 4 * (size_t)t)) result = FILTER_BAD_POINT;
+  else if (filter_bad_point(A.s.point_status[t], A.s.points + 4 * (size_t)t)) result = FILTER_BAD_POINT;
   int m = 0;
   if (result == 0) {
     const int n = end - off;
@@ -130,7 +128,7 @@ __global__ __launch_bounds__(FILTER_THREADS) void filter_track_kernel(FilterArgs
     for (int k = lane; k < min(n, FILTER_STAGE); k += 64) {
       const int o = off + k;
       ray[k] = A.ray[o];
-      fr[k] = A.c.owner[o] == t && A.code[o] == 0 ? A.c.obs[o].frame : -1;
+      fr[k] = A.owner[o] == t && A.code[o] == 0 ? A.s.obs[o].frame : -1;
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -235,7 +233,7 @@ __global__ __launch_bounds__(256) void filter_apply_kernel(FilterArgs A)
 {
   __shared__ uint2 red[4];
   __shared__ int s_longest[4];
-  const int T = cand_T(A.c), O = cand_O(A.c);
+  const int T = scene_T(A.s), O = scene_O(A.s);
   int longest = 0;
   for (int tile = blockIdx.x; tile < A.ntiles; tile += gridDim.x) {
     const long long i0 = (long long)tile * FILTER_TILE + threadIdx.x * 8;
@@ -264,7 +262,7 @@ __global__ __launch_bounds__(256) void filter_apply_kernel(FilterArgs A)
       A.track_offsets_out[tn + 1] = off + m;
       A.point_views_out[tn] = m;
       A.point_status_out[tn] = 0;
-      const unsigned *src = reinterpret_cast<const unsigned *>(A.c.points) + 4 * (size_t)t;
+      const unsigned *src = reinterpret_cast<const unsigned *>(A.s.points) + 4 * (size_t)t;
       unsigned *dst = reinterpret_cast<unsigned *>(A.points_out) + 4 * (size_t)tn;
       dst[0] = src[0]; dst[1] = src[1]; dst[2] = src[2];
       longest = max(longest, m);
@@ -283,23 +281,23 @@ __global__ __launch_bounds__(FILTER_THREADS) void filter_write_kernel(FilterArgs
 {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const long long tl = (long long)blockIdx.x * FILTER_WAVES + wave;
-  if (tl >= cand_T(A.c)) return;
+  if (tl >= scene_T(A.s)) return;
   const int t = (int)tl;
   const int m = A.keep[t];
   if (m <= 0) return;                          // a surviving track has a valid range: the track launch checked it
-  const int off = A.c.track_offsets[t], end = A.c.track_offsets[t + 1];
+  const int off = A.s.track_offsets[t], end = A.s.track_offsets[t + 1];
   const int tn = A.track_map[t], at = A.newoff[t];
-  const int4 *obs = reinterpret_cast<const int4 *>(A.c.obs);
   int base = 0;
   float s = 0.0f;
   for (int o0 = off; o0 < end; o0 += 64) {
     const int o = o0 + lane;
-    const bool kept = o < end && A.c.owner[o] == t && A.code[o] == 0;
+    const bool kept = o < end && A.owner[o] == t && A.code[o] == 0;
     const float e2 = kept ? A.ray[o].w : 0.0f;
     unsigned long long mask = __ballot(kept);
     const int rank = base + __popcll(mask & ((1ull << lane) - 1ull));
     if (kept && rank < m) {                    // rank < m always: m is this count
-      A.obs_out[at + rank] = obs[o];
+      const TrackObs ob = track_obs_load(A.s.obs + o);
+      A.obs_out[at + rank] = make_int4(ob.frame, ob.record, __float_as_int(ob.xpos), __float_as_int(ob.ypos));
       if (A.obs_map) A.obs_map[o] = at + rank;
     }
     base += __popcll(mask);
@@ -324,15 +322,12 @@ size_t filter_tracks_batch_tmp_bytes(int max_tracks, int max_obs, int nimages)
 }
 
 // Enqueue misift_filter_tracks_batch on the context stream (common.hpp): a copy, three memsets and six launches.
-// h_intrinsics: the pinned copy, nimages x 4.
-int launch_filter_tracks_batch(misift_ctx *ctx, int max_tracks, int max_obs, const int *d_track_offsets,
-                               const void *d_obs, const int *d_export_summary, const float *d_points,
-                               const int *d_point_status, int nimages, const float *d_cam, const int *d_cam_pair,
-                               const float *h_intrinsics, float thresh2, float max_cos, int min_views, int unique_frames,
-                               int *d_track_offsets_out, void *d_obs_out, int *d_export_summary_out, float *d_points_out,
-                               int *d_point_views_out, int *d_point_status_out, int *d_track_map, int *d_obs_map,
-                               int *d_summary)
+int launch_filter_tracks_batch(misift_ctx *ctx, const TrackScene &scene, float thresh2, float max_cos, int min_views,
+                               int unique_frames, int *d_track_offsets_out, void *d_obs_out, int *d_export_summary_out,
+                               float *d_points_out, int *d_point_views_out, int *d_point_status_out, int *d_track_map,
+                               int *d_obs_map, int *d_summary)
 {
+  const int max_tracks = scene.max_tracks, max_obs = scene.max_obs, nimages = scene.nimages;
   const int rc = misift_ensure_tmp(ctx, filter_tracks_batch_tmp_bytes(max_tracks, max_obs, nimages));
   if (rc) return rc;
   const size_t obs_ints = filter_align16(sizeof(int) * (size_t)max_obs);
@@ -341,24 +336,22 @@ int launch_filter_tracks_batch(misift_ctx *ctx, int max_tracks, int max_obs, con
   const size_t tile_bytes = filter_align16(8 * (size_t)ntiles);
   char *t = reinterpret_cast<char *>(ctx->d_match_tmp);
   FilterArgs A;
-  A.c.max_tracks = max_tracks; A.c.max_obs = max_obs; A.c.nimages = nimages;
-  A.c.track_offsets = d_track_offsets; A.c.obs = reinterpret_cast<const CandObs *>(d_obs);
-  A.c.export_summary = d_export_summary; A.c.points = d_points; A.c.point_status = d_point_status;
-  A.c.key = nullptr;
+  A.s = scene;
   A.ray = reinterpret_cast<float4 *>(t); t += 16 * (size_t)max_obs;
-  A.c.owner = reinterpret_cast<int *>(t); t += obs_ints;
+  int *owner = reinterpret_cast<int *>(t); t += obs_ints;
+  A.owner = owner;
   A.code = reinterpret_cast<int *>(t); t += obs_ints;
   A.keep = reinterpret_cast<int *>(t); t += track_ints;
   A.newoff = reinterpret_cast<int *>(t); t += track_ints;
   A.tile = reinterpret_cast<unsigned long long *>(t); t += tile_bytes;
   float *d_intrinsics = reinterpret_cast<float *>(t);
-  A.cam = d_cam; A.cam_pair = d_cam_pair; A.intrinsics = d_intrinsics;
+  A.s.intrinsics = d_intrinsics;
   A.E2 = thresh2; A.max_cos = max_cos; A.min_views = min_views; A.unique_frames = unique_frames; A.ntiles = ntiles;
   A.track_offsets_out = d_track_offsets_out; A.obs_out = reinterpret_cast<int4 *>(d_obs_out);
   A.export_summary_out = d_export_summary_out; A.points_out = d_points_out; A.point_views_out = d_point_views_out;
   A.point_status_out = d_point_status_out; A.track_map = d_track_map; A.obs_map = d_obs_map; A.summary = d_summary;
-  HIP_TRY(hipMemcpyAsync(d_intrinsics, h_intrinsics, 16 * (size_t)nimages, hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(hipMemsetAsync(A.c.owner, 0xff, sizeof(int) * (size_t)max_obs, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(d_intrinsics, scene.intrinsics, 16 * (size_t)nimages, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hipMemsetAsync(owner, 0xff, sizeof(int) * (size_t)max_obs, ctx->stream));
   HIP_TRY(hipMemsetAsync(A.tile, 0, tile_bytes, ctx->stream));
   HIP_TRY(hipMemsetAsync(d_summary, 0, 8 * sizeof(int), ctx->stream));
   const int ncu = ctx->num_cus > 0 ? ctx->num_cus : 256;
@@ -366,12 +359,13 @@ int launch_filter_tracks_batch(misift_ctx *ctx, int max_tracks, int max_obs, con
   int lrc;
   {
     LaunchScope ls(ctx, "filter_owner");
-    hipLaunchKernelGGL(cand_owner_kernel, cand_blocks(max_tracks), dim3(CAND_THREADS), 0, ctx->stream, A.c);
+    launch_track_candidates(ctx, scene, owner, nullptr);
     if ((lrc = ls.finish())) return lrc;
   }
   {
     LaunchScope ls(ctx, "filter_classify");
-    hipLaunchKernelGGL(filter_classify_kernel, cand_blocks(max_obs), dim3(CAND_THREADS), 0, ctx->stream, A);
+    const dim3 per_slot((unsigned)(((long long)max_obs + FILTER_THREADS - 1) / FILTER_THREADS));
+    hipLaunchKernelGGL(filter_classify_kernel, per_slot, dim3(FILTER_THREADS), 0, ctx->stream, A);
     if ((lrc = ls.finish())) return lrc;
   }
   {
@@ -405,7 +399,6 @@ extern "C" int misift_test_filter_tracks(int max_tracks, int max_obs, const int 
                                          float *points_out, int *point_views_out, int *point_status_out, int *track_map,
                                          int *obs_map, int *summary)
 {
-  static_assert(sizeof(FilterHostObs) == sizeof(misift_track_obs), "FilterHostObs mirrors misift_track_obs");
   const bool ok = max_tracks >= 1 && max_obs >= 1 && nimages >= 1 && track_offsets && obs && export_summary && points &&
                   point_status && cam && cam_pair && intrinsics && max_error > 0.0f && max_cos == max_cos &&
                   min_views >= 2 && (unique_frames == 0 || unique_frames == 1) && track_offsets_out && obs_out &&
@@ -414,9 +407,10 @@ extern "C" int misift_test_filter_tracks(int max_tracks, int max_obs, const int 
     misift_set_error("misift_test_filter_tracks: invalid argument");
     return MISIFT_EINVAL;
   }
-  filter_tracks_host(max_tracks, max_obs, track_offsets, reinterpret_cast<const FilterHostObs *>(obs), export_summary,
-                     points, point_status, nimages, cam, cam_pair, intrinsics, max_error * max_error, max_cos, min_views,
-                     unique_frames, track_offsets_out, reinterpret_cast<FilterHostObs *>(obs_out), export_summary_out,
-                     points_out, point_views_out, point_status_out, track_map, obs_map, summary);
+  const TrackScene S{max_tracks, max_obs, nimages, track_offsets, reinterpret_cast<const TrackObs *>(obs), export_summary,
+                     points, point_status, cam, cam_pair, intrinsics};
+  filter_tracks_host(S, max_error * max_error, max_cos, min_views, unique_frames, track_offsets_out,
+                     reinterpret_cast<TrackObs *>(obs_out), export_summary_out, points_out, point_views_out,
+                     point_status_out, track_map, obs_map, summary);
   return MISIFT_OK;
 }

@@ -6,7 +6,7 @@
 //
 // Two memsets (the owners, the summary) and three launches, whatever the data:
 //   cand_owner_kernel      the owner of every slot and
-//   cand_key_kernel        the image every slot is a candidate of: track_candidates.hpp, shared with kernels_resect.hip.
+//   cand_key_kernel        the image every slot is a candidate of: launch_track_candidates (track_candidates.hpp).
 //   refine_cameras_kernel  one 256-thread workgroup per image, thread s being slot s of the call's sum.  A pass walks the
 //                          keys o = s, s + 256, ... < O with coalesced 4-byte loads, eight ahead; for a key that names its
 //                          image the lane loads the owner, the 16-byte observation and the point, decides membership under
@@ -31,10 +31,8 @@ constexpr int REFINE_AHEAD = 8;                // slot keys a lane loads before 
 struct RefineArgs {
   int min_obs, num_loops, orthonormalise;
   float thresh2;
-  CandArgs c;                                  // the tracks, the observations, the points; owner and key in temp
-  const float *cam;
-  const int *cam_pair;
-  const float *intrinsics;                     // the pinned host copy: nimages x 4
+  TrackScene s;                                // intrinsics: the pinned host copy
+  const int *owner, *key;                      // temp: max_obs each
   const int *held;                             // the pinned host copy: nimages flags
   float *cam_out;
   int *cam_obs;
@@ -54,8 +52,8 @@ struct RefineBlockExec {
   __device__ __forceinline__ bool terms(int o, const float (&cam1)[12], const float (&cam)[12], float thresh2,
                                         float (&x)[REFINE_SUMS], int &n, bool &behind) const
   {
-    const float *P = A.c.points + 4 * (size_t)A.c.owner[o];
-    const CandObs ob = A.c.obs[o];
+    const float *P = A.s.points + 4 * (size_t)A.owner[o];
+    const TrackObs ob = track_obs_load(A.s.obs + o);
     const float X[3] = {P[0], P[1], P[2]};
     if (!refine_member(cam1, k, X, ob.xpos, ob.ypos, thresh2)) return false;
     n++;
@@ -81,7 +79,7 @@ struct RefineBlockExec {
 #pragma unroll
       for (int u = 0; u < REFINE_AHEAD; u++) {
         const long long o = base + u * FUND_SLOTS;
-        key[u] = o < O ? A.c.key[o] : -1;
+        key[u] = o < O ? A.key[o] : -1;
       }
 #pragma unroll
       for (int u = 0; u < REFINE_AHEAD; u++) {
@@ -121,8 +119,8 @@ __global__ __launch_bounds__(REFINE_THREADS) void refine_cameras_kernel(RefineAr
   __shared__ float s_p[REFINE_SUMS * FUND_SLOTS];
   __shared__ int s_cnt[8];
   const int i = blockIdx.x, tid = threadIdx.x;
-  if (i == 0 && tid == 0) A.summary[0] = cand_T(A.c);
-  const unsigned *bits = reinterpret_cast<const unsigned *>(A.cam) + 12 * (size_t)i;
+  if (i == 0 && tid == 0) A.summary[0] = scene_T(A.s);
+  const unsigned *bits = reinterpret_cast<const unsigned *>(A.s.cam) + 12 * (size_t)i;
   unsigned given[12];
   float cam_in[12];
 #pragma unroll
@@ -130,11 +128,11 @@ __global__ __launch_bounds__(REFINE_THREADS) void refine_cameras_kernel(RefineAr
     given[j] = bits[j];
     cam_in[j] = __uint_as_float(given[j]);
   }
-  const int pair = A.cam_pair[i];
-  const float k[4] = {A.intrinsics[4 * (size_t)i], A.intrinsics[4 * (size_t)i + 1], A.intrinsics[4 * (size_t)i + 2],
-                      A.intrinsics[4 * (size_t)i + 3]};
+  const int pair = A.s.cam_pair[i];
+  const float *kp = A.s.intrinsics + 4 * (size_t)i;
+  const float k[4] = {kp[0], kp[1], kp[2], kp[3]};
   const bool fixed = pair == POSEGRAPH_ROOT || A.held[i] != 0;
-  RefineBlockExec ex{A, s_p, s_cnt, i, cand_O(A.c), k};
+  RefineBlockExec ex{A, s_p, s_cnt, i, scene_O(A.s), k};
   RefineResult r;
   refine_camera(ex, cam_in, pair == POSEGRAPH_UNSET, fixed, k, A.orthonormalise, A.min_obs, A.num_loops, A.thresh2, r);
   if (tid != 0) return;                        // every thread holds the same result; the input was read above
@@ -155,35 +153,21 @@ __global__ __launch_bounds__(REFINE_THREADS) void refine_cameras_kernel(RefineAr
 
 size_t refine_cameras_batch_tmp_bytes(int max_obs) { return 2 * sizeof(int) * (size_t)max_obs; }
 
-// Enqueue misift_refine_cameras_batch on the context stream (common.hpp): two memsets and three launches.  h_lists: the
-// pinned copies, nimages x 4 intrinsics and then nimages held flags.
-int launch_refine_cameras_batch(misift_ctx *ctx, int max_tracks, int max_obs, const int *d_track_offsets,
-                                const void *d_obs, const int *d_export_summary, const float *d_points,
-                                const int *d_point_status, int nimages, const float *d_cam, const int *d_cam_pair,
-                                const void *h_lists, int min_obs, int num_loops, float thresh2, int orthonormalise,
-                                float *d_cam_out, int *d_cam_obs, float *d_cam_rms, int *d_cam_steps, int *d_cam_status,
-                                int *d_summary)
+// Enqueue misift_refine_cameras_batch on the context stream (common.hpp): two memsets and three launches.
+int launch_refine_cameras_batch(misift_ctx *ctx, const TrackScene &scene, const int *h_held, int min_obs, int num_loops,
+                                float thresh2, int orthonormalise, float *d_cam_out, int *d_cam_obs, float *d_cam_rms,
+                                int *d_cam_steps, int *d_cam_status, int *d_summary)
 {
-  const int rc = misift_ensure_tmp(ctx, refine_cameras_batch_tmp_bytes(max_obs));
+  const int rc = misift_ensure_tmp(ctx, refine_cameras_batch_tmp_bytes(scene.max_obs));
   if (rc) return rc;
-  RefineArgs A;
-  A.min_obs = min_obs; A.num_loops = num_loops; A.orthonormalise = orthonormalise; A.thresh2 = thresh2;
-  A.c.max_tracks = max_tracks; A.c.max_obs = max_obs; A.c.nimages = nimages;
-  A.c.track_offsets = d_track_offsets; A.c.obs = reinterpret_cast<const CandObs *>(d_obs);
-  A.c.export_summary = d_export_summary; A.c.points = d_points;
-  A.c.point_status = d_point_status; A.cam = d_cam; A.cam_pair = d_cam_pair;
-  A.intrinsics = reinterpret_cast<const float *>(h_lists);
-  A.held = reinterpret_cast<const int *>(A.intrinsics + 4 * (size_t)nimages);
-  A.c.owner = reinterpret_cast<int *>(ctx->d_match_tmp);
-  A.c.key = A.c.owner + max_obs;
-  A.cam_out = d_cam_out; A.cam_obs = d_cam_obs; A.cam_rms = d_cam_rms; A.cam_steps = d_cam_steps;
-  A.cam_status = d_cam_status; A.summary = d_summary;
-  HIP_TRY(hipMemsetAsync(A.c.owner, 0xff, sizeof(int) * (size_t)max_obs, ctx->stream));
+  int *owner = reinterpret_cast<int *>(ctx->d_match_tmp), *key = owner + scene.max_obs;
+  const RefineArgs A{min_obs, num_loops, orthonormalise, thresh2, scene, owner, key, h_held, d_cam_out, d_cam_obs,
+                     d_cam_rms, d_cam_steps, d_cam_status, d_summary};
+  HIP_TRY(hipMemsetAsync(owner, 0xff, sizeof(int) * (size_t)scene.max_obs, ctx->stream));
   HIP_TRY(hipMemsetAsync(d_summary, 0, 8 * sizeof(int), ctx->stream));
   LaunchScope ls(ctx, "refine_cameras");
-  hipLaunchKernelGGL(cand_owner_kernel, cand_blocks(max_tracks), dim3(CAND_THREADS), 0, ctx->stream, A.c);
-  hipLaunchKernelGGL(cand_key_kernel, cand_blocks(max_obs), dim3(CAND_THREADS), 0, ctx->stream, A.c);
-  hipLaunchKernelGGL(refine_cameras_kernel, dim3(nimages), dim3(REFINE_THREADS), 0, ctx->stream, A);
+  launch_track_candidates(ctx, scene, owner, key);
+  hipLaunchKernelGGL(refine_cameras_kernel, dim3(scene.nimages), dim3(REFINE_THREADS), 0, ctx->stream, A);
   return ls.finish();
 }
 

@@ -7,7 +7,7 @@
 // Two memsets (the owners, the summary) and six launches, whatever the data (nsel == 0: the summary's memset and the
 // pick launch alone, which writes T):
 //   cand_owner_kernel     the owner of every slot and
-//   cand_key_kernel       the image every slot is a candidate of: track_candidates.hpp, shared with kernels_refine.hip.
+//   cand_key_kernel       the image every slot is a candidate of: launch_track_candidates (track_candidates.hpp).
 //   resect_gather_kernel  one 1024-thread workgroup per entry walks the keys in ascending slot order; a ballot / popcount
 //                         compaction keeps that order (a sample position p means "the p-th candidate"), and the lane of
 //                         a candidate writes its x, y, X, Y, Z as SoA into the entry's temp.  Then wave 0 draws the
@@ -38,13 +38,13 @@ namespace {
 constexpr int RESECT_META = 4;                 // ints of meta per entry
 
 struct ResectArgs {
-  CandArgs c;                                  // the tracks, the observations, the points; owner and key in temp
+  TrackScene s;                                // intrinsics: the pinned host copy; cam and cam_pair may be NULL
+  const int *owner, *key;                      // temp: max_obs each
   int nsel, max_cand, mc16;                    // mc16 = min(max_cand, max_obs) rounded up to 16
   int num_loops, lp;                           // hypotheses; their stride, num_loops rounded up to 16
   int min_inliers, only_unset, install;
   float thresh2;
-  const float *intrinsics;                     // the pinned host copies: nimages x 4,
-  const int *images;                           // nsel,
+  const int *images;                           // the pinned host copies: nsel,
   const unsigned *seeds;                       // nsel
   // temp behind owner and key, per entry e:  coord[5 x mc16] | sample[6 x lp] | hyp[12 x lp] | hcount[lp] | meta[4]
   float *coord;                                // x, y, X, Y, Z of the candidates in slot order, SoA
@@ -70,14 +70,14 @@ __global__ __launch_bounds__(1024) void resect_gather_kernel(ResectArgs A)
     if (tid == 0) { meta[0] = 0; meta[1] = RESECT_SKIPPED; meta[2] = 0; }
     return;
   }
-  const int O = cand_O(A.c), T = cand_T(A.c);
+  const int O = scene_O(A.s), T = scene_T(A.s);
   float *coord = A.coord + (size_t)e * 5 * A.mc16;
   const int mc = A.mc16;
   if (tid == 0) base_s = 0;
   __syncthreads();
   for (long long o0 = 0; o0 < O; o0 += 1024) {
     const long long o = o0 + tid;
-    const bool ok = o < O && A.c.key[o] == img;
+    const bool ok = o < O && A.key[o] == img;
     const unsigned long long m = __ballot(ok);
     if (lane == 0) wave_cnt[wave] = __popcll(m);
     __syncthreads();
@@ -85,10 +85,10 @@ __global__ __launch_bounds__(1024) void resect_gather_kernel(ResectArgs A)
     for (int w = 0; w < wave; w++) off += wave_cnt[w];
     const int pos = off + __popcll(m & ((1ull << lane) - 1ull));
     if (ok && pos < A.max_cand) {              // beyond max_cand only the count goes on
-      const int t = A.c.owner[o];
+      const int t = A.owner[o];
       const bool t_ok = (unsigned)t < (unsigned)T;           // an index from device memory: checked before use
-      const float *P = A.c.points + 4 * (size_t)(t_ok ? t : 0);
-      const CandObs ob = A.c.obs[o];
+      const float *P = A.s.points + 4 * (size_t)(t_ok ? t : 0);
+      const TrackObs ob = track_obs_load(A.s.obs + o);
       coord[pos] = ob.xpos;
       coord[mc + pos] = ob.ypos;
       coord[2 * mc + pos] = t_ok ? P[0] : 0.0f;
@@ -154,7 +154,7 @@ __global__ __launch_bounds__(64) void resect_solve_kernel(ResectArgs A, int hblo
     in_range = in_range && pos_ok;
     x[k] = coord[i]; y[k] = coord[mc + i]; X[k] = coord[2 * mc + i]; Y[k] = coord[3 * mc + i]; Z[k] = coord[4 * mc + i];
   }
-  const float *kp = A.intrinsics + 4 * (size_t)A.images[e];
+  const float *kp = A.s.intrinsics + 4 * (size_t)A.images[e];
   const float k[4] = {kp[0], kp[1], kp[2], kp[3]};
   ResectLdsMat m{s_m + threadIdx.x};
   float cam[12];
@@ -188,7 +188,7 @@ __global__ __launch_bounds__(64) void resect_count_kernel(ResectArgs A, int hblo
   float cam[12];
 #pragma unroll
   for (int j = 0; j < 12; j++) cam[j] = hyp[j * lp + h];
-  const float *kp = A.intrinsics + 4 * (size_t)A.images[e];
+  const float *kp = A.s.intrinsics + 4 * (size_t)A.images[e];
   const float k[4] = {kp[0], kp[1], kp[2], kp[3]};
   const float thresh2 = A.thresh2;
   int cnt = 0;
@@ -203,7 +203,7 @@ __global__ __launch_bounds__(64) void resect_count_kernel(ResectArgs A, int hblo
 __global__ __launch_bounds__(1024) void resect_pick_kernel(ResectArgs A)
 {
   const int e = blockIdx.x, tid = threadIdx.x;
-  if (e == 0 && tid == 0) A.summary[0] = cand_T(A.c);
+  if (e == 0 && tid == 0) A.summary[0] = scene_T(A.s);
   if (e >= A.nsel) return;                     // nsel == 0: the one workgroup that writes T
   const int *meta = A.meta + (size_t)RESECT_META * e;
   const bool searched = meta[0] != 0;
@@ -266,15 +266,13 @@ size_t resect_cameras_batch_tmp_bytes(int max_obs, int nsel, int max_cand, int n
   return sizeof(int) * (2 * (size_t)max_obs + (size_t)nsel * resect_entry_words(max_obs, max_cand, num_loops));
 }
 
-// Enqueue misift_resect_cameras_batch on the context stream (common.hpp): two memsets and six launches.  h_lists: the
-// pinned copies, nimages x 4 intrinsics, then nsel images, then nsel seeds.
-int launch_resect_cameras_batch(misift_ctx *ctx, int max_tracks, int max_obs, const int *d_track_offsets,
-                                const void *d_obs, const int *d_export_summary, const float *d_points,
-                                const int *d_point_status, int nimages, int nsel, const void *h_lists, int max_cand,
-                                int num_loops, float thresh2, int min_inliers, int only_unset, int install, float *d_cam,
-                                int *d_cam_pair, float *d_res_cam, int *d_res_cand, int *d_res_inliers,
-                                int *d_res_status, int *d_summary)
+// Enqueue misift_resect_cameras_batch on the context stream (common.hpp): two memsets and six launches.
+int launch_resect_cameras_batch(misift_ctx *ctx, const TrackScene &scene, int nsel, const int *h_images,
+                                const unsigned *h_seeds, int max_cand, int num_loops, float thresh2, int min_inliers,
+                                int only_unset, int install, float *d_cam, int *d_cam_pair, float *d_res_cam,
+                                int *d_res_cand, int *d_res_inliers, int *d_res_status, int *d_summary)
 {
+  const int max_obs = scene.max_obs;
   const int cap = resect_capacity(max_obs, max_cand);
   if (!resect_cameras_batch_one_launch(max_obs, nsel, max_cand, num_loops)) {                // the wrapper's check
     misift_set_error("misift_resect_cameras_batch: %d entries x %d loops x %d candidates is beyond one launch", nsel,
@@ -282,22 +280,18 @@ int launch_resect_cameras_batch(misift_ctx *ctx, int max_tracks, int max_obs, co
     return MISIFT_EINVAL;
   }
   ResectArgs A{};
+  A.s = scene;
   A.nsel = nsel; A.max_cand = max_cand; A.mc16 = ransac_round16(cap);
   A.num_loops = num_loops; A.lp = ransac_round16(num_loops);
   A.min_inliers = min_inliers; A.only_unset = only_unset; A.install = install; A.thresh2 = thresh2;
   const int hblocks = (num_loops + 63) / 64, chunks = (A.mc16 + RANSAC_CHUNK - 1) / RANSAC_CHUNK;
   const int rc = misift_ensure_tmp(ctx, resect_cameras_batch_tmp_bytes(max_obs, nsel, max_cand, num_loops));
   if (rc) return rc;
-  A.c.max_tracks = max_tracks; A.c.max_obs = max_obs; A.c.nimages = nimages;
-  A.c.track_offsets = d_track_offsets; A.c.obs = reinterpret_cast<const CandObs *>(d_obs);
-  A.c.export_summary = d_export_summary; A.c.points = d_points; A.c.point_status = d_point_status;
-  A.intrinsics = reinterpret_cast<const float *>(h_lists);
-  A.images = reinterpret_cast<const int *>(A.intrinsics + 4 * (size_t)nimages);
-  A.seeds = reinterpret_cast<const unsigned *>(A.images + nsel);
+  A.images = h_images; A.seeds = h_seeds;
   const size_t ns = (size_t)nsel, mc = (size_t)A.mc16, lp = (size_t)A.lp;
-  A.c.owner = reinterpret_cast<int *>(ctx->d_match_tmp);
-  A.c.key = A.c.owner + max_obs;
-  A.coord = reinterpret_cast<float *>(A.c.key + max_obs);
+  int *owner = reinterpret_cast<int *>(ctx->d_match_tmp), *key = owner + max_obs;
+  A.owner = owner; A.key = key;
+  A.coord = reinterpret_cast<float *>(key + max_obs);
   A.sample = reinterpret_cast<int *>(A.coord + ns * 5 * mc);
   A.hyp = reinterpret_cast<float *>(A.sample + ns * RESECT_SAMPLE * lp);
   A.hcount = reinterpret_cast<int *>(A.hyp + ns * 12 * lp);
@@ -311,12 +305,11 @@ int launch_resect_cameras_batch(misift_ctx *ctx, int max_tracks, int max_obs, co
     hipLaunchKernelGGL(resect_pick_kernel, dim3(1), dim3(1024), 0, ctx->stream, A);
     return ls.finish();
   }
-  HIP_TRY(hipMemsetAsync(A.c.owner, 0xff, sizeof(int) * (size_t)max_obs, ctx->stream));
+  HIP_TRY(hipMemsetAsync(owner, 0xff, sizeof(int) * (size_t)max_obs, ctx->stream));
   int r;
   {
     LaunchScope ls(ctx, "resect_gather");
-    hipLaunchKernelGGL(cand_owner_kernel, cand_blocks(max_tracks), dim3(CAND_THREADS), 0, ctx->stream, A.c);
-    hipLaunchKernelGGL(cand_key_kernel, cand_blocks(max_obs), dim3(CAND_THREADS), 0, ctx->stream, A.c);
+    launch_track_candidates(ctx, scene, owner, key);
     hipLaunchKernelGGL(resect_gather_kernel, dim3(nsel), dim3(1024), 0, ctx->stream, A);
     r = ls.finish();
     if (r) return r;

@@ -29,20 +29,10 @@ constexpr int TRI_THREADS = 256;
 constexpr int TRI_CAPACITY = 512;              // images whose cameras and intrinsics are staged in LDS
 constexpr int TRI_WORDS = 17;                  // per staged image
 
-struct alignas(16) TriObs {                    // misift_track_obs, read with one 16-byte load
-  int frame, record;
-  float xpos, ypos;
-};
-static_assert(sizeof(TriObs) == sizeof(misift_track_obs), "TriObs mirrors misift_track_obs");
-
 struct TriArgs {
-  int max_tracks, max_obs, nimages, min_views, num_loops;
-  const int *track_offsets;
-  const TriObs *obs;
-  const int *export_summary;
-  const float *cam;
-  const int *cam_pair;
-  const float *intrinsics;                     // the pinned host copy (staged) or its device copy (beyond the capacity)
+  TrackScene s;                                // no points yet; intrinsics: the pinned host copy (staged) or its device
+                                               // copy (beyond the capacity)
+  int min_views, num_loops;
   float *points;
   int *point_views, *point_status;
   float *obs_error;                            // may be NULL
@@ -60,16 +50,16 @@ struct TriCamsStaged {
 template <class Cams>
 __device__ __forceinline__ int tri_lane(const TriArgs &A, const Cams &C, int t, int *views, int *kept)
 {
-  const int off = A.track_offsets[t], end = A.track_offsets[t + 1];
+  const int off = A.s.track_offsets[t], end = A.s.track_offsets[t + 1];
   float *point = A.points + 4 * (size_t)t;
-  if (!tri_range_ok(off, end, A.max_obs)) {
+  if (!tri_range_ok(off, end, A.s.max_obs)) {
     const float nan = pose_one_nan(NAN);
     point[0] = point[1] = point[2] = point[3] = nan;
     *views = 0;
     *kept = 0;
     return TRI_BAD_RANGE;
   }
-  return tri_track(C, A.nimages, A.obs + off, end - off, A.min_views, A.num_loops, point, views,
+  return tri_track(C, A.s.nimages, A.s.obs + off, end - off, A.min_views, A.num_loops, point, views,
                    A.obs_error ? A.obs_error + off : nullptr, kept);
 }
 
@@ -77,17 +67,18 @@ __global__ __launch_bounds__(TRI_THREADS) void triangulate_tracks_kernel(TriArgs
 {
   extern __shared__ __attribute__((aligned(16))) float s_cams[];
   const int tid = threadIdx.x;
-  const int T = min(max(A.export_summary[2], 0), A.max_tracks);
+  const int T = scene_T(A.s);
   if (blockIdx.x == 0 && tid == 0) A.summary[0] = T;
   const int first = blockIdx.x * TRI_THREADS;  // at most max_tracks - 1: no overflow
   if (first >= T) return;                      // the same in every thread
-  const bool staged = A.nimages <= TRI_CAPACITY;
+  const int nimages = A.s.nimages;
+  const bool staged = nimages <= TRI_CAPACITY;
   if (staged) {
-    for (int i = tid; i < 12 * A.nimages; i += TRI_THREADS) s_cams[TRI_WORDS * (i / 12) + i % 12] = A.cam[i];
-    for (int i = tid; i < 4 * A.nimages; i += TRI_THREADS) s_cams[TRI_WORDS * (i >> 2) + 12 + (i & 3)] = A.intrinsics[i];
+    for (int i = tid; i < 12 * nimages; i += TRI_THREADS) s_cams[TRI_WORDS * (i / 12) + i % 12] = A.s.cam[i];
+    for (int i = tid; i < 4 * nimages; i += TRI_THREADS) s_cams[TRI_WORDS * (i >> 2) + 12 + (i & 3)] = A.s.intrinsics[i];
     __syncthreads();
-    for (int i = tid; i < A.nimages; i += TRI_THREADS) {       // TriCamsPlain::set, once per image
-      bool ok = A.cam_pair[i] != POSEGRAPH_UNSET;
+    for (int i = tid; i < nimages; i += TRI_THREADS) {         // TriCamsPlain::set, once per image
+      bool ok = A.s.cam_pair[i] != POSEGRAPH_UNSET;
       for (int j = 0; j < 12; j++) ok = ok && fundamental_finite(s_cams[TRI_WORDS * i + j]);
       s_cams[TRI_WORDS * i + 16] = ok ? 1.0f : 0.0f;
     }
@@ -99,7 +90,7 @@ __global__ __launch_bounds__(TRI_THREADS) void triangulate_tracks_kernel(TriArgs
     // the two calls differ in nothing but where the cameras are read, and are kept apart so that the staged one compiles
     // to LDS instructions and not to flat ones
     if (staged) status = tri_lane(A, TriCamsStaged{s_cams}, t, &views, &kept);
-    else status = tri_lane(A, TriCamsPlain{A.cam, A.cam_pair, A.intrinsics}, t, &views, &kept);
+    else status = tri_lane(A, TriCamsPlain{A.s.cam, A.s.cam_pair, A.s.intrinsics}, t, &views, &kept);
     A.point_views[t] = views;
     A.point_status[t] = status;
   }
@@ -120,29 +111,22 @@ size_t triangulate_tracks_batch_tmp_bytes(int nimages)
 }
 
 // Enqueue misift_triangulate_tracks_batch on the context stream (common.hpp): a memset and one launch; beyond the
-// staging capacity a copy of the intrinsics into temp memory goes first.  h_intrinsics: the pinned copy, nimages x 4.
-int launch_triangulate_tracks_batch(misift_ctx *ctx, int max_tracks, int max_obs, const int *d_track_offsets,
-                                    const void *d_obs, const int *d_export_summary, int nimages, const float *d_cam,
-                                    const int *d_cam_pair, const float *h_intrinsics, int min_views, int num_loops,
+// staging capacity a copy of the intrinsics into temp memory goes first.  scene.intrinsics: the pinned copy.
+int launch_triangulate_tracks_batch(misift_ctx *ctx, const TrackScene &scene, int min_views, int num_loops,
                                     float *d_points, int *d_point_views, int *d_point_status, float *d_obs_error,
                                     int *d_summary)
 {
-  TriArgs A;
-  A.max_tracks = max_tracks; A.max_obs = max_obs; A.nimages = nimages; A.min_views = min_views; A.num_loops = num_loops;
-  A.track_offsets = d_track_offsets; A.obs = reinterpret_cast<const TriObs *>(d_obs);
-  A.export_summary = d_export_summary; A.cam = d_cam; A.cam_pair = d_cam_pair; A.intrinsics = h_intrinsics;
-  A.points = d_points; A.point_views = d_point_views; A.point_status = d_point_status; A.obs_error = d_obs_error;
-  A.summary = d_summary;
-  const size_t tmp = triangulate_tracks_batch_tmp_bytes(nimages);
+  TriArgs A{scene, min_views, num_loops, d_points, d_point_views, d_point_status, d_obs_error, d_summary};
+  const size_t tmp = triangulate_tracks_batch_tmp_bytes(scene.nimages);
   if (tmp) {
     const int rc = misift_ensure_tmp(ctx, tmp);
     if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(ctx->d_match_tmp, h_intrinsics, tmp, hipMemcpyHostToDevice, ctx->stream));
-    A.intrinsics = reinterpret_cast<const float *>(ctx->d_match_tmp);
+    HIP_TRY(hipMemcpyAsync(ctx->d_match_tmp, scene.intrinsics, tmp, hipMemcpyHostToDevice, ctx->stream));
+    A.s.intrinsics = reinterpret_cast<const float *>(ctx->d_match_tmp);
   }
   HIP_TRY(hipMemsetAsync(d_summary, 0, 8 * sizeof(int), ctx->stream));
-  const size_t lds = tmp ? 0 : sizeof(float) * TRI_WORDS * (size_t)nimages;
-  const unsigned blocks = (unsigned)(((long long)max_tracks + TRI_THREADS - 1) / TRI_THREADS);
+  const size_t lds = tmp ? 0 : sizeof(float) * TRI_WORDS * (size_t)scene.nimages;
+  const unsigned blocks = (unsigned)(((long long)scene.max_tracks + TRI_THREADS - 1) / TRI_THREADS);
   LaunchScope ls(ctx, "triangulate_tracks");
   hipLaunchKernelGGL(triangulate_tracks_kernel, dim3(blocks), dim3(TRI_THREADS), lds, ctx->stream, A);
   return ls.finish();
@@ -161,7 +145,7 @@ extern "C" int misift_test_triangulate_track(const float *cams, const int *cam_p
     misift_set_error("misift_test_triangulate_track: invalid argument");
     return MISIFT_EINVAL;
   }
-  *status = tri_track(TriCamsPlain{cams, cam_pair, intrinsics}, nimages, obs, nobs, min_views, num_loops, point4, views,
-                      obs_error, gn_accepted);
+  *status = tri_track(TriCamsPlain{cams, cam_pair, intrinsics}, nimages, reinterpret_cast<const TrackObs *>(obs), nobs,
+                      min_views, num_loops, point4, views, obs_error, gn_accepted);
   return MISIFT_OK;
 }

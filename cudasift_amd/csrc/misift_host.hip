@@ -2592,6 +2592,40 @@ extern "C" int misift_export_tracks_batch(misift_ctx *ctx, const void *d_recs, i
   });
 }
 
+// ---- the track chain: the five calls over one scene
+// The scene checked and filled in (TrackScene, triangulate_core.hpp): the sizes, the pointers every one of the calls
+// needs, d_obs aligned for the kernels' one 16-byte load (track_obs_load) and usable intrinsics for every image.  What
+// only some calls need (the points, the cameras) is taken as given and checked by the call.  S->intrinsics is the
+// caller's list until the launch lambda puts the pinned copy in its place.
+static int check_scene(const char *who, TrackScene *S, int max_tracks, int max_obs, const int *d_track_offsets,
+                       const misift_track_obs *d_obs, const int *d_export_summary, const float *d_points,
+                       const int *d_point_status, int nimages, const float *d_cam, const int *d_cam_pair,
+                       const float *intrinsics)
+{
+  ARG_CHECK_IN(who, max_tracks >= 1 && max_obs >= 1 && nimages >= 1);
+  ARG_CHECK_IN(who, d_track_offsets && d_obs && d_export_summary && intrinsics);
+  ARG_CHECK_IN(who, ((uintptr_t)d_obs & 15) == 0);
+  for (int i = 0; i < nimages; i++) ARG_CHECK_IN(who, intrinsics_usable(intrinsics + 4 * (size_t)i, 1));
+  *S = TrackScene{max_tracks, max_obs, nimages, d_track_offsets, reinterpret_cast<const TrackObs *>(d_obs),
+                  d_export_summary, d_points, d_point_status, d_cam, d_cam_pair, intrinsics};
+  return MISIFT_OK;
+}
+
+// an output may be its input in place, or share no byte with it
+static bool same_or_disjoint(const void *a, const void *b, size_t bytes)
+{
+  const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+  return pa == pb || pa + bytes <= pb || pb + bytes <= pa;
+}
+
+// a flag per image from a list of images, each checked to lie in [0, nimages)
+static std::vector<int> held_flags(int nimages, int nhold, const int *hold)
+{
+  std::vector<int> held(nimages, 0);
+  for (int j = 0; j < nhold; j++) held[hold[j]] = 1;
+  return held;
+}
+
 // One world point per exported track under the cameras of misift_link_poses_batch: the call that joins the track chain
 // to the pose chain.  The intrinsics go to the pinned slot.
 extern "C" int misift_triangulate_tracks_batch(misift_ctx *ctx, int max_tracks, int max_obs, const int *d_track_offsets,
@@ -2600,17 +2634,18 @@ extern "C" int misift_triangulate_tracks_batch(misift_ctx *ctx, int max_tracks, 
                                                int min_views, int num_loops, float *d_points, int *d_point_views,
                                                int *d_point_status, float *d_obs_error, int *d_summary)
 {
-  ARG_CHECK(ctx && max_tracks >= 1 && max_obs >= 1 && nimages >= 1);
-  ARG_CHECK(d_track_offsets && d_obs && d_export_summary && d_cam && d_cam_pair && intrinsics);
-  ARG_CHECK(d_points && d_point_views && d_point_status && d_summary);
-  ARG_CHECK(((uintptr_t)d_obs & 15) == 0);
+  ARG_CHECK(ctx != nullptr);
+  TrackScene S;
+  int rc = check_scene(__func__, &S, max_tracks, max_obs, d_track_offsets, d_obs, d_export_summary, nullptr, nullptr,
+                       nimages, d_cam, d_cam_pair, intrinsics);
+  if (rc) return rc;
+  ARG_CHECK(d_cam && d_cam_pair && d_points && d_point_views && d_point_status && d_summary);
   ARG_CHECK(min_views >= 2 && num_loops >= 0);
-  for (int i = 0; i < nimages; i++) ARG_CHECK(intrinsics_usable(intrinsics + 4 * (size_t)i, 1));
   RoctxRange range(__func__);
   return run_batch(ctx, {{intrinsics, sizeof(float) * 4 * (size_t)nimages}}, 0, [&](int *h_lists, void *) {
-    return launch_triangulate_tracks_batch(ctx, max_tracks, max_obs, d_track_offsets, d_obs, d_export_summary, nimages,
-                                           d_cam, d_cam_pair, reinterpret_cast<const float *>(h_lists), min_views,
-                                           num_loops, d_points, d_point_views, d_point_status, d_obs_error, d_summary);
+    S.intrinsics = reinterpret_cast<const float *>(h_lists);
+    return launch_triangulate_tracks_batch(ctx, S, min_views, num_loops, d_points, d_point_views, d_point_status,
+                                           d_obs_error, d_summary);
   });
 }
 
@@ -2625,29 +2660,28 @@ extern "C" int misift_refine_cameras_batch(misift_ctx *ctx, int max_tracks, int 
                                            int orthonormalise, float *d_cam_out, int *d_cam_obs, float *d_cam_rms,
                                            int *d_cam_steps, int *d_cam_status, int *d_summary)
 {
-  ARG_CHECK(ctx && max_tracks >= 1 && max_obs >= 1 && nimages >= 1);
-  ARG_CHECK(d_track_offsets && d_obs && d_export_summary && d_points && d_point_status && d_cam && d_cam_pair);
-  ARG_CHECK(intrinsics && d_cam_out && d_cam_obs && d_cam_rms && d_cam_steps && d_cam_status && d_summary);
-  ARG_CHECK(((uintptr_t)d_obs & 15) == 0);
+  ARG_CHECK(ctx != nullptr);
+  TrackScene S;
+  int rc = check_scene(__func__, &S, max_tracks, max_obs, d_track_offsets, d_obs, d_export_summary, d_points,
+                       d_point_status, nimages, d_cam, d_cam_pair, intrinsics);
+  if (rc) return rc;
+  ARG_CHECK(d_points && d_point_status && d_cam && d_cam_pair);
+  ARG_CHECK(d_cam_out && d_cam_obs && d_cam_rms && d_cam_steps && d_cam_status && d_summary);
   ARG_CHECK(min_obs >= 3 && num_loops >= 0);
   ARG_CHECK(max_error > 0.0f);                                              // NaN fails too
   ARG_CHECK(orthonormalise == 0 || orthonormalise == 1);
   ARG_CHECK(nhold >= 0 && (nhold == 0 || hold));
   for (int j = 0; j < nhold; j++) ARG_CHECK(hold[j] >= 0 && hold[j] < nimages);
-  for (int i = 0; i < nimages; i++) ARG_CHECK(intrinsics_usable(intrinsics + 4 * (size_t)i, 1));
-  const uintptr_t in = (uintptr_t)d_cam, out = (uintptr_t)d_cam_out, span = sizeof(float) * 12 * (size_t)nimages;
-  ARG_CHECK(in == out || in + span <= out || out + span <= in);
-  std::vector<int> held(nimages, 0);
-  for (int j = 0; j < nhold; j++) held[hold[j]] = 1;
+  ARG_CHECK(same_or_disjoint(d_cam, d_cam_out, sizeof(float) * 12 * (size_t)nimages));
+  const std::vector<int> held = held_flags(nimages, nhold, hold);
   const float thresh2 = max_error * max_error;                              // rounded once, here
   RoctxRange range(__func__);
   return run_batch(ctx, {{intrinsics, sizeof(float) * 4 * (size_t)nimages}, {held.data(), sizeof(int) * (size_t)nimages}},
                    0, [&](int *h_lists, void *) {
-                     return launch_refine_cameras_batch(ctx, max_tracks, max_obs, d_track_offsets, d_obs,
-                                                        d_export_summary, d_points, d_point_status, nimages, d_cam,
-                                                        d_cam_pair, h_lists, min_obs, num_loops, thresh2, orthonormalise,
-                                                        d_cam_out, d_cam_obs, d_cam_rms, d_cam_steps, d_cam_status,
-                                                        d_summary);
+                     S.intrinsics = reinterpret_cast<const float *>(h_lists);
+                     return launch_refine_cameras_batch(ctx, S, h_lists + 4 * (size_t)nimages, min_obs, num_loops, thresh2,
+                                                        orthonormalise, d_cam_out, d_cam_obs, d_cam_rms, d_cam_steps,
+                                                        d_cam_status, d_summary);
                    });
 }
 
@@ -2662,18 +2696,20 @@ extern "C" int misift_resect_cameras_batch(misift_ctx *ctx, int max_tracks, int 
                                            int install, float *d_cam, int *d_cam_pair, float *d_res_cam, int *d_res_cand,
                                            int *d_res_inliers, int *d_res_status, int *d_summary)
 {
-  ARG_CHECK(ctx && max_tracks >= 1 && max_obs >= 1 && nimages >= 1);
-  ARG_CHECK(d_track_offsets && d_obs && d_export_summary && d_points && d_point_status && intrinsics);
+  ARG_CHECK(ctx != nullptr);
+  TrackScene S;
+  int rc = check_scene(__func__, &S, max_tracks, max_obs, d_track_offsets, d_obs, d_export_summary, d_points,
+                       d_point_status, nimages, d_cam, d_cam_pair, intrinsics);
+  if (rc) return rc;
+  ARG_CHECK(d_points && d_point_status);
   ARG_CHECK(d_res_cam && d_res_cand && d_res_inliers && d_res_status && d_summary);
-  ARG_CHECK(((uintptr_t)d_obs & 15) == 0);
   ARG_CHECK(nsel >= 0 && (nsel == 0 || (images && seeds)));
   ARG_CHECK(max_cand >= 6 && num_loops >= 1 && min_inliers >= 6);
   ARG_CHECK(thresh > 0.0f);                                                 // NaN fails too
   ARG_CHECK((only_unset == 0 || only_unset == 1) && (install == 0 || install == 1));
   ARG_CHECK(d_cam_pair || !(only_unset || install));
   ARG_CHECK(d_cam || !install);
-  for (int i = 0; i < nimages; i++) ARG_CHECK(intrinsics_usable(intrinsics + 4 * (size_t)i, 1));
-  int rc = check_frames(__func__, nsel, images, 1, nimages, 0);
+  rc = check_frames(__func__, nsel, images, 1, nimages, 0);
   if (rc) return rc;
   ARG_CHECK(resect_cameras_batch_one_launch(max_obs, nsel, max_cand, num_loops));
   const float thresh2 = thresh * thresh;                                    // rounded once, here
@@ -2681,11 +2717,13 @@ extern "C" int misift_resect_cameras_batch(misift_ctx *ctx, int max_tracks, int 
   return run_batch(ctx, {{intrinsics, sizeof(float) * 4 * (size_t)nimages}, {images, sizeof(int) * (size_t)nsel},
                          {seeds, sizeof(unsigned) * (size_t)nsel}},
                    0, [&](int *h_lists, void *) {
-                     return launch_resect_cameras_batch(ctx, max_tracks, max_obs, d_track_offsets, d_obs,
-                                                        d_export_summary, d_points, d_point_status, nimages, nsel,
-                                                        h_lists, max_cand, num_loops, thresh2, min_inliers, only_unset,
-                                                        install, d_cam, d_cam_pair, d_res_cam, d_res_cand, d_res_inliers,
-                                                        d_res_status, d_summary);
+                     S.intrinsics = reinterpret_cast<const float *>(h_lists);
+                     const int *h_images = h_lists + 4 * (size_t)nimages;
+                     return launch_resect_cameras_batch(ctx, S, nsel, h_images,
+                                                        reinterpret_cast<const unsigned *>(h_images + nsel), max_cand,
+                                                        num_loops, thresh2, min_inliers, only_unset, install, d_cam,
+                                                        d_cam_pair, d_res_cam, d_res_cand, d_res_inliers, d_res_status,
+                                                        d_summary);
                    });
 }
 
@@ -2702,11 +2740,14 @@ extern "C" int misift_adjust_bundle_robust_batch(misift_ctx *ctx, int max_tracks
                                                  int *d_cam_obs, int *d_cam_status, float *d_cam_rms, int *d_point_obs,
                                                  float *d_history, float *d_cost, float *d_obs_weight, int *d_summary)
 {
-  ARG_CHECK(ctx && max_tracks >= 1 && max_obs >= 1 && nimages >= 1);
-  ARG_CHECK(d_track_offsets && d_obs && d_export_summary && d_points && d_point_status && d_cam && d_cam_pair);
-  ARG_CHECK(intrinsics && d_cam_out && d_points_out && d_cam_obs && d_cam_status && d_cam_rms && d_point_obs);
+  ARG_CHECK(ctx != nullptr);
+  TrackScene S;
+  int rc = check_scene(__func__, &S, max_tracks, max_obs, d_track_offsets, d_obs, d_export_summary, d_points,
+                       d_point_status, nimages, d_cam, d_cam_pair, intrinsics);
+  if (rc) return rc;
+  ARG_CHECK(d_points && d_point_status && d_cam && d_cam_pair);
+  ARG_CHECK(d_cam_out && d_points_out && d_cam_obs && d_cam_status && d_cam_rms && d_point_obs);
   ARG_CHECK(d_cost && d_summary && (d_history || num_loops == 0));
-  ARG_CHECK(((uintptr_t)d_obs & 15) == 0);
   ARG_CHECK(min_views >= 2 && min_obs >= 3 && num_loops >= 0 && cg_iters >= 0);
   ARG_CHECK(max_error > 0.0f);                                              // NaN fails too
   ARG_CHECK(lambda0 > 0.0f && lambda0 <= 3.402823466e+38f);
@@ -2715,27 +2756,18 @@ extern "C" int misift_adjust_bundle_robust_batch(misift_ctx *ctx, int max_tracks
   if (loss != MISIFT_LOSS_NONE) ARG_CHECK(loss_scale > 0.0f && loss_scale <= 3.402823466e+38f);   // not read with loss 0
   ARG_CHECK(nhold >= 0 && (nhold == 0 || hold));
   for (int j = 0; j < nhold; j++) ARG_CHECK(hold[j] >= 0 && hold[j] < nimages);
-  for (int i = 0; i < nimages; i++) ARG_CHECK(intrinsics_usable(intrinsics + 4 * (size_t)i, 1));
-  {
-    const uintptr_t in = (uintptr_t)d_cam, out = (uintptr_t)d_cam_out, span = sizeof(float) * 12 * (size_t)nimages;
-    ARG_CHECK(in == out || in + span <= out || out + span <= in);
-  }
-  {
-    const uintptr_t in = (uintptr_t)d_points, out = (uintptr_t)d_points_out, span = sizeof(float) * 4 * (size_t)max_tracks;
-    ARG_CHECK(in == out || in + span <= out || out + span <= in);
-  }
-  std::vector<int> held(nimages, 0);
-  for (int j = 0; j < nhold; j++) held[hold[j]] = 1;
+  ARG_CHECK(same_or_disjoint(d_cam, d_cam_out, sizeof(float) * 12 * (size_t)nimages));
+  ARG_CHECK(same_or_disjoint(d_points, d_points_out, sizeof(float) * 4 * (size_t)max_tracks));
+  const std::vector<int> held = held_flags(nimages, nhold, hold);
   const float thresh2 = max_error * max_error;                              // rounded once, here
   const float c = loss != MISIFT_LOSS_NONE ? loss_scale : 0.0f;
   const float c2 = c * c;                                                   // and so is this
   RoctxRange range(__func__);
   return run_batch(ctx, {{intrinsics, sizeof(float) * 4 * (size_t)nimages}, {held.data(), sizeof(int) * (size_t)nimages}},
                    0, [&](int *h_lists, void *) {
-                     return launch_adjust_bundle_batch(ctx, max_tracks, max_obs, d_track_offsets, d_obs,
-                                                       d_export_summary, d_points, d_point_status, nimages, d_cam,
-                                                       d_cam_pair, h_lists, min_views, min_obs, num_loops, cg_iters,
-                                                       thresh2, lambda0, orthonormalise, loss, c, c2, d_cam_out,
+                     S.intrinsics = reinterpret_cast<const float *>(h_lists);
+                     return launch_adjust_bundle_batch(ctx, S, h_lists + 4 * (size_t)nimages, min_views, min_obs, num_loops,
+                                                       cg_iters, thresh2, lambda0, orthonormalise, loss, c, c2, d_cam_out,
                                                        d_points_out, d_cam_obs, d_cam_status, d_cam_rms, d_point_obs,
                                                        d_history, d_cost, d_obs_weight, d_summary);
                    });
@@ -2770,15 +2802,18 @@ extern "C" int misift_filter_tracks_batch(misift_ctx *ctx, int max_tracks, int m
                                           int *d_export_summary_out, float *d_points_out, int *d_point_views_out,
                                           int *d_point_status_out, int *d_track_map, int *d_obs_map, int *d_summary)
 {
-  ARG_CHECK(ctx && max_tracks >= 1 && max_obs >= 1 && nimages >= 1);
-  ARG_CHECK(d_track_offsets && d_obs && d_export_summary && d_points && d_point_status && d_cam && d_cam_pair);
-  ARG_CHECK(intrinsics && d_track_offsets_out && d_obs_out && d_export_summary_out && d_points_out);
+  ARG_CHECK(ctx != nullptr);
+  TrackScene S;
+  int rc = check_scene(__func__, &S, max_tracks, max_obs, d_track_offsets, d_obs, d_export_summary, d_points,
+                       d_point_status, nimages, d_cam, d_cam_pair, intrinsics);
+  if (rc) return rc;
+  ARG_CHECK(d_points && d_point_status && d_cam && d_cam_pair);
+  ARG_CHECK(d_track_offsets_out && d_obs_out && d_export_summary_out && d_points_out);
   ARG_CHECK(d_point_views_out && d_point_status_out && d_track_map && d_summary);
-  ARG_CHECK(((uintptr_t)d_obs & 15) == 0 && ((uintptr_t)d_obs_out & 15) == 0);
+  ARG_CHECK(((uintptr_t)d_obs_out & 15) == 0);
   ARG_CHECK(min_views >= 2 && (unique_frames == 0 || unique_frames == 1));
   ARG_CHECK(max_error > 0.0f);                                              // NaN fails too
   ARG_CHECK(max_cos == max_cos);
-  for (int i = 0; i < nimages; i++) ARG_CHECK(intrinsics_usable(intrinsics + 4 * (size_t)i, 1));
   {
     // compaction moves entries across workgroups: no output may share a byte with an input or with another output
     const size_t mt = (size_t)max_tracks, mo = (size_t)max_obs, n = (size_t)nimages;
@@ -2798,11 +2833,10 @@ extern "C" int misift_filter_tracks_batch(misift_ctx *ctx, int max_tracks, int m
   const float thresh2 = max_error * max_error;                              // rounded once, here
   RoctxRange range(__func__);
   return run_batch(ctx, {{intrinsics, sizeof(float) * 4 * (size_t)nimages}}, 0, [&](int *h_lists, void *) {
-    return launch_filter_tracks_batch(ctx, max_tracks, max_obs, d_track_offsets, d_obs, d_export_summary, d_points,
-                                      d_point_status, nimages, d_cam, d_cam_pair,
-                                      reinterpret_cast<const float *>(h_lists), thresh2, max_cos, min_views,
-                                      unique_frames, d_track_offsets_out, d_obs_out, d_export_summary_out, d_points_out,
-                                      d_point_views_out, d_point_status_out, d_track_map, d_obs_map, d_summary);
+    S.intrinsics = reinterpret_cast<const float *>(h_lists);
+    return launch_filter_tracks_batch(ctx, S, thresh2, max_cos, min_views, unique_frames, d_track_offsets_out, d_obs_out,
+                                      d_export_summary_out, d_points_out, d_point_views_out, d_point_status_out,
+                                      d_track_map, d_obs_map, d_summary);
   });
 }
 

@@ -9,12 +9,53 @@
 //
 // A function here reads the cameras through a `Cams` (cam(i): the twelve floats of image i, k(i): its fx fy cx cy,
 // set(i): whether it has a camera whose floats are all finite), so the kernel can hand in its LDS copy or the global
-// arrays and the hook plain host arrays; an `Obs` has frame, xpos and ypos.
+// arrays and the hook plain host arrays.
+//
+// The scene that the five track-chain calls share (triangulate, refine, resect, adjust, filter) is stated here once:
+// TrackObs and how it is loaded, TrackScene with T and O, and, at the end of the file, the candidate rule of
+// include/misift.h (misift_refine_cameras_batch) as the two functions that the candidate kernels
+// (kernels_track_candidates.hip) and the host hooks both run.
 #pragma once
 #include <math.h>
 #include "posegraph_core.hpp"
 
 enum { TRI_OK = 0, TRI_FEW_VIEWS = 1, TRI_SINGULAR = 2, TRI_BEHIND = 3, TRI_BAD_RANGE = 4 };
+
+// misift_track_obs (the static_assert is in common.hpp, which sees both).  The type is as aligned as its
+// fields: a host hook reads the caller's array where it lies.
+struct TrackObs {
+  int frame, record;
+  float xpos, ypos;
+};
+
+// One observation.  On the device it is one 16-byte load: every entry point rejects a d_obs that is not 16-byte aligned
+// (check_scene, misift_host.hip), and this is the one place that relies on it.
+FUND_HD TrackObs track_obs_load(const TrackObs *p)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+  return *static_cast<const TrackObs *>(__builtin_assume_aligned(p, 16));
+#else
+  return *p;
+#endif
+}
+
+// what the five calls are given: the lists of misift_export_tracks_batch, the points of triangulate (NULL in triangulate
+// itself) and the cameras
+struct TrackScene {
+  int max_tracks, max_obs, nimages;
+  const int *track_offsets;
+  const TrackObs *obs;
+  const int *export_summary;
+  const float *points;                         // max_tracks x 4
+  const int *point_status;
+  const float *cam;                            // nimages x 12
+  const int *cam_pair;
+  const float *intrinsics;                     // nimages x 4
+};
+
+FUND_HD int scene_clamp(int v, int hi) { const int lo = v > 0 ? v : 0; return lo < hi ? lo : hi; }   // min(max(v, 0), hi)
+FUND_HD int scene_T(const TrackScene &S) { return scene_clamp(S.export_summary[2], S.max_tracks); }
+FUND_HD int scene_O(const TrackScene &S) { return scene_clamp(S.export_summary[3], S.max_obs); }
 
 // the cameras as misift_link_poses_batch leaves them and the intrinsics as the caller lists them
 struct TriCamsPlain {
@@ -70,8 +111,8 @@ FUND_HD bool tri_solve(const TriNormal &N, float (&x)[3])
 }
 
 // step 1: observation o is a usable view
-template <class Cams, class Obs>
-FUND_HD bool tri_usable(const Cams &C, int nimages, const Obs &o)
+template <class Cams>
+FUND_HD bool tri_usable(const Cams &C, int nimages, const TrackObs &o)
 {
   const int f = o.frame;
   if (!(f >= 0 && f < nimages)) return false;  // before it addresses anything
@@ -107,16 +148,16 @@ FUND_HD bool tri_view(const float *c, const float *k, float x, float y, const fl
 }
 
 // step 3 over a track: false when a used view is not in front
-template <class Cams, class Obs>
-FUND_HD bool tri_residuals(const Cams &C, int nimages, const Obs *obs, int n, const float (&X)[3], float &cost,
+template <class Cams>
+FUND_HD bool tri_residuals(const Cams &C, int nimages, const TrackObs *obs, int n, const float (&X)[3], float &cost,
                            TriNormal &N)
 {
   cost = 0.0f;
   tri_clear(N);
-  Obs next = n > 0 ? obs[0] : Obs{};
+  TrackObs next = n > 0 ? track_obs_load(obs) : TrackObs{};
   for (int k = 0; k < n; k++) {
-    const Obs o = next;
-    if (k + 1 < n) next = obs[k + 1];          // the next load is under way while this view is worked on
+    const TrackObs o = next;
+    if (k + 1 < n) next = track_obs_load(obs + k + 1);          // the next load is under way while this view is worked on
     if (!tri_usable(C, nimages, o)) continue;
     float ru, rv;
     if (!tri_view(C.cam(o.frame), C.k(o.frame), o.xpos, o.ypos, X, ru, rv, true, cost, N)) return false;
@@ -126,8 +167,8 @@ FUND_HD bool tri_residuals(const Cams &C, int nimages, const Obs *obs, int n, co
 
 // Steps 1-5 for one track of n >= 0 observations: the status; point4, *views and, when not NULL, obs_error[0 .. n) as the
 // call writes them; *accepted = the Gauss-Newton steps kept.
-template <class Cams, class Obs>
-FUND_HD int tri_track(const Cams &C, int nimages, const Obs *obs, int n, int min_views, int num_loops, float *point4,
+template <class Cams>
+FUND_HD int tri_track(const Cams &C, int nimages, const TrackObs *obs, int n, int min_views, int num_loops, float *point4,
                       int *views, float *obs_error, int *accepted)
 {
   const float nan = pose_one_nan(NAN);
@@ -135,10 +176,10 @@ FUND_HD int tri_track(const Cams &C, int nimages, const Obs *obs, int n, int min
   float X[3] = {0.0f, 0.0f, 0.0f}, cost = 0.0f;
   TriNormal N;
   tri_clear(N);
-  Obs next = n > 0 ? obs[0] : Obs{};
+  TrackObs next = n > 0 ? track_obs_load(obs) : TrackObs{};
   for (int k = 0; k < n; k++) {
-    const Obs o = next;
-    if (k + 1 < n) next = obs[k + 1];
+    const TrackObs o = next;
+    if (k + 1 < n) next = track_obs_load(obs + k + 1);
     if (!tri_usable(C, nimages, o)) continue;
     m++;
     tri_linear_rows(C.cam(o.frame), C.k(o.frame), o.xpos, o.ypos, N);
@@ -169,11 +210,11 @@ FUND_HD int tri_track(const Cams &C, int nimages, const Obs *obs, int n, int min
     point4[0] = point4[1] = point4[2] = point4[3] = nan;
   }
   if (obs_error) {
-    if (n > 0) next = obs[0];
+    if (n > 0) next = track_obs_load(obs);
     for (int k = 0; k < n; k++) {
       float e = nan;
-      const Obs o = next;
-      if (k + 1 < n) next = obs[k + 1];
+      const TrackObs o = next;
+      if (k + 1 < n) next = track_obs_load(obs + k + 1);
       if (status == TRI_OK) {
         float ru, rv;
         if (tri_usable(C, nimages, o) &&
@@ -188,3 +229,32 @@ FUND_HD int tri_track(const Cams &C, int nimages, const Obs *obs, int n, int min
 
 // the track's range in d_obs, from device memory: checked before it addresses anything
 FUND_HD bool tri_range_ok(int off, int end, int max_obs) { return 0 <= off && off <= end && end <= max_obs; }
+
+// ---- the candidate rule, for the kernels and the host hooks alike
+
+// what track t < T does to owner[] (-1 everywhere before): a slot ends with the largest valid track that holds it
+FUND_HD void scene_track_owns(const TrackScene &S, int *owner, int t)
+{
+  const int off = S.track_offsets[t], end = S.track_offsets[t + 1];
+  if (!tri_range_ok(off, end, scene_O(S))) return;           // before it addresses anything
+  for (int o = off; o < end; o++) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    atomicMax(&owner[o], t);
+#else
+    if (t > owner[o]) owner[o] = t;
+#endif
+  }
+}
+
+// the image slot o < O is a candidate of: its frame when its owner has status 0 and a finite point, its position is
+// finite and its frame lies in [0, nimages); otherwise -1
+FUND_HD int scene_slot_key(const TrackScene &S, const int *owner, int o)
+{
+  const int t = owner[o];
+  if (t < 0 || S.point_status[t] != TRI_OK) return -1;
+  const float *X = S.points + 4 * (size_t)t;
+  const TrackObs ob = track_obs_load(S.obs + o);
+  const bool ok = fundamental_finite(X[0]) && fundamental_finite(X[1]) && fundamental_finite(X[2]) &&
+                  fundamental_finite(ob.xpos) && fundamental_finite(ob.ypos) && ob.frame >= 0 && ob.frame < S.nimages;
+  return ok ? ob.frame : -1;
+}
