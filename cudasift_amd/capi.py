@@ -26,6 +26,8 @@ assert POINT_DTYPE.itemsize == 576
 TRACK_OBS_DTYPE = np.dtype([("frame", "<i4"), ("record", "<i4"), ("xpos", "<f4"), ("ypos", "<f4")])
 CAM_UNSET, CAM_ROOT, CAM_RESECTED = -2, -1, -3                 # cam_pair values that are no pair index
 LOSS_NONE, LOSS_HUBER, LOSS_GEMAN_MCCLURE = 0, 1, 2            # MISIFT_LOSS_*: adjust_bundle_robust_batch
+MAX_FOCAL_GROUPS = 8                                           # MISIFT_MAX_FOCAL_GROUPS: adjust_bundle_focal_batch
+FOCAL_REFINED, FOCAL_NO_MEMBER, FOCAL_NOT_REFINED = 0, 1, 2    # MISIFT_FOCAL_*: d_focal[3g + 2]
 assert TRACK_OBS_DTYPE.itemsize == 16
 
 
@@ -135,6 +137,12 @@ SIGNATURES = {
                                                _i, _f, _f, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "misift_test_adjust_bundle_robust": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i,
                                               _f, _f, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "misift_adjust_bundle_focal_batch": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _i,
+                                              _i, _f, _f, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                              _vp, _vp, _vp]),
+    "misift_test_adjust_bundle_focal": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i,
+                                             _f, _f, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                             _vp, _vp]),
     "misift_test_adjust_bundle": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _f, _f,
                                        _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "misift_filter_tracks_batch": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _f, _f, _i, _i, _vp, _vp,
@@ -1130,6 +1138,64 @@ class Context:
             _dptr(cost), _dptr(obs_weight) if obs_weight is not None else None, _dptr(summary)),
             "misift_adjust_bundle_robust_batch")
         return cam_out, points_out, cam_obs, cam_status, cam_rms, point_obs, history, cost, obs_weight, summary
+
+    def adjust_bundle_focal_batch(self, max_tracks, max_obs, track_offsets, obs, export_summary, points, point_status,
+                                  nimages, cam, cam_pair, intrinsics, group, ngroups=None, hold=(), min_views=2,
+                                  min_obs=6, num_loops=5, cg_iters=10, max_error=np.inf, lambda0=1e-3,
+                                  orthonormalise=True, loss=LOSS_NONE, loss_scale=2.0, cam_out=None, points_out=None,
+                                  cam_obs=None, cam_status=None, cam_rms=None, point_obs=None, history=None, cost=None,
+                                  obs_weight=None, summary=None, intrinsics_out=None, focal=None):
+        """misift_adjust_bundle_focal_batch: adjust_bundle_robust_batch with one focal scale per physical camera among
+        the unknowns.  group (host, nimages ints) names the camera that took each image, -1 for an image whose
+        intrinsics stay as given; ngroups (at most MAX_FOCAL_GROUPS) defaults to max(group) + 1.  The further arguments
+        and the ten outputs are those of adjust_bundle_robust_batch (obs_weight: None or False leaves it out, True
+        allocates it); intrinsics_out (nimages x 4 floats: fx*s, fy*s, cx, cy under the final scales, to be read back
+        and handed to the next call of the chain) and focal (ngroups x 3 words: the scale, the members, FOCAL_*) are
+        device buffers, allocated here when not passed; returns the twelve.  Enqueued on the context stream."""
+        group = np.ascontiguousarray(group, np.int32).reshape(-1)
+        if ngroups is None:
+            ngroups = int(group.max()) + 1 if len(group) else 0
+        assert ngroups == 0 or len(group) == nimages
+        if intrinsics_out is None:
+            intrinsics_out = self.zeros(16 * max(nimages, 1))
+        if focal is None:
+            focal = self.zeros(12 * max(int(ngroups), 1))
+        if obs_weight is True:
+            obs_weight = self.zeros(4 * max(max_obs, 1))
+        elif obs_weight is False:
+            obs_weight = None
+        intrinsics = np.ascontiguousarray(intrinsics, np.float32).reshape(-1, 4)
+        assert len(intrinsics) == nimages
+        hold = np.ascontiguousarray(hold, np.int32).reshape(-1)
+        if cam_out is None:
+            cam_out = self.zeros(48 * max(nimages, 1))
+        if points_out is None:
+            points_out = self.zeros(16 * max(max_tracks, 1))
+        if cam_obs is None:
+            cam_obs = self.zeros(4 * max(nimages, 1))
+        if cam_status is None:
+            cam_status = self.zeros(4 * max(nimages, 1))
+        if cam_rms is None:
+            cam_rms = self.zeros(8 * max(nimages, 1))
+        if point_obs is None:
+            point_obs = self.zeros(4 * max(max_tracks, 1))
+        if history is None:
+            history = self.zeros(16 * max(int(num_loops), 1))
+        if cost is None:
+            cost = self.zeros(8)
+        if summary is None:
+            summary = self.zeros(4 * 8)
+        check(lib().misift_adjust_bundle_focal_batch(
+            self.h, max_tracks, max_obs, _dptr(track_offsets), _dptr(obs), _dptr(export_summary), _dptr(points),
+            _dptr(point_status), nimages, _dptr(cam), _dptr(cam_pair), intrinsics.ctypes.data, len(hold),
+            hold.ctypes.data if len(hold) else None, int(min_views), int(min_obs), int(num_loops), int(cg_iters),
+            float(max_error), float(lambda0), int(orthonormalise), int(loss), float(loss_scale), int(ngroups),
+            group.ctypes.data if len(group) else None, _dptr(cam_out), _dptr(points_out), _dptr(cam_obs),
+            _dptr(cam_status), _dptr(cam_rms), _dptr(point_obs), _dptr(history), _dptr(cost),
+            _dptr(obs_weight) if obs_weight is not None else None, _dptr(summary), _dptr(intrinsics_out), _dptr(focal)),
+            "misift_adjust_bundle_focal_batch")
+        return (cam_out, points_out, cam_obs, cam_status, cam_rms, point_obs, history, cost, obs_weight, summary,
+                intrinsics_out, focal)
 
     def filter_tracks_batch(self, max_tracks, max_obs, track_offsets, obs, export_summary, points, point_status,
                             nimages, cam, cam_pair, intrinsics, max_error=np.inf, max_cos=np.inf, min_angle_deg=None,

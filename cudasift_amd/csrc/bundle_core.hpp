@@ -6,7 +6,10 @@
 // is in include/misift.h.  misift_adjust_bundle_robust_batch is the same call with a loss: bundle_loss gives rho, w and
 // sqrt(w) of a member's squared residual, step 1 scales the member's 20 values by sqrt(w) where it writes them, the cost
 // pass stores rho in place of the squared residual, and every phase downstream reads what those two wrote.  ROBUST is a
-// template argument of the two, so the plain call compiles to what it was.
+// template argument of the two, so the plain call compiles to what it was.  misift_adjust_bundle_focal_batch adds one
+// focal scale per camera group: FOCAL is a template argument (or a function of its own, *_focal) of every phase that
+// reads the scale, the focal Jacobian of a slot lives in an array of its own beside the 20 values, and the groups'
+// scalars are carried by the scalar workgroup beside the images' 6-vectors.
 //
 // The rules of refine_core.hpp hold: fp32 with every operation rounded, only + - * / sqrtf and fabsf, no fmaf, and the
 // build's -ffp-contract=off.  A per-track sum is taken by one work item in ascending slot.  A per-image or cross-image
@@ -26,6 +29,10 @@ constexpr int BUNDLE_LIN = 20;                 // per slot: Ju_c (6), Jv_c (6), 
 constexpr int BUNDLE_NORMAL = 33;              // per image: U (21, row-major upper triangle), gc (6), sum of W y (6)
 constexpr float BUNDLE_LAMBDA_FLOOR = 1e-7f;   // below it 1 + lambda is 1 in fp32
 enum { BUNDLE_LOSS_NONE = 0, BUNDLE_LOSS_HUBER = 1, BUNDLE_LOSS_GEMAN_MCCLURE = 2 };   // MISIFT_LOSS_*
+constexpr int BUNDLE_MAX_GROUPS = 8;           // MISIFT_MAX_FOCAL_GROUPS
+constexpr int BUNDLE_IMAGE_FOCAL = 9;          // per image with a group: U_cf (6), Uff, gf, the sum of wf . y_t
+constexpr int BUNDLE_NORMAL_FOCAL = BUNDLE_NORMAL + BUNDLE_IMAGE_FOCAL;
+enum { BUNDLE_FOCAL_REFINED = 0, BUNDLE_FOCAL_NO_MEMBER = 1, BUNDLE_FOCAL_NOT_REFINED = 2 };   // MISIFT_FOCAL_*
 
 struct BundleData {
   TrackScene s;                                // the call's inputs
@@ -53,6 +60,19 @@ struct BundleData {
   float *cam_out, *points_out, *cam_rms, *history, *cost;
   int *cam_obs, *cam_status, *point_obs, *summary;
   float *obs_weight;                           // max_obs, or NULL
+  // misift_adjust_bundle_focal_batch only (the FOCAL instances): one focal scale per camera group
+  int ngroups;
+  const int *grp;                              // nimages: the group of the image, or -1
+  int *fcount;                                 // BUNDLE_MAX_GROUPS: the members in the group's images
+  float *fs;                                   // 2 x BUNDLE_MAX_GROUPS: s_g in the two state buffers
+  float *fvec;                                 // 5 x BUNDLE_MAX_GROUPS: x, r, z, p, y of the groups
+  float *fsc;                                  // 2 x BUNDLE_MAX_GROUPS: l1 * U_gg, then S_gg
+  float *flin;                                 // max_obs x 2: Juf, Jvf of a slot
+  float *tfd;                                  // max_tracks x BUNDLE_MAX_GROUPS: w_gt . SOLVE(V'_t, w_gt)
+  float *iuf;                                  // nimages x BUNDLE_IMAGE_FOCAL: U_cf (6), then the sums of Uff, gf, wf . y_t
+  float *ifv;                                  // nimages x 2 per CG iteration: U_cf . p_i, the sum of wf . q_t
+  float *intrinsics_out;                       // nimages x 4
+  int *focal_out;                              // ngroups x 3 words: s_g, the members, the status
 };
 
 FUND_HD void bundle_raise(int *flag)
@@ -177,6 +197,25 @@ FUND_HD bool bundle_linearise(const float (&c)[12], const float *k, const float 
   return true;
 }
 
+// FOCAL: the intrinsics a member of image k is projected with under state buffer b: fx*s_g, fy*s_g, cx, cy, each
+// product rounded (s = 1 for an image without a group); otherwise the intrinsics as given
+template <bool FOCAL>
+FUND_HD const float *bundle_intrinsics(const BundleData &D, int b, int k, float (&kk)[4])
+{
+  const float *given = D.s.intrinsics + 4 * (size_t)k;
+  if (!FOCAL) return given;
+  const int g = D.grp[k];
+  const float s = g >= 0 ? D.fs[b * BUNDLE_MAX_GROUPS + g] : 1.0f;
+  kk[0] = given[0] * s; kk[1] = given[1] * s; kk[2] = given[2]; kk[3] = given[3];
+  return kk;
+}
+// wf[q] = Juf*Pu[q] + Jvf*Pv[q] of slot o, and wf . v
+FUND_HD float bundle_wf(const float *l, const float *f, int q) { return f[0] * l[12 + q] + f[1] * l[15 + q]; }
+FUND_HD float bundle_wf3(const float *l, const float *f, const float *v)
+{
+  return (bundle_wf(l, f, 0) * v[0] + bundle_wf(l, f, 1) * v[1]) + bundle_wf(l, f, 2) * v[2];
+}
+
 // W[r][q] = Ju_c[r]*Ju_p[q] + Jv_c[r]*Jv_p[q]
 FUND_HD float bundle_w(const float *l, int r, int q) { return l[r] * l[12 + q] + l[6 + r] * l[15 + q]; }
 // (W v)[r] for a 3-vector v, (W^T v)[q] for a 6-vector v
@@ -216,21 +255,21 @@ FUND_HD BundleLoss bundle_loss(int loss, float c, float c2, float s)
 }
 
 // a member's squared residual, or its rho, under state buffer b (trial: the buffer the state is not in); one not in front raises BAD
-template <bool ROBUST>
+template <bool ROBUST, bool FOCAL = false>
 FUND_HD void bundle_eval_slot(const BundleData &D, int o, bool trial)
 {
   const int k = D.key[o];
   if (k < 0) return;
   if (trial && D.ctl[BUNDLE_FAIL]) return;
   const int b = trial ? 1 - D.ctl[BUNDLE_CUR] : D.ctl[BUNDLE_CUR];
-  float c[12];
+  float c[12], kk[4];
   bundle_load_cam(D.cams + 12 * ((size_t)b * D.s.nimages + k), c);
   const float *P = D.pts + 3 * ((size_t)b * D.s.max_tracks + D.owner[o]);
   const float X[3] = {P[0], P[1], P[2]};
   const TrackObs ob = track_obs_load(D.s.obs + o);
   RefineView v;
   float e = 0.0f;
-  if (refine_view(c, D.s.intrinsics + 4 * (size_t)k, X, ob.xpos, ob.ypos, v)) {
+  if (refine_view(c, bundle_intrinsics<FOCAL>(D, b, k, kk), X, ob.xpos, ob.ypos, v)) {
     e = v.ru * v.ru + v.rv * v.rv;
     if (ROBUST) e = bundle_loss(D.loss, D.loss_scale, D.loss_scale2, e).rho;
   } else {
@@ -289,6 +328,22 @@ FUND_HD void bundle_scalar_init(const BundleData &D, Sum &S, bool lead)
   D.fctl[BUNDLE_RHO] = 0.0f;
 }
 
+// FOCAL, in the scalar workgroup before any state is evaluated: s_g = 1 in both buffers, the members of every group
+template <class Sum>
+FUND_HD void bundle_focal_init(const BundleData &D, Sum &S, int lane, int lanes)
+{
+  for (int g = lane; g < BUNDLE_MAX_GROUPS; g += lanes) {
+    D.fcount[g] = 0;
+    D.fs[g] = D.fs[BUNDLE_MAX_GROUPS + g] = 1.0f;
+  }
+  S.fence();
+  for (int i = lane; i < D.s.nimages; i += lanes) {
+    const int g = D.grp[i];
+    if (g >= 0 && D.icount[i] > 0) bundle_count(&D.fcount[g], D.icount[i]);
+  }
+  S.fence();
+}
+
 // ---- one LM step
 
 // step 1 and 2 for an active track: its members linearised under the state (ROBUST: each of the 20 values times sw,
@@ -335,6 +390,89 @@ FUND_HD void bundle_track_normal(const BundleData &D, int t)
   q[0] = y[0]; q[1] = y[1]; q[2] = y[2];
 }
 
+// FOCAL: the groups' vector `which`; a group is live iff an image of it has a member
+FUND_HD float *bundle_fvec(const BundleData &D, int which) { return D.fvec + which * BUNDLE_MAX_GROUPS; }
+FUND_HD bool bundle_group_live(const BundleData &D, int g) { return D.fcount[g] > 0; }
+
+// FOCAL: bundle_track_normal with the focal Jacobian of every member beside the 20 values (Juf = fx*a, Jvf = fy*b with
+// the given fx, fy, times sw under a loss), and per group w_gt . SOLVE(V', w_gt) for the group's Schur scalar.  A function
+// of its own, so that the plain one compiles to what it was
+template <bool ROBUST>
+FUND_HD void bundle_track_normal_focal(const BundleData &D, int t)
+{
+  if (!bundle_active(D, t)) return;
+  const int b = D.ctl[BUNDLE_CUR];
+  const float lam1 = 1.0f + D.fctl[BUNDLE_LAM];
+  const float *P = D.pts + 3 * ((size_t)b * D.s.max_tracks + t);
+  const float X[3] = {P[0], P[1], P[2]};
+  TriNormal N;
+  tri_clear(N);
+  const int off = D.s.track_offsets[t], end = D.s.track_offsets[t + 1];
+  for (int o = off; o < end; o++) {
+    const int k = D.key[o];
+    if (D.owner[o] != t || k < 0) continue;
+    float c[12], l[BUNDLE_LIN], kk[4], f[2];
+    bundle_load_cam(D.cams + 12 * ((size_t)b * D.s.nimages + k), c);
+    const TrackObs ob = track_obs_load(D.s.obs + o);
+    const float *kp = bundle_intrinsics<true>(D, b, k, kk);
+    if (!bundle_linearise(c, kp, X, ob.xpos, ob.ypos, l)) {
+      bundle_raise(&D.ctl[BUNDLE_FAIL]);       // the state has every member in front: not reached
+#pragma unroll
+      for (int j = 0; j < BUNDLE_LIN; j++) l[j] = 0.0f;
+    }
+    RefineView view;                           // a, b of the same view once more: the same bits
+    const bool front = refine_view(c, kp, X, ob.xpos, ob.ypos, view);
+    f[0] = front ? D.s.intrinsics[4 * (size_t)k] * view.a : 0.0f;
+    f[1] = front ? D.s.intrinsics[4 * (size_t)k + 1] * view.b : 0.0f;
+    if (ROBUST) {
+      const float sw = bundle_loss(D.loss, D.loss_scale, D.loss_scale2, l[18] * l[18] + l[19] * l[19]).sw;
+#pragma unroll
+      for (int j = 0; j < BUNDLE_LIN; j++) l[j] = sw * l[j];
+      f[0] = sw * f[0];
+      f[1] = sw * f[1];
+    }
+    float *dst = D.lin + (size_t)BUNDLE_LIN * o;
+#pragma unroll
+    for (int j = 0; j < BUNDLE_LIN; j++) dst[j] = l[j];
+    D.flin[2 * (size_t)o] = f[0];
+    D.flin[2 * (size_t)o + 1] = f[1];
+    tri_accumulate(N, l[12], l[13], l[14], l[18]);
+    tri_accumulate(N, l[15], l[16], l[17], l[19]);
+  }
+  N.m00 = N.m00 * lam1; N.m11 = N.m11 * lam1; N.m22 = N.m22 * lam1;
+  float y[3];
+  if (!tri_solve(N, y)) bundle_raise(&D.ctl[BUNDLE_FAIL]);
+  float *v = D.tv + 9 * (size_t)t, *q = D.tq + 3 * (size_t)t;
+  v[0] = N.m00; v[1] = N.m01; v[2] = N.m02; v[3] = N.m11; v[4] = N.m12; v[5] = N.m22;
+  v[6] = N.g0; v[7] = N.g1; v[8] = N.g2;
+  q[0] = y[0]; q[1] = y[1]; q[2] = y[2];
+  // w_gt of every group in one more walk over the members: BUNDLE_MAX_GROUPS 3-vectors, every index a constant of the
+  // unrolled loop so that they stay in registers; a member adds to its own group's alone
+  float w[BUNDLE_MAX_GROUPS][3];
+#pragma unroll
+  for (int g = 0; g < BUNDLE_MAX_GROUPS; g++) w[g][0] = w[g][1] = w[g][2] = 0.0f;
+  for (int o = off; o < end; o++) {
+    const int k = D.key[o];
+    if (D.owner[o] != t || k < 0) continue;
+    const int mine = D.grp[k];
+    if (mine < 0) continue;
+    const float *l = D.lin + (size_t)BUNDLE_LIN * o, *f = D.flin + 2 * (size_t)o;
+    const float wf[3] = {bundle_wf(l, f, 0), bundle_wf(l, f, 1), bundle_wf(l, f, 2)};
+#pragma unroll
+    for (int g = 0; g < BUNDLE_MAX_GROUPS; g++)
+#pragma unroll
+      for (int j = 0; j < 3; j++) w[g][j] = mine == g ? w[g][j] + wf[j] : w[g][j];
+  }
+#pragma unroll
+  for (int g = 0; g < BUNDLE_MAX_GROUPS; g++) {
+    if (g >= D.ngroups || !bundle_group_live(D, g)) continue;
+    float x[3];
+    N.g0 = w[g][0]; N.g1 = w[g][1]; N.g2 = w[g][2];
+    tri_solve(N, x);                           // a failed solve gives zeros, and has failed the step above
+    D.tfd[(size_t)BUNDLE_MAX_GROUPS * t + g] = (w[g][0] * x[0] + w[g][1] * x[1]) + w[g][2] * x[2];
+  }
+}
+
 // V'^-1 rhs for track t; a failed solve gives zeros
 FUND_HD void bundle_track_solve(const BundleData &D, int t, const float (&rhs)[3], float (&x)[3])
 {
@@ -346,16 +484,29 @@ FUND_HD void bundle_track_solve(const BundleData &D, int t, const float (&rhs)[3
 }
 
 // sum over the track's members in free images, in ascending slot, of W^T v_image; v = the 6-vectors `which`
+// FOCAL: a member in an image of group g then adds wf * v_g, whatever the image's status
+template <bool FOCAL = false>
 FUND_HD void bundle_track_gather(const BundleData &D, int t, int which, float (&s)[3])
 {
   s[0] = s[1] = s[2] = 0.0f;
   const int off = D.s.track_offsets[t], end = D.s.track_offsets[t + 1];
   for (int o = off; o < end; o++) {
     const int k = D.key[o];
-    if (D.owner[o] != t || k < 0 || D.istate[k] != BUNDLE_ADJUSTED) continue;
-    const float *l = D.lin + (size_t)BUNDLE_LIN * o, *v = bundle_vec(D, which, k);
+    if (D.owner[o] != t || k < 0) continue;
+    const float *l = D.lin + (size_t)BUNDLE_LIN * o;
+    if (D.istate[k] == BUNDLE_ADJUSTED) {
+      const float *v = bundle_vec(D, which, k);
 #pragma unroll
-    for (int q = 0; q < 3; q++) s[q] = s[q] + bundle_wt6(l, q, v);
+      for (int q = 0; q < 3; q++) s[q] = s[q] + bundle_wt6(l, q, v);
+    }
+    if (FOCAL) {
+      const int g = D.grp[k];
+      if (g < 0) continue;
+      const float *f = D.flin + 2 * (size_t)o;
+      const float vg = D.fvec[which * BUNDLE_MAX_GROUPS + g];
+#pragma unroll
+      for (int q = 0; q < 3; q++) s[q] = s[q] + bundle_wf(l, f, q) * vg;
+    }
   }
 }
 
@@ -379,14 +530,37 @@ struct BundleNormalTerm {
     return true;
   }
 };
-template <class Sum>
-FUND_HD void bundle_image_normal(const BundleData &D, Sum &S, int i, bool lead)
+// FOCAL: the three focal sums of an image with a group (Uff, gf, wf . y_t), after the 33 and U_cf when it is free
+struct BundleFocalTerm {
+  const BundleData &D;
+  const int *list;
+  FUND_HD void focal(int o, float *x) const
+  {
+    const float *l = D.lin + (size_t)BUNDLE_LIN * o, *f = D.flin + 2 * (size_t)o, *y = D.tq + 3 * (size_t)D.owner[o];
+    x[0] = f[0] * f[0] + f[1] * f[1];
+    x[1] = f[0] * l[18] + f[1] * l[19];
+    x[2] = bundle_wf3(l, f, y);
+  }
+  FUND_HD bool operator()(int p, float (&x)[3]) const
+  {
+    focal(list[p], x);
+    return true;
+  }
+  FUND_HD bool operator()(int p, float (&x)[BUNDLE_NORMAL_FOCAL]) const
+  {
+    const int o = list[p];
+    BundleNormalTerm base{D, list};
+    base(p, reinterpret_cast<float(&)[BUNDLE_NORMAL]>(x));
+    const float *l = D.lin + (size_t)BUNDLE_LIN * o, *f = D.flin + 2 * (size_t)o;
+#pragma unroll
+    for (int r = 0; r < 6; r++) x[BUNDLE_NORMAL + r] = l[r] * f[0] + l[6 + r] * f[1];
+    focal(o, x + BUNDLE_NORMAL + 6);
+    return true;
+  }
+};
+// the lead thread's half of step 3: U', b from the 33 sums, the LDL^T checked
+FUND_HD void bundle_image_normal_finish(const BundleData &D, int i, const float *s)
 {
-  if (D.istate[i] != BUNDLE_ADJUSTED) return;
-  BundleNormalTerm term{D, D.list + D.istart[i]};
-  float s[BUNDLE_NORMAL];
-  S.template sum<BUNDLE_NORMAL>(D.icount[i], term, s);
-  if (!lead) return;
   const float lam1 = 1.0f + D.fctl[BUNDLE_LAM];
   float R[REFINE_SUMS], delta[6];
   R[0] = 0.0f;
@@ -405,6 +579,39 @@ FUND_HD void bundle_image_normal(const BundleData &D, Sum &S, int i, bool lead)
 #pragma unroll
   for (int r = 0; r < REFINE_SUMS; r++) dst[r] = R[r];
 }
+template <class Sum>
+FUND_HD void bundle_image_normal(const BundleData &D, Sum &S, int i, bool lead)
+{
+  if (D.istate[i] != BUNDLE_ADJUSTED) return;
+  BundleNormalTerm term{D, D.list + D.istart[i]};
+  float s[BUNDLE_NORMAL];
+  S.template sum<BUNDLE_NORMAL>(D.icount[i], term, s);
+  if (lead) bundle_image_normal_finish(D, i, s);
+}
+// FOCAL: a usable image with a group takes the three focal sums too, a free one among them the six of U_cf: 42 sums
+template <class Sum>
+FUND_HD void bundle_image_normal_focal(const BundleData &D, Sum &S, int i, bool lead)
+{
+  if (D.grp[i] < 0) return bundle_image_normal(D, S, i, lead);
+  if (D.istate[i] == BUNDLE_NO_CAMERA) return;
+  BundleFocalTerm term{D, D.list + D.istart[i]};
+  float *dst = D.iuf + (size_t)BUNDLE_IMAGE_FOCAL * i;
+  if (D.istate[i] != BUNDLE_ADJUSTED) {
+    float s[3];
+    S.template sum<3>(D.icount[i], term, s);
+    if (!lead) return;
+#pragma unroll
+    for (int r = 0; r < 6; r++) dst[r] = 0.0f;
+    dst[6] = s[0]; dst[7] = s[1]; dst[8] = s[2];
+    return;
+  }
+  float s[BUNDLE_NORMAL_FOCAL];
+  S.template sum<BUNDLE_NORMAL_FOCAL>(D.icount[i], term, s);
+  if (!lead) return;
+#pragma unroll
+  for (int r = 0; r < BUNDLE_IMAGE_FOCAL; r++) dst[r] = s[BUNDLE_NORMAL + r];
+  bundle_image_normal_finish(D, i, s);
+}
 
 // M^-1 v for image i (the LDL^T of U'); a failed solve gives zeros
 FUND_HD void bundle_precondition(const BundleData &D, int i, const float *v, float *z)
@@ -420,11 +627,53 @@ FUND_HD void bundle_precondition(const BundleData &D, int i, const float *v, flo
   for (int r = 0; r < 6; r++) z[r] = delta[r];
 }
 
+// FOCAL: the cross-image and cross-track sums of group g, and the groups' share of a dot product (ascending live g)
+struct BundleGroupNormalTerm {
+  const BundleData &D;
+  int g;
+  FUND_HD bool operator()(int i, float (&x)[3]) const
+  {
+    if (D.grp[i] != g || D.istate[i] == BUNDLE_NO_CAMERA) return false;
+    const float *src = D.iuf + (size_t)BUNDLE_IMAGE_FOCAL * i + 6;
+    x[0] = src[0]; x[1] = src[1]; x[2] = src[2];
+    return true;
+  }
+};
+struct BundleGroupCgTerm {
+  const BundleData &D;
+  int g;
+  FUND_HD bool operator()(int i, float (&x)[2]) const
+  {
+    if (D.grp[i] != g || D.istate[i] == BUNDLE_NO_CAMERA) return false;
+    x[0] = D.ifv[2 * (size_t)i]; x[1] = D.ifv[2 * (size_t)i + 1];
+    return true;
+  }
+};
+struct BundleGroupSchurTerm {
+  const BundleData &D;
+  int g;
+  FUND_HD bool operator()(int t, float (&x)[1]) const
+  {
+    if (!(D.tcount[t] >= D.min_views)) return false;
+    x[0] = D.tfd[(size_t)BUNDLE_MAX_GROUPS * t + g];
+    return true;
+  }
+};
+template <bool FOCAL>
+FUND_HD float bundle_dot_groups(const BundleData &D, float acc, int a, int b)
+{
+  if (FOCAL)
+    for (int g = 0; g < D.ngroups; g++)
+      if (bundle_group_live(D, g)) acc = acc + bundle_fvec(D, a)[g] * bundle_fvec(D, b)[g];
+  return acc;
+}
+
 // step 4, the start of PCG in the scalar workgroup; this thread takes the images lane, lane + lanes, ...
-template <class Sum>
+// FOCAL: per live group U_gg, g_g, the Schur scalar S_gg (not finite and > 0: the step fails), x, r, z = r / S_gg, p
+template <bool FOCAL = false, class Sum>
 FUND_HD void bundle_cg_start(const BundleData &D, Sum &S, int lane, int lanes, bool lead)
 {
-  const bool fail = D.ctl[BUNDLE_FAIL] != 0;
+  bool fail = D.ctl[BUNDLE_FAIL] != 0;
   for (int i = lane; i < D.s.nimages; i += lanes) {
     if (D.istate[i] != BUNDLE_ADJUSTED) continue;
     float *x = bundle_vec(D, BUNDLE_X, i), *r = bundle_vec(D, BUNDLE_R, i), *z = bundle_vec(D, BUNDLE_Z, i),
@@ -435,11 +684,33 @@ FUND_HD void bundle_cg_start(const BundleData &D, Sum &S, int lane, int lanes, b
     bundle_precondition(D, i, r, z);
     for (int j = 0; j < 6; j++) p[j] = z[j];
   }
+  if (FOCAL && !fail) {
+    const float lam1 = 1.0f + D.fctl[BUNDLE_LAM];
+    const int T = scene_T(D.s);
+    for (int g = 0; g < D.ngroups; g++) {
+      if (!bundle_group_live(D, g)) continue;
+      BundleGroupNormalTerm nterm{D, g};
+      BundleGroupSchurTerm sterm{D, g};
+      float u[3], d[1];
+      S.template sum<3>(D.s.nimages, nterm, u);
+      S.template sum<1>(T, sterm, d);
+      const float ul = u[0] * lam1, sg = ul - d[0], bg = u[1] - u[2];
+      if (!(fundamental_finite(sg) && sg > 0.0f)) fail = true;
+      if (!lead) continue;
+      D.fsc[g] = ul;
+      D.fsc[BUNDLE_MAX_GROUPS + g] = sg;
+      bundle_fvec(D, BUNDLE_X)[g] = 0.0f;
+      bundle_fvec(D, BUNDLE_R)[g] = bg;
+      bundle_fvec(D, BUNDLE_Z)[g] = bundle_fvec(D, BUNDLE_P)[g] = bg / sg;
+    }
+    if (fail && lead) bundle_raise(&D.ctl[BUNDLE_FAIL]);
+  }
   float rho[1] = {0.0f};
   if (!fail) {                                 // the same in every thread
     S.fence();
     BundleDotTerm term{D.istate, D.ivec + 6 * (size_t)BUNDLE_R * D.s.nimages, D.ivec + 6 * (size_t)BUNDLE_Z * D.s.nimages};
     S.template sum<1>(D.s.nimages, term, rho);
+    rho[0] = bundle_dot_groups<FOCAL>(D, rho[0], BUNDLE_R, BUNDLE_Z);
   }
   if (!lead) return;
   D.fctl[BUNDLE_RHO] = rho[0];
@@ -448,11 +719,12 @@ FUND_HD void bundle_cg_start(const BundleData &D, Sum &S, int lane, int lanes, b
 }
 
 // a CG iteration, per active track: q_t = V'^-1 sum W^T p_image
+template <bool FOCAL = false>
 FUND_HD void bundle_cg_track(const BundleData &D, int t)
 {
   if (!D.ctl[BUNDLE_ALIVE] || !bundle_active(D, t)) return;
   float s[3], q[3];
-  bundle_track_gather(D, t, BUNDLE_P, s);
+  bundle_track_gather<FOCAL>(D, t, BUNDLE_P, s);
   bundle_track_solve(D, t, s, q);
   float *dst = D.tq + 3 * (size_t)t;
   dst[0] = q[0]; dst[1] = q[1]; dst[2] = q[2];
@@ -493,17 +765,86 @@ FUND_HD void bundle_cg_image(const BundleData &D, Sum &S, int i, bool lead)
 #pragma unroll
   for (int r = 0; r < 6; r++) y[r] = bundle_dot6(U[r], p) - s[r];
 }
+// FOCAL: a usable image with a group sums wf . q_t too; a free one has y_i[r] = (U'[r] . p_i + U_cf[r]*p_g) - ...
+struct BundleWqFocalTerm {
+  const BundleData &D;
+  const int *list;
+  FUND_HD bool operator()(int p, float (&x)[1]) const
+  {
+    const int o = list[p];
+    x[0] = bundle_wf3(D.lin + (size_t)BUNDLE_LIN * o, D.flin + 2 * (size_t)o, D.tq + 3 * (size_t)D.owner[o]);
+    return true;
+  }
+  FUND_HD bool operator()(int p, float (&x)[7]) const
+  {
+    const int o = list[p];
+    const float *l = D.lin + (size_t)BUNDLE_LIN * o, *q = D.tq + 3 * (size_t)D.owner[o];
+#pragma unroll
+    for (int r = 0; r < 6; r++) x[r] = bundle_w3(l, r, q);
+    x[6] = bundle_wf3(l, D.flin + 2 * (size_t)o, q);
+    return true;
+  }
+};
+template <class Sum>
+FUND_HD void bundle_cg_image_focal(const BundleData &D, Sum &S, int i, bool lead)
+{
+  const int g = D.grp[i];
+  if (g < 0) return bundle_cg_image(D, S, i, lead);
+  if (!D.ctl[BUNDLE_ALIVE] || D.istate[i] == BUNDLE_NO_CAMERA) return;
+  BundleWqFocalTerm term{D, D.list + D.istart[i]};
+  float *dst = D.ifv + 2 * (size_t)i;
+  if (D.istate[i] != BUNDLE_ADJUSTED) {
+    float s[1];
+    S.template sum<1>(D.icount[i], term, s);
+    if (!lead) return;
+    dst[0] = 0.0f;
+    dst[1] = s[0];
+    return;
+  }
+  float s[7];
+  S.template sum<7>(D.icount[i], term, s);
+  if (!lead) return;
+  const float *src = D.iu + (size_t)REFINE_SUMS * i, *p = bundle_vec(D, BUNDLE_P, i);
+  const float *ucf = D.iuf + (size_t)BUNDLE_IMAGE_FOCAL * i;
+  const float pg = bundle_fvec(D, BUNDLE_P)[g];
+  float U[6][6];
+  int j = 1;
+#pragma unroll
+  for (int r = 0; r < 6; r++)
+#pragma unroll
+    for (int c = r; c < 6; c++) {
+      U[r][c] = U[c][r] = src[j];
+      j++;
+    }
+  float *y = bundle_vec(D, BUNDLE_Y, i);
+#pragma unroll
+  for (int r = 0; r < 6; r++) y[r] = (bundle_dot6(U[r], p) + ucf[r] * pg) - s[r];
+  dst[0] = bundle_dot6(ucf, p);
+  dst[1] = s[6];
+}
 
 // a CG iteration in the scalar workgroup: sigma, alpha, x, r, z, rho', beta, p
-template <class Sum>
+// FOCAL: first y_g = (l1*U_gg * p_g + the cross-image sum of U_cf . p_i) - the cross-image sum of the sums of wf . q_t
+template <bool FOCAL = false, class Sum>
 FUND_HD void bundle_cg_scalar(const BundleData &D, Sum &S, int lane, int lanes, bool lead)
 {
   if (!D.ctl[BUNDLE_ALIVE]) return;            // the same in every thread
   const float rho = D.fctl[BUNDLE_RHO];
   const size_t n6 = 6 * (size_t)D.s.nimages;
+  if (FOCAL) {
+    for (int g = 0; g < D.ngroups; g++) {
+      if (!bundle_group_live(D, g)) continue;
+      BundleGroupCgTerm term{D, g};
+      float v[2];
+      S.template sum<2>(D.s.nimages, term, v);
+      if (lead) bundle_fvec(D, BUNDLE_Y)[g] = (D.fsc[g] * bundle_fvec(D, BUNDLE_P)[g] + v[0]) - v[1];
+    }
+    S.fence();
+  }
   BundleDotTerm sterm{D.istate, D.ivec + BUNDLE_P * n6, D.ivec + BUNDLE_Y * n6};
   float sigma[1], rho2[1];
   S.template sum<1>(D.s.nimages, sterm, sigma);
+  sigma[0] = bundle_dot_groups<FOCAL>(D, sigma[0], BUNDLE_P, BUNDLE_Y);
   if (!(fundamental_finite(sigma[0]) && sigma[0] > 0.0f)) {
     S.fence();                                 // every thread has read ALIVE
     if (lead) D.ctl[BUNDLE_ALIVE] = 0;
@@ -518,12 +859,25 @@ FUND_HD void bundle_cg_scalar(const BundleData &D, Sum &S, int lane, int lanes, 
     for (int j = 0; j < 6; j++) r[j] = r[j] - alpha * y[j];
     bundle_precondition(D, i, r, z);
   }
+  if (FOCAL)
+    for (int g = lane; g < D.ngroups; g += lanes) {
+      if (!bundle_group_live(D, g)) continue;
+      float *x = bundle_fvec(D, BUNDLE_X) + g, *r = bundle_fvec(D, BUNDLE_R) + g;
+      x[0] = x[0] + alpha * bundle_fvec(D, BUNDLE_P)[g];
+      r[0] = r[0] - alpha * bundle_fvec(D, BUNDLE_Y)[g];
+      bundle_fvec(D, BUNDLE_Z)[g] = r[0] / D.fsc[BUNDLE_MAX_GROUPS + g];
+    }
   S.fence();
   BundleDotTerm rterm{D.istate, D.ivec + BUNDLE_R * n6, D.ivec + BUNDLE_Z * n6};
   S.template sum<1>(D.s.nimages, rterm, rho2);
+  rho2[0] = bundle_dot_groups<FOCAL>(D, rho2[0], BUNDLE_R, BUNDLE_Z);
   const bool on = fundamental_finite(rho2[0]);
   if (on) {
     const float beta = rho2[0] / rho;
+    if (FOCAL)
+      for (int g = lane; g < D.ngroups; g += lanes)
+        if (bundle_group_live(D, g))
+          bundle_fvec(D, BUNDLE_P)[g] = bundle_fvec(D, BUNDLE_Z)[g] + beta * bundle_fvec(D, BUNDLE_P)[g];
     for (int i = lane; i < D.s.nimages; i += lanes) {
       if (D.istate[i] != BUNDLE_ADJUSTED) continue;
       float *p = bundle_vec(D, BUNDLE_P, i);
@@ -539,12 +893,13 @@ FUND_HD void bundle_cg_scalar(const BundleData &D, Sum &S, int lane, int lanes, 
 }
 
 // step 5 for an active track: delta_t = V'^-1 (gp - sum W^T x_image), the trial point
+template <bool FOCAL = false>
 FUND_HD void bundle_track_trial(const BundleData &D, int t)
 {
   if (D.ctl[BUNDLE_FAIL] || !bundle_active(D, t)) return;
   const int b = D.ctl[BUNDLE_CUR];
   float s[3], d[3];
-  bundle_track_gather(D, t, BUNDLE_X, s);
+  bundle_track_gather<FOCAL>(D, t, BUNDLE_X, s);
   const float *v = D.tv + 9 * (size_t)t;
   const float rhs[3] = {v[6] - s[0], v[7] - s[1], v[8] - s[2]};
   bundle_track_solve(D, t, rhs, d);
@@ -574,6 +929,18 @@ FUND_HD void bundle_image_trial(const BundleData &D, int i)
 #pragma unroll
   for (int j = 0; j < 12; j++) dst[j] = out[j];
   if (!refine_finite12(out)) bundle_raise(&D.ctl[BUNDLE_BAD]);
+}
+
+// FOCAL, step 5 for group g < BUNDLE_MAX_GROUPS: the trial scale s_g + x_g; one that is not finite and > 0 raises BAD
+FUND_HD void bundle_focal_trial(const BundleData &D, int g)
+{
+  if (D.ctl[BUNDLE_FAIL]) return;
+  const int b = D.ctl[BUNDLE_CUR];
+  const float s = D.fs[b * BUNDLE_MAX_GROUPS + g];
+  const bool live = g < D.ngroups && bundle_group_live(D, g);
+  const float e = live ? s + bundle_fvec(D, BUNDLE_X)[g] : s;
+  D.fs[(1 - b) * BUNDLE_MAX_GROUPS + g] = e;
+  if (live && !(fundamental_finite(e) && e > 0.0f)) bundle_raise(&D.ctl[BUNDLE_BAD]);
 }
 
 // step 6 in the scalar workgroup
@@ -666,19 +1033,20 @@ FUND_HD void bundle_track_out(const BundleData &D, int t)
 }
 
 // d_obs_weight for slot o < O: -1 for a slot that is no member, w of a member under the final state
+template <bool FOCAL = false>
 FUND_HD void bundle_weight_slot(const BundleData &D, int o)
 {
   const int k = D.key[o];
   float w = -1.0f;
   if (k >= 0) {
     const int b = D.ctl[BUNDLE_CUR];
-    float c[12];
+    float c[12], kk[4];
     bundle_load_cam(D.cams + 12 * ((size_t)b * D.s.nimages + k), c);
     const float *P = D.pts + 3 * ((size_t)b * D.s.max_tracks + D.owner[o]);
     const float X[3] = {P[0], P[1], P[2]};
     const TrackObs ob = track_obs_load(D.s.obs + o);
     RefineView v;
-    if (refine_view(c, D.s.intrinsics + 4 * (size_t)k, X, ob.xpos, ob.ypos, v))
+    if (refine_view(c, bundle_intrinsics<FOCAL>(D, b, k, kk), X, ob.xpos, ob.ypos, v))
       w = pose_one_nan(bundle_loss(D.loss, D.loss_scale, D.loss_scale2, v.ru * v.ru + v.rv * v.rv).w);
     else
       w = pose_one_nan(NAN);                   // the final state has every member in front: not reached
@@ -686,10 +1054,40 @@ FUND_HD void bundle_weight_slot(const BundleData &D, int o)
   D.obs_weight[o] = w;
 }
 
+// d_intrinsics_out of image i and d_focal of group g < ngroups.  `refined`: an image has a group, so the FOCAL instances
+// ran; otherwise every s_g is 1, no member is counted and the intrinsics come back bit for bit
+FUND_HD int bundle_focal_status(const BundleData &D, int g, bool refined)
+{
+  if (D.num_loops == 0) return BUNDLE_FOCAL_NOT_REFINED;
+  return refined && bundle_group_live(D, g) ? BUNDLE_FOCAL_REFINED : BUNDLE_FOCAL_NO_MEMBER;
+}
+FUND_HD void bundle_intrinsics_out(const BundleData &D, int i, bool refined)
+{
+  const unsigned *given = reinterpret_cast<const unsigned *>(D.s.intrinsics) + 4 * (size_t)i;
+  unsigned w[4] = {given[0], given[1], given[2], given[3]};
+  const int g = D.grp ? D.grp[i] : -1;
+  if (g >= 0 && refined && bundle_focal_status(D, g, true) == BUNDLE_FOCAL_REFINED && D.istate[i] != BUNDLE_NO_CAMERA) {
+    const float s = D.fs[D.ctl[BUNDLE_CUR] * BUNDLE_MAX_GROUPS + g];
+    const float fx = D.s.intrinsics[4 * (size_t)i] * s, fy = D.s.intrinsics[4 * (size_t)i + 1] * s;
+    __builtin_memcpy(&w[0], &fx, sizeof fx);
+    __builtin_memcpy(&w[1], &fy, sizeof fy);
+  }
+  unsigned *out = reinterpret_cast<unsigned *>(D.intrinsics_out) + 4 * (size_t)i;
+  out[0] = w[0]; out[1] = w[1]; out[2] = w[2]; out[3] = w[3];
+}
+FUND_HD void bundle_focal_out(const BundleData &D, int g, bool refined)
+{
+  const float s = refined ? D.fs[D.ctl[BUNDLE_CUR] * BUNDLE_MAX_GROUPS + g] : 1.0f;
+  int *out = D.focal_out + 3 * (size_t)g;
+  __builtin_memcpy(&out[0], &s, sizeof s);
+  out[1] = refined ? D.fcount[g] : 0;
+  out[2] = bundle_focal_status(D, g, refined);
+}
+
 // ---- the host's side: the Sum as a loop, the phases in the order of the launches
 
 struct BundleHostSum {
-  float p[BUNDLE_NORMAL * FUND_SLOTS];
+  float p[BUNDLE_NORMAL_FOCAL * FUND_SLOTS];
   void fence() {}
   template <int K, class V>
   void sum(int n, V &v, float (&out)[K])

@@ -692,6 +692,17 @@ int launch_adjust_bundle_batch(misift_ctx *ctx, const TrackScene &scene, const i
                                float loss_scale, float loss_scale2, float *d_cam_out, float *d_points_out, int *d_cam_obs,
                                int *d_cam_status, float *d_cam_rms, int *d_point_obs, float *d_history, float *d_cost,
                                float *d_obs_weight, int *d_summary);
+// misift_adjust_bundle_focal_batch (kernels_bundle.hip).  h_group: the pinned copy of `group`; focal: an image has a
+// group.  Without one the launches and the temp are those of launch_adjust_bundle_batch, which is this function with no
+// group and no d_intrinsics_out; with d_intrinsics_out one launch more at the end writes it and d_focal
+size_t adjust_bundle_focal_batch_tmp_bytes(int max_tracks, int max_obs, int nimages);
+int launch_adjust_bundle_focal_batch(misift_ctx *ctx, const TrackScene &scene, const int *h_held, int min_views,
+                                     int min_obs, int num_loops, int cg_iters, float thresh2, float lambda0,
+                                     int orthonormalise, int loss, float loss_scale, float loss_scale2, int ngroups,
+                                     const int *h_group, bool focal, float *d_cam_out, float *d_points_out, int *d_cam_obs,
+                                     int *d_cam_status, float *d_cam_rms, int *d_point_obs, float *d_history,
+                                     float *d_cost, float *d_obs_weight, int *d_summary, float *d_intrinsics_out,
+                                     int *d_focal);
 // misift_filter_tracks_batch (kernels_filter.hip): a copy, three memsets + six launches; temp from misift_ensure_tmp,
 // sized from max_tracks, max_obs and nimages only
 size_t filter_tracks_batch_tmp_bytes(int max_tracks, int max_obs, int nimages);

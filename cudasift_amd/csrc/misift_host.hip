@@ -2727,6 +2727,60 @@ extern "C" int misift_resect_cameras_batch(misift_ctx *ctx, int max_tracks, int 
                    });
 }
 
+// The body of the three bundle calls: the robust call, with ngroups > 0 and a group for some image the focal scales
+// among the unknowns, and with d_intrinsics_out the focal call's two outputs.
+static int adjust_bundle(const char *who, misift_ctx *ctx, int max_tracks, int max_obs, const int *d_track_offsets,
+                         const misift_track_obs *d_obs, const int *d_export_summary, const float *d_points,
+                         const int *d_point_status, int nimages, const float *d_cam, const int *d_cam_pair,
+                         const float *intrinsics, int nhold, const int *hold, int min_views, int min_obs, int num_loops,
+                         int cg_iters, float max_error, float lambda0, int orthonormalise, int loss, float loss_scale,
+                         int ngroups, const int *group, float *d_cam_out, float *d_points_out, int *d_cam_obs,
+                         int *d_cam_status, float *d_cam_rms, int *d_point_obs, float *d_history, float *d_cost,
+                         float *d_obs_weight, int *d_summary, float *d_intrinsics_out, int *d_focal)
+{
+  ARG_CHECK_IN(who, ctx != nullptr);
+  TrackScene S;
+  int rc = check_scene(who, &S, max_tracks, max_obs, d_track_offsets, d_obs, d_export_summary, d_points,
+                       d_point_status, nimages, d_cam, d_cam_pair, intrinsics);
+  if (rc) return rc;
+  ARG_CHECK_IN(who, d_points && d_point_status && d_cam && d_cam_pair);
+  ARG_CHECK_IN(who, d_cam_out && d_points_out && d_cam_obs && d_cam_status && d_cam_rms && d_point_obs);
+  ARG_CHECK_IN(who, d_cost && d_summary && (d_history || num_loops == 0));
+  ARG_CHECK_IN(who, min_views >= 2 && min_obs >= 3 && num_loops >= 0 && cg_iters >= 0);
+  ARG_CHECK_IN(who, max_error > 0.0f);                                              // NaN fails too
+  ARG_CHECK_IN(who, lambda0 > 0.0f && lambda0 <= 3.402823466e+38f);
+  ARG_CHECK_IN(who, orthonormalise == 0 || orthonormalise == 1);
+  ARG_CHECK_IN(who, loss == MISIFT_LOSS_NONE || loss == MISIFT_LOSS_HUBER || loss == MISIFT_LOSS_GEMAN_MCCLURE);
+  if (loss != MISIFT_LOSS_NONE) ARG_CHECK_IN(who, loss_scale > 0.0f && loss_scale <= 3.402823466e+38f);   // not read with loss 0
+  ARG_CHECK_IN(who, nhold >= 0 && (nhold == 0 || hold));
+  for (int j = 0; j < nhold; j++) ARG_CHECK_IN(who, hold[j] >= 0 && hold[j] < nimages);
+  ARG_CHECK_IN(who, same_or_disjoint(d_cam, d_cam_out, sizeof(float) * 12 * (size_t)nimages));
+  ARG_CHECK_IN(who, same_or_disjoint(d_points, d_points_out, sizeof(float) * 4 * (size_t)max_tracks));
+  ARG_CHECK_IN(who, ngroups >= 0 && ngroups <= MISIFT_MAX_FOCAL_GROUPS && (ngroups == 0 || group));
+  bool focal = false;
+  for (int i = 0; ngroups > 0 && i < nimages; i++) {
+    ARG_CHECK_IN(who, group[i] >= -1 && group[i] < ngroups);
+    focal = focal || group[i] >= 0;
+  }
+  const std::vector<int> held = held_flags(nimages, nhold, hold);
+  const std::vector<int> none(d_intrinsics_out && ngroups == 0 ? nimages : 0, -1);   // the two old calls copy no group
+  const float thresh2 = max_error * max_error;                              // rounded once, here
+  const float c = loss != MISIFT_LOSS_NONE ? loss_scale : 0.0f;
+  const float c2 = c * c;                                                   // and so is this
+  RoctxRange range(who);
+  return run_batch(ctx, {{intrinsics, sizeof(float) * 4 * (size_t)nimages}, {held.data(), sizeof(int) * (size_t)nimages},
+                         {ngroups > 0 ? group : none.data(), d_intrinsics_out ? sizeof(int) * (size_t)nimages : 0}},
+                   0, [&](int *h_lists, void *) {
+                     S.intrinsics = reinterpret_cast<const float *>(h_lists);
+                     const int *h_held = h_lists + 4 * (size_t)nimages;
+                     return launch_adjust_bundle_focal_batch(ctx, S, h_held, min_views, min_obs, num_loops, cg_iters,
+                                                             thresh2, lambda0, orthonormalise, loss, c, c2, ngroups,
+                                                             h_held + nimages, focal, d_cam_out, d_points_out, d_cam_obs,
+                                                             d_cam_status, d_cam_rms, d_point_obs, d_history, d_cost,
+                                                             d_obs_weight, d_summary, d_intrinsics_out, d_focal);
+                   });
+}
+
 // Levenberg-Marquardt over all free cameras and all active track points at once, the points eliminated in every step:
 // what misift_refine_cameras_batch and misift_triangulate_tracks_batch do in turns, done jointly, under a loss (0: the
 // plain sum of squares).  The intrinsics and a flag per image (1 = held) go to the pinned slot.
@@ -2740,37 +2794,33 @@ extern "C" int misift_adjust_bundle_robust_batch(misift_ctx *ctx, int max_tracks
                                                  int *d_cam_obs, int *d_cam_status, float *d_cam_rms, int *d_point_obs,
                                                  float *d_history, float *d_cost, float *d_obs_weight, int *d_summary)
 {
-  ARG_CHECK(ctx != nullptr);
-  TrackScene S;
-  int rc = check_scene(__func__, &S, max_tracks, max_obs, d_track_offsets, d_obs, d_export_summary, d_points,
-                       d_point_status, nimages, d_cam, d_cam_pair, intrinsics);
-  if (rc) return rc;
-  ARG_CHECK(d_points && d_point_status && d_cam && d_cam_pair);
-  ARG_CHECK(d_cam_out && d_points_out && d_cam_obs && d_cam_status && d_cam_rms && d_point_obs);
-  ARG_CHECK(d_cost && d_summary && (d_history || num_loops == 0));
-  ARG_CHECK(min_views >= 2 && min_obs >= 3 && num_loops >= 0 && cg_iters >= 0);
-  ARG_CHECK(max_error > 0.0f);                                              // NaN fails too
-  ARG_CHECK(lambda0 > 0.0f && lambda0 <= 3.402823466e+38f);
-  ARG_CHECK(orthonormalise == 0 || orthonormalise == 1);
-  ARG_CHECK(loss == MISIFT_LOSS_NONE || loss == MISIFT_LOSS_HUBER || loss == MISIFT_LOSS_GEMAN_MCCLURE);
-  if (loss != MISIFT_LOSS_NONE) ARG_CHECK(loss_scale > 0.0f && loss_scale <= 3.402823466e+38f);   // not read with loss 0
-  ARG_CHECK(nhold >= 0 && (nhold == 0 || hold));
-  for (int j = 0; j < nhold; j++) ARG_CHECK(hold[j] >= 0 && hold[j] < nimages);
-  ARG_CHECK(same_or_disjoint(d_cam, d_cam_out, sizeof(float) * 12 * (size_t)nimages));
-  ARG_CHECK(same_or_disjoint(d_points, d_points_out, sizeof(float) * 4 * (size_t)max_tracks));
-  const std::vector<int> held = held_flags(nimages, nhold, hold);
-  const float thresh2 = max_error * max_error;                              // rounded once, here
-  const float c = loss != MISIFT_LOSS_NONE ? loss_scale : 0.0f;
-  const float c2 = c * c;                                                   // and so is this
-  RoctxRange range(__func__);
-  return run_batch(ctx, {{intrinsics, sizeof(float) * 4 * (size_t)nimages}, {held.data(), sizeof(int) * (size_t)nimages}},
-                   0, [&](int *h_lists, void *) {
-                     S.intrinsics = reinterpret_cast<const float *>(h_lists);
-                     return launch_adjust_bundle_batch(ctx, S, h_lists + 4 * (size_t)nimages, min_views, min_obs, num_loops,
-                                                       cg_iters, thresh2, lambda0, orthonormalise, loss, c, c2, d_cam_out,
-                                                       d_points_out, d_cam_obs, d_cam_status, d_cam_rms, d_point_obs,
-                                                       d_history, d_cost, d_obs_weight, d_summary);
-                   });
+  return adjust_bundle(__func__, ctx, max_tracks, max_obs, d_track_offsets, d_obs, d_export_summary, d_points,
+                       d_point_status, nimages, d_cam, d_cam_pair, intrinsics, nhold, hold, min_views, min_obs, num_loops,
+                       cg_iters, max_error, lambda0, orthonormalise, loss, loss_scale, 0, nullptr, d_cam_out, d_points_out,
+                       d_cam_obs, d_cam_status, d_cam_rms, d_point_obs, d_history, d_cost, d_obs_weight, d_summary,
+                       nullptr, nullptr);
+}
+
+// The robust call with one focal scale per camera group among the unknowns; the group of every image goes to the pinned
+// slot behind the held flags.
+extern "C" int misift_adjust_bundle_focal_batch(misift_ctx *ctx, int max_tracks, int max_obs, const int *d_track_offsets,
+                                                const misift_track_obs *d_obs, const int *d_export_summary,
+                                                const float *d_points, const int *d_point_status, int nimages,
+                                                const float *d_cam, const int *d_cam_pair, const float *intrinsics,
+                                                int nhold, const int *hold, int min_views, int min_obs, int num_loops,
+                                                int cg_iters, float max_error, float lambda0, int orthonormalise,
+                                                int loss, float loss_scale, int ngroups, const int *group,
+                                                float *d_cam_out, float *d_points_out, int *d_cam_obs, int *d_cam_status,
+                                                float *d_cam_rms, int *d_point_obs, float *d_history, float *d_cost,
+                                                float *d_obs_weight, int *d_summary, float *d_intrinsics_out,
+                                                int *d_focal)
+{
+  ARG_CHECK(d_intrinsics_out && (d_focal || ngroups == 0));
+  return adjust_bundle(__func__, ctx, max_tracks, max_obs, d_track_offsets, d_obs, d_export_summary, d_points,
+                       d_point_status, nimages, d_cam, d_cam_pair, intrinsics, nhold, hold, min_views, min_obs, num_loops,
+                       cg_iters, max_error, lambda0, orthonormalise, loss, loss_scale, ngroups, group, d_cam_out,
+                       d_points_out, d_cam_obs, d_cam_status, d_cam_rms, d_point_obs, d_history, d_cost, d_obs_weight,
+                       d_summary, d_intrinsics_out, d_focal);
 }
 
 // The plain sum of squares: loss 0 and no weights.

@@ -1222,7 +1222,7 @@ int misift_triangulate_tracks_batch(misift_ctx *ctx,
  *   - Not done here: camera and point steps are not taken jointly (no Schur complement: misift_adjust_bundle_batch does
  *     that; or alternate with triangulate), no robust kernel re-weights a residual (max_error is a hard gate, decided once;
  *     misift_filter_tracks_batch revises the lists between calls), and the intrinsics are
- *     not refined.
+ *     not refined (misift_adjust_bundle_focal_batch refines a focal scale per camera).
  *   - NULL ctx; max_tracks, max_obs or nimages < 1; NULL d_track_offsets, d_obs, d_export_summary, d_points,
  *     d_point_status, d_cam, d_cam_pair, intrinsics, d_cam_out, d_cam_obs, d_cam_rms, d_cam_steps, d_cam_status or
  *     d_summary; d_obs not 16-byte aligned; min_obs < 3; num_loops < 0; max_error NaN or <= 0; orthonormalise other than
@@ -1439,7 +1439,8 @@ int misift_resect_cameras_batch(misift_ctx *ctx,
  *     preconditioner is the damped U' of each camera, not the Schur diagonal block.
  *   - Not done here: no robust kernel re-weights a residual in this call (max_error is a hard gate, decided once:
  *     misift_adjust_bundle_robust_batch is this call under a Huber or a Geman-McClure loss), the intrinsics are not
- *     refined, the member set is not revised between steps, and no Schur-diagonal preconditioner is formed.
+ *     refined (misift_adjust_bundle_focal_batch refines a focal scale per camera), the member set is not revised
+ *     between steps, and no Schur-diagonal preconditioner is formed.
  *   - NULL ctx; max_tracks, max_obs or nimages < 1; NULL d_track_offsets, d_obs, d_export_summary, d_points,
  *     d_point_status, d_cam, d_cam_pair, intrinsics, d_cam_out, d_points_out, d_cam_obs, d_cam_status, d_cam_rms,
  *     d_point_obs, d_cost or d_summary, NULL d_history with num_loops > 0; d_obs not 16-byte aligned; min_views < 2;
@@ -1515,7 +1516,8 @@ int misift_adjust_bundle_batch(misift_ctx *ctx,
  *     by the outliers and adjust -> filter -> adjust removes clean observations with them.
  *   - Not done here: no robust loss in misift_refine_cameras_batch or misift_triangulate_tracks_batch, no Cauchy loss
  *     (its cost needs logf, which the arithmetic rules exclude), no second-order correction, the intrinsics are not
- *     refined, the member set is not revised between steps (max_error is still the hard gate, decided once).
+ *     refined (misift_adjust_bundle_focal_batch is this call with a focal scale per camera), the member set is not
+ *     revised between steps (max_error is still the hard gate, decided once).
  *   - The argument errors of misift_adjust_bundle_batch; a loss other than 0, 1 or 2; with loss != 0 a loss_scale that
  *     is not finite and > 0: MISIFT_EINVAL, before anything is enqueued.  A d_obs_weight overlapping another buffer is
  *     the caller's error and is not checked.
@@ -1550,6 +1552,118 @@ int misift_adjust_bundle_robust_batch(misift_ctx *ctx,
                                       float *d_cost,                  /* 2: before, after */
                                       float *d_obs_weight,            /* max_obs; may be NULL */
                                       int   *d_summary);              /* 8 ints */
+
+/* misift_adjust_bundle_robust_batch with one focal scale per physical camera among the unknowns (no reference
+ * counterpart): every image is given the GROUP of the camera that took it, and each group g has one scalar s_g that
+ * multiplies the given fx and fy of all its images.  A focal length from EXIF or guessed from the image width is
+ * routinely 5 to 10 % off; this call estimates the correction jointly with the cameras and the points.  In the chain it
+ * stands where adjust stands; a caller that carries on reads d_intrinsics_out back (16 * nimages bytes) and hands it
+ * to the next call as its `intrinsics`.
+ *   The arguments are those of misift_adjust_bundle_robust_batch in the same order, with `ngroups` and `group` after
+ *   `loss_scale` and `d_intrinsics_out` and `d_focal` after `d_summary`.  ngroups lies in 0 ... MISIFT_MAX_FOCAL_GROUPS
+ *   (8: a lane holds one 3-vector per group for its track, 24 registers, and forms them in one walk over the members; the
+ *   constant also bounds the loops of the scalar workgroup and costs 32 bytes per track of temp).  group[i] is the group of image i, or -1 for an
+ *   image whose intrinsics stay as given.  The definition is that of misift_adjust_bundle_robust_batch, every word of
+ *   it, the arithmetic rules included, with the amendments below.  With ngroups == 0 or every group[i] == -1 there is no
+ *   amendment: the call is the robust call.
+ *   The unknown.  s_g = 1.0f at the start.  The sets are decided under the given intrinsics as there.  M_g = the
+ *   members in the usable images of group g (an integer sum); a group with M_g == 0 is not LIVE: its s_g stays 1 and it
+ *   takes no part below.  Wherever a member of an image i with g = group[i] >= 0 is projected under a state (the cost,
+ *   step 1, d_obs_weight), the intrinsics are fx_i*s_g, fy_i*s_g, cx_i, cy_i with s_g of that state, each product
+ *   rounded; an image with group -1 uses its four floats as given.
+ *   Step 1.  Beside the 20 values a member of a grouped image has Juf = fx_i * a and Jvf = fy_i * b with the given fx_i,
+ *   fy_i (and a, b of the view under the state); with loss != 0 both are multiplied by sw like the 20.  For such a
+ *   member wf[q] = Juf*Pu[q] + Jvf*Pv[q], and wf . v = (wf[0]*v0 + wf[1]*v1) + wf[2]*v2 for a 3-vector v.
+ *   Step 2.  Per active track and per live group g, after V' and y_t: w_gt = the per-track sum of wf over the track's
+ *   members in images of group g (per component), and d_gt = (w_gt[0]*x0 + w_gt[1]*x1) + w_gt[2]*x2 with
+ *   x = SOLVE(V', w_gt) (zeros when it fails).
+ *   Step 3.  A usable image i with a group takes three more per-image sums, whatever its status: Uff_i with the term
+ *   Juf*Juf + Jvf*Jvf, gf_i with Juf*ru + Jvf*rv, and wy_i with wf . y_t.  A free image with a group takes six more,
+ *   Ucf_i[r] with Ju[r]*Juf + Jv[r]*Jvf: 42 sums in one pass.  U', b and M^-1 of a free image are unchanged.  Then per
+ *   live group, in ascending g: U_gg, g_g and wy_g are the cross-image sums of Uff_i, gf_i and wy_i over the usable
+ *   images of the group; D_g is the sum of d_gt over the active tracks by the 256-slot rule on the track index t (a
+ *   track that is not active is skipped); UL_g = U_gg * l1, S_gg = UL_g - D_g, b_g = g_g - wy_g.  An S_gg that is not
+ *   finite and > 0 makes the step FAIL like a failed SOLVE.
+ *   Step 4.  PCG runs over the free images' 6-vectors and the live groups' scalars.  A dot product of two such vectors
+ *   is the cross-image sum of the 6-vector dot products, to which v_g * w_g is added for each live group in ascending g,
+ *   one at a time.  x_g = 0, r_g = b_g, z_g = r_g / S_gg, p_g = z_g.  In an iteration:
+ *     the per-track sum for q_t takes, for each member in ascending slot, first (W^T p_i) if its image is free, then
+ *     wf * p_g (per component) if its image has a group;
+ *     a free image with a group has y_i[r] = (U'[r] . p_i + Ucf_i[r] * p_g) - (the per-image sum of (W q_t)[r]); and
+ *     every usable image with a group takes the per-image sum wq_i of wf . q_t, a free one also c_i = Ucf_i . p_i (the
+ *     6-vector dot product), any other c_i = 0;
+ *     per live group y_g = (UL_g * p_g + the cross-image sum of c_i) - the cross-image sum of wq_i, both over the usable
+ *     images of the group;
+ *     sigma, alpha, rho', beta as there with the extended dot product; x_g += alpha*p_g, r_g -= alpha*y_g,
+ *     z_g = r_g / S_gg, p_g = z_g + beta*p_g.
+ *   Step 5.  The per-track sum of delta_t takes wf * x_g after (W^T x_i) in the same way.  The trial scale of a live
+ *   group is s_g + x_g; one that is not finite and > 0 makes the trial state not finite (the step is turned away).
+ *   Step 6 is unchanged: s_g is kept or turned away with the cameras and the points.
+ *   Outputs.  The ten of misift_adjust_bundle_robust_batch.  d_intrinsics_out[4i..4i+3] = fx_i*s_g, fy_i*s_g (each
+ *   rounded), cx_i, cy_i under the final state for a usable image of a group whose status is 0; the four input floats
+ *   bit for bit for any other image.  d_focal[3g..3g+2] for g < ngroups: s_g of the final state (float), M_g (int),
+ *   and the status (int): 0 MISIFT_FOCAL_REFINED, 1 MISIFT_FOCAL_NO_MEMBER (the group is not live), 2
+ *   MISIFT_FOCAL_NOT_REFINED (num_loops == 0; s_g is 1.0f).  With every group[i] == -1, M_g is 0 and the status 1 (2
+ *   with num_loops == 0).
+ *   - With ngroups == 0, or every group[i] == -1, the ten shared outputs equal those of
+ *     misift_adjust_bundle_robust_batch byte for byte (with loss 0 those of misift_adjust_bundle_batch too), the call
+ *     launches that call's kernels, and d_intrinsics_out is the input bit for bit.  With num_loops == 0
+ *     d_intrinsics_out is the input bit for bit and every s_g is 1.0f.
+ *   - A held, root or demoted pose does not hold the focal scale: the members of such an image enter the focal sums.
+ *     The gauge still needs two held poses (or a root and a held one); with fewer, scale and focal drift together.
+ *   - The focal unknown is preconditioned by its own Schur scalar S_gg, not by its damped diagonal UL_g: with the plain
+ *     diagonal PCG barely moves the focal scale (on 24 images, 400 tracks, 10 iterations it is still 7 % off after
+ *     eight steps where S_gg leaves 0.5 %).
+ *   - On planted scenes (120 tracks over 8 images and 400 over 24, 0.5 px noise) whose fx, fy are given 10 % off (one
+ *     group), or 10 % short and long for two cameras taking turns, 8 steps at cg_iters 10 bring s_g within 1.34e-2
+ *     (relative) of the planted 1 / 1.1 and 1 / 0.9 and within 1.27e-2 of a float64 Levenberg-Marquardt with every step
+ *     solved exactly, and the pooled rms within 7.51e-3 px of that one's 0.46 px (MEASURED, the worst of the four scenes;
+ *     tests/test_bundle_focal_cpu.py, which also holds fp32 to float64: 9.77e-4 on s_g, 1.73e-3 px on the rms).  The
+ *     robust call on the same input ends at 0.58 to 10 px.
+ *   - Not done here: no principal point, aspect ratio or distortion is estimated, there is no focal prior, and at most
+ *     MISIFT_MAX_FOCAL_GROUPS groups; the other calls of the chain keep taking `intrinsics` from the host.
+ *   - The argument errors of misift_adjust_bundle_robust_batch; ngroups outside 0 ... MISIFT_MAX_FOCAL_GROUPS; NULL
+ *     group with ngroups > 0; a group[i] outside [-1, ngroups); NULL d_intrinsics_out; NULL d_focal with ngroups > 0:
+ *     MISIFT_EINVAL, before anything is enqueued.  The new outputs overlapping another buffer is the caller's error.
+ *   - Stream, copies and ordering as misift_adjust_bundle_batch; `group` is copied.  Without a grouped image: the
+ *     memsets and launches of the robust call and one launch more (the two new outputs), the same temp.  With one: three
+ *     memsets and 13 + num_loops * (8 + 3 * cg_iters) launches (one more with d_obs_weight): the groups' members in the
+ *     scalar workgroup during the setup and the two new outputs at the end are the two more; the trial scale is set in
+ *     the launch of the trial cameras and the groups' sums run in the scalar workgroup's existing launches.  The
+ *     per-image pass of step 3 holds 42 sums (42 KiB of LDS).  Temp: 108 bytes per slot, 108 per track and 396 per
+ *     image, each array rounded up to 16, and 320 bytes for the groups. */
+#define MISIFT_MAX_FOCAL_GROUPS 8
+#define MISIFT_FOCAL_REFINED 0
+#define MISIFT_FOCAL_NO_MEMBER 1
+#define MISIFT_FOCAL_NOT_REFINED 2
+int misift_adjust_bundle_focal_batch(misift_ctx *ctx,
+                                     int max_tracks, int max_obs,
+                                     const int *d_track_offsets,     /* max_tracks + 1, from export */
+                                     const misift_track_obs *d_obs,  /* max_obs, from export, 16-byte aligned */
+                                     const int *d_export_summary,    /* 8 ints, from export: [2] = T, [3] = O */
+                                     const float *d_points,          /* max_tracks x 4, from triangulate */
+                                     const int *d_point_status,      /* max_tracks, from triangulate */
+                                     int nimages,
+                                     const float *d_cam,             /* nimages x 12 */
+                                     const int *d_cam_pair,          /* nimages */
+                                     const float *intrinsics,        /* host, nimages x 4: fx fy cx cy, copied */
+                                     int nhold, const int *hold,     /* host, images kept as they are, copied; may be NULL */
+                                     int min_views, int min_obs, int num_loops, int cg_iters,
+                                     float max_error, float lambda0, int orthonormalise,
+                                     int loss, float loss_scale /* px */,
+                                     int ngroups, const int *group,  /* host, nimages: the group of the image or -1, copied */
+                                     float *d_cam_out,               /* nimages x 12; may be d_cam itself */
+                                     float *d_points_out,            /* max_tracks x 4; may be d_points itself */
+                                     int   *d_cam_obs,               /* nimages */
+                                     int   *d_cam_status,            /* nimages */
+                                     float *d_cam_rms,               /* nimages x 2: before, after */
+                                     int   *d_point_obs,             /* max_tracks */
+                                     float *d_history,               /* num_loops x 4 words */
+                                     float *d_cost,                  /* 2: before, after */
+                                     float *d_obs_weight,            /* max_obs; may be NULL */
+                                     int   *d_summary,               /* 8 ints */
+                                     float *d_intrinsics_out,        /* nimages x 4 */
+                                     int   *d_focal);                /* ngroups x 3 words: s_g, M_g, status */
 
 /* The observation lists of misift_export_tracks_batch gated against the current points and cameras and written out
  * again, compact and in export's own format (no reference counterpart): per observation the reprojection error, per
@@ -1745,6 +1859,16 @@ int misift_test_adjust_bundle_robust(int max_tracks, int max_obs, const int *tra
                                      float max_error, float lambda0, int orthonormalise, int loss, float loss_scale,
                                      float *cam_out, float *points_out, int *cam_obs, int *cam_status, float *cam_rms,
                                      int *point_obs, float *history, float *cost, float *obs_weight, int *summary);
+/* The same for misift_adjust_bundle_focal_batch; misift_test_adjust_bundle_robust is this one with ngroups 0 and neither
+ * intrinsics_out nor focal. */
+int misift_test_adjust_bundle_focal(int max_tracks, int max_obs, const int *track_offsets, const misift_track_obs *obs,
+                                    const int *export_summary, const float *points, const int *point_status,
+                                    int nimages, const float *cam, const int *cam_pair, const float *intrinsics,
+                                    int nhold, const int *hold, int min_views, int min_obs, int num_loops, int cg_iters,
+                                    float max_error, float lambda0, int orthonormalise, int loss, float loss_scale,
+                                    int ngroups, const int *group, float *cam_out, float *points_out, int *cam_obs,
+                                    int *cam_status, float *cam_rms, int *point_obs, float *history, float *cost,
+                                    float *obs_weight, int *summary, float *intrinsics_out, int *focal);
 
 /* Test-only, host-only: the whole of misift_filter_tracks_batch on host arrays, every rule compiled from the function
  * its kernels run (filter_core.hpp).  The arguments are those of the call without the context; all pointers are host;

@@ -16,6 +16,9 @@ events around every launch; shares are of their sum.  All nine outputs are compa
 (tests/bundle_cases.expected_bundle) at this size before anything is timed.  Prints one JSON line; --out FILE also writes
 it there.
 
+--focal times misift_adjust_bundle_focal_batch instead: the plain call, the new call with ngroups 0 (which must give the
+plain call's bytes), with all images in one group and with the images dealt to eight groups, the focal given 10 % long
+(both compared with their restatement, tests/bundle_focal_cases.expected_focal), taking turns, for one step and for --num-loops.
 --losses times misift_adjust_bundle_robust_batch instead of (a) and (b): the plain call, loss 0 through the new call,
 Huber at --huber px and Geman-McClure at --geman-mcclure px without d_obs_weight, and Huber with it (one launch more),
 each at num_loops 1 and --num-loops, cg_iters --cg-iters.  The ten take turns within every repetition in one process.  The
@@ -35,6 +38,7 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 from cudasift_amd import capi  # noqa: E402
 import bench_common  # noqa: E402,F401  (puts tests/ on the path)
 import bundle_cases as BC  # noqa: E402
+import bundle_focal_cases as BF  # noqa: E402
 import bundle_robust_cases as BR  # noqa: E402
 import pose_cases as PC  # noqa: E402
 import posegraph_cases as G  # noqa: E402
@@ -58,6 +62,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--reps", type=int, default=40)
     ap.add_argument("--losses", action="store_true")
+    ap.add_argument("--focal", action="store_true")
     ap.add_argument("--huber", type=float, default=2.0)
     ap.add_argument("--geman-mcclure", type=float, default=4.0)
     ap.add_argument("--out", default="")
@@ -167,6 +172,64 @@ def main():
         a.window, nf, n, a.min_len), "pairs": npairs, "tracks": int(P.T), "observations": int(P.O), "images": nf,
         "held": hold, "min_obs": a.min_obs, "lambda0": a.lambda0, "summary": e["summary"].view(np.int32).tolist(),
         "reps": a.reps}
+    if a.focal:
+        # misift_adjust_bundle_focal_batch: the plain call, the new call without a group (the plain call's kernels) and
+        # with all images in one group, the given fx, fy 10 % long; the three take turns
+        Kf = K.copy()
+        Kf[:, :2] *= np.float32(1.1)
+        dk, dfocal = ctx.zeros(16 * nf), ctx.zeros(12 * BF.MAX_GROUPS)
+        groups = {0: np.zeros(nf, np.int32), 1: np.zeros(nf, np.int32),
+                  BF.MAX_GROUPS: (np.arange(nf) % BF.MAX_GROUPS).astype(np.int32)}
+
+        def focal_adjust(num_loops, ngroups):
+            ctx.adjust_bundle_focal_batch(max_tracks, max_obs, doff, dobs, dsum, dpts, dstatus, nf, dcam, dcam_pair,
+                                          Kf if ngroups else K, groups[ngroups], ngroups=ngroups, hold=hold,
+                                          num_loops=num_loops,
+                                          cg_iters=a.cg_iters, loss=BR.NONE, intrinsics_out=dk, focal=dfocal, **args, **outs)
+
+        plain = {k: ctx.download(outs[k], (sizes[k],), np.uint32).tobytes() for k in BC.OUTPUTS}
+        focal_adjust(a.num_loops, 0)
+        ctx.sync()
+        assert all(ctx.download(outs[k], (sizes[k],), np.uint32).tobytes() == plain[k] for k in BC.OUTPUTS)
+        assert ctx.download(dk, (nf, 4), np.float32).tobytes() == K.tobytes()
+        r["focal"] = {"given_focal_factor": 1.1, "cg_iters": a.cg_iters}
+        for ng in (1, BF.MAX_GROUPS):
+            focal_adjust(a.num_loops, ng)
+            ctx.sync()
+            x = BF.expected_focal(BF.focal(dict(case, intrinsics=Kf), groups[ng], ng))
+            for k in BC.OUTPUTS:
+                assert ctx.download(outs[k], (sizes[k],), np.uint32).tobytes() == x[k].tobytes(), (ng, k)
+            assert ctx.download(dk, (4 * nf,), np.uint32).tobytes() == x["intrinsics_out"].tobytes()
+            assert ctx.download(dfocal, (3 * ng,), np.uint32).tobytes() == x["focal"].tobytes()
+            r["focal"]["groups%d" % ng] = {"scale": [round(float(v), 6) for v in x["res"]["scale"][:ng]],
+                                          "steps": x["res"]["trace"], "rms_px_after": round(BF.pooled_rms(x["res"]), 4)}
+        variants = (("plain", lambda loops: adjust(loops, a.cg_iters)), ("groups0", lambda loops: focal_adjust(loops, 0)),
+                    ("group1", lambda loops: focal_adjust(loops, 1)),
+                    ("groups8", lambda loops: focal_adjust(loops, BF.MAX_GROUPS)))
+        names = ["adjust_%s_loops%d_cg%d_events_ms" % (v[0], loops, a.cg_iters) for loops in (1, a.num_loops)
+                 for v in variants]
+        times = {k: [] for k in names}
+        for rep in range(a.warmup + a.reps):
+            t = [events(lambda: v[1](loops)) for loops in (1, a.num_loops) for v in variants]
+            if rep >= a.warmup:
+                for k, v in zip(names, t):
+                    times[k].append(v)
+        percentiles(r, times)
+        r["kernels_ms"], r["launches_per_call"] = {}, {}
+        for v in variants:
+            r["kernels_ms"][v[0]], r["launches_per_call"][v[0]] = launches_of(lambda: v[1](a.num_loops))
+        for loops in (1, a.num_loops):
+            key = "adjust_%%s_loops%d_cg%d_events_ms" % (loops, a.cg_iters)
+            r["ratios_loops%d" % loops] = {"groups0_vs_plain": round(r[key % "groups0"] / r[key % "plain"], 4),
+                                           "group1_vs_plain": round(r[key % "group1"] / r[key % "plain"], 4),
+                                           "groups8_vs_plain": round(r[key % "groups8"] / r[key % "plain"], 4)}
+        print(json.dumps(r), flush=True)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                json.dump(r, f, indent=1)
+        ctx.close()
+        return
     if a.losses:
         variants = (("plain", None, 0.0, False), ("loss0", BR.NONE, 0.0, False), ("huber", BR.HUBER, a.huber, False),
                     ("geman_mcclure", BR.GEMAN_MCCLURE, a.geman_mcclure, False),
