@@ -11,7 +11,7 @@ HIPFLAGS := --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Iinclu
 HIPSRCS  := $(CSRC)/kernels_pyramid.hip $(CSRC)/kernels_dog.hip $(CSRC)/kernels_points.hip \
             $(CSRC)/kernels_match.hip $(CSRC)/misift_host.hip $(CSRC)/homography.hip $(CSRC)/pipeline.hip \
             $(CSRC)/multigpu.hip $(CSRC)/kernels_guided.hip $(CSRC)/kernels_match_i8.hip $(CSRC)/kernels_tracks.hip \
-            $(CSRC)/kernels_fundamental.hip $(CSRC)/kernels_pose.hip \
+            $(CSRC)/kernels_fundamental.hip $(CSRC)/kernels_pose.hip $(CSRC)/kernels_pose_planar.hip \
             $(CSRC)/kernels_posegraph.hip $(CSRC)/kernels_triangulate.hip $(CSRC)/kernels_refine.hip \
             $(CSRC)/kernels_resect.hip $(CSRC)/kernels_bundle.hip $(CSRC)/kernels_filter.hip \
             $(CSRC)/kernels_track_candidates.hip
@@ -20,7 +20,7 @@ HIPOBJS  := $(patsubst $(CSRC)/%.hip,$(BUILD)/%.o,$(HIPSRCS))
 all: cudasift_amd/libmisift.so cudasift_amd/libcudasift.so cudasift_amd/libcudasift_managed.so oracle dropin build/pmc_calib build/valu_rates build/scan_rates build/single_call
 
 $(BUILD)/%.o: $(CSRC)/%.hip $(CSRC)/common.hpp $(CSRC)/chain.hpp $(CSRC)/match_sweep.inc $(CSRC)/match_i8_sweep.inc \
-            $(CSRC)/homography_core.inc $(CSRC)/ransac_batch.hpp $(CSRC)/fundamental_core.hpp $(CSRC)/pose_core.hpp $(CSRC)/posegraph_core.hpp \
+            $(CSRC)/homography_core.inc $(CSRC)/ransac_batch.hpp $(CSRC)/fundamental_core.hpp $(CSRC)/pose_core.hpp $(CSRC)/pose_planar_core.hpp $(CSRC)/posegraph_core.hpp \
             $(CSRC)/epipolar_core.hpp $(CSRC)/triangulate_core.hpp $(CSRC)/refine_core.hpp \
             $(CSRC)/resect_core.hpp $(CSRC)/bundle_core.hpp $(CSRC)/filter_core.hpp $(CSRC)/scan_core.hpp \
             $(CSRC)/track_candidates.hpp \

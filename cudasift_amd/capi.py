@@ -113,6 +113,8 @@ SIGNATURES = {
     "misift_score_fundamental_batch": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _i, _f, _f, _f, _vp, _vp]),
     "misift_improve_fundamental_batch": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _f, _f, _f, _vp, _vp, _vp]),
     "misift_recover_pose_batch": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _f, _f, _f, _vp, _vp, _vp, _vp, _vp]),
+    "misift_recover_pose_planar_batch": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _f, _f, _f, _f, _f, _i, _f, _vp,
+                                              _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "misift_link_poses_batch": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _f, _f, _f, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i,
                                      _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "misift_match_guided_batch": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _f, _i, _vp]),
@@ -167,6 +169,8 @@ SIGNATURES = {
     "misift_test_fundamental_solve9": (_i, [_vp, _i, _vp, _vp]),
     "misift_test_pose_decompose": (_i, [_vp, _vp, _vp, _vp]),
     "misift_test_pose_vote": (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
+    "misift_test_pose_planar_decompose": (_i, [_vp, _vp, _f, _vp, _vp]),
+    "misift_test_pose_planar_vote": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _f, _f, _f, _i, _vp, _vp, _vp, _vp]),
     "misift_test_posegraph_ratio": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _f, _f, _f, _i, _vp, _vp]),
     "misift_test_posegraph_compose": (_i, [_i, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "misift_test_posegraph_capacity": (_i, [_i]),
@@ -790,6 +794,43 @@ class Context:
                                               _dptr(votes), _dptr(xyz)),
               "misift_recover_pose_batch")
         return pose, num_front
+
+    def recover_pose_planar_batch(self, frames, intrinsics, recs, nframes, counts, homography, fundamental=None,
+                                  offsets=None, stride=0, model=None, hf_counts=None, pose=None, num_front=None,
+                                  votes=None, xyz=None, pose_alt=None, plane=None, min_score=0.85, max_ambiguity=0.95,
+                                  thresh_h=1.0, thresh_f=1.0, planar_ratio=0.8, min_inliers=8, min_baseline=0.02):
+        """misift_recover_pose_planar_batch: behind recover_pose_batch, the pose of every frame frames[i] whose matches
+        lie on one plane (model 1) or whose camera only rotates (model 2), from homography[9i..9i+8] (device, set-1 to
+        set-2 pixels, e.g. improve_homography_batch's result) and intrinsics[i] (host, nsel x 8).  With fundamental
+        (device, nsel x 9) an entry is a candidate when its H-inliers at thresh_h number at least min_inliers and
+        planar_ratio times its F-inliers at thresh_f; without it, min_inliers alone decides.  pose, num_front, votes and
+        xyz are recover_pose_batch's own buffers: entries of model 1 and 2 are overwritten, all others are left alone
+        (pose and num_front are allocated here when None).  model (device, nsel ints: -1, 0, 1, 2) and hf_counts
+        (device, nsel x 2 ints: nH, nF) are allocated here when None; pose_alt (device, nsel x 12: the other rotation's
+        better hypothesis) and plane (device, nsel x 4: N in camera 1 and d in units of |t|) are optional.  Returns
+        (model, hf_counts, pose, num_front).  The thresholds default to 1 px as `thresh` does in every sibling wrapper, so
+        the chain's calls agree when none is given; planar_ratio and min_baseline default to the header's 0.8 and 0.02.
+        The records are not written.  Enqueued on the context stream."""
+        frames = np.ascontiguousarray(frames, np.int32).reshape(-1)
+        intrinsics = np.ascontiguousarray(intrinsics, np.float32).reshape(-1, 8)
+        assert len(intrinsics) == len(frames)
+        ns = max(len(frames), 1)
+        if model is None:
+            model = self.zeros(4 * ns)
+        if hf_counts is None:
+            hf_counts = self.zeros(4 * 2 * ns)
+        if pose is None:
+            pose = self.zeros(4 * 12 * ns)
+        if num_front is None:
+            num_front = self.zeros(4 * ns)
+        check(lib().misift_recover_pose_planar_batch(self.h, len(frames), frames.ctypes.data, intrinsics.ctypes.data,
+                                                     _dptr(recs), nframes, _dptr(counts), _dptr(offsets), stride,
+                                                     min_score, max_ambiguity, thresh_h, thresh_f, planar_ratio,
+                                                     min_inliers, min_baseline, _dptr(homography), _dptr(fundamental),
+                                                     _dptr(model), _dptr(hf_counts), _dptr(pose), _dptr(num_front),
+                                                     _dptr(votes), _dptr(xyz), _dptr(pose_alt), _dptr(plane)),
+              "misift_recover_pose_planar_batch")
+        return model, hf_counts, pose, num_front
 
     def link_poses_batch(self, pairs, nimages, rows, row_counts, max_pts, pose, num_front, xyz, links, seed_pair,
                          root_image, walk, min_common=8, link_ratio=None, link_common=None, pair_scale=None, cam=None,

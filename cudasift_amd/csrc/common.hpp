@@ -630,6 +630,22 @@ int launch_improve_fundamental_batch(misift_ctx *ctx, int nsel, const int *h_fra
 int launch_recover_pose_batch(misift_ctx *ctx, int nsel, const int *h_frames, const float *h_intrinsics,
                               const BatchLayout &set, float min_score, float max_ambiguity, float thresh,
                               const float *F, float *pose, int *num_front, int *votes, float *xyz);
+// misift_recover_pose_planar_batch (kernels_pose_planar.hip): one launch, no temp; h_intrinsics as above.  F and the last
+// four outputs may be NULL
+struct PlanarPoseParams {
+  float min_score, max_ambiguity, thresh_h, thresh_f, planar_ratio;
+  int min_inliers;
+  float min_baseline;
+};
+struct PlanarPoseOut {
+  int *model, *hf_counts;
+  float *pose;
+  int *num_front, *votes;
+  float *xyz, *pose_alt, *plane;
+};
+int launch_recover_pose_planar_batch(misift_ctx *ctx, int nsel, const int *h_frames, const float *h_intrinsics,
+                                     const BatchLayout &set, const PlanarPoseParams &p, const float *H, const float *F,
+                                     const PlanarPoseOut &out);
 // misift_match_guided_batch (kernels_guided.hip): bin + match.  h_pair_d: the index of each pair's set-2 frame among
 // the nd distinct ones, h_distinct; temp from misift_ensure_tmp, sized from npairs, nd and max_pts only
 size_t match_guided_batch_tmp_bytes(int npairs, int nd, int max_pts);

@@ -2245,7 +2245,7 @@ extern "C" int misift_match_pairs_batch(misift_ctx *ctx, int npairs, const int *
                         });
 }
 
-// The six frame-list calls (one entry per selected frame of one set of records) share everything but the checks that are
+// The seven frame-list calls (one entry per selected frame of one set of records) share everything but the checks that are
 // an entry point's own; the counterpart of pair_match_call.  null_failed: NULL, or the text of the entry point's own NULL
 // check that failed.  own(): evaluated behind the NULL checks and the layout only, NULL or the text of the entry point's
 // own check that failed.  Then the frames of the list (each frame in at most one entry), and launch(h_frames, h_extra,
@@ -2382,6 +2382,36 @@ extern "C" int misift_recover_pose_batch(misift_ctx *ctx, int nsel, const int *f
       [&](const int *h_frames, const void *h_intrinsics, const BatchLayout &set) {
         return launch_recover_pose_batch(ctx, nsel, h_frames, (const float *)h_intrinsics, set, min_score,
                                          max_ambiguity, thresh, d_fundamental, d_pose, d_num_front, d_votes, d_xyz);
+      });
+}
+
+// Behind misift_recover_pose_batch: the pose of each frame pair that is planar or rotation-only from its homography,
+// written over that call's outputs; every other entry is left alone.
+extern "C" int misift_recover_pose_planar_batch(misift_ctx *ctx, int nsel, const int *frames, const float *intrinsics,
+                                                const void *d_recs, int nframes, const int *d_counts,
+                                                const int *d_offsets, int stride, float min_score, float max_ambiguity,
+                                                float thresh_h, float thresh_f, float planar_ratio, int min_inliers,
+                                                float min_baseline, const float *d_homography,
+                                                const float *d_fundamental, int *d_model, int *d_hf_counts,
+                                                float *d_pose, int *d_num_front, int *d_votes, float *d_xyz,
+                                                float *d_pose_alt, float *d_plane)
+{
+  const PairSide s{d_recs, nframes, d_counts, d_offsets, stride};
+  return frame_list_call(
+      __func__, ctx, nsel, frames, s,
+      OWN_CHECK(intrinsics && d_homography && d_model && d_hf_counts && d_pose && d_num_front),
+      HostList{intrinsics, sizeof(float) * 8 * (size_t)nsel},
+      [&]() -> const char * {
+        for (int i = 0; i < nsel; i++)
+          if (!intrinsics_usable(intrinsics + (size_t)8 * i)) return "intrinsics_usable(intrinsics + (size_t)8 * i)";
+        return OWN_CHECK(thresh_h > 0.0f && thresh_f > 0.0f && planar_ratio >= 0.0f && min_inliers >= 4 &&
+                         min_baseline >= 0.0f);                   // a NaN fails each
+      },
+      [&](const int *h_frames, const void *h_intrinsics, const BatchLayout &set) {
+        const PlanarPoseParams p{min_score, max_ambiguity, thresh_h, thresh_f, planar_ratio, min_inliers, min_baseline};
+        const PlanarPoseOut out{d_model, d_hf_counts, d_pose, d_num_front, d_votes, d_xyz, d_pose_alt, d_plane};
+        return launch_recover_pose_planar_batch(ctx, nsel, h_frames, (const float *)h_intrinsics, set, p, d_homography,
+                                                d_fundamental, out);
       });
 }
 

@@ -442,7 +442,7 @@ int misift_match_pairs_batch(misift_ctx *ctx, int npairs, const int *pairs,
  *   - misift_match_batch, misift_match_pairs_batch, misift_quantize_batch, misift_match_batch_i8,
  *     misift_match_pairs_batch_i8, misift_find_homography_batch, misift_improve_homography_batch,
  *     misift_find_fundamental_batch, misift_score_fundamental_batch, misift_improve_fundamental_batch,
- *     misift_recover_pose_batch, misift_link_poses_batch, misift_match_guided_batch,
+ *     misift_recover_pose_batch, misift_recover_pose_planar_batch, misift_link_poses_batch, misift_match_guided_batch,
  *     misift_match_epipolar_batch, misift_link_tracks_batch, misift_export_tracks_batch,
  *     misift_triangulate_tracks_batch and misift_refine_cameras_batch (which run on the context stream) on a batch's
  *     packed records: make the context stream wait for that batch first
@@ -759,6 +759,96 @@ int misift_recover_pose_batch(misift_ctx *ctx, int nsel, const int *frames,
                               int   *d_num_front /* nsel */,
                               int   *d_votes     /* nsel x 4, may be NULL */,
                               float *d_xyz       /* 4 floats per record, indexed like d_recs, may be NULL */);
+/* Relative camera pose per pair from batch homographies, for planar and rotation-only pairs (no reference counterpart).
+ * A fundamental matrix is degenerate where every match lies on one plane (the 8-point solve fits a one-parameter family
+ * and misift_recover_pose_batch decomposes an arbitrary member into a confident wrong pose) and undefined where the
+ * camera only rotates.  This call sits behind misift_recover_pose_batch in the chain,
+ *   ... find_fundamental -> improve_fundamental -> recover_pose -> recover_pose_planar -> link_poses ...,
+ * with d_homography from misift_find_homography_batch / misift_improve_homography_batch over the same frames, and
+ * OVERWRITES d_pose, d_num_front, d_votes and the frame's d_xyz rows of exactly those entries it judges planar (model 1)
+ * or rotation-only (model 2); an entry it judges general (model 0) or cannot decompose (model -1) keeps what
+ * misift_recover_pose_batch wrote: apart from d_model and d_hf_counts, nothing of such an entry is written.  With
+ * d_fundamental NULL every entry with enough H-inliers is a candidate: the stand-alone use behind the homography calls.
+ * Exactly as in misift_recover_pose_batch: frames, layouts and count -1, the copied host lists (`frames`, and
+ * `intrinsics` with it, intrinsics[8i..8i+7] = fx1 fy1 cx1 cy1 fx2 fy2 cx2 cy2) with no frame repeated, stream order on
+ * the context stream with no host synchronisation and no host read, ordering behind batches in flight, the pose
+ * convention X2 = R . X1 + t with |t| = 1, the gate score > min_score && ambiguity < max_ambiguity, the arithmetic rules
+ * (fp32, every operation rounded, only + - * /, sqrtf and fabsf, no contraction, a comparison with a NaN is false, a
+ * stored NaN is 0x7fc00000) and its MISIFT_EINVAL list, with d_homography, d_model, d_hf_counts, d_pose and d_num_front the
+ * pointers that must not be NULL (d_fundamental may be).  Five more cases are MISIFT_EINVAL, checked on the host before
+ * anything is enqueued: thresh_h or thresh_f NaN or <= 0, planar_ratio NaN or < 0, min_inliers < 4, min_baseline NaN or
+ * < 0.  d_recs is not written.  One launch whatever nsel, no temp memory.
+ *   d_homography[9i..9i+8] = H, row-major, set-1 pixel positions to set-2 pixel positions, all nine entries used as
+ *   given.  Entry i has frame f and n = max(d_counts[f], 0) records.  A sum written a*b + c*d + e*f is taken left to
+ *   right, (a*b + c*d) + e*f; every other association is written out.  A cross product's component is (a*b) - (c*d).
+ *   1. Count, over the records that pass the gate.  deno = (h6*x1 + h7*y1) + h8, nomx = (h0*x1 + h1*y1) + h2, nomy =
+ *      (h3*x1 + h4*y1) + h5, errx = x2*deno - nomx, erry = y2*deno - nomy; the record is an H-INLIER iff
+ *      errx*errx + erry*erry < (thresh_h*thresh_h) * (deno*deno).  nH = the H-inliers.  These are plain rounded products:
+ *      the round-toward-zero products of the reference's homography search (misift_find_homography_batch) are not
+ *      restated here, so a borderline record may count differently from that call's own count.  nF = |inl(F)| of
+ *      misift_improve_fundamental_batch under d_fundamental[9i..9i+8] at thresh_f, 0 when d_fundamental is NULL.
+ *      d_hf_counts[2i] = nH, d_hf_counts[2i+1] = nF, always.
+ *   2. Decide.  d_model[i] = 0 if nH < min_inliers, or if d_fundamental is given and (float)nH >= planar_ratio *
+ *      (float)nF is false.  planar_ratio 0.8 is recommended (COLMAP's max_H_inlier_ratio).  Nothing else of a model-0
+ *      entry is written.
+ *   3. Normalise.  A = K2^-1 . H . K1: G[r][0] = H[r][0]*fx1, G[r][1] = H[r][1]*fy1, G[r][2] = (H[r][0]*cx1 +
+ *      H[r][1]*cy1) + H[r][2]; A[0][c] = (G[0][c] - cx2*G[2][c]) / fx2, A[1][c] = (G[1][c] - cy2*G[2][c]) / fy2, A[2][c] =
+ *      G[2][c].  m = the largest fabsf of A.  The entry is INVALID (d_model[i] = -1, nothing else written) if an entry of
+ *      A is non-finite or m is 0.  A = A / m entry by entry.  det = (A00*(A11*A22 - A12*A21) - A01*(A10*A22 - A12*A20)) +
+ *      A02*(A10*A21 - A11*A20).  If det < 0 every entry of A is negated and det is computed again; INVALID if det > 0 is
+ *      then false.  (H and -H are one homography; the one with the positive determinant keeps the camera on one side of
+ *      the plane it sees.)
+ *   4. Jacobi.  B = A, V = I; six sweeps of step 2 of misift_recover_pose_batch over the column pairs (0,1), (0,2),
+ *      (1,2), applied to B and V alike.  w[j] = the squared norm of column j of B.  hi = the index of the largest w,
+ *      searched with a strict '>' (the first maximum wins); mid = the larger of the other two (again the first wins);
+ *      lo = the third.  INVALID unless w[lo] > 0.  s1 = w[hi] / w[mid], s3 = w[lo] / w[mid].
+ *   5. Rotation-only.  b = sqrtf(s1) - sqrtf(s3): |t| over the distance of the plane.  If b > min_baseline is false,
+ *      d_model[i] = 2: with u_j = B.j / sqrtf(w[j]), R[r][c] = (u_0[r]*V[c][0] + u_1[r]*V[c][1]) + u_2[r]*V[c][2], and
+ *      t = 0.  d_pose = R then three zeros, d_pose_alt the same twelve floats, d_num_front[i] = 0 (so
+ *      misift_link_poses_batch skips the pair), d_votes four zeros, d_plane four zeros, and every d_xyz row of the frame
+ *      four quiet NaNs.  (A fit of 400 matches with 0.5 px noise under a pure rotation leaves b near 1e-3; min_baseline
+ *      0.02 separates that from a baseline of a fiftieth of the plane's distance.)
+ *   6. Planar, d_model[i] = 1.  Hn = A (after the sign, before the sweeps) / sqrtf(w[mid]).  v1, v2, v3 = the columns
+ *      hi, mid, lo of V.  a = sqrtf(1 - s3), c = sqrtf(s1 - 1), dd = sqrtf(s1 - s3); ua = (a*v1 + c*v3) / dd and ub =
+ *      (a*v1 - c*v3) / dd, component by component.  For u = ua and u = ub: N = v2 x u; p = Hn . v2 and q = Hn . u (each
+ *      row a three-term sum); s = p x q; R[r][c] = (p[r]*v2[c] + q[r]*u[c]) + s[r]*N[c]; T[r] = ((Hn[r][0] - R[r][0])*N[0]
+ *      + (Hn[r][1] - R[r][1])*N[1]) + (Hn[r][2] - R[r][2])*N[2]; |T| = sqrtf(T.T); t = T / |T|, d = 1 / |T|.  INVALID if a
+ *      |T| is not finite and > 0.  The plane is N . X1 = d in the frame of camera 1, d in units of |t|.  The hypotheses
+ *      are k = 0: (Ra, ta, Na, da), 1: (Ra, -ta, -Na, da), 2: (Rb, tb, Nb, db), 3: (Rb, -tb, -Nb, db).
+ *   7. Vote, over the records that pass the gate (H-inliers or not).  For k = 0 and k = 2, F_k = K2^-T . [t]x . R .
+ *      K1^-1: E[0][c] = t1*R[2][c] - t2*R[1][c], E[1][c] = t2*R[0][c] - t0*R[2][c], E[2][c] = t0*R[1][c] - t1*R[0][c];
+ *      G[r][0] = E[r][0] / fx1, G[r][1] = E[r][1] / fy1, G[r][2] = (E[r][2] - G[r][0]*cx1) - G[r][1]*cy1; F[0][c] =
+ *      G[0][c] / fx2, F[1][c] = G[1][c] / fy2, F[2][c] = (G[2][c] - cx2*F[0][c]) - cy2*F[1][c].  Under -t, F changes sign
+ *      and the test does not, so k = 1 and 3 share F_0 and F_2.  A record counts for k iff e*e < (thresh_f*thresh_f) * den
+ *      under F_k and it is IN FRONT under (R_k, t_k), both exactly as in misift_recover_pose_batch.  Records on the plane
+ *      satisfy both rotations' epipolar geometry by construction and vote through their depths alone, which separates
+ *      +-N; records off the plane separate Ra from Rb.  Pick: the largest vote at the smallest k.  The alternative: of
+ *      the two hypotheses of the other rotation, the one with the larger vote (the smaller k on a tie).  The two-fold
+ *      ambiguity of an exactly planar scene is real: no two-view test resolves it.  d_votes and d_pose_alt are how the
+ *      caller sees it, and a third view is how it is resolved; this call does not do that.
+ *   8. Outputs of a model-1 entry, as misift_recover_pose_batch writes them: d_pose[12i..12i+11] = R then t of the pick,
+ *      d_num_front[i] = its vote, d_votes[4i..4i+3] = the four votes, d_xyz for EVERY record r < n of the frame under the
+ *      pick (step 7 of that call, the entry valid); d_pose_alt[12i..12i+11] = R then t of the alternative; d_plane[4i..
+ *      4i+3] = N then d of the pick.  d_votes, d_xyz, d_pose_alt and d_plane may each be NULL. */
+int misift_recover_pose_planar_batch(misift_ctx *ctx, int nsel, const int *frames,
+                                     const float *intrinsics /* host, nsel x 8, as misift_recover_pose_batch, copied */,
+                                     const void *d_recs, int nframes, const int *d_counts, const int *d_offsets,
+                                     int stride, float min_score, float max_ambiguity,
+                                     float thresh_h, float thresh_f, float planar_ratio, int min_inliers,
+                                     float min_baseline,
+                                     const float *d_homography  /* nsel x 9, set-1 px -> set-2 px */,
+                                     const float *d_fundamental /* nsel x 9, may be NULL */,
+                                     int   *d_model      /* nsel: -1 invalid, 0 general (entry left alone), 1 planar,
+                                                            2 rotation */,
+                                     int   *d_hf_counts  /* nsel x 2: nH, nF */,
+                                     float *d_pose       /* nsel x 12, written for model 1 and 2 only */,
+                                     int   *d_num_front  /* nsel, likewise */,
+                                     int   *d_votes      /* nsel x 4, likewise, may be NULL */,
+                                     float *d_xyz        /* 4 floats per record, rows of model 1 and 2 entries only,
+                                                            may be NULL */,
+                                     float *d_pose_alt   /* nsel x 12, likewise, may be NULL */,
+                                     float *d_plane      /* nsel x 4: N (camera 1) and d in units of |t|, likewise, may
+                                                            be NULL */);
 /* Homography-guided matching (no reference counterpart as an API: MatchAll, mainSift.cpp:95-147, does it as a host
  * diagnostic; the C++ drop-in headers, cudaSift.h, do not change): for each pair i = (f1, f2) = (pairs[2i], pairs[2i+1]),
  * every record of frame f1 of set 1 is matched only against the records of frame f2 of set 2 that lie within `radius`
@@ -1812,6 +1902,20 @@ int misift_test_fundamental_solve9(const float *M81, int lanes, float *n9, int *
 int misift_test_pose_decompose(const float *F9, const float *K8, float *out48, int *valid);
 int misift_test_pose_vote(const float *pose12, const float *K8, const float *xy, int n, unsigned char *front_out,
                           float *xyz_out);
+/* Test-only, host-only: steps 3-6 with the two F of step 7, and steps 1 and 7 record by record, of
+ * misift_recover_pose_planar_batch, compiled from the functions the kernel runs.  decompose: *model = -1, 1 or 2 for H9
+ * under K8 and min_baseline; out84 = s1, s3, then for k = 0..3 R and t (12) and N and d (4) of hypothesis k, then F_0 and
+ * F_2 (9 each).  Model 2 gives R, t = 0 and zeros for the planes and the F; model -1 gives 84 zeros.  vote: for record
+ * r < n with xy[4r..4r+3] = x1 y1 x2 y2 and gate[r] = whether it passes the gate: h_in[r] = 1 iff it is an H-inlier of H9
+ * at thresh_h, f_in[r] = 1 iff F9 is given and it is an inlier of F9 at thresh_f, votes[4r+k] = 1 iff it counts for
+ * hypothesis k of hyp84 (decompose's out84) at thresh_f; decision9 = nH, nF, 1 iff step 2 lets the entry go on under
+ * planar_ratio and min_inliers (F9 NULL: no F is given), the four votes, the pick and the alternative of step 7.  The d_xyz
+ * rows are those of misift_test_pose_vote. */
+int misift_test_pose_planar_decompose(const float *H9, const float *K8, float min_baseline, float *out84, int *model);
+int misift_test_pose_planar_vote(const float *H9, const float *F9, const float *hyp84, const float *K8, const float *xy,
+                                 const unsigned char *gate, int n, float thresh_h, float thresh_f, float planar_ratio,
+                                 int min_inliers, unsigned char *h_in, unsigned char *f_in, unsigned char *votes,
+                                 int *decision9);
 /* Test-only, host-only: step 1 of misift_link_poses_batch for one link and steps 2 and 3 for a whole graph, compiled from
  * the functions the kernels run.  ratio: rows_p / rows_q are row 0 of the two pairs (host memory, 576-byte records),
  * xyz_p / xyz_q their d_xyz rows, count_p / count_q their row counts as d_row_counts holds them; *ratio and *common = what
