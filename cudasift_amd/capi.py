@@ -179,6 +179,7 @@ SIGNATURES = {
     "misift_test_guided_gather": (_i, [_vp, _vp, _i, _vp, _i, _f, _vp, _vp, _vp]),
     "misift_test_frame_shares": (_i, [_i, _i, C.c_void_p, C.c_void_p]),
     "misift_test_pyramid_layout": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "misift_test_describe_detections": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp]),
     "misift_test_set_knob": (_i, [_vp, C.c_char_p, C.c_double]),
     "misift_test_knob_names": (C.c_char_p, []),
     "misift_test_set_guard": (_i, [_i]),
@@ -544,6 +545,35 @@ class Context:
         check(lib().misift_descriptors(self.h, src.ptr, w, h, p, subsampling, octave, d.ptr, max_pts),
               "misift_descriptors")
         return self.download(d, (len(pts),), POINT_DTYPE), self.get_counters()
+
+    def describe_detections_raw(self, levels, dets, pts_ptr, max_pts, scale_up=False):
+        """misift_test_describe_detections on host levels and detections, records to the device pointer pts_ptr.
+        levels[f][k]: the float32 image of octave k + 1 (k = 0: the coarsest level) of frame f, the last one the finest
+        (its size is the call's width x height); dets[f][k]: [n, 5] float32 (xpos, ypos, scale, sharpness, edgeness).
+        Returns (rc, numPts[nframes]); rc != 0 is NOT raised."""
+        nframes, noct = len(levels), len(levels[0])
+        h, w = levels[0][-1].shape
+        lv = [np.ascontiguousarray(a, np.float32) for f in levels for a in f]
+        dd = [np.ascontiguousarray(a, np.float32).reshape(-1, 5) for f in dets for a in f]
+        assert len(lv) == len(dd) == nframes * noct
+        ptrs = (C.c_void_p * len(lv))(*[a.ctypes.data for a in lv])
+        counts = np.array([len(a) for a in dd], np.int32)
+        flat = np.ascontiguousarray(np.concatenate(dd) if dd else np.zeros((0, 5), np.float32))
+        n = np.full(nframes, -1, np.int32)
+        rc = lib().misift_test_describe_detections(self.h, nframes, w, h, noct, int(scale_up), ptrs,
+                                                   flat.ctypes.data if len(flat) else None, counts.ctypes.data, pts_ptr,
+                                                   max_pts, n.ctypes.data)
+        return rc, n
+
+    def describe_detections(self, levels, dets, max_pts, scale_up=False):
+        """The production per-keypoint kernels (binning, orient_all, descr_all, descr_big) on planted detections: see
+        describe_detections_raw.  Returns (points[nframes, max_pts], numPts[nframes], counters[nframes, 17])."""
+        nframes = len(levels)
+        pts = self.zeros(576 * max_pts * nframes)
+        rc, n = self.describe_detections_raw(levels, dets, pts.ptr, max_pts, scale_up)
+        check(rc, "misift_test_describe_detections")
+        cnt = np.stack([self.get_counters(f) for f in range(nframes)])
+        return self.download(pts, (nframes, max_pts), POINT_DTYPE), n, cnt
 
     # ---- whole path
     def extract(self, img, num_octaves=5, init_blur=1.0, thresh=3.0, lowest_scale=0.0, scale_up=False,

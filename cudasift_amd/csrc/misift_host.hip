@@ -1183,6 +1183,68 @@ bool misift_tiny_call(int width, int height, int num_octaves)
   return width < 16 || height < 16 || (width >> (num_octaves - 1)) < 8 || (height >> (num_octaves - 1)) < 8;
 }
 
+// The level table of the merged-octave kernels for a call's pyramid (dims[o]: level o as pyramid_levels lays it out, off =
+// float offset inside a frame's arena; SS = floats between the frames' arenas).  Returns the candidate slots one frame
+// needs (the sum of the octaves' cand_cap).
+static unsigned fill_pyramid_info(const misift_ctx *ctx, PyramidInfo *P, const LevelDim *dims, int num_octaves, int nframes,
+                                  long long SS, float lowest_scale, int scale_up)
+{
+  P->noct = num_octaves; P->nframes = nframes; P->frame_stride = SS;
+  P->fix_numpts = ctx->opt.fix_numpts ? 1 : 0;
+  P->patch_reach = ctx->patch_reach;
+  P->out_scale = scale_up ? 0.5f : 1.0f;             // RescalePositions (cudaSiftH.cu:130) folded into the record write
+  unsigned off = 0;
+  for (int o = 1; o <= num_octaves; o++) {
+    OctaveInfo &L = P->o[o];
+    L.w = dims[o].w; L.h = dims[o].h; L.p = dims[o].p;
+    L.img_off = dims[o].off;
+    L.subsampling = (float)(1 << (num_octaves - o));
+    L.lowest_scale = lowest_scale / L.subsampling;
+    size_t c = (size_t)L.w * L.h / 4;
+    if (c < 16384) c = 16384;
+    L.cand_cap = (unsigned)c;
+    L.cand_off = off;
+    off += L.cand_cap;
+  }
+  return off;
+}
+
+// The per-keypoint tail of the merged-octave sequence: every octave's detections wait in the staging area (d_det, their
+// counts in CNT_DET + o) and the pyramid levels in the arena; this orders them, computes orientations and descriptors and
+// writes the records in the reference's segment order.  Called by misift_extract_enqueue behind refine_all, and by
+// misift_test_describe_detections on detections the caller supplies (allow_fuse = false: never the fused launch).
+static int enqueue_keypoint_tail(misift_ctx *ctx, const float *d_scratch, const PyramidInfo &P, SiftPointD *pts, int max_pts,
+                                 bool allow_fuse)
+{
+  int rc;
+  // (a counting sort per (octave, frame) is one workgroup each: for a frame or two it is a dependent dispatch that buys
+  //  nothing — the keypoints of one frame share the caches anyway)
+  const bool binned = (ctx->bin_detections && P.nframes >= ctx->bin_min_frames) || ctx->opt.deterministic;
+  ctx->cur_binned = binned ? 1 : 0;
+  ctx->cur_balanced = 0;              // set by launch_bin_detections (its extra workgroup builds the block tables) or, without binning, by build_block_maps
+  if (binned) {                       // spatial order for the per-keypoint kernels (L1/L2 reuse between neighbours);
+    rc = launch_bin_detections(ctx, P, max_pts);      // deterministic mode: a total order
+    if (rc) return rc;
+  }
+  // a frame or two: orientations and descriptors in one launch (the descriptor pass of a workgroup waits in the kernel for
+  // the coarser octaves' orientations, whose duplicate counts decide where its records go)
+  // (off by default: measured 12 us slower than the two launches)
+  if (allow_fuse && ctx->fuse_orient && !binned && !ctx->pack_dst && P.nframes <= ctx->small_frames && ctx->tile_descr && !ctx->tile_orient &&
+      !ctx->in_capture)
+    return launch_orient_descr_fused(ctx, d_scratch, P, pts, max_pts);
+  rc = launch_orient_all(ctx, d_scratch, P, pts, max_pts);
+  if (rc) return rc;
+  if (ctx->opt.deterministic) {       // second-orientation slots in keypoint order instead of atomic order
+    rc = launch_renumber_dups(ctx, P, max_pts);
+    if (rc) return rc;
+  }
+  if (ctx->pack_dst) {                // counts and offsets are known as soon as the orientations are: pack while writing
+    rc = launch_export_counts_staged(ctx, P.nframes, P.noct, max_pts, ctx->pack_counts, ctx->pack_offsets);
+    if (rc) return rc;
+  }
+  return launch_descr_all(ctx, d_scratch, P, pts, max_pts, ctx->pack_offsets, ctx->pack_dst);
+}
+
 // Enqueue the whole launch sequence of one batch on the context stream (no synchronisation).
 // d_imgs: fp32 frames, or 8-bit frames when src_u8 (pitch / frame_stride in source elements).
 int misift_extract_enqueue(misift_ctx *ctx, const void *d_imgs, int src_u8, int nframes, long long frame_stride,
@@ -1290,24 +1352,12 @@ int misift_extract_enqueue(misift_ctx *ctx, const void *d_imgs, int src_u8, int 
   memset(&P, 0, sizeof(P));
   std::vector<LaplaceTaps> tapsv(num_octaves + 1);
   if (ctx->opt.fused) {
-    P.noct = num_octaves; P.nframes = nframes; P.frame_stride = SS;
-    P.fix_numpts = ctx->opt.fix_numpts ? 1 : 0;
-    P.patch_reach = ctx->patch_reach;
-    P.out_scale = scale_up ? 0.5f : 1.0f;             // RescalePositions (cudaSiftH.cu:130) folded into the record write
-    unsigned off = 0;
+    LevelDim dims[MISIFT_MAX_OCTAVES + 1];
     for (int o = 1; o <= num_octaves; o++) {
-      OctaveInfo &L = P.o[o];
-      L.w = lv[o].w; L.h = lv[o].h; L.p = lv[o].p;
-      L.img_off = (long long)(lv[o].img - d_scratch);
-      L.subsampling = (float)(1 << (num_octaves - o));
-      L.lowest_scale = lowest_scale / L.subsampling;
-      size_t c = (size_t)L.w * L.h / 4;
-      if (c < 16384) c = 16384;
-      L.cand_cap = (unsigned)c;
-      L.cand_off = off;
-      off += L.cand_cap;
+      dims[o].w = lv[o].w; dims[o].h = lv[o].h; dims[o].p = lv[o].p; dims[o].off = (long long)(lv[o].img - d_scratch);
       tapsv[o] = octave_taps(table, o);
     }
+    const unsigned off = fill_pyramid_info(ctx, &P, dims, num_octaves, nframes, SS, lowest_scale, scale_up);
     rc = misift_ensure_frames(ctx, nframes, off);
     if (rc) return rc;
     // the staging area is indexed with the CURRENT max_pts (kernels use it as the per-octave stride)
@@ -1392,32 +1442,7 @@ int misift_extract_enqueue(misift_ctx *ctx, const void *d_imgs, int src_u8, int 
     }
     rc = launch_refine_all(ctx, d_scratch, P, tapsv.data(), thresh, 10.0f, 1.0f / NUM_SCALES, max_pts);
     if (rc) return rc;
-    // (a counting sort per (octave, frame) is one workgroup each: for a frame or two it is a dependent dispatch that buys
-    //  nothing — the keypoints of one frame share the caches anyway)
-    const bool binned = (ctx->bin_detections && nframes >= ctx->bin_min_frames) || ctx->opt.deterministic;
-    ctx->cur_binned = binned ? 1 : 0;
-    ctx->cur_balanced = 0;              // set by launch_bin_detections (its extra workgroup builds the block tables) or, without binning, by build_block_maps
-    if (binned) {                       // spatial order for the per-keypoint kernels (L1/L2 reuse between neighbours);
-      rc = launch_bin_detections(ctx, P, max_pts);      // deterministic mode: a total order
-      if (rc) return rc;
-    }
-    // a frame or two: orientations and descriptors in one launch (the descriptor pass of a workgroup waits in the kernel for
-    // the coarser octaves' orientations, whose duplicate counts decide where its records go)
-    // (off by default: measured 12 us slower than the two launches)
-    if (ctx->fuse_orient && !binned && !ctx->pack_dst && nframes <= ctx->small_frames && ctx->tile_descr && !ctx->tile_orient &&
-        !ctx->in_capture)
-      return launch_orient_descr_fused(ctx, d_scratch, P, pts, max_pts);
-    rc = launch_orient_all(ctx, d_scratch, P, pts, max_pts);
-    if (rc) return rc;
-    if (ctx->opt.deterministic) {       // second-orientation slots in keypoint order instead of atomic order
-      rc = launch_renumber_dups(ctx, P, max_pts);
-      if (rc) return rc;
-    }
-    if (ctx->pack_dst) {                // counts and offsets are known as soon as the orientations are: pack while writing
-      rc = launch_export_counts_staged(ctx, nframes, num_octaves, max_pts, ctx->pack_counts, ctx->pack_offsets);
-      if (rc) return rc;
-    }
-    return launch_descr_all(ctx, d_scratch, P, pts, max_pts, ctx->pack_offsets, ctx->pack_dst);
+    return enqueue_keypoint_tail(ctx, d_scratch, P, pts, max_pts, true);
   }
   // --- octaves, coarsest first (cudaSiftH.cu:161 after the recursion)
   for (int o = 1; o <= num_octaves; o++) {
@@ -1705,6 +1730,89 @@ int misift_extract_sync(misift_ctx *ctx, const void *d_imgs, int src_u8, int nfr
   }
   ctx->opt.fused = fused_saved;
   return MISIFT_OK;
+}
+
+// Test-only (include/misift.h): the per-keypoint tail of the merged-octave sequence on detections and pyramid levels the
+// caller supplies.  Everything the tail reads is set up as misift_extract_enqueue sets it up — arena layout, level table,
+// candidate buffer (descr_big's list lives there), staging area, counter blocks — and the counters come back through
+// read_counts, so a call of a frame or two runs the folded shape with its on-demand descr_big launch.
+extern "C" int misift_test_describe_detections(misift_ctx *ctx, int nframes, int width, int height, int num_octaves,
+                                               int scale_up, const float *const *levels, const float *dets,
+                                               const int *det_counts, void *d_pts, int max_pts, int *num_pts)
+{
+  ARG_CHECK(ctx && levels && det_counts && d_pts && num_pts);
+  ARG_CHECK(nframes >= 1 && width >= 1 && height >= 1 && max_pts >= 1);
+  ARG_CHECK(num_octaves >= 1 && num_octaves <= MISIFT_MAX_OCTAVES);
+  ARG_CHECK(width < 16384 && height < 16384);
+  LevelDim dims[MISIFT_MAX_OCTAVES + 1];
+  pyramid_levels(width, height, num_octaves, 0, dims);
+  ARG_CHECK(dims[1].w >= 1 && dims[1].h >= 1);                  // the coarsest level holds a pixel, hence all do
+  long long total = 0;
+  for (int k = 0; k < nframes * num_octaves; k++) {
+    ARG_CHECK(levels[k] != nullptr && det_counts[k] >= 0);
+    total += det_counts[k];
+  }
+  ARG_CHECK(total == 0 || dets != nullptr);
+  HIP_TRY(hipSetDevice(ctx->device));
+  extra(ctx)->last_lane = nullptr;      // this call runs on the context itself, like misift_extract_enqueue
+  extra(ctx)->last_done = nullptr;
+  size_t cap = (size_t)width * height / 4;
+  if (cap < 65536) cap = 65536;
+  int rc = misift_ensure_frames(ctx, nframes, cap);
+  if (rc) return rc;
+  const size_t S = misift_scratch_floats(width, height, num_octaves, 0);
+  if (ctx->own_scratch_floats < S * nframes) {
+    if (ctx->d_own_scratch) HIP_TRY(misift_dev_free(ctx->d_own_scratch));
+    ctx->d_own_scratch = nullptr; ctx->own_scratch_floats = 0;
+    HIP_TRY(misift_dev_alloc((void **)&ctx->d_own_scratch, sizeof(float) * S * nframes, "own_scratch"));
+    ctx->own_scratch_floats = S * nframes;
+  }
+  float *d_scratch = ctx->d_own_scratch;
+  ctx->exported = 0;
+  PyramidInfo P;
+  memset(&P, 0, sizeof(P));
+  const unsigned off = fill_pyramid_info(ctx, &P, dims, num_octaves, nframes, (long long)S, 0.0f, scale_up);
+  rc = misift_ensure_frames(ctx, nframes, off);
+  if (rc) return rc;
+  rc = ensure_det(ctx, nframes, max_pts);
+  if (rc) return rc;
+  // the counter blocks as the prefilter leaves them (all zero, the spare blocks behind the last frame's included), then
+  // what refine_all adds: the octaves' detection counts (uncapped) and the detections that found no room
+  std::vector<unsigned> counters((size_t)CNT_STRIDE * ((size_t)nframes + CNT_SPARE_BLOCKS), 0u);
+  std::vector<Detection> staged;
+  const float *src = dets;
+  for (int f = 0; f < nframes; f++)
+    for (int o = 1; o <= num_octaves; o++) {
+      const int k = f * num_octaves + (o - 1), n = det_counts[k], kept = n < max_pts ? n : max_pts;
+      HIP_TRY(hipMemcpy2DAsync(d_scratch + (size_t)f * S + dims[o].off, sizeof(float) * (size_t)dims[o].p, levels[k],
+                               sizeof(float) * (size_t)dims[o].w, sizeof(float) * (size_t)dims[o].w, dims[o].h,
+                               hipMemcpyHostToDevice, ctx->stream));
+      counters[(size_t)f * CNT_STRIDE + CNT_DET + o] = (unsigned)n;
+      counters[(size_t)f * CNT_STRIDE + CNT_PTOVF] += (unsigned)(n - kept);
+      staged.resize((size_t)kept);
+      for (int i = 0; i < kept; i++) {
+        const float *d = src + 5 * (size_t)i;
+        staged[i] = Detection{d[0], d[1], d[2], d[3], d[4], 0.0f, 0.0f, -1};
+      }
+      src += 5 * (size_t)n;
+      if (kept) {
+        HIP_TRY(hipMemcpyAsync(ctx->d_det + ((size_t)f * MISIFT_MAX_OCTAVES + (o - 1)) * max_pts, staged.data(),
+                               sizeof(Detection) * (size_t)kept, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));            // `staged` is reused for the next octave
+      }
+    }
+  HIP_TRY(hipMemcpyAsync(ctx->d_counters, counters.data(), sizeof(unsigned) * counters.size(), hipMemcpyHostToDevice,
+                         ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  ctx->want_export = 1;
+  rc = enqueue_keypoint_tail(ctx, d_scratch, P, (SiftPointD *)d_pts, max_pts, false);
+  ctx->want_export = 0;
+  bool ovf = false;
+  if (!rc) rc = read_counts(ctx, nframes, num_octaves, max_pts, num_pts, &ovf);
+  if (rc == MISIFT_RETRY_CHAIN || rc == MISIFT_RETRY_FUSE) rc = MISIFT_EHIP;       // (neither kernel runs here)
+  if (rc) return rc;
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return resolve_profile(ctx);
 }
 
 extern "C" int misift_extract(misift_ctx *ctx, const float *d_img, int width, int height, int pitch, int num_octaves,

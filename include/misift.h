@@ -2040,6 +2040,27 @@ int misift_test_frame_shares(int nblocks, int nframes, const unsigned *points, i
 int misift_test_set_knob(misift_ctx *ctx, const char *name, double value);
 const char *misift_test_knob_names(void);
 
+/* Test-only: the per-keypoint tail of the extraction calls' merged-octave sequence — spatial binning, orientations,
+ * duplicate renumbering (deterministic mode), descriptors incl. the large-window kernel — on detections and pyramid
+ * levels the CALLER supplies, instead of what the detector finds in an image.  The launches, their shapes (binned,
+ * balanced, folded single call ...) and every buffer are those of an extraction call of `nframes` frames of width x height
+ * with num_octaves octaves; the fused orientation + descriptor launch (knob fuse_orient) is never taken.
+ *   scale_up != 0: the records' xpos / ypos / scale are halved as after an up-sampled call (RescalePositions); the level
+ *     sizes stay those of width x height.
+ *   levels[f * num_octaves + (o - 1)]: host image of octave o of frame f (o = 1: the coarsest level ... num_octaves: the
+ *     finest, width x height; sizes as misift_test_pyramid_layout reports them), rows tightly packed.  The levels need
+ *     not be a pyramid of one another.
+ *   det_counts[f * num_octaves + (o - 1)]: detections of that frame and octave; dets: all of them in that order (frame
+ *     by frame, coarsest octave first), five host floats each: xpos, ypos, scale, sharpness, edgeness in the level's own
+ *     coordinates.  Finite values, scale > 0; xpos / ypos may lie outside the level.  Of an octave with more than max_pts
+ *     detections the first max_pts are kept (the count stays), as the refinement does.
+ *   d_pts: nframes x max_pts device records; num_pts[f] as an extraction call reports it.  The call returns when the
+ *     records are complete; misift_get_counters / misift_get_counter_block then read this call's counters.
+ * A bad argument returns MISIFT_EINVAL and enqueues nothing. */
+int misift_test_describe_detections(misift_ctx *ctx, int nframes, int width, int height, int num_octaves, int scale_up,
+                                    const float *const *levels, const float *dets, const int *det_counts, void *d_pts,
+                                    int max_pts, int *num_pts);
+
 /* Test-only: guard mode (out-of-bounds policing in the test build).  While it is on, every device
  * allocation the library makes — misift_malloc for the caller, and its own counters, candidate lists, detection staging,
  * block tables, matcher scratch, pipeline buffers — carries 64 KiB of a byte pattern in front of and behind the payload,
