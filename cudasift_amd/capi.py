@@ -156,6 +156,9 @@ SIGNATURES = {
                                          _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "misift_test_resect_samples": (_i, [C.c_uint, _i, _i, _vp]),
     "misift_test_resect_solve": (_i, [_vp, _vp, _vp, _vp]),
+    "misift_select_pairs_batch": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _f, _f, _i, _i, _i, _vp, _vp, _vp, _vp, _vp,
+                                       _vp]),
+    "misift_test_select_pairs": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _f, _f, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "misift_test_quantize": (_i, [_vp, C.c_long, _vp]),
     "misift_test_match_i8_plan": (_i, [_i, _i, _vp, _vp, _vp, _ip, _ip, _ip]),
     "misift_test_libc_rand": (_i, [C.c_uint, _i, _vp]),
@@ -286,6 +289,26 @@ def check_guards():
     if bad != 0:
         raise MisiftError("guard check: %d damaged allocation(s): %s" % (bad, lib().misift_last_error().decode()))
     return n.value
+
+
+def select_pairs_host(recs, q, counts, offsets, stride, top, min_score, max_ambiguity, min_votes, k, max_pairs,
+                      fill=0):
+    """misift_test_select_pairs (host-only): misift_select_pairs_batch on host arrays by plain loops.  recs: POINT_DTYPE
+    records, q: their int8 descriptors, counts / offsets (or None) / stride the layout.  Returns (sel, sel_counts, votes,
+    pairs, pair_votes, summary) as int32 arrays of the stated sizes (at least one word each), pre-filled with the word
+    `fill` so that unwritten entries show."""
+    recs = np.ascontiguousarray(recs, POINT_DTYPE)
+    q = np.ascontiguousarray(q, np.int8)
+    counts = np.ascontiguousarray(counts, np.int32)
+    offsets = None if offsets is None else np.ascontiguousarray(offsets, np.int32)
+    n = len(counts)
+    out = [np.full(max(w, 1), fill, np.uint32).view(np.int32)
+           for w in (n * top, n, n * n, 2 * max_pairs, max_pairs, 8)]
+    check(lib().misift_test_select_pairs(recs.ctypes.data, q.ctypes.data, n, counts.ctypes.data,
+                                         None if offsets is None else offsets.ctypes.data, stride, top, min_score,
+                                         max_ambiguity, min_votes, k, max_pairs, *[o.ctypes.data for o in out]),
+          "misift_test_select_pairs")
+    return tuple(out)
 
 
 class DevBuf:
@@ -983,6 +1006,47 @@ class Context:
                                                 int(mutual), _dptr(out), _dptr(out_counts), _dptr(num_matched)),
               "misift_match_pairs_batch_i8")
         return out, out_counts, num_matched
+
+    def select_pairs_batch(self, recs, q, nframes, counts, offsets=None, stride=0, top=256, min_score=0.85,
+                           max_ambiguity=0.95, min_votes=4, k=8, max_pairs=None, sel=None, sel_counts=None, votes=None,
+                           pairs=None, pair_votes=None, summary=None):
+        """misift_select_pairs_batch (preemptive matching): the frame pairs worth matching.  The `top` largest-scale
+        records of every frame (q: quantize_batch's output for recs) are matched against those of every other frame,
+        votes[a, b] counts the mutual matches that pass the gate (min_score, max_ambiguity), every frame takes its k
+        best partners with at least min_votes votes, and the selected pairs (a < b) are written in ascending order
+        while they fit max_pairs (default: every pair).  sel (nframes x top ints), sel_counts (nframes), votes (nframes
+        x nframes), pairs (2 x max_pairs), pair_votes (max_pairs) and summary (8 ints: pairs selected, pairs written,
+        frames without neighbour, frames with more than top records, max votes) are device buffers, allocated here
+        when None; returns the six.  Enqueued on the context stream; read_selected_pairs() is the host step."""
+        if max_pairs is None:
+            max_pairs = nframes * (nframes - 1) // 2
+        n = max(nframes, 1)
+        if sel is None:
+            sel = self.zeros(4 * n * max(top, 1))
+        if sel_counts is None:
+            sel_counts = self.zeros(4 * n)
+        if votes is None:
+            votes = self.zeros(4 * n * n)
+        if pairs is None:
+            pairs = self.zeros(8 * max(max_pairs, 1))
+        if pair_votes is None:
+            pair_votes = self.zeros(4 * max(max_pairs, 1))
+        if summary is None:
+            summary = self.zeros(4 * 8)
+        check(lib().misift_select_pairs_batch(self.h, _dptr(recs), _dptr(q), nframes, _dptr(counts), _dptr(offsets),
+                                              stride, top, min_score, max_ambiguity, min_votes, k, max_pairs, _dptr(sel),
+                                              _dptr(sel_counts), _dptr(votes), _dptr(pairs), _dptr(pair_votes),
+                                              _dptr(summary)), "misift_select_pairs_batch")
+        return sel, sel_counts, votes, pairs, pair_votes, summary
+
+    def read_selected_pairs(self, pairs, summary):
+        """The host step behind select_pairs_batch: waits for the stream and returns the written pairs as the (n, 2)
+        int32 host array the pair matchers take."""
+        s = self.download(summary, (8,), np.int32)
+        n = int(s[1])
+        if n == 0:
+            return np.zeros((0, 2), np.int32)
+        return self.download(pairs, (n, 2), np.int32)
 
     def link_tracks_batch(self, pairs, rows, row_counts, max_pts, nframes, counts, offsets=None, stride=0,
                           max_records=None, min_score=0.85, max_ambiguity=0.95, max_error=float("inf"), track=None,

@@ -668,6 +668,12 @@ int launch_export_tracks_batch(misift_ctx *ctx, const BatchLayout &set, int nfra
                                const int *d_track_len, const int *d_track_frames, int min_len, int consistent_only,
                                int max_tracks, int max_obs, int *d_track_offsets, int *d_track_root, void *d_obs,
                                int *d_record_obs, int *d_summary);
+// misift_select_pairs_batch (kernels_select.hip): six launches (select, votes, pick, count, scan, emit; fewer with fewer
+// than two frames or max_pairs == 0), no memset; temp from misift_ensure_tmp, select_pairs_tmp_bytes(nframes, top)
+size_t select_pairs_tmp_bytes(int nframes, int top);
+int launch_select_pairs_batch(misift_ctx *ctx, const BatchLayout &set, const int8_t *q, int nframes, int top,
+                              float min_score, float max_ambiguity, int min_votes, int k, int max_pairs, int *d_sel,
+                              int *d_sel_counts, int *d_votes, int *d_pairs, int *d_pair_votes, int *d_summary);
 // misift_link_poses_batch (kernels_posegraph.hip): two launches; temp from misift_ensure_tmp, sized from npairs, nlinks
 // and nwalk only.  h_lists: the links (nlinks x 3), the pairs (npairs x 2) and the walk (nwalk), in that order
 size_t link_poses_batch_tmp_bytes(int npairs, int nlinks, int nwalk);

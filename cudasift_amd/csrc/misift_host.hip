@@ -2665,6 +2665,45 @@ extern "C" int misift_link_tracks_batch(misift_ctx *ctx, int npairs, const int *
   });
 }
 
+// Preemptive matching: the frame pairs worth matching, chosen on the device from the `top` largest-scale features of
+// every frame (kernels_select.hip; the rules are select_core.hpp).  The byte ranges the host knows: every output, the
+// counts, the offsets and, in a padded layout, the records and their q; of a packed layout's records and q only the
+// first byte, since their extent is device data.
+extern "C" int misift_select_pairs_batch(misift_ctx *ctx, const void *d_recs, const int8_t *d_q, int nframes,
+                                         const int *d_counts, const int *d_offsets, int stride, int top, float min_score,
+                                         float max_ambiguity, int min_votes, int k, int max_pairs, int *d_sel,
+                                         int *d_sel_counts, int *d_votes, int *d_pairs, int *d_pair_votes, int *d_summary)
+{
+  ARG_CHECK(ctx && d_recs && d_q && d_counts);
+  ARG_CHECK(d_sel && d_sel_counts && d_votes && d_pairs && d_pair_votes && d_summary);
+  ARG_CHECK(((uintptr_t)d_q & 15) == 0);
+  ARG_CHECK(nframes >= 0 && nframes <= MISIFT_SELECT_MAX_FRAMES);
+  ARG_CHECK(top >= 1 && top <= MISIFT_SELECT_MAX_TOP && k >= 1 && min_votes >= 1 && max_pairs >= 0);
+  ARG_CHECK(min_score == min_score && max_ambiguity == max_ambiguity);      // not NaN
+  BatchLayout set;
+  int rc = batch_layout(__func__, d_recs, d_counts, d_offsets, stride, &set);
+  if (rc) return rc;
+  struct Range { const void *p; size_t bytes; };
+  const size_t N = (size_t)nframes, span = d_offsets ? 0 : N * (size_t)stride;
+  const Range outs[6] = {{d_sel, 4 * N * top}, {d_sel_counts, 4 * N}, {d_votes, 4 * N * N},
+                         {d_pairs, 8 * (size_t)max_pairs}, {d_pair_votes, 4 * (size_t)max_pairs}, {d_summary, 32}};
+  const Range ins[4] = {{d_recs, span ? span * MISIFT_POINT_BYTES : 1}, {d_q, span ? span * 128 : 1}, {d_counts, 4 * N},
+                        {d_offsets, d_offsets ? 4 * N : 0}};
+  const auto overlap = [](const Range &a, const Range &b) {
+    const uintptr_t pa = (uintptr_t)a.p, pb = (uintptr_t)b.p;
+    return a.bytes && b.bytes && pa < pb + b.bytes && pb < pa + a.bytes;
+  };
+  for (int i = 0; i < 6; i++) {
+    for (int j = i + 1; j < 6; j++) ARG_CHECK(!overlap(outs[i], outs[j]));
+    for (int j = 0; j < 4; j++) ARG_CHECK(!overlap(outs[i], ins[j]));
+  }
+  RoctxRange range(__func__);
+  return run_batch(ctx, {}, 0, [&](int *, void *) {
+    return launch_select_pairs_batch(ctx, set, d_q, nframes, top, min_score, max_ambiguity, min_votes, k, max_pairs,
+                                     d_sel, d_sel_counts, d_votes, d_pairs, d_pair_votes, d_summary);
+  });
+}
+
 // The pair poses of misift_recover_pose_batch joined into one frame: a relative scale per link, the scales propagated
 // from a seed pair, a camera per image along a walk.  The three host lists go to the pinned slot: links, pairs, walk.
 extern "C" int misift_link_poses_batch(misift_ctx *ctx, int npairs, const int *pairs, int nimages, const void *d_rows,

@@ -440,7 +440,8 @@ int misift_match_pairs_batch(misift_ctx *ctx, int npairs, const int *pairs,
  *     misift_gather_post (marks the most recent batch) or misift_ctx_sync;
  *   - the scratch arena and the output buffers of a call must stay untouched until that batch is done: rotate >= K sets.
  *   - misift_match_batch, misift_match_pairs_batch, misift_quantize_batch, misift_match_batch_i8,
- *     misift_match_pairs_batch_i8, misift_find_homography_batch, misift_improve_homography_batch,
+ *     misift_match_pairs_batch_i8, misift_select_pairs_batch, misift_find_homography_batch,
+ *     misift_improve_homography_batch,
  *     misift_find_fundamental_batch, misift_score_fundamental_batch, misift_improve_fundamental_batch,
  *     misift_recover_pose_batch, misift_recover_pose_planar_batch, misift_link_poses_batch, misift_match_guided_batch,
  *     misift_match_epipolar_batch, misift_link_tracks_batch, misift_export_tracks_batch,
@@ -991,6 +992,63 @@ int misift_match_pairs_batch_i8(misift_ctx *ctx, int npairs, const int *pairs,
                                 void *d_out,          /* npairs * max_pts records (576 B each), device */
                                 int *d_out_counts,    /* npairs, device */
                                 int *d_num_matched);  /* npairs, device, may be NULL */
+
+/* Preemptive matching (no reference counterpart; Wu, "Towards linear-time incremental structure from motion"): WHICH
+ * frame pairs of an unordered batch are worth matching, decided on the device.  Only the `top` largest-scale features of
+ * every frame are matched against those of every other frame on the int8 matrix cores, only a vote count per pair is
+ * kept, and every frame proposes its k best partners.  The call fills the `pairs` array the pair matchers take, in place
+ * of an exhaustive list.  One record batch as in misift_link_tracks_batch (d_recs, nframes, d_counts, d_offsets or
+ * stride; a count of -1 means no records: n = max(count, 0)); d_q are its 128-byte descriptors from
+ * misift_quantize_batch.  Of the records only `scale` is read.
+ *   1. Features.  The key of record r is the bit pattern of scale if scale > 0, else 0 (a NaN compares false: 0; +inf is
+ *      the largest key).  The chosen records of frame f are the h(f) = min(n, top) records with the largest keys, ordered
+ *      by key descending, then index ascending.  d_sel[f * top + i] = the frame-local index of the i-th, or -1 for
+ *      i >= h(f); d_sel_counts[f] = h(f).
+ *   2. Votes, for every unordered pair a < b, on the chosen descriptors qa (rows) and qb (columns) in the order of d_sel:
+ *      S_ij = sum_k qa[i][k] * qb[j][k], exact in int32.  Row i: best = the largest S_ij > 0, m = the smallest j that
+ *      attains it, second = the largest S_ij over j != m, or 0 (the rule of misift_match_batch_i8).  Column m's best row
+ *      is the row with the largest S_im > 0, the smallest row on a tie (the mutual rule of misift_match_pairs_batch_i8).
+ *      Row i votes iff m >= 0, row i is column m's best row, score = (float)best * 2^-16 > min_score, and
+ *      ((float)second * 2^-16) / (score + 1e-6f) < max_ambiguity in fp32.  V[a][b] = V[b][a] = the voting rows,
+ *      V[f][f] = 0: the rows misift_match_pairs_batch_i8(mutual = 1) on the two gathered subsets would write and the gate
+ *      of misift_link_tracks_batch with max_error = +inf would accept.  d_votes (nframes x nframes) is fully written.
+ *   3. Pairs.  The neighbours of f are the g != f with V[f][g] >= min_votes, ordered by V descending, then g ascending;
+ *      the first k are taken.  Pair (a, b), a < b, is selected iff b is a neighbour taken by a or a one taken by b.  With
+ *      P selected pairs, for i < min(P, max_pairs) in ascending (a, b) order: d_pairs[2i], d_pairs[2i + 1] = (a, b) and
+ *      d_pair_votes[i] = V[a][b].  d_summary (8 ints): [0] P, [1] pairs written, [2] frames with at least one record and
+ *      no neighbour, [3] frames with more than `top` records, [4] the largest V, [5] = [6] = [7] = 0.
+ *   - No byte beyond these is written: entries of d_pairs and d_pair_votes at or past the pairs written stay untouched.
+ *   - The host step: the chain's calls take `pairs` as a host array, so the caller reads d_summary[0 .. 1] and the first
+ *     8 * d_summary[1] bytes of d_pairs once, and hands that array to misift_match_pairs_batch_i8, the homography and
+ *     fundamental calls, misift_link_tracks_batch and the rest.  That is the one small host read the selection needs;
+ *     the call itself reads nothing back.
+ *   - Deterministic: the selection is an exact radix select, the scores are integers, the pair list a prefix sum:
+ *     byte-identical from run to run whatever the dispatch order.
+ *   - NULL ctx, d_recs, d_q, d_counts or output pointer; d_q not 16-byte aligned; nframes < 0 or above
+ *     MISIFT_SELECT_MAX_FRAMES (the vote matrix stays at 64 MB or less); top outside [1, MISIFT_SELECT_MAX_TOP]; k < 1;
+ *     min_votes < 1; max_pairs < 0; min_score or max_ambiguity NaN; d_offsets NULL with a negative stride; an output
+ *     that shares a byte with another output or with an input: MISIFT_EINVAL, before anything is enqueued.  The outputs
+ *     are taken at their stated sizes (d_pairs: 2 * max_pairs ints), d_counts and d_offsets at nframes ints, d_recs and
+ *     d_q at nframes * stride records in a padded layout; with d_offsets their extent is device data, and only their
+ *     first byte is tested.  nframes == 0 writes only the summary.
+ *   - The call runs on the context stream and returns before the GPU work is done; no host synchronisation and no host
+ *     read of any count.  Ordering behind batches in flight (K > 1): as misift_match_batch.
+ *   - Six launches and no memset, whatever the data (select and gather, votes, pick, count, scan, emit; the votes and emit
+ *     launches fall away with fewer than two frames, emit with max_pairs == 0, all but the scan with no frame); no
+ *     workgroup waits for another.  Temp memory, from the library's own allocator, is sized from nframes and top only:
+ *     nframes * top' * 128 bytes of gathered descriptors (top' = top rounded up to 32), nframes^2 keep flags, 24 bytes
+ *     per frame, each part rounded up to 16, plus 16. */
+#define MISIFT_SELECT_MAX_TOP 256
+#define MISIFT_SELECT_MAX_FRAMES 4096
+int misift_select_pairs_batch(misift_ctx *ctx, const void *d_recs, const int8_t *d_q /* 16-byte aligned */, int nframes,
+                              const int *d_counts, const int *d_offsets, int stride,
+                              int top, float min_score, float max_ambiguity, int min_votes, int k, int max_pairs,
+                              int *d_sel,         /* nframes x top ints */
+                              int *d_sel_counts,  /* nframes ints */
+                              int *d_votes,       /* nframes x nframes ints */
+                              int *d_pairs,       /* 2 x max_pairs ints */
+                              int *d_pair_votes,  /* max_pairs ints */
+                              int *d_summary);    /* 8 ints */
 
 /* Feature tracks of a pair-indexed batch (no reference counterpart): the accepted matches of every pair of
  * misift_match_pairs_batch / misift_match_pairs_batch_i8 joined ACROSS pairs into connected components, on the device.
@@ -2016,6 +2074,12 @@ int misift_test_guided_gather(const float *H9, const float *xy1, int n1, const f
 int misift_test_quantize(const float *src, long n, int8_t *dst);
 int misift_test_match_i8_plan(int num_cus, int npairs, const int *n1, const int *n2, int *plan5, int *nitems,
                               int *chunks, int *partial_items_bound);
+/* host-only: misift_select_pairs_batch on host arrays (the rules of select_core.hpp applied with plain loops); writes
+ * exactly the bytes the device call writes.  Argument errors as the device call's, but for alignment and overlap. */
+int misift_test_select_pairs(const void *recs, const int8_t *q, int nframes, const int *counts, const int *offsets,
+                             int stride, int top, float min_score, float max_ambiguity, int min_votes, int k,
+                             int max_pairs, int *sel, int *sel_counts, int *votes, int *pairs, int *pair_votes,
+                             int *summary);
 
 /* Test-only, host-only: where the extraction calls put the pyramid inside ONE frame's arena (frame f of a batch: add
  * f * misift_scratch_floats()).  Entry i = pyramid level num_octaves - i (i = 0: the prefiltered image, or its doubled
