@@ -156,6 +156,15 @@ SIGNATURES = {
                                          _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "misift_test_resect_samples": (_i, [C.c_uint, _i, _i, _vp]),
     "misift_test_resect_solve": (_i, [_vp, _vp, _vp, _vp]),
+    "misift_correspond_tracks_batch": (_i, [_vp, _i, _i, _vp, _i, _i, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "misift_align_points_batch": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _f, _i, _i, _vp, _vp, _vp,
+                                       _vp, _vp, _vp]),
+    "misift_transform_scene_batch": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "misift_test_align_samples": (_i, [C.c_uint, _i, _i, _vp]),
+    "misift_test_align_solve": (_i, [_vp, _vp, _vp, _vp]),
+    "misift_test_align_refit": (_i, [_vp, _vp, _i, _f, _i, _vp, _vp, _vp]),
+    "misift_test_transform_camera": (_i, [_vp, _vp, _vp]),
+    "misift_test_transform_point": (_i, [_vp, _vp, _vp]),
     "misift_select_pairs_batch": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _f, _f, _i, _i, _i, _vp, _vp, _vp, _vp, _vp,
                                        _vp]),
     "misift_test_select_pairs": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _f, _f, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -1422,6 +1431,75 @@ class Context:
                                                 _dptr(res_inliers), _dptr(res_status), _dptr(summary)),
               "misift_resect_cameras_batch")
         return res_cam, res_cand, res_inliers, res_status, summary
+
+    def correspond_tracks_batch(self, max_records_a, record_obs_a, max_tracks_a, max_obs_a, track_offsets_a,
+                                export_summary_a, max_records_b, record_obs_b, max_tracks_b, max_obs_b, track_offsets_b,
+                                export_summary_b, shift=0, track_map=None, summary=None):
+        """misift_correspond_tracks_batch: for every track of exported scene A the track of scene B that holds the same
+        records (record g of A is record g - shift of B), -1 for none and -2 for several.  record_obs_*: the
+        d_record_obs of export_tracks_batch, filled with -1 before the export.  track_map (max_tracks_a ints) and
+        summary (8 ints: T_A, T_B, ties, mapped, in conflict) are device buffers, allocated here when not passed;
+        returns the two.  Enqueued on the context stream."""
+        if track_map is None:
+            track_map = self.zeros(4 * max_tracks_a)
+        if summary is None:
+            summary = self.zeros(4 * 8)
+        check(lib().misift_correspond_tracks_batch(self.h, int(shift), max_records_a, _dptr(record_obs_a), max_tracks_a,
+                                                   max_obs_a, _dptr(track_offsets_a), _dptr(export_summary_a),
+                                                   max_records_b, _dptr(record_obs_b), max_tracks_b, max_obs_b,
+                                                   _dptr(track_offsets_b), _dptr(export_summary_b), _dptr(track_map),
+                                                   _dptr(summary)), "misift_correspond_tracks_batch")
+        return track_map, summary
+
+    def align_points_batch(self, src, dst, point_map, ranges, seeds, src_status=None, dst_status=None, count=None,
+                           count_stride=1, num_loops=256, thresh=0.05, min_inliers=3, refit_loops=5, sim=None,
+                           align_cand=None, align_inliers=None, align_status=None, inlier=None, summary=None):
+        """misift_align_points_batch: per entry the similarity transform b = s R a + t between the points of src and
+        their correspondents in dst (pooled device arrays of 4 floats per point; point_map: per source point the index
+        of its correspondent relative to the entry's dst_first, or negative), by RANSAC over num_loops three-point
+        solves with the 3-D distance thresh, refitted refit_loops times over its inliers.  ranges: host, nsel x 4
+        (src_first, src_cap, dst_first, dst_cap); seeds: host, one rand() seed per entry; count: device, the number of
+        source points of entry e at count[e * count_stride], or None for src_cap.  sim (nsel x 16 floats: R, t, s, rms),
+        align_cand, align_inliers, align_status (nsel ints; 0 ok, 1 too few candidates, 2 fewer than min_inliers
+        inliers) and summary (8 ints) are device buffers, allocated here when not passed; inlier (one int per source
+        point) is written only when passed.  Returns the five.  Enqueued on the context stream."""
+        ranges = np.ascontiguousarray(ranges, np.int32).reshape(-1, 4)
+        seeds = np.ascontiguousarray(seeds, np.uint32).reshape(-1)
+        nsel = len(ranges)
+        assert len(seeds) == nsel
+        if sim is None:
+            sim = self.zeros(64 * max(nsel, 1))
+        if align_cand is None:
+            align_cand = self.zeros(4 * max(nsel, 1))
+        if align_inliers is None:
+            align_inliers = self.zeros(4 * max(nsel, 1))
+        if align_status is None:
+            align_status = self.zeros(4 * max(nsel, 1))
+        if summary is None:
+            summary = self.zeros(4 * 8)
+        check(lib().misift_align_points_batch(self.h, _dptr(src), _dptr(src_status), _dptr(dst), _dptr(dst_status),
+                                              _dptr(point_map), nsel, ranges.ctypes.data if nsel else None,
+                                              seeds.ctypes.data if nsel else None, _dptr(count), int(count_stride),
+                                              int(num_loops), float(thresh), int(min_inliers), int(refit_loops),
+                                              _dptr(sim), _dptr(align_cand), _dptr(align_inliers), _dptr(align_status),
+                                              _dptr(inlier), _dptr(summary)), "misift_align_points_batch")
+        return sim, align_cand, align_inliers, align_status, summary
+
+    def transform_scene_batch(self, sim, max_tracks, export_summary, points, point_status, nimages, cam, cam_pair,
+                              sim_status=None, points_out=None, cam_out=None):
+        """misift_transform_scene_batch: the transform sim (16 device floats, one entry of align_points_batch; applied
+        only when sim_status, its device status word, is None or holds 0) applied to the points with status 0 of the
+        first T tracks and to the cameras that are set, so that every reprojection is unchanged; everything else is
+        copied.  points_out and cam_out may be points and cam; allocated here when not passed.  Returns the two."""
+        if points_out is None:
+            points_out = self.zeros(16 * max_tracks)
+        if cam_out is None:
+            cam_out = self.zeros(48 * nimages)
+        check(lib().misift_transform_scene_batch(self.h, _dptr(sim), _dptr(sim_status), max_tracks,
+                                                 _dptr(export_summary), _dptr(points), _dptr(point_status), nimages,
+                                                 _dptr(cam), _dptr(cam_pair), _dptr(points_out), _dptr(cam_out)),
+              "misift_transform_scene_batch")
+        return points_out, cam_out
 
     def match_split(self, pts1, n1, pts2, n2, own_tile_begin, own_tile_end):
         """Test hook: misift_match with the column sweep cut into two launches (the sharded matcher's cut)."""

@@ -705,6 +705,26 @@ int launch_resect_cameras_batch(misift_ctx *ctx, const TrackScene &scene, int ns
                                 const unsigned *h_seeds, int max_cand, int num_loops, float thresh2, int min_inliers,
                                 int only_unset, int install, float *d_cam, int *d_cam_pair, float *d_res_cam,
                                 int *d_res_cand, int *d_res_inliers, int *d_res_status, int *d_summary);
+// misift_align_points_batch (kernels_align.hip): one memset + five launches; temp from misift_ensure_tmp, sized from nsel,
+// the largest src_cap (max_cap) and num_loops only.  h_ranges (nsel x 4), h_seeds (nsel): the pinned copies
+size_t align_points_batch_tmp_bytes(int nsel, int max_cap, int num_loops);
+bool align_points_batch_one_launch(int nsel, int max_cap, int num_loops);
+int launch_align_points_batch(misift_ctx *ctx, const float *d_src, const int *d_src_status, const float *d_dst,
+                              const int *d_dst_status, const int *d_map, int nsel, const int *h_ranges,
+                              const unsigned *h_seeds, int max_cap, const int *d_count, int count_stride, int num_loops,
+                              float thresh2, int min_inliers, int refit_loops, float *d_sim, int *d_align_cand,
+                              int *d_align_inliers, int *d_align_status, int *d_inlier, int *d_summary);
+// misift_correspond_tracks_batch: three memsets + two launches; temp: 8 bytes per track of max_tracks_a
+int launch_correspond_tracks_batch(misift_ctx *ctx, int shift, int max_records_a, const int *d_record_obs_a,
+                                   int max_tracks_a, int max_obs_a, const int *d_track_offsets_a,
+                                   const int *d_export_summary_a, int max_records_b, const int *d_record_obs_b,
+                                   int max_tracks_b, int max_obs_b, const int *d_track_offsets_b,
+                                   const int *d_export_summary_b, int *d_map, int *d_summary);
+// misift_transform_scene_batch: one launch, no temp
+int launch_transform_scene_batch(misift_ctx *ctx, const float *d_sim, const int *d_sim_status, int max_tracks,
+                                 const int *d_export_summary, const float *d_points, const int *d_point_status,
+                                 int nimages, const float *d_cam, const int *d_cam_pair, float *d_points_out,
+                                 float *d_cam_out);
 // misift_adjust_bundle_batch and misift_adjust_bundle_robust_batch (kernels_bundle.hip): three memsets + 11 + num_loops *
 // (8 + 3 * cg_iters) launches, one more with d_obs_weight; temp from misift_ensure_tmp, sized from max_tracks, max_obs
 // and nimages only.  h_held: as launch_refine_cameras_batch.  loss 0 and a NULL d_obs_weight is the plain call

@@ -12,6 +12,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <math.h>
+#include <algorithm>
 #include <initializer_list>
 #include <map>
 #include <mutex>
@@ -2902,6 +2903,91 @@ extern "C" int misift_resect_cameras_batch(misift_ctx *ctx, int max_tracks, int 
                                                         d_cam_pair, d_res_cam, d_res_cand, d_res_inliers, d_res_status,
                                                         d_summary);
                    });
+}
+
+// Which track of scene B holds the records of each track of scene A: where the d_map of misift_align_points_batch comes
+// from.  No host lists.
+extern "C" int misift_correspond_tracks_batch(misift_ctx *ctx, int shift, int max_records_a, const int *d_record_obs_a,
+                                              int max_tracks_a, int max_obs_a, const int *d_track_offsets_a,
+                                              const int *d_export_summary_a, int max_records_b,
+                                              const int *d_record_obs_b, int max_tracks_b, int max_obs_b,
+                                              const int *d_track_offsets_b, const int *d_export_summary_b, int *d_map,
+                                              int *d_summary)
+{
+  ARG_CHECK(ctx != nullptr);
+  ARG_CHECK(max_records_a >= 1 && max_tracks_a >= 1 && max_obs_a >= 1);
+  ARG_CHECK(max_records_b >= 1 && max_tracks_b >= 1 && max_obs_b >= 1);
+  ARG_CHECK(d_record_obs_a && d_track_offsets_a && d_export_summary_a);
+  ARG_CHECK(d_record_obs_b && d_track_offsets_b && d_export_summary_b);
+  ARG_CHECK(d_map && d_summary);
+  RoctxRange range(__func__);
+  return run_batch(ctx, {}, 0, [&](int *, void *) {
+    return launch_correspond_tracks_batch(ctx, shift, max_records_a, d_record_obs_a, max_tracks_a, max_obs_a,
+                                          d_track_offsets_a, d_export_summary_a, max_records_b, d_record_obs_b,
+                                          max_tracks_b, max_obs_b, d_track_offsets_b, d_export_summary_b, d_map,
+                                          d_summary);
+  });
+}
+
+// Per entry the similarity transform between corresponding points of two pooled arrays, by batch RANSAC over three-point
+// closed-form solves, refitted over its inliers.  The ranges and the seeds go to the pinned slot, in that order.
+extern "C" int misift_align_points_batch(misift_ctx *ctx, const float *d_src, const int *d_src_status,
+                                         const float *d_dst, const int *d_dst_status, const int *d_map, int nsel,
+                                         const int *ranges, const unsigned *seeds, const int *d_count, int count_stride,
+                                         int num_loops, float thresh, int min_inliers, int refit_loops, float *d_sim,
+                                         int *d_align_cand, int *d_align_inliers, int *d_align_status, int *d_inlier,
+                                         int *d_summary)
+{
+  ARG_CHECK(ctx != nullptr);
+  ARG_CHECK(d_src && d_dst && d_map);
+  ARG_CHECK(d_sim && d_align_cand && d_align_inliers && d_align_status && d_summary);
+  ARG_CHECK(nsel >= 0 && (nsel == 0 || (ranges && seeds)));
+  ARG_CHECK(num_loops >= 1 && min_inliers >= 3 && refit_loops >= 0);
+  ARG_CHECK(thresh > 0.0f);                                                 // NaN fails too
+  ARG_CHECK(!d_count || count_stride >= 0);
+  int max_cap = 1;
+  for (int e = 0; e < nsel; e++) {
+    const int *r = ranges + 4 * (size_t)e;
+    ARG_CHECK(r[0] >= 0 && r[1] >= 1 && r[2] >= 0 && r[3] >= 1);
+    ARG_CHECK((long long)r[0] + r[1] <= 0x7fffffffLL && (long long)r[2] + r[3] <= 0x7fffffffLL);
+    max_cap = r[1] > max_cap ? r[1] : max_cap;
+  }
+  if (d_inlier && nsel > 1) {                                               // d_inlier is per source point: no overlap
+    std::vector<std::pair<int, int>> spans((size_t)nsel);
+    for (int e = 0; e < nsel; e++) spans[e] = {ranges[4 * (size_t)e], ranges[4 * (size_t)e + 1]};
+    std::sort(spans.begin(), spans.end());
+    for (int e = 1; e < nsel; e++)
+      ARG_CHECK((long long)spans[e - 1].first + spans[e - 1].second <= spans[e].first);
+  }
+  ARG_CHECK(align_points_batch_one_launch(nsel, max_cap, num_loops));
+  const float thresh2 = thresh * thresh;                                    // rounded once, here
+  RoctxRange range(__func__);
+  return run_batch(ctx, {{ranges, sizeof(int) * 4 * (size_t)nsel}, {seeds, sizeof(unsigned) * (size_t)nsel}}, 0,
+                   [&](int *h_lists, void *) {
+                     return launch_align_points_batch(ctx, d_src, d_src_status, d_dst, d_dst_status, d_map, nsel, h_lists,
+                                                      reinterpret_cast<const unsigned *>(h_lists + 4 * (size_t)nsel),
+                                                      max_cap, d_count, count_stride, num_loops, thresh2, min_inliers,
+                                                      refit_loops, d_sim, d_align_cand, d_align_inliers, d_align_status,
+                                                      d_inlier, d_summary);
+                   });
+}
+
+// A similarity transform applied to the points and the cameras of a scene.  No host lists.
+extern "C" int misift_transform_scene_batch(misift_ctx *ctx, const float *d_sim, const int *d_sim_status, int max_tracks,
+                                            const int *d_export_summary, const float *d_points,
+                                            const int *d_point_status, int nimages, const float *d_cam,
+                                            const int *d_cam_pair, float *d_points_out, float *d_cam_out)
+{
+  ARG_CHECK(ctx != nullptr);
+  ARG_CHECK(max_tracks >= 1 && nimages >= 1);
+  ARG_CHECK(d_sim && d_export_summary && d_points && d_point_status && d_cam && d_cam_pair && d_points_out && d_cam_out);
+  ARG_CHECK(same_or_disjoint(d_points, d_points_out, sizeof(float) * 4 * (size_t)max_tracks));
+  ARG_CHECK(same_or_disjoint(d_cam, d_cam_out, sizeof(float) * 12 * (size_t)nimages));
+  RoctxRange range(__func__);
+  return run_batch(ctx, {}, 0, [&](int *, void *) {
+    return launch_transform_scene_batch(ctx, d_sim, d_sim_status, max_tracks, d_export_summary, d_points, d_point_status,
+                                        nimages, d_cam, d_cam_pair, d_points_out, d_cam_out);
+  });
 }
 
 // The body of the three bundle calls: the robust call, with ngroups > 0 and a group for some image the focal scales

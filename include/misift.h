@@ -1509,6 +1509,166 @@ int misift_resect_cameras_batch(misift_ctx *ctx,
                                 int   *d_res_status,            /* nsel */
                                 int   *d_summary);              /* 8 ints */
 
+/* Two reconstructions related (no reference counterpart).  Everything the chain produces lives in one arbitrary gauge:
+ * the frame of root_image and the unit of seed_pair.  The three calls below relate two such gauges: the other side of a
+ * break in the walk of misift_link_poses_batch reconstructed from its own seed, overlapping windows of a long sequence,
+ * a reconstruction against surveyed points.  misift_correspond_tracks_batch finds which points correspond,
+ * misift_align_points_batch estimates the similarity transform b = s R a + t between them robustly, and
+ * misift_transform_scene_batch applies it to points and cameras.
+ *   - Not done here: no reprojection-error inlier test (the test is the 3-D distance in the units of d_dst); no
+ *     camera-centre correspondences; no merging of the two scenes' tracks into one export; no re-adjustment afterwards,
+ *     which misift_adjust_bundle_* does on the merged scene.
+ *
+ * misift_correspond_tracks_batch: two exported scenes A and B over the same records (two link / export runs over different
+ * pair sets of one record batch, or over two views into one packed batch).  Record g of A (its global index, as
+ * d_record_obs of misift_export_tracks_batch is indexed) is record g - shift of B; shift == 0 means one batch.
+ *   PRECONDITION: each d_record_obs was filled with -1 by the caller before its export, since export leaves the entries
+ *   of invalid records untouched.  A stale entry can at worst make a wrong tie; it cannot make the call read or write out
+ *   of bounds.
+ *   T_A = min(max(d_export_summary_a[2], 0), max_tracks_a), O_A = min(max(d_export_summary_a[3], 0), max_obs_a), T_B and
+ *   O_B likewise, all read on the device.
+ *   The TRACK OF a slot o among T tracks with offsets off: T < 1: none.  Otherwise lo = 0, hi = T; while hi - lo > 1:
+ *   mid = lo + (hi - lo) / 2, and off[mid] <= o ? lo = mid : hi = mid.  The track is lo iff off[lo] <= o < off[lo + 1],
+ *   otherwise none (so hostile offsets only drop the record; only off[0 .. T] is read).
+ *   Record g in [0, max_records_a) makes a TIE (t_A, t_B) iff 0 <= g - shift < max_records_b (in 64 bits),
+ *   o_A = d_record_obs_a[g] lies in [0, O_A), o_B = d_record_obs_b[g - shift] lies in [0, O_B), t_A is the track of o_A
+ *   among A's and t_B the track of o_B among B's, and both exist.
+ *   d_map[t], t < T_A: -1 when no tie names t as t_A; the one t_B when all its ties name the same; -2 when they name
+ *   several.  d_map at or beyond T_A stays untouched.  d_summary (8 ints): [0] T_A, [1] T_B, [2] ties, [3] tracks with
+ *   d_map >= 0, [4] tracks with d_map == -2, [5..7] 0.
+ *   - NULL ctx or pointer; a capacity < 1: MISIFT_EINVAL, before anything is enqueued.  None of the inputs is written.
+ *   - Stream semantics as misift_resect_cameras_batch; no host read.  Three memsets and two launches whatever the data:
+ *     one thread per record (atomicMin and atomicMax of t_B per t_A, which no order of the threads changes), one per
+ *     track.  Temp memory from the library's own allocator: 8 bytes per track of max_tracks_a. */
+int misift_correspond_tracks_batch(misift_ctx *ctx, int shift,
+                                   int max_records_a, const int *d_record_obs_a,   /* max_records_a, from export A */
+                                   int max_tracks_a, int max_obs_a,
+                                   const int *d_track_offsets_a,                   /* max_tracks_a + 1 */
+                                   const int *d_export_summary_a,                  /* 8 ints */
+                                   int max_records_b, const int *d_record_obs_b,
+                                   int max_tracks_b, int max_obs_b,
+                                   const int *d_track_offsets_b, const int *d_export_summary_b,
+                                   int *d_map,                                     /* max_tracks_a */
+                                   int *d_summary);                                /* 8 ints */
+
+/* misift_align_points_batch: per entry, the similarity transform (s, R, t) with b = s R a + t between corresponding 3-D
+ * points, by RANSAC over three-point closed-form solves (Horn 1987 / Umeyama 1991), refitted over its inliers.
+ *   d_src and d_dst are pooled arrays of four floats per point, X Y Z and a word that is not read (the format of
+ *   d_points); d_src_status and d_dst_status, where given, hold 0 for a usable point (as d_point_status); d_map holds one
+ *   int per source point.  Entry e < nsel has ranges[4e .. 4e+3] = src_first, src_cap, dst_first, dst_cap: its source
+ *   points are d_src[4 (src_first + i)], i < src_cap, with d_map[src_first + i] beside them, and the correspondent of
+ *   source point i is point dst_first + d_map[src_first + i] of d_dst.  n_e = src_cap when d_count is NULL, otherwise
+ *   min(max(d_count[e * count_stride], 0), src_cap), read on the device (the export summaries of the entries laid end to
+ *   end: d_count = summaries + 2, count_stride = 8 gives T).
+ *   The arithmetic is that of misift_refine_cameras_batch: fp32, every operation rounded, only + - * /, sqrtf and fabsf,
+ *   no contraction, a comparison with a NaN is false, everything taken left to right as written.  A single result that
+ *   is a NaN is stored as 0x7fc00000.  FINITE means fabsf(v) <= FLT_MAX.
+ *   Per entry e, independently of every other entry:
+ *   1. Candidates.  Source point i < n_e is a CANDIDATE iff m = d_map[src_first + i] lies in [0, dst_cap),
+ *      d_src_status[src_first + i] == 0 and d_dst_status[dst_first + m] == 0 where the arrays are given, and all six
+ *      coordinates a = d_src[4 (src_first + i) .. + 2], b = d_dst[4 (dst_first + m) .. + 2] are FINITE.  The candidates in
+ *      ascending i form the ordered list; candidate p < n.  d_align_cand[e] = n.  n < max(3, min_inliers): status 1,
+ *      sixteen zeros, d_align_inliers[e] = 0.
+ *   2. Draw.  rand() is glibc's after srand(seeds[e]) (as misift_find_homography_batch restates it).  The num_loops
+ *      hypotheses are drawn one after another from the one stream.  A hypothesis is three positions: first
+ *      p_k = rand() % n for k = 0, 1, 2; then for k = 1, 2 in turn, while p_k equals an earlier one: p_k = rand() % n.
+ *   3. Solve (a_k, b_k the candidate at position p_k; K = 3 and the sums run over k = 0, 1, 2 one at a time from +0):
+ *      a. Centroids: ca_j = (((0 + a_0j) + a_1j) + a_2j) / 3, cb likewise.  da_k = a_k - ca, db_k = b_k - cb.
+ *      b. Per correspondence the eleven TERMS M[r][c] = db[r] * da[c] (r, c < 3), qa = (da0*da0 + da1*da1) + da2*da2 and
+ *         qb likewise from db.  M, sa and sb are their sums.
+ *      c. m = the largest fabsf of the nine entries of M; an entry that is not FINITE, or m == 0: INVALID.  A = M / m per
+ *         entry, V = I; six sweeps of the one-sided Jacobi rotation of step 2 of misift_recover_pose_batch over the
+ *         column pairs (0,1), (0,2), (1,2), applied to A and V alike.  w_j = A0j*A0j + A1j*A1j + A2j*A2j.  i1 = the
+ *         column of the largest w, i2 that of the second largest, chosen as step 3 of misift_recover_pose_batch chooses
+ *         them (strict '>', the first maximum wins; of the other two the later only if strictly larger).  w_i2 > 0 false, or
+ *         w_i2 > w_i1 * 1e-10f false: INVALID (collinear or coincident points; the second gate, sigma2 / sigma1 <= 1e-5
+ *         or about 84 eps, catches the sets that are collinear up to the roundings of M / m, whose second column is
+ *         noise and need not even be orthogonal to the first.  The singular values of M go with the squares of the
+ *         spreads: the gate turns away a point set more than about 300 times as long as it is wide, whose rotation
+ *         about its long axis float32 would get wrong by a hundredth or more).
+ *      d. u1 = column i1 of A / sqrtf(w_i1), u2 = column i2 of A / sqrtf(w_i2), v1, v2 = those columns of V;
+ *         u3 = u1 x u2, v3 = v1 x v2 (x: (a1*b2 - a2*b1, a2*b0 - a0*b2, a0*b1 - a1*b0));
+ *         R[r][c] = (u1[r]*v1[c] + u2[r]*v2[c]) + u3[r]*v3[c].  This is Umeyama's answer, the reflection case included: a
+ *         proper rotation by construction, and well defined for three points, whose M has rank 2.
+ *      e. sa == 0: INVALID.  s = sqrtf(sb / sa); s == 0 or not FINITE: INVALID.
+ *         t_r = cb_r - s * ((R[r][0]*ca_0 + R[r][1]*ca_1) + R[r][2]*ca_2).  One of the thirteen numbers not FINITE:
+ *         INVALID.
+ *      An INVALID hypothesis is thirteen 0x7fc00000, which no candidate fits (zeros would fit points near the origin).
+ *   4. Count.  E2 of a candidate under (R, t, s): p_r = s * ((R[r][0]*a_0 + R[r][1]*a_1) + R[r][2]*a_2) + t_r,
+ *      d_r = b_r - p_r, E2 = (d_0*d_0 + d_1*d_1) + d_2*d_2.  It is a MEMBER iff E2 < thresh2, thresh2 = thresh * thresh
+ *      rounded once on the host (thresh = +inf: every candidate with a FINITE E2).  The count of a hypothesis runs over
+ *      all n candidates.
+ *   5. Pick.  The hypothesis with the largest count, the smallest index among equals.  count < min_inliers: status 2,
+ *      sixteen zeros, d_align_inliers[e] = that count.
+ *   6. Refit, otherwise.  h = the picked transform, c = its count.  Up to refit_loops times: the members under h;
+ *      S = the sum over them of (a_0 a_1 a_2 b_0 b_1 b_2); ca = S[0..2] / (float)c, cb = S[3..5] / (float)c, each one
+ *      division; the sum over them of the eleven terms of step 3b under these centroids; steps 3c to 3e give h'.  h'
+ *      INVALID: stop.  c' = the members under h'; c' < c: stop.  Otherwise h = h', c = c'.  Then
+ *      rms = sqrtf(E / (float)c), E the sum of E2 over the members under h.  Every sum over members is the sum of
+ *      misift_improve_fundamental_batch over the candidate position p: 256 partial sums from +0, slot p mod 256 adding
+ *      its members in ascending p (a candidate that is no member adds nothing), then p[t] = p[t] + p[t + off] for
+ *      off = 128 .. 1.  Status 0; d_align_inliers[e] = c; d_sim[16e .. 16e+15] = R row-major, t, s, rms, 0, 0.
+ *   d_align_status[e] = the status.  d_inlier, when given: d_inlier[src_first + i] for every i < src_cap = 1 for a member
+ *   under the final h of a status-0 entry, 0 for any other candidate, -1 for a source point that is no candidate.
+ *   d_summary (8 ints, integer sums, so deterministic): [0] entries with status 0, [1] their inliers, [2] entries with
+ *   status 1, [3] with status 2, [4] the candidates of all entries, [5] the refits kept, [6..7] 0.
+ *   Every other byte stays untouched.
+ *   - NULL ctx, d_src, d_dst, d_map, d_sim, d_align_cand, d_align_inliers, d_align_status or d_summary; nsel < 0, nsel > 0
+ *     with NULL ranges or seeds; src_first or dst_first < 0, src_cap or dst_cap < 1, first + cap beyond 2^31 - 1;
+ *     d_count given with count_stride < 0; num_loops < 1; thresh NaN or <= 0; min_inliers < 3; refit_loops < 0; d_inlier
+ *     given and two entries' source ranges overlapping; nsel x ceil(num_loops / 64) x ceil(max src_cap / 512) beyond
+ *     2^31 - 1 (one launch), or num_loops or a src_cap beyond 2^31 - 16: MISIFT_EINVAL, before anything is enqueued.
+ *     nsel == 0 is no error: only d_summary is written.  None of the inputs is written.
+ *   - Stream semantics as misift_resect_cameras_batch: `ranges` and `seeds` are copied; no host synchronisation and no
+ *     host read.
+ *   - One memset and five launches whatever the data: per entry the ordered candidate list and the draw, one lane per
+ *     (entry, hypothesis) for the solve, one 64-lane workgroup per (entry, 64 hypotheses, 512 candidates) for the count
+ *     (VALU work; the matrix cores' fused accumulation would break the definition), the pick, and one 256-thread
+ *     workgroup per entry for the refit.  Temp memory from the library's own allocator, sized from nsel, the largest
+ *     src_cap and num_loops only: per entry 28 bytes per candidate of the largest src_cap and 68 bytes per hypothesis
+ *     (both rounded up to 16), and 80 bytes. */
+int misift_align_points_batch(misift_ctx *ctx,
+                              const float *d_src,             /* pooled, 4 floats per point */
+                              const int *d_src_status,        /* pooled with d_src, may be NULL */
+                              const float *d_dst,
+                              const int *d_dst_status,        /* may be NULL */
+                              const int *d_map,               /* pooled with d_src */
+                              int nsel, const int *ranges,    /* host, nsel x 4, copied */
+                              const unsigned *seeds,          /* host, nsel, copied */
+                              const int *d_count, int count_stride,   /* may be NULL */
+                              int num_loops, float thresh /* d_dst units */, int min_inliers, int refit_loops,
+                              float *d_sim,                   /* nsel x 16 */
+                              int   *d_align_cand,            /* nsel */
+                              int   *d_align_inliers,         /* nsel */
+                              int   *d_align_status,          /* nsel */
+                              int   *d_inlier,                /* pooled with d_src, may be NULL */
+                              int   *d_summary);              /* 8 ints */
+
+/* misift_transform_scene_batch: the transform d_sim[0 .. 12] = R row-major, t, s (one entry of d_sim above) applied to
+ * the points and the cameras of a scene, so that every reprojection is unchanged.  APPLY iff d_sim_status is NULL or
+ * d_sim_status[0] == 0, read on the device.  T = min(max(d_export_summary[2], 0), max_tracks).
+ *   Point t < max_tracks: with APPLY, t < T and d_point_status[t] == 0,
+ *   d_points_out[4t + r] = s * ((R[r][0]*X_0 + R[r][1]*X_1) + R[r][2]*X_2) + t_r and the fourth word copied; otherwise
+ *   all four words are copied bit for bit.
+ *   Image i < nimages: with APPLY and d_cam_pair[i] != -2, from its R_i row-major and t_i:
+ *   R'[r][c] = (R_i[r][0]*R[c][0] + R_i[r][1]*R[c][1]) + R_i[r][2]*R[c][2] (R' = R_i R^T),
+ *   t'_r = s * t_i[r] - ((R'[r][0]*t_0 + R'[r][1]*t_1) + R'[r][2]*t_2): the camera frame scales with the world.
+ *   Otherwise the twelve words are copied bit for bit.  A computed NaN is stored as 0x7fc00000.
+ *   d_points_out may be d_points and d_cam_out may be d_cam; otherwise they share no byte.
+ *   - NULL ctx or pointer other than d_sim_status; max_tracks or nimages < 1; an output that overlaps its input without
+ *     being it: MISIFT_EINVAL, before anything is enqueued.  One launch, no temp, no host read. */
+int misift_transform_scene_batch(misift_ctx *ctx,
+                                 const float *d_sim,          /* 16 floats: one entry of misift_align_points_batch */
+                                 const int *d_sim_status,     /* its status word, may be NULL */
+                                 int max_tracks, const int *d_export_summary,
+                                 const float *d_points,       /* max_tracks x 4 */
+                                 const int *d_point_status,   /* max_tracks */
+                                 int nimages,
+                                 const float *d_cam,          /* nimages x 12 */
+                                 const int *d_cam_pair,       /* nimages */
+                                 float *d_points_out,         /* max_tracks x 4 */
+                                 float *d_cam_out);           /* nimages x 12 */
+
 /* The cameras and the track points adjusted jointly (bundle adjustment; no reference counterpart): what
  * misift_refine_cameras_batch and misift_triangulate_tracks_batch do in turns, done in one Levenberg-Marquardt step over
  * all free cameras (6 parameters each) and all active track points (3 each).  Each step eliminates the points (Schur
@@ -2049,6 +2209,21 @@ int misift_test_filter_stage(void);
  * cy: cam12 = R row-major then t (twelve zeros when invalid) and *valid = 0 / 1. */
 int misift_test_resect_samples(unsigned seed, int n, int num_loops, int *out);
 int misift_test_resect_solve(const float *xyXYZ, const float *intrinsics4, float *cam12, int *valid);
+
+/* Test-only, host-only: steps 2, 3 and 6 of misift_align_points_batch and the arithmetic of
+ * misift_transform_scene_batch, compiled from the functions their kernels run (align_core.hpp).  The sample positions:
+ * out[3 * loop + j] = position j (in the ordered list of n >= 3 candidates) of hypothesis loop after srand(seed).  The
+ * three-point solve of a9 = the three source points, b9 = their correspondents (x y z each): out13 = R row-major, t, s
+ * (thirteen 0x7fc00000 when INVALID) and *valid = 0 / 1.  The refit: step 6 on the n candidates a3, b3 (n x 3 floats
+ * each, candidate p at 3p) from the transform sim13, refitted in place, with thresh2 = thresh * thresh; the 256 slots
+ * run one after another; out_counts[0] = the final members, [1] = the refits kept, *rms = the rms.  The transform of one
+ * camera cam12 (R_i row-major, t_i) and of one point under sim13. */
+int misift_test_align_samples(unsigned seed, int n, int num_loops, int *out);
+int misift_test_align_solve(const float *a9, const float *b9, float *out13, int *valid);
+int misift_test_align_refit(const float *a3, const float *b3, int n, float thresh, int refit_loops, float *sim13,
+                            int *out_counts, float *rms);
+int misift_test_transform_camera(const float *sim13, const float *cam12, float *out12);
+int misift_test_transform_point(const float *sim13, const float *x3, float *out3);
 /* Test-only, host-only: the gate and the gather of misift_match_epipolar_batch, compiled from the same headers and
  * functions as the kernel.  xy1: n1 set-1 positions (x, y), xy2: n2 set-2 positions.  gate: pass[i * n2 + j] = 1 iff
  * record j is a candidate of row i under F9 and radius.  gather: builds the cell grid of xy2 as the bin launch does
