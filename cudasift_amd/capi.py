@@ -24,7 +24,13 @@ assert POINT_DTYPE.itemsize == 576
 
 # misift_track_obs: one observation of an exported track (misift_export_tracks_batch)
 TRACK_OBS_DTYPE = np.dtype([("frame", "<i4"), ("record", "<i4"), ("xpos", "<f4"), ("ypos", "<f4")])
-CAM_UNSET, CAM_ROOT, CAM_RESECTED = -2, -1, -3                 # cam_pair values that are no pair index
+CAM_UNSET, CAM_ROOT, CAM_RESECTED, CAM_MERGED = -2, -1, -3, -4  # cam_pair values that are no pair index
+# the arguments that state one scene to merge_scenes_batch, in the order of the C call; the last two are optional
+MERGE_SCENE_KEYS = ("max_tracks", "max_obs", "track_offsets", "obs", "export_summary", "points", "point_views",
+                    "point_status", "nimages", "cam", "cam_pair", "max_records", "record_obs")
+MERGE_OUTPUTS = ("track_offsets_out", "obs_out", "export_summary_out", "points_out", "point_views_out",
+                 "point_status_out", "cam_out", "cam_pair_out", "track_map_a", "obs_map_a", "obs_map_b",
+                 "record_obs_out", "summary")
 LOSS_NONE, LOSS_HUBER, LOSS_GEMAN_MCCLURE = 0, 1, 2            # MISIFT_LOSS_*: adjust_bundle_robust_batch
 MAX_FOCAL_GROUPS = 8                                           # MISIFT_MAX_FOCAL_GROUPS: adjust_bundle_focal_batch
 FOCAL_REFINED, FOCAL_NO_MEMBER, FOCAL_NOT_REFINED = 0, 1, 2    # MISIFT_FOCAL_*: d_focal[3g + 2]
@@ -160,6 +166,11 @@ SIGNATURES = {
     "misift_align_points_batch": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _f, _i, _i, _vp, _vp, _vp,
                                        _vp, _vp, _vp]),
     "misift_transform_scene_batch": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "misift_merge_scenes_batch": (_i, [_vp] + 2 * [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp] +
+                                  [_vp, _vp] + 8 * [_i] + 13 * [_vp]),
+    "misift_test_merge_scenes": (_i, 2 * [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp] + [_vp, _vp] +
+                                 8 * [_i] + 13 * [_vp]),
+    "misift_test_merge_capacity": (_i, []),
     "misift_test_align_samples": (_i, [C.c_uint, _i, _i, _vp]),
     "misift_test_align_solve": (_i, [_vp, _vp, _vp, _vp]),
     "misift_test_align_refit": (_i, [_vp, _vp, _i, _f, _i, _vp, _vp, _vp]),
@@ -278,6 +289,11 @@ def laplace_taps(num_octaves):
     k = np.zeros(8 * 12 * 16, np.float32)
     check(lib().misift_laplace_taps(num_octaves, k.ctypes.data_as(_fp)), "misift_laplace_taps")
     return k
+
+
+def merge_capacity():
+    """misift_test_merge_capacity (host-only): the elements of a union merge_scenes_batch stages on chip."""
+    return int(lib().misift_test_merge_capacity())
 
 
 def knob_names():
@@ -1500,6 +1516,52 @@ class Context:
                                                  _dptr(cam), _dptr(cam_pair), _dptr(points_out), _dptr(cam_out)),
               "misift_transform_scene_batch")
         return points_out, cam_out
+
+    def merge_scenes_batch(self, a, b, point_map, nimages_out, max_tracks_out, max_obs_out, accept=None, fshift_a=0,
+                           fshift_b=0, rshift_a=0, rshift_b=0, max_records_out=0, track_offsets_out=None, obs_out=None,
+                           export_summary_out=None, points_out=None, point_views_out=None, point_status_out=None,
+                           cam_out=None, cam_pair_out=None, track_map_a=None, obs_map_a=True, obs_map_b=True,
+                           record_obs_out=None, summary=None):
+        """misift_merge_scenes_batch: scene a (after transform_scene_batch has moved it into b's gauge) and scene b
+        written out as one scene in export's format.  a and b are dicts of the MERGE_SCENE_KEYS: the capacities and
+        device buffers of export_tracks_batch (track_offsets, obs, export_summary, and record_obs with max_records when
+        record_obs_out is wanted), of triangulate_tracks_batch (points, point_views, point_status) and the cameras
+        (nimages, cam, cam_pair).  point_map: the track_map of correspond_tracks_batch(a, b); accept: the inlier buffer
+        of align_points_batch over a's tracks, or None.  Image i of a is image i + fshift_a of the merged scene of
+        nimages_out images, record g of a is record g + rshift_a of max_records_out, and likewise for b.  b's tracks
+        keep their numbers and a's unmatched tracks follow; an observation both scenes hold stays once, as b's.
+        track_offsets_out, obs_out, export_summary_out, points_out, point_views_out, point_status_out, cam_out and
+        cam_pair_out go to triangulate, refine, resect, filter and adjust as they are; track_map_a (a's max_tracks
+        ints), obs_map_a, obs_map_b (True allocates, None leaves out), record_obs_out (True allocates; needs both
+        record_obs) and summary (8 ints) tell what became of what.  All are device buffers, allocated here when not
+        passed; returns a dict of the MERGE_OUTPUTS.  Nothing may overlap.  Enqueued on the context stream."""
+        mt, mo, ni = max(max_tracks_out, 1), max(max_obs_out, 1), max(nimages_out, 1)
+        outs = dict(track_offsets_out=track_offsets_out, obs_out=obs_out, export_summary_out=export_summary_out,
+                    points_out=points_out, point_views_out=point_views_out, point_status_out=point_status_out,
+                    cam_out=cam_out, cam_pair_out=cam_pair_out, track_map_a=track_map_a, obs_map_a=obs_map_a,
+                    obs_map_b=obs_map_b, record_obs_out=record_obs_out, summary=summary)
+        sizes = dict(track_offsets_out=4 * (mt + 1), obs_out=16 * mo, export_summary_out=32, points_out=16 * mt,
+                     point_views_out=4 * mt, point_status_out=4 * mt, cam_out=48 * ni, cam_pair_out=4 * ni,
+                     track_map_a=4 * max(a["max_tracks"], 1), obs_map_a=4 * max(a["max_obs"], 1),
+                     obs_map_b=4 * max(b["max_obs"], 1), record_obs_out=4 * max(max_records_out, 1), summary=32)
+        optional = ("obs_map_a", "obs_map_b", "record_obs_out")
+        for k in MERGE_OUTPUTS:
+            if outs[k] is True or (outs[k] is None and k not in optional):
+                outs[k] = self.zeros(sizes[k])
+
+        def scene(s):
+            return [_dptr(s.get(k)) if k in ("track_offsets", "obs", "export_summary", "points", "point_views",
+                                             "point_status", "cam", "cam_pair", "record_obs") else int(s.get(k) or 0)
+                    for k in MERGE_SCENE_KEYS]
+
+        check(lib().misift_merge_scenes_batch(self.h, *scene(a), *scene(b), _dptr(point_map), _dptr(accept),
+                                              int(fshift_a), int(fshift_b), int(nimages_out), int(rshift_a),
+                                              int(rshift_b), int(max_records_out), int(max_tracks_out),
+                                              int(max_obs_out), *[_dptr(outs[k]) for k in MERGE_OUTPUTS]),
+              "misift_merge_scenes_batch")
+        return outs
+
+    merge_scenes = merge_scenes_batch
 
     def match_split(self, pts1, n1, pts2, n2, own_tile_begin, own_tile_end):
         """Test hook: misift_match with the column sweep cut into two launches (the sharded matcher's cut)."""

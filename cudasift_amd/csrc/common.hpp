@@ -752,6 +752,11 @@ int launch_filter_tracks_batch(misift_ctx *ctx, const TrackScene &scene, float t
                                int unique_frames, int *d_track_offsets_out, void *d_obs_out, int *d_export_summary_out,
                                float *d_points_out, int *d_point_views_out, int *d_point_status_out, int *d_track_map,
                                int *d_obs_map, int *d_summary);
+// misift_merge_scenes_batch (kernels_merge.hip): three memsets + ten launches; temp from misift_ensure_tmp, sized from the
+// four capacities only.  MergeIn (merge_core.hpp): both scenes, the map, the outputs, all checked by the caller
+struct MergeIn;
+size_t merge_scenes_batch_tmp_bytes(int max_tracks_a, int max_obs_a, int max_tracks_b, int max_obs_b);
+int launch_merge_scenes_batch(misift_ctx *ctx, const MergeIn &in);
 int launch_test_exp2(misift_ctx *ctx, const float *x, float *out, int n);
 int launch_test_points_fn(misift_ctx *ctx, int fn, const float *x, const float *y, float *out, float *out2, int n);
 int launch_selftest(misift_ctx *ctx);

@@ -21,6 +21,7 @@
 #include <vector>
 #include "common.hpp"
 #include "chain.hpp"
+#include "merge_core.hpp"
 #include "pair_plan.hpp"
 
 // ------------------------------------------------------------------ errors
@@ -3151,6 +3152,129 @@ extern "C" int misift_filter_tracks_batch(misift_ctx *ctx, int max_tracks, int m
                                       d_export_summary_out, d_points_out, d_point_views_out, d_point_status_out,
                                       d_track_map, d_obs_map, d_summary);
   });
+}
+
+// Two scenes in one gauge written out as one: the arguments of misift_merge_scenes_batch and of its host hook checked
+// and put into a MergeIn (merge_core.hpp).  Every rule of the header's error list but the NULL context is here.
+static int merge_check(const char *who, MergeIn *in, int max_tracks_a, int max_obs_a, const int *track_offsets_a, const misift_track_obs *obs_a,
+                      const int *export_summary_a, const float *points_a, const int *point_views_a,
+                      const int *point_status_a, int nimages_a, const float *cam_a, const int *cam_pair_a,
+                      int max_records_a, const int *record_obs_a, int max_tracks_b, int max_obs_b,
+                      const int *track_offsets_b, const misift_track_obs *obs_b, const int *export_summary_b,
+                      const float *points_b, const int *point_views_b, const int *point_status_b, int nimages_b,
+                      const float *cam_b, const int *cam_pair_b, int max_records_b, const int *record_obs_b,
+                      const int *map, const int *accept, int fshift_a, int fshift_b, int nimages_out, int rshift_a,
+                      int rshift_b, int max_records_out, int max_tracks_out, int max_obs_out, int *track_offsets_out,
+                      misift_track_obs *obs_out, int *export_summary_out, float *points_out, int *point_views_out,
+                      int *point_status_out, float *cam_out, int *cam_pair_out, int *track_map_a, int *obs_map_a,
+                      int *obs_map_b, int *record_obs_out, int *summary)
+{
+  ARG_CHECK_IN(who, max_tracks_a >= 1 && max_obs_a >= 1 && nimages_a >= 1);
+  ARG_CHECK_IN(who, max_tracks_b >= 1 && max_obs_b >= 1 && nimages_b >= 1);
+  ARG_CHECK_IN(who, max_tracks_out >= 1 && max_obs_out >= 1 && nimages_out >= 1);
+  ARG_CHECK_IN(who, track_offsets_a && obs_a && export_summary_a && points_a && point_views_a && point_status_a);
+  ARG_CHECK_IN(who, track_offsets_b && obs_b && export_summary_b && points_b && point_views_b && point_status_b);
+  ARG_CHECK_IN(who, cam_a && cam_pair_a && cam_b && cam_pair_b && map);
+  ARG_CHECK_IN(who, track_offsets_out && obs_out && export_summary_out && points_out && point_views_out);
+  ARG_CHECK_IN(who, point_status_out && cam_out && cam_pair_out && track_map_a && summary);
+  ARG_CHECK_IN(who, fshift_a >= 0 && fshift_b >= 0 && rshift_a >= 0 && rshift_b >= 0);
+  ARG_CHECK_IN(who, (long long)nimages_a + fshift_a <= nimages_out && (long long)nimages_b + fshift_b <= nimages_out);
+  if (record_obs_out) {
+    ARG_CHECK_IN(who, record_obs_a && record_obs_b);
+    ARG_CHECK_IN(who, max_records_a >= 1 && max_records_b >= 1 && max_records_out >= 1);
+    ARG_CHECK_IN(who, (long long)max_records_a + rshift_a <= max_records_out);
+    ARG_CHECK_IN(who, (long long)max_records_b + rshift_b <= max_records_out);
+  }
+  ARG_CHECK_IN(who, (((uintptr_t)obs_a | (uintptr_t)obs_b | (uintptr_t)obs_out) & 15) == 0);
+  {
+    // the copy moves entries across workgroups: no output may share a byte with an input or with another output
+    const size_t ta = (size_t)max_tracks_a, oa = (size_t)max_obs_a, na = (size_t)nimages_a;
+    const size_t tb = (size_t)max_tracks_b, ob = (size_t)max_obs_b, nb = (size_t)nimages_b;
+    const size_t to = (size_t)max_tracks_out, oo = (size_t)max_obs_out, no = (size_t)nimages_out;
+    const size_t ra = record_obs_out ? (size_t)max_records_a : 0, rb = record_obs_out ? (size_t)max_records_b : 0;
+    const struct { const void *p; size_t bytes; } span[33] = {
+        {track_offsets_out, 4 * (to + 1)}, {obs_out, 16 * oo}, {export_summary_out, 32}, {points_out, 16 * to},
+        {point_views_out, 4 * to}, {point_status_out, 4 * to}, {cam_out, 48 * no}, {cam_pair_out, 4 * no},
+        {track_map_a, 4 * ta}, {obs_map_a, 4 * oa}, {obs_map_b, 4 * ob}, {record_obs_out, 4 * (size_t)max_records_out},
+        {summary, 32},
+        {track_offsets_a, 4 * (ta + 1)}, {obs_a, 16 * oa}, {export_summary_a, 32}, {points_a, 16 * ta},
+        {point_views_a, 4 * ta}, {point_status_a, 4 * ta}, {cam_a, 48 * na}, {cam_pair_a, 4 * na}, {record_obs_a, 4 * ra},
+        {track_offsets_b, 4 * (tb + 1)}, {obs_b, 16 * ob}, {export_summary_b, 32}, {points_b, 16 * tb},
+        {point_views_b, 4 * tb}, {point_status_b, 4 * tb}, {cam_b, 48 * nb}, {cam_pair_b, 4 * nb}, {record_obs_b, 4 * rb},
+        {map, 4 * ta}, {accept, 4 * ta}};
+    for (int a = 0; a < 13; a++)
+      for (int b = a + 1; b < 33; b++) {
+        if (!span[a].p || !span[b].p || !span[a].bytes || !span[b].bytes) continue;    // the optional ones
+        const uintptr_t pa = (uintptr_t)span[a].p, pb = (uintptr_t)span[b].p;
+        ARG_CHECK_IN(who, pa + span[a].bytes <= pb || pb + span[b].bytes <= pa);
+      }
+  }
+  const TrackScene sa{max_tracks_a, max_obs_a, nimages_a, track_offsets_a, reinterpret_cast<const TrackObs *>(obs_a),
+                      export_summary_a, points_a, point_status_a, cam_a, cam_pair_a, nullptr};
+  const TrackScene sb{max_tracks_b, max_obs_b, nimages_b, track_offsets_b, reinterpret_cast<const TrackObs *>(obs_b),
+                      export_summary_b, points_b, point_status_b, cam_b, cam_pair_b, nullptr};
+  in->a = MergeScene{sa, point_views_a, record_obs_out ? record_obs_a : nullptr, max_records_a, fshift_a, rshift_a};
+  in->b = MergeScene{sb, point_views_b, record_obs_out ? record_obs_b : nullptr, max_records_b, fshift_b, rshift_b};
+  in->map = map;
+  in->accept = accept;
+  in->out = MergeOut{max_tracks_out, max_obs_out, nimages_out, max_records_out, track_offsets_out,
+                     reinterpret_cast<TrackObs *>(obs_out), export_summary_out, points_out, point_views_out,
+                     point_status_out, cam_out, cam_pair_out, track_map_a, obs_map_a, obs_map_b, record_obs_out, summary};
+  return MISIFT_OK;
+}
+
+extern "C" int misift_merge_scenes_batch(misift_ctx *ctx, int max_tracks_a, int max_obs_a, const int *track_offsets_a, const misift_track_obs *obs_a,
+                      const int *export_summary_a, const float *points_a, const int *point_views_a,
+                      const int *point_status_a, int nimages_a, const float *cam_a, const int *cam_pair_a,
+                      int max_records_a, const int *record_obs_a, int max_tracks_b, int max_obs_b,
+                      const int *track_offsets_b, const misift_track_obs *obs_b, const int *export_summary_b,
+                      const float *points_b, const int *point_views_b, const int *point_status_b, int nimages_b,
+                      const float *cam_b, const int *cam_pair_b, int max_records_b, const int *record_obs_b,
+                      const int *map, const int *accept, int fshift_a, int fshift_b, int nimages_out, int rshift_a,
+                      int rshift_b, int max_records_out, int max_tracks_out, int max_obs_out, int *track_offsets_out,
+                      misift_track_obs *obs_out, int *export_summary_out, float *points_out, int *point_views_out,
+                      int *point_status_out, float *cam_out, int *cam_pair_out, int *track_map_a, int *obs_map_a,
+                      int *obs_map_b, int *record_obs_out, int *summary)
+{
+  ARG_CHECK(ctx != nullptr);
+  MergeIn in;
+  const int rc = merge_check(__func__, &in, max_tracks_a, max_obs_a, track_offsets_a, obs_a, export_summary_a, points_a, point_views_a, point_status_a,
+                      nimages_a, cam_a, cam_pair_a, max_records_a, record_obs_a, max_tracks_b, max_obs_b, track_offsets_b,
+                      obs_b, export_summary_b, points_b, point_views_b, point_status_b, nimages_b, cam_b, cam_pair_b,
+                      max_records_b, record_obs_b, map, accept, fshift_a, fshift_b, nimages_out, rshift_a, rshift_b,
+                      max_records_out, max_tracks_out, max_obs_out, track_offsets_out, obs_out, export_summary_out,
+                      points_out, point_views_out, point_status_out, cam_out, cam_pair_out, track_map_a, obs_map_a,
+                      obs_map_b, record_obs_out, summary);
+  if (rc) return rc;
+  RoctxRange range(__func__);
+  return run_batch(ctx, {}, 0, [&](int *, void *) { return launch_merge_scenes_batch(ctx, in); });
+}
+
+// Test-only, host-only: the whole call on host arrays by the rules the kernels compile (merge_core.hpp).
+extern "C" int misift_test_merge_scenes(int max_tracks_a, int max_obs_a, const int *track_offsets_a, const misift_track_obs *obs_a,
+                      const int *export_summary_a, const float *points_a, const int *point_views_a,
+                      const int *point_status_a, int nimages_a, const float *cam_a, const int *cam_pair_a,
+                      int max_records_a, const int *record_obs_a, int max_tracks_b, int max_obs_b,
+                      const int *track_offsets_b, const misift_track_obs *obs_b, const int *export_summary_b,
+                      const float *points_b, const int *point_views_b, const int *point_status_b, int nimages_b,
+                      const float *cam_b, const int *cam_pair_b, int max_records_b, const int *record_obs_b,
+                      const int *map, const int *accept, int fshift_a, int fshift_b, int nimages_out, int rshift_a,
+                      int rshift_b, int max_records_out, int max_tracks_out, int max_obs_out, int *track_offsets_out,
+                      misift_track_obs *obs_out, int *export_summary_out, float *points_out, int *point_views_out,
+                      int *point_status_out, float *cam_out, int *cam_pair_out, int *track_map_a, int *obs_map_a,
+                      int *obs_map_b, int *record_obs_out, int *summary)
+{
+  MergeIn in;
+  const int rc = merge_check(__func__, &in, max_tracks_a, max_obs_a, track_offsets_a, obs_a, export_summary_a, points_a, point_views_a, point_status_a,
+                      nimages_a, cam_a, cam_pair_a, max_records_a, record_obs_a, max_tracks_b, max_obs_b, track_offsets_b,
+                      obs_b, export_summary_b, points_b, point_views_b, point_status_b, nimages_b, cam_b, cam_pair_b,
+                      max_records_b, record_obs_b, map, accept, fshift_a, fshift_b, nimages_out, rshift_a, rshift_b,
+                      max_records_out, max_tracks_out, max_obs_out, track_offsets_out, obs_out, export_summary_out,
+                      points_out, point_views_out, point_status_out, cam_out, cam_pair_out, track_map_a, obs_map_a,
+                      obs_map_b, record_obs_out, summary);
+  if (rc) return rc;
+  merge_scenes_host(in);
+  return MISIFT_OK;
 }
 
 // ------------------------------------------------------------------- timing

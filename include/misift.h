@@ -445,7 +445,8 @@ int misift_match_pairs_batch(misift_ctx *ctx, int npairs, const int *pairs,
  *     misift_find_fundamental_batch, misift_score_fundamental_batch, misift_improve_fundamental_batch,
  *     misift_recover_pose_batch, misift_recover_pose_planar_batch, misift_link_poses_batch, misift_match_guided_batch,
  *     misift_match_epipolar_batch, misift_link_tracks_batch, misift_export_tracks_batch,
- *     misift_triangulate_tracks_batch and misift_refine_cameras_batch (which run on the context stream) on a batch's
+ *     misift_triangulate_tracks_batch, misift_refine_cameras_batch and misift_merge_scenes_batch (which run on the
+ *     context stream) on a batch's
  *     packed records: make the context stream wait for that batch first
  *     (misift_ctx_wait_batch(ctx, <the context's stream>), or an event from misift_ctx_record_batch).
  * K = 1 (default) is the plain in-order context.  Also MISIFT_BATCHES_IN_FLIGHT at context creation.  Changing K drains
@@ -1515,9 +1516,9 @@ int misift_resect_cameras_batch(misift_ctx *ctx,
  * a reconstruction against surveyed points.  misift_correspond_tracks_batch finds which points correspond,
  * misift_align_points_batch estimates the similarity transform b = s R a + t between them robustly, and
  * misift_transform_scene_batch applies it to points and cameras.
+ * misift_merge_scenes_batch then writes the two scenes out as one, which every call of the track chain takes.
  *   - Not done here: no reprojection-error inlier test (the test is the 3-D distance in the units of d_dst); no
- *     camera-centre correspondences; no merging of the two scenes' tracks into one export; no re-adjustment afterwards,
- *     which misift_adjust_bundle_* does on the merged scene.
+ *     camera-centre correspondences; no re-adjustment afterwards, which misift_adjust_bundle_* does on the merged scene.
  *
  * misift_correspond_tracks_batch: two exported scenes A and B over the same records (two link / export runs over different
  * pair sets of one record batch, or over two views into one packed batch).  Record g of A (its global index, as
@@ -1668,6 +1669,124 @@ int misift_transform_scene_batch(misift_ctx *ctx,
                                  const int *d_cam_pair,       /* nimages */
                                  float *d_points_out,         /* max_tracks x 4 */
                                  float *d_cam_out);           /* nimages x 12 */
+
+/* misift_merge_scenes_batch: two exported scenes that lie in one gauge written out as ONE scene (no reference
+ * counterpart): one export, one point array, one camera array and one record index, which triangulate, refine, resect,
+ * filter and adjust take unchanged.  Scene B is the reference: its gauge is the merged gauge, and
+ * misift_align_points_batch with A as the source and B as the destination followed by misift_transform_scene_batch on A
+ * puts A's points and cameras there; this call takes A after that transform.  The chain
+ * export A, export B -> triangulate each -> correspond -> align -> transform(A) -> merge(A into B) -> triangulate or
+ * adjust on the merged scene runs with no host read.
+ *   Per scene S (A or B): d_track_offsets_S, d_obs_S and d_export_summary_S from export (or filter) for max_tracks_S and
+ *   max_obs_S; d_points_S, d_point_views_S and d_point_status_S from triangulate (A's points after the transform); d_cam_S
+ *   and d_cam_pair_S for nimages_S images; d_record_obs_S (max_records_S ints, from export; read only when
+ *   d_record_obs_out is given, otherwise it may be NULL and max_records_S is not looked at).  d_map (max_tracks_a ints) is
+ *   what misift_correspond_tracks_batch wrote for (A, B); d_accept (max_tracks_a ints, may be NULL) is d_inlier of
+ *   misift_align_points_batch for the entry whose source points are A's tracks.  Image i of S is image i + fshift_S of
+ *   the merged scene, which has nimages_out images; global record g of S is record g + rshift_S of the merged index of
+ *   max_records_out records.  rshift_b - rshift_a is the `shift` correspond was called with; the call does not check
+ *   that.  Intrinsics are host arrays: the caller lays out the merged scene's itself.
+ *   T_A, O_A, T_B and O_B are read on the device and clamped as in misift_correspond_tracks_batch.  VALID tracks and the
+ *   OWNER of a slot are those of misift_refine_cameras_batch, per scene; the observations of a valid track are the slots
+ *   it owns.  Everything is integer work and bit copies: there is no floating-point arithmetic in the call.
+ *   1. Live observations.  Slot o of a valid track of scene S is LIVE iff its frame lies in [0, nimages_S).  Its KEY is
+ *      the 64-bit value ((int64)(frame + fshift_S) << 32) | (uint32)record.
+ *   2. Class of A-track t < T_A, the first that applies: -1 the track is not valid; -2 d_map[t] == -2; -4 d_map[t] < -2
+ *      or d_map[t] >= T_B; -3 d_map[t] >= 0, d_accept is given and d_accept[t] == 0 (a tie that the 3-D test rejected).
+ *      Otherwise the track is a PARTNER of B-track d_map[t] when that is >= 0 and ALONE when it is -1.  A tie whose
+ *      d_accept is 1 or -1 is merged (-1: one of the two points failed, so nothing speaks against the shared records).
+ *   3. Merged tracks.  B-track tB < T_B is merged track t' = tB: B's numbering is kept.  The ALONE A-tracks follow in
+ *      ascending tA: t' = T_B + the number of ALONE tracks before tA; N = T_B + the number of ALONE tracks.  The UNION of
+ *      t' < T_B is the live observations of tB (source 0; none if tB is not valid) and the live observations of every
+ *      PARTNER of tB (source 1); the UNION of an ALONE track is its own live observations (source 1).  An element of a
+ *      union is KEPT iff no other element of that union has the same KEY and a smaller (source, slot): a record seen by
+ *      both scenes stays once, as B's, and hostile duplicates inside one list collapse too.  len'[t'] = the number of
+ *      kept elements; a kept element's place in the track = the number of kept elements with a smaller KEY (ascending
+ *      (frame, record): export's order for any layout whose frames ascend in memory).  Both rules are order-free, so the
+ *      output depends neither on the order in which partners are enumerated (the partner lists are filled by atomicAdd,
+ *      unordered) nor on whether the input lists are sorted.  len' == 0 is allowed and keeps its number.
+ *   4. Capacity, as export's.  off'[t'] = the sum of len' before t' (in 64 bits).  Track t' is WRITTEN iff
+ *      t' < max_tracks_out and off'[t'] + len'[t'] <= max_obs_out.  The written tracks are a prefix T' holding O'
+ *      observations; no track is cut in the middle.
+ *   5. Outputs, for t' < T': d_track_offsets_out[0 .. T'] = off' ([0] = 0 always); d_obs_out[off' + k] = for the k-th
+ *      kept element its frame + fshift_S, its record, and the bits of xpos and ypos; d_points_out[4t' .. 4t'+3],
+ *      d_point_views_out[t'] and d_point_status_out[t'] = bit copies from B at tB when t' < T_B and from A at tA otherwise
+ *      (the rms word and the view count are stale by construction: call triangulate or adjust next).
+ *      d_track_map_a[t], t < T_A: the negative class, or the merged t', or -6 when that t' >= T'.
+ *      d_obs_map_a[o], o < O_A (may be NULL): -1 when the slot has no owner; the owner's negative code (its class, or -6)
+ *      when the owner was dropped or cut; -5 when the observation is not live; otherwise the new slot of the kept element
+ *      with its KEY, so a duplicate maps onto its surviving twin.  d_obs_map_b[o], o < O_B (may be NULL): the same, with
+ *      -1, -6, -5 or the slot.
+ *      d_record_obs_out (max_records_out ints, may be NULL; needs both d_record_obs_a and d_record_obs_b): every entry is
+ *      written.  Entry g' = the first that applies: d_obs_map_b[d_record_obs_b[g' - rshift_b]] when the index lies in
+ *      [0, max_records_b), the slot in [0, O_B) and the map value is >= 0; else the same through A; else -1 (the map
+ *      values are those defined above whether or not the maps are given).
+ *      Cameras, image i' < nimages_out, the first that applies: iB = i' - fshift_b lies in [0, nimages_b) and
+ *      d_cam_pair_b[iB] != -2: B's twelve words bit for bit and d_cam_pair_out[i'] = d_cam_pair_b[iB]; the same holds
+ *      through A: A's twelve words and d_cam_pair_out[i'] = MISIFT_CAM_MERGED (a second root must not appear; as stated
+ *      under misift_resect_cameras_batch every value but -2 means "has a camera" and only -1 is the root); neither:
+ *      twelve zeros and -2.
+ *      d_export_summary_out (export's layout): [0] N, [1] the kept observations of all N tracks, [2] T', [3] O', [4] the
+ *      longest written track, [5..7] 0.  d_summary (8 ints): [0] T', [1] O', [2] A-tracks written as partners, [3]
+ *      A-tracks written alone, [4] A-tracks with class -1 ... -4, [5] duplicate observations removed in written tracks,
+ *      [6] N - T', [7] images whose camera came from A.
+ *      Outputs beyond T', T' + 1 (the offsets), O', T_A (d_track_map_a), O_A and O_B (the slot maps) stay untouched.
+ *   - Not done here: B's point is taken as it is and the merged point is not re-estimated (triangulate or adjust does
+ *     that next); an A-track tied to several B-tracks (-2) is dropped, not used to join them; intrinsics are the caller's.
+ *   - NULL ctx, or a NULL pointer other than d_accept, d_obs_map_a, d_obs_map_b and d_record_obs_out (and the two
+ *     d_record_obs_S without it); a capacity or image count < 1 (max_records_* only with d_record_obs_out); a negative
+ *     shift; nimages_S + fshift_S > nimages_out, or max_records_S + rshift_S > max_records_out where d_record_obs_out is
+ *     given; d_record_obs_out given without both input record arrays; d_obs_a, d_obs_b or d_obs_out not 16-byte aligned;
+ *     any output overlapping an input or another output, each at its stated size: MISIFT_EINVAL, before anything is
+ *     enqueued.  None of the inputs is written.
+ *   - Deterministic: byte-identical from run to run.  Every index read from device memory (T, O, offsets, frames, map
+ *     values, record slots) is range-checked before it addresses anything.
+ *   - The call runs on the context stream and returns before the GPU work is done; no host synchronisation and no host
+ *     read.  Ordering behind batches in flight (K > 1): as misift_match_batch.
+ *   - Three memsets and ten launches whatever the data: the owners of both scenes, one lane per A-track for the class and
+ *     the partner counts, the scan of 2048-track tile sums in one workgroup and one lane per B-track for the partner
+ *     lists, their unordered fill, one wavefront per merged track for the union (its first 256 elements staged on chip,
+ *     ranked by all-pairs comparison across the 64 lanes; a longer union takes a piece of temp memory), the tile scan and
+ *     one lane per merged track for the numbering, and one lane per slot, A-track, record and image for the copy.  No
+ *     workgroup waits for another.  Temp memory from the library's own allocator, sized from the capacities only: 24
+ *     bytes per slot of max_obs_a + max_obs_b, 20 per track of max_tracks_a, 20 per track of max_tracks_b plus 16 per
+ *     2048 tracks, each array rounded up to 16. */
+#define MISIFT_CAM_MERGED (-4)
+int misift_merge_scenes_batch(misift_ctx *ctx,
+                              int max_tracks_a, int max_obs_a,
+                              const int *d_track_offsets_a,     /* max_tracks_a + 1, from export */
+                              const misift_track_obs *d_obs_a,  /* max_obs_a, 16-byte aligned */
+                              const int *d_export_summary_a,    /* 8 ints: [2] = T_A, [3] = O_A */
+                              const float *d_points_a,          /* max_tracks_a x 4, after the transform */
+                              const int *d_point_views_a,       /* max_tracks_a */
+                              const int *d_point_status_a,      /* max_tracks_a */
+                              int nimages_a,
+                              const float *d_cam_a,             /* nimages_a x 12, after the transform */
+                              const int *d_cam_pair_a,          /* nimages_a */
+                              int max_records_a, const int *d_record_obs_a,   /* may be NULL */
+                              int max_tracks_b, int max_obs_b,
+                              const int *d_track_offsets_b, const misift_track_obs *d_obs_b,
+                              const int *d_export_summary_b, const float *d_points_b, const int *d_point_views_b,
+                              const int *d_point_status_b, int nimages_b, const float *d_cam_b,
+                              const int *d_cam_pair_b, int max_records_b, const int *d_record_obs_b,
+                              const int *d_map,                 /* max_tracks_a, from correspond */
+                              const int *d_accept,              /* max_tracks_a, d_inlier of align; may be NULL */
+                              int fshift_a, int fshift_b, int nimages_out,
+                              int rshift_a, int rshift_b, int max_records_out,
+                              int max_tracks_out, int max_obs_out,
+                              int *d_track_offsets_out,         /* max_tracks_out + 1 */
+                              misift_track_obs *d_obs_out,      /* max_obs_out, 16-byte aligned */
+                              int *d_export_summary_out,        /* 8 ints, export's layout */
+                              float *d_points_out,              /* max_tracks_out x 4 */
+                              int *d_point_views_out,           /* max_tracks_out */
+                              int *d_point_status_out,          /* max_tracks_out */
+                              float *d_cam_out,                 /* nimages_out x 12 */
+                              int *d_cam_pair_out,              /* nimages_out */
+                              int *d_track_map_a,               /* max_tracks_a: t', or the reason */
+                              int *d_obs_map_a,                 /* max_obs_a: the new slot or the reason; may be NULL */
+                              int *d_obs_map_b,                 /* max_obs_b; may be NULL */
+                              int *d_record_obs_out,            /* max_records_out; may be NULL */
+                              int *d_summary);                  /* 8 ints */
 
 /* The cameras and the track points adjusted jointly (bundle adjustment; no reference counterpart): what
  * misift_refine_cameras_batch and misift_triangulate_tracks_batch do in turns, done in one Levenberg-Marquardt step over
@@ -2202,6 +2321,24 @@ int misift_test_filter_tracks(int max_tracks, int max_obs, const int *track_offs
                               misift_track_obs *obs_out, int *export_summary_out, float *points_out,
                               int *point_views_out, int *point_status_out, int *track_map, int *obs_map, int *summary);
 int misift_test_filter_stage(void);
+
+/* Test-only, host-only: the whole of misift_merge_scenes_batch on host arrays, every rule compiled from the function its
+ * kernels run (merge_core.hpp).  The arguments are those of the call without the context; all pointers are host; the
+ * argument checks are the call's own.  misift_test_merge_capacity: the elements of a union its wavefront stages on chip. */
+int misift_test_merge_scenes(int max_tracks_a, int max_obs_a, const int *track_offsets_a, const misift_track_obs *obs_a,
+                             const int *export_summary_a, const float *points_a, const int *point_views_a,
+                             const int *point_status_a, int nimages_a, const float *cam_a, const int *cam_pair_a,
+                             int max_records_a, const int *record_obs_a, int max_tracks_b, int max_obs_b,
+                             const int *track_offsets_b, const misift_track_obs *obs_b, const int *export_summary_b,
+                             const float *points_b, const int *point_views_b, const int *point_status_b, int nimages_b,
+                             const float *cam_b, const int *cam_pair_b, int max_records_b, const int *record_obs_b,
+                             const int *map, const int *accept, int fshift_a, int fshift_b, int nimages_out, int rshift_a,
+                             int rshift_b, int max_records_out, int max_tracks_out, int max_obs_out,
+                             int *track_offsets_out, misift_track_obs *obs_out, int *export_summary_out,
+                             float *points_out, int *point_views_out, int *point_status_out, float *cam_out,
+                             int *cam_pair_out, int *track_map_a, int *obs_map_a, int *obs_map_b, int *record_obs_out,
+                             int *summary);
+int misift_test_merge_capacity(void);
 
 /* Test-only, host-only: steps 3 and 4 of misift_resect_cameras_batch, compiled from the functions its kernels run.  The
  * sample positions: out[6 * loop + j] = position j (in the ordered list of n >= 6 candidates) of hypothesis loop after
