@@ -23,7 +23,7 @@ all: cudasift_amd/libmisift.so cudasift_amd/libcudasift.so cudasift_amd/libcudas
 $(BUILD)/%.o: $(CSRC)/%.hip $(CSRC)/common.hpp $(CSRC)/chain.hpp $(CSRC)/match_sweep.inc $(CSRC)/match_i8_sweep.inc \
             $(CSRC)/homography_core.inc $(CSRC)/ransac_batch.hpp $(CSRC)/fundamental_core.hpp $(CSRC)/pose_core.hpp $(CSRC)/pose_planar_core.hpp $(CSRC)/posegraph_core.hpp \
             $(CSRC)/epipolar_core.hpp $(CSRC)/triangulate_core.hpp $(CSRC)/refine_core.hpp \
-            $(CSRC)/resect_core.hpp $(CSRC)/bundle_core.hpp $(CSRC)/filter_core.hpp $(CSRC)/scan_core.hpp \
+            $(CSRC)/resect_core.hpp $(CSRC)/bundle_core.hpp $(CSRC)/bundle_host.hpp $(CSRC)/filter_core.hpp $(CSRC)/scan_core.hpp \
             $(CSRC)/track_candidates.hpp $(CSRC)/select_core.hpp $(CSRC)/align_core.hpp $(CSRC)/merge_core.hpp \
             $(CSRC)/libc_rand.hpp $(CSRC)/quantize_i8.hpp $(CSRC)/pair_plan.hpp $(CSRC)/pair_plan_body.inc include/misift.h
 	@mkdir -p $(BUILD)

@@ -34,6 +34,8 @@ MERGE_OUTPUTS = ("track_offsets_out", "obs_out", "export_summary_out", "points_o
 LOSS_NONE, LOSS_HUBER, LOSS_GEMAN_MCCLURE = 0, 1, 2            # MISIFT_LOSS_*: adjust_bundle_robust_batch
 MAX_FOCAL_GROUPS = 8                                           # MISIFT_MAX_FOCAL_GROUPS: adjust_bundle_focal_batch
 FOCAL_REFINED, FOCAL_NO_MEMBER, FOCAL_NOT_REFINED = 0, 1, 2    # MISIFT_FOCAL_*: d_focal[3g + 2]
+MAX_RADIAL_GROUPS = MAX_FOCAL_GROUPS                           # MISIFT_MAX_RADIAL_GROUPS: adjust_bundle_radial_batch
+RADIAL_REFINED, RADIAL_NO_MEMBER, RADIAL_NOT_REFINED, RADIAL_HELD = 0, 1, 2, 3   # MISIFT_RADIAL_*: d_radial[3g + 2]
 assert TRACK_OBS_DTYPE.itemsize == 16
 
 
@@ -151,6 +153,12 @@ SIGNATURES = {
     "misift_test_adjust_bundle_focal": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i,
                                              _f, _f, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                              _vp, _vp]),
+    "misift_adjust_bundle_radial_batch": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _i,
+                                               _i, _f, _f, _i, _i, _f, _i, _vp, _vp, _vp] + 13 * [_vp]),
+    "misift_test_adjust_bundle_radial": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i,
+                                              _f, _f, _i, _i, _f, _i, _vp, _vp, _vp] + 13 * [_vp]),
+    "misift_undistort_obs_batch": (_i, [_vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp]),
+    "misift_test_undistort_obs": (_i, [_i, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp]),
     "misift_test_adjust_bundle": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _f, _f,
                                        _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "misift_filter_tracks_batch": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _f, _f, _i, _i, _vp, _vp,
@@ -1356,6 +1364,91 @@ class Context:
             "misift_adjust_bundle_focal_batch")
         return (cam_out, points_out, cam_obs, cam_status, cam_rms, point_obs, history, cost, obs_weight, summary,
                 intrinsics_out, focal)
+
+    def adjust_bundle_radial_batch(self, max_tracks, max_obs, track_offsets, obs, export_summary, points, point_status,
+                                   nimages, cam, cam_pair, intrinsics, group, ngroups=None, radial=None, k0=None, hold=(),
+                                   min_views=2, min_obs=6, num_loops=5, cg_iters=10, max_error=np.inf, lambda0=1e-3,
+                                   orthonormalise=True, loss=LOSS_NONE, loss_scale=2.0, cam_out=None, points_out=None,
+                                   cam_obs=None, cam_status=None, cam_rms=None, point_obs=None, history=None, cost=None,
+                                   obs_weight=None, summary=None, intrinsics_out=None, focal=None, radial_out=None):
+        """misift_adjust_bundle_radial_batch: adjust_bundle_focal_batch with one radial coefficient per camera group
+        among the unknowns, applied to the observation (the model is in include/misift.h).  radial (host, ngroups ints,
+        1 = the coefficient is an unknown) and k0 (host, ngroups floats, its start and, where radial is 0, held value)
+        are both given or both None (all zero).  The further arguments and the twelve outputs are those of
+        adjust_bundle_focal_batch; radial_out (ngroups x 3 words: the coefficient, the members, RADIAL_*) is a device
+        buffer, allocated here when not passed, and what undistort_obs_batch takes; returns the thirteen.  Enqueued on
+        the context stream."""
+        group = np.ascontiguousarray(group, np.int32).reshape(-1)
+        if ngroups is None:
+            ngroups = int(group.max()) + 1 if len(group) else 0
+        assert ngroups == 0 or len(group) == nimages
+        assert (radial is None) == (k0 is None)
+        if radial is not None:
+            radial = np.ascontiguousarray(radial, np.int32).reshape(-1)
+            k0 = np.ascontiguousarray(k0, np.float32).reshape(-1)
+            assert len(radial) == ngroups and len(k0) == ngroups
+        if intrinsics_out is None:
+            intrinsics_out = self.zeros(16 * max(nimages, 1))
+        if focal is None:
+            focal = self.zeros(12 * max(int(ngroups), 1))
+        if radial_out is None:
+            radial_out = self.zeros(12 * max(int(ngroups), 1))
+        if obs_weight is True:
+            obs_weight = self.zeros(4 * max(max_obs, 1))
+        elif obs_weight is False:
+            obs_weight = None
+        intrinsics = np.ascontiguousarray(intrinsics, np.float32).reshape(-1, 4)
+        assert len(intrinsics) == nimages
+        hold = np.ascontiguousarray(hold, np.int32).reshape(-1)
+        if cam_out is None:
+            cam_out = self.zeros(48 * max(nimages, 1))
+        if points_out is None:
+            points_out = self.zeros(16 * max(max_tracks, 1))
+        if cam_obs is None:
+            cam_obs = self.zeros(4 * max(nimages, 1))
+        if cam_status is None:
+            cam_status = self.zeros(4 * max(nimages, 1))
+        if cam_rms is None:
+            cam_rms = self.zeros(8 * max(nimages, 1))
+        if point_obs is None:
+            point_obs = self.zeros(4 * max(max_tracks, 1))
+        if history is None:
+            history = self.zeros(16 * max(int(num_loops), 1))
+        if cost is None:
+            cost = self.zeros(8)
+        if summary is None:
+            summary = self.zeros(4 * 8)
+        check(lib().misift_adjust_bundle_radial_batch(
+            self.h, max_tracks, max_obs, _dptr(track_offsets), _dptr(obs), _dptr(export_summary), _dptr(points),
+            _dptr(point_status), nimages, _dptr(cam), _dptr(cam_pair), intrinsics.ctypes.data, len(hold),
+            hold.ctypes.data if len(hold) else None, int(min_views), int(min_obs), int(num_loops), int(cg_iters),
+            float(max_error), float(lambda0), int(orthonormalise), int(loss), float(loss_scale), int(ngroups),
+            group.ctypes.data if len(group) else None, radial.ctypes.data if radial is not None and len(radial) else None,
+            k0.ctypes.data if k0 is not None and len(k0) else None, _dptr(cam_out), _dptr(points_out), _dptr(cam_obs),
+            _dptr(cam_status), _dptr(cam_rms), _dptr(point_obs), _dptr(history), _dptr(cost),
+            _dptr(obs_weight) if obs_weight is not None else None, _dptr(summary), _dptr(intrinsics_out), _dptr(focal),
+            _dptr(radial_out)), "misift_adjust_bundle_radial_batch")
+        return (cam_out, points_out, cam_obs, cam_status, cam_rms, point_obs, history, cost, obs_weight, summary,
+                intrinsics_out, focal, radial_out)
+
+    def undistort_obs_batch(self, max_obs, obs, export_summary, nimages, intrinsics, group, radial, ngroups=None,
+                            obs_out=None):
+        """misift_undistort_obs_batch: the observation list under the radial model with the coefficients of `radial`
+        (the device buffer adjust_bundle_radial_batch wrote).  intrinsics are the given ones (host); obs_out may be obs
+        itself and is allocated here when not passed; returns it.  Enqueued on the context stream."""
+        group = np.ascontiguousarray(group, np.int32).reshape(-1)
+        if ngroups is None:
+            ngroups = int(group.max()) + 1 if len(group) else 0
+        assert ngroups == 0 or len(group) == nimages
+        intrinsics = np.ascontiguousarray(intrinsics, np.float32).reshape(-1, 4)
+        assert len(intrinsics) == nimages
+        if obs_out is None:
+            obs_out = self.zeros(16 * max(max_obs, 1))
+        check(lib().misift_undistort_obs_batch(
+            self.h, max_obs, _dptr(obs), _dptr(export_summary), nimages, intrinsics.ctypes.data, int(ngroups),
+            group.ctypes.data if len(group) else None, _dptr(radial) if radial is not None else None, _dptr(obs_out)),
+            "misift_undistort_obs_batch")
+        return obs_out
 
     def filter_tracks_batch(self, max_tracks, max_obs, track_offsets, obs, export_summary, points, point_status,
                             nimages, cam, cam_pair, intrinsics, max_error=np.inf, max_cos=np.inf, min_angle_deg=None,

@@ -9,7 +9,11 @@
 // template argument of the two, so the plain call compiles to what it was.  misift_adjust_bundle_focal_batch adds one
 // focal scale per camera group: FOCAL is a template argument (or a function of its own, *_focal) of every phase that
 // reads the scale, the focal Jacobian of a slot lives in an array of its own beside the 20 values, and the groups'
-// scalars are carried by the scalar workgroup beside the images' 6-vectors.
+// scalars are carried by the scalar workgroup beside the images' 6-vectors.  misift_adjust_bundle_radial_batch adds one
+// radial coefficient per group, applied to the observation (bundle_radial_apply, which misift_undistort_obs_batch shares):
+// RADIAL is a second template argument (or a function of its own, *_radial) of the phases that read an observation or
+// carry a scalar; the column of k_g lives in an array of its own beside the focal one.  Every instance without RADIAL
+// compiles to what it was.
 //
 // The rules of refine_core.hpp hold: fp32 with every operation rounded, only + - * / sqrtf and fabsf, no fmaf, and the
 // build's -ffp-contract=off.  A per-track sum is taken by one work item in ascending slot.  A per-image or cross-image
@@ -33,6 +37,10 @@ constexpr int BUNDLE_MAX_GROUPS = 8;           // MISIFT_MAX_FOCAL_GROUPS
 constexpr int BUNDLE_IMAGE_FOCAL = 9;          // per image with a group: U_cf (6), Uff, gf, the sum of wf . y_t
 constexpr int BUNDLE_NORMAL_FOCAL = BUNDLE_NORMAL + BUNDLE_IMAGE_FOCAL;
 enum { BUNDLE_FOCAL_REFINED = 0, BUNDLE_FOCAL_NO_MEMBER = 1, BUNDLE_FOCAL_NOT_REFINED = 2 };   // MISIFT_FOCAL_*
+constexpr int BUNDLE_IMAGE_RADIAL = 10;        // per image of a radial group: U_ck (6), Ukk, gk, the sum of wk . y_t, Ufk
+constexpr int BUNDLE_NORMAL_RADIAL = BUNDLE_NORMAL_FOCAL + BUNDLE_IMAGE_RADIAL;
+enum { BUNDLE_RADIAL_REFINED = 0, BUNDLE_RADIAL_NO_MEMBER = 1, BUNDLE_RADIAL_NOT_REFINED = 2,
+       BUNDLE_RADIAL_HELD = 3 };               // MISIFT_RADIAL_*
 
 struct BundleData {
   TrackScene s;                                // the call's inputs
@@ -73,6 +81,17 @@ struct BundleData {
   float *ifv;                                  // nimages x 2 per CG iteration: U_cf . p_i, the sum of wf . q_t
   float *intrinsics_out;                       // nimages x 4
   int *focal_out;                              // ngroups x 3 words: s_g, the members, the status
+  // misift_adjust_bundle_radial_batch only (the RADIAL instances): one radial coefficient per camera group
+  const int *rad;                              // BUNDLE_MAX_GROUPS flags: k_g is an unknown (0 from ngroups on)
+  const float *k0;                             // BUNDLE_MAX_GROUPS: k_g at the start (0 from ngroups on)
+  float *ks;                                   // 2 x BUNDLE_MAX_GROUPS: k_g in the two state buffers
+  float *kvec;                                 // 5 x BUNDLE_MAX_GROUPS: x, r, z, p, y of the coefficients
+  float *ksc;                                  // 3 x BUNDLE_MAX_GROUPS: l1 * U_kk, then S_kk, then U_fk
+  float *rlin;                                 // max_obs x 2: Juk, Jvk of a slot
+  float *tkd;                                  // max_tracks x BUNDLE_MAX_GROUPS: wk_gt . SOLVE(V'_t, wk_gt)
+  float *iuk;                                  // nimages x BUNDLE_IMAGE_RADIAL: U_ck (6), then the sums of Ukk, gk, wk . y_t, Ufk
+  float *ikv;                                  // nimages x 2 per CG iteration: U_ck . p_i, the sum of wk . q_t
+  int *radial_out;                             // ngroups x 3 words: k_g, the members, the status
 };
 
 FUND_HD void bundle_raise(int *flag)
@@ -106,6 +125,32 @@ FUND_HD void bundle_load_cam(const float *src, float (&c)[12])
   for (int j = 0; j < 12; j++) c[j] = src[j];
 }
 
+// The radial model of include/misift.h, on an observation: every operation rounded on its own.  k = the given fx fy cx cy
+FUND_HD void bundle_radial_apply(const float *k, float coef, float &x, float &y, float &qu, float &qv)
+{
+  const float dx = x - k[2], dy = y - k[3];
+  const float nx = dx / k[0], ny = dy / k[1];
+  const float rho2 = nx * nx + ny * ny;
+  const float e = coef * rho2;
+  qu = dx * rho2;
+  qv = dy * rho2;
+  x = x + dx * e;
+  y = y + dy * e;
+}
+// RADIAL: the observation of slot o in image k as it enters under the coefficients `ks` (one per group); otherwise, and
+// for an image without a group, as given
+template <bool RADIAL>
+FUND_HD void bundle_observe(const BundleData &D, const float *ks, int k, const TrackObs &ob, float &x, float &y)
+{
+  x = ob.xpos;
+  y = ob.ypos;
+  if (!RADIAL) return;
+  const int g = D.grp[k];
+  if (g < 0) return;
+  float qu, qv;
+  bundle_radial_apply(D.s.intrinsics + 4 * (size_t)k, ks[g], x, y, qu, qv);
+}
+
 // ---- the sets, decided once
 
 // an image's state and the camera both state buffers start with
@@ -135,7 +180,8 @@ FUND_HD void bundle_image_init(const BundleData &D, int i)
   }
 }
 
-// slot o < O: a candidate stays in `key` iff it is a pre-member
+// slot o < O: a candidate stays in `key` iff it is a pre-member (RADIAL: of the observation under k0)
+template <bool RADIAL = false>
 FUND_HD void bundle_slot_premember(const BundleData &D, int o)
 {
   const int k = D.key[o];
@@ -147,7 +193,9 @@ FUND_HD void bundle_slot_premember(const BundleData &D, int o)
     const float *P = D.s.points + 4 * (size_t)D.owner[o];
     const float X[3] = {P[0], P[1], P[2]};
     const TrackObs ob = track_obs_load(D.s.obs + o);
-    in = refine_member(c, D.s.intrinsics + 4 * (size_t)k, X, ob.xpos, ob.ypos, D.thresh2);
+    float x, y;
+    bundle_observe<RADIAL>(D, D.k0, k, ob, x, y);
+    in = refine_member(c, D.s.intrinsics + 4 * (size_t)k, X, x, y, D.thresh2);
   }
   if (!in) D.key[o] = -1;
 }
@@ -255,7 +303,7 @@ FUND_HD BundleLoss bundle_loss(int loss, float c, float c2, float s)
 }
 
 // a member's squared residual, or its rho, under state buffer b (trial: the buffer the state is not in); one not in front raises BAD
-template <bool ROBUST, bool FOCAL = false>
+template <bool ROBUST, bool FOCAL = false, bool RADIAL = false>
 FUND_HD void bundle_eval_slot(const BundleData &D, int o, bool trial)
 {
   const int k = D.key[o];
@@ -268,8 +316,9 @@ FUND_HD void bundle_eval_slot(const BundleData &D, int o, bool trial)
   const float X[3] = {P[0], P[1], P[2]};
   const TrackObs ob = track_obs_load(D.s.obs + o);
   RefineView v;
-  float e = 0.0f;
-  if (refine_view(c, bundle_intrinsics<FOCAL>(D, b, k, kk), X, ob.xpos, ob.ypos, v)) {
+  float e = 0.0f, x, y;
+  bundle_observe<RADIAL>(D, D.ks + b * BUNDLE_MAX_GROUPS, k, ob, x, y);
+  if (refine_view(c, bundle_intrinsics<FOCAL>(D, b, k, kk), X, x, y, v)) {
     e = v.ru * v.ru + v.rv * v.rv;
     if (ROBUST) e = bundle_loss(D.loss, D.loss_scale, D.loss_scale2, e).rho;
   } else {
@@ -329,12 +378,14 @@ FUND_HD void bundle_scalar_init(const BundleData &D, Sum &S, bool lead)
 }
 
 // FOCAL, in the scalar workgroup before any state is evaluated: s_g = 1 in both buffers, the members of every group
-template <class Sum>
+// RADIAL: and k_g = k0_g in both buffers
+template <bool RADIAL = false, class Sum>
 FUND_HD void bundle_focal_init(const BundleData &D, Sum &S, int lane, int lanes)
 {
   for (int g = lane; g < BUNDLE_MAX_GROUPS; g += lanes) {
     D.fcount[g] = 0;
     D.fs[g] = D.fs[BUNDLE_MAX_GROUPS + g] = 1.0f;
+    if (RADIAL) D.ks[g] = D.ks[BUNDLE_MAX_GROUPS + g] = D.k0[g];
   }
   S.fence();
   for (int i = lane; i < D.s.nimages; i += lanes) {
@@ -393,11 +444,21 @@ FUND_HD void bundle_track_normal(const BundleData &D, int t)
 // FOCAL: the groups' vector `which`; a group is live iff an image of it has a member
 FUND_HD float *bundle_fvec(const BundleData &D, int which) { return D.fvec + which * BUNDLE_MAX_GROUPS; }
 FUND_HD bool bundle_group_live(const BundleData &D, int g) { return D.fcount[g] > 0; }
+// RADIAL: a coefficient is live iff it is an unknown and its group is live; wk[q] = Juk*Pu[q] + Jvk*Pv[q] of slot o
+FUND_HD bool bundle_radial_live(const BundleData &D, int g) { return D.rad[g] != 0 && D.fcount[g] > 0; }
+FUND_HD float bundle_wk(const float *l, const float *f, int q) { return f[0] * l[12 + q] + f[1] * l[15 + q]; }
+FUND_HD float bundle_wk3(const float *l, const float *f, const float *v)
+{
+  return (bundle_wk(l, f, 0) * v[0] + bundle_wk(l, f, 1) * v[1]) + bundle_wk(l, f, 2) * v[2];
+}
 
 // FOCAL: bundle_track_normal with the focal Jacobian of every member beside the 20 values (Juf = fx*a, Jvf = fy*b with
 // the given fx, fy, times sw under a loss), and per group w_gt . SOLVE(V', w_gt) for the group's Schur scalar.  A function
-// of its own, so that the plain one compiles to what it was
-template <bool ROBUST>
+// of its own, so that the plain one compiles to what it was.  RADIAL: the observation enters as (x', y') under k_g of the
+// state; a member of a group whose k_g is an unknown has the column Juk = -(dx*rho2), Jvk = -(dy*rho2) (ru = x' - u
+// grows by dx*rho2 per unit of k, so the column has the sign of the others: r falls by J times the step), times sw
+// under a loss, any other member zeros; per group wk_gt . V'^-1 wk_gt from one more walk that reuses the registers of w_gt
+template <bool ROBUST, bool RADIAL = false>
 FUND_HD void bundle_track_normal_focal(const BundleData &D, int t)
 {
   if (!bundle_active(D, t)) return;
@@ -415,13 +476,25 @@ FUND_HD void bundle_track_normal_focal(const BundleData &D, int t)
     bundle_load_cam(D.cams + 12 * ((size_t)b * D.s.nimages + k), c);
     const TrackObs ob = track_obs_load(D.s.obs + o);
     const float *kp = bundle_intrinsics<true>(D, b, k, kk);
-    if (!bundle_linearise(c, kp, X, ob.xpos, ob.ypos, l)) {
+    float x = ob.xpos, y = ob.ypos, rk[2] = {0.0f, 0.0f};
+    if (RADIAL) {
+      const int g = D.grp[k];
+      if (g >= 0) {
+        float qu, qv;
+        bundle_radial_apply(D.s.intrinsics + 4 * (size_t)k, D.ks[b * BUNDLE_MAX_GROUPS + g], x, y, qu, qv);
+        if (D.rad[g]) {
+          rk[0] = -qu;
+          rk[1] = -qv;
+        }
+      }
+    }
+    if (!bundle_linearise(c, kp, X, x, y, l)) {
       bundle_raise(&D.ctl[BUNDLE_FAIL]);       // the state has every member in front: not reached
 #pragma unroll
       for (int j = 0; j < BUNDLE_LIN; j++) l[j] = 0.0f;
     }
     RefineView view;                           // a, b of the same view once more: the same bits
-    const bool front = refine_view(c, kp, X, ob.xpos, ob.ypos, view);
+    const bool front = refine_view(c, kp, X, x, y, view);
     f[0] = front ? D.s.intrinsics[4 * (size_t)k] * view.a : 0.0f;
     f[1] = front ? D.s.intrinsics[4 * (size_t)k + 1] * view.b : 0.0f;
     if (ROBUST) {
@@ -430,12 +503,20 @@ FUND_HD void bundle_track_normal_focal(const BundleData &D, int t)
       for (int j = 0; j < BUNDLE_LIN; j++) l[j] = sw * l[j];
       f[0] = sw * f[0];
       f[1] = sw * f[1];
+      if (RADIAL) {
+        rk[0] = sw * rk[0];
+        rk[1] = sw * rk[1];
+      }
     }
     float *dst = D.lin + (size_t)BUNDLE_LIN * o;
 #pragma unroll
     for (int j = 0; j < BUNDLE_LIN; j++) dst[j] = l[j];
     D.flin[2 * (size_t)o] = f[0];
     D.flin[2 * (size_t)o + 1] = f[1];
+    if (RADIAL) {
+      D.rlin[2 * (size_t)o] = rk[0];
+      D.rlin[2 * (size_t)o + 1] = rk[1];
+    }
     tri_accumulate(N, l[12], l[13], l[14], l[18]);
     tri_accumulate(N, l[15], l[16], l[17], l[19]);
   }
@@ -471,6 +552,30 @@ FUND_HD void bundle_track_normal_focal(const BundleData &D, int t)
     tri_solve(N, x);                           // a failed solve gives zeros, and has failed the step above
     D.tfd[(size_t)BUNDLE_MAX_GROUPS * t + g] = (w[g][0] * x[0] + w[g][1] * x[1]) + w[g][2] * x[2];
   }
+  if (!RADIAL) return;
+  // wk_gt in the same registers: the members of the groups whose k_g is an unknown
+#pragma unroll
+  for (int g = 0; g < BUNDLE_MAX_GROUPS; g++) w[g][0] = w[g][1] = w[g][2] = 0.0f;
+  for (int o = off; o < end; o++) {
+    const int k = D.key[o];
+    if (D.owner[o] != t || k < 0) continue;
+    const int mine = D.grp[k];
+    if (mine < 0 || !D.rad[mine]) continue;
+    const float *l = D.lin + (size_t)BUNDLE_LIN * o, *f = D.rlin + 2 * (size_t)o;
+    const float wk[3] = {bundle_wk(l, f, 0), bundle_wk(l, f, 1), bundle_wk(l, f, 2)};
+#pragma unroll
+    for (int g = 0; g < BUNDLE_MAX_GROUPS; g++)
+#pragma unroll
+      for (int j = 0; j < 3; j++) w[g][j] = mine == g ? w[g][j] + wk[j] : w[g][j];
+  }
+#pragma unroll
+  for (int g = 0; g < BUNDLE_MAX_GROUPS; g++) {
+    if (g >= D.ngroups || !bundle_radial_live(D, g)) continue;
+    float x[3];
+    N.g0 = w[g][0]; N.g1 = w[g][1]; N.g2 = w[g][2];
+    tri_solve(N, x);
+    D.tkd[(size_t)BUNDLE_MAX_GROUPS * t + g] = (w[g][0] * x[0] + w[g][1] * x[1]) + w[g][2] * x[2];
+  }
 }
 
 // V'^-1 rhs for track t; a failed solve gives zeros
@@ -485,7 +590,8 @@ FUND_HD void bundle_track_solve(const BundleData &D, int t, const float (&rhs)[3
 
 // sum over the track's members in free images, in ascending slot, of W^T v_image; v = the 6-vectors `which`
 // FOCAL: a member in an image of group g then adds wf * v_g, whatever the image's status
-template <bool FOCAL = false>
+// RADIAL: and then wk * v_k when k_g is an unknown
+template <bool FOCAL = false, bool RADIAL = false>
 FUND_HD void bundle_track_gather(const BundleData &D, int t, int which, float (&s)[3])
 {
   s[0] = s[1] = s[2] = 0.0f;
@@ -506,6 +612,12 @@ FUND_HD void bundle_track_gather(const BundleData &D, int t, int which, float (&
       const float vg = D.fvec[which * BUNDLE_MAX_GROUPS + g];
 #pragma unroll
       for (int q = 0; q < 3; q++) s[q] = s[q] + bundle_wf(l, f, q) * vg;
+      if (RADIAL && D.rad[g]) {
+        const float *rk = D.rlin + 2 * (size_t)o;
+        const float vk = D.kvec[which * BUNDLE_MAX_GROUPS + g];
+#pragma unroll
+        for (int q = 0; q < 3; q++) s[q] = s[q] + bundle_wk(l, rk, q) * vk;
+      }
     }
   }
 }
@@ -546,15 +658,20 @@ struct BundleFocalTerm {
     focal(list[p], x);
     return true;
   }
-  FUND_HD bool operator()(int p, float (&x)[BUNDLE_NORMAL_FOCAL]) const
+  // the 42 values of a free image with a group into x[0 .. 41]
+  FUND_HD void all(int p, float *x) const
   {
     const int o = list[p];
     BundleNormalTerm base{D, list};
-    base(p, reinterpret_cast<float(&)[BUNDLE_NORMAL]>(x));
+    base(p, *reinterpret_cast<float(*)[BUNDLE_NORMAL]>(x));
     const float *l = D.lin + (size_t)BUNDLE_LIN * o, *f = D.flin + 2 * (size_t)o;
 #pragma unroll
     for (int r = 0; r < 6; r++) x[BUNDLE_NORMAL + r] = l[r] * f[0] + l[6 + r] * f[1];
     focal(o, x + BUNDLE_NORMAL + 6);
+  }
+  FUND_HD bool operator()(int p, float (&x)[BUNDLE_NORMAL_FOCAL]) const
+  {
+    all(p, x);
     return true;
   }
 };
@@ -613,6 +730,67 @@ FUND_HD void bundle_image_normal_focal(const BundleData &D, Sum &S, int i, bool 
   bundle_image_normal_finish(D, i, s);
 }
 
+// RADIAL: a usable image of a group whose k_g is an unknown takes four more sums (Ukk, gk, wk . y_t, Ufk), a free one
+// among them the six of U_ck: 52 sums.  Any other image is the focal call's
+struct BundleRadialTerm {
+  const BundleData &D;
+  const int *list;
+  FUND_HD void radial(int o, float *x) const
+  {
+    const float *l = D.lin + (size_t)BUNDLE_LIN * o, *f = D.flin + 2 * (size_t)o, *k = D.rlin + 2 * (size_t)o;
+    const float *y = D.tq + 3 * (size_t)D.owner[o];
+    x[0] = k[0] * k[0] + k[1] * k[1];
+    x[1] = k[0] * l[18] + k[1] * l[19];
+    x[2] = bundle_wk3(l, k, y);
+    x[3] = f[0] * k[0] + f[1] * k[1];
+  }
+  FUND_HD bool operator()(int p, float (&x)[7]) const
+  {
+    BundleFocalTerm base{D, list};
+    base.focal(list[p], x);
+    radial(list[p], x + 3);
+    return true;
+  }
+  FUND_HD bool operator()(int p, float (&x)[BUNDLE_NORMAL_RADIAL]) const
+  {
+    const int o = list[p];
+    BundleFocalTerm base{D, list};
+    base.all(p, x);
+    const float *l = D.lin + (size_t)BUNDLE_LIN * o, *k = D.rlin + 2 * (size_t)o;
+#pragma unroll
+    for (int r = 0; r < 6; r++) x[BUNDLE_NORMAL_FOCAL + r] = l[r] * k[0] + l[6 + r] * k[1];
+    radial(o, x + BUNDLE_NORMAL_FOCAL + 6);
+    return true;
+  }
+};
+template <class Sum>
+FUND_HD void bundle_image_normal_radial(const BundleData &D, Sum &S, int i, bool lead)
+{
+  const int g = D.grp[i];
+  if (g < 0 || !D.rad[g]) return bundle_image_normal_focal(D, S, i, lead);
+  if (D.istate[i] == BUNDLE_NO_CAMERA) return;
+  BundleRadialTerm term{D, D.list + D.istart[i]};
+  float *dst = D.iuf + (size_t)BUNDLE_IMAGE_FOCAL * i, *dk = D.iuk + (size_t)BUNDLE_IMAGE_RADIAL * i;
+  if (D.istate[i] != BUNDLE_ADJUSTED) {
+    float s[7];
+    S.template sum<7>(D.icount[i], term, s);
+    if (!lead) return;
+#pragma unroll
+    for (int r = 0; r < 6; r++) dst[r] = dk[r] = 0.0f;
+    dst[6] = s[0]; dst[7] = s[1]; dst[8] = s[2];
+    dk[6] = s[3]; dk[7] = s[4]; dk[8] = s[5]; dk[9] = s[6];
+    return;
+  }
+  float s[BUNDLE_NORMAL_RADIAL];
+  S.template sum<BUNDLE_NORMAL_RADIAL>(D.icount[i], term, s);
+  if (!lead) return;
+#pragma unroll
+  for (int r = 0; r < BUNDLE_IMAGE_FOCAL; r++) dst[r] = s[BUNDLE_NORMAL + r];
+#pragma unroll
+  for (int r = 0; r < BUNDLE_IMAGE_RADIAL; r++) dk[r] = s[BUNDLE_NORMAL_FOCAL + r];
+  bundle_image_normal_finish(D, i, s);
+}
+
 // M^-1 v for image i (the LDL^T of U'); a failed solve gives zeros
 FUND_HD void bundle_precondition(const BundleData &D, int i, const float *v, float *z)
 {
@@ -659,18 +837,55 @@ struct BundleGroupSchurTerm {
     return true;
   }
 };
-template <bool FOCAL>
+// RADIAL: the same three for the coefficient of group g, and its share of a dot product behind the focal scalars'
+struct BundleGroupRadialTerm {
+  const BundleData &D;
+  int g;
+  FUND_HD bool operator()(int i, float (&x)[4]) const
+  {
+    if (D.grp[i] != g || D.istate[i] == BUNDLE_NO_CAMERA) return false;
+    const float *src = D.iuk + (size_t)BUNDLE_IMAGE_RADIAL * i + 6;
+    x[0] = src[0]; x[1] = src[1]; x[2] = src[2]; x[3] = src[3];
+    return true;
+  }
+};
+struct BundleGroupCgRadialTerm {
+  const BundleData &D;
+  int g;
+  FUND_HD bool operator()(int i, float (&x)[2]) const
+  {
+    if (D.grp[i] != g || D.istate[i] == BUNDLE_NO_CAMERA) return false;
+    x[0] = D.ikv[2 * (size_t)i]; x[1] = D.ikv[2 * (size_t)i + 1];
+    return true;
+  }
+};
+struct BundleGroupSchurRadialTerm {
+  const BundleData &D;
+  int g;
+  FUND_HD bool operator()(int t, float (&x)[1]) const
+  {
+    if (!(D.tcount[t] >= D.min_views)) return false;
+    x[0] = D.tkd[(size_t)BUNDLE_MAX_GROUPS * t + g];
+    return true;
+  }
+};
+FUND_HD float *bundle_kvec(const BundleData &D, int which) { return D.kvec + which * BUNDLE_MAX_GROUPS; }
+template <bool FOCAL, bool RADIAL = false>
 FUND_HD float bundle_dot_groups(const BundleData &D, float acc, int a, int b)
 {
   if (FOCAL)
     for (int g = 0; g < D.ngroups; g++)
       if (bundle_group_live(D, g)) acc = acc + bundle_fvec(D, a)[g] * bundle_fvec(D, b)[g];
+  if (RADIAL)
+    for (int g = 0; g < D.ngroups; g++)
+      if (bundle_radial_live(D, g)) acc = acc + bundle_kvec(D, a)[g] * bundle_kvec(D, b)[g];
   return acc;
 }
 
 // step 4, the start of PCG in the scalar workgroup; this thread takes the images lane, lane + lanes, ...
 // FOCAL: per live group U_gg, g_g, the Schur scalar S_gg (not finite and > 0: the step fails), x, r, z = r / S_gg, p
-template <bool FOCAL = false, class Sum>
+// RADIAL: then per group with a live coefficient U_kk, g_k, U_fk and the Schur scalar S_kk in the same way
+template <bool FOCAL = false, bool RADIAL = false, class Sum>
 FUND_HD void bundle_cg_start(const BundleData &D, Sum &S, int lane, int lanes, bool lead)
 {
   bool fail = D.ctl[BUNDLE_FAIL] != 0;
@@ -703,6 +918,24 @@ FUND_HD void bundle_cg_start(const BundleData &D, Sum &S, int lane, int lanes, b
       bundle_fvec(D, BUNDLE_R)[g] = bg;
       bundle_fvec(D, BUNDLE_Z)[g] = bundle_fvec(D, BUNDLE_P)[g] = bg / sg;
     }
+    if (RADIAL)
+      for (int g = 0; g < D.ngroups; g++) {
+        if (!bundle_radial_live(D, g)) continue;
+        BundleGroupRadialTerm nterm{D, g};
+        BundleGroupSchurRadialTerm sterm{D, g};
+        float u[4], d[1];
+        S.template sum<4>(D.s.nimages, nterm, u);
+        S.template sum<1>(T, sterm, d);
+        const float ul = u[0] * lam1, sk = ul - d[0], bk = u[1] - u[2];
+        if (!(fundamental_finite(sk) && sk > 0.0f)) fail = true;
+        if (!lead) continue;
+        D.ksc[g] = ul;
+        D.ksc[BUNDLE_MAX_GROUPS + g] = sk;
+        D.ksc[2 * BUNDLE_MAX_GROUPS + g] = u[3];
+        bundle_kvec(D, BUNDLE_X)[g] = 0.0f;
+        bundle_kvec(D, BUNDLE_R)[g] = bk;
+        bundle_kvec(D, BUNDLE_Z)[g] = bundle_kvec(D, BUNDLE_P)[g] = bk / sk;
+      }
     if (fail && lead) bundle_raise(&D.ctl[BUNDLE_FAIL]);
   }
   float rho[1] = {0.0f};
@@ -710,7 +943,7 @@ FUND_HD void bundle_cg_start(const BundleData &D, Sum &S, int lane, int lanes, b
     S.fence();
     BundleDotTerm term{D.istate, D.ivec + 6 * (size_t)BUNDLE_R * D.s.nimages, D.ivec + 6 * (size_t)BUNDLE_Z * D.s.nimages};
     S.template sum<1>(D.s.nimages, term, rho);
-    rho[0] = bundle_dot_groups<FOCAL>(D, rho[0], BUNDLE_R, BUNDLE_Z);
+    rho[0] = bundle_dot_groups<FOCAL, RADIAL>(D, rho[0], BUNDLE_R, BUNDLE_Z);
   }
   if (!lead) return;
   D.fctl[BUNDLE_RHO] = rho[0];
@@ -719,12 +952,12 @@ FUND_HD void bundle_cg_start(const BundleData &D, Sum &S, int lane, int lanes, b
 }
 
 // a CG iteration, per active track: q_t = V'^-1 sum W^T p_image
-template <bool FOCAL = false>
+template <bool FOCAL = false, bool RADIAL = false>
 FUND_HD void bundle_cg_track(const BundleData &D, int t)
 {
   if (!D.ctl[BUNDLE_ALIVE] || !bundle_active(D, t)) return;
   float s[3], q[3];
-  bundle_track_gather<FOCAL>(D, t, BUNDLE_P, s);
+  bundle_track_gather<FOCAL, RADIAL>(D, t, BUNDLE_P, s);
   bundle_track_solve(D, t, s, q);
   float *dst = D.tq + 3 * (size_t)t;
   dst[0] = q[0]; dst[1] = q[1]; dst[2] = q[2];
@@ -823,9 +1056,76 @@ FUND_HD void bundle_cg_image_focal(const BundleData &D, Sum &S, int i, bool lead
   dst[1] = s[6];
 }
 
+// RADIAL: a usable image of a group whose k_g is an unknown sums wk . q_t too; a free one has
+// y_i[r] = ((U'[r] . p_i + U_cf[r]*p_g) + U_ck[r]*p_k) - ...  Any other image is the focal call's
+struct BundleWqRadialTerm {
+  const BundleData &D;
+  const int *list;
+  FUND_HD bool operator()(int p, float (&x)[2]) const
+  {
+    const int o = list[p];
+    const float *l = D.lin + (size_t)BUNDLE_LIN * o, *q = D.tq + 3 * (size_t)D.owner[o];
+    x[0] = bundle_wf3(l, D.flin + 2 * (size_t)o, q);
+    x[1] = bundle_wk3(l, D.rlin + 2 * (size_t)o, q);
+    return true;
+  }
+  FUND_HD bool operator()(int p, float (&x)[8]) const
+  {
+    const int o = list[p];
+    const float *l = D.lin + (size_t)BUNDLE_LIN * o, *q = D.tq + 3 * (size_t)D.owner[o];
+#pragma unroll
+    for (int r = 0; r < 6; r++) x[r] = bundle_w3(l, r, q);
+    x[6] = bundle_wf3(l, D.flin + 2 * (size_t)o, q);
+    x[7] = bundle_wk3(l, D.rlin + 2 * (size_t)o, q);
+    return true;
+  }
+};
+template <class Sum>
+FUND_HD void bundle_cg_image_radial(const BundleData &D, Sum &S, int i, bool lead)
+{
+  const int g = D.grp[i];
+  if (g < 0 || !D.rad[g]) return bundle_cg_image_focal(D, S, i, lead);
+  if (!D.ctl[BUNDLE_ALIVE] || D.istate[i] == BUNDLE_NO_CAMERA) return;
+  BundleWqRadialTerm term{D, D.list + D.istart[i]};
+  float *dst = D.ifv + 2 * (size_t)i, *dk = D.ikv + 2 * (size_t)i;
+  if (D.istate[i] != BUNDLE_ADJUSTED) {
+    float s[2];
+    S.template sum<2>(D.icount[i], term, s);
+    if (!lead) return;
+    dst[0] = dk[0] = 0.0f;
+    dst[1] = s[0];
+    dk[1] = s[1];
+    return;
+  }
+  float s[8];
+  S.template sum<8>(D.icount[i], term, s);
+  if (!lead) return;
+  const float *src = D.iu + (size_t)REFINE_SUMS * i, *p = bundle_vec(D, BUNDLE_P, i);
+  const float *ucf = D.iuf + (size_t)BUNDLE_IMAGE_FOCAL * i, *uck = D.iuk + (size_t)BUNDLE_IMAGE_RADIAL * i;
+  const float pg = bundle_fvec(D, BUNDLE_P)[g], pk = bundle_kvec(D, BUNDLE_P)[g];
+  float U[6][6];
+  int j = 1;
+#pragma unroll
+  for (int r = 0; r < 6; r++)
+#pragma unroll
+    for (int c = r; c < 6; c++) {
+      U[r][c] = U[c][r] = src[j];
+      j++;
+    }
+  float *y = bundle_vec(D, BUNDLE_Y, i);
+#pragma unroll
+  for (int r = 0; r < 6; r++) y[r] = ((bundle_dot6(U[r], p) + ucf[r] * pg) + uck[r] * pk) - s[r];
+  dst[0] = bundle_dot6(ucf, p);
+  dst[1] = s[6];
+  dk[0] = bundle_dot6(uck, p);
+  dk[1] = s[7];
+}
+
 // a CG iteration in the scalar workgroup: sigma, alpha, x, r, z, rho', beta, p
 // FOCAL: first y_g = (l1*U_gg * p_g + the cross-image sum of U_cf . p_i) - the cross-image sum of the sums of wf . q_t
-template <bool FOCAL = false, class Sum>
+// RADIAL: a group with a live coefficient has y_g = ((l1*U_gg * p_g + U_fk * p_k) + ...) - ..., and
+// y_k = ((l1*U_kk * p_k + U_fk * p_g) + the cross-image sum of U_ck . p_i) - the cross-image sum of the sums of wk . q_t
+template <bool FOCAL = false, bool RADIAL = false, class Sum>
 FUND_HD void bundle_cg_scalar(const BundleData &D, Sum &S, int lane, int lanes, bool lead)
 {
   if (!D.ctl[BUNDLE_ALIVE]) return;            // the same in every thread
@@ -837,14 +1137,24 @@ FUND_HD void bundle_cg_scalar(const BundleData &D, Sum &S, int lane, int lanes, 
       BundleGroupCgTerm term{D, g};
       float v[2];
       S.template sum<2>(D.s.nimages, term, v);
-      if (lead) bundle_fvec(D, BUNDLE_Y)[g] = (D.fsc[g] * bundle_fvec(D, BUNDLE_P)[g] + v[0]) - v[1];
+      float diag = D.fsc[g] * bundle_fvec(D, BUNDLE_P)[g];
+      if (RADIAL && bundle_radial_live(D, g)) {
+        BundleGroupCgRadialTerm kterm{D, g};
+        float w[2];
+        S.template sum<2>(D.s.nimages, kterm, w);
+        const float ufk = D.ksc[2 * BUNDLE_MAX_GROUPS + g], pk = bundle_kvec(D, BUNDLE_P)[g];
+        if (lead)
+          bundle_kvec(D, BUNDLE_Y)[g] = ((D.ksc[g] * pk + ufk * bundle_fvec(D, BUNDLE_P)[g]) + w[0]) - w[1];
+        diag = diag + ufk * pk;
+      }
+      if (lead) bundle_fvec(D, BUNDLE_Y)[g] = (diag + v[0]) - v[1];
     }
     S.fence();
   }
   BundleDotTerm sterm{D.istate, D.ivec + BUNDLE_P * n6, D.ivec + BUNDLE_Y * n6};
   float sigma[1], rho2[1];
   S.template sum<1>(D.s.nimages, sterm, sigma);
-  sigma[0] = bundle_dot_groups<FOCAL>(D, sigma[0], BUNDLE_P, BUNDLE_Y);
+  sigma[0] = bundle_dot_groups<FOCAL, RADIAL>(D, sigma[0], BUNDLE_P, BUNDLE_Y);
   if (!(fundamental_finite(sigma[0]) && sigma[0] > 0.0f)) {
     S.fence();                                 // every thread has read ALIVE
     if (lead) D.ctl[BUNDLE_ALIVE] = 0;
@@ -867,10 +1177,18 @@ FUND_HD void bundle_cg_scalar(const BundleData &D, Sum &S, int lane, int lanes, 
       r[0] = r[0] - alpha * bundle_fvec(D, BUNDLE_Y)[g];
       bundle_fvec(D, BUNDLE_Z)[g] = r[0] / D.fsc[BUNDLE_MAX_GROUPS + g];
     }
+  if (RADIAL)
+    for (int g = lane; g < D.ngroups; g += lanes) {
+      if (!bundle_radial_live(D, g)) continue;
+      float *x = bundle_kvec(D, BUNDLE_X) + g, *r = bundle_kvec(D, BUNDLE_R) + g;
+      x[0] = x[0] + alpha * bundle_kvec(D, BUNDLE_P)[g];
+      r[0] = r[0] - alpha * bundle_kvec(D, BUNDLE_Y)[g];
+      bundle_kvec(D, BUNDLE_Z)[g] = r[0] / D.ksc[BUNDLE_MAX_GROUPS + g];
+    }
   S.fence();
   BundleDotTerm rterm{D.istate, D.ivec + BUNDLE_R * n6, D.ivec + BUNDLE_Z * n6};
   S.template sum<1>(D.s.nimages, rterm, rho2);
-  rho2[0] = bundle_dot_groups<FOCAL>(D, rho2[0], BUNDLE_R, BUNDLE_Z);
+  rho2[0] = bundle_dot_groups<FOCAL, RADIAL>(D, rho2[0], BUNDLE_R, BUNDLE_Z);
   const bool on = fundamental_finite(rho2[0]);
   if (on) {
     const float beta = rho2[0] / rho;
@@ -878,6 +1196,10 @@ FUND_HD void bundle_cg_scalar(const BundleData &D, Sum &S, int lane, int lanes, 
       for (int g = lane; g < D.ngroups; g += lanes)
         if (bundle_group_live(D, g))
           bundle_fvec(D, BUNDLE_P)[g] = bundle_fvec(D, BUNDLE_Z)[g] + beta * bundle_fvec(D, BUNDLE_P)[g];
+    if (RADIAL)
+      for (int g = lane; g < D.ngroups; g += lanes)
+        if (bundle_radial_live(D, g))
+          bundle_kvec(D, BUNDLE_P)[g] = bundle_kvec(D, BUNDLE_Z)[g] + beta * bundle_kvec(D, BUNDLE_P)[g];
     for (int i = lane; i < D.s.nimages; i += lanes) {
       if (D.istate[i] != BUNDLE_ADJUSTED) continue;
       float *p = bundle_vec(D, BUNDLE_P, i);
@@ -893,13 +1215,13 @@ FUND_HD void bundle_cg_scalar(const BundleData &D, Sum &S, int lane, int lanes, 
 }
 
 // step 5 for an active track: delta_t = V'^-1 (gp - sum W^T x_image), the trial point
-template <bool FOCAL = false>
+template <bool FOCAL = false, bool RADIAL = false>
 FUND_HD void bundle_track_trial(const BundleData &D, int t)
 {
   if (D.ctl[BUNDLE_FAIL] || !bundle_active(D, t)) return;
   const int b = D.ctl[BUNDLE_CUR];
   float s[3], d[3];
-  bundle_track_gather<FOCAL>(D, t, BUNDLE_X, s);
+  bundle_track_gather<FOCAL, RADIAL>(D, t, BUNDLE_X, s);
   const float *v = D.tv + 9 * (size_t)t;
   const float rhs[3] = {v[6] - s[0], v[7] - s[1], v[8] - s[2]};
   bundle_track_solve(D, t, rhs, d);
@@ -941,6 +1263,18 @@ FUND_HD void bundle_focal_trial(const BundleData &D, int g)
   const float e = live ? s + bundle_fvec(D, BUNDLE_X)[g] : s;
   D.fs[(1 - b) * BUNDLE_MAX_GROUPS + g] = e;
   if (live && !(fundamental_finite(e) && e > 0.0f)) bundle_raise(&D.ctl[BUNDLE_BAD]);
+}
+
+// RADIAL, step 5 for group g < BUNDLE_MAX_GROUPS: the trial coefficient k_g + x_k; one that is not finite raises BAD
+FUND_HD void bundle_radial_trial(const BundleData &D, int g)
+{
+  if (D.ctl[BUNDLE_FAIL]) return;
+  const int b = D.ctl[BUNDLE_CUR];
+  const float k = D.ks[b * BUNDLE_MAX_GROUPS + g];
+  const bool live = g < D.ngroups && bundle_radial_live(D, g);
+  const float e = live ? k + bundle_kvec(D, BUNDLE_X)[g] : k;
+  D.ks[(1 - b) * BUNDLE_MAX_GROUPS + g] = e;
+  if (live && !fundamental_finite(e)) bundle_raise(&D.ctl[BUNDLE_BAD]);
 }
 
 // step 6 in the scalar workgroup
@@ -1033,7 +1367,7 @@ FUND_HD void bundle_track_out(const BundleData &D, int t)
 }
 
 // d_obs_weight for slot o < O: -1 for a slot that is no member, w of a member under the final state
-template <bool FOCAL = false>
+template <bool FOCAL = false, bool RADIAL = false>
 FUND_HD void bundle_weight_slot(const BundleData &D, int o)
 {
   const int k = D.key[o];
@@ -1046,7 +1380,9 @@ FUND_HD void bundle_weight_slot(const BundleData &D, int o)
     const float X[3] = {P[0], P[1], P[2]};
     const TrackObs ob = track_obs_load(D.s.obs + o);
     RefineView v;
-    if (refine_view(c, bundle_intrinsics<FOCAL>(D, b, k, kk), X, ob.xpos, ob.ypos, v))
+    float x, y;
+    bundle_observe<RADIAL>(D, D.ks + b * BUNDLE_MAX_GROUPS, k, ob, x, y);
+    if (refine_view(c, bundle_intrinsics<FOCAL>(D, b, k, kk), X, x, y, v))
       w = pose_one_nan(bundle_loss(D.loss, D.loss_scale, D.loss_scale2, v.ru * v.ru + v.rv * v.rv).w);
     else
       w = pose_one_nan(NAN);                   // the final state has every member in front: not reached
@@ -1084,10 +1420,38 @@ FUND_HD void bundle_focal_out(const BundleData &D, int g, bool refined)
   out[2] = bundle_focal_status(D, g, refined);
 }
 
+// d_radial of group g < ngroups.  `refined` as above; `radial`: the RADIAL instances ran, otherwise k_g is k0_g
+FUND_HD void bundle_radial_out(const BundleData &D, int g, bool refined, bool radial)
+{
+  const float k = radial ? D.ks[D.ctl[BUNDLE_CUR] * BUNDLE_MAX_GROUPS + g] : D.k0[g];
+  const int n = refined ? D.fcount[g] : 0;
+  int status = BUNDLE_RADIAL_HELD;
+  if (D.rad[g] && D.num_loops == 0) status = BUNDLE_RADIAL_NOT_REFINED;
+  else if (D.rad[g]) status = radial && n > 0 ? BUNDLE_RADIAL_REFINED : BUNDLE_RADIAL_NO_MEMBER;
+  int *out = D.radial_out + 3 * (size_t)g;
+  __builtin_memcpy(&out[0], &k, sizeof k);
+  out[1] = n;
+  out[2] = status;
+}
+
+// misift_undistort_obs_batch, slot o < O: frame and record copied, the position under the radial model with k_g of
+// d_radial when the frame is an image with a group, otherwise bit for bit
+FUND_HD TrackObs bundle_undistort_obs(TrackObs ob, int nimages, const float *intrinsics, const int *group,
+                                      const int *radial)
+{
+  if (ob.frame < 0 || ob.frame >= nimages) return ob;
+  const int g = group[ob.frame];
+  if (g < 0) return ob;
+  float k, qu, qv;
+  __builtin_memcpy(&k, &radial[3 * (size_t)g], sizeof k);
+  bundle_radial_apply(intrinsics + 4 * (size_t)ob.frame, k, ob.xpos, ob.ypos, qu, qv);
+  return ob;
+}
+
 // ---- the host's side: the Sum as a loop, the phases in the order of the launches
 
 struct BundleHostSum {
-  float p[BUNDLE_NORMAL_FOCAL * FUND_SLOTS];
+  float p[BUNDLE_NORMAL_RADIAL * FUND_SLOTS];
   void fence() {}
   template <int K, class V>
   void sum(int n, V &v, float (&out)[K])

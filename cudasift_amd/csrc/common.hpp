@@ -745,6 +745,22 @@ int launch_adjust_bundle_focal_batch(misift_ctx *ctx, const TrackScene &scene, c
                                      int *d_cam_status, float *d_cam_rms, int *d_point_obs, float *d_history,
                                      float *d_cost, float *d_obs_weight, int *d_summary, float *d_intrinsics_out,
                                      int *d_focal);
+// misift_adjust_bundle_radial_batch (kernels_bundle.hip).  h_radial, h_k0: the pinned copies of `radial` and `k0`, padded
+// with zeros to MISIFT_MAX_RADIAL_GROUPS; radial: an image has a group and some k_g is an unknown or starts off zero.
+// Without that the launches and the temp are those of launch_adjust_bundle_focal_batch; one launch more writes d_radial
+size_t adjust_bundle_radial_batch_tmp_bytes(int max_tracks, int max_obs, int nimages);
+int launch_adjust_bundle_radial_batch(misift_ctx *ctx, const TrackScene &scene, const int *h_held, int min_views,
+                                      int min_obs, int num_loops, int cg_iters, float thresh2, float lambda0,
+                                      int orthonormalise, int loss, float loss_scale, float loss_scale2, int ngroups,
+                                      const int *h_group, bool focal, const int *h_radial, const float *h_k0, bool radial,
+                                      float *d_cam_out, float *d_points_out, int *d_cam_obs, int *d_cam_status,
+                                      float *d_cam_rms, int *d_point_obs, float *d_history, float *d_cost,
+                                      float *d_obs_weight, int *d_summary, float *d_intrinsics_out, int *d_focal,
+                                      int *d_radial);
+// misift_undistort_obs_batch (kernels_bundle.hip): one launch, no temp.  h_intrinsics, h_group: the pinned copies
+int launch_undistort_obs_batch(misift_ctx *ctx, int max_obs, const TrackObs *d_obs, const int *d_export_summary,
+                               int nimages, const float *h_intrinsics, const int *h_group, const int *d_radial,
+                               TrackObs *d_obs_out);
 // misift_filter_tracks_batch (kernels_filter.hip): a copy, three memsets + six launches; temp from misift_ensure_tmp,
 // sized from max_tracks, max_obs and nimages only
 size_t filter_tracks_batch_tmp_bytes(int max_tracks, int max_obs, int nimages);

@@ -2,8 +2,8 @@
 // at once.  Each step eliminates the points (Schur complement), solves the reduced camera system matrix-free by a fixed
 // number of block-Jacobi preconditioned conjugate-gradient iterations, back-substitutes the points and is kept or turned
 // away on the device.  No reference counterpart.  The arithmetic is bundle_core.hpp: every kernel here is a few lines
-// that hand one work item to the function of its phase, the same function the host-only test hook at the end of this
-// file runs in a loop.
+// that hand one work item to the function of its phase, the same function the host-only test hook (bundle_host.hpp,
+// wrapped at the end of this file) runs in a loop.
 //
 // Three memsets (the owners, the control words, the summary) and 11 + num_loops * (8 + 3 * cg_iters) launches, whatever
 // the data.  A dispatch boundary is the only barrier between workgroups: nothing in here waits for another workgroup.
@@ -43,6 +43,21 @@
 //   bundle_cg_track/_image/_scalar_focal_kernel   the focal terms of the gather, of y_i, and y_g; 7 sums per image
 //   bundle_track_trial_focal_kernel, bundle_image_trial_focal_kernel   the trial point; the trial camera and scale
 // so 13 + num_loops * (8 + 3 * cg_iters) launches: the two more are the groups' members and the two new outputs.
+// misift_adjust_bundle_radial_batch adds one radial coefficient per camera group, applied to the observation.  With
+// nothing radial (no grouped image, or no unknown coefficient and every start zero) it is the focal call's sequence and
+// one launch more at the end (bundle_radial_out_kernel: d_radial).  Otherwise a RADIAL instance stands where the FOCAL
+// one stood, launch for launch:
+//   bundle_premember_radial_kernel, bundle_eval_kernel<.., true, true>, bundle_weight_out_radial_kernel
+//                                      the observation enters as (x', y') under k_g (the member test: under k0)
+//   bundle_radial_init_kernel          bundle_focal_init_kernel, and k_g = k0_g in both state buffers
+//   bundle_track_normal_radial_kernel  the column Juk, Jvk of every member beside Juf, Jvf; per group wk_gt . V'^-1 wk_gt,
+//                                      the wk_gt from a walk of their own in the registers of the w_gt (no scratch)
+//   bundle_image_normal_radial_kernel  52 sums (52 KiB of LDS): the 42, U_ck, Ukk, gk, wk . y_t, Ufk
+//   bundle_cg_start/_track/_image/_scalar_radial_kernel   S_kk and U_fk per group; the terms of k_g in the gather, in
+//                                      y_i, y_g and y_k; 8 sums per image
+//   bundle_track_trial_radial_kernel, bundle_image_trial_radial_kernel   the trial point; the trial camera, scale and k_g
+// so 14 + num_loops * (8 + 3 * cg_iters) launches.  misift_undistort_obs_batch is undistort_obs_kernel alone.
+// The host's side (the temp layout and the test hooks' body) is bundle_host.hpp.
 // Jc, Jp and r are written once per LM step and read by both views: recomputing them in each CG pass instead gives the
 // same bits and measured 10 to 13 % slower.
 #include <stdint.h>
@@ -51,6 +66,7 @@
 #include <vector>
 #include "common.hpp"
 #include "bundle_core.hpp"
+#include "bundle_host.hpp"
 #include "track_candidates.hpp"
 
 namespace {
@@ -148,11 +164,11 @@ __global__ __launch_bounds__(BUNDLE_THREADS) void bundle_gather_kernel(BundleDat
   }
 }
 
-template <bool ROBUST, bool FOCAL = false>
+template <bool ROBUST, bool FOCAL = false, bool RADIAL = false>
 __global__ __launch_bounds__(BUNDLE_THREADS) void bundle_eval_kernel(BundleData D, int trial)
 {
   const int o = blockIdx.x * BUNDLE_THREADS + threadIdx.x;
-  if (o < scene_O(D.s)) bundle_eval_slot<ROBUST, FOCAL>(D, o, trial != 0);
+  if (o < scene_O(D.s)) bundle_eval_slot<ROBUST, FOCAL, RADIAL>(D, o, trial != 0);
 }
 
 __global__ __launch_bounds__(BUNDLE_THREADS) void bundle_cost_kernel(BundleData D, int trial)
@@ -325,44 +341,103 @@ __global__ __launch_bounds__(BUNDLE_THREADS) void bundle_focal_out_kernel(Bundle
   if (i < D.ngroups) bundle_focal_out(D, i, refined != 0);
 }
 
-// the temp of the call laid out behind `base` (NULL: only the size is wanted); every array starts 16-byte aligned
-size_t bundle_layout(BundleData &D, char *base, bool focal = false)
+// ---- misift_adjust_bundle_radial_batch: the RADIAL instances of the phases that read an observation or carry a
+// scalar, beside the plain and the FOCAL ones, which hold no trace of the coefficient
+
+__global__ __launch_bounds__(BUNDLE_THREADS) void bundle_premember_radial_kernel(BundleData D)
 {
-  size_t at = 0;
-  auto take = [&](size_t bytes) {
-    char *p = base ? base + at : nullptr;
-    at += (bytes + 15) & ~(size_t)15;
-    return p;
-  };
-  const size_t mo = (size_t)D.s.max_obs, mt = (size_t)D.s.max_tracks, n = (size_t)D.s.nimages;
-  D.owner = reinterpret_cast<int *>(take(4 * mo));
-  D.key = reinterpret_cast<int *>(take(4 * mo));
-  D.list = reinterpret_cast<int *>(take(4 * mo));
-  D.istart = reinterpret_cast<int *>(take(4 * n));
-  D.icount = reinterpret_cast<int *>(take(4 * n));
-  D.istate = reinterpret_cast<int *>(take(4 * n));
-  D.tcount = reinterpret_cast<int *>(take(4 * mt));
-  D.ctl = reinterpret_cast<int *>(take(4 * BUNDLE_CTL));
-  D.fctl = reinterpret_cast<float *>(take(4 * BUNDLE_FCTL));
-  D.lin = reinterpret_cast<float *>(take(4 * BUNDLE_LIN * mo));
-  D.eterm = reinterpret_cast<float *>(take(4 * 2 * mo));
-  D.cams = reinterpret_cast<float *>(take(4 * 2 * 12 * n));
-  D.pts = reinterpret_cast<float *>(take(4 * 2 * 3 * mt));
-  D.tv = reinterpret_cast<float *>(take(4 * 9 * mt));
-  D.tq = reinterpret_cast<float *>(take(4 * 3 * mt));
-  D.iu = reinterpret_cast<float *>(take(4 * REFINE_SUMS * n));
-  D.ivec = reinterpret_cast<float *>(take(4 * 5 * 6 * n));
-  D.icost = reinterpret_cast<float *>(take(4 * 3 * n));
-  if (!focal) return at;
-  D.fcount = reinterpret_cast<int *>(take(4 * BUNDLE_MAX_GROUPS));
-  D.fs = reinterpret_cast<float *>(take(4 * 2 * BUNDLE_MAX_GROUPS));
-  D.fvec = reinterpret_cast<float *>(take(4 * 5 * BUNDLE_MAX_GROUPS));
-  D.fsc = reinterpret_cast<float *>(take(4 * 2 * BUNDLE_MAX_GROUPS));
-  D.flin = reinterpret_cast<float *>(take(4 * 2 * mo));
-  D.tfd = reinterpret_cast<float *>(take(4 * BUNDLE_MAX_GROUPS * mt));
-  D.iuf = reinterpret_cast<float *>(take(4 * BUNDLE_IMAGE_FOCAL * n));
-  D.ifv = reinterpret_cast<float *>(take(4 * 2 * n));
-  return at;
+  const int o = blockIdx.x * BUNDLE_THREADS + threadIdx.x;
+  if (o < scene_O(D.s)) bundle_slot_premember<true>(D, o);
+}
+
+__global__ __launch_bounds__(BUNDLE_THREADS) void bundle_radial_init_kernel(BundleData D)
+{
+  BundleBlockSum S{nullptr};
+  bundle_focal_init<true>(D, S, threadIdx.x, BUNDLE_THREADS);
+}
+
+template <bool ROBUST>
+__global__ __launch_bounds__(BUNDLE_THREADS) void bundle_track_normal_radial_kernel(BundleData D)
+{
+  const int t = blockIdx.x * BUNDLE_THREADS + threadIdx.x;
+  if (t < scene_T(D.s)) bundle_track_normal_focal<ROBUST, true>(D, t);
+}
+
+__global__ __launch_bounds__(BUNDLE_THREADS) void bundle_image_normal_radial_kernel(BundleData D)
+{
+  __shared__ float s_p[BUNDLE_NORMAL_RADIAL * FUND_SLOTS];
+  BundleBlockSum S{s_p};
+  bundle_image_normal_radial(D, S, blockIdx.x, threadIdx.x == 0);
+}
+
+__global__ __launch_bounds__(BUNDLE_THREADS) void bundle_cg_start_radial_kernel(BundleData D)
+{
+  __shared__ float s_p[4 * FUND_SLOTS];
+  BundleBlockSum S{s_p};
+  bundle_cg_start<true, true>(D, S, threadIdx.x, BUNDLE_THREADS, threadIdx.x == 0);
+}
+
+__global__ __launch_bounds__(BUNDLE_THREADS) void bundle_cg_track_radial_kernel(BundleData D)
+{
+  const int t = blockIdx.x * BUNDLE_THREADS + threadIdx.x;
+  if (t < scene_T(D.s)) bundle_cg_track<true, true>(D, t);
+}
+
+__global__ __launch_bounds__(BUNDLE_THREADS) void bundle_cg_image_radial_kernel(BundleData D)
+{
+  __shared__ float s_p[8 * FUND_SLOTS];
+  BundleBlockSum S{s_p};
+  bundle_cg_image_radial(D, S, blockIdx.x, threadIdx.x == 0);
+}
+
+__global__ __launch_bounds__(BUNDLE_THREADS) void bundle_cg_scalar_radial_kernel(BundleData D)
+{
+  __shared__ float s_p[2 * FUND_SLOTS];
+  BundleBlockSum S{s_p};
+  bundle_cg_scalar<true, true>(D, S, threadIdx.x, BUNDLE_THREADS, threadIdx.x == 0);
+}
+
+__global__ __launch_bounds__(BUNDLE_THREADS) void bundle_track_trial_radial_kernel(BundleData D)
+{
+  const int t = blockIdx.x * BUNDLE_THREADS + threadIdx.x;
+  if (t < scene_T(D.s)) bundle_track_trial<true, true>(D, t);
+}
+
+// lane per image: its trial camera; the first BUNDLE_MAX_GROUPS lanes: the trial scale and coefficient of a group
+__global__ __launch_bounds__(BUNDLE_THREADS) void bundle_image_trial_radial_kernel(BundleData D)
+{
+  const int i = blockIdx.x * BUNDLE_THREADS + threadIdx.x;
+  if (i < D.s.nimages) bundle_image_trial(D, i);
+  if (i < BUNDLE_MAX_GROUPS) {
+    bundle_focal_trial(D, i);
+    bundle_radial_trial(D, i);
+  }
+}
+
+__global__ __launch_bounds__(BUNDLE_THREADS) void bundle_weight_out_radial_kernel(BundleData D)
+{
+  const int o = blockIdx.x * BUNDLE_THREADS + threadIdx.x;
+  if (o < scene_O(D.s)) bundle_weight_slot<true, true>(D, o);
+}
+
+// the first ngroups lanes: d_radial
+__global__ __launch_bounds__(BUNDLE_THREADS) void bundle_radial_out_kernel(BundleData D, int refined, int radial)
+{
+  const int g = threadIdx.x;
+  if (g < D.ngroups) bundle_radial_out(D, g, refined != 0, radial != 0);
+}
+
+// misift_undistort_obs_batch: lane per slot, one 16-byte load and one 16-byte store
+__global__ __launch_bounds__(BUNDLE_THREADS) void undistort_obs_kernel(int max_obs, const TrackObs *obs,
+                                                                       const int *export_summary, int nimages,
+                                                                       const float *intrinsics, const int *group,
+                                                                       const int *radial, TrackObs *out)
+{
+  const long long o = (long long)blockIdx.x * BUNDLE_THREADS + threadIdx.x;
+  const int O = scene_clamp(export_summary[3], max_obs);
+  if (o >= O) return;
+  const TrackObs ob = bundle_undistort_obs(track_obs_load(obs + o), nimages, intrinsics, group, radial);
+  reinterpret_cast<int4 *>(out)[o] = make_int4(ob.frame, ob.record, __float_as_int(ob.xpos), __float_as_int(ob.ypos));
 }
 
 }  // namespace
@@ -379,6 +454,13 @@ size_t adjust_bundle_focal_batch_tmp_bytes(int max_tracks, int max_obs, int nima
   BundleData D;
   D.s.max_tracks = max_tracks; D.s.max_obs = max_obs; D.s.nimages = nimages;
   return bundle_layout(D, nullptr, true);
+}
+
+size_t adjust_bundle_radial_batch_tmp_bytes(int max_tracks, int max_obs, int nimages)
+{
+  BundleData D;
+  D.s.max_tracks = max_tracks; D.s.max_obs = max_obs; D.s.nimages = nimages;
+  return bundle_layout(D, nullptr, true, true);
 }
 
 // Enqueue misift_adjust_bundle_robust_batch on the context stream (common.hpp); misift_adjust_bundle_batch is loss 0 and
@@ -398,26 +480,39 @@ int launch_adjust_bundle_batch(misift_ctx *ctx, const TrackScene &scene, const i
 // Enqueue misift_adjust_bundle_focal_batch.  focal: an image has a group, so the FOCAL instances run, with one launch
 // more in the setup (the groups' members) and the wider temp; otherwise the launches are those of the robust call.  With
 // d_intrinsics_out one launch more at the end writes it and d_focal; the two existing calls pass NULL.
-int launch_adjust_bundle_focal_batch(misift_ctx *ctx, const TrackScene &scene, const int *h_held, int min_views,
-                                     int min_obs, int num_loops, int cg_iters, float thresh2, float lambda0,
-                                     int orthonormalise, int loss, float loss_scale, float loss_scale2, int ngroups,
-                                     const int *h_group, bool focal, float *d_cam_out, float *d_points_out, int *d_cam_obs,
-                                     int *d_cam_status, float *d_cam_rms, int *d_point_obs, float *d_history,
-                                     float *d_cost, float *d_obs_weight, int *d_summary, float *d_intrinsics_out,
-                                     int *d_focal)
+// misift_adjust_bundle_radial_batch is the same sequence: R (NULL in the focal call) has the pinned copies of `radial`
+// and `k0`, d_radial, and `on`: an image has a group and some k_g is an unknown or starts off zero, so the RADIAL
+// instances run in place of the FOCAL ones, launch for launch.  One launch more at the end writes d_radial.
+struct BundleRadialArgs {
+  const int *h_radial;
+  const float *h_k0;
+  bool on;
+  int *d_radial;
+};
+static int bundle_launch(misift_ctx *ctx, const TrackScene &scene, const int *h_held, int min_views, int min_obs,
+                         int num_loops, int cg_iters, float thresh2, float lambda0, int orthonormalise, int loss,
+                         float loss_scale, float loss_scale2, int ngroups, const int *h_group, bool focal,
+                         float *d_cam_out, float *d_points_out, int *d_cam_obs, int *d_cam_status, float *d_cam_rms,
+                         int *d_point_obs, float *d_history, float *d_cost, float *d_obs_weight, int *d_summary,
+                         float *d_intrinsics_out, int *d_focal, const BundleRadialArgs *R)
 {
   const int max_tracks = scene.max_tracks, max_obs = scene.max_obs, nimages = scene.nimages;
-  const int rc = misift_ensure_tmp(ctx, focal ? adjust_bundle_focal_batch_tmp_bytes(max_tracks, max_obs, nimages)
-                                              : adjust_bundle_batch_tmp_bytes(max_tracks, max_obs, nimages));
+  const bool radial = R && R->on;
+  const int rc = misift_ensure_tmp(ctx, radial  ? adjust_bundle_radial_batch_tmp_bytes(max_tracks, max_obs, nimages)
+                                        : focal ? adjust_bundle_focal_batch_tmp_bytes(max_tracks, max_obs, nimages)
+                                                : adjust_bundle_batch_tmp_bytes(max_tracks, max_obs, nimages));
   if (rc) return rc;
   BundleData D;
+  if (R) {
+    D.rad = R->h_radial; D.k0 = R->h_k0; D.radial_out = R->d_radial;
+  }
   D.ngroups = ngroups; D.grp = h_group; D.intrinsics_out = d_intrinsics_out; D.focal_out = d_focal;
   D.s = scene; D.min_views = min_views; D.min_obs = min_obs;
   D.num_loops = num_loops; D.cg_iters = cg_iters; D.orthonormalise = orthonormalise; D.thresh2 = thresh2;
   D.lambda0 = lambda0;
   D.loss = loss; D.loss_scale = loss_scale; D.loss_scale2 = loss_scale2;
   D.held = h_held;
-  bundle_layout(D, reinterpret_cast<char *>(ctx->d_match_tmp), focal);
+  bundle_layout(D, reinterpret_cast<char *>(ctx->d_match_tmp), focal, radial);
   D.cam_out = d_cam_out; D.points_out = d_points_out; D.cam_rms = d_cam_rms; D.history = d_history; D.cost = d_cost;
   D.cam_obs = d_cam_obs; D.cam_status = d_cam_status; D.point_obs = d_point_obs; D.summary = d_summary;
   D.obs_weight = d_obs_weight;
@@ -436,46 +531,53 @@ int launch_adjust_bundle_focal_batch(misift_ctx *ctx, const TrackScene &scene, c
   // the loss is the same for the whole call: the two kernels that read it are picked here
   const bool robust = loss != BUNDLE_LOSS_NONE;
   auto eval = [&](int trial) {
-    if (focal && robust) hipLaunchKernelGGL((bundle_eval_kernel<true, true>), per_slot, th, 0, s, D, trial);
+    if (radial && robust) hipLaunchKernelGGL((bundle_eval_kernel<true, true, true>), per_slot, th, 0, s, D, trial);
+    else if (radial) hipLaunchKernelGGL((bundle_eval_kernel<false, true, true>), per_slot, th, 0, s, D, trial);
+    else if (focal && robust) hipLaunchKernelGGL((bundle_eval_kernel<true, true>), per_slot, th, 0, s, D, trial);
     else if (focal) hipLaunchKernelGGL((bundle_eval_kernel<false, true>), per_slot, th, 0, s, D, trial);
     else if (robust) hipLaunchKernelGGL(bundle_eval_kernel<true>, per_slot, th, 0, s, D, trial);
     else hipLaunchKernelGGL(bundle_eval_kernel<false>, per_slot, th, 0, s, D, trial);
   };
   auto track_normal = [&] {
-    if (focal && robust) hipLaunchKernelGGL(bundle_track_normal_focal_kernel<true>, per_track, th, 0, s, D);
+    if (radial && robust) hipLaunchKernelGGL(bundle_track_normal_radial_kernel<true>, per_track, th, 0, s, D);
+    else if (radial) hipLaunchKernelGGL(bundle_track_normal_radial_kernel<false>, per_track, th, 0, s, D);
+    else if (focal && robust) hipLaunchKernelGGL(bundle_track_normal_focal_kernel<true>, per_track, th, 0, s, D);
     else if (focal) hipLaunchKernelGGL(bundle_track_normal_focal_kernel<false>, per_track, th, 0, s, D);
     else if (robust) hipLaunchKernelGGL(bundle_track_normal_kernel<true>, per_track, th, 0, s, D);
     else hipLaunchKernelGGL(bundle_track_normal_kernel<false>, per_track, th, 0, s, D);
   };
   // a phase that reads the focal scale has a FOCAL instance; the plain one holds no trace of it
-  auto pick = [&](auto plain, auto with_focal, dim3 grid) {
-    if (focal) hipLaunchKernelGGL(with_focal, grid, th, 0, s, D);
+  auto pick = [&](auto plain, auto with_focal, auto with_radial, dim3 grid) {
+    if (radial) hipLaunchKernelGGL(with_radial, grid, th, 0, s, D);
+    else if (focal) hipLaunchKernelGGL(with_focal, grid, th, 0, s, D);
     else hipLaunchKernelGGL(plain, grid, th, 0, s, D);
   };
   const dim3 per_image_or_group = bundle_blocks(nimages > BUNDLE_MAX_GROUPS ? nimages : BUNDLE_MAX_GROUPS);
   int r = scope("bundle_setup", [&] {
     launch_track_candidates(ctx, scene, D.owner, D.key);
     hipLaunchKernelGGL(bundle_image_init_kernel, per_image, th, 0, s, D);
-    hipLaunchKernelGGL(bundle_premember_kernel, per_slot, th, 0, s, D);
+    pick(bundle_premember_kernel, bundle_premember_kernel, bundle_premember_radial_kernel, per_slot);
     hipLaunchKernelGGL(bundle_activate_kernel, per_track, th, 0, s, D);
     hipLaunchKernelGGL(bundle_gather_kernel, image_wg, th, 0, s, D);
-    if (focal) hipLaunchKernelGGL(bundle_focal_init_kernel, one, th, 0, s, D);
+    if (radial) hipLaunchKernelGGL(bundle_radial_init_kernel, one, th, 0, s, D);
+    else if (focal) hipLaunchKernelGGL(bundle_focal_init_kernel, one, th, 0, s, D);
     eval(0);
     hipLaunchKernelGGL(bundle_cost_kernel, image_wg, th, 0, s, D, 0);
     hipLaunchKernelGGL(bundle_start_kernel, one, th, 0, s, D);
   });
   for (int loop = 0; loop < num_loops && !r; loop++) {
     r = scope("bundle_track", [&] { track_normal(); });
-    if (!r) r = scope("bundle_image", [&] { pick(bundle_image_normal_kernel, bundle_image_normal_focal_kernel, image_wg); });
-    if (!r) r = scope("bundle_scalar", [&] { pick(bundle_cg_start_kernel, bundle_cg_start_focal_kernel, one); });
+    if (!r) r = scope("bundle_image", [&] { pick(bundle_image_normal_kernel, bundle_image_normal_focal_kernel, bundle_image_normal_radial_kernel, image_wg); });
+    if (!r) r = scope("bundle_scalar", [&] { pick(bundle_cg_start_kernel, bundle_cg_start_focal_kernel, bundle_cg_start_radial_kernel, one); });
     for (int it = 0; it < cg_iters && !r; it++) {
-      r = scope("bundle_track", [&] { pick(bundle_cg_track_kernel, bundle_cg_track_focal_kernel, per_track); });
-      if (!r) r = scope("bundle_image", [&] { pick(bundle_cg_image_kernel, bundle_cg_image_focal_kernel, image_wg); });
-      if (!r) r = scope("bundle_scalar", [&] { pick(bundle_cg_scalar_kernel, bundle_cg_scalar_focal_kernel, one); });
+      r = scope("bundle_track", [&] { pick(bundle_cg_track_kernel, bundle_cg_track_focal_kernel, bundle_cg_track_radial_kernel, per_track); });
+      if (!r) r = scope("bundle_image", [&] { pick(bundle_cg_image_kernel, bundle_cg_image_focal_kernel, bundle_cg_image_radial_kernel, image_wg); });
+      if (!r) r = scope("bundle_scalar", [&] { pick(bundle_cg_scalar_kernel, bundle_cg_scalar_focal_kernel, bundle_cg_scalar_radial_kernel, one); });
     }
-    if (!r) r = scope("bundle_track", [&] { pick(bundle_track_trial_kernel, bundle_track_trial_focal_kernel, per_track); });
+    if (!r) r = scope("bundle_track", [&] { pick(bundle_track_trial_kernel, bundle_track_trial_focal_kernel, bundle_track_trial_radial_kernel, per_track); });
     if (!r) r = scope("bundle_trial", [&] {
-      if (focal) hipLaunchKernelGGL(bundle_image_trial_focal_kernel, per_image_or_group, th, 0, s, D);
+      if (radial) hipLaunchKernelGGL(bundle_image_trial_radial_kernel, per_image_or_group, th, 0, s, D);
+      else if (focal) hipLaunchKernelGGL(bundle_image_trial_focal_kernel, per_image_or_group, th, 0, s, D);
       else hipLaunchKernelGGL(bundle_image_trial_kernel, per_image, th, 0, s, D);
       eval(1);
     });
@@ -486,131 +588,71 @@ int launch_adjust_bundle_focal_batch(misift_ctx *ctx, const TrackScene &scene, c
   return scope("bundle_out", [&] {
     hipLaunchKernelGGL(bundle_image_out_kernel, per_image, th, 0, s, D);
     hipLaunchKernelGGL(bundle_track_out_kernel, per_track, th, 0, s, D);
-    if (d_obs_weight) pick(bundle_weight_out_kernel, bundle_weight_out_focal_kernel, per_slot);
+    if (d_obs_weight) pick(bundle_weight_out_kernel, bundle_weight_out_focal_kernel, bundle_weight_out_radial_kernel, per_slot);
     if (d_intrinsics_out) hipLaunchKernelGGL(bundle_focal_out_kernel, per_image_or_group, th, 0, s, D, focal ? 1 : 0);
+    if (R && ngroups > 0) hipLaunchKernelGGL(bundle_radial_out_kernel, one, th, 0, s, D, focal ? 1 : 0, radial ? 1 : 0);
   });
 }
 
-namespace {
-
-// the phases of the host hook that read the loss
-template <bool ROBUST, bool FOCAL>
-void bundle_host_eval(const BundleData &D, int O, bool trial)
+int launch_adjust_bundle_focal_batch(misift_ctx *ctx, const TrackScene &scene, const int *h_held, int min_views,
+                                     int min_obs, int num_loops, int cg_iters, float thresh2, float lambda0,
+                                     int orthonormalise, int loss, float loss_scale, float loss_scale2, int ngroups,
+                                     const int *h_group, bool focal, float *d_cam_out, float *d_points_out, int *d_cam_obs,
+                                     int *d_cam_status, float *d_cam_rms, int *d_point_obs, float *d_history,
+                                     float *d_cost, float *d_obs_weight, int *d_summary, float *d_intrinsics_out,
+                                     int *d_focal)
 {
-  for (int o = 0; o < O; o++) bundle_eval_slot<ROBUST, FOCAL>(D, o, trial);
-}
-template <bool ROBUST, bool FOCAL>
-void bundle_host_track_normal(const BundleData &D, int T)
-{
-  for (int t = 0; t < T; t++) FOCAL ? bundle_track_normal_focal<ROBUST>(D, t) : bundle_track_normal<ROBUST>(D, t);
-}
-
-// the phases of the hook in the order of the launches
-template <bool ROBUST, bool FOCAL>
-void bundle_host_run(const BundleData &D, int T, int O)
-{
-  const int nimages = D.s.nimages;
-  BundleHostSum S;
-  if (FOCAL) bundle_focal_init(D, S, 0, 1);
-  bundle_host_eval<ROBUST, FOCAL>(D, O, false);
-  for (int i = 0; i < nimages; i++) bundle_image_cost(D, S, i, false, true);
-  bundle_scalar_init(D, S, true);
-  for (int loop = 0; loop < D.num_loops; loop++) {
-    bundle_host_track_normal<ROBUST, FOCAL>(D, T);
-    for (int i = 0; i < nimages; i++) FOCAL ? bundle_image_normal_focal(D, S, i, true) : bundle_image_normal(D, S, i, true);
-    bundle_cg_start<FOCAL>(D, S, 0, 1, true);
-    for (int it = 0; it < D.cg_iters; it++) {
-      for (int t = 0; t < T; t++) bundle_cg_track<FOCAL>(D, t);
-      for (int i = 0; i < nimages; i++) FOCAL ? bundle_cg_image_focal(D, S, i, true) : bundle_cg_image(D, S, i, true);
-      bundle_cg_scalar<FOCAL>(D, S, 0, 1, true);
-    }
-    for (int t = 0; t < T; t++) bundle_track_trial<FOCAL>(D, t);
-    for (int i = 0; i < nimages; i++) bundle_image_trial(D, i);
-    if (FOCAL)
-      for (int g = 0; g < BUNDLE_MAX_GROUPS; g++) bundle_focal_trial(D, g);
-    bundle_host_eval<ROBUST, FOCAL>(D, O, true);
-    for (int i = 0; i < nimages; i++) bundle_image_cost(D, S, i, true, true);
-    bundle_decide(D, S, 0, 1, true);
-  }
-  for (int i = 0; i < nimages; i++) bundle_image_out(D, i);
-  for (int t = 0; t < T; t++) bundle_track_out(D, t);
-  if (D.obs_weight)
-    for (int o = 0; o < O; o++) bundle_weight_slot<FOCAL>(D, o);
-  if (D.intrinsics_out) {
-    for (int i = 0; i < nimages; i++) bundle_intrinsics_out(D, i, FOCAL);
-    for (int g = 0; g < D.ngroups; g++) bundle_focal_out(D, g, FOCAL);
-  }
+  return bundle_launch(ctx, scene, h_held, min_views, min_obs, num_loops, cg_iters, thresh2, lambda0, orthonormalise, loss,
+                       loss_scale, loss_scale2, ngroups, h_group, focal, d_cam_out, d_points_out, d_cam_obs, d_cam_status,
+                       d_cam_rms, d_point_obs, d_history, d_cost, d_obs_weight, d_summary, d_intrinsics_out, d_focal,
+                       nullptr);
 }
 
-}  // namespace
+int launch_adjust_bundle_radial_batch(misift_ctx *ctx, const TrackScene &scene, const int *h_held, int min_views,
+                                      int min_obs, int num_loops, int cg_iters, float thresh2, float lambda0,
+                                      int orthonormalise, int loss, float loss_scale, float loss_scale2, int ngroups,
+                                      const int *h_group, bool focal, const int *h_radial, const float *h_k0, bool radial,
+                                      float *d_cam_out, float *d_points_out, int *d_cam_obs, int *d_cam_status,
+                                      float *d_cam_rms, int *d_point_obs, float *d_history, float *d_cost,
+                                      float *d_obs_weight, int *d_summary, float *d_intrinsics_out, int *d_focal,
+                                      int *d_radial)
+{
+  const BundleRadialArgs R{h_radial, h_k0, radial, d_radial};
+  return bundle_launch(ctx, scene, h_held, min_views, min_obs, num_loops, cg_iters, thresh2, lambda0, orthonormalise, loss,
+                       loss_scale, loss_scale2, ngroups, h_group, focal, d_cam_out, d_points_out, d_cam_obs, d_cam_status,
+                       d_cam_rms, d_point_obs, d_history, d_cost, d_obs_weight, d_summary, d_intrinsics_out, d_focal, &R);
+}
 
-// The hooks' common body: the whole call on host arrays; ngroups 0 and no intrinsics_out is the robust call.
-static int bundle_host(const char *who, int max_tracks, int max_obs, const int *track_offsets,
+// Enqueue misift_undistort_obs_batch: one launch, no temp
+int launch_undistort_obs_batch(misift_ctx *ctx, int max_obs, const TrackObs *d_obs, const int *d_export_summary,
+                               int nimages, const float *h_intrinsics, const int *h_group, const int *d_radial,
+                               TrackObs *d_obs_out)
+{
+  LaunchScope ls(ctx, "undistort_obs");
+  hipLaunchKernelGGL(undistort_obs_kernel, bundle_blocks(max_obs), dim3(BUNDLE_THREADS), 0, ctx->stream, max_obs, d_obs,
+                     d_export_summary, nimages, h_intrinsics, h_group, d_radial, d_obs_out);
+  return ls.finish();
+}
+
+// The hooks' common body (bundle_host.hpp) with the library's error message.
+static int bundle_hook(const char *who, int max_tracks, int max_obs, const int *track_offsets,
                        const misift_track_obs *obs, const int *export_summary, const float *points,
                        const int *point_status, int nimages, const float *cam, const int *cam_pair,
                        const float *intrinsics, int nhold, const int *hold, int min_views, int min_obs, int num_loops,
                        int cg_iters, float max_error, float lambda0, int orthonormalise, int loss, float loss_scale,
                        int ngroups, const int *group, float *cam_out, float *points_out, int *cam_obs, int *cam_status,
                        float *cam_rms, int *point_obs, float *history, float *cost, float *obs_weight, int *summary,
-                       float *intrinsics_out, int *focal_out)
+                       float *intrinsics_out, int *focal_out, const int *radial_flags = nullptr,
+                       const float *k0 = nullptr, int *radial_out = nullptr)
 {
-  bool ok = max_tracks >= 1 && max_obs >= 1 && nimages >= 1 && track_offsets && obs && export_summary && points &&
-            point_status && cam && cam_pair && intrinsics && nhold >= 0 && (nhold == 0 || hold) && min_views >= 2 &&
-            min_obs >= 3 && num_loops >= 0 && cg_iters >= 0 && max_error > 0.0f && lambda0 > 0.0f &&
-            fundamental_finite(lambda0) && (orthonormalise == 0 || orthonormalise == 1) && cam_out && points_out &&
-            cam_obs && cam_status && cam_rms && point_obs && (history || num_loops == 0) && cost && summary &&
-            loss >= BUNDLE_LOSS_NONE && loss <= BUNDLE_LOSS_GEMAN_MCCLURE &&
-            (loss == BUNDLE_LOSS_NONE || (loss_scale > 0.0f && fundamental_finite(loss_scale)));
-  for (int j = 0; ok && j < nhold; j++) ok = hold[j] >= 0 && hold[j] < nimages;
-  ok = ok && ngroups >= 0 && ngroups <= BUNDLE_MAX_GROUPS && (ngroups == 0 || group);
-  bool focal = false;
-  for (int i = 0; ok && ngroups > 0 && i < nimages; i++) {
-    ok = group[i] >= -1 && group[i] < ngroups;
-    focal = focal || group[i] >= 0;
-  }
-  if (!ok) {
-    misift_set_error((std::string(who) + ": invalid argument").c_str());
-    return MISIFT_EINVAL;
-  }
-  BundleData D;
-  D.ngroups = ngroups; D.grp = ngroups > 0 ? group : nullptr; D.intrinsics_out = intrinsics_out; D.focal_out = focal_out;
-  D.s = TrackScene{max_tracks, max_obs, nimages, track_offsets, reinterpret_cast<const TrackObs *>(obs), export_summary,
-                   points, point_status, cam, cam_pair, intrinsics};
-  D.min_views = min_views; D.min_obs = min_obs; D.num_loops = num_loops; D.cg_iters = cg_iters;
-  D.orthonormalise = orthonormalise;
-  D.thresh2 = max_error * max_error; D.lambda0 = lambda0;
-  const bool robust = loss != BUNDLE_LOSS_NONE;
-  D.loss = loss; D.loss_scale = robust ? loss_scale : 0.0f; D.loss_scale2 = D.loss_scale * D.loss_scale;
-  std::vector<int> held(nimages, 0);
-  for (int j = 0; j < nhold; j++) held[hold[j]] = 1;
-  D.held = held.data();
-  std::vector<char> tmp(bundle_layout(D, nullptr, focal) + 16, 0);
-  bundle_layout(D, reinterpret_cast<char *>(((uintptr_t)tmp.data() + 15) & ~(uintptr_t)15), focal);
-  D.cam_out = cam_out; D.points_out = points_out; D.cam_rms = cam_rms; D.history = history; D.cost = cost;
-  D.cam_obs = cam_obs; D.cam_status = cam_status; D.point_obs = point_obs; D.summary = summary;
-  D.obs_weight = obs_weight;
-  const int T = scene_T(D.s), O = scene_O(D.s);
-  // the owners and the candidates, as launch_track_candidates
-  for (int o = 0; o < max_obs; o++) D.owner[o] = -1;
-  for (int t = 0; t < T; t++) scene_track_owns(D.s, D.owner, t);
-  for (int o = 0; o < O; o++) D.key[o] = scene_slot_key(D.s, D.owner, o);
-  for (int j = 0; j < 8; j++) summary[j] = 0;
-  for (int i = 0; i < nimages; i++) bundle_image_init(D, i);
-  for (int o = 0; o < O; o++) bundle_slot_premember(D, o);
-  for (int t = 0; t < T; t++) bundle_track_activate(D, t);
-  {
-    int at = 0;
-    for (int i = 0; i < nimages; i++) {
-      D.istart[i] = at;
-      for (int o = 0; o < O; o++)
-        if (D.key[o] == i) D.list[at++] = o;
-      D.icount[i] = at - D.istart[i];
-      if (D.istate[i] == BUNDLE_ADJUSTED && D.icount[i] < min_obs) D.istate[i] = BUNDLE_FEW_OBS;
-    }
-  }
-  if (focal) robust ? bundle_host_run<true, true>(D, T, O) : bundle_host_run<false, true>(D, T, O);
-  else robust ? bundle_host_run<true, false>(D, T, O) : bundle_host_run<false, false>(D, T, O);
-  return MISIFT_OK;
+  if (bundle_host(max_tracks, max_obs, track_offsets, reinterpret_cast<const TrackObs *>(obs), export_summary, points,
+                  point_status, nimages, cam, cam_pair, intrinsics, nhold, hold, min_views, min_obs, num_loops, cg_iters,
+                  max_error, lambda0, orthonormalise, loss, loss_scale, ngroups, group, cam_out, points_out, cam_obs,
+                  cam_status, cam_rms, point_obs, history, cost, obs_weight, summary, intrinsics_out, focal_out,
+                  radial_flags, k0, radial_out))
+    return MISIFT_OK;
+  misift_set_error((std::string(who) + ": invalid argument").c_str());
+  return MISIFT_EINVAL;
 }
 
 // Test-only, host-only: the whole call on host arrays, phase after phase through bundle_core.hpp.
@@ -629,10 +671,48 @@ extern "C" int misift_test_adjust_bundle_focal(int max_tracks, int max_obs, cons
     misift_set_error("misift_test_adjust_bundle_focal: invalid argument");
     return MISIFT_EINVAL;
   }
-  return bundle_host(__func__, max_tracks, max_obs, track_offsets, obs, export_summary, points, point_status, nimages, cam,
+  return bundle_hook(__func__, max_tracks, max_obs, track_offsets, obs, export_summary, points, point_status, nimages, cam,
                      cam_pair, intrinsics, nhold, hold, min_views, min_obs, num_loops, cg_iters, max_error, lambda0,
                      orthonormalise, loss, loss_scale, ngroups, group, cam_out, points_out, cam_obs, cam_status, cam_rms,
                      point_obs, history, cost, obs_weight, summary, intrinsics_out, focal);
+}
+
+// The same for misift_adjust_bundle_radial_batch.
+extern "C" int misift_test_adjust_bundle_radial(int max_tracks, int max_obs, const int *track_offsets,
+                                                const misift_track_obs *obs, const int *export_summary,
+                                                const float *points, const int *point_status, int nimages,
+                                                const float *cam, const int *cam_pair, const float *intrinsics,
+                                                int nhold, const int *hold, int min_views, int min_obs, int num_loops,
+                                                int cg_iters, float max_error, float lambda0, int orthonormalise,
+                                                int loss, float loss_scale, int ngroups, const int *group,
+                                                const int *radial, const float *k0, float *cam_out, float *points_out,
+                                                int *cam_obs, int *cam_status, float *cam_rms, int *point_obs,
+                                                float *history, float *cost, float *obs_weight, int *summary,
+                                                float *intrinsics_out, int *focal, float *radial_out)
+{
+  static const int no_flag[BUNDLE_MAX_GROUPS] = {0};
+  static const float no_k0[BUNDLE_MAX_GROUPS] = {0.0f};
+  if (!intrinsics_out || (ngroups > 0 && (!focal || !radial_out)) || (radial != nullptr) != (k0 != nullptr)) {
+    misift_set_error("misift_test_adjust_bundle_radial: invalid argument");
+    return MISIFT_EINVAL;
+  }
+  return bundle_hook(__func__, max_tracks, max_obs, track_offsets, obs, export_summary, points, point_status, nimages, cam,
+                     cam_pair, intrinsics, nhold, hold, min_views, min_obs, num_loops, cg_iters, max_error, lambda0,
+                     orthonormalise, loss, loss_scale, ngroups, group, cam_out, points_out, cam_obs, cam_status, cam_rms,
+                     point_obs, history, cost, obs_weight, summary, intrinsics_out, focal, radial ? radial : no_flag,
+                     k0 ? k0 : no_k0, reinterpret_cast<int *>(radial_out));
+}
+
+// Test-only, host-only: misift_undistort_obs_batch on host arrays.
+extern "C" int misift_test_undistort_obs(int max_obs, const misift_track_obs *obs, const int *export_summary, int nimages,
+                                         const float *intrinsics, int ngroups, const int *group, const float *radial,
+                                         misift_track_obs *obs_out)
+{
+  if (bundle_host_undistort(max_obs, reinterpret_cast<const TrackObs *>(obs), export_summary, nimages, intrinsics, ngroups,
+                            group, reinterpret_cast<const int *>(radial), reinterpret_cast<TrackObs *>(obs_out)))
+    return MISIFT_OK;
+  misift_set_error("misift_test_undistort_obs: invalid argument");
+  return MISIFT_EINVAL;
 }
 
 extern "C" int misift_test_adjust_bundle_robust(int max_tracks, int max_obs, const int *track_offsets,
@@ -645,7 +725,7 @@ extern "C" int misift_test_adjust_bundle_robust(int max_tracks, int max_obs, con
                                                 int *cam_obs, int *cam_status, float *cam_rms, int *point_obs,
                                                 float *history, float *cost, float *obs_weight, int *summary)
 {
-  return bundle_host(__func__, max_tracks, max_obs, track_offsets, obs, export_summary, points, point_status, nimages, cam,
+  return bundle_hook(__func__, max_tracks, max_obs, track_offsets, obs, export_summary, points, point_status, nimages, cam,
                      cam_pair, intrinsics, nhold, hold, min_views, min_obs, num_loops, cg_iters, max_error, lambda0,
                      orthonormalise, loss, loss_scale, 0, nullptr, cam_out, points_out, cam_obs, cam_status, cam_rms,
                      point_obs, history, cost, obs_weight, summary, nullptr, nullptr);

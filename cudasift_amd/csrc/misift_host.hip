@@ -2992,7 +2992,8 @@ extern "C" int misift_transform_scene_batch(misift_ctx *ctx, const float *d_sim,
 }
 
 // The body of the three bundle calls: the robust call, with ngroups > 0 and a group for some image the focal scales
-// among the unknowns, and with d_intrinsics_out the focal call's two outputs.
+// among the unknowns, and with d_intrinsics_out the focal call's two outputs.  With d_radial it is the radial call:
+// `radial` and `k0` (both or neither NULL: all zero) go to the pinned slot behind the groups, padded with zeros.
 static int adjust_bundle(const char *who, misift_ctx *ctx, int max_tracks, int max_obs, const int *d_track_offsets,
                          const misift_track_obs *d_obs, const int *d_export_summary, const float *d_points,
                          const int *d_point_status, int nimages, const float *d_cam, const int *d_cam_pair,
@@ -3000,7 +3001,9 @@ static int adjust_bundle(const char *who, misift_ctx *ctx, int max_tracks, int m
                          int cg_iters, float max_error, float lambda0, int orthonormalise, int loss, float loss_scale,
                          int ngroups, const int *group, float *d_cam_out, float *d_points_out, int *d_cam_obs,
                          int *d_cam_status, float *d_cam_rms, int *d_point_obs, float *d_history, float *d_cost,
-                         float *d_obs_weight, int *d_summary, float *d_intrinsics_out, int *d_focal)
+                         float *d_obs_weight, int *d_summary, float *d_intrinsics_out, int *d_focal,
+                         bool with_radial = false, const int *radial = nullptr, const float *k0 = nullptr,
+                         float *d_radial = nullptr)
 {
   ARG_CHECK_IN(who, ctx != nullptr);
   TrackScene S;
@@ -3026,6 +3029,19 @@ static int adjust_bundle(const char *who, misift_ctx *ctx, int max_tracks, int m
     ARG_CHECK_IN(who, group[i] >= -1 && group[i] < ngroups);
     focal = focal || group[i] >= 0;
   }
+  int h_rad[MISIFT_MAX_RADIAL_GROUPS] = {0};
+  float h_k0[MISIFT_MAX_RADIAL_GROUPS] = {0.0f};
+  bool radial_on = false;
+  if (with_radial) {
+    ARG_CHECK_IN(who, (radial != nullptr) == (k0 != nullptr) && (d_radial || ngroups == 0));
+    for (int g = 0; radial && g < ngroups; g++) {
+      ARG_CHECK_IN(who, radial[g] == 0 || radial[g] == 1);
+      ARG_CHECK_IN(who, k0[g] >= -3.402823466e+38f && k0[g] <= 3.402823466e+38f);   // NaN fails too
+      h_rad[g] = radial[g];
+      h_k0[g] = k0[g];
+      radial_on = radial_on || (focal && (h_rad[g] != 0 || h_k0[g] != 0.0f));
+    }
+  }
   const std::vector<int> held = held_flags(nimages, nhold, hold);
   const std::vector<int> none(d_intrinsics_out && ngroups == 0 ? nimages : 0, -1);   // the two old calls copy no group
   const float thresh2 = max_error * max_error;                              // rounded once, here
@@ -3033,10 +3049,20 @@ static int adjust_bundle(const char *who, misift_ctx *ctx, int max_tracks, int m
   const float c2 = c * c;                                                   // and so is this
   RoctxRange range(who);
   return run_batch(ctx, {{intrinsics, sizeof(float) * 4 * (size_t)nimages}, {held.data(), sizeof(int) * (size_t)nimages},
-                         {ngroups > 0 ? group : none.data(), d_intrinsics_out ? sizeof(int) * (size_t)nimages : 0}},
+                         {ngroups > 0 ? group : none.data(), d_intrinsics_out ? sizeof(int) * (size_t)nimages : 0},
+                         {h_rad, with_radial ? sizeof h_rad : 0}, {h_k0, with_radial ? sizeof h_k0 : 0}},
                    0, [&](int *h_lists, void *) {
                      S.intrinsics = reinterpret_cast<const float *>(h_lists);
                      const int *h_held = h_lists + 4 * (size_t)nimages;
+                     if (with_radial) {
+                       const int *p_rad = h_held + 2 * (size_t)nimages;
+                       return launch_adjust_bundle_radial_batch(
+                           ctx, S, h_held, min_views, min_obs, num_loops, cg_iters, thresh2, lambda0, orthonormalise, loss,
+                           c, c2, ngroups, h_held + nimages, focal, p_rad,
+                           reinterpret_cast<const float *>(p_rad + MISIFT_MAX_RADIAL_GROUPS), radial_on, d_cam_out,
+                           d_points_out, d_cam_obs, d_cam_status, d_cam_rms, d_point_obs, d_history, d_cost, d_obs_weight,
+                           d_summary, d_intrinsics_out, d_focal, reinterpret_cast<int *>(d_radial));
+                     }
                      return launch_adjust_bundle_focal_batch(ctx, S, h_held, min_views, min_obs, num_loops, cg_iters,
                                                              thresh2, lambda0, orthonormalise, loss, c, c2, ngroups,
                                                              h_held + nimages, focal, d_cam_out, d_points_out, d_cam_obs,
@@ -3085,6 +3111,53 @@ extern "C" int misift_adjust_bundle_focal_batch(misift_ctx *ctx, int max_tracks,
                        cg_iters, max_error, lambda0, orthonormalise, loss, loss_scale, ngroups, group, d_cam_out,
                        d_points_out, d_cam_obs, d_cam_status, d_cam_rms, d_point_obs, d_history, d_cost, d_obs_weight,
                        d_summary, d_intrinsics_out, d_focal);
+}
+
+// The focal call with one radial coefficient per camera group among the unknowns (applied to the observation).
+extern "C" int misift_adjust_bundle_radial_batch(misift_ctx *ctx, int max_tracks, int max_obs, const int *d_track_offsets,
+                                                 const misift_track_obs *d_obs, const int *d_export_summary,
+                                                 const float *d_points, const int *d_point_status, int nimages,
+                                                 const float *d_cam, const int *d_cam_pair, const float *intrinsics,
+                                                 int nhold, const int *hold, int min_views, int min_obs, int num_loops,
+                                                 int cg_iters, float max_error, float lambda0, int orthonormalise,
+                                                 int loss, float loss_scale, int ngroups, const int *group,
+                                                 const int *radial, const float *k0, float *d_cam_out,
+                                                 float *d_points_out, int *d_cam_obs, int *d_cam_status, float *d_cam_rms,
+                                                 int *d_point_obs, float *d_history, float *d_cost, float *d_obs_weight,
+                                                 int *d_summary, float *d_intrinsics_out, int *d_focal, float *d_radial)
+{
+  ARG_CHECK(d_intrinsics_out && (d_focal || ngroups == 0));
+  return adjust_bundle(__func__, ctx, max_tracks, max_obs, d_track_offsets, d_obs, d_export_summary, d_points,
+                       d_point_status, nimages, d_cam, d_cam_pair, intrinsics, nhold, hold, min_views, min_obs, num_loops,
+                       cg_iters, max_error, lambda0, orthonormalise, loss, loss_scale, ngroups, group, d_cam_out,
+                       d_points_out, d_cam_obs, d_cam_status, d_cam_rms, d_point_obs, d_history, d_cost, d_obs_weight,
+                       d_summary, d_intrinsics_out, d_focal, true, radial, k0, d_radial);
+}
+
+// An observation list undistorted under the coefficients the radial call left on the device: one launch.  The given
+// intrinsics and the groups go to the pinned slot.
+extern "C" int misift_undistort_obs_batch(misift_ctx *ctx, int max_obs, const misift_track_obs *d_obs,
+                                          const int *d_export_summary, int nimages, const float *intrinsics, int ngroups,
+                                          const int *group, const float *d_radial, misift_track_obs *d_obs_out)
+{
+  ARG_CHECK(ctx != nullptr);
+  ARG_CHECK(max_obs >= 1 && nimages >= 1 && d_obs && d_export_summary && intrinsics && d_obs_out);
+  ARG_CHECK(((uintptr_t)d_obs & 15) == 0 && ((uintptr_t)d_obs_out & 15) == 0);
+  ARG_CHECK(same_or_disjoint(d_obs, d_obs_out, sizeof(misift_track_obs) * (size_t)max_obs));
+  ARG_CHECK(ngroups >= 0 && ngroups <= MISIFT_MAX_RADIAL_GROUPS && (ngroups == 0 || (group && d_radial)));
+  for (int i = 0; i < nimages; i++) ARG_CHECK(intrinsics_usable(intrinsics + 4 * (size_t)i, 1));
+  for (int i = 0; ngroups > 0 && i < nimages; i++) ARG_CHECK(group[i] >= -1 && group[i] < ngroups);
+  const std::vector<int> none(ngroups == 0 ? nimages : 0, -1);
+  RoctxRange range(__func__);
+  return run_batch(ctx, {{intrinsics, sizeof(float) * 4 * (size_t)nimages},
+                         {ngroups > 0 ? group : none.data(), sizeof(int) * (size_t)nimages}},
+                   0, [&](int *h_lists, void *) {
+                     return launch_undistort_obs_batch(ctx, max_obs, reinterpret_cast<const TrackObs *>(d_obs),
+                                                       d_export_summary, nimages, reinterpret_cast<const float *>(h_lists),
+                                                       h_lists + 4 * (size_t)nimages,
+                                                       reinterpret_cast<const int *>(d_radial),
+                                                       reinterpret_cast<TrackObs *>(d_obs_out));
+                   });
 }
 
 // The plain sum of squares: loss 0 and no weights.

@@ -2092,6 +2092,152 @@ int misift_adjust_bundle_focal_batch(misift_ctx *ctx,
                                      float *d_intrinsics_out,        /* nimages x 4 */
                                      int   *d_focal);                /* ngroups x 3 words: s_g, M_g, status */
 
+/* THE RADIAL MODEL of misift_adjust_bundle_radial_batch and misift_undistort_obs_batch: one coefficient k_g per camera
+ * group, applied to the OBSERVATION, not to the projection (so the 20 values of step 1 are what they were and
+ * undistorting is closed-form).  For an observation (x, y) of image i with the GIVEN fx, fy, cx, cy, g = group[i] >= 0
+ * and k = k_g:
+ *     dx = x - cx;  dy = y - cy;  nx = dx / fx;  ny = dy / fy;
+ *     rho2 = nx*nx + ny*ny;  e = k * rho2;
+ *     x' = x + dx*e;  y' = y + dy*e;
+ * every operation fp32 and rounded on its own, no contraction.  With k == 0 and a finite rho2, x' == x and y' == y (a
+ * zero of either sign is added).  An observation so far out that rho2 overflows (beyond about 1.8e19 focal lengths
+ * from the principal point) gives NaN whatever k is; nearer ones can still overflow dx*rho2 or dx*e (1e20 px at a focal
+ * length of 500 does) and give an infinite or NaN x' unless k == 0.  rho2 always
+ * takes the given fx, fy, never the scaled ones of the focal call: k_g is a coefficient relative to the given
+ * intrinsics and its derivative column does not depend on the state.  An image with group[i] == -1 uses x, y as given.
+ *
+ * misift_adjust_bundle_focal_batch with k_g among the unknowns (no reference counterpart).  A few percent of radial
+ * displacement at the image corners is tens of pixels at 1920 x 1080: the hard gates throw such observations away and a
+ * robust loss bends the solution to the image centre.  In the chain it stands where adjust stands, and
+ * misift_undistort_obs_batch behind it hands every later call an undistorted list, so that they stay pinhole.
+ *   The arguments are those of misift_adjust_bundle_focal_batch in the same order, with `radial` and `k0` after `group`
+ *   and `d_radial` after `d_focal`.  radial[g] is 1 when k_g is an unknown and 0 when it is held at k0[g]; k0[g] is the
+ *   value every state starts with.  Both NULL means all zero; one NULL without the other is an error.  ngroups lies in
+ *   0 ... MISIFT_MAX_RADIAL_GROUPS, which is MISIFT_MAX_FOCAL_GROUPS: the per-track 3-vectors of the coefficients are
+ *   formed in a walk of their own over the members, in the registers the focal ones have left, so the count of groups
+ *   did not have to come down (no scratch memory in any instance).
+ *   The definition is that of misift_adjust_bundle_focal_batch, every word of it, with the amendments below.
+ *   Observations.  Wherever an observation of a grouped image enters, it is (x', y') under k_g of that state: in the
+ *   member test (under the start state, k_g = k0[g]), in the cost, in step 1 and in d_obs_weight.
+ *   The unknown.  k_g = k0[g] at the start.  A group is RADIAL-LIVE when radial[g] == 1 and it is live (M_g > 0).
+ *   Step 1.  A member of a group with radial[g] == 1 has one more column: Juk = -(dx*rho2), Jvk = -(dy*rho2), each
+ *   product rounded and then negated.  The sign: ru = x' - u grows by dx*rho2 per unit of k, and every column J of the
+ *   definition is such that r falls by J times the step, so the column is the negative of that growth.  Under a loss
+ *   both are multiplied by sw like the 20.  For such a member wk[q] = Juk*Pu[q] + Jvk*Pv[q].
+ *   Step 2.  Per active track and per radial-live group, after the d_gt: wk_gt = the per-track sum of wk over the
+ *   track's members in images of group g, and dk_gt = wk_gt . SOLVE(V', wk_gt) as d_gt.
+ *   Step 3.  A usable image of a group with radial[g] == 1 takes four more per-image sums, whatever its status: Ukk_i
+ *   (Juk*Juk + Jvk*Jvk), gk_i (Juk*ru + Jvk*rv), wyk_i (wk . y_t) and Ufk_i (Juf*Juk + Jvf*Jvk); a free one six more,
+ *   Uck_i[r] = Ju[r]*Juk + Jv[r]*Jvk: 52 sums in one pass, in the order the 33, Ucf, the focal three, Uck, these four.
+ *   Per radial-live group in ascending g, after all the focal scalars: U_kk, g_k, wy_k and U_fk are the cross-image sums
+ *   over the usable images of the group, Dk_g the sum of dk_gt by the 256-slot rule on t; UL_k = U_kk * l1,
+ *   S_kk = UL_k - Dk_g, b_k = g_k - wy_k.  An S_kk that is not finite and > 0 makes the step FAIL.  U_fk is not damped.
+ *   Step 4.  The PCG vector gains one scalar per radial-live group, appended after the focal scalars in ascending g: a
+ *   dot product adds v_k * w_k for each, one at a time, after the focal ones.  x_k = 0, r_k = b_k, z_k = r_k / S_kk,
+ *   p_k = z_k.  In an iteration:
+ *     the per-track sum takes, for each member, after wf * p_g, wk * p_k (per component) if radial[g] == 1;
+ *     a free image of such a group has y_i[r] = ((U'[r] . p_i + Ucf_i[r]*p_g) + Uck_i[r]*p_k) - (the sum of (W q_t)[r]);
+ *     every usable image of such a group takes the per-image sum wqk_i of wk . q_t, a free one also ck_i = Uck_i . p_i;
+ *     per radial-live group y_g = ((UL_g*p_g + U_fk*p_k) + the sum of c_i) - the sum of wq_i, and
+ *     y_k = ((UL_k*p_k + U_fk*p_g) + the cross-image sum of ck_i) - the cross-image sum of wqk_i;
+ *     x_k += alpha*p_k, r_k -= alpha*y_k, z_k = r_k / S_kk, p_k = z_k + beta*p_k.
+ *   Step 5.  The per-track sum of delta_t takes wk * x_k in the same way.  The trial coefficient of a radial-live group
+ *   is k_g + x_k; one that is not finite makes the trial state not finite.  Any other k_g stays.
+ *   Step 6.  s_g, k_g, the cameras and the points are kept or turned away together.
+ *   Outputs.  The ten shared ones; d_intrinsics_out and d_focal exactly as in the focal call; d_radial[3g..3g+2] for
+ *   g < ngroups: k_g of the final state (float), M_g (int, the word of d_focal), and the status (int):
+ *   3 MISIFT_RADIAL_HELD when radial[g] == 0 (k_g is k0[g]), otherwise 2 MISIFT_RADIAL_NOT_REFINED with
+ *   num_loops == 0, otherwise 0 MISIFT_RADIAL_REFINED for a radial-live group and 1 MISIFT_RADIAL_NO_MEMBER for any other.
+ *   - Identity.  With ngroups == 0, or every group[i] == -1, or every radial[g] == 0 and every k0[g] == 0, the call
+ *     launches the kernels of misift_adjust_bundle_focal_batch and one launch more (d_radial, with ngroups > 0), with that
+ *     call's temp; the twelve shared outputs are that call's byte for byte.
+ *   - The two scalars of a group are preconditioned each by its own Schur scalar (S_gg, S_kk), not by their 2 x 2 Schur
+ *     block [[S_gg, S_fk], [S_fk, S_kk]].  MEASURED in float64 restatements on the four recovery scenes below, 8 steps at
+ *     cg_iters 10, against a Levenberg-Marquardt with every step solved exactly, worst case: the two diagonals end
+ *     within 1.27e-2 (k_g, in units of the planted coefficient) and 1.26e-2 (s_g, relative) of it, the 2 x 2 block
+ *     within 2.84e-2 and 1.79e-2.  The block is not closer, so the simpler choice stands and S_fk is not formed.
+ *   - On planted scenes (120 tracks over 8 images and 400 over 24, 0.5 px noise) displaced by the model itself with
+ *     k = -0.15 (one group), or -0.15 and +0.08 for two cameras taking turns, at the normalised corner radius of the
+ *     image, the focal given 10 % off, 8 steps at cg_iters 10 bring k_g within 7.46e-2 of the planted coefficient (in
+ *     units of it; 1.65e-2 with one group) and s_g within 1.42e-2, and the pooled rms within 7.99e-3 px of the exact
+ *     Levenberg-Marquardt's 0.46 px (MEASURED, the worst of the four scenes; tests/test_bundle_radial_cpu.py, which
+ *     also holds fp32 to float64: 3.12e-2 on k_g, 1.02e-3 on s_g, 1.20e-3 px on the rms).  The focal call on the same
+ *     input ends at 1.30 to 2.09 px.  A scene planted with the forward model x_d = x_u*(1 + k*r_u^2) instead (120 tracks,
+ *     8 images, one group) is left at 0.484 px by this one-parameter inverse model where the focal call leaves 1.09 px.
+ *   - Not done here: one coefficient only (no k2, no tangential terms, no principal point); no prior on k; no check
+ *     that 1 + 3*k*rho2 stays positive over the image (where it does not, the model folds over).  The model is the
+ *     inverse (undistorting) one: a k from a forward-model calibration x_d = x_u*(1 + k*r_u^2) has roughly the opposite
+ *     sign.
+ *   - The argument errors of misift_adjust_bundle_focal_batch; a radial[g] that is not 0 or 1; a k0[g] that is not
+ *     finite; one of radial and k0 NULL without the other; NULL d_radial with ngroups > 0: MISIFT_EINVAL, before anything
+ *     is enqueued.
+ *   - Stream, copies and ordering as misift_adjust_bundle_focal_batch; `radial` and `k0` are copied.  With a grouped image
+ *     and a radial[g] == 1 or a k0[g] != 0: three memsets and 14 + num_loops * (8 + 3 * cg_iters) launches (one more with
+ *     d_obs_weight), launch for launch the focal call's with the d_radial launch at the end.  The column Juk, Jvk is
+ *     stored per slot once per step (8 bytes) beside Juf, Jvf: a per-track pass then reads 8 bytes where recomputing
+ *     would read the 16-byte observation, the image's 16 bytes and sw.  The per-image pass of step 3 holds 52 sums
+ *     (52 KiB of LDS).  Temp: 116 bytes per slot, 140 per track and 444 per image, each array rounded up to 16, and 640
+ *     bytes for the groups. */
+#define MISIFT_MAX_RADIAL_GROUPS MISIFT_MAX_FOCAL_GROUPS
+#define MISIFT_RADIAL_REFINED 0
+#define MISIFT_RADIAL_NO_MEMBER 1
+#define MISIFT_RADIAL_NOT_REFINED 2
+#define MISIFT_RADIAL_HELD 3
+int misift_adjust_bundle_radial_batch(misift_ctx *ctx,
+                                      int max_tracks, int max_obs,
+                                      const int *d_track_offsets,     /* max_tracks + 1, from export */
+                                      const misift_track_obs *d_obs,  /* max_obs, from export, 16-byte aligned */
+                                      const int *d_export_summary,    /* 8 ints, from export: [2] = T, [3] = O */
+                                      const float *d_points,          /* max_tracks x 4, from triangulate */
+                                      const int *d_point_status,      /* max_tracks, from triangulate */
+                                      int nimages,
+                                      const float *d_cam,             /* nimages x 12 */
+                                      const int *d_cam_pair,          /* nimages */
+                                      const float *intrinsics,        /* host, nimages x 4: fx fy cx cy, copied */
+                                      int nhold, const int *hold,     /* host, images kept as they are, copied; may be NULL */
+                                      int min_views, int min_obs, int num_loops, int cg_iters,
+                                      float max_error, float lambda0, int orthonormalise,
+                                      int loss, float loss_scale /* px */,
+                                      int ngroups, const int *group,  /* host, nimages: the group of the image or -1, copied */
+                                      const int *radial,              /* host, ngroups: 1 = k_g is an unknown, copied; may be NULL */
+                                      const float *k0,                /* host, ngroups: k_g at the start, copied; NULL with radial */
+                                      float *d_cam_out,               /* nimages x 12; may be d_cam itself */
+                                      float *d_points_out,            /* max_tracks x 4; may be d_points itself */
+                                      int   *d_cam_obs,               /* nimages */
+                                      int   *d_cam_status,            /* nimages */
+                                      float *d_cam_rms,               /* nimages x 2: before, after */
+                                      int   *d_point_obs,             /* max_tracks */
+                                      float *d_history,               /* num_loops x 4 words */
+                                      float *d_cost,                  /* 2: before, after */
+                                      float *d_obs_weight,            /* max_obs; may be NULL */
+                                      int   *d_summary,               /* 8 ints */
+                                      float *d_intrinsics_out,        /* nimages x 4 */
+                                      int   *d_focal,                 /* ngroups x 3 words: s_g, M_g, status */
+                                      float *d_radial);               /* ngroups x 3 words: k_g, M_g, status */
+
+/* An observation list undistorted under THE RADIAL MODEL above with the coefficients misift_adjust_bundle_radial_batch
+ * left on the device (no reference counterpart): ... -> refine -> adjust_bundle_radial -> undistort_obs -> triangulate /
+ * filter / adjust / resect on the undistorted list with d_intrinsics_out, all of them pinhole and unchanged.
+ *   For every slot o < min(max(O, 0), max_obs), with O read on the device from d_export_summary[3]: frame and record
+ *   are copied; xpos, ypos become x', y' under k = d_radial[3g] (whatever the group's status) when the frame lies in
+ *   [0, nimages) and g = group[frame] >= 0, otherwise they are copied bit for bit.  Slots from O on are untouched.
+ *   `intrinsics` are the GIVEN ones, those the radial call was given.  ngroups == 0: every slot is copied.
+ *   - d_obs_out may be d_obs itself; any other overlap, a d_obs or d_obs_out that is not 16-byte aligned, NULL d_obs,
+ *     d_export_summary, intrinsics or d_obs_out, NULL group or d_radial with ngroups > 0, max_obs or nimages < 1,
+ *     ngroups outside 0 ... MISIFT_MAX_RADIAL_GROUPS, a group[i] outside [-1, ngroups), unusable intrinsics:
+ *     MISIFT_EINVAL, before anything is enqueued.
+ *   - One launch on the context stream, one lane per slot, one 16-byte load and one 16-byte store; no temp memory, no
+ *     host read; `intrinsics` and `group` are copied. */
+int misift_undistort_obs_batch(misift_ctx *ctx,
+                               int max_obs,
+                               const misift_track_obs *d_obs,         /* max_obs, 16-byte aligned */
+                               const int *d_export_summary,           /* 8 ints, from export: [3] = O */
+                               int nimages,
+                               const float *intrinsics,               /* host, nimages x 4, the given ones, copied */
+                               int ngroups, const int *group,         /* host, nimages, copied */
+                               const float *d_radial,                 /* ngroups x 3 words, from the radial call */
+                               misift_track_obs *d_obs_out);          /* max_obs; may be d_obs itself */
+
 /* The observation lists of misift_export_tracks_batch gated against the current points and cameras and written out
  * again, compact and in export's own format (no reference counterpart): per observation the reprojection error, per
  * track the duplicate frames, the number of views and the triangulation angle.  It is what "gate on d_obs_error and call
@@ -2310,6 +2456,19 @@ int misift_test_adjust_bundle_focal(int max_tracks, int max_obs, const int *trac
                                     int ngroups, const int *group, float *cam_out, float *points_out, int *cam_obs,
                                     int *cam_status, float *cam_rms, int *point_obs, float *history, float *cost,
                                     float *obs_weight, int *summary, float *intrinsics_out, int *focal);
+/* The same for misift_adjust_bundle_radial_batch, and misift_undistort_obs_batch on host arrays. */
+int misift_test_adjust_bundle_radial(int max_tracks, int max_obs, const int *track_offsets, const misift_track_obs *obs,
+                                     const int *export_summary, const float *points, const int *point_status,
+                                     int nimages, const float *cam, const int *cam_pair, const float *intrinsics,
+                                     int nhold, const int *hold, int min_views, int min_obs, int num_loops, int cg_iters,
+                                     float max_error, float lambda0, int orthonormalise, int loss, float loss_scale,
+                                     int ngroups, const int *group, const int *radial, const float *k0, float *cam_out,
+                                     float *points_out, int *cam_obs, int *cam_status, float *cam_rms, int *point_obs,
+                                     float *history, float *cost, float *obs_weight, int *summary, float *intrinsics_out,
+                                     int *focal, float *radial_out);
+int misift_test_undistort_obs(int max_obs, const misift_track_obs *obs, const int *export_summary, int nimages,
+                              const float *intrinsics, int ngroups, const int *group, const float *radial,
+                              misift_track_obs *obs_out);
 
 /* Test-only, host-only: the whole of misift_filter_tracks_batch on host arrays, every rule compiled from the function
  * its kernels run (filter_core.hpp).  The arguments are those of the call without the context; all pointers are host;

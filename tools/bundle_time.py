@@ -19,6 +19,13 @@ it there.
 --focal times misift_adjust_bundle_focal_batch instead: the plain call, the new call with ngroups 0 (which must give the
 plain call's bytes), with all images in one group and with the images dealt to eight groups, the focal given 10 % long
 (both compared with their restatement, tests/bundle_focal_cases.expected_focal), taking turns, for one step and for --num-loops.
+--radial times misift_adjust_bundle_radial_batch instead: the plain call, the focal call with all images in one group, the
+new call on the same input with nothing radial (which must give the focal call's bytes and launches its kernels), with the
+one group's coefficient an unknown and with the images dealt to eight groups, all unknown, the observations displaced by a
+planted lens (one group compared with its restatement, tests/bundle_radial_cases.expected_radial), taking turns, for one
+step and for --num-loops; then misift_undistort_obs_batch beside the device-to-host copy of the observation list it saves.
+--parent-json FILE (with --radial) takes the JSON that `bundle_time.py --focal --out FILE` of the parent commit wrote in a
+process of its own and puts its one-group figures beside these under "parent_focal_call_in_its_own_process".
 --losses times misift_adjust_bundle_robust_batch instead of (a) and (b): the plain call, loss 0 through the new call,
 Huber at --huber px and Geman-McClure at --geman-mcclure px without d_obs_weight, and Huber with it (one launch more),
 each at num_loops 1 and --num-loops, cg_iters --cg-iters.  The ten take turns within every repetition in one process.  The
@@ -29,6 +36,7 @@ import ctypes as C
 import json
 import os
 import sys
+import time
 
 import numpy as np
 
@@ -39,6 +47,7 @@ from cudasift_amd import capi  # noqa: E402
 import bench_common  # noqa: E402,F401  (puts tests/ on the path)
 import bundle_cases as BC  # noqa: E402
 import bundle_focal_cases as BF  # noqa: E402
+import bundle_radial_cases as BD  # noqa: E402
 import bundle_robust_cases as BR  # noqa: E402
 import pose_cases as PC  # noqa: E402
 import posegraph_cases as G  # noqa: E402
@@ -63,6 +72,8 @@ def main():
     ap.add_argument("--reps", type=int, default=40)
     ap.add_argument("--losses", action="store_true")
     ap.add_argument("--focal", action="store_true")
+    ap.add_argument("--radial", action="store_true")
+    ap.add_argument("--parent-json", default="")
     ap.add_argument("--huber", type=float, default=2.0)
     ap.add_argument("--geman-mcclure", type=float, default=4.0)
     ap.add_argument("--out", default="")
@@ -223,6 +234,99 @@ def main():
             r["ratios_loops%d" % loops] = {"groups0_vs_plain": round(r[key % "groups0"] / r[key % "plain"], 4),
                                            "group1_vs_plain": round(r[key % "group1"] / r[key % "plain"], 4),
                                            "groups8_vs_plain": round(r[key % "groups8"] / r[key % "plain"], 4)}
+        print(json.dumps(r), flush=True)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                json.dump(r, f, indent=1)
+        ctx.close()
+        return
+    if a.radial:
+        # misift_adjust_bundle_radial_batch: the given fx, fy 10 % long as under --focal, the observations displaced by a
+        # lens of 5 % at the image corner; the five variants take turns
+        Kf = K.copy()
+        Kf[:, :2] *= np.float32(1.1)
+        groups = {1: np.zeros(nf, np.int32), BD.MAX_GROUPS: (np.arange(nf) % BD.MAX_GROUPS).astype(np.int32)}
+        kplant = BD.corner_k(dict(intrinsics=K), -0.05)
+        lens = BD.distort_obs(dict(case, group=groups[1]), [kplant])["obs"]
+        dlens = ctx.upload(lens)
+        dk, dfocal, dradial = ctx.zeros(16 * nf), ctx.zeros(12 * BD.MAX_GROUPS), ctx.zeros(12 * BD.MAX_GROUPS)
+
+        def focal_adjust(num_loops):
+            ctx.adjust_bundle_focal_batch(max_tracks, max_obs, doff, dlens, dsum, dpts, dstatus, nf, dcam, dcam_pair, Kf,
+                                          groups[1], ngroups=1, hold=hold, num_loops=num_loops, cg_iters=a.cg_iters,
+                                          loss=BR.NONE, intrinsics_out=dk, focal=dfocal, **args, **outs)
+
+        def radial_adjust(num_loops, ngroups, on):
+            ctx.adjust_bundle_radial_batch(max_tracks, max_obs, doff, dlens, dsum, dpts, dstatus, nf, dcam, dcam_pair, Kf,
+                                           groups[ngroups], ngroups=ngroups, radial=[on] * ngroups, k0=[0.0] * ngroups,
+                                           hold=hold, num_loops=num_loops, cg_iters=a.cg_iters, loss=BR.NONE,
+                                           intrinsics_out=dk, focal=dfocal, radial_out=dradial, **args, **outs)
+
+        def words():
+            got = {k: ctx.download(outs[k], (sizes[k],), np.uint32).tobytes() for k in BC.OUTPUTS}
+            got["intrinsics_out"] = ctx.download(dk, (4 * nf,), np.uint32).tobytes()
+            got["focal"] = ctx.download(dfocal, (3,), np.uint32).tobytes()
+            return got
+
+        focal_adjust(a.num_loops)
+        ctx.sync()
+        foc = words()
+        radial_adjust(a.num_loops, 1, 0)
+        ctx.sync()
+        assert words() == foc, "nothing radial: not the focal call's bytes"
+        radial_adjust(a.num_loops, 1, 1)
+        ctx.sync()
+        x = BD.expected_radial(BD.radial(BF.focal(dict(case, obs=lens, intrinsics=Kf), groups[1], 1), [1], [0.0]))
+        for k in BC.OUTPUTS:
+            assert ctx.download(outs[k], (sizes[k],), np.uint32).tobytes() == x[k].tobytes(), k
+        assert ctx.download(dk, (4 * nf,), np.uint32).tobytes() == x["intrinsics_out"].tobytes()
+        assert ctx.download(dradial, (3,), np.uint32).tobytes() == x["radial_out"].tobytes()
+        r["radial"] = {"given_focal_factor": 1.1, "planted_k": round(float(kplant), 6), "cg_iters": a.cg_iters,
+                       "group1": {"k": round(float(x["res"]["coef"][0]), 6), "scale": round(float(x["res"]["scale"][0]), 6),
+                                  "steps": x["res"]["trace"], "rms_px_after": round(BD.pooled_rms(x["res"]), 4)}}
+        variants = (("plain", lambda loops: adjust(loops, a.cg_iters)), ("focal", focal_adjust),
+                    ("radial_none", lambda loops: radial_adjust(loops, 1, 0)),
+                    ("radial_group1", lambda loops: radial_adjust(loops, 1, 1)),
+                    ("radial_groups8", lambda loops: radial_adjust(loops, BD.MAX_GROUPS, 1)))
+        names = ["adjust_%s_loops%d_cg%d_events_ms" % (v[0], loops, a.cg_iters) for loops in (1, a.num_loops)
+                 for v in variants]
+        times = {k: [] for k in names}
+        dund = ctx.zeros(16 * max_obs)
+        und, d2h = [], []
+        for rep in range(a.warmup + a.reps):
+            t = [events(lambda: v[1](loops)) for loops in (1, a.num_loops) for v in variants]
+            u = events(lambda: ctx.undistort_obs_batch(max_obs, dlens, dsum, nf, Kf, groups[1], dradial, ngroups=1,
+                                                       obs_out=dund))
+            ctx.sync()
+            t0 = time.perf_counter()                             # a synchronous copy: the host's clock around it
+            ctx.download(dlens, (max_obs,), TC.OBS_DTYPE)
+            c = 1e3 * (time.perf_counter() - t0)
+            if rep >= a.warmup:
+                for k, v in zip(names, t):
+                    times[k].append(v)
+                und.append(u)
+                d2h.append(c)
+        times["undistort_obs_events_ms"], times["obs_list_to_host_wall_ms"] = und, d2h
+        percentiles(r, times)
+        r["kernels_ms"], r["launches_per_call"] = {}, {}
+        for v in variants:
+            r["kernels_ms"][v[0]], r["launches_per_call"][v[0]] = launches_of(lambda: v[1](a.num_loops))
+        for loops in (1, a.num_loops):
+            key = "adjust_%%s_loops%d_cg%d_events_ms" % (loops, a.cg_iters)
+            r["ratios_loops%d" % loops] = {"radial_none_vs_focal": round(r[key % "radial_none"] / r[key % "focal"], 4),
+                                           "radial_group1_vs_focal": round(r[key % "radial_group1"] / r[key % "focal"], 4),
+                                           "radial_groups8_vs_focal": round(r[key % "radial_groups8"] / r[key % "focal"], 4)}
+        if a.parent_json:
+            with open(a.parent_json) as f:
+                parent = json.load(f)
+            own = {k: v for k, v in parent.items() if k.startswith("adjust_group1_")}
+            own["kernels_ms"] = parent["kernels_ms"]["group1"]
+            r["parent_focal_call_in_its_own_process"] = own
+            for loops in (1, a.num_loops):
+                lo, hi = own["adjust_group1_loops%d_cg%d_events_p10_p90_ms" % (loops, a.cg_iters)]
+                mine = r["adjust_radial_none_loops%d_cg%d_events_ms" % (loops, a.cg_iters)]
+                r["ratios_loops%d" % loops]["radial_none_within_parent_p10_p90"] = bool(lo <= mine <= hi)
         print(json.dumps(r), flush=True)
         if a.out:
             os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
