@@ -270,6 +270,15 @@ def lib():
     return _lib
 
 
+def hip_runtime():
+    """The HIP runtime libmisift.so is bound to, as a ctypes handle of its own (symbols are looked up through libmisift's
+    dependencies): where raw streams and events that are handed to the library come from.  C.CDLL("libamdhip64.so") can
+    be another runtime: torch bundles one and loads it under that name when it is imported after libmisift, and a stream
+    or event of the one aborts inside the other."""
+    lib()
+    return C.CDLL(LIB_PATH)
+
+
 def check(rc, what=""):
     if rc != 0:
         raise MisiftError("%s failed (rc=%d): %s" % (what, rc, lib().misift_last_error().decode()))
@@ -454,6 +463,11 @@ class Context:
 
     def sync(self):
         check(lib().misift_ctx_sync(self.h), "misift_ctx_sync")
+
+    def set_stream(self, stream):
+        """misift_ctx_set_stream: later calls run on `stream` (a raw hipStream_t value, None for the NULL stream), behind
+        everything enqueued through this context so far; no host wait."""
+        check(lib().misift_ctx_set_stream(self.h, stream), "misift_ctx_set_stream")
 
     # ---- memory helpers
     def upload(self, arr):
@@ -1717,7 +1731,7 @@ class HipEvent:
 
     def __init__(self):
         if HipEvent._hip is None:
-            HipEvent._hip = C.CDLL("libamdhip64.so")
+            HipEvent._hip = hip_runtime()
             HipEvent._hip.hipEventElapsedTime.argtypes = [C.POINTER(C.c_float), C.c_void_p, C.c_void_p]
             HipEvent._hip.hipStreamWaitEvent.argtypes = [C.c_void_p, C.c_void_p, C.c_uint]
             HipEvent._hip.hipEventSynchronize.argtypes = [C.c_void_p]

@@ -117,6 +117,7 @@ struct CtxExtra {
   std::vector<hipEvent_t> lane_done;   // 2K events: done[ticket % 2K] is recorded behind batch `ticket` on its lane's stream
   hipEvent_t ev_in = nullptr;          // recorded on the caller's stream at every call: the lane starts behind it
   hipEvent_t ev_single = nullptr;      // K = 1: misift_ctx_wait_batch records this one on the context stream
+  hipEvent_t ev_switch = nullptr;      // misift_ctx_set_stream: recorded on the old stream, waited for on the new one
   unsigned long long ticket = 0;
   misift_ctx *last_lane = nullptr;     // the pipeline that took the most recent batch (nullptr: the context itself)
   hipEvent_t last_done = nullptr;
@@ -632,6 +633,7 @@ extern "C" void misift_ctx_destroy(misift_ctx *ctx)
   for (hipEvent_t e : x->lane_done) hipEventDestroy(e);
   if (x->ev_in) hipEventDestroy(x->ev_in);
   if (x->ev_single) hipEventDestroy(x->ev_single);
+  if (x->ev_switch) hipEventDestroy(x->ev_switch);
   if (x->gexec) hipGraphExecDestroy(x->gexec);
   if (x->gstream) { hipStreamSynchronize(x->gstream); hipStreamDestroy(x->gstream); }
   if (x->gev_in) hipEventDestroy(x->gev_in);
@@ -674,7 +676,16 @@ extern "C" int misift_ctx_set_graph_replay(misift_ctx *ctx, int on)
 extern "C" int misift_ctx_set_stream(misift_ctx *ctx, void *stream)
 {
   ARG_CHECK(ctx != nullptr);
-  ctx->stream = (hipStream_t)stream;
+  hipStream_t to = (hipStream_t)stream;
+  if (to == ctx->stream) return MISIFT_OK;
+  // The context stays one in-order pipeline: its temp, its pair plan, its pinned ring and its counters are not tied to a
+  // stream, so the new stream starts behind everything enqueued through the context on the old one.  No host wait.
+  CtxExtra *x = extra(ctx);
+  HIP_TRY(hipSetDevice(ctx->device));
+  if (!x->ev_switch) HIP_TRY(hipEventCreateWithFlags(&x->ev_switch, hipEventDisableTiming));
+  HIP_TRY(hipEventRecord(x->ev_switch, ctx->stream));
+  HIP_TRY(hipStreamWaitEvent(to, x->ev_switch, 0));
+  ctx->stream = to;
   return MISIFT_OK;
 }
 

@@ -104,6 +104,15 @@ int misift_ctx_set_graph_replay(misift_ctx *ctx, int on);
  * pinned read-back buffer and the filter tap tables (cudaSiftD.cu:15-17). */
 int misift_ctx_create(int device, void *stream, misift_ctx **out);
 void misift_ctx_destroy(misift_ctx *ctx);
+/* Moves the context to another hipStream_t (NULL = the null stream).  The context stays ONE in-order pipeline across the
+ * switch: its temp memory, its pair plan, its pinned ring of host lists and its counters belong to the context, not to a
+ * stream, so work enqueued through the context after the call starts behind everything enqueued through it before (an
+ * event of the context's is recorded on the old stream and the new stream waits for it).  The call does not wait on the
+ * host, and the caller's old stream may be destroyed once its work is done.  Switching to the stream the context is
+ * already on does nothing.  ctx NULL: MISIFT_EINVAL.  The event is recorded when the call is made, so whatever the
+ * caller itself had put on the old stream by then is waited for as well, and what it puts there afterwards is not.
+ * Out of scope: a switch while misift_ctx_set_batches_in_flight(K > 1) pipelines or a misift_pipe on this context are
+ * active (drain them first), and graph replay (a captured graph belongs to the stream it was captured for). */
 int misift_ctx_set_stream(misift_ctx *ctx, void *stream);
 /* Synchronous calls return at the last kernel's completion flag (1) instead of after a stream synchronisation (0, the
  * default): see misift_extract.  The host polls a word of pinned memory, i.e. it spins a core while it waits. */

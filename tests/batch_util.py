@@ -94,14 +94,14 @@ def same_rows(got, exp, what, fields=None):
 
 
 @contextlib.contextmanager
-def guarded_context(min_checked):
-    """A fresh context on device 0 with every allocation guarded.  When the body ends, check_guards() must find no band
-    damaged and, with min_checked not None, at least that many allocations; then the context is closed and the previous
-    guard mode restored."""
+def guarded_context(min_checked, stream=None):
+    """A fresh context on device 0 (on `stream`, a raw hipStream_t value; None: the NULL stream) with every allocation
+    guarded.  When the body ends, check_guards() must find no band damaged and, with min_checked not None, at least that
+    many allocations; then the context is closed and the previous guard mode restored."""
     from cudasift_amd import capi
     old = capi.set_guard(True)
     try:
-        g = capi.Context(0)
+        g = capi.Context(0, stream)
         try:
             yield g
             n = capi.check_guards()

@@ -984,7 +984,7 @@ def test_batches_in_flight_inside_one_context(ctx):
         # misift_ctx_wait_batch: a copy on the caller's own stream ordered behind the most recent batch
         import ctypes as C
         side = C.c_void_p()
-        hip = C.CDLL("libamdhip64.so")
+        hip = capi.hip_runtime()                      # the runtime the library is bound to: `side` is handed to it
         assert hip.hipStreamCreateWithFlags(C.byref(side), 1) == 0
         probe = ctx.zeros(4 * (2 * B + 1))
         capi.check(capi.lib().misift_extract_batch_packed_async(

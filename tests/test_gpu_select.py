@@ -21,9 +21,7 @@ def gctx():
         yield g
 
 
-def sizes_of(case):
-    n, top, mp = len(case["counts"]), case["top"], case["max_pairs"]
-    return dict(zip(SC.OUTPUTS, (n * top, n, n * n, 2 * mp, mp, 8)))
+sizes_of, tmp_bytes, SelectStep = U.select_sizes, U.select_tmp_bytes, U.SelectStep         # in the form of used_context.py
 
 
 def upload(ctx, case):
@@ -87,42 +85,6 @@ def test_guards_stay_intact_at_the_largest_shapes():
 
 
 # ---- a context other calls have used
-
-def align16(v):
-    return (v + 15) // 16 * 16
-
-
-def tmp_bytes(case):
-    """include/misift.h: the gathered descriptors, the keep flags, 24 bytes per frame, each part rounded up to 16, and
-    16."""
-    n, hp = len(case["counts"]), (case["top"] + 31) // 32 * 32
-    return align16(n * hp * 128) + align16(n * n) + 16 * n + 2 * align16(4 * n) + 16
-
-
-class SelectStep(U.Step):
-    """misift_select_pairs_batch in the form of used_context.py: a call that hands the library no host list."""
-    name = "select_pairs_batch"
-    carries_lists = False
-    CASES = dict(small="ring_small", large="frames_65_top33")
-
-    def build(self, size):
-        return SC.all_cases()[self.CASES[size]]
-
-    def uploads(self, case):
-        return {k: case[k] for k in INPUTS if case[k] is not None}
-
-    def outputs(self, case):
-        return {k: U.poisoned(w) for k, w in sizes_of(case).items()}
-
-    def enqueue(self, ctx, case, dev, lists):
-        enqueue(ctx, case, dict(dev, offs=dev.get("offs")))
-
-    def expected(self, case, lists):
-        return SC.expected(case)
-
-    def tmp_bytes(self, case, ncu):
-        return tmp_bytes(case)
-
 
 def test_on_a_context_other_calls_have_used():
     """Between calls that leave the shared temp full of their own partials, keys and labels: large, small, large again,

@@ -13,6 +13,9 @@ restatement; what is new is only the form: every step gives, per size,
   expected(case, lists) name -> the bytes of every device buffer the call writes (outputs, and inputs refined in place)
   tmp_bytes(case, ncu)  the bytes of the context's shared temp the call asks for
 and check() holds every device buffer to expected(), or to what was uploaded where the call must not write.
+zeroed(case) is the case with every device input zero-filled: what a call that ran too early would have been given
+(stream_util.py).  table() holds the 14 calls test_gpu_used_context.py sizes its plans from; stream_table() is table()
+and, at `small` only and without tmp_bytes(), the further batch calls the caller-stream tests run.
 
 Sizes.  `small` is the smallest case of the call's own tests that still runs every launch, off the multiples of 16;
 `large` is a few times that in every dimension that sizes temp.  `huge` asks for more temp than any other step at
@@ -64,6 +67,7 @@ class Step:
     no_huge = None                                               # for a step without `huge`: the reason
     temp = True                                                  # uses the shared temp
     carries_lists = True                                         # hands the library a host list
+    takes_slot = True                                            # takes a slot of the pinned ring (with or without a list)
 
     def __init__(self):
         self._cases, self._expected = {}, {}
@@ -79,6 +83,15 @@ class Step:
 
     def other_lists(self, case):
         return {}
+
+    def zeroed(self, case):
+        """The case with every device input zero-filled and the host lists as they are: what a call that ran before its
+        inputs were staged would have been given.  expected(zeroed(case), lists) is what it would have written."""
+        out = {k: v for k, v in case.items() if not k.startswith("memo")}
+        for k, v in self.uploads(case).items():
+            assert k in case, (self.name, k)
+            out[k] = np.zeros_like(np.ascontiguousarray(v))
+        return out
 
     def expected_for(self, size, lists=None):
         """expected() of the case of `size` under `lists` (default: its own), computed once per content of the lists."""
@@ -677,6 +690,9 @@ class RecoverPose(Step):
     def uploads(self, case):
         return {k: case[k] for k in ("recs", "counts", "offs", "F")}
 
+    def zeroed(self, case):
+        return dict(Step.zeroed(self, case), fr=[np.zeros_like(p) for p in case["fr"]])
+
     def outputs(self, case):
         ns = len(case["sel"])
         return dict(pose=poisoned(12 * ns), num_front=poisoned(ns), votes=poisoned(4 * ns),
@@ -871,7 +887,512 @@ class FindHomography(Step):
         return _search_tmp(len(case["sel"]), case["max_pts"], case["loops"], 4 + 8)
 
 
-# ---- the table
+# ---- the calls only stream_table() holds: `small` alone, and no tmp_bytes() (the stream tests assert only that the temp
+# does not change).  Their host lists (intrinsics, hold, group, ranges, seeds, frames) are arguments of the case, handed
+# over as the case holds them: carries_lists is False and lists() empty.
+
+def select_sizes(case):
+    import select_cases as SC
+    n, top, mp = len(case["counts"]), case["top"], case["max_pairs"]
+    return dict(zip(SC.OUTPUTS, (n * top, n, n * n, 2 * mp, mp, 8)))
+
+
+def select_tmp_bytes(case):
+    """include/misift.h: the gathered descriptors, the keep flags, 24 bytes per frame, each part rounded up to 16, and
+    16."""
+    n, hp = len(case["counts"]), (case["top"] + 31) // 32 * 32
+    return align16(n * hp * 128) + align16(n * n) + 16 * n + 2 * align16(4 * n) + 16
+
+
+class SelectStep(Step):
+    """misift_select_pairs_batch: a call that hands the library no host list."""
+    name = "select_pairs_batch"
+    carries_lists = False
+    CASES = dict(small="ring_small", large="frames_65_top33")
+    INPUTS = ("recs", "q", "counts", "offs")
+
+    def build(self, size):
+        import select_cases as SC
+        return SC.all_cases()[self.CASES[size]]
+
+    def uploads(self, case):
+        return {k: case[k] for k in self.INPUTS if case[k] is not None}
+
+    def zeroed(self, case):
+        return dict(Step.zeroed(self, case), memo={})            # select_cases shares stage 1 and 2 among variants
+
+    def outputs(self, case):
+        return {k: poisoned(w) for k, w in select_sizes(case).items()}
+
+    def enqueue(self, ctx, case, dev, lists):
+        import select_cases as SC
+        ctx.select_pairs_batch(dev["recs"], dev["q"], len(case["counts"]), dev["counts"], dev.get("offs"), case["stride"],
+                               **{k: case[k] for k in SC.ARGS}, **{k: dev[k] for k in SC.OUTPUTS})
+
+    def expected(self, case, lists):
+        import select_cases as SC
+        return SC.expected(case)
+
+    def tmp_bytes(self, case, ncu):
+        return select_tmp_bytes(case)
+
+
+class _Small(Step):
+    sizes = ("small",)
+    carries_lists = False
+    no_huge = "not in table(): the stream tests hold the temp to what it was"
+
+
+def _without(e, *keys):
+    return {k: v for k, v in e.items() if k not in keys}
+
+
+class Bundle(_Small):
+    """The four bundle adjusters on one planted scene of 4 images and 40 tracks, 2 steps of 4 CG iterations: plain, under
+    a Huber loss, with one focal group, with one radial group."""
+    CALLS = dict(plain="adjust_bundle_batch", robust="adjust_bundle_robust_batch", focal="adjust_bundle_focal_batch",
+                 radial="adjust_bundle_radial_batch")
+    KW = ("hold", "min_views", "min_obs", "num_loops", "cg_iters", "max_error", "lambda0", "orthonormalise")
+
+    def __init__(self, kind):
+        super().__init__()
+        self.kind, self.name = kind, self.CALLS[kind]
+
+    def mod(self):
+        import bundle_cases as BC
+        import bundle_focal_cases as BF
+        import bundle_radial_cases as BD
+        import bundle_robust_cases as BR
+        return dict(plain=BC, robust=BR, focal=BF, radial=BD)[self.kind]
+
+    def build(self, size):
+        import bundle_cases as BC
+        import bundle_focal_cases as BF
+        import bundle_radial_cases as BD
+        import bundle_robust_cases as BR
+        base = BC.planted(40, 4, 1, num_loops=2, cg_iters=4)["case"]
+        return dict(plain=lambda: base, robust=lambda: BR.robust(base, BR.HUBER, 2.0), focal=lambda: BF.one_group(base),
+                    radial=lambda: BD.one_group(base))[self.kind]()
+
+    def uploads(self, case):
+        import filter_cases as FC
+        return FC.inputs(case)
+
+    def outputs(self, case):
+        return {k: poisoned(n) for k, n in self.mod().sizes(case).items()}
+
+    def enqueue(self, ctx, case, dev, lists):
+        args = (case["max_tracks"], case["max_obs"], dev["track_offsets"], dev["obs"], dev["export_summary"], dev["points"],
+                dev["point_status"], case["nimages"], dev["cam"], dev["cam_pair"], case["intrinsics"])
+        kw = dict({k: case[k] for k in self.KW}, **{k: dev[k] for k in self.mod().OUTPUTS})
+        if self.kind == "plain":
+            return ctx.adjust_bundle_batch(*args, **kw)
+        kw.update(loss=case["loss"], loss_scale=case["loss_scale"])
+        if self.kind == "robust":
+            return ctx.adjust_bundle_robust_batch(*args, **kw)
+        if self.kind == "focal":
+            return ctx.adjust_bundle_focal_batch(*args, case["group"], ngroups=case["ngroups"], **kw)
+        return ctx.adjust_bundle_radial_batch(*args, case["group"], ngroups=case["ngroups"], radial=case.get("radial"),
+                                              k0=case.get("k0"), **kw)
+
+    def expected(self, case, lists):
+        m = self.mod()
+        e = getattr(m, dict(plain="expected_bundle", robust="expected_bundle", focal="expected_focal",
+                            radial="expected_radial")[self.kind])(case)
+        return {k: e[k] for k in m.OUTPUTS}
+
+
+class FilterTracks(_Small):
+    """misift_filter_tracks_batch on tracks of 2 to 17 views over 8 images (beyond 8 views a track holds duplicates) under
+    an error gate of 2 px."""
+    name = "filter_tracks_batch"
+
+    def build(self, size):
+        import filter_cases as FC
+        return FC.lengths_case((2, 3, 4, 9, 17, 5, 2, 8), max_error=2.0)
+
+    def uploads(self, case):
+        import filter_cases as FC
+        return FC.inputs(case)
+
+    def outputs(self, case):
+        import filter_cases as FC
+        return {k: poisoned(n) for k, n in FC.sizes(case).items()}
+
+    def enqueue(self, ctx, case, dev, lists):
+        import filter_cases as FC
+        ctx.filter_tracks_batch(case["max_tracks"], case["max_obs"], dev["track_offsets"], dev["obs"], dev["export_summary"],
+                                dev["points"], dev["point_status"], case["nimages"], dev["cam"], dev["cam_pair"],
+                                case["intrinsics"], **{k: case[k] for k in FC.ARGS}, **{k: dev[k] for k in FC.OUTPUTS})
+
+    def expected(self, case, lists):
+        import filter_cases as FC
+        return _without(FC.expected_filter(case), "res")
+
+
+class CorrespondTracks(_Small):
+    """misift_correspond_tracks_batch: 40 tracks of A against the tracks B makes of every second record, shifted by 5."""
+    name = "correspond_tracks_batch"
+    KEYS = ("record_obs", "track_offsets", "export_summary")
+
+    def build(self, size):
+        import align_cases as AC
+        return AC.correspond_cases()["shift +5"]
+
+    def uploads(self, case):
+        return {s + "_" + k: i32(case[s][k]) for s in "ab" for k in self.KEYS}
+
+    def zeroed(self, case):
+        return dict(case, **{s: dict(case[s], **{k: np.zeros_like(i32(case[s][k])) for k in self.KEYS}) for s in "ab"})
+
+    def outputs(self, case):
+        return dict(track_map=poisoned(case["a"]["max_tracks"]), summary=poisoned(8))
+
+    def enqueue(self, ctx, case, dev, lists):
+        A, B = case["a"], case["b"]
+        ctx.correspond_tracks_batch(A["max_records"], dev["a_record_obs"], A["max_tracks"], A["max_obs"],
+                                    dev["a_track_offsets"], dev["a_export_summary"], B["max_records"], dev["b_record_obs"],
+                                    B["max_tracks"], B["max_obs"], dev["b_track_offsets"], dev["b_export_summary"],
+                                    shift=case["shift"], track_map=dev["track_map"], summary=dev["summary"])
+
+    def expected(self, case, lists):
+        import align_cases as AC
+        e = AC.expected_correspond(case)
+        return dict(track_map=e["map"], summary=e["summary"])
+
+
+class AlignPoints(_Small):
+    """misift_align_points_batch on four entries that end in status 0, 1, 2 and 0, each with its own dst_first."""
+    name = "align_points_batch"
+    INPUTS = ("src", "dst", "map", "src_status", "dst_status", "count")
+
+    def build(self, size):
+        import align_cases as AC
+        return AC.gpu_cases()["four entries"]
+
+    def uploads(self, case):
+        return {k: np.ascontiguousarray(case[k], f32 if k in ("src", "dst") else np.int32) for k in self.INPUTS
+                if case.get(k) is not None}
+
+    def outputs(self, case):
+        n = len(case["ranges"])
+        return dict(sim=poisoned(16 * n), align_cand=poisoned(n), align_inliers=poisoned(n), align_status=poisoned(n),
+                    summary=poisoned(8), inlier=poisoned(len(case["map"])))
+
+    def enqueue(self, ctx, case, dev, lists):
+        ctx.align_points_batch(dev["src"], dev["dst"], dev["map"], case["ranges"], case["seeds"],
+                               src_status=dev.get("src_status"), dst_status=dev.get("dst_status"), count=dev.get("count"),
+                               count_stride=case["count_stride"], num_loops=case["num_loops"], thresh=case["thresh"],
+                               min_inliers=case["min_inliers"], refit_loops=case["refit_loops"],
+                               **{k: dev[k] for k in self.outputs(case)})
+
+    def expected(self, case, lists):
+        import align_cases as AC
+        return _without(AC.expected_align(AC.variant(case)), "entries")
+
+
+class TransformScene(_Small):
+    """misift_transform_scene_batch under a status word of 0: unset and root cameras, failed points, tracks behind T."""
+    name = "transform_scene_batch"
+
+    def build(self, size):
+        import align_cases as AC
+        return AC.transform_case()
+
+    def uploads(self, case):
+        return dict(sim=np.ascontiguousarray(case["sim"], f32), sim_status=i32([case["sim_status"]]),
+                    export_summary=i32(case["export_summary"]), points=np.ascontiguousarray(case["points"], f32),
+                    point_status=i32(case["point_status"]), cam=np.ascontiguousarray(case["cam"], f32),
+                    cam_pair=i32(case["cam_pair"]))
+
+    def zeroed(self, case):
+        return dict(Step.zeroed(self, case), sim_status=0)
+
+    def outputs(self, case):
+        return dict(points_out=poisoned(4 * case["max_tracks"]), cam_out=poisoned(12 * case["nimages"]))
+
+    def enqueue(self, ctx, case, dev, lists):
+        ctx.transform_scene_batch(dev["sim"], case["max_tracks"], dev["export_summary"], dev["points"], dev["point_status"],
+                                  case["nimages"], dev["cam"], dev["cam_pair"], sim_status=dev["sim_status"],
+                                  points_out=dev["points_out"], cam_out=dev["cam_out"])
+
+    def expected(self, case, lists):
+        import align_cases as AC
+        return AC.expected_transform(case)
+
+
+class MergeScenes(_Small):
+    """misift_merge_scenes_batch on two windows of 63 and 65 tracks over one world, every optional output wanted."""
+    name = "merge_scenes_batch"
+
+    def build(self, size):
+        import merge_cases as MC
+        case = MC.gpu_cases()["T 63 65"]
+        assert all(case["want"].values())
+        return case
+
+    def uploads(self, case):
+        import merge_cases as MC
+        ins = MC.inputs(case)
+        ups = {s + "_" + k: v for s in "ab" for k, v in ins[s].items() if v is not None}
+        ups["map"] = ins["map"]
+        if ins["accept"] is not None:
+            ups["accept"] = ins["accept"]
+        return ups
+
+    def zeroed(self, case):
+        import merge_cases as MC
+        ins = MC.inputs(case)
+        out = dict(case, map=np.zeros_like(ins["map"]))
+        for s in "ab":
+            out[s] = dict(case[s], **{k: np.zeros_like(v) for k, v in ins[s].items() if v is not None})
+        if ins["accept"] is not None:
+            out["accept"] = np.zeros_like(ins["accept"])
+        return out
+
+    def outputs(self, case):
+        import merge_cases as MC
+        return {k: poisoned(n) for k, n in MC.sizes(case).items()}
+
+    def enqueue(self, ctx, case, dev, lists):
+        import merge_cases as MC
+        from cudasift_amd import capi
+
+        def scene(s):
+            S = case[s]
+            d = {k: dev.get(s + "_" + k) for k in capi.MERGE_SCENE_KEYS}
+            return dict(d, max_tracks=S["max_tracks"], max_obs=S["max_obs"], nimages=S["nimages"],
+                        max_records=int(S.get("max_records") or 0))
+
+        ctx.merge_scenes_batch(scene("a"), scene("b"), dev["map"], case["nimages_out"], case["max_tracks_out"],
+                               case["max_obs_out"], accept=dev.get("accept"), fshift_a=case["fshift_a"],
+                               fshift_b=case["fshift_b"], rshift_a=case["rshift_a"], rshift_b=case["rshift_b"],
+                               max_records_out=case["max_records_out"], **{k: dev[k] for k in MC.OUTPUTS})
+
+    def expected(self, case, lists):
+        import merge_cases as MC
+        return _without(MC.expected_merge(case), "res")
+
+
+class RecoverPosePlanar(_Small):
+    """misift_recover_pose_planar_batch without F, min_inliers 4: frames of count -1, 0, 3 (below min_inliers), 65 and 257
+    records of planted planar scenes, a frame that is in no entry, the entries not in frame order."""
+    name = "recover_pose_planar_batch"
+    temp = False
+    SHAPE = ([40, 0, 3, 65, 30, 257], [5, 0, 3, 1, 2])
+    KW = dict(min_inliers=4)
+
+    def build(self, size):
+        import pose_cases as PC
+        import pose_planar_cases as PP
+        sizes, sel = self.SHAPE
+        fr, H, K = [], [], []
+        for f, n in enumerate(sizes):
+            s = PP.planar_scene(seed=300 + f, n=max(n, 8), baseline=0.5 if f % 2 else 0.1, off=0.1,
+                                k2=PC.K_B if f % 2 else PC.K_A)
+            fr.append(PC.records(s["xy"], 300 + f, fail=0.1 if n >= 10 else 0.0)[:n])
+            H.append(s["H"])
+            K.append(s["K8"])
+        counts = [-1] + sizes[1:]
+        recs, offs, _ = layout(fr, counts, False, min_stride=0, pad_error=-7.0)
+        return dict(recs=recs, counts=i32(counts), offs=offs, sel=i32(sel), fr=fr,
+                    H=np.ascontiguousarray(np.stack([H[f] for f in sel]), f32).reshape(-1, 9),
+                    K=np.ascontiguousarray(np.stack([K[f] for f in sel]), f32).reshape(-1, 8))
+
+    def uploads(self, case):
+        return {k: case[k] for k in ("recs", "counts", "offs", "H")}
+
+    def zeroed(self, case):
+        return dict(Step.zeroed(self, case), fr=[np.zeros_like(p) for p in case["fr"]])
+
+    def sizes_of(self, case):
+        ns = len(case["sel"])
+        return dict(model=ns, hf=2 * ns, pose=12 * ns, num_front=ns, votes=4 * ns, xyz=4 * len(case["recs"]),
+                    pose_alt=12 * ns, plane=4 * ns)
+
+    def outputs(self, case):
+        return {k: poisoned(n) for k, n in self.sizes_of(case).items()}
+
+    def enqueue(self, ctx, case, dev, lists):
+        import pose_planar_cases as PP
+        ctx.recover_pose_planar_batch(case["sel"], case["K"], dev["recs"], len(case["counts"]), dev["counts"], dev["H"],
+                                      None, dev["offs"], 0, model=dev["model"], hf_counts=dev["hf"], pose=dev["pose"],
+                                      num_front=dev["num_front"], votes=dev["votes"], xyz=dev["xyz"],
+                                      pose_alt=dev["pose_alt"], plane=dev["plane"], min_score=GATES[0],
+                                      max_ambiguity=GATES[1], **dict(PP.PARAMS, **self.KW))
+
+    def expected(self, case, lists):
+        import pose_planar_cases as PP
+        sel, ns = case["sel"].tolist(), len(case["sel"])
+        exp = [PP.expected_planar(case["fr"][f], int(case["counts"][f]), case["H"][i], None, case["K"][i], **self.KW)
+               for i, f in enumerate(sel)]
+        want = dict(model=np.array([e["model"] for e in exp], np.int32).view(np.uint32),
+                    hf=np.stack([e["hf"] for e in exp]).reshape(-1).view(np.uint32))
+        for k, n in self.sizes_of(case).items():
+            if k not in want:
+                want[k] = np.full(n, POISON_WORD, np.uint32).reshape(ns if k != "xyz" else len(case["recs"]), -1)
+        for i, (f, e) in enumerate(zip(sel, exp)):
+            if e["model"] <= 0:                                  # general or invalid: everything keeps the poison
+                continue
+            for k in ("pose", "pose_alt", "plane"):
+                want[k][i] = e[k].astype(f32).view(np.uint32)
+            want["num_front"][i] = e["num_front"]
+            want["votes"][i] = e["votes"].view(np.uint32)
+            want["xyz"][span(case["offs"], 0, f, max(int(case["counts"][f]), 0))] = e["xyz"].view(np.uint32)
+        return {k: v.reshape(-1) for k, v in want.items()}
+
+
+class MatchBatch(_Small):
+    """misift_match_batch (the set-1 records written in place) under the context's default options, and
+    misift_match_batch_i8 on descriptors quantised on the host: five frames of set 1, one of them empty and one of count
+    -1, each against a frame of set 2; a set-2 frame below the 32 columns of the reference's sweep."""
+    SHAPES = ([130, 33, 64, 0, 77, 20], [70, 129, 31, 64, 0])
+    PAIRS = [(0, 1), (1, 2), (2, 3), (3, 0), (4, 4), (5, 1)]
+
+    def __init__(self, i8):
+        super().__init__()
+        self.i8, self.name = i8, "match_batch_i8" if i8 else "match_batch"
+
+    def build(self, size):
+        s1, s2 = self.SHAPES
+        c1 = list(s1)
+        c1[-1] = -1
+        r1, o1, _ = layout(frames(s1, 31, self.i8), c1, False, min_stride=0, pad_error=0.0)
+        r2, o2, _ = layout(frames(s2, 32, self.i8), s2, False, min_stride=0, pad_error=0.0)
+        case = dict(recs1=r1, counts1=i32(c1), offs1=o1, recs2=r2, counts2=i32(s2), offs2=o2, pairs=i32(self.PAIRS))
+        if self.i8:
+            case.update(q1=quantize_np(r1["data"]).reshape(len(r1), 128), q2=quantize_np(r2["data"]).reshape(len(r2), 128))
+        return case
+
+    def uploads(self, case):
+        return {k: case[k] for k in ("recs1", "counts1", "offs1", "recs2", "counts2", "offs2") +
+                (("q1", "q2") if self.i8 else ())}
+
+    def outputs(self, case):
+        return {}
+
+    def enqueue(self, ctx, case, dev, lists):
+        n1, n2 = len(case["counts1"]), len(case["counts2"])
+        if self.i8:
+            return ctx.match_batch_i8(case["pairs"], dev["recs1"], dev["q1"], n1, dev["counts1"], dev["offs1"], 0,
+                                      dev["recs2"], dev["q2"], n2, dev["counts2"], dev["offs2"], 0)
+        ctx.match_batch(case["pairs"], dev["recs1"], n1, dev["counts1"], dev["offs1"], 0, dev["recs2"], n2,
+                        dev["counts2"], dev["offs2"], 0)
+
+    def expected(self, case, lists):
+        from batch_util import MATCH_FIELDS, match_np
+        exp = case["recs1"].copy()
+        for f1, f2 in case["pairs"].tolist():
+            n1, n2 = max(int(case["counts1"][f1]), 0), max(int(case["counts2"][f2]), 0)
+            if n1 == 0 or n2 == 0:
+                continue
+            a, b = span(case["offs1"], 0, f1, n1), span(case["offs2"], 0, f2, n2)
+            if self.i8:
+                exp[a] = match_np(case["recs1"][a], case["q1"][a], case["recs2"][b], case["q2"][b])
+                continue
+            ref = case["recs1"][a].copy()
+            orc().match(ref, n1, case["recs2"][b].copy(), n2, full=False, exact=False)
+            for k in MATCH_FIELDS:
+                exp[k][a] = ref[k]
+        return dict(recs1=exp)
+
+
+class QuantizeBatch(_Small):
+    """misift_quantize_batch into a buffer that holds a pattern: the frames' records quantised, the rest kept."""
+    name = "quantize_batch"
+    temp = False
+    takes_slot = False                                           # no host side beyond the launch
+    SIZES = [130, 0, 33, 64, 20]
+
+    def build(self, size):
+        counts = list(self.SIZES)
+        counts[-1] = -1
+        recs, offs, _ = layout(frames(self.SIZES, 33, True), counts, False, min_stride=0, pad_error=0.0)
+        recs["data"][::7, ::5] = np.random.default_rng(1).normal(0, 0.4, recs["data"][::7, ::5].shape)
+        recs["data"][3, :4] = [np.nan, np.inf, -np.inf, 127.5 / 256]
+        return dict(recs=recs, counts=i32(counts), offs=offs)
+
+    def uploads(self, case):
+        return {k: case[k] for k in ("recs", "counts", "offs")}
+
+    def outputs(self, case):
+        return dict(q=np.random.default_rng(9).integers(-128, 128, (len(case["recs"]) + 3, 128)).astype(np.int8))
+
+    def enqueue(self, ctx, case, dev, lists):
+        ctx.quantize_batch(dev["recs"], len(case["counts"]), dev["counts"], dev["offs"], 0, dev["q"])
+
+    def expected(self, case, lists):
+        q = self.outputs(case)["q"]
+        for f, c in enumerate(case["counts"].tolist()):
+            sl = span(case["offs"], 0, f, max(c, 0))
+            q[sl] = quantize_np(case["recs"]["data"][sl])
+        return dict(q=q)
+
+
+class ScoreFundamental(_Small):
+    """misift_score_fundamental_batch on the frames and the start matrices of the improve step: match_error of the
+    records is written in place."""
+    name = "score_fundamental_batch"
+    temp = False
+
+    def build(self, size):
+        return step("improve_fundamental_batch").case("small")
+
+    def uploads(self, case):
+        return {k: case[k] for k in ("recs", "counts", "offs", "F")}
+
+    def outputs(self, case):
+        return dict(num_fit=poisoned(len(case["sel"])))
+
+    def enqueue(self, ctx, case, dev, lists):
+        ctx.score_fundamental_batch(case["sel"], dev["recs"], len(case["counts"]), dev["counts"], dev["F"], dev["offs"], 0,
+                                    num_fit=dev["num_fit"], min_score=GATES[0], max_ambiguity=GATES[1], thresh=1.0)
+
+    def expected(self, case, lists):
+        from test_fundamental_cpu import expected_score
+        want, fit = case["recs"].copy(), np.zeros(len(case["sel"]), np.int32)
+        for i, f in enumerate(case["sel"].tolist()):
+            n = int(case["counts"][f])
+            sl = span(case["offs"], 0, f, max(n, 0))
+            want[sl], fit[i] = expected_score(case["recs"][sl], n, case["F"][i], *GATES, 1.0)
+        return dict(recs=want, num_fit=fit)
+
+
+class UndistortObs(_Small):
+    """misift_undistort_obs_batch out of place: 257 of 300 slots over five images in three groups and one in none."""
+    name = "undistort_obs_batch"
+    temp = False
+
+    def build(self, size):
+        import bundle_radial_cases as BD
+        from test_bundle_radial_cpu import _words
+        return dict(BD.undistort_case(257), words=np.ascontiguousarray(_words([0.07, -0.11, 0.0], BD.HELD), np.uint32))
+
+    def uploads(self, case):
+        return dict(obs=np.ascontiguousarray(case["obs"][:case["max_obs"]]), export_summary=i32(case["export_summary"]),
+                    words=case["words"])
+
+    def outputs(self, case):
+        return dict(obs_out=poisoned(4 * case["max_obs"]))
+
+    def enqueue(self, ctx, case, dev, lists):
+        ctx.undistort_obs_batch(case["max_obs"], dev["obs"], dev["export_summary"], case["nimages"], case["intrinsics"],
+                                case["group"], dev["words"], ngroups=case["ngroups"], obs_out=dev["obs_out"])
+
+    def expected(self, case, lists):
+        import bundle_radial_cases as BD
+        return dict(obs_out=BD.expected_undistort(case, case["obs"], case["words"]))
+
+
+# ---- the tables
+
+@functools.lru_cache(maxsize=None)
+def stream_table():
+    """table() and, at `small` only, the calls it does not hold: what the caller-stream tests run (stream_util.py)."""
+    return table() + (SelectStep(), Bundle("plain"), Bundle("robust"), Bundle("focal"), Bundle("radial"), FilterTracks(),
+                      CorrespondTracks(), AlignPoints(), TransformScene(), MergeScenes(), RecoverPosePlanar(),
+                      MatchBatch(False), QuantizeBatch(), MatchBatch(True), ScoreFundamental(), UndistortObs())
+
 
 @functools.lru_cache(maxsize=None)
 def table():
@@ -881,4 +1402,4 @@ def table():
 
 
 def step(name):
-    return {s.name: s for s in table()}[name]
+    return {s.name: s for s in stream_table()}[name]
