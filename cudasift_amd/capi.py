@@ -387,6 +387,9 @@ def _set2(set1, set2):
     return set2 if set2[-1] is not None else set2[:-1] + set1[-1:]
 
 
+_NO_ARGUMENT = object()                                         # _adjust_bundle: the call has no obs_weight
+
+
 class Context:
     """One per device (+ optional hipStream_t given as an int)."""
 
@@ -1243,36 +1246,40 @@ class Context:
         after), point_obs (max_tracks ints), history (num_loops x 4 words: the trial cost, the damping, kept, CG
         iterations), cost (2 floats: before, after) and summary (8 ints) are device buffers, allocated here when not
         passed; returns the nine.  Enqueued on the context stream."""
+        return self._adjust_bundle("misift_adjust_bundle_batch", max_tracks, max_obs, track_offsets, obs, export_summary,
+                                   points, point_status, nimages, cam, cam_pair, intrinsics, hold,
+                                   (min_views, min_obs, num_loops, cg_iters, max_error, lambda0, orthonormalise), (),
+                                   (cam_out, points_out, cam_obs, cam_status, cam_rms, point_obs, history, cost, summary))
+
+    def _adjust_bundle(self, name, max_tracks, max_obs, track_offsets, obs, export_summary, points, point_status,
+                       nimages, cam, cam_pair, intrinsics, hold, steps, model, nine, obs_weight=_NO_ARGUMENT, more=()):
+        """The body of the four adjust_bundle*_batch methods: the C function `name` on the scene, the hold list and
+        steps (min_views ... orthonormalise), then `model` (what the call takes between orthonormalise and cam_out, as
+        ctypes arguments), the nine outputs, obs_weight between cost and summary where the call has it (True allocates
+        it, None or False leaves it out) and `more`, the outputs behind summary as (buffer or None, bytes).  An output
+        that is None is allocated here; returns all of them in the order of the C call."""
         intrinsics = np.ascontiguousarray(intrinsics, np.float32).reshape(-1, 4)
         assert len(intrinsics) == nimages
         hold = np.ascontiguousarray(hold, np.int32).reshape(-1)
-        if cam_out is None:
-            cam_out = self.zeros(48 * max(nimages, 1))
-        if points_out is None:
-            points_out = self.zeros(16 * max(max_tracks, 1))
-        if cam_obs is None:
-            cam_obs = self.zeros(4 * max(nimages, 1))
-        if cam_status is None:
-            cam_status = self.zeros(4 * max(nimages, 1))
-        if cam_rms is None:
-            cam_rms = self.zeros(8 * max(nimages, 1))
-        if point_obs is None:
-            point_obs = self.zeros(4 * max(max_tracks, 1))
-        if history is None:
-            history = self.zeros(16 * max(int(num_loops), 1))
-        if cost is None:
-            cost = self.zeros(8)
-        if summary is None:
-            summary = self.zeros(4 * 8)
-        check(lib().misift_adjust_bundle_batch(self.h, max_tracks, max_obs, _dptr(track_offsets), _dptr(obs),
-                                               _dptr(export_summary), _dptr(points), _dptr(point_status), nimages,
-                                               _dptr(cam), _dptr(cam_pair), intrinsics.ctypes.data, len(hold),
-                                               hold.ctypes.data if len(hold) else None, int(min_views), int(min_obs),
-                                               int(num_loops), int(cg_iters), float(max_error), float(lambda0),
-                                               int(orthonormalise), _dptr(cam_out), _dptr(points_out), _dptr(cam_obs),
-                                               _dptr(cam_status), _dptr(cam_rms), _dptr(point_obs), _dptr(history),
-                                               _dptr(cost), _dptr(summary)), "misift_adjust_bundle_batch")
-        return cam_out, points_out, cam_obs, cam_status, cam_rms, point_obs, history, cost, summary
+        min_views, min_obs, num_loops, cg_iters, max_error, lambda0, orthonormalise = steps
+        per_image, per_track = 4 * max(nimages, 1), 4 * max(max_tracks, 1)
+        sizes = (12 * per_image, 4 * per_track, per_image, per_image, 2 * per_image, per_track,
+                 16 * max(int(num_loops), 1), 8, 4 * 8)
+        outs = [self.zeros(n) if b is None else b for b, n in zip(nine, sizes)]
+        if obs_weight is not _NO_ARGUMENT:
+            if obs_weight is True:
+                obs_weight = self.zeros(4 * max(max_obs, 1))
+            elif obs_weight is False:
+                obs_weight = None
+            outs.insert(8, obs_weight)
+        outs += [self.zeros(n) if b is None else b for b, n in more]
+        check(getattr(lib(), name)(
+            self.h, max_tracks, max_obs, _dptr(track_offsets), _dptr(obs), _dptr(export_summary), _dptr(points),
+            _dptr(point_status), nimages, _dptr(cam), _dptr(cam_pair), intrinsics.ctypes.data, len(hold),
+            hold.ctypes.data if len(hold) else None, int(min_views), int(min_obs), int(num_loops), int(cg_iters),
+            float(max_error), float(lambda0), int(orthonormalise), *model,
+            *[_dptr(b) if b is not None else None for b in outs]), name)
+        return tuple(outs)
 
     def adjust_bundle_robust_batch(self, max_tracks, max_obs, track_offsets, obs, export_summary, points, point_status,
                                    nimages, cam, cam_pair, intrinsics, hold=(), min_views=2, min_obs=6, num_loops=5,
@@ -1286,40 +1293,12 @@ class Context:
         error; obs_weight (max_obs floats: the weight of each observation used under the final state, -1 for one not
         used) is a device buffer, allocated here when True, left out when None or False; returns the ten (obs_weight
         None when left out).  Enqueued on the context stream."""
-        if obs_weight is True:
-            obs_weight = self.zeros(4 * max(max_obs, 1))
-        elif obs_weight is False:
-            obs_weight = None
-        intrinsics = np.ascontiguousarray(intrinsics, np.float32).reshape(-1, 4)
-        assert len(intrinsics) == nimages
-        hold = np.ascontiguousarray(hold, np.int32).reshape(-1)
-        if cam_out is None:
-            cam_out = self.zeros(48 * max(nimages, 1))
-        if points_out is None:
-            points_out = self.zeros(16 * max(max_tracks, 1))
-        if cam_obs is None:
-            cam_obs = self.zeros(4 * max(nimages, 1))
-        if cam_status is None:
-            cam_status = self.zeros(4 * max(nimages, 1))
-        if cam_rms is None:
-            cam_rms = self.zeros(8 * max(nimages, 1))
-        if point_obs is None:
-            point_obs = self.zeros(4 * max(max_tracks, 1))
-        if history is None:
-            history = self.zeros(16 * max(int(num_loops), 1))
-        if cost is None:
-            cost = self.zeros(8)
-        if summary is None:
-            summary = self.zeros(4 * 8)
-        check(lib().misift_adjust_bundle_robust_batch(
-            self.h, max_tracks, max_obs, _dptr(track_offsets), _dptr(obs), _dptr(export_summary), _dptr(points),
-            _dptr(point_status), nimages, _dptr(cam), _dptr(cam_pair), intrinsics.ctypes.data, len(hold),
-            hold.ctypes.data if len(hold) else None, int(min_views), int(min_obs), int(num_loops), int(cg_iters),
-            float(max_error), float(lambda0), int(orthonormalise), int(loss), float(loss_scale), _dptr(cam_out),
-            _dptr(points_out), _dptr(cam_obs), _dptr(cam_status), _dptr(cam_rms), _dptr(point_obs), _dptr(history),
-            _dptr(cost), _dptr(obs_weight) if obs_weight is not None else None, _dptr(summary)),
-            "misift_adjust_bundle_robust_batch")
-        return cam_out, points_out, cam_obs, cam_status, cam_rms, point_obs, history, cost, obs_weight, summary
+        return self._adjust_bundle("misift_adjust_bundle_robust_batch", max_tracks, max_obs, track_offsets, obs,
+                                   export_summary, points, point_status, nimages, cam, cam_pair, intrinsics, hold,
+                                   (min_views, min_obs, num_loops, cg_iters, max_error, lambda0, orthonormalise),
+                                   (int(loss), float(loss_scale)),
+                                   (cam_out, points_out, cam_obs, cam_status, cam_rms, point_obs, history, cost, summary),
+                                   obs_weight)
 
     def adjust_bundle_focal_batch(self, max_tracks, max_obs, track_offsets, obs, export_summary, points, point_status,
                                   nimages, cam, cam_pair, intrinsics, group, ngroups=None, hold=(), min_views=2,
@@ -1338,46 +1317,12 @@ class Context:
         if ngroups is None:
             ngroups = int(group.max()) + 1 if len(group) else 0
         assert ngroups == 0 or len(group) == nimages
-        if intrinsics_out is None:
-            intrinsics_out = self.zeros(16 * max(nimages, 1))
-        if focal is None:
-            focal = self.zeros(12 * max(int(ngroups), 1))
-        if obs_weight is True:
-            obs_weight = self.zeros(4 * max(max_obs, 1))
-        elif obs_weight is False:
-            obs_weight = None
-        intrinsics = np.ascontiguousarray(intrinsics, np.float32).reshape(-1, 4)
-        assert len(intrinsics) == nimages
-        hold = np.ascontiguousarray(hold, np.int32).reshape(-1)
-        if cam_out is None:
-            cam_out = self.zeros(48 * max(nimages, 1))
-        if points_out is None:
-            points_out = self.zeros(16 * max(max_tracks, 1))
-        if cam_obs is None:
-            cam_obs = self.zeros(4 * max(nimages, 1))
-        if cam_status is None:
-            cam_status = self.zeros(4 * max(nimages, 1))
-        if cam_rms is None:
-            cam_rms = self.zeros(8 * max(nimages, 1))
-        if point_obs is None:
-            point_obs = self.zeros(4 * max(max_tracks, 1))
-        if history is None:
-            history = self.zeros(16 * max(int(num_loops), 1))
-        if cost is None:
-            cost = self.zeros(8)
-        if summary is None:
-            summary = self.zeros(4 * 8)
-        check(lib().misift_adjust_bundle_focal_batch(
-            self.h, max_tracks, max_obs, _dptr(track_offsets), _dptr(obs), _dptr(export_summary), _dptr(points),
-            _dptr(point_status), nimages, _dptr(cam), _dptr(cam_pair), intrinsics.ctypes.data, len(hold),
-            hold.ctypes.data if len(hold) else None, int(min_views), int(min_obs), int(num_loops), int(cg_iters),
-            float(max_error), float(lambda0), int(orthonormalise), int(loss), float(loss_scale), int(ngroups),
-            group.ctypes.data if len(group) else None, _dptr(cam_out), _dptr(points_out), _dptr(cam_obs),
-            _dptr(cam_status), _dptr(cam_rms), _dptr(point_obs), _dptr(history), _dptr(cost),
-            _dptr(obs_weight) if obs_weight is not None else None, _dptr(summary), _dptr(intrinsics_out), _dptr(focal)),
-            "misift_adjust_bundle_focal_batch")
-        return (cam_out, points_out, cam_obs, cam_status, cam_rms, point_obs, history, cost, obs_weight, summary,
-                intrinsics_out, focal)
+        return self._adjust_bundle("misift_adjust_bundle_focal_batch", max_tracks, max_obs, track_offsets, obs,
+                                   export_summary, points, point_status, nimages, cam, cam_pair, intrinsics, hold,
+                                   (min_views, min_obs, num_loops, cg_iters, max_error, lambda0, orthonormalise),
+                                   (int(loss), float(loss_scale), int(ngroups), group.ctypes.data if len(group) else None),
+                                   (cam_out, points_out, cam_obs, cam_status, cam_rms, point_obs, history, cost, summary),
+                                   obs_weight, ((intrinsics_out, 16 * max(nimages, 1)), (focal, 12 * max(int(ngroups), 1))))
 
     def adjust_bundle_radial_batch(self, max_tracks, max_obs, track_offsets, obs, export_summary, points, point_status,
                                    nimages, cam, cam_pair, intrinsics, group, ngroups=None, radial=None, k0=None, hold=(),
@@ -1401,49 +1346,15 @@ class Context:
             radial = np.ascontiguousarray(radial, np.int32).reshape(-1)
             k0 = np.ascontiguousarray(k0, np.float32).reshape(-1)
             assert len(radial) == ngroups and len(k0) == ngroups
-        if intrinsics_out is None:
-            intrinsics_out = self.zeros(16 * max(nimages, 1))
-        if focal is None:
-            focal = self.zeros(12 * max(int(ngroups), 1))
-        if radial_out is None:
-            radial_out = self.zeros(12 * max(int(ngroups), 1))
-        if obs_weight is True:
-            obs_weight = self.zeros(4 * max(max_obs, 1))
-        elif obs_weight is False:
-            obs_weight = None
-        intrinsics = np.ascontiguousarray(intrinsics, np.float32).reshape(-1, 4)
-        assert len(intrinsics) == nimages
-        hold = np.ascontiguousarray(hold, np.int32).reshape(-1)
-        if cam_out is None:
-            cam_out = self.zeros(48 * max(nimages, 1))
-        if points_out is None:
-            points_out = self.zeros(16 * max(max_tracks, 1))
-        if cam_obs is None:
-            cam_obs = self.zeros(4 * max(nimages, 1))
-        if cam_status is None:
-            cam_status = self.zeros(4 * max(nimages, 1))
-        if cam_rms is None:
-            cam_rms = self.zeros(8 * max(nimages, 1))
-        if point_obs is None:
-            point_obs = self.zeros(4 * max(max_tracks, 1))
-        if history is None:
-            history = self.zeros(16 * max(int(num_loops), 1))
-        if cost is None:
-            cost = self.zeros(8)
-        if summary is None:
-            summary = self.zeros(4 * 8)
-        check(lib().misift_adjust_bundle_radial_batch(
-            self.h, max_tracks, max_obs, _dptr(track_offsets), _dptr(obs), _dptr(export_summary), _dptr(points),
-            _dptr(point_status), nimages, _dptr(cam), _dptr(cam_pair), intrinsics.ctypes.data, len(hold),
-            hold.ctypes.data if len(hold) else None, int(min_views), int(min_obs), int(num_loops), int(cg_iters),
-            float(max_error), float(lambda0), int(orthonormalise), int(loss), float(loss_scale), int(ngroups),
-            group.ctypes.data if len(group) else None, radial.ctypes.data if radial is not None and len(radial) else None,
-            k0.ctypes.data if k0 is not None and len(k0) else None, _dptr(cam_out), _dptr(points_out), _dptr(cam_obs),
-            _dptr(cam_status), _dptr(cam_rms), _dptr(point_obs), _dptr(history), _dptr(cost),
-            _dptr(obs_weight) if obs_weight is not None else None, _dptr(summary), _dptr(intrinsics_out), _dptr(focal),
-            _dptr(radial_out)), "misift_adjust_bundle_radial_batch")
-        return (cam_out, points_out, cam_obs, cam_status, cam_rms, point_obs, history, cost, obs_weight, summary,
-                intrinsics_out, focal, radial_out)
+        return self._adjust_bundle("misift_adjust_bundle_radial_batch", max_tracks, max_obs, track_offsets, obs,
+                                   export_summary, points, point_status, nimages, cam, cam_pair, intrinsics, hold,
+                                   (min_views, min_obs, num_loops, cg_iters, max_error, lambda0, orthonormalise),
+                                   (int(loss), float(loss_scale), int(ngroups), group.ctypes.data if len(group) else None,
+                                    radial.ctypes.data if radial is not None and len(radial) else None,
+                                    k0.ctypes.data if k0 is not None and len(k0) else None),
+                                   (cam_out, points_out, cam_obs, cam_status, cam_rms, point_obs, history, cost, summary),
+                                   obs_weight, ((intrinsics_out, 16 * max(nimages, 1)), (focal, 12 * max(int(ngroups), 1)),
+                                                (radial_out, 12 * max(int(ngroups), 1))))
 
     def undistort_obs_batch(self, max_obs, obs, export_summary, nimages, intrinsics, group, radial, ngroups=None,
                             obs_out=None):

@@ -1,9 +1,11 @@
 // bundle_core.hpp — the arithmetic of misift_adjust_bundle_batch, for host and device: every phase of the call as a
 // function of one work item (a slot, a track, an image) over a BundleData, a struct of plain pointers.  The kernels
 // (kernels_bundle.hip) hand in the call's arguments and temp memory and run one work item per lane or per workgroup; the
-// host-only test hook (misift_test_adjust_bundle) hands in host arrays and runs the same functions in loops, phase after
-// phase in the order of the launches.  So what a CPU test pins is what the device runs.  The definition, step by step,
-// is in include/misift.h.  misift_adjust_bundle_robust_batch is the same call with a loss: bundle_loss gives rho, w and
+// host-only test hook (misift_test_adjust_bundle) hands in host arrays and runs the same functions in loops.  Both go
+// through the phase types at the end of this file, in the order bundle_schedule (bundle_host.hpp) states once for the
+// two.  So what a CPU test pins is what the device runs: arithmetic, sequence and instance.  The definition, step by
+// step, is in include/misift.h.
+// misift_adjust_bundle_robust_batch is the same call with a loss: bundle_loss gives rho, w and
 // sqrt(w) of a member's squared residual, step 1 scales the member's 20 values by sqrt(w) where it writes them, the cost
 // pass stores rho in place of the squared residual, and every phase downstream reads what those two wrote.  ROBUST is a
 // template argument of the two, so the plain call compiles to what it was.  misift_adjust_bundle_focal_batch adds one
@@ -1448,7 +1450,169 @@ FUND_HD TrackObs bundle_undistort_obs(TrackObs ob, int nimages, const float *int
   return ob;
 }
 
-// ---- the host's side: the Sum as a loop, the phases in the order of the launches
+// ---- the model <FOCAL, RADIAL> under one name per phase, so that no caller picks among the functions above by hand.
+// Each forwards to the function of its model and holds no statement of its own: the bodies stay apart because a shared
+// one moved the register allocation.  Beside them the number of sums each phase hands its Sum at once.
+
+template <bool FOCAL, bool RADIAL>
+constexpr int BUNDLE_NORMAL_SUMS = RADIAL ? BUNDLE_NORMAL_RADIAL : FOCAL ? BUNDLE_NORMAL_FOCAL : BUNDLE_NORMAL;
+template <bool FOCAL, bool RADIAL>
+constexpr int BUNDLE_CG_IMAGE_SUMS = RADIAL ? 8 : FOCAL ? 7 : 6;
+template <bool FOCAL, bool RADIAL>
+constexpr int BUNDLE_CG_START_SUMS = RADIAL ? 4 : FOCAL ? 3 : 1;
+template <bool FOCAL, bool RADIAL>
+constexpr int BUNDLE_CG_SCALAR_SUMS = FOCAL ? 2 : 1;
+
+template <bool ROBUST, bool FOCAL, bool RADIAL>
+FUND_HD void bundle_track_normal_of(const BundleData &D, int t)
+{
+  if constexpr (FOCAL) bundle_track_normal_focal<ROBUST, RADIAL>(D, t);
+  else bundle_track_normal<ROBUST>(D, t);
+}
+template <bool FOCAL, bool RADIAL, class Sum>
+FUND_HD void bundle_image_normal_of(const BundleData &D, Sum &S, int i, bool lead)
+{
+  if constexpr (RADIAL) bundle_image_normal_radial(D, S, i, lead);
+  else if constexpr (FOCAL) bundle_image_normal_focal(D, S, i, lead);
+  else bundle_image_normal(D, S, i, lead);
+}
+template <bool FOCAL, bool RADIAL, class Sum>
+FUND_HD void bundle_cg_image_of(const BundleData &D, Sum &S, int i, bool lead)
+{
+  if constexpr (RADIAL) bundle_cg_image_radial(D, S, i, lead);
+  else if constexpr (FOCAL) bundle_cg_image_focal(D, S, i, lead);
+  else bundle_cg_image(D, S, i, lead);
+}
+// the trial scalars of group g < BUNDLE_MAX_GROUPS: the scale, then the coefficient
+template <bool FOCAL, bool RADIAL>
+FUND_HD void bundle_group_trial(const BundleData &D, int g)
+{
+  if constexpr (FOCAL) bundle_focal_trial(D, g);
+  if constexpr (RADIAL) bundle_radial_trial(D, g);
+}
+
+// ---- the phases as stateless types, by the shape of their work item: what the kernels (kernels_bundle.hip) and the
+// loops of the hook (bundle_host.hpp) are instantiated over, and what the schedule (bundle_host.hpp) names.  `run` is
+// the function of the phase itself where it takes (D, work item, flag of the launch ...), so a kernel calls it as
+// directly as a kernel written by hand would (a forwarding function in between moved one instruction of the robust
+// cost pass); where the function is a template over the Sum, run forwards to it and holds no other statement.
+
+// lane per slot o < O
+template <bool RADIAL>
+struct BundlePremember {
+  static constexpr auto run = &bundle_slot_premember<RADIAL>;
+};
+template <bool ROBUST, bool FOCAL, bool RADIAL>
+struct BundleEval {
+  static constexpr auto run = &bundle_eval_slot<ROBUST, FOCAL, RADIAL>;   // (D, o, trial)
+};
+template <bool FOCAL, bool RADIAL>
+struct BundleWeightOut {
+  static constexpr auto run = &bundle_weight_slot<FOCAL, RADIAL>;
+};
+
+// lane per track t < T
+struct BundleActivate {
+  static constexpr auto run = &bundle_track_activate;
+};
+template <bool ROBUST, bool FOCAL, bool RADIAL>
+struct BundleTrackNormal {
+  static constexpr auto run = &bundle_track_normal_of<ROBUST, FOCAL, RADIAL>;
+};
+template <bool FOCAL, bool RADIAL>
+struct BundleCgTrack {
+  static constexpr auto run = &bundle_cg_track<FOCAL, RADIAL>;
+};
+template <bool FOCAL, bool RADIAL>
+struct BundleTrackTrial {
+  static constexpr auto run = &bundle_track_trial<FOCAL, RADIAL>;
+};
+struct BundleTrackOut {
+  static constexpr auto run = &bundle_track_out;
+};
+
+// lane per image i < nimages; with GROUPS the first groups(D) lanes of the launch take a group each as well
+struct BundleImageInit {
+  static constexpr bool GROUPS = false;
+  static constexpr auto run = &bundle_image_init;
+};
+template <bool FOCAL, bool RADIAL>
+struct BundleImageTrial {
+  static constexpr bool GROUPS = FOCAL;
+  static FUND_HD int groups(const BundleData &) { return BUNDLE_MAX_GROUPS; }
+  static constexpr auto run = &bundle_image_trial;
+  static constexpr auto group = &bundle_group_trial<FOCAL, RADIAL>;
+};
+struct BundleImageOut {
+  static constexpr bool GROUPS = false;
+  static constexpr auto run = &bundle_image_out;
+};
+struct BundleIntrinsicsOut {                   // d_intrinsics_out, and d_focal of the ngroups groups
+  static constexpr bool GROUPS = true;
+  static FUND_HD int groups(const BundleData &D) { return D.ngroups; }
+  static constexpr auto run = &bundle_intrinsics_out;   // (D, i, refined)
+  static constexpr auto group = &bundle_focal_out;      // (D, g, refined)
+};
+
+// workgroup (or loop) per image with SUMS sums at once: run<Sum>(D, S, i, lead, flag of the launch ...)
+struct BundleCost {
+  static constexpr int SUMS = 1;
+  template <class Sum>
+  static FUND_HD void run(const BundleData &D, Sum &S, int i, bool lead, int trial)
+  {
+    bundle_image_cost(D, S, i, trial != 0, lead);
+  }
+};
+template <bool FOCAL, bool RADIAL>
+struct BundleImageNormal {
+  static constexpr int SUMS = BUNDLE_NORMAL_SUMS<FOCAL, RADIAL>;
+  template <class Sum>
+  static constexpr auto run = &bundle_image_normal_of<FOCAL, RADIAL, Sum>;
+};
+template <bool FOCAL, bool RADIAL>
+struct BundleCgImage {
+  static constexpr int SUMS = BUNDLE_CG_IMAGE_SUMS<FOCAL, RADIAL>;
+  template <class Sum>
+  static constexpr auto run = &bundle_cg_image_of<FOCAL, RADIAL, Sum>;
+};
+
+// the scalar workgroup (or one pass of the hook) with SUMS sums at once: run<Sum>(D, S, lane, lanes, lead)
+struct BundleStart {
+  static constexpr int SUMS = 1;
+  template <class Sum>
+  static FUND_HD void run(const BundleData &D, Sum &S, int, int, bool lead)
+  {
+    bundle_scalar_init(D, S, lead);
+  }
+};
+template <bool RADIAL>
+struct BundleGroupInit {                       // takes no sum: the Sum it is handed has no memory
+  static constexpr int SUMS = 0;
+  template <class Sum>
+  static FUND_HD void run(const BundleData &D, Sum &S, int lane, int lanes, bool)
+  {
+    bundle_focal_init<RADIAL>(D, S, lane, lanes);
+  }
+};
+template <bool FOCAL, bool RADIAL>
+struct BundleCgStart {
+  static constexpr int SUMS = BUNDLE_CG_START_SUMS<FOCAL, RADIAL>;
+  template <class Sum>
+  static constexpr auto run = &bundle_cg_start<FOCAL, RADIAL, Sum>;
+};
+template <bool FOCAL, bool RADIAL>
+struct BundleCgScalar {
+  static constexpr int SUMS = BUNDLE_CG_SCALAR_SUMS<FOCAL, RADIAL>;
+  template <class Sum>
+  static constexpr auto run = &bundle_cg_scalar<FOCAL, RADIAL, Sum>;
+};
+struct BundleDecide {
+  static constexpr int SUMS = 1;
+  template <class Sum>
+  static constexpr auto run = &bundle_decide<Sum>;
+};
+
+// ---- the host's side: the Sum as a loop
 
 struct BundleHostSum {
   float p[BUNDLE_NORMAL_RADIAL * FUND_SLOTS];

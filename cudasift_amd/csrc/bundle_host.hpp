@@ -1,6 +1,9 @@
-// bundle_host.hpp — the host's side of the bundle calls: the temp layout, the phases of bundle_core.hpp in the order of
-// the launches, and the whole call on host arrays.  kernels_bundle.hip wraps bundle_host into the test hooks
-// (misift_test_adjust_bundle*); tools/bundle_radial_sanitize.cpp runs it under the sanitizers.  Host code only.
+// bundle_host.hpp — the host's side of the bundle calls, shared by the device path and the test hooks: the temp layout;
+// the call as one struct (BundleCall), what is derived from it (bundle_derive) and the BundleData both sides run on
+// (bundle_data); the order of the phases of bundle_core.hpp, written once (bundle_schedule) over an executor; and the
+// host executor with the whole call on host arrays (bundle_host).  kernels_bundle.hip holds the device executor and
+// wraps bundle_host into the test hooks (misift_test_adjust_bundle*); tools/bundle_radial_sanitize.cpp runs it under the
+// sanitizers.  Host code only.
 #pragma once
 #include <stdint.h>
 #include <vector>
@@ -54,143 +57,262 @@ inline size_t bundle_layout(BundleData &D, char *base, bool focal = false, bool 
   return at;
 }
 
+// ---- one call description
 
-// the phases of the host hook that read the loss
-template <bool ROBUST, bool FOCAL, bool RADIAL>
-inline void bundle_host_eval(const BundleData &D, int O, bool trial)
+// The public arguments of the four calls (include/misift.h) in one struct; what a call does not have is NULL or 0.  The
+// plain call is loss 0 without obs_weight, the robust call ngroups 0 without intrinsics_out.  The pointers are the
+// device's for the entry points and the host's for the hooks.
+struct BundleCall {
+  int max_tracks, max_obs;
+  const int *track_offsets;
+  const TrackObs *obs;
+  const int *export_summary;
+  const float *points;
+  const int *point_status;
+  int nimages;
+  const float *cam;
+  const int *cam_pair;
+  const float *intrinsics;                     // host
+  int nhold;
+  const int *hold;                             // host
+  int min_views, min_obs, num_loops, cg_iters;
+  float max_error, lambda0;
+  int orthonormalise, loss;
+  float loss_scale;
+  int ngroups;
+  const int *group;                            // host
+  bool radial_call;                            // misift_adjust_bundle_radial_batch: its two lists may both be NULL
+  const int *radial;                           // host, ngroups flags
+  const float *k0;                             // host, ngroups
+  float *cam_out, *points_out;
+  int *cam_obs, *cam_status;
+  float *cam_rms;
+  int *point_obs;
+  float *history, *cost, *obs_weight;
+  int *summary;
+  float *intrinsics_out;
+  int *focal_out, *radial_out;
+};
+
+// What a call with valid arguments derives from them, once, for the device and the hook alike.
+struct BundleDerived {
+  bool focal;                                  // an image has a group: the FOCAL instances run
+  bool radial;                                 // and some k_g is an unknown or starts off zero: the RADIAL ones
+  int rad[BUNDLE_MAX_GROUPS];                  // the flags and k0, 0 from ngroups on
+  float k0[BUNDLE_MAX_GROUPS];
+  float thresh2, c, c2;                        // max_error^2; the loss scale (0 with loss 0) and its square: each
+                                               // rounded once, here, so that host and device read the same bits
+  std::vector<int> held;                       // nimages flags
+  std::vector<int> none;                       // nimages times -1 where intrinsics_out is wanted without a group
+};
+inline BundleDerived bundle_derive(const BundleCall &c)
 {
-  for (int o = 0; o < O; o++) bundle_eval_slot<ROBUST, FOCAL, RADIAL>(D, o, trial);
-}
-template <bool ROBUST, bool FOCAL, bool RADIAL>
-inline void bundle_host_track_normal(const BundleData &D, int T)
-{
-  for (int t = 0; t < T; t++) FOCAL ? bundle_track_normal_focal<ROBUST, RADIAL>(D, t) : bundle_track_normal<ROBUST>(D, t);
+  BundleDerived d{};
+  for (int i = 0; c.ngroups > 0 && i < c.nimages; i++) d.focal = d.focal || c.group[i] >= 0;
+  for (int g = 0; c.radial && g < c.ngroups; g++) {
+    d.rad[g] = c.radial[g];
+    d.k0[g] = c.k0[g];
+    d.radial = d.radial || (d.focal && (d.rad[g] != 0 || d.k0[g] != 0.0f));
+  }
+  d.thresh2 = c.max_error * c.max_error;
+  d.c = c.loss != BUNDLE_LOSS_NONE ? c.loss_scale : 0.0f;
+  d.c2 = d.c * d.c;
+  d.held.assign(c.nimages, 0);
+  for (int j = 0; j < c.nhold; j++) d.held[c.hold[j]] = 1;
+  d.none.assign(c.intrinsics_out && c.ngroups == 0 ? c.nimages : 0, -1);
+  return d;
 }
 
-// the phases of the hook in the order of the launches
-template <bool ROBUST, bool FOCAL, bool RADIAL = false>
-inline void bundle_host_run(const BundleData &D, int T, int O)
+// The lists the phases read through host pointers: the entry points' pinned copies, or for the hook what
+// bundle_derive left.  rad and k0 are NULL unless the call is the radial one.
+struct BundleLists {
+  const int *held, *group, *rad;
+  const float *k0;
+};
+
+// The arguments and the outputs of the call as the phases read them; the temp is bundle_layout's to add.
+inline BundleData bundle_data(const TrackScene &scene, const BundleCall &c, const BundleDerived &d, const BundleLists &l)
 {
-  const int nimages = D.s.nimages;
-  BundleHostSum S;
-  if (FOCAL) bundle_focal_init<RADIAL>(D, S, 0, 1);
-  bundle_host_eval<ROBUST, FOCAL, RADIAL>(D, O, false);
-  for (int i = 0; i < nimages; i++) bundle_image_cost(D, S, i, false, true);
-  bundle_scalar_init(D, S, true);
+  BundleData D{};
+  D.s = scene;
+  D.min_views = c.min_views; D.min_obs = c.min_obs; D.num_loops = c.num_loops; D.cg_iters = c.cg_iters;
+  D.orthonormalise = c.orthonormalise; D.thresh2 = d.thresh2; D.lambda0 = c.lambda0;
+  D.loss = c.loss; D.loss_scale = d.c; D.loss_scale2 = d.c2;
+  D.held = l.held; D.ngroups = c.ngroups; D.grp = l.group; D.rad = l.rad; D.k0 = l.k0;
+  D.cam_out = c.cam_out; D.points_out = c.points_out; D.cam_rms = c.cam_rms; D.history = c.history; D.cost = c.cost;
+  D.cam_obs = c.cam_obs; D.cam_status = c.cam_status; D.point_obs = c.point_obs; D.summary = c.summary;
+  D.obs_weight = c.obs_weight; D.intrinsics_out = c.intrinsics_out; D.focal_out = c.focal_out;
+  D.radial_out = c.radial_out;
+  return D;
+}
+
+// ---- one schedule
+
+// The order of the phases, for the device and the hook alike.  X is the executor: slots, tracks, images, image_sums and
+// scalar run a phase type of bundle_core.hpp over its work items (a launch, or a loop), scope groups them under a
+// profile entry and gives 0 or the error that ends the call.  What differs by nature between the two sides is a named
+// step of the executor: clear (the owners -1, the control words and the summary 0), candidates (the owner of every slot
+// and the image it is a candidate of), gather (every image's members listed in ascending slot, an image with too few
+// demoted) and radial_out (d_radial from the first ngroups lanes of one workgroup).
+template <bool ROBUST, bool FOCAL, bool RADIAL, class X>
+inline int bundle_schedule(X &x, const BundleData &D)
+{
+  int r = x.clear();
+  auto step = [&](const char *entry, auto phases) {
+    if (!r) r = x.scope(entry, phases);
+  };
+  step("bundle_setup", [&] {
+    x.candidates();
+    x.template images<BundleImageInit>();
+    x.template slots<BundlePremember<RADIAL>>();
+    x.template tracks<BundleActivate>();
+    x.gather();
+    if (FOCAL) x.template scalar<BundleGroupInit<RADIAL>>();
+    x.template slots<BundleEval<ROBUST, FOCAL, RADIAL>>(0);
+    x.template image_sums<BundleCost>(0);
+    x.template scalar<BundleStart>();
+  });
   for (int loop = 0; loop < D.num_loops; loop++) {
-    bundle_host_track_normal<ROBUST, FOCAL, RADIAL>(D, T);
-    for (int i = 0; i < nimages; i++) {
-      if (RADIAL) bundle_image_normal_radial(D, S, i, true);
-      else FOCAL ? bundle_image_normal_focal(D, S, i, true) : bundle_image_normal(D, S, i, true);
-    }
-    bundle_cg_start<FOCAL, RADIAL>(D, S, 0, 1, true);
+    // the normal equations, the points eliminated
+    step("bundle_track", [&] { x.template tracks<BundleTrackNormal<ROBUST, FOCAL, RADIAL>>(); });
+    step("bundle_image", [&] { x.template image_sums<BundleImageNormal<FOCAL, RADIAL>>(); });
+    // the reduced system by conjugate gradients
+    step("bundle_scalar", [&] { x.template scalar<BundleCgStart<FOCAL, RADIAL>>(); });
     for (int it = 0; it < D.cg_iters; it++) {
-      for (int t = 0; t < T; t++) bundle_cg_track<FOCAL, RADIAL>(D, t);
-      for (int i = 0; i < nimages; i++) {
-        if (RADIAL) bundle_cg_image_radial(D, S, i, true);
-        else FOCAL ? bundle_cg_image_focal(D, S, i, true) : bundle_cg_image(D, S, i, true);
-      }
-      bundle_cg_scalar<FOCAL, RADIAL>(D, S, 0, 1, true);
+      step("bundle_track", [&] { x.template tracks<BundleCgTrack<FOCAL, RADIAL>>(); });
+      step("bundle_image", [&] { x.template image_sums<BundleCgImage<FOCAL, RADIAL>>(); });
+      step("bundle_scalar", [&] { x.template scalar<BundleCgScalar<FOCAL, RADIAL>>(); });
     }
-    for (int t = 0; t < T; t++) bundle_track_trial<FOCAL, RADIAL>(D, t);
-    for (int i = 0; i < nimages; i++) bundle_image_trial(D, i);
-    if (FOCAL)
-      for (int g = 0; g < BUNDLE_MAX_GROUPS; g++) bundle_focal_trial(D, g);
-    if (RADIAL)
-      for (int g = 0; g < BUNDLE_MAX_GROUPS; g++) bundle_radial_trial(D, g);
-    bundle_host_eval<ROBUST, FOCAL, RADIAL>(D, O, true);
-    for (int i = 0; i < nimages; i++) bundle_image_cost(D, S, i, true, true);
-    bundle_decide(D, S, 0, 1, true);
+    // the trial state, its cost, kept or turned away
+    step("bundle_track", [&] { x.template tracks<BundleTrackTrial<FOCAL, RADIAL>>(); });
+    step("bundle_trial", [&] {
+      x.template images<BundleImageTrial<FOCAL, RADIAL>>();
+      x.template slots<BundleEval<ROBUST, FOCAL, RADIAL>>(1);
+    });
+    step("bundle_image", [&] { x.template image_sums<BundleCost>(1); });
+    step("bundle_scalar", [&] { x.template scalar<BundleDecide>(); });
   }
-  for (int i = 0; i < nimages; i++) bundle_image_out(D, i);
-  for (int t = 0; t < T; t++) bundle_track_out(D, t);
-  if (D.obs_weight)
-    for (int o = 0; o < O; o++) bundle_weight_slot<FOCAL, RADIAL>(D, o);
-  if (D.intrinsics_out) {
-    for (int i = 0; i < nimages; i++) bundle_intrinsics_out(D, i, FOCAL);
-    for (int g = 0; g < D.ngroups; g++) bundle_focal_out(D, g, FOCAL);
-  }
-  if (D.radial_out)
-    for (int g = 0; g < D.ngroups; g++) bundle_radial_out(D, g, FOCAL, RADIAL);
+  step("bundle_out", [&] {
+    x.template images<BundleImageOut>();
+    x.template tracks<BundleTrackOut>();
+    if (D.obs_weight) x.template slots<BundleWeightOut<FOCAL, RADIAL>>();
+    if (D.intrinsics_out) x.template images<BundleIntrinsicsOut>(FOCAL ? 1 : 0);
+    if (D.radial_out && D.ngroups > 0) x.radial_out(FOCAL, RADIAL);
+  });
+  return r;
 }
 
-// The hooks' common body: the whole call on host arrays; ngroups 0 and no intrinsics_out is the robust call, no
-// radial_flags the focal call.  false: an invalid argument, nothing written.
-inline bool bundle_host(int max_tracks, int max_obs, const int *track_offsets, const TrackObs *obs,
-                        const int *export_summary, const float *points, const int *point_status, int nimages,
-                        const float *cam, const int *cam_pair, const float *intrinsics, int nhold, const int *hold,
-                        int min_views, int min_obs, int num_loops, int cg_iters, float max_error, float lambda0,
-                        int orthonormalise, int loss, float loss_scale, int ngroups, const int *group, float *cam_out,
-                        float *points_out, int *cam_obs, int *cam_status, float *cam_rms, int *point_obs, float *history,
-                        float *cost, float *obs_weight, int *summary, float *intrinsics_out, int *focal_out,
-                        const int *radial_flags = nullptr, const float *k0 = nullptr, int *radial_out = nullptr)
+// the loss and the model are the same for the whole call: one of six instances of the schedule, picked here and nowhere else
+template <class X>
+inline int bundle_run(X &x, const BundleData &D, bool focal, bool radial)
 {
-  bool ok = max_tracks >= 1 && max_obs >= 1 && nimages >= 1 && track_offsets && obs && export_summary && points &&
-            point_status && cam && cam_pair && intrinsics && nhold >= 0 && (nhold == 0 || hold) && min_views >= 2 &&
-            min_obs >= 3 && num_loops >= 0 && cg_iters >= 0 && max_error > 0.0f && lambda0 > 0.0f &&
-            fundamental_finite(lambda0) && (orthonormalise == 0 || orthonormalise == 1) && cam_out && points_out &&
-            cam_obs && cam_status && cam_rms && point_obs && (history || num_loops == 0) && cost && summary &&
-            loss >= BUNDLE_LOSS_NONE && loss <= BUNDLE_LOSS_GEMAN_MCCLURE &&
-            (loss == BUNDLE_LOSS_NONE || (loss_scale > 0.0f && fundamental_finite(loss_scale)));
-  for (int j = 0; ok && j < nhold; j++) ok = hold[j] >= 0 && hold[j] < nimages;
-  ok = ok && ngroups >= 0 && ngroups <= BUNDLE_MAX_GROUPS && (ngroups == 0 || group);
-  bool focal = false;
-  for (int i = 0; ok && ngroups > 0 && i < nimages; i++) {
-    ok = group[i] >= -1 && group[i] < ngroups;
-    focal = focal || group[i] >= 0;
+  const bool robust = D.loss != BUNDLE_LOSS_NONE;
+  if (radial) return robust ? bundle_schedule<true, true, true>(x, D) : bundle_schedule<false, true, true>(x, D);
+  if (focal) return robust ? bundle_schedule<true, true, false>(x, D) : bundle_schedule<false, true, false>(x, D);
+  return robust ? bundle_schedule<true, false, false>(x, D) : bundle_schedule<false, false, false>(x, D);
+}
+
+// ---- the host executor: every phase a loop over its work items, the workgroup's sums by BundleHostSum
+
+struct BundleHostExec {
+  const BundleData &D;
+  const int T, O;
+  BundleHostSum S;
+  int clear()
+  {
+    for (int o = 0; o < D.s.max_obs; o++) D.owner[o] = -1;
+    for (int j = 0; j < BUNDLE_CTL; j++) D.ctl[j] = 0;
+    for (int j = 0; j < 8; j++) D.summary[j] = 0;
+    return 0;
   }
-  // the radial call: the flags and k0 padded to BUNDLE_MAX_GROUPS; on: the RADIAL instances run
-  int rad[BUNDLE_MAX_GROUPS] = {0};
-  float kstart[BUNDLE_MAX_GROUPS] = {0.0f};
-  bool radial = false;
-  ok = ok && (radial_flags != nullptr) == (k0 != nullptr);
-  for (int g = 0; ok && radial_flags && g < ngroups; g++) {
-    ok = (radial_flags[g] == 0 || radial_flags[g] == 1) && fundamental_finite(k0[g]);
-    rad[g] = radial_flags[g];
-    kstart[g] = k0[g];
-    radial = radial || (focal && (rad[g] != 0 || kstart[g] != 0.0f));
+  template <class F>
+  int scope(const char *, F phases)
+  {
+    phases();
+    return 0;
   }
-  if (!ok) return false;
-  BundleData D;
-  D.rad = rad; D.k0 = kstart; D.radial_out = radial_out;
-  D.ngroups = ngroups; D.grp = ngroups > 0 ? group : nullptr; D.intrinsics_out = intrinsics_out; D.focal_out = focal_out;
-  D.s = TrackScene{max_tracks, max_obs, nimages, track_offsets, obs, export_summary,
-                   points, point_status, cam, cam_pair, intrinsics};
-  D.min_views = min_views; D.min_obs = min_obs; D.num_loops = num_loops; D.cg_iters = cg_iters;
-  D.orthonormalise = orthonormalise;
-  D.thresh2 = max_error * max_error; D.lambda0 = lambda0;
-  const bool robust = loss != BUNDLE_LOSS_NONE;
-  D.loss = loss; D.loss_scale = robust ? loss_scale : 0.0f; D.loss_scale2 = D.loss_scale * D.loss_scale;
-  std::vector<int> held(nimages, 0);
-  for (int j = 0; j < nhold; j++) held[hold[j]] = 1;
-  D.held = held.data();
-  std::vector<char> tmp(bundle_layout(D, nullptr, focal, radial) + 16, 0);
-  bundle_layout(D, reinterpret_cast<char *>(((uintptr_t)tmp.data() + 15) & ~(uintptr_t)15), focal, radial);
-  D.cam_out = cam_out; D.points_out = points_out; D.cam_rms = cam_rms; D.history = history; D.cost = cost;
-  D.cam_obs = cam_obs; D.cam_status = cam_status; D.point_obs = point_obs; D.summary = summary;
-  D.obs_weight = obs_weight;
-  const int T = scene_T(D.s), O = scene_O(D.s);
-  // the owners and the candidates, as launch_track_candidates
-  for (int o = 0; o < max_obs; o++) D.owner[o] = -1;
-  for (int t = 0; t < T; t++) scene_track_owns(D.s, D.owner, t);
-  for (int o = 0; o < O; o++) D.key[o] = scene_slot_key(D.s, D.owner, o);
-  for (int j = 0; j < 8; j++) summary[j] = 0;
-  for (int i = 0; i < nimages; i++) bundle_image_init(D, i);
-  for (int o = 0; o < O; o++) radial ? bundle_slot_premember<true>(D, o) : bundle_slot_premember(D, o);
-  for (int t = 0; t < T; t++) bundle_track_activate(D, t);
+  void candidates()                            // as launch_track_candidates
+  {
+    for (int t = 0; t < T; t++) scene_track_owns(D.s, D.owner, t);
+    for (int o = 0; o < O; o++) D.key[o] = scene_slot_key(D.s, D.owner, o);
+  }
+  void gather()
   {
     int at = 0;
-    for (int i = 0; i < nimages; i++) {
+    for (int i = 0; i < D.s.nimages; i++) {
       D.istart[i] = at;
       for (int o = 0; o < O; o++)
         if (D.key[o] == i) D.list[at++] = o;
       D.icount[i] = at - D.istart[i];
-      if (D.istate[i] == BUNDLE_ADJUSTED && D.icount[i] < min_obs) D.istate[i] = BUNDLE_FEW_OBS;
+      if (D.istate[i] == BUNDLE_ADJUSTED && D.icount[i] < D.min_obs) D.istate[i] = BUNDLE_FEW_OBS;
     }
   }
-  if (radial) robust ? bundle_host_run<true, true, true>(D, T, O) : bundle_host_run<false, true, true>(D, T, O);
-  else if (focal) robust ? bundle_host_run<true, true>(D, T, O) : bundle_host_run<false, true>(D, T, O);
-  else robust ? bundle_host_run<true, false>(D, T, O) : bundle_host_run<false, false>(D, T, O);
+  template <class P, class... A>
+  void slots(A... a)
+  {
+    for (int o = 0; o < O; o++) P::run(D, o, a...);
+  }
+  template <class P, class... A>
+  void tracks(A... a)
+  {
+    for (int t = 0; t < T; t++) P::run(D, t, a...);
+  }
+  template <class P, class... A>
+  void images(A... a)
+  {
+    for (int i = 0; i < D.s.nimages; i++) P::run(D, i, a...);
+    if constexpr (P::GROUPS)
+      for (int g = 0; g < P::groups(D); g++) P::group(D, g, a...);
+  }
+  template <class P, class... A>
+  void image_sums(A... a)
+  {
+    for (int i = 0; i < D.s.nimages; i++) P::template run<BundleHostSum>(D, S, i, true, a...);
+  }
+  template <class P>
+  void scalar()
+  {
+    P::template run<BundleHostSum>(D, S, 0, 1, true);
+  }
+  void radial_out(bool refined, bool radial)
+  {
+    for (int g = 0; g < D.ngroups; g++) bundle_radial_out(D, g, refined, radial);
+  }
+};
+
+// The rules of the hooks: false for an argument set the calls refuse (the context and the device's alignment and
+// aliasing rules aside, which the entry points check for themselves).
+inline bool bundle_call_ok(const BundleCall &c)
+{
+  bool ok = c.max_tracks >= 1 && c.max_obs >= 1 && c.nimages >= 1 && c.track_offsets && c.obs && c.export_summary &&
+            c.points && c.point_status && c.cam && c.cam_pair && c.intrinsics && c.nhold >= 0 &&
+            (c.nhold == 0 || c.hold) && c.min_views >= 2 && c.min_obs >= 3 && c.num_loops >= 0 && c.cg_iters >= 0 &&
+            c.max_error > 0.0f && c.lambda0 > 0.0f && fundamental_finite(c.lambda0) &&
+            (c.orthonormalise == 0 || c.orthonormalise == 1) && c.cam_out && c.points_out && c.cam_obs &&
+            c.cam_status && c.cam_rms && c.point_obs && (c.history || c.num_loops == 0) && c.cost && c.summary &&
+            c.loss >= BUNDLE_LOSS_NONE && c.loss <= BUNDLE_LOSS_GEMAN_MCCLURE &&
+            (c.loss == BUNDLE_LOSS_NONE || (c.loss_scale > 0.0f && fundamental_finite(c.loss_scale)));
+  for (int j = 0; ok && j < c.nhold; j++) ok = c.hold[j] >= 0 && c.hold[j] < c.nimages;
+  ok = ok && c.ngroups >= 0 && c.ngroups <= BUNDLE_MAX_GROUPS && (c.ngroups == 0 || c.group);
+  for (int i = 0; ok && c.ngroups > 0 && i < c.nimages; i++) ok = c.group[i] >= -1 && c.group[i] < c.ngroups;
+  ok = ok && (c.radial != nullptr) == (c.k0 != nullptr);
+  for (int g = 0; ok && c.radial && g < c.ngroups; g++)
+    ok = (c.radial[g] == 0 || c.radial[g] == 1) && fundamental_finite(c.k0[g]);
+  return ok;
+}
+
+// The hooks' common body: the whole call on host arrays.  false: an invalid argument, nothing written.
+inline bool bundle_host(const BundleCall &c)
+{
+  if (!bundle_call_ok(c)) return false;
+  const BundleDerived d = bundle_derive(c);
+  const TrackScene scene{c.max_tracks, c.max_obs, c.nimages, c.track_offsets, c.obs, c.export_summary,
+                         c.points, c.point_status, c.cam, c.cam_pair, c.intrinsics};
+  BundleData D = bundle_data(scene, c, d, {d.held.data(), c.ngroups > 0 ? c.group : d.none.data(), d.rad, d.k0});
+  std::vector<char> tmp(bundle_layout(D, nullptr, d.focal, d.radial) + 16, 0);
+  bundle_layout(D, reinterpret_cast<char *>(((uintptr_t)tmp.data() + 15) & ~(uintptr_t)15), d.focal, d.radial);
+  BundleHostExec x{D, scene_T(D.s), scene_O(D.s), {}};
+  bundle_run(x, D, d.focal, d.radial);
   return true;
 }
 

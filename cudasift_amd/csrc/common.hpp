@@ -725,38 +725,18 @@ int launch_transform_scene_batch(misift_ctx *ctx, const float *d_sim, const int 
                                  const int *d_export_summary, const float *d_points, const int *d_point_status,
                                  int nimages, const float *d_cam, const int *d_cam_pair, float *d_points_out,
                                  float *d_cam_out);
-// misift_adjust_bundle_batch and misift_adjust_bundle_robust_batch (kernels_bundle.hip): three memsets + 11 + num_loops *
-// (8 + 3 * cg_iters) launches, one more with d_obs_weight; temp from misift_ensure_tmp, sized from max_tracks, max_obs
-// and nimages only.  h_held: as launch_refine_cameras_batch.  loss 0 and a NULL d_obs_weight is the plain call
-size_t adjust_bundle_batch_tmp_bytes(int max_tracks, int max_obs, int nimages);
-int launch_adjust_bundle_batch(misift_ctx *ctx, const TrackScene &scene, const int *h_held, int min_views, int min_obs,
-                               int num_loops, int cg_iters, float thresh2, float lambda0, int orthonormalise, int loss,
-                               float loss_scale, float loss_scale2, float *d_cam_out, float *d_points_out, int *d_cam_obs,
-                               int *d_cam_status, float *d_cam_rms, int *d_point_obs, float *d_history, float *d_cost,
-                               float *d_obs_weight, int *d_summary);
-// misift_adjust_bundle_focal_batch (kernels_bundle.hip).  h_group: the pinned copy of `group`; focal: an image has a
-// group.  Without one the launches and the temp are those of launch_adjust_bundle_batch, which is this function with no
-// group and no d_intrinsics_out; with d_intrinsics_out one launch more at the end writes it and d_focal
-size_t adjust_bundle_focal_batch_tmp_bytes(int max_tracks, int max_obs, int nimages);
-int launch_adjust_bundle_focal_batch(misift_ctx *ctx, const TrackScene &scene, const int *h_held, int min_views,
-                                     int min_obs, int num_loops, int cg_iters, float thresh2, float lambda0,
-                                     int orthonormalise, int loss, float loss_scale, float loss_scale2, int ngroups,
-                                     const int *h_group, bool focal, float *d_cam_out, float *d_points_out, int *d_cam_obs,
-                                     int *d_cam_status, float *d_cam_rms, int *d_point_obs, float *d_history,
-                                     float *d_cost, float *d_obs_weight, int *d_summary, float *d_intrinsics_out,
-                                     int *d_focal);
-// misift_adjust_bundle_radial_batch (kernels_bundle.hip).  h_radial, h_k0: the pinned copies of `radial` and `k0`, padded
-// with zeros to MISIFT_MAX_RADIAL_GROUPS; radial: an image has a group and some k_g is an unknown or starts off zero.
-// Without that the launches and the temp are those of launch_adjust_bundle_focal_batch; one launch more writes d_radial
-size_t adjust_bundle_radial_batch_tmp_bytes(int max_tracks, int max_obs, int nimages);
-int launch_adjust_bundle_radial_batch(misift_ctx *ctx, const TrackScene &scene, const int *h_held, int min_views,
-                                      int min_obs, int num_loops, int cg_iters, float thresh2, float lambda0,
-                                      int orthonormalise, int loss, float loss_scale, float loss_scale2, int ngroups,
-                                      const int *h_group, bool focal, const int *h_radial, const float *h_k0, bool radial,
-                                      float *d_cam_out, float *d_points_out, int *d_cam_obs, int *d_cam_status,
-                                      float *d_cam_rms, int *d_point_obs, float *d_history, float *d_cost,
-                                      float *d_obs_weight, int *d_summary, float *d_intrinsics_out, int *d_focal,
-                                      int *d_radial);
+// misift_adjust_bundle_batch, _robust_batch, _focal_batch and _radial_batch (kernels_bundle.hip): three memsets + 11 +
+// num_loops * (8 + 3 * cg_iters) launches, one more each with d_obs_weight, with a grouped image, with
+// d_intrinsics_out and with d_radial; temp from misift_ensure_tmp, sized from max_tracks, max_obs and nimages and
+// wider where the FOCAL or the RADIAL instances run.  BundleCall, BundleDerived, BundleLists (bundle_host.hpp): the
+// checked arguments, what bundle_derive made of them, and the pinned copies of the held flags, the groups and, for the
+// radial call, the flags and k0 padded to MISIFT_MAX_RADIAL_GROUPS; scene.intrinsics is pinned too
+struct BundleCall;
+struct BundleDerived;
+struct BundleLists;
+size_t adjust_bundle_batch_tmp_bytes(int max_tracks, int max_obs, int nimages, bool focal, bool radial);
+int launch_adjust_bundle_batch(misift_ctx *ctx, const TrackScene &scene, const BundleCall &call,
+                               const BundleDerived &derived, const BundleLists &pinned);
 // misift_undistort_obs_batch (kernels_bundle.hip): one launch, no temp.  h_intrinsics, h_group: the pinned copies
 int launch_undistort_obs_batch(misift_ctx *ctx, int max_obs, const TrackObs *d_obs, const int *d_export_summary,
                                int nimages, const float *h_intrinsics, const int *h_group, const int *d_radial,

@@ -20,6 +20,7 @@
 #include <utility>
 #include <vector>
 #include "common.hpp"
+#include "bundle_host.hpp"
 #include "chain.hpp"
 #include "merge_core.hpp"
 #include "pair_plan.hpp"
@@ -3002,83 +3003,53 @@ extern "C" int misift_transform_scene_batch(misift_ctx *ctx, const float *d_sim,
   });
 }
 
-// The body of the three bundle calls: the robust call, with ngroups > 0 and a group for some image the focal scales
-// among the unknowns, and with d_intrinsics_out the focal call's two outputs.  With d_radial it is the radial call:
-// `radial` and `k0` (both or neither NULL: all zero) go to the pinned slot behind the groups, padded with zeros.
-static int adjust_bundle(const char *who, misift_ctx *ctx, int max_tracks, int max_obs, const int *d_track_offsets,
-                         const misift_track_obs *d_obs, const int *d_export_summary, const float *d_points,
-                         const int *d_point_status, int nimages, const float *d_cam, const int *d_cam_pair,
-                         const float *intrinsics, int nhold, const int *hold, int min_views, int min_obs, int num_loops,
-                         int cg_iters, float max_error, float lambda0, int orthonormalise, int loss, float loss_scale,
-                         int ngroups, const int *group, float *d_cam_out, float *d_points_out, int *d_cam_obs,
-                         int *d_cam_status, float *d_cam_rms, int *d_point_obs, float *d_history, float *d_cost,
-                         float *d_obs_weight, int *d_summary, float *d_intrinsics_out, int *d_focal,
-                         bool with_radial = false, const int *radial = nullptr, const float *k0 = nullptr,
-                         float *d_radial = nullptr)
+// The body of the four bundle calls, each described by a BundleCall (bundle_host.hpp): the arguments checked, what they
+// derive computed once (bundle_derive), the host lists pinned.  The intrinsics, the held flags and, with
+// d_intrinsics_out, the groups go to the pinned slot in that order; for the radial call `radial` and `k0` (both or
+// neither NULL: all zero) follow, padded with zeros.
+static int adjust_bundle(const char *who, misift_ctx *ctx, const BundleCall &c)
 {
   ARG_CHECK_IN(who, ctx != nullptr);
   TrackScene S;
-  int rc = check_scene(who, &S, max_tracks, max_obs, d_track_offsets, d_obs, d_export_summary, d_points,
-                       d_point_status, nimages, d_cam, d_cam_pair, intrinsics);
+  int rc = check_scene(who, &S, c.max_tracks, c.max_obs, c.track_offsets,
+                       reinterpret_cast<const misift_track_obs *>(c.obs), c.export_summary, c.points, c.point_status,
+                       c.nimages, c.cam, c.cam_pair, c.intrinsics);
   if (rc) return rc;
-  ARG_CHECK_IN(who, d_points && d_point_status && d_cam && d_cam_pair);
-  ARG_CHECK_IN(who, d_cam_out && d_points_out && d_cam_obs && d_cam_status && d_cam_rms && d_point_obs);
-  ARG_CHECK_IN(who, d_cost && d_summary && (d_history || num_loops == 0));
-  ARG_CHECK_IN(who, min_views >= 2 && min_obs >= 3 && num_loops >= 0 && cg_iters >= 0);
-  ARG_CHECK_IN(who, max_error > 0.0f);                                              // NaN fails too
-  ARG_CHECK_IN(who, lambda0 > 0.0f && lambda0 <= 3.402823466e+38f);
-  ARG_CHECK_IN(who, orthonormalise == 0 || orthonormalise == 1);
-  ARG_CHECK_IN(who, loss == MISIFT_LOSS_NONE || loss == MISIFT_LOSS_HUBER || loss == MISIFT_LOSS_GEMAN_MCCLURE);
-  if (loss != MISIFT_LOSS_NONE) ARG_CHECK_IN(who, loss_scale > 0.0f && loss_scale <= 3.402823466e+38f);   // not read with loss 0
-  ARG_CHECK_IN(who, nhold >= 0 && (nhold == 0 || hold));
-  for (int j = 0; j < nhold; j++) ARG_CHECK_IN(who, hold[j] >= 0 && hold[j] < nimages);
-  ARG_CHECK_IN(who, same_or_disjoint(d_cam, d_cam_out, sizeof(float) * 12 * (size_t)nimages));
-  ARG_CHECK_IN(who, same_or_disjoint(d_points, d_points_out, sizeof(float) * 4 * (size_t)max_tracks));
-  ARG_CHECK_IN(who, ngroups >= 0 && ngroups <= MISIFT_MAX_FOCAL_GROUPS && (ngroups == 0 || group));
-  bool focal = false;
-  for (int i = 0; ngroups > 0 && i < nimages; i++) {
-    ARG_CHECK_IN(who, group[i] >= -1 && group[i] < ngroups);
-    focal = focal || group[i] >= 0;
-  }
-  int h_rad[MISIFT_MAX_RADIAL_GROUPS] = {0};
-  float h_k0[MISIFT_MAX_RADIAL_GROUPS] = {0.0f};
-  bool radial_on = false;
-  if (with_radial) {
-    ARG_CHECK_IN(who, (radial != nullptr) == (k0 != nullptr) && (d_radial || ngroups == 0));
-    for (int g = 0; radial && g < ngroups; g++) {
-      ARG_CHECK_IN(who, radial[g] == 0 || radial[g] == 1);
-      ARG_CHECK_IN(who, k0[g] >= -3.402823466e+38f && k0[g] <= 3.402823466e+38f);   // NaN fails too
-      h_rad[g] = radial[g];
-      h_k0[g] = k0[g];
-      radial_on = radial_on || (focal && (h_rad[g] != 0 || h_k0[g] != 0.0f));
+  ARG_CHECK_IN(who, c.points && c.point_status && c.cam && c.cam_pair);
+  ARG_CHECK_IN(who, c.cam_out && c.points_out && c.cam_obs && c.cam_status && c.cam_rms && c.point_obs);
+  ARG_CHECK_IN(who, c.cost && c.summary && (c.history || c.num_loops == 0));
+  ARG_CHECK_IN(who, c.min_views >= 2 && c.min_obs >= 3 && c.num_loops >= 0 && c.cg_iters >= 0);
+  ARG_CHECK_IN(who, c.max_error > 0.0f);                                            // NaN fails too
+  ARG_CHECK_IN(who, c.lambda0 > 0.0f && c.lambda0 <= 3.402823466e+38f);
+  ARG_CHECK_IN(who, c.orthonormalise == 0 || c.orthonormalise == 1);
+  ARG_CHECK_IN(who, c.loss == MISIFT_LOSS_NONE || c.loss == MISIFT_LOSS_HUBER || c.loss == MISIFT_LOSS_GEMAN_MCCLURE);
+  if (c.loss != MISIFT_LOSS_NONE)                                                   // not read with loss 0
+    ARG_CHECK_IN(who, c.loss_scale > 0.0f && c.loss_scale <= 3.402823466e+38f);
+  ARG_CHECK_IN(who, c.nhold >= 0 && (c.nhold == 0 || c.hold));
+  for (int j = 0; j < c.nhold; j++) ARG_CHECK_IN(who, c.hold[j] >= 0 && c.hold[j] < c.nimages);
+  ARG_CHECK_IN(who, same_or_disjoint(c.cam, c.cam_out, sizeof(float) * 12 * (size_t)c.nimages));
+  ARG_CHECK_IN(who, same_or_disjoint(c.points, c.points_out, sizeof(float) * 4 * (size_t)c.max_tracks));
+  ARG_CHECK_IN(who, c.ngroups >= 0 && c.ngroups <= MISIFT_MAX_FOCAL_GROUPS && (c.ngroups == 0 || c.group));
+  for (int i = 0; c.ngroups > 0 && i < c.nimages; i++) ARG_CHECK_IN(who, c.group[i] >= -1 && c.group[i] < c.ngroups);
+  if (c.radial_call) {
+    ARG_CHECK_IN(who, (c.radial != nullptr) == (c.k0 != nullptr) && (c.radial_out || c.ngroups == 0));
+    for (int g = 0; c.radial && g < c.ngroups; g++) {
+      ARG_CHECK_IN(who, c.radial[g] == 0 || c.radial[g] == 1);
+      ARG_CHECK_IN(who, c.k0[g] >= -3.402823466e+38f && c.k0[g] <= 3.402823466e+38f);   // NaN fails too
     }
   }
-  const std::vector<int> held = held_flags(nimages, nhold, hold);
-  const std::vector<int> none(d_intrinsics_out && ngroups == 0 ? nimages : 0, -1);   // the two old calls copy no group
-  const float thresh2 = max_error * max_error;                              // rounded once, here
-  const float c = loss != MISIFT_LOSS_NONE ? loss_scale : 0.0f;
-  const float c2 = c * c;                                                   // and so is this
+  const BundleDerived d = bundle_derive(c);
+  const size_t n = (size_t)c.nimages, padded = c.radial_call ? sizeof d.rad : 0;
   RoctxRange range(who);
-  return run_batch(ctx, {{intrinsics, sizeof(float) * 4 * (size_t)nimages}, {held.data(), sizeof(int) * (size_t)nimages},
-                         {ngroups > 0 ? group : none.data(), d_intrinsics_out ? sizeof(int) * (size_t)nimages : 0},
-                         {h_rad, with_radial ? sizeof h_rad : 0}, {h_k0, with_radial ? sizeof h_k0 : 0}},
+  return run_batch(ctx, {{c.intrinsics, sizeof(float) * 4 * n}, {d.held.data(), sizeof(int) * n},
+                         {c.ngroups > 0 ? c.group : d.none.data(), c.intrinsics_out ? sizeof(int) * n : 0},
+                         {d.rad, padded}, {d.k0, padded}},
                    0, [&](int *h_lists, void *) {
                      S.intrinsics = reinterpret_cast<const float *>(h_lists);
-                     const int *h_held = h_lists + 4 * (size_t)nimages;
-                     if (with_radial) {
-                       const int *p_rad = h_held + 2 * (size_t)nimages;
-                       return launch_adjust_bundle_radial_batch(
-                           ctx, S, h_held, min_views, min_obs, num_loops, cg_iters, thresh2, lambda0, orthonormalise, loss,
-                           c, c2, ngroups, h_held + nimages, focal, p_rad,
-                           reinterpret_cast<const float *>(p_rad + MISIFT_MAX_RADIAL_GROUPS), radial_on, d_cam_out,
-                           d_points_out, d_cam_obs, d_cam_status, d_cam_rms, d_point_obs, d_history, d_cost, d_obs_weight,
-                           d_summary, d_intrinsics_out, d_focal, reinterpret_cast<int *>(d_radial));
-                     }
-                     return launch_adjust_bundle_focal_batch(ctx, S, h_held, min_views, min_obs, num_loops, cg_iters,
-                                                             thresh2, lambda0, orthonormalise, loss, c, c2, ngroups,
-                                                             h_held + nimages, focal, d_cam_out, d_points_out, d_cam_obs,
-                                                             d_cam_status, d_cam_rms, d_point_obs, d_history, d_cost,
-                                                             d_obs_weight, d_summary, d_intrinsics_out, d_focal);
+                     const int *h_held = h_lists + 4 * n, *h_rad = c.radial_call ? h_held + 2 * n : nullptr;
+                     const float *h_k0 =
+                         h_rad ? reinterpret_cast<const float *>(h_rad + MISIFT_MAX_RADIAL_GROUPS) : nullptr;
+                     return launch_adjust_bundle_batch(ctx, S, c, d, {h_held, h_held + n, h_rad, h_k0});
                    });
 }
 
@@ -3095,11 +3066,16 @@ extern "C" int misift_adjust_bundle_robust_batch(misift_ctx *ctx, int max_tracks
                                                  int *d_cam_obs, int *d_cam_status, float *d_cam_rms, int *d_point_obs,
                                                  float *d_history, float *d_cost, float *d_obs_weight, int *d_summary)
 {
-  return adjust_bundle(__func__, ctx, max_tracks, max_obs, d_track_offsets, d_obs, d_export_summary, d_points,
-                       d_point_status, nimages, d_cam, d_cam_pair, intrinsics, nhold, hold, min_views, min_obs, num_loops,
-                       cg_iters, max_error, lambda0, orthonormalise, loss, loss_scale, 0, nullptr, d_cam_out, d_points_out,
-                       d_cam_obs, d_cam_status, d_cam_rms, d_point_obs, d_history, d_cost, d_obs_weight, d_summary,
-                       nullptr, nullptr);
+  return adjust_bundle(
+      __func__, ctx,
+      {.max_tracks = max_tracks, .max_obs = max_obs, .track_offsets = d_track_offsets,
+       .obs = reinterpret_cast<const TrackObs *>(d_obs), .export_summary = d_export_summary, .points = d_points,
+       .point_status = d_point_status, .nimages = nimages, .cam = d_cam, .cam_pair = d_cam_pair, .intrinsics = intrinsics,
+       .nhold = nhold, .hold = hold, .min_views = min_views, .min_obs = min_obs, .num_loops = num_loops,
+       .cg_iters = cg_iters, .max_error = max_error, .lambda0 = lambda0, .orthonormalise = orthonormalise, .loss = loss,
+       .loss_scale = loss_scale, .cam_out = d_cam_out, .points_out = d_points_out, .cam_obs = d_cam_obs,
+       .cam_status = d_cam_status, .cam_rms = d_cam_rms, .point_obs = d_point_obs, .history = d_history, .cost = d_cost,
+       .obs_weight = d_obs_weight, .summary = d_summary});
 }
 
 // The robust call with one focal scale per camera group among the unknowns; the group of every image goes to the pinned
@@ -3117,11 +3093,17 @@ extern "C" int misift_adjust_bundle_focal_batch(misift_ctx *ctx, int max_tracks,
                                                 int *d_focal)
 {
   ARG_CHECK(d_intrinsics_out && (d_focal || ngroups == 0));
-  return adjust_bundle(__func__, ctx, max_tracks, max_obs, d_track_offsets, d_obs, d_export_summary, d_points,
-                       d_point_status, nimages, d_cam, d_cam_pair, intrinsics, nhold, hold, min_views, min_obs, num_loops,
-                       cg_iters, max_error, lambda0, orthonormalise, loss, loss_scale, ngroups, group, d_cam_out,
-                       d_points_out, d_cam_obs, d_cam_status, d_cam_rms, d_point_obs, d_history, d_cost, d_obs_weight,
-                       d_summary, d_intrinsics_out, d_focal);
+  return adjust_bundle(
+      __func__, ctx,
+      {.max_tracks = max_tracks, .max_obs = max_obs, .track_offsets = d_track_offsets,
+       .obs = reinterpret_cast<const TrackObs *>(d_obs), .export_summary = d_export_summary, .points = d_points,
+       .point_status = d_point_status, .nimages = nimages, .cam = d_cam, .cam_pair = d_cam_pair, .intrinsics = intrinsics,
+       .nhold = nhold, .hold = hold, .min_views = min_views, .min_obs = min_obs, .num_loops = num_loops,
+       .cg_iters = cg_iters, .max_error = max_error, .lambda0 = lambda0, .orthonormalise = orthonormalise, .loss = loss,
+       .loss_scale = loss_scale, .ngroups = ngroups, .group = group, .cam_out = d_cam_out, .points_out = d_points_out,
+       .cam_obs = d_cam_obs, .cam_status = d_cam_status, .cam_rms = d_cam_rms, .point_obs = d_point_obs,
+       .history = d_history, .cost = d_cost, .obs_weight = d_obs_weight, .summary = d_summary,
+       .intrinsics_out = d_intrinsics_out, .focal_out = d_focal});
 }
 
 // The focal call with one radial coefficient per camera group among the unknowns (applied to the observation).
@@ -3138,11 +3120,18 @@ extern "C" int misift_adjust_bundle_radial_batch(misift_ctx *ctx, int max_tracks
                                                  int *d_summary, float *d_intrinsics_out, int *d_focal, float *d_radial)
 {
   ARG_CHECK(d_intrinsics_out && (d_focal || ngroups == 0));
-  return adjust_bundle(__func__, ctx, max_tracks, max_obs, d_track_offsets, d_obs, d_export_summary, d_points,
-                       d_point_status, nimages, d_cam, d_cam_pair, intrinsics, nhold, hold, min_views, min_obs, num_loops,
-                       cg_iters, max_error, lambda0, orthonormalise, loss, loss_scale, ngroups, group, d_cam_out,
-                       d_points_out, d_cam_obs, d_cam_status, d_cam_rms, d_point_obs, d_history, d_cost, d_obs_weight,
-                       d_summary, d_intrinsics_out, d_focal, true, radial, k0, d_radial);
+  return adjust_bundle(
+      __func__, ctx,
+      {.max_tracks = max_tracks, .max_obs = max_obs, .track_offsets = d_track_offsets,
+       .obs = reinterpret_cast<const TrackObs *>(d_obs), .export_summary = d_export_summary, .points = d_points,
+       .point_status = d_point_status, .nimages = nimages, .cam = d_cam, .cam_pair = d_cam_pair, .intrinsics = intrinsics,
+       .nhold = nhold, .hold = hold, .min_views = min_views, .min_obs = min_obs, .num_loops = num_loops,
+       .cg_iters = cg_iters, .max_error = max_error, .lambda0 = lambda0, .orthonormalise = orthonormalise, .loss = loss,
+       .loss_scale = loss_scale, .ngroups = ngroups, .group = group, .radial_call = true, .radial = radial, .k0 = k0,
+       .cam_out = d_cam_out, .points_out = d_points_out, .cam_obs = d_cam_obs, .cam_status = d_cam_status,
+       .cam_rms = d_cam_rms, .point_obs = d_point_obs, .history = d_history, .cost = d_cost, .obs_weight = d_obs_weight,
+       .summary = d_summary, .intrinsics_out = d_intrinsics_out, .focal_out = d_focal,
+       .radial_out = reinterpret_cast<int *>(d_radial)});
 }
 
 // An observation list undistorted under the coefficients the radial call left on the device: one launch.  The given

@@ -429,6 +429,56 @@ def test_export_triangulate_refine_radial_adjust_undistort_then_triangulate_and_
                "chain, plain adjust")
 
 
+PROFILE_ENTRIES = ("bundle_setup", "bundle_track", "bundle_image", "bundle_scalar", "bundle_trial", "bundle_out")
+
+
+@pytest.mark.parametrize("loss,scale", BD.LOSSES[:2], ids=("none", "huber"))
+@pytest.mark.parametrize("model", ("plain", "focal", "radial"))
+def test_profile_entries_and_calls(g, model, loss, scale):
+    """The launch structure tools/bundle_time.py reads: with the profile on, a call reports exactly six entries, setup
+    and out once, the per-track, per-image and scalar launches num_loops * (2 + cg_iters) times each, the trial state
+    num_loops times; the same for the plain call, the focal call with every image in one group and the radial call with
+    that group's coefficient an unknown.  Without a loop only setup and out appear."""
+    assert loss in (BD.NONE, BD.HUBER)
+    for num_loops, cg_iters in ((2, 3), (0, 3)):
+        base = BC.planted(40, 4, 1, num_loops=num_loops, cg_iters=cg_iters)["case"]
+        case = {"plain": lambda: BF.focal(base, np.full(base["nimages"], -1), 0, loss=loss, loss_scale=scale),
+                "focal": lambda: BF.one_group(base, loss=loss, loss_scale=scale),
+                "radial": lambda: BD.one_group(base, loss=loss, loss_scale=scale)}[model]()
+        dev = {k: g.upload(v) for k, v in FC.inputs(case).items()}
+        args = (case["max_tracks"], case["max_obs"], dev["track_offsets"], dev["obs"], dev["export_summary"],
+                dev["points"], dev["point_status"], case["nimages"], dev["cam"], dev["cam_pair"], case["intrinsics"])
+        kw = dict(hold=case["hold"], min_views=case["min_views"], min_obs=case["min_obs"], num_loops=num_loops,
+                  cg_iters=cg_iters, max_error=case["max_error"], lambda0=case["lambda0"],
+                  orthonormalise=case["orthonormalise"])
+        lossy = dict(loss=loss, loss_scale=scale, obs_weight=None)
+        g.sync()
+        g.profile_enable(True)
+        g.profile_reset()
+        try:
+            if model == "plain" and loss == BD.NONE:
+                g.adjust_bundle_batch(*args, **kw)
+            elif model == "plain":
+                g.adjust_bundle_robust_batch(*args, **kw, **lossy)
+            elif model == "focal":
+                g.adjust_bundle_focal_batch(*args, case["group"], ngroups=1, **kw, **lossy)
+            else:
+                assert list(case["radial"]) == [1]
+                g.adjust_bundle_radial_batch(*args, case["group"], ngroups=1, radial=case["radial"], k0=case["k0"],
+                                             **kw, **lossy)
+            g.sync()
+            read = g.profile_read()
+        finally:
+            g.profile_enable(False)
+        per_step = num_loops * (2 + cg_iters)
+        want = dict(bundle_setup=1, bundle_track=per_step, bundle_image=per_step, bundle_scalar=per_step,
+                    bundle_trial=num_loops, bundle_out=1)
+        got = {k: v["calls"] for k, v in read.items()}
+        print(model, loss, num_loops, cg_iters, got)
+        assert got == {k: n for k, n in want.items() if n}, (model, num_loops, got)
+        assert set(got) <= set(PROFILE_ENTRIES)
+
+
 def test_guards_intact_at_the_end(g):
     from cudasift_amd import capi
     assert capi.check_guards() >= 1

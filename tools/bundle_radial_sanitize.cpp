@@ -100,14 +100,20 @@ int run(Rng &g, const Scene &S, int loss, int num_loops, int cg_iters, float max
       history(4 * (size_t)(num_loops > 0 ? num_loops : 1)), cost(2), weight(S.mo), kout(4 * (size_t)S.n);
   std::vector<int> cam_obs(S.n), cam_status(S.n), point_obs(S.mt), summary(8), focal(3 * (size_t)(S.G > 0 ? S.G : 1)),
       radial(3 * (size_t)(S.G > 0 ? S.G : 1));
-  const bool ok = bundle_host(S.mt, S.mo, S.off.data(), S.obs.data(), S.summary.data(), S.points.data(), S.status.data(),
-                              S.n, S.cam.data(), S.pair.data(), S.K.data(), (int)S.hold.size(), S.hold.data(), 2, 3,
-                              num_loops, cg_iters, max_error, 1e-3f, g.below(2), loss, 2.0f, S.G,
-                              S.G > 0 ? S.group.data() : nullptr, cam_out.data(), points_out.data(), cam_obs.data(),
-                              cam_status.data(), cam_rms.data(), point_obs.data(), history.data(), cost.data(),
-                              g.below(2) ? weight.data() : nullptr, summary.data(), kout.data(), focal.data(),
-                              lists && S.G > 0 ? S.radial.data() : nullptr, lists && S.G > 0 ? S.k0.data() : nullptr,
-                              radial.data());
+  const bool weights = g.below(2), grouped = S.G > 0;
+  BundleCall c{};
+  c.max_tracks = S.mt; c.max_obs = S.mo; c.track_offsets = S.off.data(); c.obs = S.obs.data();
+  c.export_summary = S.summary.data(); c.points = S.points.data(); c.point_status = S.status.data();
+  c.nimages = S.n; c.cam = S.cam.data(); c.cam_pair = S.pair.data(); c.intrinsics = S.K.data();
+  c.nhold = (int)S.hold.size(); c.hold = S.hold.data(); c.min_views = 2; c.min_obs = 3; c.num_loops = num_loops;
+  c.cg_iters = cg_iters; c.max_error = max_error; c.lambda0 = 1e-3f; c.orthonormalise = g.below(2); c.loss = loss;
+  c.loss_scale = 2.0f; c.ngroups = S.G; c.group = grouped ? S.group.data() : nullptr; c.radial_call = true;
+  c.radial = lists && grouped ? S.radial.data() : nullptr; c.k0 = lists && grouped ? S.k0.data() : nullptr;
+  c.cam_out = cam_out.data(); c.points_out = points_out.data(); c.cam_obs = cam_obs.data();
+  c.cam_status = cam_status.data(); c.cam_rms = cam_rms.data(); c.point_obs = point_obs.data();
+  c.history = history.data(); c.cost = cost.data(); c.obs_weight = weights ? weight.data() : nullptr;
+  c.summary = summary.data(); c.intrinsics_out = kout.data(); c.focal_out = focal.data(); c.radial_out = radial.data();
+  const bool ok = bundle_host(c);
   if (!ok) return 0;
   // the list undistorted under what the call left, out of place and in place
   std::vector<TrackObs> out(S.mo), same(S.obs);
