@@ -699,7 +699,6 @@ int launch_refine_cameras_batch(misift_ctx *ctx, const TrackScene &scene, const 
 // misift_resect_cameras_batch (kernels_resect.hip): two memsets + six launches; temp from misift_ensure_tmp, sized from
 // max_obs, nsel, max_cand and num_loops only.  h_images, h_seeds: the pinned copies, nsel each.  scene.cam and
 // scene.cam_pair are d_cam and d_cam_pair, which may be NULL as the header states
-size_t resect_cameras_batch_tmp_bytes(int max_obs, int nsel, int max_cand, int num_loops);
 bool resect_cameras_batch_one_launch(int max_obs, int nsel, int max_cand, int num_loops);
 int launch_resect_cameras_batch(misift_ctx *ctx, const TrackScene &scene, int nsel, const int *h_images,
                                 const unsigned *h_seeds, int max_cand, int num_loops, float thresh2, int min_inliers,
@@ -707,7 +706,6 @@ int launch_resect_cameras_batch(misift_ctx *ctx, const TrackScene &scene, int ns
                                 int *d_res_cand, int *d_res_inliers, int *d_res_status, int *d_summary);
 // misift_align_points_batch (kernels_align.hip): one memset + five launches; temp from misift_ensure_tmp, sized from nsel,
 // the largest src_cap (max_cap) and num_loops only.  h_ranges (nsel x 4), h_seeds (nsel): the pinned copies
-size_t align_points_batch_tmp_bytes(int nsel, int max_cap, int num_loops);
 bool align_points_batch_one_launch(int nsel, int max_cap, int num_loops);
 int launch_align_points_batch(misift_ctx *ctx, const float *d_src, const int *d_src_status, const float *d_dst,
                               const int *d_dst_status, const int *d_map, int nsel, const int *h_ranges,

@@ -342,35 +342,39 @@ extern "C" int misift_improve_homography(misift_ctx *ctx, void *d_pts, int npts,
 // Improve, one launch: one 64-lane workgroup per entry runs the single call's rounds on the frame's records in place.
 namespace {
 
-struct HomographyModel {
-  static constexpr int SAMPLE = 4, PARAMS = 8;
+struct HomographyModel : RansacPlainLane {
+  typedef RansacArgs Args;
+  static constexpr int SAMPLE = 4, PARAMS = 8, COORDS = 4;
+  static constexpr bool INDEX = true;          // the valid records, which the sample positions go through
   static constexpr bool COUNT_ALL = true;      // TestHomographies tests every record, valid or not
   template <class Ring>
   static __device__ __forceinline__ void draw(LibcRand<Ring> &g, const FastMod31 &fm, int (&p)[4])
   {
     homography_draw4(g, fm, p);
   }
-  static __device__ __forceinline__ bool inlier(const float (&a)[8], float x1, float y1, float x2, float y2,
-                                                float thresh2)
+  static __device__ __forceinline__ bool inlier(const float (&a)[8], Lane, const float (&q)[4], float thresh2)
   {
-    return homography_inlier(a, x1, y1, x2, y2, thresh2);
+    return homography_inlier(a, q[0], q[1], q[2], q[3], thresh2);
   }
   static __device__ __forceinline__ float done(int k) { return k % 4 == 0 ? 1.0f : 0.0f; }      // the identity
   static __device__ __forceinline__ void picked(float *H) { H[8] = 1.0f; }
 };
 
+// Written out, not between ransac_solve_begin and ransac_store_hyp: the fragment brings its own position loads and
+// stores, and this is the kernel whose scratch-resident LU is sensitive to what surrounds it.
 __global__ __launch_bounds__(64) void homo_batch_solve_kernel(RansacArgs G, int hblocks)
 {
+  const RansacSearch &S = G.rs;
   const int e = blockIdx.x / hblocks;
   const int idx = (blockIdx.x % hblocks) * 64 + threadIdx.x;
-  if (G.meta[RANSAC_META * e] == 0 || idx >= G.num_loops) return;
-  const int num_loops = G.lp;                  // the fragment's stride of sample and homo
-  const float *coord = G.coord + (size_t)e * 4 * G.mp16;
-  const int stride = G.mp16;
-  const int *valid = G.valid + (size_t)e * G.mp16;
-  const int *sample = G.sample + (size_t)e * 4 * num_loops;
-  float *homo = G.hyp + (size_t)e * 8 * num_loops;
-  G.hcount[(size_t)e * num_loops + idx] = 0;
+  if (S.meta[RANSAC_META * e] == 0 || idx >= S.num_loops) return;
+  const int num_loops = S.lp;                  // the fragment's stride of sample and homo
+  const float *coord = S.coord + (size_t)e * 4 * S.cap16;
+  const int stride = S.cap16;
+  const int *valid = S.index + (size_t)e * S.cap16;
+  const int *sample = S.sample + (size_t)e * 4 * num_loops;
+  float *homo = S.hyp + (size_t)e * 8 * num_loops;
+  S.hcount[(size_t)e * num_loops + idx] = 0;
 #define HOMO_CORE_SOLVE
 #include "homography_core.inc"
 #undef HOMO_CORE_SOLVE
@@ -414,13 +418,10 @@ int launch_find_homography_batch(misift_ctx *ctx, int nsel, const int *h_frames,
                                  const BatchLayout &set, int max_pts, int num_loops, float min_score,
                                  float max_ambiguity, float thresh, float *H, int *num)
 {
-  const RansacNames names{"misift_find_homography_batch", "homo_batch_gather", "homo_batch_solve", "homo_batch_count",
-                          "homo_batch_pick"};
-  const RansacArgs G = ransac_args(h_frames, h_seeds, set, max_pts, ransac_round16(num_loops), min_score, max_ambiguity,
-                                   thresh, H, num);
-  return ransac_batch_run<HomographyModel>(ctx, names, nsel, G, [&](const RansacArgs &A, int hblocks) {
-    hipLaunchKernelGGL(homo_batch_solve_kernel, dim3(nsel * hblocks), dim3(64), 0, ctx->stream, A, hblocks);
-  });
+  const RansacNames names{"misift_find_homography_batch", "points", "homo_batch_gather", "homo_batch_solve",
+                          "homo_batch_count", "homo_batch_pick"};
+  return ransac_batch_run<HomographyModel>(ctx, names, nsel, h_frames, h_seeds, set, max_pts, ransac_round16(num_loops),
+                                           min_score, max_ambiguity, thresh, H, num, homo_batch_solve_kernel);
 }
 
 int launch_improve_homography_batch(misift_ctx *ctx, int nsel, const int *h_frames, const BatchLayout &set,
@@ -457,13 +458,6 @@ extern "C" int misift_test_homography_samples(unsigned seed, int num_valid, int 
     misift_set_error("misift_test_homography_samples: invalid argument");
     return MISIFT_EINVAL;
   }
-  LibcRand<LibcRandArrayRing> g;
-  g.seed(seed);
-  const FastMod31 fm((uint32_t)num_valid);
-  for (int loop = 0; loop < num_loops; loop++) {
-    int p[4];
-    homography_draw4(g, fm, p);
-    for (int k = 0; k < 4; k++) out[4 * loop + k] = p[k];
-  }
+  ransac_host_samples(seed, num_valid, num_loops, out, homography_draw4<LibcRandArrayRing>);
   return MISIFT_OK;
 }

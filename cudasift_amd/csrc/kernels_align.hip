@@ -6,21 +6,15 @@
 // No reference counterpart.  The arithmetic is align_core.hpp, shared with the host-only test hooks at the end of this
 // file.
 //
-// misift_align_points_batch: one memset (the summary) and five launches, whatever the data (nsel == 0: the memset alone):
-//   align_gather_kernel  one 1024-thread workgroup per entry walks the entry's source points in ascending index; a ballot /
-//                        popcount compaction keeps that order (a sample position p means "the p-th candidate"), and the
-//                        lane of a candidate writes its six coordinates as SoA into the entry's temp, with its index.
-//                        d_inlier gets 0 / -1 here.  Then wave 0 draws the entry's sample positions from libc rand()
-//                        restated on the device (libc_rand.hpp), seeded with seeds[e], one hypothesis after another.
-//   align_solve_kernel   one lane per (entry, hypothesis), 64-lane workgroups, all in registers: positions -> 13 floats.
-//                        It also zeroes the entry's counts.
-//   align_count_kernel   the hot path: one 64-lane workgroup per (entry, 64 hypotheses, 512-candidate chunk).  The chunk's
-//                        six coordinates are staged once in LDS (12 KiB) and read by broadcast; each lane holds one
-//                        hypothesis in registers, tests every candidate of the chunk, then adds its count atomically (an
-//                        integer sum: the order of the chunks does not matter).
-//   align_pick_kernel    one 1024-thread workgroup per entry: the largest count at the smallest index (ransac_pick).
-//   align_refit_kernel   one 256-thread workgroup per entry: the refits (align_refit; the 256-slot sums in 11 KiB of
-//                        LDS), the rms, and every output of the entry.
+// misift_align_points_batch: the search is ransac_batch.hpp's with AlignModel below.  What is this file's: one memset
+// (the summary) and, whatever the data, five launches (nsel == 0: the memset alone):
+//   align_gather_kernel  walks the entry's source points in ascending index; the lane of a candidate writes its six
+//                        coordinates and its index.  d_inlier gets 0 / -1 here.
+//   align_solve_kernel   all in registers: positions -> 13 floats.
+//   (count)              ransac_count_kernel<AlignModel>: align_error2 under the threshold, 12 KiB of LDS.
+//   align_pick_kernel    the picked hypothesis into cur, the tail of the entry's temp, and its count into meta[3].
+//   align_refit_kernel   behind the search, one 256-thread workgroup per entry: the refits (align_refit; the 256-slot
+//                        sums in 11 KiB of LDS), the rms, and every output of the entry.
 // Not built: a reprojection-error inlier test, a local optimisation inside the search.
 #include <stdint.h>
 #include <string.h>
@@ -30,49 +24,54 @@
 
 namespace {
 
-constexpr int ALIGN_META = 4;                  // ints of meta per entry
 constexpr int ALIGN_COORDS = 6;
+constexpr int ALIGN_TAIL = 16;                 // words of temp per entry behind the search's: cur
 
 struct AlignArgs {
+  RansacSearch rs;                             // coord: ax ay az bx by bz of the candidates in index order; index: the
+                                               // source index i of each; meta[1] a done entry's status, [2] candidates,
+                                               // [3] the picked count
   const float *src, *dst;                      // pooled, four floats per point
   const int *src_status, *dst_status;          // pooled, or NULL
   const int *map;                              // pooled with src
-  const int *ranges;                           // the pinned host copies: nsel x 4,
-  const unsigned *seeds;                       // nsel
+  const int *ranges;                           // the pinned host copy: nsel x 4
   const int *count;                            // device, or NULL
   long long count_stride;
-  int nsel, mc16;                              // mc16 = the largest src_cap rounded up to 16
-  int num_loops, lp;                           // hypotheses; their stride, num_loops rounded up to 16
   int min_inliers, refit_loops;
-  float thresh2;
-  // temp, per entry e:  coord[6 x mc16] | index[mc16] | sample[3 x lp] | hyp[13 x lp] | hcount[lp] | meta[4] | cur[16]
-  float *coord;                                // ax ay az bx by bz of the candidates in index order, SoA
-  int *index;                                  // the source index i of each candidate
-  int *sample;
-  float *hyp;
-  int *hcount;
-  int *meta;                                   // [0] candidates to count (0: entry done), [1] a done entry's status,
-                                               // [2] candidates, [3] the picked count
-  float *cur;                                  // the picked hypothesis
+  float *cur;                                  // temp: the picked hypothesis
   float *sim;
   int *cand, *inliers, *status, *inlier, *summary;
 };
 
+struct AlignModel : RansacPlainLane {
+  typedef AlignArgs Args;
+  static constexpr int SAMPLE = ALIGN_SAMPLE, PARAMS = ALIGN_PARAMS, COORDS = ALIGN_COORDS;
+  static constexpr bool INDEX = true, COUNT_ALL = true;
+  template <class Ring>
+  static __device__ __forceinline__ void draw(LibcRand<Ring> &g, const FastMod31 &fm, int (&p)[ALIGN_SAMPLE])
+  {
+    align_draw3(g, fm, p);
+  }
+  static __device__ __forceinline__ bool inlier(const float (&g)[ALIGN_PARAMS], Lane, const float (&q)[6], float thresh2)
+  {
+    return align_error2(g, q[0], q[1], q[2], q[3], q[4], q[5]) < thresh2;
+  }
+  static __device__ __forceinline__ float invalid() { return pose_one_nan(NAN); }      // align_invalid
+};
+
 __global__ __launch_bounds__(1024) void align_gather_kernel(AlignArgs A)
 {
-  __shared__ int wave_cnt[16];
-  __shared__ int base_s;
-  const int e = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const RansacSearch &S = A.rs;
+  const int e = blockIdx.x, tid = threadIdx.x;
   const int src_first = A.ranges[4 * e], src_cap = A.ranges[4 * e + 1];
   const int dst_first = A.ranges[4 * e + 2], dst_cap = A.ranges[4 * e + 3];
   int ne = src_cap;
   if (A.count) ne = scene_clamp(A.count[(long long)e * A.count_stride], src_cap);
-  int *meta = A.meta + (size_t)ALIGN_META * e;
-  const int mc = A.mc16;
-  float *coord = A.coord + (size_t)e * ALIGN_COORDS * mc;
-  int *index = A.index + (size_t)e * mc;
-  if (tid == 0) base_s = 0;
-  __syncthreads();
+  int *meta = S.meta + (size_t)RANSAC_META * e;
+  const int mc = S.cap16;
+  float *coord = S.coord + (size_t)e * ALIGN_COORDS * mc;
+  int *index = S.index + (size_t)e * mc;
+  const RansacCompaction c = ransac_compaction();
   for (int i0 = 0; i0 < src_cap; i0 += 1024) {
     const int i = i0 + tid;
     bool ok = false;
@@ -91,12 +90,7 @@ __global__ __launch_bounds__(1024) void align_gather_kernel(AlignArgs A)
         }
       }
     }
-    const unsigned long long m = __ballot(ok);
-    if (lane == 0) wave_cnt[wave] = __popcll(m);
-    __syncthreads();
-    int off = base_s;
-    for (int w = 0; w < wave; w++) off += wave_cnt[w];
-    const int pos = off + __popcll(m & ((1ull << lane) - 1ull));
+    const int pos = c.place(ok);
     if (ok) {                                  // pos <= i < src_cap <= mc
 #pragma unroll
       for (int k = 0; k < 3; k++) {
@@ -106,55 +100,32 @@ __global__ __launch_bounds__(1024) void align_gather_kernel(AlignArgs A)
       index[pos] = i;
     }
     if (A.inlier && i < src_cap) A.inlier[(size_t)src_first + (size_t)i] = ok ? 0 : -1;
-    __syncthreads();
-    if (tid == 0) {
-      int s = 0;
-      for (int w = 0; w < 16; w++) s += wave_cnt[w];
-      base_s += s;
-    }
-    __syncthreads();
+    c.next();
   }
-  const int n = base_s;
+  const int n = c.total();
   const int need = A.min_inliers > ALIGN_SAMPLE ? A.min_inliers : ALIGN_SAMPLE;
   if (n < need) {
     if (tid == 0) { meta[0] = 0; meta[1] = ALIGN_FEW_CAND; meta[2] = n; meta[3] = 0; }
     return;
   }
-  if (tid < 64) {                              // wave 0: the entry's rand() stream, hypotheses one after another
-    const int L = A.num_loops, lp = A.lp;
-    int *sample = A.sample + (size_t)e * ALIGN_SAMPLE * lp;
-    LibcRand<LibcRandWaveRing> g;
-    g.seed(A.seeds[e]);
-    const FastMod31 fm((uint32_t)n);
-    for (int loop = 0; loop < L; loop++) {
-      int p[ALIGN_SAMPLE];
-      align_draw3(g, fm, p);
-      if (tid == 0)
-        for (int k = 0; k < ALIGN_SAMPLE; k++) sample[k * lp + loop] = p[k];
-    }
+  if (tid < 64) {                              // wave 0
+    ransac_draw<AlignModel>(S.seeds[e], n, S.sample + (size_t)e * ALIGN_SAMPLE * S.lp, S.num_loops, S.lp);
     if (tid == 0) { meta[0] = n; meta[1] = 0; meta[2] = n; meta[3] = 0; }
   }
 }
 
 __global__ __launch_bounds__(64) void align_solve_kernel(AlignArgs A, int hblocks)
 {
-  const int e = blockIdx.x / hblocks;
-  const int idx = (blockIdx.x % hblocks) * 64 + threadIdx.x;
-  const int *meta = A.meta + (size_t)ALIGN_META * e;
-  const int n = min(meta[0], A.mc16);
-  if (n <= 0 || idx >= A.num_loops) return;
-  const int lp = A.lp, mc = A.mc16;
-  const float *coord = A.coord + (size_t)e * ALIGN_COORDS * mc;
-  const int *sample = A.sample + (size_t)e * ALIGN_SAMPLE * lp;
-  A.hcount[(size_t)e * lp + idx] = 0;
+  const RansacSearch &S = A.rs;
+  int e, idx, n;
+  if (!ransac_solve_begin(S, hblocks, e, idx, n)) return;
+  const int mc = S.cap16;
+  const float *coord = S.coord + (size_t)e * ALIGN_COORDS * mc;
   float a[3][3], b[3][3];
-  bool in_range = true;                        // positions come from device memory: checked before use
+  bool in_range = true;
 #pragma unroll
   for (int k = 0; k < ALIGN_SAMPLE; k++) {
-    const int pos = sample[k * lp + idx];
-    const bool pos_ok = (unsigned)pos < (unsigned)n;
-    const int i = pos_ok ? pos : 0;
-    in_range = in_range && pos_ok;
+    const int i = ransac_sample_position<AlignModel>(S, e, idx, k, n, in_range);
 #pragma unroll
     for (int j = 0; j < 3; j++) {
       a[k][j] = coord[j * mc + i];
@@ -163,58 +134,22 @@ __global__ __launch_bounds__(64) void align_solve_kernel(AlignArgs A, int hblock
   }
   float h[ALIGN_PARAMS];
   align_solve3(a, b, h);
-  if (!in_range) align_invalid(h);
-  float *hyp = A.hyp + (size_t)e * ALIGN_PARAMS * lp;
-#pragma unroll
-  for (int j = 0; j < ALIGN_PARAMS; j++) hyp[j * lp + idx] = h[j];
-}
-
-__global__ __launch_bounds__(64) void align_count_kernel(AlignArgs A, int hblocks, int chunks)
-{
-  __shared__ float4 s_a[RANSAC_CHUNK];         // ax, ay, az, bx
-  __shared__ float2 s_b[RANSAC_CHUNK];         // by, bz
-  const int c = blockIdx.x % chunks, eh = blockIdx.x / chunks;
-  const int e = eh / hblocks, hb = eh % hblocks;
-  const int *meta = A.meta + (size_t)ALIGN_META * e;
-  const int total = min(meta[0], A.mc16);
-  const int i0 = c * RANSAC_CHUNK;
-  if (i0 >= total) return;                     // beyond the candidates, or an entry already done (0)
-  const int n = min(RANSAC_CHUNK, total - i0);
-  const int lp = A.lp, mc = A.mc16;
-  const float *coord = A.coord + (size_t)e * ALIGN_COORDS * mc + i0;
-  for (int i = threadIdx.x; i < n; i += 64) {
-    s_a[i] = make_float4(coord[i], coord[mc + i], coord[2 * mc + i], coord[3 * mc + i]);
-    s_b[i] = make_float2(coord[4 * mc + i], coord[5 * mc + i]);
-  }
-  __syncthreads();
-  const int h = hb * 64 + threadIdx.x;
-  if (h >= A.num_loops) return;
-  const float *hyp = A.hyp + (size_t)e * ALIGN_PARAMS * lp;
-  float g[ALIGN_PARAMS];
-#pragma unroll
-  for (int j = 0; j < ALIGN_PARAMS; j++) g[j] = hyp[j * lp + h];
-  const float thresh2 = A.thresh2;
-  int cnt = 0;
-  for (int i = 0; i < n; i++) {
-    const float4 q = s_a[i];
-    const float2 r = s_b[i];
-    cnt += align_error2(g, q.x, q.y, q.z, q.w, r.x, r.y) < thresh2 ? 1 : 0;
-  }
-  atomicAdd(&A.hcount[(size_t)e * lp + h], cnt);
+  ransac_store_hyp<AlignModel>(S, e, idx, in_range, h);
 }
 
 __global__ __launch_bounds__(1024) void align_pick_kernel(AlignArgs A)
 {
+  const RansacSearch &S = A.rs;
   const int e = blockIdx.x, tid = threadIdx.x;
-  int *meta = A.meta + (size_t)ALIGN_META * e;
+  int *meta = S.meta + (size_t)RANSAC_META * e;
   if (meta[0] == 0) return;
-  const unsigned long long best = ransac_pick(A.hcount + (size_t)e * A.lp, A.num_loops);
+  const unsigned long long best = ransac_pick(S.hcount + (size_t)e * S.lp, S.num_loops);
   if (tid != 0) return;
-  const int idx = min(max(ransac_pick_index(best), 0), A.num_loops - 1);
-  const float *hyp = A.hyp + (size_t)e * ALIGN_PARAMS * A.lp;
-  float *cur = A.cur + 16 * (size_t)e;
+  const int idx = min(max(ransac_pick_index(best), 0), S.num_loops - 1);
+  const float *hyp = S.hyp + (size_t)e * ALIGN_PARAMS * S.lp;
+  float *cur = A.cur + ALIGN_TAIL * (size_t)e;
 #pragma unroll
-  for (int j = 0; j < ALIGN_PARAMS; j++) cur[j] = hyp[j * A.lp + idx];
+  for (int j = 0; j < ALIGN_PARAMS; j++) cur[j] = hyp[j * S.lp + idx];
   meta[3] = ransac_pick_count(best);
 }
 
@@ -271,9 +206,10 @@ __global__ __launch_bounds__(FUND_SLOTS) void align_refit_kernel(AlignArgs A)
 {
   __shared__ float s_p[ALIGN_MOMENT_SUMS * FUND_SLOTS];
   __shared__ int s_cnt[4];
+  const RansacSearch &S = A.rs;
   const int e = blockIdx.x, tid = threadIdx.x;
-  const int *meta = A.meta + (size_t)ALIGN_META * e;
-  const int n = min(meta[0], A.mc16);          // 0: the gather marked the entry done
+  const int *meta = S.meta + (size_t)RANSAC_META * e;
+  const int n = min(meta[0], S.cap16);         // 0: the gather marked the entry done
   int status = meta[1], inliers = 0, kept = 0;
   float h[ALIGN_PARAMS], rms = 0.0f;
 #pragma unroll
@@ -282,21 +218,21 @@ __global__ __launch_bounds__(FUND_SLOTS) void align_refit_kernel(AlignArgs A)
     inliers = meta[3];
     status = inliers < A.min_inliers ? ALIGN_NO_MODEL : ALIGN_OK;
   }
-  const AlignTempCand cand{A.coord + (size_t)e * ALIGN_COORDS * A.mc16, A.mc16};
+  const AlignTempCand cand{S.coord + (size_t)e * ALIGN_COORDS * S.cap16, S.cap16};
   if (n > 0 && status == ALIGN_OK) {
-    const float *cur = A.cur + 16 * (size_t)e;
+    const float *cur = A.cur + ALIGN_TAIL * (size_t)e;
 #pragma unroll
     for (int j = 0; j < ALIGN_PARAMS; j++) h[j] = cur[j];
     AlignBlockExec ex{s_p, s_cnt};
-    align_refit(ex, cand, n, A.thresh2, A.refit_loops, h, inliers, kept, rms);
+    align_refit(ex, cand, n, S.thresh2, A.refit_loops, h, inliers, kept, rms);
     if (A.inlier) {
       const int src_first = A.ranges[4 * e], src_cap = A.ranges[4 * e + 1];
-      const int *index = A.index + (size_t)e * A.mc16;
+      const int *index = S.index + (size_t)e * S.cap16;
       for (int p = tid; p < n; p += FUND_SLOTS) {
         float a[3], b[3];
         cand.load(p, a, b);
         const int i = index[p];
-        if (align_error2(h, a[0], a[1], a[2], b[0], b[1], b[2]) < A.thresh2 && (unsigned)i < (unsigned)src_cap)
+        if (align_error2(h, a[0], a[1], a[2], b[0], b[1], b[2]) < S.thresh2 && (unsigned)i < (unsigned)src_cap)
           A.inlier[(size_t)src_first + (size_t)i] = 1;
       }
     }
@@ -318,13 +254,6 @@ __global__ __launch_bounds__(FUND_SLOTS) void align_refit_kernel(AlignArgs A)
     atomicAdd(&A.summary[5], kept);
   }
   atomicAdd(&A.summary[4], meta[2]);
-}
-
-// the words of temp one entry takes
-size_t align_entry_words(int max_cap, int num_loops)
-{
-  return (ALIGN_COORDS + 1) * (size_t)ransac_round16(max_cap) +
-         (ALIGN_SAMPLE + ALIGN_PARAMS + 1) * (size_t)ransac_round16(num_loops) + ALIGN_META + 16;
 }
 
 // ---- misift_correspond_tracks_batch
@@ -428,18 +357,9 @@ __global__ __launch_bounds__(256) void transform_scene_kernel(TransformArgs A)
 
 }  // namespace
 
-// whether the count's grid, nsel x hypothesis blocks x chunks, fits one launch (and num_loops its stride)
 bool align_points_batch_one_launch(int nsel, int max_cap, int num_loops)
 {
-  const long long hb = ((long long)num_loops + 63) / 64;
-  const long long ch = ((long long)max_cap + RANSAC_CHUNK - 1) / RANSAC_CHUNK;
-  return num_loops <= 0x7fffffff - 15 && max_cap <= 0x7fffffff - 15 && nsel * hb <= 0x7fffffffLL &&
-         nsel * hb * ch <= 0x7fffffffLL;
-}
-
-size_t align_points_batch_tmp_bytes(int nsel, int max_cap, int num_loops)
-{
-  return sizeof(int) * (size_t)nsel * align_entry_words(max_cap, num_loops);
+  return ransac_one_launch(nsel, max_cap, num_loops);
 }
 
 // Enqueue misift_align_points_batch on the context stream (common.hpp): one memset and five launches.  h_ranges and
@@ -450,60 +370,29 @@ int launch_align_points_batch(misift_ctx *ctx, const float *d_src, const int *d_
                               float thresh2, int min_inliers, int refit_loops, float *d_sim, int *d_align_cand,
                               int *d_align_inliers, int *d_align_status, int *d_inlier, int *d_summary)
 {
-  if (!align_points_batch_one_launch(nsel, max_cap, num_loops)) {                            // the wrapper's check
-    misift_set_error("misift_align_points_batch: %d entries x %d loops x %d candidates is beyond one launch", nsel,
-                     num_loops, max_cap);
-    return MISIFT_EINVAL;
-  }
+  const RansacNames names{"misift_align_points_batch", "candidates", "align_gather", "align_solve", "align_count",
+                          "align_pick"};
+  AlignArgs A{};
+  int rc = ransac_search(names, nsel, max_cap, num_loops, thresh2, h_seeds, A.rs);
+  if (rc) return rc;
   HIP_TRY(hipMemsetAsync(d_summary, 0, 8 * sizeof(int), ctx->stream));
   if (nsel == 0) return MISIFT_OK;
-  AlignArgs A{};
-  A.src = d_src; A.dst = d_dst; A.src_status = d_src_status; A.dst_status = d_dst_status; A.map = d_map;
-  A.ranges = h_ranges; A.seeds = h_seeds; A.count = d_count; A.count_stride = count_stride;
-  A.nsel = nsel; A.mc16 = ransac_round16(max_cap);
-  A.num_loops = num_loops; A.lp = ransac_round16(num_loops);
-  A.min_inliers = min_inliers; A.refit_loops = refit_loops; A.thresh2 = thresh2;
-  const int hblocks = (num_loops + 63) / 64, chunks = (A.mc16 + RANSAC_CHUNK - 1) / RANSAC_CHUNK;
-  const int rc = misift_ensure_tmp(ctx, align_points_batch_tmp_bytes(nsel, max_cap, num_loops));
+  void *tail;
+  rc = ransac_temp<AlignModel>(ctx, A.rs, 0, ALIGN_TAIL, &tail);
   if (rc) return rc;
-  const size_t ns = (size_t)nsel, mc = (size_t)A.mc16, lp = (size_t)A.lp;
-  A.coord = reinterpret_cast<float *>(ctx->d_match_tmp);
-  A.index = reinterpret_cast<int *>(A.coord + ns * ALIGN_COORDS * mc);
-  A.sample = A.index + ns * mc;
-  A.hyp = reinterpret_cast<float *>(A.sample + ns * ALIGN_SAMPLE * lp);
-  A.hcount = reinterpret_cast<int *>(A.hyp + ns * ALIGN_PARAMS * lp);
-  A.meta = A.hcount + ns * lp;
-  A.cur = reinterpret_cast<float *>(A.meta + ns * ALIGN_META);
+  A.cur = static_cast<float *>(tail);
+  A.src = d_src; A.dst = d_dst; A.src_status = d_src_status; A.dst_status = d_dst_status; A.map = d_map;
+  A.ranges = h_ranges; A.count = d_count; A.count_stride = count_stride;
+  A.min_inliers = min_inliers; A.refit_loops = refit_loops;
   A.sim = d_sim; A.cand = d_align_cand; A.inliers = d_align_inliers; A.status = d_align_status; A.inlier = d_inlier;
   A.summary = d_summary;
-  int r;
-  {
-    LaunchScope ls(ctx, "align_gather");
-    hipLaunchKernelGGL(align_gather_kernel, dim3(nsel), dim3(1024), 0, ctx->stream, A);
-    r = ls.finish();
-    if (r) return r;
-  }
-  {
-    LaunchScope ls(ctx, "align_solve");
-    hipLaunchKernelGGL(align_solve_kernel, dim3(nsel * hblocks), dim3(64), 0, ctx->stream, A, hblocks);
-    r = ls.finish();
-    if (r) return r;
-  }
-  {
-    LaunchScope ls(ctx, "align_count");
-    hipLaunchKernelGGL(align_count_kernel, dim3(nsel * hblocks * chunks), dim3(64), 0, ctx->stream, A, hblocks, chunks);
-    r = ls.finish();
-    if (r) return r;
-  }
-  {
-    LaunchScope ls(ctx, "align_pick");
-    hipLaunchKernelGGL(align_pick_kernel, dim3(nsel), dim3(1024), 0, ctx->stream, A);
-    r = ls.finish();
-    if (r) return r;
-  }
-  LaunchScope ls(ctx, "align_refit");
-  hipLaunchKernelGGL(align_refit_kernel, dim3(nsel), dim3(FUND_SLOTS), 0, ctx->stream, A);
-  return ls.finish();
+  rc = ransac_launches<AlignModel>(
+      ctx, names, A, [&] { hipLaunchKernelGGL(align_gather_kernel, dim3(nsel), dim3(1024), 0, ctx->stream, A); },
+      align_solve_kernel, [&] { hipLaunchKernelGGL(align_pick_kernel, dim3(nsel), dim3(1024), 0, ctx->stream, A); });
+  if (rc) return rc;
+  return ransac_scope(ctx, "align_refit", [&] {
+    hipLaunchKernelGGL(align_refit_kernel, dim3(nsel), dim3(FUND_SLOTS), 0, ctx->stream, A);
+  });
 }
 
 // Enqueue misift_correspond_tracks_batch: three memsets and two launches; temp: two ints per track of A's capacity.
@@ -563,14 +452,7 @@ extern "C" int misift_test_align_samples(unsigned seed, int n, int num_loops, in
     misift_set_error("misift_test_align_samples: invalid argument");
     return MISIFT_EINVAL;
   }
-  LibcRand<LibcRandArrayRing> g;
-  g.seed(seed);
-  const FastMod31 fm((uint32_t)n);
-  for (int loop = 0; loop < num_loops; loop++) {
-    int p[ALIGN_SAMPLE];
-    align_draw3(g, fm, p);
-    for (int k = 0; k < ALIGN_SAMPLE; k++) out[ALIGN_SAMPLE * loop + k] = p[k];
-  }
+  ransac_host_samples(seed, n, num_loops, out, align_draw3<LibcRandArrayRing>);
   return MISIFT_OK;
 }
 

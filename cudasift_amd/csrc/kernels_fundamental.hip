@@ -22,21 +22,23 @@
 
 namespace {
 
-struct FundamentalModel {
-  static constexpr int SAMPLE = 8, PARAMS = 9;
+struct FundamentalModel : RansacPlainLane {
+  typedef RansacArgs Args;
+  static constexpr int SAMPLE = 8, PARAMS = 9, COORDS = 4;
+  static constexpr bool INDEX = true;          // the valid records
   static constexpr bool COUNT_ALL = false;     // only the records that pass the gate vote
   template <class Ring>
   static __device__ __forceinline__ void draw(LibcRand<Ring> &g, const FastMod31 &fm, int (&p)[8])
   {
     fundamental_draw8(g, fm, p);
   }
-  static __device__ __forceinline__ bool inlier(const float (&F)[9], float x1, float y1, float x2, float y2,
-                                                float thresh2)
+  static __device__ __forceinline__ bool inlier(const float (&F)[9], Lane, const float (&q)[4], float thresh2)
   {
     float den;
-    const float e2 = fundamental_sampson(F, x1, y1, x2, y2, den);
+    const float e2 = fundamental_sampson(F, q[0], q[1], q[2], q[3], den);
     return fundamental_inlier(e2, den, thresh2);
   }
+  static __device__ __forceinline__ float invalid() { return 0.0f; }
   static __device__ __forceinline__ float done(int) { return 0.0f; }
   static __device__ __forceinline__ void picked(float *) {}
 };
@@ -51,24 +53,18 @@ struct FundamentalLdsMat {
 __global__ __launch_bounds__(64) void fund_batch_solve_kernel(RansacArgs G, int hblocks)
 {
   __shared__ float s_m[72 * 64];
-  const int e = blockIdx.x / hblocks;
-  const int idx = (blockIdx.x % hblocks) * 64 + threadIdx.x;
-  const int *meta = G.meta + (size_t)RANSAC_META * e;
-  const int num_valid = meta[0], npts = meta[2];
-  if (num_valid == 0 || idx >= G.num_loops) return;
-  const int lp = G.lp, mp = G.mp16;
-  const float *coord = G.coord + (size_t)e * 4 * mp;
-  const int *valid = G.valid + (size_t)e * mp;
-  const int *sample = G.sample + (size_t)e * 8 * lp;
-  G.hcount[(size_t)e * lp + idx] = 0;
+  const RansacSearch &S = G.rs;
+  int e, idx, num_valid;
+  if (!ransac_solve_begin(S, hblocks, e, idx, num_valid)) return;
+  const int npts = S.meta[(size_t)RANSAC_META * e + 2], mp = S.cap16;
+  const float *coord = S.coord + (size_t)e * 4 * mp;
+  const int *valid = S.index + (size_t)e * mp;
   float x1[8], y1[8], x2[8], y2[8];
-  bool in_range = true;                        // positions and record indices come from device memory: checked before use
+  bool in_range = true;                        // the record indices come from device memory too: checked before use
 #pragma unroll
   for (int k = 0; k < 8; k++) {
-    const int pos = sample[k * lp + idx];
-    const bool pos_ok = (unsigned)pos < (unsigned)num_valid;
-    const int pt = valid[pos_ok ? pos : 0];
-    const bool pt_ok = pos_ok && (unsigned)pt < (unsigned)npts;
+    const int pt = valid[ransac_sample_position<FundamentalModel>(S, e, idx, k, num_valid, in_range)];
+    const bool pt_ok = (unsigned)pt < (unsigned)npts;
     const int i = pt_ok ? pt : 0;
     in_range = in_range && pt_ok;
     x1[k] = coord[i]; y1[k] = coord[mp + i]; x2[k] = coord[2 * mp + i]; y2[k] = coord[3 * mp + i];
@@ -76,9 +72,7 @@ __global__ __launch_bounds__(64) void fund_batch_solve_kernel(RansacArgs G, int 
   FundamentalLdsMat m{s_m + threadIdx.x};
   float F[9];
   fundamental_solve8(m, x1, y1, x2, y2, F);
-  float *hyp = G.hyp + (size_t)e * 9 * lp;
-#pragma unroll
-  for (int k = 0; k < 9; k++) hyp[k * lp + idx] = in_range ? F[k] : 0.0f;
+  ransac_store_hyp<FundamentalModel>(S, e, idx, in_range, F);
 }
 
 struct FbScoreArgs {
@@ -271,12 +265,10 @@ int launch_find_fundamental_batch(misift_ctx *ctx, int nsel, const int *h_frames
                                   const BatchLayout &set, int max_pts, int num_loops, float min_score,
                                   float max_ambiguity, float thresh, float *F, int *num)
 {
-  const RansacNames names{"misift_find_fundamental_batch", "fund_batch_gather", "fund_batch_solve", "fund_batch_count",
-                          "fund_batch_pick"};
-  const RansacArgs G = ransac_args(h_frames, h_seeds, set, max_pts, num_loops, min_score, max_ambiguity, thresh, F, num);
-  return ransac_batch_run<FundamentalModel>(ctx, names, nsel, G, [&](const RansacArgs &A, int hblocks) {
-    hipLaunchKernelGGL(fund_batch_solve_kernel, dim3(nsel * hblocks), dim3(64), 0, ctx->stream, A, hblocks);
-  });
+  const RansacNames names{"misift_find_fundamental_batch", "points", "fund_batch_gather", "fund_batch_solve",
+                          "fund_batch_count", "fund_batch_pick"};
+  return ransac_batch_run<FundamentalModel>(ctx, names, nsel, h_frames, h_seeds, set, max_pts, num_loops, min_score,
+                                            max_ambiguity, thresh, F, num, fund_batch_solve_kernel);
 }
 
 int launch_score_fundamental_batch(misift_ctx *ctx, int nsel, const int *h_frames, const BatchLayout &set,
@@ -315,14 +307,7 @@ extern "C" int misift_test_fundamental_samples(unsigned seed, int num_valid, int
     misift_set_error("misift_test_fundamental_samples: invalid argument");
     return MISIFT_EINVAL;
   }
-  LibcRand<LibcRandArrayRing> g;
-  g.seed(seed);
-  const FastMod31 fm((uint32_t)num_valid);
-  for (int loop = 0; loop < num_loops; loop++) {
-    int p[8];
-    fundamental_draw8(g, fm, p);
-    for (int k = 0; k < 8; k++) out[8 * loop + k] = p[k];
-  }
+  ransac_host_samples(seed, num_valid, num_loops, out, fundamental_draw8<LibcRandArrayRing>);
   return MISIFT_OK;
 }
 
