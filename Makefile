@@ -15,7 +15,7 @@ HIPSRCS  := $(CSRC)/kernels_pyramid.hip $(CSRC)/kernels_dog.hip $(CSRC)/kernels_
             $(CSRC)/kernels_posegraph.hip $(CSRC)/kernels_triangulate.hip $(CSRC)/kernels_refine.hip \
             $(CSRC)/kernels_resect.hip $(CSRC)/kernels_bundle.hip $(CSRC)/kernels_filter.hip \
             $(CSRC)/kernels_track_candidates.hip $(CSRC)/kernels_select.hip $(CSRC)/kernels_align.hip \
-            $(CSRC)/kernels_merge.hip
+            $(CSRC)/kernels_merge.hip $(CSRC)/kernels_localize.hip
 HIPOBJS  := $(patsubst $(CSRC)/%.hip,$(BUILD)/%.o,$(HIPSRCS))
 
 all: cudasift_amd/libmisift.so cudasift_amd/libcudasift.so cudasift_amd/libcudasift_managed.so oracle dropin build/pmc_calib build/valu_rates build/scan_rates build/single_call
@@ -24,7 +24,7 @@ $(BUILD)/%.o: $(CSRC)/%.hip $(CSRC)/common.hpp $(CSRC)/chain.hpp $(CSRC)/match_s
             $(CSRC)/homography_core.inc $(CSRC)/ransac_batch.hpp $(CSRC)/fundamental_core.hpp $(CSRC)/pose_core.hpp $(CSRC)/pose_planar_core.hpp $(CSRC)/posegraph_core.hpp \
             $(CSRC)/epipolar_core.hpp $(CSRC)/triangulate_core.hpp $(CSRC)/refine_core.hpp \
             $(CSRC)/resect_core.hpp $(CSRC)/bundle_core.hpp $(CSRC)/bundle_host.hpp $(CSRC)/filter_core.hpp $(CSRC)/scan_core.hpp \
-            $(CSRC)/track_candidates.hpp $(CSRC)/select_core.hpp $(CSRC)/align_core.hpp $(CSRC)/merge_core.hpp \
+            $(CSRC)/track_candidates.hpp $(CSRC)/select_core.hpp $(CSRC)/align_core.hpp $(CSRC)/merge_core.hpp $(CSRC)/localize_core.hpp $(CSRC)/resect_model.hpp \
             $(CSRC)/libc_rand.hpp $(CSRC)/quantize_i8.hpp $(CSRC)/pair_plan.hpp $(CSRC)/pair_plan_body.inc include/misift.h
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@

@@ -170,6 +170,13 @@ SIGNATURES = {
                                          _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "misift_test_resect_samples": (_i, [C.c_uint, _i, _i, _vp]),
     "misift_test_resect_solve": (_i, [_vp, _vp, _vp, _vp]),
+    "misift_describe_points_batch": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp,
+                                          _vp, _vp]),
+    "misift_test_describe_points": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp,
+                                         _vp]),
+    "misift_localize_frames_batch": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i,
+                                          _f, _f, _i, _f, _i, _i, _i] + 7 * [_vp] + [_i] + 7 * [_vp]),
+    "misift_test_localize_candidates": (_i, [_vp, _i, _i, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp]),
     "misift_correspond_tracks_batch": (_i, [_vp, _i, _i, _vp, _i, _i, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     "misift_align_points_batch": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _f, _i, _i, _vp, _vp, _vp,
                                        _vp, _vp, _vp]),
@@ -1465,6 +1472,79 @@ class Context:
                                                 _dptr(res_inliers), _dptr(res_status), _dptr(summary)),
               "misift_resect_cameras_batch")
         return res_cam, res_cand, res_inliers, res_status, summary
+
+    def describe_points_batch(self, max_tracks, max_obs, track_offsets, obs, export_summary, points, point_status, q,
+                              nframes, counts, offsets=None, stride=0, max_records=None, scene_q=None, scene_recs=None,
+                              scene_count=None, point_members=None, summary=None):
+        """misift_describe_points_batch: an 8-bit descriptor per track point (the rounded mean of the rows of q its
+        observations name; q: quantize_batch's output for the record batch of nframes frames, counts, offsets or
+        stride, max_records records) as a one-frame record set: scene_q (max_tracks x 128 bytes), scene_recs (max_tracks
+        records whose xpos, ypos, scale are X, Y, Z), scene_count (1 int, T), point_members (max_tracks ints) and
+        summary (8 ints: T, described points, their observations, observations that do not contribute) are device
+        buffers, allocated here when None; returns the five.  match_pairs_batch_i8 takes them as recs2 = scene_recs,
+        q2 = scene_q, nframes2 = 1, counts2 = scene_count, stride2 = max_tracks.  Enqueued on the context stream."""
+        if scene_q is None:
+            scene_q = self.zeros(128 * max_tracks)
+        if scene_recs is None:
+            scene_recs = self.zeros(POINT_DTYPE.itemsize * max_tracks)
+        if scene_count is None:
+            scene_count = self.zeros(4)
+        if point_members is None:
+            point_members = self.zeros(4 * max_tracks)
+        if summary is None:
+            summary = self.zeros(4 * 8)
+        check(lib().misift_describe_points_batch(self.h, max_tracks, max_obs, _dptr(track_offsets), _dptr(obs),
+                                                 _dptr(export_summary), _dptr(points), _dptr(point_status), _dptr(q),
+                                                 nframes, _dptr(counts), _dptr(offsets), stride, int(max_records),
+                                                 _dptr(scene_q), _dptr(scene_recs), _dptr(scene_count),
+                                                 _dptr(point_members), _dptr(summary)),
+              "misift_describe_points_batch")
+        return scene_q, scene_recs, scene_count, point_members, summary
+
+    def localize_frames_batch(self, rows, nframes_rows, counts, offsets, stride, max_tracks, export_summary, points,
+                              point_status, nimages, intrinsics, frames, images, seeds, max_pts, max_found,
+                              min_score=0.85, max_ambiguity=0.95, num_loops=1024, thresh=4.0, min_inliers=12,
+                              only_unset=False, install=False, cam=None, cam_pair=None, res_cam=None, res_cand=None,
+                              res_inliers=None, res_status=None, summary=None, found_offsets=None, found_obs=None,
+                              found_summary=None, found_points=None, found_views=None, found_status=None,
+                              found_map=None):
+        """misift_localize_frames_batch: the camera of image images[e] from the rows of frame frames[e] (rows: a batch of
+        nframes_rows frames, counts, offsets or stride, as find_homography_batch takes it; after match_pairs_batch_i8
+        against describe_points_batch's scene: frame = pair, stride = max_pts, counts = out_counts) whose match names
+        a point of the scene (export_summary, points, point_status for max_tracks), by resect_cameras_batch's search
+        over the rows that pass min_score and max_ambiguity; seeds, num_loops, thresh, min_inliers, only_unset, install,
+        cam, cam_pair and the five res_* / summary outputs as in resect_cameras_batch (status 4: more than max_pts
+        rows).  The inliers go out as a scene for merge_scenes_batch: found_offsets (max_found + 1 ints), found_obs
+        (max_found observations), found_summary (8 ints, export's layout), found_points (max_found x 4 floats),
+        found_views, found_status and found_map (max_found ints each: the point of the scene each find belongs to, the
+        merge's point_map).  Device buffers are allocated here when None; returns a dict of the twelve outputs.
+        Enqueued on the context stream."""
+        intrinsics = np.ascontiguousarray(intrinsics, np.float32).reshape(-1, 4)
+        assert len(intrinsics) == nimages
+        frames = np.ascontiguousarray(frames, np.int32).reshape(-1)
+        images = np.ascontiguousarray(images, np.int32).reshape(-1)
+        seeds = np.ascontiguousarray(seeds, np.uint32).reshape(-1)
+        nsel = len(frames)
+        assert len(images) == nsel and len(seeds) == nsel
+        n, m = max(nsel, 1), max(max_found, 1)
+        sizes = dict(res_cam=48 * n, res_cand=4 * n, res_inliers=4 * n, res_status=4 * n, summary=32,
+                     found_offsets=4 * (m + 1), found_obs=16 * m, found_summary=32, found_points=16 * m,
+                     found_views=4 * m, found_status=4 * m, found_map=4 * m)
+        given = dict(res_cam=res_cam, res_cand=res_cand, res_inliers=res_inliers, res_status=res_status, summary=summary,
+                     found_offsets=found_offsets, found_obs=found_obs, found_summary=found_summary,
+                     found_points=found_points, found_views=found_views, found_status=found_status, found_map=found_map)
+        o = {k: self.zeros(sizes[k]) if v is None else v for k, v in given.items()}
+        check(lib().misift_localize_frames_batch(
+            self.h, _dptr(rows), nframes_rows, _dptr(counts), _dptr(offsets), stride, max_tracks, _dptr(export_summary),
+            _dptr(points), _dptr(point_status), nimages, intrinsics.ctypes.data, nsel,
+            frames.ctypes.data if nsel else None, images.ctypes.data if nsel else None,
+            seeds.ctypes.data if nsel else None, int(max_pts), float(min_score), float(max_ambiguity), int(num_loops),
+            float(thresh), int(min_inliers), int(only_unset), int(install), _dptr(cam), _dptr(cam_pair),
+            _dptr(o["res_cam"]), _dptr(o["res_cand"]), _dptr(o["res_inliers"]), _dptr(o["res_status"]),
+            _dptr(o["summary"]), int(max_found), _dptr(o["found_offsets"]), _dptr(o["found_obs"]),
+            _dptr(o["found_summary"]), _dptr(o["found_points"]), _dptr(o["found_views"]), _dptr(o["found_status"]),
+            _dptr(o["found_map"])), "misift_localize_frames_batch")
+        return o
 
     def correspond_tracks_batch(self, max_records_a, record_obs_a, max_tracks_a, max_obs_a, track_offsets_a,
                                 export_summary_a, max_records_b, record_obs_b, max_tracks_b, max_obs_b, track_offsets_b,

@@ -751,6 +751,38 @@ int launch_filter_tracks_batch(misift_ctx *ctx, const TrackScene &scene, float t
 struct MergeIn;
 size_t merge_scenes_batch_tmp_bytes(int max_tracks_a, int max_obs_a, int max_tracks_b, int max_obs_b);
 int launch_merge_scenes_batch(misift_ctx *ctx, const MergeIn &in);
+// misift_describe_points_batch (kernels_localize.hip): one memset + one launch, no temp.  DescribeIn, DescribeOut
+// (localize_core.hpp): the scene, the record batch and the outputs, all checked by the caller
+struct DescribeIn;
+struct DescribeOut;
+int launch_describe_points_batch(misift_ctx *ctx, const DescribeIn &in, const DescribeOut &out);
+// misift_localize_frames_batch (kernels_localize.hip): one memset + five launches (nsel == 0: the memset, the pick and
+// the emit); temp from misift_ensure_tmp, sized from nsel, max_pts and num_loops only.  The host lists are the pinned
+// copies; scene holds max_tracks, nimages, d_export_summary, the points, their status and the pinned intrinsics
+struct LocalizeCall {
+  int nsel;
+  const int *h_frames, *h_images;
+  const unsigned *h_seeds;
+  BatchLayout rows;
+  int max_pts;
+  float min_score, max_ambiguity;
+  int num_loops;
+  float thresh2;
+  int min_inliers, only_unset, install;
+  float *d_cam;
+  int *d_cam_pair;
+  float *d_res_cam;
+  int *d_res_cand, *d_res_inliers, *d_res_status, *d_summary;
+  int max_found;
+  int *d_found_offsets;
+  TrackObs *d_found_obs;
+  int *d_found_summary;
+  float *d_found_points;
+  int *d_found_views, *d_found_status, *d_found_map;
+};
+bool localize_frames_batch_one_launch(int nsel, int max_pts, int num_loops);
+size_t localize_frames_batch_tmp_bytes(int nsel, int max_pts, int num_loops);
+int launch_localize_frames_batch(misift_ctx *ctx, const TrackScene &scene, const LocalizeCall &call);
 int launch_test_exp2(misift_ctx *ctx, const float *x, float *out, int n);
 int launch_test_points_fn(misift_ctx *ctx, int fn, const float *x, const float *y, float *out, float *out2, int n);
 int launch_selftest(misift_ctx *ctx);

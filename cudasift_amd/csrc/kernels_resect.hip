@@ -4,7 +4,8 @@
 // does not rest on the chain of pair poses.  No reference counterpart.  The arithmetic is resect_core.hpp (the draw, the
 // solve) and refine_core.hpp (the inlier test), shared with the host-only test hooks at the end of this file.
 //
-// The search is ransac_batch.hpp's with ResectModel below.  What is this file's: two memsets (the owners, the summary)
+// The search is ransac_batch.hpp's with ResectModel (resect_model.hpp: the model, the solve of a lane and the entry's
+// results, shared with misift_localize_frames_batch).  What is this file's: two memsets (the owners, the summary)
 // and, whatever the data, six launches (nsel == 0: the summary's memset and the pick launch alone, which writes T):
 //   cand_owner_kernel     the owner of every slot and
 //   cand_key_kernel       the image every slot is a candidate of: launch_track_candidates (track_candidates.hpp), in the
@@ -23,6 +24,7 @@
 #include "common.hpp"
 #include "ransac_batch.hpp"
 #include "resect_core.hpp"
+#include "resect_model.hpp"
 #include "track_candidates.hpp"
 
 namespace {
@@ -41,31 +43,7 @@ struct ResectArgs {
   int *res_cand, *res_inliers, *res_status, *summary;
 };
 
-struct ResectModel {
-  typedef ResectArgs Args;
-  static constexpr int SAMPLE = RESECT_SAMPLE, PARAMS = 12, COORDS = 5;
-  static constexpr bool INDEX = false, COUNT_ALL = true;
-  template <class Ring>
-  static __device__ __forceinline__ void draw(LibcRand<Ring> &g, const FastMod31 &fm, int (&p)[RESECT_SAMPLE])
-  {
-    resect_draw6(g, fm, p);
-  }
-  struct Lane {
-    float k[4];                                // the image's intrinsics
-  };
-  static __device__ __forceinline__ Lane lane(const ResectArgs &A, int e)
-  {
-    const float *kp = A.s.intrinsics + 4 * (size_t)A.images[e];
-    return Lane{{kp[0], kp[1], kp[2], kp[3]}};
-  }
-  static __device__ __forceinline__ bool inlier(const float (&cam)[12], const Lane &ln, const float (&q)[5],
-                                                float thresh2)
-  {
-    const float X[3] = {q[2], q[3], q[4]};
-    return refine_member(cam, ln.k, X, q[0], q[1], thresh2);
-  }
-  static __device__ __forceinline__ float invalid() { return 0.0f; }
-};
+typedef ResectModelOf<ResectArgs, false> ResectModel;     // resect_model.hpp, shared with the localise search
 
 __global__ __launch_bounds__(1024) void resect_gather_kernel(ResectArgs A)
 {
@@ -110,33 +88,10 @@ __global__ __launch_bounds__(1024) void resect_gather_kernel(ResectArgs A)
   }
 }
 
-// a lane's 11 x 12 system in LDS: word (r, c) at (12 r + c) * 64 from the lane's base
-struct ResectLdsMat {
-  float *base;
-  __device__ float get(int r, int c) const { return base[(RESECT_COLS * r + c) * 64]; }
-  __device__ void set(int r, int c, float v) { base[(RESECT_COLS * r + c) * 64] = v; }
-};
-
 __global__ __launch_bounds__(64) void resect_solve_kernel(ResectArgs A, int hblocks)
 {
-  __shared__ float s_m[RESECT_ROWS * RESECT_COLS * 64];
-  const RansacSearch &S = A.rs;
-  int e, idx, n;
-  if (!ransac_solve_begin(S, hblocks, e, idx, n)) return;
-  const int mc = S.cap16;
-  const float *coord = S.coord + (size_t)e * 5 * mc;
-  float x[6], y[6], X[6], Y[6], Z[6];
-  bool in_range = true;
-#pragma unroll
-  for (int k = 0; k < RESECT_SAMPLE; k++) {
-    const int i = ransac_sample_position<ResectModel>(S, e, idx, k, n, in_range);
-    x[k] = coord[i]; y[k] = coord[mc + i]; X[k] = coord[2 * mc + i]; Y[k] = coord[3 * mc + i]; Z[k] = coord[4 * mc + i];
-  }
-  const ResectModel::Lane ln = ResectModel::lane(A, e);
-  ResectLdsMat m{s_m + threadIdx.x};
-  float cam[12];
-  resect_solve6(m, x, y, X, Y, Z, ln.k, cam);
-  ransac_store_hyp<ResectModel>(S, e, idx, in_range, cam);
+  __shared__ float s_m[RESECT_SOLVE_LDS];
+  resect_solve_lane<ResectModel>(A, hblocks, s_m);
 }
 
 __global__ __launch_bounds__(1024) void resect_pick_kernel(ResectArgs A)
@@ -150,35 +105,8 @@ __global__ __launch_bounds__(1024) void resect_pick_kernel(ResectArgs A)
   unsigned long long best = 0;
   if (searched) best = ransac_pick(S.hcount + (size_t)e * S.lp, S.num_loops);
   if (tid != 0) return;
-  int status = meta[1], inliers = 0;
-  float cam[12];
-#pragma unroll
-  for (int j = 0; j < 12; j++) cam[j] = 0.0f;
-  if (searched) {
-    inliers = ransac_pick_count(best);
-    status = inliers < A.min_inliers ? RESECT_NO_MODEL : RESECT_OK;
-    if (status == RESECT_OK) {
-      const int idx = min(max(ransac_pick_index(best), 0), S.num_loops - 1);
-      const float *hyp = S.hyp + (size_t)e * 12 * S.lp;
-#pragma unroll
-      for (int j = 0; j < 12; j++) cam[j] = pose_one_nan(hyp[j * S.lp + idx]);
-    }
-  }
-  float *out = A.res_cam + 12 * (size_t)e;
-#pragma unroll
-  for (int j = 0; j < 12; j++) out[j] = cam[j];
-  A.res_cand[e] = meta[2];
-  A.res_inliers[e] = inliers;
-  A.res_status[e] = status;
-  if (A.install && status == RESECT_OK) {
-    const int img = A.images[e];
-    float *dst = A.cam + 12 * (size_t)img;
-#pragma unroll
-    for (int j = 0; j < 12; j++) dst[j] = cam[j];
-    A.cam_pair[img] = POSEGRAPH_RESECTED;
-  }
-  atomicAdd(&A.summary[status == RESECT_OK ? 1 : status + 2], 1);
-  if (status == RESECT_OK) atomicAdd(&A.summary[2], inliers);
+  int picked;
+  resect_entry_results(A, e, searched, best, &picked);
 }
 
 // the candidates an entry's temp has room for: an image has no more than O <= max_obs, so n > max_cand decides as stated

@@ -22,6 +22,7 @@
 #include "common.hpp"
 #include "bundle_host.hpp"
 #include "chain.hpp"
+#include "localize_core.hpp"
 #include "merge_core.hpp"
 #include "pair_plan.hpp"
 
@@ -2916,6 +2917,175 @@ extern "C" int misift_resect_cameras_batch(misift_ctx *ctx, int max_tracks, int 
                                                         d_cam_pair, d_res_cam, d_res_cand, d_res_inliers, d_res_status,
                                                         d_summary);
                    });
+}
+
+// ---- new frames against a reconstruction: a descriptor per point, then cameras from 2-D/3-D matches
+// The arguments of misift_describe_points_batch and of its host hook checked and put into a DescribeIn and a
+// DescribeOut (localize_core.hpp).  Every rule of the header's error list but the NULL context is here.
+static int describe_check(const char *who, DescribeIn *in, DescribeOut *out, int max_tracks, int max_obs,
+                          const int *track_offsets, const misift_track_obs *obs, const int *export_summary,
+                          const float *points, const int *point_status, const void *q, int nframes, const int *counts,
+                          const int *offsets, int stride, int max_records, void *scene_q, void *scene_recs,
+                          int *scene_count, int *point_members, int *summary)
+{
+  ARG_CHECK_IN(who, max_tracks >= 1 && max_obs >= 1 && max_records >= 1 && nframes >= 0);
+  ARG_CHECK_IN(who, track_offsets && obs && export_summary && points && point_status && q && counts);
+  ARG_CHECK_IN(who, scene_q && scene_recs && scene_count && point_members && summary);
+  ARG_CHECK_IN(who, offsets || stride >= 0);
+  ARG_CHECK_IN(who, (((uintptr_t)obs | (uintptr_t)q | (uintptr_t)scene_q | (uintptr_t)scene_recs) & 15) == 0);
+  {
+    // the call only reads its inputs: no output may share a byte with an input or with another output
+    const size_t mt = (size_t)max_tracks, mo = (size_t)max_obs, nf = (size_t)nframes;
+    const struct { const void *p; size_t bytes; } span[13] = {
+        {scene_q, 128 * mt}, {scene_recs, MISIFT_POINT_BYTES * mt}, {scene_count, 4}, {point_members, 4 * mt},
+        {summary, 32},
+        {track_offsets, 4 * (mt + 1)}, {obs, 16 * mo}, {export_summary, 32}, {points, 16 * mt}, {point_status, 4 * mt},
+        {q, 128 * (size_t)max_records}, {counts, 4 * nf}, {offsets, offsets ? 4 * nf : 0}};
+    for (int a = 0; a < 5; a++)
+      for (int b = a + 1; b < 13; b++) {
+        if (!span[a].bytes || !span[b].bytes) continue;
+        const uintptr_t pa = (uintptr_t)span[a].p, pb = (uintptr_t)span[b].p;
+        ARG_CHECK_IN(who, pa + span[a].bytes <= pb || pb + span[b].bytes <= pa);
+      }
+  }
+  in->s = TrackScene{max_tracks, max_obs, 0, track_offsets, reinterpret_cast<const TrackObs *>(obs), export_summary,
+                     points, point_status, nullptr, nullptr, nullptr};
+  in->q = reinterpret_cast<const signed char *>(q);
+  in->nframes = nframes;
+  in->counts = counts; in->offsets = offsets;
+  in->stride = stride; in->max_records = max_records;
+  *out = DescribeOut{reinterpret_cast<signed char *>(scene_q), reinterpret_cast<uint32_t *>(scene_recs), scene_count,
+                     point_members, summary};
+  return MISIFT_OK;
+}
+
+// An 8-bit descriptor per track point, laid out as a one-frame record set for the int8 pair matchers.  No host lists.
+extern "C" int misift_describe_points_batch(misift_ctx *ctx, int max_tracks, int max_obs, const int *d_track_offsets,
+                                            const misift_track_obs *d_obs, const int *d_export_summary,
+                                            const float *d_points, const int *d_point_status, const void *d_q,
+                                            int nframes, const int *d_counts, const int *d_offsets, int stride,
+                                            int max_records, void *d_scene_q, void *d_scene_recs, int *d_scene_count,
+                                            int *d_point_members, int *d_summary)
+{
+  ARG_CHECK(ctx != nullptr);
+  DescribeIn in;
+  DescribeOut out;
+  const int rc = describe_check(__func__, &in, &out, max_tracks, max_obs, d_track_offsets, d_obs, d_export_summary,
+                                d_points, d_point_status, d_q, nframes, d_counts, d_offsets, stride, max_records,
+                                d_scene_q, d_scene_recs, d_scene_count, d_point_members, d_summary);
+  if (rc) return rc;
+  RoctxRange range(__func__);
+  return run_batch(ctx, {}, 0, [&](int *, void *) { return launch_describe_points_batch(ctx, in, out); });
+}
+
+// Test-only, host-only: the whole call on host arrays by the rules the kernel compiles (localize_core.hpp).
+extern "C" int misift_test_describe_points(int max_tracks, int max_obs, const int *track_offsets,
+                                           const misift_track_obs *obs, const int *export_summary, const float *points,
+                                           const int *point_status, const void *q, int nframes, const int *counts,
+                                           const int *offsets, int stride, int max_records, void *scene_q,
+                                           void *scene_recs, int *scene_count, int *point_members, int *summary)
+{
+  DescribeIn in;
+  DescribeOut out;
+  const int rc = describe_check(__func__, &in, &out, max_tracks, max_obs, track_offsets, obs, export_summary, points,
+                                point_status, q, nframes, counts, offsets, stride, max_records, scene_q, scene_recs,
+                                scene_count, point_members, summary);
+  if (rc) return rc;
+  describe_points_host(in, out);
+  return MISIFT_OK;
+}
+
+// The camera of each selected image from the rows of a frame matched against the scene's points, by resect's search, and
+// the inliers as a scene for misift_merge_scenes_batch.  The intrinsics, the frames, the images and the seeds go to the
+// pinned slot, in that order.
+extern "C" int misift_localize_frames_batch(misift_ctx *ctx, const void *d_rows, int nframes_rows, const int *d_counts,
+                                            const int *d_offsets, int stride, int max_tracks,
+                                            const int *d_export_summary, const float *d_points,
+                                            const int *d_point_status, int nimages, const float *intrinsics, int nsel,
+                                            const int *frames, const int *images, const unsigned *seeds, int max_pts,
+                                            float min_score, float max_ambiguity, int num_loops, float thresh,
+                                            int min_inliers, int only_unset, int install, float *d_cam, int *d_cam_pair,
+                                            float *d_res_cam, int *d_res_cand, int *d_res_inliers, int *d_res_status,
+                                            int *d_summary, int max_found, int *d_found_offsets,
+                                            misift_track_obs *d_found_obs, int *d_found_summary, float *d_found_points,
+                                            int *d_found_views, int *d_found_status, int *d_found_map)
+{
+  ARG_CHECK(ctx != nullptr);
+  ARG_CHECK(max_tracks >= 1 && nimages >= 1 && nframes_rows >= 1 && max_pts >= 1 && max_found >= 1);
+  ARG_CHECK(d_rows && d_counts && d_export_summary && d_points && d_point_status && intrinsics);
+  ARG_CHECK(d_res_cam && d_res_cand && d_res_inliers && d_res_status && d_summary);
+  ARG_CHECK(d_found_offsets && d_found_obs && d_found_summary && d_found_points && d_found_views && d_found_status &&
+            d_found_map);
+  ARG_CHECK(((uintptr_t)d_found_obs & 15) == 0);
+  for (int i = 0; i < nimages; i++) ARG_CHECK(intrinsics_usable(intrinsics + 4 * (size_t)i, 1));
+  BatchLayout rows;
+  int rc = batch_layout(__func__, d_rows, d_counts, d_offsets, stride, &rows);
+  if (rc) return rc;
+  ARG_CHECK(nsel >= 0 && (nsel == 0 || (frames && images && seeds)));
+  ARG_CHECK(num_loops >= 1 && min_inliers >= 6);
+  ARG_CHECK(min_score == min_score && max_ambiguity == max_ambiguity);      // not NaN
+  ARG_CHECK(thresh > 0.0f);                                                 // NaN fails too
+  ARG_CHECK((only_unset == 0 || only_unset == 1) && (install == 0 || install == 1));
+  ARG_CHECK(d_cam_pair || !(only_unset || install));
+  ARG_CHECK(d_cam || !install);
+  rc = check_frames(__func__, nsel, frames, 1, nframes_rows, 0);
+  if (!rc) rc = check_frames(__func__, nsel, images, 1, nimages, 0);
+  if (rc) return rc;
+  ARG_CHECK(localize_frames_batch_one_launch(nsel, max_pts, num_loops));
+  TrackScene S{max_tracks, 0, nimages, nullptr, nullptr, d_export_summary, d_points, d_point_status, d_cam, d_cam_pair,
+               intrinsics};
+  LocalizeCall call{};
+  call.nsel = nsel;
+  call.rows = rows;
+  call.max_pts = max_pts;
+  call.min_score = min_score; call.max_ambiguity = max_ambiguity;
+  call.num_loops = num_loops;
+  call.thresh2 = thresh * thresh;                                           // rounded once, here
+  call.min_inliers = min_inliers; call.only_unset = only_unset; call.install = install;
+  call.d_cam = d_cam; call.d_cam_pair = d_cam_pair;
+  call.d_res_cam = d_res_cam; call.d_res_cand = d_res_cand; call.d_res_inliers = d_res_inliers;
+  call.d_res_status = d_res_status; call.d_summary = d_summary;
+  call.max_found = max_found;
+  call.d_found_offsets = d_found_offsets; call.d_found_obs = reinterpret_cast<TrackObs *>(d_found_obs);
+  call.d_found_summary = d_found_summary; call.d_found_points = d_found_points; call.d_found_views = d_found_views;
+  call.d_found_status = d_found_status; call.d_found_map = d_found_map;
+  RoctxRange range(__func__);
+  return run_batch(ctx, {{intrinsics, sizeof(float) * 4 * (size_t)nimages}, {frames, sizeof(int) * (size_t)nsel},
+                         {images, sizeof(int) * (size_t)nsel}, {seeds, sizeof(unsigned) * (size_t)nsel}},
+                   0, [&](int *h_lists, void *) {
+                     S.intrinsics = reinterpret_cast<const float *>(h_lists);
+                     call.h_frames = h_lists + 4 * (size_t)nimages;
+                     call.h_images = call.h_frames + nsel;
+                     call.h_seeds = reinterpret_cast<const unsigned *>(call.h_images + nsel);
+                     return launch_localize_frames_batch(ctx, S, call);
+                   });
+}
+
+// Test-only, host-only: the ordered candidate list of one frame of rows (localize_core.hpp): out5 gets x y X Y Z per
+// candidate, out_row its row, out_track its point, *out_n their number.  Each output holds nrows entries.
+extern "C" int misift_test_localize_candidates(const void *rows, int nrows, int T, const float *points,
+                                               const int *point_status, float min_score, float max_ambiguity,
+                                               float *out5, int *out_row, int *out_track, int *out_n)
+{
+  if (nrows < 0 || T < 0 || !out_n || (nrows > 0 && (!rows || !out5 || !out_row || !out_track)) ||
+      (T > 0 && (!points || !point_status))) {
+    misift_set_error("misift_test_localize_candidates: invalid argument");
+    return MISIFT_EINVAL;
+  }
+  const float *r = reinterpret_cast<const float *>(rows);
+  int n = 0;
+  for (int i = 0; i < nrows; i++) {
+    LocCandidate c;
+    if (!loc_candidate(r + (size_t)i * (MISIFT_POINT_BYTES / 4), T, points, point_status, min_score, max_ambiguity, c))
+      continue;
+    float *o = out5 + 5 * (size_t)n;
+    o[0] = c.x; o[1] = c.y; o[2] = c.X; o[3] = c.Y; o[4] = c.Z;
+    out_row[n] = i;
+    out_track[n] = c.t;
+    n++;
+  }
+  *out_n = n;
+  return MISIFT_OK;
 }
 
 // Which track of scene B holds the records of each track of scene A: where the d_map of misift_align_points_batch comes

@@ -1,6 +1,7 @@
 // ransac_batch.hpp — the batch RANSAC search that misift_find_homography_batch (homography.hip),
-// misift_find_fundamental_batch (kernels_fundamental.hip), misift_resect_cameras_batch (kernels_resect.hip) and
-// misift_align_points_batch (kernels_align.hip) share.  Entry e gathers its candidates on the device and writes result
+// misift_find_fundamental_batch (kernels_fundamental.hip), misift_resect_cameras_batch (kernels_resect.hip),
+// misift_align_points_batch (kernels_align.hip) and misift_localize_frames_batch (kernels_localize.hip: resect's model
+// over its own candidates, resect_model.hpp) share.  Entry e gathers its candidates on the device and writes result
 // slot e; no host round trip.  Four launches whatever the number of entries (ransac_launches):
 //   gather  one 1024-thread workgroup per entry: SoA coordinates of the entry's candidates into its temp, in ORDER
 //           (RansacCompaction: a sample position p means "the p-th candidate"), then wave 0 draws the entry's sample
@@ -35,7 +36,8 @@
 //   the candidates    the records of a frame with (x, y, match x, match y), gated by score and ambiguity (homography,
 //                     fundamental); the observations an image makes of triangulated points, (x, y, X, Y, Z) (resect:
 //                     its own gather, which goes on counting past max_cand without storing); the mapped point pairs of
-//                     two scenes, (a, b) (align: its own gather, which also marks d_inlier and keeps each index).
+//                     two scenes, (a, b) (align: its own gather, which also marks d_inlier and keeps each index); the rows
+//                     of a frame matched against a scene's points, (x, y, X, Y, Z) with the row index kept (localise).
 //   what is counted   the homography counts inliers over ALL n records of the frame, invalid ones included (the reference's
 //                     TestHomographies); the fundamental counts over the valid list only, each index range-checked;
 //                     resect and align store only candidates, and count them all.

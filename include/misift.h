@@ -1797,6 +1797,155 @@ int misift_merge_scenes_batch(misift_ctx *ctx,
                               int *d_record_obs_out,            /* max_records_out; may be NULL */
                               int *d_summary);                  /* 8 ints */
 
+/* misift_describe_points_batch: an 8-bit descriptor per track point, laid out as a one-frame record set that the int8
+ * pair matchers take (no reference counterpart).  With misift_localize_frames_batch below it places a frame that arrived
+ * after the tracks were linked: quantize the new frames -> describe -> misift_match_pairs_batch_i8 (new frame, scene) ->
+ * localize -> merge -> refine / adjust, with no host read.
+ *   d_track_offsets, d_obs, d_export_summary: from export (or filter, or merge) for max_tracks and max_obs; d_points and
+ *   d_point_status from triangulate.  d_q is what misift_quantize_batch wrote for the record batch the observations
+ *   index: nframes frames, d_counts, d_offsets or stride, max_records records in all.  The layout and the rule "a frame
+ *   whose records do not all lie in [0, max_records) takes no part" are those of misift_link_tracks_batch:
+ *   n(f) = max(d_counts[f], 0), base(f) = d_offsets[f], or f * stride without d_offsets (in 64 bits); frame f TAKES PART
+ *   iff n(f) == 0 or 0 <= base(f) and base(f) + n(f) <= max_records.
+ *   T and O are read on the device and clamped as in misift_refine_cameras_batch: T = min(max(d_export_summary[2], 0),
+ *   max_tracks), O likewise with [3] and max_obs.  Track t < T is VALID by the rule of misift_refine_cameras_batch:
+ *   0 <= off[t] <= off[t+1] <= O.  The observations of a valid track are the slots off[t] .. off[t+1] - 1, its own range
+ *   whether or not another track's range overlaps it (the call only reads: there is no owner rule); a track that is not
+ *   valid has none.
+ *   An observation (frame f, record r) CONTRIBUTES iff f lies in [0, nframes), frame f takes part and r lies in
+ *   [0, n(f)).  Its descriptor row is the 128 signed bytes at d_q + 128 * (base(f) + r).  xpos and ypos are not read.
+ *   Per track t < T: m = the number of its contributing observations; sum_k = the sum of byte k over them, as integers
+ *   (the library sums in 64 bits).  The point is DESCRIBED iff the track is valid, d_point_status[t] == 0, d_points[4t],
+ *   [4t+1] and [4t+2] are FINITE (fabsf(v) <= FLT_MAX) and m > 0.  A described point has byte k =
+ *   (2 * sum_k + m) / (2 * m) in integer division: the mean, a half rounded up, in [0, 127] for the bytes quantize writes.
+ *   Outputs, for t < T (what lies at or beyond T stays untouched):
+ *     d_scene_q[128t .. 128t+127]   the bytes of a described point; 128 zeros otherwise.  Every int8 matcher counts only
+ *                                   S > 0, so a zero row is nobody's match and nobody's second best: no compaction.
+ *     d_scene_recs record t         every one of its 576 bytes: zeros, except that a described point has the bits of X, Y, Z
+ *                                   in xpos, ypos, scale.  The pair matcher copies xpos / ypos of set 2, so match_xpos and
+ *                                   match_ypos of a row carry X and Y.
+ *     d_point_members[t]            m.
+ *   d_scene_count[0] = T.  d_summary (8 ints, integer sums, so deterministic): [0] T, [1] described points, [2] the
+ *   contributing observations of described points, [3] observations of valid tracks that do not contribute (an
+ *   observation in the ranges of two tracks counts with each), [4..7] 0.
+ *   The scene then is set 2 of misift_match_pairs_batch_i8 as ONE frame: d_recs2 = d_scene_recs, d_q2 = d_scene_q,
+ *   nframes2 = 1, d_counts2 = d_scene_count, d_offsets2 = NULL, stride2 = max_tracks, pairs (query frame, 0).  `match` of
+ *   a row is the track number.  That call turns a pair away whose set-2 frame holds more than its max_pts records, so
+ *   its max_pts is at least T (max_tracks always does), and so is the stride of its output rows; the max_pts of
+ *   misift_localize_frames_batch is its own and bounds the rows of a query frame only.
+ *   - Not done here: the mean is not renormalised, so scores against points are lower than cosines (the ambiguity ratio
+ *     is unaffected; min_score is the caller's); no fp32 descriptor: `data` of the scene records is zero and the fp32
+ *     matchers find nothing there.
+ *   - NULL ctx or pointer other than d_offsets; max_tracks, max_obs or max_records < 1; nframes < 0; d_offsets NULL with
+ *     stride < 0; d_obs, d_q, d_scene_q or d_scene_recs not 16-byte aligned; an output that shares a byte with an input or
+ *     with another output, each at its stated size (d_q: 128 * max_records bytes, d_counts and d_offsets: nframes ints):
+ *     MISIFT_EINVAL, before anything is enqueued.  None of the inputs is written.
+ *   - Integer work only and deterministic: byte-identical from run to run whatever the dispatch order.  Every index read
+ *     from device memory (T, O, offsets, frames, records, counts, frame offsets) is range-checked before it addresses
+ *     anything.
+ *   - The call runs on the context stream and returns before the GPU work is done; no host synchronisation and no host
+ *     read.  Ordering behind batches in flight (K > 1): as misift_match_batch.
+ *   - One memset and one launch: one wavefront per track, 16 lanes per observation with 8 bytes of its row each.  No temp
+ *     memory. */
+int misift_describe_points_batch(misift_ctx *ctx,
+                                 int max_tracks, int max_obs,
+                                 const int *d_track_offsets,     /* max_tracks + 1, from export */
+                                 const misift_track_obs *d_obs,  /* max_obs, from export, 16-byte aligned */
+                                 const int *d_export_summary,    /* 8 ints, from export: [2] = T, [3] = O */
+                                 const float *d_points,          /* max_tracks x 4, from triangulate */
+                                 const int *d_point_status,      /* max_tracks, from triangulate */
+                                 const void *d_q,                /* max_records x 128 int8, from quantize, 16-byte aligned */
+                                 int nframes, const int *d_counts, const int *d_offsets, int stride,
+                                 int max_records,
+                                 void *d_scene_q,                /* max_tracks x 128 int8, 16-byte aligned */
+                                 void *d_scene_recs,             /* max_tracks records of 576 bytes, 16-byte aligned */
+                                 int *d_scene_count,             /* 1 int */
+                                 int *d_point_members,           /* max_tracks */
+                                 int *d_summary);                /* 8 ints */
+
+/* misift_localize_frames_batch: the camera of a new image from the rows of a frame matched against the scene's points,
+ * by the search of misift_resect_cameras_batch over 2-D/3-D matches, and the inliers written out as a scene that
+ * misift_merge_scenes_batch takes as its scene A (no reference counterpart).  Resect finds its candidates through d_obs,
+ * so it places only images whose records sit in the exported tracks; here the candidates come from match rows.
+ *   The rows are a batch as misift_find_homography_batch takes it: d_rows, nframes_rows frames, d_counts, d_offsets or
+ *   stride.  After misift_match_pairs_batch_i8: frame i = pair i, stride = its max_pts, d_counts = d_out_counts.
+ *   d_export_summary, d_points, d_point_status: the scene's, for max_tracks; T as in misift_describe_points_batch.
+ *   intrinsics[4i..4i+3] = fx fy cx cy of image i < nimages.  Entry e < nsel works on the rows of frame frames[e], gives
+ *   the camera of image images[e] (distinct; so are the frames) with the seed seeds[e], and writes result slot e.
+ *   The arithmetic, FINITE and the NaN rule are those of misift_resect_cameras_batch.
+ *   Per entry e, independently of every other entry:
+ *   1. Skip: step 1 of misift_resect_cameras_batch with i = images[e] (status 3).
+ *   2. Candidates.  c = d_counts[frames[e]].  c > max_pts: status 4, d_res_cand[e] = 0, twelve zeros, d_res_inliers[e] = 0
+ *      and nothing of the frame is read.  Otherwise the frame has max(c, 0) rows, and row r is a CANDIDATE, in ascending
+ *      r, iff score > min_score and ambiguity < max_ambiguity (a NaN fails); t = match lies in [0, T);
+ *      d_point_status[t] == 0; d_points[4t], [4t+1], [4t+2] are FINITE; xpos and ypos are FINITE.  Candidate p < n has
+ *      (x, y) = the row's xpos, ypos and (X, Y, Z) = d_points[4t..4t+2].  d_res_cand[e] = n.  n < max(6, min_inliers):
+ *      status 1, twelve zeros and d_res_inliers[e] = 0.
+ *   3. Draw, solve, count, pick and install: steps 3 to 7 of misift_resect_cameras_batch, word for word, under the
+ *      intrinsics of image images[e]; d_cam and d_cam_pair are indexed by images[e].
+ *   4. Emit.  A FIND is a candidate of an entry with status 0 that is an inlier (step 5) of the entry's picked hypothesis,
+ *      tested on the hypothesis as the count tested it; an entry has exactly d_res_inliers[e] finds.  The finds are
+ *      numbered a = 0, 1, ... over the entries in ascending e and within an entry in ascending r; N = their number.  Find
+ *      a is WRITTEN iff a < max_found; T' = min(N, max_found).  For a written find of entry e from row r naming point t:
+ *      d_found_offsets[a] = a; d_found_obs[a] = (frame images[e], record r, the bits of x and y); d_found_map[a] = t;
+ *      d_found_points[4a..4a+3] = bit copies of d_points[4t..4t+3]; d_found_views[a] = 1; d_found_status[a] = 0.
+ *      d_found_offsets[T'] = T' closes the last track.  d_found_summary (export's layout): [0] N, [1] N, [2] T', [3] T',
+ *      [4] 1 if T' > 0 else 0, [5..7] 0.  What lies at or beyond T' (T' + 1 for the offsets) stays untouched.
+ *      Two rows of one frame that name the same point are two finds; misift_filter_tracks_batch with unique_frames
+ *      resolves them after the merge.
+ *   d_res_cam, d_res_cand, d_res_inliers, d_res_status and d_summary[0..6] are as in misift_resect_cameras_batch;
+ *   d_summary[7] = T'.
+ *   The merge then needs nothing more: with install the localised cameras are in the caller's d_cam at images[e] (sized
+ *   to hold the new images, which start at d_cam_pair == -2); d_found_* is scene A with max_tracks_a = max_obs_a =
+ *   max_found and d_found_map is d_map; d_accept NULL, fshift 0 and the same camera arrays on both sides.
+ *   - Not done here: no guided second pass against projected points; no P3P solver and no local optimisation inside the
+ *     search (as resect); the pairs of the match are the caller's host list, not device data.
+ *   - NULL ctx; NULL d_rows, d_counts, d_export_summary, d_points, d_point_status, intrinsics, d_res_*, d_summary or
+ *     d_found_*; d_offsets NULL with stride < 0; max_tracks, nimages, nframes_rows, max_pts or max_found < 1; NULL
+ *     d_cam_pair with only_unset or install set, NULL d_cam with install set; d_found_obs not 16-byte aligned; nsel < 0,
+ *     nsel > 0 with NULL frames, images or seeds; a frame outside [0, nframes_rows) or an image outside [0, nimages) or
+ *     either listed twice; num_loops < 1; min_inliers < 6; min_score or max_ambiguity NaN; thresh NaN or <= 0;
+ *     only_unset or install other than 0 or 1; intrinsics as in misift_resect_cameras_batch; nsel x ceil(num_loops / 64)
+ *     x ceil(max_pts / 512) beyond 2^31 - 1 (one launch), or num_loops or max_pts beyond 2^31 - 16: MISIFT_EINVAL, before
+ *     anything is enqueued.  nsel == 0 is no error: only d_summary, d_found_summary and d_found_offsets[0] are written.
+ *     None of the inputs is written, except d_cam and d_cam_pair under install.
+ *   - Deterministic: the base of an entry's finds is an integer prefix over the entries before it.
+ *   - The call runs on the context stream and returns before the GPU work is done; the host lists are copied; no host
+ *     synchronisation and no host read.  Ordering behind batches in flight (K > 1): as misift_match_batch.
+ *   - One memset and five launches whatever the data (nsel == 0: the memset and two launches): per entry the ordered
+ *     candidate list and the draw, resect's solve and count, the pick, and per entry the ordered list of finds.  Temp
+ *     memory from the library's own allocator, sized from nsel, max_pts and num_loops only: per entry 24 bytes per row of
+ *     max_pts and 76 bytes per hypothesis (both rounded up to 16), and 24 bytes. */
+int misift_localize_frames_batch(misift_ctx *ctx,
+                                 const void *d_rows, int nframes_rows, const int *d_counts, const int *d_offsets,
+                                 int stride,
+                                 int max_tracks,
+                                 const int *d_export_summary,    /* 8 ints: [2] = T */
+                                 const float *d_points,          /* max_tracks x 4 */
+                                 const int *d_point_status,      /* max_tracks */
+                                 int nimages,
+                                 const float *intrinsics,        /* host, nimages x 4: fx fy cx cy, copied */
+                                 int nsel, const int *frames,    /* host, nsel distinct frames of the rows, copied */
+                                 const int *images,              /* host, nsel distinct image indices, copied */
+                                 const unsigned *seeds,          /* host, nsel, copied */
+                                 int max_pts, float min_score, float max_ambiguity,
+                                 int num_loops, float thresh /* px */, int min_inliers, int only_unset, int install,
+                                 float *d_cam,                   /* nimages x 12: written when install */
+                                 int   *d_cam_pair,              /* nimages: read when only_unset, written when install */
+                                 float *d_res_cam,               /* nsel x 12 */
+                                 int   *d_res_cand,              /* nsel */
+                                 int   *d_res_inliers,           /* nsel */
+                                 int   *d_res_status,            /* nsel */
+                                 int   *d_summary,               /* 8 ints */
+                                 int max_found,
+                                 int *d_found_offsets,           /* max_found + 1 */
+                                 misift_track_obs *d_found_obs,  /* max_found, 16-byte aligned */
+                                 int *d_found_summary,           /* 8 ints, export's layout */
+                                 float *d_found_points,          /* max_found x 4 */
+                                 int *d_found_views,             /* max_found */
+                                 int *d_found_status,            /* max_found */
+                                 int *d_found_map);              /* max_found */
+
 /* The cameras and the track points adjusted jointly (bundle adjustment; no reference counterpart): what
  * misift_refine_cameras_batch and misift_triangulate_tracks_batch do in turns, done in one Levenberg-Marquardt step over
  * all free cameras (6 parameters each) and all active track points (3 each).  Each step eliminates the points (Schur
@@ -2514,6 +2663,21 @@ int misift_test_merge_capacity(void);
  * cy: cam12 = R row-major then t (twelve zeros when invalid) and *valid = 0 / 1. */
 int misift_test_resect_samples(unsigned seed, int n, int num_loops, int *out);
 int misift_test_resect_solve(const float *xyXYZ, const float *intrinsics4, float *cam12, int *valid);
+
+/* Test-only, host-only: the whole of misift_describe_points_batch on host arrays, every rule compiled from the function
+ * its kernel runs (localize_core.hpp).  The arguments are those of the call without the context; all pointers are host;
+ * the argument checks are the call's own.
+ * misift_test_localize_candidates: step 2 of misift_localize_frames_batch on one frame of nrows >= 0 host rows against T
+ * points: candidate p < *out_n has out5[5p..5p+4] = x y X Y Z, out_row[p] = its row and out_track[p] = its point, in
+ * ascending row order; each output holds nrows entries.  The draw and the solve are misift_test_resect_samples and
+ * misift_test_resect_solve. */
+int misift_test_describe_points(int max_tracks, int max_obs, const int *track_offsets, const misift_track_obs *obs,
+                                const int *export_summary, const float *points, const int *point_status, const void *q,
+                                int nframes, const int *counts, const int *offsets, int stride, int max_records,
+                                void *scene_q, void *scene_recs, int *scene_count, int *point_members, int *summary);
+int misift_test_localize_candidates(const void *rows, int nrows, int T, const float *points, const int *point_status,
+                                    float min_score, float max_ambiguity, float *out5, int *out_row, int *out_track,
+                                    int *out_n);
 
 /* Test-only, host-only: steps 2, 3 and 6 of misift_align_points_batch and the arithmetic of
  * misift_transform_scene_batch, compiled from the functions their kernels run (align_core.hpp).  The sample positions:
