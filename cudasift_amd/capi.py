@@ -218,6 +218,7 @@ SIGNATURES = {
     "misift_test_frame_shares": (_i, [_i, _i, C.c_void_p, C.c_void_p]),
     "misift_test_pyramid_layout": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "misift_test_describe_detections": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp]),
+    "misift_test_detect_levels": (_i, [_vp, _i, _i, _i, _i, _f, _f, _i, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "misift_test_set_knob": (_i, [_vp, C.c_char_p, C.c_double]),
     "misift_test_knob_names": (C.c_char_p, []),
     "misift_test_set_guard": (_i, [_i]),
@@ -654,6 +655,36 @@ class Context:
         check(rc, "misift_test_describe_detections")
         cnt = np.stack([self.get_counters(f) for f in range(nframes)])
         return self.download(pts, (nframes, max_pts), POINT_DTYPE), n, cnt
+
+    def detect_levels_raw(self, levels, thresh, lowest_scale, max_pts, scale_up=False, two_ranges=False):
+        """misift_test_detect_levels on host levels (levels[f][k] as describe_detections_raw takes them).  Returns
+        (rc, out); rc != 0 is NOT raised.  out: cand[nframes, noct, slots] uint32 and cand_counts[nframes, noct],
+        dets[nframes, noct, max_pts, 5] float32 and det_counts[nframes, noct], counters[nframes, 64] uint32,
+        seg_rows[noct], nstrips[noct] (index k = octave k + 1) and cand_caps[noct], the octaves' list capacities."""
+        nframes, noct = len(levels), len(levels[0])
+        h, w = levels[0][-1].shape
+        lv = [np.ascontiguousarray(a, np.float32) for f in levels for a in f]
+        assert len(lv) == nframes * noct
+        ptrs = (C.c_void_p * len(lv))(*[a.ctypes.data for a in lv])
+        caps = np.array([max((w >> (noct - 1 - k)) * (h >> (noct - 1 - k)) // 4, 16384) for k in range(noct)], np.int64)
+        slots = int(caps.max())
+        out = dict(cand=np.zeros((nframes, noct, slots), np.uint32), cand_counts=np.full((nframes, noct), -1, np.int32),
+                   dets=np.zeros((nframes, noct, max(max_pts, 1), 5), np.float32),
+                   det_counts=np.full((nframes, noct), -1, np.int32), counters=np.zeros((nframes, 64), np.uint32),
+                   cand_caps=caps)
+        geom = np.full((noct, 2), -1, np.int32)
+        rc = lib().misift_test_detect_levels(self.h, nframes, w, h, noct, thresh, lowest_scale, int(scale_up), ptrs, max_pts,
+                                             int(two_ranges), out["cand"].ctypes.data, slots, out["cand_counts"].ctypes.data,
+                                             out["dets"].ctypes.data, out["det_counts"].ctypes.data,
+                                             out["counters"].ctypes.data, geom.ctypes.data)
+        out["seg_rows"], out["nstrips"] = geom[:, 0].copy(), geom[:, 1].copy()
+        return rc, out
+
+    def detect_levels(self, levels, thresh, lowest_scale=0.0, max_pts=4096, scale_up=False, two_ranges=False):
+        """The production detector (dog_scan_all, refine_all) on planted pyramid levels: see detect_levels_raw."""
+        rc, out = self.detect_levels_raw(levels, thresh, lowest_scale, max_pts, scale_up, two_ranges)
+        check(rc, "misift_test_detect_levels")
+        return out
 
     # ---- whole path
     def extract(self, img, num_octaves=5, init_blur=1.0, thresh=3.0, lowest_scale=0.0, scale_up=False,

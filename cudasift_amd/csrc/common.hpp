@@ -575,9 +575,10 @@ int launch_export_counts_staged(misift_ctx *ctx, int nframes, int num_octaves, i
 struct ScanAll;
 struct ChainGeom;
 // chain (optional): the ScaleDown chain that produces the coarse levels runs in the first workgroups of the same launch
+// geom_out (optional, tests): seg_rows and nstrips of every scanned level, two ints each, in the order scanned
 int launch_dog_scan_all(misift_ctx *ctx, const float *scratch, const PyramidInfo &P, const LaplaceTaps *taps,
                         float thresh, int lev_begin, int lev_end, const ChainGeom *chain = nullptr,
-                        const float *k5 = nullptr);
+                        const float *k5 = nullptr, int *geom_out = nullptr);
 int make_chain_geom(ChainGeom *G, long long frame_stride, const int (*dims)[3], const long long *offs, int nlev, int tile);
 int launch_refine_all(misift_ctx *ctx, const float *scratch, const PyramidInfo &P, const LaplaceTaps *taps,
                       float thresh, float edge_limit, float factor, int max_pts);

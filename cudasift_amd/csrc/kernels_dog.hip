@@ -1696,7 +1696,7 @@ static int ensure_capcnt(misift_ctx *ctx, const PyramidInfo &P, const CapLayout 
 
 // lev_begin..lev_end: pyramid levels to scan, 0 = finest (all levels: 0, P.noct)
 int launch_dog_scan_all(misift_ctx *ctx, const float *scratch, const PyramidInfo &P, const LaplaceTaps *taps,
-                        float thresh, int lev_begin, int lev_end, const ChainGeom *chain, const float *k5)
+                        float thresh, int lev_begin, int lev_end, const ChainGeom *chain, const float *k5, int *geom_out)
 {
   ScanAllGeom G;
   memset(&G, 0, sizeof(G));
@@ -1740,6 +1740,7 @@ int launch_dog_scan_all(misift_ctx *ctx, const float *scratch, const PyramidInfo
 #endif
     S.seg_rows = seg;
     S.nsegs = (L.h + seg - 1) / seg;
+    if (geom_out) { geom_out[2 * (lev - lev_begin)] = S.seg_rows; geom_out[2 * (lev - lev_begin) + 1] = S.nstrips; }
     S.item_begin = items;
     items += (long long)P.nframes * S.nstrips * S.nsegs;
     if ((L.p & 3) != 0 || (L.img_off & 3) != 0) fast = false;

@@ -1830,6 +1830,107 @@ extern "C" int misift_test_describe_detections(misift_ctx *ctx, int nframes, int
   return resolve_profile(ctx);
 }
 
+// Test-only (include/misift.h): the detector of the merged-octave sequence — dog_scan_all, then refine_all — on pyramid
+// levels the caller supplies.  Arena, level table, candidate / staging / counter buffers and the kernels' arguments are
+// those of misift_extract_enqueue; the scan never carries the embedded ScaleDown chain (chain = NULL), and its two-range
+// form is issued on the context's one stream.
+extern "C" int misift_test_detect_levels(misift_ctx *ctx, int nframes, int width, int height, int num_octaves, float thresh,
+                                         float lowest_scale, int scale_up, const float *const *levels, int max_pts,
+                                         int two_ranges, unsigned int *cand, int cand_slots, int *cand_counts, float *dets,
+                                         int *det_counts, unsigned int *counters, int *scan_geom)
+{
+  ARG_CHECK(ctx && levels && cand && cand_counts && dets && det_counts && counters && scan_geom);
+  ARG_CHECK(nframes >= 1 && width >= 1 && height >= 1 && max_pts >= 1);
+  ARG_CHECK(num_octaves >= 1 && num_octaves <= MISIFT_MAX_OCTAVES);
+  ARG_CHECK(width < 16384 && height < 16384);
+  ARG_CHECK(!misift_tiny_call(width, height, num_octaves));     // the entry points never send such a call to these kernels
+  ARG_CHECK(two_ranges == 0 || (two_ranges == 1 && num_octaves >= 3));
+  LevelDim dims[MISIFT_MAX_OCTAVES + 1];
+  pyramid_levels(width, height, num_octaves, 0, dims);
+  for (int k = 0; k < nframes * num_octaves; k++) ARG_CHECK(levels[k] != nullptr);
+  PyramidInfo P;
+  memset(&P, 0, sizeof(P));
+  const size_t S = misift_scratch_floats(width, height, num_octaves, 0);
+  if (scale_up) lowest_scale *= 2.0f;                           // as misift_extract_enqueue (cudaSiftH.cu:119-123)
+  const unsigned off = fill_pyramid_info(ctx, &P, dims, num_octaves, nframes, (long long)S, lowest_scale, scale_up);
+  for (int o = 1; o <= num_octaves; o++) ARG_CHECK((unsigned)cand_slots >= P.o[o].cand_cap);
+  HIP_TRY(hipSetDevice(ctx->device));
+  extra(ctx)->last_lane = nullptr;      // this call runs on the context itself, like misift_extract_enqueue
+  extra(ctx)->last_done = nullptr;
+  size_t cap = (size_t)width * height / 4;
+  if (cap < 65536) cap = 65536;
+  int rc = misift_ensure_frames(ctx, nframes, cap);
+  if (rc) return rc;
+  if (ctx->own_scratch_floats < S * nframes) {
+    if (ctx->d_own_scratch) HIP_TRY(misift_dev_free(ctx->d_own_scratch));
+    ctx->d_own_scratch = nullptr; ctx->own_scratch_floats = 0;
+    HIP_TRY(misift_dev_alloc((void **)&ctx->d_own_scratch, sizeof(float) * S * nframes, "own_scratch"));
+    ctx->own_scratch_floats = S * nframes;
+  }
+  float *d_scratch = ctx->d_own_scratch;
+  ctx->exported = 0;
+  rc = misift_ensure_frames(ctx, nframes, off);
+  if (rc) return rc;
+  rc = ensure_det(ctx, nframes, max_pts);
+  if (rc) return rc;
+  CtxExtra *xt = extra(ctx);
+  if (xt->taps_noct != num_octaves) {
+    misift_laplace_taps(num_octaves, xt->taps_table);
+    xt->taps_noct = num_octaves;
+  }
+  std::vector<LaplaceTaps> tapsv(num_octaves + 1);
+  for (int o = 1; o <= num_octaves; o++) tapsv[o] = octave_taps(xt->taps_table, o);
+  for (int f = 0; f < nframes; f++)
+    for (int o = 1; o <= num_octaves; o++)
+      HIP_TRY(hipMemcpy2DAsync(d_scratch + (size_t)f * S + dims[o].off, sizeof(float) * (size_t)dims[o].p,
+                               levels[f * num_octaves + (o - 1)], sizeof(float) * (size_t)dims[o].w,
+                               sizeof(float) * (size_t)dims[o].w, dims[o].h, hipMemcpyHostToDevice, ctx->stream));
+  // the counter blocks as the prefilter leaves them: all zero, the spare blocks behind the last frame's included
+  HIP_TRY(hipMemsetAsync(ctx->d_counters, 0, sizeof(unsigned) * CNT_STRIDE * ((size_t)nframes + CNT_SPARE_BLOCKS), ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));                   // (the levels are pageable host memory)
+  int geom[2 * MISIFT_MAX_OCTAVES];
+  if (two_ranges) {                                             // split-tail mode's two launches, here on one stream
+    rc = launch_dog_scan_all(ctx, d_scratch, P, tapsv.data(), thresh, 0, 2, nullptr, nullptr, geom);
+    if (!rc) rc = launch_dog_scan_all(ctx, d_scratch, P, tapsv.data(), thresh, 2, num_octaves, nullptr, nullptr, geom + 4);
+  } else {
+    rc = launch_dog_scan_all(ctx, d_scratch, P, tapsv.data(), thresh, 0, num_octaves, nullptr, nullptr, geom);
+  }
+  if (!rc) rc = launch_refine_all(ctx, d_scratch, P, tapsv.data(), thresh, 10.0f, 1.0f / NUM_SCALES, max_pts);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(counters, ctx->d_counters, sizeof(unsigned) * CNT_STRIDE * (size_t)nframes, hipMemcpyDeviceToHost,
+                         ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  for (int lev = 0; lev < num_octaves; lev++) {                 // geom: finest level first; scan_geom: by octave
+    scan_geom[2 * (num_octaves - lev - 1)] = geom[2 * lev];
+    scan_geom[2 * (num_octaves - lev - 1) + 1] = geom[2 * lev + 1];
+  }
+  std::vector<Detection> staged;
+  for (int f = 0; f < nframes; f++)
+    for (int o = 1; o <= num_octaves; o++) {
+      const int k = f * num_octaves + (o - 1);
+      const unsigned *cnt = counters + (size_t)f * CNT_STRIDE;
+      const unsigned nc = cnt[CNT_CAND + o] < P.o[o].cand_cap ? cnt[CNT_CAND + o] : P.o[o].cand_cap;
+      const unsigned nd = cnt[CNT_DET + o] < (unsigned)max_pts ? cnt[CNT_DET + o] : (unsigned)max_pts;
+      cand_counts[k] = (int)nc;
+      det_counts[k] = (int)nd;
+      if (nc)
+        HIP_TRY(hipMemcpyAsync(cand + (size_t)k * cand_slots, ctx->d_cand + (size_t)f * off + P.o[o].cand_off,
+                               sizeof(unsigned) * nc, hipMemcpyDeviceToHost, ctx->stream));
+      staged.resize(nd);
+      if (nd)
+        HIP_TRY(hipMemcpyAsync(staged.data(), ctx->d_det + ((size_t)f * MISIFT_MAX_OCTAVES + (o - 1)) * max_pts,
+                               sizeof(Detection) * nd, hipMemcpyDeviceToHost, ctx->stream));
+      HIP_TRY(hipStreamSynchronize(ctx->stream));               // `staged` is reused for the next octave
+      float *out = dets + 5 * (size_t)k * max_pts;
+      for (unsigned i = 0; i < nd; i++) {
+        const Detection &d = staged[i];
+        out[5 * i + 0] = d.xpos; out[5 * i + 1] = d.ypos; out[5 * i + 2] = d.scale;
+        out[5 * i + 3] = d.sharpness; out[5 * i + 4] = d.edgeness;
+      }
+    }
+  return resolve_profile(ctx);
+}
+
 extern "C" int misift_extract(misift_ctx *ctx, const float *d_img, int width, int height, int pitch, int num_octaves,
                               float init_blur, float thresh, float lowest_scale, int scale_up, float *d_scratch,
                               void *d_pts, int max_pts, int *num_pts_out)

@@ -2769,6 +2769,31 @@ int misift_test_describe_detections(misift_ctx *ctx, int nframes, int width, int
                                     const float *const *levels, const float *dets, const int *det_counts, void *d_pts,
                                     int max_pts, int *num_pts);
 
+/* Test-only: the detector of the extraction calls' merged-octave sequence — the DoG candidate scan over all levels in one
+ * launch, then the refinement of its candidates — on pyramid levels the CALLER supplies, instead of what the prefilter
+ * and the ScaleDown chain make of an image.  Arena, level table, candidate list, staging area, counter blocks (zeroed)
+ * and every kernel argument are those of an extraction call of `nframes` frames of width x height with num_octaves
+ * octaves; the scan launch never carries the embedded ScaleDown chain.  Nothing runs behind the refinement.
+ *   thresh, lowest_scale: as the extraction calls take them (the octaves' scale floors are derived from lowest_scale);
+ *     scale_up != 0 doubles lowest_scale as an up-sampled call does; the level sizes stay those of width x height.
+ *   levels[f * num_octaves + (o - 1)]: as misift_test_describe_detections.
+ *   two_ranges: 0 = one scan launch over all levels; 1 = split-tail mode's two launches, the two finest levels and then
+ *     the others (num_octaves >= 3), here both on the context's stream.
+ * Returned to host memory, entry k = f * num_octaves + (o - 1):
+ *   cand[k * cand_slots ...]: the candidate codes the scan wrote (x | y << 14 | plane << 28, plane 0..4 = DoG plane 1..5),
+ *     cand_counts[k] = min(candidates counted, the octave's list capacity) of them, in no particular order; cand_slots must
+ *     hold the largest octave's capacity, max(level width * height / 4, 16384);
+ *   dets[k * max_pts * 5 ...]: the staged detections, det_counts[k] = min(detections counted, max_pts) of them, five floats
+ *     each: xpos, ypos, scale, sharpness, edgeness in the level's own coordinates;
+ *   counters[f * 64 ...]: frame f's counter block as misift_get_counter_block reads it (uncapped counts, overflow words);
+ *   scan_geom[2 * (o - 1)], [2 * (o - 1) + 1]: rows per segment and strips of 240 columns the scan cut level o into.
+ * A bad argument — a call the extraction entry points would route to the dense kernels (under 16 x 16, or a coarsest
+ * level under 8 pixels) included — returns MISIFT_EINVAL and enqueues nothing. */
+int misift_test_detect_levels(misift_ctx *ctx, int nframes, int width, int height, int num_octaves, float thresh,
+                              float lowest_scale, int scale_up, const float *const *levels, int max_pts, int two_ranges,
+                              unsigned int *cand, int cand_slots, int *cand_counts, float *dets, int *det_counts,
+                              unsigned int *counters, int *scan_geom);
+
 /* Test-only: guard mode (out-of-bounds policing in the test build).  While it is on, every device
  * allocation the library makes — misift_malloc for the caller, and its own counters, candidate lists, detection staging,
  * block tables, matcher scratch, pipeline buffers — carries 64 KiB of a byte pattern in front of and behind the payload,
