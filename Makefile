@@ -18,7 +18,7 @@ HIPSRCS  := $(CSRC)/kernels_pyramid.hip $(CSRC)/kernels_dog.hip $(CSRC)/kernels_
             $(CSRC)/kernels_merge.hip $(CSRC)/kernels_localize.hip
 HIPOBJS  := $(patsubst $(CSRC)/%.hip,$(BUILD)/%.o,$(HIPSRCS))
 
-all: cudasift_amd/libmisift.so cudasift_amd/libcudasift.so cudasift_amd/libcudasift_managed.so oracle dropin build/pmc_calib build/valu_rates build/scan_rates build/single_call
+all: cudasift_amd/libmisift.so cudasift_amd/libcudasift.so cudasift_amd/libcudasift_managed.so oracle dropin build/pmc_calib build/valu_rates build/scan_rates build/single_call build/dropin_check build/dropin_check_managed
 
 $(BUILD)/%.o: $(CSRC)/%.hip $(CSRC)/common.hpp $(CSRC)/chain.hpp $(CSRC)/match_sweep.inc $(CSRC)/match_i8_sweep.inc \
             $(CSRC)/homography_core.inc $(CSRC)/ransac_batch.hpp $(CSRC)/fundamental_core.hpp $(CSRC)/pose_core.hpp $(CSRC)/pose_planar_core.hpp $(CSRC)/posegraph_core.hpp \
@@ -59,6 +59,15 @@ build/scan_rates: tools/scan_rates.hip
 build/single_call: tools/single_call.cpp include/cudaSift.h include/cudaImage.h cudasift_amd/libcudasift.so
 	@mkdir -p $(BUILD)
 	$(CXX) -O2 -std=c++17 -Iinclude -o $@ tools/single_call.cpp -Lcudasift_amd -lcudasift -lmisift -Wl,-rpath,'$$ORIGIN/../cudasift_amd'
+
+# one scenario of the drop-in API per process, dumped for tests/test_gpu_dropin_api.py (both flavours of the shim)
+build/dropin_check: tools/dropin_check.cpp include/cudaSift.h include/cudaImage.h include/misift.h cudasift_amd/libcudasift.so
+	@mkdir -p $(BUILD)
+	$(CXX) -O2 -std=c++17 -Wall -Iinclude -o $@ tools/dropin_check.cpp -Lcudasift_amd -lcudasift -lmisift -Wl,-rpath,'$$ORIGIN/../cudasift_amd'
+
+build/dropin_check_managed: tools/dropin_check.cpp include/cudaSift.h include/cudaImage.h include/misift.h cudasift_amd/libcudasift_managed.so
+	@mkdir -p $(BUILD)
+	$(CXX) -O2 -std=c++17 -Wall -DMANAGEDMEM -Iinclude -o $@ tools/dropin_check.cpp -Lcudasift_amd -lcudasift_managed -lmisift -Wl,-rpath,'$$ORIGIN/../cudasift_amd'
 
 # the MANAGEDMEM flavour of the drop-in API (cudaSift.h:27-32: SiftData holds ONE managed pointer, m_data)
 cudasift_amd/libcudasift_managed.so: $(CSRC)/shim_cudasift.cpp include/cudaSift.h include/cudaImage.h include/misift.h cudasift_amd/libmisift.so
