@@ -216,6 +216,8 @@ SIGNATURES = {
     "misift_test_epipolar_gather": (_i, [_vp, _vp, _i, _vp, _i, _f, _vp, _vp]),
     "misift_test_guided_gather": (_i, [_vp, _vp, _i, _vp, _i, _f, _vp, _vp, _vp]),
     "misift_test_frame_shares": (_i, [_i, _i, C.c_void_p, C.c_void_p]),
+    "misift_test_block_maps": (_i, [_vp, _ip, _ip, _vp, _i]),
+    "misift_test_strip_geom": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "misift_test_pyramid_layout": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "misift_test_describe_detections": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp]),
     "misift_test_detect_levels": (_i, [_vp, _i, _i, _i, _i, _f, _f, _i, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
@@ -462,6 +464,22 @@ class Context:
 
     def last_call_balanced(self):
         return lib().misift_ctx_last_call_balanced(self.h)
+
+    def block_maps(self, cap_rows):
+        """misift_test_block_maps: (orient_all's table, descr_all's table) of the last, completed call as int32 [T, 4]
+        arrays; raises when that call was not balanced or holds more than cap_rows rows."""
+        ta, tb = _i(0), _i(0)
+        rows = np.zeros((max(cap_rows, 1), 4), np.int32)
+        check(lib().misift_test_block_maps(self.h, C.byref(ta), C.byref(tb), rows.ctypes.data, cap_rows),
+              "misift_test_block_maps")
+        return rows[:ta.value].copy(), rows[ta.value:ta.value + tb.value].copy()
+
+    def strip_geom(self, w, h, pitch, nframes, out_w, out_rows, out_lanes):
+        """misift_test_strip_geom (no HIP call): (nstrips, seg_rows, nsegs) of a streaming launch of this context."""
+        out = np.zeros(3, np.int32)
+        check(lib().misift_test_strip_geom(self.h, w, h, pitch, nframes, out_w, out_rows, out_lanes, out.ctypes.data),
+              "misift_test_strip_geom")
+        return tuple(int(v) for v in out)
 
     def descr_big_fallbacks(self):
         return lib().misift_ctx_descr_big_fallbacks(self.h)

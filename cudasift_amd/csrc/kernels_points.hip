@@ -2232,6 +2232,30 @@ static int build_block_maps(misift_ctx *ctx, const PyramidInfo &P, int max_pts)
   return rc;
 }
 
+// Test-only: the block tables of the context's last call, read after it has completed (the copy runs on the context
+// stream and is waited for): the two table sizes, then the int4 rows themselves, orient_all's table first.
+extern "C" int misift_test_block_maps(misift_ctx *ctx, int *t_orient, int *t_descr, int *rows, int cap_rows)
+{
+  if (!ctx || !t_orient || !t_descr || !rows || cap_rows < 0) {
+    misift_set_error("misift_test_block_maps: invalid argument");
+    return MISIFT_EINVAL;
+  }
+  if (!ctx->cur_balanced || !ctx->d_block_map) {
+    misift_set_error("misift_test_block_maps: the last call was not balanced");
+    return MISIFT_EINVAL;
+  }
+  const long long n = (long long)ctx->map_t_orient + ctx->map_t_descr;
+  if (n > cap_rows || n > ctx->block_map_cap) {
+    misift_set_error("misift_test_block_maps: %lld rows but room for %d", n, cap_rows);
+    return MISIFT_EINVAL;
+  }
+  *t_orient = ctx->map_t_orient; *t_descr = ctx->map_t_descr;
+  HIP_TRY(hipSetDevice(ctx->device));
+  HIP_TRY(hipMemcpyAsync(rows, ctx->d_block_map, sizeof(int4) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return MISIFT_OK;
+}
+
 int launch_orient_all(misift_ctx *ctx, const float *scratch, const PyramidInfo &P, SiftPointD *pts, int max_pts)
 {
   (void)pts;

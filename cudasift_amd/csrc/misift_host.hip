@@ -1179,6 +1179,18 @@ extern "C" int misift_test_pyramid_layout(int width, int height, int num_octaves
   return MISIFT_OK;
 }
 
+// Test-only, host state only (no HIP call): the decomposition make_geom gives a streaming launch of this context — with
+// its CU count and its knobs as they stand — as out = {nstrips, seg_rows, nsegs}.
+extern "C" int misift_test_strip_geom(misift_ctx *ctx, int w, int h, int pitch, int nframes, int out_w, int out_rows,
+                                      int out_lanes, int *out)
+{
+  ARG_CHECK(ctx && out && w >= 1 && h >= 1 && pitch >= w && nframes >= 1);
+  ARG_CHECK(out_w >= 1 && out_rows >= 1 && out_lanes >= 1);
+  const StripGeom g = make_geom(ctx, w, h, pitch, nframes, 0, out_w, out_rows, out_lanes);
+  out[0] = g.nstrips; out[1] = g.seg_rows; out[2] = g.nsegs;
+  return MISIFT_OK;
+}
+
 // Images under 16 x 16, or whose coarsest pyramid level is under 8 px: the reference runs them (levels shrink to a few
 // pixels, every access clamped: cudaSiftH.cu:72-167) and so do we — on the dense per-level kernels, whose quad loads clamp
 // at any width >= 1.  The merged-octave kernels (tiled prefilter, cone chain, strips sized for whole wavefronts) are

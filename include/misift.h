@@ -2738,6 +2738,20 @@ int misift_test_pyramid_layout(int width, int height, int num_octaves, int scale
  * frame_shares_kernel evaluates on the device.  nblocks >= nframes. */
 int misift_test_frame_shares(int nblocks, int nframes, const unsigned *points, int *shares);
 
+/* Test-only: the block tables the last extraction call of this context built for its balanced per-keypoint launches.  Call
+ * it once that call has completed (it copies on the context stream and waits).  *t_orient / *t_descr: the workgroups of the
+ * orient_all and of the descr_all launch; rows: *t_orient + *t_descr rows of four ints, orient_all's table first — (frame,
+ * sub-block, sub-blocks of the frame, 0), frame after frame, then (-1, 0, 0, 0) for the spare workgroups.  cap_rows: the
+ * rows there is room for.  MISIFT_EINVAL when the last call was not balanced, or when cap_rows is too small. */
+int misift_test_block_maps(misift_ctx *ctx, int *t_orient, int *t_descr, int *rows, int cap_rows);
+
+/* Test-only, host state only (no HIP call): how a streaming launch of this context (prefilter, LowPass, ScaleDown) over
+ * nframes frames of w x h pixels (row stride pitch) that writes out_w x out_rows pixels, out_lanes quads of four columns
+ * per strip, is cut up under the context's CU count and knobs: out[0] = strips per row, out[1] = rows of a segment (a
+ * multiple of 8 between 8 and 128 for batches), out[2] = segments per frame. */
+int misift_test_strip_geom(misift_ctx *ctx, int w, int h, int pitch, int nframes, int out_w, int out_rows, int out_lanes,
+                           int *out);
+
 /* Test / tuning only: developer knobs of a context — launch shapes (segment lengths, workgroups per CU, dynamic-LDS padding)
  * and path selection (spatial binning, balanced per-keypoint launches, embedded ScaleDown chain, split pyramid tail, hipGraph
  * replay, LDS-window vs global-memory sampling, descr_big threshold ...).  Defaults are the measured optimum

@@ -117,3 +117,63 @@ def oracle_shapes(w, h, num_octaves, scale_up):
         out.append((w, h))
         w, h = w // 2, h // 2
     return out
+
+
+# ---- pyramid levels read back from a call's arena (test_gpu_pyramid_rowloop.py, test_gpu_many_frames.py)
+
+ARENA_POISON = 0x7FC0BAD1            # what the arena holds before the call
+
+
+def oracle_pyramid(pix, noct, blur):
+    """The levels noct ... 1 of the oracle's chain lowpass -> scaledown -> ... on one frame, finest first."""
+    from oracle import pyoracle
+    lvl = pyoracle.lowpass(np.asarray(pix).astype(np.float32), blur)
+    pyr = [lvl]
+    for _ in range(noct - 1):
+        lvl = pyoracle.scaledown(lvl)
+        pyr.append(lvl)
+    return pyr
+
+
+def pyramids(ctx, frames, noct, fused, blur, thresh, max_pts):
+    """One batch extraction of frames [B, h, w] (uint8 or float32) placed at pitch128; returns (pyramid levels per
+    frame, launches)."""
+    from cudasift_amd import capi
+    frames = np.asarray(frames)
+    u8 = frames.dtype == np.uint8
+    B, h, w = frames.shape
+    base, pitch, stride = geometry("pitch128", w, h)
+    host = place(frames, base, pitch, stride)
+    src = ctx.upload(host)
+    S = capi.scratch_floats(w, h, noct, False)
+    arena = ctx.upload(np.full(S * B, ARENA_POISON, np.uint32))
+    pts = ctx.zeros(576 * max_pts * B)
+    saved = ctx.get_options().fused
+    ctx.set_options(fused=fused)
+    ctx.profile_reset()
+    ctx.profile_enable(True)
+    try:
+        rc, _ = ctx.extract_batch_raw(src.ptr, u8, B, stride, w, h, pitch, arena.ptr, pts.ptr, num_octaves=noct,
+                                      init_blur=blur, thresh=thresh, max_pts=max_pts)
+        ctx.sync()
+        calls = {k: v["calls"] for k, v in ctx.profile_read().items()}
+    finally:
+        ctx.profile_enable(False)
+        ctx.set_options(fused=saved)
+    assert rc == 0, (rc, capi.lib().misift_last_error())
+    fl = ctx.download(arena, (S * B,), np.uint32).view(np.float32)
+    lay = capi.pyramid_layout(w, h, noct, False)
+    return [[fl[f * S + off:f * S + off + lh * lp].reshape(lh, lp)[:, :lw] for off, lw, lh, lp in lay] for f in range(B)], calls
+
+
+def check_pixels(pyr, want, what):
+    """pyr[i]: the levels read back for frame i, want[i]: the oracle's; bit for bit."""
+    assert len(pyr) == len(want)
+    for i, levels in enumerate(want):
+        assert len(pyr[i]) == len(levels)
+        for lev, (got, ref) in enumerate(zip(pyr[i], levels)):
+            assert got.shape == ref.shape, (what, i, lev, got.shape, ref.shape)
+            if not same_bytes(got, ref):
+                bad = np.argwhere(np.ascontiguousarray(got).view(np.uint32) != ref.view(np.uint32))
+                raise AssertionError("%s: frame %d pyramid level %d differs from the oracle at %d pixels, first (y, x) = %s, "
+                                     "last %s" % (what, i, lev, len(bad), bad[0].tolist(), bad[-1].tolist()))

@@ -26,21 +26,10 @@ import geometry_util as gu
 pytestmark = pytest.mark.gpu
 
 BLUR, THRESH, MAX_PTS = 1.0, 2.5, 4096
-POISON = 0x7FC0BAD1
 SHAPES = [(248, 23), (244, 64), (484, 137), (323, 70), (64, 18)]
 U8_SHAPES = SHAPES[:2]
 LONG = [(696, 150), (695, 151)]
 NFRAMES_LONG, DISTINCT_LONG = 13, 3
-
-
-def _capi():
-    from cudasift_amd import capi
-    return capi
-
-
-def _orc():
-    from oracle import pyoracle
-    return pyoracle
 
 
 def _noct(w, h):
@@ -53,42 +42,13 @@ def _noct(w, h):
 
 @functools.lru_cache(maxsize=None)
 def _oracle_pyramid(f, w, h, u8):
-    pix = gu.crop(f, w, h, u8).astype(np.float32)
-    lvl = _orc().lowpass(pix, BLUR)
-    pyr = [lvl]
-    for _ in range(_noct(w, h) - 1):
-        lvl = _orc().scaledown(lvl)
-        pyr.append(lvl)
-    return pyr
+    return gu.oracle_pyramid(gu.crop(f, w, h, u8), _noct(w, h), BLUR)
 
 
 def _pyramids(ctx, w, h, frame_ids, u8, fused):
     """One batch extraction of the frames; returns (pyramid levels per frame, launches)."""
-    capi = _capi()
-    B, noct = len(frame_ids), _noct(w, h)
     frames = np.stack([gu.crop(f, w, h, u8) for f in frame_ids])
-    base, pitch, stride = gu.geometry("pitch128", w, h)
-    host = gu.place(frames, base, pitch, stride)
-    src = ctx.upload(host)
-    S = capi.scratch_floats(w, h, noct, False)
-    arena = ctx.upload(np.full(S * B, POISON, np.uint32))
-    pts = ctx.zeros(576 * MAX_PTS * B)
-    saved = ctx.get_options().fused
-    ctx.set_options(fused=fused)
-    ctx.profile_reset()
-    ctx.profile_enable(True)
-    try:
-        rc, _ = ctx.extract_batch_raw(src.ptr, u8, B, stride, w, h, pitch, arena.ptr, pts.ptr, num_octaves=noct,
-                                      init_blur=BLUR, thresh=THRESH, max_pts=MAX_PTS)
-        ctx.sync()
-        calls = {k: v["calls"] for k, v in ctx.profile_read().items()}
-    finally:
-        ctx.profile_enable(False)
-        ctx.set_options(fused=saved)
-    assert rc == 0, (rc, capi.lib().misift_last_error())
-    fl = ctx.download(arena, (S * B,), np.uint32).view(np.float32)
-    lay = capi.pyramid_layout(w, h, noct, False)
-    return [[fl[f * S + off:f * S + off + lh * lp].reshape(lh, lp)[:, :lw] for off, lw, lh, lp in lay] for f in range(B)], calls
+    return gu.pyramids(ctx, frames, _noct(w, h), fused, BLUR, THRESH, MAX_PTS)
 
 
 def _check_launches(calls, noct, fused):
@@ -101,15 +61,7 @@ def _check_launches(calls, noct, fused):
 
 
 def _check_pixels(pyr, w, h, frame_ids, u8, what):
-    for i, f in enumerate(frame_ids):
-        want = _oracle_pyramid(f, w, h, u8)
-        assert len(pyr[i]) == len(want)
-        for lev, (got, ref) in enumerate(zip(pyr[i], want)):
-            assert got.shape == ref.shape, (what, i, lev, got.shape, ref.shape)
-            if not gu.same_bytes(got, ref):
-                bad = np.argwhere(np.ascontiguousarray(got).view(np.uint32) != ref.view(np.uint32))
-                raise AssertionError("%s: frame %d pyramid level %d differs from the oracle at %d pixels, first (y, x) = %s, "
-                                     "last %s" % (what, i, lev, len(bad), bad[0].tolist(), bad[-1].tolist()))
+    gu.check_pixels(pyr, [_oracle_pyramid(f, w, h, u8) for f in frame_ids], what)
 
 
 @pytest.mark.parametrize("fused", [1, 0])
